@@ -1,25 +1,28 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the hot path (BASELINE.json): Mrays/s (primary + secondary) of the wavefront path tracer on the
-Sponza-class scene, 1920x1080, 8 bounces, with the roofline of the dominant kernel and a CPU baseline (the oracle's scalar traversal)
-timed on the same box.
+Sponza-class scene, 1920x1080, 8 bounces; with --full also the roofline of the dominant kernel and a CPU baseline (the oracle's scalar
+traversal) timed on the same box.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one path-traced frame (1 spp) of the whole 1920x1080 image = one pass of the hot path over one batch: camera rays /
 cached primary hits -> bounce 0 (k_shade_first) -> every further bounce in ONE launch (k_path: traversal + shading) -> accumulate.
-The timed region (W untimed warm-up steps, then exactly K steps between barriers) is repeated R times from the same start frame;
-`value` is the median, the spread is printed beside it.
+The timed region (W untimed warm-up steps, then exactly K steps between barriers) runs once; with --full it is repeated R = 7 times
+from the same start frame (--repeats R sets it either way), `value` is the median and the spread is printed beside it.
+--dump-outputs DIR writes what the timed steps computed, the accumulated W x H x 3 fp32 radiance a caller reads back, as DIR/radiance.npy
+(a fixed, seeded sample of its pixels when the image is larger than 64 MB).  The inputs are generated from fixed seeds.
 
 N > 1: the frame is sharded by 32x32 pixel tile over the GPUs (zero communication while rendering) and the timed region ends with the
-single gather of the fp32 radiance on GPU 0 (RCCL over xGMI, inside the library).  Before anything is timed the assembled N-GPU image of two frames
-is compared bit for bit with the 1-GPU image (exit 3 on a mismatch; --no-selfcheck skips it).  Total work is fixed as N grows -> "scaling": "strong".
+single gather of the fp32 radiance on GPU 0 (RCCL over xGMI, inside the library).  With --full (or --selfcheck), before anything is timed,
+the assembled N-GPU image of two frames is compared bit for bit with the 1-GPU image (exit 3 on a mismatch; --no-selfcheck skips it).
+Total work is fixed as N grows -> "scaling": "strong".
 Two ways to get N GPUs, the same tile shard and gather either way:
   * started by a launcher (WORLD_SIZE = N): one process per GPU, adypt_comm_* (ncclCommInitRank);
   * started plainly as `python bench.py --gpus N`: ONE process drives the N devices through adypt_create_multi (ncclCommInitAll) — and
     exits non-zero if the box has fewer than N devices.  It never falls back to fewer GPUs than asked for.
 
-What the JSON line carries besides the contract's fields:
+What the JSON line carries besides the contract's fields (the blocks below are measured with --full only, and are null without it):
   roofline               the dominant kernel of the timed region (k_path<false>: 98 % of the GPU time): `bound` names what binds it ("valu_issue" on this
                          scene); achieved / frac / traffic are what the metric's name asks for and `frac_of` says so: fabric-side bytes the counters saw
                          per ray (committed rocprofv3 --pmc passes of this very command, hash-checked against the device sources) x this run's rays/s of
@@ -285,12 +288,44 @@ def cpu_baseline(inst, c):
             "sample_1_thread": "one %dx%d frame, %d rays, %.1f s" % (c.width, c.height // 4, s1.rays, t1)}
 
 
+def default_cache():
+    """.adypt_cache beside this file when the tree is writable; otherwise (a read-only checkout) a temporary directory removed at exit: the
+    scene is generated from its seed again, never taken from a cache another version of the generator may have written."""
+    d = os.path.join(ROOT, ".adypt_cache")
+    if os.access(d if os.path.isdir(d) else ROOT, os.W_OK | os.X_OK):
+        return d
+    import atexit, shutil, tempfile
+    d = tempfile.mkdtemp(prefix="adypt_bench_")
+    atexit.register(shutil.rmtree, d, True)
+    return d
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 22  # 48 MB of fp32 RGB
+
+
+def dump_outputs(out_dir, image):
+    """DIR/radiance.npy: the accumulated fp32 radiance of the timed steps, H x W x 3 — or, when that exceeds 64 MB, the pixels of a fixed
+    seeded sample (ascending pixel index), P x 3, so that two builds can be compared output for output."""
+    assert image is not None, "no image on this rank"
+    rgb = np.ascontiguousarray(image, dtype=np.float32)
+    if rgb.nbytes > DUMP_MAX_BYTES:
+        flat = rgb.reshape(-1, 3)
+        rgb = flat[np.sort(np.random.RandomState(SEED).choice(len(flat), DUMP_SAMPLE_PIXELS, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "radiance.npy"), rgb)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--repeats", type=int, default=7, help="the timed region (warm-up + K steps from the same start frame) is run this many times; value = median")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region (warm-up + K steps from the same start frame) is run this many times; value = median "
+                                                               "(default 1, with --full 7)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline figure: 7 repeats, roofline (census pass), primary_only, tmp_lifetime_1, "
+                                                        "sun_visibility, single_frame, roofline_hbm_resident, cpu_baseline, and the N > 1 self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the radiance the timed steps accumulated (fp32, W x H x 3) as DIR/radiance.npy")
     ap.add_argument("--scene", default="sponza")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -301,13 +336,20 @@ def main() -> None:
     ap.add_argument("--no-hbm-block", action="store_true", help="skip roofline_hbm_resident (the 10 M-triangle scene: ~25 s of setup)")
     ap.add_argument("--no-single-frame", action="store_true")
     ap.add_argument("--no-extra-blocks", action="store_true", help="skip primary_only and tmp_lifetime_1")
-    ap.add_argument("--cache", default=os.environ.get("ADYPT_CACHE", os.path.join(ROOT, ".adypt_cache")))
-    ap.add_argument("--selfcheck", action="store_true", help="(accepted for older command lines; the check below is the default for N > 1 and this flag changes nothing)")
-    ap.add_argument("--no-selfcheck", action="store_true", help="N > 1: skip the self-check — before anything is timed, 2 frames are rendered on the N GPUs and on GPU 0 alone and the two images "
-                    "compared bit for bit (exit 3 on a mismatch); it is also skipped, and says so in config.selfcheck, when GPU 0 has no room for a second context of the scene")
+    ap.add_argument("--cache", default=os.environ.get("ADYPT_CACHE"),
+                    help="where the generated scenes and their .bvh files go (default: .adypt_cache beside this file, or a temporary directory removed at exit "
+                         "when the tree is not writable)")
+    ap.add_argument("--selfcheck", action="store_true", help="N > 1: run the self-check below without --full")
+    ap.add_argument("--no-selfcheck", action="store_true", help="N > 1: skip the self-check (on with --full or --selfcheck) — before anything is timed, 2 frames are rendered on the N GPUs and "
+                    "on GPU 0 alone and the two images compared bit for bit (exit 3 on a mismatch); it is also skipped, and says so in config.selfcheck, when GPU 0 has no room for a "
+                    "second context of the scene")
     ap.add_argument("--rehearsal", action="store_true", help="NOT a measurement: enables the library's test hooks (adypt_enable_test_hooks) so that ADYPT_MULTI_SHARED_DEVICE / "
                                                              "ADYPT_COMM_TRANSPORT=host can stand in for N GPUs on a box with one")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
+    if args.cache is None:
+        args.cache = default_cache()
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0 or args.repeats < 1:
         raise SystemExit("bench.py: --gpus, --steps, --repeats must be >= 1 and --warmup >= 0")
 
@@ -437,7 +479,7 @@ def main() -> None:
 
     # ---- --selfcheck: the assembled N-GPU image against the 1-GPU image of the same frames, before anything is timed ------------
     selfcheck = None
-    if (multi or world > 1) and not args.no_selfcheck:  # (on by default: a scaling line must never describe a wrong image)
+    if (multi or world > 1) and (args.full or args.selfcheck) and not args.no_selfcheck:
         pt.Reset()
         pt.Trace(True, 2)
         img_n = gather()
@@ -534,8 +576,11 @@ def main() -> None:
             total_rays = int(st["rays"])
         image = pt.CommReadResult()  # untimed (collective): the image on the host for the checksum
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, image)
+
     single_gpu = world == 1 and not multi
-    extras = single_gpu and rank == 0
+    extras = args.full and single_gpu and rank == 0
     roofline = primary_only = life1 = single = hbm = cpu = sun_vis = None
     if extras:
         # ---- census (untimed): the same K frames again through the instrumented kernels -> exact algorithmic bytes ------

@@ -35,6 +35,48 @@ def test_gpus_must_match_a_launchers_world_size(tmp_path):
     assert r.returncode != 0 and b"WORLD_SIZE=2" in r.stderr
 
 
+def test_dump_of_an_image_over_64_mb_is_a_fixed_sample(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    img = np.random.RandomState(1).rand(2400, 2400, 3).astype(np.float32)  # 69 MB
+    bench.dump_outputs(str(tmp_path / "a"), img)
+    bench.dump_outputs(str(tmp_path / "b"), img)
+    a, b = np.load(tmp_path / "a" / "radiance.npy"), np.load(tmp_path / "b" / "radiance.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE_PIXELS, 3) and np.array_equal(a, b)
+    assert os.path.getsize(tmp_path / "a" / "radiance.npy") <= 64 << 20
+    assert np.isin(a[:, 0], img[..., 0]).all()  # pixels of the image, not something else
+    bench.dump_outputs(str(tmp_path / "c"), img[:1000])  # 29 MB: the whole image
+    assert np.array_equal(np.load(tmp_path / "c" / "radiance.npy"), img[:1000])
+
+
+def test_scene_cache_of_a_read_only_tree_is_a_fresh_temporary_directory(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.delenv("ADYPT_CACHE", raising=False)
+    monkeypatch.setattr(bench.os, "access", lambda path, mode: False)  # (root writes anywhere: the permission check itself is what is stood in for)
+    d = bench.default_cache()
+    assert os.path.isdir(d) and not os.listdir(d) and not d.startswith(ROOT + os.sep)
+    os.rmdir(d)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_only_its_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain run: one timed region of exactly --steps steps, nothing else measured; --full adds the repeats and the other blocks. Both dump the same
+    radiance, which is what the line's image_mean was taken from."""
+    plain = _bench(["--gpus", "1", "--steps", "4", "--warmup", "2", "--cache", str(tmp_path), "--dump-outputs", str(tmp_path / "plain")] + SMALL)
+    assert plain.returncode == 0, plain.stderr.decode()[-2000:]
+    full = _bench(["--gpus", "1", "--steps", "4", "--warmup", "2", "--cache", str(tmp_path), "--dump-outputs", str(tmp_path / "full"), "--full"] + SMALL)
+    assert full.returncode == 0, full.stderr.decode()[-2000:]
+    a, b = json.loads(plain.stdout.decode().strip().splitlines()[-1]), json.loads(full.stdout.decode().strip().splitlines()[-1])
+    assert a["steps"] == 4 and a["repeats"] == 1 and len(a["ms_per_step_all"]) == 1 and a["ms_per_step"] > 0
+    assert a["roofline"] is None and b["repeats"] == 7 and len(b["ms_per_step_all"]) == 7 and b["roofline"]["kernel_rays"] > 0
+    import numpy as np
+    ra, rb = np.load(tmp_path / "plain" / "radiance.npy"), np.load(tmp_path / "full" / "radiance.npy")
+    assert ra.dtype == np.float32 and ra.shape == (128, 192, 3)
+    assert np.array_equal(ra.view(np.uint32), rb.view(np.uint32)) and float(ra.mean()) == a["image_mean"]
+
+
 @pytest.mark.gpu
 def test_single_process_multi_device_path_on_one_card(tmp_path):
     """The one-process path of `bench.py --gpus 3` with the three tile shards on ONE device (ADYPT_MULTI_SHARED_DEVICE, a test hook: the line

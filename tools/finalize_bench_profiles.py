@@ -1,9 +1,9 @@
 """Developer tool: copy the bench lines and the shard / primary-rate measurements of a GPU run (gpurun_out/r6/final/, written by the command in
 this file's last lines) into profiles/r6_bench_json_*.json and profiles/r6_primary_rate_and_shard_emulation_1gpu.txt, and print the numbers the
 documents quote.    python tools/finalize_bench_profiles.py [dir]
-GPU side (tools/full_cycle.sh does all of it):  O=gpurun_out/r6/final; python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_command.json; python bench.py > $O/default.json;
-  ADYPT_FUSED_BOUNCES=0 python bench.py --gpus 1 --steps 20 --warmup 5 --no-hbm-block --no-cpu-baseline > $O/launch_per_bounce.json;
-  python bench.py --scene salle --width 4096 --height 4096 --steps 8 --warmup 2 --no-hbm-block --no-cpu-baseline > $O/salle.json;
+GPU side (tools/full_cycle.sh does all of it, $O = its output directory):  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver_command.json;
+  python bench.py --full > $O/default.json;  ADYPT_FUSED_BOUNCES=0 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-hbm-block --no-cpu-baseline > $O/launch_per_bounce.json;
+  python bench.py --full --scene salle --width 4096 --height 4096 --steps 8 --warmup 2 --no-hbm-block --no-cpu-baseline > $O/salle.json;
   for n in 1 2 4 8; do SWEEP_NRANKS=$n python tools/path_sweep.py 1 "-:" "-:ADYPT_FUSED_BOUNCES=0"; done > $O/shard.log;
   python tools/primary_rate.py 200 > $O/primary.log; python tools/shard_breakdown.py > $O/shard_breakdown.log"""
 import json, os, sys

@@ -21,11 +21,11 @@ echo "[cycle] counter profiles, 10 M-triangle scene"; bash tools/collect_profile
 echo "[cycle] counter profiles, primary rays only (config 2)"; bash tools/collect_profiles.sh primary > gpurun_out/collect_primary.log 2>&1 || exit 1
 fi
 echo "[cycle] bench lines"
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_command.json 2> $O/driver_command.err || exit 1
-python bench.py > $O/default.json 2> $O/default.err || exit 1
-ADYPT_FUSED_BOUNCES=0 python bench.py --gpus 1 --steps 20 --warmup 5 --no-hbm-block --no-cpu-baseline > $O/launch_per_bounce.json 2> /dev/null || exit 1
-ADYPT_RARE_MIN=0 python bench.py --gpus 1 --steps 20 --warmup 5 --no-hbm-block --no-cpu-baseline --no-single-frame --no-extra-blocks > $O/no_deferral.json 2> /dev/null || exit 1
-python bench.py --scene salle --width 4096 --height 4096 --steps 8 --warmup 2 --no-hbm-block --no-cpu-baseline > $O/salle.json 2> /dev/null || exit 1
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver_command.json 2> $O/driver_command.err || exit 1
+python bench.py --full > $O/default.json 2> $O/default.err || exit 1
+ADYPT_FUSED_BOUNCES=0 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-hbm-block --no-cpu-baseline > $O/launch_per_bounce.json 2> /dev/null || exit 1
+ADYPT_RARE_MIN=0 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-hbm-block --no-cpu-baseline --no-single-frame --no-extra-blocks > $O/no_deferral.json 2> /dev/null || exit 1
+python bench.py --full --scene salle --width 4096 --height 4096 --steps 8 --warmup 2 --no-hbm-block --no-cpu-baseline > $O/salle.json 2> /dev/null || exit 1
 for n in 1 2 4 8; do SWEEP_NRANKS=$n python tools/path_sweep.py 1 "-:" "-:ADYPT_FUSED_BOUNCES=0"; done > $O/shard.log 2> $O/shard.err || exit 1
 python tools/primary_rate.py 200 > $O/primary.log 2> /dev/null || exit 1
 python tools/shard_breakdown.py > $O/shard_breakdown.log 2> $O/shard_breakdown.err || exit 1

@@ -4,7 +4,7 @@
 set -u
 export TMPDIR=/tmp ADYPT_CACHE=${ADYPT_CACHE:-/tmp/adypt_cache}
 OUT=gpurun_out/pmc_ab; rm -rf $OUT; mkdir -p $OUT
-CMD="python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-block --no-single-frame --no-extra-blocks --repeats 1"
+CMD="python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-block --no-single-frame --no-extra-blocks --repeats 1"
 $CMD > /dev/null 2>&1
 for lib in "$@"; do
   if [ "$lib" != "default" ]; then export ADYPT_LIB=$PWD/adypt_amd/$lib; else unset ADYPT_LIB; fi

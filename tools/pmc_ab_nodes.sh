@@ -5,7 +5,7 @@
 set -u
 export TMPDIR=/tmp ADYPT_CACHE=${ADYPT_CACHE:-/tmp/adypt_cache}
 OUT=gpurun_out/pmc_ab_nodes; rm -rf $OUT; mkdir -p $OUT
-CMD="python3 bench.py --scene sanmiguel --steps 32 --warmup 16 --repeats 1 --no-cpu-baseline --no-single-frame --no-extra-blocks --no-hbm-block"
+CMD="python3 bench.py --full --scene sanmiguel --steps 32 --warmup 16 --repeats 1 --no-cpu-baseline --no-single-frame --no-extra-blocks --no-hbm-block"
 $CMD > /dev/null 2>&1
 for lib in default libadypt_node128.so; do
   if [ "$lib" != "default" ]; then export ADYPT_LIB=$PWD/adypt_amd/$lib; else unset ADYPT_LIB; fi

@@ -5,8 +5,8 @@
 set -u
 export TMPDIR=/tmp ADYPT_CACHE=${ADYPT_CACHE:-/tmp/adypt_cache}
 OUT=gpurun_out/pmc_vmem; rm -rf $OUT; mkdir -p $OUT
-CMD="python3 bench.py --steps 8 --warmup 4 --no-cpu-baseline --no-hbm-block --no-single-frame"
-python3 bench.py --steps 4 --warmup 0 --no-cpu-baseline --no-hbm-block --no-single-frame > /dev/null 2>&1
+CMD="python3 bench.py --full --steps 8 --warmup 4 --no-cpu-baseline --no-hbm-block --no-single-frame"
+python3 bench.py --full --steps 4 --warmup 0 --no-cpu-baseline --no-hbm-block --no-single-frame > /dev/null 2>&1
 i=0
 for grp in "TA_TA_BUSY_sum TA_FLAT_READ_WAVEFRONTS_sum GRBM_GUI_ACTIVE" \
            "TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum" \
