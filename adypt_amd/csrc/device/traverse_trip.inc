@@ -171,7 +171,7 @@
 				             "s_mov_b64 exec, %[ex]"
 				             : [t] "+v"(hit_t), [w] "+v"(win4), [ex] "=&s"(ex)
 				             : [v0] "v"(v0), [v1] "v"(v1), [v2] "v"(v2_), [b4] "v"(b4), [m1] "s"(m1), [m2] "s"(m2), [m3] "s"(m3)
-				             : "vcc");
+				             : "vcc", "scc");
 				won = win4 != b4 + 12u;
 			}
 			{

@@ -943,6 +943,85 @@ ORC_API void orc_brute_force(const void *triangles, int64_t n_tris, const float 
 	});
 }
 
+// The binary64 truth the tests hold traversal results against (tests/helpers.py: fp64_truth).  Unlike orc_brute_force it traces the
+// ray the shader traces: the direction components are first replaced as in traversal.glsl:16-23 (in binary32, like the shader),
+// then normalised in binary64.  Möller-Trumbore on the triangle's own vertices; barycentrics in the shader's convention (hit point
+// = p1 u + p2 v + p3 (1 - u - v)).  Per ray, rec = (t, u, v, edge) with edge = the hit point's distance to the nearest edge line of
+// the triangle, in scene units, negative when it lies outside.
+//   mode 0 (closest hit): the nearest hit with t in (tmin, 1e9); id -1 and t = 1e9 when there is none.
+//   mode 1 (any hit):     of all hits with t in (tmin, 1e9), the one farthest from being no hit at all: the largest
+//                         min(edge, t - tmin); id -1 when there is none.
+//   mode 2 (given):       the triangle tri_io[i] (in/out, -1 = none) against ray i, whatever t is; t = inf when the ray is parallel.
+// (t, u, v) of ray (o, d) against triangle t; false when the ray is parallel to it.  f64_edge: the distance of barycentrics (u, v) to
+// the nearest edge line, negative outside; -inf for a triangle of no area (never hit; its rounded det need not be 0).
+static inline bool f64_ray_tri(const Tri &t, const double o[3], const double d[3], double rec[4])
+{
+	double e1[3], e2[3], pv[3], tv[3], qv[3];
+	for(int c = 0; c < 3; ++c) { e1[c] = (double)t.p[0][c] - t.p[2][c]; e2[c] = (double)t.p[1][c] - t.p[2][c]; }
+	pv[0] = d[1] * e2[2] - d[2] * e2[1]; pv[1] = d[2] * e2[0] - d[0] * e2[2]; pv[2] = d[0] * e2[1] - d[1] * e2[0];
+	const double det = e1[0] * pv[0] + e1[1] * pv[1] + e1[2] * pv[2];
+	if(det == 0.0) { rec[0] = INFINITY; rec[1] = rec[2] = 0.0; rec[3] = -INFINITY; return false; }
+	const double id = 1.0 / det;
+	for(int c = 0; c < 3; ++c) tv[c] = o[c] - t.p[2][c];
+	qv[0] = tv[1] * e1[2] - tv[2] * e1[1]; qv[1] = tv[2] * e1[0] - tv[0] * e1[2]; qv[2] = tv[0] * e1[1] - tv[1] * e1[0];
+	rec[0] = (e2[0] * qv[0] + e2[1] * qv[1] + e2[2] * qv[2]) * id;
+	rec[1] = (tv[0] * pv[0] + tv[1] * pv[1] + tv[2] * pv[2]) * id;
+	rec[2] = (d[0] * qv[0] + d[1] * qv[1] + d[2] * qv[2]) * id;
+	return true;
+}
+static inline double f64_edge(const Tri &t, double u, double v)
+{
+	double e1[3], e2[3], x[3];
+	for(int c = 0; c < 3; ++c) { e1[c] = (double)t.p[0][c] - t.p[2][c]; e2[c] = (double)t.p[1][c] - t.p[2][c]; x[c] = (double)t.p[0][c] - t.p[1][c]; }
+	const double cr[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+	const double a2 = sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]); // twice the area
+	if(!(a2 > 0.0)) return -INFINITY;
+	// distance to the edge opposite vertex k = barycentric k x the triangle's height over that edge (2 area / edge length)
+	const double l0 = sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]), l1 = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+	const double l2 = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+	return fmin(fmin(u * a2 / l0, v * a2 / l1), (1.0 - u - v) * a2 / l2);
+}
+
+ORC_API void orc_brute_force_ex(const void *triangles, int64_t n_tris, const float *rays, int64_t n, int mode, int32_t *tri_io,
+								double *rec_out, int n_threads)
+{
+	const Tri *tris = (const Tri *)triangles;
+	parallel_rows((int)n, n_threads, [&](int i, int) {
+		const float *r = rays + (size_t)i * 8;
+		const float ooeps = u2f((127u - 64u) << 23); // traversal.glsl:16-19, in binary32
+		double o[3] = {r[0], r[1], r[2]}, d[3];
+		for(int c = 0; c < 3; ++c) d[c] = fabsf(r[4 + c]) > ooeps ? r[4 + c] : (r[4 + c] >= 0 ? ooeps : -ooeps);
+		const double len = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+		for(double &c : d) c /= len;
+		const double tmin = r[3];
+		double *out = rec_out + (size_t)i * 4;
+		if(mode == 2)
+		{
+			if(tri_io[i] < 0 || tri_io[i] >= n_tris) { out[0] = 1e9; out[1] = out[2] = out[3] = 0.0; tri_io[i] = -1; }
+			else if(f64_ray_tri(tris[tri_io[i]], o, d, out)) out[3] = f64_edge(tris[tri_io[i]], out[1], out[2]);
+			return;
+		}
+		double best[4] = {1e9, 0.0, 0.0, 0.0}, score = -INFINITY;
+		int32_t bi = -1;
+		for(int64_t k = 0; k < n_tris; ++k)
+		{
+			double rec[4];
+			if(!f64_ray_tri(tris[k], o, d, rec)) continue;
+			if(!(rec[0] > tmin && rec[0] < 1e9 && rec[1] >= 0.0 && rec[2] >= 0.0 && rec[1] + rec[2] <= 1.0)) continue;
+			if(mode == 0 && !(rec[0] < best[0])) continue;
+			rec[3] = f64_edge(tris[k], rec[1], rec[2]);
+			if(!(rec[3] >= 0.0)) continue;
+			if(mode == 0 ? rec[0] < best[0] : fmin(rec[3], rec[0] - tmin) > score)
+			{
+				memcpy(best, rec, sizeof(best)); bi = (int32_t)k;
+				score = fmin(rec[3], rec[0] - tmin);
+			}
+		}
+		tri_io[i] = bi;
+		memcpy(out, best, sizeof(best));
+	});
+}
+
 
 // ---- test hooks: the shading pieces on their own (tests/test_oracle_shading.py checks them against fp64 closed forms) --------
 // SampleHemisphere (pathtracer.glsl:52-64) for n (r.x, r.y) pairs in [0,1): the pairs are used as Sobol(b) directly (shift 0)

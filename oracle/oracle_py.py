@@ -293,6 +293,21 @@ def brute_force(triangles: np.ndarray, rays: np.ndarray, n_threads: Optional[int
     return ids, t
 
 
+def brute_force_ex(triangles: np.ndarray, rays: np.ndarray, mode: str = "closest", tri_ids: Optional[np.ndarray] = None,
+                   n_threads: Optional[int] = None):
+    """binary64 truth after the shader's ray setup (oracle.cpp: orc_brute_force_ex).  mode "closest" | "any" | "given" (the triangle
+    tri_ids[i] against ray i).  Returns (ids int32[n], rec float64[n, 4] = t, u, v, signed distance of the hit to the nearest edge)."""
+    tri = np.ascontiguousarray(triangles).view(TRI_DT).reshape(-1)
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    m = {"closest": 0, "any": 1, "given": 2}[mode]
+    ids = np.full(len(rays), -1, dtype=np.int32) if tri_ids is None else np.array(tri_ids, dtype=np.int32).reshape(-1).copy()
+    assert len(ids) == len(rays)
+    rec = np.empty((len(rays), 4), dtype=np.float64)
+    lib().orc_brute_force_ex(_p(tri), C.c_int64(len(tri)), _p(rays), C.c_int64(len(rays)), C.c_int(m), _p(ids), _p(rec),
+                             C.c_int(n_threads or default_threads()))
+    return ids, rec
+
+
 # ---------------------------------------------------------------------------------------------------
 # reference binary (build container only)
 # ---------------------------------------------------------------------------------------------------

@@ -41,5 +41,6 @@ def test_gpu_anyhit_bit_exact(name, w, h, scene_cache):
     assert g.tobytes() == o.tobytes()  # first accepted triangle, u/v/t bits, nodes, tris, visit hash, max depth
     g2 = inst.m_path_tracer.TraceRays(rays, with_stats=False, any_hit=True)
     assert np.array_equal(g2["tri_id"], o["tri_id"]) and np.array_equal(bits(g2["t"]), bits(o["t"]))
+    assert np.array_equal(bits(g2["u"]), bits(o["u"])) and np.array_equal(bits(g2["v"]), bits(o["v"]))
     # closest-hit queries are unaffected by the any-hit instantiation
     assert inst.m_path_tracer.TraceRays(rays, with_stats=True).tobytes() == O.trace(osc, rays, inst.m_config.c.stack_size).tobytes()

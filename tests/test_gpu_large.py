@@ -7,7 +7,8 @@ import pytest
 
 from adypt_amd import distributed as D
 from oracle import oracle_py as O
-from tests.helpers import bits, oracle_params_from_config, oracle_scene_from_instance, random_rays
+from tests.helpers import (TMIN_CLASSES, bits, check_against_fp64_truth, mixed_rays, oracle_params_from_config,
+                           oracle_scene_from_instance, random_rays, tmin_class)
 from tests.test_gpu_parity import make_instance
 
 pytestmark = pytest.mark.gpu
@@ -105,6 +106,25 @@ def test_sanmiguel_10M_random_rays_closest_and_any_bit_exact(sanmiguel):
     # the non-instrumented kernel (the one the bench times) returns the same hits
     g2 = pt.TraceRays(rays, with_stats=False)
     assert np.array_equal(g2["tri_id"], g["tri_id"]) and np.array_equal(bits(g2["t"]), bits(g["t"]))
+    assert np.array_equal(bits(g2["u"]), bits(g["u"])) and np.array_equal(bits(g2["v"]), bits(g["v"]))
+
+
+def test_sanmiguel_10M_mixed_tmin_rays_bit_exact_and_against_fp64(sanmiguel):
+    """tmin per ray varying inside every wave (tests/test_gpu_ray_tmin.py) on 10 M triangles; a subsample against the binary64 truth."""
+    osc = oracle_scene_from_instance(sanmiguel)
+    pt, stack = sanmiguel.m_path_tracer, sanmiguel.m_config.c.stack_size
+    rays = mixed_rays(sanmiguel.scene.triangles, 100000, 9, lambda r: O.trace(osc, r, stack))
+    g = pt.TraceRays(rays, with_stats=True)
+    assert g.tobytes() == O.trace(osc, rays, stack).tobytes()
+    ga = pt.TraceRays(rays, with_stats=True, any_hit=True)
+    assert ga.tobytes() == O.trace(osc, rays, stack, any_hit=True).tobytes()
+    g2 = pt.TraceRays(rays, with_stats=False)
+    for k in ("tri_id", "u", "v", "t"):
+        assert g2[k].tobytes() == g[k].tobytes(), k
+    sub = slice(0, 1000)  # 1000 rays x 10 M triangles in binary64
+    excused = check_against_fp64_truth(sanmiguel.scene.triangles, rays[sub], g2[sub])
+    boundary = np.isin(tmin_class(len(rays))[sub], [TMIN_CLASSES.index(k) for k in ("at_hit", "above_hit", "below_hit")])
+    assert excused[~boundary].mean() < 2e-3
 
 
 def test_sanmiguel_10M_1080p_8_bounce_frames_bit_exact(sanmiguel, sobol_matrices):

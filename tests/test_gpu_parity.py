@@ -94,6 +94,7 @@ def test_full_pipeline_bit_exact_vs_oracle(name, w, h, spp, scene_cache, sobol_m
     assert gh.tobytes() == oh.tobytes()  # ids, u/v/t bits, nodes visited, triangles tested, visit hash, max depth
     gh2 = pt.TraceRays(rays, with_stats=False)
     assert np.array_equal(gh2["tri_id"], oh["tri_id"]) and np.array_equal(bits(gh2["t"]), bits(oh["t"]))
+    assert np.array_equal(bits(gh2["u"]), bits(oh["u"])) and np.array_equal(bits(gh2["v"]), bits(oh["v"]))
     pt.SetInstrumentation(counters=True)
     pt.ResetStats()
     pt.Trace(True, spp)
