@@ -32,6 +32,7 @@
 // The kernel ends when the global queue is dry and every workgroup has finished the paths it holds.
 #pragma once
 #include "traverse.hpp"
+#include "path_limits.hpp"
 
 namespace adypt {
 
@@ -44,11 +45,8 @@ constexpr int kTabFields = 10;                   // path word | direction | thro
 constexpr int kRareCap = 96;                     // entries of the ring of deferred hits (glossy lobe / dielectric): what does not fit is shaded at once
 static_assert(kRareCap >= 64 && kRareCap % 8 == 0 && kRareCap + 64 <= kTraceThreads, "k_path: the deferred ring holds a round's worth (rare_min <= 64), keeps PathCtl 16-byte aligned behind it, and leaves the to-shade ring a full batch when every path waits");
 constexpr int kParkDwords = 8;                   // per-lane ray state a shading wave parks in LDS for the round (node and triangle groups | hit distance, node, slot | stack pointer)
-constexpr uint32_t kPwBounceShift = 26;          // path word in the table: bits 25..0 path id, 30..26 bounce index (kPwShadow: the ray is the path's sun-visibility query), 31 radiance parked
-constexpr uint32_t kPwShadow = 31;               // (so the query needs max_bounce <= 31: tracer.hip keeps the launch-per-bounce pipeline otherwise)
 constexpr uint32_t kRingMiss = 0x8000u;          // to-shade ring entry: the slot's ray hit nothing (its origin fields still hold the origin)
 constexpr uint32_t kPwIdMask = (1u << kPwBounceShift) - 1u;
-constexpr int64_t kPathMaxPaths = (int64_t)1 << kPwBounceShift; // batches with more paths keep the launch-per-bounce pipeline
 enum { T_PW = 0, T_DX, T_DY, T_DZ, T_CX, T_CY, T_CZ, T_OX, T_OY, T_OZ };
 
 struct PathCtl {                                 // workgroup control block in LDS (zeroed at start)

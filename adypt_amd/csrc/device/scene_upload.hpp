@@ -1,0 +1,131 @@
+// HBM residency of the scene: what adypt_create uploads, and in which layout the kernels read it.  A section of tracer.hip (included there
+// only, after context.hpp, upload() and k_expand_references): every function is one step of adypt_create and returns its error code.
+#pragma once
+#include "context.hpp"
+#include "../../../include/adypt_host.h"
+
+#include <cstring>
+
+namespace {
+
+constexpr long kRefTrianglesAutoMaxMB = 1l << 20; // ADYPT_REF_TRIANGLES_MAX_MB unset: the per-reference triangle copy is made whatever its size
+
+int upload_woop(adypt_ctx *c, const adypt_scene_desc *d)
+{
+	std::vector<float> woop;
+	const float *wp = d->woop;
+	if(!wp) { woop.resize((size_t)d->n_refs * 12); adypt_woop_matrices(d->triangles, d->tri_indices, d->n_refs, woop.data()); wp = woop.data(); }
+	return upload(c, &c->d_woop, wp, (size_t)d->n_refs * 12);
+}
+
+int upload_triangles(adypt_ctx *c, const adypt_scene_desc *d)
+{
+	// 100-byte Triangle -> 112-byte device record (shade.hpp): [p n matid pad] + [tc pad]
+	std::vector<float> packed((size_t)d->n_tris * kTriFloat4 * 4, 0.0f);
+	const uint8_t *src = (const uint8_t *)d->triangles;
+	for(int64_t i = 0; i < d->n_tris; ++i)
+	{
+		float *o = packed.data() + (size_t)i * kTriFloat4 * 4;
+		memcpy(o, src + i * 100, 72);            // positions + normals
+		memcpy(o + 18, src + i * 100 + 96, 4);   // material id
+		// class word (shade.hpp): 1 = a hit here runs the glossy lobe or the dielectric branch of Render() — what k_path's shading rounds defer to a
+		// round of their own (path.hpp).  A grouping hint only: never an input of the arithmetic.
+		int32_t matid; memcpy(&matid, src + i * 100 + 96, 4);
+		if(matid >= 0 && matid < d->n_mats)
+		{
+			const uint8_t *mat = (const uint8_t *)d->materials + (size_t)matid * 64;
+			int32_t dtex, illum; float shininess;
+			memcpy(&dtex, mat, 4); memcpy(&illum, mat + 48, 4); memcpy(&shininess, mat + 52, 4);
+			const uint32_t cls = material_class(illum, shininess, false), word = (cls == 3u || cls == 6u) ? 1u : 0u;
+			memcpy(o + 19, &word, 4);
+		}
+		memcpy(o + 20, src + i * 100 + 72, 24);  // texture coordinates
+	}
+	return upload(c, &c->d_triangles, packed.data(), packed.size());
+}
+
+int upload_shade_classes(adypt_ctx *c, const adypt_scene_desc *d)
+{
+	// k_shade's sort key per triangle (shade.hpp: material_class).  Off unless ADYPT_SHADE_BIN=1: measured +10 % k_shade time on both
+	// bench scenes (profiles/r3_ablations_k_trace.txt item 9) — the kernel waits on its gathers, not on divergent vector-ALU work
+	if(!c->tun.shade_bin) return ADYPT_OK;
+	std::vector<uint8_t> cls((size_t)std::max<int64_t>(d->n_tris, 1), (uint8_t)5);
+	const uint8_t *tri = (const uint8_t *)d->triangles, *mat = (const uint8_t *)d->materials;
+	for(int64_t i = 0; i < d->n_tris; ++i)
+	{
+		int32_t matid, dtex, illum; float shininess;
+		memcpy(&matid, tri + i * 100 + 96, 4);
+		if(matid < 0 || matid >= d->n_mats) continue;
+		memcpy(&dtex, mat + (size_t)matid * 64, 4); memcpy(&illum, mat + (size_t)matid * 64 + 48, 4); memcpy(&shininess, mat + (size_t)matid * 64 + 52, 4);
+		cls[(size_t)i] = (uint8_t)material_class(illum, shininess, d->n_textures != 0 && dtex >= 0 && dtex < d->n_textures);
+	}
+	return upload(c, &c->d_tri_class, cls.data(), cls.size());
+}
+
+int upload_textures_and_materials(adypt_ctx *c, const adypt_scene_desc *d)
+{
+	// textures: RGB8 -> RGBA8 words, every row w + 1 texels long — the extra one repeats the row's first texel, so the horizontal
+	// neighbour of the last column (GL_REPEAT) sits next to it and sample_texture fetches a row's two texels in one 8-byte load
+	std::vector<uint32_t> texels;
+	std::vector<int32_t> desc;
+	for(int t = 0; t < d->n_textures; ++t)
+	{
+		const adypt_texture &tx = d->textures[t];
+		if(tx.width <= 0 || tx.height <= 0 || !tx.rgb) return fail(c, ADYPT_E_INVALID, "adypt_create: bad texture " + std::to_string(t));
+		desc.push_back((int32_t)texels.size()); desc.push_back(tx.width); desc.push_back(tx.height); desc.push_back(0);
+		const size_t base = texels.size(), row = (size_t)tx.width + 1;
+		if(base + row * (size_t)tx.height >= ((size_t)1 << 31)) return fail(c, ADYPT_E_INVALID, "adypt_create: more than 2^31 texels");
+		texels.resize(base + row * (size_t)tx.height);
+		for(int y = 0; y < tx.height; ++y)
+		{
+			uint32_t *o = texels.data() + base + row * (size_t)y;
+			const uint8_t *in = tx.rgb + (size_t)y * tx.width * 3;
+			for(int x = 0; x < tx.width; ++x) o[x] = (uint32_t)in[x * 3] | (uint32_t)in[x * 3 + 1] << 8 | (uint32_t)in[x * 3 + 2] << 16 | 0xff000000u;
+			o[tx.width] = o[0];
+		}
+	}
+	TRY_CREATE(upload(c, &c->d_texels, texels.data(), texels.size()));
+	// materials: the reference's 64 bytes + the descriptor of the diffuse texture (one fetch less per textured hit)
+	std::vector<uint8_t> mats((size_t)std::max<int64_t>(d->n_mats, 1) * kMatFloat4 * 16, 0);
+	for(int64_t m = 0; m < d->n_mats; ++m)
+	{
+		uint8_t *o = mats.data() + (size_t)m * kMatFloat4 * 16;
+		memcpy(o, (const uint8_t *)d->materials + (size_t)m * 64, 64);
+		int32_t dtex; memcpy(&dtex, o, 4);
+		if(dtex >= 0 && dtex < d->n_textures) memcpy(o + 64, desc.data() + (size_t)dtex * 4, 16);
+	}
+	return upload(c, &c->d_materials, mats.data(), mats.size());
+}
+
+int make_reference_triangles(adypt_ctx *c)
+{
+	// k_path looks a hit's triangle up by reference index in a second copy of the records (path.hpp): made here, once, so that nothing is
+	// allocated while frames are traced.  Above the size threshold, or when the memory cannot be had, k_path applies the 4-byte
+	// uTriIndices remap (traversal.glsl:253-254) in its shading round instead — same image.
+	const size_t n16 = (size_t)c->n_refs * kTriFloat4, bytes = std::max<size_t>(n16, 1) * sizeof(float4);
+	const long max_mb = c->tun.ref_triangles_max_mb >= 0 ? c->tun.ref_triangles_max_mb : kRefTrianglesAutoMaxMB;
+	if(max_mb != 0 && (bytes >> 20) <= (size_t)max_mb) // (0 = never, whatever the size: the tests' way into the remap path with scenes of a few triangles)
+	{
+		if(hipMalloc(&c->d_ref_triangles, bytes) != hipSuccess) { c->d_ref_triangles = nullptr; (void)hipGetLastError(); }
+		else if(n16)
+		{
+			hipLaunchKernelGGL(k_expand_references, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream, (const float4 *)c->d_triangles, (const int32_t *)c->d_tri_indices, (size_t)c->n_refs, (float4 *)c->d_ref_triangles);
+			HIP_TRY(c, hipGetLastError());
+		}
+	}
+	return ADYPT_OK;
+}
+
+int upload_scene(adypt_ctx *c, const adypt_scene_desc *d)
+{
+	TRY_CREATE(upload(c, &c->d_nodes, (const uint8_t *)d->nodes, (size_t)d->n_nodes * 80));
+	TRY_CREATE(upload(c, &c->d_tri_indices, d->tri_indices, (size_t)d->n_refs));
+	TRY_CREATE(upload_woop(c, d));
+	TRY_CREATE(upload_triangles(c, d));
+	TRY_CREATE(upload_shade_classes(c, d));
+	TRY_CREATE(upload_textures_and_materials(c, d));
+	TRY_CREATE(upload(c, &c->d_local_blocks, c->local_blocks.data(), c->local_blocks.size()));
+	return make_reference_triangles(c);
+}
+
+}  // namespace

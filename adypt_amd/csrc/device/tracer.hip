@@ -1,19 +1,19 @@
 // C-ABI implementation of include/adypt_hip.h: context, HBM residency of the scene, launch sequencing of the
-// wavefront path tracer on one HIP stream.  Replaces OglScene + OglPathTracer (src/Tracer/*.cpp) of the reference.
+// wavefront path tracer.  Replaces OglScene + OglPathTracer (src/Tracer/*.cpp) of the reference.
 //
 // Per frame (= one OglPathTracer::Trace(true), OglPathTracer.cpp:34-61):
 //     memset counters -> k_gen_primary -> [ k_trace -> k_shade ] x maxBounce      (no host sync; queue sizes live in
 //     device memory, the traversal kernel is persistent, the shade grid covers the worst case)
-// A batch of several frames is cut into sub-batches ("pipes"), each the chain above on its OWN HIP stream over its own window
-// of the ray queues: while one pipe's traversal launch drains (its last, longest rays) or its shade kernel streams the queues
-// through HBM, the other pipe's traversal keeps the vector ALUs busy.  The reference has no barrier between bounces at all
-// (one dispatch runs the whole for(b < uMaxBounce) loop, shaders/pathtracer.glsl:107); results do not depend on any of this:
-// per-path work is independent of queue order and k_resolve applies the finished samples in frame order.
+// or, by default, k_shade_first -> k_path: the reference has no barrier between bounces at all (one dispatch runs the whole
+// for(b < uMaxBounce) loop, shaders/pathtracer.glsl:107).  Which of the two a pass takes: frame_plan.hpp; how it is enqueued: frame_schedule.hpp.
+// This is the ONE translation unit that instantiates the traversal / path kernels; its sections: context.hpp (struct adypt_ctx), the launch
+// helpers below, scene_upload.hpp, frame_schedule.hpp, the C ABI.
 // There is no CPU fallback anywhere in this file: without a HIP device adypt_create fails with ADYPT_E_NO_DEVICE.
 #include "traverse.hpp"
 #include "path.hpp"
 #include "ctx_access.hpp"
 #include "tunables.hpp"
+#include "context.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
 
@@ -29,23 +29,7 @@ using namespace adypt;
 
 namespace {
 
-constexpr int kMaxBounce = 32;
-constexpr int kMaxFramesInFlight = 128;
-constexpr int kMaxPipes = 4;           // sub-batches of a batch that run as concurrent chains (adypt_set_pipeline)
-constexpr long kRefTrianglesAutoMaxMB = 1l << 20; // ADYPT_REF_TRIANGLES_MAX_MB unset: the per-reference triangle copy is made whatever its size
-constexpr int kRollMaxPixels = 1 << 22;   // single frames in a row overlap on two streams up to this many local pixels (trace_rolling_frame)
-constexpr int kDefaultPipes = 1;       // measured: a second chain overlaps but recovers nothing (profiles/r3_ablations_k_trace.txt)
-
-struct FrameCounters {                 // one memset per frame; every counter on its own 128-byte line
-	uint32_t count[kMaxBounce + 1][kNumSegments * kCursorStride];   // live rays per queue segment after bounce b
-	uint32_t cursor[kMaxBounce + 1][kNumSegments * kCursorStride];  // traversal fetch cursors per segment
-	uint32_t sh_count[kMaxBounce + 1][kNumSegments * kCursorStride];  // sun-visibility queries per segment of bounce b
-	uint32_t sh_cursor[kMaxBounce + 1][kNumSegments * kCursorStride];
-};
-
 thread_local std::string g_create_error;
-
-struct EventPair { hipEvent_t a, b; int kind; };
 
 // Zeroes the counters of `n` pipes.  A kernel rather than hipMemsetAsync: while round 3's queue corruption was being hunted (the
 // append_slot fault) the memset was suspected of not being ordered against the kernels around it and replaced; that changed the timing, not the
@@ -86,143 +70,6 @@ __global__ void k_expand_references(const float4 *triangles, const int32_t *tri_
 	const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if(i < n_refs * kTriFloat4) out[i] = triangles[(size_t)tri_indices[i / kTriFloat4] * kTriFloat4 + i % kTriFloat4];
 }
-
-// One sub-batch chain of a pipelined batch.  Pipe 0 runs on the context's stream.
-struct Pipe {
-	hipStream_t stream = nullptr;
-	hipEvent_t done = nullptr;         // end of the pipe's chain; the context's stream waits for it before k_resolve
-	FrameCounters *counters = nullptr;
-	uint2 *spill = nullptr;            // traversal stack spill of this pipe's launches (two pipes' launches overlap)
-};
-
-// The part of the ray queues a pass works in: slots [offset, offset + kNumSegments * seg_cap)
-struct QueueWindow { size_t offset; uint32_t seg_cap; };
-
-}  // namespace
-
-struct adypt_ctx {
-	int device = 0;
-	hipStream_t stream = nullptr;
-	std::string error;
-	Tunables tun;              // the environment as adypt_create found it (tunables.hpp)
-
-	// scene (immutable after create)
-	void *d_nodes = nullptr, *d_woop = nullptr, *d_tri_indices = nullptr, *d_triangles = nullptr, *d_materials = nullptr, *d_tri_class = nullptr;
-	void *d_texels = nullptr, *d_local_blocks = nullptr;
-	void *d_ref_triangles = nullptr;          // k_path: the triangle records once per REFERENCE (uTriIndices order), made at adypt_create; null = k_path remaps through d_tri_indices
-	void *d_all_blocks = nullptr;             // adypt_assemble_radiance: block lists of all ranks
-	std::vector<int64_t> all_blocks_offset;
-	int64_t n_nodes = 0, n_refs = 0, n_tris = 0, n_mats = 0;
-	int n_tex = 0;
-	int width = 0, height = 0, blocks_x = 0, blocks_y = 0, rank = 0, nranks = 1;
-	int n_local_blocks = 0, n_local_px = 0;
-	int64_t n_image_px = 0; // pixels of the owned blocks that lie inside the image (= camera rays per frame)
-	std::vector<int32_t> local_blocks;
-
-	// per local pixel
-	float4 *d_accum = nullptr, *d_cache = nullptr;
-	float4 *d_cache_next = nullptr; // primary hits of the 2nd, 3rd, ... tmpLifetime group of a batch (shade.hpp PixelArgs)
-	int cache_next_slices = 0;
-	uint8_t *d_shift = nullptr;
-
-	// wavefront queues
-	int64_t capacity = 0;      // queue slots = kNumSegments * seg_cap
-	uint32_t seg_cap = 0;      // slots per XCD-affine segment (multiple of kShadeThreads)
-	size_t alloc_slots = 0;    // allocated slots (>= capacity: the windows of a pipelined batch round up separately)
-	int pipeline = kDefaultPipes; // sub-batches per batch (adypt_set_pipeline); 1 = one chain on the context's stream
-	Pipe pipes[kMaxPipes];
-	hipEvent_t fork_ev = nullptr;
-	// Single frames in a row (one frame per wavefront pass): frame k's k_path runs on pipe 1 + (k & 1) while frame k + 1's bounce 0 and k_path are already
-	// enqueued behind it on the other pipe, so the END of frame k's launch (its last paths' sequential bounces, ~0.5 ms of 2 ms) is covered by frame k + 1.
-	// roll_frame[s] = the frame whose k_path is in flight (or finished, not yet applied) in slot s, -1 = none
-	int roll_frame[2] = {-1, -1};
-	hipEvent_t roll_ready[2] = {nullptr, nullptr}; // bounce 0 of the slot's frame is done (context's stream) -> its k_path may start (pipe's stream)
-	int single_overlap = 1;        // ADYPT_SINGLE_OVERLAP=0: single frames strictly one after the other
-	float4 *q_o[2] = {nullptr, nullptr}, *q_d[2] = {nullptr, nullptr}, *q_col[2] = {nullptr, nullptr};
-	float4 *d_hit = nullptr;
-	float4 *sh_o = nullptr, *sh_d = nullptr, *sh_col = nullptr, *sh_hit = nullptr; // sun-visibility queue (allocated when enabled)
-	int sun_visibility = 0;
-	float sun_dir[3] = {0.6f, 1.0f, 0.2f}; // normalised at the time it is set
-	float4 *d_done = nullptr;  // [frames_in_flight][local pixels] finished samples of a multi-frame batch
-	float *d_sobol = nullptr;  // [kMaxFramesInFlight][64] Sobol points of the frames of the current batch
-	// pinned staging of the Sobol points, one slot per batch in flight on the stream: the upload is then a true
-	// asynchronous copy and enqueueing a batch never waits for the GPU (adypt_trace_spp_async)
-	static constexpr int kSobolSlots = 4;
-	float *h_sobol[kSobolSlots] = {nullptr, nullptr, nullptr, nullptr};
-	hipEvent_t sobol_done[kSobolSlots] = {nullptr, nullptr, nullptr, nullptr};
-	int sobol_next = 0;
-	int frames_in_flight = 1;
-	bool queues_ok = false;    // false after a failed (re)allocation of the queues: trace calls return ADYPT_E_STATE
-	uint32_t *d_display = nullptr; // adypt_read_display: one RGBA8 word per local pixel (allocated on first use)
-	RayStats *d_ray_stats = nullptr;
-	uint32_t *d_audit_seen = nullptr; // slot-claim audit: one bit per path id (instrumentation flag 4)
-	bool audit_selftest = false;      // ADYPT_AUDIT_SELFTEST=1: a double claim is planted before every check (tests that the detector detects)
-	size_t audit_words = 0;
-	FrameCounters *d_counters = nullptr; // [kMaxPipes]; pipe k uses d_counters + k
-	uint32_t *d_camera_cursors = nullptr; // k_trace_camera's own fetch cursors [kNumSegments][kCursorStride] + its counts of workgroups that have left [kNumSegments + 1][kCursorStride]: zero between launches (the kernel leaves them so)
-	DeviceStats *d_stats = nullptr;
-	uint32_t *h_overflow = nullptr; // pinned: DeviceStats::host_overflow
-	uint2 *d_spill = nullptr;  // [kMaxPipes][stack_size - lds_depth][total lanes]
-	size_t spill_bytes = 0;
-	size_t lds_bytes = 0;      // dynamic LDS of a traversal launch (>= the stack's: padded when it has to cap the workgroups per CU)
-
-	// launch geometry of the persistent traversal kernel
-	int num_cus = 0, trace_blocks = 0, lds_depth = 0, occupancy_api = 0;
-	size_t lds_per_cu = (size_t)160 * 1024; // hipDeviceProp_t::maxSharedMemoryPerMultiProcessor
-	uint32_t refill_min = kRefillMin, chunk = kChunk, bite = kBite, endgame = kEndgame;
-	// Camera rays come in queue order = 8x8 pixel tiles, so a wave's rays are coherent and finish together: a wave takes a WHOLE tile when all its
-	// lanes are idle (refill threshold 64, bites of 64 from the workgroup's reservation) and its lanes then walk the same nodes.  Measured (round 4,
-	// k_trace_camera, primary rays only, 1080p; profiles/r4_ablations_k_path.txt item 17): threshold / bite 8/8, 16/16, 32/32, 48/48, 64/64 ->
-	// 0.422 / 0.361 / 0.326 / 0.381 / 0.291 ms per launch; thresholds off the bite (28, 36 with bite 32) cost 8-38 %.  Secondary rays are
-	// incoherent and keep the low threshold.
-	uint32_t refill_min_primary = 64, bite_primary = 64;
-	int first_fused = 1;           // ADYPT_FIRST_FUSED=0: camera rays and bounce 0 of a batch as k_gen_primary + k_shade (rounds 1-2)
-	int fused_bounces = 1;         // bounces 1 .. maxBounce-1 of a batch in ONE launch (k_path, path.hpp); ADYPT_FUSED_BOUNCES=0: k_trace + k_shade per bounce
-	int single_fused = 1;          // a single frame runs as a batch of one through the same pipeline (ADYPT_SINGLE_FUSED=0: gen -> [trace -> shade] x maxBounce)
-	int path_blocks = 0, path_lds_depth = 0; // launch geometry of k_path
-	size_t path_lds = 0;
-	uint32_t shade_min = 64;       // deposited hits a wave of k_path waits for before it shades a batch
-	uint32_t defer_max = 24;       // ... and a round defers them only when it holds at most this many (tunables.hpp)
-	uint32_t rare_min = 48;        // deferred hits (glossy lobe / dielectric) a shading round of k_path waits for; 0 = nothing is deferred
-	int deal_chunks = 1;           // k_gen_primary deals 256-path chunks round-robin to the 8 queue segments (ADYPT_GEN_DEAL=0: one contiguous run each)
-
-	// state
-	adypt_pt_params params{}, pending{};
-	bool have_params = false, have_camera = false, pt_started = false;
-	float origin[3] = {0, 0, 0}, inv_proj[16] = {0}, inv_view[16] = {0};
-	int spp = 0;
-	// frames traced ahead (adypt_set_lookahead): the last wavefront batch covered frames [batch_spp, batch_spp + batch_frames);
-	// frames [batch_spp + ahead_pos, batch_spp + batch_frames) are finished samples parked in d_done, not yet in the image
-	int lookahead = 0, batch_spp = 0, batch_frames = 0, ahead_pos = 0, ahead_count = 0;
-	int cache_group = 0;        // which tmpLifetime group of that batch image 1 (d_cache) currently holds (0 = the batch's first)
-	uint32_t shift_seed_loaded = 0;
-	bool shift_loaded = false;
-	int instrumentation = 0;
-	int view_type = 0;          // uuViewer.uType of the image in d_accum: the viewer type of the last primary frame, 3 after path tracing
-
-	// RCCL communicator state of the native multi-GPU path (multi.hip owns and frees it)
-	void *comm = nullptr;
-	void (*comm_free)(void *) = nullptr;
-
-	std::vector<EventPair> events;
-	std::vector<EventPair> free_events;
-	double trace_ms = 0, shade_ms = 0, path_ms = 0;
-	uint32_t trace_launches = 0, path_launches = 0;
-	bool last_batch_fused = false;
-};
-
-namespace {
-
-#define HIP_TRY(ctx, expr)                                                                             \
-	do {                                                                                               \
-		hipError_t e_ = (expr);                                                                        \
-		if(e_ != hipSuccess) {                                                                         \
-			(ctx)->error = std::string(#expr) + ": " + hipGetErrorString(e_);                          \
-			return e_ == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP;                              \
-		}                                                                                              \
-	} while(0)
-
-int fail(adypt_ctx *c, int code, const std::string &msg) { c->error = msg; return code; }
 
 // block ownership of the pixel-tile shard: diagonal interleave so that every rank gets sky and floor alike
 inline int block_owner(int bx, int by, int nranks) { return (bx + by) % nranks; }
@@ -409,6 +256,9 @@ int launch_path(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, int pari
 	a.nodes = (const uint4 *)c->d_nodes; a.woop = (const float4 *)c->d_woop;
 	a.in_o = (const float *)c->q_o[parity] + 3 * win.offset; a.in_d = c->q_d[parity] + win.offset; a.in_col = (const float *)c->q_col[parity] + 3 * win.offset;
 	a.ray_stats = nullptr;
+	// the triangle records by REFERENCE index when the context holds that copy, else the uTriIndices remap inside k_path
+	SceneArgs sc_ref = sc;
+	if(c->d_ref_triangles) sc_ref.triangles = (const float4 *)c->d_ref_triangles;
 	a.tri_remap = c->d_ref_triangles ? nullptr : (const int32_t *)c->d_tri_indices;
 	a.count = count; a.cursor = cursor;
 	a.spill = pipe.spill; a.stats = c->d_stats;
@@ -417,7 +267,7 @@ int launch_path(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, int pari
 	a.refill_min = c->refill_min; a.shade_min = c->shade_min; a.rare_min = c->rare_min; a.defer_max = c->defer_max;
 	a.b0 = b0; a.tmin = c->params.ray_tmin;
 	hipEvent_t *stop = begin_timing(c, 2, pipe.stream);
-	const PathKernArgs K{a, f, sc, px, stats ? 1 : 0};
+	const PathKernArgs K{a, f, sc_ref, px, stats ? 1 : 0};
 	// (the SUN variant: rays that end at their first accepted triangle among the others — only where the queue can hold such queries)
 	if(f.sun_query)
 	{
@@ -729,154 +579,10 @@ int apply_params(adypt_ctx *c)
 	return load_shift(c);
 }
 
-// Running-mean step (pathtracer.glsl:224-226) of frames [first, first + count) of the batch last traced (its finished samples
-// are parked in d_done), in frame order; afterwards image 1 holds the primary hits of the tmpLifetime group of the last frame
-// applied — what frame-by-frame tracing leaves there (pathtracer.glsl:121-127).
-int resolve_batch_frames(adypt_ctx *c, const SceneArgs &sc, const PixelArgs &px, int first, int count)
-{
-	if(count <= 0) return ADYPT_OK;
-	FrameArgs f;
-	fill_frame(c, &f);
-	f.spp = c->batch_spp; f.n_frames = c->batch_frames;
-	hipEvent_t *stop = begin_timing(c, 1, c->stream);
-	hipLaunchKernelGGL(k_resolve, dim3((c->n_local_px + 255) / 256), dim3(256), 0, c->stream, f, sc, px, first, count);
-	end_timing(stop, c->stream);
-	HIP_TRY(c, hipGetLastError());
-	const int life = std::max(1, c->params.tmp_lifetime);
-	const int group = (c->batch_spp + first + count - 1) / life - c->batch_spp / life;
-	if(group > c->cache_group)
-	{
-		HIP_TRY(c, hipMemcpyAsync(c->d_cache, c->d_cache_next + (size_t)(group - 1) * (size_t)c->n_local_px, (size_t)c->n_local_px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-		c->cache_group = group;
-	}
-	return ADYPT_OK;
-}
-
-// frames traced ahead belong to the camera / parameters / queues they were traced with: anything that changes those drops
-// them (they are re-traced on demand — the sample sequence is a function of the frame index alone)
-// The same for single frames whose k_path was started ahead in a rolling slot: waited for (their kernels read queues, counters and the camera's
-// cache image) and forgotten.
-void drop_rolling(adypt_ctx *c)
-{
-	if(c->roll_frame[0] < 0 && c->roll_frame[1] < 0) return;
-	(void)hipSetDevice(c->device);
-	(void)hipStreamSynchronize(c->stream);
-	for(int s = 0; s < 2; ++s) { (void)hipStreamSynchronize(c->pipes[1 + s].stream); c->roll_frame[s] = -1; }
-}
-inline void drop_lookahead(adypt_ctx *c) { c->ahead_count = 0; c->ahead_pos = 0; drop_rolling(c); }
-
-
-// Sobol::Next (src/Util/Sobol.cpp:16-21) for frames [first, first + m): staged in a pinned slot, copied to `dst` on the context's stream
-int upload_sobol(adypt_ctx *c, int first, int m, float *dst)
-{
-	const int max_bounce = c->params.max_bounce;
-	const int slot = c->sobol_next;
-	c->sobol_next = (slot + 1) % adypt_ctx::kSobolSlots;
-	HIP_TRY(c, hipEventSynchronize(c->sobol_done[slot])); // the copy that last used this slot has left it
-	std::vector<float> pts((size_t)m * 2 * max_bounce);
-	int r = adypt_sobol_points(2 * max_bounce, first, m, pts.data());
-	if(r != ADYPT_OK) return fail(c, r, adypt_host_last_error());
-	float *padded = c->h_sobol[slot];
-	memset(padded, 0, (size_t)m * 64 * sizeof(float));
-	for(int k = 0; k < m; ++k) memcpy(&padded[(size_t)k * 64], &pts[(size_t)k * 2 * max_bounce], sizeof(float) * 2 * (size_t)max_bounce);
-	HIP_TRY(c, hipMemcpyAsync(dst, padded, (size_t)m * 64 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-	HIP_TRY(c, hipEventRecord(c->sobol_done[slot], c->stream));
-	return ADYPT_OK;
-}
-
-// the arguments of single frame `frame` in rolling slot `s`: a batch of one whose Sobol points, finished samples, queue window, counters and
-// stream are the slot's
-void roll_frame_args(const adypt_ctx *c, int frame, int s, FrameArgs *f)
-{
-	fill_frame(c, f);
-	f->spp = frame; f->n_frames = 1; f->frame_first = 0; f->frame_stride = 1; f->batched = 1;
-	f->sun_query = c->sun_visibility; // (a rolling frame always takes the one-launch pipeline: the escaped paths' queries travel with it)
-	f->sobol = c->d_sobol + (size_t)s * 64;
-	f->done = c->d_done + (size_t)s * (size_t)std::max(c->n_local_px, 64);
-}
-
-// Enqueues single frame `frame` in rolling slot `s`: [camera rays of a re-tracing frame ->] counters -> k_shade_first on the CONTEXT's stream (it
-// reads the primary-hit cache, which the next re-tracing frame rewrites on that stream), then k_path on the slot's own stream behind an event.
-// Nothing here waits for the slot's previous frame: the caller has enqueued that frame's running-mean step — which waits for its k_path — on the
-// context's stream before it calls this.
-int roll_launch(adypt_ctx *c, const SceneArgs &sc, const PixelArgs &px, bool stats, int frame, int s)
-{
-	const Pipe &pipe = c->pipes[1 + s];
-	const QueueWindow win = pipe_window(c, s, 2);
-	FrameArgs f;
-	roll_frame_args(c, frame, s, &f);
-	int r = upload_sobol(c, frame, 1, c->d_sobol + (size_t)s * 64);
-	if(r != ADYPT_OK) return r;
-	if(frame % std::max(1, c->params.tmp_lifetime) == 0)
-	{
-		// the frame re-traces its primary rays (pathtracer.glsl:113-127): one camera launch into the cache image, on the context's stream
-		FrameArgs fc = f;
-		fc.frame_stride = std::max(1, c->params.tmp_lifetime);
-		r = launch_trace_camera(c, c->pipes[0], full_window(c), fc, px, 1, stats);
-		if(r != ADYPT_OK) return r;
-	}
-	clear_counters(c, pipe.counters, 1, c->stream);
-	hipEvent_t *stop = begin_timing(c, 1, c->stream);
-	QueueArgs q = queue_args(c, win, 0, pipe.counters->count[0], pipe.counters->count[1], 1); // out = queue 1 = bounce 1's rays
-	audit_before(c, q, c->stream, 1 + s);
-	hipLaunchKernelGGL(k_shade_first, dim3((unsigned)(c->n_local_px / kShadeThreads)), dim3(kShadeThreads), 0, c->stream, f, sc, q, px, stats ? 1 : 0);
-	audit_after(c, q, c->stream, 1 + s);
-	end_timing(stop, c->stream);
-	HIP_TRY(c, hipGetLastError());
-	c->last_batch_fused = true;
-	if(c->params.max_bounce > 1 || c->sun_visibility) // (with one bounce the queue still holds the sun-visibility queries of the paths that escaped at once)
-	{
-		HIP_TRY(c, hipEventRecord(c->roll_ready[s], c->stream));
-		HIP_TRY(c, hipStreamWaitEvent(pipe.stream, c->roll_ready[s], 0));
-		SceneArgs sc_ref = sc;
-		if(c->d_ref_triangles) sc_ref.triangles = (const float4 *)c->d_ref_triangles;
-		r = launch_path(c, pipe, win, 1, pipe.counters->count[1], pipe.counters->cursor[1], f, sc_ref, px, 1, stats);
-		if(r != ADYPT_OK) return r;
-	}
-	HIP_TRY(c, hipEventRecord(pipe.done, pipe.stream));
-	c->roll_frame[s] = frame;
-	return ADYPT_OK;
-}
-
-// frame c->spp as a rolling single frame; `more` = the call wants the frame after it too
-int trace_rolling_frame(adypt_ctx *c, const SceneArgs &sc, const PixelArgs &px, bool stats, bool more)
-{
-	const int frame = c->spp, s = frame & 1;
-	// While frames come in order the slots hold nothing but `frame` (slot s: started ahead by the previous call) and `frame + 1` (slot s ^ 1); anything else
-	// is waited for and forgotten first.
-	if((c->roll_frame[s] >= 0 && c->roll_frame[s] != frame) || (c->roll_frame[s ^ 1] >= 0 && c->roll_frame[s ^ 1] != frame + 1)) drop_rolling(c);
-	if(c->roll_frame[s] != frame)
-	{
-		const int r = roll_launch(c, sc, px, stats, frame, s);
-		if(r != ADYPT_OK) { drop_rolling(c); return r; }
-	}
-	// The frame after it, when this call asks for it (or the caller switched look-ahead on and it belongs to the same tmpLifetime group, so that image 1
-	// stays what frame-by-frame tracing leaves there): enqueued NOW, behind frame `frame`'s k_path — it fills the compute units as that launch's workgroups
-	// end.  Its slot's previous frame (frame - 1) had its running-mean step enqueued by the previous call of this function.  Only while a frame is small
-	// enough for the end of its launch to matter: at 4096 x 4096 (99 M rays, 14 ms per frame) the next frame's bounce 0 running beside the current k_path
-	// costs the 3 % the launch's end is worth (6566 against 6777 Mrays/s, profiles/r5_ablations.txt 3).
-	const int life = std::max(1, c->params.tmp_lifetime);
-	const bool ahead = c->single_overlap && c->n_local_px <= kRollMaxPixels && (more || (c->lookahead && (frame + 1) % life != 0));
-	if(ahead && c->roll_frame[s ^ 1] != frame + 1)
-	{
-		const int r = roll_launch(c, sc, px, stats, frame + 1, s ^ 1);
-		if(r != ADYPT_OK) { drop_rolling(c); return r; }
-	}
-	// running mean of frame `frame` (pathtracer.glsl:224-226) once its k_path has ended
-	HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pipes[1 + s].done, 0));
-	FrameArgs f;
-	roll_frame_args(c, frame, s, &f);
-	hipEvent_t *stop = begin_timing(c, 1, c->stream);
-	hipLaunchKernelGGL(k_resolve, dim3((c->n_local_px + 255) / 256), dim3(256), 0, c->stream, f, sc, px, 0, 1);
-	end_timing(stop, c->stream);
-	HIP_TRY(c, hipGetLastError());
-	c->roll_frame[s] = -1;
-	c->batch_spp = frame; c->batch_frames = 1; c->cache_group = 0; c->ahead_pos = 1; c->ahead_count = 0;
-	c->spp += 1;
-	return ADYPT_OK;
-}
-
 }  // namespace
+
+#include "scene_upload.hpp"
+#include "frame_schedule.hpp"
 
 namespace adypt {
 
@@ -940,6 +646,117 @@ void ctx_set_error(adypt_ctx *c, const std::string &msg) { c->error = msg; }
 void **ctx_comm_slot(adypt_ctx *c, void (***free_fn)(void *)) { *free_fn = &c->comm_free; return &c->comm; }
 }  // namespace adypt
 
+namespace {
+
+// ---- the steps of adypt_create ----
+
+int create_streams(adypt_ctx *c)
+{
+	HIP_TRY(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+	c->pipes[0].stream = c->stream;
+	for(int k = 1; k < kMaxPipes; ++k) HIP_TRY(c, hipStreamCreateWithFlags(&c->pipes[k].stream, hipStreamNonBlocking));
+	for(int k = 0; k < kMaxPipes; ++k) HIP_TRY(c, hipEventCreateWithFlags(&c->pipes[k].done, hipEventDisableTiming));
+	HIP_TRY(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
+	for(int s = 0; s < 2; ++s) HIP_TRY(c, hipEventCreateWithFlags(&c->roll_ready[s], hipEventDisableTiming));
+	return ADYPT_OK;
+}
+
+void apply_tunables(adypt_ctx *c)
+{
+	c->tun = read_tunables();
+	c->pipeline = c->tun.pipeline;
+	const Tunables &t = c->tun;
+	if(t.refill_min > 0) c->refill_min = c->refill_min_primary = (uint32_t)t.refill_min;
+	if(t.refill_min_primary > 0) c->refill_min_primary = (uint32_t)t.refill_min_primary;
+	c->deal_chunks = t.gen_deal; c->first_fused = t.first_fused; c->fused_bounces = t.fused_bounces; c->single_fused = t.single_fused;
+	c->audit_selftest = t.audit_selftest; c->single_overlap = t.single_overlap;
+	if(t.shade_min > 0) c->shade_min = (uint32_t)t.shade_min;
+	if(t.rare_min >= 0) c->rare_min = (uint32_t)t.rare_min;
+	if(t.defer_max >= 0) c->defer_max = (uint32_t)t.defer_max;
+	if(t.chunk > 0) c->chunk = (uint32_t)t.chunk;
+	if(t.endgame >= 0) c->endgame = (uint32_t)t.endgame;
+	if(t.bite > 0) c->bite = c->bite_primary = (uint32_t)t.bite;
+	if(t.bite_primary > 0) c->bite_primary = (uint32_t)t.bite_primary;
+}
+
+// the sizes of the scene and the pixel-tile shard: which 32x32 blocks of the image are this context's
+void set_shard(adypt_ctx *c, const adypt_scene_desc *d)
+{
+	c->n_nodes = d->n_nodes; c->n_refs = d->n_refs; c->n_tris = d->n_tris; c->n_mats = d->n_mats; c->n_tex = d->n_textures;
+	c->width = d->width; c->height = d->height; c->rank = d->tile_rank; c->nranks = d->tile_nranks;
+	c->blocks_x = (c->width + kBlockDim - 1) / kBlockDim; c->blocks_y = (c->height + kBlockDim - 1) / kBlockDim;
+	c->local_blocks = owned_blocks(c->width, c->height, c->rank, c->nranks);
+	c->n_local_blocks = (int)c->local_blocks.size();
+	c->n_local_px = c->n_local_blocks * kBlockPixels;
+	c->n_image_px = 0;
+	for(int32_t blk : c->local_blocks)
+	{
+		const int bx = blk % c->blocks_x, by = blk / c->blocks_x;
+		c->n_image_px += (int64_t)std::min(kBlockDim, c->width - bx * kBlockDim) * (int64_t)std::min(kBlockDim, c->height - by * kBlockDim);
+	}
+}
+
+// per-pixel images, ray queues, Sobol staging, counters and statistics
+int alloc_frame_state(adypt_ctx *c)
+{
+	const size_t npx = (size_t)std::max(c->n_local_px, 64);
+	HIP_TRY(c, hipMalloc((void **)&c->d_accum, npx * sizeof(float4)));
+	HIP_TRY(c, hipMalloc((void **)&c->d_cache, npx * sizeof(float4)));
+	HIP_TRY(c, hipMalloc((void **)&c->d_shift, npx * 2));
+	HIP_TRY(c, hipMemset(c->d_accum, 0, npx * sizeof(float4)));
+	HIP_TRY(c, hipMemset(c->d_cache, 0xff, npx * sizeof(float4)));
+	HIP_TRY(c, hipMemset(c->d_shift, 0, npx * 2));
+	{
+		// frames in flight: enough consecutive frames per wavefront pass to keep ~64 Mi paths in flight (32 frames of a
+		// 1080p image, 128 frames = the maximum for the 260 k-pixel tile shard of an 8-GPU run): the drain of a persistent
+		// launch (its longest rays) is amortised over more work; ADYPT_FRAMES_IN_FLIGHT overrides
+		int fif = (int)std::min<size_t>(kMaxFramesInFlight, std::max<size_t>(1, ((size_t)64 << 20) / npx));
+		if(c->tun.frames_in_flight > 0) fif = std::min(kMaxFramesInFlight, c->tun.frames_in_flight);
+		TRY_CREATE(alloc_queues(c, fif));
+	}
+	HIP_TRY(c, hipMalloc((void **)&c->d_sobol, (size_t)kMaxFramesInFlight * 64 * sizeof(float)));
+	for(int i = 0; i < adypt_ctx::kSobolSlots; ++i) // allocated here, not lazily: nothing is allocated while frames are traced
+	{
+		HIP_TRY(c, hipHostMalloc((void **)&c->h_sobol[i], (size_t)kMaxFramesInFlight * 64 * sizeof(float), hipHostMallocDefault));
+		HIP_TRY(c, hipEventCreateWithFlags(&c->sobol_done[i], hipEventDisableTiming));
+	}
+	HIP_TRY(c, hipMalloc((void **)&c->d_counters, sizeof(FrameCounters) * kMaxPipes));
+	for(int k = 0; k < kMaxPipes; ++k) c->pipes[k].counters = c->d_counters + k;
+	HIP_TRY(c, hipMalloc((void **)&c->d_stats, sizeof(DeviceStats)));
+	HIP_TRY(c, hipMemset(c->d_counters, 0, sizeof(FrameCounters) * kMaxPipes));
+	HIP_TRY(c, hipMalloc((void **)&c->d_camera_cursors, sizeof(uint32_t) * (2 * kNumSegments + 1) * kCursorStride));
+	HIP_TRY(c, hipMemset(c->d_camera_cursors, 0, sizeof(uint32_t) * (2 * kNumSegments + 1) * kCursorStride));
+	HIP_TRY(c, hipMemset(c->d_stats, 0, sizeof(DeviceStats)));
+	HIP_TRY(c, hipHostMalloc((void **)&c->h_overflow, sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+	*c->h_overflow = 0u;
+	HIP_TRY(c, hipMemcpy(&c->d_stats->host_overflow, &c->h_overflow, sizeof(uint32_t *), hipMemcpyHostToDevice));
+	return ADYPT_OK;
+}
+
+int create_steps(adypt_ctx *c, const adypt_scene_desc *d)
+{
+	HIP_TRY(c, hipSetDevice(c->device));
+	TRY_CREATE(create_streams(c));
+	apply_tunables(c);
+	hipDeviceProp_t prop;
+	HIP_TRY(c, hipGetDeviceProperties(&prop, c->device));
+	c->num_cus = prop.multiProcessorCount;
+	if(prop.maxSharedMemoryPerMultiProcessor >= 64 * 1024) c->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
+	set_shard(c, d);
+	TRY_CREATE(upload_scene(c, d));
+	TRY_CREATE(alloc_frame_state(c));
+	// defaults of InstanceConfig::PT (src/InstanceConfig.hpp:21-27), seed 0
+	c->pending.stack_size = 12; c->pending.max_bounce = 5; c->pending.subpixel = 8; c->pending.tmp_lifetime = 16;
+	c->pending.ray_tmin = 0.0001f; c->pending.clamp = 4.0f; c->pending.sun[0] = c->pending.sun[1] = c->pending.sun[2] = 0.0f;
+	c->pending.shift_seed = 0;
+	TRY_CREATE(apply_params(c));
+	HIP_TRY(c, hipDeviceSynchronize()); // the uploads / memsets above ran on the legacy stream
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	return ADYPT_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int adypt_abi_version(void) { return ADYPT_ABI_VERSION; }
@@ -997,194 +814,9 @@ int adypt_create(adypt_ctx **out, const adypt_scene_desc *d)
 	if(d->device < 0 || d->device >= n_dev) { g_create_error = "adypt_create: device ordinal out of range"; return ADYPT_E_INVALID; }
 
 	adypt_ctx *c = new adypt_ctx();
-	auto bail = [&](int code) { g_create_error = c->error; adypt_destroy(c); return code; };
 	c->device = d->device;
-	int r;
-#define TRY_CREATE(expr) do { r = (expr); if(r != ADYPT_OK) return bail(r); } while(0)
-#define HIP_CREATE(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) { c->error = std::string(#expr) + ": " + hipGetErrorString(e_); return bail(e_ == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP); } } while(0)
-	HIP_CREATE(hipSetDevice(c->device));
-	HIP_CREATE(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-	c->pipes[0].stream = c->stream;
-	for(int k = 1; k < kMaxPipes; ++k) HIP_CREATE(hipStreamCreateWithFlags(&c->pipes[k].stream, hipStreamNonBlocking));
-	for(int k = 0; k < kMaxPipes; ++k) HIP_CREATE(hipEventCreateWithFlags(&c->pipes[k].done, hipEventDisableTiming));
-	HIP_CREATE(hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
-	for(int s = 0; s < 2; ++s) HIP_CREATE(hipEventCreateWithFlags(&c->roll_ready[s], hipEventDisableTiming));
-	c->tun = read_tunables();
-	c->pipeline = c->tun.pipeline;
-	hipDeviceProp_t prop;
-	HIP_CREATE(hipGetDeviceProperties(&prop, c->device));
-	c->num_cus = prop.multiProcessorCount;
-	if(prop.maxSharedMemoryPerMultiProcessor >= 64 * 1024) c->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
-	{
-		const Tunables &t = c->tun;
-		if(t.refill_min > 0) c->refill_min = c->refill_min_primary = (uint32_t)t.refill_min;
-		if(t.refill_min_primary > 0) c->refill_min_primary = (uint32_t)t.refill_min_primary;
-		c->deal_chunks = t.gen_deal; c->first_fused = t.first_fused; c->fused_bounces = t.fused_bounces; c->single_fused = t.single_fused;
-		c->audit_selftest = t.audit_selftest; c->single_overlap = t.single_overlap;
-		if(t.shade_min > 0) c->shade_min = (uint32_t)t.shade_min;
-		if(t.rare_min >= 0) c->rare_min = (uint32_t)t.rare_min;
-		if(t.defer_max >= 0) c->defer_max = (uint32_t)t.defer_max;
-		if(t.chunk > 0) c->chunk = (uint32_t)t.chunk;
-		if(t.endgame >= 0) c->endgame = (uint32_t)t.endgame;
-		if(t.bite > 0) c->bite = c->bite_primary = (uint32_t)t.bite;
-		if(t.bite_primary > 0) c->bite_primary = (uint32_t)t.bite_primary;
-	}
-
-	c->n_nodes = d->n_nodes; c->n_refs = d->n_refs; c->n_tris = d->n_tris; c->n_mats = d->n_mats; c->n_tex = d->n_textures;
-	c->width = d->width; c->height = d->height; c->rank = d->tile_rank; c->nranks = d->tile_nranks;
-	c->blocks_x = (c->width + kBlockDim - 1) / kBlockDim; c->blocks_y = (c->height + kBlockDim - 1) / kBlockDim;
-	c->local_blocks = owned_blocks(c->width, c->height, c->rank, c->nranks);
-	c->n_local_blocks = (int)c->local_blocks.size();
-	c->n_local_px = c->n_local_blocks * kBlockPixels;
-	c->n_image_px = 0;
-	for(int32_t blk : c->local_blocks)
-	{
-		const int bx = blk % c->blocks_x, by = blk / c->blocks_x;
-		c->n_image_px += (int64_t)std::min(kBlockDim, c->width - bx * kBlockDim) * (int64_t)std::min(kBlockDim, c->height - by * kBlockDim);
-	}
-
-	TRY_CREATE(upload(c, &c->d_nodes, (const uint8_t *)d->nodes, (size_t)d->n_nodes * 80));
-	TRY_CREATE(upload(c, &c->d_tri_indices, d->tri_indices, (size_t)d->n_refs));
-	{
-		std::vector<float> woop;
-		const float *wp = d->woop;
-		if(!wp) { woop.resize((size_t)d->n_refs * 12); adypt_woop_matrices(d->triangles, d->tri_indices, d->n_refs, woop.data()); wp = woop.data(); }
-		TRY_CREATE(upload(c, &c->d_woop, wp, (size_t)d->n_refs * 12));
-	}
-	{
-		// 100-byte Triangle -> 112-byte device record (shade.hpp): [p n matid pad] + [tc pad]
-		std::vector<float> packed((size_t)d->n_tris * kTriFloat4 * 4, 0.0f);
-		const uint8_t *src = (const uint8_t *)d->triangles;
-		for(int64_t i = 0; i < d->n_tris; ++i)
-		{
-			float *o = packed.data() + (size_t)i * kTriFloat4 * 4;
-			memcpy(o, src + i * 100, 72);            // positions + normals
-			memcpy(o + 18, src + i * 100 + 96, 4);   // material id
-			// class word (shade.hpp): 1 = a hit here runs the glossy lobe or the dielectric branch of Render() — what k_path's shading rounds defer to a
-			// round of their own (path.hpp).  A grouping hint only: never an input of the arithmetic.
-			int32_t matid; memcpy(&matid, src + i * 100 + 96, 4);
-			if(matid >= 0 && matid < d->n_mats)
-			{
-				const uint8_t *mat = (const uint8_t *)d->materials + (size_t)matid * 64;
-				int32_t dtex, illum; float shininess;
-				memcpy(&dtex, mat, 4); memcpy(&illum, mat + 48, 4); memcpy(&shininess, mat + 52, 4);
-				const uint32_t cls = material_class(illum, shininess, false), word = (cls == 3u || cls == 6u) ? 1u : 0u;
-				memcpy(o + 19, &word, 4);
-			}
-			memcpy(o + 20, src + i * 100 + 72, 24);  // texture coordinates
-		}
-		TRY_CREATE(upload(c, &c->d_triangles, packed.data(), packed.size()));
-	}
-	{
-		// k_shade's sort key per triangle (shade.hpp: material_class).  Off unless ADYPT_SHADE_BIN=1: measured +10 % k_shade time on both
-		// bench scenes (profiles/r3_ablations_k_trace.txt item 9) — the kernel waits on its gathers, not on divergent vector-ALU work
-		if(c->tun.shade_bin)
-		{
-			std::vector<uint8_t> cls((size_t)std::max<int64_t>(d->n_tris, 1), (uint8_t)5);
-			const uint8_t *tri = (const uint8_t *)d->triangles, *mat = (const uint8_t *)d->materials;
-			for(int64_t i = 0; i < d->n_tris; ++i)
-			{
-				int32_t matid, dtex, illum; float shininess;
-				memcpy(&matid, tri + i * 100 + 96, 4);
-				if(matid < 0 || matid >= d->n_mats) continue;
-				memcpy(&dtex, mat + (size_t)matid * 64, 4); memcpy(&illum, mat + (size_t)matid * 64 + 48, 4); memcpy(&shininess, mat + (size_t)matid * 64 + 52, 4);
-				cls[(size_t)i] = (uint8_t)material_class(illum, shininess, d->n_textures != 0 && dtex >= 0 && dtex < d->n_textures);
-			}
-			TRY_CREATE(upload(c, &c->d_tri_class, cls.data(), cls.size()));
-		}
-	}
-	{
-		// textures: RGB8 -> RGBA8 words, every row w + 1 texels long — the extra one repeats the row's first texel, so the horizontal
-		// neighbour of the last column (GL_REPEAT) sits next to it and sample_texture fetches a row's two texels in one 8-byte load
-		std::vector<uint32_t> texels;
-		std::vector<int32_t> desc;
-		for(int t = 0; t < d->n_textures; ++t)
-		{
-			const adypt_texture &tx = d->textures[t];
-			if(tx.width <= 0 || tx.height <= 0 || !tx.rgb) { c->error = "adypt_create: bad texture " + std::to_string(t); return bail(ADYPT_E_INVALID); }
-			desc.push_back((int32_t)texels.size()); desc.push_back(tx.width); desc.push_back(tx.height); desc.push_back(0);
-			const size_t base = texels.size(), row = (size_t)tx.width + 1;
-			if(base + row * (size_t)tx.height >= ((size_t)1 << 31)) { c->error = "adypt_create: more than 2^31 texels"; return bail(ADYPT_E_INVALID); }
-			texels.resize(base + row * (size_t)tx.height);
-			for(int y = 0; y < tx.height; ++y)
-			{
-				uint32_t *o = texels.data() + base + row * (size_t)y;
-				const uint8_t *in = tx.rgb + (size_t)y * tx.width * 3;
-				for(int x = 0; x < tx.width; ++x) o[x] = (uint32_t)in[x * 3] | (uint32_t)in[x * 3 + 1] << 8 | (uint32_t)in[x * 3 + 2] << 16 | 0xff000000u;
-				o[tx.width] = o[0];
-			}
-		}
-		TRY_CREATE(upload(c, &c->d_texels, texels.data(), texels.size()));
-		// materials: the reference's 64 bytes + the descriptor of the diffuse texture (one fetch less per textured hit)
-		std::vector<uint8_t> mats((size_t)std::max<int64_t>(d->n_mats, 1) * kMatFloat4 * 16, 0);
-		for(int64_t m = 0; m < d->n_mats; ++m)
-		{
-			uint8_t *o = mats.data() + (size_t)m * kMatFloat4 * 16;
-			memcpy(o, (const uint8_t *)d->materials + (size_t)m * 64, 64);
-			int32_t dtex; memcpy(&dtex, o, 4);
-			if(dtex >= 0 && dtex < d->n_textures) memcpy(o + 64, desc.data() + (size_t)dtex * 4, 16);
-		}
-		TRY_CREATE(upload(c, &c->d_materials, mats.data(), mats.size()));
-	}
-	TRY_CREATE(upload(c, &c->d_local_blocks, c->local_blocks.data(), c->local_blocks.size()));
-	{
-		// k_path looks a hit's triangle up by reference index in a second copy of the records (path.hpp): made here, once, so that nothing is
-		// allocated while frames are traced.  Above the size threshold, or when the memory cannot be had, k_path applies the 4-byte
-		// uTriIndices remap (traversal.glsl:253-254) in its shading round instead — same image.
-		const size_t n16 = (size_t)c->n_refs * kTriFloat4, bytes = std::max<size_t>(n16, 1) * sizeof(float4);
-		const long max_mb = c->tun.ref_triangles_max_mb >= 0 ? c->tun.ref_triangles_max_mb : kRefTrianglesAutoMaxMB;
-		if(max_mb != 0 && (bytes >> 20) <= (size_t)max_mb) // (0 = never, whatever the size: the tests' way into the remap path with scenes of a few triangles)
-		{
-			if(hipMalloc(&c->d_ref_triangles, bytes) != hipSuccess) { c->d_ref_triangles = nullptr; (void)hipGetLastError(); }
-			else if(n16)
-			{
-				hipLaunchKernelGGL(k_expand_references, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream, (const float4 *)c->d_triangles, (const int32_t *)c->d_tri_indices, (size_t)c->n_refs, (float4 *)c->d_ref_triangles);
-				HIP_CREATE(hipGetLastError());
-			}
-		}
-	}
-
-	const size_t npx = (size_t)std::max(c->n_local_px, 64);
-	HIP_CREATE(hipMalloc((void **)&c->d_accum, npx * sizeof(float4)));
-	HIP_CREATE(hipMalloc((void **)&c->d_cache, npx * sizeof(float4)));
-	HIP_CREATE(hipMalloc((void **)&c->d_shift, npx * 2));
-	HIP_CREATE(hipMemset(c->d_accum, 0, npx * sizeof(float4)));
-	HIP_CREATE(hipMemset(c->d_cache, 0xff, npx * sizeof(float4)));
-	HIP_CREATE(hipMemset(c->d_shift, 0, npx * 2));
-	{
-		// frames in flight: enough consecutive frames per wavefront pass to keep ~64 Mi paths in flight (32 frames of a
-		// 1080p image, 128 frames = the maximum for the 260 k-pixel tile shard of an 8-GPU run): the drain of a persistent
-		// launch (its longest rays) is amortised over more work; ADYPT_FRAMES_IN_FLIGHT overrides
-		int fif = (int)std::min<size_t>(kMaxFramesInFlight, std::max<size_t>(1, ((size_t)64 << 20) / npx));
-		if(c->tun.frames_in_flight > 0) fif = std::min(kMaxFramesInFlight, c->tun.frames_in_flight);
-		TRY_CREATE(alloc_queues(c, fif));
-	}
-	HIP_CREATE(hipMalloc((void **)&c->d_sobol, (size_t)kMaxFramesInFlight * 64 * sizeof(float)));
-	for(int i = 0; i < adypt_ctx::kSobolSlots; ++i) // allocated here, not lazily: nothing is allocated while frames are traced
-	{
-		HIP_CREATE(hipHostMalloc((void **)&c->h_sobol[i], (size_t)kMaxFramesInFlight * 64 * sizeof(float), hipHostMallocDefault));
-		HIP_CREATE(hipEventCreateWithFlags(&c->sobol_done[i], hipEventDisableTiming));
-	}
-	HIP_CREATE(hipMalloc((void **)&c->d_counters, sizeof(FrameCounters) * kMaxPipes));
-	for(int k = 0; k < kMaxPipes; ++k) c->pipes[k].counters = c->d_counters + k;
-	HIP_CREATE(hipMalloc((void **)&c->d_stats, sizeof(DeviceStats)));
-	HIP_CREATE(hipMemset(c->d_counters, 0, sizeof(FrameCounters) * kMaxPipes));
-	HIP_CREATE(hipMalloc((void **)&c->d_camera_cursors, sizeof(uint32_t) * (2 * kNumSegments + 1) * kCursorStride));
-	HIP_CREATE(hipMemset(c->d_camera_cursors, 0, sizeof(uint32_t) * (2 * kNumSegments + 1) * kCursorStride));
-	HIP_CREATE(hipMemset(c->d_stats, 0, sizeof(DeviceStats)));
-	HIP_CREATE(hipHostMalloc((void **)&c->h_overflow, sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-	*c->h_overflow = 0u;
-	HIP_CREATE(hipMemcpy(&c->d_stats->host_overflow, &c->h_overflow, sizeof(uint32_t *), hipMemcpyHostToDevice));
-
-	// defaults of InstanceConfig::PT (src/InstanceConfig.hpp:21-27), seed 0
-	c->pending.stack_size = 12; c->pending.max_bounce = 5; c->pending.subpixel = 8; c->pending.tmp_lifetime = 16;
-	c->pending.ray_tmin = 0.0001f; c->pending.clamp = 4.0f; c->pending.sun[0] = c->pending.sun[1] = c->pending.sun[2] = 0.0f;
-	c->pending.shift_seed = 0;
-	TRY_CREATE(apply_params(c));
-	HIP_CREATE(hipDeviceSynchronize()); // the uploads / memsets above ran on the legacy stream
-	HIP_CREATE(hipStreamSynchronize(c->stream));
-#undef TRY_CREATE
-#undef HIP_CREATE
+	const int r = create_steps(c, d);
+	if(r != ADYPT_OK) { g_create_error = c->error; adypt_destroy(c); return r; }
 	*out = c;
 	return ADYPT_OK;
 }
@@ -1396,198 +1028,19 @@ int adypt_trace_spp_async(adypt_ctx *c, int n_spp)
 		c->spp += n_spp;
 		return ADYPT_OK;
 	}
-	SceneArgs sc; PixelArgs px;
-	fill_scene(c, &sc); fill_pixels(c, &px);
-	const bool stats = (c->instrumentation & 2) != 0;
 	for(int remaining = n_spp; remaining > 0;)
 	{
-		if(c->ahead_count > 0)
+		int r, done;
+		if(c->ahead_count > 0) r = hand_out_parked(c, done = std::min(remaining, c->ahead_count));
+		else
 		{
-			// frames already traced ahead by an earlier call: only their running-mean step is left (frame order is kept)
-			const int k = std::min(remaining, c->ahead_count);
-			int r = resolve_batch_frames(c, sc, px, c->ahead_pos, k);
-			if(r != ADYPT_OK) return r;
-			c->ahead_pos += k; c->ahead_count -= k; c->spp += k; remaining -= k;
-			continue;
+			if(!c->pt_started && (r = start_path_tracing(c)) != ADYPT_OK) return r;
+			const PassPlan p = plan_pass(plan_input(c, remaining));
+			r = p.kind == PassPlan::Rolling ? trace_rolling_frame(c, p, remaining > 1) : enqueue_batch(c, p);
+			done = p.hand_out;
 		}
-		if(!c->pt_started)
-		{
-			// first path-traced frame (OglPathTracer.cpp:39-46): apply config, clear the result image, restart Sobol
-			int r = apply_params(c);
-			if(r != ADYPT_OK) return r;
-			HIP_TRY(c, hipMemsetAsync(c->d_accum, 0, (size_t)std::max(c->n_local_px, 64) * sizeof(float4), c->stream));
-			c->spp = 0;
-			c->pt_started = true;
-			c->view_type = 3; // kPTRadiance (OglPathTracer.cpp:38)
-		}
-		const int max_bounce = c->params.max_bounce, life = c->params.tmp_lifetime;
-		// Batch = up to frames_in_flight consecutive frames traced as ONE wavefront (frames are independent samples; the
-		// running mean is applied afterwards in frame order, so the result is bit-identical to frame-by-frame).  A batch
-		// may span several tmpLifetime groups: the frames that re-trace their primary rays (spp % tmpLifetime == 0) run
-		// first, as one primary-only pass, and park their hits in the cache image of their group.
-		// With look-ahead on, a call for fewer frames than fit in a pass (Instance::Update asks for ONE, src/Instance.cpp:44-57)
-		// still traces a full pass: frames are independent samples of a deterministic sequence, so the frames beyond the ones
-		// asked for are simply finished early and parked; later calls hand them out one running-mean step at a time.
-		const int m = c->lookahead ? c->frames_in_flight : std::min(remaining, c->frames_in_flight);
-		const int hand_out = std::min(remaining, m);
-		// One frame per pass through the one-launch pipeline: a rolling single frame (frame k + 1 is enqueued under the end of frame k's k_path)
-		// (the sun-visibility query rides in k_path as bounce index kPwShadow = 31: with 32 bounces configured the launch-per-bounce pipeline keeps it)
-		const bool sun_ok = !c->sun_visibility || max_bounce <= (int)kPwShadow;
-		if(m == 1 && c->single_fused && c->first_fused && c->fused_bounces && sun_ok && (int64_t)c->n_local_px <= kPathMaxPaths)
-		{
-			int r = trace_rolling_frame(c, sc, px, stats, remaining > 1);
-			if(r != ADYPT_OK) return r;
-			remaining -= 1;
-			continue;
-		}
-		drop_rolling(c); // (a batch works in the whole queues)
-		const int first_retrace = (life - c->spp % life) % life;                       // batch index of the first re-tracing frame
-		const int n_retrace = first_retrace < m ? (m - 1 - first_retrace) / life + 1 : 0;
-		const int n_groups = (c->spp + m - 1) / life - c->spp / life + 1;
-		if(m > 1 && n_groups > 1)
-		{
-			int r = ensure_cache_slices(c, n_groups - 1);
-			if(r != ADYPT_OK) return r;
-			fill_pixels(c, &px);
-		}
-		FrameArgs f;
-		fill_frame(c, &f);
-		{ int r = upload_sobol(c, c->spp, m, c->d_sobol); if(r != ADYPT_OK) return r; } // Sobol::Next (src/Util/Sobol.cpp:16-21) for the m frames of the batch
-		// A single frame (no look-ahead, or one frame in flight) runs as a batch of one — camera launch, k_shade_first, k_path, k_resolve: 4 launches
-		// instead of 1 + 2 x maxBounce — whenever a batch would take the one-launch pipeline (ADYPT_SINGLE_FUSED=0: the launch-per-bounce frame)
-		const bool as_batch = m > 1 || (c->single_fused && c->first_fused && c->fused_bounces && sun_ok && (int64_t)c->n_local_px <= kPathMaxPaths);
-		const int use_cache = (!as_batch && n_retrace) ? 0 : 1;
-		f.batched = as_batch ? 1 : 0;
-		if(as_batch && n_retrace)
-		{
-			// primary-only pass of the re-tracing frames: camera rays -> traversal -> cache image of each frame's group
-			// (on the context's stream, in the whole queue: every sub-batch below starts from these cache images)
-			const Pipe &pipe = c->pipes[0];
-			const QueueWindow win = full_window(c);
-			f.n_frames = n_retrace; f.frame_first = first_retrace; f.frame_stride = life;
-			int r = launch_trace_camera(c, pipe, win, f, px, 1, stats);
-			if(r != ADYPT_OK) return r;
-			f.frame_stride = 1;
-		}
-		// The main pass, cut into n_pipes sub-batches of consecutive frames; sub-batch k = the chain gen -> [trace -> shade] x
-		// maxBounce on pipe k's stream in window k of the queues.  Everything before this point (Sobol upload, primary-only
-		// pass, the previous batch's k_resolve) is ordered before every chain by the fork event, every chain before k_resolve.
-		const int n_pipes = m > 1 ? std::max(1, std::min(std::min(c->pipeline, kMaxPipes), m)) : 1;
-		// batches start every frame from a cached primary hit: camera rays and bounce 0 in one kernel (k_shade_first).  With the sun-visibility query on, only when
-		// k_path follows (it traces the queries k_shade_first emits for the paths that escape at once); else the launch-per-bounce pipeline and its query queue
-		const bool path_ok = n_pipes == 1 && c->fused_bounces && (int64_t)m * (int64_t)c->n_local_px <= kPathMaxPaths;
-		const bool fused_first = as_batch && use_cache && c->first_fused && (!c->sun_visibility || (path_ok && sun_ok));
-		f.sun_query = (c->sun_visibility && fused_first) ? 1 : 0;
-		if(c->sun_visibility && !f.sun_query) { int r = ensure_shadow_queue(c); if(r != ADYPT_OK) return r; }
-		// the counters of all pipes are contiguous: one clearing launch, on the context's stream, before the chains fork
-		clear_counters(c, c->d_counters, n_pipes, c->stream);
-		// a launch or HIP call that fails between the fork and the join must not leave the other chains running unjoined: what follows on the
-		// context's stream (or the caller's next call) only synchronises c->stream, and those chains would still be writing queues, done[] and
-		// counters.  Every early return from here to the join goes through abandon().
-		auto abandon = [&](int code) { for(int k = 1; k < kMaxPipes; ++k) (void)hipStreamSynchronize(c->pipes[k].stream); return code; };
-#define HIP_TRY_JOINED(expr)                                                                          \
-		do {                                                                                           \
-			hipError_t e_ = (expr);                                                                    \
-			if(e_ != hipSuccess) {                                                                     \
-				c->error = std::string(#expr) + ": " + hipGetErrorString(e_);                          \
-				return abandon(e_ == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP);                 \
-			}                                                                                          \
-		} while(0)
-		if(n_pipes > 1)
-		{
-			HIP_TRY_JOINED(hipEventRecord(c->fork_ev, c->stream));
-			for(int k = 1; k < n_pipes; ++k) HIP_TRY_JOINED(hipStreamWaitEvent(c->pipes[k].stream, c->fork_ev, 0));
-		}
-		struct Sub { QueueWindow win; FrameArgs f; int grid; };
-		Sub sub[kMaxPipes];
-		for(int k = 0, frame0 = 0; k < n_pipes; ++k)
-		{
-			const int frames_k = m / n_pipes + (k < m % n_pipes ? 1 : 0);
-			sub[k].win = pipe_window(c, k, n_pipes);
-			sub[k].f = f;
-			sub[k].f.n_frames = frames_k; sub[k].f.frame_first = frame0;
-			sub[k].grid = (int)(kNumSegments * (pass_seg_paths(c, sub[k].win, frames_k) / kShadeThreads)); // kNumSegments x chunks per segment
-			frame0 += frames_k;
-			const Pipe &pipe = c->pipes[k];
-			hipEvent_t *stop = begin_timing(c, 1, pipe.stream);
-			if(fused_first)
-			{
-				// camera rays + bounce 0 of every frame from the cached primary hits, the surface fetched once per pixel and tmpLifetime group
-				QueueArgs q = queue_args(c, sub[k].win, 0, pipe.counters->count[0], pipe.counters->count[1], frames_k); // out = queue 1 = bounce 1's rays
-				audit_before(c, q, pipe.stream, k);
-				hipLaunchKernelGGL(k_shade_first, dim3((unsigned)(c->n_local_px / kShadeThreads)), dim3(kShadeThreads), 0, pipe.stream, sub[k].f, sc, q, px, stats ? 1 : 0);
-				audit_after(c, q, pipe.stream, k);
-			}
-			else
-			{
-				QueueArgs q = queue_args(c, sub[k].win, 1, pipe.counters->count[0], pipe.counters->count[0], frames_k); // out = queue 0
-				audit_before(c, q, pipe.stream, k);
-				hipLaunchKernelGGL(k_gen_primary, dim3(sub[k].grid), dim3(kShadeThreads), 0, pipe.stream, sub[k].f, sc, q, px, use_cache, 1);
-				audit_after(c, q, pipe.stream, k);
-			}
-			end_timing(stop, pipe.stream);
-		}
-		// every bounce after the first in ONE launch (k_path): the reference's for(b < uMaxBounce) inside a single dispatch
-		const bool fused_bounces = fused_first && n_pipes == 1 && c->fused_bounces && (int64_t)m * (int64_t)c->n_local_px <= kPathMaxPaths;
-		c->last_batch_fused = fused_bounces;
-		if(fused_bounces && (max_bounce > 1 || f.sun_query))
-		{
-			const Pipe &pipe = c->pipes[0];
-			SceneArgs sc_ref = sc; // the triangle records by REFERENCE index when the context holds that copy, else the uTriIndices remap inside k_path
-			if(c->d_ref_triangles) sc_ref.triangles = (const float4 *)c->d_ref_triangles;
-			int r = launch_path(c, pipe, sub[0].win, 1, pipe.counters->count[1], pipe.counters->cursor[1], sub[0].f, sc_ref, px, 1, stats);
-			if(r != ADYPT_OK) return abandon(r);
-		}
-		for(int b = fused_first ? 1 : 0; b < max_bounce && !fused_bounces; ++b)
-		{
-			const int in = b & 1;
-			for(int k = 0; k < n_pipes; ++k) // bounce by bounce over the pipes: their launches reach the GPU interleaved
-			{
-				const Pipe &pipe = c->pipes[k];
-				FrameCounters *ctr = pipe.counters;
-				if(!(b == 0 && use_cache))
-				{
-					int r = launch_trace(c, pipe, sub[k].win, in, ctr->count[b], ctr->cursor[b], c->params.stack_size, stats, nullptr, false, false, true, b == 0); // (b == 0: camera rays from the queue, tile by tile)
-					if(r != ADYPT_OK) return abandon(r);
-				}
-				QueueArgs q = queue_args(c, sub[k].win, in, ctr->count[b], ctr->count[b + 1], sub[k].f.n_frames);
-				ShadowArgs sh;
-				sh.o = c->sh_o + sub[k].win.offset; sh.d = c->sh_d + sub[k].win.offset; sh.col = c->sh_col + sub[k].win.offset; sh.hit = c->sh_hit + sub[k].win.offset;
-				sh.count = ctr->sh_count[b];
-				memcpy(sh.dir, c->sun_dir, sizeof(sh.dir));
-				sh.enabled = c->sun_visibility;
-				hipEvent_t *stop = begin_timing(c, 1, pipe.stream);
-				audit_before(c, q, pipe.stream, k);
-				hipLaunchKernelGGL(k_shade, dim3(sub[k].grid), dim3(kShadeThreads), 0, pipe.stream, sub[k].f, sc, q, px, sh, b, (b == 0 && !use_cache) ? 1 : 0, stats ? 1 : 0);
-				audit_after(c, q, pipe.stream, k);
-				end_timing(stop, pipe.stream);
-				if(c->sun_visibility)
-				{
-					// the escaped paths of this bounce: any-hit query towards the sun, then sun term + accumulate (pathtracer.glsl:130-135)
-					int r = launch_trace(c, pipe, sub[k].win, 0, ctr->sh_count[b], ctr->sh_cursor[b], c->params.stack_size, stats, nullptr, true, true);
-					if(r != ADYPT_OK) return abandon(r);
-					stop = begin_timing(c, 1, pipe.stream);
-					hipLaunchKernelGGL(k_shadow_resolve, dim3(sub[k].grid), dim3(kShadeThreads), 0, pipe.stream, sub[k].f, q, px, sh);
-					end_timing(stop, pipe.stream);
-				}
-			}
-		}
-		for(int k = 1; k < n_pipes; ++k)
-		{
-			HIP_TRY_JOINED(hipEventRecord(c->pipes[k].done, c->pipes[k].stream));
-			HIP_TRY_JOINED(hipStreamWaitEvent(c->stream, c->pipes[k].done, 0));
-		}
-		HIP_TRY_JOINED(hipGetLastError());
-#undef HIP_TRY_JOINED
-		if(as_batch)
-		{
-			c->batch_spp = c->spp; c->batch_frames = m; c->cache_group = 0;
-			int r = resolve_batch_frames(c, sc, px, 0, hand_out);
-			if(r != ADYPT_OK) return r;
-			c->ahead_pos = hand_out; c->ahead_count = m - hand_out;
-		}
-		c->spp += hand_out;
-		remaining -= hand_out;
+		if(r != ADYPT_OK) return r;
+		remaining -= done;
 	}
 	return ADYPT_OK; // everything is enqueued on the context's stream; adypt_wait collects errors and kernel timings
 }

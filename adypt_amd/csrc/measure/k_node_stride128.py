@@ -15,7 +15,7 @@ def edit(name, pairs):
 
 
 edit("traverse.hpp", [("constexpr int kNodeUint4 = 5;", "constexpr int kNodeUint4 = 8;")])
-edit("tracer.hip", [("	TRY_CREATE(upload(c, &c->d_nodes, (const uint8_t *)d->nodes, (size_t)d->n_nodes * 80));",
+edit("scene_upload.hpp", [("	TRY_CREATE(upload(c, &c->d_nodes, (const uint8_t *)d->nodes, (size_t)d->n_nodes * 80));",
                      "	{ std::vector<uint8_t> padded((size_t)d->n_nodes * 128, 0);\n"
                      "	  for(int64_t i = 0; i < d->n_nodes; ++i) memcpy(&padded[(size_t)i * 128], (const uint8_t *)d->nodes + (size_t)i * 80, 80);\n"
                      "	  TRY_CREATE(upload(c, &c->d_nodes, padded.data(), padded.size())); }")])

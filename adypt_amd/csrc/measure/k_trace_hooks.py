@@ -55,6 +55,8 @@ edit("traverse_trip.inc", [
 ])
 edit("tracer.hip", [
     ('#include "traverse.hpp"\n', '#define ADYPT_TRACER_TU // (measure/k_trace_ablations.hpp defines its read-back entry points in this translation unit only)\n#include "traverse.hpp"\n'),
+])
+edit("scene_upload.hpp", [
     ("\tTRY_CREATE(upload(c, &c->d_nodes, (const uint8_t *)d->nodes, (size_t)d->n_nodes * 80));\n",
      "#ifdef ADYPT_MEASURE_FP16_NODES // 128-byte nodes with binary16 bounds\n\t{\n\t\tconst std::vector<uint8_t> wide = adypt::nodes_as_fp16((const uint8_t *)d->nodes, (size_t)d->n_nodes);\n"
      "\t\tTRY_CREATE(upload(c, &c->d_nodes, wide.data(), wide.size()));\n\t}\n#else\n\tTRY_CREATE(upload(c, &c->d_nodes, (const uint8_t *)d->nodes, (size_t)d->n_nodes * 80));\n#endif\n"),
