@@ -30,7 +30,7 @@ int resolve_batch_frames(adypt_ctx *c, int first, int count)
 	FrameArgs f;
 	fill_frame(c, &f);
 	f.spp = c->batch_spp; f.n_frames = c->batch_frames;
-	hipEvent_t *stop = begin_timing(c, 1, c->stream);
+	hipEvent_t stop = begin_timing(c, 1, c->stream);
 	hipLaunchKernelGGL(k_resolve, dim3((c->n_local_px + 255) / 256), dim3(256), 0, c->stream, f, a.sc, a.px, first, count);
 	end_timing(stop, c->stream);
 	HIP_TRY(c, hipGetLastError());
@@ -80,7 +80,7 @@ int upload_sobol(adypt_ctx *c, int first, int m, float *dst)
 void launch_shade_first(adypt_ctx *c, hipStream_t stream, int k, const QueueWindow &win, const FrameArgs &f, const PassArgs &a)
 {
 	FrameCounters *ctr = c->pipes[k].counters;
-	hipEvent_t *stop = begin_timing(c, 1, stream);
+	hipEvent_t stop = begin_timing(c, 1, stream);
 	QueueArgs q = queue_args(c, win, 0, ctr->count[0], ctr->count[1], f.n_frames);
 	audit_before(c, q, stream, k);
 	hipLaunchKernelGGL(k_shade_first, dim3((unsigned)(c->n_local_px / kShadeThreads)), dim3(kShadeThreads), 0, stream, f, a.sc, q, a.px, a.stats ? 1 : 0);
@@ -96,7 +96,7 @@ void roll_frame_args(const adypt_ctx *c, const PassPlan &p, int frame, int s, Fr
 	f->spp = frame; f->n_frames = 1; f->frame_first = 0; f->frame_stride = 1; f->batched = 1;
 	f->sun_query = p.sun_query; // (a rolling frame always takes the one-launch pipeline: the escaped paths' queries travel with it)
 	f->sobol = c->d_sobol + (size_t)s * 64;
-	f->done = c->d_done + (size_t)s * (size_t)std::max(c->n_local_px, 64);
+	f->done = c->q.done + (size_t)s * (size_t)std::max(c->n_local_px, 64);
 }
 
 // Enqueues single frame `frame` in rolling slot `s`: [camera rays of a re-tracing frame ->] counters -> k_shade_first on the CONTEXT's stream (it
@@ -164,7 +164,7 @@ int trace_rolling_frame(adypt_ctx *c, const PassPlan &p, bool more)
 	HIP_TRY(c, hipStreamWaitEvent(c->stream, c->pipes[1 + s].done, 0));
 	FrameArgs f;
 	roll_frame_args(c, p, frame, s, &f);
-	hipEvent_t *stop = begin_timing(c, 1, c->stream);
+	hipEvent_t stop = begin_timing(c, 1, c->stream);
 	hipLaunchKernelGGL(k_resolve, dim3((c->n_local_px + 255) / 256), dim3(256), 0, c->stream, f, a.sc, a.px, 0, 1);
 	end_timing(stop, c->stream);
 	HIP_TRY(c, hipGetLastError());
@@ -210,7 +210,7 @@ int launch_retrace_pass(adypt_ctx *c, const PassPlan &p, const PassArgs &a)
 void launch_gen_primary(adypt_ctx *c, const PassPlan &p, const PassArgs &a, const SubBatch &sb, int k)
 {
 	const Pipe &pipe = c->pipes[k];
-	hipEvent_t *stop = begin_timing(c, 1, pipe.stream);
+	hipEvent_t stop = begin_timing(c, 1, pipe.stream);
 	QueueArgs q = queue_args(c, sb.win, 1, pipe.counters->count[0], pipe.counters->count[0], sb.f.n_frames); // out = queue 0
 	audit_before(c, q, pipe.stream, k);
 	hipLaunchKernelGGL(k_gen_primary, dim3(sb.grid), dim3(kShadeThreads), 0, pipe.stream, sb.f, a.sc, q, a.px, p.use_cache ? 1 : 0, 1);
@@ -224,7 +224,7 @@ int launch_sun_queries(adypt_ctx *c, const PassArgs &a, const SubBatch &sb, int 
 	const Pipe &pipe = c->pipes[k];
 	int r = launch_trace(c, pipe, sb.win, 0, pipe.counters->sh_count[b], pipe.counters->sh_cursor[b], c->params.stack_size, a.stats, nullptr, true, true);
 	if(r != ADYPT_OK) return r;
-	hipEvent_t *stop = begin_timing(c, 1, pipe.stream);
+	hipEvent_t stop = begin_timing(c, 1, pipe.stream);
 	hipLaunchKernelGGL(k_shadow_resolve, dim3(sb.grid), dim3(kShadeThreads), 0, pipe.stream, sb.f, q, a.px, sh);
 	end_timing(stop, pipe.stream);
 	return ADYPT_OK;
@@ -243,11 +243,11 @@ int launch_bounce(adypt_ctx *c, const PassPlan &p, const PassArgs &a, const SubB
 	}
 	QueueArgs q = queue_args(c, sb.win, in, ctr->count[b], ctr->count[b + 1], sb.f.n_frames);
 	ShadowArgs sh;
-	sh.o = c->sh_o + sb.win.offset; sh.d = c->sh_d + sb.win.offset; sh.col = c->sh_col + sb.win.offset; sh.hit = c->sh_hit + sb.win.offset;
+	sh.o = c->q.sh_o + sb.win.offset; sh.d = c->q.sh_d + sb.win.offset; sh.col = c->q.sh_col + sb.win.offset; sh.hit = c->q.sh_hit + sb.win.offset;
 	sh.count = ctr->sh_count[b];
 	memcpy(sh.dir, c->sun_dir, sizeof(sh.dir));
 	sh.enabled = p.sun_queue ? 1 : 0;
-	hipEvent_t *stop = begin_timing(c, 1, pipe.stream);
+	hipEvent_t stop = begin_timing(c, 1, pipe.stream);
 	audit_before(c, q, pipe.stream, k);
 	hipLaunchKernelGGL(k_shade, dim3(sb.grid), dim3(kShadeThreads), 0, pipe.stream, sb.f, a.sc, q, a.px, sh, b, (b == 0 && !p.use_cache) ? 1 : 0, a.stats ? 1 : 0);
 	audit_after(c, q, pipe.stream, k);

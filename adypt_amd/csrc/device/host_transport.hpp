@@ -7,6 +7,7 @@
 // shared-memory mailbox; a receive is a host function on the caller's stream that waits for the mailbox, then a host-to-device copy —
 // asynchronous and stream-ordered like the real collectives.  Single node, no performance claim.
 #pragma once
+#include "resources.hpp"
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -33,7 +34,7 @@ struct Mailbox {                     // one per (sender, receiver) pair and per 
 	unsigned char data[1];
 };
 
-struct Staging { void *p = nullptr; size_t cap = 0; }; // pinned: a stream-ordered copy from / to pageable memory would be staged at CALL time
+using Staging = adypt::PinnedBuffer<unsigned char>; // pinned: a stream-ordered copy from / to pageable memory would be staged at CALL time
 struct HostComm {
 	std::string name;                // from the 128-byte id
 	int rank = 0, nranks = 1;
@@ -96,15 +97,12 @@ inline Mailbox *map_box(const std::string &name, size_t bytes, bool create, doub
 // (host functions must not call the HIP API: buffers are (re)allocated here, on the calling thread, and freed by CommDestroy)
 inline void *staging(Staging &b, size_t bytes, hipStream_t stream)
 {
-	if(b.cap < bytes || !b.p)
+	if(b.bytes() < bytes || !b)
 	{
 		(void)hipStreamSynchronize(stream);
-		if(b.p) (void)hipHostFree(b.p);
-		b.p = nullptr; b.cap = 0;
-		if(hipHostMalloc(&b.p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) return nullptr;
-		b.cap = bytes ? bytes : 1;
+		if(b.alloc(bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) return nullptr;
 	}
-	return b.p;
+	return b;
 }
 
 struct Op { HostComm *c; void *staging; size_t bytes; int peer; uint64_t seq; int kind; ncclRedOp_t red; ncclDataType_t dt; size_t count; }; // freed by its host function
@@ -199,9 +197,7 @@ inline ncclResult_t CommDestroy(ncclComm_t comm)
 {
 	HostComm *c = (HostComm *)comm;
 	(void)hipDeviceSynchronize();
-	for(int i = 0; i < 64; ++i) { if(c->send_buf[i].p) (void)hipHostFree(c->send_buf[i].p); if(c->recv_buf[i].p) (void)hipHostFree(c->recv_buf[i].p); }
-	if(c->all_buf.p) (void)hipHostFree(c->all_buf.p);
-	delete c;
+	delete c; // (with its staging buffers)
 	return ncclSuccess;
 }
 inline ncclResult_t Send(const void *buf, size_t count, ncclDataType_t dt, int peer, ncclComm_t comm, hipStream_t stream)

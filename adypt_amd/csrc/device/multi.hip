@@ -10,6 +10,7 @@
 // librccl is loaded with dlopen on first use: the library has no link-time dependency on it, and a process that already
 // holds an RCCL (e.g. the copy PyTorch ships) shares that one instead of bringing a second.
 #include "ctx_access.hpp"
+#include "resources.hpp"
 #include "host_transport.hpp"
 #include "tunables.hpp"
 #include "../../../include/adypt_hip.h"
@@ -121,9 +122,9 @@ struct Comm {
 	int device = 0, rank = 0, nranks = 1;
 	std::vector<int64_t> counts;     // float4 per rank
 	int64_t stride = 0;              // max of counts: rank r's tiles land at gathered + r * stride
-	float4 *gathered = nullptr;      // root only
-	float *rgb = nullptr;            // root only: assembled W*H*3
-	double *scratch = nullptr;       // all-reduce staging (device)
+	Buffer<float4> gathered;         // root only
+	Buffer<float> rgb;               // root only: assembled W*H*3
+	Buffer<double> scratch;          // all-reduce staging (device)
 	static constexpr int kScratch = 64;
 	const Tunables tun = read_tunables(); // read once, when the communicator is made (tunables.hpp)
 };
@@ -134,10 +135,7 @@ void free_comm(void *p)
 	if(!k) return;
 	(void)hipSetDevice(k->device);
 	if(k->comm && k->api) (void)k->api->CommDestroy(k->comm);
-	if(k->gathered) (void)hipFree(k->gathered);
-	if(k->rgb) (void)hipFree(k->rgb);
-	if(k->scratch) (void)hipFree(k->scratch);
-	delete k;
+	delete k; // (its buffers go with it: resources.hpp)
 }
 
 #define HIP_OK(ctx, expr)                                                                              \
@@ -210,11 +208,11 @@ int finish_comm(adypt_ctx *ctx, Comm *k)
 	k->counts = shard_counts(i.width, i.height, i.nranks);
 	k->stride = std::max<int64_t>(1024, *std::max_element(k->counts.begin(), k->counts.end()));
 	HIP_OK(ctx, hipSetDevice(i.device));
-	HIP_OK(ctx, hipMalloc((void **)&k->scratch, Comm::kScratch * sizeof(double)));
+	HIP_OK(ctx, k->scratch.alloc(Comm::kScratch * sizeof(double)));
 	if(i.rank == 0)
 	{
-		HIP_OK(ctx, hipMalloc((void **)&k->gathered, (size_t)k->stride * (size_t)i.nranks * sizeof(float4)));
-		HIP_OK(ctx, hipMalloc((void **)&k->rgb, (size_t)i.width * i.height * 3 * sizeof(float)));
+		HIP_OK(ctx, k->gathered.alloc((size_t)k->stride * (size_t)i.nranks * sizeof(float4)));
+		HIP_OK(ctx, k->rgb.alloc((size_t)i.width * i.height * 3 * sizeof(float)));
 	}
 	return ADYPT_OK;
 }

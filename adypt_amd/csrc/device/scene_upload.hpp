@@ -106,7 +106,7 @@ int make_reference_triangles(adypt_ctx *c)
 	const long max_mb = c->tun.ref_triangles_max_mb >= 0 ? c->tun.ref_triangles_max_mb : kRefTrianglesAutoMaxMB;
 	if(max_mb != 0 && (bytes >> 20) <= (size_t)max_mb) // (0 = never, whatever the size: the tests' way into the remap path with scenes of a few triangles)
 	{
-		if(hipMalloc(&c->d_ref_triangles, bytes) != hipSuccess) { c->d_ref_triangles = nullptr; (void)hipGetLastError(); }
+		if(c->d_ref_triangles.alloc(bytes) != hipSuccess) (void)hipGetLastError(); // (left empty)
 		else if(n16)
 		{
 			hipLaunchKernelGGL(k_expand_references, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream, (const float4 *)c->d_triangles, (const int32_t *)c->d_tri_indices, (size_t)c->n_refs, (float4 *)c->d_ref_triangles);

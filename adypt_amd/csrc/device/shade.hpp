@@ -27,12 +27,10 @@
 // one 128-byte line per gather (at 112 bytes a record straddled two lines three times out of four).
 #pragma once
 #include "canon_math.hpp"
+#include "tile_layout.hpp"
 
 namespace adypt {
 
-constexpr int kBlockShift = 5;                 // 32x32 pixel shard blocks
-constexpr int kBlockDim = 1 << kBlockShift;
-constexpr int kBlockPixels = kBlockDim * kBlockDim;
 constexpr int kTraceThreads = 256;             // 4 waves per workgroup
 constexpr int kLdsStackMax = 8;                // stack entries kept in LDS per lane; deeper entries spill to HBM
 constexpr int kNumSegments = 8;                // one ray-queue segment per XCD
@@ -159,11 +157,7 @@ struct PixelArgs {
 
 __device__ __forceinline__ bool local_pixel_xy(const FrameArgs &f, const int32_t *local_blocks, int L, int *x, int *y)
 {
-	const int blk = local_blocks[L >> 10];
-	const int in = L & 1023, wt = in >> 6, ln = in & 63;
-	const int bx = blk % f.blocks_x, by = blk / f.blocks_x;
-	*x = bx * kBlockDim + (wt & 3) * 8 + (ln & 7);
-	*y = by * kBlockDim + (wt >> 2) * 8 + (ln >> 3);
+	block_pixel_xy(local_blocks[L >> 10], L & 1023, f.blocks_x, x, y);
 	return *x < f.width && *y < f.height;
 }
 
@@ -817,10 +811,8 @@ __global__ void k_untile(const float4 *local, const int32_t *local_blocks, int n
 {
 	const int L = blockIdx.x * blockDim.x + threadIdx.x;
 	if(L >= n_local_px) return;
-	const int blk = local_blocks[L >> 10];
-	const int in = L & 1023, wt = in >> 6, ln = in & 63;
-	const int x = (blk % blocks_x) * kBlockDim + (wt & 3) * 8 + (ln & 7);
-	const int y = (blk / blocks_x) * kBlockDim + (wt >> 2) * 8 + (ln >> 3);
+	int x, y;
+	block_pixel_xy(local_blocks[L >> 10], L & 1023, blocks_x, &x, &y);
 	if(x >= width || y >= height) return;
 	const float4 v = local[L];
 	float *o = rgb + ((size_t)y * width + x) * 3;

@@ -9,11 +9,8 @@
 // This is the ONE translation unit that instantiates the traversal / path kernels; its sections: context.hpp (struct adypt_ctx), the launch
 // helpers below, scene_upload.hpp, frame_schedule.hpp, the C ABI.
 // There is no CPU fallback anywhere in this file: without a HIP device adypt_create fails with ADYPT_E_NO_DEVICE.
-#include "traverse.hpp"
-#include "path.hpp"
-#include "ctx_access.hpp"
-#include "tunables.hpp"
 #include "context.hpp"
+#include "ctx_access.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
 
@@ -23,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace adypt;
@@ -71,25 +69,29 @@ __global__ void k_expand_references(const float4 *triangles, const int32_t *tri_
 	if(i < n_refs * kTriFloat4) out[i] = triangles[(size_t)tri_indices[i / kTriFloat4] * kTriFloat4 + i % kTriFloat4];
 }
 
-// block ownership of the pixel-tile shard: diagonal interleave so that every rank gets sky and floor alike
-inline int block_owner(int bx, int by, int nranks) { return (bx + by) % nranks; }
-
-std::vector<int32_t> owned_blocks(int width, int height, int rank, int nranks)
+template <class D, class T> int upload(adypt_ctx *c, Buffer<D> *dst, const T *src, size_t n)
 {
-	const int nbx = (width + kBlockDim - 1) / kBlockDim, nby = (height + kBlockDim - 1) / kBlockDim;
-	std::vector<int32_t> v;
-	for(int by = 0; by < nby; ++by)
-		for(int bx = 0; bx < nbx; ++bx)
-			if(block_owner(bx, by, nranks) == rank) v.push_back(by * nbx + bx);
-	return v;
-}
-
-template <class T> int upload(adypt_ctx *c, void **dst, const T *src, size_t n)
-{
-	size_t bytes = std::max<size_t>(n * sizeof(T), 16);
-	HIP_TRY(c, hipMalloc(dst, bytes));
+	HIP_TRY(c, dst->alloc(std::max<size_t>(n * sizeof(T), 16)));
 	if(n) HIP_TRY(c, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
 	return ADYPT_OK;
+}
+
+// `b` holds at least `bytes` afterwards.  Before the old array goes, what may still be using it is drained: the context's stream, or the whole
+// device where launches of any pipe may.  What the array held is not kept.
+template <class T> int grow(adypt_ctx *c, Buffer<T> &b, size_t bytes, bool whole_device = false)
+{
+	if(b.bytes() >= bytes) return ADYPT_OK;
+	HIP_TRY(c, whole_device ? hipDeviceSynchronize() : hipStreamSynchronize(c->stream));
+	HIP_TRY(c, b.alloc(bytes));
+	return ADYPT_OK;
+}
+
+// The two run-time flags of a traversal launch as compile-time ones: f(std::bool_constant<a>, std::bool_constant<b>), so that a launcher
+// names its kernel template once.  (The order of the arms is the order in which the four instances are emitted.)
+template <class F> void with_flags(bool a, bool b, F &&f)
+{
+	if(b) { if(a) f(std::true_type{}, std::true_type{}); else f(std::false_type{}, std::true_type{}); }
+	else if(a) f(std::true_type{}, std::false_type{}); else f(std::false_type{}, std::false_type{});
 }
 
 // Structural validation of the BVH arrays: a corrupt child/triangle range would make the kernel read out of
@@ -136,32 +138,32 @@ bool validate_bvh(const adypt_scene_desc &d, std::string *why)
 	return true;
 }
 
-hipEvent_t *begin_timing(adypt_ctx *c, int kind, hipStream_t stream)
+hipEvent_t begin_timing(adypt_ctx *c, int kind, hipStream_t stream)
 {
 	if(!(c->instrumentation & 1)) return nullptr;
 	EventPair p;
-	if(!c->free_events.empty()) { p = c->free_events.back(); c->free_events.pop_back(); }
-	else { if(hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return nullptr; }
+	if(!c->free_events.empty()) { p = std::move(c->free_events.back()); c->free_events.pop_back(); }
+	else { if(hipEventCreate(p.a.out()) != hipSuccess || hipEventCreate(p.b.out()) != hipSuccess) return nullptr; }
 	p.kind = kind;
-	c->events.push_back(p);
+	c->events.push_back(std::move(p));
 	(void)hipEventRecord(c->events.back().a, stream);
-	return &c->events.back().b;
+	return c->events.back().b;
 }
-inline void end_timing(hipEvent_t *stop, hipStream_t stream) { if(stop) (void)hipEventRecord(*stop, stream); }
+inline void end_timing(hipEvent_t stop, hipStream_t stream) { if(stop) (void)hipEventRecord(stop, stream); }
 
 void harvest_events(adypt_ctx *c)
 {
 	std::vector<EventPair> pending; // launches of a frame started ahead on its own stream may still be running: their turn comes later
 	for(EventPair &p : c->events)
 	{
-		if(hipEventQuery(p.b) == hipErrorNotReady) { pending.push_back(p); continue; }
+		if(hipEventQuery(p.b) == hipErrorNotReady) { pending.push_back(std::move(p)); continue; }
 		float ms = 0.0f;
 		if(hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess)
 		{
 			if(p.kind == 0 || p.kind == 2) { c->trace_ms += ms; ++c->trace_launches; } else c->shade_ms += ms;
 			if(p.kind == 2) { c->path_ms += ms; ++c->path_launches; }
 		}
-		c->free_events.push_back(p);
+		c->free_events.push_back(std::move(p));
 	}
 	c->events.swap(pending);
 }
@@ -178,15 +180,7 @@ int ensure_spill(adypt_ctx *c, int stack_size)
 	const int extra = stack_size - c->lds_depth, extra_path = c->path_blocks ? stack_size - c->path_lds_depth : 0;
 	if(extra <= 0 && extra_path <= 0) return ADYPT_OK;
 	const size_t per_pipe = std::max((size_t)std::max(extra, 0) * (size_t)c->trace_blocks, (size_t)std::max(extra_path, 0) * (size_t)c->path_blocks) * kTraceThreads;
-	const size_t need = per_pipe * kMaxPipes * sizeof(uint2);
-	if(need > c->spill_bytes)
-	{
-		HIP_TRY(c, hipDeviceSynchronize()); // launches of any pipe may still be using the old array
-		if(c->d_spill) (void)hipFree(c->d_spill);
-		c->d_spill = nullptr; c->spill_bytes = 0;
-		HIP_TRY(c, hipMalloc((void **)&c->d_spill, need));
-		c->spill_bytes = need;
-	}
+	TRY_CREATE(grow(c, c->d_spill, per_pipe * kMaxPipes * sizeof(uint2), true)); // launches of any pipe may still be using the old array
 	for(int k = 0; k < kMaxPipes; ++k) c->pipes[k].spill = c->d_spill + (size_t)k * per_pipe;
 	return ADYPT_OK;
 }
@@ -254,7 +248,7 @@ int launch_path(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, int pari
 {
 	PathArgs a;
 	a.nodes = (const uint4 *)c->d_nodes; a.woop = (const float4 *)c->d_woop;
-	a.in_o = (const float *)c->q_o[parity] + 3 * win.offset; a.in_d = c->q_d[parity] + win.offset; a.in_col = (const float *)c->q_col[parity] + 3 * win.offset;
+	a.in_o = (const float *)c->q.o[parity].get() + 3 * win.offset; a.in_d = c->q.d[parity] + win.offset; a.in_col = (const float *)c->q.col[parity].get() + 3 * win.offset;
 	a.ray_stats = nullptr;
 	// the triangle records by REFERENCE index when the context holds that copy, else the uTriIndices remap inside k_path
 	SceneArgs sc_ref = sc;
@@ -266,16 +260,12 @@ int launch_path(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, int pari
 	a.stack_size = c->params.stack_size; a.lds_depth = c->path_lds_depth;
 	a.refill_min = c->refill_min; a.shade_min = c->shade_min; a.rare_min = c->rare_min; a.defer_max = c->defer_max;
 	a.b0 = b0; a.tmin = c->params.ray_tmin;
-	hipEvent_t *stop = begin_timing(c, 2, pipe.stream);
+	hipEvent_t stop = begin_timing(c, 2, pipe.stream);
 	const PathKernArgs K{a, f, sc_ref, px, stats ? 1 : 0};
 	// (the SUN variant: rays that end at their first accepted triangle among the others — only where the queue can hold such queries)
-	if(f.sun_query)
-	{
-		if(stats) hipLaunchKernelGGL((k_path<true, true>), dim3(c->path_blocks), dim3(kTraceThreads), c->path_lds, pipe.stream, K);
-		else hipLaunchKernelGGL((k_path<false, true>), dim3(c->path_blocks), dim3(kTraceThreads), c->path_lds, pipe.stream, K);
-	}
-	else if(stats) hipLaunchKernelGGL((k_path<true, false>), dim3(c->path_blocks), dim3(kTraceThreads), c->path_lds, pipe.stream, K);
-	else hipLaunchKernelGGL((k_path<false, false>), dim3(c->path_blocks), dim3(kTraceThreads), c->path_lds, pipe.stream, K);
+	with_flags(stats, f.sun_query != 0, [&](auto S, auto Sun) {
+		hipLaunchKernelGGL((k_path<decltype(S)::value, decltype(Sun)::value>), dim3(c->path_blocks), dim3(kTraceThreads), c->path_lds, pipe.stream, K);
+	});
 	end_timing(stop, pipe.stream);
 	HIP_TRY(c, hipGetLastError());
 	return ADYPT_OK;
@@ -293,14 +283,14 @@ int launch_trace(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, int par
 	a.packed = packed ? 1u : 0u; a.tmin = c->params.ray_tmin;
 	if(packed)
 	{
-		a.ray_o = (const float4 *)((const float *)c->q_o[parity] + 3 * win.offset);
-		a.hit = (float4 *)((float *)c->d_hit + 3 * win.offset);
-		a.ray_d = c->q_d[parity] + win.offset;
+		a.ray_o = (const float4 *)((const float *)c->q.o[parity].get() + 3 * win.offset);
+		a.hit = (float4 *)((float *)c->q.hit.get() + 3 * win.offset);
+		a.ray_d = c->q.d[parity] + win.offset;
 	}
 	else
 	{
-		a.ray_o = (shadow_queue ? c->sh_o : c->q_o[parity]) + win.offset; a.ray_d = (shadow_queue ? c->sh_d : c->q_d[parity]) + win.offset;
-		a.hit = (shadow_queue ? c->sh_hit : c->d_hit) + win.offset;
+		a.ray_o = (shadow_queue ? c->q.sh_o : c->q.o[parity]) + win.offset; a.ray_d = (shadow_queue ? c->q.sh_d : c->q.d[parity]) + win.offset;
+		a.hit = (shadow_queue ? c->q.sh_hit : c->q.hit) + win.offset;
 	}
 	a.ray_stats = ray_stats;
 	a.count = count; a.cursor = cursor;
@@ -309,15 +299,10 @@ int launch_trace(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, int par
 	a.seg_cap = win.seg_cap;
 	a.refill_min = camera_rays ? c->refill_min_primary : c->refill_min; a.chunk = c->chunk; a.bite = camera_rays ? c->bite_primary : c->bite; a.endgame = c->endgame;
 	a.stack_size = stack_size; a.lds_depth = c->lds_depth;
-	const size_t lds = c->lds_bytes;
-	hipEvent_t *stop = begin_timing(c, 0, pipe.stream);
-	if(any_hit)
-	{
-		if(stats) hipLaunchKernelGGL((k_trace<true, true>), dim3(c->trace_blocks), dim3(kTraceThreads), lds, pipe.stream, a);
-		else hipLaunchKernelGGL((k_trace<false, true>), dim3(c->trace_blocks), dim3(kTraceThreads), lds, pipe.stream, a);
-	}
-	else if(stats) hipLaunchKernelGGL(k_trace<true>, dim3(c->trace_blocks), dim3(kTraceThreads), lds, pipe.stream, a);
-	else hipLaunchKernelGGL(k_trace<false>, dim3(c->trace_blocks), dim3(kTraceThreads), lds, pipe.stream, a);
+	hipEvent_t stop = begin_timing(c, 0, pipe.stream);
+	with_flags(stats, any_hit, [&](auto S, auto Any) {
+		hipLaunchKernelGGL((k_trace<decltype(S)::value, decltype(Any)::value>), dim3(c->trace_blocks), dim3(kTraceThreads), c->lds_bytes, pipe.stream, a);
+	});
 	end_timing(stop, pipe.stream);
 	HIP_TRY(c, hipGetLastError());
 	return ADYPT_OK;
@@ -333,7 +318,7 @@ void fill_frame(const adypt_ctx *c, FrameArgs *f)
 	f->clamp = c->params.clamp;
 	f->width = c->width; f->height = c->height;
 	f->spp = c->spp; f->subpixel = c->params.subpixel; f->tmp_life = c->params.tmp_lifetime; f->max_bounce = c->params.max_bounce;
-	f->sobol = c->d_sobol; f->done = c->d_done; f->n_frames = 1; f->frame_first = 0; f->frame_stride = 1; f->batched = 0;
+	f->sobol = c->d_sobol; f->done = c->q.done; f->n_frames = 1; f->frame_first = 0; f->frame_stride = 1; f->batched = 0;
 	f->n_local_px = c->n_local_px; f->blocks_x = c->blocks_x; f->rank = c->rank; f->nranks = c->nranks;
 	f->n_tris = (int32_t)c->n_tris; f->n_mats = (int32_t)c->n_mats; f->n_tex = c->n_tex;
 	f->deal_chunks = c->deal_chunks;
@@ -390,17 +375,12 @@ int launch_trace_camera(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, 
 	a.refill_min = c->refill_min_primary; a.chunk = c->chunk; a.bite = c->bite_primary; a.endgame = c->endgame;
 	a.stack_size = c->params.stack_size; a.lds_depth = c->lds_depth;
 	K.f = f; K.local_blocks = (const int32_t *)c->d_local_blocks; K.px = px; K.bias_mode = bias_mode;
-	hipEvent_t *stop = begin_timing(c, 0, pipe.stream);
+	hipEvent_t stop = begin_timing(c, 0, pipe.stream);
 	const bool viewer = viewer_type >= 0; // a primary-only call: the pixel is coloured when its ray has finished (no viewer launch)
 	if(viewer) { fill_scene(c, &K.sc); K.viewer_type = viewer_type; }
-	const dim3 grid(c->trace_blocks), block(kTraceThreads);
-	if(viewer)
-	{
-		if(stats) hipLaunchKernelGGL((k_trace_camera<true, true>), grid, block, c->lds_bytes, pipe.stream, K);
-		else hipLaunchKernelGGL((k_trace_camera<false, true>), grid, block, c->lds_bytes, pipe.stream, K);
-	}
-	else if(stats) hipLaunchKernelGGL((k_trace_camera<true, false>), grid, block, c->lds_bytes, pipe.stream, K);
-	else hipLaunchKernelGGL((k_trace_camera<false, false>), grid, block, c->lds_bytes, pipe.stream, K);
+	with_flags(stats, viewer, [&](auto S, auto Viewer) {
+		hipLaunchKernelGGL((k_trace_camera<decltype(S)::value, decltype(Viewer)::value>), dim3(c->trace_blocks), dim3(kTraceThreads), c->lds_bytes, pipe.stream, K);
+	});
 	end_timing(stop, pipe.stream);
 	HIP_TRY(c, hipGetLastError());
 	return ADYPT_OK;
@@ -410,9 +390,9 @@ QueueArgs queue_args(adypt_ctx *c, const QueueWindow &win, int in, const uint32_
 {
 	QueueArgs q;
 	q.seg_paths = frames > 0 ? pass_seg_paths(c, win, frames) : win.seg_cap;
-	q.ray_o = (float *)c->q_o[in] + 3 * win.offset; q.ray_d = c->q_d[in] + win.offset; q.col = (float *)c->q_col[in] + 3 * win.offset;
-	q.hit = (float *)c->d_hit + 3 * win.offset;
-	q.out_o = (float *)c->q_o[in ^ 1] + 3 * win.offset; q.out_d = c->q_d[in ^ 1] + win.offset; q.out_col = (float *)c->q_col[in ^ 1] + 3 * win.offset;
+	q.ray_o = (float *)c->q.o[in].get() + 3 * win.offset; q.ray_d = c->q.d[in] + win.offset; q.col = (float *)c->q.col[in].get() + 3 * win.offset;
+	q.hit = (float *)c->q.hit.get() + 3 * win.offset;
+	q.out_o = (float *)c->q.o[in ^ 1].get() + 3 * win.offset; q.out_d = c->q.d[in ^ 1] + win.offset; q.out_col = (float *)c->q.col[in ^ 1].get() + 3 * win.offset;
 	q.count_in = count_in; q.count_out = count_out;
 	q.seg_cap = win.seg_cap;
 	return q;
@@ -430,17 +410,10 @@ int load_shift(adypt_ctx *c)
 	if(c->shift_loaded && c->shift_seed_loaded == c->params.shift_seed) return ADYPT_OK;
 	std::vector<uint8_t> full((size_t)c->width * c->height * 2), local((size_t)c->n_local_px * 2, 0);
 	adypt_shift_bytes(c->params.shift_seed, c->width, c->height, full.data());
-	for(int L = 0; L < c->n_local_px; ++L)
-	{
-		const int blk = c->local_blocks[(size_t)(L >> 10)];
-		const int in = L & 1023, wt = in >> 6, ln = in & 63;
-		const int x = (blk % c->blocks_x) * kBlockDim + (wt & 3) * 8 + (ln & 7), y = (blk / c->blocks_x) * kBlockDim + (wt >> 2) * 8 + (ln >> 3);
-		if(x < c->width && y < c->height)
-		{
-			local[(size_t)L * 2] = full[((size_t)y * c->width + x) * 2];
-			local[(size_t)L * 2 + 1] = full[((size_t)y * c->width + x) * 2 + 1];
-		}
-	}
+	for_each_local_pixel(c->local_blocks, c->width, c->height, [&](size_t L, int x, int y) {
+		local[L * 2] = full[((size_t)y * c->width + x) * 2];
+		local[L * 2 + 1] = full[((size_t)y * c->width + x) * 2 + 1];
+	});
 	// frames enqueued earlier (adypt_trace_spp_async, then adypt_reset + adypt_set_params) may still be reading d_shift
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	if(!local.empty()) HIP_TRY(c, hipMemcpy(c->d_shift, local.data(), local.size(), hipMemcpyHostToDevice));
@@ -451,17 +424,11 @@ int load_shift(adypt_ctx *c)
 // (re)allocate the wavefront queues for `fif` frames in flight: capacity = fif x local pixels, cut into 8 segments
 int alloc_queues_raw(adypt_ctx *c, int fif)
 {
-	void *old[] = {c->q_o[0], c->q_o[1], c->q_d[0], c->q_d[1], c->q_col[0], c->q_col[1], c->d_hit, c->d_done, c->d_ray_stats,
-				   c->sh_o, c->sh_d, c->sh_col, c->sh_hit};
-	for(void *b : old) if(b) (void)hipFree(b);
-	c->q_o[0] = c->q_o[1] = c->q_d[0] = c->q_d[1] = c->q_col[0] = c->q_col[1] = c->d_hit = c->d_done = nullptr;
-	c->sh_o = c->sh_d = c->sh_col = c->sh_hit = nullptr; // re-created by ensure_shadow_queue when the option is on
-	c->d_ray_stats = nullptr;
+	c->q = Queues{}; // the old ones go FIRST: old and new together would double the peak.  (The sun-visibility queue and the ray statistics come back when asked for)
 	const size_t npx = (size_t)std::max(c->n_local_px, 64);
 	const size_t paths = npx * (size_t)fif;
 	if(paths >= ((size_t)1 << 31)) return fail(c, ADYPT_E_INVALID, "frames in flight x pixels exceeds 2^31 paths");
-	const size_t chunks = (paths + kShadeThreads - 1) / kShadeThreads;
-	c->seg_cap = (uint32_t)(((chunks + kNumSegments - 1) / kNumSegments) * kShadeThreads);
+	c->seg_cap = seg_slots_for(c, fif);
 	c->capacity = (int64_t)c->seg_cap * kNumSegments;
 	c->frames_in_flight = fif;
 	size_t nq = (size_t)c->capacity;
@@ -470,13 +437,13 @@ int alloc_queues_raw(adypt_ctx *c, int fif)
 	c->alloc_slots = nq;
 	for(int i = 0; i < 2; ++i)
 	{
-		HIP_TRY(c, hipMalloc((void **)&c->q_o[i], nq * sizeof(float4)));
-		HIP_TRY(c, hipMalloc((void **)&c->q_d[i], nq * sizeof(float4)));
-		HIP_TRY(c, hipMalloc((void **)&c->q_col[i], nq * sizeof(float4)));
+		HIP_TRY(c, c->q.o[i].alloc(nq * sizeof(float4)));
+		HIP_TRY(c, c->q.d[i].alloc(nq * sizeof(float4)));
+		HIP_TRY(c, c->q.col[i].alloc(nq * sizeof(float4)));
 	}
-	HIP_TRY(c, hipMalloc((void **)&c->d_hit, nq * sizeof(float4)));
+	HIP_TRY(c, c->q.hit.alloc(nq * sizeof(float4)));
 	// finished samples of a batch / parked radiance of live paths; two frames at least: single frames in a row alternate between two slots
-	HIP_TRY(c, hipMalloc((void **)&c->d_done, npx * (size_t)std::max(fif, 2) * sizeof(float4)));
+	HIP_TRY(c, c->q.done.alloc(npx * (size_t)std::max(fif, 2) * sizeof(float4)));
 	return ADYPT_OK;
 }
 
@@ -497,9 +464,7 @@ int alloc_queues(adypt_ctx *c, int fif)
 		return r;
 	}
 	// nothing usable is left: free the partial allocation of the failed attempt
-	void *bufs[] = {c->q_o[0], c->q_o[1], c->q_d[0], c->q_d[1], c->q_col[0], c->q_col[1], c->d_hit, c->d_done};
-	for(void *b : bufs) if(b) (void)hipFree(b);
-	c->q_o[0] = c->q_o[1] = c->q_d[0] = c->q_d[1] = c->q_col[0] = c->q_col[1] = c->d_hit = c->d_done = nullptr;
+	c->q = Queues{};
 	c->capacity = 0; c->seg_cap = 0; c->alloc_slots = 0; c->frames_in_flight = previous;
 	c->error = why + " (the context has no ray queues left: destroy it)";
 	return r;
@@ -507,59 +472,41 @@ int alloc_queues(adypt_ctx *c, int fif)
 
 int ensure_shadow_queue(adypt_ctx *c)
 {
-	if(c->sh_o) return ADYPT_OK;
+	if(c->q.sh_o) return ADYPT_OK;
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	const size_t nq = c->alloc_slots;
-	HIP_TRY(c, hipMalloc((void **)&c->sh_o, nq * sizeof(float4)));
-	HIP_TRY(c, hipMalloc((void **)&c->sh_d, nq * sizeof(float4)));
-	HIP_TRY(c, hipMalloc((void **)&c->sh_col, nq * sizeof(float4)));
-	HIP_TRY(c, hipMalloc((void **)&c->sh_hit, nq * sizeof(float4)));
+	HIP_TRY(c, c->q.sh_o.alloc(nq * sizeof(float4)));
+	HIP_TRY(c, c->q.sh_d.alloc(nq * sizeof(float4)));
+	HIP_TRY(c, c->q.sh_col.alloc(nq * sizeof(float4)));
+	HIP_TRY(c, c->q.sh_hit.alloc(nq * sizeof(float4)));
 	return ADYPT_OK;
 }
 
-int ensure_cache_slices(adypt_ctx *c, int extra)
-{
-	if(extra <= c->cache_next_slices) return ADYPT_OK;
-	HIP_TRY(c, hipStreamSynchronize(c->stream)); // the previous batch may still be reading the slices about to be freed
-	if(c->d_cache_next) (void)hipFree(c->d_cache_next); // (they hold nothing between batches)
-	c->d_cache_next = nullptr; c->cache_next_slices = 0;
-	HIP_TRY(c, hipMalloc((void **)&c->d_cache_next, (size_t)extra * (size_t)std::max(c->n_local_px, 64) * sizeof(float4)));
-	c->cache_next_slices = extra;
-	return ADYPT_OK;
-}
+// (the previous batch may still be reading the slices about to be freed; they hold nothing between batches)
+int ensure_cache_slices(adypt_ctx *c, int extra) { return grow(c, c->d_cache_next, (size_t)extra * (size_t)std::max(c->n_local_px, 64) * sizeof(float4)); }
 
-// the audit's bitmap over the path ids (one bit per queue slot is enough: ids are < capacity)
-int ensure_audit(adypt_ctx *c)
-{
-	const size_t words = ((size_t)c->alloc_slots + 31) / 32 + 1;
-	if(c->d_audit_seen && c->audit_words >= words) return ADYPT_OK;
-	HIP_TRY(c, hipDeviceSynchronize());
-	if(c->d_audit_seen) (void)hipFree(c->d_audit_seen);
-	c->d_audit_seen = nullptr; c->audit_words = 0;
-	HIP_TRY(c, hipMalloc((void **)&c->d_audit_seen, words * kMaxPipes * sizeof(uint32_t))); // one bitmap per chain: they check concurrently
-	c->audit_words = words;
-	return ADYPT_OK;
-}
+// the audit's bitmap over the path ids (one bit per queue slot is enough: ids are < capacity), one bitmap per chain: they check concurrently
+int ensure_audit(adypt_ctx *c) { return grow(c, c->d_audit_seen, (((size_t)c->alloc_slots + 31) / 32 + 1) * kMaxPipes * sizeof(uint32_t), true); }
+size_t audit_words(const adypt_ctx *c) { return c->d_audit_seen.bytes() / (kMaxPipes * sizeof(uint32_t)); } // words of ONE bitmap
 // around a kernel that appends to q's output queue: poison before, check after (both on the launch's stream)
 void audit_before(adypt_ctx *c, const QueueArgs &q, hipStream_t stream, int pipe = 0)
 {
-	if(!(c->instrumentation & 4) || !c->d_audit_seen || c->audit_words * 32 < c->alloc_slots) return;
-	const size_t n = (size_t)kNumSegments * q.seg_cap, n_seen = c->audit_words; // path ids are numbered over the whole batch, not over the chain's window
-	hipLaunchKernelGGL(k_audit_poison, dim3((unsigned)((std::max(n, n_seen) + 255) / 256)), dim3(256), 0, stream, q.out_d, n, c->d_audit_seen + (size_t)pipe * c->audit_words, n_seen);
+	if(!(c->instrumentation & 4) || !c->d_audit_seen || audit_words(c) * 32 < c->alloc_slots) return;
+	const size_t n = (size_t)kNumSegments * q.seg_cap, n_seen = audit_words(c); // path ids are numbered over the whole batch, not over the chain's window
+	hipLaunchKernelGGL(k_audit_poison, dim3((unsigned)((std::max(n, n_seen) + 255) / 256)), dim3(256), 0, stream, q.out_d, n, c->d_audit_seen + (size_t)pipe * audit_words(c), n_seen);
 }
 __global__ void k_audit_plant(float4 *out_d, const uint32_t *count) { if(count[0] >= 2u) out_d[1].w = out_d[0].w; } // (self-test of the detector: two slots, one path)
 void audit_after(adypt_ctx *c, const QueueArgs &q, hipStream_t stream, int pipe = 0)
 {
-	if(!(c->instrumentation & 4) || !c->d_audit_seen || c->audit_words * 32 < c->alloc_slots) return;
+	if(!(c->instrumentation & 4) || !c->d_audit_seen || audit_words(c) * 32 < c->alloc_slots) return;
 	if(c->audit_selftest) hipLaunchKernelGGL(k_audit_plant, dim3(1), dim3(1), 0, stream, q.out_d, (const uint32_t *)q.count_out);
-	hipLaunchKernelGGL(k_audit_check, dim3((q.seg_cap + 255) / 256, kNumSegments), dim3(256), 0, stream, (const float4 *)q.out_d, (const uint32_t *)q.count_out, q.seg_cap, c->d_audit_seen + (size_t)pipe * c->audit_words,
-					   (uint32_t)std::min<size_t>(c->audit_words * 32, 0xffffffffu), &c->d_stats->audit_errors);
+	hipLaunchKernelGGL(k_audit_check, dim3((q.seg_cap + 255) / 256, kNumSegments), dim3(256), 0, stream, (const float4 *)q.out_d, (const uint32_t *)q.count_out, q.seg_cap, c->d_audit_seen + (size_t)pipe * audit_words(c),
+					   (uint32_t)std::min<size_t>(audit_words(c) * 32, 0xffffffffu), &c->d_stats->audit_errors);
 }
 
 int ensure_ray_stats(adypt_ctx *c)
 {
-	if(c->d_ray_stats) return ADYPT_OK;
-	HIP_TRY(c, hipMalloc((void **)&c->d_ray_stats, (size_t)c->capacity * sizeof(RayStats)));
+	if(!c->q.ray_stats) HIP_TRY(c, c->q.ray_stats.alloc((size_t)c->capacity * sizeof(RayStats)));
 	return ADYPT_OK;
 }
 
@@ -567,15 +514,10 @@ int ensure_ray_stats(adypt_ctx *c)
 int apply_params(adypt_ctx *c)
 {
 	c->params = c->pending;
-	int r = configure_trace(c, c->params.stack_size);
-	if(r != ADYPT_OK) return r;
+	TRY_CREATE(configure_trace(c, c->params.stack_size));
 	// cache slices for the tmpLifetime groups a batch of frames_in_flight frames can span (none for one frame at a time)
 	const int life = std::max(1, c->params.tmp_lifetime);
-	if(c->frames_in_flight > 1)
-	{
-		r = ensure_cache_slices(c, (c->frames_in_flight - 2) / life + 1);
-		if(r != ADYPT_OK) return r;
-	}
+	if(c->frames_in_flight > 1) TRY_CREATE(ensure_cache_slices(c, (c->frames_in_flight - 2) / life + 1));
 	return load_shift(c);
 }
 
@@ -648,16 +590,27 @@ void **ctx_comm_slot(adypt_ctx *c, void (***free_fn)(void *)) { *free_fn = &c->c
 
 namespace {
 
+// First line of a C-ABI function that touches the device: the context's device current (a process may hold contexts on several devices) and,
+// DRAINED, everything enqueued on the context's stream finished.  Which of the two an entry point takes is its own (include/adypt_hip.h).
+#define ENTER(c) HIP_TRY(c, hipSetDevice(c->device))
+#define ENTER_DRAINED(c) do { ENTER(c); HIP_TRY(c, hipStreamSynchronize(c->stream)); } while(0)
+
+int read_device_stats(adypt_ctx *c, DeviceStats *st)
+{
+	ENTER_DRAINED(c);
+	HIP_TRY(c, hipMemcpy(st, c->d_stats, sizeof(*st), hipMemcpyDeviceToHost));
+	return ADYPT_OK;
+}
+
 // ---- the steps of adypt_create ----
 
 int create_streams(adypt_ctx *c)
 {
-	HIP_TRY(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-	c->pipes[0].stream = c->stream;
-	for(int k = 1; k < kMaxPipes; ++k) HIP_TRY(c, hipStreamCreateWithFlags(&c->pipes[k].stream, hipStreamNonBlocking));
-	for(int k = 0; k < kMaxPipes; ++k) HIP_TRY(c, hipEventCreateWithFlags(&c->pipes[k].done, hipEventDisableTiming));
-	HIP_TRY(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
-	for(int s = 0; s < 2; ++s) HIP_TRY(c, hipEventCreateWithFlags(&c->roll_ready[s], hipEventDisableTiming));
+	for(int k = 0; k < kMaxPipes; ++k) HIP_TRY(c, hipStreamCreateWithFlags(c->pipes[k].stream.out(), hipStreamNonBlocking));
+	c->stream = c->pipes[0].stream;
+	for(int k = 0; k < kMaxPipes; ++k) HIP_TRY(c, hipEventCreateWithFlags(c->pipes[k].done.out(), hipEventDisableTiming));
+	HIP_TRY(c, hipEventCreateWithFlags(c->fork_ev.out(), hipEventDisableTiming));
+	for(int s = 0; s < 2; ++s) HIP_TRY(c, hipEventCreateWithFlags(c->roll_ready[s].out(), hipEventDisableTiming));
 	return ADYPT_OK;
 }
 
@@ -700,9 +653,9 @@ void set_shard(adypt_ctx *c, const adypt_scene_desc *d)
 int alloc_frame_state(adypt_ctx *c)
 {
 	const size_t npx = (size_t)std::max(c->n_local_px, 64);
-	HIP_TRY(c, hipMalloc((void **)&c->d_accum, npx * sizeof(float4)));
-	HIP_TRY(c, hipMalloc((void **)&c->d_cache, npx * sizeof(float4)));
-	HIP_TRY(c, hipMalloc((void **)&c->d_shift, npx * 2));
+	HIP_TRY(c, c->d_accum.alloc(npx * sizeof(float4)));
+	HIP_TRY(c, c->d_cache.alloc(npx * sizeof(float4)));
+	HIP_TRY(c, c->d_shift.alloc(npx * 2));
 	HIP_TRY(c, hipMemset(c->d_accum, 0, npx * sizeof(float4)));
 	HIP_TRY(c, hipMemset(c->d_cache, 0xff, npx * sizeof(float4)));
 	HIP_TRY(c, hipMemset(c->d_shift, 0, npx * 2));
@@ -714,28 +667,29 @@ int alloc_frame_state(adypt_ctx *c)
 		if(c->tun.frames_in_flight > 0) fif = std::min(kMaxFramesInFlight, c->tun.frames_in_flight);
 		TRY_CREATE(alloc_queues(c, fif));
 	}
-	HIP_TRY(c, hipMalloc((void **)&c->d_sobol, (size_t)kMaxFramesInFlight * 64 * sizeof(float)));
+	HIP_TRY(c, c->d_sobol.alloc((size_t)kMaxFramesInFlight * 64 * sizeof(float)));
 	for(int i = 0; i < adypt_ctx::kSobolSlots; ++i) // allocated here, not lazily: nothing is allocated while frames are traced
 	{
-		HIP_TRY(c, hipHostMalloc((void **)&c->h_sobol[i], (size_t)kMaxFramesInFlight * 64 * sizeof(float), hipHostMallocDefault));
-		HIP_TRY(c, hipEventCreateWithFlags(&c->sobol_done[i], hipEventDisableTiming));
+		HIP_TRY(c, c->h_sobol[i].alloc((size_t)kMaxFramesInFlight * 64 * sizeof(float), hipHostMallocDefault));
+		HIP_TRY(c, hipEventCreateWithFlags(c->sobol_done[i].out(), hipEventDisableTiming));
 	}
-	HIP_TRY(c, hipMalloc((void **)&c->d_counters, sizeof(FrameCounters) * kMaxPipes));
+	HIP_TRY(c, c->d_counters.alloc(sizeof(FrameCounters) * kMaxPipes));
 	for(int k = 0; k < kMaxPipes; ++k) c->pipes[k].counters = c->d_counters + k;
-	HIP_TRY(c, hipMalloc((void **)&c->d_stats, sizeof(DeviceStats)));
+	HIP_TRY(c, c->d_stats.alloc(sizeof(DeviceStats)));
 	HIP_TRY(c, hipMemset(c->d_counters, 0, sizeof(FrameCounters) * kMaxPipes));
-	HIP_TRY(c, hipMalloc((void **)&c->d_camera_cursors, sizeof(uint32_t) * (2 * kNumSegments + 1) * kCursorStride));
+	HIP_TRY(c, c->d_camera_cursors.alloc(sizeof(uint32_t) * (2 * kNumSegments + 1) * kCursorStride));
 	HIP_TRY(c, hipMemset(c->d_camera_cursors, 0, sizeof(uint32_t) * (2 * kNumSegments + 1) * kCursorStride));
 	HIP_TRY(c, hipMemset(c->d_stats, 0, sizeof(DeviceStats)));
-	HIP_TRY(c, hipHostMalloc((void **)&c->h_overflow, sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+	HIP_TRY(c, c->h_overflow.alloc(sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
 	*c->h_overflow = 0u;
-	HIP_TRY(c, hipMemcpy(&c->d_stats->host_overflow, &c->h_overflow, sizeof(uint32_t *), hipMemcpyHostToDevice));
+	uint32_t *const h_overflow = c->h_overflow;
+	HIP_TRY(c, hipMemcpy(&c->d_stats->host_overflow, &h_overflow, sizeof(uint32_t *), hipMemcpyHostToDevice));
 	return ADYPT_OK;
 }
 
 int create_steps(adypt_ctx *c, const adypt_scene_desc *d)
 {
-	HIP_TRY(c, hipSetDevice(c->device));
+	ENTER(c);
 	TRY_CREATE(create_streams(c));
 	apply_tunables(c);
 	hipDeviceProp_t prop;
@@ -780,18 +734,11 @@ int64_t adypt_shard_block_count(int width, int height, int rank, int nranks)
 int adypt_untile_host(int width, int height, int rank, int nranks, const float *local_rgba, float *rgb)
 {
 	if(width <= 0 || height <= 0 || nranks <= 0 || rank < 0 || rank >= nranks || !local_rgba || !rgb) return ADYPT_E_INVALID;
-	const std::vector<int32_t> blocks = owned_blocks(width, height, rank, nranks);
-	const int nbx = (width + kBlockDim - 1) / kBlockDim;
-	for(size_t bi = 0; bi < blocks.size(); ++bi)
-		for(int in = 0; in < kBlockPixels; ++in)
-		{
-			const int wt = in >> 6, ln = in & 63;
-			const int x = (blocks[bi] % nbx) * kBlockDim + (wt & 3) * 8 + (ln & 7), y = (blocks[bi] / nbx) * kBlockDim + (wt >> 2) * 8 + (ln >> 3);
-			if(x >= width || y >= height) continue;
-			const float *s = local_rgba + (bi * kBlockPixels + (size_t)in) * 4;
-			float *o = rgb + ((size_t)y * width + x) * 3;
-			o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
-		}
+	for_each_local_pixel(owned_blocks(width, height, rank, nranks), width, height, [&](size_t L, int x, int y) {
+		const float *s = local_rgba + L * 4;
+		float *o = rgb + ((size_t)y * width + x) * 3;
+		o[0] = s[0]; o[1] = s[1]; o[2] = s[2];
+	});
 	return ADYPT_OK;
 }
 
@@ -827,28 +774,7 @@ void adypt_destroy(adypt_ctx *c)
 	(void)hipSetDevice(c->device);
 	for(int k = 0; k < kMaxPipes; ++k) if(c->pipes[k].stream) (void)hipStreamSynchronize(c->pipes[k].stream);
 	if(c->comm && c->comm_free) c->comm_free(c->comm);
-	c->comm = nullptr;
-	for(EventPair &p : c->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-	for(EventPair &p : c->free_events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-	void *bufs[] = {c->sh_o, c->sh_d, c->sh_col, c->sh_hit, c->d_all_blocks, c->d_nodes, c->d_woop, c->d_tri_indices, c->d_triangles, c->d_materials, c->d_tri_class, c->d_texels, c->d_ref_triangles, c->d_local_blocks,
-					c->d_accum, c->d_cache, c->d_cache_next, c->d_shift, c->q_o[0], c->q_o[1], c->q_d[0], c->q_d[1], c->q_col[0], c->q_col[1],
-					c->d_hit, c->d_ray_stats, c->d_audit_seen, c->d_counters, c->d_camera_cursors, c->d_stats, c->d_spill, c->d_done, c->d_sobol, c->d_display};
-	for(void *b : bufs) if(b) (void)hipFree(b);
-	for(int i = 0; i < adypt_ctx::kSobolSlots; ++i)
-	{
-		if(c->h_sobol[i]) (void)hipHostFree(c->h_sobol[i]);
-		if(c->sobol_done[i]) (void)hipEventDestroy(c->sobol_done[i]);
-	}
-	for(int k = 0; k < kMaxPipes; ++k)
-	{
-		if(c->pipes[k].done) (void)hipEventDestroy(c->pipes[k].done);
-		if(k > 0 && c->pipes[k].stream) (void)hipStreamDestroy(c->pipes[k].stream);
-	}
-	if(c->h_overflow) (void)hipHostFree(c->h_overflow);
-	if(c->fork_ev) (void)hipEventDestroy(c->fork_ev);
-	for(int s = 0; s < 2; ++s) if(c->roll_ready[s]) (void)hipEventDestroy(c->roll_ready[s]);
-	if(c->stream) (void)hipStreamDestroy(c->stream);
-	delete c;
+	delete c; // every member releases itself, the streams and events last (context.hpp)
 }
 
 int adypt_set_params(adypt_ctx *c, const adypt_pt_params *p)
@@ -861,7 +787,7 @@ int adypt_set_params(adypt_ctx *c, const adypt_pt_params *p)
 	c->have_params = true;
 	if(!c->pt_started)
 	{
-		HIP_TRY(c, hipSetDevice(c->device));
+		ENTER(c); // (not drained: each step of apply_params that replaces something in use waits for its users itself)
 		return apply_params(c);
 	}
 	return ADYPT_OK;
@@ -901,18 +827,17 @@ int adypt_set_instrumentation(adypt_ctx *c, int flags)
 {
 	if(!c) return ADYPT_E_INVALID;
 	c->instrumentation = flags;
-	if(flags & 4) { HIP_TRY(c, hipSetDevice(c->device)); int r = ensure_audit(c); if(r != ADYPT_OK) return r; }
+	if(flags & 4) { ENTER(c); TRY_CREATE(ensure_audit(c)); }
 	if(flags & 1)
 	{
 		// a pool of event pairs for the kernel timing, created here rather than while frames are being traced
-		HIP_TRY(c, hipSetDevice(c->device));
+		ENTER(c);
 		while(c->free_events.size() + c->events.size() < 96)
 		{
 			EventPair p;
-			p.kind = 0;
-			HIP_TRY(c, hipEventCreate(&p.a));
-			HIP_TRY(c, hipEventCreate(&p.b));
-			c->free_events.push_back(p);
+			HIP_TRY(c, hipEventCreate(p.a.out()));
+			HIP_TRY(c, hipEventCreate(p.b.out()));
+			c->free_events.push_back(std::move(p));
 		}
 	}
 	return ADYPT_OK;
@@ -926,8 +851,7 @@ int adypt_set_sun_visibility(adypt_ctx *c, int enabled, const float dir[3])
 	const float len2 = fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0]));
 	if(!(len2 > 0.0f) || !(len2 < INFINITY)) return fail(c, ADYPT_E_INVALID, "adypt_set_sun_visibility: direction must be finite and non-zero");
 	const float inv = 1.0f / sqrtf(len2); // normalize() in the canonical arithmetic (canon_math.hpp normalize3)
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	ENTER_DRAINED(c);
 	c->sun_dir[0] = d[0] * inv; c->sun_dir[1] = d[1] * inv; c->sun_dir[2] = d[2] * inv;
 	c->sun_visibility = enabled ? 1 : 0;
 	drop_lookahead(c);
@@ -938,8 +862,7 @@ int adypt_set_frames_in_flight(adypt_ctx *c, int n)
 {
 	if(!c) return ADYPT_E_INVALID;
 	if(n < 1 || n > kMaxFramesInFlight) return fail(c, ADYPT_E_INVALID, "adypt_set_frames_in_flight: n_frames must be in [1, " + std::to_string(kMaxFramesInFlight) + "]");
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	ENTER_DRAINED(c);
 	if(n == c->frames_in_flight && c->queues_ok) return ADYPT_OK;
 	drop_lookahead(c); // the parked samples live in the buffers about to be reallocated
 	int r = alloc_queues(c, n);
@@ -973,21 +896,19 @@ int adypt_trace_primary(adypt_ctx *c, int viewer_type)
 	if(!c) return ADYPT_E_INVALID;
 	if(!c->have_camera) return fail(c, ADYPT_E_STATE, "adypt_trace_primary: call adypt_set_camera first");
 	if(!c->queues_ok) return fail(c, ADYPT_E_STATE, "adypt_trace_primary: the context lost its ray queues (failed adypt_set_frames_in_flight)");
-	HIP_TRY(c, hipSetDevice(c->device));
+	ENTER(c);
 	// Trace(false): leaves path-tracing mode (OglPathTracer.cpp:53-58)
 	c->pt_started = false; c->spp = 0;
 	drop_lookahead(c);
 	c->view_type = viewer_type;
-	int r = apply_params(c);
-	if(r != ADYPT_OK) return r;
+	TRY_CREATE(apply_params(c));
 	if(c->n_local_px == 0) return ADYPT_OK; // a tile shard that owns no 32x32 block (more ranks than block diagonals): nothing to render
 	FrameArgs f; SceneArgs sc; PixelArgs px;
 	fill_frame(c, &f); fill_scene(c, &sc); fill_pixels(c, &px);
 	const Pipe &pipe = c->pipes[0];
 	const QueueWindow win = full_window(c);
 	// camera rays -> traversal -> cache image and the viewer's colour of every pixel (primaryray.glsl:46-94): one launch is the whole call
-	r = launch_trace_camera(c, pipe, win, f, px, 0, (c->instrumentation & 2) != 0, viewer_type);
-	if(r != ADYPT_OK) return r;
+	TRY_CREATE(launch_trace_camera(c, pipe, win, f, px, 0, (c->instrumentation & 2) != 0, viewer_type));
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	harvest_events(c);
@@ -997,8 +918,7 @@ int adypt_trace_primary(adypt_ctx *c, int viewer_type)
 int adypt_wait(adypt_ctx *c)
 {
 	if(!c) return ADYPT_E_INVALID;
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	ENTER_DRAINED(c);
 	harvest_events(c);
 	return check_async_errors(c);
 }
@@ -1014,15 +934,14 @@ int adypt_trace_spp_async(adypt_ctx *c, int n_spp)
 	if(!c || n_spp < 0) return ADYPT_E_INVALID;
 	if(!c->have_camera) return fail(c, ADYPT_E_STATE, "adypt_trace_spp: call adypt_set_camera first");
 	if(!c->queues_ok) return fail(c, ADYPT_E_STATE, "adypt_trace_spp: the context lost its ray queues (failed adypt_set_frames_in_flight)");
-	HIP_TRY(c, hipSetDevice(c->device));
+	ENTER(c);
 	if(c->n_local_px == 0)
 	{
 		// a tile shard that owns no 32x32 block (more ranks than block diagonals, e.g. 64x36 on 4 ranks): the frame counter
 		// and the parameter hand-over advance like everywhere else, no kernel runs (they would divide by n_local_px)
 		if(n_spp > 0 && !c->pt_started)
 		{
-			int r = apply_params(c);
-			if(r != ADYPT_OK) return r;
+			TRY_CREATE(apply_params(c));
 			c->spp = 0; c->pt_started = true; c->view_type = 3;
 		}
 		c->spp += n_spp;
@@ -1048,10 +967,9 @@ int adypt_trace_spp_async(adypt_ctx *c, int n_spp)
 int adypt_read_radiance(adypt_ctx *c, float *rgb)
 {
 	if(!c || !rgb) return ADYPT_E_INVALID;
-	HIP_TRY(c, hipSetDevice(c->device));
 	// the context's stream is non-blocking: a legacy-stream copy is not ordered after the frames enqueued by
 	// adypt_trace_spp_async, so wait for them here (include/adypt_hip.h: entry points that read results synchronise)
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	ENTER_DRAINED(c);
 	if(c->n_local_px == 0) return ADYPT_OK; // a shard that owns no block: nothing of the image is this context's
 	std::vector<float> local((size_t)c->n_local_px * 4);
 	HIP_TRY(c, hipMemcpy(local.data(), c->d_accum, local.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -1061,43 +979,30 @@ int adypt_read_radiance(adypt_ctx *c, float *rgb)
 int adypt_read_display(adypt_ctx *c, uint8_t *rgba8)
 {
 	if(!c || !rgba8) return ADYPT_E_INVALID;
-	HIP_TRY(c, hipSetDevice(c->device));
+	ENTER(c); // (not drained, on purpose: the display transform and the copy are enqueued BEHIND the frames on the context's stream, then waited for)
 	if(c->n_local_px == 0) return ADYPT_OK;
-	if(!c->d_display) HIP_TRY(c, hipMalloc((void **)&c->d_display, (size_t)c->n_local_px * sizeof(uint32_t))); // once: the size never changes
+	if(!c->d_display) HIP_TRY(c, c->d_display.alloc((size_t)c->n_local_px * sizeof(uint32_t))); // once: the size never changes
 	hipLaunchKernelGGL(k_display, dim3((c->n_local_px + 255) / 256), dim3(256), 0, c->stream, (const float4 *)c->d_accum, c->n_local_px, c->view_type, c->d_display);
 	std::vector<uint32_t> local((size_t)c->n_local_px);
 	HIP_TRY(c, hipGetLastError());
 	HIP_TRY(c, hipMemcpyAsync(local.data(), c->d_display, local.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	for(int L = 0; L < c->n_local_px; ++L)
-	{
-		const int blk = c->local_blocks[(size_t)(L >> 10)];
-		const int in = L & 1023, wt = in >> 6, ln = in & 63;
-		const int x = (blk % c->blocks_x) * kBlockDim + (wt & 3) * 8 + (ln & 7), y = (blk / c->blocks_x) * kBlockDim + (wt >> 2) * 8 + (ln >> 3);
-		if(x >= c->width || y >= c->height) continue;
-		memcpy(rgba8 + ((size_t)y * c->width + x) * 4, &local[(size_t)L], 4);
-	}
+	for_each_local_pixel(c->local_blocks, c->width, c->height, [&](size_t L, int x, int y) { memcpy(rgba8 + ((size_t)y * c->width + x) * 4, &local[L], 4); });
 	return ADYPT_OK;
 }
 
 int adypt_read_hits(adypt_ctx *c, int32_t *tri, float *uv)
 {
 	if(!c || !tri || !uv) return ADYPT_E_INVALID;
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, hipStreamSynchronize(c->stream)); // see adypt_read_radiance
+	ENTER_DRAINED(c); // see adypt_read_radiance
 	if(c->n_local_px == 0) return ADYPT_OK;
 	std::vector<float> local((size_t)c->n_local_px * 4);
 	HIP_TRY(c, hipMemcpy(local.data(), c->d_cache, local.size() * sizeof(float), hipMemcpyDeviceToHost));
-	for(int L = 0; L < c->n_local_px; ++L)
-	{
-		const int blk = c->local_blocks[(size_t)(L >> 10)];
-		const int in = L & 1023, wt = in >> 6, ln = in & 63;
-		const int x = (blk % c->blocks_x) * kBlockDim + (wt & 3) * 8 + (ln & 7), y = (blk / c->blocks_x) * kBlockDim + (wt >> 2) * 8 + (ln >> 3);
-		if(x >= c->width || y >= c->height) continue;
+	for_each_local_pixel(c->local_blocks, c->width, c->height, [&](size_t L, int x, int y) {
 		const size_t p = (size_t)y * c->width + x;
-		memcpy(&tri[p], &local[(size_t)L * 4], 4);
-		uv[p * 2] = local[(size_t)L * 4 + 1]; uv[p * 2 + 1] = local[(size_t)L * 4 + 2];
-	}
+		memcpy(&tri[p], &local[L * 4], 4);
+		uv[p * 2] = local[L * 4 + 1]; uv[p * 2 + 1] = local[L * 4 + 2];
+	});
 	return ADYPT_OK;
 }
 
@@ -1105,10 +1010,10 @@ static int trace_rays_impl(adypt_ctx *c, const float *rays, int64_t n, adypt_hit
 {
 	if(!c || n < 0 || (n > 0 && (!rays || !hits))) return ADYPT_E_INVALID;
 	if(!c->queues_ok) return fail(c, ADYPT_E_STATE, "adypt_trace_rays: the context lost its ray queues (failed adypt_set_frames_in_flight)");
-	HIP_TRY(c, hipSetDevice(c->device));
+	ENTER(c);
 	drop_rolling(c); // (a frame started ahead works in a window of the queues this call is about to fill)
-	if(!c->pt_started) { int r = apply_params(c); if(r != ADYPT_OK) return r; }
-	if(with_stats) { int r = ensure_ray_stats(c); if(r != ADYPT_OK) return r; }
+	if(!c->pt_started) TRY_CREATE(apply_params(c));
+	if(with_stats) TRY_CREATE(ensure_ray_stats(c));
 	std::vector<float4> o, d, h;
 	std::vector<RayStats> rs;
 	for(int64_t done = 0; done < n;)
@@ -1132,19 +1037,18 @@ static int trace_rays_impl(adypt_ctx *c, const float *rays, int64_t n, adypt_hit
 			counts[s * kCursorStride] = (uint32_t)n_s;
 			if(n_s <= 0) continue;
 			const size_t off = (size_t)s * c->seg_cap;
-			HIP_TRY(c, hipMemcpyAsync(c->q_o[0] + off, o.data() + b0, (size_t)n_s * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-			HIP_TRY(c, hipMemcpyAsync(c->q_d[0] + off, d.data() + b0, (size_t)n_s * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+			HIP_TRY(c, hipMemcpyAsync(c->q.o[0] + off, o.data() + b0, (size_t)n_s * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+			HIP_TRY(c, hipMemcpyAsync(c->q.d[0] + off, d.data() + b0, (size_t)n_s * sizeof(float4), hipMemcpyHostToDevice, c->stream));
 		}
 		HIP_TRY(c, hipMemcpyAsync(c->d_counters->count[0], counts, sizeof(counts), hipMemcpyHostToDevice, c->stream));
-		int r = launch_trace(c, c->pipes[0], full_window(c), 0, c->d_counters->count[0], c->d_counters->cursor[0], c->params.stack_size, with_stats != 0, with_stats ? c->d_ray_stats : nullptr, any_hit);
-		if(r != ADYPT_OK) return r;
+		TRY_CREATE(launch_trace(c, c->pipes[0], full_window(c), 0, c->d_counters->count[0], c->d_counters->cursor[0], c->params.stack_size, with_stats != 0, with_stats ? c->q.ray_stats : nullptr, any_hit));
 		for(int s = 0; s < kNumSegments; ++s)
 		{
 			const int64_t b0 = std::min<int64_t>(piece * s, m), n_s = std::min<int64_t>(piece, m - b0);
 			if(n_s <= 0) continue;
 			const size_t off = (size_t)s * c->seg_cap;
-			HIP_TRY(c, hipMemcpyAsync(h.data() + b0, c->d_hit + off, (size_t)n_s * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-			if(with_stats) HIP_TRY(c, hipMemcpyAsync(rs.data() + b0, c->d_ray_stats + off, (size_t)n_s * sizeof(RayStats), hipMemcpyDeviceToHost, c->stream));
+			HIP_TRY(c, hipMemcpyAsync(h.data() + b0, c->q.hit + off, (size_t)n_s * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+			if(with_stats) HIP_TRY(c, hipMemcpyAsync(rs.data() + b0, c->q.ray_stats + off, (size_t)n_s * sizeof(RayStats), hipMemcpyDeviceToHost, c->stream));
 		}
 		HIP_TRY(c, hipStreamSynchronize(c->stream));
 		for(int64_t i = 0; i < m; ++i)
@@ -1178,11 +1082,9 @@ int adypt_trace_rays_any(adypt_ctx *c, const float *rays, int64_t n, adypt_hit *
 int adypt_get_stats(adypt_ctx *c, adypt_stats *out)
 {
 	if(!c || !out) return ADYPT_E_INVALID;
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	harvest_events(c);
 	DeviceStats st;
-	HIP_TRY(c, hipMemcpy(&st, c->d_stats, sizeof(st), hipMemcpyDeviceToHost));
+	TRY_CREATE(read_device_stats(c, &st));
+	harvest_events(c);
 	out->rays = st.rays; out->nodes_visited = st.nodes; out->tris_tested = st.tris; out->hits = st.hits; out->shaded = st.shaded;
 	out->stack_overflows = st.overflows; out->bad_materials = st.bad_materials; out->max_stack = st.max_stack;
 	out->trace_launches = c->trace_launches; out->trace_ms = c->trace_ms; out->shade_ms = c->shade_ms;
@@ -1194,10 +1096,8 @@ int adypt_get_stats(adypt_ctx *c, adypt_stats *out)
 int adypt_get_shader_clock(adypt_ctx *c, uint64_t out[2])
 {
 	if(!c || !out) return ADYPT_E_INVALID;
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	DeviceStats st;
-	HIP_TRY(c, hipMemcpy(&st, c->d_stats, sizeof(st), hipMemcpyDeviceToHost));
+	TRY_CREATE(read_device_stats(c, &st));
 	out[0] = st.clock_cycles; out[1] = st.clock_ticks;
 	return ADYPT_OK;
 }
@@ -1205,10 +1105,8 @@ int adypt_get_shader_clock(adypt_ctx *c, uint64_t out[2])
 int adypt_get_wave_profile(adypt_ctx *c, uint64_t out[8])
 {
 	if(!c || !out) return ADYPT_E_INVALID;
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	DeviceStats st;
-	HIP_TRY(c, hipMemcpy(&st, c->d_stats, sizeof(st), hipMemcpyDeviceToHost));
+	TRY_CREATE(read_device_stats(c, &st));
 	for(int i = 0; i < 8; ++i) out[i] = st.wave_profile[i];
 	return ADYPT_OK;
 }
@@ -1216,8 +1114,7 @@ int adypt_get_wave_profile(adypt_ctx *c, uint64_t out[8])
 int adypt_reset_stats(adypt_ctx *c)
 {
 	if(!c) return ADYPT_E_INVALID;
-	HIP_TRY(c, hipSetDevice(c->device));
-	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	ENTER_DRAINED(c);
 	harvest_events(c);
 	// on the context's own stream: a legacy-stream hipMemset is not ordered against a non-blocking stream
 	HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, offsetof(DeviceStats, host_overflow), c->stream));
@@ -1232,7 +1129,7 @@ int64_t adypt_local_pixel_count(const adypt_ctx *c) { return c ? c->n_local_px :
 int adypt_copy_local_radiance(adypt_ctx *c, void *dst, int64_t capacity_float4)
 {
 	if(!c || !dst || capacity_float4 < c->n_local_px) return ADYPT_E_INVALID;
-	HIP_TRY(c, hipSetDevice(c->device));
+	ENTER(c); // (not drained, as adypt_read_display: the copy is enqueued behind the frames)
 	HIP_TRY(c, hipMemcpyAsync(dst, c->d_accum, (size_t)c->n_local_px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
 	if(capacity_float4 > c->n_local_px)
 		HIP_TRY(c, hipMemsetAsync((char *)dst + (size_t)c->n_local_px * sizeof(float4), 0, (size_t)(capacity_float4 - c->n_local_px) * sizeof(float4), c->stream));
@@ -1243,7 +1140,7 @@ int adypt_copy_local_radiance(adypt_ctx *c, void *dst, int64_t capacity_float4)
 int adypt_assemble_radiance(adypt_ctx *c, const void *gathered, int64_t stride_float4, void *rgb_device)
 {
 	if(!c || !gathered || !rgb_device || stride_float4 < 0) return ADYPT_E_INVALID;
-	HIP_TRY(c, hipSetDevice(c->device));
+	ENTER(c);
 	if(!c->d_all_blocks)
 	{
 		// block lists of every rank of the shard, back to back (uploaded once)
@@ -1255,8 +1152,7 @@ int adypt_assemble_radiance(adypt_ctx *c, const void *gathered, int64_t stride_f
 			all.insert(all.end(), b.begin(), b.end());
 			c->all_blocks_offset.push_back((int64_t)all.size());
 		}
-		int rr = upload(c, &c->d_all_blocks, all.data(), all.size());
-		if(rr != ADYPT_OK) return rr;
+		TRY_CREATE(upload(c, &c->d_all_blocks, all.data(), all.size()));
 	}
 	for(int r = 0; r < c->nranks; ++r)
 	{
