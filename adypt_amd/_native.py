@@ -57,6 +57,14 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Noise(C.Structure):
+    _fields_ = [("mean_noise", C.c_double), ("worst_block", C.c_double), ("worst_index", C.c_int32), ("spp", C.c_int32),
+                ("pixels", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class BvhParams(C.Structure):
     _fields_ = [("max_spatial_depth", C.c_int32), ("triangle_sah", C.c_float), ("node_sah", C.c_float)]
 
@@ -115,6 +123,18 @@ _SIGS = {
     "adypt_assemble_radiance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "adypt_shard_block_count": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "adypt_untile_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # noise statistics
+    "adypt_set_noise_stats": (C.c_int, [C.c_void_p, C.c_int]),
+    "adypt_get_noise_stats": (C.c_int, [C.c_void_p]),
+    "adypt_get_noise": (C.c_int, [C.c_void_p, C.POINTER(Noise)]),
+    "adypt_read_noise": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_read_noise_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_read_block_noise": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "adypt_trace_until": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Noise)]),
+    "adypt_multi_set_noise_stats": (C.c_int, [C.c_void_p, C.c_int]),
+    "adypt_multi_get_noise": (C.c_int, [C.c_void_p, C.POINTER(Noise)]),
+    "adypt_multi_read_noise": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_multi_trace_until": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Noise)]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),

@@ -429,6 +429,51 @@ class HipPathTracer:
         N.check(N.lib.adypt_read_radiance(self._ctx, rgb.ctypes.data), self._ctx)
         return rgb
 
+    # ---- noise statistics (adypt_set_noise_stats, include/adypt_hip.h) ----
+    def SetNoiseStats(self, enabled: bool) -> None:
+        """Per-pixel luminance moments next to the running mean; enable at 0 spp.  The image never changes."""
+        N.check(N.lib.adypt_set_noise_stats(self._ctx, 1 if enabled else 0), self._ctx)
+
+    def GetNoiseStats(self) -> bool:
+        return N.lib.adypt_get_noise_stats(self._ctx) == 1
+
+    def GetNoise(self) -> dict:
+        """mean_noise, worst_block, worst_index, spp, pixels of the blocks this context owns (needs >= 2 spp)."""
+        out = N.Noise()
+        N.check(N.lib.adypt_get_noise(self._ctx, C.byref(out)), self._ctx)
+        return out.as_dict()
+
+    def ReadNoise(self) -> np.ndarray:
+        """H x W float32: the relative standard error of every pixel's mean luminance."""
+        e = np.zeros((self.height, self.width), dtype=np.float32)
+        N.check(N.lib.adypt_read_noise(self._ctx, e.ctypes.data), self._ctx)
+        return e
+
+    def ReadNoiseMoments(self) -> np.ndarray:
+        """H x W x 2 float32: (mean, m2) of every pixel's luminance."""
+        m = np.zeros((self.height, self.width, 2), dtype=np.float32)
+        N.check(N.lib.adypt_read_noise_moments(self._ctx, m.ctypes.data), self._ctx)
+        return m
+
+    def ReadBlockNoise(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(block index int32, sum float64, count uint32) of the owned 32x32 blocks, ascending block index."""
+        n = N.lib.adypt_read_block_noise(self._ctx, None, None, None, 0)
+        if n < 0:
+            N.check(int(n), self._ctx)
+        idx, s, cnt = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint32)
+        if n:
+            r = N.lib.adypt_read_block_noise(self._ctx, idx.ctypes.data, s.ctypes.data, cnt.ctypes.data, n)
+            if r < 0:
+                N.check(int(r), self._ctx)
+        return idx, s, cnt
+
+    def TraceUntil(self, target: float, min_spp: int = 16, max_spp: int = 1024, check_every: int = 16) -> dict:
+        """Trace(true) in steps of check_every until worst_block <= target (and spp >= min_spp) or spp >= max_spp; the last GetNoise()."""
+        self.m_viewer_type = ViewerTypes.kPTRadiance
+        out = N.Noise()
+        N.check(N.lib.adypt_trace_until(self._ctx, float(target), min_spp, max_spp, check_every, C.byref(out)), self._ctx)
+        return out.as_dict()
+
     def ReadDisplay(self) -> np.ndarray:
         """What OglPathTracer::DrawScreen puts on screen (shaders/screen.glsl:15-21): H x W x 4 uint8."""
         rgba = np.zeros((self.height, self.width, 4), dtype=np.uint8)
@@ -643,6 +688,53 @@ class MultiPathTracer:
         st = N.Stats()
         self._check(N.lib.adypt_multi_get_stats(self._m, C.byref(st)))
         return st.as_dict()
+
+    # ---- noise statistics of the whole image: the devices' blocks merged on the host (adypt_multi_get_noise) ----
+    def SetNoiseStats(self, enabled: bool) -> None:
+        self._check(N.lib.adypt_multi_set_noise_stats(self._m, 1 if enabled else 0))
+
+    def GetNoiseStats(self) -> bool:
+        return N.lib.adypt_get_noise_stats(self._contexts()[0]) == 1
+
+    def GetNoise(self) -> dict:
+        out = N.Noise()
+        self._check(N.lib.adypt_multi_get_noise(self._m, C.byref(out)))
+        return out.as_dict()
+
+    def ReadNoise(self) -> np.ndarray:
+        e = np.zeros((self.height, self.width), dtype=np.float32)
+        self._check(N.lib.adypt_multi_read_noise(self._m, e.ctypes.data))
+        return e
+
+    def ReadNoiseMoments(self) -> np.ndarray:
+        """Every device writes the pixels of its own tiles."""
+        m = np.zeros((self.height, self.width, 2), dtype=np.float32)
+        for c in self._contexts():
+            N.check(N.lib.adypt_read_noise_moments(c, m.ctypes.data), c)
+        return m
+
+    def ReadBlockNoise(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The devices' blocks merged and sorted by block index."""
+        parts = []
+        for c in self._contexts():
+            n = N.lib.adypt_read_block_noise(c, None, None, None, 0)
+            if n < 0:
+                N.check(int(n), c)
+            idx, s, cnt = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint32)
+            if n:
+                r = N.lib.adypt_read_block_noise(c, idx.ctypes.data, s.ctypes.data, cnt.ctypes.data, n)
+                if r < 0:
+                    N.check(int(r), c)
+            parts.append((idx, s, cnt))
+        idx, s, cnt = (np.concatenate([p[i] for p in parts]) for i in range(3))
+        order = np.argsort(idx, kind="stable")
+        return idx[order], s[order], cnt[order]
+
+    def TraceUntil(self, target: float, min_spp: int = 16, max_spp: int = 1024, check_every: int = 16) -> dict:
+        self.m_viewer_type = ViewerTypes.kPTRadiance
+        out = N.Noise()
+        self._check(N.lib.adypt_multi_trace_until(self._m, float(target), min_spp, max_spp, check_every, C.byref(out)))
+        return out.as_dict()
 
     def ReadDisplay(self) -> np.ndarray:
         """What the reference's window shows (screen.glsl:15-21), H x W x 4 uint8: every device converts its own tiles."""

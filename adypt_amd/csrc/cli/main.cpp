@@ -3,12 +3,15 @@
 //   (src/Tracer/OglPathTracer.cpp:199-212).  The interactive window / ImGui front-end is out of scope.
 //
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
-//             [--device D | --devices D0,D1,...] [--save-every K]
+//             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]]
 //   --sun-visibility: enable the occlusion query the reference has commented out (pathtracer.glsl:132)
 //   --preview: what the reference shows in its window (shaders/screen.glsl), as PNG
 //   --devices: pixel tiles sharded over several GPUs of the node (adypt_create_multi), radiance gathered on the first one
 //   --save-every K: progressive rendering as in the reference's window — the running mean is written to --out (and --preview)
 //                   every K samples; the file on disk is always a complete image of what has converged so far
+//   --noise T: render until the noisiest 32x32 block of the image is at or below T (adypt_trace_until: the relative standard error of the mean
+//              luminance, adypt_hip.h); --spp is then the cap, --min-spp (default 16) the least, and the noise is looked at every --check-every
+//              (default 16) samples.  --noise-out: the per-pixel noise as a grey EXR
 #include "adypt_hip.h"
 #include "adypt_host.h"
 
@@ -27,7 +30,10 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]]\n", argv[0]); return 2; }
+	int min_spp = 16, check_every = 16;
+	double noise_target = -1.0; // < 0: render to a fixed sample count
+	std::string noise_out;
 	int spp = 64, fp16 = 0, primary = -1, sun_visibility = 0, save_every = 0;
 	std::vector<int> devices(1, 0);
 	unsigned seed = 12345;
@@ -59,8 +65,16 @@ int main(int argc, char **argv)
 			if(devices.empty()) { fprintf(stderr, "empty --devices list\n"); return 2; }
 		}
 		else if(a == "--save-every" && i + 1 < argc) save_every = atoi(argv[++i]);
+		else if(a == "--noise" && i + 1 < argc) noise_target = atof(argv[++i]);
+		else if(a == "--min-spp" && i + 1 < argc) min_spp = atoi(argv[++i]);
+		else if(a == "--check-every" && i + 1 < argc) check_every = atoi(argv[++i]);
+		else if(a == "--noise-out" && i + 1 < argc) noise_out = argv[++i];
 		else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
 	}
+	const bool until = noise_target >= 0.0;
+	if(!until && !noise_out.empty()) { fprintf(stderr, "--noise-out needs --noise T\n"); return 2; }
+	if(until && (primary >= 0 || spp < 2 || check_every < 1)) { fprintf(stderr, "--noise needs --spp >= 2, --check-every >= 1 and no --primary\n"); return 2; }
+	if(until) min_spp = std::max(2, std::min(min_spp, spp));
 	adypt_config cfg;
 	adypt_config_default(&cfg);
 	if(adypt_config_load(argv[1], &cfg) != ADYPT_OK) { fprintf(stderr, "[INSTANCE]Err: Invalid instance %s: %s\n", argv[1], adypt_host_last_error()); return 1; }
@@ -110,6 +124,7 @@ int main(int argc, char **argv)
 	if(r == ADYPT_OK) r = many ? adypt_multi_set_camera(multi, cfg.position, ip, iv) : adypt_set_camera(ctx, cfg.position, ip, iv);
 	if(r == ADYPT_OK && sun_visibility) r = many ? adypt_multi_set_sun_visibility(multi, 1, nullptr) : adypt_set_sun_visibility(ctx, 1, nullptr);
 	if(r == ADYPT_OK) r = many ? adypt_multi_set_instrumentation(multi, 1) : adypt_set_instrumentation(ctx, 1);
+	if(r == ADYPT_OK && until) r = many ? adypt_multi_set_noise_stats(multi, 1) : adypt_set_noise_stats(ctx, 1);
 	if(r != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
 
 	std::vector<float> rgb((size_t)cfg.width * cfg.height * 3, 0.0f);
@@ -131,7 +146,31 @@ int main(int argc, char **argv)
 	};
 
 	double t0 = now_ms(), t_save = 0.0;
-	if(primary >= 0) r = many ? adypt_multi_trace_primary(multi, primary) : adypt_trace_primary(ctx, primary);
+	adypt_noise noise;
+	memset(&noise, 0, sizeof(noise));
+	if(until)
+	{
+		// to the noise target, --spp the cap.  With --save-every K the image is written whenever K more samples are in: the call is then capped at
+		// the next multiple of K and taken up again (the noise is looked at every check_every samples from there).
+		for(bool done = false; !done && r == ADYPT_OK;)
+		{
+			const int now = many ? adypt_multi_get_spp(multi) : adypt_get_spp(ctx);
+			const int cap = save_every > 0 ? std::min(spp, std::max(2, (now / save_every + 1) * save_every)) : spp;
+			const int least = std::min(min_spp, cap);
+			r = many ? adypt_multi_trace_until(multi, noise_target, least, cap, check_every, &noise) : adypt_trace_until(ctx, noise_target, least, cap, check_every, &noise);
+			if(r != ADYPT_OK) break;
+			done = noise.spp >= spp || (noise.spp >= min_spp && noise.worst_block <= noise_target);
+			if(!done)
+			{
+				const double ts = now_ms();
+				if(!save()) return 1;
+				t_save += now_ms() - ts;
+				printf("[PT]INFO: %d spp saved to %s\n", noise.spp, out.c_str());
+				fflush(stdout);
+			}
+		}
+	}
+	else if(primary >= 0) r = many ? adypt_multi_trace_primary(multi, primary) : adypt_trace_primary(ctx, primary);
 	else if(save_every <= 0 || save_every >= spp) r = many ? adypt_multi_trace_spp(multi, spp) : adypt_trace_spp(ctx, spp);
 	else
 		for(int done = 0; done < spp && r == ADYPT_OK;)
@@ -158,6 +197,18 @@ int main(int argc, char **argv)
 	if(!save()) return 1;
 	printf("[PT]INFO: Saved image to %s\n", out.c_str());
 	if(!preview.empty()) printf("[PT]INFO: Saved preview to %s\n", preview.c_str());
+	if(until)
+	{
+		if(!noise_out.empty())
+		{
+			std::vector<float> e((size_t)cfg.width * cfg.height, 0.0f), grey((size_t)cfg.width * cfg.height * 3);
+			if((many ? adypt_multi_read_noise(multi, e.data()) : adypt_read_noise(ctx, e.data())) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+			for(size_t i = 0; i < e.size(); ++i) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = e[i];
+			if(adypt_save_exr(noise_out.c_str(), grey.data(), cfg.width, cfg.height, 0) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
+			printf("[PT]INFO: Saved noise to %s\n", noise_out.c_str());
+		}
+		printf("[PT]NOISE: spp %d mean_noise %.9g worst_block %.9g worst_index %d (target %.9g)\n", noise.spp, noise.mean_noise, noise.worst_block, noise.worst_index, noise_target);
+	}
 	if(many) adypt_destroy_multi(multi);
 	else adypt_destroy(ctx);
 	adypt_bvh_free(bvh);

@@ -22,13 +22,14 @@ struct PlanInput {
 	int lookahead, frames_in_flight, tmp_lifetime, max_bounce, pipeline;
 	int single_fused, first_fused, fused_bounces, sun_visibility; // the tunables (tunables.hpp) and adypt_set_sun_visibility
 	int64_t n_local_px;                // > 0: a shard that owns no block never gets here
+	int noise_stats = 0;               // adypt_set_noise_stats: every finished sample is parked and applied by the running-mean kernel, which keeps the moments
 };
 
 struct PassPlan {
 	enum Kind { Rolling, Batch } kind;
 	int m, hand_out;                         // frames [spp, spp + m) are traced by the pass; the first hand_out go into the image now, the others stay parked
 	int first_retrace, n_retrace, n_groups;  // frames with frame % tmpLifetime == 0 re-trace their primary rays: batch index of the first, how many, tmpLifetime groups spanned
-	bool as_batch;                           // finished samples are parked and applied by k_resolve (false: the lone launch-per-bounce frame accumulates by itself)
+	bool as_batch;                           // finished samples are parked and applied by k_resolve (false: the lone launch-per-bounce frame accumulates by itself, unless the noise statistics are on)
 	bool use_cache;                          // bounce 0 starts from the cached primary hits (false: that lone frame re-traces, its k_gen_primary makes camera rays)
 	bool fused_first, fused_bounces;         // bounce 0 is k_shade_first | the bounces after it are one k_path launch
 	bool sun_query, sun_queue;               // sun visibility on: the queries ride in k_shade_first + k_path | go through the query queue after every k_shade
@@ -62,9 +63,11 @@ inline PassPlan plan_pass(const PlanInput &in)
 	// A single frame (no look-ahead, or one frame in flight) runs as a batch of one — camera launch, k_shade_first, k_path, k_resolve: 4 launches
 	// instead of 1 + 2 x maxBounce — whenever a batch would take the one-launch pipeline (ADYPT_SINGLE_FUSED=0: the launch-per-bounce frame)
 	p.kind = (p.m == 1 && in.single_fused && one_launch_ok(in, 1, 1)) ? PassPlan::Rolling : PassPlan::Batch;
-	p.as_batch = p.m > 1 || p.kind == PassPlan::Rolling;
+	// (with the noise statistics on the lone launch-per-bounce frame is a batch of one too: it keeps its launches, its sample goes through k_resolve_noise)
+	const bool lone = p.m == 1 && p.kind != PassPlan::Rolling;
+	p.as_batch = !lone || in.noise_stats != 0;
 	p.use_cache = p.as_batch || !p.n_retrace;
-	p.fused_bounces = p.as_batch && one_launch_ok(in, p.m, p.n_pipes);
+	p.fused_bounces = p.as_batch && !lone && one_launch_ok(in, p.m, p.n_pipes);
 	// batches start every frame from a cached primary hit.  With the sun-visibility query on, k_shade_first only when k_path follows (it traces the
 	// queries k_shade_first emits for the paths that escape at once); else the launch-per-bounce pipeline and its query queue
 	p.fused_first = p.as_batch && in.first_fused && (!in.sun_visibility || p.fused_bounces);

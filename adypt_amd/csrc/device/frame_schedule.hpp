@@ -20,6 +20,15 @@ PassArgs pass_args(const adypt_ctx *c)
 	return a;
 }
 
+// The running-mean kernel over frames [first, first + count) of `f`'s parked samples, on the context's stream: k_resolve, or with the noise
+// statistics on its sibling that keeps the luminance moments as well (noise.hpp)
+void launch_resolve(adypt_ctx *c, const FrameArgs &f, const PassArgs &a, int first, int count)
+{
+	const dim3 grid((c->n_local_px + 255) / 256), block(256);
+	if(c->noise_stats) hipLaunchKernelGGL(k_resolve_noise, grid, block, 0, c->stream, f, a.sc, a.px, c->d_noise_moments.get(), first, count);
+	else hipLaunchKernelGGL(k_resolve, grid, block, 0, c->stream, f, a.sc, a.px, first, count);
+}
+
 // Running-mean step (pathtracer.glsl:224-226) of frames [first, first + count) of the batch last traced (its finished samples
 // are parked in d_done), in frame order; afterwards image 1 holds the primary hits of the tmpLifetime group of the last frame
 // applied — what frame-by-frame tracing leaves there (pathtracer.glsl:121-127).
@@ -31,7 +40,7 @@ int resolve_batch_frames(adypt_ctx *c, int first, int count)
 	fill_frame(c, &f);
 	f.spp = c->batch_spp; f.n_frames = c->batch_frames;
 	hipEvent_t stop = begin_timing(c, 1, c->stream);
-	hipLaunchKernelGGL(k_resolve, dim3((c->n_local_px + 255) / 256), dim3(256), 0, c->stream, f, a.sc, a.px, first, count);
+	launch_resolve(c, f, a, first, count);
 	end_timing(stop, c->stream);
 	HIP_TRY(c, hipGetLastError());
 	const int life = std::max(1, c->params.tmp_lifetime);
@@ -165,7 +174,7 @@ int trace_rolling_frame(adypt_ctx *c, const PassPlan &p, bool more)
 	FrameArgs f;
 	roll_frame_args(c, p, frame, s, &f);
 	hipEvent_t stop = begin_timing(c, 1, c->stream);
-	hipLaunchKernelGGL(k_resolve, dim3((c->n_local_px + 255) / 256), dim3(256), 0, c->stream, f, a.sc, a.px, 0, 1);
+	launch_resolve(c, f, a, 0, 1);
 	end_timing(stop, c->stream);
 	HIP_TRY(c, hipGetLastError());
 	c->roll_frame[s] = -1;
@@ -353,7 +362,7 @@ int start_path_tracing(adypt_ctx *c)
 PlanInput plan_input(const adypt_ctx *c, int remaining)
 {
 	return PlanInput{c->spp, remaining, c->lookahead, c->frames_in_flight, c->params.tmp_lifetime, c->params.max_bounce, c->pipeline,
-	                 c->single_fused, c->first_fused, c->fused_bounces, c->sun_visibility, c->n_local_px};
+	                 c->single_fused, c->first_fused, c->fused_bounces, c->sun_visibility, c->n_local_px, c->noise_stats};
 }
 
 }  // namespace

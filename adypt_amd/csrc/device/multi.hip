@@ -13,6 +13,8 @@
 #include "resources.hpp"
 #include "host_transport.hpp"
 #include "tunables.hpp"
+#include "tile_layout.hpp"
+#include "noise.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
 
@@ -420,6 +422,63 @@ int adypt_multi_trace_spp(adypt_multi *m, int n_spp)
 {
 	FOR_ALL(m, adypt_trace_spp_async(c, n_spp)); // every device has its frames enqueued before the first one is waited for
 	FOR_ALL(m, adypt_wait(c));
+	return ADYPT_OK;
+}
+
+int adypt_multi_set_noise_stats(adypt_multi *m, int enabled) { FOR_ALL(m, adypt_set_noise_stats(c, enabled)); return ADYPT_OK; }
+// every context writes the pixels of its own tiles
+int adypt_multi_read_noise(adypt_multi *m, float *e) { if(!e) return ADYPT_E_INVALID; FOR_ALL(m, adypt_read_noise(c, e)); return ADYPT_OK; }
+
+// the devices' block results merged by block index (every block has one owner), then the image formulas of noise.hpp: the one-device numbers
+int adypt_multi_get_noise(adypt_multi *m, adypt_noise *out)
+{
+	if(!m || !out || m->ctx.empty()) return ADYPT_E_INVALID;
+	const CtxInfo info = ctx_info(m->ctx[0]);
+	const size_t n_blocks = (size_t)((info.width + kBlockDim - 1) / kBlockDim) * (size_t)((info.height + kBlockDim - 1) / kBlockDim);
+	std::vector<int32_t> index(n_blocks), idx;
+	std::vector<double> sum(n_blocks, 0.0), s;
+	std::vector<uint32_t> count(n_blocks, 0u), cnt;
+	for(size_t i = 0; i < n_blocks; ++i) index[i] = (int32_t)i;
+	int64_t pixels = 0;
+	for(adypt_ctx *c : m->ctx)
+	{
+		int64_t n = adypt_read_block_noise(c, nullptr, nullptr, nullptr, 0);
+		if(n < 0) return mfail_ctx(m, (int)n, c);
+		if(n == 0) continue; // a shard that owns no block
+		idx.resize((size_t)n); s.resize((size_t)n); cnt.resize((size_t)n);
+		n = adypt_read_block_noise(c, idx.data(), s.data(), cnt.data(), n);
+		if(n < 0) return mfail_ctx(m, (int)n, c);
+		for(int64_t i = 0; i < n; ++i)
+		{
+			if(idx[(size_t)i] < 0 || (size_t)idx[(size_t)i] >= n_blocks) return mfail(m, ADYPT_E_STATE, "adypt_multi_get_noise: block index out of range");
+			sum[(size_t)idx[(size_t)i]] = s[(size_t)i]; count[(size_t)idx[(size_t)i]] = cnt[(size_t)i];
+			pixels += cnt[(size_t)i];
+		}
+	}
+	const NoiseImage img = noise_of_image(index.data(), sum.data(), count.data(), n_blocks, pixels);
+	out->mean_noise = img.mean_noise; out->worst_block = img.worst_block; out->worst_index = img.worst_index;
+	out->spp = adypt_get_spp(m->ctx[0]); out->pixels = pixels;
+	return ADYPT_OK;
+}
+
+int adypt_multi_trace_until(adypt_multi *m, double target, int min_spp, int max_spp, int check_every, adypt_noise *out)
+{
+	if(!m || m->ctx.empty()) return ADYPT_E_INVALID;
+	if(adypt_get_noise_stats(m->ctx[0]) != 1) return mfail(m, ADYPT_E_STATE, "adypt_multi_trace_until: the noise statistics are off (adypt_multi_set_noise_stats)");
+	if(check_every < 1 || min_spp < 2 || max_spp < min_spp || !(target == target)) return mfail(m, ADYPT_E_INVALID, "adypt_multi_trace_until: needs check_every >= 1, 2 <= min_spp <= max_spp and a target that is a number");
+	adypt_noise last;
+	memset(&last, 0, sizeof(last));
+	for(;;) // (adypt_trace_until's loop over all devices)
+	{
+		const int spp = adypt_multi_get_spp(m), n = std::min(check_every, max_spp - spp);
+		int r = n > 0 ? adypt_multi_trace_spp(m, n) : ADYPT_OK;
+		if(r != ADYPT_OK) return r;
+		const int now = adypt_multi_get_spp(m);
+		if(now >= 2 && (r = adypt_multi_get_noise(m, &last)) != ADYPT_OK) return r;
+		if(n <= 0 || now >= max_spp || (now >= min_spp && last.worst_block <= target)) break;
+	}
+	last.spp = adypt_multi_get_spp(m);
+	if(out) *out = last;
 	return ADYPT_OK;
 }
 

@@ -28,6 +28,7 @@
 #pragma once
 #include "canon_math.hpp"
 #include "tile_layout.hpp"
+#include "noise.hpp"
 
 namespace adypt {
 
@@ -306,6 +307,27 @@ __global__ __launch_bounds__(256) void k_resolve(FrameArgs f, SceneArgs sc, Pixe
 		acc = make_float4(fmaf(acc.x, fs, r.x) / fs1, fmaf(acc.y, fs, r.y) / fs1, fmaf(acc.z, fs, r.z) / fs1, 1.0f);
 	}
 	px.accum[L] = acc;
+}
+
+// k_resolve with the noise statistics on (adypt_set_noise_stats): the same running mean, and the luminance moments of noise.hpp carried through
+// the same loop — every clamped sample passes here exactly once, in frame order.  The frame with global index 0 starts the moments from zero:
+// they are cleared where the image is, without a memset.
+__global__ __launch_bounds__(256) void k_resolve_noise(FrameArgs f, SceneArgs sc, PixelArgs px, NoiseMoments *moments, int first, int count)
+{
+	const int L = blockIdx.x * blockDim.x + threadIdx.x;
+	int x, y;
+	if(L >= f.n_local_px || !local_pixel_xy(f, sc.local_blocks, L, &x, &y)) return;
+	float4 acc = px.accum[L];
+	NoiseMoments m = f.spp + first == 0 ? NoiseMoments{0.0f, 0.0f} : moments[L];
+	for(int k = first; k < first + count; ++k)
+	{
+		const float4 r = f.done[(size_t)k * f.n_local_px + L];
+		const float fs = (float)(f.spp + k), fs1 = (float)(f.spp + k + 1);
+		acc = make_float4(fmaf(acc.x, fs, r.x) / fs1, fmaf(acc.y, fs, r.y) / fs1, fmaf(acc.z, fs, r.z) / fs1, 1.0f);
+		m = noise_add_sample(m, f.spp + k, r.x, r.y, r.z);
+	}
+	px.accum[L] = acc;
+	moments[L] = m;
 }
 
 __device__ __forceinline__ int pos_mod(int a, int n) { int r = a % n; return r < 0 ? r + n : r; }
@@ -817,6 +839,45 @@ __global__ void k_untile(const float4 *local, const int32_t *local_blocks, int n
 	const float4 v = local[L];
 	float *o = rgb + ((size_t)y * width + x) * 3;
 	o[0] = v.x; o[1] = v.y; o[2] = v.z;
+}
+
+// The noise of every owned block after `spp` >= 2 frames (noise.hpp): one workgroup of 256 threads per block, thread t takes the block's pixels
+// t, t + 256, t + 512, t + 768 in that order; the sums (binary64) are added across the lanes of a wave by a butterfly, then across the four
+// waves in wave order by thread 0 — a fixed order, so two runs give the same bits.  Pixels outside the image count for nothing.
+// `e_out` (may be null): the per-pixel noise, one float per local pixel, 0 outside the image.
+__global__ __launch_bounds__(256) void k_noise_blocks(const NoiseMoments *moments, const int32_t *local_blocks, int blocks_x, int width, int height, int spp,
+                                                      NoiseBlock *out, float *e_out)
+{
+	__shared__ double wave_sum[4];
+	__shared__ uint32_t wave_count[4];
+	const int blk = local_blocks[blockIdx.x];
+	double sum = 0.0;
+	uint32_t count = 0;
+#pragma unroll
+	for(int j = 0; j < kBlockPixels / 256; ++j)
+	{
+		const int in = j * 256 + (int)threadIdx.x;
+		const size_t L = (size_t)blockIdx.x * kBlockPixels + in;
+		int x, y;
+		block_pixel_xy(blk, in, blocks_x, &x, &y);
+		const bool inside = x < width && y < height;
+		const float e = inside ? noise_of_pixel(moments[L], spp) : 0.0f;
+		if(inside) { sum += (double)e; ++count; }
+		if(e_out) e_out[L] = e;
+	}
+#pragma unroll
+	for(int d = 1; d < 64; d <<= 1) { sum += __shfl_xor(sum, d); count += __shfl_xor(count, d); }
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	if(lane == 0) { wave_sum[wave] = sum; wave_count[wave] = count; }
+	__syncthreads();
+	if(threadIdx.x == 0)
+	{
+		NoiseBlock b;
+		b.sum = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+		b.count = ((wave_count[0] + wave_count[1]) + wave_count[2]) + wave_count[3];
+		b.pad = 0u;
+		out[blockIdx.x] = b;
+	}
 }
 
 }  // namespace adypt

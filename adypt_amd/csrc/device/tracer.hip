@@ -1006,6 +1006,154 @@ int adypt_read_hits(adypt_ctx *c, int32_t *tri, float *uv)
 	return ADYPT_OK;
 }
 
+// ---- noise statistics (noise.hpp) ----
+
+int adypt_set_noise_stats(adypt_ctx *c, int enabled)
+{
+	if(!c) return ADYPT_E_INVALID;
+	if((enabled != 0) == (c->noise_stats != 0)) return ADYPT_OK;
+	if(enabled && c->spp != 0) return fail(c, ADYPT_E_STATE, "adypt_set_noise_stats: the moments start with the image: enable at 0 spp (after adypt_create, adypt_reset or adypt_trace_primary)");
+	ENTER_DRAINED(c); // (the running-mean kernels enqueued so far have left the moments)
+	if(!enabled)
+	{
+		c->noise_stats = 0;
+		c->d_noise_moments.release(); c->d_noise_blocks.release(); c->d_noise_e.release();
+		return ADYPT_OK;
+	}
+	if(c->n_local_px > 0)
+	{
+		const hipError_t e1 = c->d_noise_moments.alloc((size_t)c->n_local_px * sizeof(NoiseMoments));
+		const hipError_t e2 = e1 == hipSuccess ? c->d_noise_blocks.alloc((size_t)c->n_local_blocks * sizeof(NoiseBlock)) : e1;
+		if(e2 != hipSuccess)
+		{
+			c->d_noise_moments.release(); c->d_noise_blocks.release();
+			(void)hipGetLastError();
+			return fail(c, e2 == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP, std::string("adypt_set_noise_stats: ") + hipGetErrorString(e2));
+		}
+	}
+	c->noise_stats = 1;
+	return ADYPT_OK;
+}
+
+int adypt_get_noise_stats(const adypt_ctx *c) { return c ? c->noise_stats : ADYPT_E_INVALID; }
+
+}  // extern "C"
+
+namespace {
+
+int noise_ready(adypt_ctx *c, const char *who, int min_spp)
+{
+	if(!c->noise_stats) return fail(c, ADYPT_E_STATE, std::string(who) + ": the noise statistics are off (adypt_set_noise_stats)");
+	if(c->spp < min_spp) return fail(c, ADYPT_E_STATE, std::string(who) + ": needs at least " + std::to_string(min_spp) + " spp");
+	return ADYPT_OK;
+}
+
+// k_noise_blocks behind the pending running-mean kernels on the context's stream; the block results on the host when the call returns.
+// per_pixel: the per-pixel noise is left in d_noise_e as well.  n_local_px > 0.
+int query_noise_blocks(adypt_ctx *c, std::vector<NoiseBlock> *blocks, bool per_pixel)
+{
+	if(per_pixel && !c->d_noise_e) HIP_TRY(c, c->d_noise_e.alloc((size_t)c->n_local_px * sizeof(float))); // once: the size never changes
+	hipLaunchKernelGGL(k_noise_blocks, dim3((unsigned)c->n_local_blocks), dim3(256), 0, c->stream, (const NoiseMoments *)c->d_noise_moments, (const int32_t *)c->d_local_blocks,
+	                   c->blocks_x, c->width, c->height, c->spp, c->d_noise_blocks.get(), per_pixel ? c->d_noise_e.get() : nullptr);
+	HIP_TRY(c, hipGetLastError());
+	blocks->resize((size_t)c->n_local_blocks);
+	HIP_TRY(c, hipMemcpyAsync(blocks->data(), c->d_noise_blocks, blocks->size() * sizeof(NoiseBlock), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	return ADYPT_OK;
+}
+
+// scatters an array of `per_px` floats per local pixel into the W x H image of the same
+int read_local_floats(adypt_ctx *c, const float *device, int per_px, float *image)
+{
+	std::vector<float> local((size_t)c->n_local_px * per_px);
+	HIP_TRY(c, hipMemcpyAsync(local.data(), device, local.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	for_each_local_pixel(c->local_blocks, c->width, c->height, [&](size_t L, int x, int y) {
+		memcpy(image + ((size_t)y * c->width + x) * per_px, &local[L * per_px], sizeof(float) * per_px);
+	});
+	return ADYPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int adypt_get_noise(adypt_ctx *c, adypt_noise *out)
+{
+	if(!c || !out) return ADYPT_E_INVALID;
+	TRY_CREATE(noise_ready(c, "adypt_get_noise", 2));
+	memset(out, 0, sizeof(*out));
+	out->spp = c->spp;
+	if(c->n_local_px == 0) return ADYPT_OK; // a shard that owns no block
+	ENTER(c); // (not drained: the query is enqueued behind the frames)
+	std::vector<NoiseBlock> blocks;
+	TRY_CREATE(query_noise_blocks(c, &blocks, false));
+	std::vector<double> sum(blocks.size());
+	std::vector<uint32_t> count(blocks.size());
+	for(size_t i = 0; i < blocks.size(); ++i) { sum[i] = blocks[i].sum; count[i] = blocks[i].count; }
+	const NoiseImage img = noise_of_image(c->local_blocks.data(), sum.data(), count.data(), blocks.size(), c->n_image_px);
+	out->mean_noise = img.mean_noise; out->worst_block = img.worst_block; out->worst_index = img.worst_index; out->pixels = c->n_image_px;
+	return ADYPT_OK;
+}
+
+int adypt_read_noise(adypt_ctx *c, float *e)
+{
+	if(!c || !e) return ADYPT_E_INVALID;
+	TRY_CREATE(noise_ready(c, "adypt_read_noise", 2));
+	if(c->n_local_px == 0) return ADYPT_OK;
+	ENTER(c);
+	std::vector<NoiseBlock> blocks;
+	TRY_CREATE(query_noise_blocks(c, &blocks, true));
+	return read_local_floats(c, c->d_noise_e, 1, e);
+}
+
+int adypt_read_noise_moments(adypt_ctx *c, float *mean_m2)
+{
+	if(!c || !mean_m2) return ADYPT_E_INVALID;
+	TRY_CREATE(noise_ready(c, "adypt_read_noise_moments", 0));
+	if(c->n_local_px == 0) return ADYPT_OK;
+	if(c->spp == 0) // nothing accumulated yet: the state of a cleared image
+	{
+		for_each_local_pixel(c->local_blocks, c->width, c->height, [&](size_t, int x, int y) { float *o = mean_m2 + ((size_t)y * c->width + x) * 2; o[0] = o[1] = 0.0f; });
+		return ADYPT_OK;
+	}
+	ENTER(c);
+	return read_local_floats(c, (const float *)c->d_noise_moments.get(), 2, mean_m2);
+}
+
+int64_t adypt_read_block_noise(adypt_ctx *c, int32_t *block_index, double *sum, uint32_t *count, int64_t capacity)
+{
+	if(!c || capacity < 0) return ADYPT_E_INVALID;
+	TRY_CREATE(noise_ready(c, "adypt_read_block_noise", 2));
+	const int64_t n = c->n_local_blocks;
+	if(n == 0 || capacity < n) return n; // (the size alone: nothing is written)
+	if(!block_index || !sum || !count) return ADYPT_E_INVALID;
+	ENTER(c);
+	std::vector<NoiseBlock> blocks;
+	TRY_CREATE(query_noise_blocks(c, &blocks, false));
+	for(int64_t i = 0; i < n; ++i) { block_index[i] = c->local_blocks[(size_t)i]; sum[i] = blocks[(size_t)i].sum; count[i] = blocks[(size_t)i].count; }
+	return n;
+}
+
+int adypt_trace_until(adypt_ctx *c, double target, int min_spp, int max_spp, int check_every, adypt_noise *out)
+{
+	if(!c) return ADYPT_E_INVALID;
+	if(!c->noise_stats) return fail(c, ADYPT_E_STATE, "adypt_trace_until: the noise statistics are off (adypt_set_noise_stats)");
+	if(check_every < 1 || min_spp < 2 || max_spp < min_spp || !(target == target)) return fail(c, ADYPT_E_INVALID, "adypt_trace_until: needs check_every >= 1, 2 <= min_spp <= max_spp and a target that is a number");
+	adypt_noise last;
+	memset(&last, 0, sizeof(last));
+	for(;;)
+	{
+		const int n = std::min(check_every, max_spp - c->spp);
+		if(n > 0) TRY_CREATE(adypt_trace_spp(c, n));
+		if(c->spp >= 2) TRY_CREATE(adypt_get_noise(c, &last));
+		if(n <= 0 || c->spp >= max_spp || (c->spp >= min_spp && last.worst_block <= target)) break;
+	}
+	last.spp = c->spp;
+	if(out) *out = last;
+	return ADYPT_OK;
+}
+
 static int trace_rays_impl(adypt_ctx *c, const float *rays, int64_t n, adypt_hit *hits, int with_stats, bool any_hit)
 {
 	if(!c || n < 0 || (n > 0 && (!rays || !hits))) return ADYPT_E_INVALID;

@@ -204,6 +204,43 @@ int adypt_read_display(adypt_ctx *ctx, uint8_t *rgba8);
 /* content of image 1 (uPrimaryTmpImg, pathtracer.glsl:114-127): scene triangle id and uv of the cached primary hit */
 int adypt_read_hits(adypt_ctx *ctx, int32_t *tri, float *uv);
 
+/* ---- noise statistics: how converged the accumulated image is, and tracing until it is converged enough ----------------------
+ * Off by default; with it off nothing changes (same kernels, same memory, same images).  The definition is pinned bit for bit in
+ * csrc/device/noise.hpp: per pixel, the luminance Y = (0.2126 r + 0.7152 g) + 0.0722 b of every clamped sample is folded in frame order into
+ * (mean, m2) by Welford's update, in binary32 without fma; after n >= 2 frames the pixel's noise is e = sqrt(m2 / (n (n - 1))) / (mean + 0.01),
+ * the relative standard error of its mean luminance.  A 32x32 block's noise is the binary64 sum of e over its pixels inside the image and their
+ * count; mean_noise = (sum of the block sums, ascending block index) / pixels, worst_block = the largest sum / count, worst_index = that block's
+ * index by * blocks_x + bx (the lowest on a tie).  The moments live and die with the accumulated image: they restart with the first path-traced
+ * frame after adypt_create / adypt_reset / adypt_trace_primary and survive a camera change like the image does.  They follow the frames handed
+ * out (adypt_get_spp), not the frames traced ahead.  The statistics never change the image. */
+typedef struct adypt_noise {
+	double mean_noise, worst_block;
+	int32_t worst_index, spp;    /* spp: the frames the numbers are of */
+	int64_t pixels;              /* pixels covered = those of the owned blocks that lie inside the image; 0: the context owns no block, all numbers 0 */
+} adypt_noise;
+/* Switches the statistics on (allocates 8 bytes per local pixel + 16 per owned block) or off (gives them back).  Enabling needs adypt_get_spp() == 0
+ * (after adypt_create / adypt_reset / adypt_trace_primary: the moments start with the image), else ADYPT_E_STATE; disabling is always allowed.
+ * While on, the running-mean kernel keeps the moments too (measured cost: DESIGN.md), and a single frame that would have run launch by launch and
+ * accumulated by itself parks its sample for that kernel like every other frame. */
+int adypt_set_noise_stats(adypt_ctx *ctx, int enabled);
+int adypt_get_noise_stats(const adypt_ctx *ctx);
+/* The image's numbers over the blocks this context owns (a tile shard: its own blocks only — one process per GPU (adypt_comm_*) has no merged
+ * variant; a launcher combines the ranks' adypt_read_block_noise itself with the formulas above).  ADYPT_E_STATE when off or below 2 spp.
+ * One small kernel behind the frames on the context's stream; two queries in a row return identical bits. */
+int adypt_get_noise(adypt_ctx *ctx, adypt_noise *out);
+/* the per-pixel noise e: W*H floats, row 0 = top; pixels of blocks this context does not own are left untouched.  ADYPT_E_STATE as above */
+int adypt_read_noise(adypt_ctx *ctx, float *e);
+/* the per-pixel moments (mean, m2): W*H*2 floats, same convention (zeros at 0 spp).  ADYPT_E_STATE when off */
+int adypt_read_noise_moments(adypt_ctx *ctx, float *mean_m2);
+/* The owned blocks' results, ascending block index.  Returns the number of owned blocks (negative: ADYPT_E_*; ADYPT_E_STATE as adypt_get_noise);
+ * the arrays are written only when capacity holds them all (capacity 0: the size alone). */
+int64_t adypt_read_block_noise(adypt_ctx *ctx, int32_t *block_index, double *sum, uint32_t *count, int64_t capacity);
+/* Continues the accumulation from the current spp until the image is converged enough: traces min(check_every, max_spp - spp) frames
+ * (adypt_trace_spp), queries, and stops when spp >= min_spp and worst_block <= target, or when spp >= max_spp.  *out (may be NULL) = the last
+ * query.  Needs the statistics on (ADYPT_E_STATE), check_every >= 1 and 2 <= min_spp <= max_spp (ADYPT_E_INVALID).  The image afterwards is
+ * bit-identical to adypt_trace_spp to the same adypt_get_spp, with look-ahead on or off and any frames in flight. */
+int adypt_trace_until(adypt_ctx *ctx, double target, int min_spp, int max_spp, int check_every, adypt_noise *out);
+
 /* Trace an arbitrary batch of rays through the same traversal kernel: rays = n x 8 floats
  * (ox, oy, oz, tmin, dx, dy, dz, unused).  with_stats selects the instrumented kernel variant. */
 int adypt_trace_rays(adypt_ctx *ctx, const float *rays, int64_t n, adypt_hit *hits, int with_stats);
@@ -287,6 +324,12 @@ int adypt_multi_read_radiance(adypt_multi *m, float *rgb);
  * default 120, 0 = unbounded) a watchdog thread prints where it stands and the state of every rank's stream to stderr and ENDS THE PROCESS with
  * exit code 86 — a collective whose peer never arrives cannot be cancelled, and a process that has touched the GPU must not be re-executed. */
 int adypt_multi_gather_radiance(adypt_multi *m, void **rgb_device);
+/* The noise statistics of the whole image (see adypt_set_noise_stats): every block is owned by exactly one device; the host merges the devices'
+ * block results by block index and applies the same formulas, so the numbers equal the one-device ones bit for bit.  No collective. */
+int adypt_multi_set_noise_stats(adypt_multi *m, int enabled);
+int adypt_multi_get_noise(adypt_multi *m, adypt_noise *out);
+int adypt_multi_read_noise(adypt_multi *m, float *e);     /* every device writes the pixels of its own tiles */
+int adypt_multi_trace_until(adypt_multi *m, double target, int min_spp, int max_spp, int check_every, adypt_noise *out);
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

@@ -164,6 +164,21 @@ public:
 
 	int GetSPP() const { return adypt_multi_get_spp(m_gpus); }
 
+	// Noise statistics (adypt_hip.h, adypt_set_noise_stats): how converged the image is, and tracing until it is converged enough.
+	// Switch them on while the sample counter is 0 (after Initialize, or after a Trace(false)); the image itself never changes.
+	bool SetNoiseStats(bool enabled) { return adypt_multi_set_noise_stats(m_gpus, enabled ? 1 : 0) == ADYPT_OK; }
+	// mean_noise / worst_block / worst_index of the whole image after GetSPP() >= 2 samples
+	bool GetNoise(adypt_noise *out) const { return adypt_multi_get_noise(m_gpus, out) == ADYPT_OK; }
+	// Trace(true) in steps of check_every until the noisiest 32x32 block is at or below `target` (and min_spp samples are in), or max_spp is reached
+	bool TraceUntil(double target, int min_spp, int max_spp, int check_every, adypt_noise *out = nullptr)
+	{
+		if(adypt_multi_get_spp(m_gpus) == 0) update_config_args();
+		m_viewer_type = kPTRadiance;
+		if(adypt_multi_trace_until(m_gpus, target, min_spp, max_spp, check_every, out) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
 	// what DrawScreen puts on screen, for a caller-owned W x H RGBA8 texture / window (every device fills in its own tiles)
 	bool ReadScreen(std::vector<uint8_t> *rgba8) const
 	{
