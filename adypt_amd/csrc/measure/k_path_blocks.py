@@ -8,9 +8,8 @@ Three counting passes (twelve counters each: ADYPT_BLOCKS_SET = trip | shade | r
 inside the trip A_pop (A_pop_spill) A_choose A_push (A_push_spill) B_tri_load B_node_load C_woop D_slab E_flush; inside a shading round S_parked S_miss S_surface
 (S_textured S_glossy S_diffuse S_mirror S_dielectric) S_dead S_alive S_replace S_early S_fetch_more S_defer (a round moves glossy / dielectric hits to the deferred ring); inside the exchange X_pick | X_take (its two exclusive branches: a round follows, or rays are taken); anywhere div_slow (the division sequence behind rcp_ieee's
 range test), F_try (one try of fetch_rays at one queue segment) and X_lock_spin.  What lies inside a block but outside its sub-blocks runs whenever the block does."""
-import sys
-d = sys.argv[1]
-import os
+import os, sys
+from _variant import edit
 COUNT = os.environ.get("ADYPT_BLOCKS_COUNT", "0") != "0"   # 0: marks only (static counts: tools/trip_budget.py); 1: marks + entry counters (tools/path_block_counts.py)
 SET = os.environ.get("ADYPT_BLOCKS_SET", "trip")           # which twelve blocks get the counters (every mark is always inserted): trip | shade | rare
 SETS = {"trip": ["setup", "exchange", "shade", "trip", "A_pop", "A_choose", "A_push", "B_tri_load", "B_node_load", "C_woop", "D_slab", "E_flush"],
@@ -28,15 +27,6 @@ NAMES = SETS_LANES[SET] if LANES else SETS[SET]
 # Counters: a value that is modified inside a divergent block cannot live in an SGPR the compiler allocates (the merge after the block is per lane).
 # So k_path is held to 96 SGPRs (amdgpu_num_sgpr) and the counters live in s96 .. s101, touched only by inline assembly: two 16-bit counters per
 # register (a wave makes < 65536 trips per launch at the batch sizes measured).
-
-
-def edit(name, pairs):
-    p = d + "/" + name
-    s = open(p).read()
-    for old, new in pairs:
-        assert s.count(old) == 1, (name, s.count(old), old[:70])
-        s = s.replace(old, new)
-    open(p, "w").write(s)
 
 
 def enter(n):  # the counter of block n goes up once per wave that enters the block (SALU: not a vector instruction, blind to the exec mask)
@@ -83,12 +73,11 @@ if LANES and SET == "wait":
         ("			if(tg_y != 0)\n			{\n				" if False else "				// more triangles of this node: next trip (the pending node is fetched in the trip that consumes the last of them)\n", "				" + enter("W_wait") + "\n"),
         ("			const bool do_test = (uint32_t)lane < n_tests;", "			if(!active) { " + enter("W_idle") + " }\n			if(tg1 != 0) { " + enter("W_two") + " }\n			if(tg2 != 0) { " + enter("W_three") + " }\n			if(tg3 != 0) { " + enter("W_four") + " }\n			const bool do_test = (uint32_t)lane < n_tests;"),
     ]
-edit("traverse_trip.inc", TRIP_EDITS)
 # (fetch_rays' loop over the 8 queue segments is unrolled: 8 equal instances of the block, one counter = tries in all)
-edit("traverse.hpp", [("		if((seg_done >> s) & 1u) continue;\n		const uint32_t seg_len = (uint32_t)__builtin_amdgcn_readlane((int)seg_len_lanes, s);",
+TRAVERSE = [("		if((seg_done >> s) & 1u) continue;\n		const uint32_t seg_len = (uint32_t)__builtin_amdgcn_readlane((int)seg_len_lanes, s);",
                        "		if((seg_done >> s) & 1u) continue;\n		" + enter("F_try") + "\n		const uint32_t seg_len = (uint32_t)__builtin_amdgcn_readlane((int)seg_len_lanes, s);"),
-                      ("		seg_done |= 1u << s;\n	}\n	*left = 0;", "		seg_done |= 1u << s;\n		" + leave("F_try") + "\n	}\n	*left = 0;")])
-edit("canon_math.hpp", [("	return 1.0f / x;\n}", "	" + enter("div_slow") + "\n	const float q_slow = 1.0f / x;\n	" + leave("div_slow") + "\n	return q_slow;\n}")])
+                      ("		seg_done |= 1u << s;\n	}\n	*left = 0;", "		seg_done |= 1u << s;\n		" + leave("F_try") + "\n	}\n	*left = 0;")]
+CANON_MATH = [("	return 1.0f / x;\n}", "	" + enter("div_slow") + "\n	const float q_slow = 1.0f / x;\n	" + leave("div_slow") + "\n	return q_slow;\n}")]
 # (k_trace includes the trip too: it gets a dummy counter array)
 zero = " ".join('asm volatile("s_mov_b32 s%d, 0" ::: "s%d");' % (r, r) for r in range(96, 102))
 read = " ".join('asm volatile("s_mov_b32 %%0, s%d" : "=s"(bc[%d]));' % (96 + i, i) for i in range(6))
@@ -119,8 +108,7 @@ SHADE_HPP = [
     ("		else if(illum == 6 || illum == 7)\n		{\n			float eta = ior;", "		else if(illum == 6 || illum == 7)\n		{\n			" + enter("S_dielectric") + "\n			float eta = ior;"),
     ("			else dir = reflect3(dir, normal);\n		}\n	}\n	return alive;", "			else dir = reflect3(dir, normal);\n			" + leave("S_dielectric") + "\n		}\n	}\n	return alive;"),
 ]
-edit("shade.hpp", SHADE_HPP)
-pairs = SHADE_PATH + [
+PATH = SHADE_PATH + [
     ("						if(early && lane == 0) rel = atomicAdd(&a.cursor[cur], n_sure);", "						if(early && lane == 0) { " + enter("S_early") + " rel = atomicAdd(&a.cursor[cur], n_sure); " + leave("S_early") + " }"),
     ("						while(served < n_dead) // (wave-uniform) the rest: paths that ended unexpectedly, or the home segment has run out\n						{", "						while(served < n_dead) // (wave-uniform) the rest: paths that ended unexpectedly, or the home segment has run out\n						{\n							" + enter("S_fetch_more")),
     ("							served += gn;\n						}", "							served += gn;\n							" + leave("S_fetch_more") + "\n						}"),
@@ -139,11 +127,14 @@ pairs = SHADE_PATH + [
     ('				asm volatile("; ADYPT_MARK exchange_end");', "				" + leave("exchange")),
 ]
 if COUNT:
-    pairs += [
+    PATH += [
         ("template <bool STATS, bool SUN>\n__global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) void k_path(PathKernArgs K)\n{",
          "template <bool STATS, bool SUN>\n__global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) __attribute__((amdgpu_num_sgpr(96))) void k_path(PathKernArgs K)\n{\n	" + zero),
         ("	// ---------------- totals: per wave -> per workgroup (LDS) -> one device atomic per workgroup ----------------",
          "	{ uint32_t bc[6]; " + read + "\n	if(lane == 0) for(int i = 0; i < 6; ++i) atomicAdd(&a.stats->wave_profile[i], " + ("(unsigned long long)bc[i]" if LANES else "(((unsigned long long)(bc[i] >> 16)) << 32) | (unsigned long long)(bc[i] & 0xffffu)") + "); } // (k_path<false> leaves wave_profile alone)\n"
          "	// ---------------- totals: per wave -> per workgroup (LDS) -> one device atomic per workgroup ----------------"),
     ]
-edit("path.hpp", pairs)
+
+if __name__ == "__main__":
+    for file, pairs in (("traverse_trip.inc", TRIP_EDITS), ("traverse.hpp", TRAVERSE), ("canon_math.hpp", CANON_MATH), ("shade.hpp", SHADE_HPP), ("path.hpp", PATH)):
+        edit(sys.argv[1], file, pairs)

@@ -3,9 +3,9 @@ Render()'s illum switch drop out of the shading code.  An upper bound on what so
 shading round of 64 mixed paths executes every branch some lane needs.
     tools/build_variant.sh oneclass --transform adypt_amd/csrc/measure/k_path_one_material_class.py"""
 import sys
-p = sys.argv[1] + "/shade.hpp"
-s = open(p).read()
-old = "\tconst int illum0 = si.illum0;\n\tconst float shininess = si.shininess, ior = si.ior;\n"
-assert s.count(old) == 1
-s = s.replace(old, "\tconst int illum0 = 1; (void)si.illum0;\n\tconst float shininess = si.shininess, ior = si.ior;\n")
-open(p, "w").write(s)
+from _variant import edit
+OLD = "\tconst int illum0 = si.illum0;\n\tconst float shininess = si.shininess, ior = si.ior;\n"
+NEW = "\tconst int illum0 = 1; (void)si.illum0;\n\tconst float shininess = si.shininess, ior = si.ior;\n"
+
+if __name__ == "__main__":
+    edit(sys.argv[1], "shade.hpp", [(OLD, NEW)])

@@ -3,20 +3,12 @@ dry?  Histogram in DeviceStats::wave_profile: bucket i (16 buckets of 100 us, tw
 after the first wave found the queue dry; workgroups that end before that count in bucket 0.  tools/path_tail_hist.py prints it.
     tools/build_variant.sh tailhist --transform adypt_amd/csrc/measure/k_path_tail_hist.py"""
 import sys
-p = sys.argv[1] + "/path.hpp"
-s = open(p).read()
-
-
-def rep(old, new):
-    global s
-    assert s.count(old) == 1, (s.count(old), old[:80])
-    s = s.replace(old, new)
-
-
-rep("""							if(gn == 0) break;
+from _variant import edit
+PATH = [
+    ("""							if(gn == 0) break;
 							if(dead && dead_rank >= served""", """							if(gn == 0) { if(lane == 0) atomicCAS(&a.stats->path_nodes, 0ull, (unsigned long long)__builtin_amdgcn_s_memrealtime()); break; }
-							if(dead && dead_rank >= served""")
-rep("""	if(threadIdx.x == 0)
+							if(dead && dead_rank >= served"""),
+    ("""	if(threadIdx.x == 0)
 	{
 		atomicAdd(&E.a.stats->rays, (unsigned long long)ctl->rays);
 """, """	if(threadIdx.x == 0)
@@ -29,5 +21,8 @@ rep("""	if(threadIdx.x == 0)
 			atomicAdd(&E.a.stats->path_tris, dry && now > dry ? now - dry : 0ull); // sum of the end times (ticks): the mean
 		}
 		atomicAdd(&E.a.stats->rays, (unsigned long long)ctl->rays);
-""")
-open(p, "w").write(s)
+"""),
+]
+
+if __name__ == "__main__":
+    edit(sys.argv[1], "path.hpp", PATH)

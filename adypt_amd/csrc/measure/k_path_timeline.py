@@ -12,18 +12,7 @@ At the end of the launch lane 0 of every wave adds its sums to DeviceStats::wave
     [7] trips << 36 | cost of one stamp, summed (a back-to-back stamp at the end of every trip: every section above contains one such cost)
     tools/build_variant.sh timeline --transform adypt_amd/csrc/measure/k_path_timeline.py [--transform adypt_amd/csrc/measure/k_path_init_cap.py]"""
 import sys
-d = sys.argv[1]
-
-
-def edit(name, pairs):
-    p = d + "/" + name
-    s = open(p).read()
-    for old, new in pairs:
-        assert s.count(old) == 1, (name, s.count(old), old[:70])
-        s = s.replace(old, new)
-    open(p, "w").write(s)
-
-
+from _variant import edit
 CLOB = '"s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99", "s100", "s101", "scc", "memory"'
 
 
@@ -32,7 +21,7 @@ def stamp(i, pre=""):  # s98 = previous stamp (low word), s100:101 = this stamp,
             % (pre, 88 + i, 88 + i, CLOB))
 
 
-edit("traverse_trip.inc", [
+TRIP = [
     ("			const bool can_pop = !pending && ng_y <= 0x00ffffffu && sp != 0;", "			" + stamp(0) + "\n			const bool can_pop = !pending && ng_y <= 0x00ffffffu && sp != 0;"),
     ("			auto pull = [](uint32_t lane4, uint32_t v)", "			" + stamp(1) + "\n			auto pull = [](uint32_t lane4, uint32_t v)"),
     ("			const uint32_t src4 = ent << 2;", "			" + stamp(2) + "\n			const uint32_t src4 = ent << 2;"),
@@ -40,16 +29,20 @@ edit("traverse_trip.inc", [
     ("			float tt, tu, tv;\n", "			" + stamp(4, "s_waitcnt vmcnt(5)\\n\\t") + "\n			float tt, tu, tv;\n"),
     ("			if(tg_y != 0)\n			{\n				// more triangles of this node", "			" + stamp(5) + "\n			if(tg_y != 0)\n			{\n				// more triangles of this node"),
     ("				active = false;\n			}\n		}", "				active = false;\n			}\n			" + stamp(6) + "\n			" + stamp(8) + "\n			asm volatile(\"s_add_u32 s95, s95, 1\" ::: \"s95\", \"scc\");\n		}"),
-])
+]
 zero = " ".join('asm volatile("s_mov_b32 s%d, 0" ::: "s%d");' % (r, r) for r in range(88, 98)) + ' asm volatile("s_memtime s[100:101]\\n\\ts_waitcnt lgkmcnt(0)\\n\\ts_mov_b32 s98, s100" ::: "s98", "s100", "s101");'
 read = " ".join('asm volatile("s_mov_b32 %%0, s%d" : "=s"(tl[%d]));' % (88 + i, i) for i in range(9))
-edit("path.hpp", [
+PATH = [
     ("template <bool STATS, bool SUN>\n__global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) void k_path(PathKernArgs K)\n{",
      "template <bool STATS, bool SUN>\n__global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) __attribute__((amdgpu_num_sgpr(88))) void k_path(PathKernArgs K)\n{\n	" + zero),
     ("	// ---------------- totals: per wave -> per workgroup (LDS) -> one device atomic per workgroup ----------------",
      "	{ uint32_t tl[9]; " + read + "\n	if(lane == 0) { for(int i = 0; i < 7; ++i) atomicAdd(&a.stats->wave_profile[i], (unsigned long long)tl[i]);\n"
      "		atomicAdd(&a.stats->wave_profile[7], ((unsigned long long)tl[7] << 36) | (unsigned long long)tl[8]); } } // (k_path<false> leaves wave_profile alone)\n"
      "	// ---------------- totals: per wave -> per workgroup (LDS) -> one device atomic per workgroup ----------------"),
-])
+]
 # (k_trace includes the trip too: its stamps write the same fixed registers, which that kernel never reads — it is not held to 88 SGPRs, so it must not be run
 # from this variant: tools/path_timeline.py uses the one-launch pipeline only)
+
+if __name__ == "__main__":
+    edit(sys.argv[1], "traverse_trip.inc", TRIP)
+    edit(sys.argv[1], "path.hpp", PATH)

@@ -9,15 +9,13 @@ do not run every trip are weighted by how often a trip executes them:
            profile (profiles/r4_k_path_wave_profile.json: exchanges / trips, rounds / trips; a setup block runs with an exchange).
 Instructions not in a measured class count as 4 cycles.
     python tools/instruction_mix.py [k_path|k_trace] > profiles/r4_<kernel>_instruction_mix.json"""
-import json, os, re, subprocess, sys, tempfile
+import json, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "adypt_amd", "csrc")
 which = sys.argv[1] if len(sys.argv) > 1 else "k_path"
-flags = re.search(r"HIPFLAGS\s*:=\s*(.*?)\n\n", open(os.path.join(CSRC, "Makefile")).read(), re.S).group(1).replace("\\\n", " ").replace("$(ARCH)", "gfx950").split()
-flags = [f for f in flags if f not in ("-fPIC",)]
-with tempfile.NamedTemporaryFile(suffix=".s") as t:
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-DADYPT_BUILD", "--cuda-device-only", "-S", os.path.join(CSRC, "device/tracer.hip"), "-o", t.name], stderr=subprocess.DEVNULL)
-    text = open(t.name).read()
+flags = [f for f in subprocess.check_output(["make", "-s", "-C", CSRC, "flags"], text=True).split() if f != "-fPIC"]
+subprocess.check_call(["make", "-s", "-C", CSRC, "asm"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)  # (the shipped objects' compile line)
+text = open(os.path.join(CSRC, "build", "tracer.s")).read()
 name = {"k_trace": "_ZN5adypt7k_traceILb0ELb0EEEvNS_9TraceArgsE", "k_path": "_ZN5adypt6k_pathILb0ELb0EEEvNS_12PathKernArgsE"}[which]
 body = text[text.index("\n" + name + ":"):text.index(".amdhsa_kernel " + name)].splitlines()
 

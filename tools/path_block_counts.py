@@ -9,14 +9,11 @@ With tools/trip_budget.py's static counts these are the EXECUTED vector instruct
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "adypt_amd", "csrc", "measure"))
 from adypt_amd import api, scenes, _native as N
+from k_path_blocks import SETS, SETS_LANES  # the blocks each pass of the counting variant counts, in counter order
 SET = os.environ.get("ADYPT_BLOCKS_SET", "trip")  # which counting variant ADYPT_LIB is: trip | shade | rare
-SETS = {"trip": ["setup", "exchange", "shade", "trip", "A_pop", "A_choose", "A_push", "B_tri_load", "B_node_load", "C_woop", "D_slab", "E_flush"],
-        "shade": ["shade", "S_parked", "S_miss", "S_surface", "S_textured", "S_glossy", "S_diffuse", "S_mirror", "S_dielectric", "S_dead", "S_alive", "S_replace"],
-        "rare": ["trip", "shade", "A_pop_spill", "A_push_spill", "div_slow", "S_fetch_more", "S_early", "X_lock_spin", "exchange", "setup", "F_try", "S_defer"]}  # = adypt_amd/csrc/measure/k_path_blocks.py
 LANES = os.environ.get("ADYPT_BLOCKS_LANES", "0") != "0"  # the variant was built with ADYPT_BLOCKS_LANES=1: the counters hold active lanes, five per pass
-SETS_LANES = {"trip": ["trip", "A_choose", "C_woop", "D_slab", "E_flush"], "shade": ["S_surface", "S_textured", "S_glossy", "S_diffuse", "S_dielectric"],
-              "rare": ["S_miss", "S_mirror", "S_dead", "S_alive", "S_replace"], "wait": ["W_idle", "W_wait", "W_two", "W_three", "W_four"]}
 NAMES = SETS_LANES[SET] if LANES else SETS[SET]
 scene = os.environ.get("SWEEP_SCENE", "sponza"); fr = int(os.environ.get("SWEEP_FRAMES", "20")); warm = int(os.environ.get("SWEEP_WARMUP", "5"))
 spec = scenes.make_scene(scene, os.environ.get("ADYPT_CACHE", "/tmp/adypt_cache"), width=1920, height=1080,

@@ -6,10 +6,12 @@ compiled to gfx950 assembly with the Makefile's flags, and the VALU instructions
 The product library has no marks inside the trip; its own totals are printed beside the marked build's (they differ by a few instructions: the marks
 are scheduling barriers).  Dynamic weights (how often a block runs) come from tools/path_block_counts.py on the GPU box.
     python tools/trip_budget.py > profiles/r6_trip_budget.json"""
-import collections, json, os, re, shutil, subprocess, sys, tempfile
+import collections, json, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "adypt_amd", "csrc")
-FN = "_ZN5adypt6k_pathILb0ELb0EEEvNS_12PathKernArgsE"
+sys.path.insert(0, os.path.join(CSRC, "measure"))
+import _variant
+FN = _variant.K_PATH
 FULL = {"v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mul_f32", "v_fma_f32", "v_fmac_f32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_not_b32", "v_add_u32", "v_sub_u32",
         "v_subrev_u32", "v_ashrrev_i32", "v_mov_b32", "v_add_co_u32", "v_sub_co_u32", "v_addc_co_u32", "v_subb_co_u32", "v_add_i32", "v_sub_i32"}
 TRANS = ("v_rcp", "v_rsq", "v_sqrt", "v_exp", "v_log", "v_sin", "v_cos")
@@ -31,9 +33,8 @@ def is_valu(s):
 
 
 def hipflags():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    f = re.search(r"HIPFLAGS\s*:=\s*(.*?)\n\n", mk, re.S).group(1).replace("\\\n", " ").replace("$(ARCH)", "gfx950").split()
-    return [x for x in f if x != "-fPIC"]
+    """the flags both builds are compiled with, as the Makefile states them (-fPIC is left out of the list as in the committed profile: it changes no instruction of the device-only compile)"""
+    return [x for x in subprocess.check_output(["make", "-s", "-C", CSRC, "flags"], text=True).split() if x != "-fPIC"]
 
 
 def body_of(asm_text):
@@ -62,22 +63,10 @@ def count(lines):
     return {"valu": sum(ops.values()), "by_class": dict(cls), "by_opcode": dict(sorted(ops.items(), key=lambda kv: -kv[1]))}
 
 
-def marked_build(flags):
-    with tempfile.TemporaryDirectory() as t:
-        # (a sibling directory two levels below: the sources include ../../../include/adypt_hip.h)
-        dev = os.path.join(t, "a", "b", "device")
-        os.makedirs(os.path.dirname(dev))
-        shutil.copytree(os.path.join(CSRC, "device"), dev)
-        shutil.copytree(os.path.join(ROOT, "include"), os.path.join(t, "include"))
-        subprocess.check_call([sys.executable, os.path.join(CSRC, "measure", "k_path_blocks.py"), dev], env=dict(os.environ, ADYPT_BLOCKS_COUNT="0"))
-        out = os.path.join(t, "marked.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-DADYPT_BUILD", "--cuda-device-only", "-S", os.path.join(dev, "tracer.hip"), "-o", out], stderr=subprocess.DEVNULL)
-        return body_of(open(out).read())
-
-
 def main():
     flags = hipflags()
-    marked = marked_build(flags)
+    marked = body_of(open(_variant.build("marks", *_variant.VARIANTS["marks"], asm=True)).read())  # (assembly comments only: no counters)
+    _variant.discard("marks")
     subprocess.check_call(["make", "-s", "-C", CSRC, "asm"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     product = body_of(open(os.path.join(CSRC, "build", "tracer.s")).read())
 
