@@ -327,57 +327,201 @@ class ViewerTypes:
     kDiffuse, kSpecular, kEmissive, kPTRadiance, kNormal, kPosition = range(6)
 
 
-class HipPathTracer:
-    """OglPathTracer (src/Tracer/OglPathTracer.hpp:66-82) on HIP."""
+def _scene_desc(scene: HipScene, width: int, height: int) -> Tuple[N.SceneDesc, list]:
+    """adypt_scene_desc of `scene` for device 0 and the whole image, and the arrays it points into (to be kept alive while it is in use)."""
+    s, b = scene.scene, scene.bvh
+    tex_arr = (N.Texture * max(1, len(s.textures)))()
+    keep = [s.triangles, s.materials, b.nodes, b.tri_indices, scene.woop, tex_arr] + list(s.textures)
+    for i, t in enumerate(s.textures):
+        tex_arr[i].width, tex_arr[i].height, tex_arr[i].rgb = t.shape[1], t.shape[0], t.ctypes.data
+    d = N.SceneDesc()
+    d.nodes, d.n_nodes = b.nodes.ctypes.data, len(b.nodes) // NODE_BYTES
+    d.tri_indices, d.n_refs = b.tri_indices.ctypes.data, len(b.tri_indices)
+    d.woop = None if scene.woop is None else scene.woop.ctypes.data
+    d.triangles, d.n_tris = s.triangles.ctypes.data, len(s.triangles) // TRI_BYTES
+    d.materials, d.n_mats = (s.materials.ctypes.data if len(s.materials) else None), len(s.materials) // MAT_BYTES
+    d.textures, d.n_textures = (C.addressof(tex_arr) if s.textures else None), len(s.textures)
+    d.width, d.height, d.device, d.tile_rank, d.tile_nranks = width, height, 0, 0, 1
+    return d, keep
+
+
+def _read_block_noise(ctx) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """adypt_read_block_noise on one context: the size first, then the blocks."""
+    n = N.lib.adypt_read_block_noise(ctx, None, None, None, 0)
+    if n < 0:
+        N.check(int(n), ctx)
+    idx, s, cnt = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint32)
+    if n:
+        r = N.lib.adypt_read_block_noise(ctx, idx.ctypes.data, s.ctypes.data, cnt.ctypes.data, n)
+        if r < 0:
+            N.check(int(r), ctx)
+    return idx, s, cnt
+
+
+class _Tracer:
+    """What HipPathTracer and MultiPathTracer both offer, written once over three things the class gives: the handle `_h`, the symbol family
+    `_family` ("adypt_" or "adypt_multi_": `_call("trace_spp", n)` is adypt_trace_spp or adypt_multi_trace_spp on the handle) and its own error
+    reader `_check(code)`.  What the C-ABI offers per context only goes through `_contexts()`."""
+    _family = ""
+    _destroy = ""
 
     def __init__(self) -> None:
-        self._ctx = C.c_void_p()
+        self._h = C.c_void_p()
         self.m_viewer_type = ViewerTypes.kDiffuse
+
+    def _fn(self, name: str):
+        return getattr(N.lib, self._family + name)
+
+    def _call(self, name: str, *args) -> None:
+        self._check(self._fn(name)(self._h, *args))
+
+    def SetConfig(self, config: N.PtParams) -> None:
+        self._call("set_params", C.byref(config))
+
+    def SetCamera(self, inv_projection: np.ndarray, inv_view: np.ndarray, position) -> None:
+        ip = np.ascontiguousarray(inv_projection, dtype=np.float32).reshape(16)
+        iv = np.ascontiguousarray(inv_view, dtype=np.float32).reshape(16)
+        pos = np.ascontiguousarray(position, dtype=np.float32).reshape(3)
+        self._call("set_camera", pos.ctypes.data, ip.ctypes.data, iv.ctypes.data)
+
+    def Trace(self, enable_pt: bool, n_spp: int = 1) -> None:
+        """Trace(true): n_spp more frames; Trace(false): one primary-ray viewer frame of m_viewer_type."""
+        if enable_pt:
+            self.m_viewer_type = ViewerTypes.kPTRadiance
+            self._call("trace_spp", n_spp)
+        else:
+            if self.m_viewer_type == ViewerTypes.kPTRadiance:
+                self.m_viewer_type = ViewerTypes.kDiffuse
+            self._call("trace_primary", self.m_viewer_type)
+
+    def SetSunVisibility(self, enabled: bool, direction=None) -> None:
+        """The occlusion query the reference has commented out (pathtracer.glsl:132); off = the reference as it runs."""
+        d = None if direction is None else np.ascontiguousarray(direction, dtype=np.float32).reshape(3)
+        self._call("set_sun_visibility", 1 if enabled else 0, None if d is None else d.ctypes.data)
+
+    def SetLookahead(self, enabled: bool) -> None:
+        """One Trace(true) per call (Instance::Update) at batched throughput: see adypt_set_lookahead."""
+        self._call("set_lookahead", 1 if enabled else 0)
+
+    def Reset(self) -> None:
+        self._call("reset")
+
+    def GetSPP(self) -> int:
+        return self._fn("get_spp")(self._h)
+
+    def CommRanks(self) -> int:
+        """Ranks of the communicator as RCCL reports them (ncclCommCount); 0 = none (one device, the shared-device test hook)."""
+        return self._fn("comm_ranks")(self._h)
+
+    def GetStats(self) -> dict:
+        """Several devices: counts summed over them, kernel times of the slowest one (they run concurrently)."""
+        st = N.Stats()
+        self._call("get_stats", C.byref(st))
+        return st.as_dict()
+
+    # ---- per context ----
+    def GetFramesInFlight(self) -> int:
+        return N.lib.adypt_get_frames_in_flight(self._contexts()[0])
+
+    def GetFusedBounces(self) -> bool:
+        """Whether the last batch of frames ran its bounces in one launch."""
+        return N.lib.adypt_get_fused_bounces(self._contexts()[0]) == 1
+
+    def ResetStats(self) -> None:
+        for c in self._contexts():
+            N.check(N.lib.adypt_reset_stats(c), c)
+
+    def DeviceSynchronize(self) -> None:
+        for c in self._contexts():
+            N.check(N.lib.adypt_device_synchronize(c), c)
+
+    def GetShaderClockGHz(self) -> float:
+        """Clock the chip held under the traversal launches since ResetStats (s_memtime / s_memrealtime of workgroup 0); 0.0 if none ran."""
+        out = (C.c_uint64 * 2)()
+        c = self._contexts()[0]
+        N.check(N.lib.adypt_get_shader_clock(c, out), c)
+        return float(out[0]) / float(out[1]) * 0.1 if out[1] else 0.0
+
+    # ---- noise statistics (adypt_set_noise_stats, include/adypt_hip.h); several devices: of the whole image, the devices' blocks merged on the host ----
+    def SetNoiseStats(self, enabled: bool) -> None:
+        """Per-pixel luminance moments next to the running mean; enable at 0 spp.  The image never changes."""
+        self._call("set_noise_stats", 1 if enabled else 0)
+
+    def GetNoiseStats(self) -> bool:
+        return N.lib.adypt_get_noise_stats(self._contexts()[0]) == 1
+
+    def GetNoise(self) -> dict:
+        """mean_noise, worst_block, worst_index, spp, pixels of the blocks this tracer owns (needs >= 2 spp)."""
+        out = N.Noise()
+        self._call("get_noise", C.byref(out))
+        return out.as_dict()
+
+    def ReadNoise(self) -> np.ndarray:
+        """H x W float32: the relative standard error of every pixel's mean luminance."""
+        e = np.zeros((self.height, self.width), dtype=np.float32)
+        self._call("read_noise", e.ctypes.data)
+        return e
+
+    def ReadNoiseMoments(self) -> np.ndarray:
+        """H x W x 2 float32: (mean, m2) of every pixel's luminance.  Every context writes the pixels of its own tiles."""
+        m = np.zeros((self.height, self.width, 2), dtype=np.float32)
+        for c in self._contexts():
+            N.check(N.lib.adypt_read_noise_moments(c, m.ctypes.data), c)
+        return m
+
+    def TraceUntil(self, target: float, min_spp: int = 16, max_spp: int = 1024, check_every: int = 16) -> dict:
+        """Trace(true) in steps of check_every until worst_block <= target (and spp >= min_spp) or spp >= max_spp; the last GetNoise()."""
+        self.m_viewer_type = ViewerTypes.kPTRadiance
+        out = N.Noise()
+        self._call("trace_until", float(target), min_spp, max_spp, check_every, C.byref(out))
+        return out.as_dict()
+
+    def ReadDisplay(self) -> np.ndarray:
+        """What OglPathTracer::DrawScreen puts on screen (shaders/screen.glsl:15-21): H x W x 4 uint8; every context converts its own tiles."""
+        rgba = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        self._call("read_display", rgba.ctypes.data)
+        return rgba
+
+    def ReadResult(self) -> np.ndarray:
+        rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        self._call("read_radiance", rgb.ctypes.data)
+        return rgb
+
+    def SaveResult(self, filename: str, save_as_fp16: bool) -> None:
+        save_exr(filename, self.ReadResult(), save_as_fp16)
+
+    def destroy(self) -> None:
+        if self._h:
+            getattr(N.lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self) -> None:
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class HipPathTracer(_Tracer):
+    """OglPathTracer (src/Tracer/OglPathTracer.hpp:66-82) on HIP."""
+    _family, _destroy = "adypt_", "adypt_destroy"
+    _ctx = property(lambda self: self._h)
+
+    def _check(self, code: int) -> None:
+        N.check(code, self._h)
+
+    def _contexts(self):
+        return [self._h]
 
     def Initialize(self, config: N.PtParams, scene: HipScene, width: int, height: int, device: int = 0,
                    tile_rank: int = 0, tile_nranks: int = 1) -> None:
         self.destroy()
         self.width, self.height = width, height
         self.tile_rank, self.tile_nranks = tile_rank, tile_nranks
-        s, b = scene.scene, scene.bvh
-        tex_arr = (N.Texture * max(1, len(s.textures)))()
-        self._keep = [s.triangles, s.materials, b.nodes, b.tri_indices, scene.woop, tex_arr] + list(s.textures)
-        for i, t in enumerate(s.textures):
-            tex_arr[i].width, tex_arr[i].height, tex_arr[i].rgb = t.shape[1], t.shape[0], t.ctypes.data
-        d = N.SceneDesc()
-        d.nodes, d.n_nodes = b.nodes.ctypes.data, len(b.nodes) // NODE_BYTES
-        d.tri_indices, d.n_refs = b.tri_indices.ctypes.data, len(b.tri_indices)
-        d.woop = None if scene.woop is None else scene.woop.ctypes.data
-        d.triangles, d.n_tris = s.triangles.ctypes.data, len(s.triangles) // TRI_BYTES
-        d.materials, d.n_mats = (s.materials.ctypes.data if len(s.materials) else None), len(s.materials) // MAT_BYTES
-        d.textures, d.n_textures = (C.addressof(tex_arr) if s.textures else None), len(s.textures)
-        d.width, d.height, d.device, d.tile_rank, d.tile_nranks = width, height, device, tile_rank, tile_nranks
-        N.check(N.lib.adypt_create(C.byref(self._ctx), C.byref(d)))
+        d, self._keep = _scene_desc(scene, width, height)
+        d.device, d.tile_rank, d.tile_nranks = device, tile_rank, tile_nranks
+        N.check(N.lib.adypt_create(C.byref(self._h), C.byref(d)))
         self.SetConfig(config)
-
-    def SetConfig(self, config: N.PtParams) -> None:
-        N.check(N.lib.adypt_set_params(self._ctx, C.byref(config)), self._ctx)
-
-    def SetCamera(self, inv_projection: np.ndarray, inv_view: np.ndarray, position) -> None:
-        ip = np.ascontiguousarray(inv_projection, dtype=np.float32).reshape(16)
-        iv = np.ascontiguousarray(inv_view, dtype=np.float32).reshape(16)
-        pos = np.ascontiguousarray(position, dtype=np.float32).reshape(3)
-        N.check(N.lib.adypt_set_camera(self._ctx, pos.ctypes.data, ip.ctypes.data, iv.ctypes.data), self._ctx)
-
-    def Trace(self, enable_pt: bool, n_spp: int = 1) -> None:
-        """Trace(true): n_spp more frames; Trace(false): one primary-ray viewer frame of m_viewer_type."""
-        if enable_pt:
-            self.m_viewer_type = ViewerTypes.kPTRadiance
-            N.check(N.lib.adypt_trace_spp(self._ctx, n_spp), self._ctx)
-        else:
-            if self.m_viewer_type == ViewerTypes.kPTRadiance:
-                self.m_viewer_type = ViewerTypes.kDiffuse
-            N.check(N.lib.adypt_trace_primary(self._ctx, self.m_viewer_type), self._ctx)
-
-    def SetSunVisibility(self, enabled: bool, direction=None) -> None:
-        """The occlusion query the reference has commented out (pathtracer.glsl:132); off = the reference as it runs."""
-        d = None if direction is None else np.ascontiguousarray(direction, dtype=np.float32).reshape(3)
-        N.check(N.lib.adypt_set_sun_visibility(self._ctx, 1 if enabled else 0, None if d is None else d.ctypes.data), self._ctx)
 
     def TraceAsync(self, n_spp: int = 1) -> None:
         """Trace(true) n_spp times without waiting for the GPU (adypt_trace_spp_async); pair with Wait()."""
@@ -387,17 +531,8 @@ class HipPathTracer:
     def Wait(self) -> None:
         N.check(N.lib.adypt_wait(self._ctx), self._ctx)
 
-    def Reset(self) -> None:
-        N.check(N.lib.adypt_reset(self._ctx), self._ctx)
-
-    def GetSPP(self) -> int:
-        return N.lib.adypt_get_spp(self._ctx)
-
     def SetFramesInFlight(self, n: int) -> None:
         N.check(N.lib.adypt_set_frames_in_flight(self._ctx, n), self._ctx)
-
-    def GetFramesInFlight(self) -> int:
-        return N.lib.adypt_get_frames_in_flight(self._ctx)
 
     def SetPipeline(self, n_pipes: int) -> None:
         """Sub-batches per batch, each a chain of kernels on its own HIP stream (adypt_set_pipeline); 1 = serial."""
@@ -410,75 +545,12 @@ class HipPathTracer:
         """Every bounce after the first of a batch in one launch (k_path); default on.  Images are bit-identical either way."""
         N.check(N.lib.adypt_set_fused_bounces(self._ctx, 1 if enabled else 0), self._ctx)
 
-    def GetFusedBounces(self) -> bool:
-        """Whether the last batch of frames ran its bounces in one launch."""
-        return N.lib.adypt_get_fused_bounces(self._ctx) == 1
-
-    def CommRanks(self) -> int:
-        return N.lib.adypt_comm_ranks(self._ctx)
-
-    def SetLookahead(self, enabled: bool) -> None:
-        """One Trace(true) per call (Instance::Update) at batched throughput: see adypt_set_lookahead."""
-        N.check(N.lib.adypt_set_lookahead(self._ctx, 1 if enabled else 0), self._ctx)
-
     def GetLookaheadFrames(self) -> int:
         return N.lib.adypt_get_lookahead_frames(self._ctx)
 
-    def ReadResult(self) -> np.ndarray:
-        rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        N.check(N.lib.adypt_read_radiance(self._ctx, rgb.ctypes.data), self._ctx)
-        return rgb
-
-    # ---- noise statistics (adypt_set_noise_stats, include/adypt_hip.h) ----
-    def SetNoiseStats(self, enabled: bool) -> None:
-        """Per-pixel luminance moments next to the running mean; enable at 0 spp.  The image never changes."""
-        N.check(N.lib.adypt_set_noise_stats(self._ctx, 1 if enabled else 0), self._ctx)
-
-    def GetNoiseStats(self) -> bool:
-        return N.lib.adypt_get_noise_stats(self._ctx) == 1
-
-    def GetNoise(self) -> dict:
-        """mean_noise, worst_block, worst_index, spp, pixels of the blocks this context owns (needs >= 2 spp)."""
-        out = N.Noise()
-        N.check(N.lib.adypt_get_noise(self._ctx, C.byref(out)), self._ctx)
-        return out.as_dict()
-
-    def ReadNoise(self) -> np.ndarray:
-        """H x W float32: the relative standard error of every pixel's mean luminance."""
-        e = np.zeros((self.height, self.width), dtype=np.float32)
-        N.check(N.lib.adypt_read_noise(self._ctx, e.ctypes.data), self._ctx)
-        return e
-
-    def ReadNoiseMoments(self) -> np.ndarray:
-        """H x W x 2 float32: (mean, m2) of every pixel's luminance."""
-        m = np.zeros((self.height, self.width, 2), dtype=np.float32)
-        N.check(N.lib.adypt_read_noise_moments(self._ctx, m.ctypes.data), self._ctx)
-        return m
-
     def ReadBlockNoise(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(block index int32, sum float64, count uint32) of the owned 32x32 blocks, ascending block index."""
-        n = N.lib.adypt_read_block_noise(self._ctx, None, None, None, 0)
-        if n < 0:
-            N.check(int(n), self._ctx)
-        idx, s, cnt = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint32)
-        if n:
-            r = N.lib.adypt_read_block_noise(self._ctx, idx.ctypes.data, s.ctypes.data, cnt.ctypes.data, n)
-            if r < 0:
-                N.check(int(r), self._ctx)
-        return idx, s, cnt
-
-    def TraceUntil(self, target: float, min_spp: int = 16, max_spp: int = 1024, check_every: int = 16) -> dict:
-        """Trace(true) in steps of check_every until worst_block <= target (and spp >= min_spp) or spp >= max_spp; the last GetNoise()."""
-        self.m_viewer_type = ViewerTypes.kPTRadiance
-        out = N.Noise()
-        N.check(N.lib.adypt_trace_until(self._ctx, float(target), min_spp, max_spp, check_every, C.byref(out)), self._ctx)
-        return out.as_dict()
-
-    def ReadDisplay(self) -> np.ndarray:
-        """What OglPathTracer::DrawScreen puts on screen (shaders/screen.glsl:15-21): H x W x 4 uint8."""
-        rgba = np.zeros((self.height, self.width, 4), dtype=np.uint8)
-        N.check(N.lib.adypt_read_display(self._ctx, rgba.ctypes.data), self._ctx)
-        return rgba
+        return _read_block_noise(self._ctx)
 
     def SavePreview(self, filename: str) -> None:
         save_png(filename, self.ReadDisplay())
@@ -488,9 +560,6 @@ class HipPathTracer:
         uv = np.zeros((self.height, self.width, 2), dtype=np.float32)
         N.check(N.lib.adypt_read_hits(self._ctx, tri.ctypes.data, uv.ctypes.data), self._ctx)
         return tri, uv
-
-    def SaveResult(self, filename: str, save_as_fp16: bool) -> None:
-        save_exr(filename, self.ReadResult(), save_as_fp16)
 
     def TraceRays(self, rays: np.ndarray, with_stats: bool = True, any_hit: bool = False) -> np.ndarray:
         """closest-hit batch (traversal.glsl:14-255) or, with any_hit, the occlusion overload (traversal.glsl:257-494)."""
@@ -504,25 +573,11 @@ class HipPathTracer:
         """audit: the slot-claim audit of the ray queues (GetStats()["audit_errors"] must stay 0); a debugging aid, slow."""
         N.check(N.lib.adypt_set_instrumentation(self._ctx, (1 if timing else 0) | (2 if counters else 0) | (4 if audit else 0)), self._ctx)
 
-    def GetStats(self) -> dict:
-        st = N.Stats()
-        N.check(N.lib.adypt_get_stats(self._ctx, C.byref(st)), self._ctx)
-        return st.as_dict()
-
     def GetWaveProfile(self) -> dict:
         out = (C.c_uint64 * 8)()
         N.check(N.lib.adypt_get_wave_profile(self._ctx, out), self._ctx)
         keys = ("trips", "trip_lanes", "tri_iters", "tri_lanes", "node_phases", "node_lanes", "refills", "empty_trips")
         return dict(zip(keys, [int(v) for v in out]))
-
-    def GetShaderClockGHz(self) -> float:
-        """Clock the chip held under the traversal launches since ResetStats (s_memtime / s_memrealtime of workgroup 0); 0.0 if none ran."""
-        out = (C.c_uint64 * 2)()
-        N.check(N.lib.adypt_get_shader_clock(self._ctx, out), self._ctx)
-        return float(out[0]) / float(out[1]) * 0.1 if out[1] else 0.0
-
-    def ResetStats(self) -> None:
-        N.check(N.lib.adypt_reset_stats(self._ctx), self._ctx)
 
     def local_pixel_count(self) -> int:
         return N.lib.adypt_local_pixel_count(self._ctx)
@@ -563,214 +618,60 @@ class HipPathTracer:
     def CommBarrier(self) -> None:
         N.check(N.lib.adypt_comm_barrier(self._ctx), self._ctx)
 
-    def DeviceSynchronize(self) -> None:
-        N.check(N.lib.adypt_device_synchronize(self._ctx), self._ctx)
 
-    def destroy(self) -> None:
-        if self._ctx:
-            N.lib.adypt_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __del__(self) -> None:
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class MultiPathTracer:
+class MultiPathTracer(_Tracer):
     """One host process driving N GPUs through the library's own multi-device boundary (adypt_create_multi): tile rank i on
     devices[i], scene replicated, the radiance gathered on devices[0] with RCCL inside adypt_multi_read_radiance.  Same method
     names as HipPathTracer / OglPathTracer."""
-
-    def __init__(self) -> None:
-        self._m = C.c_void_p()
-        self.m_viewer_type = ViewerTypes.kDiffuse
+    _family, _destroy = "adypt_multi_", "adypt_destroy_multi"
+    _m = property(lambda self: self._h)
 
     def _check(self, code: int) -> None:
         if code != N.ADYPT_OK:
-            msg = N.lib.adypt_multi_last_error(self._m if self._m else None)
+            msg = N.lib.adypt_multi_last_error(self._h if self._h else None)
             raise N.AdyptError(code, (msg or b"").decode("utf-8", "replace"))
+
+    def _contexts(self):
+        return [N.lib.adypt_multi_context(self._m, i) for i in range(self.DeviceCount())]
 
     def Initialize(self, config: N.PtParams, scene: HipScene, width: int, height: int, devices: Sequence[int] = (0,)) -> None:
         self.destroy()
         self.width, self.height = width, height
-        s, b = scene.scene, scene.bvh
-        tex_arr = (N.Texture * max(1, len(s.textures)))()
-        self._keep = [s.triangles, s.materials, b.nodes, b.tri_indices, scene.woop, tex_arr] + list(s.textures)
-        for i, t in enumerate(s.textures):
-            tex_arr[i].width, tex_arr[i].height, tex_arr[i].rgb = t.shape[1], t.shape[0], t.ctypes.data
-        d = N.SceneDesc()
-        d.nodes, d.n_nodes = b.nodes.ctypes.data, len(b.nodes) // NODE_BYTES
-        d.tri_indices, d.n_refs = b.tri_indices.ctypes.data, len(b.tri_indices)
-        d.woop = None if scene.woop is None else scene.woop.ctypes.data
-        d.triangles, d.n_tris = s.triangles.ctypes.data, len(s.triangles) // TRI_BYTES
-        d.materials, d.n_mats = (s.materials.ctypes.data if len(s.materials) else None), len(s.materials) // MAT_BYTES
-        d.textures, d.n_textures = (C.addressof(tex_arr) if s.textures else None), len(s.textures)
-        d.width, d.height, d.device, d.tile_rank, d.tile_nranks = width, height, 0, 0, 1
+        d, self._keep = _scene_desc(scene, width, height)
         devs = (C.c_int * len(devices))(*devices)
-        self._check(N.lib.adypt_create_multi(C.byref(self._m), C.byref(d), devs, len(devices)))
+        self._check(N.lib.adypt_create_multi(C.byref(self._h), C.byref(d), devs, len(devices)))
         self.SetConfig(config)
 
     def SetupSeconds(self, i: int) -> float:
         """Seconds adypt_create took for devices[i] (the contexts are created concurrently, one host thread each)."""
         return float(N.lib.adypt_multi_setup_seconds(self._m, i))
 
-    def SetConfig(self, config: N.PtParams) -> None:
-        self._check(N.lib.adypt_multi_set_params(self._m, C.byref(config)))
-
-    def SetCamera(self, inv_projection: np.ndarray, inv_view: np.ndarray, position) -> None:
-        ip = np.ascontiguousarray(inv_projection, dtype=np.float32).reshape(16)
-        iv = np.ascontiguousarray(inv_view, dtype=np.float32).reshape(16)
-        pos = np.ascontiguousarray(position, dtype=np.float32).reshape(3)
-        self._check(N.lib.adypt_multi_set_camera(self._m, pos.ctypes.data, ip.ctypes.data, iv.ctypes.data))
-
-    def SetLookahead(self, enabled: bool) -> None:
-        self._check(N.lib.adypt_multi_set_lookahead(self._m, 1 if enabled else 0))
-
     def CommInit(self) -> None:
         self._check(N.lib.adypt_multi_comm_init(self._m))
-
-    def CommRanks(self) -> int:
-        """Ranks of the communicator as RCCL reports them (ncclCommCount); 0 = none (one device, the shared-device test hook)."""
-        return N.lib.adypt_multi_comm_ranks(self._m)
-
-    def _contexts(self):
-        return [N.lib.adypt_multi_context(self._m, i) for i in range(self.DeviceCount())]
-
-    def GetFramesInFlight(self) -> int:
-        return N.lib.adypt_get_frames_in_flight(self._contexts()[0])
-
-    def GetFusedBounces(self) -> bool:
-        return N.lib.adypt_get_fused_bounces(self._contexts()[0]) == 1
-
-    def ResetStats(self) -> None:
-        for c in self._contexts():
-            N.check(N.lib.adypt_reset_stats(c), c)
-
-    def DeviceSynchronize(self) -> None:
-        for c in self._contexts():
-            N.check(N.lib.adypt_device_synchronize(c), c)
-
-    def GetShaderClockGHz(self) -> float:
-        out = (C.c_uint64 * 2)()
-        c = self._contexts()[0]
-        N.check(N.lib.adypt_get_shader_clock(c, out), c)
-        return float(out[0]) / float(out[1]) * 0.1 if out[1] else 0.0
-
-    def Trace(self, enable_pt: bool, n_spp: int = 1) -> None:
-        if enable_pt:
-            self.m_viewer_type = ViewerTypes.kPTRadiance
-            self._check(N.lib.adypt_multi_trace_spp(self._m, n_spp))
-        else:
-            if self.m_viewer_type == ViewerTypes.kPTRadiance:
-                self.m_viewer_type = ViewerTypes.kDiffuse
-            self._check(N.lib.adypt_multi_trace_primary(self._m, self.m_viewer_type))
-
-    def Reset(self) -> None:
-        self._check(N.lib.adypt_multi_reset(self._m))
-
-    def GetSPP(self) -> int:
-        return N.lib.adypt_multi_get_spp(self._m)
 
     def DeviceCount(self) -> int:
         return N.lib.adypt_multi_device_count(self._m)
 
-    def SetSunVisibility(self, enabled: bool, direction=None) -> None:
-        d = None if direction is None else np.ascontiguousarray(direction, dtype=np.float32).reshape(3)
-        self._check(N.lib.adypt_multi_set_sun_visibility(self._m, 1 if enabled else 0, None if d is None else d.ctypes.data))
-
     def SetInstrumentation(self, timing: bool = False, counters: bool = False) -> None:
         self._check(N.lib.adypt_multi_set_instrumentation(self._m, (1 if timing else 0) | (2 if counters else 0)))
 
-    def GetStats(self) -> dict:
-        """Counts summed over the devices, kernel times of the slowest one (they run concurrently)."""
-        st = N.Stats()
-        self._check(N.lib.adypt_multi_get_stats(self._m, C.byref(st)))
-        return st.as_dict()
-
-    # ---- noise statistics of the whole image: the devices' blocks merged on the host (adypt_multi_get_noise) ----
-    def SetNoiseStats(self, enabled: bool) -> None:
-        self._check(N.lib.adypt_multi_set_noise_stats(self._m, 1 if enabled else 0))
-
-    def GetNoiseStats(self) -> bool:
-        return N.lib.adypt_get_noise_stats(self._contexts()[0]) == 1
-
-    def GetNoise(self) -> dict:
-        out = N.Noise()
-        self._check(N.lib.adypt_multi_get_noise(self._m, C.byref(out)))
-        return out.as_dict()
-
-    def ReadNoise(self) -> np.ndarray:
-        e = np.zeros((self.height, self.width), dtype=np.float32)
-        self._check(N.lib.adypt_multi_read_noise(self._m, e.ctypes.data))
-        return e
-
-    def ReadNoiseMoments(self) -> np.ndarray:
-        """Every device writes the pixels of its own tiles."""
-        m = np.zeros((self.height, self.width, 2), dtype=np.float32)
-        for c in self._contexts():
-            N.check(N.lib.adypt_read_noise_moments(c, m.ctypes.data), c)
-        return m
-
     def ReadBlockNoise(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """The devices' blocks merged and sorted by block index."""
-        parts = []
-        for c in self._contexts():
-            n = N.lib.adypt_read_block_noise(c, None, None, None, 0)
-            if n < 0:
-                N.check(int(n), c)
-            idx, s, cnt = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint32)
-            if n:
-                r = N.lib.adypt_read_block_noise(c, idx.ctypes.data, s.ctypes.data, cnt.ctypes.data, n)
-                if r < 0:
-                    N.check(int(r), c)
-            parts.append((idx, s, cnt))
+        parts = [_read_block_noise(c) for c in self._contexts()]
         idx, s, cnt = (np.concatenate([p[i] for p in parts]) for i in range(3))
         order = np.argsort(idx, kind="stable")
         return idx[order], s[order], cnt[order]
-
-    def TraceUntil(self, target: float, min_spp: int = 16, max_spp: int = 1024, check_every: int = 16) -> dict:
-        self.m_viewer_type = ViewerTypes.kPTRadiance
-        out = N.Noise()
-        self._check(N.lib.adypt_multi_trace_until(self._m, float(target), min_spp, max_spp, check_every, C.byref(out)))
-        return out.as_dict()
-
-    def ReadDisplay(self) -> np.ndarray:
-        """What the reference's window shows (screen.glsl:15-21), H x W x 4 uint8: every device converts its own tiles."""
-        out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
-        self._check(N.lib.adypt_multi_read_display(self._m, out.ctypes.data))
-        return out
 
     def ContextStats(self, i: int) -> dict:
         st = N.Stats()
         N.check(N.lib.adypt_get_stats(N.lib.adypt_multi_context(self._m, i), C.byref(st)))
         return st.as_dict()
 
-    def ReadResult(self) -> np.ndarray:
-        rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
-        self._check(N.lib.adypt_multi_read_radiance(self._m, rgb.ctypes.data))
-        return rgb
-
     def GatherDevice(self) -> int:
         """Device pointer (on devices[0]) of the assembled W x H x 3 fp32 image; owned by the library."""
         p = C.c_void_p()
         self._check(N.lib.adypt_multi_gather_radiance(self._m, C.byref(p)))
         return p.value
-
-    def SaveResult(self, filename: str, save_as_fp16: bool) -> None:
-        save_exr(filename, self.ReadResult(), save_as_fp16)
-
-    def destroy(self) -> None:
-        if self._m:
-            N.lib.adypt_destroy_multi(self._m)
-            self._m = C.c_void_p()
-
-    def __del__(self) -> None:
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 class Instance:

@@ -9,7 +9,7 @@
 //   --devices: pixel tiles sharded over several GPUs of the node (adypt_create_multi), radiance gathered on the first one
 //   --save-every K: progressive rendering as in the reference's window — the running mean is written to --out (and --preview)
 //                   every K samples; the file on disk is always a complete image of what has converged so far
-//   --noise T: render until the noisiest 32x32 block of the image is at or below T (adypt_trace_until: the relative standard error of the mean
+//   --noise T: render until the noisiest 32x32 block of the image is at or below T (adypt_multi_trace_until: the relative standard error of the mean
 //              luminance, adypt_hip.h); --spp is then the cap, --min-spp (default 16) the least, and the noise is looked at every --check-every
 //              (default 16) samples.  --noise-out: the per-pixel noise as a grey EXR
 #include "adypt_hip.h"
@@ -105,26 +105,24 @@ int main(int argc, char **argv)
 	d.triangles = tris; d.n_tris = n_tris; d.materials = mats; d.n_mats = n_mats;
 	d.textures = (const adypt_texture *)tex; d.n_textures = n_tex;
 	d.width = cfg.width; d.height = cfg.height; d.device = devices[0]; d.tile_rank = 0; d.tile_nranks = 1;
-	// one device: a plain context; several: the library's multi-device boundary (tile rank i on devices[i], one gather per saved image)
-	adypt_ctx *ctx = nullptr;
+	// any number of devices through the library's multi-device boundary (one device is its n_dev = 1 case): tile rank i on devices[i], one gather per saved image
 	adypt_multi *multi = nullptr;
-	const bool many = devices.size() > 1;
-	if(many ? adypt_create_multi(&multi, &d, devices.data(), (int)devices.size()) != ADYPT_OK : adypt_create(&ctx, &d) != ADYPT_OK)
+	if(adypt_create_multi(&multi, &d, devices.data(), (int)devices.size()) != ADYPT_OK)
 	{
-		fprintf(stderr, "[TRACER]Err: %s\n", many ? adypt_multi_last_error(nullptr) : adypt_last_error(nullptr));
+		fprintf(stderr, "[TRACER]Err: %s\n", adypt_multi_last_error(nullptr));
 		return 1;
 	}
-	auto err = [&]() { return many ? adypt_multi_last_error(multi) : adypt_last_error(ctx); };
+	auto err = [&]() { return adypt_multi_last_error(multi); };
 	adypt_pt_params p;
 	p.stack_size = cfg.stack_size; p.max_bounce = cfg.max_bounce; p.subpixel = cfg.subpixel; p.tmp_lifetime = cfg.tmp_lifetime;
 	p.ray_tmin = cfg.ray_tmin; p.clamp = cfg.clamp; memcpy(p.sun, cfg.sun, 12); p.shift_seed = seed;
 	float ip[16], iv[16];
 	adypt_camera_matrices(cfg.fov, cfg.yaw, cfg.pitch, cfg.width, cfg.height, ip, iv);
-	int r = many ? adypt_multi_set_params(multi, &p) : adypt_set_params(ctx, &p);
-	if(r == ADYPT_OK) r = many ? adypt_multi_set_camera(multi, cfg.position, ip, iv) : adypt_set_camera(ctx, cfg.position, ip, iv);
-	if(r == ADYPT_OK && sun_visibility) r = many ? adypt_multi_set_sun_visibility(multi, 1, nullptr) : adypt_set_sun_visibility(ctx, 1, nullptr);
-	if(r == ADYPT_OK) r = many ? adypt_multi_set_instrumentation(multi, 1) : adypt_set_instrumentation(ctx, 1);
-	if(r == ADYPT_OK && until) r = many ? adypt_multi_set_noise_stats(multi, 1) : adypt_set_noise_stats(ctx, 1);
+	int r = adypt_multi_set_params(multi, &p);
+	if(r == ADYPT_OK) r = adypt_multi_set_camera(multi, cfg.position, ip, iv);
+	if(r == ADYPT_OK && sun_visibility) r = adypt_multi_set_sun_visibility(multi, 1, nullptr);
+	if(r == ADYPT_OK) r = adypt_multi_set_instrumentation(multi, 1);
+	if(r == ADYPT_OK && until) r = adypt_multi_set_noise_stats(multi, 1);
 	if(r != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
 
 	std::vector<float> rgb((size_t)cfg.width * cfg.height * 3, 0.0f);
@@ -132,13 +130,13 @@ int main(int argc, char **argv)
 	// SaveResult (OglPathTracer.cpp:199-212) + the window's picture; written to a temporary name first so that a reader of a
 	// progressive render never sees a half-written file
 	auto save = [&]() -> bool {
-		if((many ? adypt_multi_read_radiance(multi, rgb.data()) : adypt_read_radiance(ctx, rgb.data())) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return false; }
+		if(adypt_multi_read_radiance(multi, rgb.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return false; }
 		const std::string tmp = out + ".part";
 		if(adypt_save_exr(tmp.c_str(), rgb.data(), cfg.width, cfg.height, fp16) != ADYPT_OK || rename(tmp.c_str(), out.c_str()) != 0) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return false; }
 		if(!preview.empty())
 		{
 			rgba8.assign((size_t)cfg.width * cfg.height * 4, 0);
-			if((many ? adypt_multi_read_display(multi, rgba8.data()) : adypt_read_display(ctx, rgba8.data())) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return false; }
+			if(adypt_multi_read_display(multi, rgba8.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return false; }
 			const std::string ptmp = preview + ".part";
 			if(adypt_save_png(ptmp.c_str(), rgba8.data(), cfg.width, cfg.height) != ADYPT_OK || rename(ptmp.c_str(), preview.c_str()) != 0) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return false; }
 		}
@@ -154,10 +152,10 @@ int main(int argc, char **argv)
 		// the next multiple of K and taken up again (the noise is looked at every check_every samples from there).
 		for(bool done = false; !done && r == ADYPT_OK;)
 		{
-			const int now = many ? adypt_multi_get_spp(multi) : adypt_get_spp(ctx);
+			const int now = adypt_multi_get_spp(multi);
 			const int cap = save_every > 0 ? std::min(spp, std::max(2, (now / save_every + 1) * save_every)) : spp;
 			const int least = std::min(min_spp, cap);
-			r = many ? adypt_multi_trace_until(multi, noise_target, least, cap, check_every, &noise) : adypt_trace_until(ctx, noise_target, least, cap, check_every, &noise);
+			r = adypt_multi_trace_until(multi, noise_target, least, cap, check_every, &noise);
 			if(r != ADYPT_OK) break;
 			done = noise.spp >= spp || (noise.spp >= min_spp && noise.worst_block <= noise_target);
 			if(!done)
@@ -170,13 +168,13 @@ int main(int argc, char **argv)
 			}
 		}
 	}
-	else if(primary >= 0) r = many ? adypt_multi_trace_primary(multi, primary) : adypt_trace_primary(ctx, primary);
-	else if(save_every <= 0 || save_every >= spp) r = many ? adypt_multi_trace_spp(multi, spp) : adypt_trace_spp(ctx, spp);
+	else if(primary >= 0) r = adypt_multi_trace_primary(multi, primary);
+	else if(save_every <= 0 || save_every >= spp) r = adypt_multi_trace_spp(multi, spp);
 	else
 		for(int done = 0; done < spp && r == ADYPT_OK;)
 		{
 			const int n = std::min(save_every, spp - done);
-			r = many ? adypt_multi_trace_spp(multi, n) : adypt_trace_spp(ctx, n);
+			r = adypt_multi_trace_spp(multi, n);
 			done += n;
 			if(r == ADYPT_OK && done < spp)
 			{
@@ -190,9 +188,9 @@ int main(int argc, char **argv)
 	double t1 = now_ms() - t_save;
 	if(r != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
 	adypt_stats st;
-	if((many ? adypt_multi_get_stats(multi, &st) : adypt_get_stats(ctx, &st)) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+	if(adypt_multi_get_stats(multi, &st) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
 	printf("[PT]INFO: %d spp on %d GPU%s, %llu rays in %.1f ms wall (%.1f Mrays/s; traversal kernels %.1f ms, shade kernels %.1f ms)\n",
-		   many ? adypt_multi_get_spp(multi) : adypt_get_spp(ctx), (int)devices.size(), many ? "s" : "", (unsigned long long)st.rays, t1 - t0,
+		   adypt_multi_get_spp(multi), (int)devices.size(), devices.size() > 1 ? "s" : "", (unsigned long long)st.rays, t1 - t0,
 		   st.rays / ((t1 - t0) * 1e3), st.trace_ms, st.shade_ms);
 	if(!save()) return 1;
 	printf("[PT]INFO: Saved image to %s\n", out.c_str());
@@ -202,15 +200,14 @@ int main(int argc, char **argv)
 		if(!noise_out.empty())
 		{
 			std::vector<float> e((size_t)cfg.width * cfg.height, 0.0f), grey((size_t)cfg.width * cfg.height * 3);
-			if((many ? adypt_multi_read_noise(multi, e.data()) : adypt_read_noise(ctx, e.data())) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+			if(adypt_multi_read_noise(multi, e.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
 			for(size_t i = 0; i < e.size(); ++i) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = e[i];
 			if(adypt_save_exr(noise_out.c_str(), grey.data(), cfg.width, cfg.height, 0) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
 			printf("[PT]INFO: Saved noise to %s\n", noise_out.c_str());
 		}
 		printf("[PT]NOISE: spp %d mean_noise %.9g worst_block %.9g worst_index %d (target %.9g)\n", noise.spp, noise.mean_noise, noise.worst_block, noise.worst_index, noise_target);
 	}
-	if(many) adypt_destroy_multi(multi);
-	else adypt_destroy(ctx);
+	adypt_destroy_multi(multi);
 	adypt_bvh_free(bvh);
 	adypt_scene_free(scene);
 	// like ~Instance (src/Instance.cpp:83-86): the config is written back on exit

@@ -14,7 +14,9 @@
 #include "host_transport.hpp"
 #include "tunables.hpp"
 #include "tile_layout.hpp"
+#include "gather_plan.hpp"
 #include "noise.hpp"
+#include "trace_until.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
 
@@ -109,22 +111,12 @@ RcclApi *rccl(std::string *err)
 	return nullptr;
 }
 
-// the shard geometry every rank computes identically: float4 elements of rank r's compact buffer
-std::vector<int64_t> shard_counts(int width, int height, int nranks)
-{
-	std::vector<int64_t> v((size_t)nranks);
-	for(int r = 0; r < nranks; ++r) v[(size_t)r] = adypt_shard_block_count(width, height, r, nranks) * 1024;
-	return v;
-}
-
 // Per-context communicator + root-side buffers.  Parked in adypt_ctx::comm, freed by adypt_destroy.
 struct Comm {
 	RcclApi *api = nullptr;
 	ncclComm_t comm = nullptr;
 	int device = 0, rank = 0, nranks = 1;
-	std::vector<int64_t> counts;     // float4 per rank
-	int64_t stride = 0;              // max of counts: rank r's tiles land at gathered + r * stride
-	Buffer<float4> gathered;         // root only
+	Buffer<float4> gathered;         // root only: GatherPlan::stride x nranks
 	Buffer<float> rgb;               // root only: assembled W*H*3
 	Buffer<double> scratch;          // all-reduce staging (device)
 	static constexpr int kScratch = 64;
@@ -207,13 +199,12 @@ int finish_comm(adypt_ctx *ctx, Comm *k)
 {
 	const CtxInfo i = ctx_info(ctx);
 	k->device = i.device; k->rank = i.rank; k->nranks = i.nranks;
-	k->counts = shard_counts(i.width, i.height, i.nranks);
-	k->stride = std::max<int64_t>(1024, *std::max_element(k->counts.begin(), k->counts.end()));
 	HIP_OK(ctx, hipSetDevice(i.device));
 	HIP_OK(ctx, k->scratch.alloc(Comm::kScratch * sizeof(double)));
 	if(i.rank == 0)
 	{
-		HIP_OK(ctx, k->gathered.alloc((size_t)k->stride * (size_t)i.nranks * sizeof(float4)));
+		const int64_t stride = plan_gather(i.width, i.height, i.nranks, {}).stride;
+		HIP_OK(ctx, k->gathered.alloc((size_t)stride * (size_t)i.nranks * sizeof(float4)));
 		HIP_OK(ctx, k->rgb.alloc((size_t)i.width * i.height * 3 * sizeof(float)));
 	}
 	return ADYPT_OK;
@@ -233,15 +224,123 @@ void park_comm(adypt_ctx *ctx, Comm *k)
 }
 
 // root side after the tiles have arrived (or for a single rank): own tiles + un-tiling, all on the root's stream
-int assemble_on_root(adypt_ctx *ctx, Comm *k)
+int assemble_on_root(adypt_ctx *ctx, Comm *k, int64_t stride)
 {
 	const CtxInfo i = ctx_info(ctx);
 	HIP_OK(ctx, hipSetDevice(i.device));
 	if(i.n_local_px > 0)
 		HIP_OK(ctx, hipMemcpyAsync(k->gathered, i.accum, (size_t)i.n_local_px * sizeof(float4), hipMemcpyDeviceToDevice, i.stream));
 	// pixels no rank owns do not exist (every block has an owner); the image is fully overwritten
-	int r = adypt_assemble_radiance(ctx, k->gathered, k->stride, k->rgb); // enqueues k_untile per rank and drains the stream
-	return r;
+	return adypt_assemble_radiance(ctx, k->gathered, stride, k->rgb); // enqueues k_untile per rank and drains the stream
+}
+
+// A rank this process owns: its context and its communicator (null: a single rank, or the shared-device test mode).
+struct LocalRank { adypt_ctx *ctx; Comm *comm; };
+
+// What the two callers do differently, by name.
+struct GatherMode {
+	const char *caller;    // the public function, for messages
+	bool drain_first;      // adypt_comm_*: what the watchdog times is the collective and its drain — not the frames a caller has queued in front of it with
+	                       // adypt_trace_spp_async, nor the skew between ranks that are still rendering: the own streams are drained before it is armed
+	                       // (rendering cannot hang on another rank: it has no collective)
+	bool device_copies;    // TEST HOOK (adypt_multi with ADYPT_MULTI_SHARED_DEVICE): every rank on one device, peer -> root by device copies, no communicator
+	const Tunables *tun;   // null: the ones the first local rank's communicator read when it was made
+};
+
+// THE gather: gather_plan.hpp decides the exchange, this executes it for the local ranks (ascending; all of them for adypt_multi, one for adypt_comm_*).
+// Errors land in the first local rank's context.  *rgb_device: the assembled image where rank 0 is local, null elsewhere.
+int gather_radiance(const std::vector<LocalRank> &local, const GatherMode &mode, void **rgb_device)
+{
+	*rgb_device = nullptr;
+	adypt_ctx *home = local.front().ctx;
+	const CtxInfo hi = ctx_info(home);
+	const bool root_local = hi.rank == 0, exchange = hi.nranks > 1;
+	auto fail_from = [&](adypt_ctx *c, int code) { if(c != home) ctx_set_error(home, adypt_last_error(c)); return code; };
+	std::vector<int> ranks;
+	std::vector<const LocalRank *> by_rank((size_t)hi.nranks, nullptr);
+	for(const LocalRank &l : local)
+	{
+		if(!l.comm && exchange && !mode.device_copies) { ctx_set_error(home, std::string(mode.caller) + ": call adypt_comm_init first"); return ADYPT_E_STATE; }
+		ranks.push_back(ctx_info(l.ctx).rank);
+		by_rank[(size_t)ranks.back()] = &l;
+	}
+	Comm *k0 = root_local ? local.front().comm : nullptr;
+	if(root_local && !k0)
+	{
+		// a single rank has nothing to exchange (and the shared-device test hook exchanges by device copies): root-side buffers only, no communicator
+		k0 = new Comm();
+		park_comm(home, k0);
+		int r = finish_comm(home, k0);
+		if(r != ADYPT_OK) return r;
+	}
+	const Tunables &tun = mode.tun ? *mode.tun : (k0 ? k0 : local.front().comm)->tun;
+	const GatherPlan plan = plan_gather(hi.width, hi.height, hi.nranks, ranks);
+	for(const LocalRank &l : local) // (what a rank sends is what the root expects of it: both are the shard geometry)
+		if(plan.counts[(size_t)ctx_info(l.ctx).rank] != ctx_info(l.ctx).n_local_px) { ctx_set_error(home, std::string(mode.caller) + ": a context's pixel count is not its shard's"); return ADYPT_E_STATE; }
+	int device = -1; // the device this function made current last: switched only when an operation is another device's
+	auto on_device = [&](int d) { if(d == device) return hipSuccess; device = d; return hipSetDevice(d); };
+	if(mode.drain_first)
+	{
+		HIP_OK(home, on_device(hi.device));
+		if(exchange) for(const LocalRank &l : local) { int r = adypt_wait(l.ctx); if(r != ADYPT_OK) return fail_from(l.ctx, r); }
+	}
+	GatherWatchdog wd(exchange ? tun.gather_timeout_s : 0.0, [&local] {
+		std::string s;
+		for(const LocalRank &l : local)
+		{
+			const CtxInfo ci = ctx_info(l.ctx);
+			s += "[adypt]   rank " + std::to_string(ci.rank) + " of " + std::to_string(ci.nranks) + " (device " + std::to_string(ci.device) + ", " + std::to_string(ci.n_local_px) + " local pixels): stream " +
+				 stream_state(ci.device, ci.stream) + "\n";
+		}
+		return s;
+	});
+	if(exchange) stall_if_asked(tun, wd);
+	if(exchange && mode.device_copies)
+	{
+		for(const GatherOp &op : plan.ops)
+		{
+			if(op.kind != GatherOp::Recv) continue;
+			adypt_ctx *peer = by_rank[(size_t)op.rank]->ctx;
+			int w = adypt_wait(peer); // the peer's frames are done (its stream is not the root's)
+			if(w != ADYPT_OK) return fail_from(peer, w);
+			if(hipMemcpyAsync(k0->gathered + (size_t)op.offset, ctx_info(peer).accum, (size_t)op.elements * sizeof(float), hipMemcpyDeviceToDevice, hi.stream) != hipSuccess)
+			{
+				ctx_set_error(home, "shared-device gather: copy failed");
+				return ADYPT_E_HIP;
+			}
+		}
+	}
+	else if(exchange)
+	{
+		// the one exchange: grouped point-to-point = ncclGather with exact per-rank sizes; peer r -> root over its own link
+		RcclApi *api = local.front().comm->api;
+		wd.stage("ncclGroupStart .. ncclGroupEnd (grouped ncclSend / ncclRecv)");
+		ncclResult_t bad = api->GroupStart();
+		if(bad != ncclSuccess) { ctx_set_error(home, std::string("ncclGroupStart: ") + api->GetErrorString(bad)); return ADYPT_E_HIP; }
+		for(const GatherOp &op : plan.ops)
+		{
+			const LocalRank &l = op.kind == GatherOp::Send ? *by_rank[(size_t)op.rank] : local.front();
+			const CtxInfo ci = ctx_info(l.ctx);
+			(void)on_device(ci.device);
+			bad = op.kind == GatherOp::Send ? api->Send(ci.accum, (size_t)op.elements, ncclFloat, 0, l.comm->comm, ci.stream)
+			                                : api->Recv(k0->gathered + (size_t)op.offset, (size_t)op.elements, ncclFloat, op.rank, l.comm->comm, ci.stream);
+			if(bad != ncclSuccess) break;
+		}
+		const ncclResult_t ge = api->GroupEnd();
+		if(bad != ncclSuccess || ge != ncclSuccess) { ctx_set_error(home, std::string("RCCL gather: ") + api->GetErrorString(bad != ncclSuccess ? bad : ge)); return ADYPT_E_HIP; }
+	}
+	if(root_local)
+	{
+		wd.stage("un-tiling on the root (drains the root's stream: the receives)");
+		int r = assemble_on_root(home, k0, plan.stride);
+		if(r != ADYPT_OK) return r;
+	}
+	// the sends complete with the root's receives; the senders' streams are drained so that their images may be overwritten again
+	wd.stage("draining the senders' streams (their sends)");
+	for(const LocalRank &l : local)
+		if(ctx_info(l.ctx).rank != 0) { int w = adypt_wait(l.ctx); if(w != ADYPT_OK) return fail_from(l.ctx, w); }
+	if(root_local) *rgb_device = k0->rgb;
+	return ADYPT_OK;
 }
 
 }  // namespace
@@ -465,21 +564,10 @@ int adypt_multi_trace_until(adypt_multi *m, double target, int min_spp, int max_
 {
 	if(!m || m->ctx.empty()) return ADYPT_E_INVALID;
 	if(adypt_get_noise_stats(m->ctx[0]) != 1) return mfail(m, ADYPT_E_STATE, "adypt_multi_trace_until: the noise statistics are off (adypt_multi_set_noise_stats)");
-	if(check_every < 1 || min_spp < 2 || max_spp < min_spp || !(target == target)) return mfail(m, ADYPT_E_INVALID, "adypt_multi_trace_until: needs check_every >= 1, 2 <= min_spp <= max_spp and a target that is a number");
-	adypt_noise last;
-	memset(&last, 0, sizeof(last));
-	for(;;) // (adypt_trace_until's loop over all devices)
-	{
-		const int spp = adypt_multi_get_spp(m), n = std::min(check_every, max_spp - spp);
-		int r = n > 0 ? adypt_multi_trace_spp(m, n) : ADYPT_OK;
-		if(r != ADYPT_OK) return r;
-		const int now = adypt_multi_get_spp(m);
-		if(now >= 2 && (r = adypt_multi_get_noise(m, &last)) != ADYPT_OK) return r;
-		if(n <= 0 || now >= max_spp || (now >= min_spp && last.worst_block <= target)) break;
-	}
-	last.spp = adypt_multi_get_spp(m);
-	if(out) *out = last;
-	return ADYPT_OK;
+	std::string refused;
+	const int r = trace_until("adypt_multi_trace_until", &refused, target, min_spp, max_spp, check_every, out, [m] { return adypt_multi_get_spp(m); },
+	                          [m](int n) { return adypt_multi_trace_spp(m, n); }, [m](adypt_noise *o) { return adypt_multi_get_noise(m, o); });
+	return refused.empty() ? r : mfail(m, r, refused);
 }
 
 int adypt_multi_comm_init(adypt_multi *m)
@@ -505,81 +593,11 @@ int adypt_multi_gather_radiance(adypt_multi *m, void **rgb_device)
 {
 	if(!m || !rgb_device) return ADYPT_E_INVALID;
 	*rgb_device = nullptr;
-	const int n = (int)m->ctx.size();
-	adypt_ctx *root = m->ctx[0];
-	if((n == 1 || m->shared_device) && !m->comms_ready)
-	{
-		// a single device has nothing to exchange (and the shared-device test hook exchanges by device copies): root-side buffers
-		// only, no communicator
-		if(!comm_of(root))
-		{
-			Comm *k = new Comm();
-			park_comm(root, k);
-			int r = finish_comm(root, k);
-			if(r != ADYPT_OK) return mfail_ctx(m, r, root);
-		}
-	}
-	else
-	{
-		int r = multi_comm_init(m);
-		if(r != ADYPT_OK) return r;
-	}
-	Comm *k0 = comm_of(root);
-	GatherWatchdog wd(n > 1 ? m->tun.gather_timeout_s : 0.0, [m] {
-		std::string s;
-		for(size_t i = 0; i < m->ctx.size(); ++i)
-		{
-			const CtxInfo ci = ctx_info(m->ctx[i]);
-			s += "[adypt]   rank " + std::to_string(i) + " (device " + std::to_string(ci.device) + ", " + std::to_string(ci.n_local_px) + " local pixels): stream " + stream_state(ci.device, ci.stream) + "\n";
-		}
-		return s;
-	});
-	if(n > 1) stall_if_asked(m->tun, wd);
-	if(n > 1 && m->shared_device)
-	{
-		for(int r = 1; r < n; ++r)
-		{
-			const CtxInfo pi = ctx_info(m->ctx[(size_t)r]);
-			if(pi.n_local_px == 0) continue;
-			int w = adypt_wait(m->ctx[(size_t)r]); // the peer's frames are done (its stream is not the root's)
-			if(w != ADYPT_OK) return mfail_ctx(m, w, m->ctx[(size_t)r]);
-			const CtxInfo ri = ctx_info(root);
-			if(hipMemcpyAsync(k0->gathered + (size_t)r * (size_t)k0->stride, pi.accum, (size_t)pi.n_local_px * sizeof(float4), hipMemcpyDeviceToDevice, ri.stream) != hipSuccess)
-				return mfail(m, ADYPT_E_HIP, "shared-device gather: copy failed");
-		}
-	}
-	else if(n > 1)
-	{
-		// the one exchange: grouped point-to-point = ncclGather with exact per-rank sizes; peer r -> root over its own link
-		RcclApi *api = k0->api;
-		wd.stage("ncclGroupStart .. ncclGroupEnd (grouped ncclSend / ncclRecv)");
-		ncclResult_t gr = api->GroupStart();
-		if(gr != ncclSuccess) return mfail(m, ADYPT_E_HIP, std::string("ncclGroupStart: ") + api->GetErrorString(gr));
-		ncclResult_t bad = ncclSuccess;
-		for(int r = 1; r < n && bad == ncclSuccess; ++r)
-		{
-			const CtxInfo pi = ctx_info(m->ctx[(size_t)r]);
-			if(pi.n_local_px == 0) continue;
-			Comm *kr = comm_of(m->ctx[(size_t)r]);
-			(void)hipSetDevice(pi.device);
-			bad = api->Send(pi.accum, (size_t)pi.n_local_px * 4, ncclFloat, 0, kr->comm, pi.stream);
-			if(bad != ncclSuccess) break;
-			const CtxInfo ri = ctx_info(root);
-			(void)hipSetDevice(ri.device);
-			bad = api->Recv(k0->gathered + (size_t)r * (size_t)k0->stride, (size_t)pi.n_local_px * 4, ncclFloat, r, k0->comm, ri.stream);
-		}
-		gr = api->GroupEnd();
-		if(bad != ncclSuccess || gr != ncclSuccess)
-			return mfail(m, ADYPT_E_HIP, std::string("RCCL gather: ") + api->GetErrorString(bad != ncclSuccess ? bad : gr));
-	}
-	wd.stage("un-tiling on the root (drains the root's stream: the receives)");
-	int r = assemble_on_root(root, k0);
-	if(r != ADYPT_OK) return mfail_ctx(m, r, root);
-	wd.stage("draining the peers' streams (their sends)");
-	// the peers' sends complete with the root's receives; drain their streams so their images may be overwritten again
-	for(int i = 1; i < n; ++i) { int w = adypt_wait(m->ctx[(size_t)i]); if(w != ADYPT_OK) return mfail_ctx(m, w, m->ctx[(size_t)i]); }
-	*rgb_device = k0->rgb;
-	return ADYPT_OK;
+	if(m->ctx.size() > 1 && !m->shared_device) { int r = multi_comm_init(m); if(r != ADYPT_OK) return r; }
+	std::vector<LocalRank> local;
+	for(adypt_ctx *c : m->ctx) local.push_back({c, comm_of(c)});
+	const int r = gather_radiance(local, {"adypt_multi_gather_radiance", false, m->shared_device, &m->tun}, rgb_device);
+	return r == ADYPT_OK ? r : mfail_ctx(m, r, m->ctx[0]);
 }
 
 int adypt_multi_read_radiance(adypt_multi *m, float *rgb)
@@ -632,57 +650,7 @@ int adypt_comm_init(adypt_ctx *ctx, const char id[ADYPT_COMM_ID_BYTES])
 int adypt_comm_gather_radiance(adypt_ctx *ctx, void **rgb_device)
 {
 	if(!ctx || !rgb_device) return ADYPT_E_INVALID;
-	*rgb_device = nullptr;
-	Comm *k = comm_of(ctx);
-	const CtxInfo i = ctx_info(ctx);
-	if(!k)
-	{
-		if(i.nranks != 1) { ctx_set_error(ctx, "adypt_comm_gather_radiance: call adypt_comm_init first"); return ADYPT_E_STATE; }
-		k = new Comm();
-		park_comm(ctx, k);
-		int r = finish_comm(ctx, k);
-		if(r != ADYPT_OK) return r;
-	}
-	HIP_OK(ctx, hipSetDevice(i.device));
-	const Tunables &tun = k->tun;
-	// What the watchdog times is the collective and its drain — not the frames a caller has queued in front of it with adypt_trace_spp_async, nor the skew
-	// between ranks that are still rendering: this rank's own stream is drained first (rendering cannot hang on another rank: it has no collective).
-	if(i.nranks > 1) { int r = adypt_wait(ctx); if(r != ADYPT_OK) return r; }
-	GatherWatchdog wd(i.nranks > 1 ? tun.gather_timeout_s : 0.0, [i] {
-		return "[adypt]   rank " + std::to_string(i.rank) + " of " + std::to_string(i.nranks) + " (device " + std::to_string(i.device) + ", " + std::to_string(i.n_local_px) + " local pixels): stream " +
-			   stream_state(i.device, i.stream) + "\n";
-	});
-	if(i.nranks > 1) stall_if_asked(tun, wd);
-	if(i.nranks > 1)
-	{
-		RcclApi *api = k->api;
-		wd.stage("ncclGroupStart .. ncclGroupEnd (grouped ncclSend / ncclRecv)");
-		NCCL_OK(ctx, api, api->GroupStart());
-		ncclResult_t bad = ncclSuccess;
-		if(i.rank == 0)
-		{
-			for(int r = 1; r < i.nranks && bad == ncclSuccess; ++r)
-				if(k->counts[(size_t)r] > 0)
-					bad = api->Recv(k->gathered + (size_t)r * (size_t)k->stride, (size_t)k->counts[(size_t)r] * 4, ncclFloat, r, k->comm, i.stream);
-		}
-		else if(i.n_local_px > 0) bad = api->Send(i.accum, (size_t)i.n_local_px * 4, ncclFloat, 0, k->comm, i.stream);
-		ncclResult_t ge = api->GroupEnd();
-		if(bad != ncclSuccess || ge != ncclSuccess)
-		{
-			ctx_set_error(ctx, std::string("RCCL gather: ") + api->GetErrorString(bad != ncclSuccess ? bad : ge));
-			return ADYPT_E_HIP;
-		}
-	}
-	if(i.rank == 0)
-	{
-		wd.stage("un-tiling on the root (drains the root's stream: the receives)");
-		int r = assemble_on_root(ctx, k);
-		if(r != ADYPT_OK) return r;
-		*rgb_device = k->rgb;
-		return ADYPT_OK;
-	}
-	wd.stage("draining this rank's stream (its send)");
-	return adypt_wait(ctx); // the send has left the accumulation image
+	return gather_radiance({{ctx, comm_of(ctx)}}, {"adypt_comm_gather_radiance", true, false, nullptr}, rgb_device);
 }
 
 int adypt_comm_read_radiance(adypt_ctx *ctx, float *rgb)

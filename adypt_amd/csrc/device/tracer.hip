@@ -11,6 +11,7 @@
 // There is no CPU fallback anywhere in this file: without a HIP device adypt_create fails with ADYPT_E_NO_DEVICE.
 #include "context.hpp"
 #include "ctx_access.hpp"
+#include "trace_until.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
 
@@ -1139,19 +1140,10 @@ int adypt_trace_until(adypt_ctx *c, double target, int min_spp, int max_spp, int
 {
 	if(!c) return ADYPT_E_INVALID;
 	if(!c->noise_stats) return fail(c, ADYPT_E_STATE, "adypt_trace_until: the noise statistics are off (adypt_set_noise_stats)");
-	if(check_every < 1 || min_spp < 2 || max_spp < min_spp || !(target == target)) return fail(c, ADYPT_E_INVALID, "adypt_trace_until: needs check_every >= 1, 2 <= min_spp <= max_spp and a target that is a number");
-	adypt_noise last;
-	memset(&last, 0, sizeof(last));
-	for(;;)
-	{
-		const int n = std::min(check_every, max_spp - c->spp);
-		if(n > 0) TRY_CREATE(adypt_trace_spp(c, n));
-		if(c->spp >= 2) TRY_CREATE(adypt_get_noise(c, &last));
-		if(n <= 0 || c->spp >= max_spp || (c->spp >= min_spp && last.worst_block <= target)) break;
-	}
-	last.spp = c->spp;
-	if(out) *out = last;
-	return ADYPT_OK;
+	std::string refused;
+	const int r = trace_until("adypt_trace_until", &refused, target, min_spp, max_spp, check_every, out, [c] { return c->spp; }, [c](int n) { return adypt_trace_spp(c, n); },
+	                          [c](adypt_noise *o) { return adypt_get_noise(c, o); });
+	return refused.empty() ? r : fail(c, r, refused);
 }
 
 static int trace_rays_impl(adypt_ctx *c, const float *rays, int64_t n, adypt_hit *hits, int with_stats, bool any_hit)

@@ -292,7 +292,8 @@ def test_state_rules(scene_cache, sobol_matrices):
     p.destroy()
 
 
-@pytest.mark.parametrize("case,n_dev", [(CASES[0], 3), (("tiny0", 64, 36, 4, 1, 12), 4)], ids=["100x75-3-shards", "64x36-4-shards-one-owns-nothing"])
+@pytest.mark.parametrize("case,n_dev", [(CASES[0], 3), (("tiny0", 64, 36, 4, 1, 12), 4), (("tiny0", 64, 36, 4, 1, 12), 1)],
+                         ids=["100x75-3-shards", "64x36-4-shards-one-owns-nothing", "64x36-one-device"])  # (one device: what the CLI's --noise rests on)
 def test_multi_device_on_one_card(case, n_dev, scene_cache, sobol_matrices, monkeypatch):
     monkeypatch.setenv("ADYPT_MULTI_SHARED_DEVICE", "1")
     name, w, h, life, sub, spp = case

@@ -215,3 +215,87 @@ int main()
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", DEVICE, str(src), "-o", exe])
     bad, lone = (int(v) for v in subprocess.check_output([exe]).split())
     assert bad == 0 and lone > 0
+
+
+UNTIL_DRIVER = r"""
+#include "trace_until.hpp"
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+// argv: target min_spp max_spp check_every start_spp worst_block...   (the scripted answers of the noise reads, in order; the last one repeats)
+// OUT: code | out.spp out.worst_block out.mean_noise | the steps traced | the spp at which the noise was read | the message
+int main(int argc, char **argv)
+{
+	if(argc < 7) return 2;
+	const double target = atof(argv[1]);
+	const int min_spp = atoi(argv[2]), max_spp = atoi(argv[3]), check_every = atoi(argv[4]);
+	int spp = atoi(argv[5]);
+	std::vector<double> script;
+	for(int i = 6; i < argc; ++i) script.push_back(atof(argv[i]));
+	std::vector<int> steps, reads;
+	adypt_noise out;
+	out.spp = -7; out.worst_block = -7.0; out.mean_noise = -7.0; out.worst_index = -7; out.pixels = -7; // (untouched when the call is refused)
+	std::string error;
+	const int r = adypt::trace_until("driver", &error, target, min_spp, max_spp, check_every, &out, [&] { return spp; },
+	                                 [&](int n) { steps.push_back(n); spp += n; return ADYPT_OK; },
+	                                 [&](adypt_noise *o) { o->worst_block = script[reads.size() < script.size() ? reads.size() : script.size() - 1]; o->mean_noise = 0.5 * o->worst_block; reads.push_back(spp); return ADYPT_OK; });
+	printf("%d | %d %.17g %.17g |", r, out.spp, out.worst_block, out.mean_noise);
+	for(int n : steps) printf(" %d", n);
+	printf(" |");
+	for(int n : reads) printf(" %d", n);
+	printf(" | %s\n", error.c_str());
+	return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def until(tmp_path_factory):
+    d = tmp_path_factory.mktemp("until_driver")
+    src, exe = str(d / "driver.cpp"), str(d / "driver")
+    open(src, "w").write(UNTIL_DRIVER)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", DEVICE, src, "-o", exe])  # (the loop needs neither hipcc nor a HIP include)
+
+    def run(target, min_spp, max_spp, check_every, start_spp, script):
+        line = subprocess.check_output([exe] + [repr(v) for v in (target, min_spp, max_spp, check_every, start_spp)] + [repr(float(v)) for v in script]).decode()
+        code, out, steps, reads, message = (f.strip() for f in line.split("|"))
+        spp, worst, mean = out.split()
+        return {"code": int(code), "spp": int(spp), "worst_block": float(worst), "mean_noise": float(mean), "steps": [int(v) for v in steps.split()],
+                "reads": [int(v) for v in reads.split()], "message": message}
+    return run
+
+
+def test_trace_until_loop_on_scripted_noise(until):
+    """The loop both adypt_trace_until and adypt_multi_trace_until run (csrc/device/trace_until.hpp), stepped over scripted noise values."""
+    # target met at the first check with spp >= min_spp: it stops there
+    r = until(0.1, 16, 1024, 16, 0, [0.05])
+    assert (r["code"], r["steps"], r["reads"], r["spp"], r["worst_block"], r["mean_noise"]) == (0, [16], [16], 16, 0.05, 0.025)
+    r = until(0.1, 2, 1024, 4, 0, [0.1])  # (at the target is met)
+    assert (r["code"], r["steps"], r["reads"], r["spp"]) == (0, [4], [4], 4)
+    # target met below min_spp: it goes on, and stops at the first check from min_spp on
+    r = until(0.1, 16, 1024, 4, 0, [0.05])
+    assert (r["code"], r["steps"], r["reads"], r["spp"]) == (0, [4, 4, 4, 4], [4, 8, 12, 16], 16)
+    r = until(0.1, 10, 1024, 4, 0, [0.05])
+    assert (r["steps"], r["spp"]) == ([4, 4, 4], 12)
+    # met only later: every step is followed by one read, the answer of the last read is returned
+    r = until(0.1, 2, 1024, 8, 0, [0.9, 0.5, 0.2, 0.09])
+    assert (r["code"], r["steps"], r["reads"], r["spp"], r["worst_block"]) == (0, [8, 8, 8, 8], [8, 16, 24, 32], 32, 0.09)
+    # cap reached with the target unmet: stops at max_spp, the last step shortened to max_spp - spp
+    r = until(0.1, 16, 40, 16, 0, [0.9])
+    assert (r["code"], r["steps"], r["reads"], r["spp"], r["worst_block"]) == (0, [16, 16, 8], [16, 32, 40], 40, 0.9)
+    r = until(0.1, 16, 40, 16, 35, [0.9])  # (taken up in the middle, as the CLI's --save-every does)
+    assert (r["steps"], r["reads"], r["spp"]) == ([5], [40], 40)
+    # a step of one frame from 0 spp: the noise is not asked below 2 spp
+    r = until(0.1, 2, 3, 1, 0, [0.9])
+    assert (r["steps"], r["reads"], r["spp"]) == ([1, 1, 1], [2, 3], 3)
+    # called with spp >= max_spp: traces nothing and returns the current noise (none if spp < 2)
+    r = until(0.1, 16, 32, 16, 32, [0.7])
+    assert (r["code"], r["steps"], r["reads"], r["spp"], r["worst_block"]) == (0, [], [32], 32, 0.7)
+    r = until(0.1, 16, 32, 16, 50, [0.7])
+    assert (r["code"], r["steps"], r["reads"], r["spp"], r["worst_block"]) == (0, [], [50], 50, 0.7)
+    # invalid arguments are rejected before anything is traced, the caller named in the message and the result untouched
+    for args in [(0.1, 16, 32, 0), (0.1, 1, 32, 16), (0.1, 16, 15, 16), (float("nan"), 16, 32, 16)]:
+        r = until(*args, 0, [0.05])
+        assert (r["code"], r["steps"], r["reads"], r["spp"], r["worst_block"]) == (-1, [], [], -7, -7.0), args
+        assert r["message"] == "driver: needs check_every >= 1, 2 <= min_spp <= max_spp and a target that is a number"
+    assert until(0.1, 2, 2, 1, 0, [0.05])["message"] == ""  # (the least that is valid)
