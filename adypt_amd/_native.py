@@ -65,6 +65,16 @@ class Noise(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Adaptive(C.Structure):
+    """adypt_adaptive: what adypt_trace_adaptive reports."""
+    _fields_ = [("noise", Noise), ("blocks", C.c_int32), ("blocks_frozen", C.c_int32), ("pixel_samples", C.c_int64)]
+
+    def as_dict(self):
+        d = self.noise.as_dict()
+        d.update(blocks=self.blocks, blocks_frozen=self.blocks_frozen, pixel_samples=self.pixel_samples)
+        return d
+
+
 class BvhParams(C.Structure):
     _fields_ = [("max_spatial_depth", C.c_int32), ("triangle_sah", C.c_float), ("node_sah", C.c_float)]
 
@@ -131,6 +141,9 @@ _SIGS = {
     "adypt_read_noise_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_read_block_noise": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "adypt_trace_until": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Noise)]),
+    "adypt_trace_adaptive": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Adaptive)]),
+    "adypt_read_block_spp": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "adypt_multi_trace_adaptive": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Adaptive)]),
     "adypt_multi_set_noise_stats": (C.c_int, [C.c_void_p, C.c_int]),
     "adypt_multi_get_noise": (C.c_int, [C.c_void_p, C.POINTER(Noise)]),
     "adypt_multi_read_noise": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -358,6 +358,19 @@ def _read_block_noise(ctx) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     return idx, s, cnt
 
 
+def _read_block_spp(ctx) -> Tuple[np.ndarray, np.ndarray]:
+    """adypt_read_block_spp on one context: the size first, then the blocks."""
+    n = N.lib.adypt_read_block_spp(ctx, None, None, 0)
+    if n < 0:
+        N.check(int(n), ctx)
+    idx, spp = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    if n:
+        r = N.lib.adypt_read_block_spp(ctx, idx.ctypes.data, spp.ctypes.data, n)
+        if r < 0:
+            N.check(int(r), ctx)
+    return idx, spp
+
+
 class _Tracer:
     """What HipPathTracer and MultiPathTracer both offer, written once over three things the class gives: the handle `_h`, the symbol family
     `_family` ("adypt_" or "adypt_multi_": `_call("trace_spp", n)` is adypt_trace_spp or adypt_multi_trace_spp on the handle) and its own error
@@ -475,6 +488,31 @@ class _Tracer:
         out = N.Noise()
         self._call("trace_until", float(target), min_spp, max_spp, check_every, C.byref(out))
         return out.as_dict()
+
+    # ---- adaptive sampling (adypt_trace_adaptive, include/adypt_hip.h): blocks at the noise target stop being traced ----
+    def TraceAdaptive(self, target: float, min_spp: int = 16, max_spp: int = 1024, check_every: int = 16) -> dict:
+        """Trace(true) in steps of check_every; from min_spp on every 32x32 block whose mean noise is <= target is frozen at its sample count.  Ends
+        when no block is active or at max_spp.  The noise numbers of all blocks (each at its own count), blocks, blocks_frozen, pixel_samples."""
+        self.m_viewer_type = ViewerTypes.kPTRadiance
+        out = N.Adaptive()
+        self._call("trace_adaptive", float(target), min_spp, max_spp, check_every, C.byref(out))
+        return out.as_dict()
+
+    def ReadBlockSPP(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(block index int32, sample count int32) of every 32x32 block this tracer owns, ascending block index."""
+        parts = [_read_block_spp(c) for c in self._contexts()]
+        idx, spp = (np.concatenate([p[i] for p in parts]) for i in range(2))
+        order = np.argsort(idx, kind="stable")
+        return idx[order], spp[order]
+
+    def ReadSPP(self) -> np.ndarray:
+        """H x W int32: the sample count of every pixel, built from the blocks (0 where no context of this tracer owns the block)."""
+        out = np.zeros((self.height, self.width), dtype=np.int32)
+        nbx = (self.width + 31) // 32
+        for b, n in zip(*self.ReadBlockSPP()):
+            by, bx = divmod(int(b), nbx)
+            out[by * 32:(by + 1) * 32, bx * 32:(bx + 1) * 32] = n
+        return out
 
     def ReadDisplay(self) -> np.ndarray:
         """What OglPathTracer::DrawScreen puts on screen (shaders/screen.glsl:15-21): H x W x 4 uint8; every context converts its own tiles."""

@@ -3,7 +3,8 @@
 //   (src/Tracer/OglPathTracer.cpp:199-212).  The interactive window / ImGui front-end is out of scope.
 //
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
-//             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]]
+//             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
+//             [--adaptive [--spp-out file.exr]]]
 //   --sun-visibility: enable the occlusion query the reference has commented out (pathtracer.glsl:132)
 //   --preview: what the reference shows in its window (shaders/screen.glsl), as PNG
 //   --devices: pixel tiles sharded over several GPUs of the node (adypt_create_multi), radiance gathered on the first one
@@ -12,6 +13,8 @@
 //   --noise T: render until the noisiest 32x32 block of the image is at or below T (adypt_multi_trace_until: the relative standard error of the mean
 //              luminance, adypt_hip.h); --spp is then the cap, --min-spp (default 16) the least, and the noise is looked at every --check-every
 //              (default 16) samples.  --noise-out: the per-pixel noise as a grey EXR
+//   --adaptive: with --noise T, every 32x32 block stops being traced at the check at which ITS mean noise is at or below T (adypt_multi_trace_adaptive);
+//              the render ends when every block has stopped, or at --spp.  --spp-out: the per-pixel sample count as a grey EXR
 #include "adypt_hip.h"
 #include "adypt_host.h"
 
@@ -30,10 +33,11 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
-	std::string noise_out;
+	std::string noise_out, spp_out;
+	int adaptive = 0;
 	int spp = 64, fp16 = 0, primary = -1, sun_visibility = 0, save_every = 0;
 	std::vector<int> devices(1, 0);
 	unsigned seed = 12345;
@@ -69,11 +73,15 @@ int main(int argc, char **argv)
 		else if(a == "--min-spp" && i + 1 < argc) min_spp = atoi(argv[++i]);
 		else if(a == "--check-every" && i + 1 < argc) check_every = atoi(argv[++i]);
 		else if(a == "--noise-out" && i + 1 < argc) noise_out = argv[++i];
+		else if(a == "--adaptive") adaptive = 1;
+		else if(a == "--spp-out" && i + 1 < argc) spp_out = argv[++i];
 		else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
 	}
 	const bool until = noise_target >= 0.0;
 	if(!until && !noise_out.empty()) { fprintf(stderr, "--noise-out needs --noise T\n"); return 2; }
 	if(until && (primary >= 0 || spp < 2 || check_every < 1)) { fprintf(stderr, "--noise needs --spp >= 2, --check-every >= 1 and no --primary\n"); return 2; }
+	if(adaptive && (!until || save_every > 0)) { fprintf(stderr, "--adaptive needs --noise T and does not combine with --save-every\n"); return 2; }
+	if(!adaptive && !spp_out.empty()) { fprintf(stderr, "--spp-out needs --adaptive\n"); return 2; }
 	if(until) min_spp = std::max(2, std::min(min_spp, spp));
 	adypt_config cfg;
 	adypt_config_default(&cfg);
@@ -146,7 +154,14 @@ int main(int argc, char **argv)
 	double t0 = now_ms(), t_save = 0.0;
 	adypt_noise noise;
 	memset(&noise, 0, sizeof(noise));
-	if(until)
+	adypt_adaptive adapt;
+	memset(&adapt, 0, sizeof(adapt));
+	if(adaptive)
+	{
+		r = adypt_multi_trace_adaptive(multi, noise_target, min_spp, spp, check_every, &adapt);
+		noise = adapt.noise;
+	}
+	else if(until)
 	{
 		// to the noise target, --spp the cap.  With --save-every K the image is written whenever K more samples are in: the call is then capped at
 		// the next multiple of K and taken up again (the noise is looked at every check_every samples from there).
@@ -205,7 +220,29 @@ int main(int argc, char **argv)
 			if(adypt_save_exr(noise_out.c_str(), grey.data(), cfg.width, cfg.height, 0) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
 			printf("[PT]INFO: Saved noise to %s\n", noise_out.c_str());
 		}
-		printf("[PT]NOISE: spp %d mean_noise %.9g worst_block %.9g worst_index %d (target %.9g)\n", noise.spp, noise.mean_noise, noise.worst_block, noise.worst_index, noise_target);
+		if(!spp_out.empty())
+		{
+			// the sample count of every pixel from the devices' blocks (every block has one owner)
+			std::vector<float> grey((size_t)cfg.width * cfg.height * 3, 0.0f);
+			const int blocks_x = (cfg.width + 31) / 32;
+			for(size_t k = 0; k < devices.size(); ++k)
+			{
+				adypt_ctx *c = adypt_multi_context(multi, (int)k);
+				const int64_t n = adypt_read_block_spp(c, nullptr, nullptr, 0);
+				std::vector<int32_t> index((size_t)std::max<int64_t>(n, 0)), count(index.size());
+				if(n < 0 || (n > 0 && adypt_read_block_spp(c, index.data(), count.data(), n) != n)) { fprintf(stderr, "[TRACER]Err: %s\n", adypt_last_error(c)); return 1; }
+				for(size_t b = 0; b < index.size(); ++b)
+					for(int y = (index[b] / blocks_x) * 32; y < std::min(cfg.height, (index[b] / blocks_x + 1) * 32); ++y)
+						for(int x = (index[b] % blocks_x) * 32; x < std::min(cfg.width, (index[b] % blocks_x + 1) * 32); ++x)
+							for(int ch = 0; ch < 3; ++ch) grey[((size_t)y * cfg.width + x) * 3 + ch] = (float)count[b];
+			}
+			if(adypt_save_exr(spp_out.c_str(), grey.data(), cfg.width, cfg.height, 0) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
+			printf("[PT]INFO: Saved sample counts to %s\n", spp_out.c_str());
+		}
+		if(adaptive)
+			printf("[PT]ADAPTIVE: spp %d frozen %d of %d pixel_samples %lld (uniform %lld) mean_noise %.9g worst_block %.9g worst_index %d (target %.9g)\n", noise.spp, adapt.blocks_frozen,
+			       adapt.blocks, (long long)adapt.pixel_samples, (long long)noise.spp * (long long)cfg.width * (long long)cfg.height, noise.mean_noise, noise.worst_block, noise.worst_index, noise_target);
+		else printf("[PT]NOISE: spp %d mean_noise %.9g worst_block %.9g worst_index %d (target %.9g)\n", noise.spp, noise.mean_noise, noise.worst_block, noise.worst_index, noise_target);
 	}
 	adypt_destroy_multi(multi);
 	adypt_bvh_free(bvh);

@@ -23,12 +23,14 @@ struct PlanInput {
 	int single_fused, first_fused, fused_bounces, sun_visibility; // the tunables (tunables.hpp) and adypt_set_sun_visibility
 	int64_t n_local_px;                // > 0: a shard that owns no block never gets here
 	int noise_stats = 0;               // adypt_set_noise_stats: every finished sample is parked and applied by the running-mean kernel, which keeps the moments
+	int cache_stale = 0;               // adaptive sampling changed the block set since the cache image was written: the pass-local pixel order is another (active_blocks.hpp)
 };
 
 struct PassPlan {
 	enum Kind { Rolling, Batch } kind;
 	int m, hand_out;                         // frames [spp, spp + m) are traced by the pass; the first hand_out go into the image now, the others stay parked
 	int first_retrace, n_retrace, n_groups;  // frames with frame % tmpLifetime == 0 re-trace their primary rays: batch index of the first, how many, tmpLifetime groups spanned
+	bool stale_retrace;                      // the pass starts inside a tmpLifetime group whose cached hits are stale: its first frame stands in for the group's re-tracing frame
 	bool as_batch;                           // finished samples are parked and applied by k_resolve (false: the lone launch-per-bounce frame accumulates by itself, unless the noise statistics are on)
 	bool use_cache;                          // bounce 0 starts from the cached primary hits (false: that lone frame re-traces, its k_gen_primary makes camera rays)
 	bool fused_first, fused_bounces;         // bounce 0 is k_shade_first | the bounces after it are one k_path launch
@@ -58,6 +60,11 @@ inline PassPlan plan_pass(const PlanInput &in)
 	p.first_retrace = (life - in.spp % life) % life;
 	p.n_retrace = p.first_retrace < p.m ? (p.m - 1 - p.first_retrace) / life + 1 : 0;
 	p.n_groups = (in.spp + p.m - 1) / life - in.spp / life + 1;
+	// A stale cache image: the camera rays of the group the pass starts in are traced again.  The primary hit is a function of the pixel and the group
+	// alone (shade.hpp frame_group, sub_idx), so batch frame 0 gives the bits the group's own re-tracing frame gave; the camera pass then runs batch
+	// frames 0, life, 2 life, ... — one per group spanned, group g from frame g x life.
+	p.stale_retrace = in.cache_stale != 0 && p.first_retrace != 0;
+	if(p.stale_retrace) { p.first_retrace = 0; p.n_retrace = p.n_groups; }
 	p.n_pipes = p.m > 1 ? std::max(1, std::min(std::min(in.pipeline, kMaxPipes), p.m)) : 1;
 	for(int k = 0; k < p.n_pipes; ++k) p.frames_of_pipe[k] = p.m / p.n_pipes + (k < p.m % p.n_pipes ? 1 : 0);
 	// A single frame (no look-ahead, or one frame in flight) runs as a batch of one — camera launch, k_shade_first, k_path, k_resolve: 4 launches

@@ -21,11 +21,13 @@ PassArgs pass_args(const adypt_ctx *c)
 }
 
 // The running-mean kernel over frames [first, first + count) of `f`'s parked samples, on the context's stream: k_resolve, or with the noise
-// statistics on its sibling that keeps the luminance moments as well (noise.hpp)
+// statistics on its sibling that keeps the luminance moments as well (noise.hpp); while blocks are frozen (they are only with the statistics on) that
+// sibling with the slot map from the pass's pixels to the owned blocks' (active_blocks.hpp)
 void launch_resolve(adypt_ctx *c, const FrameArgs &f, const PassArgs &a, int first, int count)
 {
-	const dim3 grid((c->n_local_px + 255) / 256), block(256);
-	if(c->noise_stats) hipLaunchKernelGGL(k_resolve_noise, grid, block, 0, c->stream, f, a.sc, a.px, c->d_noise_moments.get(), first, count);
+	const dim3 grid((c->pass_px + 255) / 256), block(256);
+	if(c->ab.any_frozen()) hipLaunchKernelGGL(k_resolve_noise_slots<true>, grid, block, 0, c->stream, f, a.sc, a.px, c->d_noise_moments.get(), (const int32_t *)c->d_active_slot, first, count);
+	else if(c->noise_stats) hipLaunchKernelGGL(k_resolve_noise, grid, block, 0, c->stream, f, a.sc, a.px, c->d_noise_moments.get(), first, count);
 	else hipLaunchKernelGGL(k_resolve, grid, block, 0, c->stream, f, a.sc, a.px, first, count);
 }
 
@@ -47,7 +49,7 @@ int resolve_batch_frames(adypt_ctx *c, int first, int count)
 	const int group = (c->batch_spp + first + count - 1) / life - c->batch_spp / life;
 	if(group > c->cache_group)
 	{
-		HIP_TRY(c, hipMemcpyAsync(c->d_cache, c->d_cache_next + (size_t)(group - 1) * (size_t)c->n_local_px, (size_t)c->n_local_px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+		HIP_TRY(c, hipMemcpyAsync(c->d_cache, c->d_cache_next + (size_t)(group - 1) * (size_t)c->pass_px, (size_t)c->pass_px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
 		c->cache_group = group;
 	}
 	return ADYPT_OK;
@@ -92,7 +94,7 @@ void launch_shade_first(adypt_ctx *c, hipStream_t stream, int k, const QueueWind
 	hipEvent_t stop = begin_timing(c, 1, stream);
 	QueueArgs q = queue_args(c, win, 0, ctr->count[0], ctr->count[1], f.n_frames);
 	audit_before(c, q, stream, k);
-	hipLaunchKernelGGL(k_shade_first, dim3((unsigned)(c->n_local_px / kShadeThreads)), dim3(kShadeThreads), 0, stream, f, a.sc, q, a.px, a.stats ? 1 : 0);
+	hipLaunchKernelGGL(k_shade_first, dim3((unsigned)(c->pass_px / kShadeThreads)), dim3(kShadeThreads), 0, stream, f, a.sc, q, a.px, a.stats ? 1 : 0);
 	audit_after(c, q, stream, k);
 	end_timing(stop, stream);
 }
@@ -120,9 +122,10 @@ int roll_launch(adypt_ctx *c, const PassPlan &p, const PassArgs &a, int frame, i
 	roll_frame_args(c, p, frame, s, &f);
 	int r = upload_sobol(c, frame, 1, c->d_sobol + (size_t)s * 64);
 	if(r != ADYPT_OK) return r;
-	if(frame % std::max(1, c->params.tmp_lifetime) == 0)
+	if(frame % std::max(1, c->params.tmp_lifetime) == 0 || (p.stale_retrace && frame == c->spp))
 	{
 		// the frame re-traces its primary rays (pathtracer.glsl:113-127): one camera launch into the cache image, on the context's stream
+		// (or stands in for its group's re-tracing frame behind a change of the block set: frame_plan.hpp stale_retrace)
 		FrameArgs fc = f;
 		fc.frame_stride = std::max(1, c->params.tmp_lifetime);
 		r = launch_trace_camera(c, c->pipes[0], full_window(c), fc, a.px, 1, a.stats);
@@ -362,7 +365,7 @@ int start_path_tracing(adypt_ctx *c)
 PlanInput plan_input(const adypt_ctx *c, int remaining)
 {
 	return PlanInput{c->spp, remaining, c->lookahead, c->frames_in_flight, c->params.tmp_lifetime, c->params.max_bounce, c->pipeline,
-	                 c->single_fused, c->first_fused, c->fused_bounces, c->sun_visibility, c->n_local_px, c->noise_stats};
+	                 c->single_fused, c->first_fused, c->fused_bounces, c->sun_visibility, c->pass_px, c->noise_stats, c->cache_stale ? 1 : 0};
 }
 
 }  // namespace

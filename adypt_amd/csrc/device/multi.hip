@@ -17,6 +17,7 @@
 #include "gather_plan.hpp"
 #include "noise.hpp"
 #include "trace_until.hpp"
+#include "active_blocks.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
 
@@ -568,6 +569,30 @@ int adypt_multi_trace_until(adypt_multi *m, double target, int min_spp, int max_
 	const int r = trace_until("adypt_multi_trace_until", &refused, target, min_spp, max_spp, check_every, out, [m] { return adypt_multi_get_spp(m); },
 	                          [m](int n) { return adypt_multi_trace_spp(m, n); }, [m](adypt_noise *o) { return adypt_multi_get_noise(m, o); });
 	return refused.empty() ? r : mfail(m, r, refused);
+}
+
+// The loop of adypt_trace_adaptive over every device: the blocks of the image merged by index (every block has one owner), every device freezes
+// its own among the blocks that reached the target — no collective.
+int adypt_multi_trace_adaptive(adypt_multi *m, double target, int min_spp, int max_spp, int check_every, adypt_adaptive *out)
+{
+	if(!m || m->ctx.empty()) return ADYPT_E_INVALID;
+	FOR_ALL(m, ctx_adaptive_ready(c, "adypt_multi_trace_adaptive"));
+	std::string refused;
+	adypt_ctx *failed = nullptr;
+	const int r = trace_adaptive("adypt_multi_trace_adaptive", &refused, target, min_spp, max_spp, check_every, out, [m] { return adypt_multi_get_spp(m); },
+	                             [m](int n) { return adypt_multi_trace_spp(m, n); },
+	                             [m, &failed](std::vector<BlockState> *blocks) {
+		                             blocks->clear();
+		                             for(adypt_ctx *c : m->ctx) { const int rc = ctx_read_blocks(c, blocks); if(rc != ADYPT_OK) { failed = c; return rc; } }
+		                             std::sort(blocks->begin(), blocks->end(), [](const BlockState &a, const BlockState &b) { return a.index < b.index; });
+		                             return (int)ADYPT_OK;
+	                             },
+	                             [m, &failed](const std::vector<int32_t> &stop, int spp) {
+		                             for(adypt_ctx *c : m->ctx) { const int rc = ctx_freeze_blocks(c, stop.data(), stop.size(), spp); if(rc != ADYPT_OK) { failed = c; return rc; } }
+		                             return (int)ADYPT_OK;
+	                             });
+	if(!refused.empty()) return mfail(m, r, refused);
+	return (r != ADYPT_OK && failed) ? mfail_ctx(m, r, failed) : r;
 }
 
 int adypt_multi_comm_init(adypt_multi *m)

@@ -12,6 +12,7 @@
 #include "context.hpp"
 #include "ctx_access.hpp"
 #include "trace_until.hpp"
+#include "active_blocks.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
 
@@ -309,6 +310,9 @@ int launch_trace(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, int par
 	return ADYPT_OK;
 }
 
+// the block list of a pass: the owned blocks, or the active ones among them while blocks are frozen (active_blocks.hpp)
+const int32_t *pass_blocks(const adypt_ctx *c) { return c->ab.any_frozen() ? (const int32_t *)c->d_active_blocks : (const int32_t *)c->d_local_blocks; }
+
 void fill_frame(const adypt_ctx *c, FrameArgs *f)
 {
 	memset(f, 0, sizeof(*f));
@@ -320,7 +324,7 @@ void fill_frame(const adypt_ctx *c, FrameArgs *f)
 	f->width = c->width; f->height = c->height;
 	f->spp = c->spp; f->subpixel = c->params.subpixel; f->tmp_life = c->params.tmp_lifetime; f->max_bounce = c->params.max_bounce;
 	f->sobol = c->d_sobol; f->done = c->q.done; f->n_frames = 1; f->frame_first = 0; f->frame_stride = 1; f->batched = 0;
-	f->n_local_px = c->n_local_px; f->blocks_x = c->blocks_x; f->rank = c->rank; f->nranks = c->nranks;
+	f->n_local_px = c->pass_px; f->blocks_x = c->blocks_x; f->rank = c->rank; f->nranks = c->nranks;
 	f->n_tris = (int32_t)c->n_tris; f->n_mats = (int32_t)c->n_mats; f->n_tex = c->n_tex;
 	f->deal_chunks = c->deal_chunks;
 	memcpy(f->sun_query_dir, c->sun_dir, 12); f->sun_query = 0; // (set by the frame driver where the one-launch pipeline carries the query)
@@ -330,23 +334,25 @@ void fill_scene(const adypt_ctx *c, SceneArgs *s)
 	s->triangles = (const float4 *)c->d_triangles;
 	s->materials = (const float4 *)c->d_materials;
 	s->texels = (const uint32_t *)c->d_texels;
-	s->local_blocks = (const int32_t *)c->d_local_blocks;
+	s->local_blocks = pass_blocks(c);
 	s->tri_class = (const uint8_t *)c->d_tri_class;
 }
 void fill_pixels(const adypt_ctx *c, PixelArgs *p)
 {
-	p->accum = c->d_accum; p->cache = c->d_cache; p->cache_next = c->d_cache_next; p->shift = c->d_shift; p->stats = c->d_stats;
+	p->accum = c->d_accum; p->cache = c->d_cache; p->cache_next = c->d_cache_next; p->shift = c->ab.any_frozen() ? c->d_active_shift.get() : c->d_shift.get(); p->stats = c->d_stats;
 }
-// slots per segment that `frames` frames of this context's pixels need (multiple of kShadeThreads)
-uint32_t seg_slots_for(const adypt_ctx *c, int frames)
+// slots per segment that `frames` frames of `px` pixels need (multiple of kShadeThreads)
+uint32_t seg_slots_px(int px, int frames)
 {
-	const size_t paths = (size_t)std::max(c->n_local_px, 64) * (size_t)std::max(1, frames);
+	const size_t paths = (size_t)std::max(px, 64) * (size_t)std::max(1, frames);
 	const size_t chunks = (paths + kShadeThreads - 1) / kShadeThreads;
 	return (uint32_t)(((chunks + kNumSegments - 1) / kNumSegments) * kShadeThreads);
 }
+// ... of this context's pixels: what the queues and their windows are sized by, whatever is frozen
+uint32_t seg_slots_for(const adypt_ctx *c, int frames) { return seg_slots_px(c->n_local_px, frames); }
 // paths per queue segment of a pass over `frames` frames (QueueArgs::seg_paths); its kernels run 8 x seg_paths / 256 workgroups.
 // Sizing the grids for the allocated capacity instead cost ~6 ns per empty workgroup: 13 ms per 8-bounce batch at 66 M slots.
-uint32_t pass_seg_paths(const adypt_ctx *c, const QueueWindow &win, int frames) { return std::min(win.seg_cap, seg_slots_for(c, frames)); }
+uint32_t pass_seg_paths(const adypt_ctx *c, const QueueWindow &win, int frames) { return std::min(win.seg_cap, seg_slots_px(c->pass_px, frames)); }
 
 inline QueueWindow full_window(const adypt_ctx *c) { return QueueWindow{0, c->seg_cap}; }
 // window of sub-batch k when a batch is cut into n_pipes sub-batches of at most ceil(frames_in_flight / n_pipes) frames
@@ -372,10 +378,10 @@ int launch_trace_camera(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, 
 	K.seg_shift = 8;
 	while((1u << K.seg_shift) < K.seg_paths) ++K.seg_shift;
 	a.seg_cap = 1u << K.seg_shift; // (positions are numbers: nothing is stored at them)
-	K.rays = (unsigned long long)c->n_image_px * (unsigned long long)f.n_frames;
+	K.rays = (unsigned long long)c->pass_image_px * (unsigned long long)f.n_frames;
 	a.refill_min = c->refill_min_primary; a.chunk = c->chunk; a.bite = c->bite_primary; a.endgame = c->endgame;
 	a.stack_size = c->params.stack_size; a.lds_depth = c->lds_depth;
-	K.f = f; K.local_blocks = (const int32_t *)c->d_local_blocks; K.px = px; K.bias_mode = bias_mode;
+	K.f = f; K.local_blocks = pass_blocks(c); K.px = px; K.bias_mode = bias_mode;
 	hipEvent_t stop = begin_timing(c, 0, pipe.stream);
 	const bool viewer = viewer_type >= 0; // a primary-only call: the pixel is coloured when its ray has finished (no viewer launch)
 	if(viewer) { fill_scene(c, &K.sc); K.viewer_type = viewer_type; }
@@ -525,7 +531,81 @@ int apply_params(adypt_ctx *c)
 }  // namespace
 
 #include "scene_upload.hpp"
+#include "adaptive_kernels.hpp" // (templates: emitted where they are first used — behind every other kernel template, see there)
 #include "frame_schedule.hpp"
+
+namespace {
+
+// ---- adaptive sampling: the block set of a pass (active_blocks.hpp) ----
+
+// Every block active again (adypt_reset, adypt_trace_primary): passes are the owned blocks' and the four buffers go back.  The cache image is
+// written again before it is read: both callers restart the accumulation, whose first frame re-traces its camera rays.
+void thaw_blocks(adypt_ctx *c)
+{
+	c->cache_stale = false;
+	if(!c->ab.any_frozen()) return;
+	(void)hipSetDevice(c->device);
+	(void)hipStreamSynchronize(c->stream); // (passes enqueued earlier read the lists about to be freed)
+	c->ab.thaw();
+	c->pass_px = c->n_local_px; c->pass_image_px = c->n_image_px;
+	c->d_active_blocks.release(); c->d_active_slot.release(); c->d_frozen_at.release(); c->d_active_shift.release();
+}
+
+// The owned blocks among blocks[0 .. n) (image block indices) stop at `spp` frames.  The lists go to the device, the compact shift image is
+// gathered for the new active list, and the cache image is marked stale: its entries are in the order of the list that was.
+int freeze_blocks(adypt_ctx *c, const int32_t *blocks, size_t n, int spp)
+{
+	std::vector<int32_t> mine; // (several devices: the list is the image's)
+	for(size_t i = 0; i < n; ++i) if(spp >= 2 && c->ab.is_active(blocks[i])) mine.push_back(blocks[i]);
+	if(mine.empty()) return ADYPT_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	drop_lookahead(c); // (refused before anything was traced; frames started ahead belong to the list that was)
+	if(!c->d_active_blocks)
+	{
+		// before the state changes: a failure here leaves the context as it was
+		const size_t list = (size_t)c->n_local_blocks * sizeof(int32_t);
+		hipError_t e = c->d_active_blocks.alloc(list);
+		if(e == hipSuccess) e = c->d_active_slot.alloc(list);
+		if(e == hipSuccess) e = c->d_frozen_at.alloc(list);
+		if(e == hipSuccess) e = c->d_active_shift.alloc((size_t)c->n_local_px * 2);
+		if(e != hipSuccess)
+		{
+			c->d_active_blocks.release(); c->d_active_slot.release(); c->d_frozen_at.release(); c->d_active_shift.release();
+			(void)hipGetLastError();
+			return fail(c, e == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP, std::string("adypt_trace_adaptive: ") + hipGetErrorString(e));
+		}
+	}
+	// The device lists first, the host state afterwards: a failure on the way leaves a context whose passes are still the set's that was.  (If that set
+	// had frozen blocks its lists are half overwritten by then: such a context refuses to trace, as one that lost its queues does.)
+	ActiveBlocks next = c->ab;
+	next.freeze(mine, spp);
+	const size_t n_active = next.active.size();
+	const int next_px = (int)(n_active * kBlockPixels);
+	const int r = [&]() -> int {
+		HIP_TRY(c, hipMemcpy(c->d_frozen_at, next.frozen_at.data(), next.frozen_at.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+		if(n_active == 0) return ADYPT_OK;
+		HIP_TRY(c, hipMemcpy(c->d_active_blocks, next.active.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice));
+		HIP_TRY(c, hipMemcpy(c->d_active_slot, next.slot.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(k_gather_blocks<uint16_t>, dim3((unsigned)((next_px + 255) / 256)), dim3(256), 0, c->stream, (const uint16_t *)c->d_shift.get(), (const int32_t *)c->d_active_slot,
+		                   (uint16_t *)c->d_active_shift.get(), next_px);
+		HIP_TRY(c, hipGetLastError());
+		return ADYPT_OK;
+	}();
+	if(r != ADYPT_OK)
+	{
+		if(c->ab.any_frozen()) { c->queues_ok = false; c->error += " (the block lists of the frozen set are lost: destroy the context)"; }
+		else { c->d_active_blocks.release(); c->d_active_slot.release(); c->d_frozen_at.release(); c->d_active_shift.release(); }
+		return r;
+	}
+	c->ab = std::move(next);
+	c->pass_px = next_px;
+	c->pass_image_px = c->ab.active_image_px(c->width, c->height);
+	c->cache_stale = true;
+	return ADYPT_OK;
+}
+
+}  // namespace
 
 namespace adypt {
 
@@ -587,6 +667,27 @@ CtxInfo ctx_info(adypt_ctx *c)
 }
 void ctx_set_error(adypt_ctx *c, const std::string &msg) { c->error = msg; }
 void **ctx_comm_slot(adypt_ctx *c, void (***free_fn)(void *)) { *free_fn = &c->comm_free; return &c->comm; }
+int ctx_adaptive_ready(adypt_ctx *c, const char *fn)
+{
+	if(!c->noise_stats) return fail(c, ADYPT_E_STATE, std::string(fn) + ": the noise statistics are off (adypt_set_noise_stats)");
+	if(c->lookahead || c->ahead_count > 0)
+		return fail(c, ADYPT_E_STATE, std::string(fn) + ": look-ahead is enabled or frames are parked ahead: they belong to a block set that a check may change (adypt_set_lookahead(ctx, 0))");
+	return ADYPT_OK;
+}
+int ctx_freeze_blocks(adypt_ctx *c, const int32_t *blocks, size_t n, int spp) { return freeze_blocks(c, blocks, n, spp); }
+int ctx_read_blocks(adypt_ctx *c, std::vector<BlockState> *blocks)
+{
+	const size_t first = blocks->size(), n = (size_t)c->n_local_blocks;
+	if(n == 0) return ADYPT_OK;
+	std::vector<int32_t> index(n);
+	std::vector<double> sum(n);
+	std::vector<uint32_t> count(n);
+	const int64_t r = adypt_read_block_noise(c, index.data(), sum.data(), count.data(), (int64_t)n);
+	if(r < 0) return (int)r;
+	blocks->resize(first + n);
+	for(size_t i = 0; i < n; ++i) (*blocks)[first + i] = BlockState{index[i], sum[i], count[i], c->ab.spp_of(i, c->spp), c->ab.frozen_at[i] != 0};
+	return ADYPT_OK;
+}
 }  // namespace adypt
 
 namespace {
@@ -648,6 +749,8 @@ void set_shard(adypt_ctx *c, const adypt_scene_desc *d)
 		const int bx = blk % c->blocks_x, by = blk / c->blocks_x;
 		c->n_image_px += (int64_t)std::min(kBlockDim, c->width - bx * kBlockDim) * (int64_t)std::min(kBlockDim, c->height - by * kBlockDim);
 	}
+	c->ab.reset(c->local_blocks); // every block active: a pass is the owned blocks'
+	c->pass_px = c->n_local_px; c->pass_image_px = c->n_image_px;
 }
 
 // per-pixel images, ray queues, Sobol staging, counters and statistics
@@ -809,6 +912,7 @@ int adypt_reset(adypt_ctx *c)
 	c->pt_started = false;
 	c->spp = 0;
 	drop_lookahead(c);
+	thaw_blocks(c);
 	return ADYPT_OK;
 }
 
@@ -901,6 +1005,7 @@ int adypt_trace_primary(adypt_ctx *c, int viewer_type)
 	// Trace(false): leaves path-tracing mode (OglPathTracer.cpp:53-58)
 	c->pt_started = false; c->spp = 0;
 	drop_lookahead(c);
+	thaw_blocks(c); // a viewer frame is of every pixel
 	c->view_type = viewer_type;
 	TRY_CREATE(apply_params(c));
 	if(c->n_local_px == 0) return ADYPT_OK; // a tile shard that owns no 32x32 block (more ranks than block diagonals): nothing to render
@@ -936,10 +1041,11 @@ int adypt_trace_spp_async(adypt_ctx *c, int n_spp)
 	if(!c->have_camera) return fail(c, ADYPT_E_STATE, "adypt_trace_spp: call adypt_set_camera first");
 	if(!c->queues_ok) return fail(c, ADYPT_E_STATE, "adypt_trace_spp: the context lost its ray queues (failed adypt_set_frames_in_flight)");
 	ENTER(c);
-	if(c->n_local_px == 0)
+	if(c->pass_px == 0)
 	{
-		// a tile shard that owns no 32x32 block (more ranks than block diagonals, e.g. 64x36 on 4 ranks): the frame counter
-		// and the parameter hand-over advance like everywhere else, no kernel runs (they would divide by n_local_px)
+		// a tile shard that owns no 32x32 block (more ranks than block diagonals, e.g. 64x36 on 4 ranks), or one whose blocks are all frozen
+		// (adypt_trace_adaptive): the frame counter and the parameter hand-over advance like everywhere else, no kernel runs (they would
+		// divide by n_local_px)
 		if(n_spp > 0 && !c->pt_started)
 		{
 			TRY_CREATE(apply_params(c));
@@ -958,6 +1064,7 @@ int adypt_trace_spp_async(adypt_ctx *c, int n_spp)
 			const PassPlan p = plan_pass(plan_input(c, remaining));
 			r = p.kind == PassPlan::Rolling ? trace_rolling_frame(c, p, remaining > 1) : enqueue_batch(c, p);
 			done = p.hand_out;
+			if(r == ADYPT_OK) c->cache_stale = false; // (the pass has written the cache image of every group it touches for the current block set)
 		}
 		if(r != ADYPT_OK) return r;
 		remaining -= done;
@@ -997,6 +1104,7 @@ int adypt_read_hits(adypt_ctx *c, int32_t *tri, float *uv)
 	if(!c || !tri || !uv) return ADYPT_E_INVALID;
 	ENTER_DRAINED(c); // see adypt_read_radiance
 	if(c->n_local_px == 0) return ADYPT_OK;
+	if(c->ab.any_frozen()) return fail(c, ADYPT_E_STATE, "adypt_read_hits: blocks are frozen (adypt_trace_adaptive): the cached primary hits are kept in the order of the active blocks");
 	std::vector<float> local((size_t)c->n_local_px * 4);
 	HIP_TRY(c, hipMemcpy(local.data(), c->d_cache, local.size() * sizeof(float), hipMemcpyDeviceToHost));
 	for_each_local_pixel(c->local_blocks, c->width, c->height, [&](size_t L, int x, int y) {
@@ -1013,6 +1121,7 @@ int adypt_set_noise_stats(adypt_ctx *c, int enabled)
 {
 	if(!c) return ADYPT_E_INVALID;
 	if((enabled != 0) == (c->noise_stats != 0)) return ADYPT_OK;
+	if(!enabled && c->ab.any_frozen()) return fail(c, ADYPT_E_STATE, "adypt_set_noise_stats: blocks are frozen at the noise target (adypt_trace_adaptive): reset first");
 	if(enabled && c->spp != 0) return fail(c, ADYPT_E_STATE, "adypt_set_noise_stats: the moments start with the image: enable at 0 spp (after adypt_create, adypt_reset or adypt_trace_primary)");
 	ENTER_DRAINED(c); // (the running-mean kernels enqueued so far have left the moments)
 	if(!enabled)
@@ -1054,8 +1163,13 @@ int noise_ready(adypt_ctx *c, const char *who, int min_spp)
 int query_noise_blocks(adypt_ctx *c, std::vector<NoiseBlock> *blocks, bool per_pixel)
 {
 	if(per_pixel && !c->d_noise_e) HIP_TRY(c, c->d_noise_e.alloc((size_t)c->n_local_px * sizeof(float))); // once: the size never changes
-	hipLaunchKernelGGL(k_noise_blocks, dim3((unsigned)c->n_local_blocks), dim3(256), 0, c->stream, (const NoiseMoments *)c->d_noise_moments, (const int32_t *)c->d_local_blocks,
-	                   c->blocks_x, c->width, c->height, c->spp, c->d_noise_blocks.get(), per_pixel ? c->d_noise_e.get() : nullptr);
+	// every owned block in the owned order, whatever is frozen: a frozen block at the frames it stopped at (k_noise_blocks_spp)
+	if(c->ab.any_frozen())
+		hipLaunchKernelGGL(k_noise_blocks_spp<true>, dim3((unsigned)c->n_local_blocks), dim3(256), 0, c->stream, (const NoiseMoments *)c->d_noise_moments, (const int32_t *)c->d_local_blocks,
+		                   c->blocks_x, c->width, c->height, c->spp, (const int32_t *)c->d_frozen_at, c->d_noise_blocks.get(), per_pixel ? c->d_noise_e.get() : nullptr);
+	else
+		hipLaunchKernelGGL(k_noise_blocks, dim3((unsigned)c->n_local_blocks), dim3(256), 0, c->stream, (const NoiseMoments *)c->d_noise_moments, (const int32_t *)c->d_local_blocks,
+		                   c->blocks_x, c->width, c->height, c->spp, c->d_noise_blocks.get(), per_pixel ? c->d_noise_e.get() : nullptr);
 	HIP_TRY(c, hipGetLastError());
 	blocks->resize((size_t)c->n_local_blocks);
 	HIP_TRY(c, hipMemcpyAsync(blocks->data(), c->d_noise_blocks, blocks->size() * sizeof(NoiseBlock), hipMemcpyDeviceToHost, c->stream));
@@ -1143,6 +1257,27 @@ int adypt_trace_until(adypt_ctx *c, double target, int min_spp, int max_spp, int
 	std::string refused;
 	const int r = trace_until("adypt_trace_until", &refused, target, min_spp, max_spp, check_every, out, [c] { return c->spp; }, [c](int n) { return adypt_trace_spp(c, n); },
 	                          [c](adypt_noise *o) { return adypt_get_noise(c, o); });
+	return refused.empty() ? r : fail(c, r, refused);
+}
+
+int64_t adypt_read_block_spp(adypt_ctx *c, int32_t *block_index, int32_t *spp, int64_t capacity)
+{
+	if(!c || capacity < 0) return ADYPT_E_INVALID;
+	const int64_t n = c->n_local_blocks;
+	if(n == 0 || capacity < n) return n; // (the size alone: nothing is written)
+	if(!block_index || !spp) return ADYPT_E_INVALID;
+	for(int64_t i = 0; i < n; ++i) { block_index[i] = c->local_blocks[(size_t)i]; spp[i] = c->ab.spp_of((size_t)i, c->spp); }
+	return n;
+}
+
+int adypt_trace_adaptive(adypt_ctx *c, double target, int min_spp, int max_spp, int check_every, adypt_adaptive *out)
+{
+	if(!c) return ADYPT_E_INVALID;
+	TRY_CREATE(ctx_adaptive_ready(c, "adypt_trace_adaptive"));
+	std::string refused;
+	const int r = trace_adaptive("adypt_trace_adaptive", &refused, target, min_spp, max_spp, check_every, out, [c] { return c->spp; }, [c](int n) { return adypt_trace_spp(c, n); },
+	                             [c](std::vector<BlockState> *blocks) { blocks->clear(); return ctx_read_blocks(c, blocks); },
+	                             [c](const std::vector<int32_t> &stop, int spp) { return freeze_blocks(c, stop.data(), stop.size(), spp); });
 	return refused.empty() ? r : fail(c, r, refused);
 }
 

@@ -241,6 +241,30 @@ int64_t adypt_read_block_noise(adypt_ctx *ctx, int32_t *block_index, double *sum
  * bit-identical to adypt_trace_spp to the same adypt_get_spp, with look-ahead on or off and any frames in flight. */
 int adypt_trace_until(adypt_ctx *ctx, double target, int min_spp, int max_spp, int check_every, adypt_noise *out);
 
+/* ---- adaptive sampling: blocks that reached the noise target stop being traced ----------------------------------------------
+ * An owned 32x32 block is ACTIVE or FROZEN at spp_b.  Active blocks advance in lockstep with the frame counter (adypt_get_spp); a frozen block
+ * keeps, bit for bit, the pixels, moments and noise of the uniform image at spp_b frames (samples are independent per pixel and indexed by frame).
+ * adypt_trace_adaptive: traces min(check_every, max_spp - spp) frames of the active blocks, reads the block noise (each block at its own sample
+ * count) and, once the counter is at or above min_spp, freezes every active block with sum / count <= target (adypt_read_block_noise's binary64
+ * values; worst_block's comparison taken per block); it ends when no block is active or the counter reaches max_spp.
+ * A frozen block stays frozen until adypt_reset or adypt_trace_primary, which thaw everything; every tracing call in between (adypt_trace_spp[_async],
+ * adypt_trace_until, another adypt_trace_adaptive, also with a lower target) traces the active blocks only, and adypt_set_camera without a reset
+ * keeps the set as it keeps the image.  With every block frozen the counter advances and no kernel runs.  With no block frozen every launch is what
+ * it is without this call.  The read-outs (radiance, display, noise, moments, the gathers) are unchanged: the persistent images keep their order;
+ * adypt_read_hits answers ADYPT_E_STATE while blocks are frozen (the cached primary hits are then kept in the order of the active blocks).
+ * ADYPT_E_STATE: the statistics are off; look-ahead is enabled or frames are parked ahead (they belong to a block set that a check may change).
+ * ADYPT_E_INVALID, nothing traced: the argument rules of adypt_trace_until.  adypt_set_noise_stats(ctx, 0) while blocks are frozen: ADYPT_E_STATE
+ * (reset first).  Memory: 2 B per local pixel + 12 B per owned block, allocated on the first freeze, given back by the thaw. */
+typedef struct adypt_adaptive {
+	adypt_noise noise;              /* of all blocks, each at its own sample count; noise.spp = the frame counter */
+	int32_t blocks, blocks_frozen;  /* owned blocks (multi: of the image) */
+	int64_t pixel_samples;          /* sum over blocks of (pixels inside the image) x (the block's sample count) */
+} adypt_adaptive;
+int adypt_trace_adaptive(adypt_ctx *ctx, double target, int min_spp, int max_spp, int check_every, adypt_adaptive *out);
+/* The sample count of every owned block, ascending block index: spp_b of a frozen block, the frame counter of an active one.  Returns the number
+ * of owned blocks and writes the arrays only when capacity holds them all, like adypt_read_block_noise; works with the statistics off. */
+int64_t adypt_read_block_spp(adypt_ctx *ctx, int32_t *block_index, int32_t *spp, int64_t capacity);
+
 /* Trace an arbitrary batch of rays through the same traversal kernel: rays = n x 8 floats
  * (ox, oy, oz, tmin, dx, dy, dz, unused).  with_stats selects the instrumented kernel variant. */
 int adypt_trace_rays(adypt_ctx *ctx, const float *rays, int64_t n, adypt_hit *hits, int with_stats);
@@ -330,6 +354,11 @@ int adypt_multi_set_noise_stats(adypt_multi *m, int enabled);
 int adypt_multi_get_noise(adypt_multi *m, adypt_noise *out);
 int adypt_multi_read_noise(adypt_multi *m, float *e);     /* every device writes the pixels of its own tiles */
 int adypt_multi_trace_until(adypt_multi *m, double target, int min_spp, int max_spp, int check_every, adypt_noise *out);
+/* adypt_trace_adaptive over the whole image: every device decides about its own blocks from its own block noise (no collective), the host merges
+ * the blocks as adypt_multi_get_noise does; the loop ends when no device has an active block, or at max_spp.  The N-device result equals the
+ * one-device result.  (One process per GPU: every rank calls adypt_trace_adaptive on its own context and ends
+ * when its own blocks are frozen, so the ranks' counters differ afterwards; a rank that owns no block runs to max_spp.) */
+int adypt_multi_trace_adaptive(adypt_multi *m, double target, int min_spp, int max_spp, int check_every, adypt_adaptive *out);
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

@@ -178,6 +178,16 @@ public:
 		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
 		return false;
 	}
+	// Adaptive sampling: as TraceUntil, but every 32x32 block stops at the check at which ITS mean noise is at or below `target`; ends when every block
+	// has stopped or at max_spp.  Stopped blocks stay so (later Trace(true) calls pass them over) until a Trace(false) or a reset of the accumulation.
+	bool TraceAdaptive(double target, int min_spp, int max_spp, int check_every, adypt_adaptive *out = nullptr)
+	{
+		if(adypt_multi_get_spp(m_gpus) == 0) update_config_args();
+		m_viewer_type = kPTRadiance;
+		if(adypt_multi_trace_adaptive(m_gpus, target, min_spp, max_spp, check_every, out) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
 
 	// what DrawScreen puts on screen, for a caller-owned W x H RGBA8 texture / window (every device fills in its own tiles)
 	bool ReadScreen(std::vector<uint8_t> *rgba8) const
