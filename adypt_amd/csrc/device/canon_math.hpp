@@ -83,6 +83,15 @@ __device__ __forceinline__ float rcp_ieee(float x)
 	return 1.0f / x;
 }
 __device__ __forceinline__ F3 normalize3(F3 a) { float inv = rcp_ieee(sqrtf(dot3(a, a))); return a * inv; }
+// Which axes of the slab test read a node's hi plane for the near distance (traversal.glsl:92-99): those with idir < 0 — NOT dir < 0, which is what the octant is made of
+// (traversal.glsl:22).  The two part at dir = -0 (idir = -inf), which normalize leaves of a negative component when the squared length overflows binary32
+// (tests/test_gpu_rcp_division_rays.py).  The compare reads an opaque copy (an empty asm, no instruction): comparing idir in place, the traversal loop's register
+// allocation comes out with two more v_mov per stack pop (profiles/r6_trip_budget.json, block A_pop: 6 in place, 3 through the copy, 4 before idir was compared at all).
+__device__ __forceinline__ void slab_swaps(F3 idir, bool &nx, bool &ny, bool &nz)
+{
+	asm volatile("" : "+v"(idir.x), "+v"(idir.y), "+v"(idir.z));
+	nx = idir.x < 0; ny = idir.y < 0; nz = idir.z < 0;
+}
 __device__ __forceinline__ F3 reflect3(F3 i, F3 n) { float k = 2.0f * dot3(n, i); return fma3(n, -k, i); }
 // (the helpers below that rewrite EXEC or use SDWA encodings — or_if_le, exp_byte, shl_bytes, traverse_trip.inc's acceptance steps — are GFX9-family wave64 code: v_cmpx writes
 // VCC and EXEC, a lane mask is 64 bits, SDWA exists.  The Makefile's ARCH / HIPFLAGS overrides cannot turn this file into something else silently.)

@@ -354,8 +354,8 @@ __device__ __forceinline__ void trace_loop(const TraceArgs a)
 				dir.z = fabsf(dir.z) > ooeps ? dir.z : (dir.z >= 0 ? ooeps : -ooeps);
 				dir = normalize3(dir);
 				idir = f3(rcp_ieee(dir.x), rcp_ieee(dir.y), rcp_ieee(dir.z));
-				nx = dir.x < 0; ny = dir.y < 0; nz = dir.z < 0;
-				octinv = 7u - ((nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u));
+				octinv = 7u - ((dir.x < 0 ? 1u : 0u) | (dir.y < 0 ? 2u : 0u) | (dir.z < 0 ? 4u : 0u));
+				slab_swaps(idir, nx, ny, nz);
 				F3 origin = f3(ro.x, ro.y, ro.z);
 				if(!CAMERA) tmin = ro.w;
 				// make the ray loads complete inside this (rare) refill block: otherwise the compiler's s_waitcnt

@@ -1067,4 +1067,26 @@ ORC_API void orc_scatter(const void *materials, const float *normal, const float
 	}
 }
 
-ORC_API int orc_abi_version(void) { return 2; }
+// normalize (canonical: v * (1 / sqrt(dot3(v, v)))) for n vectors
+ORC_API void orc_normalize3(const float *v, int64_t n, float *out)
+{
+	for(int64_t i = 0; i < n; ++i)
+	{
+		V3 r = normalize3(v3(v[i * 3], v[i * 3 + 1], v[i * 3 + 2]));
+		out[i * 3] = r.x; out[i * 3 + 1] = r.y; out[i * 3 + 2] = r.z;
+	}
+}
+// the texture fetch of FetchInfo (GL_LINEAR / GL_REPEAT) of one w x h RGB8 texture at n coordinates (s, t).  A NaN coordinate is the
+// caller's to avoid: its conversion to int is undefined here.
+ORC_API void orc_sample_texture(const uint8_t *rgb, int w, int h, const float *s, const float *t, int64_t n, float *out)
+{
+	const OrcTexture tex{w, h, rgb};
+	Counters cn;
+	for(int64_t i = 0; i < n; ++i)
+	{
+		V3 r = sample_texture(tex, s[i], t[i], cn);
+		out[i * 3] = r.x; out[i * 3 + 1] = r.y; out[i * 3 + 2] = r.z;
+	}
+}
+
+ORC_API int orc_abi_version(void) { return 3; }

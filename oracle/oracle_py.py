@@ -71,7 +71,7 @@ def lib():
         build()
         _lib = C.CDLL(_LIB_PATH)
         _lib.orc_abi_version.restype = C.c_int
-        assert _lib.orc_abi_version() == 2
+        assert _lib.orc_abi_version() == 3
     return _lib
 
 
@@ -280,6 +280,27 @@ def scatter(materials: np.ndarray, normal: np.ndarray, dir_in: np.ndarray, r: np
     assert len(m) == len(nrm) == len(d) == len(rr)
     out = np.empty((len(m), 8), dtype=np.float32)
     lib().orc_scatter(_p(m), _p(nrm), _p(d), _p(rr), C.c_int(len(m)), _p(out))
+    return out
+
+
+def normalize3(v: np.ndarray) -> np.ndarray:
+    """canonical normalize: v * (1 / sqrt(dot3(v, v))) — test hook."""
+    v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
+    out = np.empty_like(v)
+    lib().orc_normalize3(_p(v), C.c_int64(len(v)), _p(out))
+    return out
+
+
+def sample_texture(rgb: np.ndarray, s: np.ndarray, t: np.ndarray) -> np.ndarray:
+    """The diffuse texture fetch of FetchInfo (GL_LINEAR / GL_REPEAT, RGB8) of one (h, w, 3) uint8 texture at coordinates (s, t) — test
+    hook.  No NaN coordinates: their conversion to int is undefined on the CPU."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3 and rgb.shape[0] > 0 and rgb.shape[1] > 0
+    s = np.ascontiguousarray(s, dtype=np.float32).reshape(-1)
+    t = np.ascontiguousarray(t, dtype=np.float32).reshape(-1)
+    assert len(s) == len(t) and not np.isnan(s).any() and not np.isnan(t).any()
+    out = np.empty((len(s), 3), dtype=np.float32)
+    lib().orc_sample_texture(_p(rgb), C.c_int(rgb.shape[1]), C.c_int(rgb.shape[0]), _p(s), _p(t), C.c_int64(len(s)), _p(out))
     return out
 
 
