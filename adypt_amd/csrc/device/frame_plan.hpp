@@ -70,7 +70,7 @@ inline PassPlan plan_pass(const PlanInput &in)
 	// A single frame (no look-ahead, or one frame in flight) runs as a batch of one — camera launch, k_shade_first, k_path, k_resolve: 4 launches
 	// instead of 1 + 2 x maxBounce — whenever a batch would take the one-launch pipeline (ADYPT_SINGLE_FUSED=0: the launch-per-bounce frame)
 	p.kind = (p.m == 1 && in.single_fused && one_launch_ok(in, 1, 1)) ? PassPlan::Rolling : PassPlan::Batch;
-	// (with the noise statistics on the lone launch-per-bounce frame is a batch of one too: it keeps its launches, its sample goes through k_resolve_noise)
+	// (with the noise statistics on the lone launch-per-bounce frame is a batch of one too: it keeps its launches, its sample goes through k_resolve<true, *>)
 	const bool lone = p.m == 1 && p.kind != PassPlan::Rolling;
 	p.as_batch = !lone || in.noise_stats != 0;
 	p.use_cache = p.as_batch || !p.n_retrace;

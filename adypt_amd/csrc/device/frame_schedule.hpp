@@ -20,15 +20,17 @@ PassArgs pass_args(const adypt_ctx *c)
 	return a;
 }
 
-// The running-mean kernel over frames [first, first + count) of `f`'s parked samples, on the context's stream: k_resolve, or with the noise
-// statistics on its sibling that keeps the luminance moments as well (noise.hpp); while blocks are frozen (they are only with the statistics on) that
-// sibling with the slot map from the pass's pixels to the owned blocks' (active_blocks.hpp)
+// The running-mean kernel over frames [first, first + count) of `f`'s parked samples, on the context's stream: with the noise statistics on the
+// instance that keeps the luminance moments as well (noise.hpp); while blocks are frozen (they are only with the statistics on) the one with the slot
+// map from the pass's pixels to the owned blocks' (active_blocks.hpp)
 void launch_resolve(adypt_ctx *c, const FrameArgs &f, const PassArgs &a, int first, int count)
 {
 	const dim3 grid((c->pass_px + 255) / 256), block(256);
-	if(c->ab.any_frozen()) hipLaunchKernelGGL(k_resolve_noise_slots<true>, grid, block, 0, c->stream, f, a.sc, a.px, c->d_noise_moments.get(), (const int32_t *)c->d_active_slot, first, count);
-	else if(c->noise_stats) hipLaunchKernelGGL(k_resolve_noise, grid, block, 0, c->stream, f, a.sc, a.px, c->d_noise_moments.get(), first, count);
-	else hipLaunchKernelGGL(k_resolve, grid, block, 0, c->stream, f, a.sc, a.px, first, count);
+	NoiseMoments *const no_moments = nullptr;
+	const int32_t *const no_slot = nullptr;
+	if(c->ab.any_frozen()) hipLaunchKernelGGL((k_resolve<true, true>), grid, block, 0, c->stream, f, a.sc, a.px, c->d_noise_moments.get(), (const int32_t *)c->adaptive.slot, first, count);
+	else if(c->noise_stats) hipLaunchKernelGGL((k_resolve<true, false>), grid, block, 0, c->stream, f, a.sc, a.px, c->d_noise_moments.get(), no_slot, first, count);
+	else hipLaunchKernelGGL((k_resolve<false, false>), grid, block, 0, c->stream, f, a.sc, a.px, no_moments, no_slot, first, count);
 }
 
 // Running-mean step (pathtracer.glsl:224-226) of frames [first, first + count) of the batch last traced (its finished samples

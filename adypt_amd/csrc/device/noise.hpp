@@ -4,7 +4,7 @@
 // restatement of these lines is bit-exact.
 //
 // Per pixel the luminance Y of every clamped sample that the running mean takes in is folded, in frame order, into (mean, m2) by Welford's
-// update; k_resolve_noise (shade.hpp) does that next to the running mean, k_noise_blocks turns the moments into numbers when somebody asks.
+// update; k_resolve<true, *> (shade.hpp) does that next to the running mean, k_noise_blocks turns the moments into numbers when somebody asks.
 #pragma once
 #include <cmath>
 #include <cstddef>

@@ -6,7 +6,9 @@
 //   k_shade             one bounce of Render(): FetchInfo, scatter, compaction, accumulate on termination
 //                                                                       (shaders/pathtracer.glsl:73-204,224-226)
 //   viewer_color        primary-ray viewer colouring, called by k_trace_camera when a ray has finished (shaders/primaryray.glsl:50-94)
-//   k_resolve, k_display, k_untile   running mean in frame order; the window's display transform; compact block-major radiance -> W x H RGB
+//   k_resolve<MOMENTS, SLOTS>, k_display, k_untile   running mean in frame order (with the noise moments; over a shrunken block set); the window's
+//                                       display transform; compact block-major radiance -> W x H RGB
+//   k_gather_blocks, k_noise_blocks<PER_BLOCK>   compact copy of a per-pixel image for the active blocks; the noise of every owned block
 //
 // Ray queue = 8 XCD-affine segments.  Workgroups are dealt round-robin over the 8 XCDs (each with a private 4 MB
 // L2), so workgroup b of every kernel works on segment b & 7: rays stay with "their" XCD from bounce to bounce, the
@@ -294,40 +296,31 @@ __global__ __launch_bounds__(kShadeThreads) void k_gen_primary(FrameArgs f, Scen
 // Applies finished samples of a batch to the running mean in frame order (pathtracer.glsl:224-226): batch frames
 // [first, first + count); f.spp = index of the batch's first frame.  The whole batch at once, or — when the caller asks for
 // one frame per call and the batch was traced ahead (adypt_set_lookahead) — a few frames per call.
-__global__ __launch_bounds__(256) void k_resolve(FrameArgs f, SceneArgs sc, PixelArgs px, int first, int count)
+// MOMENTS (adypt_set_noise_stats): the luminance moments of noise.hpp are carried through the same loop — every clamped sample passes here exactly
+// once, in frame order.  The frame with global index 0 starts the moments from zero: they are cleared where the image is, without a memset.
+// SLOTS (a pass over a shrunken block set, active_blocks.hpp): f.n_local_px, sc.local_blocks and done[] are the pass's (active blocks), accum and
+// the moments stay in owned-block order — pass-local pixel P is owned pixel slot[P >> 10] * 1024 + (P & 1023).
+// An instance is given null for what it does not read (`moments`, `slot`).  Three instances: blocks freeze only with the noise statistics on.
+template <bool MOMENTS, bool SLOTS> __global__ __launch_bounds__(256) void k_resolve(FrameArgs f, SceneArgs sc, PixelArgs px, NoiseMoments *moments, const int32_t *slot, int first, int count)
 {
-	const int L = blockIdx.x * blockDim.x + threadIdx.x;
+	static_assert(MOMENTS || !SLOTS, "blocks freeze only with the noise statistics on");
+	const int P = blockIdx.x * blockDim.x + threadIdx.x;
 	int x, y;
-	if(L >= f.n_local_px || !local_pixel_xy(f, sc.local_blocks, L, &x, &y)) return;
+	if(P >= f.n_local_px || !local_pixel_xy(f, sc.local_blocks, P, &x, &y)) return;
+	size_t L = (size_t)P;
+	if constexpr(SLOTS) L = (size_t)slot[P >> 10] * kBlockPixels + (size_t)(P & 1023);
 	float4 acc = px.accum[L];
+	[[maybe_unused]] NoiseMoments m{0.0f, 0.0f};
+	if constexpr(MOMENTS) m = f.spp + first == 0 ? NoiseMoments{0.0f, 0.0f} : moments[L];
 	for(int k = first; k < first + count; ++k)
 	{
-		const float4 r = f.done[(size_t)k * f.n_local_px + L];
+		const float4 r = f.done[(size_t)k * f.n_local_px + P];
 		const float fs = (float)(f.spp + k), fs1 = (float)(f.spp + k + 1);
 		acc = make_float4(fmaf(acc.x, fs, r.x) / fs1, fmaf(acc.y, fs, r.y) / fs1, fmaf(acc.z, fs, r.z) / fs1, 1.0f);
+		if constexpr(MOMENTS) m = noise_add_sample(m, f.spp + k, r.x, r.y, r.z);
 	}
 	px.accum[L] = acc;
-}
-
-// k_resolve with the noise statistics on (adypt_set_noise_stats): the same running mean, and the luminance moments of noise.hpp carried through
-// the same loop — every clamped sample passes here exactly once, in frame order.  The frame with global index 0 starts the moments from zero:
-// they are cleared where the image is, without a memset.
-__global__ __launch_bounds__(256) void k_resolve_noise(FrameArgs f, SceneArgs sc, PixelArgs px, NoiseMoments *moments, int first, int count)
-{
-	const int L = blockIdx.x * blockDim.x + threadIdx.x;
-	int x, y;
-	if(L >= f.n_local_px || !local_pixel_xy(f, sc.local_blocks, L, &x, &y)) return;
-	float4 acc = px.accum[L];
-	NoiseMoments m = f.spp + first == 0 ? NoiseMoments{0.0f, 0.0f} : moments[L];
-	for(int k = first; k < first + count; ++k)
-	{
-		const float4 r = f.done[(size_t)k * f.n_local_px + L];
-		const float fs = (float)(f.spp + k), fs1 = (float)(f.spp + k + 1);
-		acc = make_float4(fmaf(acc.x, fs, r.x) / fs1, fmaf(acc.y, fs, r.y) / fs1, fmaf(acc.z, fs, r.z) / fs1, 1.0f);
-		m = noise_add_sample(m, f.spp + k, r.x, r.y, r.z);
-	}
-	px.accum[L] = acc;
-	moments[L] = m;
+	if constexpr(MOMENTS) moments[L] = m;
 }
 
 __device__ __forceinline__ int pos_mod(int a, int n) { int r = a % n; return r < 0 ? r + n : r; }
@@ -841,16 +834,28 @@ __global__ void k_untile(const float4 *local, const int32_t *local_blocks, int n
 	o[0] = v.x; o[1] = v.y; o[2] = v.z;
 }
 
+// dst[P] = src[slot[P >> 10] * 1024 + (P & 1023)] for the n_px = active blocks x 1024 pass-local pixels P: the compact copy of a per-pixel image
+// for the active list (the shift image, 2 bytes per pixel: T = uint16_t), rebuilt whenever the set changes.  slot[] < owned blocks (ActiveBlocks::slot).
+template <class T> __global__ __launch_bounds__(256) void k_gather_blocks(const T *src, const int32_t *slot, T *dst, int n_px)
+{
+	const int P = blockIdx.x * blockDim.x + threadIdx.x;
+	if(P >= n_px) return;
+	dst[P] = src[(size_t)slot[P >> 10] * kBlockPixels + (size_t)(P & 1023)];
+}
+
 // The noise of every owned block after `spp` >= 2 frames (noise.hpp): one workgroup of 256 threads per block, thread t takes the block's pixels
 // t, t + 256, t + 512, t + 768 in that order; the sums (binary64) are added across the lanes of a wave by a butterfly, then across the four
 // waves in wave order by thread 0 — a fixed order, so two runs give the same bits.  Pixels outside the image count for nothing.
-// `e_out` (may be null): the per-pixel noise, one float per local pixel, 0 outside the image.
-__global__ __launch_bounds__(256) void k_noise_blocks(const NoiseMoments *moments, const int32_t *local_blocks, int blocks_x, int width, int height, int spp,
-                                                      NoiseBlock *out, float *e_out)
+// PER_BLOCK (while blocks are frozen): a sample count per owned block — frozen_at[b] != 0 = owned block b stopped at that many frames, else it
+// holds `spp`; without, `frozen_at` is null.  `e_out` (may be null): the per-pixel noise, one float per local pixel, 0 outside the image.
+template <bool PER_BLOCK> __global__ __launch_bounds__(256) void k_noise_blocks(const NoiseMoments *moments, const int32_t *local_blocks, int blocks_x, int width, int height, int spp,
+                                                                               const int32_t *frozen_at, NoiseBlock *out, float *e_out)
 {
 	__shared__ double wave_sum[4];
 	__shared__ uint32_t wave_count[4];
 	const int blk = local_blocks[blockIdx.x];
+	int n = spp;
+	if constexpr(PER_BLOCK) { const int at = frozen_at[blockIdx.x]; n = at ? at : spp; }
 	double sum = 0.0;
 	uint32_t count = 0;
 #pragma unroll
@@ -861,7 +866,7 @@ __global__ __launch_bounds__(256) void k_noise_blocks(const NoiseMoments *moment
 		int x, y;
 		block_pixel_xy(blk, in, blocks_x, &x, &y);
 		const bool inside = x < width && y < height;
-		const float e = inside ? noise_of_pixel(moments[L], spp) : 0.0f;
+		const float e = inside ? noise_of_pixel(moments[L], n) : 0.0f;
 		if(inside) { sum += (double)e; ++count; }
 		if(e_out) e_out[L] = e;
 	}

@@ -311,7 +311,7 @@ int launch_trace(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, int par
 }
 
 // the block list of a pass: the owned blocks, or the active ones among them while blocks are frozen (active_blocks.hpp)
-const int32_t *pass_blocks(const adypt_ctx *c) { return c->ab.any_frozen() ? (const int32_t *)c->d_active_blocks : (const int32_t *)c->d_local_blocks; }
+const int32_t *pass_blocks(const adypt_ctx *c) { return c->ab.any_frozen() ? (const int32_t *)c->adaptive.blocks : (const int32_t *)c->d_local_blocks; }
 
 void fill_frame(const adypt_ctx *c, FrameArgs *f)
 {
@@ -339,7 +339,7 @@ void fill_scene(const adypt_ctx *c, SceneArgs *s)
 }
 void fill_pixels(const adypt_ctx *c, PixelArgs *p)
 {
-	p->accum = c->d_accum; p->cache = c->d_cache; p->cache_next = c->d_cache_next; p->shift = c->ab.any_frozen() ? c->d_active_shift.get() : c->d_shift.get(); p->stats = c->d_stats;
+	p->accum = c->d_accum; p->cache = c->d_cache; p->cache_next = c->d_cache_next; p->shift = c->ab.any_frozen() ? c->adaptive.shift.get() : c->d_shift.get(); p->stats = c->d_stats;
 }
 // slots per segment that `frames` frames of `px` pixels need (multiple of kShadeThreads)
 uint32_t seg_slots_px(int px, int frames)
@@ -531,14 +531,21 @@ int apply_params(adypt_ctx *c)
 }  // namespace
 
 #include "scene_upload.hpp"
-#include "adaptive_kernels.hpp" // (templates: emitted where they are first used — behind every other kernel template, see there)
 #include "frame_schedule.hpp"
 
 namespace {
 
+// what every entry point of the noise statistics asks first: they are on, and the image has `min_spp` frames
+int noise_ready(adypt_ctx *c, const char *who, int min_spp)
+{
+	if(!c->noise_stats) return fail(c, ADYPT_E_STATE, std::string(who) + ": the noise statistics are off (adypt_set_noise_stats)");
+	if(c->spp < min_spp) return fail(c, ADYPT_E_STATE, std::string(who) + ": needs at least " + std::to_string(min_spp) + " spp");
+	return ADYPT_OK;
+}
+
 // ---- adaptive sampling: the block set of a pass (active_blocks.hpp) ----
 
-// Every block active again (adypt_reset, adypt_trace_primary): passes are the owned blocks' and the four buffers go back.  The cache image is
+// Every block active again (adypt_reset, adypt_trace_primary): passes are the owned blocks' and the device lists go back.  The cache image is
 // written again before it is read: both callers restart the accumulation, whose first frame re-traces its camera rays.
 void thaw_blocks(adypt_ctx *c)
 {
@@ -548,7 +555,7 @@ void thaw_blocks(adypt_ctx *c)
 	(void)hipStreamSynchronize(c->stream); // (passes enqueued earlier read the lists about to be freed)
 	c->ab.thaw();
 	c->pass_px = c->n_local_px; c->pass_image_px = c->n_image_px;
-	c->d_active_blocks.release(); c->d_active_slot.release(); c->d_frozen_at.release(); c->d_active_shift.release();
+	c->adaptive = AdaptiveBuffers{};
 }
 
 // The owned blocks among blocks[0 .. n) (image block indices) stop at `spp` frames.  The lists go to the device, the compact shift image is
@@ -561,17 +568,12 @@ int freeze_blocks(adypt_ctx *c, const int32_t *blocks, size_t n, int spp)
 	HIP_TRY(c, hipSetDevice(c->device));
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
 	drop_lookahead(c); // (refused before anything was traced; frames started ahead belong to the list that was)
-	if(!c->d_active_blocks)
+	if(!c->adaptive)
 	{
 		// before the state changes: a failure here leaves the context as it was
-		const size_t list = (size_t)c->n_local_blocks * sizeof(int32_t);
-		hipError_t e = c->d_active_blocks.alloc(list);
-		if(e == hipSuccess) e = c->d_active_slot.alloc(list);
-		if(e == hipSuccess) e = c->d_frozen_at.alloc(list);
-		if(e == hipSuccess) e = c->d_active_shift.alloc((size_t)c->n_local_px * 2);
+		const hipError_t e = c->adaptive.alloc((size_t)c->n_local_blocks, (size_t)c->n_local_px);
 		if(e != hipSuccess)
 		{
-			c->d_active_blocks.release(); c->d_active_slot.release(); c->d_frozen_at.release(); c->d_active_shift.release();
 			(void)hipGetLastError();
 			return fail(c, e == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP, std::string("adypt_trace_adaptive: ") + hipGetErrorString(e));
 		}
@@ -583,19 +585,19 @@ int freeze_blocks(adypt_ctx *c, const int32_t *blocks, size_t n, int spp)
 	const size_t n_active = next.active.size();
 	const int next_px = (int)(n_active * kBlockPixels);
 	const int r = [&]() -> int {
-		HIP_TRY(c, hipMemcpy(c->d_frozen_at, next.frozen_at.data(), next.frozen_at.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+		HIP_TRY(c, hipMemcpy(c->adaptive.frozen_at, next.frozen_at.data(), next.frozen_at.size() * sizeof(int32_t), hipMemcpyHostToDevice));
 		if(n_active == 0) return ADYPT_OK;
-		HIP_TRY(c, hipMemcpy(c->d_active_blocks, next.active.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice));
-		HIP_TRY(c, hipMemcpy(c->d_active_slot, next.slot.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice));
-		hipLaunchKernelGGL(k_gather_blocks<uint16_t>, dim3((unsigned)((next_px + 255) / 256)), dim3(256), 0, c->stream, (const uint16_t *)c->d_shift.get(), (const int32_t *)c->d_active_slot,
-		                   (uint16_t *)c->d_active_shift.get(), next_px);
+		HIP_TRY(c, hipMemcpy(c->adaptive.blocks, next.active.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice));
+		HIP_TRY(c, hipMemcpy(c->adaptive.slot, next.slot.data(), n_active * sizeof(int32_t), hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(k_gather_blocks<uint16_t>, dim3((unsigned)((next_px + 255) / 256)), dim3(256), 0, c->stream, (const uint16_t *)c->d_shift.get(), (const int32_t *)c->adaptive.slot,
+		                   (uint16_t *)c->adaptive.shift.get(), next_px);
 		HIP_TRY(c, hipGetLastError());
 		return ADYPT_OK;
 	}();
 	if(r != ADYPT_OK)
 	{
 		if(c->ab.any_frozen()) { c->queues_ok = false; c->error += " (the block lists of the frozen set are lost: destroy the context)"; }
-		else { c->d_active_blocks.release(); c->d_active_slot.release(); c->d_frozen_at.release(); c->d_active_shift.release(); }
+		else c->adaptive = AdaptiveBuffers{};
 		return r;
 	}
 	c->ab = std::move(next);
@@ -669,7 +671,7 @@ void ctx_set_error(adypt_ctx *c, const std::string &msg) { c->error = msg; }
 void **ctx_comm_slot(adypt_ctx *c, void (***free_fn)(void *)) { *free_fn = &c->comm_free; return &c->comm; }
 int ctx_adaptive_ready(adypt_ctx *c, const char *fn)
 {
-	if(!c->noise_stats) return fail(c, ADYPT_E_STATE, std::string(fn) + ": the noise statistics are off (adypt_set_noise_stats)");
+	TRY_CREATE(noise_ready(c, fn, 0));
 	if(c->lookahead || c->ahead_count > 0)
 		return fail(c, ADYPT_E_STATE, std::string(fn) + ": look-ahead is enabled or frames are parked ahead: they belong to a block set that a check may change (adypt_set_lookahead(ctx, 0))");
 	return ADYPT_OK;
@@ -1151,25 +1153,20 @@ int adypt_get_noise_stats(const adypt_ctx *c) { return c ? c->noise_stats : ADYP
 
 namespace {
 
-int noise_ready(adypt_ctx *c, const char *who, int min_spp)
-{
-	if(!c->noise_stats) return fail(c, ADYPT_E_STATE, std::string(who) + ": the noise statistics are off (adypt_set_noise_stats)");
-	if(c->spp < min_spp) return fail(c, ADYPT_E_STATE, std::string(who) + ": needs at least " + std::to_string(min_spp) + " spp");
-	return ADYPT_OK;
-}
-
 // k_noise_blocks behind the pending running-mean kernels on the context's stream; the block results on the host when the call returns.
 // per_pixel: the per-pixel noise is left in d_noise_e as well.  n_local_px > 0.
 int query_noise_blocks(adypt_ctx *c, std::vector<NoiseBlock> *blocks, bool per_pixel)
 {
 	if(per_pixel && !c->d_noise_e) HIP_TRY(c, c->d_noise_e.alloc((size_t)c->n_local_px * sizeof(float))); // once: the size never changes
-	// every owned block in the owned order, whatever is frozen: a frozen block at the frames it stopped at (k_noise_blocks_spp)
+	// every owned block in the owned order, whatever is frozen: a frozen block at the frames it stopped at
+	const dim3 grid((unsigned)c->n_local_blocks), block(256);
+	const NoiseMoments *moments = c->d_noise_moments;
+	const int32_t *owned = c->d_local_blocks, *no_count = nullptr;
+	float *e_out = per_pixel ? c->d_noise_e.get() : nullptr;
 	if(c->ab.any_frozen())
-		hipLaunchKernelGGL(k_noise_blocks_spp<true>, dim3((unsigned)c->n_local_blocks), dim3(256), 0, c->stream, (const NoiseMoments *)c->d_noise_moments, (const int32_t *)c->d_local_blocks,
-		                   c->blocks_x, c->width, c->height, c->spp, (const int32_t *)c->d_frozen_at, c->d_noise_blocks.get(), per_pixel ? c->d_noise_e.get() : nullptr);
+		hipLaunchKernelGGL(k_noise_blocks<true>, grid, block, 0, c->stream, moments, owned, c->blocks_x, c->width, c->height, c->spp, (const int32_t *)c->adaptive.frozen_at, c->d_noise_blocks.get(), e_out);
 	else
-		hipLaunchKernelGGL(k_noise_blocks, dim3((unsigned)c->n_local_blocks), dim3(256), 0, c->stream, (const NoiseMoments *)c->d_noise_moments, (const int32_t *)c->d_local_blocks,
-		                   c->blocks_x, c->width, c->height, c->spp, c->d_noise_blocks.get(), per_pixel ? c->d_noise_e.get() : nullptr);
+		hipLaunchKernelGGL(k_noise_blocks<false>, grid, block, 0, c->stream, moments, owned, c->blocks_x, c->width, c->height, c->spp, no_count, c->d_noise_blocks.get(), e_out);
 	HIP_TRY(c, hipGetLastError());
 	blocks->resize((size_t)c->n_local_blocks);
 	HIP_TRY(c, hipMemcpyAsync(blocks->data(), c->d_noise_blocks, blocks->size() * sizeof(NoiseBlock), hipMemcpyDeviceToHost, c->stream));
@@ -1253,7 +1250,7 @@ int64_t adypt_read_block_noise(adypt_ctx *c, int32_t *block_index, double *sum, 
 int adypt_trace_until(adypt_ctx *c, double target, int min_spp, int max_spp, int check_every, adypt_noise *out)
 {
 	if(!c) return ADYPT_E_INVALID;
-	if(!c->noise_stats) return fail(c, ADYPT_E_STATE, "adypt_trace_until: the noise statistics are off (adypt_set_noise_stats)");
+	TRY_CREATE(noise_ready(c, "adypt_trace_until", 0));
 	std::string refused;
 	const int r = trace_until("adypt_trace_until", &refused, target, min_spp, max_spp, check_every, out, [c] { return c->spp; }, [c](int n) { return adypt_trace_spp(c, n); },
 	                          [c](adypt_noise *o) { return adypt_get_noise(c, o); });

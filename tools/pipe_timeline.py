@@ -8,9 +8,9 @@ if sys.argv[1] == "--analyse":
     rows = []
     for f in glob.glob(sys.argv[2] + "/**/*kernel_trace.csv", recursive=True):
         for r in csv.DictReader(open(f)):
-            rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("adypt::", ""), r.get("Queue_Id", "?"), r.get("Stream_Id", "?")))
+            rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("adypt::", "").removeprefix("void "), r.get("Queue_Id", "?"), r.get("Stream_Id", "?")))
     rows.sort()
-    # the last k_resolve ends the last batch; the batch starts after the previous k_resolve
+    # the last k_resolve ends the last batch; the batch starts after the previous k_resolve (a template instance is printed as "void k_resolve<...>")
     res = [i for i, r in enumerate(rows) if r[2].startswith("k_resolve")]
     a, b = res[-2] + 1, res[-1] + 1
     batch = rows[a:b]
