@@ -75,6 +75,11 @@ class Adaptive(C.Structure):
         return d
 
 
+class DenoiseParams(C.Structure):
+    """adypt_denoise_params."""
+    _fields_ = [("levels", C.c_int32), ("sigma_l", C.c_float), ("sigma_z", C.c_float)]
+
+
 class BvhParams(C.Structure):
     _fields_ = [("max_spatial_depth", C.c_int32), ("triangle_sah", C.c_float), ("node_sah", C.c_float)]
 
@@ -148,6 +153,14 @@ _SIGS = {
     "adypt_multi_get_noise": (C.c_int, [C.c_void_p, C.POINTER(Noise)]),
     "adypt_multi_read_noise": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_trace_until": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Noise)]),
+    # denoising
+    "adypt_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams)]),
+    "adypt_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_read_denoise_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adypt_get_denoise_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
+    "adypt_multi_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams)]),
+    "adypt_multi_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_multi_read_denoise_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),

@@ -514,6 +514,32 @@ class _Tracer:
             out[by * 32:(by + 1) * 32, bx * 32:(bx + 1) * 32] = n
         return out
 
+    # ---- denoising (adypt_denoise, include/adypt_hip.h; the definition: csrc/device/denoise.hpp); several devices: of the whole image ----
+    def Denoise(self, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 0.1) -> np.ndarray:
+        """H x W x 3 float32: the accumulated image through the variance- and primary-hit-guided a-trous filter.  Needs the noise statistics on and
+        >= 2 spp in every block; the image, the statistics and the tracing state are left as they are."""
+        prm = N.DenoiseParams(levels, sigma_l, sigma_z)
+        self._call("denoise", C.byref(prm))
+        rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        self._call("read_denoised", rgb.ctypes.data)
+        return rgb
+
+    def ReadDenoiseGuides(self) -> dict:
+        """The feature images of the pixel-centre camera ray under the current camera: albedo, normal, position (H x W x 3 float32) and hit (H x W bool)."""
+        a, n, p = (np.zeros((self.height, self.width, 3), dtype=np.float32) for _ in range(3))
+        hit = np.zeros((self.height, self.width), dtype=np.uint8)
+        self._call("read_denoise_guides", a.ctypes.data, n.ctypes.data, p.ctypes.data, hit.ctypes.data)
+        return {"albedo": a, "normal": n, "position": p, "hit": hit.astype(bool)}
+
+    def GetDenoiseTiming(self) -> dict:
+        """HIP-event milliseconds of the last Denoise() on the (first) device: guides (0 with several devices: the upload instead), prepare, levels."""
+        ms = (C.c_float * 16)()
+        c = self._contexts()[0]
+        n = N.lib.adypt_get_denoise_timing(c, ms, 16)
+        if n < 0:
+            N.check(n, c)
+        return {"guides": ms[0], "prepare": ms[1], "levels": [ms[i] for i in range(2, n)], "total": sum(ms[i] for i in range(n))}
+
     def ReadDisplay(self) -> np.ndarray:
         """What OglPathTracer::DrawScreen puts on screen (shaders/screen.glsl:15-21): H x W x 4 uint8; every context converts its own tiles."""
         rgba = np.zeros((self.height, self.width, 4), dtype=np.uint8)

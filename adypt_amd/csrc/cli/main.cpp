@@ -4,7 +4,7 @@
 //
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
-//             [--adaptive [--spp-out file.exr]]]
+//             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX]
 //   --sun-visibility: enable the occlusion query the reference has commented out (pathtracer.glsl:132)
 //   --preview: what the reference shows in its window (shaders/screen.glsl), as PNG
 //   --devices: pixel tiles sharded over several GPUs of the node (adypt_create_multi), radiance gathered on the first one
@@ -15,6 +15,9 @@
 //              (default 16) samples.  --noise-out: the per-pixel noise as a grey EXR
 //   --adaptive: with --noise T, every 32x32 block stops being traced at the check at which ITS mean noise is at or below T (adypt_multi_trace_adaptive);
 //              the render ends when every block has stopped, or at --spp.  --spp-out: the per-pixel sample count as a grey EXR
+//   --denoise file.exr: the image through the variance- and primary-hit-guided a-trous filter (adypt_multi_denoise) next to --out; switches the noise
+//              statistics on before the first sample, as --noise does; needs --spp >= 2 and no --primary.  --denoise-levels L: 1 .. 6 levels (default 5)
+//   --guides-out PREFIX: the feature images of the primary hit as PREFIX.albedo.exr, PREFIX.normal.exr and PREFIX.position.exr
 #include "adypt_hip.h"
 #include "adypt_host.h"
 
@@ -33,10 +36,11 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
-	std::string noise_out, spp_out;
+	std::string noise_out, spp_out, denoise_out, guides_out;
+	int denoise_levels = 5;
 	int adaptive = 0;
 	int spp = 64, fp16 = 0, primary = -1, sun_visibility = 0, save_every = 0;
 	std::vector<int> devices(1, 0);
@@ -75,6 +79,9 @@ int main(int argc, char **argv)
 		else if(a == "--noise-out" && i + 1 < argc) noise_out = argv[++i];
 		else if(a == "--adaptive") adaptive = 1;
 		else if(a == "--spp-out" && i + 1 < argc) spp_out = argv[++i];
+		else if(a == "--denoise" && i + 1 < argc) denoise_out = argv[++i];
+		else if(a == "--denoise-levels" && i + 1 < argc) denoise_levels = atoi(argv[++i]);
+		else if(a == "--guides-out" && i + 1 < argc) guides_out = argv[++i];
 		else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
 	}
 	const bool until = noise_target >= 0.0;
@@ -82,6 +89,9 @@ int main(int argc, char **argv)
 	if(until && (primary >= 0 || spp < 2 || check_every < 1)) { fprintf(stderr, "--noise needs --spp >= 2, --check-every >= 1 and no --primary\n"); return 2; }
 	if(adaptive && (!until || save_every > 0)) { fprintf(stderr, "--adaptive needs --noise T and does not combine with --save-every\n"); return 2; }
 	if(!adaptive && !spp_out.empty()) { fprintf(stderr, "--spp-out needs --adaptive\n"); return 2; }
+	const bool denoise = !denoise_out.empty();
+	if(denoise && (primary >= 0 || spp < 2)) { fprintf(stderr, "--denoise needs --spp >= 2 and no --primary\n"); return 2; }
+	if(denoise && (denoise_levels < 1 || denoise_levels > 6)) { fprintf(stderr, "--denoise-levels must be in 1 .. 6\n"); return 2; }
 	if(until) min_spp = std::max(2, std::min(min_spp, spp));
 	adypt_config cfg;
 	adypt_config_default(&cfg);
@@ -130,7 +140,7 @@ int main(int argc, char **argv)
 	if(r == ADYPT_OK) r = adypt_multi_set_camera(multi, cfg.position, ip, iv);
 	if(r == ADYPT_OK && sun_visibility) r = adypt_multi_set_sun_visibility(multi, 1, nullptr);
 	if(r == ADYPT_OK) r = adypt_multi_set_instrumentation(multi, 1);
-	if(r == ADYPT_OK && until) r = adypt_multi_set_noise_stats(multi, 1);
+	if(r == ADYPT_OK && (until || denoise)) r = adypt_multi_set_noise_stats(multi, 1);
 	if(r != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
 
 	std::vector<float> rgb((size_t)cfg.width * cfg.height * 3, 0.0f);
@@ -243,6 +253,24 @@ int main(int argc, char **argv)
 			printf("[PT]ADAPTIVE: spp %d frozen %d of %d pixel_samples %lld (uniform %lld) mean_noise %.9g worst_block %.9g worst_index %d (target %.9g)\n", noise.spp, adapt.blocks_frozen,
 			       adapt.blocks, (long long)adapt.pixel_samples, (long long)noise.spp * (long long)cfg.width * (long long)cfg.height, noise.mean_noise, noise.worst_block, noise.worst_index, noise_target);
 		else printf("[PT]NOISE: spp %d mean_noise %.9g worst_block %.9g worst_index %d (target %.9g)\n", noise.spp, noise.mean_noise, noise.worst_block, noise.worst_index, noise_target);
+	}
+	if(denoise)
+	{
+		const adypt_denoise_params dp{denoise_levels, 4.0f, 0.1f};
+		std::vector<float> den((size_t)cfg.width * cfg.height * 3, 0.0f);
+		if(adypt_multi_denoise(multi, &dp) != ADYPT_OK || adypt_multi_read_denoised(multi, den.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		if(adypt_save_exr(denoise_out.c_str(), den.data(), cfg.width, cfg.height, fp16) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
+		printf("[PT]INFO: Saved denoised image (%d levels) to %s\n", denoise_levels, denoise_out.c_str());
+	}
+	if(!guides_out.empty())
+	{
+		std::vector<float> g[3];
+		for(auto &v : g) v.assign((size_t)cfg.width * cfg.height * 3, 0.0f);
+		if(adypt_multi_read_denoise_guides(multi, g[0].data(), g[1].data(), g[2].data(), nullptr) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		const char *const what[3] = {".albedo.exr", ".normal.exr", ".position.exr"};
+		for(int k = 0; k < 3; ++k)
+			if(adypt_save_exr((guides_out + what[k]).c_str(), g[k].data(), cfg.width, cfg.height, 0) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
+		printf("[PT]INFO: Saved guide images to %s.{albedo,normal,position}.exr\n", guides_out.c_str());
 	}
 	adypt_destroy_multi(multi);
 	adypt_bvh_free(bvh);

@@ -192,6 +192,9 @@ struct adypt_ctx {
 	// RCCL communicator state of the native multi-GPU path (multi.hip owns and frees it)
 	void *comm = nullptr;
 	void (*comm_free)(void *) = nullptr;
+	// the denoiser's images (denoise.hip owns and frees them): allocated at the first adypt_denoise / adypt_read_denoise_guides
+	void *denoise = nullptr;
+	void (*denoise_free)(void *) = nullptr;
 
 	double trace_ms = 0, shade_ms = 0, path_ms = 0;
 	uint32_t trace_launches = 0, path_launches = 0;

@@ -7,6 +7,7 @@
 #include <vector>
 
 struct adypt_ctx;
+struct adypt_multi;
 
 namespace adypt {
 
@@ -30,5 +31,23 @@ void **ctx_comm_slot(adypt_ctx *c, void (***free_fn)(void *));
 int ctx_adaptive_ready(adypt_ctx *c, const char *fn);
 int ctx_read_blocks(adypt_ctx *c, std::vector<BlockState> *blocks);
 int ctx_freeze_blocks(adypt_ctx *c, const int32_t *blocks, size_t n, int spp);
+
+// The denoiser (denoise.hip), per context.  slot: where its images are parked (freed by adypt_destroy through *free_fn).  ready: ADYPT_OK, or
+// ADYPT_E_STATE with the reason in the context's error (statistics off, a viewer's image, a block below 2 spp).  inputs: the block-major local images
+// the filter reads and every owned block's sample count.  capture_guides: see tracer.hip.
+struct DenoiseInputs {
+	const float4 *accum;               // running mean per local pixel
+	const float2 *moments;             // luminance (mean, m2) per local pixel
+	const int32_t *blocks;             // device: image block index of every owned block
+	int n_blocks;
+	std::vector<int32_t> block_index;  // host copy of `blocks`
+	std::vector<int32_t> block_spp;    // samples in every owned block
+};
+void **ctx_denoise_slot(adypt_ctx *c, void (***free_fn)(void *));
+int ctx_denoise_ready(adypt_ctx *c, const char *fn);
+DenoiseInputs ctx_denoise_inputs(adypt_ctx *c);
+int ctx_capture_guides(adypt_ctx *c, const char *fn, float4 *albedo, float4 *normal, float4 *position, float4 *hits);
+// multi.hip: the message adypt_multi_last_error answers
+void multi_set_error(adypt_multi *m, const std::string &msg);
 
 }  // namespace adypt

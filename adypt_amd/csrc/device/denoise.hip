@@ -1,0 +1,406 @@
+// The denoiser (include/adypt_hip.h adypt_denoise ...; the definition: denoise.hpp).  A translation unit of its own: nothing here is part of the
+// tracer's code object.  What runs, all on the context's stream behind the frames:
+//     guide capture  three launches of the viewer instance of k_trace_camera over the owned blocks (tracer.hip ctx_capture_guides), into scratch
+//                    owned here: albedo, normal, position, primary hit — block-major like every local image
+//     k_denoise_prepare  block-major accum / moments / block sample counts / guides  ->  row-major float4 images X0 = (D0.rgb, V0), X1 = (N.xyz, hit),
+//                    X2 = (P.xyz, .), XA = (A.rgb, .)
+//     k_atrous<LAST>  one level per launch, X0 ping-pongs; the last level multiplies the albedo back and writes the W x H x 3 result
+// Several devices: every context captures the guides of its own blocks, the host merges the local images by block index (every block has one owner)
+// into the block-major images of the WHOLE picture, uploads them to the first device and runs the same two kernels there — no collective; the result
+// is the one-device result bit for bit because the inputs are.
+#include "ctx_access.hpp"
+#include "resources.hpp"
+#include "tile_layout.hpp"
+#include "denoise.hpp"
+#include "../../../include/adypt_hip.h"
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+using namespace adypt;
+
+namespace {
+
+__global__ __launch_bounds__(256) void k_denoise_prepare(const float4 *accum, const float2 *moments, const int32_t *blocks, const int32_t *block_spp, int n_px, int blocks_x, int width,
+                                                         int height, const float4 *g_albedo, const float4 *g_normal, const float4 *g_position, const float4 *g_hits, float4 *x0,
+                                                         float4 *x1, float4 *x2, float4 *xa)
+{
+	const int L = blockIdx.x * blockDim.x + threadIdx.x;
+	if(L >= n_px) return;
+	int x, y;
+	block_pixel_xy(blocks[L >> 10], L & 1023, blocks_x, &x, &y);
+	if(x >= width || y >= height) return; // (blocks at the right and bottom edge stick out)
+	const size_t p = (size_t)y * width + x;
+	const float4 c = accum[L], a = g_albedo[L], n = g_normal[L], q = g_position[L];
+	const Dn4 d = denoise_prepare(c.x, c.y, c.z, moments[L].y, (float)block_spp[L >> 10], a.x, a.y, a.z);
+	x0[p] = make_float4(d.x, d.y, d.z, d.w);
+	x1[p] = make_float4(n.x, n.y, n.z, __float_as_int(g_hits[L].x) != -1 ? 1.0f : 0.0f);
+	x2[p] = make_float4(q.x, q.y, q.z, 0.0f);
+	xa[p] = make_float4(a.x, a.y, a.z, 0.0f);
+}
+
+struct DeviceImages {
+	const float4 *a, *b, *c;
+	__device__ __forceinline__ static Dn4 load(const float4 *p, int i) { const float4 v = p[i]; return Dn4{v.x, v.y, v.z, v.w}; }
+	__device__ __forceinline__ Dn4 x0(int i) const { return load(a, i); }
+	__device__ __forceinline__ Dn4 x1(int i) const { return load(b, i); }
+	__device__ __forceinline__ Dn4 x2(int i) const { return load(c, i); }
+};
+
+constexpr int kAtrousX = 32, kAtrousY = 8; // a workgroup = 32 x 8 pixels: a wave reads two rows of 32 pixels x 16 bytes
+
+// one pixel per thread; plain global loads (three 16-byte loads per tap): at these sizes the working set (48 B per pixel read) sits in the L2 / Infinity Cache
+template <bool LAST>
+__global__ __launch_bounds__(kAtrousX * kAtrousY) void k_atrous(const float4 *x0, const float4 *x1, const float4 *x2, const float4 *xa, float4 *x0_out, float *rgb, int width, int height,
+                                                                 int step, float sigma_l, float sigma_z)
+{
+	const int x = blockIdx.x * kAtrousX + threadIdx.x, y = blockIdx.y * kAtrousY + threadIdx.y;
+	if(x >= width || y >= height) return;
+	const DeviceImages img{x0, x1, x2};
+	const Dn4 r = denoise_level(img, width, height, x, y, step, sigma_l, sigma_z);
+	const size_t p = (size_t)y * width + x;
+	if(LAST)
+	{
+		float out[3];
+		denoise_remodulate(r, DeviceImages::load(xa, (int)p), out);
+		rgb[p * 3] = out[0]; rgb[p * 3 + 1] = out[1]; rgb[p * 3 + 2] = out[2];
+	}
+	else x0_out[p] = make_float4(r.x, r.y, r.z, r.w);
+}
+
+// the block-major images of a set of blocks on one device: a context's own (accum and moments are then the context's) or the merged ones of all devices
+struct LocalImages {
+	const float4 *accum; const float2 *moments; const int32_t *blocks, *block_spp;
+	const float4 *albedo, *normal, *position, *hits;
+	int n_blocks;
+};
+
+constexpr int kTimingEvents = 3 + kDenoiseMaxLevels; // start, guides, prepare, every level
+
+// Everything the denoiser keeps per context; parked in adypt_ctx::denoise, freed by adypt_destroy (the context's device is current then).
+struct Denoiser {
+	int width = 0, height = 0;
+	// guide scratch of the owned blocks, block-major: 64 B per local pixel + 4 B per owned block
+	Buffer<float4> g_albedo, g_normal, g_position, g_hits;
+	Buffer<int32_t> d_block_spp;
+	// the filter's row-major images of the whole picture: 80 B + 12 B (the result) per image pixel
+	Buffer<float4> x0[2], x1, x2, xa;
+	Buffer<float> rgb;
+	bool have_result = false;
+	// several devices: the merged block-major images of the whole picture on the first device (88 B per pixel of the blocks + 8 B per block)
+	Buffer<float4> m_accum, m_albedo, m_normal, m_position, m_hits;
+	Buffer<float2> m_moments;
+	Buffer<int32_t> m_blocks, m_block_spp;
+	Event ev[kTimingEvents];
+	int levels_timed = 0;
+};
+
+void free_denoiser(void *p) { delete (Denoiser *)p; }
+
+int cfail(adypt_ctx *c, int code, const std::string &msg) { ctx_set_error(c, msg); return code; }
+
+#define DN_TRY(c, expr)                                                                                     \
+	do {                                                                                                    \
+		const hipError_t e_ = (expr);                                                                       \
+		if(e_ != hipSuccess) { (void)hipGetLastError(); return cfail(c, e_ == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } \
+	} while(0)
+#define DN_STEP(expr) do { const int r_ = (expr); if(r_ != ADYPT_OK) return r_; } while(0)
+
+Denoiser *denoiser_of(adypt_ctx *c)
+{
+	void (**free_fn)(void *) = nullptr;
+	void **slot = ctx_denoise_slot(c, &free_fn);
+	if(!*slot) { *slot = new Denoiser(); *free_fn = free_denoiser; }
+	return (Denoiser *)*slot;
+}
+Denoiser *denoiser_if_any(adypt_ctx *c)
+{
+	void (**free_fn)(void *) = nullptr;
+	return (Denoiser *)*ctx_denoise_slot(c, &free_fn);
+}
+
+template <class T> int ensure(adypt_ctx *c, Buffer<T> &b, size_t n)
+{
+	const size_t bytes = std::max<size_t>(n * sizeof(T), 64);
+	if(b.bytes() >= bytes) return ADYPT_OK;
+	DN_TRY(c, b.alloc(bytes));
+	return ADYPT_OK;
+}
+
+// the guide scratch of the context's own blocks (allocated at the first call: the size never changes)
+int ensure_guides(adypt_ctx *c, Denoiser *d, const CtxInfo &i)
+{
+	const size_t n = (size_t)std::max(i.n_local_px, 64);
+	DN_STEP(ensure(c, d->g_albedo, n)); DN_STEP(ensure(c, d->g_normal, n)); DN_STEP(ensure(c, d->g_position, n)); DN_STEP(ensure(c, d->g_hits, n));
+	return ensure(c, d->d_block_spp, (size_t)std::max(i.n_local_px / kBlockPixels, 1));
+}
+
+int ensure_filter_images(adypt_ctx *c, Denoiser *d, const CtxInfo &i)
+{
+	const size_t n = (size_t)i.width * (size_t)i.height;
+	d->width = i.width; d->height = i.height;
+	DN_STEP(ensure(c, d->x0[0], n)); DN_STEP(ensure(c, d->x0[1], n)); DN_STEP(ensure(c, d->x1, n)); DN_STEP(ensure(c, d->x2, n)); DN_STEP(ensure(c, d->xa, n));
+	DN_STEP(ensure(c, d->rgb, n * 3));
+	for(Event &e : d->ev) if(!(hipEvent_t)e) DN_TRY(c, hipEventCreate(e.out()));
+	return ADYPT_OK;
+}
+
+// prepare + the levels, on `stream`; d's images are the whole picture's (ensure_filter_images)
+int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages &in, const DenoiseParams &prm)
+{
+	const int width = d->width, height = d->height, n_px = in.n_blocks * kBlockPixels;
+	const int blocks_x = (width + kBlockDim - 1) / kBlockDim;
+	hipLaunchKernelGGL(k_denoise_prepare, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, stream, in.accum, in.moments, in.blocks, in.block_spp, n_px, blocks_x, width, height, in.albedo,
+	                   in.normal, in.position, in.hits, d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get());
+	DN_TRY(c, hipGetLastError());
+	DN_TRY(c, hipEventRecord(d->ev[2], stream));
+	const dim3 grid((unsigned)((width + kAtrousX - 1) / kAtrousX), (unsigned)((height + kAtrousY - 1) / kAtrousY)), block(kAtrousX, kAtrousY);
+	for(int l = 0; l < prm.levels; ++l)
+	{
+		const float4 *src = d->x0[l & 1];
+		float4 *dst = d->x0[(l & 1) ^ 1];
+		if(l == prm.levels - 1)
+			hipLaunchKernelGGL(k_atrous<true>, grid, block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
+		else
+			hipLaunchKernelGGL(k_atrous<false>, grid, block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
+		DN_TRY(c, hipGetLastError());
+		DN_TRY(c, hipEventRecord(d->ev[3 + l], stream));
+	}
+	d->levels_timed = prm.levels;
+	DN_TRY(c, hipStreamSynchronize(stream));
+	d->have_result = true;
+	return ADYPT_OK;
+}
+
+int params_of(const adypt_denoise_params *p, DenoiseParams *out, std::string *why, const char *fn)
+{
+	*out = p ? DenoiseParams{p->levels, p->sigma_l, p->sigma_z} : kDenoiseDefaults;
+	if(denoise_params_valid(*out)) return ADYPT_OK;
+	*why = std::string(fn) + ": levels must be in [1, " + std::to_string(kDenoiseMaxLevels) + "], sigma_l and sigma_z positive numbers";
+	return ADYPT_E_INVALID;
+}
+
+// the context's guides into its own scratch, enqueued behind its frames
+int capture_guides(adypt_ctx *c, Denoiser *d, const CtxInfo &i, const char *fn)
+{
+	DN_STEP(ensure_guides(c, d, i));
+	return ctx_capture_guides(c, fn, d->g_albedo, d->g_normal, d->g_position, d->g_hits);
+}
+
+int read_result(adypt_ctx *c, const char *fn, float *rgb)
+{
+	Denoiser *d = denoiser_if_any(c);
+	if(!d || !d->have_result) return cfail(c, ADYPT_E_STATE, std::string(fn) + ": nothing has been denoised yet (adypt_denoise)");
+	const CtxInfo i = ctx_info(c);
+	DN_TRY(c, hipSetDevice(i.device));
+	DN_TRY(c, hipMemcpyAsync(rgb, d->rgb, (size_t)d->width * d->height * 3 * sizeof(float), hipMemcpyDeviceToHost, i.stream));
+	DN_TRY(c, hipStreamSynchronize(i.stream));
+	return ADYPT_OK;
+}
+
+// one block-major local image of a context on the host (the stream is drained when it returns)
+template <class T> int fetch(adypt_ctx *c, const CtxInfo &i, const T *device, std::vector<T> *host)
+{
+	host->resize((size_t)i.n_local_px);
+	if(host->empty()) return ADYPT_OK;
+	DN_TRY(c, hipMemcpyAsync(host->data(), device, host->size() * sizeof(T), hipMemcpyDeviceToHost, i.stream));
+	DN_TRY(c, hipStreamSynchronize(i.stream));
+	return ADYPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int adypt_denoise(adypt_ctx *c, const adypt_denoise_params *p)
+{
+	if(!c) return ADYPT_E_INVALID;
+	DenoiseParams prm;
+	std::string why;
+	if(params_of(p, &prm, &why, "adypt_denoise") != ADYPT_OK) return cfail(c, ADYPT_E_INVALID, why);
+	const CtxInfo i = ctx_info(c);
+	if(i.nranks != 1) return cfail(c, ADYPT_E_STATE, "adypt_denoise: the context is a tile shard (tile_nranks > 1): the filter needs the whole image (adypt_multi_denoise)");
+	DN_STEP(ctx_denoise_ready(c, "adypt_denoise"));
+	DN_TRY(c, hipSetDevice(i.device));
+	Denoiser *d = denoiser_of(c);
+	DN_STEP(ensure_filter_images(c, d, i));
+	DN_STEP(ensure_guides(c, d, i));
+	d->have_result = false;
+	DN_TRY(c, hipEventRecord(d->ev[0], i.stream));
+	DN_STEP(capture_guides(c, d, i, "adypt_denoise"));
+	DN_TRY(c, hipEventRecord(d->ev[1], i.stream));
+	const DenoiseInputs in = ctx_denoise_inputs(c);
+	DN_TRY(c, hipMemcpyAsync(d->d_block_spp, in.block_spp.data(), in.block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
+	const LocalImages local{in.accum, in.moments, in.blocks, d->d_block_spp, d->g_albedo, d->g_normal, d->g_position, d->g_hits, in.n_blocks};
+	return run_filter(c, d, i.stream, local, prm);
+}
+
+int adypt_read_denoised(adypt_ctx *c, float *rgb)
+{
+	if(!c || !rgb) return ADYPT_E_INVALID;
+	return read_result(c, "adypt_read_denoised", rgb);
+}
+
+int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float *position, uint8_t *hit)
+{
+	if(!c) return ADYPT_E_INVALID;
+	const CtxInfo i = ctx_info(c);
+	if(i.n_local_px == 0) return ADYPT_OK; // a shard that owns no block
+	DN_TRY(c, hipSetDevice(i.device));
+	Denoiser *d = denoiser_of(c);
+	DN_STEP(capture_guides(c, d, i, "adypt_read_denoise_guides"));
+	const std::vector<int32_t> blocks = owned_blocks(i.width, i.height, i.rank, i.nranks);
+	std::vector<float4> local;
+	float *const image[3] = {albedo, normal, position};
+	const float4 *const device[3] = {d->g_albedo, d->g_normal, d->g_position};
+	for(int k = 0; k < 3; ++k)
+	{
+		if(!image[k]) continue;
+		DN_STEP(fetch(c, i, device[k], &local));
+		for_each_local_pixel(blocks, i.width, i.height, [&](size_t L, int x, int y) {
+			float *o = image[k] + ((size_t)y * i.width + x) * 3;
+			o[0] = local[L].x; o[1] = local[L].y; o[2] = local[L].z;
+		});
+	}
+	if(hit)
+	{
+		DN_STEP(fetch(c, i, (const float4 *)d->g_hits, &local));
+		for_each_local_pixel(blocks, i.width, i.height, [&](size_t L, int x, int y) {
+			int32_t tri;
+			memcpy(&tri, &local[L].x, 4);
+			hit[(size_t)y * i.width + x] = tri != -1 ? 1 : 0;
+		});
+	}
+	DN_TRY(c, hipStreamSynchronize(i.stream));
+	return ADYPT_OK;
+}
+
+int adypt_get_denoise_timing(adypt_ctx *c, float *ms, int capacity)
+{
+	if(!c || !ms || capacity < 0) return ADYPT_E_INVALID;
+	Denoiser *d = denoiser_if_any(c);
+	if(!d || !d->have_result) return cfail(c, ADYPT_E_STATE, "adypt_get_denoise_timing: nothing has been denoised yet (adypt_denoise)");
+	const int n = 2 + d->levels_timed;
+	if(capacity < n) return n;
+	for(int k = 0; k < n; ++k)
+	{
+		ms[k] = 0.0f;
+		(void)hipEventElapsedTime(&ms[k], d->ev[k], d->ev[k + 1]); // (several devices: no capture was timed on this context; the entry stays 0)
+	}
+	(void)hipGetLastError();
+	return n;
+}
+
+// ---- one process, N devices ----
+
+int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p)
+{
+	const int n_dev = adypt_multi_device_count(m);
+	if(n_dev < 1) return ADYPT_E_INVALID;
+	adypt_ctx *root = adypt_multi_context(m, 0);
+	if(n_dev == 1)
+	{
+		const int r = adypt_denoise(root, p);
+		if(r != ADYPT_OK) multi_set_error(m, adypt_last_error(root));
+		return r;
+	}
+	auto fail_ctx = [m](adypt_ctx *c, int r) { multi_set_error(m, adypt_last_error(c)); return r; };
+	DenoiseParams prm;
+	std::string why;
+	if(params_of(p, &prm, &why, "adypt_multi_denoise") != ADYPT_OK) { multi_set_error(m, why); return ADYPT_E_INVALID; }
+	std::vector<adypt_ctx *> ctx;
+	for(int k = 0; k < n_dev; ++k) ctx.push_back(adypt_multi_context(m, k));
+	for(adypt_ctx *c : ctx) { const int r = ctx_denoise_ready(c, "adypt_multi_denoise"); if(r != ADYPT_OK) return fail_ctx(c, r); }
+	// every device captures the guides of its own blocks: all enqueued before the first is waited for
+	for(adypt_ctx *c : ctx)
+	{
+		const CtxInfo i = ctx_info(c);
+		if(i.n_local_px == 0) continue;
+		int r = hipSetDevice(i.device) == hipSuccess ? ADYPT_OK : cfail(c, ADYPT_E_HIP, "adypt_multi_denoise: hipSetDevice failed");
+		if(r == ADYPT_OK) r = capture_guides(c, denoiser_of(c), i, "adypt_multi_denoise");
+		if(r != ADYPT_OK) return fail_ctx(c, r);
+	}
+	// the local images of every device merged by block index: block b of the picture at place b of the merged block-major images
+	const CtxInfo ri = ctx_info(root);
+	const int n_blocks = ((ri.width + kBlockDim - 1) / kBlockDim) * ((ri.height + kBlockDim - 1) / kBlockDim);
+	const size_t n_px = (size_t)n_blocks * kBlockPixels;
+	std::vector<float4> accum(n_px), albedo(n_px), normal(n_px), position(n_px), hits(n_px), local;
+	std::vector<float2> moments(n_px), local2;
+	std::vector<int32_t> blocks((size_t)n_blocks), block_spp((size_t)n_blocks, 0);
+	for(int b = 0; b < n_blocks; ++b) blocks[(size_t)b] = b;
+	for(adypt_ctx *c : ctx)
+	{
+		const CtxInfo i = ctx_info(c);
+		if(i.n_local_px == 0) continue;
+		if(hipSetDevice(i.device) != hipSuccess) return fail_ctx(c, cfail(c, ADYPT_E_HIP, "adypt_multi_denoise: hipSetDevice failed"));
+		Denoiser *d = denoiser_of(c);
+		const DenoiseInputs in = ctx_denoise_inputs(c);
+		auto scatter = [&](const auto &from, auto &to) {
+			for(size_t k = 0; k < in.block_index.size(); ++k)
+				std::copy(from.begin() + (ptrdiff_t)(k * kBlockPixels), from.begin() + (ptrdiff_t)((k + 1) * kBlockPixels), to.begin() + (ptrdiff_t)((size_t)in.block_index[k] * kBlockPixels));
+		};
+		const float4 *const device[5] = {in.accum, d->g_albedo, d->g_normal, d->g_position, d->g_hits};
+		std::vector<float4> *const merged[5] = {&accum, &albedo, &normal, &position, &hits};
+		for(int k = 0; k < 5; ++k)
+		{
+			const int r = fetch(c, i, device[k], &local);
+			if(r != ADYPT_OK) return fail_ctx(c, r);
+			scatter(local, *merged[k]);
+		}
+		const int r = fetch(c, i, in.moments, &local2);
+		if(r != ADYPT_OK) return fail_ctx(c, r);
+		scatter(local2, moments);
+		for(size_t k = 0; k < in.block_index.size(); ++k) block_spp[(size_t)in.block_index[k]] = in.block_spp[k];
+	}
+	// ... uploaded to the first device, where the same prepare / a-trous launches run
+	adypt_ctx *c = root;
+	auto steps = [&]() -> int {
+		DN_TRY(c, hipSetDevice(ri.device));
+		Denoiser *d = denoiser_of(c);
+		DN_STEP(ensure_filter_images(c, d, ri));
+		d->have_result = false;
+		DN_STEP(ensure(c, d->m_accum, n_px)); DN_STEP(ensure(c, d->m_albedo, n_px)); DN_STEP(ensure(c, d->m_normal, n_px)); DN_STEP(ensure(c, d->m_position, n_px));
+		DN_STEP(ensure(c, d->m_hits, n_px)); DN_STEP(ensure(c, d->m_moments, n_px)); DN_STEP(ensure(c, d->m_blocks, (size_t)n_blocks)); DN_STEP(ensure(c, d->m_block_spp, (size_t)n_blocks));
+		DN_TRY(c, hipEventRecord(d->ev[0], ri.stream));
+		DN_TRY(c, hipMemcpyAsync(d->m_accum, accum.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
+		DN_TRY(c, hipMemcpyAsync(d->m_albedo, albedo.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
+		DN_TRY(c, hipMemcpyAsync(d->m_normal, normal.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
+		DN_TRY(c, hipMemcpyAsync(d->m_position, position.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
+		DN_TRY(c, hipMemcpyAsync(d->m_hits, hits.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
+		DN_TRY(c, hipMemcpyAsync(d->m_moments, moments.data(), n_px * sizeof(float2), hipMemcpyHostToDevice, ri.stream));
+		DN_TRY(c, hipMemcpyAsync(d->m_blocks, blocks.data(), blocks.size() * sizeof(int32_t), hipMemcpyHostToDevice, ri.stream));
+		DN_TRY(c, hipMemcpyAsync(d->m_block_spp, block_spp.data(), block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, ri.stream));
+		DN_TRY(c, hipEventRecord(d->ev[1], ri.stream));
+		const LocalImages all{d->m_accum, d->m_moments, d->m_blocks, d->m_block_spp, d->m_albedo, d->m_normal, d->m_position, d->m_hits, n_blocks};
+		return run_filter(c, d, ri.stream, all, prm);
+	};
+	const int r = steps();
+	return r == ADYPT_OK ? r : fail_ctx(root, r);
+}
+
+int adypt_multi_read_denoised(adypt_multi *m, float *rgb)
+{
+	if(adypt_multi_device_count(m) < 1 || !rgb) return ADYPT_E_INVALID;
+	adypt_ctx *root = adypt_multi_context(m, 0);
+	const int r = read_result(root, "adypt_multi_read_denoised", rgb);
+	if(r != ADYPT_OK) multi_set_error(m, adypt_last_error(root));
+	return r;
+}
+
+// every device writes the pixels of its own tiles
+int adypt_multi_read_denoise_guides(adypt_multi *m, float *albedo, float *normal, float *position, uint8_t *hit)
+{
+	const int n_dev = adypt_multi_device_count(m);
+	if(n_dev < 1) return ADYPT_E_INVALID;
+	for(int k = 0; k < n_dev; ++k)
+	{
+		adypt_ctx *c = adypt_multi_context(m, k);
+		const int r = adypt_read_denoise_guides(c, albedo, normal, position, hit);
+		if(r != ADYPT_OK) { multi_set_error(m, adypt_last_error(c)); return r; }
+	}
+	return ADYPT_OK;
+}
+
+}  // extern "C"

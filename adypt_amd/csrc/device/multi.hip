@@ -360,6 +360,8 @@ struct adypt_multi {
 	Tunables tun;
 };
 
+namespace adypt { void multi_set_error(adypt_multi *m, const std::string &msg) { if(m) m->error = msg; } }
+
 namespace {
 
 int mfail(adypt_multi *m, int code, const std::string &msg) { m->error = msg; return code; }

@@ -365,7 +365,8 @@ inline QueueWindow pipe_window(const adypt_ctx *c, int k, int n_pipes)
 
 // Camera rays of a pass -> traversal -> cache images, one launch (k_trace_camera) and nothing in front of it.  `f` names the frames of the pass
 // (n_frames, frame_first, frame_stride).  On the context's stream only: the launches share one set of fetch cursors.
-int launch_trace_camera(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, const FrameArgs &f, const PixelArgs &px, int bias_mode, bool stats, int viewer_type = -1)
+// owned: over the OWNED blocks whatever is frozen (the denoiser's guide capture; f.n_local_px is then the owned pixels'), not over the pass's.
+int launch_trace_camera(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, const FrameArgs &f, const PixelArgs &px, int bias_mode, bool stats, int viewer_type = -1, bool owned = false)
 {
 	TraceCameraArgs K;
 	memset(&K, 0, sizeof(K));
@@ -374,17 +375,17 @@ int launch_trace_camera(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, 
 	a.packed = 1u; a.tmin = c->params.ray_tmin;
 	a.cursor = c->d_camera_cursors; K.left = c->d_camera_cursors + kNumSegments * kCursorStride;
 	a.spill = pipe.spill; a.stats = c->d_stats;
-	K.seg_paths = pass_seg_paths(c, win, f.n_frames);
+	K.seg_paths = owned ? std::min(win.seg_cap, seg_slots_px(c->n_local_px, f.n_frames)) : pass_seg_paths(c, win, f.n_frames);
 	K.seg_shift = 8;
 	while((1u << K.seg_shift) < K.seg_paths) ++K.seg_shift;
 	a.seg_cap = 1u << K.seg_shift; // (positions are numbers: nothing is stored at them)
-	K.rays = (unsigned long long)c->pass_image_px * (unsigned long long)f.n_frames;
+	K.rays = (unsigned long long)(owned ? c->n_image_px : c->pass_image_px) * (unsigned long long)f.n_frames;
 	a.refill_min = c->refill_min_primary; a.chunk = c->chunk; a.bite = c->bite_primary; a.endgame = c->endgame;
 	a.stack_size = c->params.stack_size; a.lds_depth = c->lds_depth;
-	K.f = f; K.local_blocks = pass_blocks(c); K.px = px; K.bias_mode = bias_mode;
+	K.f = f; K.local_blocks = owned ? (const int32_t *)c->d_local_blocks : pass_blocks(c); K.px = px; K.bias_mode = bias_mode;
 	hipEvent_t stop = begin_timing(c, 0, pipe.stream);
 	const bool viewer = viewer_type >= 0; // a primary-only call: the pixel is coloured when its ray has finished (no viewer launch)
-	if(viewer) { fill_scene(c, &K.sc); K.viewer_type = viewer_type; }
+	if(viewer) { fill_scene(c, &K.sc); K.sc.local_blocks = K.local_blocks; K.viewer_type = viewer_type; }
 	with_flags(stats, viewer, [&](auto S, auto Viewer) {
 		hipLaunchKernelGGL((k_trace_camera<decltype(S)::value, decltype(Viewer)::value>), dim3(c->trace_blocks), dim3(kTraceThreads), c->lds_bytes, pipe.stream, K);
 	});
@@ -677,6 +678,51 @@ int ctx_adaptive_ready(adypt_ctx *c, const char *fn)
 	return ADYPT_OK;
 }
 int ctx_freeze_blocks(adypt_ctx *c, const int32_t *blocks, size_t n, int spp) { return freeze_blocks(c, blocks, n, spp); }
+
+// ---- what the denoiser (denoise.hip) needs of a context ----
+void **ctx_denoise_slot(adypt_ctx *c, void (***free_fn)(void *)) { *free_fn = &c->denoise_free; return &c->denoise; }
+int ctx_denoise_ready(adypt_ctx *c, const char *fn)
+{
+	TRY_CREATE(noise_ready(c, fn, 0));
+	if(c->view_type != 3) return fail(c, ADYPT_E_STATE, std::string(fn) + ": the image is not path-traced (the last frame was a primary-ray viewer's)");
+	for(size_t i = 0; i < c->ab.owned.size(); ++i)
+		if(c->ab.spp_of(i, c->spp) < 2) return fail(c, ADYPT_E_STATE, std::string(fn) + ": needs at least 2 spp in every block (the variance of a pixel's mean is not defined below)");
+	if(c->ab.owned.empty() && c->spp < 2) return fail(c, ADYPT_E_STATE, std::string(fn) + ": needs at least 2 spp in every block (the variance of a pixel's mean is not defined below)");
+	return ADYPT_OK;
+}
+DenoiseInputs ctx_denoise_inputs(adypt_ctx *c)
+{
+	DenoiseInputs in;
+	in.accum = c->d_accum; in.moments = (const float2 *)c->d_noise_moments.get(); in.blocks = c->d_local_blocks;
+	in.n_blocks = c->n_local_blocks; in.block_index = c->local_blocks;
+	in.block_spp.resize(c->ab.owned.size());
+	for(size_t i = 0; i < in.block_spp.size(); ++i) in.block_spp[i] = c->ab.spp_of(i, c->spp);
+	return in;
+}
+// Albedo, normal, position (the viewer colours of types 0, 4, 5) and the primary hit of the pixel-centre camera ray of every owned pixel, under the
+// current camera and parameters, into the caller's four block-major images (each max(owned pixels, 64) float4): three launches of the viewer
+// instance of k_trace_camera over the OWNED blocks, on the context's stream behind the frames.  Nothing of the context's own changes: not the image,
+// not the primary-hit cache, not view_type / spp / the frozen set / the frames parked ahead.
+int ctx_capture_guides(adypt_ctx *c, const char *fn, float4 *albedo, float4 *normal, float4 *position, float4 *hits)
+{
+	if(!c->have_camera) return fail(c, ADYPT_E_STATE, std::string(fn) + ": call adypt_set_camera first");
+	if(!c->queues_ok) return fail(c, ADYPT_E_STATE, std::string(fn) + ": the context lost its ray queues (failed adypt_set_frames_in_flight)");
+	if(c->n_local_px == 0) return ADYPT_OK;
+	HIP_TRY(c, hipSetDevice(c->device));
+	FrameArgs f;
+	fill_frame(c, &f);
+	f.n_local_px = c->n_local_px; f.spp = 0;
+	float4 *const image[3] = {albedo, normal, position};
+	const int type[3] = {0, 4, 5};
+	for(int k = 0; k < 3; ++k)
+	{
+		PixelArgs px;
+		fill_pixels(c, &px);
+		px.accum = image[k]; px.cache = hits; px.cache_next = hits; px.shift = c->d_shift;
+		TRY_CREATE(launch_trace_camera(c, c->pipes[0], full_window(c), f, px, 0, false, type[k], true));
+	}
+	return ADYPT_OK;
+}
 int ctx_read_blocks(adypt_ctx *c, std::vector<BlockState> *blocks)
 {
 	const size_t first = blocks->size(), n = (size_t)c->n_local_blocks;
@@ -880,6 +926,7 @@ void adypt_destroy(adypt_ctx *c)
 	(void)hipSetDevice(c->device);
 	for(int k = 0; k < kMaxPipes; ++k) if(c->pipes[k].stream) (void)hipStreamSynchronize(c->pipes[k].stream);
 	if(c->comm && c->comm_free) c->comm_free(c->comm);
+	if(c->denoise && c->denoise_free) c->denoise_free(c->denoise);
 	delete c; // every member releases itself, the streams and events last (context.hpp)
 }
 

@@ -265,6 +265,35 @@ int adypt_trace_adaptive(adypt_ctx *ctx, double target, int min_spp, int max_spp
  * of owned blocks and writes the arrays only when capacity holds them all, like adypt_read_block_noise; works with the statistics off. */
 int64_t adypt_read_block_spp(adypt_ctx *ctx, int32_t *block_index, int32_t *spp, int64_t capacity);
 
+/* ---- denoising: a usable image at 16-32 spp from the statistics the library already keeps --------------------------------------
+ * An edge-avoiding a-trous wavelet filter (the spatial half of SVGF) over the albedo-demodulated radiance, guided by the primary hit's normal,
+ * position and hit flag; the luminance edge-stopping is scaled by the variance of the pixel's mean, m2 / (n (n - 1)) from the noise moments with n
+ * the sample count of the pixel's 32x32 block, and the variance is filtered along.  The definition is pinned bit for bit in
+ * csrc/device/denoise.hpp (binary32, no fma, no exp / pow); tests/denoise_truth.py restates it in numpy.  The guides are the viewer colours of
+ * types 0, 4 and 5 of the pixel-centre camera ray under the current camera and parameters and whether that ray hit anything; they are captured
+ * into scratch of the denoiser's own.  NOTHING of the context changes: the image, the moments, the primary-hit cache, the frame counter, the
+ * frozen blocks and the frames parked ahead are what they were, and tracing goes on as if the call had not happened.
+ * Memory, allocated at the first call and given back by adypt_destroy: 92 B per image pixel (five float4 images and the result) + 64 B per local
+ * pixel (the guide scratch). */
+typedef struct adypt_denoise_params {
+	int32_t levels;              /* 1 .. 6 a-trous levels, tap distance 1 << level; default 5 */
+	float sigma_l, sigma_z;      /* luminance and depth edge-stopping; defaults 4.0 and 0.1 */
+} adypt_denoise_params;
+/* Filters the accumulated image; params NULL = the defaults.  Enqueued on the context's stream behind the frames, waited for before it returns; two
+ * calls in a row leave the same bits.  ADYPT_E_STATE, the reason in adypt_last_error: the noise statistics are off; the image is not path-traced;
+ * a block has fewer than 2 samples; the context is a tile shard (tile_nranks > 1: adypt_multi_denoise; one process per GPU has no variant).
+ * ADYPT_E_INVALID: levels outside [1, 6], a sigma that is not a positive number. */
+int adypt_denoise(adypt_ctx *ctx, const adypt_denoise_params *params);
+/* the result of the last adypt_denoise: W*H*3 floats, row 0 = top.  ADYPT_E_STATE before the first */
+int adypt_read_denoised(adypt_ctx *ctx, float *rgb);
+/* The guide images, captured by this call (also the feature-image export an external denoiser asks for): albedo, normal, position W*H*3 floats each,
+ * hit W*H bytes (1 = the camera ray hit a triangle).  Any pointer may be NULL.  Pixels of blocks this context does not own are left untouched.
+ * Needs a camera; works in any state of the accumulation, which it leaves alone. */
+int adypt_read_denoise_guides(adypt_ctx *ctx, float *albedo, float *normal, float *position, uint8_t *hit);
+/* HIP-event times of the last adypt_denoise in ms: [0] the guide capture, [1] prepare, [2 ..] every level.  Returns the number of entries and writes
+ * them only when capacity holds them all. */
+int adypt_get_denoise_timing(adypt_ctx *ctx, float *ms, int capacity);
+
 /* Trace an arbitrary batch of rays through the same traversal kernel: rays = n x 8 floats
  * (ox, oy, oz, tmin, dx, dy, dz, unused).  with_stats selects the instrumented kernel variant. */
 int adypt_trace_rays(adypt_ctx *ctx, const float *rays, int64_t n, adypt_hit *hits, int with_stats);
@@ -359,6 +388,12 @@ int adypt_multi_trace_until(adypt_multi *m, double target, int min_spp, int max_
  * one-device result.  (One process per GPU: every rank calls adypt_trace_adaptive on its own context and ends
  * when its own blocks are frozen, so the ranks' counters differ afterwards; a rank that owns no block runs to max_spp.) */
 int adypt_multi_trace_adaptive(adypt_multi *m, double target, int min_spp, int max_spp, int check_every, adypt_adaptive *out);
+/* adypt_denoise for the whole image.  One device: the context's call.  Several: every device captures the guides of its own blocks, the host merges
+ * the devices' local images by block index (every block has one owner), uploads them to device_ids[0] and the same two kernels run there; the
+ * result equals the one-device result bit for bit.  No collective. */
+int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *params);
+int adypt_multi_read_denoised(adypt_multi *m, float *rgb);
+int adypt_multi_read_denoise_guides(adypt_multi *m, float *albedo, float *normal, float *position, uint8_t *hit); /* every device writes its own tiles */
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);
