@@ -371,6 +371,14 @@ def _read_block_spp(ctx) -> Tuple[np.ndarray, np.ndarray]:
     return idx, spp
 
 
+def _blocks_by_index(parts) -> Tuple[np.ndarray, ...]:
+    """The contexts' per-block arrays (block index first) as one set, ascending block index: every block has one owner, and one context's list is
+    ascending already."""
+    cols = [np.concatenate(col) for col in zip(*parts)]
+    order = np.argsort(cols[0], kind="stable")
+    return tuple(col[order] for col in cols)
+
+
 class _Tracer:
     """What HipPathTracer and MultiPathTracer both offer, written once over three things the class gives: the handle `_h`, the symbol family
     `_family` ("adypt_" or "adypt_multi_": `_call("trace_spp", n)` is adypt_trace_spp or adypt_multi_trace_spp on the handle) and its own error
@@ -500,10 +508,11 @@ class _Tracer:
 
     def ReadBlockSPP(self) -> Tuple[np.ndarray, np.ndarray]:
         """(block index int32, sample count int32) of every 32x32 block this tracer owns, ascending block index."""
-        parts = [_read_block_spp(c) for c in self._contexts()]
-        idx, spp = (np.concatenate([p[i] for p in parts]) for i in range(2))
-        order = np.argsort(idx, kind="stable")
-        return idx[order], spp[order]
+        return _blocks_by_index([_read_block_spp(c) for c in self._contexts()])
+
+    def ReadBlockNoise(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(block index int32, sum float64, count uint32) of every 32x32 block this tracer owns, ascending block index (needs >= 2 spp)."""
+        return _blocks_by_index([_read_block_noise(c) for c in self._contexts()])
 
     def ReadSPP(self) -> np.ndarray:
         """H x W int32: the sample count of every pixel, built from the blocks (0 where no context of this tracer owns the block)."""
@@ -612,10 +621,6 @@ class HipPathTracer(_Tracer):
     def GetLookaheadFrames(self) -> int:
         return N.lib.adypt_get_lookahead_frames(self._ctx)
 
-    def ReadBlockNoise(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """(block index int32, sum float64, count uint32) of the owned 32x32 blocks, ascending block index."""
-        return _read_block_noise(self._ctx)
-
     def SavePreview(self, filename: str) -> None:
         save_png(filename, self.ReadDisplay())
 
@@ -718,13 +723,6 @@ class MultiPathTracer(_Tracer):
 
     def SetInstrumentation(self, timing: bool = False, counters: bool = False) -> None:
         self._check(N.lib.adypt_multi_set_instrumentation(self._m, (1 if timing else 0) | (2 if counters else 0)))
-
-    def ReadBlockNoise(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """The devices' blocks merged and sorted by block index."""
-        parts = [_read_block_noise(c) for c in self._contexts()]
-        idx, s, cnt = (np.concatenate([p[i] for p in parts]) for i in range(3))
-        order = np.argsort(idx, kind="stable")
-        return idx[order], s[order], cnt[order]
 
     def ContextStats(self, i: int) -> dict:
         st = N.Stats()

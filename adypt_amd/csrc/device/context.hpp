@@ -8,6 +8,7 @@
 #include "active_blocks.hpp"
 #include "tunables.hpp"
 #include "resources.hpp"
+#include "ctx_access.hpp"
 #include "../../../include/adypt_hip.h"
 
 #include <string>
@@ -189,12 +190,9 @@ struct adypt_ctx {
 	int instrumentation = 0;
 	int view_type = 0;          // uuViewer.uType of the image in d_accum: the viewer type of the last primary frame, 3 after path tracing
 
-	// RCCL communicator state of the native multi-GPU path (multi.hip owns and frees it)
-	void *comm = nullptr;
-	void (*comm_free)(void *) = nullptr;
-	// the denoiser's images (denoise.hip owns and frees them): allocated at the first adypt_denoise / adypt_read_denoise_guides
-	void *denoise = nullptr;
-	void (*denoise_free)(void *) = nullptr;
+	// What other translation units park here (ctx_access.hpp): multi.hip the RCCL communicator state of the native multi-GPU path, denoise.hip the
+	// denoiser's images (allocated at the first adypt_denoise / adypt_read_denoise_guides).  adypt_destroy releases them in this order.
+	Attachment attached[kAttachKinds];
 
 	double trace_ms = 0, shade_ms = 0, path_ms = 0;
 	uint32_t trace_launches = 0, path_launches = 0;

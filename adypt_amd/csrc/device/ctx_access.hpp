@@ -2,6 +2,7 @@
 // fields the collective needs, without exposing the context's layout.  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "noise.hpp"
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -10,8 +11,6 @@ struct adypt_ctx;
 struct adypt_multi;
 
 namespace adypt {
-
-struct BlockState; // active_blocks.hpp
 
 struct CtxInfo {
 	int device;
@@ -23,18 +22,33 @@ struct CtxInfo {
 
 CtxInfo ctx_info(adypt_ctx *c);
 void ctx_set_error(adypt_ctx *c, const std::string &msg);
-// where multi.hip parks its per-context communicator (freed by adypt_destroy through *free_fn)
-void **ctx_comm_slot(adypt_ctx *c, void (***free_fn)(void *));
-// adaptive sampling, per context (adypt_trace_adaptive and adypt_multi_trace_adaptive are one loop over these: active_blocks.hpp).
-// ready: ADYPT_OK, or ADYPT_E_STATE with the context's error set (statistics off, look-ahead); read: APPENDS the owned blocks, ascending, each at its
-// own sample count; freeze: the owned blocks among the image blocks given stop at `spp` frames.
+// What another translation unit parks in a context, which owns it from then on: released through free_fn when something else takes its place and
+// by adypt_destroy (streams drained, the context's device current), the communicator first.
+struct Attachment {
+	void *p = nullptr;
+	void (*free_fn)(void *) = nullptr;
+	Attachment() = default;
+	Attachment(const Attachment &) = delete;
+	Attachment &operator=(const Attachment &) = delete;
+	~Attachment() { reset(); }
+	void reset(void *q = nullptr, void (*f)(void *) = nullptr) { if(p && free_fn) free_fn(p); p = q; free_fn = f; }
+};
+enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachKinds }; // multi.hip's communicator, denoise.hip's images
+Attachment &ctx_attachment(adypt_ctx *c, AttachKind kind);
+
+// ---- noise statistics and adaptive sampling, per context (adypt_trace_adaptive and adypt_multi_trace_adaptive are one loop over these) ----
+// ADYPT_OK when the statistics are on and the image has min_spp frames, else ADYPT_E_STATE with `fn` named in the context's error
+int noise_ready(adypt_ctx *c, const char *fn, int min_spp);
+// noise_ready(c, fn, 0), and no look-ahead: parked frames belong to a block set that a check may change
 int ctx_adaptive_ready(adypt_ctx *c, const char *fn);
+// THE reader of a context's block results (k_noise_blocks behind the frames; adypt_get_noise and adypt_read_block_noise are written on it): APPENDS
+// the owned blocks, ascending, each at its own sample count; nothing for a shard that owns no block.  The caller has asked noise_ready(c, fn, 2).
 int ctx_read_blocks(adypt_ctx *c, std::vector<BlockState> *blocks);
+// the owned blocks among the image blocks given stop at `spp` frames
 int ctx_freeze_blocks(adypt_ctx *c, const int32_t *blocks, size_t n, int spp);
 
-// The denoiser (denoise.hip), per context.  slot: where its images are parked (freed by adypt_destroy through *free_fn).  ready: ADYPT_OK, or
-// ADYPT_E_STATE with the reason in the context's error (statistics off, a viewer's image, a block below 2 spp).  inputs: the block-major local images
-// the filter reads and every owned block's sample count.  capture_guides: see tracer.hip.
+// ---- the denoiser (denoise.hip), per context ----
+// what ctx_denoise_inputs gives: the block-major local images the filter reads and every owned block's sample count
 struct DenoiseInputs {
 	const float4 *accum;               // running mean per local pixel
 	const float2 *moments;             // luminance (mean, m2) per local pixel
@@ -43,9 +57,10 @@ struct DenoiseInputs {
 	std::vector<int32_t> block_index;  // host copy of `blocks`
 	std::vector<int32_t> block_spp;    // samples in every owned block
 };
-void **ctx_denoise_slot(adypt_ctx *c, void (***free_fn)(void *));
+// ADYPT_OK, or ADYPT_E_STATE with the reason in the context's error (statistics off, a viewer's image, a block below 2 spp)
 int ctx_denoise_ready(adypt_ctx *c, const char *fn);
 DenoiseInputs ctx_denoise_inputs(adypt_ctx *c);
+// see tracer.hip
 int ctx_capture_guides(adypt_ctx *c, const char *fn, float4 *albedo, float4 *normal, float4 *position, float4 *hits);
 // multi.hip: the message adypt_multi_last_error answers
 void multi_set_error(adypt_multi *m, const std::string &msg);

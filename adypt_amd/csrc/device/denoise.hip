@@ -5,9 +5,9 @@
 //     k_denoise_prepare  block-major accum / moments / block sample counts / guides  ->  row-major float4 images X0 = (D0.rgb, V0), X1 = (N.xyz, hit),
 //                    X2 = (P.xyz, .), XA = (A.rgb, .)
 //     k_atrous<LAST>  one level per launch, X0 ping-pongs; the last level multiplies the albedo back and writes the W x H x 3 result
-// Several devices: every context captures the guides of its own blocks, the host merges the local images by block index (every block has one owner)
-// into the block-major images of the WHOLE picture, uploads them to the first device and runs the same two kernels there — no collective; the result
-// is the one-device result bit for bit because the inputs are.
+// Several devices: every context captures the guides of its own blocks, the host puts the devices' local images back to back in rank order, their
+// block lists likewise (every block has one owner, and k_denoise_prepare takes any block list and writes at the picture's coordinates), uploads them
+// to the first device and runs the same two kernels there — no collective; the result is the one-device result bit for bit because the inputs are.
 #include "ctx_access.hpp"
 #include "resources.hpp"
 #include "tile_layout.hpp"
@@ -79,7 +79,7 @@ struct LocalImages {
 
 constexpr int kTimingEvents = 3 + kDenoiseMaxLevels; // start, guides, prepare, every level
 
-// Everything the denoiser keeps per context; parked in adypt_ctx::denoise, freed by adypt_destroy (the context's device is current then).
+// Everything the denoiser keeps per context; parked in the context (ctx_attachment), freed by adypt_destroy (the context's device is current then).
 struct Denoiser {
 	int width = 0, height = 0;
 	// guide scratch of the owned blocks, block-major: 64 B per local pixel + 4 B per owned block
@@ -89,7 +89,8 @@ struct Denoiser {
 	Buffer<float4> x0[2], x1, x2, xa;
 	Buffer<float> rgb;
 	bool have_result = false;
-	// several devices: the merged block-major images of the whole picture on the first device (88 B per pixel of the blocks + 8 B per block)
+	// several devices: the block-major images of every device's blocks, back to back in rank order, on the first device (88 B per pixel of the blocks
+	// + 8 B per block)
 	Buffer<float4> m_accum, m_albedo, m_normal, m_position, m_hits;
 	Buffer<float2> m_moments;
 	Buffer<int32_t> m_blocks, m_block_spp;
@@ -108,17 +109,11 @@ int cfail(adypt_ctx *c, int code, const std::string &msg) { ctx_set_error(c, msg
 	} while(0)
 #define DN_STEP(expr) do { const int r_ = (expr); if(r_ != ADYPT_OK) return r_; } while(0)
 
+Denoiser *denoiser_if_any(adypt_ctx *c) { return (Denoiser *)ctx_attachment(c, kAttachDenoise).p; }
 Denoiser *denoiser_of(adypt_ctx *c)
 {
-	void (**free_fn)(void *) = nullptr;
-	void **slot = ctx_denoise_slot(c, &free_fn);
-	if(!*slot) { *slot = new Denoiser(); *free_fn = free_denoiser; }
-	return (Denoiser *)*slot;
-}
-Denoiser *denoiser_if_any(adypt_ctx *c)
-{
-	void (**free_fn)(void *) = nullptr;
-	return (Denoiser *)*ctx_denoise_slot(c, &free_fn);
+	if(!denoiser_if_any(c)) ctx_attachment(c, kAttachDenoise).reset(new Denoiser(), free_denoiser);
+	return denoiser_if_any(c);
 }
 
 template <class T> int ensure(adypt_ctx *c, Buffer<T> &b, size_t n)
@@ -200,12 +195,10 @@ int read_result(adypt_ctx *c, const char *fn, float *rgb)
 	return ADYPT_OK;
 }
 
-// one block-major local image of a context on the host (the stream is drained when it returns)
-template <class T> int fetch(adypt_ctx *c, const CtxInfo &i, const T *device, std::vector<T> *host)
+// one block-major local image of a context (n_local_px > 0 elements) on the host (the stream is drained when it returns)
+template <class T> int fetch(adypt_ctx *c, const CtxInfo &i, const T *device, T *host)
 {
-	host->resize((size_t)i.n_local_px);
-	if(host->empty()) return ADYPT_OK;
-	DN_TRY(c, hipMemcpyAsync(host->data(), device, host->size() * sizeof(T), hipMemcpyDeviceToHost, i.stream));
+	DN_TRY(c, hipMemcpyAsync(host, device, (size_t)i.n_local_px * sizeof(T), hipMemcpyDeviceToHost, i.stream));
 	DN_TRY(c, hipStreamSynchronize(i.stream));
 	return ADYPT_OK;
 }
@@ -226,7 +219,6 @@ int adypt_denoise(adypt_ctx *c, const adypt_denoise_params *p)
 	DN_TRY(c, hipSetDevice(i.device));
 	Denoiser *d = denoiser_of(c);
 	DN_STEP(ensure_filter_images(c, d, i));
-	DN_STEP(ensure_guides(c, d, i));
 	d->have_result = false;
 	DN_TRY(c, hipEventRecord(d->ev[0], i.stream));
 	DN_STEP(capture_guides(c, d, i, "adypt_denoise"));
@@ -252,13 +244,13 @@ int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float 
 	Denoiser *d = denoiser_of(c);
 	DN_STEP(capture_guides(c, d, i, "adypt_read_denoise_guides"));
 	const std::vector<int32_t> blocks = owned_blocks(i.width, i.height, i.rank, i.nranks);
-	std::vector<float4> local;
+	std::vector<float4> local((size_t)i.n_local_px);
 	float *const image[3] = {albedo, normal, position};
 	const float4 *const device[3] = {d->g_albedo, d->g_normal, d->g_position};
 	for(int k = 0; k < 3; ++k)
 	{
 		if(!image[k]) continue;
-		DN_STEP(fetch(c, i, device[k], &local));
+		DN_STEP(fetch(c, i, device[k], local.data()));
 		for_each_local_pixel(blocks, i.width, i.height, [&](size_t L, int x, int y) {
 			float *o = image[k] + ((size_t)y * i.width + x) * 3;
 			o[0] = local[L].x; o[1] = local[L].y; o[2] = local[L].z;
@@ -266,7 +258,7 @@ int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float 
 	}
 	if(hit)
 	{
-		DN_STEP(fetch(c, i, (const float4 *)d->g_hits, &local));
+		DN_STEP(fetch(c, i, (const float4 *)d->g_hits, local.data()));
 		for_each_local_pixel(blocks, i.width, i.height, [&](size_t L, int x, int y) {
 			int32_t tri;
 			memcpy(&tri, &local[L].x, 4);
@@ -322,14 +314,16 @@ int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p)
 		if(r == ADYPT_OK) r = capture_guides(c, denoiser_of(c), i, "adypt_multi_denoise");
 		if(r != ADYPT_OK) return fail_ctx(c, r);
 	}
-	// the local images of every device merged by block index: block b of the picture at place b of the merged block-major images
+	// the local images of every device back to back in rank order, and their block lists and sample counts likewise (the counts from each context's
+	// own state in that order: multi.hip's merge is sorted by block index, which is not this order, and would launch k_noise_blocks for nothing)
 	const CtxInfo ri = ctx_info(root);
-	const int n_blocks = ((ri.width + kBlockDim - 1) / kBlockDim) * ((ri.height + kBlockDim - 1) / kBlockDim);
-	const size_t n_px = (size_t)n_blocks * kBlockPixels;
-	std::vector<float4> accum(n_px), albedo(n_px), normal(n_px), position(n_px), hits(n_px), local;
-	std::vector<float2> moments(n_px), local2;
-	std::vector<int32_t> blocks((size_t)n_blocks), block_spp((size_t)n_blocks, 0);
-	for(int b = 0; b < n_blocks; ++b) blocks[(size_t)b] = b;
+	size_t n_px = 0;
+	for(adypt_ctx *c : ctx) n_px += (size_t)ctx_info(c).n_local_px;
+	const int n_blocks = (int)(n_px / kBlockPixels);
+	std::vector<float4> accum(n_px), albedo(n_px), normal(n_px), position(n_px), hits(n_px);
+	std::vector<float2> moments(n_px);
+	std::vector<int32_t> blocks, block_spp;
+	size_t at = 0; // the rank's first pixel in them
 	for(adypt_ctx *c : ctx)
 	{
 		const CtxInfo i = ctx_info(c);
@@ -337,22 +331,14 @@ int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p)
 		if(hipSetDevice(i.device) != hipSuccess) return fail_ctx(c, cfail(c, ADYPT_E_HIP, "adypt_multi_denoise: hipSetDevice failed"));
 		Denoiser *d = denoiser_of(c);
 		const DenoiseInputs in = ctx_denoise_inputs(c);
-		auto scatter = [&](const auto &from, auto &to) {
-			for(size_t k = 0; k < in.block_index.size(); ++k)
-				std::copy(from.begin() + (ptrdiff_t)(k * kBlockPixels), from.begin() + (ptrdiff_t)((k + 1) * kBlockPixels), to.begin() + (ptrdiff_t)((size_t)in.block_index[k] * kBlockPixels));
-		};
 		const float4 *const device[5] = {in.accum, d->g_albedo, d->g_normal, d->g_position, d->g_hits};
-		std::vector<float4> *const merged[5] = {&accum, &albedo, &normal, &position, &hits};
-		for(int k = 0; k < 5; ++k)
-		{
-			const int r = fetch(c, i, device[k], &local);
-			if(r != ADYPT_OK) return fail_ctx(c, r);
-			scatter(local, *merged[k]);
-		}
-		const int r = fetch(c, i, in.moments, &local2);
+		float4 *const merged[5] = {accum.data(), albedo.data(), normal.data(), position.data(), hits.data()};
+		int r = fetch(c, i, in.moments, moments.data() + at);
+		for(int k = 0; k < 5 && r == ADYPT_OK; ++k) r = fetch(c, i, device[k], merged[k] + at);
 		if(r != ADYPT_OK) return fail_ctx(c, r);
-		scatter(local2, moments);
-		for(size_t k = 0; k < in.block_index.size(); ++k) block_spp[(size_t)in.block_index[k]] = in.block_spp[k];
+		blocks.insert(blocks.end(), in.block_index.begin(), in.block_index.end());
+		block_spp.insert(block_spp.end(), in.block_spp.begin(), in.block_spp.end());
+		at += (size_t)i.n_local_px;
 	}
 	// ... uploaded to the first device, where the same prepare / a-trous launches run
 	adypt_ctx *c = root;

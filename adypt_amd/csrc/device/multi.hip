@@ -211,18 +211,8 @@ int finish_comm(adypt_ctx *ctx, Comm *k)
 	return ADYPT_OK;
 }
 
-Comm *comm_of(adypt_ctx *ctx)
-{
-	void (**free_fn)(void *) = nullptr;
-	return (Comm *)*ctx_comm_slot(ctx, &free_fn);
-}
-void park_comm(adypt_ctx *ctx, Comm *k)
-{
-	void (**free_fn)(void *) = nullptr;
-	void **slot = ctx_comm_slot(ctx, &free_fn);
-	if(*slot) free_comm(*slot);
-	*slot = k; *free_fn = free_comm;
-}
+Comm *comm_of(adypt_ctx *ctx) { return (Comm *)ctx_attachment(ctx, kAttachComm).p; }
+void park_comm(adypt_ctx *ctx, Comm *k) { ctx_attachment(ctx, kAttachComm).reset(k, free_comm); } // (one parked before is freed)
 
 // root side after the tiles have arrived (or for a single rank): own tiles + un-tiling, all on the root's stream
 int assemble_on_root(adypt_ctx *ctx, Comm *k, int64_t stride)
@@ -470,7 +460,7 @@ int adypt_create_multi(adypt_multi **out, const adypt_scene_desc *desc, const in
 void adypt_destroy_multi(adypt_multi *m)
 {
 	if(!m) return;
-	for(adypt_ctx *c : m->ctx) adypt_destroy(c); // frees the communicators as well (adypt_ctx::comm_free)
+	for(adypt_ctx *c : m->ctx) adypt_destroy(c); // frees the communicators as well (adypt_ctx::attached)
 	delete m;
 }
 
@@ -531,33 +521,31 @@ int adypt_multi_set_noise_stats(adypt_multi *m, int enabled) { FOR_ALL(m, adypt_
 // every context writes the pixels of its own tiles
 int adypt_multi_read_noise(adypt_multi *m, float *e) { if(!e) return ADYPT_E_INVALID; FOR_ALL(m, adypt_read_noise(c, e)); return ADYPT_OK; }
 
-// the devices' block results merged by block index (every block has one owner), then the image formulas of noise.hpp: the one-device numbers
+// THE merge of the devices' blocks: every context's (ctx_read_blocks) appended and sorted by block index — every block has one owner, so this is the
+// one-device list.  Every context is asked noise_ready(c, fn, 2) first; a failure is reported with the failing context's message.
+static int read_all_blocks(adypt_multi *m, const char *fn, std::vector<BlockState> *blocks)
+{
+	blocks->clear();
+	for(adypt_ctx *c : m->ctx)
+	{
+		int r = noise_ready(c, fn, 2);
+		if(r == ADYPT_OK) r = ctx_read_blocks(c, blocks);
+		if(r != ADYPT_OK) return mfail_ctx(m, r, c);
+	}
+	std::sort(blocks->begin(), blocks->end(), [](const BlockState &a, const BlockState &b) { return a.index < b.index; });
+	return ADYPT_OK;
+}
+
+// the image formulas of noise.hpp over the merged blocks: the one-device numbers
 int adypt_multi_get_noise(adypt_multi *m, adypt_noise *out)
 {
 	if(!m || !out || m->ctx.empty()) return ADYPT_E_INVALID;
-	const CtxInfo info = ctx_info(m->ctx[0]);
-	const size_t n_blocks = (size_t)((info.width + kBlockDim - 1) / kBlockDim) * (size_t)((info.height + kBlockDim - 1) / kBlockDim);
-	std::vector<int32_t> index(n_blocks), idx;
-	std::vector<double> sum(n_blocks, 0.0), s;
-	std::vector<uint32_t> count(n_blocks, 0u), cnt;
-	for(size_t i = 0; i < n_blocks; ++i) index[i] = (int32_t)i;
+	std::vector<BlockState> blocks;
+	const int r = read_all_blocks(m, "adypt_multi_get_noise", &blocks);
+	if(r != ADYPT_OK) return r;
 	int64_t pixels = 0;
-	for(adypt_ctx *c : m->ctx)
-	{
-		int64_t n = adypt_read_block_noise(c, nullptr, nullptr, nullptr, 0);
-		if(n < 0) return mfail_ctx(m, (int)n, c);
-		if(n == 0) continue; // a shard that owns no block
-		idx.resize((size_t)n); s.resize((size_t)n); cnt.resize((size_t)n);
-		n = adypt_read_block_noise(c, idx.data(), s.data(), cnt.data(), n);
-		if(n < 0) return mfail_ctx(m, (int)n, c);
-		for(int64_t i = 0; i < n; ++i)
-		{
-			if(idx[(size_t)i] < 0 || (size_t)idx[(size_t)i] >= n_blocks) return mfail(m, ADYPT_E_STATE, "adypt_multi_get_noise: block index out of range");
-			sum[(size_t)idx[(size_t)i]] = s[(size_t)i]; count[(size_t)idx[(size_t)i]] = cnt[(size_t)i];
-			pixels += cnt[(size_t)i];
-		}
-	}
-	const NoiseImage img = noise_of_image(index.data(), sum.data(), count.data(), n_blocks, pixels);
+	for(const BlockState &b : blocks) pixels += b.count;
+	const NoiseImage img = noise_of_image(blocks.data(), blocks.size(), pixels);
 	out->mean_noise = img.mean_noise; out->worst_block = img.worst_block; out->worst_index = img.worst_index;
 	out->spp = adypt_get_spp(m->ctx[0]); out->pixels = pixels;
 	return ADYPT_OK;
@@ -580,21 +568,14 @@ int adypt_multi_trace_adaptive(adypt_multi *m, double target, int min_spp, int m
 	if(!m || m->ctx.empty()) return ADYPT_E_INVALID;
 	FOR_ALL(m, ctx_adaptive_ready(c, "adypt_multi_trace_adaptive"));
 	std::string refused;
-	adypt_ctx *failed = nullptr;
 	const int r = trace_adaptive("adypt_multi_trace_adaptive", &refused, target, min_spp, max_spp, check_every, out, [m] { return adypt_multi_get_spp(m); },
 	                             [m](int n) { return adypt_multi_trace_spp(m, n); },
-	                             [m, &failed](std::vector<BlockState> *blocks) {
-		                             blocks->clear();
-		                             for(adypt_ctx *c : m->ctx) { const int rc = ctx_read_blocks(c, blocks); if(rc != ADYPT_OK) { failed = c; return rc; } }
-		                             std::sort(blocks->begin(), blocks->end(), [](const BlockState &a, const BlockState &b) { return a.index < b.index; });
-		                             return (int)ADYPT_OK;
-	                             },
-	                             [m, &failed](const std::vector<int32_t> &stop, int spp) {
-		                             for(adypt_ctx *c : m->ctx) { const int rc = ctx_freeze_blocks(c, stop.data(), stop.size(), spp); if(rc != ADYPT_OK) { failed = c; return rc; } }
+	                             [m](std::vector<BlockState> *blocks) { return read_all_blocks(m, "adypt_multi_trace_adaptive", blocks); },
+	                             [m](const std::vector<int32_t> &stop, int spp) {
+		                             for(adypt_ctx *c : m->ctx) { const int rc = ctx_freeze_blocks(c, stop.data(), stop.size(), spp); if(rc != ADYPT_OK) return mfail_ctx(m, rc, c); }
 		                             return (int)ADYPT_OK;
 	                             });
-	if(!refused.empty()) return mfail(m, r, refused);
-	return (r != ADYPT_OK && failed) ? mfail_ctx(m, r, failed) : r;
+	return refused.empty() ? r : mfail(m, r, refused); // (a step that failed has left its context's message)
 }
 
 int adypt_multi_comm_init(adypt_multi *m)

@@ -48,21 +48,27 @@ ADYPT_HOST_DEVICE float noise_of_pixel(NoiseMoments s, int n_frames)
 	return sqrtf(s.m2 / (n * (n - 1.0f))) / (s.mean + kNoiseBlackLevel);
 }
 
-// The image's numbers from its blocks' (host only).  `index` = the image block index of each entry, ascending; `pixels` = the pixels the entries
-// cover (width x height for a whole image).  mean_noise = (sum of the block sums, in that order) / pixels; worst_block = the largest sum / count,
-// worst_index its block index — the lowest one on a tie.  Nothing covered: zeros.
+// THE host record of one 32x32 block of an image: what k_noise_blocks found for it (sum, count), which block of the image it is, the frames it holds
+// and whether it is frozen at them (active_blocks.hpp).  Every host-side consumer reads blocks in this shape; the C ABI's parallel arrays are
+// filled from it at the boundary.
+struct BlockState { int32_t index; double sum; uint32_t count; int32_t spp; bool frozen; };
+
+// The image's numbers from its blocks' (host only).  blocks[0 .. n_blocks): ascending index; `pixels` = the pixels the entries cover (width x height
+// for a whole image).  mean_noise = (sum of the block sums, in that order) / pixels; worst_block = the largest sum / count, worst_index its block
+// index — the lowest one on a tie.  Entries without a pixel (count 0) are passed over.  Nothing covered: zeros.
 struct NoiseImage { double mean_noise, worst_block; int32_t worst_index; };
-inline NoiseImage noise_of_image(const int32_t *index, const double *sum, const uint32_t *count, size_t n_blocks, int64_t pixels)
+inline NoiseImage noise_of_image(const BlockState *blocks, size_t n_blocks, int64_t pixels)
 {
 	NoiseImage r{0.0, 0.0, 0};
 	double total = 0.0;
 	bool any = false;
 	for(size_t i = 0; i < n_blocks; ++i)
 	{
-		if(count[i] == 0) continue;
-		total += sum[i];
-		const double m = sum[i] / (double)count[i];
-		if(!any || m > r.worst_block) { r.worst_block = m; r.worst_index = index[i]; any = true; }
+		const BlockState &b = blocks[i];
+		if(b.count == 0) continue;
+		total += b.sum;
+		const double m = b.sum / (double)b.count;
+		if(!any || m > r.worst_block) { r.worst_block = m; r.worst_index = b.index; any = true; }
 	}
 	if(any && pixels > 0) r.mean_noise = total / (double)pixels;
 	return r;

@@ -534,8 +534,7 @@ int apply_params(adypt_ctx *c)
 #include "scene_upload.hpp"
 #include "frame_schedule.hpp"
 
-namespace {
-
+namespace adypt {
 // what every entry point of the noise statistics asks first: they are on, and the image has `min_spp` frames
 int noise_ready(adypt_ctx *c, const char *who, int min_spp)
 {
@@ -543,6 +542,9 @@ int noise_ready(adypt_ctx *c, const char *who, int min_spp)
 	if(c->spp < min_spp) return fail(c, ADYPT_E_STATE, std::string(who) + ": needs at least " + std::to_string(min_spp) + " spp");
 	return ADYPT_OK;
 }
+}  // namespace adypt
+
+namespace {
 
 // ---- adaptive sampling: the block set of a pass (active_blocks.hpp) ----
 
@@ -669,7 +671,7 @@ CtxInfo ctx_info(adypt_ctx *c)
 	return i;
 }
 void ctx_set_error(adypt_ctx *c, const std::string &msg) { c->error = msg; }
-void **ctx_comm_slot(adypt_ctx *c, void (***free_fn)(void *)) { *free_fn = &c->comm_free; return &c->comm; }
+Attachment &ctx_attachment(adypt_ctx *c, AttachKind kind) { return c->attached[kind]; }
 int ctx_adaptive_ready(adypt_ctx *c, const char *fn)
 {
 	TRY_CREATE(noise_ready(c, fn, 0));
@@ -680,7 +682,6 @@ int ctx_adaptive_ready(adypt_ctx *c, const char *fn)
 int ctx_freeze_blocks(adypt_ctx *c, const int32_t *blocks, size_t n, int spp) { return freeze_blocks(c, blocks, n, spp); }
 
 // ---- what the denoiser (denoise.hip) needs of a context ----
-void **ctx_denoise_slot(adypt_ctx *c, void (***free_fn)(void *)) { *free_fn = &c->denoise_free; return &c->denoise; }
 int ctx_denoise_ready(adypt_ctx *c, const char *fn)
 {
 	TRY_CREATE(noise_ready(c, fn, 0));
@@ -721,19 +722,6 @@ int ctx_capture_guides(adypt_ctx *c, const char *fn, float4 *albedo, float4 *nor
 		px.accum = image[k]; px.cache = hits; px.cache_next = hits; px.shift = c->d_shift;
 		TRY_CREATE(launch_trace_camera(c, c->pipes[0], full_window(c), f, px, 0, false, type[k], true));
 	}
-	return ADYPT_OK;
-}
-int ctx_read_blocks(adypt_ctx *c, std::vector<BlockState> *blocks)
-{
-	const size_t first = blocks->size(), n = (size_t)c->n_local_blocks;
-	if(n == 0) return ADYPT_OK;
-	std::vector<int32_t> index(n);
-	std::vector<double> sum(n);
-	std::vector<uint32_t> count(n);
-	const int64_t r = adypt_read_block_noise(c, index.data(), sum.data(), count.data(), (int64_t)n);
-	if(r < 0) return (int)r;
-	blocks->resize(first + n);
-	for(size_t i = 0; i < n; ++i) (*blocks)[first + i] = BlockState{index[i], sum[i], count[i], c->ab.spp_of(i, c->spp), c->ab.frozen_at[i] != 0};
 	return ADYPT_OK;
 }
 }  // namespace adypt
@@ -925,8 +913,7 @@ void adypt_destroy(adypt_ctx *c)
 	if(!c) return;
 	(void)hipSetDevice(c->device);
 	for(int k = 0; k < kMaxPipes; ++k) if(c->pipes[k].stream) (void)hipStreamSynchronize(c->pipes[k].stream);
-	if(c->comm && c->comm_free) c->comm_free(c->comm);
-	if(c->denoise && c->denoise_free) c->denoise_free(c->denoise);
+	for(Attachment &a : c->attached) a.reset(); // the communicator, then the denoiser
 	delete c; // every member releases itself, the streams and events last (context.hpp)
 }
 
@@ -1235,6 +1222,20 @@ int read_local_floats(adypt_ctx *c, const float *device, int per_px, float *imag
 
 }  // namespace
 
+namespace adypt {
+int ctx_read_blocks(adypt_ctx *c, std::vector<BlockState> *blocks)
+{
+	if(c->n_local_px == 0) return ADYPT_OK; // a shard that owns no block
+	ENTER(c); // (not drained: the query is enqueued behind the frames)
+	std::vector<NoiseBlock> found;
+	TRY_CREATE(query_noise_blocks(c, &found, false));
+	blocks->reserve(blocks->size() + found.size());
+	for(size_t i = 0; i < found.size(); ++i)
+		blocks->push_back(BlockState{c->local_blocks[i], found[i].sum, found[i].count, c->ab.spp_of(i, c->spp), c->ab.frozen_at[i] != 0});
+	return ADYPT_OK;
+}
+}  // namespace adypt
+
 extern "C" {
 
 int adypt_get_noise(adypt_ctx *c, adypt_noise *out)
@@ -1243,14 +1244,9 @@ int adypt_get_noise(adypt_ctx *c, adypt_noise *out)
 	TRY_CREATE(noise_ready(c, "adypt_get_noise", 2));
 	memset(out, 0, sizeof(*out));
 	out->spp = c->spp;
-	if(c->n_local_px == 0) return ADYPT_OK; // a shard that owns no block
-	ENTER(c); // (not drained: the query is enqueued behind the frames)
-	std::vector<NoiseBlock> blocks;
-	TRY_CREATE(query_noise_blocks(c, &blocks, false));
-	std::vector<double> sum(blocks.size());
-	std::vector<uint32_t> count(blocks.size());
-	for(size_t i = 0; i < blocks.size(); ++i) { sum[i] = blocks[i].sum; count[i] = blocks[i].count; }
-	const NoiseImage img = noise_of_image(c->local_blocks.data(), sum.data(), count.data(), blocks.size(), c->n_image_px);
+	std::vector<BlockState> blocks;
+	TRY_CREATE(ctx_read_blocks(c, &blocks));
+	const NoiseImage img = noise_of_image(blocks.data(), blocks.size(), c->n_image_px);
 	out->mean_noise = img.mean_noise; out->worst_block = img.worst_block; out->worst_index = img.worst_index; out->pixels = c->n_image_px;
 	return ADYPT_OK;
 }
@@ -1287,10 +1283,9 @@ int64_t adypt_read_block_noise(adypt_ctx *c, int32_t *block_index, double *sum, 
 	const int64_t n = c->n_local_blocks;
 	if(n == 0 || capacity < n) return n; // (the size alone: nothing is written)
 	if(!block_index || !sum || !count) return ADYPT_E_INVALID;
-	ENTER(c);
-	std::vector<NoiseBlock> blocks;
-	TRY_CREATE(query_noise_blocks(c, &blocks, false));
-	for(int64_t i = 0; i < n; ++i) { block_index[i] = c->local_blocks[(size_t)i]; sum[i] = blocks[(size_t)i].sum; count[i] = blocks[(size_t)i].count; }
+	std::vector<BlockState> blocks;
+	TRY_CREATE(ctx_read_blocks(c, &blocks));
+	for(int64_t i = 0; i < n; ++i) { block_index[i] = blocks[(size_t)i].index; sum[i] = blocks[(size_t)i].sum; count[i] = blocks[(size_t)i].count; }
 	return n;
 }
 

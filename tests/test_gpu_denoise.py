@@ -200,6 +200,39 @@ def test_multi_device_on_one_card(shape, n_dev, scene_cache, sobol_matrices, mon
     single.destroy()
 
 
+def test_multi_device_with_blocks_frozen_at_different_counts(scene_cache, sobol_matrices, monkeypatch):
+    """tiny0 100x75 on 3 shards after the adaptive run of test_adaptive_blocks_at_their_own_sample_counts (three or more freeze counts, a block still
+    active): the root's images, block list and sample counts are the shards' back to back, and the filter gives the one-context result, which that test
+    holds against the truth."""
+    monkeypatch.setenv("ADYPT_MULTI_SHARED_DEVICE", "1")
+    case = A.TINY0
+    name, w, h, life, sub, every, min_spp, cap, nominal = case
+    inst, _ = A._instance(scene_cache, case)
+    single = inst.m_path_tracer
+    samples, images = A._truth(inst, case, sobol_matrices)
+    table, target, spp_b, counter, frozen = A.plan_of(case, samples)
+    spp32, counter32, frozen32 = A.schedule(table, target, every, min_spp, 32)
+    assert 0 < len(frozen32) < len(spp32) and len(set(spp32.tolist())) >= 3
+    c = inst.m_config
+    m = api.MultiPathTracer()
+    m.Initialize(c.pt_params(A.SEED), inst.m_hipscene, c.m_width, c.m_height, (0,) * 3)
+    ip, iv = inst.m_camera.matrices()
+    m.SetCamera(ip, iv, inst.m_camera.position)
+    assert m.DeviceCount() == 3
+    for t in (single, m):
+        t.SetNoiseStats(True)
+        t.TraceAdaptive(target, min_spp, 32, every)
+    before = m.ReadBlockSPP()
+    assert np.array_equal(before[1], spp32) and np.array_equal(single.ReadBlockSPP()[1], spp32)
+    assert np.array_equal(bits(m.Denoise()), bits(single.Denoise())), "default parameters"
+    assert np.array_equal(bits(m.Denoise(2, 2.0, 0.3)), bits(single.Denoise(2, 2.0, 0.3))), "(2, 2.0, 0.3)"
+    assert_guides(m.ReadDenoiseGuides(), single.ReadDenoiseGuides(), "3 shards against one context")
+    after = m.ReadBlockSPP()
+    assert np.array_equal(after[0], before[0]) and np.array_equal(after[1], before[1]), "the sample counts moved"
+    m.destroy()
+    single.destroy()
+
+
 def test_refusals(scene_cache):
     inst = make_instance(scene_cache, "tiny0", 96, 64)
     p = inst.m_path_tracer

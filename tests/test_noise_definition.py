@@ -50,7 +50,9 @@ int main(int argc, char **argv)
 		const size_t n = (size_t)h[0];
 		std::vector<int32_t> index(n); std::vector<double> sum(n); std::vector<uint32_t> count(n);
 		if(fread(index.data(), 4, n, in) != n || fread(sum.data(), 8, n, in) != n || fread(count.data(), 4, n, in) != n) return 4;
-		const NoiseImage r = noise_of_image(index.data(), sum.data(), count.data(), n, h[1]);
+		std::vector<BlockState> blocks(n);
+		for(size_t i = 0; i < n; ++i) blocks[i] = BlockState{index[i], sum[i], count[i], 0, false};
+		const NoiseImage r = noise_of_image(blocks.data(), n, h[1]);
 		fwrite(&r.mean_noise, 8, 1, out); fwrite(&r.worst_block, 8, 1, out); fwrite(&r.worst_index, 4, 1, out);
 	}
 	fclose(out);
