@@ -161,6 +161,11 @@ _SIGS = {
     "adypt_multi_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams)]),
     "adypt_multi_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_read_denoise_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # moving geometry
+    "adypt_update_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "adypt_read_bvh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adypt_get_refit_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
+    "adypt_multi_update_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),
@@ -218,6 +223,7 @@ _SIGS = {
     "adypt_bvh_free": (None, [C.c_void_p]),
     "adypt_bvh_nodes": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "adypt_bvh_tri_indices": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "adypt_bvh_refit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "adypt_woop_matrices": (None, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "adypt_camera_matrices": (None, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "adypt_sobol_points": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),

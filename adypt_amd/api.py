@@ -185,6 +185,15 @@ class WideBVH:
         self.build_info = info
         self._pull()
 
+    def Refit(self, scene: Scene) -> None:
+        """adypt_bvh_refit: the boxes of the nodes recomputed, in place, for the triangles of `scene` as they are now (the same triangles, moved).
+        The topology and GetTriIndices() stay; the Woop data of the pose is woop_matrices(scene.triangles, GetTriIndices())."""
+        nodes = np.array(self.nodes, dtype=np.uint8)  # (all or nothing: self.nodes stays when the arrays are refused)
+        t = np.ascontiguousarray(scene.triangles).view(np.uint8).reshape(-1)
+        idx = np.ascontiguousarray(self.tri_indices, dtype=np.int32)
+        N.check_host(N.lib.adypt_bvh_refit(nodes.ctypes.data, len(nodes) // NODE_BYTES, idx.ctypes.data, len(idx), t.ctypes.data, len(t) // TRI_BYTES))
+        self.nodes = nodes
+
     def GetNodes(self) -> np.ndarray:
         return self.nodes
 
@@ -548,6 +557,33 @@ class _Tracer:
         if n < 0:
             N.check(n, c)
         return {"guides": ms[0], "prepare": ms[1], "levels": [ms[i] for i in range(2, n)], "total": sum(ms[i] for i in range(n))}
+
+    # ---- moving geometry (adypt_update_triangles, include/adypt_hip.h; the definition: csrc/device/refit.hpp) ----
+    def UpdateTriangles(self, first: int, positions: np.ndarray, normals: Optional[np.ndarray] = None) -> None:
+        """New positions (count x 9 float32: p0 p1 p2) and, when given, normals (count x 9) of triangles [first, first + count); every reference's Woop
+        data and every node are then refitted on the GPU.  Leaves the tracer as Reset() does (0 spp).  Several devices: on every device."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 9)
+        nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 9)
+        if nrm is not None and len(nrm) != len(pos):
+            raise ValueError("UpdateTriangles: positions and normals differ in length")
+        self._call("update_triangles", first, len(pos), pos.ctypes.data, None if nrm is None else nrm.ctypes.data)
+
+    def ReadBVH(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(nodes uint8 [n_nodes * 80], woop float32 [n_refs, 12]) as they are on the (first) device."""
+        b = self._keep[2:4]
+        nodes, woop = np.zeros(len(b[0]), dtype=np.uint8), np.zeros((len(b[1]), 12), dtype=np.float32)
+        c = self._contexts()[0]
+        N.check(N.lib.adypt_read_bvh(c, nodes.ctypes.data, woop.ctypes.data), c)
+        return nodes, woop
+
+    def GetRefitTiming(self) -> dict:
+        """HIP-event milliseconds of the last UpdateTriangles() on the (first) device."""
+        ms = (C.c_float * 4)()
+        c = self._contexts()[0]
+        n = N.lib.adypt_get_refit_timing(c, ms, 4)
+        if n < 0:
+            N.check(n, c)
+        return {"scatter": ms[0], "references_woop": ms[1], "nodes": ms[2], "total": ms[3]}
 
     def ReadDisplay(self) -> np.ndarray:
         """What OglPathTracer::DrawScreen puts on screen (shaders/screen.glsl:15-21): H x W x 4 uint8; every context converts its own tiles."""

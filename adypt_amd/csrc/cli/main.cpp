@@ -4,7 +4,9 @@
 //
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
-//             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX]
+//             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj]
+//   --pose moved.obj: the scene of the config (and its cached .bvh) with the vertices and normals of moved.obj — the same triangles in the same order,
+//              moved — through adypt_multi_update_triangles: the BVH and the Woop data are refitted on the GPU, nothing is rebuilt
 //   --sun-visibility: enable the occlusion query the reference has commented out (pathtracer.glsl:132)
 //   --preview: what the reference shows in its window (shaders/screen.glsl), as PNG
 //   --devices: pixel tiles sharded over several GPUs of the node (adypt_create_multi), radiance gathered on the first one
@@ -36,10 +38,10 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
-	std::string noise_out, spp_out, denoise_out, guides_out;
+	std::string noise_out, spp_out, denoise_out, guides_out, pose;
 	int denoise_levels = 5;
 	int adaptive = 0;
 	int spp = 64, fp16 = 0, primary = -1, sun_visibility = 0, save_every = 0;
@@ -82,6 +84,7 @@ int main(int argc, char **argv)
 		else if(a == "--denoise" && i + 1 < argc) denoise_out = argv[++i];
 		else if(a == "--denoise-levels" && i + 1 < argc) denoise_levels = atoi(argv[++i]);
 		else if(a == "--guides-out" && i + 1 < argc) guides_out = argv[++i];
+		else if(a == "--pose" && i + 1 < argc) pose = argv[++i];
 		else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
 	}
 	const bool until = noise_target >= 0.0;
@@ -105,6 +108,23 @@ int main(int argc, char **argv)
 	int32_t n_tex = adypt_scene_textures(scene, &tex);
 	printf("[SCENE]Info: %lld triangles loaded from %s\n", (long long)n_tris, cfg.obj_filename);
 	if(*adypt_scene_warnings(scene)) printf("[SCENE]Warn: %s", adypt_scene_warnings(scene)); // undecodable textures: their materials render black
+
+	std::vector<float> pose_positions, pose_normals; // --pose: what replaces the scene's vertices and normals once the context exists
+	if(!pose.empty())
+	{
+		adypt_scene *moved = nullptr;
+		if(adypt_scene_load(pose.c_str(), &moved) != ADYPT_OK) { fprintf(stderr, "[INSTANCE]Err: Unable to load pose %s: %s\n", pose.c_str(), adypt_host_last_error()); return 1; }
+		const void *mt;
+		const int64_t n_moved = adypt_scene_triangles(moved, &mt);
+		if(n_moved != n_tris) { fprintf(stderr, "[INSTANCE]Err: pose %s has %lld triangles, the scene has %lld\n", pose.c_str(), (long long)n_moved, (long long)n_tris); return 1; }
+		pose_positions.resize((size_t)n_tris * 9); pose_normals.resize((size_t)n_tris * 9);
+		for(int64_t i = 0; i < n_tris; ++i) // (100-byte records: 9 position floats, 9 normal floats, ...)
+		{
+			memcpy(&pose_positions[(size_t)i * 9], (const uint8_t *)mt + i * 100, 36);
+			memcpy(&pose_normals[(size_t)i * 9], (const uint8_t *)mt + i * 100 + 36, 36);
+		}
+		adypt_scene_free(moved);
+	}
 
 	adypt_bvh *bvh = nullptr;
 	if(adypt_bvh_load(cfg.bvh_filename, &cfg.bvh, &bvh) != ADYPT_OK)
@@ -142,6 +162,13 @@ int main(int argc, char **argv)
 	if(r == ADYPT_OK) r = adypt_multi_set_instrumentation(multi, 1);
 	if(r == ADYPT_OK && (until || denoise)) r = adypt_multi_set_noise_stats(multi, 1);
 	if(r != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+	if(!pose.empty())
+	{
+		if(adypt_multi_update_triangles(multi, 0, n_tris, pose_positions.data(), pose_normals.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		float ms[4] = {0, 0, 0, 0};
+		(void)adypt_get_refit_timing(adypt_multi_context(multi, 0), ms, 4);
+		printf("[PT]INFO: pose %s: %lld triangles moved, refit %.3f ms (scatter %.3f, references and Woop %.3f, nodes %.3f)\n", pose.c_str(), (long long)n_tris, ms[3], ms[0], ms[1], ms[2]);
+	}
 
 	std::vector<float> rgb((size_t)cfg.width * cfg.height * 3, 0.0f);
 	std::vector<uint8_t> rgba8;

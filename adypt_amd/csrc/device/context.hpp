@@ -90,7 +90,7 @@ struct adypt_ctx {
 	Event sobol_done[kSobolSlots];
 	std::vector<EventPair> events, free_events; // kernel timing (instrumentation flag 1): pairs in flight, pairs to use again
 
-	// scene (immutable after create)
+	// scene (the topology is immutable after create; adypt_update_triangles, refit.hip, rewrites positions, normals, Woop data and the boxes in place)
 	Buffer<uint4> d_nodes;
 	Buffer<float4> d_woop, d_triangles, d_materials;
 	Buffer<int32_t> d_tri_indices, d_local_blocks;
@@ -191,7 +191,8 @@ struct adypt_ctx {
 	int view_type = 0;          // uuViewer.uType of the image in d_accum: the viewer type of the last primary frame, 3 after path tracing
 
 	// What other translation units park here (ctx_access.hpp): multi.hip the RCCL communicator state of the native multi-GPU path, denoise.hip the
-	// denoiser's images (allocated at the first adypt_denoise / adypt_read_denoise_guides).  adypt_destroy releases them in this order.
+	// denoiser's images (allocated at the first adypt_denoise / adypt_read_denoise_guides), refit.hip the refit plan, level lists and exact boxes (made at the
+	// first adypt_update_triangles).  adypt_destroy releases them in this order.
 	Attachment attached[kAttachKinds];
 
 	double trace_ms = 0, shade_ms = 0, path_ms = 0;

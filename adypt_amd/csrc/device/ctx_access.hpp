@@ -33,7 +33,7 @@ struct Attachment {
 	~Attachment() { reset(); }
 	void reset(void *q = nullptr, void (*f)(void *) = nullptr) { if(p && free_fn) free_fn(p); p = q; free_fn = f; }
 };
-enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachKinds }; // multi.hip's communicator, denoise.hip's images
+enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes
 Attachment &ctx_attachment(adypt_ctx *c, AttachKind kind);
 
 // ---- noise statistics and adaptive sampling, per context (adypt_trace_adaptive and adypt_multi_trace_adaptive are one loop over these) ----
@@ -62,6 +62,22 @@ int ctx_denoise_ready(adypt_ctx *c, const char *fn);
 DenoiseInputs ctx_denoise_inputs(adypt_ctx *c);
 // see tracer.hip
 int ctx_capture_guides(adypt_ctx *c, const char *fn, float4 *albedo, float4 *normal, float4 *position, float4 *hits);
+
+// ---- moving geometry (refit.hip), per context ----
+// the scene arrays on the device, which refit.hip rewrites in place between frames
+struct CtxScene {
+	uint4 *nodes;                 // n_nodes x 80 bytes
+	float4 *woop;                 // n_refs x 3
+	float4 *triangles;            // n_tris records of tri_float4 float4: floats 0..8 the positions, 9..17 the normals (shade.hpp)
+	const int32_t *tri_indices;   // n_refs
+	int64_t n_nodes, n_refs, n_tris;
+	int tri_float4;
+};
+CtxScene ctx_scene(adypt_ctx *c);
+// the per-reference copy of the triangle records made again from the records as they are now, on the context's stream; nothing when the context keeps none
+int ctx_expand_references(adypt_ctx *c);
+// everything the context has enqueued on any of its streams has finished (the scene arrays are about to change under it)
+int ctx_drain(adypt_ctx *c);
 // multi.hip: the message adypt_multi_last_error answers
 void multi_set_error(adypt_multi *m, const std::string &msg);
 

@@ -1,0 +1,278 @@
+// Moving geometry (include/adypt_hip.h adypt_update_triangles ...; the definition: refit.hpp, the order: refit_plan.hpp, the Woop data: woop.hpp).  A
+// translation unit of its own: nothing here is part of the tracer's code object.  What one update runs, all on the context's stream after the context
+// has been drained:
+//     k_refit_scatter  the new positions (and normals) of triangles [first, first + count) into the device triangle records
+//     (tracer.hip)     k_expand_references again, when the context keeps the per-reference copy of the records
+//     k_refit_woop     one thread per reference: its triangle's Woop matrix
+//     k_refit_nodes    one launch per level of the tree, deepest first: 8 lanes per node, one slot per lane.  A level reads only the exact boxes of
+//                      deeper levels, which earlier launches on the same stream wrote: the stream order is the whole dependency — no atomics, no
+//                      flags between workgroups, no fences.
+// The plan (every node's level) is made once per context, at the first update, from one copy of the node array to the host; the topology never changes.
+#include "ctx_access.hpp"
+#include "resources.hpp"
+#include "refit_plan.hpp"
+#include "woop.hpp"
+#include "../../../include/adypt_hip.h"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+using namespace adypt;
+
+namespace {
+
+constexpr int kRefitThreads = 256;
+constexpr int kLanesPerNode = 8, kNodesPerGroup = kRefitThreads / kLanesPerNode; // a workgroup refits 32 nodes
+constexpr int kNodeUint4 = kNodeBytes / 16;
+
+// one thread per triangle: 9 position floats, and 9 normal floats when given, into floats 0..8 and 9..17 of the record
+__global__ __launch_bounds__(kRefitThreads) void k_refit_scatter(float4 *triangles, int tri_float4, int64_t first, int64_t count, const float *positions, const float *normals)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= count) return;
+	float4 *rec = triangles + (size_t)(first + i) * (size_t)tri_float4;
+	const float *p = positions + (size_t)i * 9;
+	rec[0] = make_float4(p[0], p[1], p[2], p[3]);
+	rec[1] = make_float4(p[4], p[5], p[6], p[7]);
+	if(!normals) { ((float *)rec)[8] = p[8]; return; }
+	const float *n = normals + (size_t)i * 9;
+	rec[2] = make_float4(p[8], n[0], n[1], n[2]);
+	rec[3] = make_float4(n[3], n[4], n[5], n[6]);
+	((float2 *)rec)[8] = make_float2(n[7], n[8]);
+}
+
+// one thread per reference
+__global__ __launch_bounds__(kRefitThreads) void k_refit_woop(const float4 *triangles, int tri_float4, const int32_t *tri_indices, int64_t n_refs, float4 *woop)
+{
+	const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(r >= n_refs) return;
+	const float4 *rec = triangles + (size_t)tri_indices[r] * (size_t)tri_float4;
+	const float4 a = rec[0], b = rec[1], c = rec[2];
+	const float p[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x};
+	float o[12];
+	woop_matrix(p, o);
+	float4 *out = woop + (size_t)r * 3;
+	out[0] = make_float4(o[0], o[1], o[2], o[3]);
+	out[1] = make_float4(o[4], o[5], o[6], o[7]);
+	out[2] = make_float4(o[8], o[9], o[10], o[11]);
+}
+
+// The nodes level[0 .. n_level) of one level.  Lane s of a node's 8 lanes owns slot s: it finds the slot's exact box (a child's from `boxes`, a leaf's from
+// its triangles), the 8 boxes are united by three xor-shuffle steps (refit_min / refit_max do not depend on the order: every lane ends with the same
+// bits), every lane quantises its own slot.  The record is assembled in LDS — the old record first, so that the bytes of empty slots and the fields
+// that stay need no special case — and goes back with five 16-byte stores.
+__global__ __launch_bounds__(kRefitThreads) void k_refit_nodes(uint4 *nodes, float4 *boxes, const int32_t *level, int n_level, const int32_t *tri_indices, const float4 *triangles,
+                                                              int tri_float4)
+{
+	__shared__ uint4 s_node[kNodesPerGroup][kNodeUint4];
+	const int g = threadIdx.x / kLanesPerNode, s = threadIdx.x % kLanesPerNode;
+	const int k = blockIdx.x * kNodesPerGroup + g;
+	const bool valid = k < n_level;
+	const size_t node = valid ? (size_t)level[k] : 0;
+	if(valid && s < kNodeUint4) s_node[g][s] = nodes[node * kNodeUint4 + s];
+	__syncthreads();
+	uint8_t *bytes = (uint8_t *)s_node[g];
+	RefitBox mine = refit_empty_box();
+	uint32_t meta = 0, old_word3 = 0;
+	if(valid)
+	{
+		meta = bytes[kNodeMeta + s];
+		old_word3 = s_node[g][0].w;
+		const uint32_t child_base = s_node[g][1].x, tri_base = s_node[g][1].y;
+		const int kind = refit_slot_kind(meta);
+		if(kind == kSlotInternal)
+		{
+			const size_t child = (size_t)child_base + refit_child_offset(meta);
+			const float4 lo = boxes[child * 2], hi = boxes[child * 2 + 1];
+			mine = RefitBox{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}};
+		}
+		else if(kind == kSlotLeaf)
+		{
+			const int count = refit_leaf_count(meta);
+			for(int r = 0; r < count; ++r)
+			{
+				const float4 *rec = triangles + (size_t)tri_indices[(size_t)tri_base + refit_leaf_offset(meta) + (size_t)r] * (size_t)tri_float4;
+				const float4 a = rec[0], b = rec[1], c = rec[2];
+				const float p[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x};
+				mine = refit_union(mine, refit_triangle_box(p));
+			}
+		}
+	}
+	RefitBox box = mine;
+	int occupied = meta != 0 ? 1 : 0;
+	for(int m = 1; m < kLanesPerNode; m <<= 1)
+	{
+		for(int a = 0; a < 3; ++a)
+		{
+			box.lo[a] = refit_min(box.lo[a], __shfl_xor(box.lo[a], m));
+			box.hi[a] = refit_max(box.hi[a], __shfl_xor(box.hi[a], m));
+		}
+		occupied |= __shfl_xor(occupied, m);
+	}
+	if(valid && s == 0)
+	{
+		boxes[node * 2] = make_float4(box.lo[0], box.lo[1], box.lo[2], 0.0f);
+		boxes[node * 2 + 1] = make_float4(box.hi[0], box.hi[1], box.hi[2], 0.0f);
+	}
+	const bool rewrite = valid && occupied; // (a node without an occupied slot stays as it is: refit.hpp)
+	if(rewrite)
+	{
+		float p[3];
+		uint32_t e[3], word3;
+		refit_header(box, old_word3, p, &word3, e);
+		if(meta != 0)
+		{
+			uint8_t q[6];
+			refit_slot_bytes(box, e, mine, q);
+			for(int a = 0; a < 6; ++a) bytes[kNodeQuant + a * 8 + s] = q[a];
+		}
+		if(s == 0) s_node[g][0] = make_uint4(refit_bits(p[0]), refit_bits(p[1]), refit_bits(p[2]), word3);
+	}
+	__syncthreads();
+	if(rewrite && s < kNodeUint4) nodes[node * kNodeUint4 + s] = s_node[g][s];
+}
+
+constexpr int kTimingEvents = 4; // start, scatter, references + Woop, nodes
+
+// Everything the refit keeps per context; parked in the context (ctx_attachment), freed by adypt_destroy (the context's device is current then).
+struct Refitter {
+	RefitPlan plan;
+	Buffer<int32_t> d_order;   // RefitPlan::order: 4 B per node
+	Buffer<float4> d_boxes;    // the exact boxes: 32 B per node
+	Buffer<float> d_stage;     // the caller's positions and normals on their way to the records: up to 72 B per updated triangle
+	Event ev[kTimingEvents];
+	bool have_plan = false, timed = false;
+};
+
+void free_refitter(void *p) { delete (Refitter *)p; }
+
+int cfail(adypt_ctx *c, int code, const std::string &msg) { ctx_set_error(c, msg); return code; }
+
+#define RF_TRY(c, expr)                                                                                     \
+	do {                                                                                                    \
+		const hipError_t e_ = (expr);                                                                       \
+		if(e_ != hipSuccess) { (void)hipGetLastError(); return cfail(c, e_ == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } \
+	} while(0)
+#define RF_STEP(expr) do { const int r_ = (expr); if(r_ != ADYPT_OK) return r_; } while(0)
+
+Refitter *refitter_if_any(adypt_ctx *c) { return (Refitter *)ctx_attachment(c, kAttachRefit).p; }
+Refitter *refitter_of(adypt_ctx *c)
+{
+	if(!refitter_if_any(c)) ctx_attachment(c, kAttachRefit).reset(new Refitter(), free_refitter);
+	return refitter_if_any(c);
+}
+
+// the plan from one copy of the node array, its level lists and the box array on the device (the context is drained)
+int ensure_plan(adypt_ctx *c, Refitter *rf, const CtxScene &sc, hipStream_t stream)
+{
+	if(rf->have_plan) return ADYPT_OK;
+	std::vector<uint8_t> nodes((size_t)sc.n_nodes * kNodeBytes);
+	RF_TRY(c, hipMemcpyAsync(nodes.data(), sc.nodes, nodes.size(), hipMemcpyDeviceToHost, stream));
+	RF_TRY(c, hipStreamSynchronize(stream));
+	std::string why;
+	if(!plan_refit(nodes.data(), sc.n_nodes, sc.n_refs, &rf->plan, &why)) return cfail(c, ADYPT_E_INVALID, "adypt_update_triangles: the node array is not one tree: " + why);
+	RF_TRY(c, rf->d_order.alloc(rf->plan.order.size() * sizeof(int32_t)));
+	RF_TRY(c, rf->d_boxes.alloc((size_t)sc.n_nodes * 2 * sizeof(float4)));
+	RF_TRY(c, hipMemcpyAsync(rf->d_order, rf->plan.order.data(), rf->plan.order.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+	RF_TRY(c, hipStreamSynchronize(stream));
+	for(Event &e : rf->ev) if(!(hipEvent_t)e) RF_TRY(c, hipEventCreate(e.out()));
+	rf->have_plan = true;
+	return ADYPT_OK;
+}
+
+unsigned grid_of(int64_t n, int per_group) { return (unsigned)((n + per_group - 1) / per_group); }
+
+}  // namespace
+
+extern "C" {
+
+int adypt_update_triangles(adypt_ctx *c, int64_t first, int64_t count, const float *positions, const float *normals)
+{
+	if(!c) return ADYPT_E_INVALID;
+	const CtxScene sc = ctx_scene(c);
+	if(!positions) return cfail(c, ADYPT_E_INVALID, "adypt_update_triangles: positions is null");
+	if(first < 0 || count < 0 || first > sc.n_tris || count > sc.n_tris - first)
+		return cfail(c, ADYPT_E_INVALID, "adypt_update_triangles: triangles [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) + ") are not all of the scene's " + std::to_string(sc.n_tris));
+	RF_STEP(ctx_drain(c));
+	const CtxInfo i = ctx_info(c);
+	Refitter *rf = refitter_of(c);
+	RF_STEP(ensure_plan(c, rf, sc, i.stream));
+	const size_t n_stage = (size_t)count * 9, stage_bytes = std::max<size_t>(n_stage * (normals ? 2 : 1) * sizeof(float), 64);
+	if(rf->d_stage.bytes() < stage_bytes) RF_TRY(c, rf->d_stage.alloc(stage_bytes));
+	rf->timed = false;
+	RF_TRY(c, hipEventRecord(rf->ev[0], i.stream));
+	if(count > 0)
+	{
+		float *d_pos = rf->d_stage, *d_nrm = normals ? d_pos + n_stage : nullptr;
+		RF_TRY(c, hipMemcpyAsync(d_pos, positions, n_stage * sizeof(float), hipMemcpyHostToDevice, i.stream));
+		if(normals) RF_TRY(c, hipMemcpyAsync(d_nrm, normals, n_stage * sizeof(float), hipMemcpyHostToDevice, i.stream));
+		hipLaunchKernelGGL(k_refit_scatter, dim3(grid_of(count, kRefitThreads)), dim3(kRefitThreads), 0, i.stream, sc.triangles, sc.tri_float4, first, count, (const float *)d_pos, (const float *)d_nrm);
+		RF_TRY(c, hipGetLastError());
+	}
+	RF_TRY(c, hipEventRecord(rf->ev[1], i.stream));
+	RF_STEP(ctx_expand_references(c));
+	if(sc.n_refs > 0)
+	{
+		hipLaunchKernelGGL(k_refit_woop, dim3(grid_of(sc.n_refs, kRefitThreads)), dim3(kRefitThreads), 0, i.stream, (const float4 *)sc.triangles, sc.tri_float4, sc.tri_indices, sc.n_refs, sc.woop);
+		RF_TRY(c, hipGetLastError());
+	}
+	RF_TRY(c, hipEventRecord(rf->ev[2], i.stream));
+	for(int l = rf->plan.levels() - 1; l >= 0; --l)
+	{
+		const int64_t begin = rf->plan.level_begin[(size_t)l], n = rf->plan.level_begin[(size_t)l + 1] - begin;
+		hipLaunchKernelGGL(k_refit_nodes, dim3(grid_of(n, kNodesPerGroup)), dim3(kRefitThreads), 0, i.stream, sc.nodes, rf->d_boxes.get(), (const int32_t *)rf->d_order + begin, (int)n, sc.tri_indices,
+		                   (const float4 *)sc.triangles, sc.tri_float4);
+		RF_TRY(c, hipGetLastError());
+	}
+	RF_TRY(c, hipEventRecord(rf->ev[3], i.stream));
+	RF_TRY(c, hipStreamSynchronize(i.stream));
+	rf->timed = true;
+	return adypt_reset(c); // the image, the frozen blocks, the frames parked ahead and the primary-hit cache were the old pose's
+}
+
+int adypt_read_bvh(adypt_ctx *c, void *nodes_out, float *woop_out)
+{
+	if(!c) return ADYPT_E_INVALID;
+	const CtxScene sc = ctx_scene(c);
+	const CtxInfo i = ctx_info(c);
+	RF_TRY(c, hipSetDevice(i.device));
+	RF_TRY(c, hipStreamSynchronize(i.stream));
+	if(nodes_out) RF_TRY(c, hipMemcpy(nodes_out, sc.nodes, (size_t)sc.n_nodes * kNodeBytes, hipMemcpyDeviceToHost));
+	if(woop_out && sc.n_refs > 0) RF_TRY(c, hipMemcpy(woop_out, sc.woop, (size_t)sc.n_refs * 12 * sizeof(float), hipMemcpyDeviceToHost));
+	return ADYPT_OK;
+}
+
+int adypt_get_refit_timing(adypt_ctx *c, float *ms, int capacity)
+{
+	if(!c || !ms || capacity < 0) return ADYPT_E_INVALID;
+	Refitter *rf = refitter_if_any(c);
+	if(!rf || !rf->timed) return cfail(c, ADYPT_E_STATE, "adypt_get_refit_timing: nothing has been refitted yet (adypt_update_triangles)");
+	const int n = kTimingEvents;
+	if(capacity < n) return n;
+	for(int k = 0; k < n - 1; ++k)
+	{
+		ms[k] = 0.0f;
+		(void)hipEventElapsedTime(&ms[k], rf->ev[k], rf->ev[k + 1]);
+	}
+	ms[n - 1] = 0.0f;
+	(void)hipEventElapsedTime(&ms[n - 1], rf->ev[0], rf->ev[n - 1]);
+	(void)hipGetLastError();
+	return n;
+}
+
+// the scene is replicated: the same update on every device
+int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals)
+{
+	const int n_dev = adypt_multi_device_count(m);
+	if(n_dev < 1) return ADYPT_E_INVALID;
+	for(int k = 0; k < n_dev; ++k)
+	{
+		adypt_ctx *c = adypt_multi_context(m, k);
+		const int r = adypt_update_triangles(c, first, count, positions, normals);
+		if(r != ADYPT_OK) { multi_set_error(m, adypt_last_error(c)); return r; } // (a bad range is refused by the first context: none has changed)
+	}
+	return ADYPT_OK;
+}
+
+}  // extern "C"

@@ -724,6 +724,27 @@ int ctx_capture_guides(adypt_ctx *c, const char *fn, float4 *albedo, float4 *nor
 	}
 	return ADYPT_OK;
 }
+
+// ---- what the refit (refit.hip) needs of a context ----
+CtxScene ctx_scene(adypt_ctx *c)
+{
+	return CtxScene{c->d_nodes, c->d_woop, c->d_triangles, c->d_tri_indices, c->n_nodes, c->n_refs, c->n_tris, kTriFloat4};
+}
+int ctx_expand_references(adypt_ctx *c)
+{
+	const size_t n16 = (size_t)c->n_refs * kTriFloat4;
+	if(!c->d_ref_triangles || !n16) return ADYPT_OK;
+	hipLaunchKernelGGL(k_expand_references, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, c->stream, (const float4 *)c->d_triangles, (const int32_t *)c->d_tri_indices, (size_t)c->n_refs, (float4 *)c->d_ref_triangles);
+	HIP_TRY(c, hipGetLastError());
+	return ADYPT_OK;
+}
+int ctx_drain(adypt_ctx *c)
+{
+	HIP_TRY(c, hipSetDevice(c->device));
+	for(int k = 0; k < kMaxPipes; ++k) if(c->pipes[k].stream) HIP_TRY(c, hipStreamSynchronize(c->pipes[k].stream));
+	harvest_events(c);
+	return ADYPT_OK; // (a stack overflow of those frames stays for adypt_wait to report)
+}
 }  // namespace adypt
 
 namespace {
@@ -913,7 +934,7 @@ void adypt_destroy(adypt_ctx *c)
 	if(!c) return;
 	(void)hipSetDevice(c->device);
 	for(int k = 0; k < kMaxPipes; ++k) if(c->pipes[k].stream) (void)hipStreamSynchronize(c->pipes[k].stream);
-	for(Attachment &a : c->attached) a.reset(); // the communicator, then the denoiser
+	for(Attachment &a : c->attached) a.reset(); // the communicator, the denoiser, the refit
 	delete c; // every member releases itself, the streams and events last (context.hpp)
 }
 

@@ -2,6 +2,7 @@
 // driver: Woop precompute, camera matrices, Sobol stream, per-pixel shift bytes, .bvh cache, OpenEXR output.
 #include "builders.hpp"
 #include "exact_sort.hpp"
+#include "../device/woop.hpp"
 #include "../../../include/adypt_hip.h"
 
 #include <algorithm>
@@ -19,34 +20,6 @@ struct adypt_bvh {
 };
 
 namespace {
-
-// ---- glm::inverse(mat4) (dep/glm/detail/func_matrix.inl:294-351): cofactor expansion, column-major m[c*4+r] ----
-void inverse4(const float *a, float *out)
-{
-	auto m = [&](int c, int r) { return a[c * 4 + r]; };
-	float c00 = m(2, 2) * m(3, 3) - m(3, 2) * m(2, 3), c02 = m(1, 2) * m(3, 3) - m(3, 2) * m(1, 3), c03 = m(1, 2) * m(2, 3) - m(2, 2) * m(1, 3);
-	float c04 = m(2, 1) * m(3, 3) - m(3, 1) * m(2, 3), c06 = m(1, 1) * m(3, 3) - m(3, 1) * m(1, 3), c07 = m(1, 1) * m(2, 3) - m(2, 1) * m(1, 3);
-	float c08 = m(2, 1) * m(3, 2) - m(3, 1) * m(2, 2), c10 = m(1, 1) * m(3, 2) - m(3, 1) * m(1, 2), c11 = m(1, 1) * m(2, 2) - m(2, 1) * m(1, 2);
-	float c12 = m(2, 0) * m(3, 3) - m(3, 0) * m(2, 3), c14 = m(1, 0) * m(3, 3) - m(3, 0) * m(1, 3), c15 = m(1, 0) * m(2, 3) - m(2, 0) * m(1, 3);
-	float c16 = m(2, 0) * m(3, 2) - m(3, 0) * m(2, 2), c18 = m(1, 0) * m(3, 2) - m(3, 0) * m(1, 2), c19 = m(1, 0) * m(2, 2) - m(2, 0) * m(1, 2);
-	float c20 = m(2, 0) * m(3, 1) - m(3, 0) * m(2, 1), c22 = m(1, 0) * m(3, 1) - m(3, 0) * m(1, 1), c23 = m(1, 0) * m(2, 1) - m(2, 0) * m(1, 1);
-	const float f0[4] = {c00, c00, c02, c03}, f1[4] = {c04, c04, c06, c07}, f2[4] = {c08, c08, c10, c11};
-	const float f3[4] = {c12, c12, c14, c15}, f4[4] = {c16, c16, c18, c19}, f5[4] = {c20, c20, c22, c23};
-	const float v0[4] = {m(1, 0), m(0, 0), m(0, 0), m(0, 0)}, v1[4] = {m(1, 1), m(0, 1), m(0, 1), m(0, 1)};
-	const float v2[4] = {m(1, 2), m(0, 2), m(0, 2), m(0, 2)}, v3[4] = {m(1, 3), m(0, 3), m(0, 3), m(0, 3)};
-	float inv[4][4];
-	for(int i = 0; i < 4; ++i)
-	{
-		const float sa = (i & 1) ? -1.0f : 1.0f, sb = -sa;
-		inv[0][i] = (v1[i] * f0[i] - v2[i] * f1[i] + v3[i] * f2[i]) * sa;
-		inv[1][i] = (v0[i] * f0[i] - v2[i] * f3[i] + v3[i] * f4[i]) * sb;
-		inv[2][i] = (v0[i] * f1[i] - v1[i] * f3[i] + v3[i] * f5[i]) * sa;
-		inv[3][i] = (v0[i] * f2[i] - v1[i] * f4[i] + v2[i] * f5[i]) * sb;
-	}
-	float det = (m(0, 0) * inv[0][0] + m(0, 1) * inv[1][0]) + (m(0, 2) * inv[2][0] + m(0, 3) * inv[3][0]);
-	float ood = 1.0f / det;
-	for(int c = 0; c < 4; ++c) for(int r = 0; r < 4; ++r) out[c * 4 + r] = inv[c][r] * ood;
-}
 
 // glm::rotate (dep/glm/ext/matrix_transform.inl:18-46)
 void rotate4(const float *m, float angle, const float axis[3], float *out)
@@ -321,15 +294,9 @@ void adypt_woop_matrices(const void *tris_, const int32_t *tri_indices, int64_t 
 	parallel_ranges(n_refs, 1 << 16, [=](int64_t begin, int64_t end) {
 	for(int64_t i = begin; i < end; ++i)
 	{
-		const TriRec &t = tris[tri_indices[i]];
-		Vec3 e0 = t.p[0] - t.p[2], e1 = t.p[1] - t.p[2];
-		Vec3 n = {e0.y * e1.z - e1.y * e0.z, e0.z * e1.x - e1.z * e0.x, e0.x * e1.y - e1.x * e0.y};
-		const float A[16] = {e0.x, e1.x, n.x, t.p[2].x, e0.y, e1.y, n.y, t.p[2].y, e0.z, e1.z, n.z, t.p[2].z, 0.0f, 0.0f, 0.0f, 1.0f};
-		float inv[16];
-		inverse4(A, inv);
-		float *o = out + i * 12;
-		o[0] = inv[8]; o[1] = inv[9]; o[2] = inv[10]; o[3] = -inv[11];
-		memcpy(o + 4, inv, 8 * sizeof(float));
+		float p[9];
+		memcpy(p, tris[tri_indices[i]].p, sizeof(p));
+		woop_matrix(p, out + i * 12); // (../device/woop.hpp: the text the device refit compiles too)
 	}
 	});
 }

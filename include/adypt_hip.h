@@ -294,6 +294,24 @@ int adypt_read_denoise_guides(adypt_ctx *ctx, float *albedo, float *normal, floa
  * them only when capacity holds them all. */
 int adypt_get_denoise_timing(adypt_ctx *ctx, float *ms, int capacity);
 
+/* ---- moving geometry: new vertex positions without a new BVH and a new context ----------------------------------------------------------------
+ * The tree's topology stays valid when vertices move; what goes stale are the boxes, the Woop data and the triangle records.  adypt_update_triangles
+ * replaces the positions (count x 9 floats: p0 p1 p2 of every triangle) and, unless normals is NULL, the normals (count x 9 floats) of triangles
+ * [first, first + count), and then ALWAYS recomputes the Woop data of every reference and refits every node, bottom up, on the GPU: the exact rule is
+ * csrc/device/refit.hpp, which the host's adypt_bvh_refit compiles too — adypt_read_bvh afterwards equals adypt_bvh_refit + adypt_woop_matrices of the
+ * moved triangles byte for byte (the 12 Woop floats of a degenerate triangle are NaN on both sides; a NaN's sign and payload are the processor's).  Material ids and texture coordinates stay.  The context is drained first (frames enqueued earlier finish with the old
+ * pose) and is left as adypt_reset leaves it: 0 spp, frozen blocks thawed, frames parked ahead dropped, the primary-hit cache invalid.  A refitted tree
+ * renders the moved scene correctly but is slower to traverse than a rebuilt one, the more the further the pose is from the one the tree was built
+ * for, and more so for trees built with spatial splits (Moving geometry): rebuild for poses that are far away.
+ * ADYPT_E_INVALID (a range outside the scene, positions NULL) changes nothing.  The first call makes the refit plan from one device-to-host copy of the
+ * nodes and allocates 36 B per node; every call stages the caller's arrays on the device (up to 72 B per updated triangle, kept). */
+int adypt_update_triangles(adypt_ctx *ctx, int64_t first, int64_t count, const float *positions, const float *normals);
+/* the node array (n_nodes x 80 bytes) and the Woop array (n_refs x 12 floats) as they are on the device; either may be NULL */
+int adypt_read_bvh(adypt_ctx *ctx, void *nodes_out, float *woop_out);
+/* HIP-event times of the last adypt_update_triangles in ms: [0] the upload and scatter of the new data, [1] the per-reference records and the Woop
+ * data, [2] the nodes (every level), [3] all of it.  Returns the number of entries and writes them only when capacity holds them all. */
+int adypt_get_refit_timing(adypt_ctx *ctx, float *ms, int capacity);
+
 /* Trace an arbitrary batch of rays through the same traversal kernel: rays = n x 8 floats
  * (ox, oy, oz, tmin, dx, dy, dz, unused).  with_stats selects the instrumented kernel variant. */
 int adypt_trace_rays(adypt_ctx *ctx, const float *rays, int64_t n, adypt_hit *hits, int with_stats);
@@ -394,6 +412,9 @@ int adypt_multi_trace_adaptive(adypt_multi *m, double target, int min_spp, int m
 int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *params);
 int adypt_multi_read_denoised(adypt_multi *m, float *rgb);
 int adypt_multi_read_denoise_guides(adypt_multi *m, float *albedo, float *normal, float *position, uint8_t *hit); /* every device writes its own tiles */
+/* adypt_update_triangles on every device: the scene is replicated and every device refits its own copy; no collective.  (One process per GPU: every
+ * rank calls adypt_update_triangles on its own context.) */
+int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals);
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

@@ -85,6 +85,13 @@ int adypt_bvh_save(const adypt_bvh *b, const char *path, const adypt_bvh_params 
 void adypt_bvh_free(adypt_bvh *b);
 int64_t adypt_bvh_nodes(const adypt_bvh *b, const void **nodes);          /* 80-byte records */
 int64_t adypt_bvh_tri_indices(const adypt_bvh *b, const int32_t **idx);
+/* Moved geometry without a rebuild: recomputes, in place, the boxes of `nodes` (p, the exponent bytes and the quantised bytes of every occupied slot)
+ * from the triangles as they are now.  The topology and the reference order stay, so tri_indices and the triangle count must be the tree's.  The rule
+ * is csrc/device/refit.hpp (the device path, adypt_update_triangles, compiles the same text); the Woop array is adypt_woop_matrices of the moved
+ * triangles.  A leaf bounds its whole triangles, so a tree built with spatial splits gets larger boxes than the builder's clipped ones: correct, but
+ * slower to traverse (Moving geometry).  ADYPT_E_INVALID — nothing is written — for arrays that are not one tree: a child index or a
+ * reference range out of range, a node reached twice or not at all, a triangle index out of range. */
+int adypt_bvh_refit(void *nodes, int64_t n_nodes, const int32_t *tri_indices, int64_t n_refs, const void *triangles, int64_t n_tris);
 
 /* ---- small restated host functions ---------------------------------------------------------------------------- */
 /* OglScene::init_triangles (src/Tracer/OglScene.cpp:93-116): out = 12 floats per reference */

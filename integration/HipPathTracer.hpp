@@ -189,6 +189,17 @@ public:
 		return false;
 	}
 
+	// Moving geometry (adypt_hip.h, adypt_update_triangles): new positions (count x 9 floats, p0 p1 p2 per triangle) and, unless null, normals (count x 9)
+	// of triangles [first, first + count) in the order of Scene::GetTriangles(); every device then refits its BVH and Woop data on the GPU — no rebuild,
+	// no new context.  The sample counter restarts as after a Trace(false).  A pose far from the one the BVH was built for traverses slower than a
+	// rebuilt BVH would (Moving geometry).
+	bool UpdateTriangles(int64_t first, int64_t count, const float *positions, const float *normals = nullptr)
+	{
+		if(adypt_multi_update_triangles(m_gpus, first, count, positions, normals) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
 	// what DrawScreen puts on screen, for a caller-owned W x H RGBA8 texture / window (every device fills in its own tiles)
 	bool ReadScreen(std::vector<uint8_t> *rgba8) const
 	{
