@@ -98,6 +98,11 @@ class BuildInfo(C.Structure):
                 ("wide_ms", C.c_double)]
 
 
+class RebuildInfo(C.Structure):
+    """adypt_rebuild_info."""
+    _fields_ = [("n_nodes", C.c_int64), ("n_refs", C.c_int64), ("levels", C.c_int32), ("binary_depth", C.c_int32)]
+
+
 # every symbol include/*.h declares, with its signature (tests/test_abi.py checks the export list against the headers)
 _SIGS = {
     # adypt_hip.h
@@ -166,6 +171,12 @@ _SIGS = {
     "adypt_read_bvh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "adypt_get_refit_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
     "adypt_multi_update_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    # rebuilding the tree on the GPU
+    "adypt_rebuild_bvh": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(RebuildInfo)]),
+    "adypt_get_rebuild_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
+    "adypt_get_bvh_sizes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "adypt_read_tri_indices": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_multi_rebuild_bvh": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(RebuildInfo)]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),
@@ -218,6 +229,8 @@ _SIGS = {
     "adypt_host_get_threads": (C.c_int, []),
     "adypt_host_selftest_sort": (C.c_int, [C.c_int64, C.c_uint32, C.c_int, C.c_int, C.c_int64]),
     "adypt_bvh_build": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(C.c_void_p), C.POINTER(BuildInfo)]),
+    "adypt_bvh_build_linear": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(C.c_void_p), C.POINTER(BuildInfo)]),
+    "adypt_lbvh_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "adypt_bvh_load": (C.c_int, [C.c_char_p, C.POINTER(BvhParams), C.POINTER(C.c_void_p)]),
     "adypt_bvh_save": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(BvhParams)]),
     "adypt_bvh_free": (None, [C.c_void_p]),

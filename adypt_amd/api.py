@@ -185,6 +185,15 @@ class WideBVH:
         self.build_info = info
         self._pull()
 
+    def BuildLinear(self, scene: Scene, cfg: N.BvhParams) -> None:
+        """adypt_bvh_build_linear: the tree of a linear BVH (csrc/device/lbvh.hpp) — what RebuildBVH() builds on the GPU, byte for byte.  No spatial
+        splits (cfg.max_spatial_depth is ignored): one reference per triangle."""
+        self._free()
+        info = N.BuildInfo()
+        N.check_host(N.lib.adypt_bvh_build_linear(scene._h, C.byref(cfg), C.byref(self._h), C.byref(info)))
+        self.build_info = info
+        self._pull()
+
     def Refit(self, scene: Scene) -> None:
         """adypt_bvh_refit: the boxes of the nodes recomputed, in place, for the triangles of `scene` as they are now (the same triangles, moved).
         The topology and GetTriIndices() stay; the Woop data of the pose is woop_matrices(scene.triangles, GetTriIndices())."""
@@ -570,11 +579,42 @@ class _Tracer:
 
     def ReadBVH(self) -> Tuple[np.ndarray, np.ndarray]:
         """(nodes uint8 [n_nodes * 80], woop float32 [n_refs, 12]) as they are on the (first) device."""
-        b = self._keep[2:4]
-        nodes, woop = np.zeros(len(b[0]), dtype=np.uint8), np.zeros((len(b[1]), 12), dtype=np.float32)
         c = self._contexts()[0]
+        n_nodes, n_refs = self.GetBVHSizes()
+        nodes, woop = np.zeros(n_nodes * NODE_BYTES, dtype=np.uint8), np.zeros((n_refs, 12), dtype=np.float32)
         N.check(N.lib.adypt_read_bvh(c, nodes.ctypes.data, woop.ctypes.data), c)
         return nodes, woop
+
+    # ---- rebuilding the tree on the GPU (adypt_rebuild_bvh, include/adypt_hip.h; the definition: csrc/device/lbvh.hpp) ----
+    def RebuildBVH(self, cfg: Optional[N.BvhParams] = None) -> dict:
+        """A new tree, built on the GPU from the triangles as UpdateTriangles() left them: WideBVH.BuildLinear's bytes.  Leaves the tracer as Reset()
+        does (0 spp).  Several devices: on every device.  Returns n_nodes, n_refs, levels (size stack_size by it) and binary_depth."""
+        info = N.RebuildInfo()
+        self._call("rebuild_bvh", None if cfg is None else C.byref(cfg), C.byref(info))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def GetBVHSizes(self) -> Tuple[int, int]:
+        """(n_nodes, n_refs) of the tree the (first) device holds now."""
+        n_nodes, n_refs = C.c_int64(), C.c_int64()
+        c = self._contexts()[0]
+        N.check(N.lib.adypt_get_bvh_sizes(c, C.byref(n_nodes), C.byref(n_refs)), c)
+        return n_nodes.value, n_refs.value
+
+    def ReadTriIndices(self) -> np.ndarray:
+        """The reference order (int32 [n_refs]) as it is on the (first) device."""
+        idx = np.zeros(max(self.GetBVHSizes()[1], 1), dtype=np.int32)
+        c = self._contexts()[0]
+        N.check(N.lib.adypt_read_tri_indices(c, idx.ctypes.data), c)
+        return idx[:self.GetBVHSizes()[1]]
+
+    def GetRebuildTiming(self) -> dict:
+        """HIP-event milliseconds of the last RebuildBVH() on the (first) device."""
+        ms = (C.c_float * 7)()
+        c = self._contexts()[0]
+        n = N.lib.adypt_get_rebuild_timing(c, ms, 7)
+        if n < 0:
+            N.check(n, c)
+        return dict(zip(("keys", "sort", "tree", "bottom_up", "emission", "woop_nodes", "total"), (ms[i] for i in range(7))))
 
     def GetRefitTiming(self) -> dict:
         """HIP-event milliseconds of the last UpdateTriangles() on the (first) device."""

@@ -4,9 +4,11 @@
 //
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
-//             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj]
+//             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild]
 //   --pose moved.obj: the scene of the config (and its cached .bvh) with the vertices and normals of moved.obj — the same triangles in the same order,
 //              moved — through adypt_multi_update_triangles: the BVH and the Woop data are refitted on the GPU, nothing is rebuilt
+//   --rebuild: a new tree for the triangles as they are then (after --pose, when given), built on the GPU through adypt_multi_rebuild_bvh with the config's
+//              SAH costs
 //   --sun-visibility: enable the occlusion query the reference has commented out (pathtracer.glsl:132)
 //   --preview: what the reference shows in its window (shaders/screen.glsl), as PNG
 //   --devices: pixel tiles sharded over several GPUs of the node (adypt_create_multi), radiance gathered on the first one
@@ -38,10 +40,11 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
 	std::string noise_out, spp_out, denoise_out, guides_out, pose;
+	bool rebuild = false;
 	int denoise_levels = 5;
 	int adaptive = 0;
 	int spp = 64, fp16 = 0, primary = -1, sun_visibility = 0, save_every = 0;
@@ -85,6 +88,7 @@ int main(int argc, char **argv)
 		else if(a == "--denoise-levels" && i + 1 < argc) denoise_levels = atoi(argv[++i]);
 		else if(a == "--guides-out" && i + 1 < argc) guides_out = argv[++i];
 		else if(a == "--pose" && i + 1 < argc) pose = argv[++i];
+		else if(a == "--rebuild") rebuild = true;
 		else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
 	}
 	const bool until = noise_target >= 0.0;
@@ -168,6 +172,15 @@ int main(int argc, char **argv)
 		float ms[4] = {0, 0, 0, 0};
 		(void)adypt_get_refit_timing(adypt_multi_context(multi, 0), ms, 4);
 		printf("[PT]INFO: pose %s: %lld triangles moved, refit %.3f ms (scatter %.3f, references and Woop %.3f, nodes %.3f)\n", pose.c_str(), (long long)n_tris, ms[3], ms[0], ms[1], ms[2]);
+	}
+	if(rebuild)
+	{
+		adypt_rebuild_info info;
+		if(adypt_multi_rebuild_bvh(multi, &cfg.bvh, &info) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		float ms[7] = {0, 0, 0, 0, 0, 0, 0};
+		(void)adypt_get_rebuild_timing(adypt_multi_context(multi, 0), ms, 7);
+		printf("[PT]INFO: rebuild: %lld nodes, %lld references, %d levels, %.3f ms (keys %.3f, sort %.3f, tree %.3f, bottom-up %.3f, emission %.3f, Woop and nodes %.3f)\n", (long long)info.n_nodes,
+		       (long long)info.n_refs, (int)info.levels, ms[6], ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
 	}
 
 	std::vector<float> rgb((size_t)cfg.width * cfg.height * 3, 0.0f);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "noise.hpp"
+#include "resources.hpp"
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -33,7 +34,7 @@ struct Attachment {
 	~Attachment() { reset(); }
 	void reset(void *q = nullptr, void (*f)(void *) = nullptr) { if(p && free_fn) free_fn(p); p = q; free_fn = f; }
 };
-enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes
+enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachBuild, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes, build.hip's scratch
 Attachment &ctx_attachment(adypt_ctx *c, AttachKind kind);
 
 // ---- noise statistics and adaptive sampling, per context (adypt_trace_adaptive and adypt_multi_trace_adaptive are one loop over these) ----
@@ -78,6 +79,8 @@ CtxScene ctx_scene(adypt_ctx *c);
 int ctx_expand_references(adypt_ctx *c);
 // everything the context has enqueued on any of its streams has finished (the scene arrays are about to change under it)
 int ctx_drain(adypt_ctx *c);
+// ---- rebuilding the tree (build.hip), per context: see tracer.hip ----
+int ctx_replace_bvh(adypt_ctx *c, Buffer<uint4> *nodes, Buffer<int32_t> *tri_indices, Buffer<float4> *woop, int64_t n_nodes, int64_t n_refs);
 // multi.hip: the message adypt_multi_last_error answers
 void multi_set_error(adypt_multi *m, const std::string &msg);
 

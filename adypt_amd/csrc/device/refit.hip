@@ -11,6 +11,7 @@
 #include "ctx_access.hpp"
 #include "resources.hpp"
 #include "refit_plan.hpp"
+#include "refit_internal.hpp"
 #include "woop.hpp"
 #include "../../../include/adypt_hip.h"
 
@@ -185,6 +186,38 @@ unsigned grid_of(int64_t n, int per_group) { return (unsigned)((n + per_group - 
 
 }  // namespace
 
+namespace adypt {
+
+hipError_t refit_launch_woop(hipStream_t stream, const float4 *triangles, int tri_float4, const int32_t *tri_indices, int64_t n_refs, float4 *woop)
+{
+	if(n_refs <= 0) return hipSuccess;
+	hipLaunchKernelGGL(k_refit_woop, dim3(grid_of(n_refs, kRefitThreads)), dim3(kRefitThreads), 0, stream, triangles, tri_float4, tri_indices, n_refs, woop);
+	return hipGetLastError();
+}
+
+hipError_t refit_launch_nodes(hipStream_t stream, uint4 *nodes, float4 *boxes, const int32_t *level, int64_t n_level, const int32_t *tri_indices, const float4 *triangles, int tri_float4)
+{
+	if(n_level <= 0) return hipSuccess;
+	hipLaunchKernelGGL(k_refit_nodes, dim3(grid_of(n_level, kNodesPerGroup)), dim3(kRefitThreads), 0, stream, nodes, boxes, level, (int)n_level, tri_indices, triangles, tri_float4);
+	return hipGetLastError();
+}
+
+int refit_adopt_tree(adypt_ctx *c, const std::vector<int64_t> &level_begin, Buffer<int32_t> &&order, Buffer<float4> &&boxes)
+{
+	Refitter *rf = refitter_of(c);
+	rf->have_plan = false; // (the old tree's: should anything below fail, the next update plans from the nodes as they are)
+	for(Event &e : rf->ev) if(!(hipEvent_t)e) RF_TRY(c, hipEventCreate(e.out()));
+	rf->plan = RefitPlan(); // (depth and order stay empty: only the levels' extents are read after the plan is on the device)
+	rf->plan.level_begin = level_begin;
+	rf->d_order = std::move(order);
+	rf->d_boxes = std::move(boxes);
+	rf->have_plan = true;
+	rf->timed = false;
+	return ADYPT_OK;
+}
+
+}  // namespace adypt
+
 extern "C" {
 
 int adypt_update_triangles(adypt_ctx *c, int64_t first, int64_t count, const float *positions, const float *normals)
@@ -212,18 +245,12 @@ int adypt_update_triangles(adypt_ctx *c, int64_t first, int64_t count, const flo
 	}
 	RF_TRY(c, hipEventRecord(rf->ev[1], i.stream));
 	RF_STEP(ctx_expand_references(c));
-	if(sc.n_refs > 0)
-	{
-		hipLaunchKernelGGL(k_refit_woop, dim3(grid_of(sc.n_refs, kRefitThreads)), dim3(kRefitThreads), 0, i.stream, (const float4 *)sc.triangles, sc.tri_float4, sc.tri_indices, sc.n_refs, sc.woop);
-		RF_TRY(c, hipGetLastError());
-	}
+	RF_TRY(c, refit_launch_woop(i.stream, (const float4 *)sc.triangles, sc.tri_float4, sc.tri_indices, sc.n_refs, sc.woop));
 	RF_TRY(c, hipEventRecord(rf->ev[2], i.stream));
 	for(int l = rf->plan.levels() - 1; l >= 0; --l)
 	{
 		const int64_t begin = rf->plan.level_begin[(size_t)l], n = rf->plan.level_begin[(size_t)l + 1] - begin;
-		hipLaunchKernelGGL(k_refit_nodes, dim3(grid_of(n, kNodesPerGroup)), dim3(kRefitThreads), 0, i.stream, sc.nodes, rf->d_boxes.get(), (const int32_t *)rf->d_order + begin, (int)n, sc.tri_indices,
-		                   (const float4 *)sc.triangles, sc.tri_float4);
-		RF_TRY(c, hipGetLastError());
+		RF_TRY(c, refit_launch_nodes(i.stream, sc.nodes, rf->d_boxes.get(), (const int32_t *)rf->d_order + begin, n, sc.tri_indices, (const float4 *)sc.triangles, sc.tri_float4));
 	}
 	RF_TRY(c, hipEventRecord(rf->ev[3], i.stream));
 	RF_TRY(c, hipStreamSynchronize(i.stream));

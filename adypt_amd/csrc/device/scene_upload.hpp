@@ -97,14 +97,22 @@ int upload_textures_and_materials(adypt_ctx *c, const adypt_scene_desc *d)
 	return upload(c, &c->d_materials, mats.data(), mats.size());
 }
 
+// whether a context with n_refs references keeps the per-reference copy of the records, and its size
+bool wants_reference_triangles(const adypt_ctx *c, int64_t n_refs, size_t *bytes)
+{
+	*bytes = std::max<size_t>((size_t)n_refs * kTriFloat4, 1) * sizeof(float4);
+	const long max_mb = c->tun.ref_triangles_max_mb >= 0 ? c->tun.ref_triangles_max_mb : kRefTrianglesAutoMaxMB;
+	return max_mb != 0 && (*bytes >> 20) <= (size_t)max_mb; // (0 = never, whatever the size: the tests' way into the remap path with scenes of a few triangles)
+}
+
 int make_reference_triangles(adypt_ctx *c)
 {
 	// k_path looks a hit's triangle up by reference index in a second copy of the records (path.hpp): made here, once, so that nothing is
 	// allocated while frames are traced.  Above the size threshold, or when the memory cannot be had, k_path applies the 4-byte
 	// uTriIndices remap (traversal.glsl:253-254) in its shading round instead — same image.
-	const size_t n16 = (size_t)c->n_refs * kTriFloat4, bytes = std::max<size_t>(n16, 1) * sizeof(float4);
-	const long max_mb = c->tun.ref_triangles_max_mb >= 0 ? c->tun.ref_triangles_max_mb : kRefTrianglesAutoMaxMB;
-	if(max_mb != 0 && (bytes >> 20) <= (size_t)max_mb) // (0 = never, whatever the size: the tests' way into the remap path with scenes of a few triangles)
+	const size_t n16 = (size_t)c->n_refs * kTriFloat4;
+	size_t bytes;
+	if(wants_reference_triangles(c, c->n_refs, &bytes))
 	{
 		if(c->d_ref_triangles.alloc(bytes) != hipSuccess) (void)hipGetLastError(); // (left empty)
 		else if(n16)

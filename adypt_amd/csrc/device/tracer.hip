@@ -745,6 +745,37 @@ int ctx_drain(adypt_ctx *c)
 	harvest_events(c);
 	return ADYPT_OK; // (a stack overflow of those frames stays for adypt_wait to report)
 }
+// ---- what the rebuild (build.hip) needs of a context ----
+// The tree is replaced by one built in the caller's buffers (the context is drained, the buffers' contents are complete on the context's stream): the
+// node, index and Woop arrays are taken, the old ones go back with the caller's owners; what adypt_create derived from the tree's size is derived again
+// (the per-reference copy of the records, the launch geometry of the traversal); the context is left as adypt_reset leaves it.  What can be refused
+// comes first: after a failure the old tree is in place and usable.
+int ctx_replace_bvh(adypt_ctx *c, Buffer<uint4> *nodes, Buffer<int32_t> *tri_indices, Buffer<float4> *woop, int64_t n_nodes, int64_t n_refs)
+{
+	HIP_TRY(c, hipSetDevice(c->device));
+	Buffer<float4> ref;
+	size_t ref_bytes;
+	if(wants_reference_triangles(c, n_refs, &ref_bytes) && ref.alloc(ref_bytes) != hipSuccess) (void)hipGetLastError(); // (left empty: k_path remaps, as after adypt_create)
+	HIP_TRY(c, hipStreamSynchronize(c->stream));
+	const int64_t old_nodes = c->n_nodes, old_refs = c->n_refs;
+	auto swap_all = [&] { std::swap(c->d_nodes, *nodes); std::swap(c->d_tri_indices, *tri_indices); std::swap(c->d_woop, *woop); std::swap(c->d_ref_triangles, ref); };
+	swap_all();
+	c->n_nodes = n_nodes; c->n_refs = n_refs;
+	const int r = configure_trace(c, c->params.stack_size);
+	if(r != ADYPT_OK)
+	{
+		const std::string why = c->error;
+		swap_all();
+		c->n_nodes = old_nodes; c->n_refs = old_refs;
+		(void)configure_trace(c, c->params.stack_size);
+		c->error = why;
+		return r;
+	}
+	const int e = ctx_expand_references(c);
+	if(e != ADYPT_OK) return e;
+	HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the old per-reference copy goes with `ref`)
+	return adypt_reset(c);
+}
 }  // namespace adypt
 
 namespace {

@@ -6,6 +6,7 @@
 #include "../../../include/adypt_hip.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <fstream>
 #include <zlib.h>
@@ -239,6 +240,43 @@ int adypt_bvh_build(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh *
 	build_wide_bvh(bin, leaves, *p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads());
 	if(info) { info->sbvh_nodes = (int64_t)bin.size(); info->refs = leaves; info->wide_nodes = (int64_t)b->nodes.size(); info->sbvh_ms = sbvh_ms; info->wide_ms = wide_ms; }
 	*out = b;
+	return ADYPT_OK;
+}
+
+int adypt_bvh_build_linear(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, adypt_build_info *info)
+{
+	if(!s || !p || !out) { set_host_error("adypt_bvh_build_linear: null argument"); return ADYPT_E_INVALID; }
+	const void *tp; int64_t nt = adypt_scene_triangles(s, &tp);
+	if(nt <= 0) { set_host_error("adypt_bvh_build_linear: scene has no triangles"); return ADYPT_E_INVALID; }
+	if(nt > ((int64_t)1 << 30)) { set_host_error("adypt_bvh_build_linear: more than 2^30 triangles"); return ADYPT_E_INVALID; }
+	if(!(p->triangle_sah > 0.0f && p->triangle_sah < FLT_MAX && p->node_sah > 0.0f && p->node_sah < FLT_MAX)) { set_host_error("adypt_bvh_build_linear: the SAH costs must be positive finite numbers"); return ADYPT_E_INVALID; }
+	std::vector<BinNode> bin;
+	double tree_ms = 0, wide_ms = 0;
+	int depth = 0;
+	const int64_t leaves = build_lbvh((const TriRec *)tp, nt, &bin, &depth, &tree_ms);
+	adypt_bvh *b = new adypt_bvh();
+	build_wide_bvh(bin, leaves, *p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads());
+	// the boxes are the refit's, not the collapse's: one rule, the device builder's too
+	for(NodeRec &n : b->nodes)
+	{
+		n.px = n.py = n.pz = 0.0f; n.ex = n.ey = n.ez = 0;
+		memset(n.qlox, 0, 48);
+	}
+	const auto t0 = std::chrono::steady_clock::now();
+	const int r = adypt_bvh_refit(b->nodes.data(), (int64_t)b->nodes.size(), b->tri_indices.data(), (int64_t)b->tri_indices.size(), tp, nt);
+	if(r != ADYPT_OK) { delete b; return r; }
+	wide_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	if(info) { info->sbvh_nodes = (int64_t)bin.size(); info->refs = leaves; info->wide_nodes = (int64_t)b->nodes.size(); info->sbvh_ms = tree_ms; info->wide_ms = wide_ms; }
+	*out = b;
+	return ADYPT_OK;
+}
+
+int adypt_lbvh_keys(const void *tris, int64_t n_tris, uint64_t *out)
+{
+	if(!tris || n_tris <= 0 || n_tris > ((int64_t)1 << 30) || !out) { set_host_error("adypt_lbvh_keys: null or empty argument"); return ADYPT_E_INVALID; }
+	std::vector<uint64_t> keys;
+	lbvh_sorted_keys((const TriRec *)tris, n_tris, &keys);
+	memcpy(out, keys.data(), keys.size() * sizeof(uint64_t));
 	return ADYPT_OK;
 }
 

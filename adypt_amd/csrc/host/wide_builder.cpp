@@ -20,6 +20,7 @@
 //     array; the run lengths are known from the DP (wide nodes below a binary node: `wide_below_`, references: the
 //     leaf count), so every subtree can be emitted by its own task at its final position.
 #include "builders.hpp"
+#include "../device/wide_cut.hpp" // the DP's arithmetic, the children of a cut and the slot assignment: the text the device builder compiles too
 
 #include <algorithm>
 #include <atomic>
@@ -34,10 +35,6 @@
 
 namespace adypt {
 namespace {
-
-enum CutType : uint8_t { kInternal = 0, kLeaf = 1, kDistribute = 2 };
-struct Cut { float sah; uint8_t type; uint8_t split[2]; uint8_t pad; }; // 8 B: 56 B of DP state per binary node
-struct CutRow { Cut c[7]; Cut &operator[](int i) { return c[i - 1]; } const Cut &operator[](int i) const { return c[i - 1]; } };
 
 class Collapser {
 public:
@@ -196,74 +193,39 @@ private:
 		}
 	}
 
-	// wide nodes emitted for the forest the DP cuts out of binary node n with a budget of i roots
-	uint32_t forest_wide(int n, int i) const
-	{
-		const Cut &c = cost_[(size_t)n][i];
-		if(c.type != kDistribute) return wide_below_[(size_t)n];
-		return forest_wide(left(n), c.split[0]) + forest_wide(right(n), c.split[1]);
-	}
+	// the tree as wide_cut.hpp walks it
+	struct View {
+		const Collapser *c;
+		int left(int n) const { return c->left(n); }
+		int right(int n) const { return Collapser::right(n); }
+		const CutRow &row(int n) const { return c->cost_[(size_t)n]; }
+		uint32_t wide_below(int n) const { return c->wide_below_[(size_t)n]; }
+	};
 
 	bool is_leaf(int i) const { return bin_[(size_t)i].left == -1; }
 	int left(int i) const { return bin_[(size_t)i].left; }
 	static int right(int i) { return i + 1; }
-	float tri_cost(int n) const { return cfg_.triangle_sah * n; }
-	float node_cost(int n) const { return cfg_.node_sah * n; }
-
 	void eval_cost(int n)
 	{
-		float area = bin_[(size_t)n].box.area();
+		const float lo[3] = {bin_[(size_t)n].box.lo.x, bin_[(size_t)n].box.lo.y, bin_[(size_t)n].box.lo.z}, hi[3] = {bin_[(size_t)n].box.hi.x, bin_[(size_t)n].box.hi.y, bin_[(size_t)n].box.hi.z};
+		const float area = cut_area(lo, hi);
 		CutRow &dp = cost_[(size_t)n];
 		if(is_leaf(n))
 		{
-			for(int i = 1; i <= 7; ++i) { dp[i].sah = tri_cost(1) * area; dp[i].type = kLeaf; dp[i].split[0] = dp[i].split[1] = 0; }
+			cut_leaf_row(area, cfg_.triangle_sah, dp);
 			tri_count_[(size_t)n] = 1;
 			wide_below_[(size_t)n] = 0;
 			return;
 		}
 		const int l = left(n), r = right(n);
-		const CutRow &L = cost_[(size_t)l], &R = cost_[(size_t)r];
 		const int tc = tri_count_[(size_t)r] + tri_count_[(size_t)l];
 		tri_count_[(size_t)n] = tc;
-		{
-			float c_leaf = tc <= 3 ? area * tri_cost(tc) : FLT_MAX;
-			float c_int = FLT_MAX;
-			float node_sah = area * node_cost(8);
-			dp[1].split[0] = dp[1].split[1] = 0;
-			for(int k = 1; k < 8; ++k)
-			{
-				float v = node_sah + L[k].sah + R[8 - k].sah;
-				if(v < c_int) { c_int = v; dp[1].split[0] = (uint8_t)k; dp[1].split[1] = (uint8_t)(8 - k); }
-			}
-			if(c_leaf < c_int) { dp[1].sah = c_leaf; dp[1].type = kLeaf; }
-			else { dp[1].sah = c_int; dp[1].type = kInternal; }
-		}
-		for(int i = 2; i <= 7; ++i)
-		{
-			float c_dist = FLT_MAX;
-			dp[i].split[0] = dp[i].split[1] = 0;
-			for(int k = 1; k < i; ++k)
-			{
-				float v = L[k].sah + R[i - k].sah;
-				if(v < c_dist) { c_dist = v; dp[i].split[0] = (uint8_t)k; dp[i].split[1] = (uint8_t)(i - k); }
-			}
-			if(c_dist < dp[i - 1].sah) { dp[i].sah = c_dist; dp[i].type = kDistribute; }
-			else dp[i] = dp[i - 1];
-		}
-		wide_below_[(size_t)n] = dp[1].type == kInternal ? 1u + forest_wide(l, dp[1].split[0]) + forest_wide(r, dp[1].split[1]) : 0u;
+		cut_inner_row(area, tc, cfg_.triangle_sah, cfg_.node_sah, cost_[(size_t)l], cost_[(size_t)r], dp);
+		wide_below_[(size_t)n] = cut_wide_below(View{this}, n);
 	}
 
 	// the binary nodes that become the children of a wide node rooted at (n, i)
-	void gather_children(int n, int i, int *count, int out[8]) const
-	{
-		const int child[2] = {left(n), right(n)};
-		const int share[2] = {cost_[(size_t)n][i].split[0], cost_[(size_t)n][i].split[1]};
-		for(int c = 0; c < 2; ++c)
-		{
-			if(cost_[(size_t)child[c]][share[c]].type == kDistribute) gather_children(child[c], share[c], count, out);
-			else out[(*count)++] = child[c];
-		}
-	}
+	void gather_children(int n, int i, int *count, int out[8]) const { cut_gather_children(View{this}, n, i, count, out); }
 
 	int append_leaf_refs(int n, Cursor *cur)
 	{
@@ -284,49 +246,6 @@ private:
 			else { st[sp++] = left(c); st[sp++] = right(c); }
 		}
 		return cnt;
-	}
-
-	// min-cost assignment of `n` rows (children) to 8 columns (slots), potentials method; slot_of[row] = column
-	static void assign_slots(const float cost[8][8], int n, int slot_of[8])
-	{
-		const float INF = 1e12f;
-		int match[9], way[9];     // match[col] = row matched to col (1-based, 0 = none)
-		float u[9], v[9], minv[9];
-		bool used[9];
-		std::fill(u, u + 9, 0.0f); std::fill(v, v + 9, 0.0f);
-		std::fill(way, way + 9, 0); std::fill(match, match + 9, 0);
-		for(int row = 1; row <= n; ++row)
-		{
-			match[0] = row;
-			int j0 = 0;
-			std::fill(minv, minv + 9, INF);
-			std::fill(used, used + 9, false);
-			do
-			{
-				used[j0] = true;
-				int i0 = match[j0], j1 = 0;
-				float delta = INF;
-				for(int j = 1; j <= 8; ++j)
-					if(!used[j])
-					{
-						float cur = cost[i0 - 1][j - 1] - u[i0] - v[j];
-						if(cur < minv[j]) { minv[j] = cur; way[j] = j0; }
-						if(minv[j] < delta) { delta = minv[j]; j1 = j; }
-					}
-				for(int j = 0; j <= 8; ++j)
-					if(used[j]) { u[match[j]] += delta; v[j] -= delta; }
-					else minv[j] -= delta;
-				j0 = j1;
-			} while(match[j0] != 0);
-			do
-			{
-				int j1 = way[j0];
-				match[j0] = match[j1];
-				j0 = j1;
-			} while(j0);
-		}
-		for(int j = 1; j <= 8; ++j)
-			if(match[j] != 0) slot_of[match[j] - 1] = j - 1;
 	}
 
 	static uint32_t f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
@@ -360,9 +279,10 @@ private:
 				for(int j = 0; j < 8; ++j)
 				{
 					Vec3 d = bin_[(size_t)child[i]].box.center() - pc;
-					m[i][j] = ((j & 1) ? -d.x : d.x) + ((j & 2) ? -d.y : d.y) + ((j & 4) ? -d.z : d.z);
+					const float dd[3] = {d.x, d.y, d.z};
+					m[i][j] = cut_slot_cost(dd, j);
 				}
-			assign_slots(m, n_child, slot_of);
+			cut_assign_slots(m, n_child, slot_of);
 		}
 		int in_slot[8];
 		std::fill(in_slot, in_slot + 8, -1);

@@ -312,6 +312,37 @@ int adypt_read_bvh(adypt_ctx *ctx, void *nodes_out, float *woop_out);
  * data, [2] the nodes (every level), [3] all of it.  Returns the number of entries and writes them only when capacity holds them all. */
 int adypt_get_refit_timing(adypt_ctx *ctx, float *ms, int capacity);
 
+/* ---- rebuilding the tree on the GPU: a new topology for the triangles as they are now ----------------------------------------------------------
+ * A refitted tree keeps the topology of the pose it was built for; adypt_rebuild_bvh builds a new CWBVH8 from the triangle records in device memory
+ * (as adypt_create uploaded them and adypt_update_triangles left them), in the same context and without an upload: Morton keys of the centroids, a
+ * radix sort, Karras's radix tree, the collapse's SAH dynamic program and layout, and boxes by the refit's rule.  The definition is
+ * csrc/device/lbvh.hpp, which the host's adypt_bvh_build_linear (adypt_host.h) compiles too: adypt_read_bvh and adypt_read_tri_indices afterwards equal
+ * that function's arrays and adypt_woop_matrices of them byte for byte (NaNs of degenerate triangles as for adypt_update_triangles).  There are no
+ * spatial splits: n_refs becomes the triangle count, so the array sizes change (adypt_get_bvh_sizes).  params: NULL for the defaults (triangleSAH 0.3,
+ * nodeSAH 1); max_spatial_depth is ignored; SAH costs that are not positive finite numbers are refused.  The context is drained first and left as
+ * adypt_reset leaves it; a later adypt_update_triangles refits the new topology.
+ * The new tree needs another traversal stack depth than the old one: the reported `levels` (the depth of the wide tree) is what a caller sizes stackSize
+ * by — a stack that is too small is reported as ADYPT_E_STACK_OVERFLOW by the next frames, as ever.
+ * ADYPT_E_INVALID (bad costs; a scene whose SAH costs overflow or are NaN) and ADYPT_E_OOM leave the old tree in place and usable.
+ * Memory: about 240 B per triangle of scratch (keys twice 8, the sort's temporary storage, binary tree 16, boxes 64, DP rows 112, counts 12), kept
+ * in the context for the next rebuild, next to the new arrays (80 B per node, 52 B per reference, 36 B per node for later refits); the old arrays are
+ * freed when the new ones are in place. */
+typedef struct adypt_bvh_params adypt_bvh_params; /* adypt_host.h */
+typedef struct adypt_rebuild_info {
+	int64_t n_nodes, n_refs;   /* of the new tree */
+	int32_t levels;            /* of the wide tree: the root's level counts */
+	int32_t binary_depth;      /* edges on the longest path of the binary radix tree */
+} adypt_rebuild_info;
+int adypt_rebuild_bvh(adypt_ctx *ctx, const adypt_bvh_params *params, adypt_rebuild_info *out);
+/* HIP-event times of the last adypt_rebuild_bvh in ms: [0] centroid box and keys, [1] sort, [2] radix tree, [3] bottom-up pass, [4] emission (with its
+ * one small read per level), [5] Woop data and node records, [6] all of it.  Returns the number of entries and writes them only when capacity holds
+ * them all. */
+int adypt_get_rebuild_timing(adypt_ctx *ctx, float *ms, int capacity);
+/* the sizes of the tree the context holds now; either pointer may be NULL */
+int adypt_get_bvh_sizes(adypt_ctx *ctx, int64_t *n_nodes, int64_t *n_refs);
+/* the reference order (n_refs triangle indices) as it is on the device */
+int adypt_read_tri_indices(adypt_ctx *ctx, int32_t *out);
+
 /* Trace an arbitrary batch of rays through the same traversal kernel: rays = n x 8 floats
  * (ox, oy, oz, tmin, dx, dy, dz, unused).  with_stats selects the instrumented kernel variant. */
 int adypt_trace_rays(adypt_ctx *ctx, const float *rays, int64_t n, adypt_hit *hits, int with_stats);
@@ -415,6 +446,8 @@ int adypt_multi_read_denoise_guides(adypt_multi *m, float *albedo, float *normal
 /* adypt_update_triangles on every device: the scene is replicated and every device refits its own copy; no collective.  (One process per GPU: every
  * rank calls adypt_update_triangles on its own context.) */
 int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals);
+/* adypt_rebuild_bvh on every device: every device rebuilds its own copy, and all get the same bytes; no collective.  *out: the last device's. */
+int adypt_multi_rebuild_bvh(adypt_multi *m, const adypt_bvh_params *params, adypt_rebuild_info *out);
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

@@ -80,6 +80,14 @@ int adypt_host_get_threads(void);
 int adypt_host_selftest_sort(int64_t n, uint32_t seed, int pattern, int threads, int64_t min_task);
 /* SBVHBuilder{cfg,&sbvh,scene}.Run(); WideBVHBuilder{cfg,&wbvh,sbvh}.Run(); (src/Instance.cpp:24-26) */
 int adypt_bvh_build(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, adypt_build_info *info);
+/* A CWBVH8 from a linear BVH: Morton keys of the centroids, a sort, Karras's radix tree, the collapse above, and boxes by the rule of adypt_bvh_refit.
+ * The definition is csrc/device/lbvh.hpp, which the device builder (adypt_hip.h, adypt_rebuild_bvh) compiles too: both give the same bytes.  No
+ * spatial splits (max_spatial_depth is ignored), so there is one reference per triangle; triangle_sah and node_sah steer the collapse and must be
+ * positive finite numbers.  info: sbvh_nodes = the binary nodes (2 n - 1), sbvh_ms = keys, sort and tree, wide_ms = collapse and boxes.  Faster to
+ * build and slower to trace than adypt_bvh_build's tree (Rebuilding on the GPU). */
+int adypt_bvh_build_linear(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, adypt_build_info *info);
+/* the sorted keys adypt_bvh_build_linear makes of n_tris 100-byte triangle records: Morton code << 32 | triangle index, ascending (for tests and tools) */
+int adypt_lbvh_keys(const void *tris, int64_t n_tris, uint64_t *out);
 int adypt_bvh_load(const char *path, const adypt_bvh_params *expected, adypt_bvh **out);  /* WideBVH::LoadFromFile */
 int adypt_bvh_save(const adypt_bvh *b, const char *path, const adypt_bvh_params *p);       /* WideBVH::SaveToFile */
 void adypt_bvh_free(adypt_bvh *b);

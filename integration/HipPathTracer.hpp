@@ -200,6 +200,16 @@ public:
 		return false;
 	}
 
+	// A new BVH for the triangles as UpdateTriangles left them, built on every device from its own copy (adypt_hip.h, adypt_rebuild_bvh): no upload, no new
+	// context.  The SAH costs are the BVH section's of the config (nullptr: its defaults).  *info: sizes, the levels of the wide tree — what stackSize has
+	// to cover — and the depth of the binary tree.  The sample counter restarts as after a Trace(false).
+	bool RebuildBVH(const adypt_bvh_params *params = nullptr, adypt_rebuild_info *info = nullptr)
+	{
+		if(adypt_multi_rebuild_bvh(m_gpus, params, info) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
 	// what DrawScreen puts on screen, for a caller-owned W x H RGBA8 texture / window (every device fills in its own tiles)
 	bool ReadScreen(std::vector<uint8_t> *rgba8) const
 	{

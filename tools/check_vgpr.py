@@ -31,7 +31,7 @@ def kernels(src):
 
 def main():
     bad = []
-    for src in ("device/tracer.hip", "device/multi.hip", "device/denoise.hip", "device/refit.hip"):
+    for src in ("device/tracer.hip", "device/multi.hip", "device/denoise.hip", "device/refit.hip", "device/build.hip"):
         for name, n, uses in sorted(kernels(src)):
             flag = ""
             if uses:
