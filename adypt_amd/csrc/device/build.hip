@@ -13,8 +13,7 @@
 //                       node and its references go was decided by the counts.  The host reads the next level's size (4 bytes) between launches
 //     (refit.hip)       k_refit_woop, then k_refit_nodes level by level, deepest first, over the queues of k_emit
 // Everything is built into new arrays; the context takes them last (ctx_replace_bvh), so a refused or failed call leaves the old tree usable.
-#include "ctx_access.hpp"
-#include "resources.hpp"
+#include "ctx_unit.hpp"
 #include "refit_internal.hpp"
 #include "lbvh.hpp"
 #include "../../../include/adypt_hip.h"
@@ -48,8 +47,8 @@ template <bool FROM_TRIANGLES> __global__ __launch_bounds__(kBuildThreads) void 
 		if(FROM_TRIANGLES)
 		{
 			const float4 *rec = in + (size_t)i * (size_t)tri_float4;
-			const float4 a = rec[0], b = rec[1], c = rec[2];
-			const float p[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x};
+			float p[9];
+			load_positions(rec, p);
 			for(int k = 0; k < 3; ++k) { const float v = lbvh_centroid(p, k); box.lo[k] = refit_min(box.lo[k], v); box.hi[k] = refit_max(box.hi[k], v); }
 		}
 		else
@@ -81,8 +80,8 @@ __global__ __launch_bounds__(kBuildThreads) void k_keys(const float4 *triangles,
 	const float4 lo = centroid_box[0], hi = centroid_box[1];
 	const RefitBox box{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}};
 	const float4 *rec = triangles + (size_t)i * (size_t)tri_float4;
-	const float4 a = rec[0], b = rec[1], c = rec[2];
-	const float p[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x};
+	float p[9];
+	load_positions(rec, p);
 	keys[i] = lbvh_key(p, box, (uint32_t)i);
 }
 
@@ -128,8 +127,8 @@ __global__ __launch_bounds__(kBuildThreads) void k_bottom_up(BinTree t, const fl
 	const int leaf = (int)(t.n - 1 + j);
 	{
 		const float4 *rec = triangles + (size_t)t.tri(leaf) * (size_t)tri_float4;
-		const float4 a = rec[0], b = rec[1], c = rec[2];
-		const float p[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x};
+		float p[9];
+		load_positions(rec, p);
 		const RefitBox box = refit_triangle_box(p);
 		t.boxes[(size_t)leaf * 2] = make_float4(box.lo[0], box.lo[1], box.lo[2], __int_as_float(1));
 		t.boxes[(size_t)leaf * 2 + 1] = make_float4(box.hi[0], box.hi[1], box.hi[2], __int_as_float(0));
@@ -189,134 +188,104 @@ struct Builder {
 	Buffer<float4> boxes, partial;
 	Buffer<CutRow> rows;
 	Buffer<uint32_t> wide_below, arrived, words; // words: [0] the flags, [1] the next level's count
-	Event ev[kTimingEvents];
-	bool timed = false;
+	StageTimer<kTimingEvents> timer;
 	adypt_rebuild_info last{};
 };
-
-void free_builder(void *p) { delete (Builder *)p; }
-
-int cfail(adypt_ctx *c, int code, const std::string &msg) { ctx_set_error(c, msg); return code; }
-
-#define BD_TRY(c, expr)                                                                                     \
-	do {                                                                                                    \
-		const hipError_t e_ = (expr);                                                                       \
-		if(e_ != hipSuccess) { (void)hipGetLastError(); return cfail(c, e_ == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } \
-	} while(0)
-#define BD_STEP(expr) do { const int r_ = (expr); if(r_ != ADYPT_OK) return r_; } while(0)
-
-Builder *builder_if_any(adypt_ctx *c) { return (Builder *)ctx_attachment(c, kAttachBuild).p; }
-Builder *builder_of(adypt_ctx *c)
-{
-	if(!builder_if_any(c)) ctx_attachment(c, kAttachBuild).reset(new Builder(), free_builder);
-	return builder_if_any(c);
-}
-
-template <class T> hipError_t at_least(Buffer<T> &b, size_t count)
-{
-	const size_t bytes = std::max<size_t>(count * sizeof(T), 64);
-	return b.bytes() >= bytes ? hipSuccess : b.alloc(bytes);
-}
-
-unsigned grid_of(int64_t n, int per_group) { return (unsigned)((n + per_group - 1) / per_group); }
 
 int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, adypt_rebuild_info *out)
 {
 	const CtxScene sc = ctx_scene(c);
 	const int64_t n = sc.n_tris;
-	if(n > ((int64_t)1 << 30)) return cfail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: more than 2^30 triangles");
-	BD_STEP(ctx_drain(c));
+	if(n > ((int64_t)1 << 30)) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: more than 2^30 triangles");
+	CTX_STEP(ctx_drain(c));
 	const hipStream_t stream = ctx_info(c).stream;
-	Builder *b = builder_of(c);
+	Builder *b = ctx_state<Builder>(c, kAttachBuild);
 	const float4 *tris = (const float4 *)sc.triangles;
 	const size_t n_bin = (size_t)(2 * n - 1), n_inner = (size_t)(n - 1);
 	size_t sort_bytes = 0;
-	BD_TRY(c, rocprim::radix_sort_keys(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)n, 0u, (unsigned)kKeyBits, stream));
-	BD_TRY(c, at_least(b->keys, (size_t)n)); BD_TRY(c, at_least(b->sorted, (size_t)n)); BD_TRY(c, at_least(b->sort_tmp, sort_bytes));
-	BD_TRY(c, at_least(b->left, n_inner)); BD_TRY(c, at_least(b->right, n_inner)); BD_TRY(c, at_least(b->parent, n_bin));
-	BD_TRY(c, at_least(b->boxes, n_bin * 2)); BD_TRY(c, at_least(b->partial, (size_t)(kMaxPartials + 1) * 2));
-	BD_TRY(c, at_least(b->rows, n_bin)); BD_TRY(c, at_least(b->wide_below, n_bin)); BD_TRY(c, at_least(b->arrived, n_inner)); BD_TRY(c, at_least(b->words, 2));
-	for(Event &e : b->ev) if(!(hipEvent_t)e) BD_TRY(c, hipEventCreate(e.out()));
-	b->timed = false;
-	BD_TRY(c, hipEventRecord(b->ev[0], stream));
+	CTX_TRY(c, rocprim::radix_sort_keys(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)n, 0u, (unsigned)kKeyBits, stream));
+	CTX_TRY(c, at_least(b->keys, (size_t)n)); CTX_TRY(c, at_least(b->sorted, (size_t)n)); CTX_TRY(c, at_least(b->sort_tmp, sort_bytes));
+	CTX_TRY(c, at_least(b->left, n_inner)); CTX_TRY(c, at_least(b->right, n_inner)); CTX_TRY(c, at_least(b->parent, n_bin));
+	CTX_TRY(c, at_least(b->boxes, n_bin * 2)); CTX_TRY(c, at_least(b->partial, (size_t)(kMaxPartials + 1) * 2));
+	CTX_TRY(c, at_least(b->rows, n_bin)); CTX_TRY(c, at_least(b->wide_below, n_bin)); CTX_TRY(c, at_least(b->arrived, n_inner)); CTX_TRY(c, at_least(b->words, 2));
+	b->timer.invalidate();
+	CTX_TRY(c, b->timer.mark(0, stream));
 	// ---- keys
 	const unsigned n_partial = std::min<unsigned>(grid_of(n, kBuildThreads), kMaxPartials);
 	float4 *centroid_box = b->partial.get() + (size_t)kMaxPartials * 2;
 	hipLaunchKernelGGL(k_centroid_box<true>, dim3(n_partial), dim3(kBuildThreads), 0, stream, tris, sc.tri_float4, n, b->partial.get());
-	BD_TRY(c, hipGetLastError());
+	CTX_TRY(c, hipGetLastError());
 	hipLaunchKernelGGL(k_centroid_box<false>, dim3(1), dim3(kBuildThreads), 0, stream, (const float4 *)b->partial.get(), 0, (int64_t)n_partial, centroid_box);
-	BD_TRY(c, hipGetLastError());
+	CTX_TRY(c, hipGetLastError());
 	hipLaunchKernelGGL(k_keys, dim3(grid_of(n, kBuildThreads)), dim3(kBuildThreads), 0, stream, tris, sc.tri_float4, n, (const float4 *)centroid_box, b->keys.get());
-	BD_TRY(c, hipGetLastError());
-	BD_TRY(c, hipEventRecord(b->ev[1], stream));
+	CTX_TRY(c, hipGetLastError());
+	CTX_TRY(c, b->timer.mark(1, stream));
 	// ---- sort
-	BD_TRY(c, rocprim::radix_sort_keys((void *)b->sort_tmp.get(), sort_bytes, b->keys.get(), b->sorted.get(), (size_t)n, 0u, (unsigned)kKeyBits, stream));
-	BD_TRY(c, hipEventRecord(b->ev[2], stream));
+	CTX_TRY(c, rocprim::radix_sort_keys((void *)b->sort_tmp.get(), sort_bytes, b->keys.get(), b->sorted.get(), (size_t)n, 0u, (unsigned)kKeyBits, stream));
+	CTX_TRY(c, b->timer.mark(2, stream));
 	// ---- the radix tree
 	BinTree t{n, b->sorted.get(), b->left.get(), b->right.get(), b->parent.get(), b->boxes.get(), b->rows.get(), b->wide_below.get()};
-	BD_TRY(c, hipMemsetAsync(b->parent.get(), 0xff, sizeof(int32_t), stream)); // the root's
+	CTX_TRY(c, hipMemsetAsync(b->parent.get(), 0xff, sizeof(int32_t), stream)); // the root's
 	if(n_inner)
 	{
 		hipLaunchKernelGGL(k_radix_tree, dim3(grid_of(n - 1, kBuildThreads)), dim3(kBuildThreads), 0, stream, t);
-		BD_TRY(c, hipGetLastError());
+		CTX_TRY(c, hipGetLastError());
 	}
-	BD_TRY(c, hipEventRecord(b->ev[3], stream));
+	CTX_TRY(c, b->timer.mark(3, stream));
 	// ---- boxes, counts and the cut, bottom up
-	BD_TRY(c, hipMemsetAsync(b->arrived.get(), 0, std::max<size_t>(n_inner, 1) * sizeof(uint32_t), stream));
-	BD_TRY(c, hipMemsetAsync(b->words.get(), 0, 2 * sizeof(uint32_t), stream));
+	CTX_TRY(c, hipMemsetAsync(b->arrived.get(), 0, std::max<size_t>(n_inner, 1) * sizeof(uint32_t), stream));
+	CTX_TRY(c, hipMemsetAsync(b->words.get(), 0, 2 * sizeof(uint32_t), stream));
 	hipLaunchKernelGGL(k_bottom_up, dim3(grid_of(n, kBuildThreads)), dim3(kBuildThreads), 0, stream, t, tris, sc.tri_float4, cfg.triangle_sah, cfg.node_sah, b->arrived.get(), b->words.get());
-	BD_TRY(c, hipGetLastError());
-	BD_TRY(c, hipEventRecord(b->ev[4], stream));
+	CTX_TRY(c, hipGetLastError());
+	CTX_TRY(c, b->timer.mark(4, stream));
 	uint32_t root_wide = 0, flags = 0;
 	float4 root_hi;
-	BD_TRY(c, hipMemcpyAsync(&root_wide, b->wide_below.get(), sizeof(root_wide), hipMemcpyDeviceToHost, stream));
-	BD_TRY(c, hipMemcpyAsync(&root_hi, b->boxes.get() + 1, sizeof(root_hi), hipMemcpyDeviceToHost, stream));
-	BD_TRY(c, hipMemcpyAsync(&flags, b->words.get(), sizeof(flags), hipMemcpyDeviceToHost, stream));
-	BD_TRY(c, hipStreamSynchronize(stream));
-	if(flags & kFlagCost) return cfail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: the SAH costs of this scene are not finite numbers below FLT_MAX (vertices that are NaN, infinite or huge)");
+	CTX_TRY(c, hipMemcpyAsync(&root_wide, b->wide_below.get(), sizeof(root_wide), hipMemcpyDeviceToHost, stream));
+	CTX_TRY(c, hipMemcpyAsync(&root_hi, b->boxes.get() + 1, sizeof(root_hi), hipMemcpyDeviceToHost, stream));
+	CTX_TRY(c, hipMemcpyAsync(&flags, b->words.get(), sizeof(flags), hipMemcpyDeviceToHost, stream));
+	CTX_TRY(c, hipStreamSynchronize(stream));
+	if(flags & kFlagCost) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: the SAH costs of this scene are not finite numbers below FLT_MAX (vertices that are NaN, infinite or huge)");
 	// ---- the wide tree, top down, into new arrays
 	const int64_t n_nodes = std::max<uint32_t>(root_wide, 1u), n_refs = n;
 	Buffer<uint4> nodes;
-	Buffer<int32_t> tri_indices, order;
-	Buffer<float4> woop, node_boxes;
+	Buffer<int32_t> tri_indices;
+	Buffer<float4> woop;
+	TreeLevels tree; // order: the queues of k_emit
 	Buffer<WideItem> items;
-	BD_TRY(c, at_least(nodes, (size_t)n_nodes * (kNodeBytes / 16))); BD_TRY(c, at_least(tri_indices, (size_t)n_refs)); BD_TRY(c, at_least(woop, (size_t)n_refs * 3));
-	BD_TRY(c, at_least(order, (size_t)n_nodes)); BD_TRY(c, at_least(node_boxes, (size_t)n_nodes * 2)); BD_TRY(c, at_least(items, (size_t)n_nodes));
-	BD_TRY(c, hipMemsetAsync(nodes.get(), 0, (size_t)n_nodes * kNodeBytes, stream));
-	BD_TRY(c, hipMemsetAsync(tri_indices.get(), 0, (size_t)n_refs * sizeof(int32_t), stream));
+	CTX_TRY(c, at_least(nodes, (size_t)n_nodes * (kNodeBytes / 16))); CTX_TRY(c, at_least(tri_indices, (size_t)n_refs)); CTX_TRY(c, at_least(woop, (size_t)n_refs * 3));
+	CTX_TRY(c, at_least(tree.order, (size_t)n_nodes)); CTX_TRY(c, at_least(tree.boxes, (size_t)n_nodes * 2)); CTX_TRY(c, at_least(items, (size_t)n_nodes));
+	CTX_TRY(c, hipMemsetAsync(nodes.get(), 0, (size_t)n_nodes * kNodeBytes, stream));
+	CTX_TRY(c, hipMemsetAsync(tri_indices.get(), 0, (size_t)n_refs * sizeof(int32_t), stream));
 	const WideItem root{0, 0, 1u, 0u};
-	BD_TRY(c, hipMemcpyAsync(items.get(), &root, sizeof(root), hipMemcpyHostToDevice, stream));
-	std::vector<int64_t> level_begin(1, 0);
+	CTX_TRY(c, hipMemcpyAsync(items.get(), &root, sizeof(root), hipMemcpyHostToDevice, stream));
+	tree.level_begin.assign(1, 0);
 	for(int64_t begin = 0, count = 1; count > 0;)
 	{
 		uint32_t *appended = b->words.get() + 1;
-		BD_TRY(c, hipMemsetAsync(appended, 0, sizeof(uint32_t), stream));
-		hipLaunchKernelGGL(k_emit, dim3(grid_of(count, kEmitThreads)), dim3(kEmitThreads), 0, stream, t, items.get(), order.get(), begin, count, appended, n_nodes, n_refs, nodes.get(), tri_indices.get(),
+		CTX_TRY(c, hipMemsetAsync(appended, 0, sizeof(uint32_t), stream));
+		hipLaunchKernelGGL(k_emit, dim3(grid_of(count, kEmitThreads)), dim3(kEmitThreads), 0, stream, t, items.get(), tree.order.get(), begin, count, appended, n_nodes, n_refs, nodes.get(), tri_indices.get(),
 		                   b->words.get());
-		BD_TRY(c, hipGetLastError());
+		CTX_TRY(c, hipGetLastError());
 		uint32_t words[2] = {0, 0};
-		BD_TRY(c, hipMemcpyAsync(words, b->words.get(), sizeof(words), hipMemcpyDeviceToHost, stream));
-		BD_TRY(c, hipStreamSynchronize(stream));
+		CTX_TRY(c, hipMemcpyAsync(words, b->words.get(), sizeof(words), hipMemcpyDeviceToHost, stream));
+		CTX_TRY(c, hipStreamSynchronize(stream));
 		begin += count;
-		level_begin.push_back(begin);
+		tree.level_begin.push_back(begin);
 		count = (int64_t)words[1];
-		if((words[0] & kFlagLayout) || begin + count > n_nodes) return cfail(c, ADYPT_E_HIP, "adypt_rebuild_bvh: the emitted nodes do not add up to the counted ones");
+		if((words[0] & kFlagLayout) || begin + count > n_nodes) return ctx_fail(c, ADYPT_E_HIP, "adypt_rebuild_bvh: the emitted nodes do not add up to the counted ones");
 	}
-	if(level_begin.back() != n_nodes) return cfail(c, ADYPT_E_HIP, "adypt_rebuild_bvh: the emitted nodes do not add up to the counted ones");
-	BD_TRY(c, hipEventRecord(b->ev[5], stream));
+	if(tree.level_begin.back() != n_nodes) return ctx_fail(c, ADYPT_E_HIP, "adypt_rebuild_bvh: the emitted nodes do not add up to the counted ones");
+	CTX_TRY(c, b->timer.mark(5, stream));
 	// ---- Woop data and the node records: the refit's kernels, deepest level first
-	BD_TRY(c, refit_launch_woop(stream, tris, sc.tri_float4, tri_indices.get(), n_refs, woop.get()));
-	const int levels = (int)level_begin.size() - 1;
-	for(int l = levels - 1; l >= 0; --l)
-		BD_TRY(c, refit_launch_nodes(stream, nodes.get(), node_boxes.get(), (const int32_t *)order.get() + level_begin[(size_t)l], level_begin[(size_t)l + 1] - level_begin[(size_t)l], tri_indices.get(), tris,
-		                             sc.tri_float4));
-	BD_TRY(c, hipEventRecord(b->ev[6], stream));
-	BD_TRY(c, hipStreamSynchronize(stream));
+	CTX_TRY(c, refit_launch_woop(stream, tris, sc.tri_float4, tri_indices.get(), n_refs, woop.get()));
+	CTX_TRY(c, refit_launch_levels(stream, tree, nodes.get(), tri_indices.get(), tris, sc.tri_float4));
+	CTX_TRY(c, b->timer.mark(6, stream));
+	CTX_TRY(c, hipStreamSynchronize(stream));
 	// ---- the context takes the new tree
-	BD_STEP(ctx_replace_bvh(c, &nodes, &tri_indices, &woop, n_nodes, n_refs));
-	BD_STEP(refit_adopt_tree(c, level_begin, std::move(order), std::move(node_boxes)));
-	b->timed = true;
-	b->last = adypt_rebuild_info{n_nodes, n_refs, levels, __builtin_bit_cast(int32_t, root_hi.w)};
+	CTX_STEP(ctx_replace_bvh(c, &nodes, &tri_indices, &woop, n_nodes, n_refs));
+	b->last = adypt_rebuild_info{n_nodes, n_refs, tree.levels(), __builtin_bit_cast(int32_t, root_hi.w)};
+	refit_adopt_tree(c, std::move(tree));
+	b->timer.complete();
 	if(out) *out = b->last;
 	return ADYPT_OK;
 }
@@ -331,27 +300,17 @@ int adypt_rebuild_bvh(adypt_ctx *c, const adypt_bvh_params *params, adypt_rebuil
 	adypt_bvh_params cfg{0, 0.3f, 1.0f}; // InstanceConfig::BVH's defaults
 	if(params) cfg = *params;
 	if(!(cfg.triangle_sah > 0.0f && cfg.triangle_sah < kCutMax && cfg.node_sah > 0.0f && cfg.node_sah < kCutMax))
-		return cfail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: the SAH costs must be positive finite numbers");
-	BD_TRY(c, hipSetDevice(ctx_info(c).device));
+		return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: the SAH costs must be positive finite numbers");
+	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
 	return rebuild(c, cfg, out);
 }
 
 int adypt_get_rebuild_timing(adypt_ctx *c, float *ms, int capacity)
 {
 	if(!c || !ms || capacity < 0) return ADYPT_E_INVALID;
-	Builder *b = builder_if_any(c);
-	if(!b || !b->timed) return cfail(c, ADYPT_E_STATE, "adypt_get_rebuild_timing: nothing has been rebuilt yet (adypt_rebuild_bvh)");
-	const int n = kTimingEvents;
-	if(capacity < n) return n;
-	for(int k = 0; k < n - 1; ++k)
-	{
-		ms[k] = 0.0f;
-		(void)hipEventElapsedTime(&ms[k], b->ev[k], b->ev[k + 1]);
-	}
-	ms[n - 1] = 0.0f;
-	(void)hipEventElapsedTime(&ms[n - 1], b->ev[0], b->ev[n - 1]);
-	(void)hipGetLastError();
-	return n;
+	const Builder *b = ctx_state_if_any<Builder>(c, kAttachBuild);
+	if(!b || !b->timer.completed()) return ctx_fail(c, ADYPT_E_STATE, "adypt_get_rebuild_timing: nothing has been rebuilt yet (adypt_rebuild_bvh)");
+	return b->timer.read(ms, capacity, kTimingEvents - 1, true);
 }
 
 int adypt_get_bvh_sizes(adypt_ctx *c, int64_t *n_nodes, int64_t *n_refs)
@@ -368,24 +327,17 @@ int adypt_read_tri_indices(adypt_ctx *c, int32_t *out)
 	if(!c || !out) return ADYPT_E_INVALID;
 	const CtxScene sc = ctx_scene(c);
 	const CtxInfo i = ctx_info(c);
-	BD_TRY(c, hipSetDevice(i.device));
-	BD_TRY(c, hipStreamSynchronize(i.stream));
-	if(sc.n_refs > 0) BD_TRY(c, hipMemcpy(out, sc.tri_indices, (size_t)sc.n_refs * sizeof(int32_t), hipMemcpyDeviceToHost));
+	CTX_TRY(c, hipSetDevice(i.device));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
+	if(sc.n_refs > 0) CTX_TRY(c, hipMemcpy(out, sc.tri_indices, (size_t)sc.n_refs * sizeof(int32_t), hipMemcpyDeviceToHost));
 	return ADYPT_OK;
 }
 
 // the scene is replicated: the same rebuild on every device
 int adypt_multi_rebuild_bvh(adypt_multi *m, const adypt_bvh_params *params, adypt_rebuild_info *out)
 {
-	const int n_dev = adypt_multi_device_count(m);
-	if(n_dev < 1) return ADYPT_E_INVALID;
-	for(int k = 0; k < n_dev; ++k)
-	{
-		adypt_ctx *c = adypt_multi_context(m, k);
-		const int r = adypt_rebuild_bvh(c, params, out);
-		if(r != ADYPT_OK) { multi_set_error(m, adypt_last_error(c)); return r; } // (bad parameters are refused by the first context: none has changed)
-	}
-	return ADYPT_OK;
+	// (bad parameters are refused by the first context: none has changed)
+	return multi_each(m, [=](adypt_ctx *c) { return adypt_rebuild_bvh(c, params, out); });
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // struct adypt_ctx and what it is made of: everything one context owns on the device, its launch geometry and its frame state.
-// Included by tracer.hip only (the one translation unit that sees the layout; multi.hip goes through ctx_access.hpp), before the
+// Included by tracer.hip only (the one translation unit that sees the layout; the others go through ctx_access.hpp), before the
 // sections that work on it: scene_upload.hpp, frame_schedule.hpp.
 #pragma once
 #include "traverse.hpp"
@@ -191,8 +191,9 @@ struct adypt_ctx {
 	int view_type = 0;          // uuViewer.uType of the image in d_accum: the viewer type of the last primary frame, 3 after path tracing
 
 	// What other translation units park here (ctx_access.hpp): multi.hip the RCCL communicator state of the native multi-GPU path, denoise.hip the
-	// denoiser's images (allocated at the first adypt_denoise / adypt_read_denoise_guides), refit.hip the refit plan, level lists and exact boxes (made at the
-	// first adypt_update_triangles).  adypt_destroy releases them in this order.
+	// denoiser's images (allocated at the first adypt_denoise / adypt_read_denoise_guides), refit.hip the level lists and exact boxes of the tree (made at
+	// the first adypt_update_triangles, or handed over by a rebuild), build.hip the scratch of a rebuild (allocated at the first adypt_rebuild_bvh, kept for
+	// the next pose).  adypt_destroy releases them in this order.
 	Attachment attached[kAttachKinds];
 
 	double trace_ms = 0, shade_ms = 0, path_ms = 0;

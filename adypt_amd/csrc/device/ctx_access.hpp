@@ -1,10 +1,12 @@
-// Internal seam between tracer.hip (owner of struct adypt_ctx) and multi.hip (RCCL gather of the tile shards): the few
-// fields the collective needs, without exposing the context's layout.  Not part of the C-ABI.
+// Internal seam between tracer.hip (owner of struct adypt_ctx) and the other translation units of the library — multi.hip (RCCL gather of the tile
+// shards), denoise.hip, refit.hip, build.hip: the few fields and functions each of them needs, without exposing the context's layout.  What those
+// units are written with on top of it: ctx_unit.hpp.  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "noise.hpp"
 #include "resources.hpp"
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -83,5 +85,8 @@ int ctx_drain(adypt_ctx *c);
 int ctx_replace_bvh(adypt_ctx *c, Buffer<uint4> *nodes, Buffer<int32_t> *tri_indices, Buffer<float4> *woop, int64_t n_nodes, int64_t n_refs);
 // multi.hip: the message adypt_multi_last_error answers
 void multi_set_error(adypt_multi *m, const std::string &msg);
+// multi.hip: the same call on every context, in device order.  The first result that is not ADYPT_OK ends it and is returned, that context's error
+// becoming the handle's; ADYPT_E_INVALID for a null or empty handle.
+int multi_each(adypt_multi *m, const std::function<int(adypt_ctx *)> &f);
 
 }  // namespace adypt

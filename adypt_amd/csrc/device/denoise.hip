@@ -8,8 +8,7 @@
 // Several devices: every context captures the guides of its own blocks, the host puts the devices' local images back to back in rank order, their
 // block lists likewise (every block has one owner, and k_denoise_prepare takes any block list and writes at the picture's coordinates), uploads them
 // to the first device and runs the same two kernels there — no collective; the result is the one-device result bit for bit because the inputs are.
-#include "ctx_access.hpp"
-#include "resources.hpp"
+#include "ctx_unit.hpp"
 #include "tile_layout.hpp"
 #include "denoise.hpp"
 #include "../../../include/adypt_hip.h"
@@ -88,57 +87,33 @@ struct Denoiser {
 	// the filter's row-major images of the whole picture: 80 B + 12 B (the result) per image pixel
 	Buffer<float4> x0[2], x1, x2, xa;
 	Buffer<float> rgb;
-	bool have_result = false;
 	// several devices: the block-major images of every device's blocks, back to back in rank order, on the first device (88 B per pixel of the blocks
 	// + 8 B per block)
 	Buffer<float4> m_accum, m_albedo, m_normal, m_position, m_hits;
 	Buffer<float2> m_moments;
 	Buffer<int32_t> m_blocks, m_block_spp;
-	Event ev[kTimingEvents];
+	StageTimer<kTimingEvents> timer; // completed: the last filter ran to its end, rgb is its result
 	int levels_timed = 0;
 };
 
-void free_denoiser(void *p) { delete (Denoiser *)p; }
-
-int cfail(adypt_ctx *c, int code, const std::string &msg) { ctx_set_error(c, msg); return code; }
-
-#define DN_TRY(c, expr)                                                                                     \
-	do {                                                                                                    \
-		const hipError_t e_ = (expr);                                                                       \
-		if(e_ != hipSuccess) { (void)hipGetLastError(); return cfail(c, e_ == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } \
-	} while(0)
-#define DN_STEP(expr) do { const int r_ = (expr); if(r_ != ADYPT_OK) return r_; } while(0)
-
-Denoiser *denoiser_if_any(adypt_ctx *c) { return (Denoiser *)ctx_attachment(c, kAttachDenoise).p; }
-Denoiser *denoiser_of(adypt_ctx *c)
-{
-	if(!denoiser_if_any(c)) ctx_attachment(c, kAttachDenoise).reset(new Denoiser(), free_denoiser);
-	return denoiser_if_any(c);
-}
-
-template <class T> int ensure(adypt_ctx *c, Buffer<T> &b, size_t n)
-{
-	const size_t bytes = std::max<size_t>(n * sizeof(T), 64);
-	if(b.bytes() >= bytes) return ADYPT_OK;
-	DN_TRY(c, b.alloc(bytes));
-	return ADYPT_OK;
-}
+Denoiser *denoiser_of(adypt_ctx *c) { return ctx_state<Denoiser>(c, kAttachDenoise); }
+Denoiser *finished_denoiser(adypt_ctx *c) { Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise); return d && d->timer.completed() ? d : nullptr; }
 
 // the guide scratch of the context's own blocks (allocated at the first call: the size never changes)
 int ensure_guides(adypt_ctx *c, Denoiser *d, const CtxInfo &i)
 {
 	const size_t n = (size_t)std::max(i.n_local_px, 64);
-	DN_STEP(ensure(c, d->g_albedo, n)); DN_STEP(ensure(c, d->g_normal, n)); DN_STEP(ensure(c, d->g_position, n)); DN_STEP(ensure(c, d->g_hits, n));
-	return ensure(c, d->d_block_spp, (size_t)std::max(i.n_local_px / kBlockPixels, 1));
+	CTX_TRY(c, at_least(d->g_albedo, n)); CTX_TRY(c, at_least(d->g_normal, n)); CTX_TRY(c, at_least(d->g_position, n)); CTX_TRY(c, at_least(d->g_hits, n));
+	CTX_TRY(c, at_least(d->d_block_spp, (size_t)std::max(i.n_local_px / kBlockPixels, 1)));
+	return ADYPT_OK;
 }
 
 int ensure_filter_images(adypt_ctx *c, Denoiser *d, const CtxInfo &i)
 {
 	const size_t n = (size_t)i.width * (size_t)i.height;
 	d->width = i.width; d->height = i.height;
-	DN_STEP(ensure(c, d->x0[0], n)); DN_STEP(ensure(c, d->x0[1], n)); DN_STEP(ensure(c, d->x1, n)); DN_STEP(ensure(c, d->x2, n)); DN_STEP(ensure(c, d->xa, n));
-	DN_STEP(ensure(c, d->rgb, n * 3));
-	for(Event &e : d->ev) if(!(hipEvent_t)e) DN_TRY(c, hipEventCreate(e.out()));
+	CTX_TRY(c, at_least(d->x0[0], n)); CTX_TRY(c, at_least(d->x0[1], n)); CTX_TRY(c, at_least(d->x1, n)); CTX_TRY(c, at_least(d->x2, n)); CTX_TRY(c, at_least(d->xa, n));
+	CTX_TRY(c, at_least(d->rgb, n * 3));
 	return ADYPT_OK;
 }
 
@@ -147,11 +122,11 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 {
 	const int width = d->width, height = d->height, n_px = in.n_blocks * kBlockPixels;
 	const int blocks_x = (width + kBlockDim - 1) / kBlockDim;
-	hipLaunchKernelGGL(k_denoise_prepare, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, stream, in.accum, in.moments, in.blocks, in.block_spp, n_px, blocks_x, width, height, in.albedo,
+	hipLaunchKernelGGL(k_denoise_prepare, dim3(grid_of(n_px, 256)), dim3(256), 0, stream, in.accum, in.moments, in.blocks, in.block_spp, n_px, blocks_x, width, height, in.albedo,
 	                   in.normal, in.position, in.hits, d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get());
-	DN_TRY(c, hipGetLastError());
-	DN_TRY(c, hipEventRecord(d->ev[2], stream));
-	const dim3 grid((unsigned)((width + kAtrousX - 1) / kAtrousX), (unsigned)((height + kAtrousY - 1) / kAtrousY)), block(kAtrousX, kAtrousY);
+	CTX_TRY(c, hipGetLastError());
+	CTX_TRY(c, d->timer.mark(2, stream));
+	const dim3 grid(grid_of(width, kAtrousX), grid_of(height, kAtrousY)), block(kAtrousX, kAtrousY);
 	for(int l = 0; l < prm.levels; ++l)
 	{
 		const float4 *src = d->x0[l & 1];
@@ -160,12 +135,12 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 			hipLaunchKernelGGL(k_atrous<true>, grid, block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
 		else
 			hipLaunchKernelGGL(k_atrous<false>, grid, block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
-		DN_TRY(c, hipGetLastError());
-		DN_TRY(c, hipEventRecord(d->ev[3 + l], stream));
+		CTX_TRY(c, hipGetLastError());
+		CTX_TRY(c, d->timer.mark(3 + l, stream));
 	}
 	d->levels_timed = prm.levels;
-	DN_TRY(c, hipStreamSynchronize(stream));
-	d->have_result = true;
+	CTX_TRY(c, hipStreamSynchronize(stream));
+	d->timer.complete();
 	return ADYPT_OK;
 }
 
@@ -180,26 +155,26 @@ int params_of(const adypt_denoise_params *p, DenoiseParams *out, std::string *wh
 // the context's guides into its own scratch, enqueued behind its frames
 int capture_guides(adypt_ctx *c, Denoiser *d, const CtxInfo &i, const char *fn)
 {
-	DN_STEP(ensure_guides(c, d, i));
+	CTX_STEP(ensure_guides(c, d, i));
 	return ctx_capture_guides(c, fn, d->g_albedo, d->g_normal, d->g_position, d->g_hits);
 }
 
 int read_result(adypt_ctx *c, const char *fn, float *rgb)
 {
-	Denoiser *d = denoiser_if_any(c);
-	if(!d || !d->have_result) return cfail(c, ADYPT_E_STATE, std::string(fn) + ": nothing has been denoised yet (adypt_denoise)");
+	Denoiser *d = finished_denoiser(c);
+	if(!d) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": nothing has been denoised yet (adypt_denoise)");
 	const CtxInfo i = ctx_info(c);
-	DN_TRY(c, hipSetDevice(i.device));
-	DN_TRY(c, hipMemcpyAsync(rgb, d->rgb, (size_t)d->width * d->height * 3 * sizeof(float), hipMemcpyDeviceToHost, i.stream));
-	DN_TRY(c, hipStreamSynchronize(i.stream));
+	CTX_TRY(c, hipSetDevice(i.device));
+	CTX_TRY(c, hipMemcpyAsync(rgb, d->rgb, (size_t)d->width * d->height * 3 * sizeof(float), hipMemcpyDeviceToHost, i.stream));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
 	return ADYPT_OK;
 }
 
 // one block-major local image of a context (n_local_px > 0 elements) on the host (the stream is drained when it returns)
 template <class T> int fetch(adypt_ctx *c, const CtxInfo &i, const T *device, T *host)
 {
-	DN_TRY(c, hipMemcpyAsync(host, device, (size_t)i.n_local_px * sizeof(T), hipMemcpyDeviceToHost, i.stream));
-	DN_TRY(c, hipStreamSynchronize(i.stream));
+	CTX_TRY(c, hipMemcpyAsync(host, device, (size_t)i.n_local_px * sizeof(T), hipMemcpyDeviceToHost, i.stream));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
 	return ADYPT_OK;
 }
 
@@ -212,19 +187,19 @@ int adypt_denoise(adypt_ctx *c, const adypt_denoise_params *p)
 	if(!c) return ADYPT_E_INVALID;
 	DenoiseParams prm;
 	std::string why;
-	if(params_of(p, &prm, &why, "adypt_denoise") != ADYPT_OK) return cfail(c, ADYPT_E_INVALID, why);
+	if(params_of(p, &prm, &why, "adypt_denoise") != ADYPT_OK) return ctx_fail(c, ADYPT_E_INVALID, why);
 	const CtxInfo i = ctx_info(c);
-	if(i.nranks != 1) return cfail(c, ADYPT_E_STATE, "adypt_denoise: the context is a tile shard (tile_nranks > 1): the filter needs the whole image (adypt_multi_denoise)");
-	DN_STEP(ctx_denoise_ready(c, "adypt_denoise"));
-	DN_TRY(c, hipSetDevice(i.device));
+	if(i.nranks != 1) return ctx_fail(c, ADYPT_E_STATE, "adypt_denoise: the context is a tile shard (tile_nranks > 1): the filter needs the whole image (adypt_multi_denoise)");
+	CTX_STEP(ctx_denoise_ready(c, "adypt_denoise"));
+	CTX_TRY(c, hipSetDevice(i.device));
 	Denoiser *d = denoiser_of(c);
-	DN_STEP(ensure_filter_images(c, d, i));
-	d->have_result = false;
-	DN_TRY(c, hipEventRecord(d->ev[0], i.stream));
-	DN_STEP(capture_guides(c, d, i, "adypt_denoise"));
-	DN_TRY(c, hipEventRecord(d->ev[1], i.stream));
+	CTX_STEP(ensure_filter_images(c, d, i));
+	d->timer.invalidate();
+	CTX_TRY(c, d->timer.mark(0, i.stream));
+	CTX_STEP(capture_guides(c, d, i, "adypt_denoise"));
+	CTX_TRY(c, d->timer.mark(1, i.stream));
 	const DenoiseInputs in = ctx_denoise_inputs(c);
-	DN_TRY(c, hipMemcpyAsync(d->d_block_spp, in.block_spp.data(), in.block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
+	CTX_TRY(c, hipMemcpyAsync(d->d_block_spp, in.block_spp.data(), in.block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
 	const LocalImages local{in.accum, in.moments, in.blocks, d->d_block_spp, d->g_albedo, d->g_normal, d->g_position, d->g_hits, in.n_blocks};
 	return run_filter(c, d, i.stream, local, prm);
 }
@@ -240,9 +215,9 @@ int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float 
 	if(!c) return ADYPT_E_INVALID;
 	const CtxInfo i = ctx_info(c);
 	if(i.n_local_px == 0) return ADYPT_OK; // a shard that owns no block
-	DN_TRY(c, hipSetDevice(i.device));
+	CTX_TRY(c, hipSetDevice(i.device));
 	Denoiser *d = denoiser_of(c);
-	DN_STEP(capture_guides(c, d, i, "adypt_read_denoise_guides"));
+	CTX_STEP(capture_guides(c, d, i, "adypt_read_denoise_guides"));
 	const std::vector<int32_t> blocks = owned_blocks(i.width, i.height, i.rank, i.nranks);
 	std::vector<float4> local((size_t)i.n_local_px);
 	float *const image[3] = {albedo, normal, position};
@@ -250,7 +225,7 @@ int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float 
 	for(int k = 0; k < 3; ++k)
 	{
 		if(!image[k]) continue;
-		DN_STEP(fetch(c, i, device[k], local.data()));
+		CTX_STEP(fetch(c, i, device[k], local.data()));
 		for_each_local_pixel(blocks, i.width, i.height, [&](size_t L, int x, int y) {
 			float *o = image[k] + ((size_t)y * i.width + x) * 3;
 			o[0] = local[L].x; o[1] = local[L].y; o[2] = local[L].z;
@@ -258,31 +233,23 @@ int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float 
 	}
 	if(hit)
 	{
-		DN_STEP(fetch(c, i, (const float4 *)d->g_hits, local.data()));
+		CTX_STEP(fetch(c, i, (const float4 *)d->g_hits, local.data()));
 		for_each_local_pixel(blocks, i.width, i.height, [&](size_t L, int x, int y) {
 			int32_t tri;
 			memcpy(&tri, &local[L].x, 4);
 			hit[(size_t)y * i.width + x] = tri != -1 ? 1 : 0;
 		});
 	}
-	DN_TRY(c, hipStreamSynchronize(i.stream));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
 	return ADYPT_OK;
 }
 
 int adypt_get_denoise_timing(adypt_ctx *c, float *ms, int capacity)
 {
 	if(!c || !ms || capacity < 0) return ADYPT_E_INVALID;
-	Denoiser *d = denoiser_if_any(c);
-	if(!d || !d->have_result) return cfail(c, ADYPT_E_STATE, "adypt_get_denoise_timing: nothing has been denoised yet (adypt_denoise)");
-	const int n = 2 + d->levels_timed;
-	if(capacity < n) return n;
-	for(int k = 0; k < n; ++k)
-	{
-		ms[k] = 0.0f;
-		(void)hipEventElapsedTime(&ms[k], d->ev[k], d->ev[k + 1]); // (several devices: no capture was timed on this context; the entry stays 0)
-	}
-	(void)hipGetLastError();
-	return n;
+	Denoiser *d = finished_denoiser(c);
+	if(!d) return ctx_fail(c, ADYPT_E_STATE, "adypt_get_denoise_timing: nothing has been denoised yet (adypt_denoise)");
+	return d->timer.read(ms, capacity, 2 + d->levels_timed, false);
 }
 
 // ---- one process, N devices ----
@@ -292,28 +259,21 @@ int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p)
 	const int n_dev = adypt_multi_device_count(m);
 	if(n_dev < 1) return ADYPT_E_INVALID;
 	adypt_ctx *root = adypt_multi_context(m, 0);
-	if(n_dev == 1)
-	{
-		const int r = adypt_denoise(root, p);
-		if(r != ADYPT_OK) multi_set_error(m, adypt_last_error(root));
-		return r;
-	}
+	if(n_dev == 1) return multi_each(m, [p](adypt_ctx *c) { return adypt_denoise(c, p); });
 	auto fail_ctx = [m](adypt_ctx *c, int r) { multi_set_error(m, adypt_last_error(c)); return r; };
 	DenoiseParams prm;
 	std::string why;
 	if(params_of(p, &prm, &why, "adypt_multi_denoise") != ADYPT_OK) { multi_set_error(m, why); return ADYPT_E_INVALID; }
 	std::vector<adypt_ctx *> ctx;
 	for(int k = 0; k < n_dev; ++k) ctx.push_back(adypt_multi_context(m, k));
-	for(adypt_ctx *c : ctx) { const int r = ctx_denoise_ready(c, "adypt_multi_denoise"); if(r != ADYPT_OK) return fail_ctx(c, r); }
+	CTX_STEP(multi_each(m, [](adypt_ctx *c) { return ctx_denoise_ready(c, "adypt_multi_denoise"); }));
 	// every device captures the guides of its own blocks: all enqueued before the first is waited for
-	for(adypt_ctx *c : ctx)
-	{
+	CTX_STEP(multi_each(m, [](adypt_ctx *c) {
 		const CtxInfo i = ctx_info(c);
-		if(i.n_local_px == 0) continue;
-		int r = hipSetDevice(i.device) == hipSuccess ? ADYPT_OK : cfail(c, ADYPT_E_HIP, "adypt_multi_denoise: hipSetDevice failed");
-		if(r == ADYPT_OK) r = capture_guides(c, denoiser_of(c), i, "adypt_multi_denoise");
-		if(r != ADYPT_OK) return fail_ctx(c, r);
-	}
+		if(i.n_local_px == 0) return (int)ADYPT_OK;
+		if(hipSetDevice(i.device) != hipSuccess) return ctx_fail(c, ADYPT_E_HIP, "adypt_multi_denoise: hipSetDevice failed");
+		return capture_guides(c, denoiser_of(c), i, "adypt_multi_denoise");
+	}));
 	// the local images of every device back to back in rank order, and their block lists and sample counts likewise (the counts from each context's
 	// own state in that order: multi.hip's merge is sorted by block index, which is not this order, and would launch k_noise_blocks for nothing)
 	const CtxInfo ri = ctx_info(root);
@@ -328,7 +288,7 @@ int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p)
 	{
 		const CtxInfo i = ctx_info(c);
 		if(i.n_local_px == 0) continue;
-		if(hipSetDevice(i.device) != hipSuccess) return fail_ctx(c, cfail(c, ADYPT_E_HIP, "adypt_multi_denoise: hipSetDevice failed"));
+		if(hipSetDevice(i.device) != hipSuccess) return fail_ctx(c, ctx_fail(c, ADYPT_E_HIP, "adypt_multi_denoise: hipSetDevice failed"));
 		Denoiser *d = denoiser_of(c);
 		const DenoiseInputs in = ctx_denoise_inputs(c);
 		const float4 *const device[5] = {in.accum, d->g_albedo, d->g_normal, d->g_position, d->g_hits};
@@ -343,22 +303,22 @@ int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p)
 	// ... uploaded to the first device, where the same prepare / a-trous launches run
 	adypt_ctx *c = root;
 	auto steps = [&]() -> int {
-		DN_TRY(c, hipSetDevice(ri.device));
+		CTX_TRY(c, hipSetDevice(ri.device));
 		Denoiser *d = denoiser_of(c);
-		DN_STEP(ensure_filter_images(c, d, ri));
-		d->have_result = false;
-		DN_STEP(ensure(c, d->m_accum, n_px)); DN_STEP(ensure(c, d->m_albedo, n_px)); DN_STEP(ensure(c, d->m_normal, n_px)); DN_STEP(ensure(c, d->m_position, n_px));
-		DN_STEP(ensure(c, d->m_hits, n_px)); DN_STEP(ensure(c, d->m_moments, n_px)); DN_STEP(ensure(c, d->m_blocks, (size_t)n_blocks)); DN_STEP(ensure(c, d->m_block_spp, (size_t)n_blocks));
-		DN_TRY(c, hipEventRecord(d->ev[0], ri.stream));
-		DN_TRY(c, hipMemcpyAsync(d->m_accum, accum.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
-		DN_TRY(c, hipMemcpyAsync(d->m_albedo, albedo.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
-		DN_TRY(c, hipMemcpyAsync(d->m_normal, normal.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
-		DN_TRY(c, hipMemcpyAsync(d->m_position, position.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
-		DN_TRY(c, hipMemcpyAsync(d->m_hits, hits.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
-		DN_TRY(c, hipMemcpyAsync(d->m_moments, moments.data(), n_px * sizeof(float2), hipMemcpyHostToDevice, ri.stream));
-		DN_TRY(c, hipMemcpyAsync(d->m_blocks, blocks.data(), blocks.size() * sizeof(int32_t), hipMemcpyHostToDevice, ri.stream));
-		DN_TRY(c, hipMemcpyAsync(d->m_block_spp, block_spp.data(), block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, ri.stream));
-		DN_TRY(c, hipEventRecord(d->ev[1], ri.stream));
+		CTX_STEP(ensure_filter_images(c, d, ri));
+		d->timer.invalidate();
+		CTX_TRY(c, at_least(d->m_accum, n_px)); CTX_TRY(c, at_least(d->m_albedo, n_px)); CTX_TRY(c, at_least(d->m_normal, n_px)); CTX_TRY(c, at_least(d->m_position, n_px));
+		CTX_TRY(c, at_least(d->m_hits, n_px)); CTX_TRY(c, at_least(d->m_moments, n_px)); CTX_TRY(c, at_least(d->m_blocks, (size_t)n_blocks)); CTX_TRY(c, at_least(d->m_block_spp, (size_t)n_blocks));
+		CTX_TRY(c, d->timer.mark(0, ri.stream));
+		CTX_TRY(c, hipMemcpyAsync(d->m_accum, accum.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
+		CTX_TRY(c, hipMemcpyAsync(d->m_albedo, albedo.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
+		CTX_TRY(c, hipMemcpyAsync(d->m_normal, normal.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
+		CTX_TRY(c, hipMemcpyAsync(d->m_position, position.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
+		CTX_TRY(c, hipMemcpyAsync(d->m_hits, hits.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
+		CTX_TRY(c, hipMemcpyAsync(d->m_moments, moments.data(), n_px * sizeof(float2), hipMemcpyHostToDevice, ri.stream));
+		CTX_TRY(c, hipMemcpyAsync(d->m_blocks, blocks.data(), blocks.size() * sizeof(int32_t), hipMemcpyHostToDevice, ri.stream));
+		CTX_TRY(c, hipMemcpyAsync(d->m_block_spp, block_spp.data(), block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, ri.stream));
+		CTX_TRY(c, d->timer.mark(1, ri.stream));
 		const LocalImages all{d->m_accum, d->m_moments, d->m_blocks, d->m_block_spp, d->m_albedo, d->m_normal, d->m_position, d->m_hits, n_blocks};
 		return run_filter(c, d, ri.stream, all, prm);
 	};
@@ -378,15 +338,7 @@ int adypt_multi_read_denoised(adypt_multi *m, float *rgb)
 // every device writes the pixels of its own tiles
 int adypt_multi_read_denoise_guides(adypt_multi *m, float *albedo, float *normal, float *position, uint8_t *hit)
 {
-	const int n_dev = adypt_multi_device_count(m);
-	if(n_dev < 1) return ADYPT_E_INVALID;
-	for(int k = 0; k < n_dev; ++k)
-	{
-		adypt_ctx *c = adypt_multi_context(m, k);
-		const int r = adypt_read_denoise_guides(c, albedo, normal, position, hit);
-		if(r != ADYPT_OK) { multi_set_error(m, adypt_last_error(c)); return r; }
-	}
-	return ADYPT_OK;
+	return multi_each(m, [=](adypt_ctx *c) { return adypt_read_denoise_guides(c, albedo, normal, position, hit); });
 }
 
 }  // extern "C"

@@ -357,6 +357,17 @@ namespace {
 int mfail(adypt_multi *m, int code, const std::string &msg) { m->error = msg; return code; }
 int mfail_ctx(adypt_multi *m, int code, adypt_ctx *c) { m->error = adypt_last_error(c); return code; }
 
+}  // namespace
+
+int adypt::multi_each(adypt_multi *m, const std::function<int(adypt_ctx *)> &f)
+{
+	if(!m || m->ctx.empty()) return ADYPT_E_INVALID;
+	for(adypt_ctx *c : m->ctx) { const int r = f(c); if(r != ADYPT_OK) return mfail_ctx(m, r, c); }
+	return ADYPT_OK;
+}
+
+namespace {
+
 int multi_comm_init(adypt_multi *m)
 {
 	if(m->comms_ready) return ADYPT_OK;

@@ -8,8 +8,7 @@
 //                      deeper levels, which earlier launches on the same stream wrote: the stream order is the whole dependency — no atomics, no
 //                      flags between workgroups, no fences.
 // The plan (every node's level) is made once per context, at the first update, from one copy of the node array to the host; the topology never changes.
-#include "ctx_access.hpp"
-#include "resources.hpp"
+#include "ctx_unit.hpp"
 #include "refit_plan.hpp"
 #include "refit_internal.hpp"
 #include "woop.hpp"
@@ -49,9 +48,8 @@ __global__ __launch_bounds__(kRefitThreads) void k_refit_woop(const float4 *tria
 	const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if(r >= n_refs) return;
 	const float4 *rec = triangles + (size_t)tri_indices[r] * (size_t)tri_float4;
-	const float4 a = rec[0], b = rec[1], c = rec[2];
-	const float p[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x};
-	float o[12];
+	float p[9], o[12];
+	load_positions(rec, p);
 	woop_matrix(p, o);
 	float4 *out = woop + (size_t)r * 3;
 	out[0] = make_float4(o[0], o[1], o[2], o[3]);
@@ -94,8 +92,8 @@ __global__ __launch_bounds__(kRefitThreads) void k_refit_nodes(uint4 *nodes, flo
 			for(int r = 0; r < count; ++r)
 			{
 				const float4 *rec = triangles + (size_t)tri_indices[(size_t)tri_base + refit_leaf_offset(meta) + (size_t)r] * (size_t)tri_float4;
-				const float4 a = rec[0], b = rec[1], c = rec[2];
-				const float p[9] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x};
+				float p[9];
+				load_positions(rec, p);
 				mine = refit_union(mine, refit_triangle_box(p));
 			}
 		}
@@ -138,51 +136,30 @@ constexpr int kTimingEvents = 4; // start, scatter, references + Woop, nodes
 
 // Everything the refit keeps per context; parked in the context (ctx_attachment), freed by adypt_destroy (the context's device is current then).
 struct Refitter {
-	RefitPlan plan;
-	Buffer<int32_t> d_order;   // RefitPlan::order: 4 B per node
-	Buffer<float4> d_boxes;    // the exact boxes: 32 B per node
+	TreeLevels tree;           // of the context's tree as it is now: planned at the first update, or handed over by a rebuild
+	bool have_plan = false;
 	Buffer<float> d_stage;     // the caller's positions and normals on their way to the records: up to 72 B per updated triangle
-	Event ev[kTimingEvents];
-	bool have_plan = false, timed = false;
+	StageTimer<kTimingEvents> timer;
 };
 
-void free_refitter(void *p) { delete (Refitter *)p; }
-
-int cfail(adypt_ctx *c, int code, const std::string &msg) { ctx_set_error(c, msg); return code; }
-
-#define RF_TRY(c, expr)                                                                                     \
-	do {                                                                                                    \
-		const hipError_t e_ = (expr);                                                                       \
-		if(e_ != hipSuccess) { (void)hipGetLastError(); return cfail(c, e_ == hipErrorOutOfMemory ? ADYPT_E_OOM : ADYPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } \
-	} while(0)
-#define RF_STEP(expr) do { const int r_ = (expr); if(r_ != ADYPT_OK) return r_; } while(0)
-
-Refitter *refitter_if_any(adypt_ctx *c) { return (Refitter *)ctx_attachment(c, kAttachRefit).p; }
-Refitter *refitter_of(adypt_ctx *c)
-{
-	if(!refitter_if_any(c)) ctx_attachment(c, kAttachRefit).reset(new Refitter(), free_refitter);
-	return refitter_if_any(c);
-}
-
-// the plan from one copy of the node array, its level lists and the box array on the device (the context is drained)
+// the levels from one copy of the node array, the lists and the box array on the device (the context is drained)
 int ensure_plan(adypt_ctx *c, Refitter *rf, const CtxScene &sc, hipStream_t stream)
 {
 	if(rf->have_plan) return ADYPT_OK;
 	std::vector<uint8_t> nodes((size_t)sc.n_nodes * kNodeBytes);
-	RF_TRY(c, hipMemcpyAsync(nodes.data(), sc.nodes, nodes.size(), hipMemcpyDeviceToHost, stream));
-	RF_TRY(c, hipStreamSynchronize(stream));
+	CTX_TRY(c, hipMemcpyAsync(nodes.data(), sc.nodes, nodes.size(), hipMemcpyDeviceToHost, stream));
+	CTX_TRY(c, hipStreamSynchronize(stream));
+	RefitPlan plan;
 	std::string why;
-	if(!plan_refit(nodes.data(), sc.n_nodes, sc.n_refs, &rf->plan, &why)) return cfail(c, ADYPT_E_INVALID, "adypt_update_triangles: the node array is not one tree: " + why);
-	RF_TRY(c, rf->d_order.alloc(rf->plan.order.size() * sizeof(int32_t)));
-	RF_TRY(c, rf->d_boxes.alloc((size_t)sc.n_nodes * 2 * sizeof(float4)));
-	RF_TRY(c, hipMemcpyAsync(rf->d_order, rf->plan.order.data(), rf->plan.order.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-	RF_TRY(c, hipStreamSynchronize(stream));
-	for(Event &e : rf->ev) if(!(hipEvent_t)e) RF_TRY(c, hipEventCreate(e.out()));
+	if(!plan_refit(nodes.data(), sc.n_nodes, sc.n_refs, &plan, &why)) return ctx_fail(c, ADYPT_E_INVALID, "adypt_update_triangles: the node array is not one tree: " + why);
+	rf->tree.level_begin = std::move(plan.level_begin);
+	CTX_TRY(c, rf->tree.order.alloc(plan.order.size() * sizeof(int32_t)));
+	CTX_TRY(c, rf->tree.boxes.alloc((size_t)sc.n_nodes * 2 * sizeof(float4)));
+	CTX_TRY(c, hipMemcpyAsync(rf->tree.order, plan.order.data(), plan.order.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+	CTX_TRY(c, hipStreamSynchronize(stream));
 	rf->have_plan = true;
 	return ADYPT_OK;
 }
-
-unsigned grid_of(int64_t n, int per_group) { return (unsigned)((n + per_group - 1) / per_group); }
 
 }  // namespace
 
@@ -195,25 +172,25 @@ hipError_t refit_launch_woop(hipStream_t stream, const float4 *triangles, int tr
 	return hipGetLastError();
 }
 
-hipError_t refit_launch_nodes(hipStream_t stream, uint4 *nodes, float4 *boxes, const int32_t *level, int64_t n_level, const int32_t *tri_indices, const float4 *triangles, int tri_float4)
+hipError_t refit_launch_levels(hipStream_t stream, const TreeLevels &tree, uint4 *nodes, const int32_t *tri_indices, const float4 *triangles, int tri_float4)
 {
-	if(n_level <= 0) return hipSuccess;
-	hipLaunchKernelGGL(k_refit_nodes, dim3(grid_of(n_level, kNodesPerGroup)), dim3(kRefitThreads), 0, stream, nodes, boxes, level, (int)n_level, tri_indices, triangles, tri_float4);
-	return hipGetLastError();
+	for(int l = tree.levels() - 1; l >= 0; --l)
+	{
+		const int64_t begin = tree.level_begin[(size_t)l], n = tree.level_begin[(size_t)l + 1] - begin;
+		if(n <= 0) continue;
+		hipLaunchKernelGGL(k_refit_nodes, dim3(grid_of(n, kNodesPerGroup)), dim3(kRefitThreads), 0, stream, nodes, tree.boxes.get(), (const int32_t *)tree.order + begin, (int)n, tri_indices, triangles, tri_float4);
+		const hipError_t e = hipGetLastError();
+		if(e != hipSuccess) return e;
+	}
+	return hipSuccess;
 }
 
-int refit_adopt_tree(adypt_ctx *c, const std::vector<int64_t> &level_begin, Buffer<int32_t> &&order, Buffer<float4> &&boxes)
+void refit_adopt_tree(adypt_ctx *c, TreeLevels &&tree)
 {
-	Refitter *rf = refitter_of(c);
-	rf->have_plan = false; // (the old tree's: should anything below fail, the next update plans from the nodes as they are)
-	for(Event &e : rf->ev) if(!(hipEvent_t)e) RF_TRY(c, hipEventCreate(e.out()));
-	rf->plan = RefitPlan(); // (depth and order stay empty: only the levels' extents are read after the plan is on the device)
-	rf->plan.level_begin = level_begin;
-	rf->d_order = std::move(order);
-	rf->d_boxes = std::move(boxes);
+	Refitter *rf = ctx_state<Refitter>(c, kAttachRefit);
+	rf->tree = std::move(tree); // (the old tree's lists and boxes go with `tree`)
 	rf->have_plan = true;
-	rf->timed = false;
-	return ADYPT_OK;
+	rf->timer.invalidate();
 }
 
 }  // namespace adypt
@@ -224,37 +201,33 @@ int adypt_update_triangles(adypt_ctx *c, int64_t first, int64_t count, const flo
 {
 	if(!c) return ADYPT_E_INVALID;
 	const CtxScene sc = ctx_scene(c);
-	if(!positions) return cfail(c, ADYPT_E_INVALID, "adypt_update_triangles: positions is null");
+	if(!positions) return ctx_fail(c, ADYPT_E_INVALID, "adypt_update_triangles: positions is null");
 	if(first < 0 || count < 0 || first > sc.n_tris || count > sc.n_tris - first)
-		return cfail(c, ADYPT_E_INVALID, "adypt_update_triangles: triangles [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) + ") are not all of the scene's " + std::to_string(sc.n_tris));
-	RF_STEP(ctx_drain(c));
+		return ctx_fail(c, ADYPT_E_INVALID, "adypt_update_triangles: triangles [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) + ") are not all of the scene's " + std::to_string(sc.n_tris));
+	CTX_STEP(ctx_drain(c));
 	const CtxInfo i = ctx_info(c);
-	Refitter *rf = refitter_of(c);
-	RF_STEP(ensure_plan(c, rf, sc, i.stream));
-	const size_t n_stage = (size_t)count * 9, stage_bytes = std::max<size_t>(n_stage * (normals ? 2 : 1) * sizeof(float), 64);
-	if(rf->d_stage.bytes() < stage_bytes) RF_TRY(c, rf->d_stage.alloc(stage_bytes));
-	rf->timed = false;
-	RF_TRY(c, hipEventRecord(rf->ev[0], i.stream));
+	Refitter *rf = ctx_state<Refitter>(c, kAttachRefit);
+	CTX_STEP(ensure_plan(c, rf, sc, i.stream));
+	const size_t n_stage = (size_t)count * 9;
+	CTX_TRY(c, at_least(rf->d_stage, n_stage * (normals ? 2 : 1)));
+	rf->timer.invalidate();
+	CTX_TRY(c, rf->timer.mark(0, i.stream));
 	if(count > 0)
 	{
 		float *d_pos = rf->d_stage, *d_nrm = normals ? d_pos + n_stage : nullptr;
-		RF_TRY(c, hipMemcpyAsync(d_pos, positions, n_stage * sizeof(float), hipMemcpyHostToDevice, i.stream));
-		if(normals) RF_TRY(c, hipMemcpyAsync(d_nrm, normals, n_stage * sizeof(float), hipMemcpyHostToDevice, i.stream));
+		CTX_TRY(c, hipMemcpyAsync(d_pos, positions, n_stage * sizeof(float), hipMemcpyHostToDevice, i.stream));
+		if(normals) CTX_TRY(c, hipMemcpyAsync(d_nrm, normals, n_stage * sizeof(float), hipMemcpyHostToDevice, i.stream));
 		hipLaunchKernelGGL(k_refit_scatter, dim3(grid_of(count, kRefitThreads)), dim3(kRefitThreads), 0, i.stream, sc.triangles, sc.tri_float4, first, count, (const float *)d_pos, (const float *)d_nrm);
-		RF_TRY(c, hipGetLastError());
+		CTX_TRY(c, hipGetLastError());
 	}
-	RF_TRY(c, hipEventRecord(rf->ev[1], i.stream));
-	RF_STEP(ctx_expand_references(c));
-	RF_TRY(c, refit_launch_woop(i.stream, (const float4 *)sc.triangles, sc.tri_float4, sc.tri_indices, sc.n_refs, sc.woop));
-	RF_TRY(c, hipEventRecord(rf->ev[2], i.stream));
-	for(int l = rf->plan.levels() - 1; l >= 0; --l)
-	{
-		const int64_t begin = rf->plan.level_begin[(size_t)l], n = rf->plan.level_begin[(size_t)l + 1] - begin;
-		RF_TRY(c, refit_launch_nodes(i.stream, sc.nodes, rf->d_boxes.get(), (const int32_t *)rf->d_order + begin, n, sc.tri_indices, (const float4 *)sc.triangles, sc.tri_float4));
-	}
-	RF_TRY(c, hipEventRecord(rf->ev[3], i.stream));
-	RF_TRY(c, hipStreamSynchronize(i.stream));
-	rf->timed = true;
+	CTX_TRY(c, rf->timer.mark(1, i.stream));
+	CTX_STEP(ctx_expand_references(c));
+	CTX_TRY(c, refit_launch_woop(i.stream, (const float4 *)sc.triangles, sc.tri_float4, sc.tri_indices, sc.n_refs, sc.woop));
+	CTX_TRY(c, rf->timer.mark(2, i.stream));
+	CTX_TRY(c, refit_launch_levels(i.stream, rf->tree, sc.nodes, sc.tri_indices, (const float4 *)sc.triangles, sc.tri_float4));
+	CTX_TRY(c, rf->timer.mark(3, i.stream));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
+	rf->timer.complete();
 	return adypt_reset(c); // the image, the frozen blocks, the frames parked ahead and the primary-hit cache were the old pose's
 }
 
@@ -263,43 +236,26 @@ int adypt_read_bvh(adypt_ctx *c, void *nodes_out, float *woop_out)
 	if(!c) return ADYPT_E_INVALID;
 	const CtxScene sc = ctx_scene(c);
 	const CtxInfo i = ctx_info(c);
-	RF_TRY(c, hipSetDevice(i.device));
-	RF_TRY(c, hipStreamSynchronize(i.stream));
-	if(nodes_out) RF_TRY(c, hipMemcpy(nodes_out, sc.nodes, (size_t)sc.n_nodes * kNodeBytes, hipMemcpyDeviceToHost));
-	if(woop_out && sc.n_refs > 0) RF_TRY(c, hipMemcpy(woop_out, sc.woop, (size_t)sc.n_refs * 12 * sizeof(float), hipMemcpyDeviceToHost));
+	CTX_TRY(c, hipSetDevice(i.device));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
+	if(nodes_out) CTX_TRY(c, hipMemcpy(nodes_out, sc.nodes, (size_t)sc.n_nodes * kNodeBytes, hipMemcpyDeviceToHost));
+	if(woop_out && sc.n_refs > 0) CTX_TRY(c, hipMemcpy(woop_out, sc.woop, (size_t)sc.n_refs * 12 * sizeof(float), hipMemcpyDeviceToHost));
 	return ADYPT_OK;
 }
 
 int adypt_get_refit_timing(adypt_ctx *c, float *ms, int capacity)
 {
 	if(!c || !ms || capacity < 0) return ADYPT_E_INVALID;
-	Refitter *rf = refitter_if_any(c);
-	if(!rf || !rf->timed) return cfail(c, ADYPT_E_STATE, "adypt_get_refit_timing: nothing has been refitted yet (adypt_update_triangles)");
-	const int n = kTimingEvents;
-	if(capacity < n) return n;
-	for(int k = 0; k < n - 1; ++k)
-	{
-		ms[k] = 0.0f;
-		(void)hipEventElapsedTime(&ms[k], rf->ev[k], rf->ev[k + 1]);
-	}
-	ms[n - 1] = 0.0f;
-	(void)hipEventElapsedTime(&ms[n - 1], rf->ev[0], rf->ev[n - 1]);
-	(void)hipGetLastError();
-	return n;
+	const Refitter *rf = ctx_state_if_any<Refitter>(c, kAttachRefit);
+	if(!rf || !rf->timer.completed()) return ctx_fail(c, ADYPT_E_STATE, "adypt_get_refit_timing: nothing has been refitted yet (adypt_update_triangles)");
+	return rf->timer.read(ms, capacity, kTimingEvents - 1, true);
 }
 
 // the scene is replicated: the same update on every device
 int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals)
 {
-	const int n_dev = adypt_multi_device_count(m);
-	if(n_dev < 1) return ADYPT_E_INVALID;
-	for(int k = 0; k < n_dev; ++k)
-	{
-		adypt_ctx *c = adypt_multi_context(m, k);
-		const int r = adypt_update_triangles(c, first, count, positions, normals);
-		if(r != ADYPT_OK) { multi_set_error(m, adypt_last_error(c)); return r; } // (a bad range is refused by the first context: none has changed)
-	}
-	return ADYPT_OK;
+	// (a bad range is refused by the first context: none has changed)
+	return multi_each(m, [=](adypt_ctx *c) { return adypt_update_triangles(c, first, count, positions, normals); });
 }
 
 }  // extern "C"

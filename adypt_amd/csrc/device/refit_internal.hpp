@@ -1,17 +1,36 @@
-// What build.hip needs of refit.hip: the two kernels that turn a topology plus triangles into Woop data and node records, and the hand-over of a new
-// tree's level lists and exact boxes to the context's refit state.  Not part of the C-ABI.
+// What build.hip needs of refit.hip: how a triangle record's positions are read, the levels of a tree as the refit keeps them, the launches that turn
+// a topology plus triangles into Woop data and node records, and the hand-over of a new tree's levels to the context's refit state.  Not part of the C-ABI.
 #pragma once
 #include "ctx_access.hpp"
 #include "resources.hpp"
 
+#include <cstdint>
+#include <vector>
+
 namespace adypt {
+
+// floats 0..8 of a triangle record (shade.hpp): the three vertices, as woop.hpp, refit.hpp and lbvh.hpp take them
+__device__ __forceinline__ void load_positions(const float4 *rec, float p[9])
+{
+	const float4 a = rec[0], b = rec[1], c = rec[2];
+	p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w; p[4] = b.x; p[5] = b.y; p[6] = b.z; p[7] = b.w; p[8] = c.x;
+}
+
+// What a refit needs of a tree once it is planned (refit_plan.hpp) or built (build.hip): level l is order[level_begin[l] .. level_begin[l + 1]), the
+// nodes in any order inside a level
+struct TreeLevels {
+	std::vector<int64_t> level_begin; // levels + 1 entries
+	Buffer<int32_t> order;            // device: 4 B per node
+	Buffer<float4> boxes;             // device: the exact boxes, 2 float4 per node
+	int levels() const { return (int)level_begin.size() - 1; }
+};
 
 // k_refit_woop: one thread per reference
 hipError_t refit_launch_woop(hipStream_t stream, const float4 *triangles, int tri_float4, const int32_t *tri_indices, int64_t n_refs, float4 *woop);
-// k_refit_nodes for the nodes level[0 .. n_level) of one level; the levels below it have been launched on the same stream before
-hipError_t refit_launch_nodes(hipStream_t stream, uint4 *nodes, float4 *boxes, const int32_t *level, int64_t n_level, const int32_t *tri_indices, const float4 *triangles, int tri_float4);
-// The context's tree has been replaced: its refit plan is now level_begin (levels + 1 entries) over `order` (the nodes level by level, any order inside
-// a level), its exact boxes are `boxes` (2 float4 per node).  Both buffers are taken.  A later adypt_update_triangles refits the new topology.
-int refit_adopt_tree(adypt_ctx *c, const std::vector<int64_t> &level_begin, Buffer<int32_t> &&order, Buffer<float4> &&boxes);
+// k_refit_nodes once per level, deepest first: a level reads the exact boxes that the launches before it on the same stream wrote
+hipError_t refit_launch_levels(hipStream_t stream, const TreeLevels &tree, uint4 *nodes, const int32_t *tri_indices, const float4 *triangles, int tri_float4);
+// The context's tree has been replaced: `tree` is taken as the refit's.  A later adypt_update_triangles refits the new topology; the timing of the last
+// update is no longer to be read.
+void refit_adopt_tree(adypt_ctx *c, TreeLevels &&tree);
 
 }  // namespace adypt
