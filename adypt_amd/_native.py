@@ -176,7 +176,9 @@ _SIGS = {
     "adypt_get_rebuild_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
     "adypt_get_bvh_sizes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "adypt_read_tri_indices": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_rebuild_bvh_ploc": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.POINTER(RebuildInfo)]),
     "adypt_multi_rebuild_bvh": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(RebuildInfo)]),
+    "adypt_multi_rebuild_bvh_ploc": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.POINTER(RebuildInfo)]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),
@@ -231,6 +233,8 @@ _SIGS = {
     "adypt_bvh_build": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(C.c_void_p), C.POINTER(BuildInfo)]),
     "adypt_bvh_build_linear": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(C.c_void_p), C.POINTER(BuildInfo)]),
     "adypt_lbvh_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "adypt_bvh_build_ploc": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.POINTER(C.c_void_p), C.POINTER(BuildInfo)]),
+    "adypt_ploc_tree": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "adypt_bvh_load": (C.c_int, [C.c_char_p, C.POINTER(BvhParams), C.POINTER(C.c_void_p)]),
     "adypt_bvh_save": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(BvhParams)]),
     "adypt_bvh_free": (None, [C.c_void_p]),

@@ -194,6 +194,15 @@ class WideBVH:
         self.build_info = info
         self._pull()
 
+    def BuildPLOC(self, scene: Scene, cfg: N.BvhParams, radius: int = 8) -> None:
+        """adypt_bvh_build_ploc: BuildLinear with the binary tree built bottom up by PLOC (csrc/device/ploc.hpp) — what RebuildBVH(method="ploc") builds
+        on the GPU, byte for byte.  radius in [1, 32]: how far a cluster looks to either side in Morton order."""
+        self._free()
+        info = N.BuildInfo()
+        N.check_host(N.lib.adypt_bvh_build_ploc(scene._h, C.byref(cfg), radius, C.byref(self._h), C.byref(info)))
+        self.build_info = info
+        self._pull()
+
     def Refit(self, scene: Scene) -> None:
         """adypt_bvh_refit: the boxes of the nodes recomputed, in place, for the triangles of `scene` as they are now (the same triangles, moved).
         The topology and GetTriIndices() stay; the Woop data of the pose is woop_matrices(scene.triangles, GetTriIndices())."""
@@ -586,11 +595,19 @@ class _Tracer:
         return nodes, woop
 
     # ---- rebuilding the tree on the GPU (adypt_rebuild_bvh, include/adypt_hip.h; the definition: csrc/device/lbvh.hpp) ----
-    def RebuildBVH(self, cfg: Optional[N.BvhParams] = None) -> dict:
-        """A new tree, built on the GPU from the triangles as UpdateTriangles() left them: WideBVH.BuildLinear's bytes.  Leaves the tracer as Reset()
-        does (0 spp).  Several devices: on every device.  Returns n_nodes, n_refs, levels (size stack_size by it) and binary_depth."""
+    def RebuildBVH(self, cfg: Optional[N.BvhParams] = None, method: str = "linear", radius: int = 8) -> dict:
+        """A new tree, built on the GPU from the triangles as UpdateTriangles() left them.  method "linear": WideBVH.BuildLinear's bytes; "ploc": those
+        of WideBVH.BuildPLOC(radius=radius) — a tighter tree on meshes for a few times the build time (csrc/device/ploc.hpp); radius counts for "ploc"
+        only.  Leaves the tracer as Reset() does (0 spp).  Several devices: on every device.  Returns n_nodes, n_refs, levels (size stack_size by it)
+        and binary_depth."""
+        if method not in ("linear", "ploc"):
+            raise ValueError("RebuildBVH: method must be 'linear' or 'ploc', not %r" % (method,))
         info = N.RebuildInfo()
-        self._call("rebuild_bvh", None if cfg is None else C.byref(cfg), C.byref(info))
+        params = None if cfg is None else C.byref(cfg)
+        if method == "ploc":
+            self._call("rebuild_bvh_ploc", params, int(radius), C.byref(info))
+        else:
+            self._call("rebuild_bvh", params, C.byref(info))
         return {k: getattr(info, k) for k, _ in info._fields_}
 
     def GetBVHSizes(self) -> Tuple[int, int]:
@@ -608,7 +625,7 @@ class _Tracer:
         return idx[:self.GetBVHSizes()[1]]
 
     def GetRebuildTiming(self) -> dict:
-        """HIP-event milliseconds of the last RebuildBVH() on the (first) device."""
+        """HIP-event milliseconds of the last RebuildBVH() on the (first) device.  After method "ploc": "tree" is all the rounds, "bottom_up" is 0."""
         ms = (C.c_float * 7)()
         c = self._contexts()[0]
         n = N.lib.adypt_get_rebuild_timing(c, ms, 7)

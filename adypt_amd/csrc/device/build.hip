@@ -12,15 +12,24 @@
 //                       the node's inner children, with the runs that are theirs, to the next level.  Only the queue slot comes from an atomic; where a
 //                       node and its references go was decided by the counts.  The host reads the next level's size (4 bytes) between launches
 //     (refit.hip)       k_refit_woop, then k_refit_nodes level by level, deepest first, over the queues of k_emit
+// adypt_rebuild_bvh_ploc (the definition: ploc.hpp) keeps the keys, the sort and everything from k_emit on, and builds the binary tree bottom up instead:
+//     k_ploc_leaves     one thread per leaf: what k_bottom_up writes for a leaf, and the first cluster list
+//     per round         k_ploc_nearest (every cluster's choice among the 2 r around it, their boxes staged in LDS), k_ploc_marks (who stays, who
+//                       merges), rocprim::exclusive_scan over the marks (new positions and merge ordinals: by position, never by arrival), k_ploc_merge
+//                       (the new nodes — k_bottom_up's loop body over children that earlier launches finished — and the next cluster list).  The host
+//                       reads the round's two counts (8 bytes) and goes on until one cluster is left; a round without a merge ends the build
+//     Stream order is the whole dependency: no atomics on the tree, no fences, nobody waits for another workgroup.
 // Everything is built into new arrays; the context takes them last (ctx_replace_bvh), so a refused or failed call leaves the old tree usable.
 #include "ctx_unit.hpp"
 #include "refit_internal.hpp"
 #include "lbvh.hpp"
+#include "ploc.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
 
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <string>
@@ -156,6 +165,103 @@ __global__ __launch_bounds__(kBuildThreads) void k_bottom_up(BinTree t, const fl
 	}
 }
 
+// ---- PLOC (ploc.hpp).  clusters: node ids in cluster order; nearest: every cluster's choice (-1: none); marks: 1 for a cluster that stays in the list,
+// 1 << 32 more for one that merges, and a zero behind the last one — so the exclusive scan's entry [m] holds the round's two counts
+
+__global__ __launch_bounds__(kBuildThreads) void k_ploc_leaves(BinTree t, const float4 *triangles, int tri_float4, float triangle_sah, int32_t *clusters, uint32_t *flags)
+{
+	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(j >= t.n) return;
+	const int leaf = (int)(t.n - 1 + j);
+	const float4 *rec = triangles + (size_t)t.tri(leaf) * (size_t)tri_float4;
+	float p[9];
+	load_positions(rec, p);
+	const RefitBox box = refit_triangle_box(p);
+	const float area = cut_area(box.lo, box.hi);
+	if(!ploc_finite(area)) atomicOr(flags, (uint32_t)kFlagCost);
+	t.boxes[(size_t)leaf * 2] = make_float4(box.lo[0], box.lo[1], box.lo[2], __int_as_float(1));
+	t.boxes[(size_t)leaf * 2 + 1] = make_float4(box.hi[0], box.hi[1], box.hi[2], __int_as_float(0));
+	CutRow row;
+	cut_leaf_row(area, triangle_sah, row);
+	t.rows[leaf] = row;
+	t.wide_below_[leaf] = 0u;
+	clusters[j] = leaf;
+}
+
+constexpr int kPlocStaged = kBuildThreads + 2 * kPlocMaxRadius;
+
+// the boxes of the positions origin .. origin + kPlocStaged - 1, one array per component: the lanes of a wave read neighbouring positions of one
+// component, which are neighbouring banks
+struct PlocStaged {
+	const float (*s)[kPlocStaged];
+	int64_t origin;
+	__device__ __forceinline__ RefitBox box(int64_t position) const
+	{
+		const int k = (int)(position - origin);
+		return RefitBox{{s[0][k], s[1][k], s[2][k]}, {s[3][k], s[4][k], s[5][k]}};
+	}
+};
+
+// One workgroup: the clusters [base, base + 256) and r more on either side, as far as they exist.  Positions outside [0, m) are neither staged nor
+// read (ploc_nearest clips its scan to the list), and a position's slot is position - (base - r) < 256 + 2 r <= kPlocStaged.
+__global__ __launch_bounds__(kBuildThreads) void k_ploc_nearest(const float4 *boxes, const int32_t *clusters, int64_t m, int r, int32_t *nearest)
+{
+	__shared__ float s_box[6][kPlocStaged];
+	const int64_t base = (int64_t)blockIdx.x * kBuildThreads, origin = base - r;
+	for(int k = (int)threadIdx.x; k < kBuildThreads + 2 * r; k += kBuildThreads)
+	{
+		const int64_t position = origin + k;
+		if(position < 0 || position >= m) continue;
+		const size_t node = (size_t)clusters[position];
+		const float4 lo = boxes[node * 2], hi = boxes[node * 2 + 1];
+		s_box[0][k] = lo.x; s_box[1][k] = lo.y; s_box[2][k] = lo.z; s_box[3][k] = hi.x; s_box[4][k] = hi.y; s_box[5][k] = hi.z;
+	}
+	__syncthreads();
+	const int64_t i = base + threadIdx.x;
+	if(i >= m) return;
+	nearest[i] = (int32_t)ploc_nearest(PlocStaged{s_box, origin}, m, i, r);
+}
+
+__global__ __launch_bounds__(kBuildThreads) void k_ploc_marks(const int32_t *nearest, int64_t m, uint64_t *marks)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(i > m) return;
+	const int role = i < m ? ploc_role(nearest, i) : kPlocLeaves;
+	marks[i] = (role != kPlocLeaves ? 1ull : 0ull) | (role == kPlocMerges ? 1ull << 32 : 0ull);
+}
+
+// scanned: the exclusive scan of the marks, m + 1 entries.  next: the inner ids from `next` on are given out (ploc.hpp).  A merging cluster writes its
+// node as k_bottom_up does, from children that earlier launches finished; every cluster that stays writes its node id to its new position.
+__global__ __launch_bounds__(kBuildThreads) void k_ploc_merge(BinTree t, const int32_t *clusters, const int32_t *nearest, const uint64_t *scanned, int64_t m, int64_t next, float triangle_sah, float node_sah,
+                                                             int32_t *clusters_out, uint32_t *flags)
+{
+	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= m) return;
+	const int role = ploc_role(nearest, i);
+	if(role == kPlocLeaves) return;
+	const uint64_t mine = scanned[i];
+	int32_t cur = clusters[i];
+	if(role == kPlocMerges)
+	{
+		const int l = cur, r = clusters[nearest[i]];
+		cur = ploc_merge_id(next, (int64_t)(scanned[m] >> 32), (int64_t)(mine >> 32));
+		if(cur < 0 || (int64_t)cur >= t.n - 1) { atomicOr(flags, (uint32_t)kFlagLayout); return; } // (counts that disagree must not turn into a stray store)
+		t.left_[cur] = l; t.right_[cur] = r;
+		t.parent[l] = cur; t.parent[r] = cur;
+		const float4 llo = t.boxes[(size_t)l * 2], lhi = t.boxes[(size_t)l * 2 + 1], rlo = t.boxes[(size_t)r * 2], rhi = t.boxes[(size_t)r * 2 + 1];
+		const RefitBox box = refit_union(RefitBox{{llo.x, llo.y, llo.z}, {lhi.x, lhi.y, lhi.z}}, RefitBox{{rlo.x, rlo.y, rlo.z}, {rhi.x, rhi.y, rhi.z}});
+		const int tc = __float_as_int(rlo.w) + __float_as_int(llo.w), height = 1 + max(__float_as_int(lhi.w), __float_as_int(rhi.w));
+		t.boxes[(size_t)cur * 2] = make_float4(box.lo[0], box.lo[1], box.lo[2], __int_as_float(tc));
+		t.boxes[(size_t)cur * 2 + 1] = make_float4(box.hi[0], box.hi[1], box.hi[2], __int_as_float(height));
+		const CutRow L = t.rows[l], R = t.rows[r];
+		CutRow row;
+		if(!cut_inner_row(cut_area(box.lo, box.hi), tc, triangle_sah, node_sah, L, R, row)) atomicOr(flags, (uint32_t)kFlagCost);
+		t.rows[cur] = row;
+		t.wide_below_[cur] = cut_wide_below(t, cur);
+	}
+	clusters_out[(uint32_t)mine] = cur;
+}
+
 // items[begin .. begin + count): this level; its inner children are appended from items[begin + count] on, *appended counts them.  n_nodes and n_refs
 // bound every store: counts that disagree raise kFlagLayout instead of writing out of range.
 __global__ __launch_bounds__(kEmitThreads) void k_emit(BinTree t, WideItem *items, int32_t *order, int64_t begin, int64_t count, uint32_t *appended, int64_t n_nodes, int64_t n_refs, uint4 *nodes,
@@ -188,15 +294,57 @@ struct Builder {
 	Buffer<float4> boxes, partial;
 	Buffer<CutRow> rows;
 	Buffer<uint32_t> wide_below, arrived, words; // words: [0] the flags, [1] the next level's count
+	Buffer<int32_t> clusters, nearest;           // PLOC: two cluster lists, the choices
+	Buffer<uint64_t> marks, scanned;             // PLOC: n + 1 each
+	bool last_ploc = false;
 	StageTimer<kTimingEvents> timer;
 	adypt_rebuild_info last{};
 };
 
-int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, adypt_rebuild_info *out)
+// the PLOC rounds: the tree, boxes, counts, rows and wide_below of every node.  The caller has cleared the flags (b->words).
+int ploc_rounds(adypt_ctx *c, Builder *b, hipStream_t stream, const BinTree &t, const float4 *tris, int tri_float4, const adypt_bvh_params &cfg, int radius, const char *who)
 {
+	const int64_t n = t.n;
+	int32_t *list[2] = {b->clusters.get(), b->clusters.get() + n};
+	hipLaunchKernelGGL(k_ploc_leaves, dim3(grid_of(n, kBuildThreads)), dim3(kBuildThreads), 0, stream, t, tris, tri_float4, cfg.triangle_sah, list[0], b->words.get());
+	CTX_TRY(c, hipGetLastError());
+	for(int64_t m = n, next = n - 1; m > 1;)
+	{
+		hipLaunchKernelGGL(k_ploc_nearest, dim3(grid_of(m, kBuildThreads)), dim3(kBuildThreads), 0, stream, (const float4 *)t.boxes, (const int32_t *)list[0], m, radius, b->nearest.get());
+		CTX_TRY(c, hipGetLastError());
+		hipLaunchKernelGGL(k_ploc_marks, dim3(grid_of(m + 1, kBuildThreads)), dim3(kBuildThreads), 0, stream, (const int32_t *)b->nearest.get(), m, b->marks.get());
+		CTX_TRY(c, hipGetLastError());
+		size_t scan_bytes = 0; // (of this round's m + 1 entries: never more than what was allocated for n + 1, and checked, since rocPRIM takes the pointer as it is)
+		CTX_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, b->marks.get(), b->scanned.get(), (uint64_t)0, (size_t)(m + 1), rocprim::plus<uint64_t>(), stream));
+		if(scan_bytes > b->sort_tmp.bytes()) return ctx_fail(c, ADYPT_E_HIP, std::string(who) + ": the scan asks for more temporary storage than it did for the whole list");
+		CTX_TRY(c, rocprim::exclusive_scan((void *)b->sort_tmp.get(), scan_bytes, b->marks.get(), b->scanned.get(), (uint64_t)0, (size_t)(m + 1), rocprim::plus<uint64_t>(), stream));
+		hipLaunchKernelGGL(k_ploc_merge, dim3(grid_of(m, kBuildThreads)), dim3(kBuildThreads), 0, stream, t, (const int32_t *)list[0], (const int32_t *)b->nearest.get(), (const uint64_t *)b->scanned.get(), m, next,
+		                   cfg.triangle_sah, cfg.node_sah, list[1], b->words.get());
+		CTX_TRY(c, hipGetLastError());
+		uint64_t counts = 0;
+		uint32_t flags = 0;
+		CTX_TRY(c, hipMemcpyAsync(&counts, b->scanned.get() + m, sizeof(counts), hipMemcpyDeviceToHost, stream));
+		CTX_TRY(c, hipMemcpyAsync(&flags, b->words.get(), sizeof(flags), hipMemcpyDeviceToHost, stream));
+		CTX_TRY(c, hipStreamSynchronize(stream));
+		const int64_t stay = (int64_t)(uint32_t)counts, merges = (int64_t)(counts >> 32);
+		if(flags & kFlagCost) return ADYPT_OK; // (the caller reads the flags again and refuses)
+		if(flags & kFlagLayout) return ctx_fail(c, ADYPT_E_HIP, std::string(who) + ": the merges of a round do not add up to the counted ones");
+		if(merges <= 0 || stay != m - merges) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": a round merged nothing (areas that are infinite or NaN)");
+		next -= merges;
+		m = stay;
+		std::swap(list[0], list[1]);
+	}
+	return ADYPT_OK;
+}
+
+// radius 0: the linear tree; otherwise PLOC with that radius
+int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, adypt_rebuild_info *out)
+{
+	const bool ploc = radius != 0;
+	const char *who = ploc ? "adypt_rebuild_bvh_ploc" : "adypt_rebuild_bvh";
 	const CtxScene sc = ctx_scene(c);
 	const int64_t n = sc.n_tris;
-	if(n > ((int64_t)1 << 30)) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: more than 2^30 triangles");
+	if(n > ((int64_t)1 << 30)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": more than 2^30 triangles");
 	CTX_STEP(ctx_drain(c));
 	const hipStream_t stream = ctx_info(c).stream;
 	Builder *b = ctx_state<Builder>(c, kAttachBuild);
@@ -204,10 +352,18 @@ int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, adypt_rebuild_info *out)
 	const size_t n_bin = (size_t)(2 * n - 1), n_inner = (size_t)(n - 1);
 	size_t sort_bytes = 0;
 	CTX_TRY(c, rocprim::radix_sort_keys(nullptr, sort_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)n, 0u, (unsigned)kKeyBits, stream));
-	CTX_TRY(c, at_least(b->keys, (size_t)n)); CTX_TRY(c, at_least(b->sorted, (size_t)n)); CTX_TRY(c, at_least(b->sort_tmp, sort_bytes));
+	size_t scan_bytes = 0;
+	if(ploc) CTX_TRY(c, rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), stream));
+	CTX_TRY(c, at_least(b->keys, (size_t)n)); CTX_TRY(c, at_least(b->sorted, (size_t)n)); CTX_TRY(c, at_least(b->sort_tmp, std::max(sort_bytes, scan_bytes)));
 	CTX_TRY(c, at_least(b->left, n_inner)); CTX_TRY(c, at_least(b->right, n_inner)); CTX_TRY(c, at_least(b->parent, n_bin));
 	CTX_TRY(c, at_least(b->boxes, n_bin * 2)); CTX_TRY(c, at_least(b->partial, (size_t)(kMaxPartials + 1) * 2));
-	CTX_TRY(c, at_least(b->rows, n_bin)); CTX_TRY(c, at_least(b->wide_below, n_bin)); CTX_TRY(c, at_least(b->arrived, n_inner)); CTX_TRY(c, at_least(b->words, 2));
+	CTX_TRY(c, at_least(b->rows, n_bin)); CTX_TRY(c, at_least(b->wide_below, n_bin)); CTX_TRY(c, at_least(b->words, 2));
+	if(ploc)
+	{
+		CTX_TRY(c, at_least(b->clusters, (size_t)n * 2)); CTX_TRY(c, at_least(b->nearest, (size_t)n));
+		CTX_TRY(c, at_least(b->marks, (size_t)n + 1)); CTX_TRY(c, at_least(b->scanned, (size_t)n + 1));
+	}
+	else CTX_TRY(c, at_least(b->arrived, n_inner));
 	b->timer.invalidate();
 	CTX_TRY(c, b->timer.mark(0, stream));
 	// ---- keys
@@ -223,20 +379,29 @@ int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, adypt_rebuild_info *out)
 	// ---- sort
 	CTX_TRY(c, rocprim::radix_sort_keys((void *)b->sort_tmp.get(), sort_bytes, b->keys.get(), b->sorted.get(), (size_t)n, 0u, (unsigned)kKeyBits, stream));
 	CTX_TRY(c, b->timer.mark(2, stream));
-	// ---- the radix tree
 	BinTree t{n, b->sorted.get(), b->left.get(), b->right.get(), b->parent.get(), b->boxes.get(), b->rows.get(), b->wide_below.get()};
 	CTX_TRY(c, hipMemsetAsync(b->parent.get(), 0xff, sizeof(int32_t), stream)); // the root's
-	if(n_inner)
+	CTX_TRY(c, hipMemsetAsync(b->words.get(), 0, 2 * sizeof(uint32_t), stream));
+	if(ploc)
 	{
-		hipLaunchKernelGGL(k_radix_tree, dim3(grid_of(n - 1, kBuildThreads)), dim3(kBuildThreads), 0, stream, t);
+		// ---- the PLOC tree with its boxes, counts and cut, round by round
+		CTX_STEP(ploc_rounds(c, b, stream, t, tris, sc.tri_float4, cfg, radius, who));
+		CTX_TRY(c, b->timer.mark(3, stream));
+	}
+	else
+	{
+		// ---- the radix tree
+		if(n_inner)
+		{
+			hipLaunchKernelGGL(k_radix_tree, dim3(grid_of(n - 1, kBuildThreads)), dim3(kBuildThreads), 0, stream, t);
+			CTX_TRY(c, hipGetLastError());
+		}
+		CTX_TRY(c, b->timer.mark(3, stream));
+		// ---- boxes, counts and the cut, bottom up
+		CTX_TRY(c, hipMemsetAsync(b->arrived.get(), 0, std::max<size_t>(n_inner, 1) * sizeof(uint32_t), stream));
+		hipLaunchKernelGGL(k_bottom_up, dim3(grid_of(n, kBuildThreads)), dim3(kBuildThreads), 0, stream, t, tris, sc.tri_float4, cfg.triangle_sah, cfg.node_sah, b->arrived.get(), b->words.get());
 		CTX_TRY(c, hipGetLastError());
 	}
-	CTX_TRY(c, b->timer.mark(3, stream));
-	// ---- boxes, counts and the cut, bottom up
-	CTX_TRY(c, hipMemsetAsync(b->arrived.get(), 0, std::max<size_t>(n_inner, 1) * sizeof(uint32_t), stream));
-	CTX_TRY(c, hipMemsetAsync(b->words.get(), 0, 2 * sizeof(uint32_t), stream));
-	hipLaunchKernelGGL(k_bottom_up, dim3(grid_of(n, kBuildThreads)), dim3(kBuildThreads), 0, stream, t, tris, sc.tri_float4, cfg.triangle_sah, cfg.node_sah, b->arrived.get(), b->words.get());
-	CTX_TRY(c, hipGetLastError());
 	CTX_TRY(c, b->timer.mark(4, stream));
 	uint32_t root_wide = 0, flags = 0;
 	float4 root_hi;
@@ -244,7 +409,7 @@ int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, adypt_rebuild_info *out)
 	CTX_TRY(c, hipMemcpyAsync(&root_hi, b->boxes.get() + 1, sizeof(root_hi), hipMemcpyDeviceToHost, stream));
 	CTX_TRY(c, hipMemcpyAsync(&flags, b->words.get(), sizeof(flags), hipMemcpyDeviceToHost, stream));
 	CTX_TRY(c, hipStreamSynchronize(stream));
-	if(flags & kFlagCost) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: the SAH costs of this scene are not finite numbers below FLT_MAX (vertices that are NaN, infinite or huge)");
+	if(flags & kFlagCost) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": the SAH costs of this scene are not finite numbers below FLT_MAX (vertices that are NaN, infinite or huge)");
 	// ---- the wide tree, top down, into new arrays
 	const int64_t n_nodes = std::max<uint32_t>(root_wide, 1u), n_refs = n;
 	Buffer<uint4> nodes;
@@ -272,9 +437,9 @@ int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, adypt_rebuild_info *out)
 		begin += count;
 		tree.level_begin.push_back(begin);
 		count = (int64_t)words[1];
-		if((words[0] & kFlagLayout) || begin + count > n_nodes) return ctx_fail(c, ADYPT_E_HIP, "adypt_rebuild_bvh: the emitted nodes do not add up to the counted ones");
+		if((words[0] & kFlagLayout) || begin + count > n_nodes) return ctx_fail(c, ADYPT_E_HIP, std::string(who) + ": the emitted nodes do not add up to the counted ones");
 	}
-	if(tree.level_begin.back() != n_nodes) return ctx_fail(c, ADYPT_E_HIP, "adypt_rebuild_bvh: the emitted nodes do not add up to the counted ones");
+	if(tree.level_begin.back() != n_nodes) return ctx_fail(c, ADYPT_E_HIP, std::string(who) + ": the emitted nodes do not add up to the counted ones");
 	CTX_TRY(c, b->timer.mark(5, stream));
 	// ---- Woop data and the node records: the refit's kernels, deepest level first
 	CTX_TRY(c, refit_launch_woop(stream, tris, sc.tri_float4, tri_indices.get(), n_refs, woop.get()));
@@ -286,6 +451,7 @@ int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, adypt_rebuild_info *out)
 	b->last = adypt_rebuild_info{n_nodes, n_refs, tree.levels(), __builtin_bit_cast(int32_t, root_hi.w)};
 	refit_adopt_tree(c, std::move(tree));
 	b->timer.complete();
+	b->last_ploc = ploc;
 	if(out) *out = b->last;
 	return ADYPT_OK;
 }
@@ -302,7 +468,19 @@ int adypt_rebuild_bvh(adypt_ctx *c, const adypt_bvh_params *params, adypt_rebuil
 	if(!(cfg.triangle_sah > 0.0f && cfg.triangle_sah < kCutMax && cfg.node_sah > 0.0f && cfg.node_sah < kCutMax))
 		return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: the SAH costs must be positive finite numbers");
 	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
-	return rebuild(c, cfg, out);
+	return rebuild(c, cfg, 0, out);
+}
+
+int adypt_rebuild_bvh_ploc(adypt_ctx *c, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out)
+{
+	if(!c) return ADYPT_E_INVALID;
+	adypt_bvh_params cfg{0, 0.3f, 1.0f};
+	if(params) cfg = *params;
+	if(!(cfg.triangle_sah > 0.0f && cfg.triangle_sah < kCutMax && cfg.node_sah > 0.0f && cfg.node_sah < kCutMax))
+		return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc: the SAH costs must be positive finite numbers");
+	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc: the radius must be in [1, 32]");
+	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
+	return rebuild(c, cfg, radius, out);
 }
 
 int adypt_get_rebuild_timing(adypt_ctx *c, float *ms, int capacity)
@@ -310,7 +488,9 @@ int adypt_get_rebuild_timing(adypt_ctx *c, float *ms, int capacity)
 	if(!c || !ms || capacity < 0) return ADYPT_E_INVALID;
 	const Builder *b = ctx_state_if_any<Builder>(c, kAttachBuild);
 	if(!b || !b->timer.completed()) return ctx_fail(c, ADYPT_E_STATE, "adypt_get_rebuild_timing: nothing has been rebuilt yet (adypt_rebuild_bvh)");
-	return b->timer.read(ms, capacity, kTimingEvents - 1, true);
+	const int n = b->timer.read(ms, capacity, kTimingEvents - 1, true);
+	if(b->last_ploc && capacity >= n) ms[3] = 0.0f; // (the rounds are entry [2]; there is no pass of its own behind them)
+	return n;
 }
 
 int adypt_get_bvh_sizes(adypt_ctx *c, int64_t *n_nodes, int64_t *n_refs)
@@ -338,6 +518,11 @@ int adypt_multi_rebuild_bvh(adypt_multi *m, const adypt_bvh_params *params, adyp
 {
 	// (bad parameters are refused by the first context: none has changed)
 	return multi_each(m, [=](adypt_ctx *c) { return adypt_rebuild_bvh(c, params, out); });
+}
+
+int adypt_multi_rebuild_bvh_ploc(adypt_multi *m, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out)
+{
+	return multi_each(m, [=](adypt_ctx *c) { return adypt_rebuild_bvh_ploc(c, params, radius, out); });
 }
 
 }  // extern "C"

@@ -14,6 +14,15 @@ int64_t build_sbvh(const TriRec *tris, int64_t n_tris, const Box &scene_box, con
 // the longest path from the root to a leaf.  Returns the number of leaves.
 void lbvh_sorted_keys(const TriRec *tris, int64_t n_tris, std::vector<uint64_t> *keys); // Morton code << 32 | triangle index, ascending
 int64_t build_lbvh(const TriRec *tris, int64_t n_tris, std::vector<BinNode> *nodes, int *depth, double *ms);
+// left, right: the children of the inner nodes 0 .. n - 2 in the node ids of lbvh.hpp (leaf of sorted position j: n - 1 + j)
+void layout_binary_tree(const TriRec *tris, int64_t n_tris, const std::vector<uint64_t> &keys, const std::vector<int32_t> &left, const std::vector<int32_t> &right, std::vector<BinNode> *nodes,
+                        int *depth);
+
+// the binary tree of ../device/ploc.hpp over the sorted keys, in the node ids of lbvh.hpp.  *rounds: the rounds it took.  ADYPT_E_INVALID for a leaf
+// whose area is no finite number and for a round that merges nothing; sequential, so the same for any number of threads
+int ploc_tree(const TriRec *tris, int64_t n_tris, int radius, const std::vector<uint64_t> &keys, std::vector<int32_t> *left, std::vector<int32_t> *right, int *rounds);
+// ... laid out as build_lbvh lays out its tree.  Returns the number of leaves, or -1 where ploc_tree refuses
+int64_t build_ploc(const TriRec *tris, int64_t n_tris, int radius, std::vector<BinNode> *nodes, int *depth, double *ms);
 
 void build_wide_bvh(const std::vector<BinNode> &bin, int64_t leaf_count, const adypt_bvh_params &cfg,
 					std::vector<NodeRec> *nodes, std::vector<int32_t> *tri_indices, double *ms, int n_threads);

@@ -3,6 +3,7 @@
 #include "builders.hpp"
 #include "exact_sort.hpp"
 #include "../device/woop.hpp"
+#include "../device/ploc.hpp"
 #include "../../../include/adypt_hip.h"
 
 #include <algorithm>
@@ -243,19 +244,12 @@ int adypt_bvh_build(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh *
 	return ADYPT_OK;
 }
 
-int adypt_bvh_build_linear(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, adypt_build_info *info)
+// the collapse of a binary tree without splits, with the boxes by the refit's rule: what the linear and the PLOC tree share
+static int collapse_unsplit(const std::vector<BinNode> &bin, int64_t leaves, const adypt_bvh_params &p, const void *tp, int64_t nt, double tree_ms, adypt_bvh **out, adypt_build_info *info)
 {
-	if(!s || !p || !out) { set_host_error("adypt_bvh_build_linear: null argument"); return ADYPT_E_INVALID; }
-	const void *tp; int64_t nt = adypt_scene_triangles(s, &tp);
-	if(nt <= 0) { set_host_error("adypt_bvh_build_linear: scene has no triangles"); return ADYPT_E_INVALID; }
-	if(nt > ((int64_t)1 << 30)) { set_host_error("adypt_bvh_build_linear: more than 2^30 triangles"); return ADYPT_E_INVALID; }
-	if(!(p->triangle_sah > 0.0f && p->triangle_sah < FLT_MAX && p->node_sah > 0.0f && p->node_sah < FLT_MAX)) { set_host_error("adypt_bvh_build_linear: the SAH costs must be positive finite numbers"); return ADYPT_E_INVALID; }
-	std::vector<BinNode> bin;
-	double tree_ms = 0, wide_ms = 0;
-	int depth = 0;
-	const int64_t leaves = build_lbvh((const TriRec *)tp, nt, &bin, &depth, &tree_ms);
+	double wide_ms = 0;
 	adypt_bvh *b = new adypt_bvh();
-	build_wide_bvh(bin, leaves, *p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads());
+	build_wide_bvh(bin, leaves, p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads());
 	// the boxes are the refit's, not the collapse's: one rule, the device builder's too
 	for(NodeRec &n : b->nodes)
 	{
@@ -268,6 +262,56 @@ int adypt_bvh_build_linear(const adypt_scene *s, const adypt_bvh_params *p, adyp
 	wide_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	if(info) { info->sbvh_nodes = (int64_t)bin.size(); info->refs = leaves; info->wide_nodes = (int64_t)b->nodes.size(); info->sbvh_ms = tree_ms; info->wide_ms = wide_ms; }
 	*out = b;
+	return ADYPT_OK;
+}
+
+// what both unsplit builders ask of their arguments; `who` names the caller in the error
+static int unsplit_arguments(const char *who, const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, const void **tp, int64_t *nt)
+{
+	if(!s || !p || !out) { set_host_error(std::string(who) + ": null argument"); return ADYPT_E_INVALID; }
+	*nt = adypt_scene_triangles(s, tp);
+	if(*nt <= 0) { set_host_error(std::string(who) + ": scene has no triangles"); return ADYPT_E_INVALID; }
+	if(*nt > ((int64_t)1 << 30)) { set_host_error(std::string(who) + ": more than 2^30 triangles"); return ADYPT_E_INVALID; }
+	if(!(p->triangle_sah > 0.0f && p->triangle_sah < FLT_MAX && p->node_sah > 0.0f && p->node_sah < FLT_MAX)) { set_host_error(std::string(who) + ": the SAH costs must be positive finite numbers"); return ADYPT_E_INVALID; }
+	return ADYPT_OK;
+}
+
+int adypt_bvh_build_linear(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, adypt_build_info *info)
+{
+	const void *tp; int64_t nt;
+	const int r = unsplit_arguments("adypt_bvh_build_linear", s, p, out, &tp, &nt);
+	if(r != ADYPT_OK) return r;
+	std::vector<BinNode> bin;
+	double tree_ms = 0;
+	int depth = 0;
+	const int64_t leaves = build_lbvh((const TriRec *)tp, nt, &bin, &depth, &tree_ms);
+	return collapse_unsplit(bin, leaves, *p, tp, nt, tree_ms, out, info);
+}
+
+int adypt_bvh_build_ploc(const adypt_scene *s, const adypt_bvh_params *p, int radius, adypt_bvh **out, adypt_build_info *info)
+{
+	const void *tp; int64_t nt;
+	const int r = unsplit_arguments("adypt_bvh_build_ploc", s, p, out, &tp, &nt);
+	if(r != ADYPT_OK) return r;
+	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) { set_host_error("adypt_bvh_build_ploc: the radius must be in [1, 32]"); return ADYPT_E_INVALID; }
+	std::vector<BinNode> bin;
+	double tree_ms = 0;
+	int depth = 0;
+	const int64_t leaves = build_ploc((const TriRec *)tp, nt, radius, &bin, &depth, &tree_ms);
+	if(leaves < 0) return ADYPT_E_INVALID;
+	return collapse_unsplit(bin, leaves, *p, tp, nt, tree_ms, out, info);
+}
+
+int adypt_ploc_tree(const void *tris, int64_t n_tris, int radius, int32_t *left, int32_t *right)
+{
+	if(!tris || n_tris <= 0 || n_tris > ((int64_t)1 << 30) || (n_tris > 1 && (!left || !right))) { set_host_error("adypt_ploc_tree: null or empty argument"); return ADYPT_E_INVALID; }
+	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) { set_host_error("adypt_ploc_tree: the radius must be in [1, 32]"); return ADYPT_E_INVALID; }
+	std::vector<uint64_t> keys;
+	lbvh_sorted_keys((const TriRec *)tris, n_tris, &keys);
+	std::vector<int32_t> l, r;
+	const int code = ploc_tree((const TriRec *)tris, n_tris, radius, keys, &l, &r, nullptr);
+	if(code != ADYPT_OK) return code;
+	if(!l.empty()) { memcpy(left, l.data(), l.size() * sizeof(int32_t)); memcpy(right, r.data(), r.size() * sizeof(int32_t)); }
 	return ADYPT_OK;
 }
 

@@ -29,20 +29,9 @@ void lbvh_sorted_keys(const TriRec *tris, int64_t n, std::vector<uint64_t> *out)
 	std::sort(keys.begin(), keys.end());
 }
 
-int64_t build_lbvh(const TriRec *tris, int64_t n, std::vector<BinNode> *bin, int *depth, double *ms)
+// a binary tree in the node ids of lbvh.hpp (left, right: n - 1 entries; the root is 0) -> pre-order with exact boxes; the PLOC tree's too (ploc_builder.cpp)
+void layout_binary_tree(const TriRec *tris, int64_t n, const std::vector<uint64_t> &keys, const std::vector<int32_t> &left, const std::vector<int32_t> &right, std::vector<BinNode> *bin, int *depth)
 {
-	const auto t0 = std::chrono::steady_clock::now();
-	std::vector<uint64_t> keys;
-	lbvh_sorted_keys(tris, n, &keys);
-	// the radix tree: node ids as in lbvh.hpp
-	std::vector<int32_t> left((size_t)std::max<int64_t>(n - 1, 0)), right(left.size());
-	for(int64_t i = 0; i + 1 < n; ++i)
-	{
-		int64_t first, last, split;
-		lbvh_inner_node(keys.data(), n, i, &first, &last, &split);
-		left[(size_t)i] = lbvh_left_child(n, first, split);
-		right[(size_t)i] = lbvh_right_child(n, last, split);
-	}
 	// pre-order, right child first
 	bin->assign((size_t)(2 * n - 1), BinNode{});
 	struct Todo { int32_t id, parent, level; };
@@ -80,6 +69,23 @@ int64_t build_lbvh(const TriRec *tris, int64_t n, std::vector<BinNode> *bin, int
 		b.box = Box({u.lo[0], u.lo[1], u.lo[2]}, {u.hi[0], u.hi[1], u.hi[2]});
 	}
 	if(depth) *depth = deepest;
+}
+
+int64_t build_lbvh(const TriRec *tris, int64_t n, std::vector<BinNode> *bin, int *depth, double *ms)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	std::vector<uint64_t> keys;
+	lbvh_sorted_keys(tris, n, &keys);
+	// the radix tree: node ids as in lbvh.hpp
+	std::vector<int32_t> left((size_t)std::max<int64_t>(n - 1, 0)), right(left.size());
+	for(int64_t i = 0; i + 1 < n; ++i)
+	{
+		int64_t first, last, split;
+		lbvh_inner_node(keys.data(), n, i, &first, &last, &split);
+		left[(size_t)i] = lbvh_left_child(n, first, split);
+		right[(size_t)i] = lbvh_right_child(n, last, split);
+	}
+	layout_binary_tree(tris, n, keys, left, right, bin, depth);
 	if(ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	return n;
 }

@@ -331,12 +331,23 @@ typedef struct adypt_bvh_params adypt_bvh_params; /* adypt_host.h */
 typedef struct adypt_rebuild_info {
 	int64_t n_nodes, n_refs;   /* of the new tree */
 	int32_t levels;            /* of the wide tree: the root's level counts */
-	int32_t binary_depth;      /* edges on the longest path of the binary radix tree */
+	int32_t binary_depth;      /* edges on the longest path of the binary tree (the radix tree, or the PLOC tree) */
 } adypt_rebuild_info;
 int adypt_rebuild_bvh(adypt_ctx *ctx, const adypt_bvh_params *params, adypt_rebuild_info *out);
+/* The same rebuild with a better binary tree: PLOC (parallel locally-ordered clustering) instead of the radix tree.  Keys and sort stay; then, in
+ * rounds, every cluster looks `radius` clusters to either side in Morton order for the one whose union with it has the smallest surface area, two
+ * clusters that choose each other merge, and the list is compacted by a scan — until one cluster, the root, is left.  The host reads 8 bytes per round
+ * (some tens of rounds).  The cut, the layout and the boxes are adypt_rebuild_bvh's.  The definition is csrc/device/ploc.hpp, which the host's
+ * adypt_bvh_build_ploc (adypt_host.h) compiles too: the arrays afterwards equal that function's byte for byte.  radius is in [1, 32]; 8 is what the
+ * callers default to.  binary_depth is the PLOC tree's.  Everything else — params, the state of the context afterwards, `levels` — is as for
+ * adypt_rebuild_bvh.  ADYPT_E_INVALID (a radius out of range, bad costs, a triangle whose box has no finite area, a round that merges nothing because
+ * areas overflow) and ADYPT_E_OOM leave the old tree in place and usable.
+ * Memory: adypt_rebuild_bvh's scratch without its 4 B per triangle of counters, and 28 B per triangle more (two cluster lists 8, the choices 4, the
+ * marks and their scan 16); the scan's temporary storage shares the sort's. */
+int adypt_rebuild_bvh_ploc(adypt_ctx *ctx, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out);
 /* HIP-event times of the last adypt_rebuild_bvh in ms: [0] centroid box and keys, [1] sort, [2] radix tree, [3] bottom-up pass, [4] emission (with its
- * one small read per level), [5] Woop data and node records, [6] all of it.  Returns the number of entries and writes them only when capacity holds
- * them all. */
+ * one small read per level), [5] Woop data and node records, [6] all of it.  After adypt_rebuild_bvh_ploc [2] is all PLOC rounds (with their one small
+ * read each) and [3] is 0.  Returns the number of entries and writes them only when capacity holds them all. */
 int adypt_get_rebuild_timing(adypt_ctx *ctx, float *ms, int capacity);
 /* the sizes of the tree the context holds now; either pointer may be NULL */
 int adypt_get_bvh_sizes(adypt_ctx *ctx, int64_t *n_nodes, int64_t *n_refs);
@@ -448,6 +459,7 @@ int adypt_multi_read_denoise_guides(adypt_multi *m, float *albedo, float *normal
 int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals);
 /* adypt_rebuild_bvh on every device: every device rebuilds its own copy, and all get the same bytes; no collective.  *out: the last device's. */
 int adypt_multi_rebuild_bvh(adypt_multi *m, const adypt_bvh_params *params, adypt_rebuild_info *out);
+int adypt_multi_rebuild_bvh_ploc(adypt_multi *m, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out); /* likewise */
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

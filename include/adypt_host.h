@@ -88,6 +88,16 @@ int adypt_bvh_build(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh *
 int adypt_bvh_build_linear(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, adypt_build_info *info);
 /* the sorted keys adypt_bvh_build_linear makes of n_tris 100-byte triangle records: Morton code << 32 | triangle index, ascending (for tests and tools) */
 int adypt_lbvh_keys(const void *tris, int64_t n_tris, uint64_t *out);
+/* A CWBVH8 from the same keys and the same sort, but with the binary tree built bottom up by PLOC (parallel locally-ordered clustering): in rounds,
+ * every cluster looks `radius` clusters to either side in Morton order for the one whose union with it has the smallest area, and two clusters that
+ * choose each other merge.  The definition is csrc/device/ploc.hpp, which the device builder (adypt_hip.h, adypt_rebuild_bvh_ploc) compiles too: both
+ * give the same bytes.  Collapse, layout and boxes are adypt_bvh_build_linear's, and so are the arguments and `info`; radius is in [1, 32], 8 is the
+ * default of the callers.  The tree does not depend on adypt_host_set_threads.  ADYPT_E_INVALID also for a triangle whose box has no finite area and
+ * for a round that merges nothing (areas that overflow).  A tighter tree than the linear one on meshes (Rebuilding on the GPU). */
+int adypt_bvh_build_ploc(const adypt_scene *s, const adypt_bvh_params *p, int radius, adypt_bvh **out, adypt_build_info *info);
+/* the binary tree adypt_bvh_build_ploc makes of n_tris 100-byte triangle records, in the node ids of csrc/device/lbvh.hpp: left[i] and right[i] are
+ * the children of inner node i (n_tris - 1 entries each; the root is 0; the leaf of sorted position j is n_tris - 1 + j).  For tests and tools. */
+int adypt_ploc_tree(const void *tris, int64_t n_tris, int radius, int32_t *left, int32_t *right);
 int adypt_bvh_load(const char *path, const adypt_bvh_params *expected, adypt_bvh **out);  /* WideBVH::LoadFromFile */
 int adypt_bvh_save(const adypt_bvh *b, const char *path, const adypt_bvh_params *p);       /* WideBVH::SaveToFile */
 void adypt_bvh_free(adypt_bvh *b);

@@ -203,9 +203,12 @@ public:
 	// A new BVH for the triangles as UpdateTriangles left them, built on every device from its own copy (adypt_hip.h, adypt_rebuild_bvh): no upload, no new
 	// context.  The SAH costs are the BVH section's of the config (nullptr: its defaults).  *info: sizes, the levels of the wide tree — what stackSize has
 	// to cover — and the depth of the binary tree.  The sample counter restarts as after a Trace(false).
-	bool RebuildBVH(const adypt_bvh_params *params = nullptr, adypt_rebuild_info *info = nullptr)
+	// method Linear (the default): the linear tree, as ever.  PLOC: the binary tree is built by PLOC with search radius `radius`, 1 .. 32
+	// (adypt_rebuild_bvh_ploc) — a tighter tree on meshes for a few times the build time (Rebuilding on the GPU).
+	enum class RebuildMethod { Linear, PLOC };
+	bool RebuildBVH(const adypt_bvh_params *params = nullptr, adypt_rebuild_info *info = nullptr, RebuildMethod method = RebuildMethod::Linear, int radius = 8)
 	{
-		if(adypt_multi_rebuild_bvh(m_gpus, params, info) == ADYPT_OK) return true;
+		if((method == RebuildMethod::PLOC ? adypt_multi_rebuild_bvh_ploc(m_gpus, params, radius, info) : adypt_multi_rebuild_bvh(m_gpus, params, info)) == ADYPT_OK) return true;
 		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
 		return false;
 	}

@@ -1,15 +1,16 @@
 """What a new tree for a moved scene costs on the GPU, next to the host's way, and what the three trees are worth afterwards (DESIGN.md §4 "Rebuilding on
 the GPU"; writes profiles/rebuild_cost.txt).
 
-    python tools/rebuild_cost.py [--scene sponza] [--steps 256] [--repeats 5] [--out profiles/rebuild_cost.txt] [--append]
+    python tools/rebuild_cost.py [--scene sponza] [--method linear|ploc [--radius 8]] [--steps 256] [--repeats 5] [--out profiles/rebuild_cost.txt] [--append]
 
 One process, the scene at 1920 x 1080 with bench.py's settings, in the wave pose of the tests (y += 1.5 sin(0.7 x) + 0.8 cos(0.9 z); x *= 1.1).  Three
 contexts are held side by side:
     refitted   the config's tree (spatial splits), UpdateTriangles to the pose
-    rebuilt    the same, then RebuildBVH: the linear tree built on the GPU
+    rebuilt    the same, then RebuildBVH: the linear tree (--method linear) or the PLOC tree (--method ploc) built on the GPU
     sbvh       adypt_bvh_build of the moved triangles + adypt_create: the parent commit's only way to a new tree
   1. `repeats` times: one RebuildBVH (HIP-event parts and the host clock around the call), and adypt_bvh_build + adypt_create (host clock).
-  2. The device's arrays after the rebuild against WideBVH.BuildLinear of the moved triangles (skipped above 2 M triangles: the host build is slow).
+  2. The device's arrays after the rebuild against WideBVH.BuildLinear / BuildPLOC of the moved triangles (skipped above 2 M triangles: the host build is
+     slow).  (The rounds a PLOC tree takes are counted without a GPU by tools/tree_quality.py.)
   3. Windows of Trace(True, steps) after a warm-up, the three contexts alternating, `repeats` times.
 A step that fails ends the run: nothing more is started on the GPU."""
 import argparse
@@ -50,6 +51,8 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--steps", type=int, default=256)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--method", choices=("linear", "ploc"), default="linear")
+    ap.add_argument("--radius", type=int, default=8, help="the search radius of --method ploc")
     ap.add_argument("--cache", default=os.environ.get("ADYPT_CACHE") or os.path.join(ROOT, ".adypt_cache"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rebuild_cost.txt"))
     ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it (a second scene)")
@@ -75,7 +78,9 @@ def main():
     pos = moved["p"].reshape(-1, 9)
     a.m_path_tracer.UpdateTriangles(0, pos)
     b.m_path_tracer.UpdateTriangles(0, pos)
-    info = b.m_path_tracer.RebuildBVH(cfg.bvh_params())  # untimed: the scratch is allocated, the code object is loaded
+    how = dict(method=args.method, radius=args.radius)
+    label = "linear tree" if args.method == "linear" else "PLOC tree, radius %d" % args.radius
+    info = b.m_path_tracer.RebuildBVH(cfg.bvh_params(), **how)  # untimed: the scratch is allocated, the code object is loaded
 
     def host_way():
         t0 = time.perf_counter()
@@ -97,7 +102,7 @@ def main():
     rebuild, host, sbvh = [], [], None
     for _ in range(args.repeats):
         t0 = time.perf_counter()
-        b.m_path_tracer.RebuildBVH(cfg.bvh_params())
+        b.m_path_tracer.RebuildBVH(cfg.bvh_params(), **how)
         ms = (time.perf_counter() - t0) * 1e3
         t = b.m_path_tracer.GetRebuildTiming()
         rebuild.append([ms] + [t[k] for k in PARTS])
@@ -109,14 +114,18 @@ def main():
     if len(rest) <= 2000000:
         plain = api.Scene.FromArrays(moved, a.scene.materials)
         lin = api.WideBVH()
-        lin.BuildLinear(plain, cfg.bvh_params())
+        if args.method == "ploc":
+            lin.BuildPLOC(plain, cfg.bvh_params(), args.radius)
+        else:
+            lin.BuildLinear(plain, cfg.bvh_params())
         nodes, woop = b.m_path_tracer.ReadBVH()
         want = api.woop_matrices(moved, lin.tri_indices)
         nan = np.isnan(want)
         same = (np.array_equal(nodes, lin.nodes) and np.array_equal(b.m_path_tracer.ReadTriIndices(), lin.tri_indices) and np.array_equal(np.isnan(woop), nan)
                 and np.array_equal(woop.view(np.uint32)[~nan], want.view(np.uint32)[~nan]))
-        assert same, "the device's tree is not the host's linear tree"
-        verdict = "equal WideBVH.BuildLinear + woop_matrices of the moved triangles byte for byte (host: %.0f ms tree, %.0f ms collapse and boxes)" % (lin.build_info.sbvh_ms, lin.build_info.wide_ms)
+        assert same, "the device's tree is not the host's (%s)" % label
+        verdict = "equal WideBVH.%s + woop_matrices of the moved triangles byte for byte (host: %.0f ms tree, %.0f ms collapse and boxes)" % (
+            "BuildPLOC" if args.method == "ploc" else "BuildLinear", lin.build_info.sbvh_ms, lin.build_info.wide_ms)
 
     def window(p):
         p.Reset()
@@ -125,7 +134,7 @@ def main():
         p.Trace(True, args.steps)
         return (time.perf_counter() - t0) * 1e3
 
-    tracers = (("refitted tree (splits, refit to the pose)", a.m_path_tracer), ("rebuilt on the GPU (linear tree)", b.m_path_tracer), ("SBVH built on the host for the pose", sbvh[0]))
+    tracers = (("refitted tree (splits, refit to the pose)", a.m_path_tracer), ("rebuilt on the GPU (%s)" % label, b.m_path_tracer), ("SBVH built on the host for the pose", sbvh[0]))
     rate = {name: [] for name, _ in tracers}
     for _, p in tracers:
         window(p)
@@ -134,12 +143,12 @@ def main():
             rate[name].append(window(p))
     lines = ["Cost of a new tree in the wave pose: %s (%d triangles), %d x %d, %d bounces; %d repeats, the variants alternating in one run." % (
                  args.scene, len(rest), args.width, args.height, PT_CFG["maxBounce"], args.repeats),
-             "config's tree: %d nodes, %d references; rebuilt on the GPU: %d nodes, %d references, %d levels, binary depth %d; SBVH for the pose: %d nodes, %d references" % (
-                 len(a.bvh.nodes) // 80, len(a.bvh.tri_indices), info["n_nodes"], info["n_refs"], info["levels"], info["binary_depth"], sbvh[3], sbvh[4]),
+             "config's tree: %d nodes, %d references; rebuilt on the GPU (%s): %d nodes, %d references, %d levels, binary depth %d; SBVH for the pose: %d nodes, %d references" % (
+                 len(a.bvh.nodes) // 80, len(a.bvh.tri_indices), label, info["n_nodes"], info["n_refs"], info["levels"], info["binary_depth"], sbvh[3], sbvh[4]),
              "After RebuildBVH the device's node, index and Woop arrays " + verdict + ".", ""]
-    lines += table("One RebuildBVH (HIP events; the first row is the host clock around the call, allocation of the new arrays and one 4-byte read per level in it):",
-                   ["host clock", "centroid box + keys", "sort (rocPRIM, 62 bits)", "radix tree", "bottom-up (boxes, counts, DP)", "emission (every level)", "Woop + node records",
-                    "device total"], rebuild)
+    tree_rows = ["radix tree", "bottom-up (boxes, counts, DP)"] if args.method == "linear" else ["PLOC rounds (tree, boxes, counts, DP; one 8-byte read each)", "(no pass of its own)"]
+    lines += table("One RebuildBVH, " + label + " (HIP events; the first row is the host clock around the call, allocation of the new arrays and one 4-byte read per level in it):",
+                   ["host clock", "centroid box + keys", "sort (rocPRIM, 62 bits)"] + tree_rows + ["emission (every level)", "Woop + node records", "device total"], rebuild)
     lines += [""] + table("The parent commit's way to a new tree (host clock):", ["adypt_bvh_build", "adypt_create"], host)
     both = statistics.median(r[0] + r[1] for r in host)
     lines += ["build + create, median of the sums: %.1f ms = %.1f x RebuildBVH's host clock" % (both, both / statistics.median(r[0] for r in rebuild)), ""]
