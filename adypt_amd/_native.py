@@ -179,6 +179,10 @@ _SIGS = {
     "adypt_rebuild_bvh_ploc": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.POINTER(RebuildInfo)]),
     "adypt_multi_rebuild_bvh": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(RebuildInfo)]),
     "adypt_multi_rebuild_bvh_ploc": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.POINTER(RebuildInfo)]),
+    "adypt_rebuild_bvh_ploc_split": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.c_double, C.POINTER(RebuildInfo)]),
+    "adypt_multi_rebuild_bvh_ploc_split": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.c_double, C.POINTER(RebuildInfo)]),
+    "adypt_get_rebuild_presplit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "adypt_read_ref_boxes": (C.c_int64, [C.c_void_p, C.c_void_p]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),
@@ -235,6 +239,9 @@ _SIGS = {
     "adypt_lbvh_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "adypt_bvh_build_ploc": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.POINTER(C.c_void_p), C.POINTER(BuildInfo)]),
     "adypt_ploc_tree": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "adypt_bvh_build_ploc_split": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.c_double, C.POINTER(C.c_void_p), C.POINTER(BuildInfo)]),
+    "adypt_bvh_ref_boxes": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "adypt_presplit_refs": (C.c_int64, [C.c_void_p, C.c_int64, C.c_double, C.c_int64, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "adypt_bvh_load": (C.c_int, [C.c_char_p, C.POINTER(BvhParams), C.POINTER(C.c_void_p)]),
     "adypt_bvh_save": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(BvhParams)]),
     "adypt_bvh_free": (None, [C.c_void_p]),

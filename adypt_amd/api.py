@@ -158,6 +158,7 @@ class WideBVH:
         self._h = C.c_void_p()
         self.nodes = np.zeros(0, dtype=np.uint8)
         self.tri_indices = np.zeros(0, dtype=np.int32)
+        self.ref_boxes = np.zeros((0, 6), dtype=np.float32)  # of a tree with split triangles (BuildPLOC(split_budget=...)): lo xyz, hi xyz per reference
         self.build_info: Optional[N.BuildInfo] = None
 
     def _pull(self) -> None:
@@ -166,6 +167,8 @@ class WideBVH:
         self.nodes = _bytes_view(p.value, n * NODE_BYTES)
         n = N.lib.adypt_bvh_tri_indices(self._h, C.byref(p))
         self.tri_indices = _bytes_view(p.value, n * 4).view(np.int32)
+        n = N.lib.adypt_bvh_ref_boxes(self._h, C.byref(p))
+        self.ref_boxes = _bytes_view(p.value, n * 24).view(np.float32).reshape(-1, 6) if n else np.zeros((0, 6), dtype=np.float32)
 
     def LoadFromFile(self, filename: str, expected: N.BvhParams) -> bool:
         self._free()
@@ -194,12 +197,17 @@ class WideBVH:
         self.build_info = info
         self._pull()
 
-    def BuildPLOC(self, scene: Scene, cfg: N.BvhParams, radius: int = 8) -> None:
+    def BuildPLOC(self, scene: Scene, cfg: N.BvhParams, radius: int = 8, split_budget: float = 0.0) -> None:
         """adypt_bvh_build_ploc: BuildLinear with the binary tree built bottom up by PLOC (csrc/device/ploc.hpp) — what RebuildBVH(method="ploc") builds
-        on the GPU, byte for byte.  radius in [1, 32]: how far a cluster looks to either side in Morton order."""
+        on the GPU, byte for byte.  radius in [1, 32]: how far a cluster looks to either side in Morton order.  split_budget in [0, 1]
+        (adypt_bvh_build_ploc_split, csrc/device/presplit.hpp): large triangles become several references with clipped boxes, at most
+        split_budget * n more references than triangles; their boxes are ref_boxes.  0: no splits, the same bytes as ever."""
         self._free()
         info = N.BuildInfo()
-        N.check_host(N.lib.adypt_bvh_build_ploc(scene._h, C.byref(cfg), radius, C.byref(self._h), C.byref(info)))
+        if split_budget == 0.0:
+            N.check_host(N.lib.adypt_bvh_build_ploc(scene._h, C.byref(cfg), radius, C.byref(self._h), C.byref(info)))
+        else:
+            N.check_host(N.lib.adypt_bvh_build_ploc_split(scene._h, C.byref(cfg), radius, float(split_budget), C.byref(self._h), C.byref(info)))
         self.build_info = info
         self._pull()
 
@@ -595,16 +603,22 @@ class _Tracer:
         return nodes, woop
 
     # ---- rebuilding the tree on the GPU (adypt_rebuild_bvh, include/adypt_hip.h; the definition: csrc/device/lbvh.hpp) ----
-    def RebuildBVH(self, cfg: Optional[N.BvhParams] = None, method: str = "linear", radius: int = 8) -> dict:
+    def RebuildBVH(self, cfg: Optional[N.BvhParams] = None, method: str = "linear", radius: int = 8, split_budget: float = 0.0) -> dict:
         """A new tree, built on the GPU from the triangles as UpdateTriangles() left them.  method "linear": WideBVH.BuildLinear's bytes; "ploc": those
         of WideBVH.BuildPLOC(radius=radius) — a tighter tree on meshes for a few times the build time (csrc/device/ploc.hpp); radius counts for "ploc"
-        only.  Leaves the tracer as Reset() does (0 spp).  Several devices: on every device.  Returns n_nodes, n_refs, levels (size stack_size by it)
+        only.  split_budget in [0, 1], for "ploc" only: large triangles are split into several references first, at most split_budget * n more than
+        triangles (csrc/device/presplit.hpp; WideBVH.BuildPLOC(split_budget=...)'s bytes; GetRebuildPresplit(), ReadRefBoxes()) — for scenes with
+        large triangles among small ones; rebuild such a tree for a new pose rather than refitting it.  Leaves the tracer as Reset() does (0 spp).  Several devices: on every device.  Returns n_nodes, n_refs, levels (size stack_size by it)
         and binary_depth."""
         if method not in ("linear", "ploc"):
             raise ValueError("RebuildBVH: method must be 'linear' or 'ploc', not %r" % (method,))
+        if split_budget != 0.0 and method != "ploc":
+            raise ValueError("RebuildBVH: split_budget needs method 'ploc'")
         info = N.RebuildInfo()
         params = None if cfg is None else C.byref(cfg)
-        if method == "ploc":
+        if method == "ploc" and split_budget != 0.0:
+            self._call("rebuild_bvh_ploc_split", params, int(radius), float(split_budget), C.byref(info))
+        elif method == "ploc":
             self._call("rebuild_bvh_ploc", params, int(radius), C.byref(info))
         else:
             self._call("rebuild_bvh", params, C.byref(info))
@@ -623,6 +637,28 @@ class _Tracer:
         c = self._contexts()[0]
         N.check(N.lib.adypt_read_tri_indices(c, idx.ctypes.data), c)
         return idx[:self.GetBVHSizes()[1]]
+
+    def GetRebuildPresplit(self) -> Tuple[int, int]:
+        """(the level of detail the last RebuildBVH() chose, -1 for none; the triangles it split) on the (first) device."""
+        out = (C.c_int32 * 2)()
+        c = self._contexts()[0]
+        N.check(N.lib.adypt_get_rebuild_presplit(c, out), c)
+        return out[0], out[1]
+
+    def ReadRefBoxes(self) -> Optional[np.ndarray]:
+        """The reference boxes (float32 [n_refs, 6]: lo xyz, hi xyz) of a tree rebuilt with split_budget as they are on the (first) device, in the
+        order of ReadTriIndices(); None when the tree has none (not built with splits, or refitted since)."""
+        c = self._contexts()[0]
+        n = N.lib.adypt_read_ref_boxes(c, None)
+        if n < 0:
+            N.check(int(n), c)
+        if n == 0:
+            return None
+        out = np.zeros((n, 6), dtype=np.float32)
+        n = N.lib.adypt_read_ref_boxes(c, out.ctypes.data)
+        if n < 0:
+            N.check(int(n), c)
+        return out
 
     def GetRebuildTiming(self) -> dict:
         """HIP-event milliseconds of the last RebuildBVH() on the (first) device.  After method "ploc": "tree" is all the rounds, "bottom_up" is 0."""

@@ -5,13 +5,15 @@
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
 //             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild]
-//             [--rebuild-method linear|ploc [--ploc-radius R]]
+//             [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]]
 //   --pose moved.obj: the scene of the config (and its cached .bvh) with the vertices and normals of moved.obj — the same triangles in the same order,
 //              moved — through adypt_multi_update_triangles: the BVH and the Woop data are refitted on the GPU, nothing is rebuilt
 //   --rebuild: a new tree for the triangles as they are then (after --pose, when given), built on the GPU through adypt_multi_rebuild_bvh with the config's
 //              SAH costs
 //   --rebuild-method ploc: the same with the binary tree built by PLOC (adypt_multi_rebuild_bvh_ploc; --ploc-radius R, 1 to 32, 8 unless given) — a tighter
 //              tree for a few times the build time; linear (the default) is --rebuild's tree.  Naming a method asks for the rebuild
+//   --split-budget B: with --rebuild-method ploc only (else exit 2): large triangles are split into several references first, at most B * n more than
+//              triangles, B in [0, 1] (adypt_multi_rebuild_bvh_ploc_split)
 //   --sun-visibility: enable the occlusion query the reference has commented out (pathtracer.glsl:132)
 //   --preview: what the reference shows in its window (shaders/screen.glsl), as PNG
 //   --devices: pixel tiles sharded over several GPUs of the node (adypt_create_multi), radiance gathered on the first one
@@ -43,12 +45,14 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R]]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
 	std::string noise_out, spp_out, denoise_out, guides_out, pose;
 	bool rebuild = false;
 	std::string rebuild_method = "linear";
+	double split_budget = 0.0;
+	bool have_split_budget = false;
 	int ploc_radius = 8;
 	int denoise_levels = 5;
 	int adaptive = 0;
@@ -96,10 +100,12 @@ int main(int argc, char **argv)
 		else if(a == "--rebuild") rebuild = true;
 		else if(a == "--rebuild-method" && i + 1 < argc) { rebuild_method = argv[++i]; rebuild = true; }
 		else if(a == "--ploc-radius" && i + 1 < argc) ploc_radius = atoi(argv[++i]);
+		else if(a == "--split-budget" && i + 1 < argc) { split_budget = atof(argv[++i]); have_split_budget = true; }
 		else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
 	}
 	const bool until = noise_target >= 0.0;
 	if(rebuild_method != "linear" && rebuild_method != "ploc") { fprintf(stderr, "--rebuild-method is linear or ploc\n"); return 2; }
+	if(have_split_budget && rebuild_method != "ploc") { fprintf(stderr, "--split-budget needs --rebuild-method ploc\n"); return 2; }
 	if(!until && !noise_out.empty()) { fprintf(stderr, "--noise-out needs --noise T\n"); return 2; }
 	if(until && (primary >= 0 || spp < 2 || check_every < 1)) { fprintf(stderr, "--noise needs --spp >= 2, --check-every >= 1 and no --primary\n"); return 2; }
 	if(adaptive && (!until || save_every > 0)) { fprintf(stderr, "--adaptive needs --noise T and does not combine with --save-every\n"); return 2; }
@@ -185,10 +191,21 @@ int main(int argc, char **argv)
 	{
 		adypt_rebuild_info info;
 		const bool ploc = rebuild_method == "ploc";
-		if((ploc ? adypt_multi_rebuild_bvh_ploc(multi, &cfg.bvh, ploc_radius, &info) : adypt_multi_rebuild_bvh(multi, &cfg.bvh, &info)) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		const int code = have_split_budget ? adypt_multi_rebuild_bvh_ploc_split(multi, &cfg.bvh, ploc_radius, split_budget, &info)
+		                 : ploc            ? adypt_multi_rebuild_bvh_ploc(multi, &cfg.bvh, ploc_radius, &info)
+		                                   : adypt_multi_rebuild_bvh(multi, &cfg.bvh, &info);
+		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
 		float ms[7] = {0, 0, 0, 0, 0, 0, 0};
 		(void)adypt_get_rebuild_timing(adypt_multi_context(multi, 0), ms, 7);
-		const std::string method = ploc ? "ploc radius " + std::to_string(ploc_radius) : "linear";
+		std::string method = ploc ? "ploc radius " + std::to_string(ploc_radius) : "linear";
+		if(have_split_budget)
+		{
+			int32_t presplit[2] = {-1, 0};
+			(void)adypt_get_rebuild_presplit(adypt_multi_context(multi, 0), presplit);
+			char text[64];
+			snprintf(text, sizeof(text), " split budget %g level %d", split_budget, (int)presplit[0]);
+			method += text;
+		}
 		printf("[PT]INFO: rebuild: %lld nodes, %lld references, %d levels, method %s, %.3f ms (keys %.3f, sort %.3f, tree %.3f, bottom-up %.3f, emission %.3f, Woop and nodes %.3f)\n", (long long)info.n_nodes,
 		       (long long)info.n_refs, (int)info.levels, method.c_str(), ms[6], ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
 	}

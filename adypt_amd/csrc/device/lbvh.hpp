@@ -42,13 +42,18 @@ ADYPT_HOST_DEVICE uint32_t lbvh_spread(uint32_t v)
 	v = (v | (v << 2)) & 0x09249249u;
 	return v;
 }
-// box: the centroid box
-ADYPT_HOST_DEVICE uint64_t lbvh_key(const float *p, const RefitBox &box, uint32_t index)
+// c: a centroid; box: the centroid box
+ADYPT_HOST_DEVICE uint64_t lbvh_key_of(const float *c, const RefitBox &box, uint32_t index)
 {
 	uint32_t cell[3];
-	for(int k = 0; k < 3; ++k) cell[k] = lbvh_cell(lbvh_centroid(p, k), box.lo[k], box.hi[k]);
+	for(int k = 0; k < 3; ++k) cell[k] = lbvh_cell(c[k], box.lo[k], box.hi[k]);
 	const uint32_t code = lbvh_spread(cell[0]) << 2 | lbvh_spread(cell[1]) << 1 | lbvh_spread(cell[2]);
 	return (uint64_t)code << 32 | index;
+}
+ADYPT_HOST_DEVICE uint64_t lbvh_key(const float *p, const RefitBox &box, uint32_t index)
+{
+	const float c[3] = {lbvh_centroid(p, 0), lbvh_centroid(p, 1), lbvh_centroid(p, 2)};
+	return lbvh_key_of(c, box, index);
 }
 
 ADYPT_HOST_DEVICE int lbvh_delta(const uint64_t *keys, int64_t n, int64_t i, int64_t j)
@@ -88,8 +93,10 @@ struct WideItem { int32_t w, s; uint32_t node_base, tri_base; };
 
 // Tree: wide_cut.hpp's, and   bool is_leaf(int n), int32_t tri(int leaf), int tri_count(int n), void box(int n, float lo[3], float hi[3]).
 // rec: the node's 80 bytes as 20 words; tri_indices: the whole reference array of ref_limit entries (nothing is written beyond: counts that disagree
-// must not turn into a stray store); kids: the inner children in gather order.  Returns their number.
-template <class Tree> ADYPT_HOST_DEVICE int lbvh_emit_node(const Tree &t, const WideItem &it, uint32_t rec[20], int32_t *tri_indices, uint32_t ref_limit, WideItem kids[8])
+// must not turn into a stray store); kids: the inner children in gather order.  Returns their number.  Placed:  void operator()(const Tree &, uint32_t
+// position, int leaf)  is told which binary leaf went to which position of tri_indices (a tree with several references per triangle: presplit.hpp).
+struct LbvhNobody { template <class Tree> ADYPT_HOST_DEVICE void operator()(const Tree &, uint32_t, int) const {} };
+template <class Tree, class Placed> ADYPT_HOST_DEVICE int lbvh_emit_node(const Tree &t, const WideItem &it, uint32_t rec[20], int32_t *tri_indices, uint32_t ref_limit, WideItem kids[8], const Placed &placed)
 {
 	int child[8], n_child = 0;
 	if(t.is_leaf(it.s)) child[n_child++] = it.s; // the one-triangle scene: the root gets that leaf as its only child
@@ -127,7 +134,7 @@ template <class Tree> ADYPT_HOST_DEVICE int lbvh_emit_node(const Tree &t, const 
 			while(sp)
 			{
 				const int b = st[--sp];
-				if(t.is_leaf(b)) { if(tri_at < ref_limit) tri_indices[tri_at] = t.tri(b); ++tri_at; ++cnt; }
+				if(t.is_leaf(b)) { if(tri_at < ref_limit) { tri_indices[tri_at] = t.tri(b); placed(t, tri_at, b); } ++tri_at; ++cnt; }
 				else if(sp <= 6) { st[sp++] = t.left(b); st[sp++] = t.right(b); }
 			}
 			meta[i] = (cnt == 1 ? 0x20u : cnt == 2 ? 0x60u : 0xe0u) | off;
@@ -156,6 +163,10 @@ template <class Tree> ADYPT_HOST_DEVICE int lbvh_emit_node(const Tree &t, const 
 		tri_at += (uint32_t)t.tri_count(child[i]);
 	}
 	return n_kids;
+}
+template <class Tree> ADYPT_HOST_DEVICE int lbvh_emit_node(const Tree &t, const WideItem &it, uint32_t rec[20], int32_t *tri_indices, uint32_t ref_limit, WideItem kids[8])
+{
+	return lbvh_emit_node(t, it, rec, tri_indices, ref_limit, kids, LbvhNobody{});
 }
 
 }  // namespace adypt

@@ -60,9 +60,10 @@ __global__ __launch_bounds__(kRefitThreads) void k_refit_woop(const float4 *tria
 // The nodes level[0 .. n_level) of one level.  Lane s of a node's 8 lanes owns slot s: it finds the slot's exact box (a child's from `boxes`, a leaf's from
 // its triangles), the 8 boxes are united by three xor-shuffle steps (refit_min / refit_max do not depend on the order: every lane ends with the same
 // bits), every lane quantises its own slot.  The record is assembled in LDS — the old record first, so that the bytes of empty slots and the fields
-// that stay need no special case — and goes back with five 16-byte stores.
-__global__ __launch_bounds__(kRefitThreads) void k_refit_nodes(uint4 *nodes, float4 *boxes, const int32_t *level, int n_level, const int32_t *tri_indices, const float4 *triangles,
-                                                              int tri_float4)
+// that stay need no special case — and goes back with five 16-byte stores.  REF_BOXES: a reference's box is ref_boxes' (a tree with split triangles,
+// presplit.hpp), not its whole triangle's; without it the kernel is what it was before there were such trees.
+template <bool REF_BOXES> __global__ __launch_bounds__(kRefitThreads) void k_refit_nodes(uint4 *nodes, float4 *boxes, const int32_t *level, int n_level, const int32_t *tri_indices, const float4 *triangles,
+                                                                                        int tri_float4, const float4 *ref_boxes)
 {
 	__shared__ uint4 s_node[kNodesPerGroup][kNodeUint4];
 	const int g = threadIdx.x / kLanesPerNode, s = threadIdx.x % kLanesPerNode;
@@ -91,6 +92,13 @@ __global__ __launch_bounds__(kRefitThreads) void k_refit_nodes(uint4 *nodes, flo
 			const int count = refit_leaf_count(meta);
 			for(int r = 0; r < count; ++r)
 			{
+				if(REF_BOXES)
+				{
+					const size_t at = (size_t)tri_base + refit_leaf_offset(meta) + (size_t)r;
+					const float4 lo = ref_boxes[at * 2], hi = ref_boxes[at * 2 + 1];
+					mine = refit_union(mine, RefitBox{{lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z}});
+					continue;
+				}
 				const float4 *rec = triangles + (size_t)tri_indices[(size_t)tri_base + refit_leaf_offset(meta) + (size_t)r] * (size_t)tri_float4;
 				float p[9];
 				load_positions(rec, p);
@@ -172,13 +180,14 @@ hipError_t refit_launch_woop(hipStream_t stream, const float4 *triangles, int tr
 	return hipGetLastError();
 }
 
-hipError_t refit_launch_levels(hipStream_t stream, const TreeLevels &tree, uint4 *nodes, const int32_t *tri_indices, const float4 *triangles, int tri_float4)
+hipError_t refit_launch_levels(hipStream_t stream, const TreeLevels &tree, uint4 *nodes, const int32_t *tri_indices, const float4 *triangles, int tri_float4, const float4 *ref_boxes)
 {
 	for(int l = tree.levels() - 1; l >= 0; --l)
 	{
 		const int64_t begin = tree.level_begin[(size_t)l], n = tree.level_begin[(size_t)l + 1] - begin;
 		if(n <= 0) continue;
-		hipLaunchKernelGGL(k_refit_nodes, dim3(grid_of(n, kNodesPerGroup)), dim3(kRefitThreads), 0, stream, nodes, tree.boxes.get(), (const int32_t *)tree.order + begin, (int)n, tri_indices, triangles, tri_float4);
+		if(ref_boxes) hipLaunchKernelGGL(k_refit_nodes<true>, dim3(grid_of(n, kNodesPerGroup)), dim3(kRefitThreads), 0, stream, nodes, tree.boxes.get(), (const int32_t *)tree.order + begin, (int)n, tri_indices, triangles, tri_float4, ref_boxes);
+		else hipLaunchKernelGGL(k_refit_nodes<false>, dim3(grid_of(n, kNodesPerGroup)), dim3(kRefitThreads), 0, stream, nodes, tree.boxes.get(), (const int32_t *)tree.order + begin, (int)n, tri_indices, triangles, tri_float4, ref_boxes);
 		const hipError_t e = hipGetLastError();
 		if(e != hipSuccess) return e;
 	}
@@ -208,6 +217,7 @@ int adypt_update_triangles(adypt_ctx *c, int64_t first, int64_t count, const flo
 	const CtxInfo i = ctx_info(c);
 	Refitter *rf = ctx_state<Refitter>(c, kAttachRefit);
 	CTX_STEP(ensure_plan(c, rf, sc, i.stream));
+	rf->tree.ref_boxes.release(); // (a split tree's clipped boxes were the old pose's: from here on its leaves bound whole triangles, as an SBVH tree's do)
 	const size_t n_stage = (size_t)count * 9;
 	CTX_TRY(c, at_least(rf->d_stage, n_stage * (normals ? 2 : 1)));
 	rf->timer.invalidate();
@@ -241,6 +251,27 @@ int adypt_read_bvh(adypt_ctx *c, void *nodes_out, float *woop_out)
 	if(nodes_out) CTX_TRY(c, hipMemcpy(nodes_out, sc.nodes, (size_t)sc.n_nodes * kNodeBytes, hipMemcpyDeviceToHost));
 	if(woop_out && sc.n_refs > 0) CTX_TRY(c, hipMemcpy(woop_out, sc.woop, (size_t)sc.n_refs * 12 * sizeof(float), hipMemcpyDeviceToHost));
 	return ADYPT_OK;
+}
+
+int64_t adypt_read_ref_boxes(adypt_ctx *c, float *out)
+{
+	if(!c) return ADYPT_E_INVALID;
+	const CtxScene sc = ctx_scene(c);
+	const CtxInfo i = ctx_info(c);
+	const Refitter *rf = ctx_state_if_any<Refitter>(c, kAttachRefit);
+	if(!rf || !rf->tree.ref_boxes.get() || sc.n_refs <= 0) return 0;
+	if(!out) return sc.n_refs;
+	CTX_TRY(c, hipSetDevice(i.device));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
+	std::vector<float4> boxes((size_t)sc.n_refs * 2);
+	CTX_TRY(c, hipMemcpy(boxes.data(), rf->tree.ref_boxes.get(), boxes.size() * sizeof(float4), hipMemcpyDeviceToHost));
+	for(int64_t r = 0; r < sc.n_refs; ++r)
+	{
+		const float4 lo = boxes[(size_t)r * 2], hi = boxes[(size_t)r * 2 + 1];
+		float *o = out + r * 6;
+		o[0] = lo.x; o[1] = lo.y; o[2] = lo.z; o[3] = hi.x; o[4] = hi.y; o[5] = hi.z;
+	}
+	return sc.n_refs;
 }
 
 int adypt_get_refit_timing(adypt_ctx *c, float *ms, int capacity)

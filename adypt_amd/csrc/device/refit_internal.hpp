@@ -22,13 +22,16 @@ struct TreeLevels {
 	std::vector<int64_t> level_begin; // levels + 1 entries
 	Buffer<int32_t> order;            // device: 4 B per node
 	Buffer<float4> boxes;             // device: the exact boxes, 2 float4 per node
+	Buffer<float4> ref_boxes;         // device: a tree built with split triangles (presplit.hpp) — the box of every reference, 2 float4 each, in the order of
+	                                  // tri_indices; empty for every other tree, and dropped by the first adypt_update_triangles (which bounds whole triangles)
 	int levels() const { return (int)level_begin.size() - 1; }
 };
 
 // k_refit_woop: one thread per reference
 hipError_t refit_launch_woop(hipStream_t stream, const float4 *triangles, int tri_float4, const int32_t *tri_indices, int64_t n_refs, float4 *woop);
-// k_refit_nodes once per level, deepest first: a level reads the exact boxes that the launches before it on the same stream wrote
-hipError_t refit_launch_levels(hipStream_t stream, const TreeLevels &tree, uint4 *nodes, const int32_t *tri_indices, const float4 *triangles, int tri_float4);
+// k_refit_nodes once per level, deepest first: a level reads the exact boxes that the launches before it on the same stream wrote.  ref_boxes: a leaf
+// slot bounds these boxes of its references (2 float4 per reference, in the order of tri_indices) instead of their whole triangles
+hipError_t refit_launch_levels(hipStream_t stream, const TreeLevels &tree, uint4 *nodes, const int32_t *tri_indices, const float4 *triangles, int tri_float4, const float4 *ref_boxes = nullptr);
 // The context's tree has been replaced: `tree` is taken as the refit's.  A later adypt_update_triangles refits the new topology; the timing of the last
 // update is no longer to be read.
 void refit_adopt_tree(adypt_ctx *c, TreeLevels &&tree);

@@ -1,13 +1,18 @@
 // adypt_bvh_refit (include/adypt_host.h): the boxes of a CWBVH8 recomputed for moved triangles, in place, on the host.  The rule is
 // ../device/refit.hpp, the order ../device/refit_plan.hpp — the texts the device path (refit.hip) compiles too.
-#include "common.hpp"
+#include "builders.hpp"
 #include "../device/refit_plan.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
 
 using namespace adypt;
 
-int adypt_bvh_refit(void *nodes_, int64_t n_nodes, const int32_t *tri_indices, int64_t n_refs, const void *triangles, int64_t n_tris)
+int adypt_bvh_refit(void *nodes, int64_t n_nodes, const int32_t *tri_indices, int64_t n_refs, const void *triangles, int64_t n_tris)
+{
+	return bvh_refit_boxes(nodes, n_nodes, tri_indices, n_refs, triangles, n_tris, nullptr);
+}
+
+int adypt::bvh_refit_boxes(void *nodes_, int64_t n_nodes, const int32_t *tri_indices, int64_t n_refs, const void *triangles, int64_t n_tris, const RefitBox *ref_boxes)
 {
 	if(!nodes_ || !triangles || n_nodes <= 0 || n_refs < 0 || n_tris <= 0 || (n_refs > 0 && !tri_indices)) { set_host_error("adypt_bvh_refit: null or empty argument"); return ADYPT_E_INVALID; }
 	for(int64_t r = 0; r < n_refs; ++r)
@@ -38,8 +43,10 @@ int adypt_bvh_refit(void *nodes_, int64_t n_nodes, const int32_t *tri_indices, i
 				else if(kind == kSlotLeaf)
 					for(int r = 0; r < refit_leaf_count(meta); ++r)
 					{
+						const size_t at = (size_t)tri_base + refit_leaf_offset(meta) + (size_t)r;
+						if(ref_boxes) { slot[s] = refit_union(slot[s], ref_boxes[at]); continue; }
 						float p[9];
-						memcpy(p, tris[tri_indices[(size_t)tri_base + refit_leaf_offset(meta) + (size_t)r]].p, sizeof(p));
+						memcpy(p, tris[tri_indices[at]].p, sizeof(p));
 						slot[s] = refit_union(slot[s], refit_triangle_box(p));
 					}
 				if(kind != kSlotEmpty) { box = refit_union(box, slot[s]); any = true; }

@@ -4,6 +4,7 @@
 #include "exact_sort.hpp"
 #include "../device/woop.hpp"
 #include "../device/ploc.hpp"
+#include "../device/presplit.hpp"
 #include "../../../include/adypt_hip.h"
 
 #include <algorithm>
@@ -19,6 +20,7 @@ using namespace adypt;
 struct adypt_bvh {
 	std::vector<NodeRec> nodes;
 	std::vector<int32_t> tri_indices;
+	std::vector<RefitBox> ref_boxes; // of a tree with split triangles (presplit.hpp), in the order of tri_indices; else empty
 };
 
 namespace {
@@ -300,6 +302,74 @@ int adypt_bvh_build_ploc(const adypt_scene *s, const adypt_bvh_params *p, int ra
 	const int64_t leaves = build_ploc((const TriRec *)tp, nt, radius, &bin, &depth, &tree_ms);
 	if(leaves < 0) return ADYPT_E_INVALID;
 	return collapse_unsplit(bin, leaves, *p, tp, nt, tree_ms, out, info);
+}
+
+static bool budget_ok(double b) { return b >= 0.0 && b <= 1.0; } // (false for NaN)
+
+int adypt_bvh_build_ploc_split(const adypt_scene *s, const adypt_bvh_params *p, int radius, double split_budget, adypt_bvh **out, adypt_build_info *info)
+{
+	const void *tp; int64_t nt;
+	const int r = unsplit_arguments("adypt_bvh_build_ploc_split", s, p, out, &tp, &nt);
+	if(r != ADYPT_OK) return r;
+	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) { set_host_error("adypt_bvh_build_ploc_split: the radius must be in [1, 32]"); return ADYPT_E_INVALID; }
+	if(!budget_ok(split_budget)) { set_host_error("adypt_bvh_build_ploc_split: the split budget must be in [0, 1]"); return ADYPT_E_INVALID; }
+	if(split_budget == 0.0) return adypt_bvh_build_ploc(s, p, radius, out, info);
+	const auto t0 = std::chrono::steady_clock::now();
+	PresplitRefs refs;
+	const int code = presplit_refs((const TriRec *)tp, nt, split_budget, &refs);
+	if(code != ADYPT_OK) return code;
+	if(refs.n_split == 0) return adypt_bvh_build_ploc(s, p, radius, out, info); // nothing is split: that tree, to the byte
+	const double split_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	std::vector<BinNode> bin;
+	double tree_ms = 0, wide_ms = 0;
+	int depth = 0;
+	const int64_t leaves = build_ploc_split((const TriRec *)tp, nt, radius, refs, &bin, &depth, &tree_ms);
+	if(leaves < 0) return ADYPT_E_INVALID;
+	adypt_bvh *b = new adypt_bvh();
+	build_wide_bvh(bin, leaves, *p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads());
+	for(NodeRec &n : b->nodes)
+	{
+		n.px = n.py = n.pz = 0.0f; n.ex = n.ey = n.ez = 0;
+		memset(n.qlox, 0, 48);
+	}
+	// the collapse placed references: their boxes and their triangles in that order
+	b->ref_boxes.resize(b->tri_indices.size());
+	for(size_t i = 0; i < b->tri_indices.size(); ++i)
+	{
+		const int32_t ref = b->tri_indices[i];
+		b->ref_boxes[i] = refs.box[(size_t)ref];
+		b->tri_indices[i] = refs.tri[(size_t)ref];
+	}
+	const auto t1 = std::chrono::steady_clock::now();
+	const int rr = bvh_refit_boxes(b->nodes.data(), (int64_t)b->nodes.size(), b->tri_indices.data(), (int64_t)b->tri_indices.size(), tp, nt, b->ref_boxes.data());
+	if(rr != ADYPT_OK) { delete b; return rr; }
+	wide_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+	if(info) { info->sbvh_nodes = (int64_t)bin.size(); info->refs = leaves; info->wide_nodes = (int64_t)b->nodes.size(); info->sbvh_ms = split_ms + tree_ms; info->wide_ms = wide_ms; }
+	*out = b;
+	return ADYPT_OK;
+}
+
+int64_t adypt_presplit_refs(const void *tris, int64_t n_tris, double split_budget, int64_t capacity, int32_t *level, int32_t *ref_tri, float *ref_box)
+{
+	if(!tris || n_tris <= 0 || n_tris > ((int64_t)1 << 30) || capacity < 0 || (capacity > 0 && (!ref_tri || !ref_box))) { set_host_error("adypt_presplit_refs: null or empty argument"); return ADYPT_E_INVALID; }
+	if(!budget_ok(split_budget)) { set_host_error("adypt_presplit_refs: the split budget must be in [0, 1]"); return ADYPT_E_INVALID; }
+	PresplitRefs refs;
+	const int code = presplit_refs((const TriRec *)tris, n_tris, split_budget, &refs);
+	if(code != ADYPT_OK) return code;
+	if(level) *level = refs.level;
+	const int64_t n = (int64_t)refs.tri.size();
+	if(n <= capacity)
+	{
+		memcpy(ref_tri, refs.tri.data(), (size_t)n * sizeof(int32_t));
+		memcpy(ref_box, refs.box.data(), (size_t)n * sizeof(RefitBox));
+	}
+	return n;
+}
+
+int64_t adypt_bvh_ref_boxes(const adypt_bvh *b, const float **boxes)
+{
+	if(boxes) *boxes = b->ref_boxes.empty() ? nullptr : b->ref_boxes[0].lo;
+	return (int64_t)b->ref_boxes.size();
 }
 
 int adypt_ploc_tree(const void *tris, int64_t n_tris, int radius, int32_t *left, int32_t *right)

@@ -30,7 +30,8 @@ void lbvh_sorted_keys(const TriRec *tris, int64_t n, std::vector<uint64_t> *out)
 }
 
 // a binary tree in the node ids of lbvh.hpp (left, right: n - 1 entries; the root is 0) -> pre-order with exact boxes; the PLOC tree's too (ploc_builder.cpp)
-void layout_binary_tree(const TriRec *tris, int64_t n, const std::vector<uint64_t> &keys, const std::vector<int32_t> &left, const std::vector<int32_t> &right, std::vector<BinNode> *bin, int *depth)
+void layout_binary_tree(const TriRec *tris, int64_t n, const std::vector<uint64_t> &keys, const std::vector<int32_t> &left, const std::vector<int32_t> &right, std::vector<BinNode> *bin, int *depth,
+                        const RefitBox *ref_box)
 {
 	// pre-order, right child first
 	bin->assign((size_t)(2 * n - 1), BinNode{});
@@ -50,9 +51,14 @@ void layout_binary_tree(const TriRec *tris, int64_t n, const std::vector<uint64_
 		{
 			b.tri = (int32_t)(uint32_t)keys[(size_t)(t.id - (n - 1))];
 			b.left = -1;
-			float p[9];
-			memcpy(p, tris[b.tri].p, sizeof(p));
-			const RefitBox r = refit_triangle_box(p);
+			RefitBox r;
+			if(ref_box) r = ref_box[b.tri]; // (b.tri is then the reference: presplit.hpp)
+			else
+			{
+				float p[9];
+				memcpy(p, tris[b.tri].p, sizeof(p));
+				r = refit_triangle_box(p);
+			}
 			b.box = Box({r.lo[0], r.lo[1], r.lo[2]}, {r.hi[0], r.hi[1], r.hi[2]});
 			continue;
 		}

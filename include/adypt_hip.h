@@ -345,9 +345,28 @@ int adypt_rebuild_bvh(adypt_ctx *ctx, const adypt_bvh_params *params, adypt_rebu
  * Memory: adypt_rebuild_bvh's scratch without its 4 B per triangle of counters, and 28 B per triangle more (two cluster lists 8, the choices 4, the
  * marks and their scan 16); the scan's temporary storage shares the sort's. */
 int adypt_rebuild_bvh_ploc(adypt_ctx *ctx, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out);
+/* adypt_rebuild_bvh_ploc with large triangles split into several references first (early split clipping), so that a long thin triangle no longer puts
+ * a box the size of a room into a leaf.  The new tree holds at most n + floor(split_budget * n) references, split_budget in [0, 1]; which triangles
+ * are cut, and how far, follows from one level of detail for the whole scene, the finest of 24 that the budget allows.  The definition is
+ * csrc/device/presplit.hpp, which the host's adypt_bvh_build_ploc_split (adypt_host.h) compiles too: nodes, indices and Woop data afterwards equal that
+ * function's byte for byte, and adypt_read_ref_boxes its reference boxes.  split_budget 0 launches what adypt_rebuild_bvh_ploc launches and gives its
+ * bytes; so does, after the counting kernels and two reads of 192 bytes, a budget under which nothing is split.  n_refs is the number of references;
+ * tri_indices names a split triangle once per reference.  A split tree, like one built with spatial splits, should be rebuilt for a new pose and not
+ * refitted: adypt_update_triangles drops the reference boxes and bounds whole triangles from then on.
+ * ADYPT_E_INVALID (a budget that is NaN or outside [0, 1], and everything adypt_rebuild_bvh_ploc refuses) and ADYPT_E_OOM leave the old tree in place.
+ * Memory: adypt_rebuild_bvh_ploc's scratch per REFERENCE instead of per triangle, and 40 B per reference (its triangle 4, its box 32, where it was
+ * emitted 4) plus 8 B per triangle (the counts and their scan) more; 32 B per reference stay with the tree for adypt_read_ref_boxes. */
+int adypt_rebuild_bvh_ploc_split(adypt_ctx *ctx, const adypt_bvh_params *params, int radius, double split_budget, adypt_rebuild_info *out);
+/* of the last rebuild: out[0] the chosen level of detail (-1: none — budget 0, another method, or no level inside the budget), out[1] the triangles
+ * that were split.  ADYPT_E_STATE before the first rebuild. */
+int adypt_get_rebuild_presplit(adypt_ctx *ctx, int32_t out[2]);
+/* the boxes of the references of a split tree as they are on the device, in the order of adypt_read_tri_indices: 6 floats each (lo xyz, hi xyz).
+ * Returns their number, n_refs, or 0 — nothing is written — when the context's tree has none (it was not built with splits, or it has been refitted
+ * since); negative: an ADYPT_E_* code.  out may be NULL to ask. */
+int64_t adypt_read_ref_boxes(adypt_ctx *ctx, float *out);
 /* HIP-event times of the last adypt_rebuild_bvh in ms: [0] centroid box and keys, [1] sort, [2] radix tree, [3] bottom-up pass, [4] emission (with its
  * one small read per level), [5] Woop data and node records, [6] all of it.  After adypt_rebuild_bvh_ploc [2] is all PLOC rounds (with their one small
- * read each) and [3] is 0.  Returns the number of entries and writes them only when capacity holds them all. */
+ * read each) and [3] is 0; the splitting of adypt_rebuild_bvh_ploc_split counts into [0].  Returns the number of entries and writes them only when capacity holds them all. */
 int adypt_get_rebuild_timing(adypt_ctx *ctx, float *ms, int capacity);
 /* the sizes of the tree the context holds now; either pointer may be NULL */
 int adypt_get_bvh_sizes(adypt_ctx *ctx, int64_t *n_nodes, int64_t *n_refs);
@@ -460,6 +479,7 @@ int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, c
 /* adypt_rebuild_bvh on every device: every device rebuilds its own copy, and all get the same bytes; no collective.  *out: the last device's. */
 int adypt_multi_rebuild_bvh(adypt_multi *m, const adypt_bvh_params *params, adypt_rebuild_info *out);
 int adypt_multi_rebuild_bvh_ploc(adypt_multi *m, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out); /* likewise */
+int adypt_multi_rebuild_bvh_ploc_split(adypt_multi *m, const adypt_bvh_params *params, int radius, double split_budget, adypt_rebuild_info *out); /* likewise */
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

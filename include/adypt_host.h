@@ -98,6 +98,23 @@ int adypt_bvh_build_ploc(const adypt_scene *s, const adypt_bvh_params *p, int ra
 /* the binary tree adypt_bvh_build_ploc makes of n_tris 100-byte triangle records, in the node ids of csrc/device/lbvh.hpp: left[i] and right[i] are
  * the children of inner node i (n_tris - 1 entries each; the root is 0; the leaf of sorted position j is n_tris - 1 + j).  For tests and tools. */
 int adypt_ploc_tree(const void *tris, int64_t n_tris, int radius, int32_t *left, int32_t *right);
+/* adypt_bvh_build_ploc with large triangles split into several references first (early split clipping; the definition is csrc/device/presplit.hpp,
+ * which the device builder, adypt_rebuild_bvh_ploc_split, compiles too: both give the same bytes).  A triangle whose box is large against the scene's
+ * is cut at the middle of its box's longest axis, again and again (at most 6 times in a row), and every piece becomes a reference with the clipped
+ * piece's box; the tree holds at most n + floor(split_budget * n) references, split_budget in [0, 1] (else ADYPT_E_INVALID; NaN too).  The level of
+ * detail is the finest of 24 (areas of S * 2^-level, S the scene box's area) that stays inside the budget.  tri_indices names a split triangle once per
+ * reference; the leaf slots bound the references' boxes (adypt_bvh_ref_boxes), not the whole triangles, which is the gain: a long thin triangle no
+ * longer puts a box the size of a room into a leaf.  Budget 0, or a budget under which nothing is split, gives adypt_bvh_build_ploc's tree to the
+ * byte.  Like a tree with spatial splits, a split tree should be rebuilt for a new pose, not refitted: adypt_bvh_refit bounds whole triangles.
+ * info->refs: the references.  The tree does not depend on adypt_host_set_threads. */
+int adypt_bvh_build_ploc_split(const adypt_scene *s, const adypt_bvh_params *p, int radius, double split_budget, adypt_bvh **out, adypt_build_info *info);
+/* the boxes of that tree's references in the order of tri_indices, 6 floats each (lo xyz, hi xyz); returns their number — 0, and *boxes = NULL, for a
+ * tree that has none (every other builder's, and a split build that split nothing) */
+int64_t adypt_bvh_ref_boxes(const adypt_bvh *b, const float **boxes);
+/* the bare reference list adypt_bvh_build_ploc_split starts from, for n_tris 100-byte records, in reference order (triangles in index order, the pieces
+ * of one depth first, low half first): *level the chosen level or -1, ref_tri[r] the triangle, ref_box + 6 r its box.  Returns the number of references,
+ * and writes the arrays only when that is <= capacity (call with capacity 0 to ask); negative: an ADYPT_E_* code.  For tests and tools. */
+int64_t adypt_presplit_refs(const void *tris, int64_t n_tris, double split_budget, int64_t capacity, int32_t *level, int32_t *ref_tri, float *ref_box);
 int adypt_bvh_load(const char *path, const adypt_bvh_params *expected, adypt_bvh **out);  /* WideBVH::LoadFromFile */
 int adypt_bvh_save(const adypt_bvh *b, const char *path, const adypt_bvh_params *p);       /* WideBVH::SaveToFile */
 void adypt_bvh_free(adypt_bvh *b);

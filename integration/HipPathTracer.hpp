@@ -205,10 +205,16 @@ public:
 	// to cover — and the depth of the binary tree.  The sample counter restarts as after a Trace(false).
 	// method Linear (the default): the linear tree, as ever.  PLOC: the binary tree is built by PLOC with search radius `radius`, 1 .. 32
 	// (adypt_rebuild_bvh_ploc) — a tighter tree on meshes for a few times the build time (Rebuilding on the GPU).
+	// split_budget, PLOC only, 0 .. 1: large triangles are split into several references first, at most split_budget * n more than triangles
+	// (adypt_rebuild_bvh_ploc_split) — for scenes with large triangles among small ones; 0 (the default): no splits.
 	enum class RebuildMethod { Linear, PLOC };
-	bool RebuildBVH(const adypt_bvh_params *params = nullptr, adypt_rebuild_info *info = nullptr, RebuildMethod method = RebuildMethod::Linear, int radius = 8)
+	bool RebuildBVH(const adypt_bvh_params *params = nullptr, adypt_rebuild_info *info = nullptr, RebuildMethod method = RebuildMethod::Linear, int radius = 8, double split_budget = 0.0)
 	{
-		if((method == RebuildMethod::PLOC ? adypt_multi_rebuild_bvh_ploc(m_gpus, params, radius, info) : adypt_multi_rebuild_bvh(m_gpus, params, info)) == ADYPT_OK) return true;
+		if(method != RebuildMethod::PLOC && split_budget != 0.0) { printf("[PT]ERR: RebuildBVH: split_budget needs RebuildMethod::PLOC\n"); return false; }
+		const int code = method != RebuildMethod::PLOC ? adypt_multi_rebuild_bvh(m_gpus, params, info)
+		                 : split_budget != 0.0         ? adypt_multi_rebuild_bvh_ploc_split(m_gpus, params, radius, split_budget, info)
+		                                               : adypt_multi_rebuild_bvh_ploc(m_gpus, params, radius, info);
+		if(code == ADYPT_OK) return true;
 		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
 		return false;
 	}

@@ -1,12 +1,13 @@
 """What a new tree for a moved scene costs on the GPU, next to the host's way, and what the three trees are worth afterwards (DESIGN.md §4 "Rebuilding on
 the GPU"; writes profiles/rebuild_cost.txt).
 
-    python tools/rebuild_cost.py [--scene sponza] [--method linear|ploc [--radius 8]] [--steps 256] [--repeats 5] [--out profiles/rebuild_cost.txt] [--append]
+    python tools/rebuild_cost.py [--scene sponza] [--method linear|ploc [--radius 8] [--split-budget 0]] [--steps 256] [--repeats 5] [--out profiles/rebuild_cost.txt] [--append]
 
 One process, the scene at 1920 x 1080 with bench.py's settings, in the wave pose of the tests (y += 1.5 sin(0.7 x) + 0.8 cos(0.9 z); x *= 1.1).  Three
 contexts are held side by side:
     refitted   the config's tree (spatial splits), UpdateTriangles to the pose
-    rebuilt    the same, then RebuildBVH: the linear tree (--method linear) or the PLOC tree (--method ploc) built on the GPU
+    rebuilt    the same, then RebuildBVH: the linear tree (--method linear) or the PLOC tree (--method ploc) built on the GPU; --split-budget B
+               (ploc only): with large triangles split into several references first, at most B * n more than triangles
     sbvh       adypt_bvh_build of the moved triangles + adypt_create: the parent commit's only way to a new tree
   1. `repeats` times: one RebuildBVH (HIP-event parts and the host clock around the call), and adypt_bvh_build + adypt_create (host clock).
   2. The device's arrays after the rebuild against WideBVH.BuildLinear / BuildPLOC of the moved triangles (skipped above 2 M triangles: the host build is
@@ -53,10 +54,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--method", choices=("linear", "ploc"), default="linear")
     ap.add_argument("--radius", type=int, default=8, help="the search radius of --method ploc")
+    ap.add_argument("--split-budget", type=float, default=0.0, help="of --method ploc: split large triangles first (csrc/device/presplit.hpp)")
     ap.add_argument("--cache", default=os.environ.get("ADYPT_CACHE") or os.path.join(ROOT, ".adypt_cache"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rebuild_cost.txt"))
     ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it (a second scene)")
     args = ap.parse_args()
+    if args.split_budget and args.method != "ploc":
+        ap.error("--split-budget needs --method ploc")
     try:
         import torch  # noqa: F401  (its copy of the HIP runtime first, as bench.py does)
     except ImportError:
@@ -80,7 +84,11 @@ def main():
     b.m_path_tracer.UpdateTriangles(0, pos)
     how = dict(method=args.method, radius=args.radius)
     label = "linear tree" if args.method == "linear" else "PLOC tree, radius %d" % args.radius
+    if args.split_budget:
+        how["split_budget"] = args.split_budget
     info = b.m_path_tracer.RebuildBVH(cfg.bvh_params(), **how)  # untimed: the scratch is allocated, the code object is loaded
+    if args.split_budget:
+        label += ", split budget %g (level %d, %d triangles split)" % ((args.split_budget,) + b.m_path_tracer.GetRebuildPresplit())
 
     def host_way():
         t0 = time.perf_counter()
@@ -115,7 +123,7 @@ def main():
         plain = api.Scene.FromArrays(moved, a.scene.materials)
         lin = api.WideBVH()
         if args.method == "ploc":
-            lin.BuildPLOC(plain, cfg.bvh_params(), args.radius)
+            lin.BuildPLOC(plain, cfg.bvh_params(), args.radius, args.split_budget)
         else:
             lin.BuildLinear(plain, cfg.bvh_params())
         nodes, woop = b.m_path_tracer.ReadBVH()
@@ -123,6 +131,8 @@ def main():
         nan = np.isnan(want)
         same = (np.array_equal(nodes, lin.nodes) and np.array_equal(b.m_path_tracer.ReadTriIndices(), lin.tri_indices) and np.array_equal(np.isnan(woop), nan)
                 and np.array_equal(woop.view(np.uint32)[~nan], want.view(np.uint32)[~nan]))
+        boxes = b.m_path_tracer.ReadRefBoxes() if args.split_budget else None
+        same = same and (boxes is None) == (len(lin.ref_boxes) == 0) and (boxes is None or np.array_equal(boxes.view(np.uint32), lin.ref_boxes.view(np.uint32)))
         assert same, "the device's tree is not the host's (%s)" % label
         verdict = "equal WideBVH.%s + woop_matrices of the moved triangles byte for byte (host: %.0f ms tree, %.0f ms collapse and boxes)" % (
             "BuildPLOC" if args.method == "ploc" else "BuildLinear", lin.build_info.sbvh_ms, lin.build_info.wide_ms)

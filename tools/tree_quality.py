@@ -1,11 +1,12 @@
 """What the trees a moved scene can get are worth, without a GPU: nodes visited and triangles tested per ray by the CPU oracle (DESIGN.md §4 "What the
 tree is worth"; the figures go into profiles/rebuild_cost.txt by hand).
 
-    python tools/tree_quality.py [--scene sponza] [--rays 200000] [--radii 8,16]
+    python tools/tree_quality.py [--scene sponza] [--rays 200000] [--radii 8,16] [--split-budget 0.1,0.3]
 
 The scene's triangles in the rest pose and in the wave pose of the tests (y += 1.5 sin(0.7 x) + 0.8 cos(0.9 z); x *= 1.1); random rays with origins
 uniform in the pose's box and normal directions (tests/refit_truth.py rays_in_box), stack 64.  Trees: WideBVH.BuildLinear, WideBVH.BuildPLOC at every
-radius (with the rounds it takes, counted by the numpy restatement tests/ploc_truth.py), WideBVH.Build (SBVH, the config's depth) of the pose."""
+radius (with the rounds it takes, counted by the numpy restatement tests/ploc_truth.py), at radius 8 with every --split-budget (large triangles split
+first: csrc/device/presplit.hpp), WideBVH.Build (SBVH, the config's depth) of the pose."""
 import argparse
 import os
 import sys
@@ -22,6 +23,7 @@ def main():
     ap.add_argument("--scene", default="sponza")
     ap.add_argument("--rays", type=int, default=200000)
     ap.add_argument("--radii", default="8,16")
+    ap.add_argument("--split-budget", default="", help="comma-separated budgets of BuildPLOC(radius 8, split_budget)")
     ap.add_argument("--cache", default=os.environ.get("ADYPT_CACHE") or os.path.join(ROOT, ".adypt_cache"))
     args = ap.parse_args()
     from adypt_amd import api, scenes
@@ -43,6 +45,8 @@ def main():
         builders = [("linear tree (BuildLinear)", lambda b: b.BuildLinear(plain, cfg.bvh_params()))]
         for r in (int(x) for x in args.radii.split(",")):
             builders.append(("PLOC tree, radius %d (BuildPLOC)" % r, lambda b, r=r: b.BuildPLOC(plain, cfg.bvh_params(), r)))
+        for budget in (float(x) for x in args.split_budget.split(",") if x):
+            builders.append(("PLOC tree, radius 8, split budget %g" % budget, lambda b, budget=budget: b.BuildPLOC(plain, cfg.bvh_params(), 8, budget)))
         builders.append(("SBVH tree built for the pose (Build)", lambda b: b.Build(plain, cfg.bvh_params())))
         hits = {}
         for name, build in builders:
