@@ -132,6 +132,7 @@ _SIGS = {
     "adypt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "adypt_reset_stats": (C.c_int, [C.c_void_p]),
     "adypt_get_wave_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "adypt_read_root_card": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_get_shader_clock": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "adypt_local_pixel_count": (C.c_int64, [C.c_void_p]),
     "adypt_set_sun_visibility": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
@@ -249,6 +250,7 @@ _SIGS = {
     "adypt_bvh_tri_indices": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "adypt_bvh_refit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "adypt_woop_matrices": (None, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "adypt_decode_root_card": (None, [C.c_void_p, C.c_int, C.c_void_p]),
     "adypt_camera_matrices": (None, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "adypt_sobol_points": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "adypt_shift_bytes": (None, [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),

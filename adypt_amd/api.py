@@ -257,6 +257,21 @@ def woop_matrices(triangles: np.ndarray, tri_indices: np.ndarray) -> np.ndarray:
     return out
 
 
+# struct RootCard (csrc/device/root_card.hpp), 264 bytes; q[child] = float(qlo x, qhi x, qlo y, qhi y, qlo z, qhi z)
+ROOT_CARD_DT = np.dtype([("q", "<f4", (8, 6)), ("scale", "<f4", 3), ("origin", "<f4", 3), ("child_base", "<u4"), ("tri_base", "<u4"), ("imask", "<u4"),
+                         ("inner_only", "<u4"), ("enabled", "<u4"), ("pad", "<u4"), ("is_inner", "u1", 8), ("bit_index", "u1", 8), ("child_bits", "u1", 8)])
+
+
+def decode_root_card(node: np.ndarray, allow: bool = True) -> np.ndarray:
+    """adypt_decode_root_card: one 80-byte node as the ROOT_CARD_DT record k_path's shading round tests new rays against."""
+    n = np.ascontiguousarray(node).view(np.uint8).reshape(-1)
+    if len(n) != NODE_BYTES:
+        raise ValueError("decode_root_card: a node is %d bytes" % NODE_BYTES)
+    card = np.zeros(1, dtype=ROOT_CARD_DT)
+    N.lib.adypt_decode_root_card(n.ctypes.data, 1 if allow else 0, card.ctypes.data)
+    return card[0]
+
+
 def sobol_points(dim: int, first: int, n: int) -> np.ndarray:
     out = np.empty((n, dim), dtype=np.float32)
     N.check_host(N.lib.adypt_sobol_points(dim, first, n, out.ctypes.data))
@@ -601,6 +616,13 @@ class _Tracer:
         nodes, woop = np.zeros(n_nodes * NODE_BYTES, dtype=np.uint8), np.zeros((n_refs, 12), dtype=np.float32)
         N.check(N.lib.adypt_read_bvh(c, nodes.ctypes.data, woop.ctypes.data), c)
         return nodes, woop
+
+    def ReadRootCard(self) -> np.ndarray:
+        """The root card of the (first) device as it is now: one ROOT_CARD_DT record (adypt_read_root_card; csrc/device/root_card.hpp)."""
+        c = self._contexts()[0]
+        card = np.zeros(1, dtype=ROOT_CARD_DT)
+        N.check(N.lib.adypt_read_root_card(c, card.ctypes.data), c)
+        return card[0]
 
     # ---- rebuilding the tree on the GPU (adypt_rebuild_bvh, include/adypt_hip.h; the definition: csrc/device/lbvh.hpp) ----
     def RebuildBVH(self, cfg: Optional[N.BvhParams] = None, method: str = "linear", radius: int = 8, split_budget: float = 0.0) -> dict:

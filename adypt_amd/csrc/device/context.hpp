@@ -97,6 +97,7 @@ struct adypt_ctx {
 	Buffer<uint8_t> d_tri_class;
 	Buffer<uint32_t> d_texels;
 	Buffer<float4> d_ref_triangles;           // k_path: the triangle records once per REFERENCE (uTriIndices order), made at adypt_create; null = k_path remaps through d_tri_indices
+	Buffer<RootCard> d_root_card;             // k_path: node 0 decoded for the shading round (root_card.hpp); written again behind everything that rewrites node 0 (refresh_root_card)
 	Buffer<int32_t> d_all_blocks;             // adypt_assemble_radiance: block lists of all ranks
 	std::vector<int64_t> all_blocks_offset;
 	int64_t n_nodes = 0, n_refs = 0, n_tris = 0, n_mats = 0;

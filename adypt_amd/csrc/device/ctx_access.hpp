@@ -79,6 +79,8 @@ struct CtxScene {
 CtxScene ctx_scene(adypt_ctx *c);
 // the per-reference copy of the triangle records made again from the records as they are now, on the context's stream; nothing when the context keeps none
 int ctx_expand_references(adypt_ctx *c);
+// the root card (root_card.hpp) written again from node 0 as it is now, on the context's stream and without a host sync: behind every launch that rewrites node 0
+int ctx_refresh_root_card(adypt_ctx *c);
 // everything the context has enqueued on any of its streams has finished (the scene arrays are about to change under it)
 int ctx_drain(adypt_ctx *c);
 // ---- rebuilding the tree (build.hip), per context: see tracer.hip ----

@@ -28,11 +28,14 @@
 //   * the optional sun-visibility query (pathtracer.glsl:132, commented out in the reference) stays inside the launch: a path that hits nothing keeps
 //     its slot and its origin, takes the sun direction and the bounce index kPwShadow, and is traced once more — ending at its first accepted triangle
 //     (traversal.glsl:257-494 per lane: the SUN variant of the kernel) — before the round that finds it again adds the sun term, or not;
+//   * a ray's first node visit — the root, for every ray — is done by the round that leaves the ray in its slot, against node 0 decoded once per scene
+//     change (root_card.hpp, root_visit() below): the lane takes the ray up behind that visit, one byte of hit mask per slot waiting for it in LDS;
 //   * no inter-workgroup communication of any kind, so none of the cross-XCD visibility questions of a streaming queue.
 // The kernel ends when the global queue is dry and every workgroup has finished the paths it holds.
 #pragma once
 #include "traverse.hpp"
 #include "path_limits.hpp"
+#include "root_card.hpp"
 
 namespace adypt {
 
@@ -72,12 +75,13 @@ struct PathArgs {
 	uint32_t defer_max;            // a round defers such hits only when it holds at most this many of them (more: those branches are well occupied where they are)
 	int32_t b0;                    // bounce index of the queue's rays (1: k_shade_first did bounce 0)
 	float tmin;
+	const RootCard *root_card;     // node 0 as the shading round tests it (root_card.hpp); its `enabled` word decides per launch whether rays start past the root
 };
 
-inline size_t path_lds_bytes(int lds_depth)
+constexpr size_t path_lds_bytes(int lds_depth)
 {
 	return (size_t)(kTraceThreads / 64) * (size_t)lds_depth * 64 * sizeof(uint2) + (size_t)kTabFields * kPathSlots * 4 + (size_t)kParkDwords * 64 * 4 + 2 * (size_t)kPathSlots * 2 +
-	       (size_t)kRareCap * 2 + sizeof(PathCtl) + kTripTabBytes;
+	       (size_t)kRareCap * 2 + sizeof(PathCtl) + kTripTabBytes + (size_t)kPathSlots; // (the last term: root_mask, one byte per path slot)
 }
 
 __device__ __forceinline__ void wg_lock(PathCtl *ctl, int lane)
@@ -116,6 +120,31 @@ __device__ __forceinline__ const PathKernArgs &rare_args()
 	return *(const PathKernArgs *)(const __attribute__((address_space(4))) PathKernArgs *)k;
 }
 
+// The part of the ray setup (traversal.glsl:16-23) that turns a direction as the path table holds it into what the slab test works with: the clamped,
+// normalised direction, its reciprocal, the octant and the three near-plane swaps.  ONE text for the lane that traverses the ray (aim(), below) and for
+// the shading round that tests the ray against the root ahead of it (root_visit()): the two cannot drift apart.
+__device__ __forceinline__ void ray_frame(F3 &dir, F3 &idir, uint32_t &octinv, bool &nx, bool &ny, bool &nz)
+{
+	const float ooeps = __uint_as_float((127u - 64u) << 23);
+	dir.x = fabsf(dir.x) > ooeps ? dir.x : (dir.x >= 0 ? ooeps : -ooeps);
+	dir.y = fabsf(dir.y) > ooeps ? dir.y : (dir.y >= 0 ? ooeps : -ooeps);
+	dir.z = fabsf(dir.z) > ooeps ? dir.z : (dir.z >= 0 ? ooeps : -ooeps);
+	dir = normalize3(dir);
+	idir = f3(rcp_ieee(dir.x), rcp_ieee(dir.y), rcp_ieee(dir.z));
+	octinv = 7u - ((dir.x < 0 ? 1u : 0u) | (dir.y < 0 ? 2u : 0u) | (dir.z < 0 ? 4u : 0u));
+	slab_swaps(idir, nx, ny, nz);
+}
+
+// the root card through the constant address space, behind a value the compiler cannot see through: its fields arrive by scalar loads where they are
+// used (a wave-uniform address in the generic space is loaded per lane, into vector registers the traversal loop has none of to spare)
+typedef const __attribute__((address_space(4))) RootCard *RootCardC;
+__device__ __forceinline__ RootCardC root_card_of(const RootCard *p)
+{
+	unsigned long long k = (unsigned long long)p;
+	asm volatile("" : "+s"(k));
+	return (RootCardC)k;
+}
+
 template <bool STATS, bool SUN>
 __global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) void k_path(PathKernArgs K)
 {
@@ -138,6 +167,7 @@ __global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) void k
 	uint16_t *to_rare = to_trace + kPathSlots;
 	PathCtl *ctl = (PathCtl *)(to_rare + kRareCap);
 	uint8_t *const trip_tab = (uint8_t *)(ctl + 1) + wave * 64; // the wave's triangle hand-out table (traverse_trip.inc, section B)
+	uint8_t *const root_mask = (uint8_t *)(ctl + 1) + kTripTabBytes; // [kPathSlots]: bits 24..31 of the root visit's hit mask of the ray waiting in the slot (root_visit(), below)
 	const uint32_t total_lanes = gridDim.x * (uint32_t)kTraceThreads;
 	const SpillColumn<true> my_spill(a.spill); // (addressed where it is used: traverse.hpp)
 	const int home = blockIdx.x & (kNumSegments - 1);
@@ -164,6 +194,41 @@ __global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) void k
 		tab[T_OX * kPathSlots + slot] = __float_as_uint(o.x); tab[T_OY * kPathSlots + slot] = __float_as_uint(o.y); tab[T_OZ * kPathSlots + slot] = __float_as_uint(o.z);
 	};
 
+	// The root visit of the ray waiting in table slot `slot` (origin and direction as the table holds them), done by whoever puts the ray there — a
+	// shading round, at its 64 busy lanes — instead of by the lane that will traverse it: section D of the trip (traverse_trip.inc) for node 0 with the
+	// node's decoded form coming from the root card in scalar registers.  Same arithmetic, bit for bit: the ray's frame is ray_frame(), as in aim(); per
+	// bound t = fma(float(q), scale * idir, (p - origin) * idir) is ONE v_fma_f32 where the trip computes it as one half of a v_pk_fma_f32 — each half
+	// of the packed instruction is the same IEEE fused multiply-add under the same rounding and denormal modes as the scalar one (canon_math.hpp), so the
+	// bits agree; near / far by the ray's sign is chosen AFTER the fma here (two scalar operands under a lane mask are not one instruction's worth),
+	// which selects between the same two values; the far distance starts at the ray's 1e9f.  Returns bits 24..31 of the hit mask: with every occupied
+	// slot of the root an internal child (RootCard::inner_only) the visit raises nothing else.
+	auto root_visit = [&](RootCardC card, uint32_t slot) -> uint32_t {
+		const float ox = __uint_as_float(tab[T_OX * kPathSlots + slot]), oy = __uint_as_float(tab[T_OY * kPathSlots + slot]), oz = __uint_as_float(tab[T_OZ * kPathSlots + slot]);
+		F3 r_dir = f3(__uint_as_float(tab[T_DX * kPathSlots + slot]), __uint_as_float(tab[T_DY * kPathSlots + slot]), __uint_as_float(tab[T_DZ * kPathSlots + slot]));
+		F3 r_idir;
+		uint32_t r_octinv;
+		bool r_nx, r_ny, r_nz;
+		ray_frame(r_dir, r_idir, r_octinv, r_nx, r_ny, r_nz);
+		const float aix = card->scale[0] * r_idir.x, aiy = card->scale[1] * r_idir.y, aiz = card->scale[2] * r_idir.z;
+		const float aox = (card->origin[0] - ox) * r_idir.x, aoy = (card->origin[1] - oy) * r_idir.y, aoz = (card->origin[2] - oz) * r_idir.z;
+		const float far = 1e9f;
+		uint32_t hitmask = 0;
+#pragma unroll
+		for(int j = 0; j < 8; ++j)
+		{
+			const float xl = fmaf(card->q[j][RC_LOX], aix, aox), xh = fmaf(card->q[j][RC_HIX], aix, aox);
+			const float yl = fmaf(card->q[j][RC_LOY], aiy, aoy), yh = fmaf(card->q[j][RC_HIY], aiy, aoy);
+			const float zl = fmaf(card->q[j][RC_LOZ], aiz, aoz), zh = fmaf(card->q[j][RC_HIZ], aiz, aoz);
+			const float cmin = fmaxf(fmaxf(r_nx ? xh : xl, r_ny ? yh : yl), max_num(r_nz ? zh : zl, tmin));   // IEEE maxNum / minNum
+			const float cmax = fminf(fminf(r_nx ? xl : xh, r_ny ? yl : yh), min_num(r_nz ? zl : zh, far));
+			// (scalar: the three bytes of child j out of the card's packed words)
+			const uint32_t is_inner = (card->is_inner4[j >> 2] >> (8 * (j & 3))) & 0xffu, bit_index0 = (card->bit_index4[j >> 2] >> (8 * (j & 3))) & 0xffu, child_bits = (card->child_bits4[j >> 2] >> (8 * (j & 3))) & 0xffu;
+			const uint32_t bit_index = bit_index0 ^ (r_octinv & (0u - is_inner));
+			or_if_le(hitmask, cmin, cmax, child_bits << (bit_index & 31u));
+		}
+		return hitmask >> 24;
+	};
+
 	// ---------------- the workgroup's first paths: wave 0 reserves them, every thread moves its share into the table ----------------
 	{
 		uint32_t *init_idx = (uint32_t *)lds_stack; // (the stacks are not in use yet)
@@ -188,6 +253,15 @@ __global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) void k
 		__syncthreads(); // the stack area is free again
 		if(threadIdx.x < have) load_path(a, i0, threadIdx.x);
 		if(threadIdx.x + kTraceThreads < have) { load_path(a, i1, threadIdx.x + kTraceThreads); to_trace[threadIdx.x] = (uint16_t)(threadIdx.x + kTraceThreads); }
+		{
+			// the root visits of these first rays (later ones: the shading round that leaves the ray in its slot); each thread reads back the slots it wrote
+			const RootCardC card = root_card_of(rare_args().a.root_card);
+			if(card->enabled != 0u)
+			{
+#pragma unroll 1
+				for(uint32_t s = threadIdx.x; s < have; s += (uint32_t)kTraceThreads) root_mask[s] = (uint8_t)root_visit(card, s);
+			}
+		}
 		__syncthreads(); // slots beyond the lanes are on the to-trace list before any wave looks at it
 	}
 
@@ -225,14 +299,7 @@ __global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) void k
 	auto aim = [&]() {
 		const float ox = __uint_as_float(tab[T_OX * kPathSlots + ray]), oy = __uint_as_float(tab[T_OY * kPathSlots + ray]), oz = __uint_as_float(tab[T_OZ * kPathSlots + ray]);
 		F3 dir = f3(__uint_as_float(tab[T_DX * kPathSlots + ray]), __uint_as_float(tab[T_DY * kPathSlots + ray]), __uint_as_float(tab[T_DZ * kPathSlots + ray]));
-		const float ooeps = __uint_as_float((127u - 64u) << 23);
-		dir.x = fabsf(dir.x) > ooeps ? dir.x : (dir.x >= 0 ? ooeps : -ooeps);
-		dir.y = fabsf(dir.y) > ooeps ? dir.y : (dir.y >= 0 ? ooeps : -ooeps);
-		dir.z = fabsf(dir.z) > ooeps ? dir.z : (dir.z >= 0 ? ooeps : -ooeps);
-		dir = normalize3(dir);
-		idir = f3(rcp_ieee(dir.x), rcp_ieee(dir.y), rcp_ieee(dir.z));
-		octinv = 7u - ((dir.x < 0 ? 1u : 0u) | (dir.y < 0 ? 2u : 0u) | (dir.z < 0 ? 4u : 0u));
-		slab_swaps(idir, nx, ny, nz);
+		ray_frame(dir, idir, octinv, nx, ny, nz);
 		od_x = v2(ox, dir.x); od_y = v2(oy, dir.y); od_z = v2(oz, dir.z);
 	};
 
@@ -256,6 +323,10 @@ __global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) void k
 			const unsigned long long starting = __ballot(setup);
 			any_setup = false;
 			asm volatile("; ADYPT_MARK setup_begin"); // (comments in the assembly: tools/instruction_mix.py weights the blocks of the loop by how often they run)
+			// Where the root card is in force a ray starts in the state its first trip used to leave: past the visit of node 0, whose hit mask whoever put
+			// the ray into its slot has left in root_mask (root_visit()).  An empty mask needs no special case: section E ends the ray in its first trip.
+			const RootCardC card = root_card_of(rare_args().a.root_card); // (the pointer from the kernarg segment here, as the round reads it: held in SGPRs across the loop it pushed one of the trip's base pointers into a spill)
+			const uint32_t root_on = card->enabled, root_child_base = card->child_base, root_tri_base = card->tri_base, root_imask = card->imask;
 			if(setup)
 			{
 				aim();
@@ -267,6 +338,11 @@ __global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) void k
 				sp = 0;
 				ng_x = 0; ng_y = 0x80000000u; tg_x = 0; tg_y = 0;
 				if(STATS) { n_nodes = 0; n_tris = 0; hash = 0x811c9dc5u; max_depth = 0; }
+				if(root_on != 0u)
+				{
+					ng_x = root_child_base; ng_y = ((uint32_t)root_mask[ray] << 24) | root_imask; tg_x = root_tri_base;
+					if(STATS) { n_nodes = 1; hash = (0x811c9dc5u * 0x01000193u) ^ 0u; } // (the root is counted once per ray, as the visit counted it)
+				}
 				overflow = false; pending = false; push_overflow = false; depth_after_push = 0;
 				active = true;
 				setup = false;
@@ -513,6 +589,17 @@ __global__ __launch_bounds__(kTraceThreads, STATS ? 4 : ADYPT_PATH_WAVES) void k
 						}
 					}
 					if(repl) load_path(a, idx, sslot);
+					// ---------------- the root visit of every ray this round leaves in a slot (a continued path, a replacement, a sun-visibility query) ----------------
+					// from the table, as aim() will read it; while the round's global stores drain
+					{
+						const RootCardC card = root_card_of(a.root_card);
+						if(card->enabled != 0u)
+						{
+							asm volatile("; ADYPT_MARK root_begin");
+							if(have && (alive || repl)) root_mask[sslot] = (uint8_t)root_visit(card, sslot);
+							asm volatile("; ADYPT_MARK root_end");
+						}
+					}
 					// every global store of this round (finished samples, parked radiance) has left before another wave of the workgroup can
 					// shade these paths again (same CU, same L1: no more is needed inside a workgroup)
 					asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -235,6 +235,7 @@ int adypt_update_triangles(adypt_ctx *c, int64_t first, int64_t count, const flo
 	CTX_TRY(c, refit_launch_woop(i.stream, (const float4 *)sc.triangles, sc.tri_float4, sc.tri_indices, sc.n_refs, sc.woop));
 	CTX_TRY(c, rf->timer.mark(2, i.stream));
 	CTX_TRY(c, refit_launch_levels(i.stream, rf->tree, sc.nodes, sc.tri_indices, (const float4 *)sc.triangles, sc.tri_float4));
+	CTX_STEP(ctx_refresh_root_card(c)); // (node 0 has new boxes: k_path's root card follows, on the same stream)
 	CTX_TRY(c, rf->timer.mark(3, i.stream));
 	CTX_TRY(c, hipStreamSynchronize(i.stream));
 	rf->timer.complete();

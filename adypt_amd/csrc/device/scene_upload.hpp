@@ -133,7 +133,8 @@ int upload_scene(adypt_ctx *c, const adypt_scene_desc *d)
 	TRY_CREATE(upload_shade_classes(c, d));
 	TRY_CREATE(upload_textures_and_materials(c, d));
 	TRY_CREATE(upload(c, &c->d_local_blocks, c->local_blocks.data(), c->local_blocks.size()));
-	return make_reference_triangles(c);
+	TRY_CREATE(make_reference_triangles(c));
+	return ctx_refresh_root_card(c);
 }
 
 }  // namespace

@@ -71,6 +71,18 @@ __global__ void k_expand_references(const float4 *triangles, const int32_t *tri_
 	if(i < n_refs * kTriFloat4) out[i] = triangles[(size_t)tri_indices[i / kTriFloat4] * kTriFloat4 + i % kTriFloat4];
 }
 
+// node 0 decoded into the root card (root_card.hpp: the definition, which the host's adypt_decode_root_card compiles too).  One workgroup; the card is a few
+// hundred bytes decoded once per scene change, so one lane does it and the others have nothing to add.
+__global__ __launch_bounds__(64) void k_root_card(const uint4 *nodes, int allow, RootCard *card)
+{
+	if(threadIdx.x != 0 || blockIdx.x != 0) return;
+	uint32_t n[20];
+	for(int i = 0; i < kNodeUint4; ++i) { const uint4 v = nodes[i]; n[4 * i] = v.x; n[4 * i + 1] = v.y; n[4 * i + 2] = v.z; n[4 * i + 3] = v.w; }
+	RootCard rc;
+	decode_root_card(n, allow != 0, &rc);
+	*card = rc;
+}
+
 template <class D, class T> int upload(adypt_ctx *c, Buffer<D> *dst, const T *src, size_t n)
 {
 	HIP_TRY(c, dst->alloc(std::max<size_t>(n * sizeof(T), 16)));
@@ -215,6 +227,8 @@ int configure_trace(adypt_ctx *c, int stack_size)
 	c->trace_blocks = c->num_cus * per_cu;
 	// k_path (path.hpp): as many workgroups per CU as its registers allow, with the deepest LDS stack that still fits next to the path table
 	{
+		// (the shipped geometry — 352 slots, LDS stack depth 4 — at six workgroups per CU: 26 592 bytes, root_mask's 352 included, inside the 26 KiB the rule below gives)
+		static_assert(ADYPT_PATH_SLOTS != 352 || (path_lds_bytes(4) == 26592 && path_lds_bytes(4) <= ((160 * 1024 - 2048) / 1024 / 6) * 1024), "k_path: six workgroups per CU at LDS stack depth 4");
 		const int want0 = c->tun.path_blocks_per_cu > 0 ? c->tun.path_blocks_per_cu : 6;
 		const size_t fixed = path_lds_bytes(0), per_entry = (size_t)(kTraceThreads / 64) * 64 * sizeof(uint2);
 		int chosen = 0, depth = 1;
@@ -262,6 +276,7 @@ int launch_path(adypt_ctx *c, const Pipe &pipe, const QueueWindow &win, int pari
 	a.stack_size = c->params.stack_size; a.lds_depth = c->path_lds_depth;
 	a.refill_min = c->refill_min; a.shade_min = c->shade_min; a.rare_min = c->rare_min; a.defer_max = c->defer_max;
 	a.b0 = b0; a.tmin = c->params.ray_tmin;
+	a.root_card = c->d_root_card;
 	hipEvent_t stop = begin_timing(c, 2, pipe.stream);
 	const PathKernArgs K{a, f, sc_ref, px, stats ? 1 : 0};
 	// (the SUN variant: rays that end at their first accepted triangle among the others — only where the queue can hold such queries)
@@ -657,6 +672,7 @@ Tunables read_tunables()
 		t.multi_shared_device = flag("ADYPT_MULTI_SHARED_DEVICE", 0) != 0;
 		t.audit_selftest = flag("ADYPT_AUDIT_SELFTEST", 0) != 0;
 		t.gather_stall_test = flag("ADYPT_GATHER_STALL_TEST", 0) != 0;
+		t.root_card = flag("ADYPT_ROOT_CARD", 1);
 		if(const char *v = getenv("ADYPT_COMM_TRANSPORT")) t.comm_transport_host = !strcmp(v, "host");
 		if(const char *v = getenv("ADYPT_HOST_TRANSPORT_TIMEOUT")) t.host_transport_timeout_s = std::max(0.1, atof(v));
 	}
@@ -738,6 +754,13 @@ int ctx_expand_references(adypt_ctx *c)
 	HIP_TRY(c, hipGetLastError());
 	return ADYPT_OK;
 }
+int ctx_refresh_root_card(adypt_ctx *c)
+{
+	if(!c->d_root_card) HIP_TRY(c, c->d_root_card.alloc(sizeof(RootCard)));
+	hipLaunchKernelGGL(k_root_card, dim3(1), dim3(64), 0, c->stream, (const uint4 *)c->d_nodes, c->tun.root_card, (RootCard *)c->d_root_card);
+	HIP_TRY(c, hipGetLastError());
+	return ADYPT_OK;
+}
 int ctx_drain(adypt_ctx *c)
 {
 	HIP_TRY(c, hipSetDevice(c->device));
@@ -773,6 +796,7 @@ int ctx_replace_bvh(adypt_ctx *c, Buffer<uint4> *nodes, Buffer<int32_t> *tri_ind
 	}
 	const int e = ctx_expand_references(c);
 	if(e != ADYPT_OK) return e;
+	TRY_CREATE(ctx_refresh_root_card(c)); // (the new tree's node 0: behind k_emit and the refit of every rebuild method, which ran on this stream)
 	HIP_TRY(c, hipStreamSynchronize(c->stream)); // (the old per-reference copy goes with `ref`)
 	return adypt_reset(c);
 }
@@ -1474,6 +1498,15 @@ int adypt_get_wave_profile(adypt_ctx *c, uint64_t out[8])
 	DeviceStats st;
 	TRY_CREATE(read_device_stats(c, &st));
 	for(int i = 0; i < 8; ++i) out[i] = st.wave_profile[i];
+	return ADYPT_OK;
+}
+
+int adypt_read_root_card(adypt_ctx *c, void *card_out)
+{
+	if(!c || !card_out) return ADYPT_E_INVALID;
+	ENTER_DRAINED(c);
+	if(!c->d_root_card) return fail(c, ADYPT_E_STATE, "adypt_read_root_card: the context has no root card");
+	HIP_TRY(c, hipMemcpy(card_out, c->d_root_card, sizeof(RootCard), hipMemcpyDeviceToHost));
 	return ADYPT_OK;
 }
 

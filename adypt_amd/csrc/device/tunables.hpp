@@ -34,6 +34,7 @@
 //   ADYPT_HOST_TRANSPORT_TIMEOUT    seconds that transport waits for a peer
 //   ADYPT_AUDIT_SELFTEST=1          the slot-claim audit plants a double claim before every check
 //   ADYPT_GATHER_STALL_TEST=1       the gather stalls forever after arming its watchdog (tests the watchdog)
+//   ADYPT_ROOT_CARD=0               k_path's rays start at the root, as k_trace's do, whatever the root card says (root_card.hpp: the A/B switch of the tests)
 #pragma once
 #include <string>
 
@@ -51,6 +52,7 @@ struct Tunables {
 	// test hooks (all off unless adypt_enable_test_hooks was called)
 	bool multi_shared_device = false, comm_transport_host = false, audit_selftest = false, gather_stall_test = false;
 	double host_transport_timeout_s = 0.0; // 0 = the transport's default
+	int root_card = 1;
 };
 
 Tunables read_tunables();

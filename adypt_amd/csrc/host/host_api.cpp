@@ -5,6 +5,7 @@
 #include "../device/woop.hpp"
 #include "../device/ploc.hpp"
 #include "../device/presplit.hpp"
+#include "../device/root_card.hpp"
 #include "../../../include/adypt_hip.h"
 
 #include <algorithm>
@@ -440,6 +441,15 @@ int64_t adypt_bvh_nodes(const adypt_bvh *b, const void **nodes) { if(nodes) *nod
 int64_t adypt_bvh_tri_indices(const adypt_bvh *b, const int32_t **idx) { if(idx) *idx = b->tri_indices.data(); return (int64_t)b->tri_indices.size(); }
 
 // ---------------------------------------------------------------------------------------------------------------
+void adypt_decode_root_card(const void *node, int allow, void *card_out)
+{
+	uint32_t n[20];
+	memcpy(n, node, sizeof(n));
+	RootCard rc;
+	decode_root_card(n, allow != 0, &rc);
+	memcpy(card_out, &rc, sizeof(rc));
+}
+
 void adypt_woop_matrices(const void *tris_, const int32_t *tri_indices, int64_t n_refs, float *out)
 {
 	const TriRec *tris = (const TriRec *)tris_;

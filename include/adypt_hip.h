@@ -396,6 +396,11 @@ int adypt_get_wave_profile(adypt_ctx *ctx, uint64_t out[8]);
  * lifetime of workgroup 0 of every traversal launch since adypt_reset_stats: out[0] / out[1] x 0.1 = the GHz the chip held under the
  * traversal kernel in THIS run (bench.py prices the vector-ALU roof with it). */
 int adypt_get_shader_clock(adypt_ctx *ctx, uint64_t out[2]);
+/* The context's root card as the device holds it now (264 bytes; the layout and its meaning are csrc/device/root_card.hpp, and adypt_decode_root_card
+ * of adypt_host.h gives the same bytes from node 0): what k_path's shading round tests a new ray against, written at adypt_create and again behind
+ * every adypt_update_triangles and adypt_rebuild_bvh*.  Its `enabled` word says whether the rays of k_path start past the root: only where every
+ * occupied slot of node 0 is an internal child. */
+int adypt_read_root_card(adypt_ctx *ctx, void *card_out);
 
 /* ---- pixel-tile sharding plumbing (multi-GPU: one context per GPU/process, one gather per output frame) ---- */
 /* number of RGBA float4 elements in the compact local radiance buffer (owned blocks x 1024 pixels) */

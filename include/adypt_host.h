@@ -129,6 +129,9 @@ int64_t adypt_bvh_tri_indices(const adypt_bvh *b, const int32_t **idx);
 int adypt_bvh_refit(void *nodes, int64_t n_nodes, const int32_t *tri_indices, int64_t n_refs, const void *triangles, int64_t n_tris);
 
 /* ---- small restated host functions ---------------------------------------------------------------------------- */
+/* One 80-byte CWBVH8 node decoded into the 264-byte root card of the device's k_path (csrc/device/root_card.hpp: the definition, which the device
+ * compiles too; adypt_read_root_card of adypt_hip.h reads a context's).  allow = 0: the card's `enabled` word stays 0 whatever the node holds. */
+void adypt_decode_root_card(const void *node, int allow, void *card_out);
 /* OglScene::init_triangles (src/Tracer/OglScene.cpp:93-116): out = 12 floats per reference */
 void adypt_woop_matrices(const void *tris, const int32_t *tri_indices, int64_t n_refs, float *out);
 /* Camera::GetView/GetProjection + the inverses of SetCamera (src/Tracer/Camera.cpp:13-23, OglPathTracer.cpp:27-32) */
