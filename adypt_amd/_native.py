@@ -103,6 +103,28 @@ class RebuildInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_int64), ("n_refs", C.c_int64), ("levels", C.c_int32), ("binary_depth", C.c_int32)]
 
 
+class TreeCost(C.Structure):
+    """adypt_tree_cost."""
+    _fields_ = [("cost", C.c_double), ("inner_q", C.c_uint64), ("leaf_q", C.c_uint64), ("n_nodes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PosePolicy(C.Structure):
+    """adypt_pose_policy."""
+    _fields_ = [("rebuild_above", C.c_double), ("method", C.c_int32), ("radius", C.c_int32), ("split_budget", C.c_double)]
+
+
+class PoseOutcome(C.Structure):
+    """adypt_pose_outcome."""
+    _fields_ = [("built", TreeCost), ("refitted", TreeCost), ("now", TreeCost), ("rebuilt", C.c_int32), ("rebuild", RebuildInfo), ("cost_ms", C.c_float)]
+
+    def as_dict(self):
+        return {"built": self.built.as_dict(), "refitted": self.refitted.as_dict(), "now": self.now.as_dict(), "rebuilt": int(self.rebuilt),
+                "rebuild": {k: getattr(self.rebuild, k) for k, _ in self.rebuild._fields_}, "cost_ms": float(self.cost_ms)}
+
+
 # every symbol include/*.h declares, with its signature (tests/test_abi.py checks the export list against the headers)
 _SIGS = {
     # adypt_hip.h
@@ -184,6 +206,11 @@ _SIGS = {
     "adypt_multi_rebuild_bvh_ploc_split": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.c_double, C.POINTER(RebuildInfo)]),
     "adypt_get_rebuild_presplit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "adypt_read_ref_boxes": (C.c_int64, [C.c_void_p, C.c_void_p]),
+    # refit or rebuild by the tree's SAH cost
+    "adypt_get_tree_cost": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(TreeCost)]),
+    "adypt_update_triangles_auto": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
+    "adypt_multi_get_tree_cost": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(TreeCost)]),
+    "adypt_multi_update_triangles_auto": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),
@@ -249,6 +276,7 @@ _SIGS = {
     "adypt_bvh_nodes": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "adypt_bvh_tri_indices": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "adypt_bvh_refit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "adypt_bvh_cost": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(BvhParams), C.POINTER(TreeCost)]),
     "adypt_woop_matrices": (None, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "adypt_decode_root_card": (None, [C.c_void_p, C.c_int, C.c_void_p]),
     "adypt_camera_matrices": (None, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

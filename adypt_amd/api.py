@@ -220,6 +220,15 @@ class WideBVH:
         N.check_host(N.lib.adypt_bvh_refit(nodes.ctypes.data, len(nodes) // NODE_BYTES, idx.ctypes.data, len(idx), t.ctypes.data, len(t) // TRI_BYTES))
         self.nodes = nodes
 
+    def Cost(self, cfg: Optional[N.BvhParams] = None) -> dict:
+        """adypt_bvh_cost: the SAH cost of the tree as the traversal sees it, from the quantised child boxes (csrc/device/tree_cost.hpp) — cost,
+        and the two integer sums inner_q and leaf_q it is made of, and n_nodes.  What the tracers' GetTreeCost() measures on the GPU, to the same
+        integers.  cfg None: triangleSAH 0.3, nodeSAH 1."""
+        nodes = np.ascontiguousarray(self.nodes, dtype=np.uint8).reshape(-1)
+        out = N.TreeCost()
+        N.check_host(N.lib.adypt_bvh_cost(nodes.ctypes.data, len(nodes) // NODE_BYTES, None if cfg is None else C.byref(cfg), C.byref(out)))
+        return out.as_dict()
+
     def GetNodes(self) -> np.ndarray:
         return self.nodes
 
@@ -600,14 +609,37 @@ class _Tracer:
         return {"guides": ms[0], "prepare": ms[1], "levels": [ms[i] for i in range(2, n)], "total": sum(ms[i] for i in range(n))}
 
     # ---- moving geometry (adypt_update_triangles, include/adypt_hip.h; the definition: csrc/device/refit.hpp) ----
-    def UpdateTriangles(self, first: int, positions: np.ndarray, normals: Optional[np.ndarray] = None) -> None:
+    def UpdateTriangles(self, first: int, positions: np.ndarray, normals: Optional[np.ndarray] = None, rebuild_above: Optional[float] = None,
+                        method: str = "ploc", radius: int = 8, split_budget: float = 0.0, cfg: Optional[N.BvhParams] = None) -> Optional[dict]:
         """New positions (count x 9 float32: p0 p1 p2) and, when given, normals (count x 9) of triangles [first, first + count); every reference's Woop
-        data and every node are then refitted on the GPU.  Leaves the tracer as Reset() does (0 spp).  Several devices: on every device."""
+        data and every node are then refitted on the GPU.  Leaves the tracer as Reset() does (0 spp).  Several devices: on every device.
+        rebuild_above None: that is all, and None is returned.  A number (adypt_update_triangles_auto): the SAH cost of the refitted tree is measured
+        (GetTreeCost) and, where it is more than rebuild_above times the cost the tree had as uploaded or as last rebuilt, the tree is rebuilt as
+        RebuildBVH(cfg, method, radius, split_budget) would; 0 always rebuilds, and there is no default (README, Moving geometry).  Returns built,
+        refitted and now (each as GetTreeCost gives it), rebuilt (0 / 1), rebuild (RebuildBVH's dict; zeros when kept) and cost_ms."""
         pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 9)
         nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 9)
         if nrm is not None and len(nrm) != len(pos):
             raise ValueError("UpdateTriangles: positions and normals differ in length")
-        self._call("update_triangles", first, len(pos), pos.ctypes.data, None if nrm is None else nrm.ctypes.data)
+        if rebuild_above is None:
+            self._call("update_triangles", first, len(pos), pos.ctypes.data, None if nrm is None else nrm.ctypes.data)
+            return None
+        if method not in ("linear", "ploc"):
+            raise ValueError("UpdateTriangles: method must be 'linear' or 'ploc', not %r" % (method,))
+        if split_budget != 0.0 and method != "ploc":
+            raise ValueError("UpdateTriangles: split_budget needs method 'ploc'")
+        policy = N.PosePolicy(float(rebuild_above), 1 if method == "ploc" else 0, int(radius), float(split_budget))
+        out = N.PoseOutcome()
+        self._call("update_triangles_auto", first, len(pos), pos.ctypes.data, None if nrm is None else nrm.ctypes.data,
+                   None if cfg is None else C.byref(cfg), C.byref(policy), C.byref(out))
+        return out.as_dict()
+
+    def GetTreeCost(self, cfg: Optional[N.BvhParams] = None) -> dict:
+        """adypt_get_tree_cost: WideBVH.Cost() of the tree the device holds now, measured there by one pass over the nodes — cost, inner_q, leaf_q,
+        n_nodes.  Several devices: every device measures, and all must agree."""
+        out = N.TreeCost()
+        self._call("get_tree_cost", None if cfg is None else C.byref(cfg), C.byref(out))
+        return out.as_dict()
 
     def ReadBVH(self) -> Tuple[np.ndarray, np.ndarray]:
         """(nodes uint8 [n_nodes * 80], woop float32 [n_refs, 12]) as they are on the (first) device."""

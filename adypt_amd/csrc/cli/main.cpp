@@ -5,7 +5,7 @@
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
 //             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild]
-//             [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]]
+//             [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R]
 //   --pose moved.obj: the scene of the config (and its cached .bvh) with the vertices and normals of moved.obj — the same triangles in the same order,
 //              moved — through adypt_multi_update_triangles: the BVH and the Woop data are refitted on the GPU, nothing is rebuilt
 //   --rebuild: a new tree for the triangles as they are then (after --pose, when given), built on the GPU through adypt_multi_rebuild_bvh with the config's
@@ -14,6 +14,10 @@
 //              tree for a few times the build time; linear (the default) is --rebuild's tree.  Naming a method asks for the rebuild
 //   --split-budget B: with --rebuild-method ploc only (else exit 2): large triangles are split into several references first, at most B * n more than
 //              triangles, B in [0, 1] (adypt_multi_rebuild_bvh_ploc_split)
+//   --rebuild-above R: with --pose only, and not with a bare --rebuild (else exit 2): the pose goes through adypt_multi_update_triangles_auto — the tree is
+//              refitted, its SAH cost measured, and rebuilt only where that is more than R times the cost of the tree as loaded (R finite and >= 0, no
+//              default; 0 always rebuilds).  --rebuild-method, --ploc-radius and --split-budget then name the rebuild of that policy (linear unless
+//              given) instead of asking for one outright
 //   --sun-visibility: enable the occlusion query the reference has commented out (pathtracer.glsl:132)
 //   --preview: what the reference shows in its window (shaders/screen.glsl), as PNG
 //   --devices: pixel tiles sharded over several GPUs of the node (adypt_create_multi), radiance gathered on the first one
@@ -32,6 +36,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -45,11 +50,12 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
 	std::string noise_out, spp_out, denoise_out, guides_out, pose;
-	bool rebuild = false;
+	bool rebuild = false, bare_rebuild = false, have_rebuild_above = false;
+	double rebuild_above = 0.0;
 	std::string rebuild_method = "linear";
 	double split_budget = 0.0;
 	bool have_split_budget = false;
@@ -97,7 +103,14 @@ int main(int argc, char **argv)
 		else if(a == "--denoise-levels" && i + 1 < argc) denoise_levels = atoi(argv[++i]);
 		else if(a == "--guides-out" && i + 1 < argc) guides_out = argv[++i];
 		else if(a == "--pose" && i + 1 < argc) pose = argv[++i];
-		else if(a == "--rebuild") rebuild = true;
+		else if(a == "--rebuild") rebuild = bare_rebuild = true;
+		else if(a == "--rebuild-above" && i + 1 < argc)
+		{
+			char *end = nullptr;
+			rebuild_above = strtod(argv[++i], &end);
+			if(end == argv[i] || *end || !(rebuild_above >= 0.0 && rebuild_above < HUGE_VAL)) { fprintf(stderr, "--rebuild-above takes a finite number >= 0, not %s\n", argv[i]); return 2; }
+			have_rebuild_above = true;
+		}
 		else if(a == "--rebuild-method" && i + 1 < argc) { rebuild_method = argv[++i]; rebuild = true; }
 		else if(a == "--ploc-radius" && i + 1 < argc) ploc_radius = atoi(argv[++i]);
 		else if(a == "--split-budget" && i + 1 < argc) { split_budget = atof(argv[++i]); have_split_budget = true; }
@@ -106,6 +119,9 @@ int main(int argc, char **argv)
 	const bool until = noise_target >= 0.0;
 	if(rebuild_method != "linear" && rebuild_method != "ploc") { fprintf(stderr, "--rebuild-method is linear or ploc\n"); return 2; }
 	if(have_split_budget && rebuild_method != "ploc") { fprintf(stderr, "--split-budget needs --rebuild-method ploc\n"); return 2; }
+	if(have_rebuild_above && pose.empty()) { fprintf(stderr, "--rebuild-above needs --pose moved.obj\n"); return 2; }
+	if(have_rebuild_above && bare_rebuild) { fprintf(stderr, "--rebuild-above decides about the rebuild itself: name its method with --rebuild-method, without --rebuild\n"); return 2; }
+	if(have_rebuild_above) rebuild = false; // (--rebuild-method names the policy's rebuild)
 	if(!until && !noise_out.empty()) { fprintf(stderr, "--noise-out needs --noise T\n"); return 2; }
 	if(until && (primary >= 0 || spp < 2 || check_every < 1)) { fprintf(stderr, "--noise needs --spp >= 2, --check-every >= 1 and no --primary\n"); return 2; }
 	if(adaptive && (!until || save_every > 0)) { fprintf(stderr, "--adaptive needs --noise T and does not combine with --save-every\n"); return 2; }
@@ -180,21 +196,9 @@ int main(int argc, char **argv)
 	if(r == ADYPT_OK) r = adypt_multi_set_instrumentation(multi, 1);
 	if(r == ADYPT_OK && (until || denoise)) r = adypt_multi_set_noise_stats(multi, 1);
 	if(r != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
-	if(!pose.empty())
-	{
-		if(adypt_multi_update_triangles(multi, 0, n_tris, pose_positions.data(), pose_normals.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
-		float ms[4] = {0, 0, 0, 0};
-		(void)adypt_get_refit_timing(adypt_multi_context(multi, 0), ms, 4);
-		printf("[PT]INFO: pose %s: %lld triangles moved, refit %.3f ms (scatter %.3f, references and Woop %.3f, nodes %.3f)\n", pose.c_str(), (long long)n_tris, ms[3], ms[0], ms[1], ms[2]);
-	}
-	if(rebuild)
-	{
-		adypt_rebuild_info info;
-		const bool ploc = rebuild_method == "ploc";
-		const int code = have_split_budget ? adypt_multi_rebuild_bvh_ploc_split(multi, &cfg.bvh, ploc_radius, split_budget, &info)
-		                 : ploc            ? adypt_multi_rebuild_bvh_ploc(multi, &cfg.bvh, ploc_radius, &info)
-		                                   : adypt_multi_rebuild_bvh(multi, &cfg.bvh, &info);
-		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+	const bool ploc = rebuild_method == "ploc";
+	// the figures of a rebuild that has just run: what the rebuild line prints
+	auto rebuild_figures = [&](const adypt_rebuild_info &info) {
 		float ms[7] = {0, 0, 0, 0, 0, 0, 0};
 		(void)adypt_get_rebuild_timing(adypt_multi_context(multi, 0), ms, 7);
 		std::string method = ploc ? "ploc radius " + std::to_string(ploc_radius) : "linear";
@@ -206,8 +210,33 @@ int main(int argc, char **argv)
 			snprintf(text, sizeof(text), " split budget %g level %d", split_budget, (int)presplit[0]);
 			method += text;
 		}
-		printf("[PT]INFO: rebuild: %lld nodes, %lld references, %d levels, method %s, %.3f ms (keys %.3f, sort %.3f, tree %.3f, bottom-up %.3f, emission %.3f, Woop and nodes %.3f)\n", (long long)info.n_nodes,
-		       (long long)info.n_refs, (int)info.levels, method.c_str(), ms[6], ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
+		char text[512];
+		snprintf(text, sizeof(text), "%lld nodes, %lld references, %d levels, method %s, %.3f ms (keys %.3f, sort %.3f, tree %.3f, bottom-up %.3f, emission %.3f, Woop and nodes %.3f)", (long long)info.n_nodes,
+		         (long long)info.n_refs, (int)info.levels, method.c_str(), ms[6], ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
+		return std::string(text);
+	};
+	if(!pose.empty())
+	{
+		adypt_pose_outcome outcome;
+		const adypt_pose_policy policy{rebuild_above, ploc ? 1 : 0, ploc_radius, split_budget};
+		const int code = have_rebuild_above ? adypt_multi_update_triangles_auto(multi, 0, n_tris, pose_positions.data(), pose_normals.data(), &cfg.bvh, &policy, &outcome)
+		                                    : adypt_multi_update_triangles(multi, 0, n_tris, pose_positions.data(), pose_normals.data());
+		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		float ms[4] = {0, 0, 0, 0};
+		(void)adypt_get_refit_timing(adypt_multi_context(multi, 0), ms, 4);
+		printf("[PT]INFO: pose %s: %lld triangles moved, refit %.3f ms (scatter %.3f, references and Woop %.3f, nodes %.3f)\n", pose.c_str(), (long long)n_tris, ms[3], ms[0], ms[1], ms[2]);
+		if(have_rebuild_above)
+			printf("[PT]INFO: pose policy: tree cost %.4f -> %.4f (ratio %.4f, allowed %g): %s\n", outcome.built.cost, outcome.refitted.cost, outcome.refitted.cost / outcome.built.cost, rebuild_above,
+			       outcome.rebuilt ? ("rebuilt (" + rebuild_figures(outcome.rebuild) + ")").c_str() : "kept");
+	}
+	if(rebuild)
+	{
+		adypt_rebuild_info info;
+		const int code = have_split_budget ? adypt_multi_rebuild_bvh_ploc_split(multi, &cfg.bvh, ploc_radius, split_budget, &info)
+		                 : ploc            ? adypt_multi_rebuild_bvh_ploc(multi, &cfg.bvh, ploc_radius, &info)
+		                                   : adypt_multi_rebuild_bvh(multi, &cfg.bvh, &info);
+		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		printf("[PT]INFO: rebuild: %s\n", rebuild_figures(info).c_str());
 	}
 
 	std::vector<float> rgb((size_t)cfg.width * cfg.height * 3, 0.0f);

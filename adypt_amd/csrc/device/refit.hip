@@ -8,13 +8,20 @@
 //                      deeper levels, which earlier launches on the same stream wrote: the stream order is the whole dependency — no atomics, no
 //                      flags between workgroups, no fences.
 // The plan (every node's level) is made once per context, at the first update, from one copy of the node array to the host; the topology never changes.
+// Also here: the SAH cost of the tree as it is (tree_cost.hpp; adypt_get_tree_cost) and the refit that rebuilds when that cost says so
+// (adypt_update_triangles_auto):
+//     k_tree_cost      one launch over the node array, 8 lanes per node, one slot per lane: two 64-bit integer sums
 #include "ctx_unit.hpp"
 #include "refit_plan.hpp"
 #include "refit_internal.hpp"
+#include "ploc.hpp"
+#include "tree_cost.hpp"
 #include "woop.hpp"
 #include "../../../include/adypt_hip.h"
+#include "../../../include/adypt_host.h"
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -140,6 +147,63 @@ template <bool REF_BOXES> __global__ __launch_bounds__(kRefitThreads) void k_ref
 	if(rewrite && s < kNodeUint4) nodes[node * kNodeUint4 + s] = s_node[g][s];
 }
 
+
+// The two sums of tree_cost.hpp over nodes [0, n_nodes), n_nodes >= 1.  The lanes of a node read its 80 bytes as five 16-byte loads — a wave reads 640
+// contiguous bytes — into LDS, and lane s takes slot s from there.  Node 0, whose union is the root area of every slot, is read at a uniform address
+// by every wave and decoded in registers.  The sums are added up across the wave by xor-shuffles, across the workgroup's waves in LDS, and one
+// workgroup adds each sum to words[0] (inner_q) and words[1] (leaf_q) with one 64-bit atomic; words[2] takes the flags.  Nobody waits for anybody.
+enum CostFlag : uint32_t { kCostFlagRoot = 1u, kCostFlagRatio = 2u };
+constexpr int kCostWaves = kRefitThreads / 64;
+__global__ __launch_bounds__(kRefitThreads) void k_tree_cost(const uint4 *__restrict__ nodes, int n_nodes, unsigned long long *words)
+{
+	__shared__ uint4 s_node[kNodesPerGroup][kNodeUint4];
+	__shared__ unsigned long long s_sum[kCostWaves][2];
+	const int g = threadIdx.x / kLanesPerNode, s = threadIdx.x % kLanesPerNode;
+	const int64_t k = (int64_t)blockIdx.x * kNodesPerGroup + g;
+	const bool valid = k < (int64_t)n_nodes;
+	if(valid && s < kNodeUint4) s_node[g][s] = nodes[(size_t)k * kNodeUint4 + s];
+	uint32_t root[kNodeBytes / 4];
+	for(int j = 0; j < kNodeUint4; ++j)
+	{
+		const uint4 v = nodes[j];
+		root[j * 4] = v.x; root[j * 4 + 1] = v.y; root[j * 4 + 2] = v.z; root[j * 4 + 3] = v.w;
+	}
+	const float A = cost_root_area(root);
+	__syncthreads();
+	uint64_t inner_q = 0, leaf_q = 0;
+	if(!cost_root_valid(A))
+	{
+		if(blockIdx.x == 0 && threadIdx.x == 0) atomicOr(words + 2, (unsigned long long)kCostFlagRoot);
+	}
+	else if(valid)
+	{
+		const uint8_t *bytes = (const uint8_t *)s_node[g];
+		const uint32_t meta = bytes[kNodeMeta + s];
+		if(meta != 0)
+		{
+			uint32_t q[6], e[3];
+			cost_slot_bytes(bytes, s, q, e);
+			const CostShare share = cost_slot(meta, cost_area(q, e), A);
+			inner_q = share.inner_q;
+			leaf_q = share.leaf_q;
+			if(!share.ok) atomicOr(words + 2, (unsigned long long)kCostFlagRatio);
+		}
+	}
+	for(int m = 1; m < 64; m <<= 1)
+	{
+		inner_q += (uint64_t)__shfl_xor((unsigned long long)inner_q, m);
+		leaf_q += (uint64_t)__shfl_xor((unsigned long long)leaf_q, m);
+	}
+	if(threadIdx.x % 64 == 0) { s_sum[threadIdx.x / 64][0] = inner_q; s_sum[threadIdx.x / 64][1] = leaf_q; }
+	__syncthreads();
+	if(threadIdx.x < 2)
+	{
+		unsigned long long sum = 0;
+		for(int w = 0; w < kCostWaves; ++w) sum += s_sum[w][threadIdx.x];
+		if(sum) atomicAdd(words + threadIdx.x, sum);
+	}
+}
+
 constexpr int kTimingEvents = 4; // start, scatter, references + Woop, nodes
 
 // Everything the refit keeps per context; parked in the context (ctx_attachment), freed by adypt_destroy (the context's device is current then).
@@ -148,6 +212,11 @@ struct Refitter {
 	bool have_plan = false;
 	Buffer<float> d_stage;     // the caller's positions and normals on their way to the records: up to 72 B per updated triangle
 	StageTimer<kTimingEvents> timer;
+	// the cost of the tree (tree_cost.hpp)
+	Buffer<unsigned long long> d_cost;  // inner_q, leaf_q, the flags
+	StageTimer<2> cost_timer;
+	adypt_tree_cost built{};            // the sums of the tree as uploaded or as last rebuilt, once measured (priced anew by every call)
+	bool have_built = false;
 };
 
 // the levels from one copy of the node array, the lists and the box array on the device (the context is drained)
@@ -167,6 +236,48 @@ int ensure_plan(adypt_ctx *c, Refitter *rf, const CtxScene &sc, hipStream_t stre
 	CTX_TRY(c, hipStreamSynchronize(stream));
 	rf->have_plan = true;
 	return ADYPT_OK;
+}
+
+// the cost of the context's tree as it is now, on the stream (the context is drained); *ms: the HIP-event time of the kernel
+int measure_cost(adypt_ctx *c, Refitter *rf, hipStream_t stream, const adypt_bvh_params &cfg, const char *who, adypt_tree_cost *out, float *ms)
+{
+	const CtxScene sc = ctx_scene(c);
+	if(sc.n_nodes <= 0) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": the tree has no nodes");
+	if(sc.n_nodes > kCostMaxNodes) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": more than 2^26 nodes");
+	CTX_TRY(c, at_least(rf->d_cost, 3));
+	unsigned long long words[3] = {0, 0, 0};
+	CTX_TRY(c, hipMemsetAsync(rf->d_cost.get(), 0, sizeof(words), stream));
+	CTX_TRY(c, rf->cost_timer.mark(0, stream));
+	hipLaunchKernelGGL(k_tree_cost, dim3(grid_of(sc.n_nodes, kNodesPerGroup)), dim3(kRefitThreads), 0, stream, (const uint4 *)sc.nodes, (int)sc.n_nodes, rf->d_cost.get());
+	CTX_TRY(c, hipGetLastError());
+	CTX_TRY(c, rf->cost_timer.mark(1, stream));
+	CTX_TRY(c, hipMemcpyAsync(words, rf->d_cost.get(), sizeof(words), hipMemcpyDeviceToHost, stream));
+	CTX_TRY(c, hipStreamSynchronize(stream));
+	if(words[2] & kCostFlagRoot) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": the root's box has no positive finite area");
+	if(words[2] & kCostFlagRatio) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": a slot is not below four times the root's area");
+	if(ms) rf->cost_timer.read(ms, 1, 1, false);
+	*out = adypt_tree_cost{cost_value((double)cfg.node_sah, (double)cfg.triangle_sah, words[0], words[1]), words[0], words[1], sc.n_nodes};
+	return ADYPT_OK;
+}
+
+// the reference of the pose policy: measured now unless it has been since the upload or the last rebuild; priced with this call's costs
+int built_cost(adypt_ctx *c, Refitter *rf, hipStream_t stream, const adypt_bvh_params &cfg, const char *who, adypt_tree_cost *out)
+{
+	if(!rf->have_built)
+	{
+		CTX_STEP(measure_cost(c, rf, stream, cfg, who, &rf->built, nullptr));
+		rf->have_built = true;
+	}
+	*out = rf->built;
+	out->cost = cost_value((double)cfg.node_sah, (double)cfg.triangle_sah, out->inner_q, out->leaf_q);
+	return ADYPT_OK;
+}
+
+bool cost_params(const adypt_bvh_params *params, adypt_bvh_params *cfg)
+{
+	*cfg = adypt_bvh_params{0, 0.3f, 1.0f}; // InstanceConfig::BVH's defaults
+	if(params) *cfg = *params;
+	return cfg->triangle_sah > 0.0f && cfg->triangle_sah < kCutMax && cfg->node_sah > 0.0f && cfg->node_sah < kCutMax; // (what the rebuilds accept)
 }
 
 }  // namespace
@@ -200,6 +311,7 @@ void refit_adopt_tree(adypt_ctx *c, TreeLevels &&tree)
 	rf->tree = std::move(tree); // (the old tree's lists and boxes go with `tree`)
 	rf->have_plan = true;
 	rf->timer.invalidate();
+	rf->have_built = false; // (a new tree: its cost is measured when it is first asked for)
 }
 
 }  // namespace adypt
@@ -240,6 +352,64 @@ int adypt_update_triangles(adypt_ctx *c, int64_t first, int64_t count, const flo
 	CTX_TRY(c, hipStreamSynchronize(i.stream));
 	rf->timer.complete();
 	return adypt_reset(c); // the image, the frozen blocks, the frames parked ahead and the primary-hit cache were the old pose's
+}
+
+int adypt_get_tree_cost(adypt_ctx *c, const adypt_bvh_params *params, adypt_tree_cost *out)
+{
+	if(!c) return ADYPT_E_INVALID;
+	if(!out) return ctx_fail(c, ADYPT_E_INVALID, "adypt_get_tree_cost: out is null");
+	adypt_bvh_params cfg;
+	if(!cost_params(params, &cfg)) return ctx_fail(c, ADYPT_E_INVALID, "adypt_get_tree_cost: the SAH costs must be positive finite numbers");
+	const CtxInfo i = ctx_info(c);
+	CTX_TRY(c, hipSetDevice(i.device));
+	CTX_STEP(ctx_drain(c));
+	Refitter *rf = ctx_state<Refitter>(c, kAttachRefit);
+	adypt_tree_cost now;
+	CTX_STEP(measure_cost(c, rf, i.stream, cfg, "adypt_get_tree_cost", &now, nullptr));
+	if(!rf->have_built) { rf->built = now; rf->have_built = true; }
+	*out = now;
+	return ADYPT_OK;
+}
+
+int adypt_update_triangles_auto(adypt_ctx *c, int64_t first, int64_t count, const float *positions, const float *normals, const adypt_bvh_params *params,
+                                const adypt_pose_policy *policy, adypt_pose_outcome *outcome)
+{
+	if(!c) return ADYPT_E_INVALID;
+	const char *who = "adypt_update_triangles_auto";
+	const CtxScene sc = ctx_scene(c);
+	if(!positions) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": positions is null");
+	if(!policy) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": policy is null");
+	if(first < 0 || count < 0 || first > sc.n_tris || count > sc.n_tris - first)
+		return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": triangles [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) + ") are not all of the scene's " + std::to_string(sc.n_tris));
+	adypt_bvh_params cfg;
+	if(!cost_params(params, &cfg)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": the SAH costs must be positive finite numbers");
+	const adypt_pose_policy p = *policy;
+	if(!(p.rebuild_above >= 0.0 && std::isfinite(p.rebuild_above))) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": rebuild_above must be a finite number >= 0");
+	if(p.method != 0 && p.method != 1) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": method must be 0 (linear) or 1 (ploc)");
+	if(p.method == 1 && (p.radius < kPlocMinRadius || p.radius > kPlocMaxRadius)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": the radius must be in [1, 32]");
+	if(!(p.split_budget >= 0.0 && p.split_budget <= 1.0)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": the split budget must be in [0, 1]");
+	if(p.method == 0 && p.split_budget != 0.0) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": a split budget needs method 1 (ploc)");
+	const CtxInfo i = ctx_info(c);
+	CTX_TRY(c, hipSetDevice(i.device));
+	CTX_STEP(ctx_drain(c));
+	Refitter *rf = ctx_state<Refitter>(c, kAttachRefit);
+	adypt_pose_outcome o{};
+	CTX_STEP(built_cost(c, rf, i.stream, cfg, who, &o.built)); // (of the tree as it is before this call's refit)
+	CTX_STEP(adypt_update_triangles(c, first, count, positions, normals));
+	const int measured = measure_cost(c, rf, i.stream, cfg, who, &o.refitted, &o.cost_ms);
+	if(measured != ADYPT_OK) return ctx_fail(c, measured, std::string(adypt_last_error(c)) + " (the triangles have been updated and the tree refitted; nothing was rebuilt)");
+	o.now = o.refitted;
+	if(o.refitted.cost > p.rebuild_above * o.built.cost)
+	{
+		// (a rebuild that is refused or fails has left the refitted tree in place and set the error)
+		if(p.method == 0) CTX_STEP(adypt_rebuild_bvh(c, &cfg, &o.rebuild));
+		else if(p.split_budget == 0.0) CTX_STEP(adypt_rebuild_bvh_ploc(c, &cfg, p.radius, &o.rebuild));
+		else CTX_STEP(adypt_rebuild_bvh_ploc_split(c, &cfg, p.radius, p.split_budget, &o.rebuild));
+		o.rebuilt = 1;
+		CTX_STEP(built_cost(c, rf, i.stream, cfg, who, &o.now)); // (the rebuild has marked it stale: the new tree's, which is the reference from here on)
+	}
+	if(outcome) *outcome = o;
+	return ADYPT_OK;
 }
 
 int adypt_read_bvh(adypt_ctx *c, void *nodes_out, float *woop_out)
@@ -288,6 +458,43 @@ int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, c
 {
 	// (a bad range is refused by the first context: none has changed)
 	return multi_each(m, [=](adypt_ctx *c) { return adypt_update_triangles(c, first, count, positions, normals); });
+}
+
+// every device measures its own copy: the sums are integers, so all must agree
+int adypt_multi_get_tree_cost(adypt_multi *m, const adypt_bvh_params *params, adypt_tree_cost *out)
+{
+	adypt_tree_cost head{};
+	int k = 0;
+	if(m && !out) { multi_set_error(m, "adypt_multi_get_tree_cost: out is null"); return ADYPT_E_INVALID; }
+	const int r = multi_each(m, [&](adypt_ctx *c) {
+		adypt_tree_cost t{};
+		CTX_STEP(adypt_get_tree_cost(c, params, &t));
+		if(k++ == 0) head = t;
+		else if(t.inner_q != head.inner_q || t.leaf_q != head.leaf_q || t.n_nodes != head.n_nodes)
+			return ctx_fail(c, ADYPT_E_HIP, "adypt_multi_get_tree_cost: device " + std::to_string(k - 1) + " holds another tree than device 0");
+		return (int)ADYPT_OK;
+	});
+	if(r == ADYPT_OK) *out = head;
+	return r;
+}
+
+int adypt_multi_update_triangles_auto(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals, const adypt_bvh_params *params,
+                                      const adypt_pose_policy *policy, adypt_pose_outcome *outcome)
+{
+	// (bad arguments are refused by the first context: none has changed)
+	adypt_pose_outcome head{};
+	int k = 0;
+	const int r = multi_each(m, [&](adypt_ctx *c) {
+		adypt_pose_outcome o{};
+		CTX_STEP(adypt_update_triangles_auto(c, first, count, positions, normals, params, policy, &o));
+		if(k++ == 0) head = o;
+		else if(o.rebuilt != head.rebuilt || o.refitted.inner_q != head.refitted.inner_q || o.refitted.leaf_q != head.refitted.leaf_q || o.now.inner_q != head.now.inner_q || o.now.leaf_q != head.now.leaf_q ||
+		        o.built.inner_q != head.built.inner_q || o.built.leaf_q != head.built.leaf_q)
+			return ctx_fail(c, ADYPT_E_HIP, "adypt_multi_update_triangles_auto: device " + std::to_string(k - 1) + " measured or decided otherwise than device 0: the trees differ from here on");
+		return (int)ADYPT_OK;
+	});
+	if(r == ADYPT_OK && outcome) *outcome = head;
+	return r;
 }
 
 }  // extern "C"

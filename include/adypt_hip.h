@@ -302,7 +302,8 @@ int adypt_get_denoise_timing(adypt_ctx *ctx, float *ms, int capacity);
  * moved triangles byte for byte (the 12 Woop floats of a degenerate triangle are NaN on both sides; a NaN's sign and payload are the processor's).  Material ids and texture coordinates stay.  The context is drained first (frames enqueued earlier finish with the old
  * pose) and is left as adypt_reset leaves it: 0 spp, frozen blocks thawed, frames parked ahead dropped, the primary-hit cache invalid.  A refitted tree
  * renders the moved scene correctly but is slower to traverse than a rebuilt one, the more the further the pose is from the one the tree was built
- * for, and more so for trees built with spatial splits (Moving geometry): rebuild for poses that are far away.
+ * for, and more so for trees built with spatial splits (Moving geometry): rebuild for poses that are far away — adypt_update_triangles_auto
+ * (below) measures how far that is and decides.
  * ADYPT_E_INVALID (a range outside the scene, positions NULL) changes nothing.  The first call makes the refit plan from one device-to-host copy of the
  * nodes and allocates 36 B per node; every call stages the caller's arrays on the device (up to 72 B per updated triangle, kept). */
 int adypt_update_triangles(adypt_ctx *ctx, int64_t first, int64_t count, const float *positions, const float *normals);
@@ -372,6 +373,50 @@ int adypt_get_rebuild_timing(adypt_ctx *ctx, float *ms, int capacity);
 int adypt_get_bvh_sizes(adypt_ctx *ctx, int64_t *n_nodes, int64_t *n_refs);
 /* the reference order (n_refs triangle indices) as it is on the device */
 int adypt_read_tri_indices(adypt_ctx *ctx, int32_t *out);
+
+/* ---- refit or rebuild: the SAH cost of the tree as it is now decides ------------------------------------------------------------------------
+ * adypt_get_tree_cost measures the tree the context holds: adypt_bvh_cost (adypt_host.h; the definition is csrc/device/tree_cost.hpp, compiled by
+ * both) of adypt_read_bvh's nodes, to the same two integers, by one pass over the node array (k_tree_cost) on the context's stream after the context
+ * has been drained.  Nothing of the context changes.  params as for adypt_bvh_cost.  ADYPT_E_INVALID for what adypt_bvh_cost refuses. */
+#ifndef ADYPT_TREE_COST_DEFINED
+#define ADYPT_TREE_COST_DEFINED
+typedef struct adypt_tree_cost {
+	double cost;
+	uint64_t inner_q, leaf_q;
+	int64_t n_nodes;
+} adypt_tree_cost;
+#endif
+int adypt_get_tree_cost(adypt_ctx *ctx, const adypt_bvh_params *params, adypt_tree_cost *out);
+/* adypt_update_triangles that rebuilds the tree when refitting has made it too expensive to traverse.  In this order: every argument is checked; the
+ * refit of adypt_update_triangles (the same launches, the same bytes afterwards); the cost of the refitted tree; and, if
+ * refitted.cost > rebuild_above * built.cost, the rebuild the policy names — method 0: adypt_rebuild_bvh(ctx, params, ..), method 1:
+ * adypt_rebuild_bvh_ploc(ctx, params, radius, ..), or adypt_rebuild_bvh_ploc_split with split_budget where that is not 0 — after which `now` is the cost
+ * of the new tree, which becomes the new `built`.  Otherwise now = refitted.
+ * `built` is the cost of the tree as adypt_create uploaded it or as the last rebuild of any kind left it.  It is measured lazily, on the tree as it is
+ * at the first adypt_get_tree_cost or adypt_update_triangles_auto after the create or rebuild (in this call: before its refit); those calls launch what
+ * they always launched and only mark `built` as stale.  So plain adypt_update_triangles calls made before that first measurement are part of what
+ * `built` describes: measure once (adypt_get_tree_cost) after the upload when the reference is to be the rest pose.  What is kept of `built` are its two
+ * integer sums; every call prices them with its own params.
+ * rebuild_above has no default: finite and >= 0; 0 always rebuilds (Moving geometry, for how to choose it).  radius and split_budget count
+ * for method 1 only (split_budget must be 0 for method 0) and obey the rules of the rebuild they are passed to.  outcome may be NULL.
+ * ADYPT_E_INVALID for a bad argument changes nothing.  A cost that cannot be taken after the refit (an invalid tree: a root without area) returns
+ * ADYPT_E_INVALID with the refit in place, and the error text says so.  A rebuild that is refused or fails returns its error and leaves the refitted
+ * tree in place and usable, as adypt_rebuild_bvh* promise.  The context is left as adypt_reset leaves it.  cost_ms: the HIP-event time of the cost
+ * kernel behind the refit. */
+typedef struct adypt_pose_policy {
+	double rebuild_above;
+	int32_t method;              /* 0 linear, 1 ploc */
+	int32_t radius;
+	double split_budget;
+} adypt_pose_policy;
+typedef struct adypt_pose_outcome {
+	adypt_tree_cost built, refitted, now;   /* built: the reference the decision was taken against */
+	int32_t rebuilt;             /* 1: the policy's rebuild ran */
+	adypt_rebuild_info rebuild;  /* of that rebuild; zeros otherwise */
+	float cost_ms;
+} adypt_pose_outcome;
+int adypt_update_triangles_auto(adypt_ctx *ctx, int64_t first, int64_t count, const float *positions, const float *normals, const adypt_bvh_params *params,
+                                const adypt_pose_policy *policy, adypt_pose_outcome *outcome);
 
 /* Trace an arbitrary batch of rays through the same traversal kernel: rays = n x 8 floats
  * (ox, oy, oz, tmin, dx, dy, dz, unused).  with_stats selects the instrumented kernel variant. */
@@ -485,6 +530,12 @@ int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, c
 int adypt_multi_rebuild_bvh(adypt_multi *m, const adypt_bvh_params *params, adypt_rebuild_info *out);
 int adypt_multi_rebuild_bvh_ploc(adypt_multi *m, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out); /* likewise */
 int adypt_multi_rebuild_bvh_ploc_split(adypt_multi *m, const adypt_bvh_params *params, int radius, double split_budget, adypt_rebuild_info *out); /* likewise */
+/* adypt_get_tree_cost / adypt_update_triangles_auto on every device.  The scene is replicated and the cost is two integer sums, so every device
+ * measures the same and decides alike; *out / *outcome are the first device's (cost_ms too).  A device whose integers or decision differ from the
+ * first one's ends the call with ADYPT_E_HIP and a text rather than letting the trees diverge.  No collective. */
+int adypt_multi_get_tree_cost(adypt_multi *m, const adypt_bvh_params *params, adypt_tree_cost *out);
+int adypt_multi_update_triangles_auto(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals, const adypt_bvh_params *params,
+                                      const adypt_pose_policy *policy, adypt_pose_outcome *outcome);
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

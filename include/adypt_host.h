@@ -127,6 +127,24 @@ int64_t adypt_bvh_tri_indices(const adypt_bvh *b, const int32_t **idx);
  * slower to traverse (Moving geometry).  ADYPT_E_INVALID — nothing is written — for arrays that are not one tree: a child index or a
  * reference range out of range, a node reached twice or not at all, a triangle index out of range. */
 int adypt_bvh_refit(void *nodes, int64_t n_nodes, const int32_t *tri_indices, int64_t n_refs, const void *triangles, int64_t n_tris);
+/* The SAH cost of a tree as the traversal sees it, from the quantised child boxes of the 80-byte nodes alone: every occupied slot's area over the area
+ * of the root (the union of node 0's slots), as an integer q = the ratio * 2^30 cut off; inner_q is the sum of q over the slots that hold a child
+ * node, leaf_q the sum of q * (the slot's references) over the leaf slots, and cost = node_sah * (1 + inner_q / 2^30) + triangle_sah * leaf_q / 2^30 in
+ * binary64: the node visits and triangle tests a random ray through the root is expected to make, priced.  The rule is csrc/device/tree_cost.hpp (the
+ * device path, adypt_get_tree_cost, compiles the same text and gives the same integers).  What it is for: a refitted tree's cost over the cost it had
+ * when it was built says how much slower the refitted tree traverses (Moving geometry; adypt_update_triangles_auto).  params: NULL for the
+ * defaults (triangleSAH 0.3, nodeSAH 1); max_spatial_depth is ignored.  ADYPT_E_INVALID — *out is not written — for no nodes or more than 2^26, SAH
+ * costs that are not positive finite numbers, a root without a positive finite area (all triangles at one point) and a slot of four times the root's
+ * area or more. */
+#ifndef ADYPT_TREE_COST_DEFINED
+#define ADYPT_TREE_COST_DEFINED
+typedef struct adypt_tree_cost {
+	double cost;
+	uint64_t inner_q, leaf_q;
+	int64_t n_nodes;
+} adypt_tree_cost;
+#endif
+int adypt_bvh_cost(const void *nodes, int64_t n_nodes, const adypt_bvh_params *params, adypt_tree_cost *out);
 
 /* ---- small restated host functions ---------------------------------------------------------------------------- */
 /* One 80-byte CWBVH8 node decoded into the 264-byte root card of the device's k_path (csrc/device/root_card.hpp: the definition, which the device

@@ -219,6 +219,36 @@ public:
 		return false;
 	}
 
+	// The SAH cost of the tree the devices hold now, measured there from the quantised boxes (adypt_hip.h, adypt_get_tree_cost): what a refitted tree's
+	// traversal work is proportional to.  params: the BVH section's SAH costs (nullptr: its defaults).
+	bool GetTreeCost(adypt_tree_cost *cost, const adypt_bvh_params *params = nullptr)
+	{
+		if(adypt_multi_get_tree_cost(m_gpus, params, cost) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
+	// UpdateTriangles that decides about a rebuild itself (adypt_hip.h, adypt_update_triangles_auto): after the refit the tree's cost is measured, and where
+	// it is above policy.rebuild_above times the cost the tree had as uploaded or as last rebuilt, the tree is rebuilt as RebuildBVH(params, ..., method,
+	// radius, split_budget) would.  rebuild_above has no default: see DESIGN.md, Moving geometry, for how to choose it.  *outcome (may be nullptr): the
+	// three costs, whether the rebuild ran, and its info.
+	struct PosePolicy
+	{
+		double rebuild_above;
+		RebuildMethod method;
+		int radius;
+		double split_budget;
+		explicit PosePolicy(double above, RebuildMethod m = RebuildMethod::PLOC, int r = 8, double budget = 0.0) : rebuild_above(above), method(m), radius(r), split_budget(budget) {}
+	};
+	bool UpdateTriangles(int64_t first, int64_t count, const float *positions, const float *normals, const PosePolicy &policy, adypt_pose_outcome *outcome = nullptr,
+	                     const adypt_bvh_params *params = nullptr)
+	{
+		const adypt_pose_policy p = {policy.rebuild_above, policy.method == RebuildMethod::PLOC ? 1 : 0, policy.radius, policy.split_budget};
+		if(adypt_multi_update_triangles_auto(m_gpus, first, count, positions, normals, params, &p, outcome) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
 	// what DrawScreen puts on screen, for a caller-owned W x H RGBA8 texture / window (every device fills in its own tiles)
 	bool ReadScreen(std::vector<uint8_t> *rgba8) const
 	{

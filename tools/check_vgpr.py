@@ -1,4 +1,4 @@
-"""Build check (run by __graft_entry__.build()): the VGPR count of every gfx950 kernel of the library, and one rule for the kernels that
+"""Build check (run by __graft_entry__.build()): the VGPR count of every gfx950 kernel of the library (and its scratch, where it has any), and one rule for the kernels that
 compact their survivors with append_slot (shade.hpp).
 
 The rule: a kernel that contains append_slot must be allocated MORE THAN 16 VGPRs.  Round 3's queue corruption (whole waves claiming one
@@ -19,23 +19,24 @@ def kernels(src):
     subprocess.check_call(["make", "-s", "-C", CSRC, "asm"], stdout=subprocess.DEVNULL)
     text = open(os.path.join(CSRC, "build", os.path.basename(src).replace(".hip", ".s"))).read()
     counts = dict((n, int(v)) for n, v in re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text))
+    scratch = dict((n, int(v)) for n, v in re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", text))
     out = []
     for name, n in counts.items():
         m = re.search(r"\n" + re.escape(name) + r":.*?\n\s+s_endpgm", text, re.S)
         body = m.group(0) if m else ""
         # append_slot: s_barrier ... global_atomic_add (returning: sc0) ... s_barrier ... v_mbcnt_hi
         uses = re.search(r"s_barrier.*?global_atomic_add\s+v\d+,.*?sc0.*?s_barrier.*?v_mbcnt_hi_u32_b32", body, re.S) is not None and "ds_cmpst" not in body
-        out.append((name, n, uses))
+        out.append((name, n, uses, scratch.get(name, 0)))
     return out
 
 
 def main():
     bad = []
     for src in ("device/tracer.hip", "device/multi.hip", "device/denoise.hip", "device/refit.hip", "device/build.hip"):
-        for name, n, uses in sorted(kernels(src)):
-            flag = ""
+        for name, n, uses, private in sorted(kernels(src)):
+            flag = "  scratch: %d B per lane" % private if private else ""
             if uses:
-                flag = "  append_slot: needs > 16" + ("" if n >= MIN_VGPRS else "  <-- VIOLATION")
+                flag += "  append_slot: needs > 16" + ("" if n >= MIN_VGPRS else "  <-- VIOLATION")
                 if n < MIN_VGPRS:
                     bad.append(name)
             print("%4d  %s%s" % (n, name, flag))
