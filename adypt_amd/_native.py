@@ -206,6 +206,15 @@ _SIGS = {
     "adypt_multi_rebuild_bvh_ploc_split": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.c_int, C.c_double, C.POINTER(RebuildInfo)]),
     "adypt_get_rebuild_presplit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "adypt_read_ref_boxes": (C.c_int64, [C.c_void_p, C.c_void_p]),
+    # replacing the triangles on the GPU
+    "adypt_set_triangles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(BvhParams), C.c_int, C.c_int, C.c_double, C.POINTER(RebuildInfo)]),
+    "adypt_create_from_triangles": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(BvhParams), C.c_int, C.c_int, C.c_double, C.POINTER(RebuildInfo)]),
+    "adypt_get_triangle_count": (C.c_int64, [C.c_void_p]),
+    "adypt_read_triangle_records": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_get_set_triangles_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
+    "adypt_multi_set_triangles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(BvhParams), C.c_int, C.c_int, C.c_double, C.POINTER(RebuildInfo)]),
+    "adypt_create_multi_from_triangles": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(BvhParams), C.c_int, C.c_int, C.c_double,
+                                                    C.POINTER(RebuildInfo)]),
     # refit or rebuild by the tree's SAH cost
     "adypt_get_tree_cost": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(TreeCost)]),
     "adypt_update_triangles_auto": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
@@ -278,6 +287,7 @@ _SIGS = {
     "adypt_bvh_refit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "adypt_bvh_cost": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(BvhParams), C.POINTER(TreeCost)]),
     "adypt_woop_matrices": (None, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "adypt_pack_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "adypt_decode_root_card": (None, [C.c_void_p, C.c_int, C.c_void_p]),
     "adypt_camera_matrices": (None, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "adypt_sobol_points": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -374,7 +374,10 @@ class HipScene:
     """OglScene: the flat arrays the kernels consume.  Initialize(scene, bvh) only records host arrays; the upload
     to HBM happens in HipPathTracer.Initialize (adypt_create) because the C-ABI creates scene + images together."""
 
-    def Initialize(self, scene: Scene, bvh: WideBVH, woop: Optional[np.ndarray] = None) -> None:
+    def Initialize(self, scene: Scene, bvh: Optional[WideBVH] = None, woop: Optional[np.ndarray] = None) -> None:
+        """bvh None: the tracer builds the first tree on the GPU from the triangles (adypt_create_from_triangles)."""
+        if bvh is None and woop is not None:
+            raise ValueError("HipScene.Initialize: Woop data need the tree they were computed for")
         self.scene, self.bvh = scene, bvh
         self.woop = None if woop is None else np.ascontiguousarray(woop, dtype=np.float32)
 
@@ -390,18 +393,33 @@ def _scene_desc(scene: HipScene, width: int, height: int) -> Tuple[N.SceneDesc, 
     """adypt_scene_desc of `scene` for device 0 and the whole image, and the arrays it points into (to be kept alive while it is in use)."""
     s, b = scene.scene, scene.bvh
     tex_arr = (N.Texture * max(1, len(s.textures)))()
-    keep = [s.triangles, s.materials, b.nodes, b.tri_indices, scene.woop, tex_arr] + list(s.textures)
+    keep = [s.triangles, s.materials, scene.woop, tex_arr] + list(s.textures) + ([] if b is None else [b.nodes, b.tri_indices])
     for i, t in enumerate(s.textures):
         tex_arr[i].width, tex_arr[i].height, tex_arr[i].rgb = t.shape[1], t.shape[0], t.ctypes.data
     d = N.SceneDesc()
-    d.nodes, d.n_nodes = b.nodes.ctypes.data, len(b.nodes) // NODE_BYTES
-    d.tri_indices, d.n_refs = b.tri_indices.ctypes.data, len(b.tri_indices)
+    if b is not None:  # (else: no tree, every field of it null)
+        d.nodes, d.n_nodes = b.nodes.ctypes.data, len(b.nodes) // NODE_BYTES
+        d.tri_indices, d.n_refs = b.tri_indices.ctypes.data, len(b.tri_indices)
     d.woop = None if scene.woop is None else scene.woop.ctypes.data
     d.triangles, d.n_tris = s.triangles.ctypes.data, len(s.triangles) // TRI_BYTES
     d.materials, d.n_mats = (s.materials.ctypes.data if len(s.materials) else None), len(s.materials) // MAT_BYTES
     d.textures, d.n_textures = (C.addressof(tex_arr) if s.textures else None), len(s.textures)
     d.width, d.height, d.device, d.tile_rank, d.tile_nranks = width, height, 0, 0, 1
     return d, keep
+
+
+def _set_triangles_args(who: str, triangles: Optional[np.ndarray], cfg: Optional[N.BvhParams], method: str, radius: int, split_budget: float) -> tuple:
+    """(triangles, n_tris, params, method, radius, split_budget) of adypt_set_triangles / adypt_create_from_triangles (the latter takes the last four);
+    what only Python can get wrong is refused here, everything else by the library."""
+    if method not in ("linear", "ploc"):
+        raise ValueError("%s: method must be 'linear' or 'ploc', not %r" % (who, method))
+    params = None if cfg is None else C.byref(cfg)
+    if triangles is None:  # (the library's refusal to give)
+        return (None, 1, params, 1 if method == "ploc" else 0, int(radius), float(split_budget))
+    t = np.ascontiguousarray(triangles).view(np.uint8).reshape(-1)
+    if len(t) % TRI_BYTES:
+        raise ValueError("%s: the triangles are not a whole number of %d-byte records" % (who, TRI_BYTES))
+    return (t.ctypes.data, len(t) // TRI_BYTES, params, 1 if method == "ploc" else 0, int(radius), float(split_budget))
 
 
 def _read_block_noise(ctx) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -678,6 +696,46 @@ class _Tracer:
             self._call("rebuild_bvh", params, C.byref(info))
         return {k: getattr(info, k) for k, _ in info._fields_}
 
+    # ---- replacing the triangles on the GPU (adypt_set_triangles, include/adypt_hip.h; the record: csrc/device/tri_record.hpp) ----
+    def SetTriangles(self, triangles: np.ndarray, cfg: Optional[N.BvhParams] = None, method: str = "ploc", radius: int = 8, split_budget: float = 0.0) -> dict:
+        """Replaces ALL triangles by the given ones (uint8, n x 100 bytes as Scene.GetTriangles() gives them; any n >= 1) and builds their tree on the
+        GPU as RebuildBVH(cfg, method, radius, split_budget) would; materials, textures, camera and configuration stay.  Nothing changes when the call
+        is refused or fails.  Leaves the tracer as Reset() does (0 spp).  Several devices: on every device.  Returns RebuildBVH's dict."""
+        info = N.RebuildInfo()
+        self._call("set_triangles", *_set_triangles_args("SetTriangles", triangles, cfg, method, radius, split_budget), C.byref(info))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def GetTriangleCount(self) -> int:
+        """The triangles the (first) device holds now."""
+        c = self._contexts()[0]
+        n = N.lib.adypt_get_triangle_count(c)
+        if n < 0:
+            N.check(int(n), c)
+        return int(n)
+
+    def ReadTriangles(self) -> np.ndarray:
+        """The triangles as they are on the (first) device, in Scene.GetTriangles()'s layout (uint8 [n * 100]): unpacked from the 128-byte records."""
+        c = self._contexts()[0]
+        rec = np.zeros((self.GetTriangleCount(), 32), dtype=np.uint32)
+        N.check(N.lib.adypt_read_triangle_records(c, rec.ctypes.data), c)
+        return np.ascontiguousarray(np.concatenate([rec[:, 0:18], rec[:, 20:26], rec[:, 18:19]], axis=1)).view(np.uint8).reshape(-1)
+
+    def ReadTriangleRecords(self) -> np.ndarray:
+        """The raw 128-byte records of the (first) device (uint32 [n, 32])."""
+        c = self._contexts()[0]
+        rec = np.zeros((self.GetTriangleCount(), 32), dtype=np.uint32)
+        N.check(N.lib.adypt_read_triangle_records(c, rec.ctypes.data), c)
+        return rec
+
+    def GetSetTrianglesTiming(self) -> dict:
+        """HIP-event milliseconds of the last SetTriangles() on the (first) device, in front of what GetRebuildTiming() gives for its build."""
+        ms = (C.c_float * 3)()
+        c = self._contexts()[0]
+        n = N.lib.adypt_get_set_triangles_timing(c, ms, 3)
+        if n < 0:
+            N.check(n, c)
+        return {"stage": ms[0], "pack": ms[1], "total": ms[2]}
+
     def GetBVHSizes(self) -> Tuple[int, int]:
         """(n_nodes, n_refs) of the tree the (first) device holds now."""
         n_nodes, n_refs = C.c_int64(), C.c_int64()
@@ -770,13 +828,23 @@ class HipPathTracer(_Tracer):
         return [self._h]
 
     def Initialize(self, config: N.PtParams, scene: HipScene, width: int, height: int, device: int = 0,
-                   tile_rank: int = 0, tile_nranks: int = 1) -> None:
+                   tile_rank: int = 0, tile_nranks: int = 1, method: str = "ploc", radius: int = 8, split_budget: float = 0.0,
+                   cfg: Optional[N.BvhParams] = None) -> None:
+        """A scene without a BVH (HipScene.Initialize(scene)): the first tree is built on the GPU as SetTriangles(cfg=cfg, method=method, radius=radius,
+        split_budget=split_budget) builds it, and build_info is what that returns; with a BVH those four are not looked at and build_info is None."""
         self.destroy()
         self.width, self.height = width, height
         self.tile_rank, self.tile_nranks = tile_rank, tile_nranks
         d, self._keep = _scene_desc(scene, width, height)
         d.device, d.tile_rank, d.tile_nranks = device, tile_rank, tile_nranks
-        N.check(N.lib.adypt_create(C.byref(self._h), C.byref(d)))
+        self.build_info = None
+        if scene.bvh is None:
+            info = N.RebuildInfo()
+            args = _set_triangles_args("HipPathTracer.Initialize", scene.scene.triangles, cfg, method, radius, split_budget)[2:]
+            N.check(N.lib.adypt_create_from_triangles(C.byref(self._h), C.byref(d), *args, C.byref(info)))
+            self.build_info = {k: getattr(info, k) for k, _ in info._fields_}
+        else:
+            N.check(N.lib.adypt_create(C.byref(self._h), C.byref(d)))
         self.SetConfig(config)
 
     def TraceAsync(self, n_spp: int = 1) -> None:
@@ -886,12 +954,21 @@ class MultiPathTracer(_Tracer):
     def _contexts(self):
         return [N.lib.adypt_multi_context(self._m, i) for i in range(self.DeviceCount())]
 
-    def Initialize(self, config: N.PtParams, scene: HipScene, width: int, height: int, devices: Sequence[int] = (0,)) -> None:
+    def Initialize(self, config: N.PtParams, scene: HipScene, width: int, height: int, devices: Sequence[int] = (0,), method: str = "ploc", radius: int = 8,
+                   split_budget: float = 0.0, cfg: Optional[N.BvhParams] = None) -> None:
+        """A scene without a BVH: as HipPathTracer.Initialize, every device building its own copy of the tree (adypt_create_multi_from_triangles)."""
         self.destroy()
         self.width, self.height = width, height
         d, self._keep = _scene_desc(scene, width, height)
         devs = (C.c_int * len(devices))(*devices)
-        self._check(N.lib.adypt_create_multi(C.byref(self._h), C.byref(d), devs, len(devices)))
+        self.build_info = None
+        if scene.bvh is None:
+            info = N.RebuildInfo()
+            args = _set_triangles_args("MultiPathTracer.Initialize", scene.scene.triangles, cfg, method, radius, split_budget)[2:]
+            self._check(N.lib.adypt_create_multi_from_triangles(C.byref(self._h), C.byref(d), devs, len(devices), *args, C.byref(info)))
+            self.build_info = {k: getattr(info, k) for k, _ in info._fields_}
+        else:
+            self._check(N.lib.adypt_create_multi(C.byref(self._h), C.byref(d), devs, len(devices)))
         self.SetConfig(config)
 
     def SetupSeconds(self, i: int) -> float:
@@ -930,32 +1007,34 @@ class Instance:
         self.m_valid = False
 
     def InitializeFromFile(self, filename: str, shift_seed: int = 12345, device: int = 0, tile_rank: int = 0,
-                           tile_nranks: int = 1, devices: Optional[Sequence[int]] = None) -> bool:
+                           tile_nranks: int = 1, devices: Optional[Sequence[int]] = None, build_on_gpu: bool = False) -> bool:
         self.m_filename = filename
         if not self.m_config.LoadFromFile(filename):
             return False
-        return self.Initialize(shift_seed, device, tile_rank, tile_nranks, devices)
+        return self.Initialize(shift_seed, device, tile_rank, tile_nranks, devices, build_on_gpu)
 
     def Initialize(self, shift_seed: int = 12345, device: int = 0, tile_rank: int = 0, tile_nranks: int = 1,
-                   devices: Optional[Sequence[int]] = None) -> bool:
-        """devices: a list of HIP device ordinals -> ONE process drives all of them through adypt_create_multi (tile rank i on
+                   devices: Optional[Sequence[int]] = None, build_on_gpu: bool = False) -> bool:
+        """build_on_gpu: no .bvh cache is read or written and no host build runs; the tracer builds the first tree on the GPU (PLOC, radius 8) with the
+        configuration's SAH costs.
+        devices: a list of HIP device ordinals -> ONE process drives all of them through adypt_create_multi (tile rank i on
         devices[i]; m_path_tracer is then a MultiPathTracer), as integration/HipPathTracer.hpp does for the reference's Instance."""
         cfg = self.m_config
         self.scene = Scene()
         if not self.scene.LoadFromFile(cfg.m_obj_filename):
             return False
-        self.bvh = WideBVH()
         bp = cfg.bvh_params()
-        if not self.bvh.LoadFromFile(cfg.m_bvh_filename, bp):
+        self.bvh = None if build_on_gpu else WideBVH()
+        if self.bvh is not None and not self.bvh.LoadFromFile(cfg.m_bvh_filename, bp):
             self.bvh.Build(self.scene, bp)
             if not self.bvh.SaveToFile(cfg.m_bvh_filename, bp):
                 return False
         self.m_hipscene.Initialize(self.scene, self.bvh)
         if devices is not None:
             self.m_path_tracer = MultiPathTracer()
-            self.m_path_tracer.Initialize(cfg.pt_params(shift_seed), self.m_hipscene, cfg.m_width, cfg.m_height, list(devices))
+            self.m_path_tracer.Initialize(cfg.pt_params(shift_seed), self.m_hipscene, cfg.m_width, cfg.m_height, list(devices), cfg=bp)
         else:
-            self.m_path_tracer.Initialize(cfg.pt_params(shift_seed), self.m_hipscene, cfg.m_width, cfg.m_height, device, tile_rank, tile_nranks)
+            self.m_path_tracer.Initialize(cfg.pt_params(shift_seed), self.m_hipscene, cfg.m_width, cfg.m_height, device, tile_rank, tile_nranks, cfg=bp)
         self.m_camera.Initialize(cfg, cfg.m_width, cfg.m_height)
         ip, iv = self.m_camera.matrices()
         self.m_path_tracer.SetCamera(ip, iv, self.m_camera.position)

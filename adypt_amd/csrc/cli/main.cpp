@@ -5,7 +5,11 @@
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
 //             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild]
-//             [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R]
+//             [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
+//   --build gpu: no .bvh cache is read or written and no tree is built on the host: the context is created from the triangles alone
+//              (adypt_create_multi_from_triangles) and its first tree built on the GPU by --rebuild-method (ploc unless given), --ploc-radius and
+//              --split-budget, which then name that build (and, with --rebuild-above, the policy's rebuild) instead of asking for a rebuild; one
+//              [PT]BUILD: line reports it.  --pose and --rebuild-above work after it as they do otherwise; a bare --rebuild with it, or any other word than gpu (or host, the default), is exit 2
 //   --pose moved.obj: the scene of the config (and its cached .bvh) with the vertices and normals of moved.obj — the same triangles in the same order,
 //              moved — through adypt_multi_update_triangles: the BVH and the Woop data are refitted on the GPU, nothing is rebuilt
 //   --rebuild: a new tree for the triangles as they are then (after --pose, when given), built on the GPU through adypt_multi_rebuild_bvh with the config's
@@ -50,7 +54,7 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
 	std::string noise_out, spp_out, denoise_out, guides_out, pose;
@@ -58,7 +62,7 @@ int main(int argc, char **argv)
 	double rebuild_above = 0.0;
 	std::string rebuild_method = "linear";
 	double split_budget = 0.0;
-	bool have_split_budget = false;
+	bool have_split_budget = false, have_rebuild_method = false, build_on_gpu = false;
 	int ploc_radius = 8;
 	int denoise_levels = 5;
 	int adaptive = 0;
@@ -111,17 +115,25 @@ int main(int argc, char **argv)
 			if(end == argv[i] || *end || !(rebuild_above >= 0.0 && rebuild_above < HUGE_VAL)) { fprintf(stderr, "--rebuild-above takes a finite number >= 0, not %s\n", argv[i]); return 2; }
 			have_rebuild_above = true;
 		}
-		else if(a == "--rebuild-method" && i + 1 < argc) { rebuild_method = argv[++i]; rebuild = true; }
+		else if(a == "--rebuild-method" && i + 1 < argc) { rebuild_method = argv[++i]; rebuild = have_rebuild_method = true; }
+		else if(a == "--build" && i + 1 < argc)
+		{
+			const std::string where = argv[++i];
+			if(where != "gpu" && where != "host") { fprintf(stderr, "--build is gpu or host, not %s\n", where.c_str()); return 2; }
+			build_on_gpu = where == "gpu";
+		}
 		else if(a == "--ploc-radius" && i + 1 < argc) ploc_radius = atoi(argv[++i]);
 		else if(a == "--split-budget" && i + 1 < argc) { split_budget = atof(argv[++i]); have_split_budget = true; }
 		else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
 	}
 	const bool until = noise_target >= 0.0;
+	if(build_on_gpu && bare_rebuild) { fprintf(stderr, "--build gpu has just built the tree: name its method with --rebuild-method, without --rebuild\n"); return 2; }
+	if(build_on_gpu && !have_rebuild_method) rebuild_method = "ploc";
 	if(rebuild_method != "linear" && rebuild_method != "ploc") { fprintf(stderr, "--rebuild-method is linear or ploc\n"); return 2; }
 	if(have_split_budget && rebuild_method != "ploc") { fprintf(stderr, "--split-budget needs --rebuild-method ploc\n"); return 2; }
 	if(have_rebuild_above && pose.empty()) { fprintf(stderr, "--rebuild-above needs --pose moved.obj\n"); return 2; }
 	if(have_rebuild_above && bare_rebuild) { fprintf(stderr, "--rebuild-above decides about the rebuild itself: name its method with --rebuild-method, without --rebuild\n"); return 2; }
-	if(have_rebuild_above) rebuild = false; // (--rebuild-method names the policy's rebuild)
+	if(have_rebuild_above || build_on_gpu) rebuild = false; // (--rebuild-method names the policy's rebuild, or the first build)
 	if(!until && !noise_out.empty()) { fprintf(stderr, "--noise-out needs --noise T\n"); return 2; }
 	if(until && (primary >= 0 || spp < 2 || check_every < 1)) { fprintf(stderr, "--noise needs --spp >= 2, --check-every >= 1 and no --primary\n"); return 2; }
 	if(adaptive && (!until || save_every > 0)) { fprintf(stderr, "--adaptive needs --noise T and does not combine with --save-every\n"); return 2; }
@@ -161,7 +173,7 @@ int main(int argc, char **argv)
 	}
 
 	adypt_bvh *bvh = nullptr;
-	if(adypt_bvh_load(cfg.bvh_filename, &cfg.bvh, &bvh) != ADYPT_OK)
+	if(!build_on_gpu && adypt_bvh_load(cfg.bvh_filename, &cfg.bvh, &bvh) != ADYPT_OK)
 	{
 		adypt_build_info info;
 		if(adypt_bvh_build(scene, &cfg.bvh, &bvh, &info) != ADYPT_OK) { fprintf(stderr, "[INSTANCE]Err: bvh build failed: %s\n", adypt_host_last_error()); return 1; }
@@ -172,14 +184,20 @@ int main(int argc, char **argv)
 	const void *nodes; const int32_t *idx;
 	adypt_scene_desc d;
 	memset(&d, 0, sizeof(d));
-	d.n_nodes = adypt_bvh_nodes(bvh, &nodes); d.nodes = nodes;
-	d.n_refs = adypt_bvh_tri_indices(bvh, &idx); d.tri_indices = idx;
+	if(bvh)
+	{
+		d.n_nodes = adypt_bvh_nodes(bvh, &nodes); d.nodes = nodes;
+		d.n_refs = adypt_bvh_tri_indices(bvh, &idx); d.tri_indices = idx;
+	}
 	d.triangles = tris; d.n_tris = n_tris; d.materials = mats; d.n_mats = n_mats;
 	d.textures = (const adypt_texture *)tex; d.n_textures = n_tex;
 	d.width = cfg.width; d.height = cfg.height; d.device = devices[0]; d.tile_rank = 0; d.tile_nranks = 1;
 	// any number of devices through the library's multi-device boundary (one device is its n_dev = 1 case): tile rank i on devices[i], one gather per saved image
 	adypt_multi *multi = nullptr;
-	if(adypt_create_multi(&multi, &d, devices.data(), (int)devices.size()) != ADYPT_OK)
+	const bool ploc = rebuild_method == "ploc";
+	adypt_rebuild_info first_build;
+	if((build_on_gpu ? adypt_create_multi_from_triangles(&multi, &d, devices.data(), (int)devices.size(), &cfg.bvh, ploc ? 1 : 0, ploc_radius, split_budget, &first_build)
+	                 : adypt_create_multi(&multi, &d, devices.data(), (int)devices.size())) != ADYPT_OK)
 	{
 		fprintf(stderr, "[TRACER]Err: %s\n", adypt_multi_last_error(nullptr));
 		return 1;
@@ -196,7 +214,6 @@ int main(int argc, char **argv)
 	if(r == ADYPT_OK) r = adypt_multi_set_instrumentation(multi, 1);
 	if(r == ADYPT_OK && (until || denoise)) r = adypt_multi_set_noise_stats(multi, 1);
 	if(r != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
-	const bool ploc = rebuild_method == "ploc";
 	// the figures of a rebuild that has just run: what the rebuild line prints
 	auto rebuild_figures = [&](const adypt_rebuild_info &info) {
 		float ms[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -215,6 +232,7 @@ int main(int argc, char **argv)
 		         (long long)info.n_refs, (int)info.levels, method.c_str(), ms[6], ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
 		return std::string(text);
 	};
+	if(build_on_gpu) printf("[PT]BUILD: %s\n", rebuild_figures(first_build).c_str());
 	if(!pose.empty())
 	{
 		adypt_pose_outcome outcome;
@@ -369,7 +387,7 @@ int main(int argc, char **argv)
 		printf("[PT]INFO: Saved guide images to %s.{albedo,normal,position}.exr\n", guides_out.c_str());
 	}
 	adypt_destroy_multi(multi);
-	adypt_bvh_free(bvh);
+	if(bvh) adypt_bvh_free(bvh);
 	adypt_scene_free(scene);
 	// like ~Instance (src/Instance.cpp:83-86): the config is written back on exit
 	adypt_config_save(argv[1], &cfg);

@@ -34,6 +34,7 @@
 // Everything is built into new arrays; the context takes them last (ctx_replace_bvh), so a refused or failed call leaves the old tree usable.
 #include "ctx_unit.hpp"
 #include "refit_internal.hpp"
+#include "build_internal.hpp"
 #include "lbvh.hpp"
 #include "ploc.hpp"
 #include "presplit.hpp"
@@ -614,16 +615,15 @@ int presplit_stage(adypt_ctx *c, Builder *b, hipStream_t stream, const float4 *t
 }
 
 // radius 0: the linear tree; otherwise PLOC with that radius, and with triangles split where budget > 0
-int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, double budget, const char *who, adypt_rebuild_info *out)
+// Of the n_tris records at `tris`: the context's own (geometry null), or new ones that the context takes together with their tree
+int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, double budget, const char *who, adypt_rebuild_info *out, const float4 *tris, int64_t n_tris, NewGeometry *geometry = nullptr)
 {
 	const bool ploc = radius != 0;
-	const CtxScene sc = ctx_scene(c);
-	const int64_t n_tris = sc.n_tris;
+	const CtxScene sc = ctx_scene(c); // (of it: the layout of a record)
 	if(n_tris > ((int64_t)1 << 30)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": more than 2^30 triangles");
 	CTX_STEP(ctx_drain(c));
 	const hipStream_t stream = ctx_info(c).stream;
 	Builder *b = ctx_state<Builder>(c, kAttachBuild);
-	const float4 *tris = (const float4 *)sc.triangles;
 	int64_t n = n_tris; // the leaves of the binary tree: the references
 	int level = -1;
 	if(budget > 0.0)
@@ -752,7 +752,8 @@ int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, double budget
 	CTX_TRY(c, b->timer.mark(6, stream));
 	CTX_TRY(c, hipStreamSynchronize(stream));
 	// ---- the context takes the new tree
-	CTX_STEP(ctx_replace_bvh(c, &nodes, &tri_indices, &woop, n_nodes, n_refs));
+	if(geometry) CTX_STEP(ctx_replace_geometry(c, geometry, &nodes, &tri_indices, &woop, n_nodes, n_refs));
+	else CTX_STEP(ctx_replace_bvh(c, &nodes, &tri_indices, &woop, n_nodes, n_refs));
 	b->last = adypt_rebuild_info{n_nodes, n_refs, tree.levels(), __builtin_bit_cast(int32_t, root_hi.w)};
 	refit_adopt_tree(c, std::move(tree));
 	b->timer.complete();
@@ -765,6 +766,12 @@ int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, double budget
 
 }  // namespace
 
+int adypt::build_for_triangles(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, double split_budget, const char *who, const float4 *triangles, NewGeometry *geometry,
+                               adypt_rebuild_info *out)
+{
+	return rebuild(c, cfg, radius, split_budget, who, out, triangles, geometry->n_tris, geometry);
+}
+
 extern "C" {
 
 int adypt_rebuild_bvh(adypt_ctx *c, const adypt_bvh_params *params, adypt_rebuild_info *out)
@@ -775,7 +782,7 @@ int adypt_rebuild_bvh(adypt_ctx *c, const adypt_bvh_params *params, adypt_rebuil
 	if(!(cfg.triangle_sah > 0.0f && cfg.triangle_sah < kCutMax && cfg.node_sah > 0.0f && cfg.node_sah < kCutMax))
 		return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: the SAH costs must be positive finite numbers");
 	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
-	return rebuild(c, cfg, 0, 0.0, "adypt_rebuild_bvh", out);
+	return rebuild(c, cfg, 0, 0.0, "adypt_rebuild_bvh", out, (const float4 *)ctx_scene(c).triangles, ctx_scene(c).n_tris);
 }
 
 int adypt_rebuild_bvh_ploc(adypt_ctx *c, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out)
@@ -787,7 +794,7 @@ int adypt_rebuild_bvh_ploc(adypt_ctx *c, const adypt_bvh_params *params, int rad
 		return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc: the SAH costs must be positive finite numbers");
 	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc: the radius must be in [1, 32]");
 	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
-	return rebuild(c, cfg, radius, 0.0, "adypt_rebuild_bvh_ploc", out);
+	return rebuild(c, cfg, radius, 0.0, "adypt_rebuild_bvh_ploc", out, (const float4 *)ctx_scene(c).triangles, ctx_scene(c).n_tris);
 }
 
 int adypt_rebuild_bvh_ploc_split(adypt_ctx *c, const adypt_bvh_params *params, int radius, double split_budget, adypt_rebuild_info *out)
@@ -800,7 +807,7 @@ int adypt_rebuild_bvh_ploc_split(adypt_ctx *c, const adypt_bvh_params *params, i
 	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc_split: the radius must be in [1, 32]");
 	if(!(split_budget >= 0.0 && split_budget <= 1.0)) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc_split: the split budget must be in [0, 1]");
 	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
-	return rebuild(c, cfg, radius, split_budget, "adypt_rebuild_bvh_ploc_split", out);
+	return rebuild(c, cfg, radius, split_budget, "adypt_rebuild_bvh_ploc_split", out, (const float4 *)ctx_scene(c).triangles, ctx_scene(c).n_tris);
 }
 
 int adypt_get_rebuild_presplit(adypt_ctx *c, int32_t out[2])

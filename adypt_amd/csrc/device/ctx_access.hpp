@@ -36,7 +36,7 @@ struct Attachment {
 	~Attachment() { reset(); }
 	void reset(void *q = nullptr, void (*f)(void *) = nullptr) { if(p && free_fn) free_fn(p); p = q; free_fn = f; }
 };
-enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachBuild, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes, build.hip's scratch
+enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachBuild, kAttachGeometry, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes, build.hip's scratch, geometry.hip's staging
 Attachment &ctx_attachment(adypt_ctx *c, AttachKind kind);
 
 // ---- noise statistics and adaptive sampling, per context (adypt_trace_adaptive and adypt_multi_trace_adaptive are one loop over these) ----
@@ -85,8 +85,30 @@ int ctx_refresh_root_card(adypt_ctx *c);
 int ctx_drain(adypt_ctx *c);
 // ---- rebuilding the tree (build.hip), per context: see tracer.hip ----
 int ctx_replace_bvh(adypt_ctx *c, Buffer<uint4> *nodes, Buffer<int32_t> *tri_indices, Buffer<float4> *woop, int64_t n_nodes, int64_t n_refs);
+// ---- replacing the triangles (geometry.hip), per context: see tracer.hip ----
+// what k_pack_triangles reads of a context, and whether the context keeps a class byte per triangle (ADYPT_SHADE_BIN=1)
+struct CtxMaterials {
+	const float4 *materials;      // n_mats records of mat_float4 float4, each beginning with the reference's 64 bytes
+	int64_t n_mats;
+	int n_textures, mat_float4;
+	bool keeps_classes;
+};
+CtxMaterials ctx_materials(adypt_ctx *c);
+// new triangles, packed and complete on the context's stream: taken by the context together with the tree built of them
+struct NewGeometry {
+	Buffer<float4> *records;      // n_tris records
+	Buffer<uint8_t> *classes;     // n_tris bytes; read only where the context keeps them
+	int64_t n_tris;
+};
+// ctx_replace_bvh that takes the triangles the tree was built of as well: records, class bytes, tree, per-reference copy and the triangle count change
+// together or not at all
+int ctx_replace_geometry(adypt_ctx *c, NewGeometry *geometry, Buffer<uint4> *nodes, Buffer<int32_t> *tri_indices, Buffer<float4> *woop, int64_t n_nodes, int64_t n_refs);
+// the reason adypt_last_error(NULL) gives on this thread: of a create that returned no context
+void ctx_set_create_error(const std::string &msg);
 // multi.hip: the message adypt_multi_last_error answers
 void multi_set_error(adypt_multi *m, const std::string &msg);
+// multi.hip: the reason adypt_multi_last_error(NULL) gives on this thread: of a create that returned no handle
+void multi_set_create_error(const std::string &msg);
 // multi.hip: the same call on every context, in device order.  The first result that is not ADYPT_OK ends it and is returned, that context's error
 // becoming the handle's; ADYPT_E_INVALID for a null or empty handle.
 int multi_each(adypt_multi *m, const std::function<int(adypt_ctx *)> &f);

@@ -1,4 +1,4 @@
-// What a translation unit beside tracer.hip is written with (denoise.hip, refit.hip, build.hip, the next one): how it reports an error into the
+// What a translation unit beside tracer.hip is written with (denoise.hip, refit.hip, build.hip, geometry.hip, the next one): how it reports an error into the
 // context, how it keeps its state in the context, how it grows a buffer and sizes a grid, how it times its stages.  Everything goes through
 // ctx_access.hpp: nothing here sees the layout of adypt_ctx.  Not part of the C-ABI.
 #pragma once

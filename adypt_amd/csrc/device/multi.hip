@@ -350,7 +350,10 @@ struct adypt_multi {
 	Tunables tun;
 };
 
-namespace adypt { void multi_set_error(adypt_multi *m, const std::string &msg) { if(m) m->error = msg; } }
+namespace adypt {
+void multi_set_error(adypt_multi *m, const std::string &msg) { if(m) m->error = msg; }
+void multi_set_create_error(const std::string &msg) { g_multi_error = msg; }
+}
 
 namespace {
 

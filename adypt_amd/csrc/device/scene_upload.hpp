@@ -20,27 +20,10 @@ int upload_woop(adypt_ctx *c, const adypt_scene_desc *d)
 
 int upload_triangles(adypt_ctx *c, const adypt_scene_desc *d)
 {
-	// 100-byte Triangle -> 112-byte device record (shade.hpp): [p n matid pad] + [tc pad]
+	// 100-byte Triangle -> 128-byte device record: tri_record.hpp
 	std::vector<float> packed((size_t)d->n_tris * kTriFloat4 * 4, 0.0f);
-	const uint8_t *src = (const uint8_t *)d->triangles;
-	for(int64_t i = 0; i < d->n_tris; ++i)
-	{
-		float *o = packed.data() + (size_t)i * kTriFloat4 * 4;
-		memcpy(o, src + i * 100, 72);            // positions + normals
-		memcpy(o + 18, src + i * 100 + 96, 4);   // material id
-		// class word (shade.hpp): 1 = a hit here runs the glossy lobe or the dielectric branch of Render() — what k_path's shading rounds defer to a
-		// round of their own (path.hpp).  A grouping hint only: never an input of the arithmetic.
-		int32_t matid; memcpy(&matid, src + i * 100 + 96, 4);
-		if(matid >= 0 && matid < d->n_mats)
-		{
-			const uint8_t *mat = (const uint8_t *)d->materials + (size_t)matid * 64;
-			int32_t dtex, illum; float shininess;
-			memcpy(&dtex, mat, 4); memcpy(&illum, mat + 48, 4); memcpy(&shininess, mat + 52, 4);
-			const uint32_t cls = material_class(illum, shininess, false), word = (cls == 3u || cls == 6u) ? 1u : 0u;
-			memcpy(o + 19, &word, 4);
-		}
-		memcpy(o + 20, src + i * 100 + 72, 24);  // texture coordinates
-	}
+	TRY_CREATE(adypt_pack_triangles(d->triangles, d->n_tris, d->materials, d->n_mats, d->n_textures, packed.data(), nullptr) == ADYPT_OK ? ADYPT_OK
+	           : fail(c, ADYPT_E_INVALID, "adypt_create: the triangles could not be packed"));
 	return upload(c, &c->d_triangles, packed.data(), packed.size());
 }
 
@@ -50,15 +33,8 @@ int upload_shade_classes(adypt_ctx *c, const adypt_scene_desc *d)
 	// bench scenes (profiles/r3_ablations_k_trace.txt item 9) — the kernel waits on its gathers, not on divergent vector-ALU work
 	if(!c->tun.shade_bin) return ADYPT_OK;
 	std::vector<uint8_t> cls((size_t)std::max<int64_t>(d->n_tris, 1), (uint8_t)5);
-	const uint8_t *tri = (const uint8_t *)d->triangles, *mat = (const uint8_t *)d->materials;
-	for(int64_t i = 0; i < d->n_tris; ++i)
-	{
-		int32_t matid, dtex, illum; float shininess;
-		memcpy(&matid, tri + i * 100 + 96, 4);
-		if(matid < 0 || matid >= d->n_mats) continue;
-		memcpy(&dtex, mat + (size_t)matid * 64, 4); memcpy(&illum, mat + (size_t)matid * 64 + 48, 4); memcpy(&shininess, mat + (size_t)matid * 64 + 52, 4);
-		cls[(size_t)i] = (uint8_t)material_class(illum, shininess, d->n_textures != 0 && dtex >= 0 && dtex < d->n_textures);
-	}
+	if(adypt_pack_triangles(d->triangles, d->n_tris, d->materials, d->n_mats, d->n_textures, nullptr, cls.data()) != ADYPT_OK)
+		return fail(c, ADYPT_E_INVALID, "adypt_create: the triangles could not be classified");
 	return upload(c, &c->d_tri_class, cls.data(), cls.size());
 }
 

@@ -31,6 +31,7 @@
 #include "canon_math.hpp"
 #include "tile_layout.hpp"
 #include "noise.hpp"
+#include "tri_record.hpp"
 
 namespace adypt {
 
@@ -111,16 +112,9 @@ struct SceneArgs {
 	const uint8_t *tri_class;      // per triangle: shading class of its material, 1..6 (material_class); null = k_shade does not bin
 };
 
-// Shading class of a material = which code of Render() a path that hits it runs (pathtracer.glsl:144-201) — only a SORT KEY for
+// Shading class of a material (material_class, tri_record.hpp) = which code of Render() a path that hits it runs — only a SORT KEY for
 // k_shade's in-workgroup binning, never an input of the arithmetic.  0 is the key of a miss, 7 of a thread without a path.
 constexpr uint32_t kClassMiss = 0, kClassNone = 7;
-inline uint32_t material_class(int illum, float shininess, bool textured)
-{
-	if(illum == 2 && shininess * 0.01f > 0.3f) return textured ? 4u : 3u; // glossy lobe: two canon_pow + sincos
-	if(illum == 1 || illum == 2) return textured ? 2u : 1u;                // diffuse lobe
-	if(illum == 6 || illum == 7) return 6u;                                // dielectric
-	return 5u;                                                             // mirror (3..5) and pass-through (0, 8+)
-}
 
 struct QueueArgs {
 	float *ray_o; float4 *ray_d; float *col; // queue being read (shade) / written (gen): 3 floats, float4, 3 floats per slot

@@ -775,21 +775,39 @@ int ctx_drain(adypt_ctx *c)
 // comes first: after a failure the old tree is in place and usable.
 int ctx_replace_bvh(adypt_ctx *c, Buffer<uint4> *nodes, Buffer<int32_t> *tri_indices, Buffer<float4> *woop, int64_t n_nodes, int64_t n_refs)
 {
+	return ctx_replace_geometry(c, nullptr, nodes, tri_indices, woop, n_nodes, n_refs);
+}
+// ---- what replacing the triangles (geometry.hip) needs of a context ----
+CtxMaterials ctx_materials(adypt_ctx *c)
+{
+	return CtxMaterials{(const float4 *)c->d_materials, c->n_mats, c->n_tex, kMatFloat4, c->tun.shade_bin != 0};
+}
+void ctx_set_create_error(const std::string &msg) { g_create_error = msg; }
+// ctx_replace_bvh, and with `geometry` the triangles the tree was built of as well (packed by k_pack_triangles, complete on the context's stream): the
+// records, the class bytes where the context keeps them, and the count are taken in the same step as the tree, and go back with it when the new tree is refused.
+int ctx_replace_geometry(adypt_ctx *c, NewGeometry *geometry, Buffer<uint4> *nodes, Buffer<int32_t> *tri_indices, Buffer<float4> *woop, int64_t n_nodes, int64_t n_refs)
+{
 	HIP_TRY(c, hipSetDevice(c->device));
 	Buffer<float4> ref;
 	size_t ref_bytes;
 	if(wants_reference_triangles(c, n_refs, &ref_bytes) && ref.alloc(ref_bytes) != hipSuccess) (void)hipGetLastError(); // (left empty: k_path remaps, as after adypt_create)
 	HIP_TRY(c, hipStreamSynchronize(c->stream));
-	const int64_t old_nodes = c->n_nodes, old_refs = c->n_refs;
-	auto swap_all = [&] { std::swap(c->d_nodes, *nodes); std::swap(c->d_tri_indices, *tri_indices); std::swap(c->d_woop, *woop); std::swap(c->d_ref_triangles, ref); };
+	int64_t other_nodes = n_nodes, other_refs = n_refs, other_tris = geometry ? geometry->n_tris : c->n_tris;
+	auto swap_all = [&] {
+		std::swap(c->d_nodes, *nodes); std::swap(c->d_tri_indices, *tri_indices); std::swap(c->d_woop, *woop); std::swap(c->d_ref_triangles, ref);
+		if(geometry)
+		{
+			std::swap(c->d_triangles, *geometry->records);
+			if(c->tun.shade_bin) std::swap(c->d_tri_class, *geometry->classes);
+		}
+		std::swap(c->n_nodes, other_nodes); std::swap(c->n_refs, other_refs); std::swap(c->n_tris, other_tris);
+	};
 	swap_all();
-	c->n_nodes = n_nodes; c->n_refs = n_refs;
 	const int r = configure_trace(c, c->params.stack_size);
 	if(r != ADYPT_OK)
 	{
 		const std::string why = c->error;
 		swap_all();
-		c->n_nodes = old_nodes; c->n_refs = old_refs;
 		(void)configure_trace(c, c->params.stack_size);
 		c->error = why;
 		return r;

@@ -6,6 +6,7 @@
 #include "../device/ploc.hpp"
 #include "../device/presplit.hpp"
 #include "../device/root_card.hpp"
+#include "../device/tri_record.hpp"
 #include "../../../include/adypt_hip.h"
 
 #include <algorithm>
@@ -461,6 +462,31 @@ void adypt_woop_matrices(const void *tris_, const int32_t *tri_indices, int64_t 
 		woop_matrix(p, out + i * 12); // (../device/woop.hpp: the text the device refit compiles too)
 	}
 	});
+}
+
+int adypt_pack_triangles(const void *triangles, int64_t n_tris, const void *materials, int64_t n_mats, int32_t n_textures, void *records_out, uint8_t *classes_out)
+{
+	if(n_tris < 0 || n_mats < 0 || (n_tris > 0 && !triangles) || (n_mats > 0 && !materials)) return ADYPT_E_INVALID;
+	const uint8_t *tris = (const uint8_t *)triangles, *mats = (const uint8_t *)materials;
+	uint8_t *records = (uint8_t *)records_out;
+	parallel_ranges(n_tris, 1 << 16, [=](int64_t begin, int64_t end) {
+	for(int64_t i = begin; i < end; ++i)
+	{
+		// (../device/tri_record.hpp: the text k_pack_triangles compiles too)
+		uint32_t src[kTriSourceWords], mat[kMatSourceWords] = {0}, rec[kTriRecordWords];
+		memcpy(src, tris + i * kTriSourceBytes, sizeof(src));
+		const int32_t matid = (int32_t)src[24];
+		if(matid >= 0 && matid < n_mats) memcpy(mat, mats + (size_t)matid * kMatSourceBytes, sizeof(mat));
+		const TriMaterialWords w = tri_material_words(matid, n_mats, n_textures, mat);
+		if(records)
+		{
+			for(int k = 0; k < kTriRecordWords; ++k) rec[k] = tri_record_word(src, k, w.class_word);
+			memcpy(records + (size_t)i * sizeof(rec), rec, sizeof(rec));
+		}
+		if(classes_out) classes_out[i] = w.class_byte;
+	}
+	});
+	return ADYPT_OK;
 }
 
 void adypt_camera_matrices(float fov, float yaw, float pitch, int width, int height, float inv_proj[16], float inv_view[16])

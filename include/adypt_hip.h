@@ -374,6 +374,37 @@ int adypt_get_bvh_sizes(adypt_ctx *ctx, int64_t *n_nodes, int64_t *n_refs);
 /* the reference order (n_refs triangle indices) as it is on the device */
 int adypt_read_tri_indices(adypt_ctx *ctx, int32_t *out);
 
+/* ---- replacing the triangles: another set, of another length, and its tree, without a host build ----------------------------------------------
+ * adypt_set_triangles replaces ALL triangles of the context by n_tris new ones (100-byte Triangle each, 1 <= n_tris <= 2^30) and builds their tree as
+ * adypt_rebuild_bvh (method 0; radius is not looked at, split_budget must be 0), adypt_rebuild_bvh_ploc or adypt_rebuild_bvh_ploc_split (method 1) would:
+ * afterwards adypt_read_bvh and adypt_read_tri_indices equal the host's adypt_bvh_build_linear / _ploc / _ploc_split of those triangles and
+ * adypt_woop_matrices of them byte for byte, and adypt_read_triangle_records equals adypt_pack_triangles (adypt_host.h; the definition is
+ * csrc/device/tri_record.hpp, compiled by both).  Materials, textures, image, camera, parameters and every switch of the context stay; material ids are
+ * not checked, as adypt_create does not check them (a bad id renders as a bad material and is counted).
+ * In this order: the arguments are checked; the context is drained; the caller's array is copied to a staging buffer on the device; k_pack_triangles
+ * writes the records (and the class bytes of ADYPT_SHADE_BIN=1) into new arrays; the tree is built from those; only then does the context take records,
+ * class bytes, tree, per-reference copy and count, in one step.  ADYPT_E_INVALID (a null array, a count outside [1, 2^30], what the rebuilds refuse, a
+ * vertex with a NaN coordinate — k_pack_triangles looks, since the builders' min and max would drop it silently —, a scene whose SAH costs are not
+ * finite), ADYPT_E_OOM and a tree the traversal cannot be configured for leave the old
+ * triangles and the old tree in place and traceable, with the error set.  After success the context is as adypt_reset leaves it, later
+ * adypt_update_triangles / adypt_rebuild_bvh* / adypt_get_tree_cost calls work on the new count, and the reference cost of
+ * adypt_update_triangles_auto is stale as after a rebuild.
+ * Memory: at the peak the old and the new records and trees exist side by side, next to the rebuild's scratch; the staging buffer (100 B per triangle)
+ * is kept at its largest. */
+int adypt_set_triangles(adypt_ctx *ctx, const void *triangles /* n_tris x 100 bytes */, int64_t n_tris, const adypt_bvh_params *params /* NULL: 0.3 / 1 */,
+                        int method /* 0 linear, 1 ploc */, int radius, double split_budget, adypt_rebuild_info *out /* may be NULL */);
+/* adypt_create without a tree: desc->nodes, tri_indices and woop must be NULL and n_nodes, n_refs 0.  Gives the context adypt_create gives for the
+ * host's adypt_bvh_build_linear / _ploc / _ploc_split tree of desc's triangles, built as adypt_set_triangles builds it; no host build and no host
+ * packing loop run.  A failure returns no context, and adypt_last_error(NULL) gives the reason. */
+int adypt_create_from_triangles(adypt_ctx **out, const adypt_scene_desc *desc, const adypt_bvh_params *params, int method, int radius, double split_budget,
+                                adypt_rebuild_info *info /* may be NULL */);
+int64_t adypt_get_triangle_count(adypt_ctx *ctx); /* negative: an ADYPT_E_* code */
+/* the device's triangle records as they are now: n_tris x 128 bytes (adypt_pack_triangles of adypt_host.h describes them) */
+int adypt_read_triangle_records(adypt_ctx *ctx, void *out);
+/* HIP-event times of the last adypt_set_triangles in ms, in front of what adypt_get_rebuild_timing gives for its build: [0] the staging copy, [1]
+ * k_pack_triangles, [2] both.  Returns the number of entries and writes them only when capacity holds them all; ADYPT_E_STATE before the first call. */
+int adypt_get_set_triangles_timing(adypt_ctx *ctx, float *ms, int capacity);
+
 /* ---- refit or rebuild: the SAH cost of the tree as it is now decides ------------------------------------------------------------------------
  * adypt_get_tree_cost measures the tree the context holds: adypt_bvh_cost (adypt_host.h; the definition is csrc/device/tree_cost.hpp, compiled by
  * both) of adypt_read_bvh's nodes, to the same two integers, by one pass over the node array (k_tree_cost) on the context's stream after the context
@@ -530,7 +561,14 @@ int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, c
 int adypt_multi_rebuild_bvh(adypt_multi *m, const adypt_bvh_params *params, adypt_rebuild_info *out);
 int adypt_multi_rebuild_bvh_ploc(adypt_multi *m, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out); /* likewise */
 int adypt_multi_rebuild_bvh_ploc_split(adypt_multi *m, const adypt_bvh_params *params, int radius, double split_budget, adypt_rebuild_info *out); /* likewise */
-/* adypt_get_tree_cost / adypt_update_triangles_auto on every device.  The scene is replicated and the cost is two integer sums, so every device
+/* adypt_set_triangles on every device, in device order: every device packs and builds its own copy, and all get the same bytes; no collective.  Bad
+ * arguments and a scene that cannot be built are refused by the first device, so no device has changed.  *out: the last device's. */
+int adypt_multi_set_triangles(adypt_multi *m, const void *triangles, int64_t n_tris, const adypt_bvh_params *params, int method, int radius, double split_budget,
+                              adypt_rebuild_info *out);
+/* adypt_create_multi without a tree (see adypt_create_from_triangles): adypt_multi_last_error(NULL) gives the reason of a failure */
+int adypt_create_multi_from_triangles(adypt_multi **out, const adypt_scene_desc *desc /* device, tile_rank, tile_nranks ignored */, const int *device_ids, int n_dev,
+                                      const adypt_bvh_params *params, int method, int radius, double split_budget, adypt_rebuild_info *info);
+/* adypt_get_tree_cost / adypt_update_triangles_auto on every device. The scene is replicated and the cost is two integer sums, so every device
  * measures the same and decides alike; *out / *outcome are the first device's (cost_ms too).  A device whose integers or decision differ from the
  * first one's ends the call with ADYPT_E_HIP and a text rather than letting the trees diverge.  No collective. */
 int adypt_multi_get_tree_cost(adypt_multi *m, const adypt_bvh_params *params, adypt_tree_cost *out);

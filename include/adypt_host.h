@@ -152,6 +152,12 @@ int adypt_bvh_cost(const void *nodes, int64_t n_nodes, const adypt_bvh_params *p
 void adypt_decode_root_card(const void *node, int allow, void *card_out);
 /* OglScene::init_triangles (src/Tracer/OglScene.cpp:93-116): out = 12 floats per reference */
 void adypt_woop_matrices(const void *tris, const int32_t *tri_indices, int64_t n_refs, float *out);
+/* The device triangle records of `n_tris` 100-byte Triangles (src/Util/Shape.hpp:70-74): records_out = n_tris x 128 bytes — floats 0..17 positions and
+ * normals, word 18 the material id, word 19 the class word (1 where the material runs the glossy lobe or the dielectric branch, 0 otherwise and for an
+ * id outside [0, n_mats)), floats 20..25 the texture coordinates, the rest zero; classes_out = one shading-class byte per triangle (1..6; 5 for an id
+ * outside [0, n_mats)).  Either may be NULL.  materials: n_mats 64-byte GPUMaterial.  The definition is csrc/device/tri_record.hpp, which the device
+ * (adypt_set_triangles of adypt_hip.h) compiles too: both give the same bytes.  ADYPT_E_INVALID for a null array that is needed or a negative count. */
+int adypt_pack_triangles(const void *triangles, int64_t n_tris, const void *materials, int64_t n_mats, int32_t n_textures, void *records_out, uint8_t *classes_out);
 /* Camera::GetView/GetProjection + the inverses of SetCamera (src/Tracer/Camera.cpp:13-23, OglPathTracer.cpp:27-32) */
 void adypt_camera_matrices(float fov, float yaw, float pitch, int width, int height, float inv_proj[16], float inv_view[16]);
 /* Sobol::Next (src/Util/Sobol.cpp:16-21): points of frames [first, first+n), dim <= 64; out = n*dim floats */

@@ -121,24 +121,39 @@ public:
 	bool Initialize(const InstanceConfig::PT *config, const Scene &scene, const WideBVH &bvh, int width, int height,
 	                const std::vector<int> &devices = std::vector<int>(1, 0), int lookahead_frames = 0)
 	{
+		return create(config, scene, &bvh, width, height, devices, lookahead_frames, nullptr, 1, 8, 0.0, nullptr);
+	}
+
+private:
+	// bvh null: no tree is uploaded; every device builds its first one from the triangles (adypt_create_multi_from_triangles)
+	bool create(const InstanceConfig::PT *config, const Scene &scene, const WideBVH *bvh, int width, int height, const std::vector<int> &devices, int lookahead_frames,
+	            const adypt_bvh_params *params, int method, int radius, double split_budget, adypt_rebuild_info *info)
+	{
 		m_config = config; m_width = width; m_height = height;
 		init_materials(scene);
 		adypt_scene_desc d;
 		memset(&d, 0, sizeof(d));
-		d.nodes = bvh.GetNodes().data();            d.n_nodes = (int64_t)bvh.GetNodes().size();
-		d.tri_indices = bvh.GetTriIndices().data(); d.n_refs = (int64_t)bvh.GetTriIndices().size();
+		if(bvh)
+		{
+			d.nodes = bvh->GetNodes().data();            d.n_nodes = (int64_t)bvh->GetNodes().size();
+			d.tri_indices = bvh->GetTriIndices().data(); d.n_refs = (int64_t)bvh->GetTriIndices().size();
+		}
 		d.woop = nullptr;                           // computed like OglScene::init_triangles
 		d.triangles = scene.GetTriangles().data();  d.n_tris = (int64_t)scene.GetTriangles().size();
 		d.materials = m_materials.data();           d.n_mats = (int64_t)m_materials.size();
 		d.textures = m_textures.data();             d.n_textures = (int32_t)m_textures.size();
 		d.width = width; d.height = height;
-		if(adypt_create_multi(&m_gpus, &d, devices.data(), (int)devices.size()) != ADYPT_OK) { printf("[PT]ERR: %s\n", adypt_multi_last_error(nullptr)); return false; }
+		const int made = bvh ? adypt_create_multi(&m_gpus, &d, devices.data(), (int)devices.size())
+		                     : adypt_create_multi_from_triangles(&m_gpus, &d, devices.data(), (int)devices.size(), params, method, radius, split_budget, info);
+		if(made != ADYPT_OK) { printf("[PT]ERR: %s\n", adypt_multi_last_error(nullptr)); return false; }
 		const int fif = lookahead_frames > 0 ? (lookahead_frames < 128 ? lookahead_frames : 128) : 1;
 		for(int i = 0; i < adypt_multi_device_count(m_gpus); ++i)
 			if(adypt_set_frames_in_flight(adypt_multi_context(m_gpus, i), fif) != ADYPT_OK) { printf("[PT]ERR: %s\n", adypt_last_error(adypt_multi_context(m_gpus, i))); return false; }
 		adypt_multi_set_lookahead(m_gpus, lookahead_frames > 0 ? 1 : 0);
 		return update_config_args();
 	}
+
+public:
 
 	void SetCamera(const glm::mat4 &projection, const glm::mat4 &view, const glm::vec3 &position)
 	{
@@ -215,6 +230,28 @@ public:
 		                 : split_budget != 0.0         ? adypt_multi_rebuild_bvh_ploc_split(m_gpus, params, radius, split_budget, info)
 		                                               : adypt_multi_rebuild_bvh_ploc(m_gpus, params, radius, info);
 		if(code == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
+	// Initialize without a WideBVH: no tree is built on the host and none is uploaded; every device builds its first tree from the triangles, as
+	// RebuildBVH(params, info, method, radius, split_budget) would (adypt_hip.h, adypt_create_from_triangles) — milliseconds instead of the SBVH builder's
+	// seconds, for a tree that traverses somewhat slower (Rebuilding on the GPU).
+	bool Initialize(const InstanceConfig::PT *config, const Scene &scene, int width, int height, const std::vector<int> &devices = std::vector<int>(1, 0),
+	                int lookahead_frames = 0, const adypt_bvh_params *params = nullptr, RebuildMethod method = RebuildMethod::PLOC, int radius = 8, double split_budget = 0.0,
+	                adypt_rebuild_info *info = nullptr)
+	{
+		return create(config, scene, nullptr, width, height, devices, lookahead_frames, params, method == RebuildMethod::PLOC ? 1 : 0, radius, split_budget, info);
+	}
+
+	// Other triangles, any number of them (adypt_hip.h, adypt_set_triangles): every device packs them and builds their tree on the GPU as
+	// RebuildBVH(params, info, method, radius, split_budget) would; materials, textures, camera and config stay, no new context.  Nothing changes when it
+	// fails.  The sample counter restarts as after a Trace(false).
+	bool SetTriangles(const std::vector<Triangle> &triangles, const adypt_bvh_params *params = nullptr, adypt_rebuild_info *info = nullptr,
+	                  RebuildMethod method = RebuildMethod::PLOC, int radius = 8, double split_budget = 0.0)
+	{
+		static_assert(sizeof(Triangle) == 100, "Triangle is the 100-byte record adypt_set_triangles takes");
+		if(adypt_multi_set_triangles(m_gpus, triangles.data(), (int64_t)triangles.size(), params, method == RebuildMethod::PLOC ? 1 : 0, radius, split_budget, info) == ADYPT_OK) return true;
 		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
 		return false;
 	}
