@@ -80,6 +80,11 @@ class DenoiseParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("sigma_l", C.c_float), ("sigma_z", C.c_float)]
 
 
+class TemporalParams(C.Structure):
+    """adypt_temporal_params."""
+    _fields_ = [("history_cap", C.c_float), ("commit", C.c_int32)]
+
+
 class BvhParams(C.Structure):
     _fields_ = [("max_spatial_depth", C.c_int32), ("triangle_sah", C.c_float), ("node_sah", C.c_float)]
 
@@ -186,6 +191,14 @@ _SIGS = {
     "adypt_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_read_denoise_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adypt_get_denoise_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
+    "adypt_denoise_temporal": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams)]),
+    "adypt_denoise_history_reset": (C.c_int, [C.c_void_p]),
+    "adypt_read_denoise_history": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_get_denoise_merge_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "adypt_multi_denoise_temporal": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams)]),
+    "adypt_multi_denoise_history_reset": (C.c_int, [C.c_void_p]),
+    "adypt_multi_read_denoise_history": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_multi_get_denoise_merge_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "adypt_multi_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams)]),
     "adypt_multi_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_read_denoise_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

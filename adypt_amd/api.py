@@ -601,14 +601,39 @@ class _Tracer:
         return out
 
     # ---- denoising (adypt_denoise, include/adypt_hip.h; the definition: csrc/device/denoise.hpp); several devices: of the whole image ----
-    def Denoise(self, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 0.1) -> np.ndarray:
+    def Denoise(self, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 0.1, temporal: bool = False, history_cap: float = 64.0,
+                commit: bool = True) -> np.ndarray:
         """H x W x 3 float32: the accumulated image through the variance- and primary-hit-guided a-trous filter.  Needs the noise statistics on and
-        >= 2 spp in every block; the image, the statistics and the tracing state are left as they are."""
+        >= 2 spp in every block; the image, the statistics and the tracing state are left as they are.
+        temporal (adypt_denoise_temporal; the definition: csrc/device/temporal.hpp): before the filter, what the last committing call left is
+        reprojected through the primary hit and counted as up to history_cap further samples where the surface is still the same; commit: this
+        call's state replaces that history (once per pose: after tracing, before the camera or the scene changes).  Give every pose a shift_seed of
+        its own (SetConfig): after a reset an unchanged camera with an unchanged seed repeats the same samples."""
         prm = N.DenoiseParams(levels, sigma_l, sigma_z)
-        self._call("denoise", C.byref(prm))
+        if temporal:
+            tp = N.TemporalParams(history_cap, 1 if commit else 0)
+            self._call("denoise_temporal", C.byref(prm), C.byref(tp))
+        else:
+            self._call("denoise", C.byref(prm))
         rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
         self._call("read_denoised", rgb.ctypes.data)
         return rgb
+
+    def ResetDenoiseHistory(self) -> None:
+        """Drops the history of Denoise(temporal=True): the next such call is the plain filter."""
+        self._call("denoise_history_reset")
+
+    def ReadDenoiseHistory(self) -> np.ndarray:
+        """H x W float32: the effective sample count of every pixel after the last Denoise(temporal=True) (the block's own where it took no history)."""
+        n = np.zeros((self.height, self.width), dtype=np.float32)
+        self._call("read_denoise_history", n.ctypes.data)
+        return n
+
+    def GetDenoiseMergeMs(self) -> float:
+        """HIP-event milliseconds of the merge kernel of the last Denoise(temporal=True)."""
+        ms = C.c_float(0.0)
+        self._call("get_denoise_merge_ms", C.byref(ms))
+        return float(ms.value)
 
     def ReadDenoiseGuides(self) -> dict:
         """The feature images of the pixel-centre camera ray under the current camera: albedo, normal, position (H x W x 3 float32) and hit (H x W bool)."""
@@ -618,7 +643,8 @@ class _Tracer:
         return {"albedo": a, "normal": n, "position": p, "hit": hit.astype(bool)}
 
     def GetDenoiseTiming(self) -> dict:
-        """HIP-event milliseconds of the last Denoise() on the (first) device: guides (0 with several devices: the upload instead), prepare, levels."""
+        """HIP-event milliseconds of the last Denoise() on the (first) device: guides (0 with several devices: the upload instead), prepare, levels.
+        After Denoise(temporal=True) the merge kernel's time is in none of the entries, so `total` leaves it out: add GetDenoiseMergeMs()."""
         ms = (C.c_float * 16)()
         c = self._contexts()[0]
         n = N.lib.adypt_get_denoise_timing(c, ms, 16)

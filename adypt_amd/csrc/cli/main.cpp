@@ -4,8 +4,8 @@
 //
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
-//             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild]
-//             [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
+//             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C]
+//             [--history-out len.exr]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
 //   --build gpu: no .bvh cache is read or written and no tree is built on the host: the context is created from the triangles alone
 //              (adypt_create_multi_from_triangles) and its first tree built on the GPU by --rebuild-method (ploc unless given), --ploc-radius and
 //              --split-budget, which then name that build (and, with --rebuild-above, the policy's rebuild) instead of asking for a rebuild; one
@@ -34,6 +34,13 @@
 //              the render ends when every block has stopped, or at --spp.  --spp-out: the per-pixel sample count as a grey EXR
 //   --denoise file.exr: the image through the variance- and primary-hit-guided a-trous filter (adypt_multi_denoise) next to --out; switches the noise
 //              statistics on before the first sample, as --noise does; needs --spp >= 2 and no --primary.  --denoise-levels L: 1 .. 6 levels (default 5)
+//   --history-from other.config: with --denoise only; repeatable, run in order before the render.  The other config names the same OBJ, width and
+//              height (else exit 1); for each one: that config's camera, --spp samples with shift_seed = --seed + 1 + its index, and a committing temporal
+//              call (adypt_multi_denoise_temporal).  Then the main config's camera and --seed, a reset of the accumulation, the render as without it, and a
+//              temporal call into the --denoise file.  --history-cap C: the most samples the history counts as (a positive finite number, default 64).
+//              --history-out len.exr: the effective sample count of every pixel after that call as a grey EXR.  One [PT]TEMPORAL: line reports how many
+//              hit pixels found history.  --history-cap or --history-out without --history-from make the --denoise call a temporal one too: it finds no
+//              history, so the file holds the plain filter's bits, every length is the block's own sample count and the line reports 0 pixels
 //   --guides-out PREFIX: the feature images of the primary hit as PREFIX.albedo.exr, PREFIX.normal.exr and PREFIX.position.exr
 #include "adypt_hip.h"
 #include "adypt_host.h"
@@ -54,7 +61,7 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C] [--history-out len.exr]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
 	std::string noise_out, spp_out, denoise_out, guides_out, pose;
@@ -65,6 +72,10 @@ int main(int argc, char **argv)
 	bool have_split_budget = false, have_rebuild_method = false, build_on_gpu = false;
 	int ploc_radius = 8;
 	int denoise_levels = 5;
+	std::vector<std::string> history_from;
+	std::string history_out;
+	double history_cap = 64.0;
+	bool have_history_cap = false;
 	int adaptive = 0;
 	int spp = 64, fp16 = 0, primary = -1, sun_visibility = 0, save_every = 0;
 	std::vector<int> devices(1, 0);
@@ -105,6 +116,15 @@ int main(int argc, char **argv)
 		else if(a == "--spp-out" && i + 1 < argc) spp_out = argv[++i];
 		else if(a == "--denoise" && i + 1 < argc) denoise_out = argv[++i];
 		else if(a == "--denoise-levels" && i + 1 < argc) denoise_levels = atoi(argv[++i]);
+		else if(a == "--history-from" && i + 1 < argc) history_from.push_back(argv[++i]);
+		else if(a == "--history-out" && i + 1 < argc) history_out = argv[++i];
+		else if(a == "--history-cap" && i + 1 < argc)
+		{
+			char *end = nullptr;
+			history_cap = strtod(argv[++i], &end);
+			if(end == argv[i] || *end || !(history_cap > 0.0 && history_cap <= 3.0e38)) { fprintf(stderr, "--history-cap takes a positive finite number, not %s\n", argv[i]); return 2; }
+			have_history_cap = true;
+		}
 		else if(a == "--guides-out" && i + 1 < argc) guides_out = argv[++i];
 		else if(a == "--pose" && i + 1 < argc) pose = argv[++i];
 		else if(a == "--rebuild") rebuild = bare_rebuild = true;
@@ -141,11 +161,24 @@ int main(int argc, char **argv)
 	const bool denoise = !denoise_out.empty();
 	if(denoise && (primary >= 0 || spp < 2)) { fprintf(stderr, "--denoise needs --spp >= 2 and no --primary\n"); return 2; }
 	if(denoise && (denoise_levels < 1 || denoise_levels > 6)) { fprintf(stderr, "--denoise-levels must be in 1 .. 6\n"); return 2; }
+	const bool temporal = !history_from.empty() || have_history_cap || !history_out.empty();
+	if(temporal && !denoise) { fprintf(stderr, "--history-from, --history-cap and --history-out need --denoise file.exr\n"); return 2; }
 	if(until) min_spp = std::max(2, std::min(min_spp, spp));
 	adypt_config cfg;
 	adypt_config_default(&cfg);
 	if(adypt_config_load(argv[1], &cfg) != ADYPT_OK) { fprintf(stderr, "[INSTANCE]Err: Invalid instance %s: %s\n", argv[1], adypt_host_last_error()); return 1; }
 	printf("[INSTANCE]Info: Instance loaded from %s\n", argv[1]);
+	std::vector<adypt_config> history_cfg(history_from.size()); // --history-from: the earlier poses, of which only the cameras are used
+	for(size_t k = 0; k < history_from.size(); ++k)
+	{
+		adypt_config_default(&history_cfg[k]);
+		if(adypt_config_load(history_from[k].c_str(), &history_cfg[k]) != ADYPT_OK) { fprintf(stderr, "[INSTANCE]Err: Invalid instance %s: %s\n", history_from[k].c_str(), adypt_host_last_error()); return 1; }
+		if(strcmp(history_cfg[k].obj_filename, cfg.obj_filename) != 0 || history_cfg[k].width != cfg.width || history_cfg[k].height != cfg.height)
+		{
+			fprintf(stderr, "[INSTANCE]Err: --history-from %s names another scene or another size than %s (%s, %d x %d)\n", history_from[k].c_str(), argv[1], cfg.obj_filename, cfg.width, cfg.height);
+			return 1;
+		}
+	}
 
 	adypt_scene *scene = nullptr;
 	if(adypt_scene_load(cfg.obj_filename, &scene) != ADYPT_OK) { fprintf(stderr, "[INSTANCE]Err: Unable to load scene %s: %s\n", cfg.obj_filename, adypt_host_last_error()); return 1; }
@@ -275,6 +308,48 @@ int main(int argc, char **argv)
 		return true;
 	};
 
+	const adypt_denoise_params dp{denoise_levels, 4.0f, 0.1f};
+	const adypt_temporal_params tp{(float)history_cap, 1};
+	// --history-from: every earlier pose is rendered and committed to the denoiser's history, each with a shift_seed of its own (an unchanged seed would
+	// repeat the very same samples, which the history would count twice); then the main config's camera and seed, from 0 spp
+	for(size_t k = 0; k < history_cfg.size() && r == ADYPT_OK; ++k)
+	{
+		const adypt_config &h = history_cfg[k];
+		float hp[16], hv[16];
+		adypt_camera_matrices(h.fov, h.yaw, h.pitch, cfg.width, cfg.height, hp, hv);
+		p.shift_seed = seed + 1u + (unsigned)k;
+		r = adypt_multi_reset(multi);
+		if(r == ADYPT_OK) r = adypt_multi_set_params(multi, &p);
+		if(r == ADYPT_OK) r = adypt_multi_set_camera(multi, h.position, hp, hv);
+		if(r == ADYPT_OK) r = adypt_multi_trace_spp(multi, spp);
+		if(r == ADYPT_OK) r = adypt_multi_denoise_temporal(multi, &dp, &tp);
+		if(r == ADYPT_OK) printf("[PT]INFO: history pose %s: %d spp committed\n", history_from[k].c_str(), spp);
+	}
+	if(!history_cfg.empty() && r == ADYPT_OK)
+	{
+		p.shift_seed = seed;
+		r = adypt_multi_reset(multi);
+		if(r == ADYPT_OK) r = adypt_multi_set_params(multi, &p);
+		if(r == ADYPT_OK) r = adypt_multi_set_camera(multi, cfg.position, ip, iv);
+	}
+	if(r != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+	// the sample count of every pixel from the devices' blocks (every block has one owner)
+	auto pixel_spp = [&](std::vector<float> *count_of) -> bool {
+		count_of->assign((size_t)cfg.width * cfg.height, 0.0f);
+		const int blocks_x = (cfg.width + 31) / 32;
+		for(size_t k = 0; k < devices.size(); ++k)
+		{
+			adypt_ctx *c = adypt_multi_context(multi, (int)k);
+			const int64_t n = adypt_read_block_spp(c, nullptr, nullptr, 0);
+			std::vector<int32_t> index((size_t)std::max<int64_t>(n, 0)), count(index.size());
+			if(n < 0 || (n > 0 && adypt_read_block_spp(c, index.data(), count.data(), n) != n)) { fprintf(stderr, "[TRACER]Err: %s\n", adypt_last_error(c)); return false; }
+			for(size_t b = 0; b < index.size(); ++b)
+				for(int y = (index[b] / blocks_x) * 32; y < std::min(cfg.height, (index[b] / blocks_x + 1) * 32); ++y)
+					for(int x = (index[b] % blocks_x) * 32; x < std::min(cfg.width, (index[b] % blocks_x + 1) * 32); ++x) (*count_of)[(size_t)y * cfg.width + x] = (float)count[b];
+		}
+		return true;
+	};
+
 	double t0 = now_ms(), t_save = 0.0;
 	adypt_noise noise;
 	memset(&noise, 0, sizeof(noise));
@@ -346,20 +421,9 @@ int main(int argc, char **argv)
 		}
 		if(!spp_out.empty())
 		{
-			// the sample count of every pixel from the devices' blocks (every block has one owner)
-			std::vector<float> grey((size_t)cfg.width * cfg.height * 3, 0.0f);
-			const int blocks_x = (cfg.width + 31) / 32;
-			for(size_t k = 0; k < devices.size(); ++k)
-			{
-				adypt_ctx *c = adypt_multi_context(multi, (int)k);
-				const int64_t n = adypt_read_block_spp(c, nullptr, nullptr, 0);
-				std::vector<int32_t> index((size_t)std::max<int64_t>(n, 0)), count(index.size());
-				if(n < 0 || (n > 0 && adypt_read_block_spp(c, index.data(), count.data(), n) != n)) { fprintf(stderr, "[TRACER]Err: %s\n", adypt_last_error(c)); return 1; }
-				for(size_t b = 0; b < index.size(); ++b)
-					for(int y = (index[b] / blocks_x) * 32; y < std::min(cfg.height, (index[b] / blocks_x + 1) * 32); ++y)
-						for(int x = (index[b] % blocks_x) * 32; x < std::min(cfg.width, (index[b] % blocks_x + 1) * 32); ++x)
-							for(int ch = 0; ch < 3; ++ch) grey[((size_t)y * cfg.width + x) * 3 + ch] = (float)count[b];
-			}
+			std::vector<float> count_of, grey((size_t)cfg.width * cfg.height * 3, 0.0f);
+			if(!pixel_spp(&count_of)) return 1;
+			for(size_t i = 0; i < count_of.size(); ++i) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = count_of[i];
 			if(adypt_save_exr(spp_out.c_str(), grey.data(), cfg.width, cfg.height, 0) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
 			printf("[PT]INFO: Saved sample counts to %s\n", spp_out.c_str());
 		}
@@ -370,11 +434,30 @@ int main(int argc, char **argv)
 	}
 	if(denoise)
 	{
-		const adypt_denoise_params dp{denoise_levels, 4.0f, 0.1f};
 		std::vector<float> den((size_t)cfg.width * cfg.height * 3, 0.0f);
-		if(adypt_multi_denoise(multi, &dp) != ADYPT_OK || adypt_multi_read_denoised(multi, den.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		if((temporal ? adypt_multi_denoise_temporal(multi, &dp, &tp) : adypt_multi_denoise(multi, &dp)) != ADYPT_OK || adypt_multi_read_denoised(multi, den.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
 		if(adypt_save_exr(denoise_out.c_str(), den.data(), cfg.width, cfg.height, fp16) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
 		printf("[PT]INFO: Saved denoised image (%d levels) to %s\n", denoise_levels, denoise_out.c_str());
+		if(temporal)
+		{
+			// on the host from the read-backs: a hit pixel found history when its effective sample count is above its block's own
+			std::vector<float> length((size_t)cfg.width * cfg.height, 0.0f), count_of;
+			std::vector<uint8_t> hit(length.size(), 0);
+			if(adypt_multi_read_denoise_history(multi, length.data()) != ADYPT_OK || adypt_multi_read_denoise_guides(multi, nullptr, nullptr, nullptr, hit.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+			if(!pixel_spp(&count_of)) return 1;
+			long long hits = 0, with_history = 0;
+			double sum = 0.0;
+			for(size_t i = 0; i < length.size(); ++i)
+				if(hit[i]) { ++hits; sum += length[i]; if(length[i] > count_of[i]) ++with_history; }
+			printf("[PT]TEMPORAL: history on %lld of %lld hit pixels, mean length %.3f\n", with_history, hits, hits ? sum / (double)hits : 0.0);
+			if(!history_out.empty())
+			{
+				std::vector<float> grey(length.size() * 3);
+				for(size_t i = 0; i < length.size(); ++i) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = length[i];
+				if(adypt_save_exr(history_out.c_str(), grey.data(), cfg.width, cfg.height, 0) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
+				printf("[PT]INFO: Saved history lengths to %s\n", history_out.c_str());
+			}
+		}
 	}
 	if(!guides_out.empty())
 	{

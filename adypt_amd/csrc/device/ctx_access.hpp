@@ -65,6 +65,9 @@ int ctx_denoise_ready(adypt_ctx *c, const char *fn);
 DenoiseInputs ctx_denoise_inputs(adypt_ctx *c);
 // see tracer.hip
 int ctx_capture_guides(adypt_ctx *c, const char *fn, float4 *albedo, float4 *normal, float4 *position, float4 *hits);
+// what adypt_set_camera was last given (the guides above are captured under it): the temporal merge keeps it beside the history it commits
+struct CtxCamera { float origin[3], inv_proj[16], inv_view[16]; };
+CtxCamera ctx_camera(adypt_ctx *c);
 
 // ---- moving geometry (refit.hip), per context ----
 // the scene arrays on the device, which refit.hip rewrites in place between frames

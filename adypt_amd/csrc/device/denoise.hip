@@ -3,14 +3,19 @@
 //     guide capture  three launches of the viewer instance of k_trace_camera over the owned blocks (tracer.hip ctx_capture_guides), into scratch
 //                    owned here: albedo, normal, position, primary hit — block-major like every local image
 //     k_denoise_prepare  block-major accum / moments / block sample counts / guides  ->  row-major float4 images X0 = (D0.rgb, V0), X1 = (N.xyz, hit),
-//                    X2 = (P.xyz, .), XA = (A.rgb, .)
+//                    X2 = (P.xyz, n), XA = (A.rgb, .)
+//     k_temporal_merge  adypt_denoise_temporal only (the definition: temporal.hpp): the history the last committing call left — its merged pre-filter
+//                    (D, V), its guides, its effective sample counts, its camera — reprojected through P and merged into (D0, V0); the levels then
+//                    read the merged image.  A commit swaps the call's images with the history's: nothing is copied
 //     k_atrous<LAST>  one level per launch, X0 ping-pongs; the last level multiplies the albedo back and writes the W x H x 3 result
 // Several devices: every context captures the guides of its own blocks, the host puts the devices' local images back to back in rank order, their
 // block lists likewise (every block has one owner, and k_denoise_prepare takes any block list and writes at the picture's coordinates), uploads them
-// to the first device and runs the same two kernels there — no collective; the result is the one-device result bit for bit because the inputs are.
+// to the first device and runs the same kernels there (the merge too: the history lives on the first device) — no collective; the result is the
+// one-device result bit for bit because the inputs are.
 #include "ctx_unit.hpp"
 #include "tile_layout.hpp"
 #include "denoise.hpp"
+#include "temporal.hpp"
 #include "../../../include/adypt_hip.h"
 
 #include <algorithm>
@@ -36,7 +41,7 @@ __global__ __launch_bounds__(256) void k_denoise_prepare(const float4 *accum, co
 	const Dn4 d = denoise_prepare(c.x, c.y, c.z, moments[L].y, (float)block_spp[L >> 10], a.x, a.y, a.z);
 	x0[p] = make_float4(d.x, d.y, d.z, d.w);
 	x1[p] = make_float4(n.x, n.y, n.z, __float_as_int(g_hits[L].x) != -1 ? 1.0f : 0.0f);
-	x2[p] = make_float4(q.x, q.y, q.z, 0.0f);
+	x2[p] = make_float4(q.x, q.y, q.z, (float)block_spp[L >> 10]); // (.w: the sample count, which only the temporal merge reads)
 	xa[p] = make_float4(a.x, a.y, a.z, 0.0f);
 }
 
@@ -69,6 +74,32 @@ __global__ __launch_bounds__(kAtrousX * kAtrousY) void k_atrous(const float4 *x0
 	else x0_out[p] = make_float4(r.x, r.y, r.z, r.w);
 }
 
+struct DeviceHistory {
+	const float4 *a, *b, *c, *d;
+	__device__ __forceinline__ Dn4 h0(int i) const { return DeviceImages::load(a, i); }
+	__device__ __forceinline__ Dn4 h1(int i) const { return DeviceImages::load(b, i); }
+	__device__ __forceinline__ Dn4 h2(int i) const { return DeviceImages::load(c, i); }
+	__device__ __forceinline__ Dn4 ha(int i) const { return DeviceImages::load(d, i); }
+};
+
+// One pixel per thread, the workgroup of k_atrous.  Reads 64 B of the call's images and up to four taps x 64 B of the history (neighbouring pixels share
+// them: 64 B per pixel reach the memory where the motion is smooth), writes the merged X0 (16 B), X2 with n_out in .w (16 B) and the history length
+// (4 B): 164 B per pixel.  The history's camera comes by value.
+__global__ __launch_bounds__(kAtrousX * kAtrousY) void k_temporal_merge(const float4 *x0, const float4 *x1, float4 *x2, const float4 *xa, const float4 *h0, const float4 *h1,
+                                                                         const float4 *h2, const float4 *ha, float4 *merged, float *length, int width, int height, int have,
+                                                                         TemporalCamera cam, float history_cap)
+{
+	const int x = blockIdx.x * kAtrousX + threadIdx.x, y = blockIdx.y * kAtrousY + threadIdx.y;
+	if(x >= width || y >= height) return;
+	const int p = y * width + x;
+	const Dn4 c2 = DeviceImages::load(x2, p);
+	const DeviceHistory hist{h0, h1, h2, ha};
+	const TemporalOut r = temporal_merge(hist, have != 0, cam, width, height, DeviceImages::load(x0, p), DeviceImages::load(x1, p), c2, DeviceImages::load(xa, p), c2.w, history_cap);
+	merged[p] = make_float4(r.x0.x, r.x0.y, r.x0.z, r.x0.w);
+	x2[p] = make_float4(c2.x, c2.y, c2.z, r.n);
+	length[p] = r.n;
+}
+
 // the block-major images of a set of blocks on one device: a context's own (accum and moments are then the context's) or the merged ones of all devices
 struct LocalImages {
 	const float4 *accum; const float2 *moments; const int32_t *blocks, *block_spp;
@@ -76,7 +107,10 @@ struct LocalImages {
 	int n_blocks;
 };
 
-constexpr int kTimingEvents = 3 + kDenoiseMaxLevels; // start, guides, prepare, every level
+constexpr int kTimingEvents = 4 + kDenoiseMaxLevels; // start, guides, prepare, (the temporal merge,) every level
+
+// what adypt_denoise_temporal adds to a call
+struct TemporalCall { float history_cap; bool commit; };
 
 // Everything the denoiser keeps per context; parked in the context (ctx_attachment), freed by adypt_destroy (the context's device is current then).
 struct Denoiser {
@@ -92,8 +126,15 @@ struct Denoiser {
 	Buffer<float4> m_accum, m_albedo, m_normal, m_position, m_hits;
 	Buffer<float2> m_moments;
 	Buffer<int32_t> m_blocks, m_block_spp;
+	// the temporal merge, allocated at the first temporal call only: the merged image of the call, the history (what the last committing call left:
+	// its merged image, its X1, X2 with n_out in .w, XA — swapped in, never copied — and its camera) and the length read-out: 84 B per image pixel
+	Buffer<float4> xm, h0, h1, h2, ha;
+	Buffer<float> length;
+	TemporalCamera h_camera;
+	bool have_history = false, have_length = false;
 	StageTimer<kTimingEvents> timer; // completed: the last filter ran to its end, rgb is its result
 	int levels_timed = 0;
+	bool merge_timed = false; // the last filter was a temporal call: the merge's stage stands between prepare's and the first level's
 };
 
 Denoiser *denoiser_of(adypt_ctx *c) { return ctx_state<Denoiser>(c, kAttachDenoise); }
@@ -117,9 +158,19 @@ int ensure_filter_images(adypt_ctx *c, Denoiser *d, const CtxInfo &i)
 	return ADYPT_OK;
 }
 
-// prepare + the levels, on `stream`; d's images are the whole picture's (ensure_filter_images)
-int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages &in, const DenoiseParams &prm)
+int ensure_history_images(adypt_ctx *c, Denoiser *d)
 {
+	const size_t n = (size_t)d->width * (size_t)d->height;
+	CTX_TRY(c, at_least(d->xm, n)); CTX_TRY(c, at_least(d->h0, n)); CTX_TRY(c, at_least(d->h1, n)); CTX_TRY(c, at_least(d->h2, n)); CTX_TRY(c, at_least(d->ha, n));
+	CTX_TRY(c, at_least(d->length, n));
+	return ADYPT_OK;
+}
+
+// prepare (+ the temporal merge) + the levels, on `stream`; d's images are the whole picture's (ensure_filter_images).  t: a temporal call, under the
+// camera `cam` of the context the guides were captured by.
+int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages &in, const DenoiseParams &prm, const TemporalCall *t = nullptr, const CtxCamera *cam = nullptr)
+{
+	if(t) CTX_STEP(ensure_history_images(c, d));
 	const int width = d->width, height = d->height, n_px = in.n_blocks * kBlockPixels;
 	const int blocks_x = (width + kBlockDim - 1) / kBlockDim;
 	hipLaunchKernelGGL(k_denoise_prepare, dim3(grid_of(n_px, 256)), dim3(256), 0, stream, in.accum, in.moments, in.blocks, in.block_spp, n_px, blocks_x, width, height, in.albedo,
@@ -127,20 +178,42 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 	CTX_TRY(c, hipGetLastError());
 	CTX_TRY(c, d->timer.mark(2, stream));
 	const dim3 grid(grid_of(width, kAtrousX), grid_of(height, kAtrousY)), block(kAtrousX, kAtrousY);
+	const int first = t ? 4 : 3; // the mark behind level 0
+	if(t)
+	{
+		d->have_length = false;
+		hipLaunchKernelGGL(k_temporal_merge, grid, block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, d->x2.get(), (const float4 *)d->xa, (const float4 *)d->h0,
+		                   (const float4 *)d->h1, (const float4 *)d->h2, (const float4 *)d->ha, d->xm.get(), d->length.get(), width, height, d->have_history ? 1 : 0, d->h_camera,
+		                   t->history_cap);
+		CTX_TRY(c, hipGetLastError());
+		CTX_TRY(c, d->timer.mark(3, stream));
+	}
 	for(int l = 0; l < prm.levels; ++l)
 	{
-		const float4 *src = d->x0[l & 1];
+		const float4 *src = (l == 0 && t) ? d->xm : d->x0[l & 1];
 		float4 *dst = d->x0[(l & 1) ^ 1];
 		if(l == prm.levels - 1)
 			hipLaunchKernelGGL(k_atrous<true>, grid, block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
 		else
 			hipLaunchKernelGGL(k_atrous<false>, grid, block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
 		CTX_TRY(c, hipGetLastError());
-		CTX_TRY(c, d->timer.mark(3 + l, stream));
+		CTX_TRY(c, d->timer.mark(first + l, stream));
 	}
 	d->levels_timed = prm.levels;
+	d->merge_timed = t != nullptr;
 	CTX_TRY(c, hipStreamSynchronize(stream));
 	d->timer.complete();
+	if(t)
+	{
+		d->have_length = true;
+		if(t->commit)
+		{
+			// this call's merged image, guides (X2.w = n_out) and camera become the history; what the history held is overwritten by the next prepare
+			std::swap(d->xm, d->h0); std::swap(d->x1, d->h1); std::swap(d->x2, d->h2); std::swap(d->xa, d->ha);
+			d->h_camera = temporal_camera(cam->origin, cam->inv_proj, cam->inv_view);
+			d->have_history = true;
+		}
+	}
 	return ADYPT_OK;
 }
 
@@ -178,30 +251,87 @@ template <class T> int fetch(adypt_ctx *c, const CtxInfo &i, const T *device, T 
 	return ADYPT_OK;
 }
 
-}  // namespace
+// the temporal half of a call's parameters (tp NULL = the defaults: cap 64, committing)
+int temporal_of(const adypt_temporal_params *tp, TemporalCall *out, std::string *why, const char *fn)
+{
+	*out = tp ? TemporalCall{tp->history_cap, tp->commit != 0} : TemporalCall{kTemporalDefaultCap, true};
+	if(temporal_cap_valid(out->history_cap)) return ADYPT_OK;
+	*why = std::string(fn) + ": history_cap must be a positive finite number";
+	return ADYPT_E_INVALID;
+}
 
-extern "C" {
-
-int adypt_denoise(adypt_ctx *c, const adypt_denoise_params *p)
+// adypt_denoise (temporal false: tp is not looked at) and adypt_denoise_temporal of one context
+int denoise_context(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp, bool temporal, const char *fn)
 {
 	if(!c) return ADYPT_E_INVALID;
 	DenoiseParams prm;
+	TemporalCall t;
 	std::string why;
-	if(params_of(p, &prm, &why, "adypt_denoise") != ADYPT_OK) return ctx_fail(c, ADYPT_E_INVALID, why);
+	if(params_of(p, &prm, &why, fn) != ADYPT_OK) return ctx_fail(c, ADYPT_E_INVALID, why);
+	if(temporal && temporal_of(tp, &t, &why, fn) != ADYPT_OK) return ctx_fail(c, ADYPT_E_INVALID, why);
 	const CtxInfo i = ctx_info(c);
-	if(i.nranks != 1) return ctx_fail(c, ADYPT_E_STATE, "adypt_denoise: the context is a tile shard (tile_nranks > 1): the filter needs the whole image (adypt_multi_denoise)");
-	CTX_STEP(ctx_denoise_ready(c, "adypt_denoise"));
+	if(i.nranks != 1) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the context is a tile shard (tile_nranks > 1): the filter needs the whole image (adypt_multi_denoise)");
+	CTX_STEP(ctx_denoise_ready(c, fn));
 	CTX_TRY(c, hipSetDevice(i.device));
 	Denoiser *d = denoiser_of(c);
 	CTX_STEP(ensure_filter_images(c, d, i));
 	d->timer.invalidate();
 	CTX_TRY(c, d->timer.mark(0, i.stream));
-	CTX_STEP(capture_guides(c, d, i, "adypt_denoise"));
+	CTX_STEP(capture_guides(c, d, i, fn));
 	CTX_TRY(c, d->timer.mark(1, i.stream));
 	const DenoiseInputs in = ctx_denoise_inputs(c);
 	CTX_TRY(c, hipMemcpyAsync(d->d_block_spp, in.block_spp.data(), in.block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
 	const LocalImages local{in.accum, in.moments, in.blocks, d->d_block_spp, d->g_albedo, d->g_normal, d->g_position, d->g_hits, in.n_blocks};
-	return run_filter(c, d, i.stream, local, prm);
+	const CtxCamera cam = ctx_camera(c);
+	return run_filter(c, d, i.stream, local, prm, temporal ? &t : nullptr, &cam);
+}
+
+int read_history_length(adypt_ctx *c, const char *fn, float *length)
+{
+	Denoiser *d = finished_denoiser(c);
+	if(!d || !d->have_length) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": no temporal call has run yet (adypt_denoise_temporal)");
+	const CtxInfo i = ctx_info(c);
+	CTX_TRY(c, hipSetDevice(i.device));
+	CTX_TRY(c, hipMemcpyAsync(length, d->length, (size_t)d->width * d->height * sizeof(float), hipMemcpyDeviceToHost, i.stream));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
+	return ADYPT_OK;
+}
+
+int read_merge_ms(adypt_ctx *c, const char *fn, float *ms)
+{
+	Denoiser *d = finished_denoiser(c);
+	if(!d || !d->merge_timed) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the last filter was not a temporal call (adypt_denoise_temporal)");
+	float all[kTimingEvents];
+	d->timer.read(all, kTimingEvents, 3 + d->levels_timed, false);
+	*ms = all[2];
+	return ADYPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int adypt_denoise(adypt_ctx *c, const adypt_denoise_params *p) { return denoise_context(c, p, nullptr, false, "adypt_denoise"); }
+
+int adypt_denoise_temporal(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return denoise_context(c, p, tp, true, "adypt_denoise_temporal"); }
+
+int adypt_denoise_history_reset(adypt_ctx *c)
+{
+	if(!c) return ADYPT_E_INVALID;
+	if(Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise)) d->have_history = false;
+	return ADYPT_OK;
+}
+
+int adypt_read_denoise_history(adypt_ctx *c, float *length)
+{
+	if(!c || !length) return ADYPT_E_INVALID;
+	return read_history_length(c, "adypt_read_denoise_history", length);
+}
+
+int adypt_get_denoise_merge_ms(adypt_ctx *c, float *ms)
+{
+	if(!c || !ms) return ADYPT_E_INVALID;
+	return read_merge_ms(c, "adypt_get_denoise_merge_ms", ms);
 }
 
 int adypt_read_denoised(adypt_ctx *c, float *rgb)
@@ -249,30 +379,43 @@ int adypt_get_denoise_timing(adypt_ctx *c, float *ms, int capacity)
 	if(!c || !ms || capacity < 0) return ADYPT_E_INVALID;
 	Denoiser *d = finished_denoiser(c);
 	if(!d) return ctx_fail(c, ADYPT_E_STATE, "adypt_get_denoise_timing: nothing has been denoised yet (adypt_denoise)");
-	return d->timer.read(ms, capacity, 2 + d->levels_timed, false);
+	const int n = 2 + d->levels_timed;
+	if(!d->merge_timed) return d->timer.read(ms, capacity, n, false);
+	// a temporal call: the merge's stage (adypt_get_denoise_merge_ms) is left out, the layout is adypt_denoise's
+	if(capacity < n) return n;
+	float all[kTimingEvents];
+	d->timer.read(all, kTimingEvents, n + 1, false);
+	for(int k = 0; k < n; ++k) ms[k] = all[k < 2 ? k : k + 1];
+	return n;
 }
 
 // ---- one process, N devices ----
+}  // extern "C"
 
-int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p)
+namespace {
+
+// adypt_multi_denoise and adypt_multi_denoise_temporal: the merge runs on the first device, where the filter runs, and the history lives there
+int multi_denoise(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp, bool temporal, const char *fn)
 {
 	const int n_dev = adypt_multi_device_count(m);
 	if(n_dev < 1) return ADYPT_E_INVALID;
 	adypt_ctx *root = adypt_multi_context(m, 0);
-	if(n_dev == 1) return multi_each(m, [p](adypt_ctx *c) { return adypt_denoise(c, p); });
+	if(n_dev == 1) return multi_each(m, [=](adypt_ctx *c) { return denoise_context(c, p, tp, temporal, fn); });
 	auto fail_ctx = [m](adypt_ctx *c, int r) { multi_set_error(m, adypt_last_error(c)); return r; };
 	DenoiseParams prm;
+	TemporalCall t;
 	std::string why;
-	if(params_of(p, &prm, &why, "adypt_multi_denoise") != ADYPT_OK) { multi_set_error(m, why); return ADYPT_E_INVALID; }
+	if(params_of(p, &prm, &why, fn) != ADYPT_OK) { multi_set_error(m, why); return ADYPT_E_INVALID; }
+	if(temporal && temporal_of(tp, &t, &why, fn) != ADYPT_OK) { multi_set_error(m, why); return ADYPT_E_INVALID; }
 	std::vector<adypt_ctx *> ctx;
 	for(int k = 0; k < n_dev; ++k) ctx.push_back(adypt_multi_context(m, k));
-	CTX_STEP(multi_each(m, [](adypt_ctx *c) { return ctx_denoise_ready(c, "adypt_multi_denoise"); }));
+	CTX_STEP(multi_each(m, [fn](adypt_ctx *c) { return ctx_denoise_ready(c, fn); }));
 	// every device captures the guides of its own blocks: all enqueued before the first is waited for
-	CTX_STEP(multi_each(m, [](adypt_ctx *c) {
+	CTX_STEP(multi_each(m, [fn](adypt_ctx *c) {
 		const CtxInfo i = ctx_info(c);
 		if(i.n_local_px == 0) return (int)ADYPT_OK;
-		if(hipSetDevice(i.device) != hipSuccess) return ctx_fail(c, ADYPT_E_HIP, "adypt_multi_denoise: hipSetDevice failed");
-		return capture_guides(c, denoiser_of(c), i, "adypt_multi_denoise");
+		if(hipSetDevice(i.device) != hipSuccess) return ctx_fail(c, ADYPT_E_HIP, std::string(fn) + ": hipSetDevice failed");
+		return capture_guides(c, denoiser_of(c), i, fn);
 	}));
 	// the local images of every device back to back in rank order, and their block lists and sample counts likewise (the counts from each context's
 	// own state in that order: multi.hip's merge is sorted by block index, which is not this order, and would launch k_noise_blocks for nothing)
@@ -288,7 +431,7 @@ int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p)
 	{
 		const CtxInfo i = ctx_info(c);
 		if(i.n_local_px == 0) continue;
-		if(hipSetDevice(i.device) != hipSuccess) return fail_ctx(c, ctx_fail(c, ADYPT_E_HIP, "adypt_multi_denoise: hipSetDevice failed"));
+		if(hipSetDevice(i.device) != hipSuccess) return fail_ctx(c, ctx_fail(c, ADYPT_E_HIP, std::string(fn) + ": hipSetDevice failed"));
 		Denoiser *d = denoiser_of(c);
 		const DenoiseInputs in = ctx_denoise_inputs(c);
 		const float4 *const device[5] = {in.accum, d->g_albedo, d->g_normal, d->g_position, d->g_hits};
@@ -320,10 +463,43 @@ int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p)
 		CTX_TRY(c, hipMemcpyAsync(d->m_block_spp, block_spp.data(), block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, ri.stream));
 		CTX_TRY(c, d->timer.mark(1, ri.stream));
 		const LocalImages all{d->m_accum, d->m_moments, d->m_blocks, d->m_block_spp, d->m_albedo, d->m_normal, d->m_position, d->m_hits, n_blocks};
-		return run_filter(c, d, ri.stream, all, prm);
+		const CtxCamera cam = ctx_camera(c); // (adypt_multi_set_camera gives every context the same)
+		return run_filter(c, d, ri.stream, all, prm, temporal ? &t : nullptr, &cam);
 	};
 	const int r = steps();
 	return r == ADYPT_OK ? r : fail_ctx(root, r);
+}
+
+// a per-context call on the first device's context, its error becoming the handle's
+template <class F> int on_root(adypt_multi *m, F f)
+{
+	if(adypt_multi_device_count(m) < 1) return ADYPT_E_INVALID;
+	adypt_ctx *root = adypt_multi_context(m, 0);
+	const int r = f(root);
+	if(r != ADYPT_OK) multi_set_error(m, adypt_last_error(root));
+	return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p) { return multi_denoise(m, p, nullptr, false, "adypt_multi_denoise"); }
+
+int adypt_multi_denoise_temporal(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return multi_denoise(m, p, tp, true, "adypt_multi_denoise_temporal"); }
+
+int adypt_multi_denoise_history_reset(adypt_multi *m) { return on_root(m, [](adypt_ctx *c) { return adypt_denoise_history_reset(c); }); }
+
+int adypt_multi_read_denoise_history(adypt_multi *m, float *length)
+{
+	if(!length) return ADYPT_E_INVALID;
+	return on_root(m, [=](adypt_ctx *c) { return read_history_length(c, "adypt_multi_read_denoise_history", length); });
+}
+
+int adypt_multi_get_denoise_merge_ms(adypt_multi *m, float *ms)
+{
+	if(!ms) return ADYPT_E_INVALID;
+	return on_root(m, [=](adypt_ctx *c) { return read_merge_ms(c, "adypt_multi_get_denoise_merge_ms", ms); });
 }
 
 int adypt_multi_read_denoised(adypt_multi *m, float *rgb)

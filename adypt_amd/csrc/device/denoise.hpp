@@ -5,7 +5,7 @@
 // only + - * / sqrtf, comparisons and selects — so that a numpy float32 restatement (tests/denoise_truth.py) is bit-exact.
 //
 // Per pixel p of the W x H image, row-major, four float4 images:  X0 = (D.rgb, V)  the demodulated radiance and the variance of its luminance
-//                                                                 X1 = (N.xyz, hit) X2 = (P.xyz, .)  XA = (A.rgb, .)
+//                                                                 X1 = (N.xyz, hit) X2 = (P.xyz, n: read by temporal.hpp only)  XA = (A.rgb, .)
 // denoise_prepare makes X0 of level 0, denoise_level makes level i + 1 from level i, denoise_remodulate the result from the last.
 #pragma once
 #include "noise.hpp"

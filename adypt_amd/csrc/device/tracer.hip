@@ -740,6 +740,12 @@ int ctx_capture_guides(adypt_ctx *c, const char *fn, float4 *albedo, float4 *nor
 	}
 	return ADYPT_OK;
 }
+CtxCamera ctx_camera(adypt_ctx *c)
+{
+	CtxCamera cam;
+	memcpy(cam.origin, c->origin, 12); memcpy(cam.inv_proj, c->inv_proj, 64); memcpy(cam.inv_view, c->inv_view, 64);
+	return cam;
+}
 
 // ---- what the refit (refit.hip) needs of a context ----
 CtxScene ctx_scene(adypt_ctx *c)

@@ -294,6 +294,35 @@ int adypt_read_denoise_guides(adypt_ctx *ctx, float *albedo, float *normal, floa
  * them only when capacity holds them all. */
 int adypt_get_denoise_timing(adypt_ctx *ctx, float *ms, int capacity);
 
+/* ---- temporal merge: the denoiser keeps its history across camera moves and poses ------------------------------------------------------------
+ * The temporal half of SVGF.  Between prepare and the first level, what the last committing call left (the history: its merged PRE-filter radiance
+ * and variance, its effective sample count per pixel, its guides and its camera) is reprojected through the current primary hit and counted as
+ * further samples where the surface is still the same: a history tap counts when it lies inside the image, was a hit, its normal, its plane and its
+ * albedo agree with the pixel's (0.9, 0.02 of the distance, 0.1), and what it holds is finite and its sample count positive.  The definition is pinned bit for bit in
+ * csrc/device/temporal.hpp; tests/temporal_truth.py restates it in numpy.  A surface that moved fails the plane test and starts again from its own
+ * samples, so adypt_update_triangles, adypt_rebuild_bvh and adypt_set_triangles leave the history alone.  Sky pixels take no history.
+ * Poses should differ in shift_seed (adypt_set_params): a reset restarts the sample sequence, so an unchanged camera with an unchanged seed
+ * repeats the very same samples, and the history would count them twice.
+ * Memory, allocated at the first temporal call and given back by adypt_destroy: 84 B per image pixel on top of the denoiser's (four float4 history
+ * images, the merged image, the length read-out).  Several devices: the merge runs on the first, where the filter runs; the history lives there. */
+typedef struct adypt_temporal_params {
+	float history_cap;           /* the most samples the history may count as; a positive finite number, default 64 */
+	int32_t commit;              /* 1 (default): this call's merged state, guides and camera replace the history.  0: the history is only read */
+} adypt_temporal_params;
+/* adypt_denoise with the merge; both pointers may be NULL (the defaults); the result is read through adypt_read_denoised.  The first call (and the
+ * first after adypt_denoise_history_reset) finds no history and is adypt_denoise to the bit.  With commit = 0 two calls in a row leave the same bits.
+ * Commit once per pose: after tracing, before the camera or the scene changes.  Refusals: adypt_denoise's, and ADYPT_E_INVALID for a history_cap
+ * that is not a positive finite number.  Nothing of the context changes, as for adypt_denoise; adypt_denoise neither reads nor writes the history. */
+int adypt_denoise_temporal(adypt_ctx *ctx, const adypt_denoise_params *params, const adypt_temporal_params *temporal);
+/* drops the history (the images stay allocated); no error when there is none */
+int adypt_denoise_history_reset(adypt_ctx *ctx);
+/* W*H floats: the effective sample count n_out of every pixel after the last adypt_denoise_temporal (the block's own count where the pixel took no
+ * history).  ADYPT_E_STATE before the first */
+int adypt_read_denoise_history(adypt_ctx *ctx, float *length);
+/* HIP-event time of the merge kernel of the last filter in ms; ADYPT_E_STATE when that was not a temporal call.  adypt_get_denoise_timing keeps its
+ * layout: the merge's time is in none of its entries */
+int adypt_get_denoise_merge_ms(adypt_ctx *ctx, float *ms);
+
 /* ---- moving geometry: new vertex positions without a new BVH and a new context ----------------------------------------------------------------
  * The tree's topology stays valid when vertices move; what goes stale are the boxes, the Woop data and the triangle records.  adypt_update_triangles
  * replaces the positions (count x 9 floats: p0 p1 p2 of every triangle) and, unless normals is NULL, the normals (count x 9 floats) of triangles
@@ -554,6 +583,12 @@ int adypt_multi_trace_adaptive(adypt_multi *m, double target, int min_spp, int m
 int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *params);
 int adypt_multi_read_denoised(adypt_multi *m, float *rgb);
 int adypt_multi_read_denoise_guides(adypt_multi *m, float *albedo, float *normal, float *position, uint8_t *hit); /* every device writes its own tiles */
+/* adypt_denoise_temporal ... for the whole image: the merge runs on the first device behind the same upload, the history lives there; the result is
+ * the one-device result bit for bit */
+int adypt_multi_denoise_temporal(adypt_multi *m, const adypt_denoise_params *params, const adypt_temporal_params *temporal);
+int adypt_multi_denoise_history_reset(adypt_multi *m);
+int adypt_multi_read_denoise_history(adypt_multi *m, float *length);
+int adypt_multi_get_denoise_merge_ms(adypt_multi *m, float *ms);
 /* adypt_update_triangles on every device: the scene is replicated and every device refits its own copy; no collective.  (One process per GPU: every
  * rank calls adypt_update_triangles on its own context.) */
 int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals);
