@@ -130,6 +130,14 @@ class PoseOutcome(C.Structure):
                 "rebuild": {k: getattr(self.rebuild, k) for k, _ in self.rebuild._fields_}, "cost_ms": float(self.cost_ms)}
 
 
+class PoseBinding(C.Structure):
+    """adypt_pose_binding."""
+    _fields_ = [("kind", C.c_int32), ("n_matrices", C.c_int32), ("n_tris", C.c_int64), ("device_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/*.h declares, with its signature (tests/test_abi.py checks the export list against the headers)
 _SIGS = {
     # adypt_hip.h
@@ -233,6 +241,17 @@ _SIGS = {
     "adypt_update_triangles_auto": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
     "adypt_multi_get_tree_cost": (C.c_int, [C.c_void_p, C.POINTER(BvhParams), C.POINTER(TreeCost)]),
     "adypt_multi_update_triangles_auto": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
+    # posing on the GPU
+    "adypt_bind_parts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "adypt_bind_skin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "adypt_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
+    "adypt_unbind_pose": (C.c_int, [C.c_void_p]),
+    "adypt_get_pose_binding": (C.c_int, [C.c_void_p, C.POINTER(PoseBinding)]),
+    "adypt_multi_bind_parts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "adypt_multi_bind_skin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "adypt_multi_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
+    "adypt_multi_unbind_pose": (C.c_int, [C.c_void_p]),
+    "adypt_multi_get_pose_binding": (C.c_int, [C.c_void_p, C.POINTER(PoseBinding)]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),
@@ -301,6 +320,7 @@ _SIGS = {
     "adypt_bvh_cost": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(BvhParams), C.POINTER(TreeCost)]),
     "adypt_woop_matrices": (None, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "adypt_pack_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "adypt_pose_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "adypt_decode_root_card": (None, [C.c_void_p, C.c_int, C.c_void_p]),
     "adypt_camera_matrices": (None, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "adypt_sobol_points": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -266,6 +266,44 @@ def woop_matrices(triangles: np.ndarray, tri_indices: np.ndarray) -> np.ndarray:
     return out
 
 
+def _pose_matrices(who: str, matrices) -> np.ndarray:
+    """n x 12 float32 of matrices given as [n, 3, 4], [n, 12] or flat"""
+    m = np.ascontiguousarray(matrices, dtype=np.float32)
+    if m.size == 0 or m.size % 12:
+        raise ValueError("%s: matrices are row-major 3x4, 12 floats each" % who)
+    return m.reshape(-1, 12)
+
+
+def _skin_arrays(who: str, joints, weights) -> Tuple[np.ndarray, np.ndarray]:
+    """(uint16 [n, 12], float32 [n, 12]) of joints and weights given per triangle as [n, 3, 4], [n, 12] or flat"""
+    j = np.asarray(joints)
+    if j.size and (j.min() < 0 or j.max() > 65535):
+        raise ValueError("%s: a joint index does not fit 16 bits" % who)
+    j = np.ascontiguousarray(j, dtype=np.uint16).reshape(-1, 12)
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1, 12)
+    if len(j) != len(w):
+        raise ValueError("%s: joints and weights differ in length" % who)
+    return j, w
+
+
+def pose_triangles(triangles: np.ndarray, matrices, parts=None, joints=None, weights=None) -> np.ndarray:
+    """adypt_pose_triangles, the host's side of Pose() (csrc/device/pose.hpp): the 100-byte triangles (uint8 [n * 100], or TRI_DT records) posed by
+    row-major 3x4 matrices — by `parts` (one index per triangle) or by `joints` and `weights` (four per vertex: [n, 3, 4]).  Returns uint8 [n * 100];
+    texture coordinates and material ids stay.  What BindParts / BindSkin / Pose refuse raises AdyptError here."""
+    t = np.ascontiguousarray(triangles).view(np.uint8).reshape(-1)
+    m = _pose_matrices("pose_triangles", matrices)
+    p = None if parts is None else np.ascontiguousarray(parts, dtype=np.int32).reshape(-1)
+    j, w = (None, None) if joints is None or weights is None else _skin_arrays("pose_triangles", joints, weights)
+    n = len(t) // 100
+    for a in (p, j):
+        if a is not None and len(a) != n:
+            raise ValueError("pose_triangles: the binding is not of %d triangles" % n)
+    out = np.empty_like(t)
+    N.check_host(N.lib.adypt_pose_triangles(t.ctypes.data, n, None if p is None else p.ctypes.data, None if j is None else j.ctypes.data,
+                                            None if w is None else w.ctypes.data, m.ctypes.data, len(m), out.ctypes.data))
+    return out
+
+
 # struct RootCard (csrc/device/root_card.hpp), 264 bytes; q[child] = float(qlo x, qhi x, qlo y, qhi y, qlo z, qhi z)
 ROOT_CARD_DT = np.dtype([("q", "<f4", (8, 6)), ("scale", "<f4", 3), ("origin", "<f4", 3), ("child_base", "<u4"), ("tri_base", "<u4"), ("imask", "<u4"),
                          ("inner_only", "<u4"), ("enabled", "<u4"), ("pad", "<u4"), ("is_inner", "u1", 8), ("bit_index", "u1", 8), ("child_bits", "u1", 8)])
@@ -676,6 +714,51 @@ class _Tracer:
         out = N.PoseOutcome()
         self._call("update_triangles_auto", first, len(pos), pos.ctypes.data, None if nrm is None else nrm.ctypes.data,
                    None if cfg is None else C.byref(cfg), C.byref(policy), C.byref(out))
+        return out.as_dict()
+
+    # ---- posing on the GPU (adypt_bind_parts, adypt_bind_skin, adypt_pose, include/adypt_hip.h; the definition: csrc/device/pose.hpp) ----
+    def BindParts(self, parts: np.ndarray, n_parts: Optional[int] = None) -> None:
+        """Every triangle belongs to one part (int32 [n], 0 <= part < n_parts; n_parts None: the largest index + 1).  The device keeps the triangles
+        as they are NOW as the rest pose; Pose() then moves them by one 3x4 matrix per part.  Replaces an earlier binding; nothing changes when
+        the call is refused.  Several devices: on every device."""
+        p = np.ascontiguousarray(parts, dtype=np.int32).reshape(-1)
+        if n_parts is None:
+            n_parts = int(p.max()) + 1 if len(p) else 0
+        self._call("bind_parts", p.ctypes.data, len(p), int(n_parts))
+
+    def BindSkin(self, joints: np.ndarray, weights: np.ndarray, n_joints: int) -> None:
+        """Every vertex follows up to four weighted joints: joints (integers below 65536) and weights (float32, finite, >= 0, used as given), each
+        [n, 3, 4] — triangle, vertex, slot.  A slot of weight 0 is skipped, its joint may be anything.  Otherwise as BindParts()."""
+        j, w = _skin_arrays("BindSkin", joints, weights)
+        self._call("bind_skin", j.ctypes.data, w.ctypes.data, len(j), int(n_joints))
+
+    def Pose(self, matrices: np.ndarray, rebuild_above: Optional[float] = None, method: str = "ploc", radius: int = 8, split_budget: float = 0.0,
+             cfg: Optional[N.BvhParams] = None) -> Optional[dict]:
+        """The bound triangles under row-major 3x4 matrices (float32 [n_parts or n_joints, 3, 4]: [r][0..2] linear, [r][3] translation), always from
+        the rest pose: positions, and normals through the cofactor matrix, are written into the device's records by one kernel, then the tree is
+        refitted as UpdateTriangles() refits it — only the matrices cross the bus.  pose_triangles() is the same arithmetic on the host, bit for
+        bit.  rebuild_above and the arguments after it, and what is returned: as for UpdateTriangles()."""
+        m = _pose_matrices("Pose", matrices)
+        if rebuild_above is None:
+            self._call("pose", m.ctypes.data, len(m), None, None, None)
+            return None
+        if method not in ("linear", "ploc"):
+            raise ValueError("Pose: method must be 'linear' or 'ploc', not %r" % (method,))
+        if split_budget != 0.0 and method != "ploc":
+            raise ValueError("Pose: split_budget needs method 'ploc'")
+        policy = N.PosePolicy(float(rebuild_above), 1 if method == "ploc" else 0, int(radius), float(split_budget))
+        out = N.PoseOutcome()
+        self._call("pose", m.ctypes.data, len(m), None if cfg is None else C.byref(cfg), C.byref(policy), C.byref(out))
+        return out.as_dict()
+
+    def UnbindPose(self) -> None:
+        """Gives the rest pose and the binding back; the triangles stay as the last Pose() left them."""
+        self._call("unbind_pose")
+
+    def GetPoseBinding(self) -> dict:
+        """kind (0 none, 1 parts, 2 skin), n_matrices, n_tris and device_bytes of the binding of the (first) device."""
+        out = N.PoseBinding()
+        self._call("get_pose_binding", C.byref(out))
         return out.as_dict()
 
     def GetTreeCost(self, cfg: Optional[N.BvhParams] = None) -> dict:

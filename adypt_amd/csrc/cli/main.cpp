@@ -5,20 +5,24 @@
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
 //             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C]
-//             [--history-out len.exr]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
+//             [--history-out len.exr]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
 //   --build gpu: no .bvh cache is read or written and no tree is built on the host: the context is created from the triangles alone
 //              (adypt_create_multi_from_triangles) and its first tree built on the GPU by --rebuild-method (ploc unless given), --ploc-radius and
 //              --split-budget, which then name that build (and, with --rebuild-above, the policy's rebuild) instead of asking for a rebuild; one
 //              [PT]BUILD: line reports it.  --pose and --rebuild-above work after it as they do otherwise; a bare --rebuild with it, or any other word than gpu (or host, the default), is exit 2
 //   --pose moved.obj: the scene of the config (and its cached .bvh) with the vertices and normals of moved.obj — the same triangles in the same order,
 //              moved — through adypt_multi_update_triangles: the BVH and the Woop data are refitted on the GPU, nothing is rebuilt
+//   --part-matrices FILE: the scene moved on the GPU, part by part (adypt_multi_bind_parts, adypt_multi_pose): a triangle's part is its material id, and
+//              triangles without a material (id -1) are one extra last part.  FILE holds lines `part m00 m01 m02 m03 m10 ... m23` (a row-major 3x4
+//              matrix: three linear entries and the translation per row; # starts a comment); parts that are not listed stay where they are.  One
+//              [PT]POSE: line reports it.  --rebuild-above and the options that name its rebuild work as after --pose; together with --pose: exit 2
 //   --rebuild: a new tree for the triangles as they are then (after --pose, when given), built on the GPU through adypt_multi_rebuild_bvh with the config's
 //              SAH costs
 //   --rebuild-method ploc: the same with the binary tree built by PLOC (adypt_multi_rebuild_bvh_ploc; --ploc-radius R, 1 to 32, 8 unless given) — a tighter
 //              tree for a few times the build time; linear (the default) is --rebuild's tree.  Naming a method asks for the rebuild
 //   --split-budget B: with --rebuild-method ploc only (else exit 2): large triangles are split into several references first, at most B * n more than
 //              triangles, B in [0, 1] (adypt_multi_rebuild_bvh_ploc_split)
-//   --rebuild-above R: with --pose only, and not with a bare --rebuild (else exit 2): the pose goes through adypt_multi_update_triangles_auto — the tree is
+//   --rebuild-above R: with --pose or --part-matrices only, and not with a bare --rebuild (else exit 2): the pose goes through adypt_multi_update_triangles_auto — the tree is
 //              refitted, its SAH cost measured, and rebuilt only where that is more than R times the cost of the tree as loaded (R finite and >= 0, no
 //              default; 0 always rebuilds).  --rebuild-method, --ploc-radius and --split-budget then name the rebuild of that policy (linear unless
 //              given) instead of asking for one outright
@@ -61,10 +65,10 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C] [--history-out len.exr]] [--guides-out PREFIX] [--pose moved.obj] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C] [--history-out len.exr]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
-	std::string noise_out, spp_out, denoise_out, guides_out, pose;
+	std::string noise_out, spp_out, denoise_out, guides_out, pose, part_matrices;
 	bool rebuild = false, bare_rebuild = false, have_rebuild_above = false;
 	double rebuild_above = 0.0;
 	std::string rebuild_method = "linear";
@@ -127,6 +131,7 @@ int main(int argc, char **argv)
 		}
 		else if(a == "--guides-out" && i + 1 < argc) guides_out = argv[++i];
 		else if(a == "--pose" && i + 1 < argc) pose = argv[++i];
+		else if(a == "--part-matrices" && i + 1 < argc) part_matrices = argv[++i];
 		else if(a == "--rebuild") rebuild = bare_rebuild = true;
 		else if(a == "--rebuild-above" && i + 1 < argc)
 		{
@@ -151,7 +156,8 @@ int main(int argc, char **argv)
 	if(build_on_gpu && !have_rebuild_method) rebuild_method = "ploc";
 	if(rebuild_method != "linear" && rebuild_method != "ploc") { fprintf(stderr, "--rebuild-method is linear or ploc\n"); return 2; }
 	if(have_split_budget && rebuild_method != "ploc") { fprintf(stderr, "--split-budget needs --rebuild-method ploc\n"); return 2; }
-	if(have_rebuild_above && pose.empty()) { fprintf(stderr, "--rebuild-above needs --pose moved.obj\n"); return 2; }
+	if(!pose.empty() && !part_matrices.empty()) { fprintf(stderr, "--pose and --part-matrices are two ways to move the scene: give one\n"); return 2; }
+	if(have_rebuild_above && pose.empty() && part_matrices.empty()) { fprintf(stderr, "--rebuild-above needs --pose moved.obj or --part-matrices FILE\n"); return 2; }
 	if(have_rebuild_above && bare_rebuild) { fprintf(stderr, "--rebuild-above decides about the rebuild itself: name its method with --rebuild-method, without --rebuild\n"); return 2; }
 	if(have_rebuild_above || build_on_gpu) rebuild = false; // (--rebuild-method names the policy's rebuild, or the first build)
 	if(!until && !noise_out.empty()) { fprintf(stderr, "--noise-out needs --noise T\n"); return 2; }
@@ -203,6 +209,46 @@ int main(int argc, char **argv)
 			memcpy(&pose_normals[(size_t)i * 9], (const uint8_t *)mt + i * 100 + 36, 36);
 		}
 		adypt_scene_free(moved);
+	}
+
+	std::vector<int32_t> part_of_triangle; // --part-matrices: the binding and one matrix per part, the identity where FILE names none
+	std::vector<float> part_matrix;
+	int32_t n_parts = 0;
+	if(!part_matrices.empty())
+	{
+		part_of_triangle.resize((size_t)n_tris);
+		bool loose = false;
+		for(int64_t i = 0; i < n_tris; ++i) // (100-byte records: the material id is the last word)
+		{
+			int32_t matid;
+			memcpy(&matid, (const uint8_t *)tris + i * 100 + 96, 4);
+			const bool known = matid >= 0 && matid < n_mats;
+			part_of_triangle[(size_t)i] = known ? matid : (int32_t)n_mats;
+			loose |= !known;
+		}
+		n_parts = (int32_t)n_mats + (loose ? 1 : 0);
+		for(int32_t k = 0; k < n_parts; ++k)
+			for(int j = 0; j < 12; ++j) part_matrix.push_back(j % 5 == 0 ? 1.0f : 0.0f);
+		FILE *f = fopen(part_matrices.c_str(), "r");
+		if(!f) { fprintf(stderr, "[INSTANCE]Err: Unable to open %s\n", part_matrices.c_str()); return 1; }
+		char line[1024];
+		for(int at = 1; fgets(line, sizeof(line), f); ++at)
+		{
+			if(char *hash = strchr(line, '#')) *hash = 0;
+			long part;
+			float m[12];
+			int used = 0;
+			const int got = sscanf(line, "%ld %f %f %f %f %f %f %f %f %f %f %f %f %n", &part, m, m + 1, m + 2, m + 3, m + 4, m + 5, m + 6, m + 7, m + 8, m + 9, m + 10, m + 11, &used);
+			if(got <= 0 && line[strspn(line, " \t\r\n")] == 0) continue;
+			if(got != 13 || line[used] != 0 || part < 0 || part >= n_parts)
+			{
+				fprintf(stderr, "[INSTANCE]Err: %s line %d is not `part m00 ... m23` with a part in [0, %d)\n", part_matrices.c_str(), at, (int)n_parts);
+				fclose(f);
+				return 1;
+			}
+			memcpy(&part_matrix[(size_t)part * 12], m, sizeof(m));
+		}
+		fclose(f);
 	}
 
 	adypt_bvh *bvh = nullptr;
@@ -276,6 +322,21 @@ int main(int argc, char **argv)
 		float ms[4] = {0, 0, 0, 0};
 		(void)adypt_get_refit_timing(adypt_multi_context(multi, 0), ms, 4);
 		printf("[PT]INFO: pose %s: %lld triangles moved, refit %.3f ms (scatter %.3f, references and Woop %.3f, nodes %.3f)\n", pose.c_str(), (long long)n_tris, ms[3], ms[0], ms[1], ms[2]);
+		if(have_rebuild_above)
+			printf("[PT]INFO: pose policy: tree cost %.4f -> %.4f (ratio %.4f, allowed %g): %s\n", outcome.built.cost, outcome.refitted.cost, outcome.refitted.cost / outcome.built.cost, rebuild_above,
+			       outcome.rebuilt ? ("rebuilt (" + rebuild_figures(outcome.rebuild) + ")").c_str() : "kept");
+	}
+	if(!part_matrices.empty())
+	{
+		adypt_pose_outcome outcome;
+		const adypt_pose_policy policy{rebuild_above, ploc ? 1 : 0, ploc_radius, split_budget};
+		int code = adypt_multi_bind_parts(multi, part_of_triangle.data(), n_tris, n_parts);
+		if(code == ADYPT_OK) code = adypt_multi_pose(multi, part_matrix.data(), n_parts, &cfg.bvh, have_rebuild_above ? &policy : nullptr, &outcome);
+		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		float ms[4] = {0, 0, 0, 0};
+		(void)adypt_get_refit_timing(adypt_multi_context(multi, 0), ms, 4);
+		printf("[PT]POSE: parts %d triangles %lld from %s, refit %.3f ms (matrices and pose %.3f, references and Woop %.3f, nodes %.3f)\n", (int)n_parts, (long long)n_tris, part_matrices.c_str(), ms[3],
+		       ms[0], ms[1], ms[2]);
 		if(have_rebuild_above)
 			printf("[PT]INFO: pose policy: tree cost %.4f -> %.4f (ratio %.4f, allowed %g): %s\n", outcome.built.cost, outcome.refitted.cost, outcome.refitted.cost / outcome.built.cost, rebuild_above,
 			       outcome.rebuilt ? ("rebuilt (" + rebuild_figures(outcome.rebuild) + ")").c_str() : "kept");

@@ -11,6 +11,7 @@
 //                         per-reference copy and count in one step (ctx_replace_geometry), so a refused or failed call leaves the old scene traceable.
 #include "ctx_unit.hpp"
 #include "build_internal.hpp"
+#include "pose_internal.hpp"
 #include "tri_record.hpp"
 #include "wide_cut.hpp"
 #include "ploc.hpp"
@@ -129,6 +130,7 @@ int set_triangles(adypt_ctx *c, const char *who, const void *triangles, int64_t 
 	NewGeometry geometry{&records, &classes, n_tris};
 	CTX_STEP(build_for_triangles(c, cfg, method == 1 ? radius : 0, split_budget, who, (const float4 *)records.get(), &geometry, out));
 	g->timer.complete(); // (the build has waited for the stream)
+	pose_drop_binding(c); // (a rest pose and a binding were the old triangles': pose.hip)
 	return ADYPT_OK; // (the old records and class bytes go with `records` and `classes`)
 }
 

@@ -7,6 +7,7 @@
 //     k_refit_nodes    one launch per level of the tree, deepest first: 8 lanes per node, one slot per lane.  A level reads only the exact boxes of
 //                      deeper levels, which earlier launches on the same stream wrote: the stream order is the whole dependency — no atomics, no
 //                      flags between workgroups, no fences.
+// Everything around the scatter is refit_begin and refit_tail (refit_internal.hpp), which adypt_pose (pose.hip) runs around its own writer of the records.
 // The plan (every node's level) is made once per context, at the first update, from one copy of the node array to the host; the topology never changes.
 // Also here: the SAH cost of the tree as it is (tree_cost.hpp; adypt_get_tree_cost) and the refit that rebuilds when that cost says so
 // (adypt_update_triangles_auto):
@@ -314,6 +315,74 @@ void refit_adopt_tree(adypt_ctx *c, TreeLevels &&tree)
 	rf->have_built = false; // (a new tree: its cost is measured when it is first asked for)
 }
 
+int refit_begin(adypt_ctx *c)
+{
+	const CtxScene sc = ctx_scene(c);
+	CTX_STEP(ctx_drain(c));
+	const CtxInfo i = ctx_info(c);
+	Refitter *rf = ctx_state<Refitter>(c, kAttachRefit);
+	CTX_STEP(ensure_plan(c, rf, sc, i.stream));
+	rf->timer.invalidate();
+	CTX_TRY(c, rf->timer.mark(0, i.stream));
+	return ADYPT_OK;
+}
+
+int refit_tail(adypt_ctx *c)
+{
+	const CtxScene sc = ctx_scene(c);
+	const CtxInfo i = ctx_info(c);
+	Refitter *rf = ctx_state<Refitter>(c, kAttachRefit);
+	rf->tree.ref_boxes.release(); // (a split tree's clipped boxes were the old pose's: from here on its leaves bound whole triangles, as an SBVH tree's do)
+	CTX_TRY(c, rf->timer.mark(1, i.stream));
+	CTX_STEP(ctx_expand_references(c));
+	CTX_TRY(c, refit_launch_woop(i.stream, (const float4 *)sc.triangles, sc.tri_float4, sc.tri_indices, sc.n_refs, sc.woop));
+	CTX_TRY(c, rf->timer.mark(2, i.stream));
+	CTX_TRY(c, refit_launch_levels(i.stream, rf->tree, sc.nodes, sc.tri_indices, (const float4 *)sc.triangles, sc.tri_float4));
+	CTX_STEP(ctx_refresh_root_card(c)); // (node 0 has new boxes: k_path's root card follows, on the same stream)
+	CTX_TRY(c, rf->timer.mark(3, i.stream));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
+	rf->timer.complete();
+	return adypt_reset(c); // the image, the frozen blocks, the frames parked ahead and the primary-hit cache were the old pose's
+}
+
+std::string refit_policy_refused(const char *who, const adypt_bvh_params *params, const adypt_pose_policy *policy, adypt_bvh_params *cfg)
+{
+	const std::string w = std::string(who) + ": ";
+	if(!cost_params(params, cfg)) return w + "the SAH costs must be positive finite numbers";
+	const adypt_pose_policy p = *policy;
+	if(!(p.rebuild_above >= 0.0 && std::isfinite(p.rebuild_above))) return w + "rebuild_above must be a finite number >= 0";
+	if(p.method != 0 && p.method != 1) return w + "method must be 0 (linear) or 1 (ploc)";
+	if(p.method == 1 && (p.radius < kPlocMinRadius || p.radius > kPlocMaxRadius)) return w + "the radius must be in [1, 32]";
+	if(!(p.split_budget >= 0.0 && p.split_budget <= 1.0)) return w + "the split budget must be in [0, 1]";
+	if(p.method == 0 && p.split_budget != 0.0) return w + "a split budget needs method 1 (ploc)";
+	return std::string();
+}
+
+int refit_under_policy(adypt_ctx *c, const char *who, const adypt_bvh_params &cfg, const adypt_pose_policy &p, adypt_pose_outcome *outcome, const std::function<int()> &refit)
+{
+	const CtxInfo i = ctx_info(c);
+	CTX_TRY(c, hipSetDevice(i.device));
+	CTX_STEP(ctx_drain(c));
+	Refitter *rf = ctx_state<Refitter>(c, kAttachRefit);
+	adypt_pose_outcome o{};
+	CTX_STEP(built_cost(c, rf, i.stream, cfg, who, &o.built)); // (of the tree as it is before this call's refit)
+	CTX_STEP(refit());
+	const int measured = measure_cost(c, rf, i.stream, cfg, who, &o.refitted, &o.cost_ms);
+	if(measured != ADYPT_OK) return ctx_fail(c, measured, std::string(adypt_last_error(c)) + " (the triangles have been updated and the tree refitted; nothing was rebuilt)");
+	o.now = o.refitted;
+	if(o.refitted.cost > p.rebuild_above * o.built.cost)
+	{
+		// (a rebuild that is refused or fails has left the refitted tree in place and set the error)
+		if(p.method == 0) CTX_STEP(adypt_rebuild_bvh(c, &cfg, &o.rebuild));
+		else if(p.split_budget == 0.0) CTX_STEP(adypt_rebuild_bvh_ploc(c, &cfg, p.radius, &o.rebuild));
+		else CTX_STEP(adypt_rebuild_bvh_ploc_split(c, &cfg, p.radius, p.split_budget, &o.rebuild));
+		o.rebuilt = 1;
+		CTX_STEP(built_cost(c, rf, i.stream, cfg, who, &o.now)); // (the rebuild has marked it stale: the new tree's, which is the reference from here on)
+	}
+	if(outcome) *outcome = o;
+	return ADYPT_OK;
+}
+
 }  // namespace adypt
 
 extern "C" {
@@ -325,15 +394,12 @@ int adypt_update_triangles(adypt_ctx *c, int64_t first, int64_t count, const flo
 	if(!positions) return ctx_fail(c, ADYPT_E_INVALID, "adypt_update_triangles: positions is null");
 	if(first < 0 || count < 0 || first > sc.n_tris || count > sc.n_tris - first)
 		return ctx_fail(c, ADYPT_E_INVALID, "adypt_update_triangles: triangles [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) + ") are not all of the scene's " + std::to_string(sc.n_tris));
-	CTX_STEP(ctx_drain(c));
 	const CtxInfo i = ctx_info(c);
+	CTX_TRY(c, hipSetDevice(i.device));
 	Refitter *rf = ctx_state<Refitter>(c, kAttachRefit);
-	CTX_STEP(ensure_plan(c, rf, sc, i.stream));
-	rf->tree.ref_boxes.release(); // (a split tree's clipped boxes were the old pose's: from here on its leaves bound whole triangles, as an SBVH tree's do)
 	const size_t n_stage = (size_t)count * 9;
 	CTX_TRY(c, at_least(rf->d_stage, n_stage * (normals ? 2 : 1)));
-	rf->timer.invalidate();
-	CTX_TRY(c, rf->timer.mark(0, i.stream));
+	CTX_STEP(refit_begin(c));
 	if(count > 0)
 	{
 		float *d_pos = rf->d_stage, *d_nrm = normals ? d_pos + n_stage : nullptr;
@@ -342,16 +408,7 @@ int adypt_update_triangles(adypt_ctx *c, int64_t first, int64_t count, const flo
 		hipLaunchKernelGGL(k_refit_scatter, dim3(grid_of(count, kRefitThreads)), dim3(kRefitThreads), 0, i.stream, sc.triangles, sc.tri_float4, first, count, (const float *)d_pos, (const float *)d_nrm);
 		CTX_TRY(c, hipGetLastError());
 	}
-	CTX_TRY(c, rf->timer.mark(1, i.stream));
-	CTX_STEP(ctx_expand_references(c));
-	CTX_TRY(c, refit_launch_woop(i.stream, (const float4 *)sc.triangles, sc.tri_float4, sc.tri_indices, sc.n_refs, sc.woop));
-	CTX_TRY(c, rf->timer.mark(2, i.stream));
-	CTX_TRY(c, refit_launch_levels(i.stream, rf->tree, sc.nodes, sc.tri_indices, (const float4 *)sc.triangles, sc.tri_float4));
-	CTX_STEP(ctx_refresh_root_card(c)); // (node 0 has new boxes: k_path's root card follows, on the same stream)
-	CTX_TRY(c, rf->timer.mark(3, i.stream));
-	CTX_TRY(c, hipStreamSynchronize(i.stream));
-	rf->timer.complete();
-	return adypt_reset(c); // the image, the frozen blocks, the frames parked ahead and the primary-hit cache were the old pose's
+	return refit_tail(c);
 }
 
 int adypt_get_tree_cost(adypt_ctx *c, const adypt_bvh_params *params, adypt_tree_cost *out)
@@ -382,34 +439,9 @@ int adypt_update_triangles_auto(adypt_ctx *c, int64_t first, int64_t count, cons
 	if(first < 0 || count < 0 || first > sc.n_tris || count > sc.n_tris - first)
 		return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": triangles [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) + ") are not all of the scene's " + std::to_string(sc.n_tris));
 	adypt_bvh_params cfg;
-	if(!cost_params(params, &cfg)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": the SAH costs must be positive finite numbers");
-	const adypt_pose_policy p = *policy;
-	if(!(p.rebuild_above >= 0.0 && std::isfinite(p.rebuild_above))) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": rebuild_above must be a finite number >= 0");
-	if(p.method != 0 && p.method != 1) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": method must be 0 (linear) or 1 (ploc)");
-	if(p.method == 1 && (p.radius < kPlocMinRadius || p.radius > kPlocMaxRadius)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": the radius must be in [1, 32]");
-	if(!(p.split_budget >= 0.0 && p.split_budget <= 1.0)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": the split budget must be in [0, 1]");
-	if(p.method == 0 && p.split_budget != 0.0) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": a split budget needs method 1 (ploc)");
-	const CtxInfo i = ctx_info(c);
-	CTX_TRY(c, hipSetDevice(i.device));
-	CTX_STEP(ctx_drain(c));
-	Refitter *rf = ctx_state<Refitter>(c, kAttachRefit);
-	adypt_pose_outcome o{};
-	CTX_STEP(built_cost(c, rf, i.stream, cfg, who, &o.built)); // (of the tree as it is before this call's refit)
-	CTX_STEP(adypt_update_triangles(c, first, count, positions, normals));
-	const int measured = measure_cost(c, rf, i.stream, cfg, who, &o.refitted, &o.cost_ms);
-	if(measured != ADYPT_OK) return ctx_fail(c, measured, std::string(adypt_last_error(c)) + " (the triangles have been updated and the tree refitted; nothing was rebuilt)");
-	o.now = o.refitted;
-	if(o.refitted.cost > p.rebuild_above * o.built.cost)
-	{
-		// (a rebuild that is refused or fails has left the refitted tree in place and set the error)
-		if(p.method == 0) CTX_STEP(adypt_rebuild_bvh(c, &cfg, &o.rebuild));
-		else if(p.split_budget == 0.0) CTX_STEP(adypt_rebuild_bvh_ploc(c, &cfg, p.radius, &o.rebuild));
-		else CTX_STEP(adypt_rebuild_bvh_ploc_split(c, &cfg, p.radius, p.split_budget, &o.rebuild));
-		o.rebuilt = 1;
-		CTX_STEP(built_cost(c, rf, i.stream, cfg, who, &o.now)); // (the rebuild has marked it stale: the new tree's, which is the reference from here on)
-	}
-	if(outcome) *outcome = o;
-	return ADYPT_OK;
+	const std::string why = refit_policy_refused(who, params, policy, &cfg);
+	if(!why.empty()) return ctx_fail(c, ADYPT_E_INVALID, why);
+	return refit_under_policy(c, who, cfg, *policy, outcome, [=]() { return adypt_update_triangles(c, first, count, positions, normals); });
 }
 
 int adypt_read_bvh(adypt_ctx *c, void *nodes_out, float *woop_out)

@@ -1,10 +1,15 @@
 // What build.hip needs of refit.hip: how a triangle record's positions are read, the levels of a tree as the refit keeps them, the launches that turn
-// a topology plus triangles into Woop data and node records, and the hand-over of a new tree's levels to the context's refit state.  Not part of the C-ABI.
+// a topology plus triangles into Woop data and node records, and the hand-over of a new tree's levels to the context's refit state.  What pose.hip
+// needs of it: the refit around another writer of the records, and the refit-or-rebuild policy around that.  Not part of the C-ABI.
 #pragma once
 #include "ctx_access.hpp"
 #include "resources.hpp"
+#include "../../../include/adypt_hip.h"
+#include "../../../include/adypt_host.h"
 
 #include <cstdint>
+#include <functional>
+#include <string>
 #include <vector>
 
 namespace adypt {
@@ -35,5 +40,20 @@ hipError_t refit_launch_levels(hipStream_t stream, const TreeLevels &tree, uint4
 // The context's tree has been replaced: `tree` is taken as the refit's.  A later adypt_update_triangles refits the new topology; the timing of the last
 // update is no longer to be read.
 void refit_adopt_tree(adypt_ctx *c, TreeLevels &&tree);
+
+// ---- one refit around whoever writes the moved records: adypt_update_triangles' k_refit_scatter, adypt_pose's k_pose (pose.hip) ----
+// Before the writer's launches: the context is drained, the plan made (at the first refit of a tree), the timing of the last refit invalidated and the
+// first timer mark put on the context's stream.
+int refit_begin(adypt_ctx *c);
+// Behind the writer's launches on the context's stream, which end the `scatter` stage of adypt_get_refit_timing: a split tree's reference boxes are
+// dropped, the per-reference copy of the records is made again (ctx_expand_references), then the Woop data (refit_launch_woop), the node levels
+// (refit_launch_levels), the root card (ctx_refresh_root_card) and the timer marks between them; the stream is waited for and the context left as
+// adypt_reset leaves it.
+int refit_tail(adypt_ctx *c);
+// What adypt_update_triangles_auto refuses of its params and policy, `cfg` being the params with their defaults filled in: the reason, or empty.
+std::string refit_policy_refused(const char *who, const adypt_bvh_params *params, const adypt_pose_policy *policy, adypt_bvh_params *cfg);
+// adypt_update_triangles_auto around any refit: the reference cost, `refit` (a refit_begin .. refit_tail that has checked its own arguments), the cost
+// of the refitted tree, and the policy's rebuild where that cost says so.
+int refit_under_policy(adypt_ctx *c, const char *who, const adypt_bvh_params &cfg, const adypt_pose_policy &policy, adypt_pose_outcome *outcome, const std::function<int()> &refit);
 
 }  // namespace adypt

@@ -338,7 +338,7 @@ int adypt_get_denoise_merge_ms(adypt_ctx *ctx, float *ms);
 int adypt_update_triangles(adypt_ctx *ctx, int64_t first, int64_t count, const float *positions, const float *normals);
 /* the node array (n_nodes x 80 bytes) and the Woop array (n_refs x 12 floats) as they are on the device; either may be NULL */
 int adypt_read_bvh(adypt_ctx *ctx, void *nodes_out, float *woop_out);
-/* HIP-event times of the last adypt_update_triangles in ms: [0] the upload and scatter of the new data, [1] the per-reference records and the Woop
+/* HIP-event times of the last adypt_update_triangles (or adypt_pose, below) in ms: [0] the upload and scatter of the new data (the matrices and k_pose), [1] the per-reference records and the Woop
  * data, [2] the nodes (every level), [3] all of it.  Returns the number of entries and writes them only when capacity holds them all. */
 int adypt_get_refit_timing(adypt_ctx *ctx, float *ms, int capacity);
 
@@ -478,6 +478,40 @@ typedef struct adypt_pose_outcome {
 int adypt_update_triangles_auto(adypt_ctx *ctx, int64_t first, int64_t count, const float *positions, const float *normals, const adypt_bvh_params *params,
                                 const adypt_pose_policy *policy, adypt_pose_outcome *outcome);
 
+/* ---- posing on the GPU: bind a rest pose once, move it by part or joint matrices ------------------------------------------------------------
+ * adypt_update_triangles takes every moved vertex from the host.  A caller whose poses are affine maps of rigid parts, or blends of them (a door, a
+ * turntable, a vehicle, a skinned figure), binds once and then uploads n x 12 floats per pose: a matrix is row-major 3x4, [r][0..2] the linear part
+ * and [r][3] the translation.  The arithmetic is csrc/device/pose.hpp, which the host's adypt_pose_triangles (adypt_host.h) compiles too:
+ * adypt_read_triangle_records after adypt_pose equals adypt_pack_triangles of that function's triangles byte for byte, and nodes and Woop data equal
+ * adypt_bvh_refit + adypt_woop_matrices of them, as after adypt_update_triangles.  Normals go through the cofactor matrix (right under any affine map,
+ * mirrors included) and are normalised again; singular matrices are allowed — a collapsed triangle gets NaN Woop data and is never hit.
+ * adypt_bind_parts gives every triangle a part (part_of_triangle[i] in [0, n_parts)); adypt_bind_skin gives every vertex four weighted joints
+ * (vertex v of triangle i: slots 12 i + 4 v + 0..3; a slot of weight 0 is skipped and its joint index may be anything; weights are finite and >= 0 and
+ * are used as given, not normalised).  A bind makes the device keep words 0..17 of the records AS THEY ARE THEN as the rest pose; every adypt_pose
+ * starts from it, so poses never compound.  A new bind replaces the old one.  adypt_rebuild_bvh* keep the binding; adypt_update_triangles writes the
+ * posed records only, never the rest pose; a successful adypt_set_triangles drops the binding.
+ * adypt_pose uploads the matrices, runs k_pose over all triangles and then the refit of adypt_update_triangles from its Woop data on, on the context's
+ * stream; adypt_get_refit_timing answers afterwards, its [0] being the matrix upload and k_pose.  policy NULL: refit only (params is not looked at,
+ * *outcome is zeroed).  With a policy the call behaves as adypt_update_triangles_auto does around its update.
+ * ADYPT_E_INVALID, checked on the host before the device is touched, nothing changes (a refused bind leaves the old binding in place): a null array;
+ * n_tris other than the context's count; n_parts or n_joints outside [1, 65536]; a part index out of range; a joint index out of range in a slot of
+ * non-zero weight; a weight that is negative or not finite; n_matrices other than the binding's; a matrix entry that is not finite; what
+ * adypt_update_triangles_auto refuses of a policy.  adypt_pose without a binding: ADYPT_E_STATE.
+ * Memory, kept until adypt_unbind_pose, adypt_set_triangles or adypt_destroy: 72 B per triangle of rest pose, 4 B (parts) or 72 B (skin) of binding,
+ * 48 B per matrix. */
+typedef struct adypt_pose_binding {
+	int32_t kind;                /* 0 none, 1 parts, 2 skin */
+	int32_t n_matrices;          /* n_parts or n_joints */
+	int64_t n_tris;
+	int64_t device_bytes;        /* what the binding holds on the device */
+} adypt_pose_binding;
+int adypt_bind_parts(adypt_ctx *ctx, const int32_t *part_of_triangle, int64_t n_tris, int32_t n_parts);
+int adypt_bind_skin(adypt_ctx *ctx, const uint16_t *joints /* n_tris x 12 */, const float *weights /* n_tris x 12 */, int64_t n_tris, int32_t n_joints);
+int adypt_pose(adypt_ctx *ctx, const float *matrices /* n_matrices x 12 */, int32_t n_matrices, const adypt_bvh_params *params, const adypt_pose_policy *policy /* NULL: refit only */,
+               adypt_pose_outcome *outcome /* may be NULL */);
+int adypt_unbind_pose(adypt_ctx *ctx);
+int adypt_get_pose_binding(adypt_ctx *ctx, adypt_pose_binding *out);
+
 /* Trace an arbitrary batch of rays through the same traversal kernel: rays = n x 8 floats
  * (ox, oy, oz, tmin, dx, dy, dz, unused).  with_stats selects the instrumented kernel variant. */
 int adypt_trace_rays(adypt_ctx *ctx, const float *rays, int64_t n, adypt_hit *hits, int with_stats);
@@ -609,6 +643,14 @@ int adypt_create_multi_from_triangles(adypt_multi **out, const adypt_scene_desc 
 int adypt_multi_get_tree_cost(adypt_multi *m, const adypt_bvh_params *params, adypt_tree_cost *out);
 int adypt_multi_update_triangles_auto(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals, const adypt_bvh_params *params,
                                       const adypt_pose_policy *policy, adypt_pose_outcome *outcome);
+/* adypt_bind_parts / adypt_bind_skin / adypt_pose / adypt_unbind_pose on every device, in device order: every device keeps its own rest pose and
+ * binding and poses its own copy; no collective.  Bad arguments are refused by the first device, so no device has changed.  With a policy *outcome is
+ * the first device's, held against the others' as for adypt_multi_update_triangles_auto.  adypt_multi_get_pose_binding: the first device's. */
+int adypt_multi_bind_parts(adypt_multi *m, const int32_t *part_of_triangle, int64_t n_tris, int32_t n_parts);
+int adypt_multi_bind_skin(adypt_multi *m, const uint16_t *joints, const float *weights, int64_t n_tris, int32_t n_joints);
+int adypt_multi_pose(adypt_multi *m, const float *matrices, int32_t n_matrices, const adypt_bvh_params *params, const adypt_pose_policy *policy, adypt_pose_outcome *outcome);
+int adypt_multi_unbind_pose(adypt_multi *m);
+int adypt_multi_get_pose_binding(adypt_multi *m, adypt_pose_binding *out);
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

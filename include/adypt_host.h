@@ -158,6 +158,13 @@ void adypt_woop_matrices(const void *tris, const int32_t *tri_indices, int64_t n
  * outside [0, n_mats)).  Either may be NULL.  materials: n_mats 64-byte GPUMaterial.  The definition is csrc/device/tri_record.hpp, which the device
  * (adypt_set_triangles of adypt_hip.h) compiles too: both give the same bytes.  ADYPT_E_INVALID for a null array that is needed or a negative count. */
 int adypt_pack_triangles(const void *triangles, int64_t n_tris, const void *materials, int64_t n_mats, int32_t n_textures, void *records_out, uint8_t *classes_out);
+/* `n_tris` 100-byte Triangles posed by row-major 3x4 matrices (n_matrices x 12 floats, n_matrices in [1, 65536]): positions through the matrix, normals
+ * through its cofactor matrix and normalised again, texture coordinates and material id as they are; triangles_out = n_tris x 100 bytes, which may be
+ * triangles_in.  Either parts (one index per triangle) or joints and weights (n_tris x 12 each: vertex v's four slots at 4 v; a slot of weight 0 is
+ * skipped, its index never read) is given, the other NULL.  The definition is csrc/device/pose.hpp, which the device (adypt_pose of adypt_hip.h)
+ * compiles too: both give the same bits.  ADYPT_E_INVALID — nothing is written — for what adypt_bind_parts / adypt_bind_skin / adypt_pose refuse. */
+int adypt_pose_triangles(const void *triangles_in, int64_t n_tris, const int32_t *parts_or_null, const uint16_t *joints_or_null, const float *weights_or_null, const float *matrices,
+                         int32_t n_matrices, void *triangles_out);
 /* Camera::GetView/GetProjection + the inverses of SetCamera (src/Tracer/Camera.cpp:13-23, OglPathTracer.cpp:27-32) */
 void adypt_camera_matrices(float fov, float yaw, float pitch, int width, int height, float inv_proj[16], float inv_view[16]);
 /* Sobol::Next (src/Util/Sobol.cpp:16-21): points of frames [first, first+n), dim <= 64; out = n*dim floats */

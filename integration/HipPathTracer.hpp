@@ -286,6 +286,41 @@ public:
 		return false;
 	}
 
+	// Posing on the GPU (adypt_hip.h, adypt_bind_parts / adypt_bind_skin / adypt_pose): bind once, then move the scene by 3x4 matrices — only the
+	// matrices cross the bus.  BindParts: one part per triangle of Scene::GetTriangles(), 0 <= part < n_parts.  BindSkin: four weighted joints per
+	// vertex (triangles x 12 each: vertex v's slots at 4 v; a slot of weight 0 is skipped).  Either makes every device keep the triangles as they are
+	// then as the rest pose, from which every Pose starts; a refused call leaves an earlier binding in place, SetTriangles drops it.
+	bool BindParts(const std::vector<int32_t> &part_of_triangle, int32_t n_parts)
+	{
+		if(adypt_multi_bind_parts(m_gpus, part_of_triangle.data(), (int64_t)part_of_triangle.size(), n_parts) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+	bool BindSkin(const std::vector<uint16_t> &joints, const std::vector<float> &weights, int32_t n_joints)
+	{
+		if(joints.size() != weights.size() || joints.size() % 12 != 0) { printf("[PT]ERR: BindSkin: joints and weights are 12 per triangle\n"); return false; }
+		if(adypt_multi_bind_skin(m_gpus, joints.data(), weights.data(), (int64_t)(joints.size() / 12), n_joints) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+	// matrices: one per part or joint, 12 floats each, row-major 3x4 ([r][0..2] linear, [r][3] translation; a glm::mat4x3 is its transpose).  The tree is
+	// refitted as UpdateTriangles refits it; the sample counter restarts as after a Trace(false).
+	bool Pose(const std::vector<float> &matrices)
+	{
+		if(matrices.size() % 12 == 0 && adypt_multi_pose(m_gpus, matrices.data(), (int32_t)(matrices.size() / 12), nullptr, nullptr, nullptr) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", matrices.size() % 12 ? "Pose: a matrix is 12 floats" : adypt_multi_last_error(m_gpus));
+		return false;
+	}
+	// ... and decides about a rebuild itself, as the UpdateTriangles overload above does
+	bool Pose(const std::vector<float> &matrices, const PosePolicy &policy, adypt_pose_outcome *outcome = nullptr, const adypt_bvh_params *params = nullptr)
+	{
+		const adypt_pose_policy p = {policy.rebuild_above, policy.method == RebuildMethod::PLOC ? 1 : 0, policy.radius, policy.split_budget};
+		if(matrices.size() % 12 == 0 && adypt_multi_pose(m_gpus, matrices.data(), (int32_t)(matrices.size() / 12), params, &p, outcome) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", matrices.size() % 12 ? "Pose: a matrix is 12 floats" : adypt_multi_last_error(m_gpus));
+		return false;
+	}
+	bool UnbindPose() { return adypt_multi_unbind_pose(m_gpus) == ADYPT_OK; }
+
 	// what DrawScreen puts on screen, for a caller-owned W x H RGBA8 texture / window (every device fills in its own tiles)
 	bool ReadScreen(std::vector<uint8_t> *rgba8) const
 	{
