@@ -29,6 +29,13 @@ class Texture(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgb", C.c_void_p)]
 
 
+class Struct(C.Structure):
+    """A C struct whose fields make a dict by name."""
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SceneDesc(C.Structure):
     _fields_ = [("nodes", C.c_void_p), ("n_nodes", C.c_int64), ("tri_indices", C.c_void_p), ("n_refs", C.c_int64),
                 ("woop", C.c_void_p), ("triangles", C.c_void_p), ("n_tris", C.c_int64), ("materials", C.c_void_p),
@@ -46,23 +53,17 @@ class Hit(C.Structure):
                 ("nodes", C.c_uint32), ("tris", C.c_uint32), ("hash", C.c_uint32), ("max_depth", C.c_uint32)]
 
 
-class Stats(C.Structure):
+class Stats(Struct):
     _fields_ = [("rays", C.c_uint64), ("nodes_visited", C.c_uint64), ("tris_tested", C.c_uint64), ("hits", C.c_uint64),
                 ("shaded", C.c_uint64), ("stack_overflows", C.c_uint64), ("bad_materials", C.c_uint64),
                 ("max_stack", C.c_uint32), ("trace_launches", C.c_uint32), ("trace_ms", C.c_double), ("shade_ms", C.c_double),
                 ("path_ms", C.c_double), ("path_launches", C.c_uint32), ("audit_errors", C.c_uint32), ("path_rays", C.c_uint64),
                 ("path_nodes", C.c_uint64), ("path_tris", C.c_uint64), ("path_hits", C.c_uint64), ("path_shaded", C.c_uint64)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class Noise(C.Structure):
+class Noise(Struct):
     _fields_ = [("mean_noise", C.c_double), ("worst_block", C.c_double), ("worst_index", C.c_int32), ("spp", C.c_int32),
                 ("pixels", C.c_int64)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Adaptive(C.Structure):
@@ -103,17 +104,14 @@ class BuildInfo(C.Structure):
                 ("wide_ms", C.c_double)]
 
 
-class RebuildInfo(C.Structure):
+class RebuildInfo(Struct):
     """adypt_rebuild_info."""
     _fields_ = [("n_nodes", C.c_int64), ("n_refs", C.c_int64), ("levels", C.c_int32), ("binary_depth", C.c_int32)]
 
 
-class TreeCost(C.Structure):
+class TreeCost(Struct):
     """adypt_tree_cost."""
     _fields_ = [("cost", C.c_double), ("inner_q", C.c_uint64), ("leaf_q", C.c_uint64), ("n_nodes", C.c_int64)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class PosePolicy(C.Structure):
@@ -127,15 +125,12 @@ class PoseOutcome(C.Structure):
 
     def as_dict(self):
         return {"built": self.built.as_dict(), "refitted": self.refitted.as_dict(), "now": self.now.as_dict(), "rebuilt": int(self.rebuilt),
-                "rebuild": {k: getattr(self.rebuild, k) for k, _ in self.rebuild._fields_}, "cost_ms": float(self.cost_ms)}
+                "rebuild": self.rebuild.as_dict(), "cost_ms": float(self.cost_ms)}
 
 
-class PoseBinding(C.Structure):
+class PoseBinding(Struct):
     """adypt_pose_binding."""
     _fields_ = [("kind", C.c_int32), ("n_matrices", C.c_int32), ("n_tris", C.c_int64), ("device_bytes", C.c_int64)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 # every symbol include/*.h declares, with its signature (tests/test_abi.py checks the export list against the headers)

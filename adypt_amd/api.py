@@ -446,18 +446,25 @@ def _scene_desc(scene: HipScene, width: int, height: int) -> Tuple[N.SceneDesc, 
     return d, keep
 
 
-def _set_triangles_args(who: str, triangles: Optional[np.ndarray], cfg: Optional[N.BvhParams], method: str, radius: int, split_budget: float) -> tuple:
-    """(triangles, n_tris, params, method, radius, split_budget) of adypt_set_triangles / adypt_create_from_triangles (the latter takes the last four);
-    what only Python can get wrong is refused here, everything else by the library."""
+def _build_args(who: str, cfg: Optional[N.BvhParams], method: str, radius: int, split_budget: float, split_needs_ploc: bool = True) -> tuple:
+    """(params, method, radius, split_budget) as every entry that builds a tree takes them (csrc/device/build_request.hpp); what only Python can get wrong is
+    refused here, everything else by the library — with split_needs_ploc False a split_budget with "linear" too."""
     if method not in ("linear", "ploc"):
         raise ValueError("%s: method must be 'linear' or 'ploc', not %r" % (who, method))
-    params = None if cfg is None else C.byref(cfg)
+    if split_needs_ploc and split_budget != 0.0 and method != "ploc":
+        raise ValueError("%s: split_budget needs method 'ploc'" % who)
+    return (None if cfg is None else C.byref(cfg), 1 if method == "ploc" else 0, int(radius), float(split_budget))
+
+
+def _set_triangles_args(who: str, triangles: Optional[np.ndarray], cfg: Optional[N.BvhParams], method: str, radius: int, split_budget: float) -> tuple:
+    """(triangles, n_tris, params, method, radius, split_budget) of adypt_set_triangles / adypt_create_from_triangles (the latter takes the last four)"""
+    build = _build_args(who, cfg, method, radius, split_budget, split_needs_ploc=False)
     if triangles is None:  # (the library's refusal to give)
-        return (None, 1, params, 1 if method == "ploc" else 0, int(radius), float(split_budget))
+        return (None, 1) + build
     t = np.ascontiguousarray(triangles).view(np.uint8).reshape(-1)
     if len(t) % TRI_BYTES:
         raise ValueError("%s: the triangles are not a whole number of %d-byte records" % (who, TRI_BYTES))
-    return (t.ctypes.data, len(t) // TRI_BYTES, params, 1 if method == "ploc" else 0, int(radius), float(split_budget))
+    return (t.ctypes.data, len(t) // TRI_BYTES) + build
 
 
 def _read_block_noise(ctx) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -706,14 +713,14 @@ class _Tracer:
         if rebuild_above is None:
             self._call("update_triangles", first, len(pos), pos.ctypes.data, None if nrm is None else nrm.ctypes.data)
             return None
-        if method not in ("linear", "ploc"):
-            raise ValueError("UpdateTriangles: method must be 'linear' or 'ploc', not %r" % (method,))
-        if split_budget != 0.0 and method != "ploc":
-            raise ValueError("UpdateTriangles: split_budget needs method 'ploc'")
-        policy = N.PosePolicy(float(rebuild_above), 1 if method == "ploc" else 0, int(radius), float(split_budget))
-        out = N.PoseOutcome()
-        self._call("update_triangles_auto", first, len(pos), pos.ctypes.data, None if nrm is None else nrm.ctypes.data,
-                   None if cfg is None else C.byref(cfg), C.byref(policy), C.byref(out))
+        return self._under_policy("UpdateTriangles", "update_triangles_auto", (first, len(pos), pos.ctypes.data, None if nrm is None else nrm.ctypes.data),
+                                  rebuild_above, cfg, method, radius, split_budget)
+
+    def _under_policy(self, who: str, name: str, args: tuple, rebuild_above: float, cfg: Optional[N.BvhParams], method: str, radius: int, split_budget: float) -> dict:
+        """adypt_update_triangles_auto / adypt_pose with the policy that the last five arguments make: the outcome"""
+        params, *build = _build_args(who, cfg, method, radius, split_budget)
+        policy, out = N.PosePolicy(float(rebuild_above), *build), N.PoseOutcome()
+        self._call(name, *args, params, C.byref(policy), C.byref(out))
         return out.as_dict()
 
     # ---- posing on the GPU (adypt_bind_parts, adypt_bind_skin, adypt_pose, include/adypt_hip.h; the definition: csrc/device/pose.hpp) ----
@@ -742,14 +749,7 @@ class _Tracer:
         if rebuild_above is None:
             self._call("pose", m.ctypes.data, len(m), None, None, None)
             return None
-        if method not in ("linear", "ploc"):
-            raise ValueError("Pose: method must be 'linear' or 'ploc', not %r" % (method,))
-        if split_budget != 0.0 and method != "ploc":
-            raise ValueError("Pose: split_budget needs method 'ploc'")
-        policy = N.PosePolicy(float(rebuild_above), 1 if method == "ploc" else 0, int(radius), float(split_budget))
-        out = N.PoseOutcome()
-        self._call("pose", m.ctypes.data, len(m), None if cfg is None else C.byref(cfg), C.byref(policy), C.byref(out))
-        return out.as_dict()
+        return self._under_policy("Pose", "pose", (m.ctypes.data, len(m)), rebuild_above, cfg, method, radius, split_budget)
 
     def UnbindPose(self) -> None:
         """Gives the rest pose and the binding back; the triangles stay as the last Pose() left them."""
@@ -791,19 +791,15 @@ class _Tracer:
         triangles (csrc/device/presplit.hpp; WideBVH.BuildPLOC(split_budget=...)'s bytes; GetRebuildPresplit(), ReadRefBoxes()) — for scenes with
         large triangles among small ones; rebuild such a tree for a new pose rather than refitting it.  Leaves the tracer as Reset() does (0 spp).  Several devices: on every device.  Returns n_nodes, n_refs, levels (size stack_size by it)
         and binary_depth."""
-        if method not in ("linear", "ploc"):
-            raise ValueError("RebuildBVH: method must be 'linear' or 'ploc', not %r" % (method,))
-        if split_budget != 0.0 and method != "ploc":
-            raise ValueError("RebuildBVH: split_budget needs method 'ploc'")
+        params, ploc, radius, split_budget = _build_args("RebuildBVH", cfg, method, radius, split_budget)
         info = N.RebuildInfo()
-        params = None if cfg is None else C.byref(cfg)
-        if method == "ploc" and split_budget != 0.0:
-            self._call("rebuild_bvh_ploc_split", params, int(radius), float(split_budget), C.byref(info))
-        elif method == "ploc":
-            self._call("rebuild_bvh_ploc", params, int(radius), C.byref(info))
+        if ploc and split_budget != 0.0:
+            self._call("rebuild_bvh_ploc_split", params, radius, split_budget, C.byref(info))
+        elif ploc:
+            self._call("rebuild_bvh_ploc", params, radius, C.byref(info))
         else:
             self._call("rebuild_bvh", params, C.byref(info))
-        return {k: getattr(info, k) for k, _ in info._fields_}
+        return info.as_dict()
 
     # ---- replacing the triangles on the GPU (adypt_set_triangles, include/adypt_hip.h; the record: csrc/device/tri_record.hpp) ----
     def SetTriangles(self, triangles: np.ndarray, cfg: Optional[N.BvhParams] = None, method: str = "ploc", radius: int = 8, split_budget: float = 0.0) -> dict:
@@ -812,7 +808,7 @@ class _Tracer:
         is refused or fails.  Leaves the tracer as Reset() does (0 spp).  Several devices: on every device.  Returns RebuildBVH's dict."""
         info = N.RebuildInfo()
         self._call("set_triangles", *_set_triangles_args("SetTriangles", triangles, cfg, method, radius, split_budget), C.byref(info))
-        return {k: getattr(info, k) for k, _ in info._fields_}
+        return info.as_dict()
 
     def GetTriangleCount(self) -> int:
         """The triangles the (first) device holds now."""
@@ -951,7 +947,7 @@ class HipPathTracer(_Tracer):
             info = N.RebuildInfo()
             args = _set_triangles_args("HipPathTracer.Initialize", scene.scene.triangles, cfg, method, radius, split_budget)[2:]
             N.check(N.lib.adypt_create_from_triangles(C.byref(self._h), C.byref(d), *args, C.byref(info)))
-            self.build_info = {k: getattr(info, k) for k, _ in info._fields_}
+            self.build_info = info.as_dict()
         else:
             N.check(N.lib.adypt_create(C.byref(self._h), C.byref(d)))
         self.SetConfig(config)
@@ -1075,7 +1071,7 @@ class MultiPathTracer(_Tracer):
             info = N.RebuildInfo()
             args = _set_triangles_args("MultiPathTracer.Initialize", scene.scene.triangles, cfg, method, radius, split_budget)[2:]
             self._check(N.lib.adypt_create_multi_from_triangles(C.byref(self._h), C.byref(d), devs, len(devices), *args, C.byref(info)))
-            self.build_info = {k: getattr(info, k) for k, _ in info._fields_}
+            self.build_info = info.as_dict()
         else:
             self._check(N.lib.adypt_create_multi(C.byref(self._h), C.byref(d), devs, len(devices)))
         self.SetConfig(config)

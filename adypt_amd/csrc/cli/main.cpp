@@ -160,6 +160,9 @@ int main(int argc, char **argv)
 	if(have_rebuild_above && pose.empty() && part_matrices.empty()) { fprintf(stderr, "--rebuild-above needs --pose moved.obj or --part-matrices FILE\n"); return 2; }
 	if(have_rebuild_above && bare_rebuild) { fprintf(stderr, "--rebuild-above decides about the rebuild itself: name its method with --rebuild-method, without --rebuild\n"); return 2; }
 	if(have_rebuild_above || build_on_gpu) rebuild = false; // (--rebuild-method names the policy's rebuild, or the first build)
+	// the tree that --rebuild-method, --ploc-radius and --split-budget name: the first build of --build gpu, the policy's rebuild, or the rebuild asked for
+	const bool ploc = rebuild_method == "ploc";
+	const adypt_pose_policy policy{rebuild_above, ploc ? 1 : 0, ploc_radius, split_budget};
 	if(!until && !noise_out.empty()) { fprintf(stderr, "--noise-out needs --noise T\n"); return 2; }
 	if(until && (primary >= 0 || spp < 2 || check_every < 1)) { fprintf(stderr, "--noise needs --spp >= 2, --check-every >= 1 and no --primary\n"); return 2; }
 	if(adaptive && (!until || save_every > 0)) { fprintf(stderr, "--adaptive needs --noise T and does not combine with --save-every\n"); return 2; }
@@ -273,9 +276,8 @@ int main(int argc, char **argv)
 	d.width = cfg.width; d.height = cfg.height; d.device = devices[0]; d.tile_rank = 0; d.tile_nranks = 1;
 	// any number of devices through the library's multi-device boundary (one device is its n_dev = 1 case): tile rank i on devices[i], one gather per saved image
 	adypt_multi *multi = nullptr;
-	const bool ploc = rebuild_method == "ploc";
 	adypt_rebuild_info first_build;
-	if((build_on_gpu ? adypt_create_multi_from_triangles(&multi, &d, devices.data(), (int)devices.size(), &cfg.bvh, ploc ? 1 : 0, ploc_radius, split_budget, &first_build)
+	if((build_on_gpu ? adypt_create_multi_from_triangles(&multi, &d, devices.data(), (int)devices.size(), &cfg.bvh, policy.method, policy.radius, policy.split_budget, &first_build)
 	                 : adypt_create_multi(&multi, &d, devices.data(), (int)devices.size())) != ADYPT_OK)
 	{
 		fprintf(stderr, "[TRACER]Err: %s\n", adypt_multi_last_error(nullptr));
@@ -315,7 +317,6 @@ int main(int argc, char **argv)
 	if(!pose.empty())
 	{
 		adypt_pose_outcome outcome;
-		const adypt_pose_policy policy{rebuild_above, ploc ? 1 : 0, ploc_radius, split_budget};
 		const int code = have_rebuild_above ? adypt_multi_update_triangles_auto(multi, 0, n_tris, pose_positions.data(), pose_normals.data(), &cfg.bvh, &policy, &outcome)
 		                                    : adypt_multi_update_triangles(multi, 0, n_tris, pose_positions.data(), pose_normals.data());
 		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
@@ -329,7 +330,6 @@ int main(int argc, char **argv)
 	if(!part_matrices.empty())
 	{
 		adypt_pose_outcome outcome;
-		const adypt_pose_policy policy{rebuild_above, ploc ? 1 : 0, ploc_radius, split_budget};
 		int code = adypt_multi_bind_parts(multi, part_of_triangle.data(), n_tris, n_parts);
 		if(code == ADYPT_OK) code = adypt_multi_pose(multi, part_matrix.data(), n_parts, &cfg.bvh, have_rebuild_above ? &policy : nullptr, &outcome);
 		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }

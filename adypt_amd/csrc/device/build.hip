@@ -614,11 +614,12 @@ int presplit_stage(adypt_ctx *c, Builder *b, hipStream_t stream, const float4 *t
 	return ADYPT_OK;
 }
 
-// radius 0: the linear tree; otherwise PLOC with that radius, and with triangles split where budget > 0
+// The tree `q` names (build_request.hpp, its checks made): the linear one, or PLOC with q.radius, and with triangles split where q.split_budget > 0
 // Of the n_tris records at `tris`: the context's own (geometry null), or new ones that the context takes together with their tree
-int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, double budget, const char *who, adypt_rebuild_info *out, const float4 *tris, int64_t n_tris, NewGeometry *geometry = nullptr)
+int rebuild(adypt_ctx *c, const BuildRequest &q, const char *who, adypt_rebuild_info *out, const float4 *tris, int64_t n_tris, NewGeometry *geometry = nullptr)
 {
-	const bool ploc = radius != 0;
+	const bool ploc = q.method == kBuildPloc;
+	const double budget = q.split_budget;
 	const CtxScene sc = ctx_scene(c); // (of it: the layout of a record)
 	if(n_tris > ((int64_t)1 << 30)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": more than 2^30 triangles");
 	CTX_STEP(ctx_drain(c));
@@ -677,7 +678,7 @@ int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, double budget
 	if(ploc)
 	{
 		// ---- the PLOC tree with its boxes, counts and cut, round by round
-		CTX_STEP(ploc_rounds(c, b, stream, t, tris, sc.tri_float4, split ? (const float4 *)b->ref_box.get() : nullptr, cfg, radius, who));
+		CTX_STEP(ploc_rounds(c, b, stream, t, tris, sc.tri_float4, split ? (const float4 *)b->ref_box.get() : nullptr, q.cfg, q.radius, who));
 		CTX_TRY(c, b->timer.mark(3, stream));
 	}
 	else
@@ -691,7 +692,7 @@ int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, double budget
 		CTX_TRY(c, b->timer.mark(3, stream));
 		// ---- boxes, counts and the cut, bottom up
 		CTX_TRY(c, hipMemsetAsync(b->arrived.get(), 0, std::max<size_t>(n_inner, 1) * sizeof(uint32_t), stream));
-		hipLaunchKernelGGL(k_bottom_up, dim3(grid_of(n, kBuildThreads)), dim3(kBuildThreads), 0, stream, t, tris, sc.tri_float4, cfg.triangle_sah, cfg.node_sah, b->arrived.get(), b->words.get());
+		hipLaunchKernelGGL(k_bottom_up, dim3(grid_of(n, kBuildThreads)), dim3(kBuildThreads), 0, stream, t, tris, sc.tri_float4, q.cfg.triangle_sah, q.cfg.node_sah, b->arrived.get(), b->words.get());
 		CTX_TRY(c, hipGetLastError());
 	}
 	CTX_TRY(c, b->timer.mark(4, stream));
@@ -766,48 +767,34 @@ int rebuild(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, double budget
 
 }  // namespace
 
-int adypt::build_for_triangles(adypt_ctx *c, const adypt_bvh_params &cfg, int radius, double split_budget, const char *who, const float4 *triangles, NewGeometry *geometry,
-                               adypt_rebuild_info *out)
+int adypt::rebuild_own_triangles(adypt_ctx *c, const BuildRequest &q, const char *who, adypt_rebuild_info *out)
 {
-	return rebuild(c, cfg, radius, split_budget, who, out, triangles, geometry->n_tris, geometry);
+	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
+	return rebuild(c, q, who, out, (const float4 *)ctx_scene(c).triangles, ctx_scene(c).n_tris);
+}
+
+int adypt::build_for_triangles(adypt_ctx *c, const BuildRequest &q, const char *who, const float4 *triangles, NewGeometry *geometry, adypt_rebuild_info *out)
+{
+	return rebuild(c, q, who, out, triangles, geometry->n_tris, geometry);
+}
+
+// what the three entries below have in common; each applies the part of method_refused that can fail for its shape of request
+static int rebuild_entry_point(adypt_ctx *c, const BuildRequest &q, const char *who, adypt_rebuild_info *out)
+{
+	if(!c) return ADYPT_E_INVALID;
+	if(const char *why = request_refused(q)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": " + why);
+	return rebuild_own_triangles(c, q, who, out);
 }
 
 extern "C" {
 
-int adypt_rebuild_bvh(adypt_ctx *c, const adypt_bvh_params *params, adypt_rebuild_info *out)
-{
-	if(!c) return ADYPT_E_INVALID;
-	adypt_bvh_params cfg{0, 0.3f, 1.0f}; // InstanceConfig::BVH's defaults
-	if(params) cfg = *params;
-	if(!(cfg.triangle_sah > 0.0f && cfg.triangle_sah < kCutMax && cfg.node_sah > 0.0f && cfg.node_sah < kCutMax))
-		return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh: the SAH costs must be positive finite numbers");
-	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
-	return rebuild(c, cfg, 0, 0.0, "adypt_rebuild_bvh", out, (const float4 *)ctx_scene(c).triangles, ctx_scene(c).n_tris);
-}
+int adypt_rebuild_bvh(adypt_ctx *c, const adypt_bvh_params *params, adypt_rebuild_info *out) { return rebuild_entry_point(c, request_linear(params), "adypt_rebuild_bvh", out); }
 
-int adypt_rebuild_bvh_ploc(adypt_ctx *c, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out)
-{
-	if(!c) return ADYPT_E_INVALID;
-	adypt_bvh_params cfg{0, 0.3f, 1.0f};
-	if(params) cfg = *params;
-	if(!(cfg.triangle_sah > 0.0f && cfg.triangle_sah < kCutMax && cfg.node_sah > 0.0f && cfg.node_sah < kCutMax))
-		return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc: the SAH costs must be positive finite numbers");
-	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc: the radius must be in [1, 32]");
-	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
-	return rebuild(c, cfg, radius, 0.0, "adypt_rebuild_bvh_ploc", out, (const float4 *)ctx_scene(c).triangles, ctx_scene(c).n_tris);
-}
+int adypt_rebuild_bvh_ploc(adypt_ctx *c, const adypt_bvh_params *params, int radius, adypt_rebuild_info *out) { return rebuild_entry_point(c, request_ploc(params, radius), "adypt_rebuild_bvh_ploc", out); }
 
 int adypt_rebuild_bvh_ploc_split(adypt_ctx *c, const adypt_bvh_params *params, int radius, double split_budget, adypt_rebuild_info *out)
 {
-	if(!c) return ADYPT_E_INVALID;
-	adypt_bvh_params cfg{0, 0.3f, 1.0f};
-	if(params) cfg = *params;
-	if(!(cfg.triangle_sah > 0.0f && cfg.triangle_sah < kCutMax && cfg.node_sah > 0.0f && cfg.node_sah < kCutMax))
-		return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc_split: the SAH costs must be positive finite numbers");
-	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc_split: the radius must be in [1, 32]");
-	if(!(split_budget >= 0.0 && split_budget <= 1.0)) return ctx_fail(c, ADYPT_E_INVALID, "adypt_rebuild_bvh_ploc_split: the split budget must be in [0, 1]");
-	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
-	return rebuild(c, cfg, radius, split_budget, "adypt_rebuild_bvh_ploc_split", out, (const float4 *)ctx_scene(c).triangles, ctx_scene(c).n_tris);
+	return rebuild_entry_point(c, request_ploc(params, radius, split_budget), "adypt_rebuild_bvh_ploc_split", out);
 }
 
 int adypt_get_rebuild_presplit(adypt_ctx *c, int32_t out[2])

@@ -13,8 +13,6 @@
 #include "build_internal.hpp"
 #include "pose_internal.hpp"
 #include "tri_record.hpp"
-#include "wide_cut.hpp"
-#include "ploc.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
 
@@ -84,22 +82,16 @@ struct Geometry {
 };
 
 // what adypt_set_triangles refuses before it touches the device: the reason, or empty
-std::string refused(const char *who, const void *triangles, int64_t n_tris, const adypt_bvh_params *params, int method, int radius, double split_budget, adypt_bvh_params *cfg)
+std::string refused(const char *who, const void *triangles, int64_t n_tris, const BuildRequest &q)
 {
 	const std::string w = std::string(who) + ": ";
-	*cfg = adypt_bvh_params{0, 0.3f, 1.0f}; // InstanceConfig::BVH's defaults
-	if(params) *cfg = *params;
 	if(!triangles) return w + "triangles is null";
 	if(n_tris < 1 || n_tris > kMaxTriangles) return w + "the number of triangles must be in [1, 2^30]";
-	if(!(cfg->triangle_sah > 0.0f && cfg->triangle_sah < kCutMax && cfg->node_sah > 0.0f && cfg->node_sah < kCutMax)) return w + "the SAH costs must be positive finite numbers";
-	if(method != 0 && method != 1) return w + "method must be 0 (linear) or 1 (ploc)";
-	if(method == 1 && (radius < kPlocMinRadius || radius > kPlocMaxRadius)) return w + "the radius must be in [1, 32]";
-	if(!(split_budget >= 0.0 && split_budget <= 1.0)) return w + "the split budget must be in [0, 1]";
-	if(method == 0 && split_budget != 0.0) return w + "a split budget needs method 1 (ploc)";
+	if(const char *why = request_refused(q)) return w + why;
 	return std::string();
 }
 
-int set_triangles(adypt_ctx *c, const char *who, const void *triangles, int64_t n_tris, const adypt_bvh_params &cfg, int method, int radius, double split_budget, adypt_rebuild_info *out)
+int set_triangles(adypt_ctx *c, const char *who, const void *triangles, int64_t n_tris, const BuildRequest &q, adypt_rebuild_info *out)
 {
 	const CtxInfo i = ctx_info(c);
 	CTX_TRY(c, hipSetDevice(i.device));
@@ -128,7 +120,7 @@ int set_triangles(adypt_ctx *c, const char *who, const void *triangles, int64_t 
 	CTX_TRY(c, hipStreamSynchronize(i.stream));
 	if(flags & kFlagNanVertex) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": a vertex has a NaN coordinate (its triangle could never be hit, and the builders would bound it as if the vertex were not there)");
 	NewGeometry geometry{&records, &classes, n_tris};
-	CTX_STEP(build_for_triangles(c, cfg, method == 1 ? radius : 0, split_budget, who, (const float4 *)records.get(), &geometry, out));
+	CTX_STEP(build_for_triangles(c, q, who, (const float4 *)records.get(), &geometry, out));
 	g->timer.complete(); // (the build has waited for the stream)
 	pose_drop_binding(c); // (a rest pose and a binding were the old triangles': pose.hip)
 	return ADYPT_OK; // (the old records and class bytes go with `records` and `classes`)
@@ -158,10 +150,10 @@ extern "C" {
 int adypt_set_triangles(adypt_ctx *c, const void *triangles, int64_t n_tris, const adypt_bvh_params *params, int method, int radius, double split_budget, adypt_rebuild_info *out)
 {
 	if(!c) return ADYPT_E_INVALID;
-	adypt_bvh_params cfg;
-	const std::string why = refused("adypt_set_triangles", triangles, n_tris, params, method, radius, split_budget, &cfg);
+	const BuildRequest q{build_cfg(params), method, radius, split_budget};
+	const std::string why = refused("adypt_set_triangles", triangles, n_tris, q);
 	if(!why.empty()) return ctx_fail(c, ADYPT_E_INVALID, why);
-	return set_triangles(c, "adypt_set_triangles", triangles, n_tris, cfg, method, radius, split_budget, out);
+	return set_triangles(c, "adypt_set_triangles", triangles, n_tris, q, out);
 }
 
 int64_t adypt_get_triangle_count(adypt_ctx *c) { return c ? ctx_scene(c).n_tris : (int64_t)ADYPT_E_INVALID; }
@@ -191,15 +183,15 @@ int adypt_create_from_triangles(adypt_ctx **out, const adypt_scene_desc *desc, c
 	ctx_set_create_error("");
 	if(!out || !desc) { ctx_set_create_error(std::string(who) + ": null argument"); return ADYPT_E_INVALID; }
 	*out = nullptr;
-	adypt_bvh_params cfg;
+	const BuildRequest q{build_cfg(params), method, radius, split_budget};
 	std::string why = refused_description(who, desc);
-	if(why.empty()) why = refused(who, desc->triangles, desc->n_tris, params, method, radius, split_budget, &cfg);
+	if(why.empty()) why = refused(who, desc->triangles, desc->n_tris, q);
 	if(!why.empty()) { ctx_set_create_error(why); return ADYPT_E_INVALID; }
 	const Placeholder first(*desc);
 	adypt_ctx *c = nullptr;
 	const int made = adypt_create(&c, &first.desc);
 	if(made != ADYPT_OK) return made; // (the reason is adypt_create's)
-	const int r = set_triangles(c, who, desc->triangles, desc->n_tris, cfg, method, radius, split_budget, info);
+	const int r = set_triangles(c, who, desc->triangles, desc->n_tris, q, info);
 	if(r != ADYPT_OK)
 	{
 		ctx_set_create_error(adypt_last_error(c));
@@ -224,9 +216,8 @@ int adypt_create_multi_from_triangles(adypt_multi **out, const adypt_scene_desc 
 	multi_set_create_error("");
 	if(!out || !desc) { multi_set_create_error(std::string(who) + ": null argument"); return ADYPT_E_INVALID; }
 	*out = nullptr;
-	adypt_bvh_params cfg;
 	std::string why = refused_description(who, desc);
-	if(why.empty()) why = refused(who, desc->triangles, desc->n_tris, params, method, radius, split_budget, &cfg);
+	if(why.empty()) why = refused(who, desc->triangles, desc->n_tris, BuildRequest{build_cfg(params), method, radius, split_budget});
 	if(!why.empty()) { multi_set_create_error(why); return ADYPT_E_INVALID; }
 	const Placeholder first(*desc);
 	adypt_multi *m = nullptr;

@@ -240,10 +240,9 @@ int adypt_pose(adypt_ctx *c, const float *matrices, int32_t n_matrices, const ad
 		if(outcome) *outcome = adypt_pose_outcome{};
 		return ADYPT_OK;
 	}
-	adypt_bvh_params cfg;
-	const std::string why = refit_policy_refused(who, params, policy, &cfg);
-	if(!why.empty()) return ctx_fail(c, ADYPT_E_INVALID, why);
-	return refit_under_policy(c, who, cfg, *policy, outcome, [&]() { return pose_and_refit(c, b, matrices); });
+	BuildRequest request;
+	if(const char *why = refit_policy_refused(params, policy, &request)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": " + why);
+	return refit_under_policy(c, who, request, policy->rebuild_above, outcome, [&]() { return pose_and_refit(c, b, matrices); });
 }
 
 int adypt_unbind_pose(adypt_ctx *c)
@@ -279,19 +278,7 @@ int adypt_multi_bind_skin(adypt_multi *m, const uint16_t *joints, const float *w
 
 int adypt_multi_pose(adypt_multi *m, const float *matrices, int32_t n_matrices, const adypt_bvh_params *params, const adypt_pose_policy *policy, adypt_pose_outcome *outcome)
 {
-	adypt_pose_outcome head{};
-	int k = 0;
-	const int r = multi_each(m, [&](adypt_ctx *c) {
-		adypt_pose_outcome o{};
-		CTX_STEP(adypt_pose(c, matrices, n_matrices, params, policy, &o));
-		if(k++ == 0) head = o;
-		else if(o.rebuilt != head.rebuilt || o.refitted.inner_q != head.refitted.inner_q || o.refitted.leaf_q != head.refitted.leaf_q || o.now.inner_q != head.now.inner_q || o.now.leaf_q != head.now.leaf_q ||
-		        o.built.inner_q != head.built.inner_q || o.built.leaf_q != head.built.leaf_q)
-			return ctx_fail(c, ADYPT_E_HIP, "adypt_multi_pose: device " + std::to_string(k - 1) + " measured or decided otherwise than device 0: the trees differ from here on");
-		return (int)ADYPT_OK;
-	});
-	if(r == ADYPT_OK && outcome) *outcome = head;
-	return r;
+	return multi_each_outcome(m, "adypt_multi_pose", outcome, [=](adypt_ctx *c, adypt_pose_outcome *o) { return adypt_pose(c, matrices, n_matrices, params, policy, o); });
 }
 
 int adypt_multi_unbind_pose(adypt_multi *m)

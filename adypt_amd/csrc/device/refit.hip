@@ -15,7 +15,7 @@
 #include "ctx_unit.hpp"
 #include "refit_plan.hpp"
 #include "refit_internal.hpp"
-#include "ploc.hpp"
+#include "build_internal.hpp"
 #include "tree_cost.hpp"
 #include "woop.hpp"
 #include "../../../include/adypt_hip.h"
@@ -274,13 +274,6 @@ int built_cost(adypt_ctx *c, Refitter *rf, hipStream_t stream, const adypt_bvh_p
 	return ADYPT_OK;
 }
 
-bool cost_params(const adypt_bvh_params *params, adypt_bvh_params *cfg)
-{
-	*cfg = adypt_bvh_params{0, 0.3f, 1.0f}; // InstanceConfig::BVH's defaults
-	if(params) *cfg = *params;
-	return cfg->triangle_sah > 0.0f && cfg->triangle_sah < kCutMax && cfg->node_sah > 0.0f && cfg->node_sah < kCutMax; // (what the rebuilds accept)
-}
-
 }  // namespace
 
 namespace adypt {
@@ -345,21 +338,18 @@ int refit_tail(adypt_ctx *c)
 	return adypt_reset(c); // the image, the frozen blocks, the frames parked ahead and the primary-hit cache were the old pose's
 }
 
-std::string refit_policy_refused(const char *who, const adypt_bvh_params *params, const adypt_pose_policy *policy, adypt_bvh_params *cfg)
+const char *refit_policy_refused(const adypt_bvh_params *params, const adypt_pose_policy *policy, BuildRequest *request)
 {
-	const std::string w = std::string(who) + ": ";
-	if(!cost_params(params, cfg)) return w + "the SAH costs must be positive finite numbers";
 	const adypt_pose_policy p = *policy;
-	if(!(p.rebuild_above >= 0.0 && std::isfinite(p.rebuild_above))) return w + "rebuild_above must be a finite number >= 0";
-	if(p.method != 0 && p.method != 1) return w + "method must be 0 (linear) or 1 (ploc)";
-	if(p.method == 1 && (p.radius < kPlocMinRadius || p.radius > kPlocMaxRadius)) return w + "the radius must be in [1, 32]";
-	if(!(p.split_budget >= 0.0 && p.split_budget <= 1.0)) return w + "the split budget must be in [0, 1]";
-	if(p.method == 0 && p.split_budget != 0.0) return w + "a split budget needs method 1 (ploc)";
-	return std::string();
+	*request = BuildRequest{build_cfg(params), p.method, p.radius, p.split_budget};
+	if(const char *why = sah_refused(request->cfg)) return why;
+	if(!(p.rebuild_above >= 0.0 && std::isfinite(p.rebuild_above))) return "rebuild_above must be a finite number >= 0";
+	return method_refused(p.method, p.radius, p.split_budget);
 }
 
-int refit_under_policy(adypt_ctx *c, const char *who, const adypt_bvh_params &cfg, const adypt_pose_policy &p, adypt_pose_outcome *outcome, const std::function<int()> &refit)
+int refit_under_policy(adypt_ctx *c, const char *who, const BuildRequest &request, double rebuild_above, adypt_pose_outcome *outcome, const std::function<int()> &refit)
 {
+	const adypt_bvh_params &cfg = request.cfg;
 	const CtxInfo i = ctx_info(c);
 	CTX_TRY(c, hipSetDevice(i.device));
 	CTX_STEP(ctx_drain(c));
@@ -370,17 +360,32 @@ int refit_under_policy(adypt_ctx *c, const char *who, const adypt_bvh_params &cf
 	const int measured = measure_cost(c, rf, i.stream, cfg, who, &o.refitted, &o.cost_ms);
 	if(measured != ADYPT_OK) return ctx_fail(c, measured, std::string(adypt_last_error(c)) + " (the triangles have been updated and the tree refitted; nothing was rebuilt)");
 	o.now = o.refitted;
-	if(o.refitted.cost > p.rebuild_above * o.built.cost)
+	if(o.refitted.cost > rebuild_above * o.built.cost)
 	{
-		// (a rebuild that is refused or fails has left the refitted tree in place and set the error)
-		if(p.method == 0) CTX_STEP(adypt_rebuild_bvh(c, &cfg, &o.rebuild));
-		else if(p.split_budget == 0.0) CTX_STEP(adypt_rebuild_bvh_ploc(c, &cfg, p.radius, &o.rebuild));
-		else CTX_STEP(adypt_rebuild_bvh_ploc_split(c, &cfg, p.radius, p.split_budget, &o.rebuild));
+		// (a rebuild that fails has left the refitted tree in place and set the error, under the name of the public rebuild of this shape)
+		CTX_STEP(rebuild_own_triangles(c, request, rebuild_entry(request), &o.rebuild));
 		o.rebuilt = 1;
 		CTX_STEP(built_cost(c, rf, i.stream, cfg, who, &o.now)); // (the rebuild has marked it stale: the new tree's, which is the reference from here on)
 	}
 	if(outcome) *outcome = o;
 	return ADYPT_OK;
+}
+
+int multi_each_outcome(adypt_multi *m, const char *who, adypt_pose_outcome *outcome, const std::function<int(adypt_ctx *, adypt_pose_outcome *)> &f)
+{
+	adypt_pose_outcome head{};
+	int k = 0;
+	const int r = multi_each(m, [&](adypt_ctx *c) {
+		adypt_pose_outcome o{};
+		CTX_STEP(f(c, &o));
+		if(k++ == 0) head = o;
+		else if(o.rebuilt != head.rebuilt || o.refitted.inner_q != head.refitted.inner_q || o.refitted.leaf_q != head.refitted.leaf_q || o.now.inner_q != head.now.inner_q || o.now.leaf_q != head.now.leaf_q ||
+		        o.built.inner_q != head.built.inner_q || o.built.leaf_q != head.built.leaf_q)
+			return ctx_fail(c, ADYPT_E_HIP, std::string(who) + ": device " + std::to_string(k - 1) + " measured or decided otherwise than device 0: the trees differ from here on");
+		return (int)ADYPT_OK;
+	});
+	if(r == ADYPT_OK && outcome) *outcome = head;
+	return r;
 }
 
 }  // namespace adypt
@@ -415,8 +420,8 @@ int adypt_get_tree_cost(adypt_ctx *c, const adypt_bvh_params *params, adypt_tree
 {
 	if(!c) return ADYPT_E_INVALID;
 	if(!out) return ctx_fail(c, ADYPT_E_INVALID, "adypt_get_tree_cost: out is null");
-	adypt_bvh_params cfg;
-	if(!cost_params(params, &cfg)) return ctx_fail(c, ADYPT_E_INVALID, "adypt_get_tree_cost: the SAH costs must be positive finite numbers");
+	const adypt_bvh_params cfg = build_cfg(params);
+	if(const char *why = sah_refused(cfg)) return ctx_fail(c, ADYPT_E_INVALID, std::string("adypt_get_tree_cost: ") + why);
 	const CtxInfo i = ctx_info(c);
 	CTX_TRY(c, hipSetDevice(i.device));
 	CTX_STEP(ctx_drain(c));
@@ -438,10 +443,9 @@ int adypt_update_triangles_auto(adypt_ctx *c, int64_t first, int64_t count, cons
 	if(!policy) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": policy is null");
 	if(first < 0 || count < 0 || first > sc.n_tris || count > sc.n_tris - first)
 		return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": triangles [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) + ") are not all of the scene's " + std::to_string(sc.n_tris));
-	adypt_bvh_params cfg;
-	const std::string why = refit_policy_refused(who, params, policy, &cfg);
-	if(!why.empty()) return ctx_fail(c, ADYPT_E_INVALID, why);
-	return refit_under_policy(c, who, cfg, *policy, outcome, [=]() { return adypt_update_triangles(c, first, count, positions, normals); });
+	BuildRequest request;
+	if(const char *why = refit_policy_refused(params, policy, &request)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": " + why);
+	return refit_under_policy(c, who, request, policy->rebuild_above, outcome, [=]() { return adypt_update_triangles(c, first, count, positions, normals); });
 }
 
 int adypt_read_bvh(adypt_ctx *c, void *nodes_out, float *woop_out)
@@ -514,19 +518,8 @@ int adypt_multi_update_triangles_auto(adypt_multi *m, int64_t first, int64_t cou
                                       const adypt_pose_policy *policy, adypt_pose_outcome *outcome)
 {
 	// (bad arguments are refused by the first context: none has changed)
-	adypt_pose_outcome head{};
-	int k = 0;
-	const int r = multi_each(m, [&](adypt_ctx *c) {
-		adypt_pose_outcome o{};
-		CTX_STEP(adypt_update_triangles_auto(c, first, count, positions, normals, params, policy, &o));
-		if(k++ == 0) head = o;
-		else if(o.rebuilt != head.rebuilt || o.refitted.inner_q != head.refitted.inner_q || o.refitted.leaf_q != head.refitted.leaf_q || o.now.inner_q != head.now.inner_q || o.now.leaf_q != head.now.leaf_q ||
-		        o.built.inner_q != head.built.inner_q || o.built.leaf_q != head.built.leaf_q)
-			return ctx_fail(c, ADYPT_E_HIP, "adypt_multi_update_triangles_auto: device " + std::to_string(k - 1) + " measured or decided otherwise than device 0: the trees differ from here on");
-		return (int)ADYPT_OK;
-	});
-	if(r == ADYPT_OK && outcome) *outcome = head;
-	return r;
+	return multi_each_outcome(m, "adypt_multi_update_triangles_auto", outcome,
+	                          [=](adypt_ctx *c, adypt_pose_outcome *o) { return adypt_update_triangles_auto(c, first, count, positions, normals, params, policy, o); });
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // a topology plus triangles into Woop data and node records, and the hand-over of a new tree's levels to the context's refit state.  What pose.hip
 // needs of it: the refit around another writer of the records, and the refit-or-rebuild policy around that.  Not part of the C-ABI.
 #pragma once
+#include "build_request.hpp"
 #include "ctx_access.hpp"
 #include "resources.hpp"
 #include "../../../include/adypt_hip.h"
@@ -50,10 +51,12 @@ int refit_begin(adypt_ctx *c);
 // (refit_launch_levels), the root card (ctx_refresh_root_card) and the timer marks between them; the stream is waited for and the context left as
 // adypt_reset leaves it.
 int refit_tail(adypt_ctx *c);
-// What adypt_update_triangles_auto refuses of its params and policy, `cfg` being the params with their defaults filled in: the reason, or empty.
-std::string refit_policy_refused(const char *who, const adypt_bvh_params *params, const adypt_pose_policy *policy, adypt_bvh_params *cfg);
+// What adypt_update_triangles_auto refuses of its params and policy, `request` being the rebuild they name: the reason as build_request.hpp gives it, or null.
+const char *refit_policy_refused(const adypt_bvh_params *params, const adypt_pose_policy *policy, BuildRequest *request);
 // adypt_update_triangles_auto around any refit: the reference cost, `refit` (a refit_begin .. refit_tail that has checked its own arguments), the cost
-// of the refitted tree, and the policy's rebuild where that cost says so.
-int refit_under_policy(adypt_ctx *c, const char *who, const adypt_bvh_params &cfg, const adypt_pose_policy &policy, adypt_pose_outcome *outcome, const std::function<int()> &refit);
+// of the refitted tree, and the rebuild `request` names where that cost is above rebuild_above times the reference.
+int refit_under_policy(adypt_ctx *c, const char *who, const BuildRequest &request, double rebuild_above, adypt_pose_outcome *outcome, const std::function<int()> &refit);
+// multi_each of a call that gives an outcome: *outcome is the first device's, and a device that measured or decided otherwise ends the call (ADYPT_E_HIP)
+int multi_each_outcome(adypt_multi *m, const char *who, adypt_pose_outcome *outcome, const std::function<int(adypt_ctx *, adypt_pose_outcome *)> &f);
 
 }  // namespace adypt

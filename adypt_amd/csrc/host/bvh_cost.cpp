@@ -1,6 +1,7 @@
 // adypt_bvh_cost (include/adypt_host.h): the SAH cost of a CWBVH8 from its quantised child boxes, on the host.  The rule is ../device/tree_cost.hpp —
 // the text the device path (refit.hip, k_tree_cost) compiles too.
 #include "builders.hpp"
+#include "../device/build_request.hpp"
 #include "../device/tree_cost.hpp"
 #include "../../../include/adypt_hip.h"
 #include "../../../include/adypt_host.h"
@@ -10,13 +11,8 @@ using namespace adypt;
 int adypt_bvh_cost(const void *nodes_, int64_t n_nodes, const adypt_bvh_params *params, adypt_tree_cost *out)
 {
 	if(!nodes_ || !out || n_nodes <= 0) { set_host_error("adypt_bvh_cost: null or empty argument"); return ADYPT_E_INVALID; }
-	adypt_bvh_params cfg{0, 0.3f, 1.0f}; // InstanceConfig::BVH's defaults
-	if(params) cfg = *params;
-	if(!(cfg.triangle_sah > 0.0f && cfg.triangle_sah < refit_inf() && cfg.node_sah > 0.0f && cfg.node_sah < refit_inf()))
-	{
-		set_host_error("adypt_bvh_cost: the SAH costs must be positive finite numbers");
-		return ADYPT_E_INVALID;
-	}
+	const adypt_bvh_params cfg = build_cfg(params);
+	if(const char *why = sah_refused(cfg, refit_inf())) { set_host_error(std::string("adypt_bvh_cost: ") + why); return ADYPT_E_INVALID; }
 	if(n_nodes > kCostMaxNodes) { set_host_error("adypt_bvh_cost: more than 2^26 nodes"); return ADYPT_E_INVALID; }
 	const uint8_t *nodes = (const uint8_t *)nodes_;
 	uint32_t root[kNodeBytes / 4];

@@ -3,7 +3,7 @@
 #include "builders.hpp"
 #include "exact_sort.hpp"
 #include "../device/woop.hpp"
-#include "../device/ploc.hpp"
+#include "../device/build_request.hpp"
 #include "../device/presplit.hpp"
 #include "../device/root_card.hpp"
 #include "../device/tri_record.hpp"
@@ -269,21 +269,22 @@ static int collapse_unsplit(const std::vector<BinNode> &bin, int64_t leaves, con
 	return ADYPT_OK;
 }
 
-// what both unsplit builders ask of their arguments; `who` names the caller in the error
-static int unsplit_arguments(const char *who, const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, const void **tp, int64_t *nt)
+static int refuse(const char *who, const char *why) { set_host_error(std::string(who) + ": " + why); return ADYPT_E_INVALID; }
+// what the builders without an SBVH ask of their arguments (`q`: request_linear(p) or request_ploc(p, ..) of build_request.hpp); `who` names the caller in the error
+static int unsplit_arguments(const char *who, const adypt_scene *s, const adypt_bvh_params *p, const BuildRequest &q, adypt_bvh **out, const void **tp, int64_t *nt)
 {
 	if(!s || !p || !out) { set_host_error(std::string(who) + ": null argument"); return ADYPT_E_INVALID; }
 	*nt = adypt_scene_triangles(s, tp);
 	if(*nt <= 0) { set_host_error(std::string(who) + ": scene has no triangles"); return ADYPT_E_INVALID; }
 	if(*nt > ((int64_t)1 << 30)) { set_host_error(std::string(who) + ": more than 2^30 triangles"); return ADYPT_E_INVALID; }
-	if(!(p->triangle_sah > 0.0f && p->triangle_sah < FLT_MAX && p->node_sah > 0.0f && p->node_sah < FLT_MAX)) { set_host_error(std::string(who) + ": the SAH costs must be positive finite numbers"); return ADYPT_E_INVALID; }
+	if(const char *why = request_refused(q)) return refuse(who, why);
 	return ADYPT_OK;
 }
 
 int adypt_bvh_build_linear(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, adypt_build_info *info)
 {
 	const void *tp; int64_t nt;
-	const int r = unsplit_arguments("adypt_bvh_build_linear", s, p, out, &tp, &nt);
+	const int r = unsplit_arguments("adypt_bvh_build_linear", s, p, request_linear(p), out, &tp, &nt);
 	if(r != ADYPT_OK) return r;
 	std::vector<BinNode> bin;
 	double tree_ms = 0;
@@ -295,9 +296,8 @@ int adypt_bvh_build_linear(const adypt_scene *s, const adypt_bvh_params *p, adyp
 int adypt_bvh_build_ploc(const adypt_scene *s, const adypt_bvh_params *p, int radius, adypt_bvh **out, adypt_build_info *info)
 {
 	const void *tp; int64_t nt;
-	const int r = unsplit_arguments("adypt_bvh_build_ploc", s, p, out, &tp, &nt);
+	const int r = unsplit_arguments("adypt_bvh_build_ploc", s, p, request_ploc(p, radius), out, &tp, &nt);
 	if(r != ADYPT_OK) return r;
-	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) { set_host_error("adypt_bvh_build_ploc: the radius must be in [1, 32]"); return ADYPT_E_INVALID; }
 	std::vector<BinNode> bin;
 	double tree_ms = 0;
 	int depth = 0;
@@ -306,15 +306,11 @@ int adypt_bvh_build_ploc(const adypt_scene *s, const adypt_bvh_params *p, int ra
 	return collapse_unsplit(bin, leaves, *p, tp, nt, tree_ms, out, info);
 }
 
-static bool budget_ok(double b) { return b >= 0.0 && b <= 1.0; } // (false for NaN)
-
 int adypt_bvh_build_ploc_split(const adypt_scene *s, const adypt_bvh_params *p, int radius, double split_budget, adypt_bvh **out, adypt_build_info *info)
 {
 	const void *tp; int64_t nt;
-	const int r = unsplit_arguments("adypt_bvh_build_ploc_split", s, p, out, &tp, &nt);
+	const int r = unsplit_arguments("adypt_bvh_build_ploc_split", s, p, request_ploc(p, radius, split_budget), out, &tp, &nt);
 	if(r != ADYPT_OK) return r;
-	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) { set_host_error("adypt_bvh_build_ploc_split: the radius must be in [1, 32]"); return ADYPT_E_INVALID; }
-	if(!budget_ok(split_budget)) { set_host_error("adypt_bvh_build_ploc_split: the split budget must be in [0, 1]"); return ADYPT_E_INVALID; }
 	if(split_budget == 0.0) return adypt_bvh_build_ploc(s, p, radius, out, info);
 	const auto t0 = std::chrono::steady_clock::now();
 	PresplitRefs refs;
@@ -354,7 +350,7 @@ int adypt_bvh_build_ploc_split(const adypt_scene *s, const adypt_bvh_params *p, 
 int64_t adypt_presplit_refs(const void *tris, int64_t n_tris, double split_budget, int64_t capacity, int32_t *level, int32_t *ref_tri, float *ref_box)
 {
 	if(!tris || n_tris <= 0 || n_tris > ((int64_t)1 << 30) || capacity < 0 || (capacity > 0 && (!ref_tri || !ref_box))) { set_host_error("adypt_presplit_refs: null or empty argument"); return ADYPT_E_INVALID; }
-	if(!budget_ok(split_budget)) { set_host_error("adypt_presplit_refs: the split budget must be in [0, 1]"); return ADYPT_E_INVALID; }
+	if(const char *why = budget_refused(split_budget)) return refuse("adypt_presplit_refs", why);
 	PresplitRefs refs;
 	const int code = presplit_refs((const TriRec *)tris, n_tris, split_budget, &refs);
 	if(code != ADYPT_OK) return code;
@@ -377,7 +373,7 @@ int64_t adypt_bvh_ref_boxes(const adypt_bvh *b, const float **boxes)
 int adypt_ploc_tree(const void *tris, int64_t n_tris, int radius, int32_t *left, int32_t *right)
 {
 	if(!tris || n_tris <= 0 || n_tris > ((int64_t)1 << 30) || (n_tris > 1 && (!left || !right))) { set_host_error("adypt_ploc_tree: null or empty argument"); return ADYPT_E_INVALID; }
-	if(radius < kPlocMinRadius || radius > kPlocMaxRadius) { set_host_error("adypt_ploc_tree: the radius must be in [1, 32]"); return ADYPT_E_INVALID; }
+	if(const char *why = radius_refused(radius)) return refuse("adypt_ploc_tree", why);
 	std::vector<uint64_t> keys;
 	lbvh_sorted_keys((const TriRec *)tris, n_tris, &keys);
 	std::vector<int32_t> l, r;

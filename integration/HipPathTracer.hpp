@@ -223,6 +223,7 @@ public:
 	// split_budget, PLOC only, 0 .. 1: large triangles are split into several references first, at most split_budget * n more than triangles
 	// (adypt_rebuild_bvh_ploc_split) — for scenes with large triangles among small ones; 0 (the default): no splits.
 	enum class RebuildMethod { Linear, PLOC };
+	static_assert((int)RebuildMethod::Linear == 0 && (int)RebuildMethod::PLOC == 1, "a RebuildMethod is the `method` of adypt_hip.h: 0 linear, 1 ploc");
 	bool RebuildBVH(const adypt_bvh_params *params = nullptr, adypt_rebuild_info *info = nullptr, RebuildMethod method = RebuildMethod::Linear, int radius = 8, double split_budget = 0.0)
 	{
 		if(method != RebuildMethod::PLOC && split_budget != 0.0) { printf("[PT]ERR: RebuildBVH: split_budget needs RebuildMethod::PLOC\n"); return false; }
@@ -241,7 +242,7 @@ public:
 	                int lookahead_frames = 0, const adypt_bvh_params *params = nullptr, RebuildMethod method = RebuildMethod::PLOC, int radius = 8, double split_budget = 0.0,
 	                adypt_rebuild_info *info = nullptr)
 	{
-		return create(config, scene, nullptr, width, height, devices, lookahead_frames, params, method == RebuildMethod::PLOC ? 1 : 0, radius, split_budget, info);
+		return create(config, scene, nullptr, width, height, devices, lookahead_frames, params, (int)method, radius, split_budget, info);
 	}
 
 	// Other triangles, any number of them (adypt_hip.h, adypt_set_triangles): every device packs them and builds their tree on the GPU as
@@ -251,7 +252,7 @@ public:
 	                  RebuildMethod method = RebuildMethod::PLOC, int radius = 8, double split_budget = 0.0)
 	{
 		static_assert(sizeof(Triangle) == 100, "Triangle is the 100-byte record adypt_set_triangles takes");
-		if(adypt_multi_set_triangles(m_gpus, triangles.data(), (int64_t)triangles.size(), params, method == RebuildMethod::PLOC ? 1 : 0, radius, split_budget, info) == ADYPT_OK) return true;
+		if(adypt_multi_set_triangles(m_gpus, triangles.data(), (int64_t)triangles.size(), params, (int)method, radius, split_budget, info) == ADYPT_OK) return true;
 		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
 		return false;
 	}
@@ -276,11 +277,12 @@ public:
 		int radius;
 		double split_budget;
 		explicit PosePolicy(double above, RebuildMethod m = RebuildMethod::PLOC, int r = 8, double budget = 0.0) : rebuild_above(above), method(m), radius(r), split_budget(budget) {}
+		adypt_pose_policy abi() const { return adypt_pose_policy{rebuild_above, (int)method, radius, split_budget}; }
 	};
 	bool UpdateTriangles(int64_t first, int64_t count, const float *positions, const float *normals, const PosePolicy &policy, adypt_pose_outcome *outcome = nullptr,
 	                     const adypt_bvh_params *params = nullptr)
 	{
-		const adypt_pose_policy p = {policy.rebuild_above, policy.method == RebuildMethod::PLOC ? 1 : 0, policy.radius, policy.split_budget};
+		const adypt_pose_policy p = policy.abi();
 		if(adypt_multi_update_triangles_auto(m_gpus, first, count, positions, normals, params, &p, outcome) == ADYPT_OK) return true;
 		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
 		return false;
@@ -314,7 +316,7 @@ public:
 	// ... and decides about a rebuild itself, as the UpdateTriangles overload above does
 	bool Pose(const std::vector<float> &matrices, const PosePolicy &policy, adypt_pose_outcome *outcome = nullptr, const adypt_bvh_params *params = nullptr)
 	{
-		const adypt_pose_policy p = {policy.rebuild_above, policy.method == RebuildMethod::PLOC ? 1 : 0, policy.radius, policy.split_budget};
+		const adypt_pose_policy p = policy.abi();
 		if(matrices.size() % 12 == 0 && adypt_multi_pose(m_gpus, matrices.data(), (int32_t)(matrices.size() / 12), params, &p, outcome) == ADYPT_OK) return true;
 		printf("[PT]ERR: %s\n", matrices.size() % 12 ? "Pose: a matrix is 12 floats" : adypt_multi_last_error(m_gpus));
 		return false;
