@@ -86,6 +86,11 @@ class TemporalParams(C.Structure):
     _fields_ = [("history_cap", C.c_float), ("commit", C.c_int32)]
 
 
+class DenoiseMotion(Struct):
+    """adypt_denoise_motion."""
+    _fields_ = [("have_snapshot", C.c_int32), ("snapshot_ms", C.c_float), ("n_tris", C.c_int64), ("device_bytes", C.c_int64)]
+
+
 class BvhParams(C.Structure):
     _fields_ = [("max_spatial_depth", C.c_int32), ("triangle_sah", C.c_float), ("node_sah", C.c_float)]
 
@@ -202,6 +207,12 @@ _SIGS = {
     "adypt_multi_denoise_history_reset": (C.c_int, [C.c_void_p]),
     "adypt_multi_read_denoise_history": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_get_denoise_merge_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "adypt_denoise_temporal_motion": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams)]),
+    "adypt_read_denoise_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adypt_get_denoise_motion": (C.c_int, [C.c_void_p, C.POINTER(DenoiseMotion)]),
+    "adypt_multi_denoise_temporal_motion": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams)]),
+    "adypt_multi_read_denoise_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adypt_multi_get_denoise_motion": (C.c_int, [C.c_void_p, C.POINTER(DenoiseMotion)]),
     "adypt_multi_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams)]),
     "adypt_multi_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_read_denoise_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

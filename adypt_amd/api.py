@@ -647,17 +647,22 @@ class _Tracer:
 
     # ---- denoising (adypt_denoise, include/adypt_hip.h; the definition: csrc/device/denoise.hpp); several devices: of the whole image ----
     def Denoise(self, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 0.1, temporal: bool = False, history_cap: float = 64.0,
-                commit: bool = True) -> np.ndarray:
+                commit: bool = True, follow_motion: bool = False) -> np.ndarray:
         """H x W x 3 float32: the accumulated image through the variance- and primary-hit-guided a-trous filter.  Needs the noise statistics on and
         >= 2 spp in every block; the image, the statistics and the tracing state are left as they are.
         temporal (adypt_denoise_temporal; the definition: csrc/device/temporal.hpp): before the filter, what the last committing call left is
         reprojected through the primary hit and counted as up to history_cap further samples where the surface is still the same; commit: this
         call's state replaces that history (once per pose: after tracing, before the camera or the scene changes).  Give every pose a shift_seed of
-        its own (SetConfig): after a reset an unchanged camera with an unchanged seed repeats the same samples."""
+        its own (SetConfig): after a reset an unchanged camera with an unchanged seed repeats the same samples.
+        follow_motion (adypt_denoise_temporal_motion; needs temporal): a committing call also keeps every triangle's positions and normals, and a
+        later call merges a pixel on a triangle that UpdateTriangles() or Pose() has moved since through the point its hit had then — the moved
+        figure keeps its history.  Give it to every call of an animation; SetTriangles() and a committing call without it start the figure again."""
+        if follow_motion and not temporal:
+            raise ValueError("Denoise: follow_motion=True needs temporal=True")
         prm = N.DenoiseParams(levels, sigma_l, sigma_z)
         if temporal:
             tp = N.TemporalParams(history_cap, 1 if commit else 0)
-            self._call("denoise_temporal", C.byref(prm), C.byref(tp))
+            self._call("denoise_temporal_motion" if follow_motion else "denoise_temporal", C.byref(prm), C.byref(tp))
         else:
             self._call("denoise", C.byref(prm))
         rgb = np.zeros((self.height, self.width, 3), dtype=np.float32)
@@ -674,8 +679,22 @@ class _Tracer:
         self._call("read_denoise_history", n.ctypes.data)
         return n
 
+    def ReadDenoiseMotion(self) -> dict:
+        """Of the last Denoise(temporal=True, follow_motion=True): previous_position (H x W x 3 float32: where every pixel's hit point was when the
+        history was committed; the current position where nothing moved) and moved (H x W bool: the hit triangle has moved since)."""
+        p = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        moved = np.zeros((self.height, self.width), dtype=np.uint8)
+        self._call("read_denoise_motion", p.ctypes.data, moved.ctypes.data)
+        return {"previous_position": p, "moved": moved.astype(bool)}
+
+    def GetDenoiseMotion(self) -> dict:
+        """have_snapshot (0 / 1), snapshot_ms, n_tris and device_bytes of what follow_motion keeps on the (first) device."""
+        out = N.DenoiseMotion()
+        self._call("get_denoise_motion", C.byref(out))
+        return out.as_dict()
+
     def GetDenoiseMergeMs(self) -> float:
-        """HIP-event milliseconds of the merge kernel of the last Denoise(temporal=True)."""
+        """HIP-event milliseconds of the merge kernel of the last Denoise(temporal=True) (with follow_motion: of the gather kernel and the merge kernel)."""
         ms = C.c_float(0.0)
         self._call("get_denoise_merge_ms", C.byref(ms))
         return float(ms.value)

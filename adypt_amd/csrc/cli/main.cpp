@@ -5,7 +5,7 @@
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
 //             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C]
-//             [--history-out len.exr]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
+//             [--history-out len.exr] [--follow-motion]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
 //   --build gpu: no .bvh cache is read or written and no tree is built on the host: the context is created from the triangles alone
 //              (adypt_create_multi_from_triangles) and its first tree built on the GPU by --rebuild-method (ploc unless given), --ploc-radius and
 //              --split-budget, which then name that build (and, with --rebuild-above, the policy's rebuild) instead of asking for a rebuild; one
@@ -45,6 +45,10 @@
 //              --history-out len.exr: the effective sample count of every pixel after that call as a grey EXR.  One [PT]TEMPORAL: line reports how many
 //              hit pixels found history.  --history-cap or --history-out without --history-from make the --denoise call a temporal one too: it finds no
 //              history, so the file holds the plain filter's bits, every length is the block's own sample count and the line reports 0 pixels
+//   --follow-motion: with a temporal --denoise call only (one of the --history options; else exit 2): every temporal call is a motion call
+//              (adypt_multi_denoise_temporal_motion), and the --history-from poses are rendered and committed BEFORE --pose / --part-matrices (and the rebuild
+//              that goes with them) is applied — they show the scene as loaded, the main render the moved one, and pixels on moved triangles find
+//              their history through the pose they had.  The [PT]TEMPORAL: line then ends `, moved M pixels`.  Without it the pose comes first
 //   --guides-out PREFIX: the feature images of the primary hit as PREFIX.albedo.exr, PREFIX.normal.exr and PREFIX.position.exr
 #include "adypt_hip.h"
 #include "adypt_host.h"
@@ -65,7 +69,7 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C] [--history-out len.exr]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C] [--history-out len.exr] [--follow-motion]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
 	std::string noise_out, spp_out, denoise_out, guides_out, pose, part_matrices;
@@ -79,7 +83,7 @@ int main(int argc, char **argv)
 	std::vector<std::string> history_from;
 	std::string history_out;
 	double history_cap = 64.0;
-	bool have_history_cap = false;
+	bool have_history_cap = false, follow_motion = false;
 	int adaptive = 0;
 	int spp = 64, fp16 = 0, primary = -1, sun_visibility = 0, save_every = 0;
 	std::vector<int> devices(1, 0);
@@ -129,6 +133,7 @@ int main(int argc, char **argv)
 			if(end == argv[i] || *end || !(history_cap > 0.0 && history_cap <= 3.0e38)) { fprintf(stderr, "--history-cap takes a positive finite number, not %s\n", argv[i]); return 2; }
 			have_history_cap = true;
 		}
+		else if(a == "--follow-motion") follow_motion = true;
 		else if(a == "--guides-out" && i + 1 < argc) guides_out = argv[++i];
 		else if(a == "--pose" && i + 1 < argc) pose = argv[++i];
 		else if(a == "--part-matrices" && i + 1 < argc) part_matrices = argv[++i];
@@ -172,6 +177,7 @@ int main(int argc, char **argv)
 	if(denoise && (denoise_levels < 1 || denoise_levels > 6)) { fprintf(stderr, "--denoise-levels must be in 1 .. 6\n"); return 2; }
 	const bool temporal = !history_from.empty() || have_history_cap || !history_out.empty();
 	if(temporal && !denoise) { fprintf(stderr, "--history-from, --history-cap and --history-out need --denoise file.exr\n"); return 2; }
+	if(follow_motion && !temporal) { fprintf(stderr, "--follow-motion needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out\n"); return 2; }
 	if(until) min_spp = std::max(2, std::min(min_spp, spp));
 	adypt_config cfg;
 	adypt_config_default(&cfg);
@@ -314,12 +320,14 @@ int main(int argc, char **argv)
 		return std::string(text);
 	};
 	if(build_on_gpu) printf("[PT]BUILD: %s\n", rebuild_figures(first_build).c_str());
+	// --pose / --part-matrices and the rebuild that goes with them: before the history poses, or with --follow-motion after them
+	auto move_scene = [&]() -> bool {
 	if(!pose.empty())
 	{
 		adypt_pose_outcome outcome;
 		const int code = have_rebuild_above ? adypt_multi_update_triangles_auto(multi, 0, n_tris, pose_positions.data(), pose_normals.data(), &cfg.bvh, &policy, &outcome)
 		                                    : adypt_multi_update_triangles(multi, 0, n_tris, pose_positions.data(), pose_normals.data());
-		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return false; }
 		float ms[4] = {0, 0, 0, 0};
 		(void)adypt_get_refit_timing(adypt_multi_context(multi, 0), ms, 4);
 		printf("[PT]INFO: pose %s: %lld triangles moved, refit %.3f ms (scatter %.3f, references and Woop %.3f, nodes %.3f)\n", pose.c_str(), (long long)n_tris, ms[3], ms[0], ms[1], ms[2]);
@@ -332,7 +340,7 @@ int main(int argc, char **argv)
 		adypt_pose_outcome outcome;
 		int code = adypt_multi_bind_parts(multi, part_of_triangle.data(), n_tris, n_parts);
 		if(code == ADYPT_OK) code = adypt_multi_pose(multi, part_matrix.data(), n_parts, &cfg.bvh, have_rebuild_above ? &policy : nullptr, &outcome);
-		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return false; }
 		float ms[4] = {0, 0, 0, 0};
 		(void)adypt_get_refit_timing(adypt_multi_context(multi, 0), ms, 4);
 		printf("[PT]POSE: parts %d triangles %lld from %s, refit %.3f ms (matrices and pose %.3f, references and Woop %.3f, nodes %.3f)\n", (int)n_parts, (long long)n_tris, part_matrices.c_str(), ms[3],
@@ -347,9 +355,12 @@ int main(int argc, char **argv)
 		const int code = have_split_budget ? adypt_multi_rebuild_bvh_ploc_split(multi, &cfg.bvh, ploc_radius, split_budget, &info)
 		                 : ploc            ? adypt_multi_rebuild_bvh_ploc(multi, &cfg.bvh, ploc_radius, &info)
 		                                   : adypt_multi_rebuild_bvh(multi, &cfg.bvh, &info);
-		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return false; }
 		printf("[PT]INFO: rebuild: %s\n", rebuild_figures(info).c_str());
 	}
+	return true;
+	};
+	if(!follow_motion && !move_scene()) return 1;
 
 	std::vector<float> rgb((size_t)cfg.width * cfg.height * 3, 0.0f);
 	std::vector<uint8_t> rgba8;
@@ -383,9 +394,11 @@ int main(int argc, char **argv)
 		if(r == ADYPT_OK) r = adypt_multi_set_params(multi, &p);
 		if(r == ADYPT_OK) r = adypt_multi_set_camera(multi, h.position, hp, hv);
 		if(r == ADYPT_OK) r = adypt_multi_trace_spp(multi, spp);
-		if(r == ADYPT_OK) r = adypt_multi_denoise_temporal(multi, &dp, &tp);
+		if(r == ADYPT_OK) r = follow_motion ? adypt_multi_denoise_temporal_motion(multi, &dp, &tp) : adypt_multi_denoise_temporal(multi, &dp, &tp);
 		if(r == ADYPT_OK) printf("[PT]INFO: history pose %s: %d spp committed\n", history_from[k].c_str(), spp);
 	}
+	if(r != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+	if(follow_motion && !move_scene()) return 1; // (the history holds the scene as loaded, with its snapshot; a pose leaves the tracer at 0 spp)
 	if(!history_cfg.empty() && r == ADYPT_OK)
 	{
 		p.shift_seed = seed;
@@ -496,7 +509,7 @@ int main(int argc, char **argv)
 	if(denoise)
 	{
 		std::vector<float> den((size_t)cfg.width * cfg.height * 3, 0.0f);
-		if((temporal ? adypt_multi_denoise_temporal(multi, &dp, &tp) : adypt_multi_denoise(multi, &dp)) != ADYPT_OK || adypt_multi_read_denoised(multi, den.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		if((follow_motion ? adypt_multi_denoise_temporal_motion(multi, &dp, &tp) : temporal ? adypt_multi_denoise_temporal(multi, &dp, &tp) : adypt_multi_denoise(multi, &dp)) != ADYPT_OK || adypt_multi_read_denoised(multi, den.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
 		if(adypt_save_exr(denoise_out.c_str(), den.data(), cfg.width, cfg.height, fp16) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
 		printf("[PT]INFO: Saved denoised image (%d levels) to %s\n", denoise_levels, denoise_out.c_str());
 		if(temporal)
@@ -510,7 +523,14 @@ int main(int argc, char **argv)
 			double sum = 0.0;
 			for(size_t i = 0; i < length.size(); ++i)
 				if(hit[i]) { ++hits; sum += length[i]; if(length[i] > count_of[i]) ++with_history; }
-			printf("[PT]TEMPORAL: history on %lld of %lld hit pixels, mean length %.3f\n", with_history, hits, hits ? sum / (double)hits : 0.0);
+			printf("[PT]TEMPORAL: history on %lld of %lld hit pixels, mean length %.3f", with_history, hits, hits ? sum / (double)hits : 0.0);
+			if(follow_motion)
+			{
+				std::vector<uint8_t> moved(length.size(), 0);
+				if(adypt_multi_read_denoise_motion(multi, nullptr, moved.data()) != ADYPT_OK) { fprintf(stderr, "\n[TRACER]Err: %s\n", err()); return 1; }
+				printf(", moved %lld pixels", (long long)std::count(moved.begin(), moved.end(), (uint8_t)1));
+			}
+			printf("\n");
 			if(!history_out.empty())
 			{
 				std::vector<float> grey(length.size() * 3);

@@ -3,7 +3,8 @@
 // THE definition for host and device (no HIP needed: tests/test_temporal_definition.py compiles it on the host with -ffp-contract=off).  Canonical
 // arithmetic as in denoise.hpp: binary32, round to nearest, the operations in the order written, NO fma, no exp / pow — only + - * / sqrtf floorf
 // fabsf, comparisons and selects — so that the numpy float32 restatement (tests/temporal_truth.py) is bit-exact.  Every comparison is written so that
-// a NaN yields "no history", and every float is range-tested before it is converted to int.
+// a NaN yields "no history", and every float is range-tested before it is converted to int.  (Following moved geometry, at the end, also compares words
+// as bits: tests/temporal_motion_truth.py restates that part.)
 //
 // The history, row-major float4 images at the picture's coordinates of the call that committed it, and that call's camera:
 //     H0 = (D.rgb, V)   the merged PRE-filter state (not the filtered result: no blur accumulates over calls)
@@ -12,6 +13,8 @@
 // the first temporal call.  A commit swaps buffers with the current call's images, nothing is copied.
 #pragma once
 #include "denoise.hpp"
+#include <cstdint>
+#include <cstring>
 
 namespace adypt {
 
@@ -69,18 +72,18 @@ ADYPT_HOST_DEVICE bool temporal_reproject(const TemporalCamera &cam, int width, 
 // What the merge leaves at a pixel: the merged (D.rgb, V) and the effective sample count n_out.
 struct TemporalOut { Dn4 x0; float n; };
 
-// The merge at pixel (px, py).  c0 = (D0.rgb, V0) of denoise_prepare, c1 = (N.xyz, hit), c2 = (P.xyz, .), ca = (A.rgb, .) of the current call, n the
-// sample count of the pixel's block.  `hist` answers h0(i), h1(i), h2(i), ha(i) for the row-major pixel index i of the history; have = false: there
-// is none.  A tap that does not count is skipped entirely (an accumulator keeps its word).
+// The body of both forms of the merge: the pixel's surface as the HISTORY holds it — its normal (nx, ny, nz) and its point (px, py, pz) at the time of the
+// last commit — is what is reprojected and what a tap's normal and plane are held against.  temporal_merge gives the current normal and point (the
+// surface stands still), temporal_merge_motion what temporal_previous_point made of the hit triangle as it was then.
 template <class Hist>
-ADYPT_HOST_DEVICE TemporalOut temporal_merge(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, const Dn4 &c1, const Dn4 &c2, const Dn4 &ca,
-                                             float n, float history_cap)
+ADYPT_HOST_DEVICE TemporalOut temporal_merge_through(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, bool hit, float nx, float ny, float nz,
+                                                     float px, float py, float pz, const Dn4 &ca, float n, float history_cap)
 {
 	TemporalOut out;
 	out.x0 = c0; out.n = n;
-	if(!have || !(c1.w != 0.0f)) return out;
+	if(!have || !hit) return out;
 	float fx, fy, dist;
-	if(!temporal_reproject(cam, width, height, c2.x, c2.y, c2.z, &fx, &fy, &dist)) return out;
+	if(!temporal_reproject(cam, width, height, px, py, pz, &fx, &fy, &dist)) return out;
 	// floorf(fx) in [-1, width - 1]: one of the two columns at least lies inside (and a NaN is refused)
 	if(!(fx >= -1.0f && fx < (float)width && fy >= -1.0f && fy < (float)height)) return out;
 	const float bx = floorf(fx), by = floorf(fy);
@@ -96,10 +99,10 @@ ADYPT_HOST_DEVICE TemporalOut temporal_merge(const Hist &hist, bool have, const 
 			const int q = qy * width + qx;
 			const Dn4 q1 = hist.h1(q);
 			if(!(q1.w != 0.0f)) continue;
-			if(!((c1.x * q1.x + c1.y * q1.y) + c1.z * q1.z >= kTemporalNormalMin)) continue;
+			if(!((nx * q1.x + ny * q1.y) + nz * q1.z >= kTemporalNormalMin)) continue;
 			const Dn4 q2 = hist.h2(q);
-			const float dx = q2.x - c2.x, dy = q2.y - c2.y, dz = q2.z - c2.z;
-			if(!(fabsf((c1.x * dx + c1.y * dy) + c1.z * dz) <= tol)) continue;
+			const float dx = q2.x - px, dy = q2.y - py, dz = q2.z - pz;
+			if(!(fabsf((nx * dx + ny * dy) + nz * dz) <= tol)) continue;
 			const Dn4 qa = hist.ha(q);
 			if(!(fabsf(qa.x - ca.x) <= kTemporalAlbedoTol && fabsf(qa.y - ca.y) <= kTemporalAlbedoTol && fabsf(qa.z - ca.z) <= kTemporalAlbedoTol)) continue;
 			const Dn4 q0 = hist.h0(q);
@@ -120,6 +123,66 @@ ADYPT_HOST_DEVICE TemporalOut temporal_merge(const Hist &hist, bool have, const 
 	out.x0.w = ((n * n) * c0.w + (nh * nh) * hv) / (den * den);
 	out.n = den;
 	return out;
+}
+
+// The merge at pixel (px, py).  c0 = (D0.rgb, V0) of denoise_prepare, c1 = (N.xyz, hit), c2 = (P.xyz, .), ca = (A.rgb, .) of the current call, n the
+// sample count of the pixel's block.  `hist` answers h0(i), h1(i), h2(i), ha(i) for the row-major pixel index i of the history; have = false: there
+// is none.  A tap that does not count is skipped entirely (an accumulator keeps its word).
+template <class Hist>
+ADYPT_HOST_DEVICE TemporalOut temporal_merge(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, const Dn4 &c1, const Dn4 &c2, const Dn4 &ca,
+                                             float n, float history_cap)
+{
+	return temporal_merge_through(hist, have, cam, width, height, c0, c1.w != 0.0f, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z, ca, n, history_cap);
+}
+
+// ---- following moved geometry ----
+// The other half of SVGF's reprojection.  A committing motion call keeps words 0..17 of every triangle record (p0 p1 p2 n0 n1 n2) beside the history;
+// a later call asks where the point it hit on a triangle WAS then, and merges through that point and that normal.  A triangle keeps its index across
+// adypt_update_triangles, adypt_pose and adypt_rebuild_bvh, which is all the correspondence there is.
+constexpr int kTemporalTriWords = 18;
+
+// where the pixel's surface was when the history was committed: xp = (P_prev.xyz, moved ? 1 : 0), xn = (N_prev.xyz, valid ? 1 : 0)
+struct TemporalPrevious { Dn4 xp, xn; };
+
+ADYPT_HOST_DEVICE bool temporal_same_word(float a, float b)
+{
+	uint32_t x, y;
+	memcpy(&x, &a, 4); memcpy(&y, &b, 4);
+	return x == y;
+}
+
+// prev, cur: words 0..17 of the hit triangle's record then and now, looked at only when `known` — the pixel hit a triangle whose index lies inside the
+// snapshot; (u, v) of the hit; c1, c2 of the current call.  Unmoved (not known: sky, a stranger; or all 18 words equal as bits): the current normal and
+// point, so that the merge is temporal_merge to the bit.  Moved: the hit's barycentric combination of the previous vertices, weighted as viewer_color
+// weighs them (p0 by u, p1 by v, p2 by w), and of the previous normals, normalised; not valid — no history — when the squared length of that normal
+// is not a positive finite number.
+ADYPT_HOST_DEVICE TemporalPrevious temporal_previous_point(const float *prev, const float *cur, bool known, float u, float v, const Dn4 &c1, const Dn4 &c2)
+{
+	TemporalPrevious r;
+	r.xp = Dn4{c2.x, c2.y, c2.z, 0.0f};
+	r.xn = Dn4{c1.x, c1.y, c1.z, 1.0f};
+	if(!known) return r;
+	bool same = true;
+	for(int k = 0; k < kTemporalTriWords; ++k) same = same && temporal_same_word(prev[k], cur[k]);
+	if(same) return r;
+	const float w = (1.0f - u) - v;
+	const float px = (prev[0] * u + prev[3] * v) + prev[6] * w, py = (prev[1] * u + prev[4] * v) + prev[7] * w, pz = (prev[2] * u + prev[5] * v) + prev[8] * w;
+	const float nx = (prev[9] * u + prev[12] * v) + prev[15] * w, ny = (prev[10] * u + prev[13] * v) + prev[16] * w, nz = (prev[11] * u + prev[14] * v) + prev[17] * w;
+	const float len2 = (nx * nx + ny * ny) + nz * nz;
+	r.xp = Dn4{px, py, pz, 1.0f};
+	if(!(len2 > 0.0f && len2 <= kTemporalFiniteMax)) { r.xn = Dn4{0.0f, 0.0f, 0.0f, 0.0f}; return r; }
+	const float len = sqrtf(len2);
+	r.xn = Dn4{nx / len, ny / len, nz / len, 1.0f};
+	return r;
+}
+
+// The motion form of the merge: through (P_prev, N_prev).  The call's own (D0, V0), and the X1 / X2 that become history on a commit, stay the current
+// pose's; the albedo test, the finiteness tests, the weights, the cap and the blend are temporal_merge's.
+template <class Hist>
+ADYPT_HOST_DEVICE TemporalOut temporal_merge_motion(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, const Dn4 &c1, const Dn4 &ca, float n,
+                                                    float history_cap, const Dn4 &xp, const Dn4 &xn)
+{
+	return temporal_merge_through(hist, have && xn.w != 0.0f, cam, width, height, c0, c1.w != 0.0f, xn.x, xn.y, xn.z, xp.x, xp.y, xp.z, ca, n, history_cap);
 }
 
 }  // namespace adypt

@@ -300,7 +300,8 @@ int adypt_get_denoise_timing(adypt_ctx *ctx, float *ms, int capacity);
  * further samples where the surface is still the same: a history tap counts when it lies inside the image, was a hit, its normal, its plane and its
  * albedo agree with the pixel's (0.9, 0.02 of the distance, 0.1), and what it holds is finite and its sample count positive.  The definition is pinned bit for bit in
  * csrc/device/temporal.hpp; tests/temporal_truth.py restates it in numpy.  A surface that moved fails the plane test and starts again from its own
- * samples, so adypt_update_triangles, adypt_rebuild_bvh and adypt_set_triangles leave the history alone.  Sky pixels take no history.
+ * samples (unless the calls are motion calls: following moved geometry, below), so adypt_update_triangles, adypt_rebuild_bvh and adypt_set_triangles
+ * leave the history alone.  Sky pixels take no history.
  * Poses should differ in shift_seed (adypt_set_params): a reset restarts the sample sequence, so an unchanged camera with an unchanged seed
  * repeats the very same samples, and the history would count them twice.
  * Memory, allocated at the first temporal call and given back by adypt_destroy: 84 B per image pixel on top of the denoiser's (four float4 history
@@ -322,6 +323,36 @@ int adypt_read_denoise_history(adypt_ctx *ctx, float *length);
 /* HIP-event time of the merge kernel of the last filter in ms; ADYPT_E_STATE when that was not a temporal call.  adypt_get_denoise_timing keeps its
  * layout: the merge's time is in none of its entries */
 int adypt_get_denoise_merge_ms(adypt_ctx *ctx, float *ms);
+
+/* ---- following moved geometry: the history reaches a surface that moved through its last pose ---------------------------------------------------
+ * adypt_denoise_temporal reprojects the CURRENT position of the primary hit, so a surface that moved finds another plane in the history and starts
+ * again.  The motion call is the other half of SVGF's reprojection: a committing motion call keeps, beside the history, the first 80 bytes of every
+ * triangle record as they are then (the snapshot); a later motion call takes every pixel's primary hit (triangle index, u, v), and where that
+ * triangle's positions or normals differ from the snapshot's in any bit, merges through the point P_prev = (p0 u + p1 v) + p2 w and the normalised
+ * normal N_prev the hit HAD then — reprojection, normal test and plane test are of (P_prev, N_prev), everything else is adypt_denoise_temporal's, and
+ * what becomes history is the current pose's.  A triangle keeps its index across adypt_update_triangles, adypt_pose and adypt_rebuild_bvh: that is
+ * the correspondence.  Pixels on triangles that did not move, sky, and indices the snapshot does not hold are adypt_denoise_temporal's to the bit; so is
+ * the whole call when there is no snapshot.  A previous normal of no positive finite length takes no history.  The definition:
+ * csrc/device/temporal.hpp (temporal_previous_point, temporal_merge_motion); tests/temporal_motion_truth.py restates it in numpy.
+ * The snapshot belongs to the history: written only by a committing motion call; dropped by adypt_denoise_history_reset, by a committing
+ * adypt_denoise_temporal (the geometry of the history is then unknown) and by adypt_set_triangles (an index means another triangle); kept across
+ * adypt_update_triangles, adypt_pose, adypt_rebuild_bvh and calls with commit = 0.
+ * Not covered: shading that changes because a NEIGHBOUR moved (a shadow, a reflection) — the history keeps what it had, history_cap is the lever.
+ * Memory: 80 B per triangle (at the first committing motion call) + 32 B per image pixel (at the first motion call).  Several devices: on the first. */
+typedef struct adypt_denoise_motion {
+	int32_t have_snapshot;       /* 1: the history has a snapshot */
+	float snapshot_ms;           /* HIP-event time of the copy kernel that wrote it; 0 without one */
+	int64_t n_tris;              /* triangles in it; 0 without one */
+	int64_t device_bytes;        /* the snapshot and the two motion images as allocated */
+} adypt_denoise_motion;
+/* adypt_denoise_temporal with the merge through the previous pose; same arguments, same refusals.  adypt_get_denoise_merge_ms covers the gather
+ * kernel and the merge kernel of such a call. */
+int adypt_denoise_temporal_motion(adypt_ctx *ctx, const adypt_denoise_params *params, const adypt_temporal_params *temporal);
+/* of the last motion call: prev_position W*H*3 floats — where every pixel's hit point was when the history was committed (the current position
+ * where nothing moved) — and moved W*H bytes (1: the hit triangle's words differ from the snapshot's).  Either may be NULL.  ADYPT_E_STATE before
+ * the first motion call */
+int adypt_read_denoise_motion(adypt_ctx *ctx, float *prev_position, uint8_t *moved);
+int adypt_get_denoise_motion(adypt_ctx *ctx, adypt_denoise_motion *out);
 
 /* ---- moving geometry: new vertex positions without a new BVH and a new context ----------------------------------------------------------------
  * The tree's topology stays valid when vertices move; what goes stale are the boxes, the Woop data and the triangle records.  adypt_update_triangles
@@ -623,6 +654,11 @@ int adypt_multi_denoise_temporal(adypt_multi *m, const adypt_denoise_params *par
 int adypt_multi_denoise_history_reset(adypt_multi *m);
 int adypt_multi_read_denoise_history(adypt_multi *m, float *length);
 int adypt_multi_get_denoise_merge_ms(adypt_multi *m, float *ms);
+/* adypt_denoise_temporal_motion ... for the whole image: snapshot, gather and merge on the first device, which holds every triangle and receives every
+ * device's primary hits; the one-device result bit for bit */
+int adypt_multi_denoise_temporal_motion(adypt_multi *m, const adypt_denoise_params *params, const adypt_temporal_params *temporal);
+int adypt_multi_read_denoise_motion(adypt_multi *m, float *prev_position, uint8_t *moved);
+int adypt_multi_get_denoise_motion(adypt_multi *m, adypt_denoise_motion *out);
 /* adypt_update_triangles on every device: the scene is replicated and every device refits its own copy; no collective.  (One process per GPU: every
  * rank calls adypt_update_triangles on its own context.) */
 int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals);

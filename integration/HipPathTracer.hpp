@@ -323,6 +323,21 @@ public:
 	}
 	bool UnbindPose() { return adypt_multi_unbind_pose(m_gpus) == ADYPT_OK; }
 
+	// The image through the denoiser with its history across poses (adypt_hip.h, adypt_denoise_temporal): W x H x 3 floats into *rgb.  Needs
+	// SetNoiseStats(true) and GetSPP() >= 2.  commit: this call's state becomes the history (once per pose: after tracing, before the camera or the
+	// scene changes).  followMotion (adypt_denoise_temporal_motion): a committing call also keeps every triangle's positions and normals, and a later
+	// call merges a pixel on a triangle that UpdateTriangles or Pose has moved since through the point its hit had then — give it to every call of an
+	// animation; SetTriangles and a committing call without it start the moved figure again.  params: levels and sigmas (nullptr: the defaults).
+	bool DenoiseTemporal(std::vector<float> *rgb, float historyCap = 64.0f, bool commit = true, bool followMotion = false, const adypt_denoise_params *params = nullptr)
+	{
+		const adypt_temporal_params t = {historyCap, commit ? 1 : 0};
+		rgb->resize((size_t)m_width * m_height * 3);
+		if((followMotion ? adypt_multi_denoise_temporal_motion(m_gpus, params, &t) : adypt_multi_denoise_temporal(m_gpus, params, &t)) == ADYPT_OK &&
+		   adypt_multi_read_denoised(m_gpus, rgb->data()) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
 	// what DrawScreen puts on screen, for a caller-owned W x H RGBA8 texture / window (every device fills in its own tiles)
 	bool ReadScreen(std::vector<uint8_t> *rgba8) const
 	{
