@@ -16,6 +16,14 @@
 // block lists likewise (every block has one owner, and k_denoise_prepare takes any block list and writes at the picture's coordinates), uploads them
 // to the first device and runs the same kernels there (the merge too: the history lives on the first device) — no collective; the result is the
 // one-device result bit for bit because the inputs are.
+// The host side, in the order of the file:
+//     BlockImages   the block-major images of a set of blocks on one device, named once (BlockImage) and handled in loops: the context's own set
+//                   and, on the first device of several, the merged set of all devices.  LocalImages is the view of a set the kernels are launched with
+//     History       what the last committing call left, its camera and its snapshot.  Its methods are the lifetime rule and its only writers
+//     Denoiser      everything kept per context.  While timer.completed(), `last` says what the last finished run was (LastRun; StageMarks knows where
+//                   the marks of a run of a mode stand), and rgb is its result
+//     DenoiseCall   one call, made once from the ABI structs (make_call): mode, parameters with their defaults, and the refusal if there is one
+//     run_filter    prepare (+ gather + merge) + levels (+ snapshot) of a call over a set of images; denoise_context and multi_denoise are the two fronts
 #include "ctx_unit.hpp"
 #include "tile_layout.hpp"
 #include "denoise.hpp"
@@ -162,268 +170,293 @@ __global__ __launch_bounds__(256) void k_motion_gather(const float4 *__restrict_
 	xn[p] = make_float4(r.xn.x, r.xn.y, r.xn.z, r.xn.w);
 }
 
-// the block-major images of a set of blocks on one device: a context's own (accum and moments are then the context's) or the merged ones of all devices
+// The block-major images of a set of blocks on one device, in the order the several-device path uploads them: the first kPixelImages hold one element
+// per local pixel, the last two one per block.  A further image is one more name here, its element type where that is not float4, its size in the table
+// and, if it is per pixel, its place in kFetchOrder.
+enum BlockImage { kAccum, kAlbedo, kNormal, kPosition, kHits, kMoments, kBlocks, kBlockSpp, kBlockImages, kPixelImages = kBlocks };
+template <BlockImage K> struct ImageElement { using type = float4; };
+template <> struct ImageElement<kMoments> { using type = float2; };
+template <> struct ImageElement<kBlocks> { using type = int32_t; };
+template <> struct ImageElement<kBlockSpp> { using type = int32_t; };
+template <BlockImage K> constexpr size_t block_bytes() { return sizeof(typename ImageElement<K>::type) * (K < kPixelImages ? kBlockPixels : 1); }
+constexpr size_t kBlockImageBytes[] = {block_bytes<kAccum>(), block_bytes<kAlbedo>(), block_bytes<kNormal>(), block_bytes<kPosition>(),
+                                       block_bytes<kHits>(), block_bytes<kMoments>(), block_bytes<kBlocks>(), block_bytes<kBlockSpp>()}; // of one block
+static_assert(sizeof(kBlockImageBytes) / sizeof(size_t) == kBlockImages, "every block-major image has its size");
+// the order in which the several-device path fetches a device's per-pixel images (the uploads go in the enum's order)
+constexpr BlockImage kFetchOrder[] = {kMoments, kAccum, kAlbedo, kNormal, kPosition, kHits};
+static_assert(sizeof(kFetchOrder) / sizeof(BlockImage) == kPixelImages, "every per-pixel image is fetched");
+constexpr unsigned kContextImages = 1u << kAccum | 1u << kMoments | 1u << kBlocks; // the images a context keeps itself (DenoiseInputs)
+
+// where the images of a set of n_blocks blocks lie: what the kernels are launched with
 struct LocalImages {
-	const float4 *accum; const float2 *moments; const int32_t *blocks, *block_spp;
-	const float4 *albedo, *normal, *position, *hits;
+	const void *image[kBlockImages];
 	int n_blocks;
+	template <BlockImage K> const typename ImageElement<K>::type *as() const { return (const typename ImageElement<K>::type *)image[K]; }
 };
+
+// The buffers of a set, grow-only.  The context's own set borrows the kContextImages from the context (64 B per local pixel + 4 B per owned block remain:
+// the guides and the sample counts); the merged set of all devices, on the first device, owns every image (88 B per pixel + 8 B per block).
+struct BlockImages {
+	Buffer<uint8_t> image[kBlockImages];
+	template <BlockImage K> typename ImageElement<K>::type *as() const { return (typename ImageElement<K>::type *)image[K].get(); }
+	// room for v->n_blocks blocks in every image but the `borrowed` ones (a mask of 1 << BlockImage), which stay what the caller made them, null included
+	int fill(adypt_ctx *c, LocalImages *v, unsigned borrowed)
+	{
+		for(int k = 0; k < kBlockImages; ++k)
+			if(!(borrowed >> k & 1))
+			{
+				CTX_TRY(c, at_least(image[k], (size_t)v->n_blocks * kBlockImageBytes[k]));
+				v->image[k] = image[k].get();
+			}
+		return ADYPT_OK;
+	}
+};
+
+// The history of the temporal merge: what the last committing call left — its merged image, its X1, X2 with n_out in .w, XA (64 B per image pixel,
+// allocated at the first temporal call) and its camera — and the snapshot, which belongs to it: the first 80 bytes of every triangle record as a
+// committing motion call found them, allocated at the first such call.  The methods are the lifetime rule, and nothing else writes a member: the
+// snapshot is written only by a committing motion call; dropped by reset, by a committing call without motion (the history's geometry is then unknown)
+// and by adypt_set_triangles (the indices mean other triangles).
+struct History {
+	Buffer<float4> h0, h1, h2, ha;
+	TemporalCamera camera;
+	bool present = false;
+	Buffer<float4> snapshot;
+	int64_t snapshot_tris = 0;       // the triangles the snapshot holds; 0: the history has none (a context's scene never has 0: adypt_create, adypt_set_triangles)
+	StageTimer<2> snapshot_timer;    // the copy kernel of the last commit with a snapshot
+
+	int ensure(adypt_ctx *c, size_t n_px)
+	{
+		CTX_TRY(c, at_least(h0, n_px)); CTX_TRY(c, at_least(h1, n_px)); CTX_TRY(c, at_least(h2, n_px)); CTX_TRY(c, at_least(ha, n_px));
+		return ADYPT_OK;
+	}
+	// how many triangles of the snapshot the gather may trust for a scene of n_tris triangles (a snapshot of another count is none: adypt_set_triangles
+	// drops it, so this only guards)
+	int64_t known_tris(int64_t n_tris) const { return present && snapshot_tris == n_tris ? snapshot_tris : 0; }
+	// The snapshot of a committing motion call: the records as they are now, enqueued on `stream` behind the call's gather, which reads the old one.  The
+	// history has none from here until the caller has waited for the stream and commits with *n_tris: a failure in between leaves every pixel unmoved.
+	int enqueue_snapshot(adypt_ctx *c, hipStream_t stream, int64_t *n_tris)
+	{
+		const CtxScene sc = ctx_scene(c);
+		snapshot_tris = 0;
+		CTX_TRY(c, at_least(snapshot, (size_t)(sc.n_tris * kSnapshotVecs)));
+		CTX_TRY(c, snapshot_timer.mark(0, stream));
+		hipLaunchKernelGGL(k_motion_snapshot, dim3(grid_of(sc.n_tris, kSnapshotGroup)), dim3(kSnapshotGroup * kSnapshotVecs), 0, stream, (const float4 *)sc.triangles, sc.tri_float4, sc.n_tris,
+		                   snapshot.get());
+		CTX_TRY(c, hipGetLastError());
+		CTX_TRY(c, snapshot_timer.mark(1, stream));
+		*n_tris = sc.n_tris;
+		return ADYPT_OK;
+	}
+	// A finished call's merged image, guides (X2.w = n_out) and camera become the history: swapped in, nothing is copied, and what the history held is
+	// overwritten by the call's next prepare.  snapshot_of: what enqueue_snapshot gave; 0: the call made none, and the history has none from here.
+	void commit(Buffer<float4> &merged, Buffer<float4> &x1, Buffer<float4> &x2, Buffer<float4> &xa, const CtxCamera &cam, int64_t snapshot_of)
+	{
+		std::swap(merged, h0); std::swap(x1, h1); std::swap(x2, h2); std::swap(xa, ha);
+		camera = temporal_camera(cam.origin, cam.inv_proj, cam.inv_view);
+		snapshot_tris = snapshot_of;
+		present = true;
+	}
+	void reset() { present = false; snapshot_tris = 0; } // (the memory stays)
+	// the snapshot's indices mean other triangles now; its memory is given back (adypt_get_denoise_motion reports it).  The history itself stays
+	void triangles_replaced() { snapshot_tris = 0; snapshot.release(); }
+};
+
+enum class Mode { Plain, Temporal, Motion }; // adypt_denoise, adypt_denoise_temporal, adypt_denoise_temporal_motion
 
 constexpr int kTimingEvents = 4 + kDenoiseMaxLevels; // start, guides, prepare, (the temporal merge,) every level
 
-// what adypt_denoise_temporal adds to a call
-struct TemporalCall { float history_cap; bool commit; bool motion; }; // motion: adypt_denoise_temporal_motion
+// Where the marks of the stage timer stand in a run of a mode: 0 the start, 1 behind the guides (several devices: the upload), 2 behind prepare, then —
+// Temporal and Motion only — one behind the merge (Motion: the gather and the merge), then one behind every level.  Stage k lies between marks k, k + 1.
+struct StageMarks {
+	int merge, first_level; // merge 0: the mode has no such stage
+	explicit StageMarks(Mode m) : merge(m == Mode::Plain ? 0 : 3), first_level(m == Mode::Plain ? 3 : 4) {}
+};
+
+struct LastRun { Mode mode = Mode::Plain; int levels = 0; };
 
 // Everything the denoiser keeps per context; parked in the context (ctx_attachment), freed by adypt_destroy (the context's device is current then).
 struct Denoiser {
 	int width = 0, height = 0;
-	// guide scratch of the owned blocks, block-major: 64 B per local pixel + 4 B per owned block
-	Buffer<float4> g_albedo, g_normal, g_position, g_hits;
-	Buffer<int32_t> d_block_spp;
+	BlockImages own, merged; // the context's own blocks (allocated at the first call: the size never changes); several devices: all blocks, on the first
 	// the filter's row-major images of the whole picture: 80 B + 12 B (the result) per image pixel
 	Buffer<float4> x0[2], x1, x2, xa;
 	Buffer<float> rgb;
-	// several devices: the block-major images of every device's blocks, back to back in rank order, on the first device (88 B per pixel of the blocks
-	// + 8 B per block)
-	Buffer<float4> m_accum, m_albedo, m_normal, m_position, m_hits;
-	Buffer<float2> m_moments;
-	Buffer<int32_t> m_blocks, m_block_spp;
-	// the temporal merge, allocated at the first temporal call only: the merged image of the call, the history (what the last committing call left:
-	// its merged image, its X1, X2 with n_out in .w, XA — swapped in, never copied — and its camera) and the length read-out: 84 B per image pixel
-	Buffer<float4> xm, h0, h1, h2, ha;
+	StageTimer<kTimingEvents> timer; // completed: the last filter ran to its end, rgb is its result and `last` says what it was
+	LastRun last;
+	// the temporal merge, allocated at the first temporal call only: the merged image of the call and the length read-out (20 B per image pixel), and the history
+	Buffer<float4> xm;
 	Buffer<float> length;
-	TemporalCamera h_camera;
-	bool have_history = false, have_length = false;
-	StageTimer<kTimingEvents> timer; // completed: the last filter ran to its end, rgb is its result
-	int levels_timed = 0;
-	bool merge_timed = false; // the last filter was a temporal call: the merge's stage stands between prepare's and the first level's
-	// following moved geometry.  XP, XN: 32 B per image pixel, allocated at the first motion call.  The snapshot belongs to the history: 80 B per
-	// triangle, allocated at the first committing motion call, written only on such a commit, dropped with the history, by a committing temporal call
-	// without motion (the history's geometry is then unknown) and by adypt_set_triangles (the indices mean other triangles)
-	Buffer<float4> xp, xn, snapshot;
-	int64_t snapshot_tris = 0;
-	bool have_snapshot = false, have_motion = false;
-	StageTimer<2> snapshot_timer; // the copy kernel of the last commit
-	void drop_snapshot() { have_snapshot = false; snapshot_tris = 0; }
+	bool length_valid = false; // a temporal call has run to its end since `length` was allocated, and none has failed over it since: calls of other modes leave it
+	History history;
+	// following moved geometry: XP, XN, 32 B per image pixel, allocated at the first motion call
+	Buffer<float4> xp, xn;
+	bool xp_valid = false; // as length_valid, of a motion call and XP, XN
+
+	size_t pixels() const { return (size_t)width * (size_t)height; }
 };
 
 Denoiser *denoiser_of(adypt_ctx *c) { return ctx_state<Denoiser>(c, kAttachDenoise); }
 Denoiser *finished_denoiser(adypt_ctx *c) { Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise); return d && d->timer.completed() ? d : nullptr; }
 
-// the guide scratch of the context's own blocks (allocated at the first call: the size never changes)
-int ensure_guides(adypt_ctx *c, Denoiser *d, const CtxInfo &i)
-{
-	const size_t n = (size_t)std::max(i.n_local_px, 64);
-	CTX_TRY(c, at_least(d->g_albedo, n)); CTX_TRY(c, at_least(d->g_normal, n)); CTX_TRY(c, at_least(d->g_position, n)); CTX_TRY(c, at_least(d->g_hits, n));
-	CTX_TRY(c, at_least(d->d_block_spp, (size_t)std::max(i.n_local_px / kBlockPixels, 1)));
-	return ADYPT_OK;
-}
-
 int ensure_filter_images(adypt_ctx *c, Denoiser *d, const CtxInfo &i)
 {
-	const size_t n = (size_t)i.width * (size_t)i.height;
 	d->width = i.width; d->height = i.height;
+	const size_t n = d->pixels();
 	CTX_TRY(c, at_least(d->x0[0], n)); CTX_TRY(c, at_least(d->x0[1], n)); CTX_TRY(c, at_least(d->x1, n)); CTX_TRY(c, at_least(d->x2, n)); CTX_TRY(c, at_least(d->xa, n));
 	CTX_TRY(c, at_least(d->rgb, n * 3));
 	return ADYPT_OK;
 }
 
-int ensure_history_images(adypt_ctx *c, Denoiser *d)
+// one call: what the three entry points of a front differ in, and what they are given
+struct DenoiseCall {
+	DenoiseParams prm;
+	Mode mode;
+	float history_cap; bool commit; // of Temporal and Motion; a Plain call commits nothing
+	const char *fn;
+	std::string refused;            // why the arguments are refused; empty: they are not
+};
+
+// the call of the ABI structs (null: the defaults — 5 levels, 4.0, 0.1; cap 64, committing); tp is looked at by Temporal and Motion only
+DenoiseCall make_call(Mode mode, const char *fn, const adypt_denoise_params *p, const adypt_temporal_params *tp)
 {
-	const size_t n = (size_t)d->width * (size_t)d->height;
-	CTX_TRY(c, at_least(d->xm, n)); CTX_TRY(c, at_least(d->h0, n)); CTX_TRY(c, at_least(d->h1, n)); CTX_TRY(c, at_least(d->h2, n)); CTX_TRY(c, at_least(d->ha, n));
-	CTX_TRY(c, at_least(d->length, n));
-	return ADYPT_OK;
+	const bool with_history = mode != Mode::Plain;
+	DenoiseCall call{p ? DenoiseParams{p->levels, p->sigma_l, p->sigma_z} : kDenoiseDefaults, mode, kTemporalDefaultCap, with_history, fn, {}};
+	if(with_history && tp) { call.history_cap = tp->history_cap; call.commit = tp->commit != 0; }
+	if(!denoise_params_valid(call.prm))
+		call.refused = std::string(fn) + ": levels must be in [1, " + std::to_string(kDenoiseMaxLevels) + "], sigma_l and sigma_z positive numbers";
+	else if(with_history && !temporal_cap_valid(call.history_cap)) call.refused = std::string(fn) + ": history_cap must be a positive finite number";
+	return call;
 }
 
-// The snapshot of a committing motion call: the records as they are now, enqueued on `stream` behind the call's gather, which reads the old one.  The
-// history has none until the caller has waited for the stream and keeps it (keep_snapshot): a failure in between leaves every pixel unmoved.
-int enqueue_snapshot(adypt_ctx *c, Denoiser *d, hipStream_t stream)
+// prepare (+ the gather + the temporal merge) + the levels (+ the snapshot) of a call, on `stream`; d's images are the whole picture's
+// (ensure_filter_images), `cam` the camera of the context the guides were captured by
+int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages &in, const DenoiseCall &call, const CtxCamera &cam)
 {
-	const CtxScene sc = ctx_scene(c);
-	const int64_t n_vecs = sc.n_tris * kSnapshotVecs;
-	d->drop_snapshot(); // (a failure below leaves none: every pixel is then unmoved)
-	d->snapshot_timer.invalidate();
-	CTX_TRY(c, at_least(d->snapshot, (size_t)n_vecs));
-	CTX_TRY(c, d->snapshot_timer.mark(0, stream));
-	hipLaunchKernelGGL(k_motion_snapshot, dim3(grid_of(sc.n_tris, kSnapshotGroup)), dim3(kSnapshotGroup * kSnapshotVecs), 0, stream, (const float4 *)sc.triangles, sc.tri_float4, sc.n_tris,
-	                   d->snapshot.get());
-	CTX_TRY(c, hipGetLastError());
-	CTX_TRY(c, d->snapshot_timer.mark(1, stream));
-	return ADYPT_OK;
-}
-void keep_snapshot(adypt_ctx *c, Denoiser *d)
-{
-	d->snapshot_timer.complete();
-	d->snapshot_tris = ctx_scene(c).n_tris;
-	d->have_snapshot = true;
-}
-
-// prepare (+ the temporal merge) + the levels, on `stream`; d's images are the whole picture's (ensure_filter_images).  t: a temporal call, under the
-// camera `cam` of the context the guides were captured by.
-int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages &in, const DenoiseParams &prm, const TemporalCall *t = nullptr, const CtxCamera *cam = nullptr)
-{
-	if(t) CTX_STEP(ensure_history_images(c, d));
-	const bool motion = t && t->motion;
-	if(motion)
+	const bool with_history = call.mode != Mode::Plain, with_motion = call.mode == Mode::Motion;
+	const DenoiseParams &prm = call.prm;
+	History &h = d->history;
+	const size_t n = d->pixels();
+	if(with_history) { CTX_TRY(c, at_least(d->xm, n)); CTX_STEP(h.ensure(c, n)); CTX_TRY(c, at_least(d->length, n)); }
+	if(with_motion)
 	{
-		const size_t n = (size_t)d->width * (size_t)d->height;
 		CTX_TRY(c, at_least(d->xp, n)); CTX_TRY(c, at_least(d->xn, n));
-		d->have_motion = false;
+		d->xp_valid = false;
 	}
 	const int width = d->width, height = d->height, n_px = in.n_blocks * kBlockPixels;
 	const int blocks_x = (width + kBlockDim - 1) / kBlockDim;
-	hipLaunchKernelGGL(k_denoise_prepare, dim3(grid_of(n_px, 256)), dim3(256), 0, stream, in.accum, in.moments, in.blocks, in.block_spp, n_px, blocks_x, width, height, in.albedo,
-	                   in.normal, in.position, in.hits, d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get());
+	const int32_t *blocks = in.as<kBlocks>();
+	const float4 *normal = in.as<kNormal>(), *position = in.as<kPosition>(), *hits = in.as<kHits>();
+	hipLaunchKernelGGL(k_denoise_prepare, dim3(grid_of(n_px, 256)), dim3(256), 0, stream, in.as<kAccum>(), in.as<kMoments>(), blocks, in.as<kBlockSpp>(), n_px, blocks_x, width, height,
+	                   in.as<kAlbedo>(), normal, position, hits, d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get());
 	CTX_TRY(c, hipGetLastError());
 	CTX_TRY(c, d->timer.mark(2, stream));
 	const dim3 grid(grid_of(width, kAtrousX), grid_of(height, kAtrousY)), block(kAtrousX, kAtrousY);
-	const int first = t ? 4 : 3; // the mark behind level 0
-	if(t)
+	const StageMarks marks(call.mode);
+	if(with_history)
 	{
-		d->have_length = false;
-		if(motion)
+		d->length_valid = false;
+		if(with_motion)
 		{
-			// (a snapshot of another triangle count is none: adypt_set_triangles drops it, so this only guards)
 			const CtxScene sc = ctx_scene(c);
-			const int64_t n_known = d->have_history && d->have_snapshot && d->snapshot_tris == sc.n_tris ? d->snapshot_tris : 0;
-			hipLaunchKernelGGL(k_motion_gather, dim3(grid_of(n_px, 256)), dim3(256), 0, stream, in.hits, in.normal, in.position, in.blocks, n_px, blocks_x, width, height,
-			                   (const float4 *)d->snapshot, n_known, (const float4 *)sc.triangles, sc.tri_float4, d->xp.get(), d->xn.get());
+			hipLaunchKernelGGL(k_motion_gather, dim3(grid_of(n_px, 256)), dim3(256), 0, stream, hits, normal, position, blocks, n_px, blocks_x, width, height, (const float4 *)h.snapshot,
+			                   h.known_tris(sc.n_tris), (const float4 *)sc.triangles, sc.tri_float4, d->xp.get(), d->xn.get());
 			CTX_TRY(c, hipGetLastError());
 		}
-		const auto merge = motion ? k_temporal_merge<true> : k_temporal_merge<false>;
-		hipLaunchKernelGGL(merge, grid, block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, d->x2.get(), (const float4 *)d->xa, (const float4 *)d->h0,
-		                   (const float4 *)d->h1, (const float4 *)d->h2, (const float4 *)d->ha, d->xm.get(), d->length.get(), width, height, d->have_history ? 1 : 0, d->h_camera,
-		                   t->history_cap, (const float4 *)d->xp, (const float4 *)d->xn);
+		const auto merge = with_motion ? k_temporal_merge<true> : k_temporal_merge<false>;
+		hipLaunchKernelGGL(merge, grid, block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, d->x2.get(), (const float4 *)d->xa, (const float4 *)h.h0, (const float4 *)h.h1,
+		                   (const float4 *)h.h2, (const float4 *)h.ha, d->xm.get(), d->length.get(), width, height, h.present ? 1 : 0, h.camera, call.history_cap, (const float4 *)d->xp,
+		                   (const float4 *)d->xn);
 		CTX_TRY(c, hipGetLastError());
-		CTX_TRY(c, d->timer.mark(3, stream));
+		CTX_TRY(c, d->timer.mark(marks.merge, stream));
 	}
 	for(int l = 0; l < prm.levels; ++l)
 	{
-		const float4 *src = (l == 0 && t) ? d->xm : d->x0[l & 1];
+		const float4 *src = (l == 0 && with_history) ? d->xm : d->x0[l & 1];
 		float4 *dst = d->x0[(l & 1) ^ 1];
-		if(l == prm.levels - 1)
-			hipLaunchKernelGGL(k_atrous<true>, grid, block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
-		else
-			hipLaunchKernelGGL(k_atrous<false>, grid, block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
+		const auto level = l == prm.levels - 1 ? k_atrous<true> : k_atrous<false>;
+		hipLaunchKernelGGL(level, grid, block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
 		CTX_TRY(c, hipGetLastError());
-		CTX_TRY(c, d->timer.mark(first + l, stream));
+		CTX_TRY(c, d->timer.mark(marks.first_level + l, stream));
 	}
-	d->levels_timed = prm.levels;
-	d->merge_timed = t != nullptr;
-	if(motion && t->commit) CTX_STEP(enqueue_snapshot(c, d, stream));
+	int64_t snapshot_of = 0;
+	if(with_motion && call.commit) CTX_STEP(h.enqueue_snapshot(c, stream, &snapshot_of));
 	CTX_TRY(c, hipStreamSynchronize(stream));
+	d->last = LastRun{call.mode, prm.levels};
 	d->timer.complete();
-	if(t)
-	{
-		d->have_length = true;
-		if(motion) d->have_motion = true;
-		if(t->commit)
-		{
-			// the snapshot goes with the history: the records of this call, or none
-			if(motion) keep_snapshot(c, d);
-			else d->drop_snapshot();
-			// this call's merged image, guides (X2.w = n_out) and camera become the history; what the history held is overwritten by the next prepare
-			std::swap(d->xm, d->h0); std::swap(d->x1, d->h1); std::swap(d->x2, d->h2); std::swap(d->xa, d->ha);
-			d->h_camera = temporal_camera(cam->origin, cam->inv_proj, cam->inv_view);
-			d->have_history = true;
-		}
-	}
+	if(with_history) d->length_valid = true;
+	if(with_motion) d->xp_valid = true;
+	if(call.commit) h.commit(d->xm, d->x1, d->x2, d->xa, cam, snapshot_of);
 	return ADYPT_OK;
 }
 
-int params_of(const adypt_denoise_params *p, DenoiseParams *out, std::string *why, const char *fn)
+// The stage times of the last finished run.  ms, where `capacity` holds them: guides, prepare and every level, adypt_get_denoise_timing's layout
+// whatever the mode (returns their number); merge_ms, where not null: the merge's stage, which stands between prepare's and the first level's.
+int read_stages(const Denoiser *d, float *ms, int capacity, float *merge_ms)
 {
-	*out = p ? DenoiseParams{p->levels, p->sigma_l, p->sigma_z} : kDenoiseDefaults;
-	if(denoise_params_valid(*out)) return ADYPT_OK;
-	*why = std::string(fn) + ": levels must be in [1, " + std::to_string(kDenoiseMaxLevels) + "], sigma_l and sigma_z positive numbers";
-	return ADYPT_E_INVALID;
+	const StageMarks marks(d->last.mode);
+	const int n = 2 + d->last.levels;
+	float all[kTimingEvents];
+	d->timer.read(all, kTimingEvents, marks.first_level - 1 + d->last.levels, false);
+	if(merge_ms) *merge_ms = marks.merge ? all[marks.merge - 1] : 0.0f;
+	if(capacity < n) return n;
+	for(int k = 0; k < n; ++k) ms[k] = all[k < 2 ? k : k + marks.first_level - 3];
+	return n;
 }
 
-// the context's guides into its own scratch, enqueued behind its frames
-int capture_guides(adypt_ctx *c, Denoiser *d, const CtxInfo &i, const char *fn)
+// the context's own set, for `in` = ctx_denoise_inputs(c): the kContextImages are the context's (moments null while it keeps no noise statistics, which
+// only the guide read-out goes without), the guides and the sample counts the denoiser's
+int own_images(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, LocalImages *v)
 {
-	CTX_STEP(ensure_guides(c, d, i));
-	return ctx_capture_guides(c, fn, d->g_albedo, d->g_normal, d->g_position, d->g_hits);
+	*v = LocalImages{{}, in.n_blocks};
+	v->image[kAccum] = in.accum; v->image[kMoments] = in.moments; v->image[kBlocks] = in.blocks;
+	return d->own.fill(c, v, kContextImages);
+}
+
+// ... and the context's guides into it, enqueued behind its frames (the sample counts are the caller's to upload)
+int capture_guides(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, LocalImages *v)
+{
+	CTX_STEP(own_images(c, d, in, v));
+	return ctx_capture_guides(c, fn, d->own.as<kAlbedo>(), d->own.as<kNormal>(), d->own.as<kPosition>(), d->own.as<kHits>());
+}
+
+// `bytes` of a device array of a context on the host (the stream is drained when it returns)
+int fetch(adypt_ctx *c, const CtxInfo &i, const void *device, void *host, size_t bytes)
+{
+	CTX_TRY(c, hipMemcpyAsync(host, device, bytes, hipMemcpyDeviceToHost, i.stream));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
+	return ADYPT_OK;
+}
+
+// A read-out of an image of the last finished run, per_pixel elements per image pixel: `image` picks it, null where the denoiser has none to read, and
+// the call is then refused with `none`.
+template <class T, class Pick> int read_image(adypt_ctx *c, const char *fn, const char *none, T *host, int per_pixel, Pick image)
+{
+	Denoiser *d = finished_denoiser(c);
+	const T *device = d ? image(d) : nullptr;
+	if(!device) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + none);
+	const CtxInfo i = ctx_info(c);
+	CTX_TRY(c, hipSetDevice(i.device));
+	return fetch(c, i, device, host, d->pixels() * per_pixel * sizeof(T));
 }
 
 int read_result(adypt_ctx *c, const char *fn, float *rgb)
 {
-	Denoiser *d = finished_denoiser(c);
-	if(!d) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": nothing has been denoised yet (adypt_denoise)");
-	const CtxInfo i = ctx_info(c);
-	CTX_TRY(c, hipSetDevice(i.device));
-	CTX_TRY(c, hipMemcpyAsync(rgb, d->rgb, (size_t)d->width * d->height * 3 * sizeof(float), hipMemcpyDeviceToHost, i.stream));
-	CTX_TRY(c, hipStreamSynchronize(i.stream));
-	return ADYPT_OK;
-}
-
-// one block-major local image of a context (n_local_px > 0 elements) on the host (the stream is drained when it returns)
-template <class T> int fetch(adypt_ctx *c, const CtxInfo &i, const T *device, T *host)
-{
-	CTX_TRY(c, hipMemcpyAsync(host, device, (size_t)i.n_local_px * sizeof(T), hipMemcpyDeviceToHost, i.stream));
-	CTX_TRY(c, hipStreamSynchronize(i.stream));
-	return ADYPT_OK;
-}
-
-// the temporal half of a call's parameters (tp NULL = the defaults: cap 64, committing)
-int temporal_of(const adypt_temporal_params *tp, bool motion, TemporalCall *out, std::string *why, const char *fn)
-{
-	*out = tp ? TemporalCall{tp->history_cap, tp->commit != 0, motion} : TemporalCall{kTemporalDefaultCap, true, motion};
-	if(temporal_cap_valid(out->history_cap)) return ADYPT_OK;
-	*why = std::string(fn) + ": history_cap must be a positive finite number";
-	return ADYPT_E_INVALID;
-}
-
-// adypt_denoise (temporal false: tp is not looked at), adypt_denoise_temporal and (motion) adypt_denoise_temporal_motion of one context
-int denoise_context(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp, bool temporal, const char *fn, bool motion = false)
-{
-	if(!c) return ADYPT_E_INVALID;
-	DenoiseParams prm;
-	TemporalCall t;
-	std::string why;
-	if(params_of(p, &prm, &why, fn) != ADYPT_OK) return ctx_fail(c, ADYPT_E_INVALID, why);
-	if(temporal && temporal_of(tp, motion, &t, &why, fn) != ADYPT_OK) return ctx_fail(c, ADYPT_E_INVALID, why);
-	const CtxInfo i = ctx_info(c);
-	if(i.nranks != 1) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the context is a tile shard (tile_nranks > 1): the filter needs the whole image (adypt_multi_denoise)");
-	CTX_STEP(ctx_denoise_ready(c, fn));
-	CTX_TRY(c, hipSetDevice(i.device));
-	Denoiser *d = denoiser_of(c);
-	CTX_STEP(ensure_filter_images(c, d, i));
-	d->timer.invalidate();
-	CTX_TRY(c, d->timer.mark(0, i.stream));
-	CTX_STEP(capture_guides(c, d, i, fn));
-	CTX_TRY(c, d->timer.mark(1, i.stream));
-	const DenoiseInputs in = ctx_denoise_inputs(c);
-	CTX_TRY(c, hipMemcpyAsync(d->d_block_spp, in.block_spp.data(), in.block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
-	const LocalImages local{in.accum, in.moments, in.blocks, d->d_block_spp, d->g_albedo, d->g_normal, d->g_position, d->g_hits, in.n_blocks};
-	const CtxCamera cam = ctx_camera(c);
-	return run_filter(c, d, i.stream, local, prm, temporal ? &t : nullptr, &cam);
+	return read_image(c, fn, ": nothing has been denoised yet (adypt_denoise)", rgb, 3, [](Denoiser *d) { return d->rgb.get(); });
 }
 
 int read_history_length(adypt_ctx *c, const char *fn, float *length)
 {
-	Denoiser *d = finished_denoiser(c);
-	if(!d || !d->have_length) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": no temporal call has run yet (adypt_denoise_temporal)");
-	const CtxInfo i = ctx_info(c);
-	CTX_TRY(c, hipSetDevice(i.device));
-	CTX_TRY(c, hipMemcpyAsync(length, d->length, (size_t)d->width * d->height * sizeof(float), hipMemcpyDeviceToHost, i.stream));
-	CTX_TRY(c, hipStreamSynchronize(i.stream));
-	return ADYPT_OK;
+	return read_image(c, fn, ": no temporal call has run yet (adypt_denoise_temporal)", length, 1, [](Denoiser *d) { return d->length_valid ? d->length.get() : nullptr; });
 }
 
-// XP, XN of the last motion call: the previous position (W x H x 3 floats) and the moved flag (W x H bytes) of every pixel; either may be null
+// XP of the last motion call: the previous position (W x H x 3 floats) and the moved flag (W x H bytes) of every pixel; either may be null
 int read_motion(adypt_ctx *c, const char *fn, float *prev_position, uint8_t *moved)
 {
-	Denoiser *d = finished_denoiser(c);
-	if(!d || !d->have_motion) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": no motion call has run yet (adypt_denoise_temporal_motion)");
-	const CtxInfo i = ctx_info(c);
-	CTX_TRY(c, hipSetDevice(i.device));
-	const size_t n = (size_t)d->width * d->height;
-	std::vector<float4> xp(n);
-	CTX_TRY(c, hipMemcpyAsync(xp.data(), d->xp, n * sizeof(float4), hipMemcpyDeviceToHost, i.stream));
-	CTX_TRY(c, hipStreamSynchronize(i.stream));
-	for(size_t k = 0; k < n; ++k)
+	const Denoiser *last = finished_denoiser(c);
+	std::vector<float4> xp(last && last->xp_valid ? last->pixels() : 0); // (nothing where the call is about to be refused)
+	CTX_STEP(read_image(c, fn, ": no motion call has run yet (adypt_denoise_temporal_motion)", xp.data(), 1, [](Denoiser *d) { return d->xp_valid ? d->xp.get() : nullptr; }));
+	for(size_t k = 0; k < xp.size(); ++k)
 	{
 		if(prev_position) { prev_position[3 * k] = xp[k].x; prev_position[3 * k + 1] = xp[k].y; prev_position[3 * k + 2] = xp[k].z; }
 		if(moved) moved[k] = xp[k].w != 0.0f ? 1 : 0;
@@ -437,84 +470,79 @@ int get_motion(adypt_ctx *c, const char *fn, adypt_denoise_motion *out)
 	*out = adypt_denoise_motion{};
 	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
 	if(!d) return ADYPT_OK;
-	out->have_snapshot = d->have_snapshot ? 1 : 0;
-	out->n_tris = d->snapshot_tris;
-	out->device_bytes = (int64_t)(d->snapshot.bytes() + d->xp.bytes() + d->xn.bytes());
-	if(d->have_snapshot) (void)d->snapshot_timer.read(&out->snapshot_ms, 1, 1, false);
+	const History &h = d->history;
+	out->have_snapshot = h.snapshot_tris > 0 ? 1 : 0;
+	out->n_tris = h.snapshot_tris;
+	out->device_bytes = (int64_t)(h.snapshot.bytes() + d->xp.bytes() + d->xn.bytes());
+	if(out->have_snapshot) (void)h.snapshot_timer.read(&out->snapshot_ms, 1, 1, false);
 	return ADYPT_OK;
 }
 
 int read_merge_ms(adypt_ctx *c, const char *fn, float *ms)
 {
 	Denoiser *d = finished_denoiser(c);
-	if(!d || !d->merge_timed) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the last filter was not a temporal call (adypt_denoise_temporal)");
-	float all[kTimingEvents];
-	d->timer.read(all, kTimingEvents, 3 + d->levels_timed, false);
-	*ms = all[2];
+	if(!d || d->last.mode == Mode::Plain) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the last filter was not a temporal call (adypt_denoise_temporal)");
+	read_stages(d, nullptr, 0, ms);
 	return ADYPT_OK;
+}
+
+// the three denoise calls of one context
+int denoise_context(adypt_ctx *c, const DenoiseCall &call)
+{
+	if(!c) return ADYPT_E_INVALID;
+	if(!call.refused.empty()) return ctx_fail(c, ADYPT_E_INVALID, call.refused);
+	const char *fn = call.fn;
+	const CtxInfo i = ctx_info(c);
+	if(i.nranks != 1) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the context is a tile shard (tile_nranks > 1): the filter needs the whole image (adypt_multi_denoise)");
+	CTX_STEP(ctx_denoise_ready(c, fn));
+	CTX_TRY(c, hipSetDevice(i.device));
+	Denoiser *d = denoiser_of(c);
+	CTX_STEP(ensure_filter_images(c, d, i));
+	d->timer.invalidate();
+	CTX_TRY(c, d->timer.mark(0, i.stream));
+	const DenoiseInputs in = ctx_denoise_inputs(c);
+	LocalImages local;
+	CTX_STEP(capture_guides(c, d, in, fn, &local));
+	CTX_TRY(c, d->timer.mark(1, i.stream));
+	CTX_TRY(c, hipMemcpyAsync(d->own.as<kBlockSpp>(), in.block_spp.data(), in.block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
+	return run_filter(c, d, i.stream, local, call, ctx_camera(c));
 }
 
 }  // namespace
 
 namespace adypt {
 
-void denoise_drop_snapshot(adypt_ctx *c)
+void denoise_triangles_replaced(adypt_ctx *c)
 {
-	Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
-	if(!d) return;
-	d->drop_snapshot();
-	d->snapshot.release();
+	if(Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise)) d->history.triangles_replaced();
 }
 
 }  // namespace adypt
 
 extern "C" {
 
-int adypt_denoise(adypt_ctx *c, const adypt_denoise_params *p) { return denoise_context(c, p, nullptr, false, "adypt_denoise"); }
+int adypt_denoise(adypt_ctx *c, const adypt_denoise_params *p) { return denoise_context(c, make_call(Mode::Plain, "adypt_denoise", p, nullptr)); }
 
-int adypt_denoise_temporal(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return denoise_context(c, p, tp, true, "adypt_denoise_temporal"); }
+int adypt_denoise_temporal(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return denoise_context(c, make_call(Mode::Temporal, "adypt_denoise_temporal", p, tp)); }
 
-int adypt_denoise_temporal_motion(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp)
-{
-	return denoise_context(c, p, tp, true, "adypt_denoise_temporal_motion", true);
-}
+int adypt_denoise_temporal_motion(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return denoise_context(c, make_call(Mode::Motion, "adypt_denoise_temporal_motion", p, tp)); }
 
 int adypt_denoise_history_reset(adypt_ctx *c)
 {
 	if(!c) return ADYPT_E_INVALID;
-	if(Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise)) { d->have_history = false; d->drop_snapshot(); }
+	if(Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise)) d->history.reset();
 	return ADYPT_OK;
 }
 
-int adypt_read_denoise_motion(adypt_ctx *c, float *prev_position, uint8_t *moved)
-{
-	if(!c) return ADYPT_E_INVALID;
-	return read_motion(c, "adypt_read_denoise_motion", prev_position, moved);
-}
+int adypt_read_denoise_motion(adypt_ctx *c, float *prev_position, uint8_t *moved) { return c ? read_motion(c, "adypt_read_denoise_motion", prev_position, moved) : ADYPT_E_INVALID; }
 
-int adypt_get_denoise_motion(adypt_ctx *c, adypt_denoise_motion *out)
-{
-	if(!c) return ADYPT_E_INVALID;
-	return get_motion(c, "adypt_get_denoise_motion", out);
-}
+int adypt_get_denoise_motion(adypt_ctx *c, adypt_denoise_motion *out) { return c ? get_motion(c, "adypt_get_denoise_motion", out) : ADYPT_E_INVALID; }
 
-int adypt_read_denoise_history(adypt_ctx *c, float *length)
-{
-	if(!c || !length) return ADYPT_E_INVALID;
-	return read_history_length(c, "adypt_read_denoise_history", length);
-}
+int adypt_read_denoise_history(adypt_ctx *c, float *length) { return c && length ? read_history_length(c, "adypt_read_denoise_history", length) : ADYPT_E_INVALID; }
 
-int adypt_get_denoise_merge_ms(adypt_ctx *c, float *ms)
-{
-	if(!c || !ms) return ADYPT_E_INVALID;
-	return read_merge_ms(c, "adypt_get_denoise_merge_ms", ms);
-}
+int adypt_get_denoise_merge_ms(adypt_ctx *c, float *ms) { return c && ms ? read_merge_ms(c, "adypt_get_denoise_merge_ms", ms) : ADYPT_E_INVALID; }
 
-int adypt_read_denoised(adypt_ctx *c, float *rgb)
-{
-	if(!c || !rgb) return ADYPT_E_INVALID;
-	return read_result(c, "adypt_read_denoised", rgb);
-}
+int adypt_read_denoised(adypt_ctx *c, float *rgb) { return c && rgb ? read_result(c, "adypt_read_denoised", rgb) : ADYPT_E_INVALID; }
 
 int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float *position, uint8_t *hit)
 {
@@ -522,16 +550,16 @@ int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float 
 	const CtxInfo i = ctx_info(c);
 	if(i.n_local_px == 0) return ADYPT_OK; // a shard that owns no block
 	CTX_TRY(c, hipSetDevice(i.device));
-	Denoiser *d = denoiser_of(c);
-	CTX_STEP(capture_guides(c, d, i, "adypt_read_denoise_guides"));
+	LocalImages own;
+	CTX_STEP(capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), "adypt_read_denoise_guides", &own));
 	const std::vector<int32_t> blocks = owned_blocks(i.width, i.height, i.rank, i.nranks);
 	std::vector<float4> local((size_t)i.n_local_px);
 	float *const image[3] = {albedo, normal, position};
-	const float4 *const device[3] = {d->g_albedo, d->g_normal, d->g_position};
+	const BlockImage guide[3] = {kAlbedo, kNormal, kPosition};
 	for(int k = 0; k < 3; ++k)
 	{
 		if(!image[k]) continue;
-		CTX_STEP(fetch(c, i, device[k], local.data()));
+		CTX_STEP(fetch(c, i, own.image[guide[k]], local.data(), local.size() * sizeof(float4)));
 		for_each_local_pixel(blocks, i.width, i.height, [&](size_t L, int x, int y) {
 			float *o = image[k] + ((size_t)y * i.width + x) * 3;
 			o[0] = local[L].x; o[1] = local[L].y; o[2] = local[L].z;
@@ -539,7 +567,7 @@ int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float 
 	}
 	if(hit)
 	{
-		CTX_STEP(fetch(c, i, (const float4 *)d->g_hits, local.data()));
+		CTX_STEP(fetch(c, i, own.image[kHits], local.data(), local.size() * sizeof(float4)));
 		for_each_local_pixel(blocks, i.width, i.height, [&](size_t L, int x, int y) {
 			int32_t tri;
 			memcpy(&tri, &local[L].x, 4);
@@ -555,14 +583,7 @@ int adypt_get_denoise_timing(adypt_ctx *c, float *ms, int capacity)
 	if(!c || !ms || capacity < 0) return ADYPT_E_INVALID;
 	Denoiser *d = finished_denoiser(c);
 	if(!d) return ctx_fail(c, ADYPT_E_STATE, "adypt_get_denoise_timing: nothing has been denoised yet (adypt_denoise)");
-	const int n = 2 + d->levels_timed;
-	if(!d->merge_timed) return d->timer.read(ms, capacity, n, false);
-	// a temporal call: the merge's stage (adypt_get_denoise_merge_ms) is left out, the layout is adypt_denoise's
-	if(capacity < n) return n;
-	float all[kTimingEvents];
-	d->timer.read(all, kTimingEvents, n + 1, false);
-	for(int k = 0; k < n; ++k) ms[k] = all[k < 2 ? k : k + 1];
-	return n;
+	return read_stages(d, ms, capacity, nullptr); // (a temporal call's merge stage is left out: adypt_get_denoise_merge_ms)
 }
 
 // ---- one process, N devices ----
@@ -570,19 +591,16 @@ int adypt_get_denoise_timing(adypt_ctx *c, float *ms, int capacity)
 
 namespace {
 
-// adypt_multi_denoise and adypt_multi_denoise_temporal: the merge runs on the first device, where the filter runs, and the history lives there
-int multi_denoise(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp, bool temporal, const char *fn, bool motion = false)
+// the three denoise calls of a handle: the merge runs on the first device, where the filter runs, and the history lives there
+int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 {
 	const int n_dev = adypt_multi_device_count(m);
 	if(n_dev < 1) return ADYPT_E_INVALID;
 	adypt_ctx *root = adypt_multi_context(m, 0);
-	if(n_dev == 1) return multi_each(m, [=](adypt_ctx *c) { return denoise_context(c, p, tp, temporal, fn, motion); });
+	if(n_dev == 1) return multi_each(m, [&call](adypt_ctx *c) { return denoise_context(c, call); });
 	auto fail_ctx = [m](adypt_ctx *c, int r) { multi_set_error(m, adypt_last_error(c)); return r; };
-	DenoiseParams prm;
-	TemporalCall t;
-	std::string why;
-	if(params_of(p, &prm, &why, fn) != ADYPT_OK) { multi_set_error(m, why); return ADYPT_E_INVALID; }
-	if(temporal && temporal_of(tp, motion, &t, &why, fn) != ADYPT_OK) { multi_set_error(m, why); return ADYPT_E_INVALID; }
+	if(!call.refused.empty()) { multi_set_error(m, call.refused); return ADYPT_E_INVALID; }
+	const char *fn = call.fn;
 	std::vector<adypt_ctx *> ctx;
 	for(int k = 0; k < n_dev; ++k) ctx.push_back(adypt_multi_context(m, k));
 	CTX_STEP(multi_each(m, [fn](adypt_ctx *c) { return ctx_denoise_ready(c, fn); }));
@@ -591,33 +609,31 @@ int multi_denoise(adypt_multi *m, const adypt_denoise_params *p, const adypt_tem
 		const CtxInfo i = ctx_info(c);
 		if(i.n_local_px == 0) return (int)ADYPT_OK;
 		if(hipSetDevice(i.device) != hipSuccess) return ctx_fail(c, ADYPT_E_HIP, std::string(fn) + ": hipSetDevice failed");
-		return capture_guides(c, denoiser_of(c), i, fn);
+		LocalImages own;
+		return capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), fn, &own);
 	}));
 	// the local images of every device back to back in rank order, and their block lists and sample counts likewise (the counts from each context's
 	// own state in that order: multi.hip's merge is sorted by block index, which is not this order, and would launch k_noise_blocks for nothing)
 	const CtxInfo ri = ctx_info(root);
-	size_t n_px = 0;
-	for(adypt_ctx *c : ctx) n_px += (size_t)ctx_info(c).n_local_px;
-	const int n_blocks = (int)(n_px / kBlockPixels);
-	std::vector<float4> accum(n_px), albedo(n_px), normal(n_px), position(n_px), hits(n_px);
-	std::vector<float2> moments(n_px);
-	std::vector<int32_t> blocks, block_spp;
-	size_t at = 0; // the rank's first pixel in them
+	size_t n_blocks = 0;
+	for(adypt_ctx *c : ctx) n_blocks += (size_t)ctx_info(c).n_local_px / kBlockPixels;
+	std::vector<uint8_t> host[kBlockImages];
+	for(int k = 0; k < kBlockImages; ++k) host[k].resize(n_blocks * kBlockImageBytes[k]);
+	size_t at = 0; // the rank's first block in them
 	for(adypt_ctx *c : ctx)
 	{
 		const CtxInfo i = ctx_info(c);
 		if(i.n_local_px == 0) continue;
 		if(hipSetDevice(i.device) != hipSuccess) return fail_ctx(c, ctx_fail(c, ADYPT_E_HIP, std::string(fn) + ": hipSetDevice failed"));
-		Denoiser *d = denoiser_of(c);
 		const DenoiseInputs in = ctx_denoise_inputs(c);
-		const float4 *const device[5] = {in.accum, d->g_albedo, d->g_normal, d->g_position, d->g_hits};
-		float4 *const merged[5] = {accum.data(), albedo.data(), normal.data(), position.data(), hits.data()};
-		int r = fetch(c, i, in.moments, moments.data() + at);
-		for(int k = 0; k < 5 && r == ADYPT_OK; ++k) r = fetch(c, i, device[k], merged[k] + at);
+		LocalImages own;
+		int r = own_images(c, denoiser_of(c), in, &own);
+		for(const BlockImage k : kFetchOrder)
+			if(r == ADYPT_OK) r = fetch(c, i, own.image[k], host[k].data() + at * kBlockImageBytes[k], (size_t)in.n_blocks * kBlockImageBytes[k]);
 		if(r != ADYPT_OK) return fail_ctx(c, r);
-		blocks.insert(blocks.end(), in.block_index.begin(), in.block_index.end());
-		block_spp.insert(block_spp.end(), in.block_spp.begin(), in.block_spp.end());
-		at += (size_t)i.n_local_px;
+		memcpy(host[kBlocks].data() + at * sizeof(int32_t), in.block_index.data(), in.block_index.size() * sizeof(int32_t));
+		memcpy(host[kBlockSpp].data() + at * sizeof(int32_t), in.block_spp.data(), in.block_spp.size() * sizeof(int32_t));
+		at += (size_t)in.n_blocks;
 	}
 	// ... uploaded to the first device, where the same prepare / a-trous launches run
 	adypt_ctx *c = root;
@@ -626,21 +642,12 @@ int multi_denoise(adypt_multi *m, const adypt_denoise_params *p, const adypt_tem
 		Denoiser *d = denoiser_of(c);
 		CTX_STEP(ensure_filter_images(c, d, ri));
 		d->timer.invalidate();
-		CTX_TRY(c, at_least(d->m_accum, n_px)); CTX_TRY(c, at_least(d->m_albedo, n_px)); CTX_TRY(c, at_least(d->m_normal, n_px)); CTX_TRY(c, at_least(d->m_position, n_px));
-		CTX_TRY(c, at_least(d->m_hits, n_px)); CTX_TRY(c, at_least(d->m_moments, n_px)); CTX_TRY(c, at_least(d->m_blocks, (size_t)n_blocks)); CTX_TRY(c, at_least(d->m_block_spp, (size_t)n_blocks));
+		LocalImages all{{}, (int)n_blocks};
+		CTX_STEP(d->merged.fill(c, &all, 0)); // (it borrows none)
 		CTX_TRY(c, d->timer.mark(0, ri.stream));
-		CTX_TRY(c, hipMemcpyAsync(d->m_accum, accum.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
-		CTX_TRY(c, hipMemcpyAsync(d->m_albedo, albedo.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
-		CTX_TRY(c, hipMemcpyAsync(d->m_normal, normal.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
-		CTX_TRY(c, hipMemcpyAsync(d->m_position, position.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
-		CTX_TRY(c, hipMemcpyAsync(d->m_hits, hits.data(), n_px * sizeof(float4), hipMemcpyHostToDevice, ri.stream));
-		CTX_TRY(c, hipMemcpyAsync(d->m_moments, moments.data(), n_px * sizeof(float2), hipMemcpyHostToDevice, ri.stream));
-		CTX_TRY(c, hipMemcpyAsync(d->m_blocks, blocks.data(), blocks.size() * sizeof(int32_t), hipMemcpyHostToDevice, ri.stream));
-		CTX_TRY(c, hipMemcpyAsync(d->m_block_spp, block_spp.data(), block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, ri.stream));
+		for(int k = 0; k < kBlockImages; ++k) CTX_TRY(c, hipMemcpyAsync(d->merged.image[k], host[k].data(), host[k].size(), hipMemcpyHostToDevice, ri.stream));
 		CTX_TRY(c, d->timer.mark(1, ri.stream));
-		const LocalImages all{d->m_accum, d->m_moments, d->m_blocks, d->m_block_spp, d->m_albedo, d->m_normal, d->m_position, d->m_hits, n_blocks};
-		const CtxCamera cam = ctx_camera(c); // (adypt_multi_set_camera gives every context the same)
-		return run_filter(c, d, ri.stream, all, prm, temporal ? &t : nullptr, &cam);
+		return run_filter(c, d, ri.stream, all, call, ctx_camera(c)); // (adypt_multi_set_camera gives every context the same camera)
 	};
 	const int r = steps();
 	return r == ADYPT_OK ? r : fail_ctx(root, r);
@@ -660,14 +667,11 @@ template <class F> int on_root(adypt_multi *m, F f)
 
 extern "C" {
 
-int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p) { return multi_denoise(m, p, nullptr, false, "adypt_multi_denoise"); }
+int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p) { return multi_denoise(m, make_call(Mode::Plain, "adypt_multi_denoise", p, nullptr)); }
 
-int adypt_multi_denoise_temporal(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return multi_denoise(m, p, tp, true, "adypt_multi_denoise_temporal"); }
+int adypt_multi_denoise_temporal(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return multi_denoise(m, make_call(Mode::Temporal, "adypt_multi_denoise_temporal", p, tp)); }
 
-int adypt_multi_denoise_temporal_motion(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp)
-{
-	return multi_denoise(m, p, tp, true, "adypt_multi_denoise_temporal_motion", true);
-}
+int adypt_multi_denoise_temporal_motion(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return multi_denoise(m, make_call(Mode::Motion, "adypt_multi_denoise_temporal_motion", p, tp)); }
 
 // the snapshot and the motion images live on the first device, beside the history
 int adypt_multi_read_denoise_motion(adypt_multi *m, float *prev_position, uint8_t *moved)
@@ -684,23 +688,17 @@ int adypt_multi_denoise_history_reset(adypt_multi *m) { return on_root(m, [](ady
 
 int adypt_multi_read_denoise_history(adypt_multi *m, float *length)
 {
-	if(!length) return ADYPT_E_INVALID;
-	return on_root(m, [=](adypt_ctx *c) { return read_history_length(c, "adypt_multi_read_denoise_history", length); });
+	return length ? on_root(m, [=](adypt_ctx *c) { return read_history_length(c, "adypt_multi_read_denoise_history", length); }) : ADYPT_E_INVALID;
 }
 
 int adypt_multi_get_denoise_merge_ms(adypt_multi *m, float *ms)
 {
-	if(!ms) return ADYPT_E_INVALID;
-	return on_root(m, [=](adypt_ctx *c) { return read_merge_ms(c, "adypt_multi_get_denoise_merge_ms", ms); });
+	return ms ? on_root(m, [=](adypt_ctx *c) { return read_merge_ms(c, "adypt_multi_get_denoise_merge_ms", ms); }) : ADYPT_E_INVALID;
 }
 
 int adypt_multi_read_denoised(adypt_multi *m, float *rgb)
 {
-	if(adypt_multi_device_count(m) < 1 || !rgb) return ADYPT_E_INVALID;
-	adypt_ctx *root = adypt_multi_context(m, 0);
-	const int r = read_result(root, "adypt_multi_read_denoised", rgb);
-	if(r != ADYPT_OK) multi_set_error(m, adypt_last_error(root));
-	return r;
+	return rgb ? on_root(m, [=](adypt_ctx *c) { return read_result(c, "adypt_multi_read_denoised", rgb); }) : ADYPT_E_INVALID;
 }
 
 // every device writes the pixels of its own tiles

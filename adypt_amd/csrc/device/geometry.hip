@@ -124,7 +124,7 @@ int set_triangles(adypt_ctx *c, const char *who, const void *triangles, int64_t 
 	CTX_STEP(build_for_triangles(c, q, who, (const float4 *)records.get(), &geometry, out));
 	g->timer.complete(); // (the build has waited for the stream)
 	pose_drop_binding(c); // (a rest pose and a binding were the old triangles': pose.hip)
-	denoise_drop_snapshot(c); // (and so was what the temporal merge followed moved geometry by: denoise.hip)
+	denoise_triangles_replaced(c); // (and so was what the temporal merge followed moved geometry by: denoise.hip)
 	return ADYPT_OK; // (the old records and class bytes go with `records` and `classes`)
 }
 

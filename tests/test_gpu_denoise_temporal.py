@@ -349,6 +349,86 @@ def test_refusals(scene_cache):
     q.destroy()
 
 
+@pytest.mark.parametrize("n_dev", [1, 2], ids=["one-context", "2-shards"])
+def test_read_outs_follow_the_call_sequence(n_dev, scene_cache, monkeypatch):
+    """tiny0 96x64 at 2 spp: after every step of a sequence of accepted and refused calls, which of the five read-outs answer and which return
+    E_STATE, and that what answers is, bit for bit, what the same read-out gave right after the call that produced it."""
+    monkeypatch.setenv("ADYPT_MULTI_SHARED_DEVICE", "1")
+    inst = make_instance(scene_cache, "tiny0", 96, 64)
+    t = inst.m_path_tracer
+    if n_dev > 1:
+        t = api.MultiPathTracer()
+        t.Initialize(inst.m_config.pt_params(SEED), inst.m_hipscene, 96, 64, (0,) * n_dev)
+        assert t.DeviceCount() == n_dev
+    t.SetNoiseStats(True)
+    set_pose(t, inst.m_config, *camera_of(inst.m_config.c, "tiny0", 0), SEED, spp=2)
+
+    def read_denoised():
+        rgb = np.zeros((64, 96, 3), F)
+        t._call("read_denoised", rgb.ctypes.data)
+        return rgb
+    reads = {"denoised": read_denoised, "length": t.ReadDenoiseHistory, "motion": t.ReadDenoiseMotion}
+    kept = {}  # what a read-out gave right after the call that produced it
+
+    def step(tag, denoised, length, motion, merge, levels):
+        """every column: "new" (answers; kept from here on), "kept" (answers with the kept bits) or None (E_STATE); merge: answers (> 0) or not"""
+        for name, want in (("denoised", denoised), ("length", length), ("motion", motion)):
+            if want is None:
+                with pytest.raises(N.AdyptError) as e:
+                    reads[name]()
+                assert e.value.code == N.E_STATE, "%s: %s" % (tag, name)
+                continue
+            got = reads[name]()
+            got = np.concatenate([got["previous_position"].reshape(-1), got["moved"].astype(F).reshape(-1)]) if name == "motion" else got
+            if want == "new":
+                kept[name] = got
+            assert same(got, kept[name]), "%s: %s is not what it was after the call that produced it" % (tag, name)
+        if merge:
+            assert t.GetDenoiseMergeMs() > 0.0, tag
+        else:
+            with pytest.raises(N.AdyptError) as e:
+                t.GetDenoiseMergeMs()
+            assert e.value.code == N.E_STATE, "%s: merge ms" % tag
+        if levels is None:
+            with pytest.raises(N.AdyptError) as e:
+                t.GetDenoiseTiming()
+            assert e.value.code == N.E_STATE, "%s: timing" % tag
+        else:
+            assert len(t.GetDenoiseTiming()["levels"]) == levels, "%s: timing entries" % tag
+
+    def refused(**kw):
+        with pytest.raises(N.AdyptError) as e:
+            t.Denoise(**kw)
+        assert e.value.code == N.E_INVALID, str(e.value)
+    step("nothing yet", None, None, None, False, None)
+    plain = t.Denoise()
+    step("Denoise()", "new", None, None, False, 5)
+    assert same(kept["denoised"], plain)
+    a = t.Denoise(temporal=True, commit=False)
+    step("temporal, commit = 0", "new", "new", None, True, 5)
+    assert same(kept["denoised"], a) and same(a, plain) and (kept["length"] == F(2)).all()  # (no history: the plain filter)
+    b = t.Denoise(temporal=True, commit=False, follow_motion=True)
+    step("motion, commit = 0", "new", "new", "new", True, 5)
+    assert same(kept["denoised"], b)
+    c = t.Denoise(temporal=True, commit=False)
+    step("temporal, commit = 0, again", "new", "new", "kept", True, 5)
+    assert same(kept["denoised"], c)
+    three = t.Denoise(levels=3)
+    step("Denoise(levels=3)", "new", "kept", "kept", False, 3)
+    assert same(kept["denoised"], three) and not same(three, plain)
+    refused(levels=7)
+    refused(temporal=True, history_cap=0.0)
+    step("refused calls", "kept", "kept", "kept", False, 3)
+    t.ResetDenoiseHistory()
+    step("history reset", "kept", "kept", "kept", False, 3)
+    last = t.Denoise(temporal=True)
+    step("temporal, committing", "new", "new", "kept", True, 5)
+    assert same(kept["denoised"], last) and same(last, plain) and (kept["length"] == F(2)).all()
+    if n_dev > 1:
+        t.destroy()
+    inst.m_path_tracer.destroy()
+
+
 def test_cli(scene_cache, sobol_matrices, tmp_path):
     """Two --history-from configs on tiny0 96x64 against the same sequence through Python."""
     case = CASES[1]
