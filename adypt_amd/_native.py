@@ -138,6 +138,11 @@ class PoseBinding(Struct):
     _fields_ = [("kind", C.c_int32), ("n_matrices", C.c_int32), ("n_tris", C.c_int64), ("device_bytes", C.c_int64)]
 
 
+class MorphBinding(Struct):
+    """adypt_morph_binding."""
+    _fields_ = [("n_targets", C.c_int32), ("n_entries", C.c_int64), ("n_tris_touched", C.c_int64), ("device_bytes", C.c_int64)]
+
+
 # every symbol include/*.h declares, with its signature (tests/test_abi.py checks the export list against the headers)
 _SIGS = {
     # adypt_hip.h
@@ -258,6 +263,15 @@ _SIGS = {
     "adypt_multi_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
     "adypt_multi_unbind_pose": (C.c_int, [C.c_void_p]),
     "adypt_multi_get_pose_binding": (C.c_int, [C.c_void_p, C.POINTER(PoseBinding)]),
+    # morph targets in front of the matrices
+    "adypt_bind_morph": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "adypt_pose_morph": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
+    "adypt_unbind_morph": (C.c_int, [C.c_void_p]),
+    "adypt_get_morph_binding": (C.c_int, [C.c_void_p, C.POINTER(MorphBinding)]),
+    "adypt_multi_bind_morph": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "adypt_multi_pose_morph": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
+    "adypt_multi_unbind_morph": (C.c_int, [C.c_void_p]),
+    "adypt_multi_get_morph_binding": (C.c_int, [C.c_void_p, C.POINTER(MorphBinding)]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),
@@ -327,6 +341,9 @@ _SIGS = {
     "adypt_woop_matrices": (None, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "adypt_pack_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "adypt_pose_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "adypt_pose_triangles_morph": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_int32, C.c_void_p]),
+    "adypt_morph_diff": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "adypt_decode_root_card": (None, [C.c_void_p, C.c_int, C.c_void_p]),
     "adypt_camera_matrices": (None, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "adypt_sobol_points": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),

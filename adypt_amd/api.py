@@ -286,10 +286,45 @@ def _skin_arrays(who: str, joints, weights) -> Tuple[np.ndarray, np.ndarray]:
     return j, w
 
 
-def pose_triangles(triangles: np.ndarray, matrices, parts=None, joints=None, weights=None) -> np.ndarray:
+def _morph_arrays(who: str, triangles, targets, deltas) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(int32 [n], int32 [n], float32 [n, 18]) of a morph layer's entries; deltas given as [n, 18] or [n, 2, 3, 3] (positions, normals) or flat"""
+    t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1)
+    k = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+    d = np.ascontiguousarray(deltas, dtype=np.float32)
+    if d.size != 18 * len(t) or len(k) != len(t):
+        raise ValueError("%s: an entry is a triangle, a target and 18 deltas" % who)
+    return t, k, d.reshape(-1, 18)
+
+
+def _morph_weights(morph_weights) -> np.ndarray:
+    return np.ascontiguousarray(morph_weights, dtype=np.float32).reshape(-1)
+
+
+def morph_diff(rest_triangles: np.ndarray, target_triangles: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """adypt_morph_diff: a dense target mesh as sparse morph entries.  (triangles int32 [k], deltas float32 [k, 18]) of the triangles whose positions
+    or normals differ in any bit between two arrays of 100-byte triangles of equal count; deltas = target - rest in float32.  A weight of 1 gives
+    rest + (target - rest): the target only up to one rounding."""
+    a = np.ascontiguousarray(rest_triangles).view(np.uint8).reshape(-1)
+    b = np.ascontiguousarray(target_triangles).view(np.uint8).reshape(-1)
+    if len(a) != len(b) or len(a) % 100:
+        raise ValueError("morph_diff: two arrays of 100-byte triangles of equal count")
+    n = len(a) // 100
+    k = N.lib.adypt_morph_diff(a.ctypes.data, b.ctypes.data, n, None, None)
+    if k < 0:
+        N.check_host(int(k))
+    tri, d = np.empty(k, dtype=np.int32), np.empty((k, 18), dtype=np.float32)
+    N.lib.adypt_morph_diff(a.ctypes.data, b.ctypes.data, n, tri.ctypes.data, d.ctypes.data)
+    return tri, d
+
+
+def pose_triangles(triangles: np.ndarray, matrices, parts=None, joints=None, weights=None, morph=None, morph_weights=None) -> np.ndarray:
     """adypt_pose_triangles, the host's side of Pose() (csrc/device/pose.hpp): the 100-byte triangles (uint8 [n * 100], or TRI_DT records) posed by
     row-major 3x4 matrices — by `parts` (one index per triangle) or by `joints` and `weights` (four per vertex: [n, 3, 4]).  Returns uint8 [n * 100];
-    texture coordinates and material ids stay.  What BindParts / BindSkin / Pose refuse raises AdyptError here."""
+    texture coordinates and material ids stay.  What BindParts / BindSkin / Pose refuse raises AdyptError here.
+    morph: the (triangles, targets, deltas) triple of BindMorph(), applied under morph_weights (one per target) before the matrices
+    (adypt_pose_triangles_morph): the host's side of Pose(..., morph_weights=...)."""
+    if (morph is None) != (morph_weights is None):
+        raise ValueError("pose_triangles: morph and morph_weights go together")
     t = np.ascontiguousarray(triangles).view(np.uint8).reshape(-1)
     m = _pose_matrices("pose_triangles", matrices)
     p = None if parts is None else np.ascontiguousarray(parts, dtype=np.int32).reshape(-1)
@@ -299,8 +334,13 @@ def pose_triangles(triangles: np.ndarray, matrices, parts=None, joints=None, wei
         if a is not None and len(a) != n:
             raise ValueError("pose_triangles: the binding is not of %d triangles" % n)
     out = np.empty_like(t)
-    N.check_host(N.lib.adypt_pose_triangles(t.ctypes.data, n, None if p is None else p.ctypes.data, None if j is None else j.ctypes.data,
-                                            None if w is None else w.ctypes.data, m.ctypes.data, len(m), out.ctypes.data))
+    binding = (None if p is None else p.ctypes.data, None if j is None else j.ctypes.data, None if w is None else w.ctypes.data, m.ctypes.data, len(m))
+    if morph is None:
+        N.check_host(N.lib.adypt_pose_triangles(t.ctypes.data, n, *binding, out.ctypes.data))
+        return out
+    mt, mk, md = _morph_arrays("pose_triangles", *morph)
+    mw = _morph_weights(morph_weights)
+    N.check_host(N.lib.adypt_pose_triangles_morph(t.ctypes.data, n, *binding, mt.ctypes.data, mk.ctypes.data, md.ctypes.data, len(mt), mw.ctypes.data, len(mw), out.ctypes.data))
     return out
 
 
@@ -759,16 +799,42 @@ class _Tracer:
         self._call("bind_skin", j.ctypes.data, w.ctypes.data, len(j), int(n_joints))
 
     def Pose(self, matrices: np.ndarray, rebuild_above: Optional[float] = None, method: str = "ploc", radius: int = 8, split_budget: float = 0.0,
-             cfg: Optional[N.BvhParams] = None) -> Optional[dict]:
+             cfg: Optional[N.BvhParams] = None, *, morph_weights=None) -> Optional[dict]:
         """The bound triangles under row-major 3x4 matrices (float32 [n_parts or n_joints, 3, 4]: [r][0..2] linear, [r][3] translation), always from
         the rest pose: positions, and normals through the cofactor matrix, are written into the device's records by one kernel, then the tree is
         refitted as UpdateTriangles() refits it — only the matrices cross the bus.  pose_triangles() is the same arithmetic on the host, bit for
-        bit.  rebuild_above and the arguments after it, and what is returned: as for UpdateTriangles()."""
+        bit.  rebuild_above and the arguments after it, and what is returned: as for UpdateTriangles().
+        morph_weights (adypt_pose_morph): one weight per target of the layer BindMorph() bound, applied to the rest pose before the matrices; None
+        is every weight 0, which gives the bytes of a binding without a layer."""
         m = _pose_matrices("Pose", matrices)
+        name, args = "pose", (m.ctypes.data, len(m))
+        if morph_weights is not None:
+            w = _morph_weights(morph_weights)
+            name, args = "pose_morph", args + (w.ctypes.data, len(w))
         if rebuild_above is None:
-            self._call("pose", m.ctypes.data, len(m), None, None, None)
+            self._call(name, *args, None, None, None)
             return None
-        return self._under_policy("Pose", "pose", (m.ctypes.data, len(m)), rebuild_above, cfg, method, radius, split_budget)
+        return self._under_policy("Pose", name, args, rebuild_above, cfg, method, radius, split_budget)
+
+    def BindMorph(self, triangles: np.ndarray, targets: np.ndarray, deltas: np.ndarray, n_targets: Optional[int] = None) -> None:
+        """Adds a morph layer (blend shapes) to the EXISTING BindParts() / BindSkin() binding: entry e moves triangle triangles[e] by deltas[e]
+        ([n, 18] or [n, 2, 3, 3]: the deltas of p0 p1 p2, then of n0 n1 n2) times the weight of target targets[e] (n_targets None: the largest
+        index + 1).  Entries in any order, at most one per (triangle, target); morph_diff() makes them from a target mesh.  Replaces an earlier
+        layer; nothing changes when the call is refused.  BindParts(), BindSkin(), UnbindPose() and SetTriangles() drop the layer; rebuilds keep it."""
+        t, k, d = _morph_arrays("BindMorph", triangles, targets, deltas)
+        if n_targets is None:
+            n_targets = int(k.max()) + 1 if len(k) else 0
+        self._call("bind_morph", t.ctypes.data, k.ctypes.data, d.ctypes.data, len(t), int(n_targets))
+
+    def UnbindMorph(self) -> None:
+        """Gives the morph layer back; the rest pose and the matrix binding stay."""
+        self._call("unbind_morph")
+
+    def GetMorphBinding(self) -> dict:
+        """n_targets (0: no layer), n_entries, n_tris_touched and device_bytes of the morph layer of the (first) device."""
+        out = N.MorphBinding()
+        self._call("get_morph_binding", C.byref(out))
+        return out.as_dict()
 
     def UnbindPose(self) -> None:
         """Gives the rest pose and the binding back; the triangles stay as the last Pose() left them."""

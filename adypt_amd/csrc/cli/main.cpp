@@ -5,7 +5,7 @@
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
 //             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C]
-//             [--history-out len.exr] [--follow-motion]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
+//             [--history-out len.exr] [--follow-motion]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
 //   --build gpu: no .bvh cache is read or written and no tree is built on the host: the context is created from the triangles alone
 //              (adypt_create_multi_from_triangles) and its first tree built on the GPU by --rebuild-method (ploc unless given), --ploc-radius and
 //              --split-budget, which then name that build (and, with --rebuild-above, the policy's rebuild) instead of asking for a rebuild; one
@@ -16,6 +16,12 @@
 //              triangles without a material (id -1) are one extra last part.  FILE holds lines `part m00 m01 m02 m03 m10 ... m23` (a row-major 3x4
 //              matrix: three linear entries and the translation per row; # starts a comment); parts that are not listed stay where they are.  One
 //              [PT]POSE: line reports it.  --rebuild-above and the options that name its rebuild work as after --pose; together with --pose: exit 2
+//   --morph-target FILE.obj (repeatable) with --morph-weights w0,w1,...: blend shapes on the GPU.  Target k is the k-th FILE given — the scene's
+//              triangles in the same order, moved — and is diffed against the scene as loaded (adypt_morph_diff); the entries are bound as one layer on
+//              the parts binding of --part-matrices (parts by material id; without --part-matrices every matrix is the identity) and posed once with
+//              the weights (adypt_multi_bind_morph, adypt_multi_pose_morph).  One [PT]MORPH: line reports targets, entries and triangles touched.
+//              --rebuild-above works as after --part-matrices.  One option without the other, a weight count other than the target count, or either
+//              together with --pose: exit 2
 //   --rebuild: a new tree for the triangles as they are then (after --pose, when given), built on the GPU through adypt_multi_rebuild_bvh with the config's
 //              SAH costs
 //   --rebuild-method ploc: the same with the binary tree built by PLOC (adypt_multi_rebuild_bvh_ploc; --ploc-radius R, 1 to 32, 8 unless given) — a tighter
@@ -73,6 +79,9 @@ int main(int argc, char **argv)
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
 	std::string noise_out, spp_out, denoise_out, guides_out, pose, part_matrices;
+	std::vector<std::string> morph_targets;
+	std::vector<float> morph_weights;
+	bool have_morph_weights = false;
 	bool rebuild = false, bare_rebuild = false, have_rebuild_above = false;
 	double rebuild_above = 0.0;
 	std::string rebuild_method = "linear";
@@ -137,6 +146,21 @@ int main(int argc, char **argv)
 		else if(a == "--guides-out" && i + 1 < argc) guides_out = argv[++i];
 		else if(a == "--pose" && i + 1 < argc) pose = argv[++i];
 		else if(a == "--part-matrices" && i + 1 < argc) part_matrices = argv[++i];
+		else if(a == "--morph-target" && i + 1 < argc) morph_targets.push_back(argv[++i]);
+		else if(a == "--morph-weights" && i + 1 < argc)
+		{
+			have_morph_weights = true;
+			morph_weights.clear();
+			for(const char *q = argv[++i];;)
+			{
+				char *end;
+				const float v = strtof(q, &end);
+				if(end == q || (*end && *end != ',')) { fprintf(stderr, "bad --morph-weights list %s\n", argv[i]); return 2; }
+				morph_weights.push_back(v);
+				if(!*end) break;
+				q = end + 1;
+			}
+		}
 		else if(a == "--rebuild") rebuild = bare_rebuild = true;
 		else if(a == "--rebuild-above" && i + 1 < argc)
 		{
@@ -162,7 +186,11 @@ int main(int argc, char **argv)
 	if(rebuild_method != "linear" && rebuild_method != "ploc") { fprintf(stderr, "--rebuild-method is linear or ploc\n"); return 2; }
 	if(have_split_budget && rebuild_method != "ploc") { fprintf(stderr, "--split-budget needs --rebuild-method ploc\n"); return 2; }
 	if(!pose.empty() && !part_matrices.empty()) { fprintf(stderr, "--pose and --part-matrices are two ways to move the scene: give one\n"); return 2; }
-	if(have_rebuild_above && pose.empty() && part_matrices.empty()) { fprintf(stderr, "--rebuild-above needs --pose moved.obj or --part-matrices FILE\n"); return 2; }
+	const bool morphing = !morph_targets.empty();
+	if(morphing != have_morph_weights) { fprintf(stderr, "--morph-target FILE.obj and --morph-weights w0,w1,... go together\n"); return 2; }
+	if(morphing && morph_weights.size() != morph_targets.size()) { fprintf(stderr, "--morph-weights has %d weights for %d --morph-target\n", (int)morph_weights.size(), (int)morph_targets.size()); return 2; }
+	if(morphing && !pose.empty()) { fprintf(stderr, "--morph-target morphs the scene as loaded: not together with --pose\n"); return 2; }
+	if(have_rebuild_above && pose.empty() && part_matrices.empty() && !morphing) { fprintf(stderr, "--rebuild-above needs --pose moved.obj, --part-matrices FILE or --morph-target\n"); return 2; }
 	if(have_rebuild_above && bare_rebuild) { fprintf(stderr, "--rebuild-above decides about the rebuild itself: name its method with --rebuild-method, without --rebuild\n"); return 2; }
 	if(have_rebuild_above || build_on_gpu) rebuild = false; // (--rebuild-method names the policy's rebuild, or the first build)
 	// the tree that --rebuild-method, --ploc-radius and --split-budget name: the first build of --build gpu, the policy's rebuild, or the rebuild asked for
@@ -223,7 +251,7 @@ int main(int argc, char **argv)
 	std::vector<int32_t> part_of_triangle; // --part-matrices: the binding and one matrix per part, the identity where FILE names none
 	std::vector<float> part_matrix;
 	int32_t n_parts = 0;
-	if(!part_matrices.empty())
+	if(!part_matrices.empty() || morphing)
 	{
 		part_of_triangle.resize((size_t)n_tris);
 		bool loose = false;
@@ -238,10 +266,10 @@ int main(int argc, char **argv)
 		n_parts = (int32_t)n_mats + (loose ? 1 : 0);
 		for(int32_t k = 0; k < n_parts; ++k)
 			for(int j = 0; j < 12; ++j) part_matrix.push_back(j % 5 == 0 ? 1.0f : 0.0f);
-		FILE *f = fopen(part_matrices.c_str(), "r");
-		if(!f) { fprintf(stderr, "[INSTANCE]Err: Unable to open %s\n", part_matrices.c_str()); return 1; }
+		FILE *f = part_matrices.empty() ? nullptr : fopen(part_matrices.c_str(), "r");
+		if(!f && !part_matrices.empty()) { fprintf(stderr, "[INSTANCE]Err: Unable to open %s\n", part_matrices.c_str()); return 1; }
 		char line[1024];
-		for(int at = 1; fgets(line, sizeof(line), f); ++at)
+		for(int at = 1; f && fgets(line, sizeof(line), f); ++at)
 		{
 			if(char *hash = strchr(line, '#')) *hash = 0;
 			long part;
@@ -257,7 +285,26 @@ int main(int argc, char **argv)
 			}
 			memcpy(&part_matrix[(size_t)part * 12], m, sizeof(m));
 		}
-		fclose(f);
+		if(f) fclose(f);
+	}
+
+	std::vector<int32_t> morph_triangle, morph_target; // --morph-target: the entries of all targets, each diffed against the scene as loaded
+	std::vector<float> morph_deltas;
+	for(size_t k = 0; k < morph_targets.size(); ++k)
+	{
+		adypt_scene *target = nullptr;
+		if(adypt_scene_load(morph_targets[k].c_str(), &target) != ADYPT_OK) { fprintf(stderr, "[INSTANCE]Err: Unable to load morph target %s: %s\n", morph_targets[k].c_str(), adypt_host_last_error()); return 1; }
+		const void *tt;
+		const int64_t n_target = adypt_scene_triangles(target, &tt);
+		if(n_target != n_tris) { fprintf(stderr, "[INSTANCE]Err: morph target %s has %lld triangles, the scene has %lld\n", morph_targets[k].c_str(), (long long)n_target, (long long)n_tris); return 1; }
+		const int64_t count = adypt_morph_diff(tris, tt, n_tris, nullptr, nullptr);
+		if(count < 0) { fprintf(stderr, "[INSTANCE]Err: %s\n", adypt_host_last_error()); return 1; }
+		const size_t at = morph_triangle.size();
+		morph_triangle.resize(at + (size_t)count);
+		morph_deltas.resize((at + (size_t)count) * 18);
+		morph_target.resize(at + (size_t)count, (int32_t)k);
+		(void)adypt_morph_diff(tris, tt, n_tris, morph_triangle.data() + at, morph_deltas.data() + at * 18);
+		adypt_scene_free(target);
 	}
 
 	adypt_bvh *bvh = nullptr;
@@ -335,15 +382,23 @@ int main(int argc, char **argv)
 			printf("[PT]INFO: pose policy: tree cost %.4f -> %.4f (ratio %.4f, allowed %g): %s\n", outcome.built.cost, outcome.refitted.cost, outcome.refitted.cost / outcome.built.cost, rebuild_above,
 			       outcome.rebuilt ? ("rebuilt (" + rebuild_figures(outcome.rebuild) + ")").c_str() : "kept");
 	}
-	if(!part_matrices.empty())
+	if(!part_matrices.empty() || morphing)
 	{
 		adypt_pose_outcome outcome;
+		adypt_morph_binding layer;
+		memset(&layer, 0, sizeof(layer));
 		int code = adypt_multi_bind_parts(multi, part_of_triangle.data(), n_tris, n_parts);
-		if(code == ADYPT_OK) code = adypt_multi_pose(multi, part_matrix.data(), n_parts, &cfg.bvh, have_rebuild_above ? &policy : nullptr, &outcome);
+		if(code == ADYPT_OK && morphing) code = adypt_multi_bind_morph(multi, morph_triangle.data(), morph_target.data(), morph_deltas.data(), (int64_t)morph_triangle.size(), (int32_t)morph_targets.size());
+		if(code == ADYPT_OK && morphing) code = adypt_multi_get_morph_binding(multi, &layer);
+		if(code == ADYPT_OK)
+			code = morphing ? adypt_multi_pose_morph(multi, part_matrix.data(), n_parts, morph_weights.data(), (int32_t)morph_weights.size(), &cfg.bvh, have_rebuild_above ? &policy : nullptr, &outcome)
+			                : adypt_multi_pose(multi, part_matrix.data(), n_parts, &cfg.bvh, have_rebuild_above ? &policy : nullptr, &outcome);
 		if(code != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return false; }
 		float ms[4] = {0, 0, 0, 0};
 		(void)adypt_get_refit_timing(adypt_multi_context(multi, 0), ms, 4);
-		printf("[PT]POSE: parts %d triangles %lld from %s, refit %.3f ms (matrices and pose %.3f, references and Woop %.3f, nodes %.3f)\n", (int)n_parts, (long long)n_tris, part_matrices.c_str(), ms[3],
+		if(morphing) printf("[PT]MORPH: targets %d entries %lld triangles %lld of %lld\n", (int)layer.n_targets, (long long)layer.n_entries, (long long)layer.n_tris_touched, (long long)n_tris);
+		if(part_matrices.empty()) printf("[PT]INFO: morph pose: refit %.3f ms (weights, matrices and pose %.3f, references and Woop %.3f, nodes %.3f)\n", ms[3], ms[0], ms[1], ms[2]);
+		else printf("[PT]POSE: parts %d triangles %lld from %s, refit %.3f ms (matrices and pose %.3f, references and Woop %.3f, nodes %.3f)\n", (int)n_parts, (long long)n_tris, part_matrices.c_str(), ms[3],
 		       ms[0], ms[1], ms[2]);
 		if(have_rebuild_above)
 			printf("[PT]INFO: pose policy: tree cost %.4f -> %.4f (ratio %.4f, allowed %g): %s\n", outcome.built.cost, outcome.refitted.cost, outcome.refitted.cost / outcome.built.cost, rebuild_above,

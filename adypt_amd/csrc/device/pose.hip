@@ -9,7 +9,10 @@
 //                        neighbouring lanes neighbouring addresses; a matrix is three 16-byte loads from an array that stays in the caches.  The record
 //                        is written as adypt_update_triangles' k_refit_scatter writes it: four 16-byte stores and one of 8 bytes for words 16 and 17,
 //                        which share their 16 bytes with the material id and the class word.  Every array of a lane is indexed by constants after
-//                        unrolling: registers, no scratch.
+//                        unrolling: registers, no scratch.  With a morph layer (adypt_bind_morph) the MORPHED instantiations put the morph stage
+//                        between the rest pose's loads and the matrices: a lane reads its two offsets and loops over its entries, which the bind has
+//                        sorted by (triangle, target); per entry the target index and the weight, and the 72 bytes of deltas — planes like the rest
+//                        pose's — only where the weight is not 0.  The weights (4 B per target) are staged beside the matrices.
 //     (refit.hip)        the refit's tail, refit_tail: per-reference copy, Woop data, node levels, root card, reset
 #include "ctx_unit.hpp"
 #include "pose.hpp"
@@ -50,16 +53,45 @@ __device__ __forceinline__ void load_matrix(const float4 *__restrict__ mats, uin
 
 // parts: n part indices (SKINNED: unused); joints, weights: three planes of n — vertex v's four joints as 16-bit halves of a uint2, its four weights as
 // a float4 (!SKINNED: unused); mats: n_matrices x 3 float4.  Every index has been checked on the host (pose.hpp, pose_refuse_*).
-template <bool SKINNED> __global__ __launch_bounds__(kPoseThreads) void k_pose(float4 *records, int tri_float4, int64_t n, const float4 *__restrict__ rest4, const float2 *__restrict__ rest2,
-                                                                               const int32_t *__restrict__ parts, const uint2 *__restrict__ joints, const float4 *__restrict__ weights,
-                                                                               const float4 *__restrict__ mats)
+// The morph layer as the kernel reads it (MORPHED; otherwise unused): offsets — n + 1 places into the entries, which are sorted by (triangle, target);
+// target — the entry's target index; d4, d2 — the entry's 18 deltas in four float4 planes and one float2 plane of n_entries; w — one weight per target.
+struct MorphView {
+	const int32_t *__restrict__ offsets;
+	const int32_t *__restrict__ target;
+	const float4 *__restrict__ d4;
+	const float2 *__restrict__ d2;
+	const float *__restrict__ w;
+	int64_t n_entries;
+};
+
+template <bool SKINNED, bool MORPHED>
+__global__ __launch_bounds__(kPoseThreads) void k_pose(float4 *records, int tri_float4, int64_t n, const float4 *__restrict__ rest4, const float2 *__restrict__ rest2,
+                                                       const int32_t *__restrict__ parts, const uint2 *__restrict__ joints, const float4 *__restrict__ weights,
+                                                       const float4 *__restrict__ mats, const MorphView morph)
 {
 	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if(i >= n) return;
 	const size_t at = (size_t)i, plane = (size_t)n;
 	const float4 a = rest4[at], b = rest4[plane + at], c = rest4[2 * plane + at], d = rest4[3 * plane + at];
 	const float2 e = rest2[at];
-	const float in[18] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w, e.x, e.y};
+	float in[18] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w, e.x, e.y};
+	if(MORPHED)
+	{
+		// the lane's entries in ascending target index: a variable trip count; the index and the weight first, the 72 bytes of deltas only where the
+		// weight is not 0.  `in` is indexed by constants only (pose_morph unrolls): registers
+		const size_t eplane = (size_t)morph.n_entries;
+		const int32_t end = morph.offsets[at + 1];
+		for(int32_t k = morph.offsets[at]; k < end; ++k)
+		{
+			const float w = morph.w[(uint32_t)morph.target[k]];
+			if(w == 0.0f) continue;
+			const size_t ek = (size_t)k;
+			const float4 da = morph.d4[ek], db = morph.d4[eplane + ek], dc = morph.d4[2 * eplane + ek], dd = morph.d4[3 * eplane + ek];
+			const float2 de = morph.d2[ek];
+			const float delta[kMorphWords] = {da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w, dc.x, dc.y, dc.z, dc.w, dd.x, dd.y, dd.z, dd.w, de.x, de.y};
+			pose_morph(in, w, delta);
+		}
+	}
 	float out[18];
 	float M[kPoseMatrixFloats];
 	if(!SKINNED) load_matrix(mats, (uint32_t)parts[at], M);
@@ -95,10 +127,24 @@ template <bool SKINNED> __global__ __launch_bounds__(kPoseThreads) void k_pose(f
 	((float2 *)rec)[8] = make_float2(out[16], out[17]); // (words 18, 19 — material id, class word — share this vector and keep their bytes)
 }
 
+// what adypt_bind_morph leaves on the device, the entries sorted by (triangle, target)
+struct Layer {
+	int32_t n_targets = 0;
+	int64_t n_entries = 0, n_tris_touched = 0;
+	Buffer<float4> d4;        // 4 planes of n_entries: 64 B per entry
+	Buffer<float2> d2;        // 8 B per entry
+	Buffer<int32_t> target;   // 4 B per entry
+	Buffer<int32_t> offsets;  // n_tris + 1
+	Buffer<float> w;          // the staging buffer of the weights: 4 B per target
+	int64_t device_bytes() const { return (int64_t)(d4.bytes() + d2.bytes() + target.bytes() + offsets.bytes() + w.bytes()); }
+	MorphView view() const { return MorphView{offsets.get(), target.get(), d4.get(), d2.get(), w.get(), n_entries}; }
+};
+
 // what a bind leaves on the device
 struct Binding {
 	int32_t kind = kPoseNone, n_matrices = 0;
 	int64_t n_tris = 0;
+	Layer layer;              // goes with the binding: its deltas are of this rest pose
 	Buffer<float4> rest4;     // 4 planes of n_tris: 64 B per triangle
 	Buffer<float2> rest2;     // 8 B per triangle
 	Buffer<int32_t> parts;    // parts: 4 B per triangle
@@ -159,18 +205,25 @@ int bind(adypt_ctx *c, const char *who, int32_t kind, const int32_t *parts, cons
 }
 
 // the refit whose writer is k_pose
-int pose_and_refit(adypt_ctx *c, const Binding &b, const float *matrices)
+template <bool SKINNED, bool MORPHED> void launch_pose(const CtxInfo &i, const CtxScene &sc, const Binding &b)
+{
+	hipLaunchKernelGGL((k_pose<SKINNED, MORPHED>), dim3(grid_of(b.n_tris, kPoseThreads)), dim3(kPoseThreads), 0, i.stream, sc.triangles, sc.tri_float4, b.n_tris,
+	                   (const float4 *)b.rest4.get(), (const float2 *)b.rest2.get(), (const int32_t *)b.parts.get(), (const uint2 *)b.joints.get(), (const float4 *)b.weights.get(),
+	                   (const float4 *)b.mats.get(), b.layer.view());
+}
+
+// the refit whose writer is k_pose; morph_weights: the layer's n_targets weights, or null for all 0 (looked at only where there is a layer)
+int pose_and_refit(adypt_ctx *c, const Binding &b, const float *matrices, const float *morph_weights)
 {
 	CTX_STEP(refit_begin(c));
 	const CtxInfo i = ctx_info(c);
 	const CtxScene sc = ctx_scene(c);
+	const bool morphed = b.layer.n_targets > 0, skinned = b.kind == kPoseSkin;
 	CTX_TRY(c, hipMemcpyAsync(b.mats.get(), matrices, (size_t)b.n_matrices * kPoseMatrixFloats * sizeof(float), hipMemcpyHostToDevice, i.stream));
-	if(b.kind == kPoseSkin)
-		hipLaunchKernelGGL(k_pose<true>, dim3(grid_of(b.n_tris, kPoseThreads)), dim3(kPoseThreads), 0, i.stream, sc.triangles, sc.tri_float4, b.n_tris, (const float4 *)b.rest4.get(),
-		                   (const float2 *)b.rest2.get(), (const int32_t *)nullptr, (const uint2 *)b.joints.get(), (const float4 *)b.weights.get(), (const float4 *)b.mats.get());
-	else
-		hipLaunchKernelGGL(k_pose<false>, dim3(grid_of(b.n_tris, kPoseThreads)), dim3(kPoseThreads), 0, i.stream, sc.triangles, sc.tri_float4, b.n_tris, (const float4 *)b.rest4.get(),
-		                   (const float2 *)b.rest2.get(), (const int32_t *)b.parts.get(), (const uint2 *)nullptr, (const float4 *)nullptr, (const float4 *)b.mats.get());
+	if(morphed && morph_weights) CTX_TRY(c, hipMemcpyAsync(b.layer.w.get(), morph_weights, (size_t)b.layer.n_targets * sizeof(float), hipMemcpyHostToDevice, i.stream));
+	if(morphed && !morph_weights) CTX_TRY(c, hipMemsetAsync(b.layer.w.get(), 0, (size_t)b.layer.n_targets * sizeof(float), i.stream));
+	if(morphed) skinned ? launch_pose<true, true>(i, sc, b) : launch_pose<false, true>(i, sc, b);
+	else skinned ? launch_pose<true, false>(i, sc, b) : launch_pose<false, false>(i, sc, b);
 	CTX_TRY(c, hipGetLastError());
 	return refit_tail(c);
 }
@@ -184,6 +237,33 @@ std::string bind_refused(adypt_ctx *c, const char *who, bool have_arrays, int64_
 	if(n_tris != have) return w + "n_tris is " + std::to_string(n_tris) + ", the context holds " + std::to_string(have) + " triangles";
 	if(pose_refuse_count(n_matrices)) return w + "the number of " + what + " must be in [1, 65536]";
 	return std::string();
+}
+
+// adypt_pose and adypt_pose_morph: morph_weights null with n_targets 0 is every weight 0
+int pose(adypt_ctx *c, const char *who, const float *matrices, int32_t n_matrices, const float *morph_weights, int32_t n_targets, const adypt_bvh_params *params,
+         const adypt_pose_policy *policy, adypt_pose_outcome *outcome)
+{
+	if(!c) return ADYPT_E_INVALID;
+	if(!matrices) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": matrices is null");
+	if(!morph_weights && n_targets != 0) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": morph_weights is null");
+	const Poser *ps = ctx_state_if_any<Poser>(c, kAttachPose);
+	if(!ps || ps->bound.kind == kPoseNone) return ctx_fail(c, ADYPT_E_STATE, std::string(who) + ": no binding (adypt_bind_parts, adypt_bind_skin; adypt_set_triangles drops it)");
+	const Binding &b = ps->bound;
+	if(b.n_tris != ctx_scene(c).n_tris) return ctx_fail(c, ADYPT_E_STATE, std::string(who) + ": the binding is not of the context's triangles");
+	if(n_matrices != b.n_matrices) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": n_matrices is " + std::to_string(n_matrices) + ", the binding has " + std::to_string(b.n_matrices));
+	if(const char *r = pose_refuse_matrices(matrices, n_matrices)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": " + r);
+	if(morph_weights || n_targets != 0)
+		if(const char *r = pose_refuse_morph_weights(morph_weights, n_targets, b.layer.n_targets)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": " + r);
+	if(!policy)
+	{
+		CTX_TRY(c, hipSetDevice(ctx_info(c).device));
+		CTX_STEP(pose_and_refit(c, b, matrices, morph_weights));
+		if(outcome) *outcome = adypt_pose_outcome{};
+		return ADYPT_OK;
+	}
+	BuildRequest request;
+	if(const char *why = refit_policy_refused(params, policy, &request)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": " + why);
+	return refit_under_policy(c, who, request, policy->rebuild_above, outcome, [&]() { return pose_and_refit(c, b, matrices, morph_weights); });
 }
 
 }  // namespace
@@ -224,25 +304,113 @@ int adypt_bind_skin(adypt_ctx *c, const uint16_t *joints, const float *weights, 
 
 int adypt_pose(adypt_ctx *c, const float *matrices, int32_t n_matrices, const adypt_bvh_params *params, const adypt_pose_policy *policy, adypt_pose_outcome *outcome)
 {
+	return pose(c, "adypt_pose", matrices, n_matrices, nullptr, 0, params, policy, outcome);
+}
+
+int adypt_pose_morph(adypt_ctx *c, const float *matrices, int32_t n_matrices, const float *morph_weights, int32_t n_targets, const adypt_bvh_params *params,
+                     const adypt_pose_policy *policy, adypt_pose_outcome *outcome)
+{
+	return pose(c, "adypt_pose_morph", matrices, n_matrices, morph_weights, n_targets, params, policy, outcome);
+}
+
+int adypt_bind_morph(adypt_ctx *c, const int32_t *triangle_of_entry, const int32_t *target_of_entry, const float *deltas, int64_t n_entries, int32_t n_targets)
+{
 	if(!c) return ADYPT_E_INVALID;
-	const char *who = "adypt_pose";
-	if(!matrices) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": matrices is null");
-	const Poser *ps = ctx_state_if_any<Poser>(c, kAttachPose);
-	if(!ps || ps->bound.kind == kPoseNone) return ctx_fail(c, ADYPT_E_STATE, std::string(who) + ": no binding (adypt_bind_parts, adypt_bind_skin; adypt_set_triangles drops it)");
-	const Binding &b = ps->bound;
-	if(b.n_tris != ctx_scene(c).n_tris) return ctx_fail(c, ADYPT_E_STATE, std::string(who) + ": the binding is not of the context's triangles");
-	if(n_matrices != b.n_matrices) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": n_matrices is " + std::to_string(n_matrices) + ", the binding has " + std::to_string(b.n_matrices));
-	if(const char *r = pose_refuse_matrices(matrices, n_matrices)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": " + r);
-	if(!policy)
+	const std::string who = "adypt_bind_morph: ";
+	if(!triangle_of_entry || !target_of_entry || !deltas) return ctx_fail(c, ADYPT_E_INVALID, who + "null argument");
+	Poser *ps = ctx_state_if_any<Poser>(c, kAttachPose);
+	if(!ps || ps->bound.kind == kPoseNone || ps->bound.n_tris != ctx_scene(c).n_tris)
+		return ctx_fail(c, ADYPT_E_STATE, who + "no binding to add the layer to (adypt_bind_parts, adypt_bind_skin)");
+	const int64_t n = ps->bound.n_tris;
+	std::vector<int32_t> order, offsets;
+	const char *r = pose_refuse_morph_counts(n_entries, n_targets);
+	if(!r) r = pose_refuse_morph_entries(triangle_of_entry, target_of_entry, deltas, n_entries, n, n_targets);
+	if(!r) r = pose_morph_order(triangle_of_entry, target_of_entry, n_entries, n, order, offsets);
+	if(r) return ctx_fail(c, ADYPT_E_INVALID, who + r);
+	// the entries in their order, in planes
+	const size_t ne = (size_t)n_entries;
+	std::vector<float4> h_d4(ne * kRestPlanes);
+	std::vector<float2> h_d2(ne);
+	std::vector<int32_t> h_target(ne);
+	for(size_t k = 0; k < ne; ++k)
 	{
-		CTX_TRY(c, hipSetDevice(ctx_info(c).device));
-		CTX_STEP(pose_and_refit(c, b, matrices));
-		if(outcome) *outcome = adypt_pose_outcome{};
-		return ADYPT_OK;
+		const float *d = deltas + (size_t)order[k] * kMorphWords;
+		for(int q = 0; q < kRestPlanes; ++q) h_d4[(size_t)q * ne + k] = make_float4(d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]);
+		h_d2[k] = make_float2(d[16], d[17]);
+		h_target[k] = target_of_entry[order[k]];
 	}
-	BuildRequest request;
-	if(const char *why = refit_policy_refused(params, policy, &request)) return ctx_fail(c, ADYPT_E_INVALID, std::string(who) + ": " + why);
-	return refit_under_policy(c, who, request, policy->rebuild_above, outcome, [&]() { return pose_and_refit(c, b, matrices); });
+	const CtxInfo i = ctx_info(c);
+	CTX_TRY(c, hipSetDevice(i.device));
+	CTX_STEP(ctx_drain(c));
+	Layer nl;
+	nl.n_targets = n_targets; nl.n_entries = n_entries;
+	for(int64_t t = 0; t < n; ++t) nl.n_tris_touched += offsets[(size_t)t + 1] > offsets[(size_t)t];
+	CTX_TRY(c, at_least(nl.d4, h_d4.size()));
+	CTX_TRY(c, at_least(nl.d2, ne));
+	CTX_TRY(c, at_least(nl.target, ne));
+	CTX_TRY(c, at_least(nl.offsets, offsets.size()));
+	CTX_TRY(c, at_least(nl.w, (size_t)n_targets));
+	CTX_TRY(c, hipMemcpyAsync(nl.d4.get(), h_d4.data(), h_d4.size() * sizeof(float4), hipMemcpyHostToDevice, i.stream));
+	CTX_TRY(c, hipMemcpyAsync(nl.d2.get(), h_d2.data(), ne * sizeof(float2), hipMemcpyHostToDevice, i.stream));
+	CTX_TRY(c, hipMemcpyAsync(nl.target.get(), h_target.data(), ne * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
+	CTX_TRY(c, hipMemcpyAsync(nl.offsets.get(), offsets.data(), offsets.size() * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
+	CTX_TRY(c, hipStreamSynchronize(i.stream));
+	ps->bound.layer = std::move(nl); // (complete: the old layer's memory goes with `nl`)
+	return ADYPT_OK;
+}
+
+int adypt_unbind_morph(adypt_ctx *c)
+{
+	if(!c) return ADYPT_E_INVALID;
+	CTX_TRY(c, hipSetDevice(ctx_info(c).device));
+	CTX_STEP(ctx_drain(c));
+	Poser *ps = ctx_state_if_any<Poser>(c, kAttachPose);
+	if(ps) ps->bound.layer = Layer();
+	return ADYPT_OK;
+}
+
+int adypt_get_morph_binding(adypt_ctx *c, adypt_morph_binding *out)
+{
+	if(!c) return ADYPT_E_INVALID;
+	if(!out) return ctx_fail(c, ADYPT_E_INVALID, "adypt_get_morph_binding: out is null");
+	const Poser *ps = ctx_state_if_any<Poser>(c, kAttachPose);
+	*out = adypt_morph_binding{};
+	if(ps && ps->bound.layer.n_targets > 0)
+	{
+		const Layer &l = ps->bound.layer;
+		out->n_targets = l.n_targets; out->n_entries = l.n_entries; out->n_tris_touched = l.n_tris_touched; out->device_bytes = l.device_bytes();
+	}
+	return ADYPT_OK;
+}
+
+int adypt_multi_bind_morph(adypt_multi *m, const int32_t *triangle_of_entry, const int32_t *target_of_entry, const float *deltas, int64_t n_entries, int32_t n_targets)
+{
+	return multi_each(m, [=](adypt_ctx *c) { return adypt_bind_morph(c, triangle_of_entry, target_of_entry, deltas, n_entries, n_targets); });
+}
+
+int adypt_multi_pose_morph(adypt_multi *m, const float *matrices, int32_t n_matrices, const float *morph_weights, int32_t n_targets, const adypt_bvh_params *params,
+                           const adypt_pose_policy *policy, adypt_pose_outcome *outcome)
+{
+	return multi_each_outcome(m, "adypt_multi_pose_morph", outcome,
+	                          [=](adypt_ctx *c, adypt_pose_outcome *o) { return adypt_pose_morph(c, matrices, n_matrices, morph_weights, n_targets, params, policy, o); });
+}
+
+int adypt_multi_unbind_morph(adypt_multi *m)
+{
+	return multi_each(m, [](adypt_ctx *c) { return adypt_unbind_morph(c); });
+}
+
+// every device holds the same layer: the first one's
+int adypt_multi_get_morph_binding(adypt_multi *m, adypt_morph_binding *out)
+{
+	if(m && !out) { multi_set_error(m, "adypt_multi_get_morph_binding: out is null"); return ADYPT_E_INVALID; }
+	int k = 0;
+	return multi_each(m, [&](adypt_ctx *c) {
+		adypt_morph_binding b{};
+		CTX_STEP(adypt_get_morph_binding(c, &b));
+		if(k++ == 0) *out = b;
+		return (int)ADYPT_OK;
+	});
 }
 
 int adypt_unbind_pose(adypt_ctx *c)

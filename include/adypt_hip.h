@@ -543,6 +543,35 @@ int adypt_pose(adypt_ctx *ctx, const float *matrices /* n_matrices x 12 */, int3
 int adypt_unbind_pose(adypt_ctx *ctx);
 int adypt_get_pose_binding(adypt_ctx *ctx, adypt_pose_binding *out);
 
+/* ---- morph targets (blend shapes): per-triangle deltas scaled by a handful of weights, in front of the matrices -------------------------------
+ * One more layer of the same pipeline: rest pose -> morph -> vertex matrix -> record (csrc/device/pose.hpp).  adypt_bind_morph adds a layer of
+ * n_targets targets (1 .. 65536) and n_entries sparse entries (1 .. 2^31 - 1) to the EXISTING parts or skin binding (without one: ADYPT_E_STATE; a
+ * figure without a skeleton binds one part and poses it with the identity).  Entry e is (triangle_of_entry[e], target_of_entry[e],
+ * deltas[18 e .. 18 e + 17]): the deltas of words 0..17 of that triangle's record, p0 p1 p2 then n0 n1 n2; adypt_morph_diff (adypt_host.h) makes them
+ * from a dense target mesh.  The entries may come in any order: a triangle's are applied in ascending target index, acc[j] = acc[j] + w * d[j], and an
+ * entry whose weight is 0 is skipped without its deltas being read.  The morphed normal is normalised only after the cofactor product.
+ * adypt_pose_morph is adypt_pose with one weight per target (finite, any sign, used as given): 4 B per target cross the bus beside the matrices.
+ * adypt_pose on a binding with a layer, and adypt_pose_morph with morph_weights NULL and n_targets 0, are the pose with every weight 0, which gives
+ * the bytes of a binding without a layer.  adypt_get_refit_timing answers afterwards, [0] covering the uploads and k_pose.
+ * adypt_read_triangle_records afterwards equals adypt_pack_triangles of adypt_pose_triangles_morph's triangles byte for byte.
+ * ADYPT_E_INVALID, checked on the host, nothing changes (a refused or failed bind leaves the old layer and the binding as they were): a null array;
+ * n_entries or n_targets out of range; a triangle or target index out of range; a delta that is not finite; two entries of one (triangle, target);
+ * at pose time a weight count other than the layer's (0 without one), a weight that is not finite, and what adypt_pose refuses.
+ * Lifetime: adypt_unbind_morph drops only the layer; adypt_bind_parts, adypt_bind_skin (a new rest pose), adypt_unbind_pose and a successful
+ * adypt_set_triangles drop it too; adypt_rebuild_bvh* keep it; adypt_update_triangles touches neither the rest pose nor the layer.
+ * Memory: 76 B per entry (72 of deltas in planes, 4 of target index), 4 B per triangle (+ 4) of offsets, 4 B per target of weights. */
+typedef struct adypt_morph_binding {
+	int32_t n_targets;           /* 0: no layer */
+	int64_t n_entries;
+	int64_t n_tris_touched;      /* triangles with at least one entry */
+	int64_t device_bytes;        /* what the layer holds on the device; not part of adypt_pose_binding's device_bytes */
+} adypt_morph_binding;
+int adypt_bind_morph(adypt_ctx *ctx, const int32_t *triangle_of_entry, const int32_t *target_of_entry, const float *deltas /* n_entries x 18 */, int64_t n_entries, int32_t n_targets);
+int adypt_pose_morph(adypt_ctx *ctx, const float *matrices /* n_matrices x 12 */, int32_t n_matrices, const float *morph_weights /* n_targets; NULL with n_targets 0: all 0 */,
+                     int32_t n_targets, const adypt_bvh_params *params, const adypt_pose_policy *policy /* NULL: refit only */, adypt_pose_outcome *outcome /* may be NULL */);
+int adypt_unbind_morph(adypt_ctx *ctx);
+int adypt_get_morph_binding(adypt_ctx *ctx, adypt_morph_binding *out);
+
 /* Trace an arbitrary batch of rays through the same traversal kernel: rays = n x 8 floats
  * (ox, oy, oz, tmin, dx, dy, dz, unused).  with_stats selects the instrumented kernel variant. */
 int adypt_trace_rays(adypt_ctx *ctx, const float *rays, int64_t n, adypt_hit *hits, int with_stats);
@@ -687,6 +716,12 @@ int adypt_multi_bind_skin(adypt_multi *m, const uint16_t *joints, const float *w
 int adypt_multi_pose(adypt_multi *m, const float *matrices, int32_t n_matrices, const adypt_bvh_params *params, const adypt_pose_policy *policy, adypt_pose_outcome *outcome);
 int adypt_multi_unbind_pose(adypt_multi *m);
 int adypt_multi_get_pose_binding(adypt_multi *m, adypt_pose_binding *out);
+/* adypt_bind_morph / adypt_pose_morph / adypt_unbind_morph on every device in the same way; adypt_multi_get_morph_binding: the first device's. */
+int adypt_multi_bind_morph(adypt_multi *m, const int32_t *triangle_of_entry, const int32_t *target_of_entry, const float *deltas, int64_t n_entries, int32_t n_targets);
+int adypt_multi_pose_morph(adypt_multi *m, const float *matrices, int32_t n_matrices, const float *morph_weights, int32_t n_targets, const adypt_bvh_params *params,
+                           const adypt_pose_policy *policy, adypt_pose_outcome *outcome);
+int adypt_multi_unbind_morph(adypt_multi *m);
+int adypt_multi_get_morph_binding(adypt_multi *m, adypt_morph_binding *out);
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

@@ -165,6 +165,19 @@ int adypt_pack_triangles(const void *triangles, int64_t n_tris, const void *mate
  * compiles too: both give the same bits.  ADYPT_E_INVALID — nothing is written — for what adypt_bind_parts / adypt_bind_skin / adypt_pose refuse. */
 int adypt_pose_triangles(const void *triangles_in, int64_t n_tris, const int32_t *parts_or_null, const uint16_t *joints_or_null, const float *weights_or_null, const float *matrices,
                          int32_t n_matrices, void *triangles_out);
+/* adypt_pose_triangles with a morph layer in front of the matrices (csrc/device/pose.hpp: rest pose -> morph -> vertex matrix): n_entries sparse
+ * entries in any order, entry e being (triangle_of_entry[e], target_of_entry[e], deltas[18 e .. 18 e + 17]) — the deltas of p0 p1 p2 n0 n1 n2 — and
+ * n_targets weights, finite and of any sign.  A triangle's entries are applied in ascending target index, acc = acc + w * d per word, an entry of
+ * weight 0 skipped: all weights 0 give adypt_pose_triangles' bytes.  The whole pipeline of adypt_bind_morph + adypt_pose_morph (adypt_hip.h) on the
+ * host, bit for bit.  ADYPT_E_INVALID — nothing is written — for what those two refuse. */
+int adypt_pose_triangles_morph(const void *triangles_in, int64_t n_tris, const int32_t *parts_or_null, const uint16_t *joints_or_null, const float *weights_or_null,
+                               const float *matrices, int32_t n_matrices, const int32_t *triangle_of_entry, const int32_t *target_of_entry, const float *deltas /* n_entries x 18 */,
+                               int64_t n_entries, const float *morph_weights /* n_targets */, int32_t n_targets, void *triangles_out);
+/* A dense target mesh as sparse morph entries: the triangles whose words 0..17 (positions, normals) differ in any bit between two arrays of n_tris
+ * 100-byte Triangles, in ascending order into triangle_out, and d = target - rest, one binary32 subtraction per word, into deltas_out (18 floats per
+ * listed triangle).  Returns their number; either output may be NULL (both NULL: the size only, at most n_tris).  Weight 1 then gives
+ * rest + (target - rest), which is the target only up to one rounding.  ADYPT_E_INVALID (negative) for a null input or a negative count. */
+int64_t adypt_morph_diff(const void *rest, const void *target, int64_t n_tris, int32_t *triangle_out, float *deltas_out);
 /* Camera::GetView/GetProjection + the inverses of SetCamera (src/Tracer/Camera.cpp:13-23, OglPathTracer.cpp:27-32) */
 void adypt_camera_matrices(float fov, float yaw, float pitch, int width, int height, float inv_proj[16], float inv_view[16]);
 /* Sobol::Next (src/Util/Sobol.cpp:16-21): points of frames [first, first+n), dim <= 64; out = n*dim floats */

@@ -323,6 +323,40 @@ public:
 	}
 	bool UnbindPose() { return adypt_multi_unbind_pose(m_gpus) == ADYPT_OK; }
 
+	// Morph targets (blend shapes) in front of the matrices (adypt_hip.h, adypt_bind_morph / adypt_pose_morph): BindMorph adds a layer of sparse
+	// entries to the binding BindParts or BindSkin made (a figure without a skeleton binds one part and poses it with the identity).  Entry e moves
+	// triangle triangle_of_entry[e] by deltas[18 e .. 18 e + 17] (the deltas of p0 p1 p2, then of n0 n1 n2) times the weight of target
+	// target_of_entry[e]; entries in any order, one per (triangle, target) at most; adypt_morph_diff (adypt_host.h) makes them from a target mesh.  A
+	// refused call leaves an earlier layer in place; BindParts, BindSkin, UnbindPose and SetTriangles drop the layer, UnbindMorph drops only it.
+	bool BindMorph(const std::vector<int32_t> &triangle_of_entry, const std::vector<int32_t> &target_of_entry, const std::vector<float> &deltas, int32_t n_targets)
+	{
+		const bool shaped = triangle_of_entry.size() == target_of_entry.size() && deltas.size() == 18 * triangle_of_entry.size();
+		if(shaped && adypt_multi_bind_morph(m_gpus, triangle_of_entry.data(), target_of_entry.data(), deltas.data(), (int64_t)triangle_of_entry.size(), n_targets) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", shaped ? adypt_multi_last_error(m_gpus) : "BindMorph: an entry is a triangle, a target and 18 deltas");
+		return false;
+	}
+	bool UnbindMorph() { return adypt_multi_unbind_morph(m_gpus) == ADYPT_OK; }
+	// Pose with one weight per target of the layer (finite, any sign): only the weights and the matrices cross the bus.  Pose(matrices) on a binding
+	// with a layer is this with every weight 0.
+	bool Pose(const std::vector<float> &matrices, const std::vector<float> &morph_weights)
+	{
+		if(matrices.size() % 12 == 0 &&
+		   adypt_multi_pose_morph(m_gpus, matrices.data(), (int32_t)(matrices.size() / 12), morph_weights.data(), (int32_t)morph_weights.size(), nullptr, nullptr, nullptr) == ADYPT_OK)
+			return true;
+		printf("[PT]ERR: %s\n", matrices.size() % 12 ? "Pose: a matrix is 12 floats" : adypt_multi_last_error(m_gpus));
+		return false;
+	}
+	bool Pose(const std::vector<float> &matrices, const std::vector<float> &morph_weights, const PosePolicy &policy, adypt_pose_outcome *outcome = nullptr,
+	          const adypt_bvh_params *params = nullptr)
+	{
+		const adypt_pose_policy p = policy.abi();
+		if(matrices.size() % 12 == 0 &&
+		   adypt_multi_pose_morph(m_gpus, matrices.data(), (int32_t)(matrices.size() / 12), morph_weights.data(), (int32_t)morph_weights.size(), params, &p, outcome) == ADYPT_OK)
+			return true;
+		printf("[PT]ERR: %s\n", matrices.size() % 12 ? "Pose: a matrix is 12 floats" : adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
 	// The image through the denoiser with its history across poses (adypt_hip.h, adypt_denoise_temporal): W x H x 3 floats into *rgb.  Needs
 	// SetNoiseStats(true) and GetSPP() >= 2.  commit: this call's state becomes the history (once per pose: after tracing, before the camera or the
 	// scene changes).  followMotion (adypt_denoise_temporal_motion): a committing call also keeps every triangle's positions and normals, and a later
