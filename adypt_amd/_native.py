@@ -91,6 +91,16 @@ class DenoiseMotion(Struct):
     _fields_ = [("have_snapshot", C.c_int32), ("snapshot_ms", C.c_float), ("n_tris", C.c_int64), ("device_bytes", C.c_int64)]
 
 
+class RectifyParams(C.Structure):
+    """adypt_rectify_params."""
+    _fields_ = [("radius", C.c_int32), ("gamma", C.c_float)]
+
+
+class DenoiseRectify(Struct):
+    """adypt_denoise_rectify."""
+    _fields_ = [("have", C.c_int32), ("radius", C.c_int32), ("gamma", C.c_float), ("window_ms", C.c_float), ("device_bytes", C.c_int64)]
+
+
 class BvhParams(C.Structure):
     _fields_ = [("max_spatial_depth", C.c_int32), ("triangle_sah", C.c_float), ("node_sah", C.c_float)]
 
@@ -218,6 +228,12 @@ _SIGS = {
     "adypt_multi_denoise_temporal_motion": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams)]),
     "adypt_multi_read_denoise_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "adypt_multi_get_denoise_motion": (C.c_int, [C.c_void_p, C.POINTER(DenoiseMotion)]),
+    "adypt_denoise_temporal_rectified": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(RectifyParams), C.c_int]),
+    "adypt_read_denoise_rectify": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_get_denoise_rectify": (C.c_int, [C.c_void_p, C.POINTER(DenoiseRectify)]),
+    "adypt_multi_denoise_temporal_rectified": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(RectifyParams), C.c_int]),
+    "adypt_multi_read_denoise_rectify": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_multi_get_denoise_rectify": (C.c_int, [C.c_void_p, C.POINTER(DenoiseRectify)]),
     "adypt_multi_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams)]),
     "adypt_multi_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_read_denoise_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -687,7 +687,7 @@ class _Tracer:
 
     # ---- denoising (adypt_denoise, include/adypt_hip.h; the definition: csrc/device/denoise.hpp); several devices: of the whole image ----
     def Denoise(self, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 0.1, temporal: bool = False, history_cap: float = 64.0,
-                commit: bool = True, follow_motion: bool = False) -> np.ndarray:
+                commit: bool = True, follow_motion: bool = False, rectify: bool = False, rectify_radius: int = 3, rectify_gamma: float = 1.0) -> np.ndarray:
         """H x W x 3 float32: the accumulated image through the variance- and primary-hit-guided a-trous filter.  Needs the noise statistics on and
         >= 2 spp in every block; the image, the statistics and the tracing state are left as they are.
         temporal (adypt_denoise_temporal; the definition: csrc/device/temporal.hpp): before the filter, what the last committing call left is
@@ -696,11 +696,20 @@ class _Tracer:
         its own (SetConfig): after a reset an unchanged camera with an unchanged seed repeats the same samples.
         follow_motion (adypt_denoise_temporal_motion; needs temporal): a committing call also keeps every triangle's positions and normals, and a
         later call merges a pixel on a triangle that UpdateTriangles() or Pose() has moved since through the point its hit had then — the moved
-        figure keeps its history.  Give it to every call of an animation; SetTriangles() and a committing call without it start the figure again."""
+        figure keeps its history.  Give it to every call of an animation; SetTriangles() and a committing call without it start the figure again.
+        rectify (adypt_denoise_temporal_rectified; needs temporal; the definition: csrc/device/rectify.hpp): the history is held against the mean of
+        the (2 rectify_radius + 1)^2 window of this call's own image on the pixel's surface and clamped to within rectify_gamma standard deviations
+        of it, and loses length by as much as it disagrees — for light that changed on a surface that stands still (a shadow that wandered, another
+        sun).  rectify_radius in [1, 3], rectify_gamma a finite number >= 0.  Combines with follow_motion."""
         if follow_motion and not temporal:
             raise ValueError("Denoise: follow_motion=True needs temporal=True")
+        if rectify and not temporal:
+            raise ValueError("Denoise: rectify=True needs temporal=True")
         prm = N.DenoiseParams(levels, sigma_l, sigma_z)
-        if temporal:
+        if temporal and rectify:
+            tp, rp = N.TemporalParams(history_cap, 1 if commit else 0), N.RectifyParams(rectify_radius, rectify_gamma)
+            self._call("denoise_temporal_rectified", C.byref(prm), C.byref(tp), C.byref(rp), 1 if follow_motion else 0)
+        elif temporal:
             tp = N.TemporalParams(history_cap, 1 if commit else 0)
             self._call("denoise_temporal_motion" if follow_motion else "denoise_temporal", C.byref(prm), C.byref(tp))
         else:
@@ -733,8 +742,23 @@ class _Tracer:
         self._call("get_denoise_motion", C.byref(out))
         return out.as_dict()
 
+    def ReadDenoiseRectify(self) -> np.ndarray:
+        """H x W float32: the share of its length every pixel's history kept in the last Denoise(temporal=True, rectify=True) (1 where the pixel found
+        no history, or its window had too few taps to say anything)."""
+        kept = np.zeros((self.height, self.width), dtype=np.float32)
+        self._call("read_denoise_rectify", kept.ctypes.data)
+        return kept
+
+    def GetDenoiseRectify(self) -> dict:
+        """have (0 / 1), radius, gamma and window_ms (the window kernel's HIP-event milliseconds) of the last rectified call, and device_bytes of what
+        rectify keeps on the (first) device."""
+        out = N.DenoiseRectify()
+        self._call("get_denoise_rectify", C.byref(out))
+        return out.as_dict()
+
     def GetDenoiseMergeMs(self) -> float:
-        """HIP-event milliseconds of the merge kernel of the last Denoise(temporal=True) (with follow_motion: of the gather kernel and the merge kernel)."""
+        """HIP-event milliseconds of the merge kernel of the last Denoise(temporal=True) (with follow_motion: of the gather kernel and the merge kernel;
+        with rectify: of the window kernel too)."""
         ms = C.c_float(0.0)
         self._call("get_denoise_merge_ms", C.byref(ms))
         return float(ms.value)

@@ -5,7 +5,7 @@
 //   adypt_hip scene.config [--spp N] [--out result.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S]
 //             [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr]
 //             [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C]
-//             [--history-out len.exr] [--follow-motion]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
+//             [--history-out len.exr] [--follow-motion] [--rectify [--rectify-gamma G] [--rectify-radius R] [--rectify-out kept.exr]]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]
 //   --build gpu: no .bvh cache is read or written and no tree is built on the host: the context is created from the triangles alone
 //              (adypt_create_multi_from_triangles) and its first tree built on the GPU by --rebuild-method (ploc unless given), --ploc-radius and
 //              --split-budget, which then name that build (and, with --rebuild-above, the policy's rebuild) instead of asking for a rebuild; one
@@ -55,6 +55,12 @@
 //              (adypt_multi_denoise_temporal_motion), and the --history-from poses are rendered and committed BEFORE --pose / --part-matrices (and the rebuild
 //              that goes with them) is applied — they show the scene as loaded, the main render the moved one, and pixels on moved triangles find
 //              their history through the pose they had.  The [PT]TEMPORAL: line then ends `, moved M pixels`.  Without it the pose comes first
+//   --rectify: with a temporal --denoise call only (else exit 2): every temporal call is a rectified one (adypt_multi_denoise_temporal_rectified) — the
+//              history is held against the mean of the window of the call's own image on the pixel's surface, clamped to within --rectify-gamma G
+//              standard deviations of it (a finite number >= 0, default 1; window radius --rectify-radius R, 1 .. 3, default 3) and loses length by as
+//              much as it disagrees: for light that changed on a surface that stands still.  Combines with --follow-motion.  --rectify-out kept.exr: the
+//              share of its length every pixel's history kept, as a grey EXR.  The [PT]TEMPORAL: line then ends `, rectified K pixels`: those with a
+//              share below 1.  --rectify-gamma, --rectify-radius and --rectify-out need --rectify
 //   --guides-out PREFIX: the feature images of the primary hit as PREFIX.albedo.exr, PREFIX.normal.exr and PREFIX.position.exr
 #include "adypt_hip.h"
 #include "adypt_host.h"
@@ -75,7 +81,7 @@ static double now_ms()
 
 int main(int argc, char **argv)
 {
-	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C] [--history-out len.exr] [--follow-motion]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]\n", argv[0]); return 2; }
+	if(argc < 2) { fprintf(stderr, "usage: %s scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] [--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--history-from other.config]... [--history-cap C] [--history-out len.exr] [--follow-motion] [--rectify [--rectify-gamma G] [--rectify-radius R] [--rectify-out kept.exr]]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--rebuild] [--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]\n", argv[0]); return 2; }
 	int min_spp = 16, check_every = 16;
 	double noise_target = -1.0; // < 0: render to a fixed sample count
 	std::string noise_out, spp_out, denoise_out, guides_out, pose, part_matrices;
@@ -93,6 +99,9 @@ int main(int argc, char **argv)
 	std::string history_out;
 	double history_cap = 64.0;
 	bool have_history_cap = false, follow_motion = false;
+	bool rectify = false, have_rectify_option = false;
+	adypt_rectify_params rp{3, 1.0f};
+	std::string rectify_out;
 	int adaptive = 0;
 	int spp = 64, fp16 = 0, primary = -1, sun_visibility = 0, save_every = 0;
 	std::vector<int> devices(1, 0);
@@ -143,6 +152,22 @@ int main(int argc, char **argv)
 			have_history_cap = true;
 		}
 		else if(a == "--follow-motion") follow_motion = true;
+		else if(a == "--rectify") rectify = true;
+		else if(a == "--rectify-out" && i + 1 < argc) { rectify_out = argv[++i]; have_rectify_option = true; }
+		else if(a == "--rectify-radius" && i + 1 < argc)
+		{
+			char *end = nullptr;
+			const long v = strtol(argv[++i], &end, 10);
+			if(end == argv[i] || *end || v < 1 || v > 3) { fprintf(stderr, "--rectify-radius takes 1, 2 or 3, not %s\n", argv[i]); return 2; }
+			rp.radius = (int32_t)v; have_rectify_option = true;
+		}
+		else if(a == "--rectify-gamma" && i + 1 < argc)
+		{
+			char *end = nullptr;
+			const double v = strtod(argv[++i], &end);
+			if(end == argv[i] || *end || !(v >= 0.0 && v <= 3.0e38)) { fprintf(stderr, "--rectify-gamma takes a finite number that is not negative, not %s\n", argv[i]); return 2; }
+			rp.gamma = (float)v; have_rectify_option = true;
+		}
 		else if(a == "--guides-out" && i + 1 < argc) guides_out = argv[++i];
 		else if(a == "--pose" && i + 1 < argc) pose = argv[++i];
 		else if(a == "--part-matrices" && i + 1 < argc) part_matrices = argv[++i];
@@ -205,6 +230,8 @@ int main(int argc, char **argv)
 	if(denoise && (denoise_levels < 1 || denoise_levels > 6)) { fprintf(stderr, "--denoise-levels must be in 1 .. 6\n"); return 2; }
 	const bool temporal = !history_from.empty() || have_history_cap || !history_out.empty();
 	if(temporal && !denoise) { fprintf(stderr, "--history-from, --history-cap and --history-out need --denoise file.exr\n"); return 2; }
+	if(have_rectify_option && !rectify) { fprintf(stderr, "--rectify-gamma, --rectify-radius and --rectify-out need --rectify\n"); return 2; }
+	if(rectify && !temporal) { fprintf(stderr, "--rectify needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out\n"); return 2; }
 	if(follow_motion && !temporal) { fprintf(stderr, "--follow-motion needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out\n"); return 2; }
 	if(until) min_spp = std::max(2, std::min(min_spp, spp));
 	adypt_config cfg;
@@ -437,6 +464,11 @@ int main(int argc, char **argv)
 
 	const adypt_denoise_params dp{denoise_levels, 4.0f, 0.1f};
 	const adypt_temporal_params tp{(float)history_cap, 1};
+	// a temporal call as the options ask for it
+	auto temporal_call = [&]() -> int {
+		if(rectify) return adypt_multi_denoise_temporal_rectified(multi, &dp, &tp, &rp, follow_motion ? 1 : 0);
+		return follow_motion ? adypt_multi_denoise_temporal_motion(multi, &dp, &tp) : adypt_multi_denoise_temporal(multi, &dp, &tp);
+	};
 	// --history-from: every earlier pose is rendered and committed to the denoiser's history, each with a shift_seed of its own (an unchanged seed would
 	// repeat the very same samples, which the history would count twice); then the main config's camera and seed, from 0 spp
 	for(size_t k = 0; k < history_cfg.size() && r == ADYPT_OK; ++k)
@@ -449,7 +481,7 @@ int main(int argc, char **argv)
 		if(r == ADYPT_OK) r = adypt_multi_set_params(multi, &p);
 		if(r == ADYPT_OK) r = adypt_multi_set_camera(multi, h.position, hp, hv);
 		if(r == ADYPT_OK) r = adypt_multi_trace_spp(multi, spp);
-		if(r == ADYPT_OK) r = follow_motion ? adypt_multi_denoise_temporal_motion(multi, &dp, &tp) : adypt_multi_denoise_temporal(multi, &dp, &tp);
+		if(r == ADYPT_OK) r = temporal_call();
 		if(r == ADYPT_OK) printf("[PT]INFO: history pose %s: %d spp committed\n", history_from[k].c_str(), spp);
 	}
 	if(r != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
@@ -564,7 +596,7 @@ int main(int argc, char **argv)
 	if(denoise)
 	{
 		std::vector<float> den((size_t)cfg.width * cfg.height * 3, 0.0f);
-		if((follow_motion ? adypt_multi_denoise_temporal_motion(multi, &dp, &tp) : temporal ? adypt_multi_denoise_temporal(multi, &dp, &tp) : adypt_multi_denoise(multi, &dp)) != ADYPT_OK || adypt_multi_read_denoised(multi, den.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
+		if((temporal ? temporal_call() : adypt_multi_denoise(multi, &dp)) != ADYPT_OK || adypt_multi_read_denoised(multi, den.data()) != ADYPT_OK) { fprintf(stderr, "[TRACER]Err: %s\n", err()); return 1; }
 		if(adypt_save_exr(denoise_out.c_str(), den.data(), cfg.width, cfg.height, fp16) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
 		printf("[PT]INFO: Saved denoised image (%d levels) to %s\n", denoise_levels, denoise_out.c_str());
 		if(temporal)
@@ -585,7 +617,21 @@ int main(int argc, char **argv)
 				if(adypt_multi_read_denoise_motion(multi, nullptr, moved.data()) != ADYPT_OK) { fprintf(stderr, "\n[TRACER]Err: %s\n", err()); return 1; }
 				printf(", moved %lld pixels", (long long)std::count(moved.begin(), moved.end(), (uint8_t)1));
 			}
+			std::vector<float> kept;
+			if(rectify)
+			{
+				kept.assign(length.size(), 1.0f);
+				if(adypt_multi_read_denoise_rectify(multi, kept.data()) != ADYPT_OK) { fprintf(stderr, "\n[TRACER]Err: %s\n", err()); return 1; }
+				printf(", rectified %lld pixels", (long long)std::count_if(kept.begin(), kept.end(), [](float k) { return k < 1.0f; }));
+			}
 			printf("\n");
+			if(!rectify_out.empty())
+			{
+				std::vector<float> grey(kept.size() * 3);
+				for(size_t i = 0; i < kept.size(); ++i) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = kept[i];
+				if(adypt_save_exr(rectify_out.c_str(), grey.data(), cfg.width, cfg.height, 0) != ADYPT_OK) { fprintf(stderr, "[PT]ERR: %s\n", adypt_host_last_error()); return 1; }
+				printf("[PT]INFO: Saved kept history shares to %s\n", rectify_out.c_str());
+			}
 			if(!history_out.empty())
 			{
 				std::vector<float> grey(length.size() * 3);

@@ -11,6 +11,9 @@
 //                    as the last committing motion call left them (the snapshot) against the record as it is now -> where the hit point and its normal
 //                    WERE then (temporal_previous_point), row-major XP = (P_prev.xyz, moved), XN = (N_prev.xyz, valid); k_temporal_merge<true> merges
 //                    through them.  k_motion_snapshot, on such a call's commit: the first 80 bytes of every record into the snapshot
+//     k_rectify_window<R>  a rectified call only (the definition: rectify.hpp), before the merge and inside its stage of the timer: per pixel the mean of the
+//                    (2 R + 1)^2 window of the call's own images on the pixel's surface and the squared limit a history value may lie from it, row-major
+//                    R0 = (mu.rgb, k), R1 = (g.rgb, 0); k_temporal_merge<., true> clamps the history to them and writes the share of its length it kept
 //     k_atrous<LAST>  one level per launch, X0 ping-pongs; the last level multiplies the albedo back and writes the W x H x 3 result
 // Several devices: every context captures the guides of its own blocks, the host puts the devices' local images back to back in rank order, their
 // block lists likewise (every block has one owner, and k_denoise_prepare takes any block list and writes at the picture's coordinates), uploads them
@@ -98,23 +101,90 @@ struct DeviceHistory {
 // One pixel per thread, the workgroup of k_atrous.  Reads 64 B of the call's images and up to four taps x 64 B of the history (neighbouring pixels share
 // them: 64 B per pixel reach the memory where the motion is smooth), writes the merged X0 (16 B), X2 with n_out in .w (16 B) and the history length
 // (4 B): 164 B per pixel.  The history's camera comes by value.  MOTION: through k_motion_gather's XP, XN (32 B per pixel more), which the other
-// instance never looks at (they stand last, so that its kernel arguments lie where they lay before there was a motion call).
-template <bool MOTION>
+// instance never looks at (they stand last, so that its kernel arguments lie where they lay before there was a motion call).  RECTIFY: the history is held
+// against k_rectify_window's R0, R1 (32 B per pixel more read) and the share of its length it kept is written (4 B); these stand last in turn, and the
+// instances without it pass temporal_merge a constant "off": their code is what it was.
+template <bool MOTION, bool RECTIFY>
 __global__ __launch_bounds__(kAtrousX * kAtrousY) void k_temporal_merge(const float4 *x0, const float4 *x1, float4 *x2, const float4 *xa, const float4 *h0, const float4 *h1,
                                                                          const float4 *h2, const float4 *ha, float4 *merged, float *length, int width, int height, int have,
-                                                                         TemporalCamera cam, float history_cap, const float4 *xp, const float4 *xn)
+                                                                         TemporalCamera cam, float history_cap, const float4 *xp, const float4 *xn, const float4 *r0, const float4 *r1, float *kept,
+                                                                         float gamma)
 {
 	const int x = blockIdx.x * kAtrousX + threadIdx.x, y = blockIdx.y * kAtrousY + threadIdx.y;
 	if(x >= width || y >= height) return;
 	const int p = y * width + x;
 	const Dn4 c2 = DeviceImages::load(x2, p);
 	const DeviceHistory hist{h0, h1, h2, ha};
+	Rectify rect;
+	if(RECTIFY) rect = Rectify{true, DeviceImages::load(r0, p), DeviceImages::load(r1, p), gamma};
 	const TemporalOut r = MOTION ? temporal_merge_motion(hist, have != 0, cam, width, height, DeviceImages::load(x0, p), DeviceImages::load(x1, p), DeviceImages::load(xa, p), c2.w, history_cap,
-	                                                     DeviceImages::load(xp, p), DeviceImages::load(xn, p))
-	                             : temporal_merge(hist, have != 0, cam, width, height, DeviceImages::load(x0, p), DeviceImages::load(x1, p), c2, DeviceImages::load(xa, p), c2.w, history_cap);
+	                                                     DeviceImages::load(xp, p), DeviceImages::load(xn, p), rect)
+	                             : temporal_merge(hist, have != 0, cam, width, height, DeviceImages::load(x0, p), DeviceImages::load(x1, p), c2, DeviceImages::load(xa, p), c2.w, history_cap, rect);
 	merged[p] = make_float4(r.x0.x, r.x0.y, r.x0.z, r.x0.w);
 	x2[p] = make_float4(c2.x, c2.y, c2.z, r.n);
 	length[p] = r.n;
+	if(RECTIFY) kept[p] = r.kept;
+}
+
+// ---- rectifying stale history: the window statistics ----
+// the planes of the staged tile, one float per pixel each: X0 = (D0.rgb, V0), the normal, the point, the albedo, the hit flag
+enum RectifyPlane { kPlaneR, kPlaneG, kPlaneB, kPlaneV, kPlaneNx, kPlaneNy, kPlaneNz, kPlanePx, kPlanePy, kPlanePz, kPlaneAr, kPlaneAg, kPlaneAb, kPlaneHit, kRectifyPlanes };
+struct RectifyOrigin { float o[3]; };
+
+// One pixel per thread, the workgroup of k_atrous.  (2 R + 1)^2 taps x 64 B per pixel would be read from the images; instead the workgroup stages its
+// 32 x 8 pixels with their halo of R once in LDS — (32 + 2 R) x (8 + 2 R) pixels, 532 at R = 3: 2.1 x the tile's own pixels, four 16-byte loads each,
+// neighbouring lanes neighbouring pixels — as kRectifyPlanes planes of floats (29 792 B at R = 3), so that for one tap the 32 lanes of a row read 32
+// consecutive words of a plane (ds_read_b32 serves lanes 0-31 and 32-63 in a cycle each: no bank conflict; a float4 per pixel would be read 16 lanes
+// at a time, 64 B apart: 4-way).  A tile pixel outside the image is staged as zeros: its hit flag refuses it, as the definition skips it.  Every thread
+// visits its taps row by row, dy outside and dx inside, through rectify_tap: the sums are the definition's to the bit.  The loops unroll (R is the
+// instance's): every LDS address is the centre's plus a constant, the sums stay in registers, no scratch.  Writes R0 and R1, 32 B per pixel.
+template <int R>
+__global__ __launch_bounds__(kAtrousX * kAtrousY) void k_rectify_window(const float4 *__restrict__ x0, const float4 *__restrict__ x1, const float4 *__restrict__ x2,
+                                                                         const float4 *__restrict__ xa, float4 *__restrict__ r0, float4 *__restrict__ r1, int width, int height,
+                                                                         RectifyOrigin origin)
+{
+	constexpr int TW = kAtrousX + 2 * R, TH = kAtrousY + 2 * R, TP = TW * TH;
+	__shared__ float tile[kRectifyPlanes][TP];
+	const int tid = threadIdx.y * kAtrousX + threadIdx.x;
+	const int gx0 = blockIdx.x * kAtrousX - R, gy0 = blockIdx.y * kAtrousY - R;
+	for(int i = tid; i < TP; i += kAtrousX * kAtrousY)
+	{
+		const int ty = i / TW, tx = i - ty * TW;
+		const int gx = gx0 + tx, gy = gy0 + ty;
+		float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a, d = a;
+		if(gx >= 0 && gy >= 0 && gx < width && gy < height)
+		{
+			const size_t q = (size_t)gy * width + gx;
+			a = x0[q]; b = x1[q]; c = x2[q]; d = xa[q];
+		}
+		tile[kPlaneR][i] = a.x; tile[kPlaneG][i] = a.y; tile[kPlaneB][i] = a.z; tile[kPlaneV][i] = a.w;
+		tile[kPlaneNx][i] = b.x; tile[kPlaneNy][i] = b.y; tile[kPlaneNz][i] = b.z; tile[kPlaneHit][i] = b.w;
+		tile[kPlanePx][i] = c.x; tile[kPlanePy][i] = c.y; tile[kPlanePz][i] = c.z;
+		tile[kPlaneAr][i] = d.x; tile[kPlaneAg][i] = d.y; tile[kPlaneAb][i] = d.z;
+	}
+	__syncthreads();
+	const int x = blockIdx.x * kAtrousX + threadIdx.x, y = blockIdx.y * kAtrousY + threadIdx.y;
+	if(x >= width || y >= height) return;
+	const int at = (threadIdx.y + R) * TW + threadIdx.x + R; // the centre in the tile; a tap is at + dy * TW + dx, inside the tile for |dx|, |dy| <= R
+	RectifySums s{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+	if(tile[kPlaneHit][at] != 0.0f)
+	{
+		const RectifyCentre ctr = rectify_centre(Dn4{tile[kPlaneNx][at], tile[kPlaneNy][at], tile[kPlaneNz][at], 1.0f}, Dn4{tile[kPlanePx][at], tile[kPlanePy][at], tile[kPlanePz][at], 0.0f},
+		                                         Dn4{tile[kPlaneAr][at], tile[kPlaneAg][at], tile[kPlaneAb][at], 0.0f}, origin.o);
+#pragma unroll
+		for(int dy = -R; dy <= R; ++dy)
+#pragma unroll
+			for(int dx = -R; dx <= R; ++dx)
+			{
+				const int q = at + dy * TW + dx;
+				rectify_tap(ctr, s, tile[kPlaneNx][q], tile[kPlaneNy][q], tile[kPlaneNz][q], tile[kPlaneHit][q], tile[kPlanePx][q], tile[kPlanePy][q], tile[kPlanePz][q], tile[kPlaneAr][q],
+				            tile[kPlaneAg][q], tile[kPlaneAb][q], tile[kPlaneR][q], tile[kPlaneG][q], tile[kPlaneB][q], tile[kPlaneV][q]);
+			}
+	}
+	const RectifyStats st = rectify_finish(s);
+	const size_t p = (size_t)y * width + x;
+	r0[p] = make_float4(st.r0.x, st.r0.y, st.r0.z, st.r0.w);
+	r1[p] = make_float4(st.r1.x, st.r1.y, st.r1.z, st.r1.w);
 }
 
 constexpr int kSnapshotVecs = 5; // the first 80 bytes of a record: words 0..17, and the material id and the class word, which nothing here reads
@@ -292,6 +362,13 @@ struct Denoiser {
 	// following moved geometry: XP, XN, 32 B per image pixel, allocated at the first motion call
 	Buffer<float4> xp, xn;
 	bool xp_valid = false; // as length_valid, of a motion call and XP, XN
+	// rectifying stale history: R0, R1 and the kept read-out, 36 B per image pixel, allocated at the first rectified call; nothing of it outlives a call
+	// but the read-outs: the parameters and the window kernel's time of the last rectified call
+	Buffer<float4> r0, r1;
+	Buffer<float> kept;
+	bool kept_valid = false; // as length_valid, of a rectified call and `kept`
+	int rectify_radius = 0; float rectify_gamma = 0.0f;
+	StageTimer<2> window_timer;
 
 	size_t pixels() const { return (size_t)width * (size_t)height; }
 };
@@ -313,19 +390,25 @@ struct DenoiseCall {
 	DenoiseParams prm;
 	Mode mode;
 	float history_cap; bool commit; // of Temporal and Motion; a Plain call commits nothing
+	bool rectify; int radius; float gamma; // of Temporal and Motion: the history is rectified (rectify.hpp)
 	const char *fn;
 	std::string refused;            // why the arguments are refused; empty: they are not
 };
 
-// the call of the ABI structs (null: the defaults — 5 levels, 4.0, 0.1; cap 64, committing); tp is looked at by Temporal and Motion only
-DenoiseCall make_call(Mode mode, const char *fn, const adypt_denoise_params *p, const adypt_temporal_params *tp)
+// the call of the ABI structs (null: the defaults — 5 levels, 4.0, 0.1; cap 64, committing; radius 3, gamma 1); tp is looked at by Temporal and Motion
+// only, rp by a rectified call (`rectify`) only
+DenoiseCall make_call(Mode mode, const char *fn, const adypt_denoise_params *p, const adypt_temporal_params *tp, bool rectify = false, const adypt_rectify_params *rp = nullptr)
 {
 	const bool with_history = mode != Mode::Plain;
-	DenoiseCall call{p ? DenoiseParams{p->levels, p->sigma_l, p->sigma_z} : kDenoiseDefaults, mode, kTemporalDefaultCap, with_history, fn, {}};
+	DenoiseCall call{p ? DenoiseParams{p->levels, p->sigma_l, p->sigma_z} : kDenoiseDefaults, mode, kTemporalDefaultCap, with_history, with_history && rectify, kRectifyDefaultRadius,
+	                 kRectifyDefaultGamma, fn, {}};
 	if(with_history && tp) { call.history_cap = tp->history_cap; call.commit = tp->commit != 0; }
+	if(call.rectify && rp) { call.radius = rp->radius; call.gamma = rp->gamma; }
 	if(!denoise_params_valid(call.prm))
 		call.refused = std::string(fn) + ": levels must be in [1, " + std::to_string(kDenoiseMaxLevels) + "], sigma_l and sigma_z positive numbers";
 	else if(with_history && !temporal_cap_valid(call.history_cap)) call.refused = std::string(fn) + ": history_cap must be a positive finite number";
+	else if(call.rectify && !rectify_params_valid(call.radius, call.gamma))
+		call.refused = std::string(fn) + ": the rectify radius must be in [1, " + std::to_string(kRectifyMaxRadius) + "], gamma a finite number that is not negative";
 	return call;
 }
 
@@ -342,6 +425,11 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 	{
 		CTX_TRY(c, at_least(d->xp, n)); CTX_TRY(c, at_least(d->xn, n));
 		d->xp_valid = false;
+	}
+	if(call.rectify)
+	{
+		CTX_TRY(c, at_least(d->r0, n)); CTX_TRY(c, at_least(d->r1, n)); CTX_TRY(c, at_least(d->kept, n));
+		d->kept_valid = false;
 	}
 	const int width = d->width, height = d->height, n_px = in.n_blocks * kBlockPixels;
 	const int blocks_x = (width + kBlockDim - 1) / kBlockDim;
@@ -363,10 +451,22 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 			                   h.known_tris(sc.n_tris), (const float4 *)sc.triangles, sc.tri_float4, d->xp.get(), d->xn.get());
 			CTX_TRY(c, hipGetLastError());
 		}
-		const auto merge = with_motion ? k_temporal_merge<true> : k_temporal_merge<false>;
+		if(call.rectify)
+		{
+			const auto window = call.radius == 1 ? k_rectify_window<1> : call.radius == 2 ? k_rectify_window<2> : k_rectify_window<3>;
+			static_assert(kRectifyMaxRadius == 3, "one instance of k_rectify_window per radius");
+			RectifyOrigin origin;
+			for(int k = 0; k < 3; ++k) origin.o[k] = cam.origin[k];
+			CTX_TRY(c, d->window_timer.mark(0, stream));
+			hipLaunchKernelGGL(window, grid, block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, d->r0.get(), d->r1.get(), width, height,
+			                   origin);
+			CTX_TRY(c, hipGetLastError());
+			CTX_TRY(c, d->window_timer.mark(1, stream));
+		}
+		const auto merge = call.rectify ? (with_motion ? k_temporal_merge<true, true> : k_temporal_merge<false, true>) : (with_motion ? k_temporal_merge<true, false> : k_temporal_merge<false, false>);
 		hipLaunchKernelGGL(merge, grid, block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, d->x2.get(), (const float4 *)d->xa, (const float4 *)h.h0, (const float4 *)h.h1,
 		                   (const float4 *)h.h2, (const float4 *)h.ha, d->xm.get(), d->length.get(), width, height, h.present ? 1 : 0, h.camera, call.history_cap, (const float4 *)d->xp,
-		                   (const float4 *)d->xn);
+		                   (const float4 *)d->xn, (const float4 *)d->r0, (const float4 *)d->r1, d->kept.get(), call.gamma);
 		CTX_TRY(c, hipGetLastError());
 		CTX_TRY(c, d->timer.mark(marks.merge, stream));
 	}
@@ -386,6 +486,7 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 	d->timer.complete();
 	if(with_history) d->length_valid = true;
 	if(with_motion) d->xp_valid = true;
+	if(call.rectify) { d->kept_valid = true; d->rectify_radius = call.radius; d->rectify_gamma = call.gamma; }
 	if(call.commit) h.commit(d->xm, d->x1, d->x2, d->xa, cam, snapshot_of);
 	return ADYPT_OK;
 }
@@ -478,6 +579,26 @@ int get_motion(adypt_ctx *c, const char *fn, adypt_denoise_motion *out)
 	return ADYPT_OK;
 }
 
+// the share of its length every pixel's history kept in the last rectified call
+int read_rectify(adypt_ctx *c, const char *fn, float *kept)
+{
+	return read_image(c, fn, ": no rectified call has run yet (adypt_denoise_temporal_rectified)", kept, 1, [](Denoiser *d) { return d->kept_valid ? d->kept.get() : nullptr; });
+}
+
+int get_rectify(adypt_ctx *c, const char *fn, adypt_denoise_rectify *out)
+{
+	if(!out) return ctx_fail(c, ADYPT_E_INVALID, std::string(fn) + ": out is null");
+	*out = adypt_denoise_rectify{};
+	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
+	if(!d) return ADYPT_OK;
+	out->device_bytes = (int64_t)(d->r0.bytes() + d->r1.bytes() + d->kept.bytes());
+	if(!d->kept_valid) return ADYPT_OK;
+	out->have = 1;
+	out->radius = d->rectify_radius; out->gamma = d->rectify_gamma;
+	(void)d->window_timer.read(&out->window_ms, 1, 1, false);
+	return ADYPT_OK;
+}
+
 int read_merge_ms(adypt_ctx *c, const char *fn, float *ms)
 {
 	Denoiser *d = finished_denoiser(c);
@@ -526,6 +647,15 @@ int adypt_denoise(adypt_ctx *c, const adypt_denoise_params *p) { return denoise_
 int adypt_denoise_temporal(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return denoise_context(c, make_call(Mode::Temporal, "adypt_denoise_temporal", p, tp)); }
 
 int adypt_denoise_temporal_motion(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return denoise_context(c, make_call(Mode::Motion, "adypt_denoise_temporal_motion", p, tp)); }
+
+int adypt_denoise_temporal_rectified(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_rectify_params *rp, int follow_motion)
+{
+	return denoise_context(c, make_call(follow_motion ? Mode::Motion : Mode::Temporal, "adypt_denoise_temporal_rectified", p, tp, true, rp));
+}
+
+int adypt_read_denoise_rectify(adypt_ctx *c, float *kept) { return c && kept ? read_rectify(c, "adypt_read_denoise_rectify", kept) : ADYPT_E_INVALID; }
+
+int adypt_get_denoise_rectify(adypt_ctx *c, adypt_denoise_rectify *out) { return c ? get_rectify(c, "adypt_get_denoise_rectify", out) : ADYPT_E_INVALID; }
 
 int adypt_denoise_history_reset(adypt_ctx *c)
 {
@@ -672,6 +802,22 @@ int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p) { return 
 int adypt_multi_denoise_temporal(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return multi_denoise(m, make_call(Mode::Temporal, "adypt_multi_denoise_temporal", p, tp)); }
 
 int adypt_multi_denoise_temporal_motion(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return multi_denoise(m, make_call(Mode::Motion, "adypt_multi_denoise_temporal_motion", p, tp)); }
+
+int adypt_multi_denoise_temporal_rectified(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_rectify_params *rp, int follow_motion)
+{
+	return multi_denoise(m, make_call(follow_motion ? Mode::Motion : Mode::Temporal, "adypt_multi_denoise_temporal_rectified", p, tp, true, rp));
+}
+
+// the window statistics and the kept read-out live on the first device, where the merge runs
+int adypt_multi_read_denoise_rectify(adypt_multi *m, float *kept)
+{
+	return kept ? on_root(m, [=](adypt_ctx *c) { return read_rectify(c, "adypt_multi_read_denoise_rectify", kept); }) : ADYPT_E_INVALID;
+}
+
+int adypt_multi_get_denoise_rectify(adypt_multi *m, adypt_denoise_rectify *out)
+{
+	return on_root(m, [=](adypt_ctx *c) { return get_rectify(c, "adypt_multi_get_denoise_rectify", out); });
+}
 
 // the snapshot and the motion images live on the first device, beside the history
 int adypt_multi_read_denoise_motion(adypt_multi *m, float *prev_position, uint8_t *moved)

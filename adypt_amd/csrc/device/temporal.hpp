@@ -28,6 +28,12 @@ constexpr float kTemporalDefaultCap = 64.0f;
 // (written so that a NaN, an infinity and anything not positive are refused)
 inline bool temporal_cap_valid(float cap) { return cap > 0.0f && cap <= kTemporalFiniteMax; }
 
+}  // namespace adypt
+
+#include "rectify.hpp" // rectifying stale history against the current call's own neighbourhood: the window statistics and the clamp (uses the constants above)
+
+namespace adypt {
+
 // The camera of the call that left the history, made only of what adypt_set_camera was given: the screen point (sx, sy) has the camera-space
 // direction t = a sx + b sy + c (columns 0, 1 and 2 + 3 of inv_proj, as camera_dir in shade.hpp), the world direction is R t with R the upper 3 x 3
 // of inv_view, kept here as its columns r[0..2], r[3..5], r[6..8].
@@ -69,18 +75,21 @@ ADYPT_HOST_DEVICE bool temporal_reproject(const TemporalCamera &cam, int width, 
 	return true;
 }
 
-// What the merge leaves at a pixel: the merged (D.rgb, V) and the effective sample count n_out.
-struct TemporalOut { Dn4 x0; float n; };
+// What the merge leaves at a pixel: the merged (D.rgb, V) and the effective sample count n_out; of a rectified merge also the share of its length the
+// history kept (1 where the pixel found no history, or was not rectified).
+struct TemporalOut { Dn4 x0; float n; float kept; };
 
 // The body of both forms of the merge: the pixel's surface as the HISTORY holds it — its normal (nx, ny, nz) and its point (px, py, pz) at the time of the
 // last commit — is what is reprojected and what a tap's normal and plane are held against.  temporal_merge gives the current normal and point (the
 // surface stands still), temporal_merge_motion what temporal_previous_point made of the hit triangle as it was then.
+// rect.on (rectify.hpp): where the window of the pixel has at least kRectifyMinTaps taps, the history's colour is clamped to the window's mean within
+// gamma * sqrt(g) per channel and its length multiplied by f before the blend; a length that is then not positive takes no history.  hv stays.
 template <class Hist>
 ADYPT_HOST_DEVICE TemporalOut temporal_merge_through(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, bool hit, float nx, float ny, float nz,
-                                                     float px, float py, float pz, const Dn4 &ca, float n, float history_cap)
+                                                     float px, float py, float pz, const Dn4 &ca, float n, float history_cap, const Rectify rect = Rectify{})
 {
 	TemporalOut out;
-	out.x0 = c0; out.n = n;
+	out.x0 = c0; out.n = n; out.kept = 1.0f;
 	if(!have || !hit) return out;
 	float fx, fy, dist;
 	if(!temporal_reproject(cam, width, height, px, py, pz, &fx, &fy, &dist)) return out;
@@ -115,9 +124,16 @@ ADYPT_HOST_DEVICE TemporalOut temporal_merge_through(const Hist &hist, bool have
 			sn = sn + w * q2.w;
 		}
 	if(!(sw > kTemporalMinWeight)) return out;
-	const float hr = sr / sw, hg = sg / sw, hb = sb / sw, hv = sv / (sw * sw);
+	float hr = sr / sw, hg = sg / sw, hb = sb / sw;
+	const float hv = sv / (sw * sw);
 	const float hq = sn / sw;
-	const float nh = hq < history_cap ? hq : history_cap;
+	float nh = hq < history_cap ? hq : history_cap;
+	if(rect.on && rect.r0.w >= (float)kRectifyMinTaps)
+	{
+		out.kept = rectify_history(rect, &hr, &hg, &hb);
+		nh = nh * out.kept;
+		if(!(nh > 0.0f)) return out;
+	}
 	const float den = n + nh;
 	out.x0.x = (n * c0.x + nh * hr) / den; out.x0.y = (n * c0.y + nh * hg) / den; out.x0.z = (n * c0.z + nh * hb) / den;
 	out.x0.w = ((n * n) * c0.w + (nh * nh) * hv) / (den * den);
@@ -130,9 +146,9 @@ ADYPT_HOST_DEVICE TemporalOut temporal_merge_through(const Hist &hist, bool have
 // is none.  A tap that does not count is skipped entirely (an accumulator keeps its word).
 template <class Hist>
 ADYPT_HOST_DEVICE TemporalOut temporal_merge(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, const Dn4 &c1, const Dn4 &c2, const Dn4 &ca,
-                                             float n, float history_cap)
+                                             float n, float history_cap, const Rectify rect = Rectify{})
 {
-	return temporal_merge_through(hist, have, cam, width, height, c0, c1.w != 0.0f, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z, ca, n, history_cap);
+	return temporal_merge_through(hist, have, cam, width, height, c0, c1.w != 0.0f, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z, ca, n, history_cap, rect);
 }
 
 // ---- following moved geometry ----
@@ -180,9 +196,9 @@ ADYPT_HOST_DEVICE TemporalPrevious temporal_previous_point(const float *prev, co
 // pose's; the albedo test, the finiteness tests, the weights, the cap and the blend are temporal_merge's.
 template <class Hist>
 ADYPT_HOST_DEVICE TemporalOut temporal_merge_motion(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, const Dn4 &c1, const Dn4 &ca, float n,
-                                                    float history_cap, const Dn4 &xp, const Dn4 &xn)
+                                                    float history_cap, const Dn4 &xp, const Dn4 &xn, const Rectify rect = Rectify{})
 {
-	return temporal_merge_through(hist, have && xn.w != 0.0f, cam, width, height, c0, c1.w != 0.0f, xn.x, xn.y, xn.z, xp.x, xp.y, xp.z, ca, n, history_cap);
+	return temporal_merge_through(hist, have && xn.w != 0.0f, cam, width, height, c0, c1.w != 0.0f, xn.x, xn.y, xn.z, xp.x, xp.y, xp.z, ca, n, history_cap, rect);
 }
 
 }  // namespace adypt

@@ -337,7 +337,7 @@ int adypt_get_denoise_merge_ms(adypt_ctx *ctx, float *ms);
  * The snapshot belongs to the history: written only by a committing motion call; dropped by adypt_denoise_history_reset, by a committing
  * adypt_denoise_temporal (the geometry of the history is then unknown) and by adypt_set_triangles (an index means another triangle); kept across
  * adypt_update_triangles, adypt_pose, adypt_rebuild_bvh and calls with commit = 0.
- * Not covered: shading that changes because a NEIGHBOUR moved (a shadow, a reflection) — the history keeps what it had, history_cap is the lever.
+ * Shading that changes because a NEIGHBOUR moved (a shadow, a reflection): the history keeps what it had unless the call is a rectified one (below).
  * Memory: 80 B per triangle (at the first committing motion call) + 32 B per image pixel (at the first motion call).  Several devices: on the first. */
 typedef struct adypt_denoise_motion {
 	int32_t have_snapshot;       /* 1: the history has a snapshot */
@@ -353,6 +353,36 @@ int adypt_denoise_temporal_motion(adypt_ctx *ctx, const adypt_denoise_params *pa
  * the first motion call */
 int adypt_read_denoise_motion(adypt_ctx *ctx, float *prev_position, uint8_t *moved);
 int adypt_get_denoise_motion(adypt_ctx *ctx, adypt_denoise_motion *out);
+
+/* ---- rectifying stale history: the history is held against what the current call's own neighbourhood says ----------------------------------------
+ * The temporal merge accepts a history tap on geometry alone.  Where the surface stands still but its LIGHT changed — a door that opened, a shadow that
+ * wandered because a neighbour moved, another sun — up to history_cap stale samples outvote the pose's own few.  A rectified call computes, per hit
+ * pixel, the mean mu and the variance of the (2 radius + 1)^2 window of the call's own demodulated radiance over the taps that lie on the pixel's
+ * surface (the history's normal, plane and albedo tests, against the centre), takes g = max(var - the window's mean V0, 0) + var / k per channel (the
+ * surface's spatial spread plus the standard error of the window mean), and where the window has at least 4 taps clamps the history's colour to
+ * mu +- gamma sqrt(g) per channel; the history's length is multiplied by the smallest lim / |h - mu| of a clamped channel: a history that disagrees by m
+ * times the limit keeps 1 / m of its length, one that then has none takes no history.  The history's variance stays.  The definition is pinned bit for
+ * bit in csrc/device/rectify.hpp and temporal.hpp; tests/rectify_truth.py restates it in numpy.  Nothing is kept across calls: the history, its
+ * snapshot and the calls without the flag are what they were.
+ * Memory: 36 B per image pixel (R0, R1, the kept read-out), allocated at the first rectified call.  Several devices: on the first. */
+typedef struct adypt_rectify_params {
+	int32_t radius;              /* of the window, in [1, 3]; default 3 */
+	float gamma;                 /* the limit in standard deviations; a finite number >= 0, default 1 */
+} adypt_rectify_params;
+typedef struct adypt_denoise_rectify {
+	int32_t have;                /* 1: a rectified call has run (else the three below are 0) */
+	int32_t radius;              /* of the last rectified call */
+	float gamma;
+	float window_ms;             /* HIP-event time of its window kernel (adypt_get_denoise_merge_ms covers it too) */
+	int64_t device_bytes;        /* R0, R1 and the kept read-out as allocated */
+} adypt_denoise_rectify;
+/* adypt_denoise_temporal (follow_motion 0) or adypt_denoise_temporal_motion (not 0) with the history rectified; rectify may be NULL (the defaults).
+ * Refusals: theirs, and ADYPT_E_INVALID for a radius outside [1, 3] or a gamma that is negative or not finite; a refused call changes nothing. */
+int adypt_denoise_temporal_rectified(adypt_ctx *ctx, const adypt_denoise_params *params, const adypt_temporal_params *temporal, const adypt_rectify_params *rectify, int follow_motion);
+/* W*H floats: the share of its length every pixel's history kept in the last rectified call (1 where the pixel found no history or its window had
+ * fewer than 4 taps).  ADYPT_E_STATE before the first */
+int adypt_read_denoise_rectify(adypt_ctx *ctx, float *kept);
+int adypt_get_denoise_rectify(adypt_ctx *ctx, adypt_denoise_rectify *out);
 
 /* ---- moving geometry: new vertex positions without a new BVH and a new context ----------------------------------------------------------------
  * The tree's topology stays valid when vertices move; what goes stale are the boxes, the Woop data and the triangle records.  adypt_update_triangles
@@ -688,6 +718,10 @@ int adypt_multi_get_denoise_merge_ms(adypt_multi *m, float *ms);
 int adypt_multi_denoise_temporal_motion(adypt_multi *m, const adypt_denoise_params *params, const adypt_temporal_params *temporal);
 int adypt_multi_read_denoise_motion(adypt_multi *m, float *prev_position, uint8_t *moved);
 int adypt_multi_get_denoise_motion(adypt_multi *m, adypt_denoise_motion *out);
+/* adypt_denoise_temporal_rectified ... for the whole image: the window statistics and the merge on the first device */
+int adypt_multi_denoise_temporal_rectified(adypt_multi *m, const adypt_denoise_params *params, const adypt_temporal_params *temporal, const adypt_rectify_params *rectify, int follow_motion);
+int adypt_multi_read_denoise_rectify(adypt_multi *m, float *kept);
+int adypt_multi_get_denoise_rectify(adypt_multi *m, adypt_denoise_rectify *out);
 /* adypt_update_triangles on every device: the scene is replicated and every device refits its own copy; no collective.  (One process per GPU: every
  * rank calls adypt_update_triangles on its own context.) */
 int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals);

@@ -372,6 +372,23 @@ public:
 		return false;
 	}
 
+	// DenoiseTemporal with the history rectified (adypt_hip.h, adypt_denoise_temporal_rectified): before it is merged, the history is held against the
+	// mean of the (2 radius + 1)^2 window of this call's own image on the pixel's surface, clamped to within gamma standard deviations of it, and loses
+	// length by as much as it disagrees — for light that changed on a surface that stands still (a shadow that wandered, a door that opened).  radius
+	// in [1, 3], gamma a finite number >= 0.  kept, where not null: W x H floats, the share of its length every pixel's history kept.
+	bool DenoiseTemporalRectified(std::vector<float> *rgb, float historyCap = 64.0f, bool commit = true, bool followMotion = false, int radius = 3, float gamma = 1.0f,
+	                              std::vector<float> *kept = nullptr, const adypt_denoise_params *params = nullptr)
+	{
+		const adypt_temporal_params t = {historyCap, commit ? 1 : 0};
+		const adypt_rectify_params r = {radius, gamma};
+		rgb->resize((size_t)m_width * m_height * 3);
+		if(kept) kept->resize((size_t)m_width * m_height);
+		if(adypt_multi_denoise_temporal_rectified(m_gpus, params, &t, &r, followMotion ? 1 : 0) == ADYPT_OK && adypt_multi_read_denoised(m_gpus, rgb->data()) == ADYPT_OK &&
+		   (!kept || adypt_multi_read_denoise_rectify(m_gpus, kept->data()) == ADYPT_OK)) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
 	// what DrawScreen puts on screen, for a caller-owned W x H RGBA8 texture / window (every device fills in its own tiles)
 	bool ReadScreen(std::vector<uint8_t> *rgba8) const
 	{
