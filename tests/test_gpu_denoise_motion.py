@@ -381,7 +381,4 @@ def test_cli_follows_the_parts_it_moves(scene_cache, tmp_path):
     # without the flag the pose comes first and the line is the old one
     code, text = cli("--denoise", d_exr, "--part-matrices", matrix_file, *history)
     assert code == 0 and text.index("[PT]POSE:") < text.index("history pose") and "moved" not in text.split("[PT]TEMPORAL:")[1].splitlines()[0], text[-2000:]
-    # the flag needs a temporal call
-    for bad in (("--follow-motion",), ("--denoise", d_exr, "--follow-motion")):
-        code, text = cli(*bad)
-        assert code == 2 and "--follow-motion" in text, text
+    # (the flag needs a temporal call: tests/test_cli_options.py)

@@ -468,14 +468,4 @@ def test_cli(scene_cache, sobol_matrices, tmp_path):
     line = "[PT]TEMPORAL: history on %d of %d hit pixels, mean length %.3f" % (took, int(hit.sum()), float(length[hit].astype(np.float64).mean()))
     assert line in text, text[-2000:]
     assert took > 0.5 * hit.sum()
-    # a config of another size is refused
-    other = json.loads(json.dumps(main))
-    other["width"] = w + 4
-    wrong = str(tmp_path / "wrong.config")
-    json.dump(other, open(wrong, "w"), indent=4)
-    code, text = cli("--denoise", d_exr, "--history-from", wrong)
-    assert code == 1 and "another size" in text, text[-2000:]
-    # the history options need --denoise, and a cap that is a positive finite number
-    for bad in (("--history-from", paths[0]), ("--denoise", d_exr, "--history-cap", "0"), ("--denoise", d_exr, "--history-cap", "nan")):
-        code, text = cli(*bad)
-        assert code == 2 and "--history" in text, text
+    # (a config of another size, the history options without --denoise, a cap that is no positive finite number: tests/test_cli_options.py)

@@ -1,6 +1,6 @@
 """-m gpu: adypt_hip --morph-target a.obj --morph-target b.obj --morph-weights w0,w1 (csrc/cli/main.cpp) renders the config's scene with both targets,
 diffed against the scene as loaded, blended in on the GPU — alone and under --part-matrices: the image BindParts + BindMorph + Pose(morph_weights=...)
-give in this process, bit for bit.  What the command line refuses is here too."""
+give in this process, bit for bit.  What the command line refuses: tests/test_cli_options.py."""
 import os
 import re
 import subprocess
@@ -89,24 +89,3 @@ def test_cli_morph_targets(scene_cache, tmp_path):
     assert not np.array_equal(bits(images[0]), bits(images[1]))
     pt.destroy()
 
-
-def test_cli_refuses(scene_cache, tmp_path):
-    spec = scenes.make_scene("tiny0", scene_cache, width=64, height=36)
-    other = scenes.make_scene("tiny2", scene_cache, width=64, height=36)
-    out = str(tmp_path / "o.exr")
-    tail = ("--spp", "1", "--out", out)
-    for args, word in ((("--morph-target", spec.obj_path), "go together"),
-                       (("--morph-weights", "0.5"), "go together"),
-                       (("--morph-target", spec.obj_path, "--morph-weights", "0.5,0.25"), "2 weights for 1"),
-                       (("--morph-target", spec.obj_path, "--morph-target", spec.obj_path, "--morph-weights", "0.5"), "1 weights for 2"),
-                       (("--morph-target", spec.obj_path, "--morph-weights", "0.5", "--pose", spec.obj_path), "--pose"),
-                       (("--morph-target", spec.obj_path, "--morph-weights", "0.5,"), "bad --morph-weights"),
-                       (("--morph-target", spec.obj_path, "--morph-weights", "half"), "bad --morph-weights")):
-        code, log = run(spec.config_path, *args, *tail)
-        assert code == 2 and word in log, (args, log)
-    # a target with another triangle count: an error, found before any device is asked for
-    code, log = run(spec.config_path, "--morph-target", other.obj_path, "--morph-weights", "1", *tail)
-    assert code == 1 and "has 5 triangles, the scene has 554" in log, log
-    code, log = run(spec.config_path, "--morph-target", str(tmp_path / "missing.obj"), "--morph-weights", "1", *tail)
-    assert code == 1 and "Unable to load morph target" in log, log
-    assert not os.path.exists(out)

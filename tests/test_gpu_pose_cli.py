@@ -54,11 +54,4 @@ def test_cli_part_matrices(scene_cache, tmp_path):
     lines = [line for line in log.splitlines() if line.startswith("[PT]POSE:")]
     assert len(lines) == 1 and re.match(r"\[PT\]POSE: parts %d triangles %d " % (n_parts, len(matid)), lines[0]), log
     assert np.array_equal(bits(api.load_exr(out)), bits(want))
-    # two ways to move the scene at once
-    r = subprocess.run([EXE, spec.config_path, "--part-matrices", table, "--pose", spec.obj_path, "--spp", "1", "--out", out], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert r.returncode == 2 and "--part-matrices" in r.stdout.decode(), r.stdout.decode()
-    # a part the scene does not have
-    with open(table, "a") as f:
-        f.write("%d 1 0 0 0 0 1 0 0 0 0 1 0\n" % n_parts)
-    r = subprocess.run([EXE, spec.config_path, "--part-matrices", table, "--spp", "1", "--out", out], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert r.returncode == 1 and "line" in r.stdout.decode(), r.stdout.decode()
+    # (two ways to move the scene at once, a part the scene does not have: tests/test_cli_options.py)

@@ -301,8 +301,4 @@ def test_cli(scene_cache, sobol_matrices, tmp_path):
     line = "[PT]TEMPORAL: history on %d of %d hit pixels, mean length %.3f, rectified %d pixels\n" % (took, int(hit.sum()), float(length[hit].astype(np.float64).mean()), int((kept < 1).sum()))
     assert line in text, text[-2000:]
     assert (kept < 1).sum() > 0
-    # the rectify options need --rectify, --rectify needs a temporal --denoise call, and parameters inside their ranges
-    for bad in (("--denoise", d_exr, "--rectify"), ("--rectify",), ("--denoise", d_exr, "--history-cap", "16", "--rectify-gamma", "1"),
-                ("--denoise", d_exr, "--history-cap", "16", "--rectify", "--rectify-radius", "4"), ("--denoise", d_exr, "--history-cap", "16", "--rectify", "--rectify-gamma", "nan")):
-        code, text = cli(*bad)
-        assert code == 2 and "--rectify" in text, text
+    # (what the command line refuses of these options: tests/test_cli_options.py)
