@@ -153,6 +153,11 @@ class MorphBinding(Struct):
     _fields_ = [("n_targets", C.c_int32), ("n_entries", C.c_int64), ("n_tris_touched", C.c_int64), ("device_bytes", C.c_int64)]
 
 
+class MeshBinding(Struct):
+    """adypt_mesh_binding."""
+    _fields_ = [("n_vertices", C.c_int64), ("n_tris", C.c_int64), ("max_valence", C.c_int32), ("device_bytes", C.c_int64)]
+
+
 # every symbol include/*.h declares, with its signature (tests/test_abi.py checks the export list against the headers)
 _SIGS = {
     # adypt_hip.h
@@ -288,6 +293,18 @@ _SIGS = {
     "adypt_multi_pose_morph": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
     "adypt_multi_unbind_morph": (C.c_int, [C.c_void_p]),
     "adypt_multi_get_morph_binding": (C.c_int, [C.c_void_p, C.POINTER(MorphBinding)]),
+    # an indexed mesh posed by its vertices
+    "adypt_bind_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "adypt_pose_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
+    "adypt_read_vertex_normals": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_get_mesh_timing": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
+    "adypt_unbind_mesh": (C.c_int, [C.c_void_p]),
+    "adypt_get_mesh_binding": (C.c_int, [C.c_void_p, C.POINTER(MeshBinding)]),
+    "adypt_multi_bind_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "adypt_multi_pose_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(BvhParams), C.POINTER(PosePolicy), C.POINTER(PoseOutcome)]),
+    "adypt_multi_read_vertex_normals": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_multi_unbind_mesh": (C.c_int, [C.c_void_p]),
+    "adypt_multi_get_mesh_binding": (C.c_int, [C.c_void_p, C.POINTER(MeshBinding)]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),
@@ -360,6 +377,9 @@ _SIGS = {
     "adypt_pose_triangles_morph": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_int32, C.c_void_p]),
     "adypt_morph_diff": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "adypt_mesh_normals": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "adypt_mesh_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adypt_weld_triangles": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adypt_decode_root_card": (None, [C.c_void_p, C.c_int, C.c_void_p]),
     "adypt_camera_matrices": (None, [C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "adypt_sobol_points": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),

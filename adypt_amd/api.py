@@ -344,6 +344,69 @@ def pose_triangles(triangles: np.ndarray, matrices, parts=None, joints=None, wei
     return out
 
 
+def _mesh_indices(who: str, indices, n_vertices: Optional[int]) -> Tuple[np.ndarray, int]:
+    """(int32 [n, 3], n_vertices) of an index buffer given as [n, 3] or flat; n_vertices None: the largest index + 1"""
+    i = np.ascontiguousarray(indices, dtype=np.int32)
+    if i.size % 3:
+        raise ValueError("%s: indices are three per triangle" % who)
+    i = i.reshape(-1, 3)
+    if n_vertices is None:
+        n_vertices = int(i.max()) + 1 if i.size else 0
+    return i, int(n_vertices)
+
+
+def _vertex_array(who: str, a) -> np.ndarray:
+    """float32 [n, 3] of one vector per vertex given as [n, 3] or flat"""
+    v = np.ascontiguousarray(a, dtype=np.float32)
+    if v.size % 3:
+        raise ValueError("%s: three floats per vertex" % who)
+    return v.reshape(-1, 3)
+
+
+def mesh_normals(indices, positions, n_vertices: Optional[int] = None) -> np.ndarray:
+    """adypt_mesh_normals, the host's side of PoseVertices() without normals (csrc/device/mesh.hpp): float32 [n_vertices, 3], a vertex's normal being
+    the sum of its triangles' area-weighted face vectors in ascending corner order, normalised where its length is a positive finite number.  A
+    vertex that no triangle names gets 0.  n_vertices None: len(positions)."""
+    p = _vertex_array("mesh_normals", positions)
+    i, nv = _mesh_indices("mesh_normals", indices, len(p) if n_vertices is None else n_vertices)
+    if nv != len(p):
+        raise ValueError("mesh_normals: %d positions for %d vertices" % (len(p), nv))
+    out = np.empty_like(p)
+    N.check_host(N.lib.adypt_mesh_normals(i.ctypes.data, len(i), nv, p.ctypes.data, out.ctypes.data))
+    return out
+
+
+def mesh_triangles(triangles: np.ndarray, indices, positions, normals=None) -> np.ndarray:
+    """adypt_mesh_triangles, the host's side of BindMesh() + PoseVertices(): the 100-byte triangles (uint8 [n * 100], or TRI_DT records) with every
+    corner's position and normal taken from its vertex — normals float32 [n_vertices, 3] used as given, or None: computed as mesh_normals() does.
+    Returns uint8 [n * 100]; texture coordinates and material ids stay.  What BindMesh / PoseVertices refuse raises AdyptError here."""
+    t = np.ascontiguousarray(triangles).view(np.uint8).reshape(-1)
+    p = _vertex_array("mesh_triangles", positions)
+    nrm = None if normals is None else _vertex_array("mesh_triangles", normals)
+    i, nv = _mesh_indices("mesh_triangles", indices, len(p))
+    if len(t) != 100 * len(i) or (nrm is not None and len(nrm) != len(p)):
+        raise ValueError("mesh_triangles: 100-byte triangles, three indices each, and one position (and normal) per vertex")
+    out = np.empty_like(t)
+    N.check_host(N.lib.adypt_mesh_triangles(t.ctypes.data, len(i), i.ctypes.data, nv, p.ctypes.data, None if nrm is None else nrm.ctypes.data, out.ctypes.data))
+    return out
+
+
+def weld_triangles(triangles: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """adypt_weld_triangles: the index buffer of a triangle soup (anything that came through the OBJ loader).  (indices int32 [n, 3], positions
+    float32 [n_vertices, 3], normals float32 [n_vertices, 3]); a vertex is a corner's position and normal compared as bits, numbered in order of
+    first appearance, so a crease — one position, two normals — stays two vertices.  mesh_triangles(t, *weld_triangles(t)) has t's bytes."""
+    t = np.ascontiguousarray(triangles).view(np.uint8).reshape(-1)
+    if len(t) % 100:
+        raise ValueError("weld_triangles: an array of 100-byte triangles")
+    n = len(t) // 100
+    nv = N.lib.adypt_weld_triangles(t.ctypes.data, n, None, None, None)
+    if nv < 0:
+        N.check_host(int(nv))
+    idx, p, nrm = np.empty((n, 3), dtype=np.int32), np.empty((nv, 3), dtype=np.float32), np.empty((nv, 3), dtype=np.float32)
+    N.lib.adypt_weld_triangles(t.ctypes.data, n, idx.ctypes.data, p.ctypes.data, nrm.ctypes.data)
+    return idx, p, nrm
+
+
 # struct RootCard (csrc/device/root_card.hpp), 264 bytes; q[child] = float(qlo x, qhi x, qlo y, qhi y, qlo z, qhi z)
 ROOT_CARD_DT = np.dtype([("q", "<f4", (8, 6)), ("scale", "<f4", 3), ("origin", "<f4", 3), ("child_base", "<u4"), ("tri_base", "<u4"), ("imask", "<u4"),
                          ("inner_only", "<u4"), ("enabled", "<u4"), ("pad", "<u4"), ("is_inner", "u1", 8), ("bit_index", "u1", 8), ("child_bits", "u1", 8)])
@@ -868,6 +931,57 @@ class _Tracer:
         """kind (0 none, 1 parts, 2 skin), n_matrices, n_tris and device_bytes of the binding of the (first) device."""
         out = N.PoseBinding()
         self._call("get_pose_binding", C.byref(out))
+        return out.as_dict()
+
+    # ---- an indexed mesh posed by its vertices (adypt_bind_mesh, adypt_pose_vertices, include/adypt_hip.h; the definition: csrc/device/mesh.hpp) ----
+    def BindMesh(self, indices: np.ndarray, n_vertices: Optional[int] = None) -> None:
+        """Every triangle corner names a vertex (int32 [n, 3], 0 <= index < n_vertices; n_vertices None: the largest index + 1).  PoseVertices()
+        then moves the mesh by one position per vertex.  No rest pose is captured.  Replaces an earlier mesh binding and is independent of
+        BindParts() / BindSkin(); nothing changes when the call is refused.  weld_triangles() makes the indices of a soup.  Several devices: on
+        every device."""
+        i, nv = _mesh_indices("BindMesh", indices, n_vertices)
+        self._call("bind_mesh", i.ctypes.data, len(i), nv)
+
+    def PoseVertices(self, positions: np.ndarray, normals: Optional[np.ndarray] = None, rebuild_above: Optional[float] = None, method: str = "ploc",
+                     radius: int = 8, split_budget: float = 0.0, cfg: Optional[N.BvhParams] = None) -> Optional[dict]:
+        """The bound mesh at new vertex positions (float32 [n_vertices, 3]) and, when given, vertex normals (used as given): 12 or 24 bytes per
+        vertex cross the bus, the device writes positions and normals into every triangle's record and refits as UpdateTriangles() does.
+        normals None: smooth normals are computed on the device (area-weighted, summed per vertex in a fixed order).  mesh_triangles() is the
+        same arithmetic on the host, bit for bit.  rebuild_above and the arguments after it, and what is returned: as for UpdateTriangles()."""
+        p = _vertex_array("PoseVertices", positions)
+        nrm = None if normals is None else _vertex_array("PoseVertices", normals)
+        if nrm is not None and len(nrm) != len(p):
+            raise ValueError("PoseVertices: positions and normals differ in length")
+        args = (p.ctypes.data, None if nrm is None else nrm.ctypes.data, len(p))
+        if rebuild_above is None:
+            self._call("pose_vertices", *args, None, None, None)
+            return None
+        return self._under_policy("PoseVertices", "pose_vertices", args, rebuild_above, cfg, method, radius, split_budget)
+
+    def ReadVertexNormals(self) -> np.ndarray:
+        """float32 [n_vertices, 3]: the vertex normals of the last PoseVertices(), computed or given, as the (first) device holds them."""
+        out = np.empty((self.GetMeshBinding()["n_vertices"], 3), dtype=np.float32)
+        self._call("read_vertex_normals", out.ctypes.data)
+        return out
+
+    def GetMeshTiming(self) -> dict:
+        """HIP-event milliseconds of the stages of the last PoseVertices() on the (first) device: upload, faces, normals (both 0 with given
+        normals), records.  Together they are GetRefitTiming()'s "scatter"."""
+        ms = (C.c_float * 4)()
+        c = self._contexts()[0]
+        n = N.lib.adypt_get_mesh_timing(c, ms, 4)
+        if n < 0:
+            N.check(n, c)
+        return {"upload": ms[0], "faces": ms[1], "normals": ms[2], "records": ms[3]}
+
+    def UnbindMesh(self) -> None:
+        """Gives the mesh binding back; the triangles stay as the last PoseVertices() left them."""
+        self._call("unbind_mesh")
+
+    def GetMeshBinding(self) -> dict:
+        """n_vertices (0: none), n_tris, max_valence and device_bytes of the mesh binding of the (first) device."""
+        out = N.MeshBinding()
+        self._call("get_mesh_binding", C.byref(out))
         return out.as_dict()
 
     def GetTreeCost(self, cfg: Optional[N.BvhParams] = None) -> dict:

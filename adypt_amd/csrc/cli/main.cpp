@@ -26,6 +26,8 @@ struct Session
 	adypt_bvh *bvh = nullptr;
 	adypt_multi *multi = nullptr;
 	std::vector<float> pose_positions, pose_normals; // --pose: what replaces the scene's vertices and normals once the context exists
+	std::vector<int32_t> mesh_indices;               // --by-vertices: the scene as loaded, welded; pose_positions and pose_normals are then per vertex
+	int64_t n_vertices = 0;
 	std::vector<int32_t> part_of_triangle;           // --part-matrices: the binding and one matrix per part, the identity where FILE names none
 	std::vector<float> part_matrix;
 	int32_t n_parts = 0;
@@ -93,6 +95,37 @@ static bool load_scene(Session &s)
 	return true;
 }
 
+// --by-vertices: the scene as loaded welded into an indexed mesh, and the pose's corners gathered into one position and one normal per vertex — those
+// of the corner at which the vertex first appeared in the weld.  A pose that gives another corner of a vertex other position bits tears it: refused.
+static bool pose_by_vertices(Session &s)
+{
+	s.mesh_indices.resize((size_t)s.n_tris * 3);
+	s.n_vertices = adypt_weld_triangles(s.tris, s.n_tris, s.mesh_indices.data(), nullptr, nullptr);
+	if(s.n_vertices < 0) return host_failed();
+	std::vector<float> positions((size_t)s.n_vertices * 3), normals((size_t)s.n_vertices * 3);
+	int64_t seen = 0; // (vertices are numbered in order of first appearance)
+	for(int64_t corner = 0; corner < s.n_tris * 3; ++corner)
+	{
+		const int64_t v = s.mesh_indices[(size_t)corner];
+		const size_t at = (size_t)(corner / 3) * 9 + (size_t)(corner % 3) * 3;
+		if(v == seen)
+		{
+			memcpy(&positions[(size_t)v * 3], &s.pose_positions[at], 12);
+			memcpy(&normals[(size_t)v * 3], &s.pose_normals[at], 12);
+			++seen;
+		}
+		else if(memcmp(&positions[(size_t)v * 3], &s.pose_positions[at], 12) != 0)
+		{
+			fprintf(stderr, "[INSTANCE]Err: pose %s tears vertex %lld, which the scene shares: corner %lld of triangle %lld has another position than its first corner\n", s.opt.pose.c_str(), (long long)v,
+			        (long long)(corner % 3), (long long)(corner / 3));
+			return false;
+		}
+	}
+	s.pose_positions.swap(positions);
+	s.pose_normals.swap(normals);
+	return true;
+}
+
 static bool load_pose(Session &s)
 {
 	const std::string &pose = s.opt.pose;
@@ -110,7 +143,7 @@ static bool load_pose(Session &s)
 		memcpy(&s.pose_normals[(size_t)i * 9], (const uint8_t *)mt + i * 100 + 36, 36);
 	}
 	adypt_scene_free(moved);
-	return true;
+	return !s.opt.by_vertices || pose_by_vertices(s);
 }
 
 // parts by material id, every matrix the identity but those the table of --part-matrices names
@@ -271,7 +304,21 @@ static bool move_scene(Session &s)
 	const adypt_pose_policy *policy = o.rebuild_above ? &o.policy : nullptr;
 	adypt_pose_outcome outcome;
 	float ms[4] = {0, 0, 0, 0};
-	if(!o.pose.empty())
+	if(o.by_vertices)
+	{
+		const float *normals = o.recompute_normals ? nullptr : s.pose_normals.data();
+		adypt_mesh_binding mesh;
+		memset(&mesh, 0, sizeof(mesh));
+		int code = adypt_multi_bind_mesh(multi, s.mesh_indices.data(), s.n_tris, s.n_vertices);
+		if(code == ADYPT_OK) code = adypt_multi_get_mesh_binding(multi, &mesh);
+		if(code == ADYPT_OK) code = adypt_multi_pose_vertices(multi, s.pose_positions.data(), normals, s.n_vertices, &cfg.bvh, policy, &outcome);
+		if(code != ADYPT_OK) return tracer_failed(multi);
+		(void)adypt_get_refit_timing(adypt_multi_context(multi, 0), ms, 4);
+		printf("[PT]MESH: vertices %lld triangles %lld max_valence %d normals %s\n", (long long)mesh.n_vertices, (long long)mesh.n_tris, (int)mesh.max_valence, normals ? "given" : "computed");
+		printf("[PT]INFO: pose %s by vertices: refit %.3f ms (upload and mesh kernels %.3f, references and Woop %.3f, nodes %.3f)\n", o.pose.c_str(), ms[3], ms[0], ms[1], ms[2]);
+		print_pose_policy(s, outcome);
+	}
+	else if(!o.pose.empty())
 	{
 		const int code = policy ? adypt_multi_update_triangles_auto(multi, 0, s.n_tris, s.pose_positions.data(), s.pose_normals.data(), &cfg.bvh, policy, &outcome)
 		                        : adypt_multi_update_triangles(multi, 0, s.n_tris, s.pose_positions.data(), s.pose_normals.data());

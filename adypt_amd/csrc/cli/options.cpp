@@ -5,6 +5,13 @@
 //              [PT]BUILD: line reports it.  --pose and --rebuild-above work after it as they do otherwise; a bare --rebuild with it, or any other word than gpu (or host, the default), is exit 2
 //   --pose moved.obj: the scene of the config (and its cached .bvh) with the vertices and normals of moved.obj — the same triangles in the same order,
 //              moved — through adypt_multi_update_triangles: the BVH and the Woop data are refitted on the GPU, nothing is rebuilt
+//   --by-vertices: with --pose only (else exit 2): the same pose by another road.  The scene as loaded is welded (adypt_weld_triangles) and bound as an
+//              indexed mesh (adypt_multi_bind_mesh); vertex v takes its position and normal from moved.obj's corner at the place where v first appeared
+//              in the weld, and the pose goes through adypt_multi_pose_vertices: 24 B per vertex cross the bus instead of 72 B per triangle.  A pose
+//              that tears a vertex the scene shares — another corner of v has other position bits in moved.obj — is refused with one line naming the
+//              vertex, exit 1.  --recompute-normals (with --by-vertices only, else exit 2): no normals are passed and the device computes smooth ones,
+//              the only way to pose with an OBJ that carries none.  One [PT]MESH: line reports vertices, triangles, the largest valence and where
+//              the normals came from.  --rebuild-above and --follow-motion act as with --pose
 //   --part-matrices FILE: the scene moved on the GPU, part by part (adypt_multi_bind_parts, adypt_multi_pose): a triangle's part is its material id, and
 //              triangles without a material (id -1) are one extra last part.  FILE holds lines `part m00 m01 m02 m03 m10 ... m23` (a row-major 3x4
 //              matrix: three linear entries and the translation per row; # starts a comment); parts that are not listed stay where they are.  One
@@ -67,7 +74,7 @@ const char *const USAGE =
 	"scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] "
 	"[--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] "
 	"[--history-from other.config]... [--history-cap C] [--history-out len.exr] [--follow-motion] [--rectify [--rectify-gamma G] [--rectify-radius R] "
-	"[--rectify-out kept.exr]]] [--guides-out PREFIX] [--pose moved.obj | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] "
+	"[--rectify-out kept.exr]]] [--guides-out PREFIX] [--pose moved.obj [--by-vertices [--recompute-normals]] | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] "
 	"[--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]";
 
 // ---- values ----
@@ -188,6 +195,8 @@ static const struct Spec { const char *name; bool value; Apply apply; } SPECS[] 
 	{"--rectify-gamma", true, rectify_gamma},
 	{"--guides-out", true, text<&Options::guides_out>},
 	{"--pose", true, text<&Options::pose>},
+	{"--by-vertices", false, flag<&Options::by_vertices>},
+	{"--recompute-normals", false, flag<&Options::recompute_normals>},
 	{"--part-matrices", true, text<&Options::part_matrices>},
 	{"--morph-target", true, one_more<&Options::morph_targets>},
 	{"--morph-weights", true, morph_weights},
@@ -235,6 +244,8 @@ int check_options(Options *opt)
 	if(method != "linear" && method != "ploc") return refuse("--rebuild-method is linear or ploc");
 	if(o.split_budget && method != "ploc") return refuse("--split-budget needs --rebuild-method ploc");
 	if(!o.pose.empty() && !o.part_matrices.empty()) return refuse("--pose and --part-matrices are two ways to move the scene: give one");
+	if(o.by_vertices && o.pose.empty()) return refuse("--by-vertices needs --pose moved.obj");
+	if(o.recompute_normals && !o.by_vertices) return refuse("--recompute-normals needs --pose moved.obj --by-vertices");
 	if(o.morphing != !o.morph_weights.empty()) return refuse("--morph-target FILE.obj and --morph-weights w0,w1,... go together");
 	if(o.morphing && o.morph_weights.size() != o.morph_targets.size()) { fprintf(stderr, "--morph-weights has %d weights for %d --morph-target\n", (int)o.morph_weights.size(), (int)o.morph_targets.size()); return 2; }
 	if(o.morphing && !o.pose.empty()) return refuse("--morph-target morphs the scene as loaded: not together with --pose");

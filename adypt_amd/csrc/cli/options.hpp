@@ -33,6 +33,7 @@ struct Options
 	adypt_rectify_params rectify_params{3, 1.0f};
 	std::string rectify_out;
 	std::string pose, part_matrices;
+	bool by_vertices = false, recompute_normals = false; // --pose by the mesh binding; its normals computed on the device
 	std::vector<std::string> morph_targets;
 	std::vector<float> morph_weights; // (a list that parses is never empty)
 	bool bare_rebuild = false, build_on_gpu = false;

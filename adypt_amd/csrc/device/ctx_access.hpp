@@ -36,7 +36,7 @@ struct Attachment {
 	~Attachment() { reset(); }
 	void reset(void *q = nullptr, void (*f)(void *) = nullptr) { if(p && free_fn) free_fn(p); p = q; free_fn = f; }
 };
-enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachBuild, kAttachGeometry, kAttachPose, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes, build.hip's scratch, geometry.hip's staging, pose.hip's rest pose and binding
+enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachBuild, kAttachGeometry, kAttachPose, kAttachMesh, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes, build.hip's scratch, geometry.hip's staging, pose.hip's rest pose and binding, mesh.hip's index buffer and incidence lists
 Attachment &ctx_attachment(adypt_ctx *c, AttachKind kind);
 
 // ---- noise statistics and adaptive sampling, per context (adypt_trace_adaptive and adypt_multi_trace_adaptive are one loop over these) ----

@@ -11,6 +11,7 @@
 //                         per-reference copy and count in one step (ctx_replace_geometry), so a refused or failed call leaves the old scene traceable.
 #include "ctx_unit.hpp"
 #include "build_internal.hpp"
+#include "mesh_internal.hpp"
 #include "pose_internal.hpp"
 #include "denoise_internal.hpp"
 #include "tri_record.hpp"
@@ -124,6 +125,7 @@ int set_triangles(adypt_ctx *c, const char *who, const void *triangles, int64_t 
 	CTX_STEP(build_for_triangles(c, q, who, (const float4 *)records.get(), &geometry, out));
 	g->timer.complete(); // (the build has waited for the stream)
 	pose_drop_binding(c); // (a rest pose and a binding were the old triangles': pose.hip)
+	mesh_drop_binding(c); // (and so were an index buffer and its incidence lists: mesh.hip)
 	denoise_triangles_replaced(c); // (and so was what the temporal merge followed moved geometry by: denoise.hip)
 	return ADYPT_OK; // (the old records and class bytes go with `records` and `classes`)
 }

@@ -399,7 +399,7 @@ int adypt_get_denoise_rectify(adypt_ctx *ctx, adypt_denoise_rectify *out);
 int adypt_update_triangles(adypt_ctx *ctx, int64_t first, int64_t count, const float *positions, const float *normals);
 /* the node array (n_nodes x 80 bytes) and the Woop array (n_refs x 12 floats) as they are on the device; either may be NULL */
 int adypt_read_bvh(adypt_ctx *ctx, void *nodes_out, float *woop_out);
-/* HIP-event times of the last adypt_update_triangles (or adypt_pose, below) in ms: [0] the upload and scatter of the new data (the matrices and k_pose), [1] the per-reference records and the Woop
+/* HIP-event times of the last adypt_update_triangles (or adypt_pose, adypt_pose_vertices, below) in ms: [0] the upload and scatter of the new data (the matrices and k_pose; the vertices and the mesh kernels), [1] the per-reference records and the Woop
  * data, [2] the nodes (every level), [3] all of it.  Returns the number of entries and writes them only when capacity holds them all. */
 int adypt_get_refit_timing(adypt_ctx *ctx, float *ms, int capacity);
 
@@ -602,6 +602,47 @@ int adypt_pose_morph(adypt_ctx *ctx, const float *matrices /* n_matrices x 12 */
 int adypt_unbind_morph(adypt_ctx *ctx);
 int adypt_get_morph_binding(adypt_ctx *ctx, adypt_morph_binding *out);
 
+/* ---- vertex animation: bind an indexed mesh once, pose it by one position (and normal) per vertex ---------------------------------------------
+ * The third way a mesh moves, for poses that are neither matrices nor blend weights (cloth, a soft body, a baked vertex cache, a simulation's
+ * output): adypt_bind_mesh gives every triangle corner a vertex (indices[3 t + c] in [0, n_vertices), n_vertices in [1, 2^31 - 1]; a triangle may
+ * name one vertex twice, a vertex that no triangle names is never read); adypt_pose_vertices then uploads 12 B per VERTEX of positions and, unless
+ * normals is NULL, 12 B of normals, writes words 0..17 of every record and refits as adypt_pose does.  Given normals are used as given, not
+ * normalised.  normals NULL: smooth normals are computed on the device — the area-weighted face vectors of a vertex's triangles summed in ascending
+ * 3 t + c and normalised by pose_normal's rule.  The arithmetic is csrc/device/mesh.hpp, which the host's adypt_mesh_normals and adypt_mesh_triangles
+ * (adypt_host.h) compile too: adypt_read_triangle_records afterwards equals adypt_pack_triangles of adypt_mesh_triangles' triangles byte for byte,
+ * adypt_read_vertex_normals equals adypt_mesh_normals on every vertex a triangle names (given normals come back as given), and nodes and Woop data
+ * equal adypt_bvh_refit + adypt_woop_matrices, as after adypt_update_triangles.  adypt_weld_triangles (adypt_host.h) makes the index buffer of a soup.
+ * A pose never reads the records, so poses do not compound, and a bind captures no rest pose.  adypt_get_refit_timing answers afterwards, [0]
+ * covering the upload and the mesh kernels.  policy NULL: refit only (params is not looked at, *outcome is zeroed); with a policy the call behaves as
+ * adypt_update_triangles_auto does around its update.
+ * ADYPT_E_INVALID, checked on the host before the device is touched, nothing changes (a refused or failed bind leaves the old binding in place, the
+ * new one being complete before it replaces the old): a null array; n_tris other than the context's count; n_vertices out of range; an index out of
+ * range; at pose time another vertex count than the binding's, a position or a given normal that is not finite, and what
+ * adypt_update_triangles_auto refuses of a policy.  adypt_pose_vertices without a binding, and adypt_read_vertex_normals before the binding's first
+ * pose: ADYPT_E_STATE.
+ * Lifetime: independent of the pose binding — adypt_pose, adypt_update_triangles and adypt_pose_vertices each write the records and the last call
+ * stands; an adypt_bind_parts or adypt_bind_skin made after a vertex pose captures the records as that pose left them.  adypt_rebuild_bvh* keep the
+ * binding (a triangle keeps its index); a successful adypt_set_triangles drops it; adypt_destroy frees it.
+ * Memory, kept until adypt_unbind_mesh, adypt_set_triangles or adypt_destroy: 40 B per triangle (12 of indices in planes, 12 of incidence list, 16 of
+ * face vector) and 32 B per vertex (8 of offset, 12 of staged positions, 12 of normals) + 8. */
+typedef struct adypt_mesh_binding {
+	int64_t n_vertices;          /* 0: none */
+	int64_t n_tris;
+	int32_t max_valence;         /* the longest incidence list */
+	int64_t device_bytes;        /* what the binding holds on the device */
+} adypt_mesh_binding;
+int adypt_bind_mesh(adypt_ctx *ctx, const int32_t *indices /* n_tris x 3 */, int64_t n_tris, int64_t n_vertices);
+int adypt_pose_vertices(adypt_ctx *ctx, const float *positions /* n_vertices x 3 */, const float *normals /* n_vertices x 3, or NULL: computed */, int64_t n_vertices,
+                        const adypt_bvh_params *params, const adypt_pose_policy *policy /* NULL: refit only */, adypt_pose_outcome *outcome /* may be NULL */);
+int adypt_read_vertex_normals(adypt_ctx *ctx, float *normals /* n_vertices x 3: of the last adypt_pose_vertices, computed or given */);
+/* HIP-event times of the stages of the last adypt_pose_vertices in ms: [0] the upload, [1] k_mesh_faces, [2] k_mesh_normals (both exactly 0 with
+ * given normals: the kernels do not run and no event is recorded for them), [3] k_mesh_records; together they are [0] of adypt_get_refit_timing.
+ * Per context, like adypt_get_refit_timing: of several devices, ask adypt_multi_context(m, k).  Returns the number of entries and writes them only when capacity
+ * holds them all; ADYPT_E_STATE before the first vertex pose. */
+int adypt_get_mesh_timing(adypt_ctx *ctx, float *ms, int capacity);
+int adypt_unbind_mesh(adypt_ctx *ctx);
+int adypt_get_mesh_binding(adypt_ctx *ctx, adypt_mesh_binding *out);
+
 /* Trace an arbitrary batch of rays through the same traversal kernel: rays = n x 8 floats
  * (ox, oy, oz, tmin, dx, dy, dz, unused).  with_stats selects the instrumented kernel variant. */
 int adypt_trace_rays(adypt_ctx *ctx, const float *rays, int64_t n, adypt_hit *hits, int with_stats);
@@ -756,6 +797,14 @@ int adypt_multi_pose_morph(adypt_multi *m, const float *matrices, int32_t n_matr
                            const adypt_pose_policy *policy, adypt_pose_outcome *outcome);
 int adypt_multi_unbind_morph(adypt_multi *m);
 int adypt_multi_get_morph_binding(adypt_multi *m, adypt_morph_binding *out);
+/* adypt_bind_mesh / adypt_pose_vertices / adypt_unbind_mesh on every device in the same way; adypt_multi_read_vertex_normals and
+ * adypt_multi_get_mesh_binding: the first device's. */
+int adypt_multi_bind_mesh(adypt_multi *m, const int32_t *indices, int64_t n_tris, int64_t n_vertices);
+int adypt_multi_pose_vertices(adypt_multi *m, const float *positions, const float *normals, int64_t n_vertices, const adypt_bvh_params *params, const adypt_pose_policy *policy,
+                              adypt_pose_outcome *outcome);
+int adypt_multi_read_vertex_normals(adypt_multi *m, float *normals);
+int adypt_multi_unbind_mesh(adypt_multi *m);
+int adypt_multi_get_mesh_binding(adypt_multi *m, adypt_mesh_binding *out);
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

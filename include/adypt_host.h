@@ -178,6 +178,23 @@ int adypt_pose_triangles_morph(const void *triangles_in, int64_t n_tris, const i
  * listed triangle).  Returns their number; either output may be NULL (both NULL: the size only, at most n_tris).  Weight 1 then gives
  * rest + (target - rest), which is the target only up to one rounding.  ADYPT_E_INVALID (negative) for a null input or a negative count. */
 int64_t adypt_morph_diff(const void *rest, const void *target, int64_t n_tris, int32_t *triangle_out, float *deltas_out);
+/* The smooth normals of an indexed mesh (csrc/device/mesh.hpp, which the device — adypt_pose_vertices of adypt_hip.h without normals — compiles too:
+ * both give the same bits): indices n_tris x 3, each in [0, n_vertices); positions and normals_out n_vertices x 3 floats.  A vertex's normal is the
+ * sum of its triangles' area-weighted face vectors in ascending 3 t + c, divided by its length where that is a positive finite number; a vertex that
+ * no triangle names gets +0.  ADYPT_E_INVALID — nothing is written — for a null array, a negative n_tris, n_vertices outside [1, 2^31 - 1], an index
+ * out of range or a position that is not finite. */
+int adypt_mesh_normals(const int32_t *indices, int64_t n_tris, int64_t n_vertices, const float *positions, float *normals_out);
+/* `n_tris` 100-byte Triangles with words 0..17 replaced by the mesh: corner c of triangle t takes positions[indices[3 t + c]] and that vertex's
+ * normal — given (used as given; finite), or with normals_or_null NULL computed as adypt_mesh_normals does.  Texture coordinates and material ids
+ * stay.  The host's side of adypt_bind_mesh + adypt_pose_vertices.  ADYPT_E_INVALID — nothing is written — for what those two refuse. */
+int adypt_mesh_triangles(const void *triangles_in, int64_t n_tris, const int32_t *indices, int64_t n_vertices, const float *positions, const float *normals_or_null,
+                         void *triangles_out);
+/* The index buffer of a triangle soup.  A vertex is the 24 bytes of a corner's position and normal, compared as bits; vertices are numbered in order
+ * of first appearance over corners in ascending 3 t + c, so corners at one position with different normals (a crease) stay different vertices.
+ * Returns n_vertices; any output may be NULL (all NULL: the size only, at most 3 n_tris): indices_out n_tris x 3, positions_out and normals_out
+ * n_vertices x 3 floats.  adypt_mesh_triangles of the three arrays has the soup's bytes.  ADYPT_E_INVALID (negative) for a null input or 3 n_tris
+ * outside [0, 2^31 - 1]. */
+int64_t adypt_weld_triangles(const void *triangles, int64_t n_tris, int32_t *indices_out, float *positions_out, float *normals_out);
 /* Camera::GetView/GetProjection + the inverses of SetCamera (src/Tracer/Camera.cpp:13-23, OglPathTracer.cpp:27-32) */
 void adypt_camera_matrices(float fov, float yaw, float pitch, int width, int height, float inv_proj[16], float inv_view[16]);
 /* Sobol::Next (src/Util/Sobol.cpp:16-21): points of frames [first, first+n), dim <= 64; out = n*dim floats */

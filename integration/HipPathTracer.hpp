@@ -357,6 +357,39 @@ public:
 		return false;
 	}
 
+	// Poses given by vertices (adypt_hip.h, adypt_bind_mesh / adypt_pose_vertices): for a mesh that neither matrices nor blend weights move — cloth, a
+	// soft body, a vertex cache.  BindMesh gives every corner of Scene::GetTriangles() a vertex (three indices per triangle, each below n_vertices;
+	// adypt_weld_triangles of adypt_host.h makes them from the soup); PoseVertices then uploads one position per vertex (3 floats) and, unless normals
+	// is empty, one normal per vertex (used as given); with normals empty the device computes smooth normals itself.  The tree is refitted as
+	// UpdateTriangles refits it.  Independent of BindParts / BindSkin: whoever wrote the records last stands.  A refused call leaves an earlier mesh
+	// binding in place; SetTriangles drops it.
+	bool BindMesh(const std::vector<int32_t> &indices, int64_t n_vertices)
+	{
+		if(indices.size() % 3 == 0 && adypt_multi_bind_mesh(m_gpus, indices.data(), (int64_t)(indices.size() / 3), n_vertices) == ADYPT_OK) return true;
+		printf("[PT]ERR: %s\n", indices.size() % 3 ? "BindMesh: indices are three per triangle" : adypt_multi_last_error(m_gpus));
+		return false;
+	}
+	bool PoseVertices(const std::vector<float> &positions, const std::vector<float> &normals = std::vector<float>())
+	{
+		const bool shaped = positions.size() % 3 == 0 && (normals.empty() || normals.size() == positions.size());
+		if(shaped && adypt_multi_pose_vertices(m_gpus, positions.data(), normals.empty() ? nullptr : normals.data(), (int64_t)(positions.size() / 3), nullptr, nullptr, nullptr) == ADYPT_OK)
+			return true;
+		printf("[PT]ERR: %s\n", shaped ? adypt_multi_last_error(m_gpus) : "PoseVertices: three floats per vertex, as many normals as positions or none");
+		return false;
+	}
+	// ... and decides about a rebuild itself, as the UpdateTriangles overload above does
+	bool PoseVertices(const std::vector<float> &positions, const std::vector<float> &normals, const PosePolicy &policy, adypt_pose_outcome *outcome = nullptr,
+	                  const adypt_bvh_params *params = nullptr)
+	{
+		const adypt_pose_policy p = policy.abi();
+		const bool shaped = positions.size() % 3 == 0 && (normals.empty() || normals.size() == positions.size());
+		if(shaped && adypt_multi_pose_vertices(m_gpus, positions.data(), normals.empty() ? nullptr : normals.data(), (int64_t)(positions.size() / 3), params, &p, outcome) == ADYPT_OK)
+			return true;
+		printf("[PT]ERR: %s\n", shaped ? adypt_multi_last_error(m_gpus) : "PoseVertices: three floats per vertex, as many normals as positions or none");
+		return false;
+	}
+	bool UnbindMesh() { return adypt_multi_unbind_mesh(m_gpus) == ADYPT_OK; }
+
 	// The image through the denoiser with its history across poses (adypt_hip.h, adypt_denoise_temporal): W x H x 3 floats into *rgb.  Needs
 	// SetNoiseStats(true) and GetSPP() >= 2.  commit: this call's state becomes the history (once per pose: after tracing, before the camera or the
 	// scene changes).  followMotion (adypt_denoise_temporal_motion): a committing call also keeps every triangle's positions and normals, and a later
