@@ -1,8 +1,9 @@
 /* TEST INFRASTRUCTURE — C-ABI of adypt_amd/libadypt_probe.so: the device helpers of csrc/device (canon_math.hpp, shade.hpp, noise.hpp), one
  * entry per helper, so that tests/test_gpu_device_probes.py can hold each of them against the oracle's piece (oracle/oracle.cpp: orc_*) and
- * against truths that need neither side.  The product never links, loads or calls this library.
+ * against truths that need neither side; and, at the end, the denoiser's kernels on images a test makes.  The product never links, loads or calls
+ * this library.
  *
- * Every entry: host pointers in and out, n elements (0 <= n <= 2^24).  It allocates, copies in, launches ONE grid of 256-thread workgroups
+ * Every entry of the helpers: host pointers in and out, n elements (0 <= n <= 2^24).  It allocates, copies in, launches ONE grid of 256-thread workgroups
  * (element i = thread i), synchronises, copies out and frees; nothing is kept between calls, nothing is read from the environment.
  * Returns 0, or the negative hipError_t of the first call that failed (-1 = hipErrorInvalidValue for a bad n, size or null pointer).
  * Arrays of vectors are packed: 3 floats per element for directions and colours, 2 for Sobol points and V2 pairs. */
@@ -42,6 +43,32 @@ int adypt_probe_display(const float *rgba, int viewer_type, uint32_t *out, int64
 /* per element: noise_add_sample over its k samples (samples[(i * k + j) * 3 ..], frame index first + j) from moments (0, 0), then
  * noise_of_pixel(moments, n_frames).  0 <= k <= 4096. */
 int adypt_probe_noise(const float *samples, int k, int first, int n_frames, float *mean, float *m2, float *e, int64_t n);
+
+/* ---- The denoiser's kernels (csrc/device/denoise_kernels.hpp, the header denoise.hip compiles), one entry per kernel, each launched ONCE with the
+ * grid and workgroup of the header's *_launch function, which denoise.hip launches it with too; tests/test_gpu_denoise_probes.py.
+ * Images are row-major, width x height (1..4096 each) float4 per pixel unless said otherwise: X0 = (D.rgb, V), X1 = (N.xyz, hit), X2 = (P.xyz, n),
+ * XA = (A.rgb, .).  Block-major arrays hold 1024 elements per block of `blocks` (n_blocks entries, 1..4096, each a block of the picture's grid of
+ * 32 x 32 blocks, in any order; anything else is refused with -1): float4 per local pixel, `moments` float2, `hits` the primary-hit float4 whose .x
+ * holds the triangle index as bits.  Every output is filled with the word 0x7fc0dead (a quiet NaN) before the launch: what no thread wrote keeps it. */
+int adypt_probe_denoise_prepare(const float *accum, const float *moments, const float *albedo, const float *normal, const float *position, const float *hits, const int32_t *blocks,
+                                const int32_t *block_spp, int n_blocks, int width, int height, float *x0, float *x1, float *x2, float *xa);
+/* k_atrous<last != 0>, 1 <= step <= 64: out is the next X0, or with `last` the width x height x 3 result */
+int adypt_probe_atrous(const float *x0, const float *x1, const float *x2, const float *xa, int width, int height, int step, float sigma_l, float sigma_z, int last, float *out);
+/* k_rectify_window<radius>, radius 1..3; origin: the current camera's, 3 floats */
+int adypt_probe_rectify_window(int radius, const float *x0, const float *x1, const float *x2, const float *xa, int width, int height, const float *origin, float *r0, float *r1);
+/* k_temporal_merge<motion != 0, rectify != 0>.  The history H0 H1 H2 HA and whether there is one (`have`), its raw camera (origin 3, inv_proj 16,
+ * inv_view 16 floats: temporal_camera is called here); xp, xn looked at only with motion, r0, r1, gamma and kept only with rectify (null otherwise).
+ * Out: merged, X2 as the kernel leaves it (n_out in .w; not pre-filled: the kernel updates it in place), length and kept (one float per pixel). */
+int adypt_probe_temporal_merge(int motion, int rectify, const float *x0, const float *x1, const float *x2, const float *xa, const float *h0, const float *h1, const float *h2, const float *ha,
+                               int have, const float *origin, const float *inv_proj, const float *inv_view, float history_cap, const float *xp, const float *xn, const float *r0,
+                               const float *r1, float gamma, int width, int height, float *merged, float *x2_out, float *length, float *kept);
+/* k_motion_gather.  snapshot: n_known elements of 5 float4; records: n_records >= n_known elements of tri_float4 (5..64) float4.  Both tables lie on
+ * the device between 64 triangles of slack filled with 12345.0f, so that an index guard that fails shows as wrong words; a hit word outside
+ * [-32, n_known + 32) is refused with -1. */
+int adypt_probe_motion_gather(const float *hits, const float *normal, const float *position, const int32_t *blocks, int n_blocks, int width, int height, const float *snapshot,
+                              int64_t n_known, const float *records, int64_t n_records, int tri_float4, float *xp, float *xn);
+/* k_motion_snapshot: n_tris (1..2^20) records of tri_float4 float4 -> n_tris elements of 5 float4 */
+int adypt_probe_motion_snapshot(const float *records, int tri_float4, int64_t n_tris, float *snapshot);
 
 #ifdef __cplusplus
 }

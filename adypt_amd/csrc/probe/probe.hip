@@ -2,9 +2,12 @@
 // with the very flags of the product's device code (csrc/Makefile: DEVICE_CC), so that the helpers run here in the float mode and with the inline
 // assembly they have inside the traversal and shading kernels.  Nothing of this is linked into libadypt_hip.so.
 //
-// Every kernel: thread i handles element i and touches nothing but element i of its arrays (the one table — the texture — is indexed by
+// At the end of the file: the denoiser's own kernels (denoise_kernels.hpp, the header denoise.hip compiles), launched as the product launches them.
+//
+// Every helper kernel: thread i handles element i and touches nothing but element i of its arrays (the one table — the texture — is indexed by
 // sample_texture itself, whose indices are wrapped into the texture).  Every entry checks n, every HIP call and the launch.
 #include "../device/shade.hpp"
+#include "../device/denoise_kernels.hpp"
 #include "probe.h"
 
 #include <vector>
@@ -37,6 +40,13 @@ public:
 		const hipError_t e = alloc(bytes);
 		return e != hipSuccess ? e : hipMemset(p_, 0, bytes_);
 	}
+	// `bytes` (a multiple of 4) of the 32-bit word `word`: an output in which what no thread wrote shows, or the slack round a table
+	hipError_t filled(size_t bytes, uint32_t word)
+	{
+		const hipError_t e = alloc(bytes);
+		return e != hipSuccess ? e : hipMemsetD32((hipDeviceptr_t)p_, (int)word, bytes_ / 4);
+	}
+	hipError_t put(size_t at, const void *host, size_t bytes) { return bytes == 0 ? hipSuccess : hipMemcpy((char *)p_ + at, host, bytes, hipMemcpyHostToDevice); }
 	hipError_t back(void *host) const { return hipMemcpy(host, p_, bytes_, hipMemcpyDeviceToHost); }
 	template <class T> T *as() const { return (T *)p_; }
 private:
@@ -376,6 +386,153 @@ int adypt_probe_noise(const float *samples, int k, int first, int n_frames, floa
 	p_noise<<<grid_for(n), kThreads>>>(n, ds.as<float>(), k, first, n_frames, dmean.as<float>(), dm2.as<float>(), de.as<float>());
 	PROBE_TRY(launched());
 	PROBE_TRY(dmean.back(mean)); PROBE_TRY(dm2.back(m2)); PROBE_TRY(de.back(e));
+	return 0;
+}
+
+} // extern "C"
+
+// ---- denoise_kernels.hpp: the product's kernels, launched with the product's launch shapes ------------------------------------------------
+namespace {
+
+constexpr uint32_t kUnwritten = 0x7fc0deadu; // every output is filled with this quiet NaN before the launch: a pixel no thread wrote keeps it
+constexpr int kMaxSide = 4096;
+constexpr int64_t kSlackTris = 64;           // triangles of slack in front of and behind the gather's two tables ...
+constexpr uint32_t kSlackWord = 0x4640e400u; // ... filled with 12345.0f
+constexpr int64_t kMaxStray = 32;            // how far outside [0, n_known) a hit word may point (the slack is twice that)
+
+bool picture_ok(int width, int height) { return width >= 1 && height >= 1 && width <= kMaxSide && height <= kMaxSide; }
+int blocks_across(int width) { return (width + kBlockDim - 1) / kBlockDim; }
+// a block list the kernels may be given: every block lies in the picture's grid of blocks (a kernel writes at the coordinates the list says)
+bool block_list_ok(const int32_t *blocks, int n_blocks, int width, int height)
+{
+	if(!blocks || n_blocks < 1 || n_blocks > 4096) return false;
+	const int n_grid = blocks_across(width) * blocks_across(height);
+	for(int k = 0; k < n_blocks; ++k)
+		if(blocks[k] < 0 || blocks[k] >= n_grid) return false;
+	return true;
+}
+
+} // namespace
+
+extern "C" {
+
+int adypt_probe_denoise_prepare(const float *accum, const float *moments, const float *albedo, const float *normal, const float *position, const float *hits, const int32_t *blocks,
+                                const int32_t *block_spp, int n_blocks, int width, int height, float *x0, float *x1, float *x2, float *xa)
+{
+	PROBE_REQUIRE(none_null(accum, moments, albedo, normal, position, hits, block_spp, x0, x1, x2, xa));
+	PROBE_REQUIRE(picture_ok(width, height) && block_list_ok(blocks, n_blocks, width, height));
+	const int n_px = n_blocks * kBlockPixels;
+	const size_t local = (size_t)n_px * 16, image = (size_t)width * height * 16;
+	Dev dc, dm, da, dn, dp, dh, db, ds, o0, o1, o2, oa;
+	PROBE_TRY(dc.in(accum, local)); PROBE_TRY(dm.in(moments, local / 2)); PROBE_TRY(da.in(albedo, local)); PROBE_TRY(dn.in(normal, local)); PROBE_TRY(dp.in(position, local));
+	PROBE_TRY(dh.in(hits, local)); PROBE_TRY(db.in(blocks, (size_t)n_blocks * 4)); PROBE_TRY(ds.in(block_spp, (size_t)n_blocks * 4));
+	PROBE_TRY(o0.filled(image, kUnwritten)); PROBE_TRY(o1.filled(image, kUnwritten)); PROBE_TRY(o2.filled(image, kUnwritten)); PROBE_TRY(oa.filled(image, kUnwritten));
+	const LaunchShape shape = prepare_launch(n_px);
+	hipLaunchKernelGGL(k_denoise_prepare, shape.grid, shape.block, 0, 0, dc.as<float4>(), dm.as<float2>(), db.as<int32_t>(), ds.as<int32_t>(), n_px, blocks_across(width), width, height,
+	                   da.as<float4>(), dn.as<float4>(), dp.as<float4>(), dh.as<float4>(), o0.as<float4>(), o1.as<float4>(), o2.as<float4>(), oa.as<float4>());
+	PROBE_TRY(launched());
+	PROBE_TRY(o0.back(x0)); PROBE_TRY(o1.back(x1)); PROBE_TRY(o2.back(x2)); PROBE_TRY(oa.back(xa));
+	return 0;
+}
+
+int adypt_probe_atrous(const float *x0, const float *x1, const float *x2, const float *xa, int width, int height, int step, float sigma_l, float sigma_z, int last, float *out)
+{
+	PROBE_REQUIRE(none_null(x0, x1, x2, xa, out) && picture_ok(width, height) && step >= 1 && step <= (1 << kDenoiseMaxLevels));
+	const size_t image = (size_t)width * height * 16;
+	Dev d0, d1, d2, da, dout;
+	PROBE_TRY(d0.in(x0, image)); PROBE_TRY(d1.in(x1, image)); PROBE_TRY(d2.in(x2, image)); PROBE_TRY(da.in(xa, image));
+	PROBE_TRY(dout.filled(last ? image / 4 * 3 : image, kUnwritten));
+	const LaunchShape shape = atrous_launch(width, height);
+	// (as run_filter launches a level: the image the instance does not write is never touched)
+	if(last) hipLaunchKernelGGL(k_atrous<true>, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), (float4 *)nullptr, dout.as<float>(), width, height,
+	                            step, sigma_l, sigma_z);
+	else hipLaunchKernelGGL(k_atrous<false>, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), dout.as<float4>(), (float *)nullptr, width, height,
+	                        step, sigma_l, sigma_z);
+	PROBE_TRY(launched());
+	PROBE_TRY(dout.back(out));
+	return 0;
+}
+
+int adypt_probe_rectify_window(int radius, const float *x0, const float *x1, const float *x2, const float *xa, int width, int height, const float *origin, float *r0, float *r1)
+{
+	PROBE_REQUIRE(none_null(x0, x1, x2, xa, origin, r0, r1) && picture_ok(width, height) && radius >= 1 && radius <= kRectifyMaxRadius);
+	const size_t image = (size_t)width * height * 16;
+	Dev d0, d1, d2, da, o0, o1;
+	PROBE_TRY(d0.in(x0, image)); PROBE_TRY(d1.in(x1, image)); PROBE_TRY(d2.in(x2, image)); PROBE_TRY(da.in(xa, image));
+	PROBE_TRY(o0.filled(image, kUnwritten)); PROBE_TRY(o1.filled(image, kUnwritten));
+	const auto window = radius == 1 ? k_rectify_window<1> : radius == 2 ? k_rectify_window<2> : k_rectify_window<3>;
+	static_assert(kRectifyMaxRadius == 3, "one instance of k_rectify_window per radius");
+	RectifyOrigin o;
+	for(int k = 0; k < 3; ++k) o.o[k] = origin[k];
+	const LaunchShape shape = window_launch(width, height);
+	hipLaunchKernelGGL(window, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), o0.as<float4>(), o1.as<float4>(), width, height, o);
+	PROBE_TRY(launched());
+	PROBE_TRY(o0.back(r0)); PROBE_TRY(o1.back(r1));
+	return 0;
+}
+
+int adypt_probe_temporal_merge(int motion, int rectify, const float *x0, const float *x1, const float *x2, const float *xa, const float *h0, const float *h1, const float *h2, const float *ha,
+                               int have, const float *origin, const float *inv_proj, const float *inv_view, float history_cap, const float *xp, const float *xn, const float *r0,
+                               const float *r1, float gamma, int width, int height, float *merged, float *x2_out, float *length, float *kept)
+{
+	PROBE_REQUIRE(none_null(x0, x1, x2, xa, h0, h1, h2, ha, origin, inv_proj, inv_view, merged, x2_out, length) && picture_ok(width, height));
+	PROBE_REQUIRE((!motion || none_null(xp, xn)) && (!rectify || none_null(r0, r1, kept)));
+	const size_t image = (size_t)width * height * 16;
+	Dev d0, d1, d2, da, e0, e1, e2, ea, dxp, dxn, dr0, dr1, om, ol, ok;
+	PROBE_TRY(d0.in(x0, image)); PROBE_TRY(d1.in(x1, image)); PROBE_TRY(d2.in(x2, image)); PROBE_TRY(da.in(xa, image));
+	PROBE_TRY(e0.in(h0, image)); PROBE_TRY(e1.in(h1, image)); PROBE_TRY(e2.in(h2, image)); PROBE_TRY(ea.in(ha, image));
+	if(motion) { PROBE_TRY(dxp.in(xp, image)); PROBE_TRY(dxn.in(xn, image)); }
+	if(rectify) { PROBE_TRY(dr0.in(r0, image)); PROBE_TRY(dr1.in(r1, image)); PROBE_TRY(ok.filled(image / 4, kUnwritten)); }
+	PROBE_TRY(om.filled(image, kUnwritten)); PROBE_TRY(ol.filled(image / 4, kUnwritten));
+	const TemporalCamera cam = temporal_camera(origin, inv_proj, inv_view);
+	const auto merge = rectify ? (motion ? k_temporal_merge<true, true> : k_temporal_merge<false, true>) : (motion ? k_temporal_merge<true, false> : k_temporal_merge<false, false>);
+	const LaunchShape shape = merge_launch(width, height);
+	// (an instance never looks at the images of a form it is not: they are null here, as they are in a context that never made such a call)
+	hipLaunchKernelGGL(merge, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), e0.as<float4>(), e1.as<float4>(), e2.as<float4>(),
+	                   ea.as<float4>(), om.as<float4>(), ol.as<float>(), width, height, have ? 1 : 0, cam, history_cap, dxp.as<float4>(), dxn.as<float4>(), dr0.as<float4>(), dr1.as<float4>(),
+	                   ok.as<float>(), gamma);
+	PROBE_TRY(launched());
+	PROBE_TRY(om.back(merged)); PROBE_TRY(d2.back(x2_out)); PROBE_TRY(ol.back(length));
+	if(rectify) PROBE_TRY(ok.back(kept));
+	return 0;
+}
+
+int adypt_probe_motion_gather(const float *hits, const float *normal, const float *position, const int32_t *blocks, int n_blocks, int width, int height, const float *snapshot,
+                              int64_t n_known, const float *records, int64_t n_records, int tri_float4, float *xp, float *xn)
+{
+	PROBE_REQUIRE(none_null(hits, normal, position, snapshot, records, xp, xn) && picture_ok(width, height) && block_list_ok(blocks, n_blocks, width, height));
+	PROBE_REQUIRE(n_known >= 0 && n_known <= n_records && n_records <= (1 << 20) && tri_float4 >= kSnapshotVecs && tri_float4 <= 64);
+	const int n_px = n_blocks * kBlockPixels;
+	// what a guard that fails would use as an index stays inside the slack
+	for(int L = 0; L < n_px; ++L)
+	{
+		int32_t tri;
+		memcpy(&tri, &hits[(size_t)L * 4], 4);
+		PROBE_REQUIRE((int64_t)tri >= -kMaxStray && (int64_t)tri < n_known + kMaxStray);
+	}
+	const size_t local = (size_t)n_px * 16, image = (size_t)width * height * 16, snap_tri = (size_t)kSnapshotVecs * 16, rec_tri = (size_t)tri_float4 * 16;
+	Dev dh, dn, dp, db, dsnap, drec, oxp, oxn;
+	PROBE_TRY(dh.in(hits, local)); PROBE_TRY(dn.in(normal, local)); PROBE_TRY(dp.in(position, local)); PROBE_TRY(db.in(blocks, (size_t)n_blocks * 4));
+	PROBE_TRY(dsnap.filled((size_t)(n_known + 2 * kSlackTris) * snap_tri, kSlackWord)); PROBE_TRY(dsnap.put((size_t)kSlackTris * snap_tri, snapshot, (size_t)n_known * snap_tri));
+	PROBE_TRY(drec.filled((size_t)(n_records + 2 * kSlackTris) * rec_tri, kSlackWord)); PROBE_TRY(drec.put((size_t)kSlackTris * rec_tri, records, (size_t)n_records * rec_tri));
+	PROBE_TRY(oxp.filled(image, kUnwritten)); PROBE_TRY(oxn.filled(image, kUnwritten));
+	const LaunchShape shape = gather_launch(n_px);
+	hipLaunchKernelGGL(k_motion_gather, shape.grid, shape.block, 0, 0, dh.as<float4>(), dn.as<float4>(), dp.as<float4>(), db.as<int32_t>(), n_px, blocks_across(width), width, height,
+	                   dsnap.as<float4>() + kSlackTris * kSnapshotVecs, n_known, drec.as<float4>() + kSlackTris * tri_float4, tri_float4, oxp.as<float4>(), oxn.as<float4>());
+	PROBE_TRY(launched());
+	PROBE_TRY(oxp.back(xp)); PROBE_TRY(oxn.back(xn));
+	return 0;
+}
+
+int adypt_probe_motion_snapshot(const float *records, int tri_float4, int64_t n_tris, float *snapshot)
+{
+	PROBE_REQUIRE(none_null(records, snapshot) && n_tris >= 1 && n_tris <= (1 << 20) && tri_float4 >= kSnapshotVecs && tri_float4 <= 64);
+	Dev drec, dsnap;
+	PROBE_TRY(drec.in(records, (size_t)n_tris * tri_float4 * 16)); PROBE_TRY(dsnap.filled((size_t)n_tris * kSnapshotVecs * 16, kUnwritten));
+	const LaunchShape shape = snapshot_launch(n_tris);
+	hipLaunchKernelGGL(k_motion_snapshot, shape.grid, shape.block, 0, 0, drec.as<float4>(), tri_float4, n_tris, dsnap.as<float4>());
+	PROBE_TRY(launched());
+	PROBE_TRY(dsnap.back(snapshot));
 	return 0;
 }
 

@@ -189,6 +189,96 @@ def display(rgba, viewer_type):
     return out.view(np.uint8).reshape(-1, 4)
 
 
+# ---- the denoiser's kernels (csrc/device/denoise_kernels.hpp), each launched as denoise.hip launches it ----
+UNWRITTEN = 0x7fc0dead  # the word every output holds before the launch
+
+
+def unwritten(a):
+    """Elementwise: the word is still the one the probe filled the output with — no thread wrote it."""
+    return np.ascontiguousarray(a, dtype=F32).view(U32) == U32(UNWRITTEN)
+
+
+def _img(a, h, w, c=4):
+    a = np.ascontiguousarray(a, dtype=F32)
+    assert a.shape == (h, w, c), (a.shape, (h, w, c))
+    return a
+
+
+def _local(a, n_blocks, c=4):
+    a = np.ascontiguousarray(a, dtype=F32)
+    assert a.shape == (n_blocks * 1024, c), (a.shape, n_blocks, c)
+    return a
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+
+
+def denoise_prepare(accum, moments, albedo, normal, position, hits, blocks, block_spp, w, h):
+    """k_denoise_prepare over block-major arrays ((n_blocks * 1024, 4) float32; moments (., 2); hits with the triangle index as the bits of .x) of the
+    block list given: X0, X1, X2, XA, each (h, w, 4)."""
+    blocks, block_spp = _i32(blocks), _i32(block_spp)
+    nb = len(blocks)
+    assert len(block_spp) == nb
+    out = [np.empty((h, w, 4), F32) for _ in range(4)]
+    _call("denoise_prepare", _local(accum, nb), _local(moments, nb, 2), _local(albedo, nb), _local(normal, nb), _local(position, nb), _local(hits, nb), blocks, block_spp, C.c_int(nb),
+          C.c_int(w), C.c_int(h), *out)
+    return out
+
+
+def atrous(x0, x1, x2, xa, step, sigma_l, sigma_z, last):
+    """k_atrous<last>: the next X0 (h, w, 4), or the result (h, w, 3)."""
+    h, w = np.shape(x0)[:2]
+    out = np.empty((h, w, 3 if last else 4), F32)
+    _call("atrous", _img(x0, h, w), _img(x1, h, w), _img(x2, h, w), _img(xa, h, w), C.c_int(w), C.c_int(h), C.c_int(step), C.c_float(sigma_l), C.c_float(sigma_z), C.c_int(1 if last else 0), out)
+    return out
+
+
+def rectify_window(radius, x0, x1, x2, xa, origin):
+    """k_rectify_window<radius>: R0, R1 (h, w, 4)."""
+    h, w = np.shape(x0)[:2]
+    r0, r1 = np.empty((h, w, 4), F32), np.empty((h, w, 4), F32)
+    _call("rectify_window", C.c_int(radius), _img(x0, h, w), _img(x1, h, w), _img(x2, h, w), _img(xa, h, w), C.c_int(w), C.c_int(h), _f(origin), r0, r1)
+    return r0, r1
+
+
+def temporal_merge(x, hist, have, cam, cap, motion=None, rectify=None):
+    """k_temporal_merge<motion is not None, rectify is not None>.  x = (X0, X1, X2, XA), hist = (H0, H1, H2, HA), cam = (origin, inv_proj, inv_view) of
+    the history, motion = (XP, XN), rectify = (R0, R1, gamma): (merged (h, w, 4), X2 as the kernel leaves it, length (h, w), kept (h, w) or None)."""
+    h, w = np.shape(x[0])[:2]
+    x, hist = [_img(a, h, w) for a in x], [_img(a, h, w) for a in hist]
+    o, ip, iv = (_f(v) for v in cam)
+    assert len(o) == 3 and len(ip) == 16 and len(iv) == 16
+    xp, xn = (_img(a, h, w) for a in motion) if motion is not None else (None, None)
+    r0, r1 = (_img(a, h, w) for a in rectify[:2]) if rectify is not None else (None, None)
+    merged, x2, length = np.empty((h, w, 4), F32), np.empty((h, w, 4), F32), np.empty((h, w), F32)
+    kept = np.empty((h, w), F32) if rectify is not None else None
+    _call("temporal_merge", C.c_int(motion is not None), C.c_int(rectify is not None), *x, *hist, C.c_int(1 if have else 0), o, ip, iv, C.c_float(cap), xp, xn, r0, r1,
+          C.c_float(rectify[2] if rectify is not None else 0.0), C.c_int(w), C.c_int(h), merged, x2, length, kept)
+    return merged, x2, length, kept
+
+
+def motion_gather(hits, normal, position, blocks, w, h, snapshot, records):
+    """k_motion_gather: snapshot (n_known, 20) float32, records (n_records >= n_known, 4 * tri_float4): XP, XN (h, w, 4)."""
+    blocks = _i32(blocks)
+    nb = len(blocks)
+    snapshot, records = np.ascontiguousarray(snapshot, dtype=F32), np.ascontiguousarray(records, dtype=F32)
+    assert snapshot.ndim == 2 and snapshot.shape[1] == 20 and records.ndim == 2 and records.shape[1] % 4 == 0
+    xp, xn = np.empty((h, w, 4), F32), np.empty((h, w, 4), F32)
+    _call("motion_gather", _local(hits, nb), _local(normal, nb), _local(position, nb), blocks, C.c_int(nb), C.c_int(w), C.c_int(h), snapshot, C.c_int64(len(snapshot)), records,
+          C.c_int64(len(records)), C.c_int(records.shape[1] // 4), xp, xn)
+    return xp, xn
+
+
+def motion_snapshot(records):
+    """k_motion_snapshot: records (n, 4 * tri_float4) float32 -> (n, 20)."""
+    records = np.ascontiguousarray(records, dtype=F32)
+    assert records.ndim == 2 and records.shape[1] % 4 == 0
+    out = np.empty((len(records), 20), F32)
+    _call("motion_snapshot", records, C.c_int(records.shape[1] // 4), C.c_int64(len(records)), out)
+    return out
+
+
 def noise(samples, first, n_frames):
     """samples (n, k, 3): noise_add_sample folded over the k samples of every element as frames first, first + 1, ..., then
     noise_of_pixel(., n_frames): (mean, m2, e)."""

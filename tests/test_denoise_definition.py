@@ -230,3 +230,24 @@ def test_the_new_symbols_are_declared_and_bound():
     assert "typedef struct adypt_denoise_params" in header and N.lib.adypt_abi_version() == 4
     import ctypes
     assert ctypes.sizeof(N.DenoiseParams) == 12
+
+
+def test_the_named_edge_inputs(driver):
+    """tests/denoise_edge_inputs.py's entries for prepare and the levels — the sizes round the 32 x 8 workgroup, sample counts 2 and 64 in neighbouring
+    blocks, m2 = 0, albedo 0, Inf and NaN in the accumulator — at six levels (steps 1 .. 32) under both pairs of sigmas: zero differing words."""
+    from tests import denoise_edge_inputs as E  # (here: the module imports this file's generators)
+    for name, case in E.filter_cases().items():
+        assert case["reach"](), name + ": the case does not reach what it is named after"
+        for sigma_l, sigma_z in E.SIGMAS:
+            kw = dict(levels=6, sigma_l=sigma_l, sigma_z=sigma_z)
+            try:
+                if np.isfinite(case["call"][0]).all() and np.isfinite(case["call"][1]).all():
+                    check(driver, case["call"], **kw)
+                else:
+                    # radiance that is no number spreads through the levels as NaN, whose sign and payload the definition does not say (g++ and numpy
+                    # order the operands of a product differently): NaN in the same places, equal words everywhere else
+                    got, want = run_driver(driver, *case["call"], **kw), D.denoise(*case["call"], **kw)
+                    assert np.isnan(want).any() and np.array_equal(np.isnan(got), np.isnan(want)), "NaN in other places than the numpy restatement"
+                    assert int((bits(got) != bits(want))[~np.isnan(want)].sum()) == 0, "words differ from the numpy restatement (%s)" % kw
+            except AssertionError as e:
+                raise AssertionError("%s: %s" % (name, e))

@@ -391,3 +391,31 @@ def test_the_new_symbols_are_declared_and_bound():
     sig = inspect.signature(api.HipPathTracer.Denoise)
     assert [sig.parameters[k].default for k in ("rectify", "rectify_radius", "rectify_gamma")] == [False, 3, 1.0]
     assert hasattr(api.HipPathTracer, "ReadDenoiseRectify") and hasattr(api.HipPathTracer, "GetDenoiseRectify")
+
+
+def test_the_named_edge_inputs(driver):
+    """tests/denoise_edge_inputs.py's entries for the window statistics and the rectified merge — every radius at the sizes round the 32 x 8 workgroup, a tap
+    refused by each test of rectify_tap in turn, sums that overflow, a limit that is no number, one clamped channel, kept = 0 — each reaching its branch
+    by the truth's account: zero differing words."""
+    from tests import denoise_edge_inputs as E  # (here: the module imports this file's generators)
+    for name, case in E.rectify_cases().items():
+        assert case["reach"](E.rectify_truth(case)), name + ": the case does not reach what it is named after"
+        for radius in ((1, 2, 3) if name.startswith("size-") else (case["kw"].get("radius", 3),)):
+            kw = dict(case["kw"], radius=radius)
+            try:
+                if np.isfinite(case["call"][0]).all() and np.isfinite(case["call"][1]).all():
+                    check(driver, case["call"], case["hist"], case["cam"], **kw)
+                else:
+                    # radiance or moments that are no numbers: the window and the merge are held word for word; the levels carry the pixel's own NaN on to
+                    # its neighbours, and the result is compared as numbers (as test_hand_made_cases does)
+                    got = run_driver(driver, case["call"], case["hist"], case["cam"], **kw)
+                    want, want_n, new, extra = RT.denoise(*case["call"], case["hist"], case["cam"], **kw)
+                    own = ~np.isfinite(new["D"]).all(-1) | ~np.isfinite(new["V"])  # the pixels whose own values are no numbers
+                    assert own.any() and not own.all()
+                    for field, exp in (("D", new["D"]), ("V", new["V"]), ("n", want_n), ("kept", extra["kept"]), ("R0", extra["R0"]), ("R1", extra["R1"])):
+                        keep = ~own if field in ("D", "V") else np.ones_like(own)
+                        assert differing(got[field][keep], exp[keep]) == 0, field
+                        assert np.array_equal(np.isnan(got[field]), np.isnan(exp)), field
+                    assert np.array_equal(np.isnan(got["rgb"]), np.isnan(want)) and differing(np.nan_to_num(got["rgb"]), np.nan_to_num(want)) == 0, "rgb"
+            except AssertionError as e:
+                raise AssertionError("%s, radius %d: %s" % (name, radius, e))

@@ -353,3 +353,15 @@ def test_the_new_symbols_are_declared_and_bound():
     assert "typedef struct adypt_temporal_params" in header and N.lib.adypt_abi_version() == 4
     import ctypes
     assert ctypes.sizeof(N.TemporalParams) == 8 and ctypes.sizeof(N.DenoiseParams) == 12
+
+
+def test_the_named_edge_inputs(driver):
+    """tests/denoise_edge_inputs.py's entries for the merge — the sizes round the 32 x 8 workgroup, every refusal of temporal_merge_through in turn, sw on
+    both sides of kTemporalMinWeight — each reaching its branch by the truth's account: zero differing words."""
+    from tests import denoise_edge_inputs as E  # (here: the module imports this file's generators)
+    for name, case in E.temporal_cases().items():
+        assert case["reach"](E.merge_truth(case)), name + ": the case does not reach what it is named after"
+        try:
+            check(driver, case["call"], case["hist"], case["cam"], **case["kw"])
+        except AssertionError as e:
+            raise AssertionError("%s: %s" % (name, e))

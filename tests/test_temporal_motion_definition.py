@@ -316,3 +316,15 @@ def test_the_new_symbols_are_declared_and_bound():
     assert "typedef struct adypt_denoise_motion" in header and N.lib.adypt_abi_version() == 4
     assert ctypes.sizeof(N.TemporalParams) == 8  # (adypt_temporal_params is ABI: the motion call is a call of its own)
     assert ctypes.sizeof(N.DenoiseMotion) == 24
+
+
+def test_the_named_edge_inputs(driver):
+    """tests/denoise_edge_inputs.py's entries for the motion form of the merge — no history, moved triangles, XN.w = 0, records that did not change, a
+    history without a snapshot — each reaching its branch by the truth's account: zero differing words."""
+    from tests import denoise_edge_inputs as E  # (here: the module imports this file's generators)
+    for name, case in E.motion_cases().items():
+        assert case["reach"](E.motion_truth(case)), name + ": the case does not reach what it is named after"
+        try:
+            check(driver, case["call"], case["hist"], case["cam"], case["tri"], case["uv"], case["cur"], **case["kw"])
+        except AssertionError as e:
+            raise AssertionError("%s: %s" % (name, e))
