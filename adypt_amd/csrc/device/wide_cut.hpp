@@ -45,7 +45,7 @@ ADYPT_HOST_DEVICE void cut_leaf_row(float area, float triangle_sah, CutRow &dp)
 
 // the row of an inner binary node with `tc` references below it from its children's rows; strict '<' everywhere (the first minimum wins).
 // false: no split of the eight slots costs less than FLT_MAX (costs that overflow, or are NaN); the row then names the split 4 + 4, so that a walk over
-// it stays inside the rows, and the caller refuses the tree (the device builder does; the host's collapse never did and took the split 0 + 0)
+// it stays inside the rows, and the caller refuses the tree (the device builder and the host's collapse both do)
 ADYPT_HOST_DEVICE bool cut_inner_row(float area, int tc, float triangle_sah, float node_sah_, const CutRow &L, const CutRow &R, CutRow &dp)
 {
 	{

@@ -7,7 +7,7 @@
 namespace adypt {
 
 // returns the number of leaves (= triangle references incl. spatial-split duplicates); the node array does not
-// depend on n_threads
+// depend on n_threads.  -1: a node for which no split costs less than FLT_MAX (areas that overflow, or are NaN) — the build would not end
 int64_t build_sbvh(const TriRec *tris, int64_t n_tris, const Box &scene_box, const adypt_bvh_params &cfg,
 				   std::vector<BinNode> *nodes, double *ms, int n_threads);
 
@@ -35,7 +35,8 @@ int64_t build_ploc_split(const TriRec *tris, int64_t n_tris, int radius, const P
 // adypt_bvh_refit with the box of every reference given (ref_boxes, in the order of tri_indices) instead of its whole triangle's; nullptr: adypt_bvh_refit
 int bvh_refit_boxes(void *nodes, int64_t n_nodes, const int32_t *tri_indices, int64_t n_refs, const void *triangles, int64_t n_tris, const RefitBox *ref_boxes);
 
-void build_wide_bvh(const std::vector<BinNode> &bin, int64_t leaf_count, const adypt_bvh_params &cfg,
+// false: the SAH costs of some node are not finite numbers below FLT_MAX (../device/wide_cut.hpp cut_inner_row); the arrays are then empty
+bool build_wide_bvh(const std::vector<BinNode> &bin, int64_t leaf_count, const adypt_bvh_params &cfg,
 					std::vector<NodeRec> *nodes, std::vector<int32_t> *tri_indices, double *ms, int n_threads);
 
 }  // namespace adypt

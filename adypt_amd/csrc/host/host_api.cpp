@@ -231,6 +231,10 @@ int adypt_host_selftest_sort(int64_t n, uint32_t seed, int pattern, int threads,
 	return ADYPT_OK;
 }
 
+// what every host builder answers where the device's answers the same (build.hip, kFlagCost): a tree over such boxes has no SAH cut, and the SBVH's
+// sweep no split — it used to go on for ever there
+static const char *const kCostRefused = "the SAH costs of this scene are not finite numbers below FLT_MAX (vertices that are NaN, infinite or huge)";
+
 int adypt_bvh_build(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, adypt_build_info *info)
 {
 	if(!s || !p || !out) { set_host_error("adypt_bvh_build: null argument"); return ADYPT_E_INVALID; }
@@ -241,19 +245,20 @@ int adypt_bvh_build(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh *
 	std::vector<BinNode> bin;
 	double sbvh_ms = 0, wide_ms = 0;
 	int64_t leaves = build_sbvh((const TriRec *)tp, nt, box, *p, &bin, &sbvh_ms, adypt_host_get_threads());
+	if(leaves < 0) { set_host_error(std::string("adypt_bvh_build: ") + kCostRefused); return ADYPT_E_INVALID; }
 	adypt_bvh *b = new adypt_bvh();
-	build_wide_bvh(bin, leaves, *p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads());
+	if(!build_wide_bvh(bin, leaves, *p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads())) { delete b; set_host_error(std::string("adypt_bvh_build: ") + kCostRefused); return ADYPT_E_INVALID; }
 	if(info) { info->sbvh_nodes = (int64_t)bin.size(); info->refs = leaves; info->wide_nodes = (int64_t)b->nodes.size(); info->sbvh_ms = sbvh_ms; info->wide_ms = wide_ms; }
 	*out = b;
 	return ADYPT_OK;
 }
 
 // the collapse of a binary tree without splits, with the boxes by the refit's rule: what the linear and the PLOC tree share
-static int collapse_unsplit(const std::vector<BinNode> &bin, int64_t leaves, const adypt_bvh_params &p, const void *tp, int64_t nt, double tree_ms, adypt_bvh **out, adypt_build_info *info)
+static int collapse_unsplit(const char *who, const std::vector<BinNode> &bin, int64_t leaves, const adypt_bvh_params &p, const void *tp, int64_t nt, double tree_ms, adypt_bvh **out, adypt_build_info *info)
 {
 	double wide_ms = 0;
 	adypt_bvh *b = new adypt_bvh();
-	build_wide_bvh(bin, leaves, p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads());
+	if(!build_wide_bvh(bin, leaves, p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads())) { delete b; set_host_error(std::string(who) + ": " + kCostRefused); return ADYPT_E_INVALID; }
 	// the boxes are the refit's, not the collapse's: one rule, the device builder's too
 	for(NodeRec &n : b->nodes)
 	{
@@ -290,7 +295,7 @@ int adypt_bvh_build_linear(const adypt_scene *s, const adypt_bvh_params *p, adyp
 	double tree_ms = 0;
 	int depth = 0;
 	const int64_t leaves = build_lbvh((const TriRec *)tp, nt, &bin, &depth, &tree_ms);
-	return collapse_unsplit(bin, leaves, *p, tp, nt, tree_ms, out, info);
+	return collapse_unsplit("adypt_bvh_build_linear", bin, leaves, *p, tp, nt, tree_ms, out, info);
 }
 
 int adypt_bvh_build_ploc(const adypt_scene *s, const adypt_bvh_params *p, int radius, adypt_bvh **out, adypt_build_info *info)
@@ -303,7 +308,7 @@ int adypt_bvh_build_ploc(const adypt_scene *s, const adypt_bvh_params *p, int ra
 	int depth = 0;
 	const int64_t leaves = build_ploc((const TriRec *)tp, nt, radius, &bin, &depth, &tree_ms);
 	if(leaves < 0) return ADYPT_E_INVALID;
-	return collapse_unsplit(bin, leaves, *p, tp, nt, tree_ms, out, info);
+	return collapse_unsplit("adypt_bvh_build_ploc", bin, leaves, *p, tp, nt, tree_ms, out, info);
 }
 
 int adypt_bvh_build_ploc_split(const adypt_scene *s, const adypt_bvh_params *p, int radius, double split_budget, adypt_bvh **out, adypt_build_info *info)
@@ -324,7 +329,7 @@ int adypt_bvh_build_ploc_split(const adypt_scene *s, const adypt_bvh_params *p, 
 	const int64_t leaves = build_ploc_split((const TriRec *)tp, nt, radius, refs, &bin, &depth, &tree_ms);
 	if(leaves < 0) return ADYPT_E_INVALID;
 	adypt_bvh *b = new adypt_bvh();
-	build_wide_bvh(bin, leaves, *p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads());
+	if(!build_wide_bvh(bin, leaves, *p, &b->nodes, &b->tri_indices, &wide_ms, adypt_host_get_threads())) { delete b; set_host_error(std::string("adypt_bvh_build_ploc_split: ") + kCostRefused); return ADYPT_E_INVALID; }
 	for(NodeRec &n : b->nodes)
 	{
 		n.px = n.py = n.pz = 0.0f; n.ex = n.ey = n.ez = 0;

@@ -32,6 +32,7 @@
 #include "exact_sort.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -87,7 +88,7 @@ public:
 	}
 
 	// sequential build of the subtree whose references are the last `root.n` entries of refs(); node indices are
-	// local to `out` (root = 0)
+	// local to `out` (root = 0).  -1: a node has no split (split() below)
 	int64_t run_subtree(const Spec &root, int root_depth)
 	{
 		nodes_.clear();
@@ -116,7 +117,7 @@ public:
 				continue;
 			}
 			Spec left, right;
-			split(t.spec, t.depth, &left, &right);
+			if(!split(t.spec, t.depth, &left, &right)) return -1;
 			// left is pushed first so that the whole right subtree is emitted before it (right child = node + 1)
 			todo.push_back({left, t.depth + 1, node});
 			todo.push_back({right, t.depth + 1, -1});
@@ -125,11 +126,11 @@ public:
 		return leaves;
 	}
 
-	// one split of the node that owns all of refs(): afterwards refs() = [left->n references | right->n references]
-	void split_once(const Spec &s, int depth, Spec *left, Spec *right)
+	// one split of the node that owns all of refs(): afterwards refs() = [left->n references | right->n references]; false: it has no split
+	bool split_once(const Spec &s, int depth, Spec *left, Spec *right)
 	{
 		min_overlap_ = scene_box_.area() * 1e-5f;
-		split(s, depth, left, right);
+		return split(s, depth, left, right);
 	}
 
 private:
@@ -304,7 +305,9 @@ private:
 		right->n = re - rb;
 	}
 
-	void split(const Spec &s, int depth, Spec *left, Spec *right)
+	// false: no object split of the node costs less than FLT_MAX (areas that overflow, or are NaN) and no spatial split parts its references.  The
+	// sweep then names no split at all (left_n 0), the right child would be the node again, and the build would never end
+	bool split(const Spec &s, int depth, Spec *left, Spec *right)
 	{
 #ifdef ADYPT_BUILD_TIMING
 		auto T0 = std::chrono::steady_clock::now();
@@ -336,11 +339,13 @@ private:
 		lap("do_spatial_split");
 		if(left->n == 0 || right->n == 0)
 		{
+			if(os.left_n == 0) return false;
 			sort_refs(s, os.dim);
 			lap("final sort");
 			left->n = os.left_n; left->box = os.left;
 			right->n = s.n - os.left_n; right->box = os.right;
 		}
+		return true;
 	}
 };
 
@@ -389,6 +394,7 @@ public:
 		for(int i = 1; i < n_threads_; ++i) pool.emplace_back([this] { work(); });
 		work();
 		for(std::thread &t : pool) t.join();
+		if(failed_) return -1;
 		return stitch(root, out);
 	}
 
@@ -405,6 +411,7 @@ private:
 	std::deque<SubTask *> ready_;
 	std::vector<std::unique_ptr<SubTask>> all_;
 	int64_t unfinished_ = 0;
+	std::atomic<bool> failed_{false}; // a task met a node without a split: it spawns nothing, the others run out
 
 	// Reference buffers are recycled between tasks: a finished task's vector (capacity intact) serves a later right
 	// child.  First-touching fresh pages costs more than the copy itself on the virtualised hosts this runs on.
@@ -476,6 +483,7 @@ private:
 		if(t->spec.n <= grain_)
 		{
 			t->leaves = b.run_subtree(t->spec, t->depth);
+			if(t->leaves < 0) failed_ = true;
 			release(std::move(b.refs()));
 			return;
 		}
@@ -483,7 +491,7 @@ private:
 		// proportional to the node's share of the scene (the nodes of one level together own about all references)
 		b.set_sort_threads((int)std::max<int64_t>(1, std::min<int64_t>(n_threads_, ((int64_t)n_threads_ * t->spec.n + n_tris_ / 2) / n_tris_)), sort_min_task_);
 		Spec ls, rs;
-		b.split_once(t->spec, t->depth, &ls, &rs);
+		if(!b.split_once(t->spec, t->depth, &ls, &rs)) { failed_ = true; return; }
 		std::vector<Ref> &r = b.refs(); // = [left | right] (spatial splits may have added references)
 		SubTask *right = new_task(), *left = new_task();
 		right->spec = rs; right->depth = t->depth + 1;

@@ -44,11 +44,12 @@ public:
 		if(const char *ev = getenv("ADYPT_BUILD_GRAIN")) { int v = atoi(ev); if(v >= 1) grain_ = v; } // tests: cut the tiny fixtures too
 	}
 
-	void run(int64_t leaf_count)
+	// false: the DP found a node whose every cut costs FLT_MAX or more, or NaN (cut_inner_row): nothing is emitted
+	bool run(int64_t leaf_count)
 	{
 		nodes_.clear();
 		idx_.clear();
-		if(bin_.empty()) return;
+		if(bin_.empty()) return true;
 #ifdef ADYPT_BUILD_TIMING
 		auto T0 = std::chrono::steady_clock::now();
 		auto lap = [&](const char *what) { auto T1 = std::chrono::steady_clock::now(); fprintf(stderr, "[wide] %s %.2f s\n", what, std::chrono::duration<double>(T1 - T0).count()); T0 = T1; };
@@ -95,6 +96,7 @@ public:
 			for(size_t k = top.size(); k-- > 0;) eval_cost(top[k]);
 		}
 		lap("dp");
+		if(!cost_ok_) return false;
 		// ---- phase 2: top-down emission
 		if(!parallel)
 		{
@@ -103,7 +105,7 @@ public:
 			Cursor cur{&nodes_, &idx_, 1, 0, true}; // node 0 is the root
 			emit_subtree(0, 0, &cur);
 			nodes_.shrink_to_fit();
-			return;
+			return true;
 		}
 		nodes_.assign((size_t)std::max(1u, wide_below_[0]), NodeRec{}); // wide_below_[0] counts the root itself
 		idx_.assign((size_t)tri_count_[0], 0);
@@ -113,6 +115,7 @@ public:
 		work();
 		for(std::thread &t : pool) t.join();
 		lap("emit");
+		return true;
 	}
 
 private:
@@ -124,6 +127,7 @@ private:
 	std::unique_ptr<int32_t[]> tri_count_;
 	std::unique_ptr<uint32_t[]> wide_below_;  // wide nodes emitted for binary node n as a direct child: itself + everything below (0 for a leaf cut)
 	int n_threads_;
+	std::atomic<bool> cost_ok_{true};   // no row of the DP was refused (written by the threads of the sweep)
 	int32_t grain_ = 1 << 15;           // binary nodes per DP sweep task / references per emission task
 
 	// where the next wide node / triangle reference of a subtree goes.  Sequential build: the arrays grow; parallel
@@ -220,7 +224,7 @@ private:
 		const int l = left(n), r = right(n);
 		const int tc = tri_count_[(size_t)r] + tri_count_[(size_t)l];
 		tri_count_[(size_t)n] = tc;
-		cut_inner_row(area, tc, cfg_.triangle_sah, cfg_.node_sah, cost_[(size_t)l], cost_[(size_t)r], dp);
+		if(!cut_inner_row(area, tc, cfg_.triangle_sah, cfg_.node_sah, cost_[(size_t)l], cost_[(size_t)r], dp)) cost_ok_ = false;
 		wide_below_[(size_t)n] = cut_wide_below(View{this}, n);
 	}
 
@@ -331,12 +335,13 @@ private:
 
 }  // namespace
 
-void build_wide_bvh(const std::vector<BinNode> &bin, int64_t leaf_count, const adypt_bvh_params &cfg,
+bool build_wide_bvh(const std::vector<BinNode> &bin, int64_t leaf_count, const adypt_bvh_params &cfg,
 					std::vector<NodeRec> *nodes, std::vector<int32_t> *tri_indices, double *ms, int n_threads)
 {
 	auto t0 = std::chrono::steady_clock::now();
-	Collapser(bin, cfg, nodes, tri_indices, n_threads).run(leaf_count);
+	const bool ok = Collapser(bin, cfg, nodes, tri_indices, n_threads).run(leaf_count);
 	if(ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	return ok;
 }
 
 }  // namespace adypt

@@ -78,7 +78,9 @@ int adypt_host_get_threads(void);
  * permutation part of the node array).  pattern 0 random, 1 heavy ties, 2 sorted, 3 reversed, 4 all equal,
  * 5 quicksort killer (reaches the heap-sort fallback).  Returns 0 when both sorts agree byte for byte. */
 int adypt_host_selftest_sort(int64_t n, uint32_t seed, int pattern, int threads, int64_t min_task);
-/* SBVHBuilder{cfg,&sbvh,scene}.Run(); WideBVHBuilder{cfg,&wbvh,sbvh}.Run(); (src/Instance.cpp:24-26) */
+/* SBVHBuilder{cfg,&sbvh,scene}.Run(); WideBVHBuilder{cfg,&wbvh,sbvh}.Run(); (src/Instance.cpp:24-26).  ADYPT_E_INVALID, like every builder below and
+ * like the device's, for a scene whose SAH costs are not finite numbers below FLT_MAX (node areas past about 2^127: vertices that are NaN, infinite or
+ * huge): the sweep then has no split to take and the collapse no cut. */
 int adypt_bvh_build(const adypt_scene *s, const adypt_bvh_params *p, adypt_bvh **out, adypt_build_info *info);
 /* A CWBVH8 from a linear BVH: Morton keys of the centroids, a sort, Karras's radix tree, the collapse above, and boxes by the rule of adypt_bvh_refit.
  * The definition is csrc/device/lbvh.hpp, which the device builder (adypt_hip.h, adypt_rebuild_bvh) compiles too: both give the same bytes.  No
