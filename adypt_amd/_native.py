@@ -101,6 +101,17 @@ class DenoiseRectify(Struct):
     _fields_ = [("have", C.c_int32), ("radius", C.c_int32), ("gamma", C.c_float), ("window_ms", C.c_float), ("device_bytes", C.c_int64)]
 
 
+class SpecularParams(C.Structure):
+    """adypt_specular_params."""
+    _fields_ = [("bounces", C.c_int32)]
+
+
+class DenoiseSpecular(Struct):
+    """adypt_denoise_specular_info."""
+    _fields_ = [("have", C.c_int32), ("bounces", C.c_int32), ("chain_ms", C.c_float), ("rays", C.c_int64), ("pixels_followed", C.c_int64),
+                ("pixels_escaped", C.c_int64), ("pixels_truncated", C.c_int64), ("device_bytes", C.c_int64)]
+
+
 class BvhParams(C.Structure):
     _fields_ = [("max_spatial_depth", C.c_int32), ("triangle_sah", C.c_float), ("node_sah", C.c_float)]
 
@@ -239,6 +250,12 @@ _SIGS = {
     "adypt_multi_denoise_temporal_rectified": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(RectifyParams), C.c_int]),
     "adypt_multi_read_denoise_rectify": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_get_denoise_rectify": (C.c_int, [C.c_void_p, C.POINTER(DenoiseRectify)]),
+    "adypt_denoise_specular": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(SpecularParams)]),
+    "adypt_read_denoise_guides_specular": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adypt_get_denoise_specular": (C.c_int, [C.c_void_p, C.POINTER(DenoiseSpecular)]),
+    "adypt_multi_denoise_specular": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(SpecularParams)]),
+    "adypt_multi_read_denoise_guides_specular": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adypt_multi_get_denoise_specular": (C.c_int, [C.c_void_p, C.POINTER(DenoiseSpecular)]),
     "adypt_multi_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams)]),
     "adypt_multi_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_read_denoise_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

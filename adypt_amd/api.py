@@ -750,7 +750,8 @@ class _Tracer:
 
     # ---- denoising (adypt_denoise, include/adypt_hip.h; the definition: csrc/device/denoise.hpp); several devices: of the whole image ----
     def Denoise(self, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 0.1, temporal: bool = False, history_cap: float = 64.0,
-                commit: bool = True, follow_motion: bool = False, rectify: bool = False, rectify_radius: int = 3, rectify_gamma: float = 1.0) -> np.ndarray:
+                commit: bool = True, follow_motion: bool = False, rectify: bool = False, rectify_radius: int = 3, rectify_gamma: float = 1.0,
+                specular_bounces: int = 0) -> np.ndarray:
         """H x W x 3 float32: the accumulated image through the variance- and primary-hit-guided a-trous filter.  Needs the noise statistics on and
         >= 2 spp in every block; the image, the statistics and the tracing state are left as they are.
         temporal (adypt_denoise_temporal; the definition: csrc/device/temporal.hpp): before the filter, what the last committing call left is
@@ -763,13 +764,23 @@ class _Tracer:
         rectify (adypt_denoise_temporal_rectified; needs temporal; the definition: csrc/device/rectify.hpp): the history is held against the mean of
         the (2 rectify_radius + 1)^2 window of this call's own image on the pixel's surface and clamped to within rectify_gamma standard deviations
         of it, and loses length by as much as it disagrees — for light that changed on a surface that stands still (a shadow that wandered, another
-        sun).  rectify_radius in [1, 3], rectify_gamma a finite number >= 0.  Combines with follow_motion."""
+        sun).  rectify_radius in [1, 3], rectify_gamma a finite number >= 0.  Combines with follow_motion.
+        specular_bounces (adypt_denoise_specular; the definition: csrc/device/guide_chain.hpp): 0 is the call above to the bit; K in [1, 8] guides a
+        pixel whose primary hit is a perfect mirror or glass by the first surface its chain of up to K reflections / transmissions ends on, and
+        keeps pixels of different chain classes from pooling.  No temporal form: the merge reprojects the position guide through the camera."""
         if follow_motion and not temporal:
             raise ValueError("Denoise: follow_motion=True needs temporal=True")
         if rectify and not temporal:
             raise ValueError("Denoise: rectify=True needs temporal=True")
+        if specular_bounces != 0 and not 1 <= specular_bounces <= 8:
+            raise ValueError("Denoise: specular_bounces must be 0 or in [1, 8]")
+        if specular_bounces and temporal:
+            raise ValueError("Denoise: specular_bounces has no temporal form (the merge reprojects the position guide through the camera)")
         prm = N.DenoiseParams(levels, sigma_l, sigma_z)
-        if temporal and rectify:
+        if specular_bounces:
+            sp = N.SpecularParams(specular_bounces)
+            self._call("denoise_specular", C.byref(prm), C.byref(sp))
+        elif temporal and rectify:
             tp, rp = N.TemporalParams(history_cap, 1 if commit else 0), N.RectifyParams(rectify_radius, rectify_gamma)
             self._call("denoise_temporal_rectified", C.byref(prm), C.byref(tp), C.byref(rp), 1 if follow_motion else 0)
         elif temporal:
@@ -826,12 +837,27 @@ class _Tracer:
         self._call("get_denoise_merge_ms", C.byref(ms))
         return float(ms.value)
 
-    def ReadDenoiseGuides(self) -> dict:
-        """The feature images of the pixel-centre camera ray under the current camera: albedo, normal, position (H x W x 3 float32) and hit (H x W bool)."""
+    def ReadDenoiseGuides(self, specular_bounces: int = 0) -> dict:
+        """The feature images of the pixel-centre camera ray under the current camera: albedo, normal, position (H x W x 3 float32) and hit (H x W bool).
+        specular_bounces K in [1, 8]: the guides Denoise(specular_bounces=K) filters with, and chain (H x W int8): every pixel's class code — 0 a
+        primary miss, 1 a primary hit that is followed nowhere, 1 + L a chain that ended on a surface after L bounces, -(L + 1) one that left the scene."""
         a, n, p = (np.zeros((self.height, self.width, 3), dtype=np.float32) for _ in range(3))
         hit = np.zeros((self.height, self.width), dtype=np.uint8)
-        self._call("read_denoise_guides", a.ctypes.data, n.ctypes.data, p.ctypes.data, hit.ctypes.data)
-        return {"albedo": a, "normal": n, "position": p, "hit": hit.astype(bool)}
+        if specular_bounces == 0:
+            self._call("read_denoise_guides", a.ctypes.data, n.ctypes.data, p.ctypes.data, hit.ctypes.data)
+            return {"albedo": a, "normal": n, "position": p, "hit": hit.astype(bool)}
+        if not 1 <= specular_bounces <= 8:
+            raise ValueError("ReadDenoiseGuides: specular_bounces must be 0 or in [1, 8]")
+        chain = np.zeros((self.height, self.width), dtype=np.int8)
+        self._call("read_denoise_guides_specular", specular_bounces, a.ctypes.data, n.ctypes.data, p.ctypes.data, chain.ctypes.data)
+        return {"albedo": a, "normal": n, "position": p, "hit": chain != 0, "chain": chain}
+
+    def GetDenoiseSpecular(self) -> dict:
+        """Of the last call with specular_bounces: have (0 / 1), bounces, chain_ms (HIP-event milliseconds of the chain stage alone), rays,
+        pixels_followed, pixels_escaped, pixels_truncated, and device_bytes of what the chain keeps (several devices: sums, the slowest device's time)."""
+        out = N.DenoiseSpecular()
+        self._call("get_denoise_specular", C.byref(out))
+        return out.as_dict()
 
     def GetDenoiseTiming(self) -> dict:
         """HIP-event milliseconds of the last Denoise() on the (first) device: guides (0 with several devices: the upload instead), prepare, levels.

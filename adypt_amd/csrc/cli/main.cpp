@@ -571,14 +571,30 @@ static bool report_temporal(Session &s)
 	return o.history_out.empty() || save_grey(s, o.history_out, length, "history lengths");
 }
 
+// the [PT]SPECULAR: line of the last call with followed guides: the chain's own counts, and the hit pixels from its class codes
+static bool report_specular(Session &s)
+{
+	adypt_denoise_specular_info info;
+	std::vector<int8_t> chain((size_t)s.cfg.width * s.cfg.height, 0);
+	if(adypt_multi_read_denoise_guides_specular(s.multi, *s.opt.denoise_specular, nullptr, nullptr, nullptr, chain.data()) != ADYPT_OK || adypt_multi_get_denoise_specular(s.multi, &info) != ADYPT_OK)
+		return tracer_failed(s.multi);
+	const long long hits = (long long)std::count_if(chain.begin(), chain.end(), [](int8_t c) { return c != 0; });
+	printf("[PT]SPECULAR: bounces %d followed %lld escaped %lld truncated %lld of %lld hit pixels, rays %lld\n", info.bounces, (long long)info.pixels_followed, (long long)info.pixels_escaped,
+	       (long long)info.pixels_truncated, hits, (long long)info.rays);
+	return true;
+}
+
 static bool save_denoised(Session &s)
 {
 	const Options &o = s.opt;
 	if(!o.denoise) return true;
 	std::vector<float> den((size_t)s.cfg.width * s.cfg.height * 3, 0.0f);
-	if((o.temporal ? temporal_call(s) : adypt_multi_denoise(s.multi, &s.denoise_params)) != ADYPT_OK || adypt_multi_read_denoised(s.multi, den.data()) != ADYPT_OK) return tracer_failed(s.multi);
+	const adypt_specular_params specular{o.denoise_specular.value_or(0)};
+	const int r = o.temporal ? temporal_call(s) : o.denoise_specular ? adypt_multi_denoise_specular(s.multi, &s.denoise_params, &specular) : adypt_multi_denoise(s.multi, &s.denoise_params);
+	if(r != ADYPT_OK || adypt_multi_read_denoised(s.multi, den.data()) != ADYPT_OK) return tracer_failed(s.multi);
 	if(adypt_save_exr(o.denoise_out.c_str(), den.data(), s.cfg.width, s.cfg.height, o.fp16) != ADYPT_OK) return host_failed();
 	printf("[PT]INFO: Saved denoised image (%d levels) to %s\n", o.denoise_levels, o.denoise_out.c_str());
+	if(o.denoise_specular && !report_specular(s)) return false;
 	return !o.temporal || report_temporal(s);
 }
 
@@ -588,12 +604,16 @@ static bool save_guides(Session &s)
 	if(prefix.empty()) return true;
 	std::vector<float> g[3];
 	for(auto &v : g) v.assign((size_t)s.cfg.width * s.cfg.height * 3, 0.0f);
-	if(adypt_multi_read_denoise_guides(s.multi, g[0].data(), g[1].data(), g[2].data(), nullptr) != ADYPT_OK) return tracer_failed(s.multi);
+	const std::optional<int> &bounces = s.opt.denoise_specular; // (the followed guides, and the class codes beside them)
+	std::vector<int8_t> chain(bounces ? (size_t)s.cfg.width * s.cfg.height : 0, 0);
+	const int r = bounces ? adypt_multi_read_denoise_guides_specular(s.multi, *bounces, g[0].data(), g[1].data(), g[2].data(), chain.data())
+	                      : adypt_multi_read_denoise_guides(s.multi, g[0].data(), g[1].data(), g[2].data(), nullptr);
+	if(r != ADYPT_OK) return tracer_failed(s.multi);
 	const char *const what[3] = {".albedo.exr", ".normal.exr", ".position.exr"};
 	for(int k = 0; k < 3; ++k)
 		if(adypt_save_exr((prefix + what[k]).c_str(), g[k].data(), s.cfg.width, s.cfg.height, 0) != ADYPT_OK) return host_failed();
 	printf("[PT]INFO: Saved guide images to %s.{albedo,normal,position}.exr\n", prefix.c_str());
-	return true;
+	return !bounces || save_grey(s, prefix + ".chain.exr", std::vector<float>(chain.begin(), chain.end()), "chain classes");
 }
 
 // like ~Instance (src/Instance.cpp:83-86): the config is written back on exit — the successful one

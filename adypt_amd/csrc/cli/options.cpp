@@ -61,7 +61,11 @@
 //              much as it disagrees: for light that changed on a surface that stands still.  Combines with --follow-motion.  --rectify-out kept.exr: the
 //              share of its length every pixel's history kept, as a grey EXR.  The [PT]TEMPORAL: line then ends `, rectified K pixels`: those with a
 //              share below 1.  --rectify-gamma, --rectify-radius and --rectify-out need --rectify
-//   --guides-out PREFIX: the feature images of the primary hit as PREFIX.albedo.exr, PREFIX.normal.exr and PREFIX.position.exr
+//   --denoise-specular K: with --denoise only, and with none of the temporal options (else exit 2): the guides of a pixel whose primary hit is a perfect
+//              mirror or glass follow the reflection / transmission for up to K bounces, 1 .. 8, to the first surface that is neither
+//              (adypt_multi_denoise_specular).  One [PT]SPECULAR: line reports the followed, escaped and truncated pixels and the rays
+//   --guides-out PREFIX: the feature images of the primary hit as PREFIX.albedo.exr, PREFIX.normal.exr and PREFIX.position.exr; with
+//              --denoise-specular the followed guides, and the class code of every pixel as the grey PREFIX.chain.exr
 #include "options.hpp"
 
 #include <algorithm>
@@ -72,7 +76,7 @@
 
 const char *const USAGE =
 	"scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] "
-	"[--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] "
+	"[--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--denoise-specular K] "
 	"[--history-from other.config]... [--history-cap C] [--history-out len.exr] [--follow-motion] [--rectify [--rectify-gamma G] [--rectify-radius R] "
 	"[--rectify-out kept.exr]]] [--guides-out PREFIX] [--pose moved.obj [--by-vertices [--recompute-normals]] | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] "
 	"[--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]";
@@ -150,6 +154,13 @@ static bool rectify_gamma(Options &o, const char *v)
 	o.rectify_params.gamma = (float)gamma;
 	return o.rectify_detail = true;
 }
+static bool denoise_specular(Options &o, const char *v)
+{
+	double bounces;
+	if(!bounded_number(v, INTEGER, 1, 8, "--denoise-specular takes a number of bounces from 1 to 8", &bounces)) return false;
+	o.denoise_specular = (int)bounces;
+	return true;
+}
 static bool rebuild_above(Options &o, const char *v)
 {
 	double ratio;
@@ -185,6 +196,7 @@ static const struct Spec { const char *name; bool value; Apply apply; } SPECS[] 
 	{"--spp-out", true, text<&Options::spp_out>},
 	{"--denoise", true, text<&Options::denoise_out>},
 	{"--denoise-levels", true, lenient_int<&Options::denoise_levels>},
+	{"--denoise-specular", true, denoise_specular},
 	{"--history-from", true, one_more<&Options::history_from>},
 	{"--history-out", true, text<&Options::history_out>},
 	{"--history-cap", true, history_cap},
@@ -257,6 +269,9 @@ int check_options(Options *opt)
 	if(!o.adaptive && !o.spp_out.empty()) return refuse("--spp-out needs --adaptive");
 	if(o.denoise && (o.primary >= 0 || o.spp < 2)) return refuse("--denoise needs --spp >= 2 and no --primary");
 	if(o.denoise && (o.denoise_levels < 1 || o.denoise_levels > 6)) return refuse("--denoise-levels must be in 1 .. 6");
+	if(o.denoise_specular && !o.denoise) return refuse("--denoise-specular needs --denoise file.exr");
+	if(o.denoise_specular && (o.temporal || o.follow_motion || o.rectify))
+		return refuse("--denoise-specular has no temporal form: not together with --history-from, --history-cap, --history-out, --follow-motion or --rectify");
 	if(o.temporal && !o.denoise) return refuse("--history-from, --history-cap and --history-out need --denoise file.exr");
 	if(o.rectify_detail && !o.rectify) return refuse("--rectify-gamma, --rectify-radius and --rectify-out need --rectify");
 	if(o.rectify && !o.temporal) return refuse("--rectify needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out");

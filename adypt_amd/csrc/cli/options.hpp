@@ -25,6 +25,7 @@ struct Options
 	int min_spp = 16, check_every = 16, adaptive = 0;
 	std::string noise_out, spp_out, denoise_out, guides_out;
 	int denoise_levels = 5;
+	std::optional<int> denoise_specular; // --denoise-specular K: the guides follow mirrors and glass for K bounces
 	std::vector<std::string> history_from;
 	std::string history_out;
 	std::optional<double> history_cap; // 64 unless given

@@ -68,6 +68,22 @@ int ctx_capture_guides(adypt_ctx *c, const char *fn, float4 *albedo, float4 *nor
 // what adypt_set_camera was last given (the guides above are captured under it): the temporal merge keeps it beside the history it commits
 struct CtxCamera { float origin[3], inv_proj[16], inv_view[16]; };
 CtxCamera ctx_camera(adypt_ctx *c);
+// The context's own ray queues and its traversal, for the chain through mirrors and glass (guide_chain.hpp): the denoiser's kernels write the rays of a
+// round into a queue, the context's k_trace finds their closest hits.  Slots: segment s owns [s * seg_cap, (s + 1) * seg_cap); a ray is (origin, tmin)
+// in o[parity] and (direction, a word carried along) in d[parity]; its hit (bits(tri), u, v, t) comes in `hit` at the same slot.  The rays of segment
+// s of round r are counted in count[r * round_stride + s * seg_stride], zero when ctx_ray_queues returns.
+struct CtxRayQueues {
+	float4 *o[2], *d[2], *hit;
+	uint32_t *count;
+	int rounds;                    // rounds the counters hold
+	uint32_t round_stride, seg_stride;
+	int segments;
+	uint32_t seg_cap;              // >= ceil(owned blocks x 4 / segments) x 256: a workgroup of 256 local pixels per segment in turn always fits
+	float tmin;                    // the ray_tmin of the context's parameters
+};
+// see tracer.hip
+int ctx_ray_queues(adypt_ctx *c, const char *fn, CtxRayQueues *q);
+int ctx_trace_queue(adypt_ctx *c, int parity, int round);
 
 // ---- moving geometry (refit.hip), per context ----
 // the scene arrays on the device, which refit.hip rewrites in place between frames
@@ -95,6 +111,7 @@ struct CtxMaterials {
 	int64_t n_mats;
 	int n_textures, mat_float4;
 	bool keeps_classes;
+	const uint32_t *texels;       // the textures' texels, as the shading reads them (texture.hpp)
 };
 CtxMaterials ctx_materials(adypt_ctx *c);
 // new triangles, packed and complete on the context's stream: taken by the context together with the tree built of them

@@ -2,8 +2,12 @@
 // tracer's code object.  What runs, all on the context's stream behind the frames:
 //     guide capture  three launches of the viewer instance of k_trace_camera over the owned blocks (tracer.hip ctx_capture_guides), into scratch
 //                    owned here: albedo, normal, position, primary hit — block-major like every local image
+//     k_chain_start, k_chain_step  adypt_denoise_specular only (the definition: guide_chain.hpp), behind the capture: pixels whose primary hit is a perfect
+//                    mirror or glass are followed for up to K bounces — k_chain_start classifies every local pixel and writes a ray for those that go on,
+//                    then K rounds of the context's own k_trace over its ray queues (ctx_ray_queues, ctx_trace_queue) and k_chain_step, which ends a
+//                    pixel (albedo, normal, position into the guide scratch, the class into the .w of its primary hit) or writes the next ray
 //     k_denoise_prepare  block-major accum / moments / block sample counts / guides  ->  row-major float4 images X0 = (D0.rgb, V0), X1 = (N.xyz, hit),
-//                    X2 = (P.xyz, n), XA = (A.rgb, .)
+//                    X2 = (P.xyz, n), XA = (A.rgb, .); k_denoise_prepare_class (followed guides): X1.w is the pixel's class instead of the hit flag
 //     k_temporal_merge  adypt_denoise_temporal only (the definition: temporal.hpp): the history the last committing call left — its merged pre-filter
 //                    (D, V), its guides, its effective sample counts, its camera — reprojected through P and merged into (D0, V0); the levels then
 //                    read the merged image.  A commit swaps the call's images with the history's: nothing is copied
@@ -174,6 +178,12 @@ struct Denoiser {
 	bool kept_valid = false; // as length_valid, of a rectified call and `kept`
 	int rectify_radius = 0; float rectify_gamma = 0.0f;
 	StageTimer<2> window_timer;
+	// following mirrors and glass (guide_chain.hpp): the chain's state, 32 B per local pixel, and its counters, allocated at the first such call; the
+	// bounces of the last one (0: none has been enqueued) and the time of its chain stage
+	Buffer<float4> chain_state;
+	Buffer<ChainCounts> chain_counts;
+	int chain_bounces = 0;
+	StageTimer<2> chain_timer;
 
 	size_t pixels() const { return (size_t)width * (size_t)height; }
 };
@@ -198,6 +208,7 @@ struct DenoiseCall {
 	bool rectify; int radius; float gamma; // of Temporal and Motion: the history is rectified (rectify.hpp)
 	const char *fn;
 	std::string refused;            // why the arguments are refused; empty: they are not
+	int bounces = 0;                // adypt_denoise_specular: the guides follow mirrors and glass for this many bounces; 0: the primary hit's guides
 };
 
 // the call of the ABI structs (null: the defaults — 5 levels, 4.0, 0.1; cap 64, committing; radius 3, gamma 1); tp is looked at by Temporal and Motion
@@ -214,6 +225,17 @@ DenoiseCall make_call(Mode mode, const char *fn, const adypt_denoise_params *p, 
 	else if(with_history && !temporal_cap_valid(call.history_cap)) call.refused = std::string(fn) + ": history_cap must be a positive finite number";
 	else if(call.rectify && !rectify_params_valid(call.radius, call.gamma))
 		call.refused = std::string(fn) + ": the rectify radius must be in [1, " + std::to_string(kRectifyMaxRadius) + "], gamma a finite number that is not negative";
+	return call;
+}
+
+// adypt_denoise_specular's call: a Plain call with followed guides
+DenoiseCall make_specular_call(const char *fn, const adypt_denoise_params *p, const adypt_specular_params *sp)
+{
+	DenoiseCall call = make_call(Mode::Plain, fn, p, nullptr);
+	if(!call.refused.empty()) return call;
+	if(!sp) call.refused = std::string(fn) + ": specular is null";
+	else if(!chain_bounces_valid(sp->bounces)) call.refused = std::string(fn) + ": bounces must be in [1, " + std::to_string(kChainMaxBounces) + "]";
+	else call.bounces = sp->bounces;
 	return call;
 }
 
@@ -241,7 +263,8 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 	const int32_t *blocks = in.as<kBlocks>();
 	const float4 *normal = in.as<kNormal>(), *position = in.as<kPosition>(), *hits = in.as<kHits>();
 	const LaunchShape prepare = prepare_launch(n_px);
-	hipLaunchKernelGGL(k_denoise_prepare, prepare.grid, prepare.block, 0, stream, in.as<kAccum>(), in.as<kMoments>(), blocks, in.as<kBlockSpp>(), n_px, blocks_x, width, height,
+	// (followed guides: X1.w is the class the chain left in the .w of the primary-hit image)
+	hipLaunchKernelGGL(call.bounces > 0 ? k_denoise_prepare_class : k_denoise_prepare, prepare.grid, prepare.block, 0, stream, in.as<kAccum>(), in.as<kMoments>(), blocks, in.as<kBlockSpp>(), n_px, blocks_x, width, height,
 	                   in.as<kAlbedo>(), normal, position, hits, d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get());
 	CTX_TRY(c, hipGetLastError());
 	CTX_TRY(c, d->timer.mark(2, stream));
@@ -321,11 +344,54 @@ int own_images(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, LocalImages *
 	return d->own.fill(c, v, kContextImages);
 }
 
-// ... and the context's guides into it, enqueued behind its frames (the sample counts are the caller's to upload)
-int capture_guides(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, LocalImages *v)
+// The chain through mirrors and glass over the context's own blocks (guide_chain.hpp), enqueued behind the guide capture on the context's stream
+// without a host sync: k_chain_start, then `bounces` rounds of the context's k_trace over the queue just written and k_chain_step, which writes the
+// other queue.  Every round is enqueued whether it has rays or not: an empty round measures 0.05 ms (two launches that read eight counters), and
+// stopping at the first one would need a count read back — a host sync in a call that has none until its end (that form is not built).
+// The queues have been asked for (ctx_ray_queues) before the capture was enqueued.
+int enqueue_chain(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, int bounces, const CtxRayQueues &q)
+{
+	const CtxInfo i = ctx_info(c);
+	const int n_px = in.n_blocks * kBlockPixels;
+	const LaunchShape start = chain_start_launch(n_px);
+	const uint32_t per_segment = ((start.grid.x + (unsigned)q.segments - 1) / (unsigned)q.segments) * kPixelThreads; // the most rays a segment is given
+	if(per_segment > q.seg_cap || bounces + 1 > q.rounds) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the context's ray queues cannot hold the chain's rays");
+	CTX_TRY(c, at_least(d->chain_state, (size_t)n_px * 2));
+	CTX_TRY(c, at_least(d->chain_counts, 1));
+	const CtxScene scene = ctx_scene(c);
+	const CtxMaterials mats = ctx_materials(c);
+	const CtxCamera cam = ctx_camera(c);
+	const ChainScene sc{(const float4 *)scene.triangles, mats.materials, mats.texels, scene.n_tris, (int32_t)mats.n_mats, mats.n_textures};
+	const ChainGuides g{d->own.as<kAlbedo>(), d->own.as<kNormal>(), d->own.as<kPosition>(), d->own.as<kHits>()};
+	const ChainOrigin origin{{cam.origin[0], cam.origin[1], cam.origin[2]}, q.tmin};
+	auto queue = [&q](int parity, int round) { return ChainQueue{q.o[parity], q.d[parity], q.count + (size_t)round * q.round_stride, q.seg_cap, q.seg_stride, q.segments}; };
+	const int blocks_x = (i.width + kBlockDim - 1) / kBlockDim;
+	d->chain_bounces = bounces;
+	CTX_TRY(c, hipMemsetAsync(d->chain_counts.get(), 0, sizeof(ChainCounts), i.stream));
+	CTX_TRY(c, d->chain_timer.mark(0, i.stream));
+	hipLaunchKernelGGL(k_chain_start, start.grid, start.block, 0, i.stream, sc, g, in.blocks, n_px, blocks_x, i.width, i.height, origin, bounces, d->chain_state.get(), queue(0, 0), d->chain_counts.get());
+	CTX_TRY(c, hipGetLastError());
+	const LaunchShape step = chain_step_launch(q.segments, per_segment);
+	for(int r = 0; r < bounces; ++r)
+	{
+		CTX_STEP(ctx_trace_queue(c, r & 1, r));
+		hipLaunchKernelGGL(k_chain_step, step.grid, step.block, 0, i.stream, sc, g, queue(r & 1, r), (const float4 *)q.hit, n_px, bounces, q.tmin, d->chain_state.get(), queue((r & 1) ^ 1, r + 1),
+		                   d->chain_counts.get());
+		CTX_TRY(c, hipGetLastError());
+	}
+	CTX_TRY(c, d->chain_timer.mark(1, i.stream));
+	return ADYPT_OK;
+}
+
+// ... and the context's guides into it, enqueued behind its frames (the sample counts are the caller's to upload); bounces > 0: followed through mirrors
+// and glass, the class of every pixel in the .w of the primary-hit image
+int capture_guides(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, LocalImages *v, int bounces = 0)
 {
 	CTX_STEP(own_images(c, d, in, v));
-	return ctx_capture_guides(c, fn, d->own.as<kAlbedo>(), d->own.as<kNormal>(), d->own.as<kPosition>(), d->own.as<kHits>());
+	CtxRayQueues q{};
+	if(bounces > 0) CTX_STEP(ctx_ray_queues(c, fn, &q)); // (first: it may have to wait for frames started ahead)
+	CTX_STEP(ctx_capture_guides(c, fn, d->own.as<kAlbedo>(), d->own.as<kNormal>(), d->own.as<kPosition>(), d->own.as<kHits>()));
+	return bounces > 0 && in.n_blocks > 0 ? enqueue_chain(c, d, in, fn, bounces, q) : (int)ADYPT_OK;
 }
 
 // `bytes` of a device array of a context on the host (the stream is drained when it returns)
@@ -406,6 +472,27 @@ int get_rectify(adypt_ctx *c, const char *fn, adypt_denoise_rectify *out)
 	return ADYPT_OK;
 }
 
+int read_guides(adypt_ctx *c, const char *fn, int bounces, float *albedo, float *normal, float *position, uint8_t *hit, int8_t *chain); // (below, beside its entry points)
+
+// what the last chain of a context did: its counters are read here, behind whatever the context's stream still holds
+int get_specular(adypt_ctx *c, const char *fn, adypt_denoise_specular_info *out)
+{
+	if(!out) return ctx_fail(c, ADYPT_E_INVALID, std::string(fn) + ": out is null");
+	*out = adypt_denoise_specular_info{};
+	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
+	if(!d) return ADYPT_OK;
+	out->device_bytes = (int64_t)(d->chain_state.bytes() + d->chain_counts.bytes());
+	if(d->chain_bounces == 0) return ADYPT_OK;
+	const CtxInfo i = ctx_info(c);
+	CTX_TRY(c, hipSetDevice(i.device));
+	ChainCounts n;
+	CTX_STEP(fetch(c, i, d->chain_counts.get(), &n, sizeof(n)));
+	out->have = 1; out->bounces = d->chain_bounces;
+	(void)d->chain_timer.read(&out->chain_ms, 1, 1, false);
+	out->rays = (int64_t)n.rays; out->pixels_followed = (int64_t)n.followed; out->pixels_escaped = (int64_t)n.escaped; out->pixels_truncated = (int64_t)n.truncated;
+	return ADYPT_OK;
+}
+
 int read_merge_ms(adypt_ctx *c, const char *fn, float *ms)
 {
 	Denoiser *d = finished_denoiser(c);
@@ -430,7 +517,7 @@ int denoise_context(adypt_ctx *c, const DenoiseCall &call)
 	CTX_TRY(c, d->timer.mark(0, i.stream));
 	const DenoiseInputs in = ctx_denoise_inputs(c);
 	LocalImages local;
-	CTX_STEP(capture_guides(c, d, in, fn, &local));
+	CTX_STEP(capture_guides(c, d, in, fn, &local, call.bounces));
 	CTX_TRY(c, d->timer.mark(1, i.stream));
 	CTX_TRY(c, hipMemcpyAsync(d->own.as<kBlockSpp>(), in.block_spp.data(), in.block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
 	return run_filter(c, d, i.stream, local, call, ctx_camera(c));
@@ -483,12 +570,32 @@ int adypt_read_denoised(adypt_ctx *c, float *rgb) { return c && rgb ? read_resul
 
 int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float *position, uint8_t *hit)
 {
+	return c ? read_guides(c, "adypt_read_denoise_guides", 0, albedo, normal, position, hit, nullptr) : ADYPT_E_INVALID;
+}
+
+int adypt_read_denoise_guides_specular(adypt_ctx *c, int32_t bounces, float *albedo, float *normal, float *position, int8_t *chain)
+{
 	if(!c) return ADYPT_E_INVALID;
+	if(!chain_bounces_valid(bounces)) return ctx_fail(c, ADYPT_E_INVALID, "adypt_read_denoise_guides_specular: bounces must be in [1, " + std::to_string(kChainMaxBounces) + "]");
+	return read_guides(c, "adypt_read_denoise_guides_specular", bounces, albedo, normal, position, nullptr, chain);
+}
+
+int adypt_denoise_specular(adypt_ctx *c, const adypt_denoise_params *p, const adypt_specular_params *sp) { return denoise_context(c, make_specular_call("adypt_denoise_specular", p, sp)); }
+
+int adypt_get_denoise_specular(adypt_ctx *c, adypt_denoise_specular_info *out) { return c ? get_specular(c, "adypt_get_denoise_specular", out) : ADYPT_E_INVALID; }
+
+}  // extern "C"
+
+namespace {
+
+// the guide read-out of a context: the pixels of its own blocks into the caller's images; bounces > 0: the followed guides, and `chain` the class codes
+int read_guides(adypt_ctx *c, const char *fn, int bounces, float *albedo, float *normal, float *position, uint8_t *hit, int8_t *chain)
+{
 	const CtxInfo i = ctx_info(c);
 	if(i.n_local_px == 0) return ADYPT_OK; // a shard that owns no block
 	CTX_TRY(c, hipSetDevice(i.device));
 	LocalImages own;
-	CTX_STEP(capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), "adypt_read_denoise_guides", &own));
+	CTX_STEP(capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), fn, &own, bounces));
 	const std::vector<int32_t> blocks = owned_blocks(i.width, i.height, i.rank, i.nranks);
 	std::vector<float4> local((size_t)i.n_local_px);
 	float *const image[3] = {albedo, normal, position};
@@ -502,18 +609,23 @@ int adypt_read_denoise_guides(adypt_ctx *c, float *albedo, float *normal, float 
 			o[0] = local[L].x; o[1] = local[L].y; o[2] = local[L].z;
 		});
 	}
-	if(hit)
+	if(hit || chain)
 	{
 		CTX_STEP(fetch(c, i, own.image[kHits], local.data(), local.size() * sizeof(float4)));
 		for_each_local_pixel(blocks, i.width, i.height, [&](size_t L, int x, int y) {
 			int32_t tri;
 			memcpy(&tri, &local[L].x, 4);
-			hit[(size_t)y * i.width + x] = tri != -1 ? 1 : 0;
+			if(hit) hit[(size_t)y * i.width + x] = tri != -1 ? 1 : 0;
+			if(chain) chain[(size_t)y * i.width + x] = (int8_t)local[L].w;
 		});
 	}
 	CTX_TRY(c, hipStreamSynchronize(i.stream));
 	return ADYPT_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int adypt_get_denoise_timing(adypt_ctx *c, float *ms, int capacity)
 {
@@ -542,12 +654,13 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 	for(int k = 0; k < n_dev; ++k) ctx.push_back(adypt_multi_context(m, k));
 	CTX_STEP(multi_each(m, [fn](adypt_ctx *c) { return ctx_denoise_ready(c, fn); }));
 	// every device captures the guides of its own blocks: all enqueued before the first is waited for
-	CTX_STEP(multi_each(m, [fn](adypt_ctx *c) {
+	const int bounces = call.bounces; // (followed guides: every device follows the chains of its own blocks; the class comes along in the primary-hit image)
+	CTX_STEP(multi_each(m, [fn, bounces](adypt_ctx *c) {
 		const CtxInfo i = ctx_info(c);
 		if(i.n_local_px == 0) return (int)ADYPT_OK;
 		if(hipSetDevice(i.device) != hipSuccess) return ctx_fail(c, ADYPT_E_HIP, std::string(fn) + ": hipSetDevice failed");
 		LocalImages own;
-		return capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), fn, &own);
+		return capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), fn, &own, bounces);
 	}));
 	// the local images of every device back to back in rank order, and their block lists and sample counts likewise (the counts from each context's
 	// own state in that order: multi.hip's merge is sorted by block index, which is not this order, and would launch k_noise_blocks for nothing)
@@ -658,6 +771,32 @@ int adypt_multi_read_denoised(adypt_multi *m, float *rgb)
 int adypt_multi_read_denoise_guides(adypt_multi *m, float *albedo, float *normal, float *position, uint8_t *hit)
 {
 	return multi_each(m, [=](adypt_ctx *c) { return adypt_read_denoise_guides(c, albedo, normal, position, hit); });
+}
+
+int adypt_multi_denoise_specular(adypt_multi *m, const adypt_denoise_params *p, const adypt_specular_params *sp) { return multi_denoise(m, make_specular_call("adypt_multi_denoise_specular", p, sp)); }
+
+int adypt_multi_read_denoise_guides_specular(adypt_multi *m, int32_t bounces, float *albedo, float *normal, float *position, int8_t *chain)
+{
+	return multi_each(m, [=](adypt_ctx *c) { return adypt_read_denoise_guides_specular(c, bounces, albedo, normal, position, chain); });
+}
+
+// every device followed the chains of its own blocks: the counts and the bytes are sums, the time the slowest device's
+int adypt_multi_get_denoise_specular(adypt_multi *m, adypt_denoise_specular_info *out)
+{
+	if(!out) return ADYPT_E_INVALID;
+	adypt_denoise_specular_info sum{};
+	const int r = multi_each(m, [&sum](adypt_ctx *c) {
+		adypt_denoise_specular_info one;
+		const int e = get_specular(c, "adypt_multi_get_denoise_specular", &one);
+		if(e != ADYPT_OK) return e;
+		sum.device_bytes += one.device_bytes;
+		if(!one.have) return (int)ADYPT_OK;
+		sum.have = 1; sum.bounces = one.bounces; sum.chain_ms = std::max(sum.chain_ms, one.chain_ms);
+		sum.rays += one.rays; sum.pixels_followed += one.pixels_followed; sum.pixels_escaped += one.pixels_escaped; sum.pixels_truncated += one.pixels_truncated;
+		return (int)ADYPT_OK;
+	});
+	if(r == ADYPT_OK) *out = sum;
+	return r;
 }
 
 }  // extern "C"

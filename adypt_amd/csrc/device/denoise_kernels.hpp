@@ -7,6 +7,8 @@
 #include "tile_layout.hpp"
 #include "denoise.hpp"
 #include "temporal.hpp"
+#include "guide_chain.hpp"
+#include "texture.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -21,9 +23,12 @@ constexpr int kPixelThreads = 256; // the workgroup of the kernels that run one 
 // one thread per local pixel of a block list of n_px local pixels
 inline LaunchShape local_pixels_launch(int n_px) { return LaunchShape{dim3((unsigned)(((int64_t)n_px + kPixelThreads - 1) / kPixelThreads)), dim3(kPixelThreads)}; }
 
-__global__ __launch_bounds__(kPixelThreads) void k_denoise_prepare(const float4 *accum, const float2 *moments, const int32_t *blocks, const int32_t *block_spp, int n_px, int blocks_x, int width,
-                                                                   int height, const float4 *g_albedo, const float4 *g_normal, const float4 *g_position, const float4 *g_hits, float4 *x0,
-                                                                   float4 *x1, float4 *x2, float4 *xa)
+// CLASS: X1.w is the class code the chain through mirrors and glass left in the .w of the primary-hit image (k_chain_start, k_chain_step) instead of the
+// hit flag: adypt_denoise_specular's instance, k_denoise_prepare_class.  The other instance is what k_denoise_prepare was before there was a chain.
+template <bool CLASS>
+__device__ __forceinline__ void denoise_prepare_pixel(const float4 *accum, const float2 *moments, const int32_t *blocks, const int32_t *block_spp, int n_px, int blocks_x, int width, int height,
+                                                      const float4 *g_albedo, const float4 *g_normal, const float4 *g_position, const float4 *g_hits, float4 *x0, float4 *x1, float4 *x2,
+                                                      float4 *xa)
 {
 	const int L = blockIdx.x * blockDim.x + threadIdx.x;
 	if(L >= n_px) return;
@@ -34,11 +39,191 @@ __global__ __launch_bounds__(kPixelThreads) void k_denoise_prepare(const float4 
 	const float4 c = accum[L], a = g_albedo[L], n = g_normal[L], q = g_position[L];
 	const Dn4 d = denoise_prepare(c.x, c.y, c.z, moments[L].y, (float)block_spp[L >> 10], a.x, a.y, a.z);
 	x0[p] = make_float4(d.x, d.y, d.z, d.w);
-	x1[p] = make_float4(n.x, n.y, n.z, __float_as_int(g_hits[L].x) != -1 ? 1.0f : 0.0f);
+	x1[p] = make_float4(n.x, n.y, n.z, CLASS ? g_hits[L].w : (__float_as_int(g_hits[L].x) != -1 ? 1.0f : 0.0f));
 	x2[p] = make_float4(q.x, q.y, q.z, (float)block_spp[L >> 10]); // (.w: the sample count, which only the temporal merge reads)
 	xa[p] = make_float4(a.x, a.y, a.z, 0.0f);
 }
+__global__ __launch_bounds__(kPixelThreads) void k_denoise_prepare(const float4 *accum, const float2 *moments, const int32_t *blocks, const int32_t *block_spp, int n_px, int blocks_x, int width,
+                                                                   int height, const float4 *g_albedo, const float4 *g_normal, const float4 *g_position, const float4 *g_hits, float4 *x0,
+                                                                   float4 *x1, float4 *x2, float4 *xa)
+{
+	denoise_prepare_pixel<false>(accum, moments, blocks, block_spp, n_px, blocks_x, width, height, g_albedo, g_normal, g_position, g_hits, x0, x1, x2, xa);
+}
+__global__ __launch_bounds__(kPixelThreads) void k_denoise_prepare_class(const float4 *accum, const float2 *moments, const int32_t *blocks, const int32_t *block_spp, int n_px, int blocks_x,
+                                                                         int width, int height, const float4 *g_albedo, const float4 *g_normal, const float4 *g_position, const float4 *g_hits,
+                                                                         float4 *x0, float4 *x1, float4 *x2, float4 *xa)
+{
+	denoise_prepare_pixel<true>(accum, moments, blocks, block_spp, n_px, blocks_x, width, height, g_albedo, g_normal, g_position, g_hits, x0, x1, x2, xa);
+}
 inline LaunchShape prepare_launch(int n_px) { return local_pixels_launch(n_px); }
+
+// ---- the chain through mirrors and glass (guide_chain.hpp) ----
+// What the chain's kernels read of the scene, the guide scratch they finish pixels in, the queue they append rays to, what they count.
+struct ChainScene { const float4 *triangles, *materials; const uint32_t *texels; int64_t n_tris; int32_t n_mats, n_tex; };
+struct ChainGuides { float4 *albedo, *normal, *position, *hits; }; // block-major, one float4 per local pixel; hits.w takes the class
+struct ChainQueue { float4 *o, *d; uint32_t *count; uint32_t seg_cap, seg_stride; int segments; }; // count[s * seg_stride]: the rays of segment s
+struct ChainCounts { unsigned long long rays, followed, escaped, truncated; };
+struct ChainOrigin { float o[3]; float tmin; };
+
+// the material of triangle `tri` for the chain; want_kd: with the diffuse colour the shading would take at (u, v), the texture's where there is one
+__device__ __forceinline__ ChainMaterial chain_material(const ChainScene &sc, int tri, float u, float v, bool want_kd)
+{
+	ChainMaterial m{true, 0, Ch3{0.0f, 0.0f, 0.0f}, Ch3{0.0f, 0.0f, 0.0f}, 1.0f};
+	const int matid = __float_as_int(sc.triangles[(size_t)tri * kTriFloat4 + 4].z);
+	if(matid < 0 || matid >= sc.n_mats) return m;
+	const float4 *mp = sc.materials + (size_t)matid * kMatFloat4;
+	const float4 md = mp[0], ms = mp[2], mx = mp[3];
+	m.bad = false; m.illum = __float_as_int(mx.x); m.ior = mx.w;
+	m.ks = Ch3{ms.y, ms.z, ms.w};
+	m.kd = Ch3{md.y, md.z, md.w};
+	const int dtex = __float_as_int(md.x);
+	if(want_kd && !chain_is_delta(false, m.illum) && sc.n_tex != 0 && dtex != -1 && dtex >= 0 && dtex < sc.n_tex)
+	{
+		const float4 mt = mp[4];
+		const SceneArgs scene{sc.triangles, sc.materials, sc.texels, nullptr, nullptr};
+		const F3 c = textured_diffuse(scene, tri, make_int4(__float_as_int(mt.x), __float_as_int(mt.y), __float_as_int(mt.z), 0), u, v, 1.0f - u - v);
+		m.kd = Ch3{c.x, c.y, c.z};
+	}
+	return m;
+}
+
+// A wave's survivors take consecutive slots of the segment: the vote, the lane's rank among the voters (v_mbcnt), ONE atomic per wave by the first
+// voter, its answer read by the others.  The vote is taken once and nothing waits between it and its use: no mask crosses a barrier.
+// Every lane of the wave calls this.  Returns the slot inside the segment (valid where `alive`).
+__device__ __forceinline__ uint32_t chain_append(bool alive, uint32_t *seg_counter)
+{
+	const unsigned long long mask = __ballot(alive);
+	const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+	uint32_t base = 0u;
+	if(alive && rank == 0u) base = atomicAdd(seg_counter, (uint32_t)__popcll(mask));
+	const int first = mask ? __ffsll((long long)mask) - 1 : 0;
+	return (uint32_t)__shfl((int)base, first) + rank;
+}
+// a count of the lanes that say `yes`: one atomic per wave
+__device__ __forceinline__ void chain_count(bool yes, unsigned long long *counter)
+{
+	const unsigned long long mask = __ballot(yes);
+	const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+	if(yes && rank == 0u) atomicAdd(counter, (unsigned long long)__popcll(mask));
+}
+
+__device__ __forceinline__ void chain_store_state(float4 *state, int L, const ChainState &s)
+{
+	state[2 * (size_t)L] = make_float4(s.t.x, s.t.y, s.t.z, __int_as_float(s.length));
+	state[2 * (size_t)L + 1] = make_float4(s.d.x, s.d.y, s.d.z, 0.0f);
+}
+__device__ __forceinline__ void chain_store_ray(const ChainQueue &q, uint32_t seg, uint32_t in_seg, const Ch3 &p, const Ch3 &d, float tmin, int L)
+{
+	if(in_seg >= q.seg_cap) return; // (the host sizes the launch so that a segment cannot overflow; never write outside one)
+	const size_t slot = (size_t)seg * q.seg_cap + in_seg;
+	q.o[slot] = make_float4(p.x, p.y, p.z, tmin);
+	q.d[slot] = make_float4(d.x, d.y, d.z, __int_as_float(L)); // (the local pixel travels in .w, as in the sun-visibility queue)
+}
+
+// One thread per local pixel of the owned block list, behind the guide capture.  Reads the primary hit (16 B) and, where it is a hit, the material
+// (48 B of its record, 16 B of the triangle's) and the normal and position guides (32 B); writes the class of a pixel that is not followed into the .w
+// of its hit (4 B), else the pixel's state (32 B) and a ray (32 B).  Workgroup b appends to segment b % segments: 256 rays at most each.
+__global__ __launch_bounds__(kPixelThreads) void k_chain_start(ChainScene sc, ChainGuides g, const int32_t *__restrict__ blocks, int n_px, int blocks_x, int width, int height,
+                                                               ChainOrigin origin, int bounces, float4 *__restrict__ state, ChainQueue out, ChainCounts *counts)
+{
+	const int L = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t seg = blockIdx.x % (uint32_t)out.segments;
+	bool go = false;
+	ChainState s{Ch3{1.0f, 1.0f, 1.0f}, Ch3{0.0f, 0.0f, 0.0f}, 0};
+	Ch3 p{0.0f, 0.0f, 0.0f};
+	if(L < n_px)
+	{
+		int x, y;
+		block_pixel_xy(blocks[L >> 10], L & 1023, blocks_x, &x, &y);
+		if(x < width && y < height)
+		{
+			const float4 hq = g.hits[L];
+			const int32_t tri = __float_as_int(hq.x);
+			if(tri >= 0 && (int64_t)tri < sc.n_tris)
+			{
+				const ChainMaterial m = chain_material(sc, tri, hq.y, hq.z, false);
+				const float4 n = g.normal[L], q = g.position[L];
+				p = Ch3{q.x, q.y, q.z};
+				go = chain_at_primary(s, m, Ch3{n.x, n.y, n.z}, p, origin.o, bounces) == kChainGoesOn;
+			}
+			if(!go) g.hits[L].w = tri != -1 ? 1.0f : 0.0f;
+		}
+	}
+	const uint32_t in_seg = chain_append(go, out.count + seg * out.seg_stride);
+	if(go)
+	{
+		chain_store_state(state, L, s);
+		chain_store_ray(out, seg, in_seg, p, s.d, origin.tmin, L);
+	}
+	chain_count(go, &counts->followed);
+	chain_count(go, &counts->rays);
+}
+inline LaunchShape chain_start_launch(int n_px) { return local_pixels_launch(n_px); }
+
+// One thread per traced ray: workgroup b takes rays [256 (b / segments), ...) of segment b % segments of the queue the traversal has just answered.
+// Reads the ray's direction word and hit (32 B), the pixel's state (32 B) and at a hit 80 B of the triangle's record, 48 B of the material's and, on a
+// textured surface that ends the chain, 16 B of texture coordinates and 4 texels; either ends the pixel — albedo, normal, position (48 B) and the class
+// into the .w of its hit (4 B) — or writes the state back and appends the next ray to the same segment of the other queue (64 B).
+__global__ __launch_bounds__(kPixelThreads) void k_chain_step(ChainScene sc, ChainGuides g, ChainQueue in, const float4 *__restrict__ hit, int n_px, int bounces, float tmin,
+                                                              float4 *__restrict__ state, ChainQueue out, ChainCounts *counts)
+{
+	const uint32_t seg = blockIdx.x % (uint32_t)in.segments, local = (blockIdx.x / (uint32_t)in.segments) * kPixelThreads + threadIdx.x;
+	const uint32_t n_in = min(in.count[seg * in.seg_stride], in.seg_cap);
+	bool go = false, escaped = false, truncated = false;
+	ChainState s{Ch3{1.0f, 1.0f, 1.0f}, Ch3{0.0f, 0.0f, 0.0f}, 0};
+	Ch3 p{0.0f, 0.0f, 0.0f};
+	int L = -1;
+	if(local < n_in)
+	{
+		const size_t slot = (size_t)seg * in.seg_cap + local;
+		L = __float_as_int(in.d[slot].w);
+		if(L < 0 || L >= n_px) L = -1; // (never an index that is none)
+	}
+	if(L >= 0)
+	{
+		const size_t slot = (size_t)seg * in.seg_cap + local;
+		const float4 h = hit[slot], s0 = state[2 * (size_t)L], s1 = state[2 * (size_t)L + 1];
+		s = ChainState{Ch3{s0.x, s0.y, s0.z}, Ch3{s1.x, s1.y, s1.z}, __float_as_int(s0.w)};
+		const int32_t tri = __float_as_int(h.x);
+		ChainEnd end;
+		if(tri < 0 || (int64_t)tri >= sc.n_tris) { end = chain_escaped(s); escaped = true; }
+		else
+		{
+			s.length = s.length + 1;
+			float w[20]; // words 0..17 of the record: positions and normals (indexed by constants after unrolling: registers)
+			const float4 *rec = sc.triangles + (size_t)tri * kTriFloat4;
+#pragma unroll
+			for(int k = 0; k < 5; ++k)
+			{
+				const float4 v = rec[k];
+				w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
+			}
+			Ch3 n;
+			chain_hit_point(w, h.y, h.z, &p, &n);
+			const ChainMaterial m = chain_material(sc, tri, h.y, h.z, true);
+			go = chain_at_surface(s, m, n, p, bounces, &end) == kChainGoesOn;
+			truncated = !go && chain_is_delta(m.bad, m.illum);
+		}
+		if(!go)
+		{
+			g.albedo[L] = make_float4(end.albedo.x, end.albedo.y, end.albedo.z, 1.0f);
+			g.normal[L] = make_float4(end.normal.x, end.normal.y, end.normal.z, 1.0f);
+			g.position[L] = make_float4(end.position.x, end.position.y, end.position.z, 1.0f);
+			g.hits[L].w = (float)end.cls;
+		}
+	}
+	const uint32_t in_seg = chain_append(go, out.count + seg * out.seg_stride);
+	if(go)
+	{
+		chain_store_state(state, L, s);
+		chain_store_ray(out, seg, in_seg, p, s.d, tmin, L);
+	}
+	chain_count(go, &counts->rays);
+	chain_count(escaped, &counts->escaped);
+	chain_count(truncated, &counts->truncated);
+}
+// rays_per_segment: the most rays a segment can hold in any round = 256 x the workgroups of k_chain_start that append to it
+inline LaunchShape chain_step_launch(int segments, uint32_t rays_per_segment) { return LaunchShape{dim3((unsigned)segments * ((rays_per_segment + kPixelThreads - 1) / kPixelThreads)), dim3(kPixelThreads)}; }
 
 struct DeviceImages {
 	const float4 *a, *b, *c;

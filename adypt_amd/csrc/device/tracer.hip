@@ -746,6 +746,31 @@ CtxCamera ctx_camera(adypt_ctx *c)
 	memcpy(cam.origin, c->origin, 12); memcpy(cam.inv_proj, c->inv_proj, 64); memcpy(cam.inv_view, c->inv_view, 64);
 	return cam;
 }
+// The context's ray queues for rounds of rays another unit writes itself (the denoiser's chain through mirrors and glass).  Towards frames started
+// ahead it behaves as adypt_trace_rays does: they work in a window of these queues and are waited for; frames parked ahead live elsewhere and stay.
+// The counters of every round are cleared on the context's stream before it returns.
+int ctx_ray_queues(adypt_ctx *c, const char *fn, CtxRayQueues *q)
+{
+	if(!c->queues_ok) return fail(c, ADYPT_E_STATE, std::string(fn) + ": the context lost its ray queues (failed adypt_set_frames_in_flight)");
+	HIP_TRY(c, hipSetDevice(c->device));
+	drop_rolling(c);
+	static_assert(sizeof(c->d_counters->count[0]) == sizeof(uint32_t) * kNumSegments * kCursorStride, "one round of counters");
+	for(int i = 0; i < 2; ++i) { q->o[i] = c->q.o[i]; q->d[i] = c->q.d[i]; }
+	q->hit = c->q.hit;
+	q->count = c->d_counters->count[0];
+	q->rounds = kMaxBounce + 1; q->round_stride = kNumSegments * kCursorStride; q->seg_stride = kCursorStride;
+	q->segments = kNumSegments; q->seg_cap = c->seg_cap;
+	q->tmin = c->params.ray_tmin;
+	clear_counters(c, c->d_counters, 1, c->stream);
+	HIP_TRY(c, hipGetLastError());
+	return ADYPT_OK;
+}
+// the closest hits of the rays of round `round` in queue `parity` (the count of every segment where ctx_ray_queues says) into the hit queue: one launch
+// of k_trace on the context's stream, no host sync
+int ctx_trace_queue(adypt_ctx *c, int parity, int round)
+{
+	return launch_trace(c, c->pipes[0], full_window(c), parity, c->d_counters->count[round], c->d_counters->cursor[round], c->params.stack_size, false, nullptr);
+}
 
 // ---- what the refit (refit.hip) needs of a context ----
 CtxScene ctx_scene(adypt_ctx *c)
@@ -786,7 +811,7 @@ int ctx_replace_bvh(adypt_ctx *c, Buffer<uint4> *nodes, Buffer<int32_t> *tri_ind
 // ---- what replacing the triangles (geometry.hip) needs of a context ----
 CtxMaterials ctx_materials(adypt_ctx *c)
 {
-	return CtxMaterials{(const float4 *)c->d_materials, c->n_mats, c->n_tex, kMatFloat4, c->tun.shade_bin != 0};
+	return CtxMaterials{(const float4 *)c->d_materials, c->n_mats, c->n_tex, kMatFloat4, c->tun.shade_bin != 0, (const uint32_t *)c->d_texels};
 }
 void ctx_set_create_error(const std::string &msg) { g_create_error = msg; }
 // ctx_replace_bvh, and with `geometry` the triangles the tree was built of as well (packed by k_pack_triangles, complete on the context's stream): the

@@ -394,6 +394,10 @@ int adypt_probe_noise(const float *samples, int k, int first, int n_frames, floa
 // ---- denoise_kernels.hpp: the product's kernels, launched with the product's launch shapes ------------------------------------------------
 namespace {
 
+// The kernels of the chain through mirrors and glass are compiled here with the others but have no entry: between two of their rounds stands the
+// context's own traversal, so they are held to their truth through the product (tests/test_gpu_denoise_specular.py), k_denoise_prepare_class with them.
+[[maybe_unused]] const void *const kKernelsWithoutEntry[] = {(const void *)k_chain_start, (const void *)k_chain_step, (const void *)k_denoise_prepare_class};
+
 constexpr uint32_t kUnwritten = 0x7fc0deadu; // every output is filled with this quiet NaN before the launch: a pixel no thread wrote keeps it
 constexpr int kMaxSide = 4096;
 constexpr int64_t kSlackTris = 64;           // triangles of slack in front of and behind the gather's two tables ...

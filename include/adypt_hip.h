@@ -384,6 +384,38 @@ int adypt_denoise_temporal_rectified(adypt_ctx *ctx, const adypt_denoise_params 
 int adypt_read_denoise_rectify(adypt_ctx *ctx, float *kept);
 int adypt_get_denoise_rectify(adypt_ctx *ctx, adypt_denoise_rectify *out);
 
+/* ---- mirrors and glass: guides of the first surface that is not a delta material ------------------------------------------------------------------
+ * adypt_denoise guides a pixel by its primary hit.  On a perfect mirror (illum 3..5) or glass (illum 6, 7) that is the mirror's own plane, its own normal
+ * and albedo 0, and the pixel carries the hit flag of the wall beside it: the levels pool across the silhouette and across everything the mirror
+ * shows.  adypt_denoise_specular follows such pixels — mirrors reflect, glass transmits where it can, else reflects — for up to `bounces` bounces and
+ * guides them by the surface the chain ends on: albedo (throughput x its diffuse colour), its normal and position; a chain that leaves the scene gets
+ * the sky's direction as its normal.  Every pixel gets a class code where the hit flag stood — 0 a primary miss, 1 a primary hit that is followed
+ * nowhere, 1 + L a chain that ended on a surface after L bounces (a chain cut at L = bounces too), -(L + 1) one that escaped after L bounces — and the
+ * levels count a tap only where its code is the centre's.  The definition is pinned bit for bit in csrc/device/guide_chain.hpp; tests/specular_truth.py
+ * restates it in numpy.  The chain's rays run through the context's own traversal kernel on its ray queues, behind the guide capture, without a host
+ * sync; towards frames started ahead the call behaves as adypt_trace_rays.  Nothing else of the context changes, as for adypt_denoise.
+ * Memory: 32 B per local pixel (throughput, direction, length), allocated at the first such call.  Several devices: every device follows the chains of its
+ * own blocks; the class travels in the .w of the primary-hit image.  No temporal form: the merge reprojects the position guide through the camera. */
+typedef struct adypt_specular_params {
+	int32_t bounces;             /* in [1, 8] */
+} adypt_specular_params;
+typedef struct adypt_denoise_specular_info {
+	int32_t have;                /* 1: adypt_denoise_specular or adypt_read_denoise_guides_specular has run on this context (else all below but device_bytes are 0) */
+	int32_t bounces;             /* of the last such call */
+	float chain_ms;              /* HIP-event time of its chain stage alone: k_chain_start, the rounds of traversal + k_chain_step */
+	int64_t rays;                /* rays the chain traced */
+	int64_t pixels_followed;     /* pixels whose primary hit is a delta material and whose chain started */
+	int64_t pixels_escaped;      /* ... that ended in the sky */
+	int64_t pixels_truncated;    /* ... that were cut on a delta surface */
+	int64_t device_bytes;        /* the per-pixel chain state and the counters as allocated */
+} adypt_denoise_specular_info;
+/* adypt_denoise with followed guides; params may be NULL (the defaults), specular may not.  The result is read through adypt_read_denoised.
+ * Refusals: adypt_denoise's, and ADYPT_E_INVALID for a NULL specular or bounces outside [1, 8]. */
+int adypt_denoise_specular(adypt_ctx *ctx, const adypt_denoise_params *params, const adypt_specular_params *specular);
+/* adypt_read_denoise_guides with the chain followed for `bounces` bounces; chain (may be NULL): W*H class codes */
+int adypt_read_denoise_guides_specular(adypt_ctx *ctx, int32_t bounces, float *albedo, float *normal, float *position, int8_t *chain);
+int adypt_get_denoise_specular(adypt_ctx *ctx, adypt_denoise_specular_info *out);
+
 /* ---- moving geometry: new vertex positions without a new BVH and a new context ----------------------------------------------------------------
  * The tree's topology stays valid when vertices move; what goes stale are the boxes, the Woop data and the triangle records.  adypt_update_triangles
  * replaces the positions (count x 9 floats: p0 p1 p2 of every triangle) and, unless normals is NULL, the normals (count x 9 floats) of triangles
@@ -763,6 +795,11 @@ int adypt_multi_get_denoise_motion(adypt_multi *m, adypt_denoise_motion *out);
 int adypt_multi_denoise_temporal_rectified(adypt_multi *m, const adypt_denoise_params *params, const adypt_temporal_params *temporal, const adypt_rectify_params *rectify, int follow_motion);
 int adypt_multi_read_denoise_rectify(adypt_multi *m, float *kept);
 int adypt_multi_get_denoise_rectify(adypt_multi *m, adypt_denoise_rectify *out);
+/* adypt_denoise_specular ... for the whole image: every device follows the chains of its own blocks before the host collects the images; the result
+ * is the one-device result bit for bit.  adypt_multi_get_denoise_specular: the counts and bytes summed over the devices, chain_ms the largest. */
+int adypt_multi_denoise_specular(adypt_multi *m, const adypt_denoise_params *params, const adypt_specular_params *specular);
+int adypt_multi_read_denoise_guides_specular(adypt_multi *m, int32_t bounces, float *albedo, float *normal, float *position, int8_t *chain);
+int adypt_multi_get_denoise_specular(adypt_multi *m, adypt_denoise_specular_info *out);
 /* adypt_update_triangles on every device: the scene is replicated and every device refits its own copy; no collective.  (One process per GPU: every
  * rank calls adypt_update_triangles on its own context.) */
 int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals);

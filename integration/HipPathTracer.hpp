@@ -422,6 +422,21 @@ public:
 		return false;
 	}
 
+	// The image through the denoiser with guides that follow perfect mirrors and glass (adypt_hip.h, adypt_denoise_specular): a pixel whose primary
+	// hit is a delta material is guided by the first surface its chain of up to `bounces` reflections / transmissions (1 .. 8) ends on, and pixels of
+	// different chain classes do not pool.  chain, where not null: W x H class codes (0 a primary miss, 1 a primary hit followed nowhere, 1 + L ended on a
+	// surface after L bounces, -(L + 1) left the scene).  No temporal form.
+	bool DenoiseSpecular(std::vector<float> *rgb, int bounces = 4, std::vector<int8_t> *chain = nullptr, const adypt_denoise_params *params = nullptr)
+	{
+		const adypt_specular_params s = {bounces};
+		rgb->resize((size_t)m_width * m_height * 3);
+		if(chain) chain->resize((size_t)m_width * m_height);
+		if(adypt_multi_denoise_specular(m_gpus, params, &s) == ADYPT_OK && adypt_multi_read_denoised(m_gpus, rgb->data()) == ADYPT_OK &&
+		   (!chain || adypt_multi_read_denoise_guides_specular(m_gpus, bounces, nullptr, nullptr, nullptr, chain->data()) == ADYPT_OK)) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
 	// what DrawScreen puts on screen, for a caller-owned W x H RGBA8 texture / window (every device fills in its own tiles)
 	bool ReadScreen(std::vector<uint8_t> *rgba8) const
 	{
