@@ -101,6 +101,11 @@ class DenoiseRectify(Struct):
     _fields_ = [("have", C.c_int32), ("radius", C.c_int32), ("gamma", C.c_float), ("window_ms", C.c_float), ("device_bytes", C.c_int64)]
 
 
+class DenoiseMoments(Struct):
+    """adypt_denoise_moments."""
+    _fields_ = [("have", C.c_int32), ("variance_ms", C.c_float), ("pixels_spatial", C.c_int64), ("device_bytes", C.c_int64)]
+
+
 class SpecularParams(C.Structure):
     """adypt_specular_params."""
     _fields_ = [("bounces", C.c_int32)]
@@ -250,6 +255,12 @@ _SIGS = {
     "adypt_multi_denoise_temporal_rectified": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(RectifyParams), C.c_int]),
     "adypt_multi_read_denoise_rectify": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_get_denoise_rectify": (C.c_int, [C.c_void_p, C.POINTER(DenoiseRectify)]),
+    "adypt_denoise_temporal_moments": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_int]),
+    "adypt_read_denoise_variance": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_get_denoise_moments": (C.c_int, [C.c_void_p, C.POINTER(DenoiseMoments)]),
+    "adypt_multi_denoise_temporal_moments": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_int]),
+    "adypt_multi_read_denoise_variance": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_multi_get_denoise_moments": (C.c_int, [C.c_void_p, C.POINTER(DenoiseMoments)]),
     "adypt_denoise_specular": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(SpecularParams)]),
     "adypt_read_denoise_guides_specular": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adypt_get_denoise_specular": (C.c_int, [C.c_void_p, C.POINTER(DenoiseSpecular)]),

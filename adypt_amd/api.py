@@ -751,9 +751,9 @@ class _Tracer:
     # ---- denoising (adypt_denoise, include/adypt_hip.h; the definition: csrc/device/denoise.hpp); several devices: of the whole image ----
     def Denoise(self, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 0.1, temporal: bool = False, history_cap: float = 64.0,
                 commit: bool = True, follow_motion: bool = False, rectify: bool = False, rectify_radius: int = 3, rectify_gamma: float = 1.0,
-                specular_bounces: int = 0) -> np.ndarray:
+                specular_bounces: int = 0, moments: bool = False) -> np.ndarray:
         """H x W x 3 float32: the accumulated image through the variance- and primary-hit-guided a-trous filter.  Needs the noise statistics on and
-        >= 2 spp in every block; the image, the statistics and the tracing state are left as they are.
+        >= 2 spp in every block (moments: 1); the image, the statistics and the tracing state are left as they are.
         temporal (adypt_denoise_temporal; the definition: csrc/device/temporal.hpp): before the filter, what the last committing call left is
         reprojected through the primary hit and counted as up to history_cap further samples where the surface is still the same; commit: this
         call's state replaces that history (once per pose: after tracing, before the camera or the scene changes).  Give every pose a shift_seed of
@@ -767,7 +767,18 @@ class _Tracer:
         sun).  rectify_radius in [1, 3], rectify_gamma a finite number >= 0.  Combines with follow_motion.
         specular_bounces (adypt_denoise_specular; the definition: csrc/device/guide_chain.hpp): 0 is the call above to the bit; K in [1, 8] guides a
         pixel whose primary hit is a perfect mirror or glass by the first surface its chain of up to K reflections / transmissions ends on, and
-        keeps pixels of different chain classes from pooling.  No temporal form: the merge reprojects the position guide through the camera."""
+        keeps pixels of different chain classes from pooling.  No temporal form: the merge reprojects the position guide through the camera.
+        moments (adypt_denoise_temporal_moments; needs temporal; the definition: csrc/device/moments.hpp): the call runs from 1 spp in every block.
+        The history carries the second moment of the demodulated luminance instead of a variance, and the variance the filter sees is made after the
+        merge: from the moments where the merged history is at least 4 samples long, from a 7 x 7 window on the pixel's surface where it is
+        shorter.  A moments call and a plain temporal call do not find each other's history.  Combines with follow_motion; not with rectify (the
+        clamp would leave the moment inconsistent with the colour) and not with specular_bounces."""
+        if moments and not temporal:
+            raise ValueError("Denoise: moments=True needs temporal=True")
+        if moments and rectify:
+            raise ValueError("Denoise: moments=True does not combine with rectify=True (the clamp would leave the second moment inconsistent with the colour)")
+        if moments and specular_bounces:
+            raise ValueError("Denoise: moments=True does not combine with specular_bounces")
         if follow_motion and not temporal:
             raise ValueError("Denoise: follow_motion=True needs temporal=True")
         if rectify and not temporal:
@@ -780,6 +791,9 @@ class _Tracer:
         if specular_bounces:
             sp = N.SpecularParams(specular_bounces)
             self._call("denoise_specular", C.byref(prm), C.byref(sp))
+        elif moments:
+            tp = N.TemporalParams(history_cap, 1 if commit else 0)
+            self._call("denoise_temporal_moments", C.byref(prm), C.byref(tp), 1 if follow_motion else 0)
         elif temporal and rectify:
             tp, rp = N.TemporalParams(history_cap, 1 if commit else 0), N.RectifyParams(rectify_radius, rectify_gamma)
             self._call("denoise_temporal_rectified", C.byref(prm), C.byref(tp), C.byref(rp), 1 if follow_motion else 0)
@@ -830,9 +844,22 @@ class _Tracer:
         self._call("get_denoise_rectify", C.byref(out))
         return out.as_dict()
 
+    def ReadDenoiseVariance(self) -> np.ndarray:
+        """H x W float32: the variance the first level saw at every pixel in the last Denoise(temporal=True, moments=True)."""
+        v = np.zeros((self.height, self.width), dtype=np.float32)
+        self._call("read_denoise_variance", v.ctypes.data)
+        return v
+
+    def GetDenoiseMoments(self) -> dict:
+        """have (0 / 1), variance_ms (the variance kernel's HIP-event milliseconds) and pixels_spatial (the pixels that took the window estimate) of the
+        last moments call, and device_bytes of what moments keeps on the (first) device: the variance read-out and the count."""
+        out = N.DenoiseMoments()
+        self._call("get_denoise_moments", C.byref(out))
+        return out.as_dict()
+
     def GetDenoiseMergeMs(self) -> float:
         """HIP-event milliseconds of the merge kernel of the last Denoise(temporal=True) (with follow_motion: of the gather kernel and the merge kernel;
-        with rectify: of the window kernel too)."""
+        with rectify: of the window kernel too; with moments: of the variance kernel too)."""
         ms = C.c_float(0.0)
         self._call("get_denoise_merge_ms", C.byref(ms))
         return float(ms.value)

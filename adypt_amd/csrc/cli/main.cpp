@@ -361,6 +361,7 @@ static bool move_scene(Session &s)
 static int temporal_call(Session &s)
 {
 	const Options &o = s.opt;
+	if(o.denoise_moments) return adypt_multi_denoise_temporal_moments(s.multi, &s.denoise_params, &s.temporal_params, o.follow_motion ? 1 : 0);
 	if(o.rectify) return adypt_multi_denoise_temporal_rectified(s.multi, &s.denoise_params, &s.temporal_params, &o.rectify_params, o.follow_motion ? 1 : 0);
 	return o.follow_motion ? adypt_multi_denoise_temporal_motion(s.multi, &s.denoise_params, &s.temporal_params) : adypt_multi_denoise_temporal(s.multi, &s.denoise_params, &s.temporal_params);
 }
@@ -566,8 +567,17 @@ static bool report_temporal(Session &s)
 		if(adypt_multi_read_denoise_rectify(s.multi, kept.data()) != ADYPT_OK) return tracer_failed(s.multi, "\n");
 		printf(", rectified %lld pixels", (long long)std::count_if(kept.begin(), kept.end(), [](float k) { return k < 1.0f; }));
 	}
+	std::vector<float> variance;
+	if(o.denoise_moments)
+	{
+		adypt_denoise_moments info;
+		variance.assign(length.size(), 0.0f);
+		if(adypt_multi_get_denoise_moments(s.multi, &info) != ADYPT_OK || adypt_multi_read_denoise_variance(s.multi, variance.data()) != ADYPT_OK) return tracer_failed(s.multi, "\n");
+		printf(", spatial variance on %lld pixels", (long long)info.pixels_spatial);
+	}
 	printf("\n");
 	if(!o.rectify_out.empty() && !save_grey(s, o.rectify_out, kept, "kept history shares")) return false;
+	if(!o.variance_out.empty() && !save_grey(s, o.variance_out, variance, "variance")) return false;
 	return o.history_out.empty() || save_grey(s, o.history_out, length, "history lengths");
 }
 

@@ -61,6 +61,11 @@
 //              much as it disagrees: for light that changed on a surface that stands still.  Combines with --follow-motion.  --rectify-out kept.exr: the
 //              share of its length every pixel's history kept, as a grey EXR.  The [PT]TEMPORAL: line then ends `, rectified K pixels`: those with a
 //              share below 1.  --rectify-gamma, --rectify-radius and --rectify-out need --rectify
+//   --denoise-moments: with a temporal --denoise call only (else exit 2): every temporal call is a moments call (adypt_multi_denoise_temporal_moments) — the
+//              history carries the second moment of the demodulated luminance, the variance is made after the merge (from a 7 x 7 window where the
+//              history is shorter than 4 samples) — and --spp may be 1, for the --history-from poses too.  Combines with --follow-motion; not with
+//              --rectify or --denoise-specular (exit 2).  The [PT]TEMPORAL: line then ends `, spatial variance on S pixels`: those that took the window
+//              estimate.  --variance-out v.exr (needs --denoise-moments): the variance the first level saw, as a grey EXR
 //   --denoise-specular K: with --denoise only, and with none of the temporal options (else exit 2): the guides of a pixel whose primary hit is a perfect
 //              mirror or glass follow the reflection / transmission for up to K bounces, 1 .. 8, to the first surface that is neither
 //              (adypt_multi_denoise_specular).  One [PT]SPECULAR: line reports the followed, escaped and truncated pixels and the rays
@@ -78,7 +83,7 @@ const char *const USAGE =
 	"scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] "
 	"[--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--denoise-specular K] "
 	"[--history-from other.config]... [--history-cap C] [--history-out len.exr] [--follow-motion] [--rectify [--rectify-gamma G] [--rectify-radius R] "
-	"[--rectify-out kept.exr]]] [--guides-out PREFIX] [--pose moved.obj [--by-vertices [--recompute-normals]] | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] "
+	"[--rectify-out kept.exr]] [--denoise-moments [--variance-out v.exr]]] [--guides-out PREFIX] [--pose moved.obj [--by-vertices [--recompute-normals]] | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] "
 	"[--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]";
 
 // ---- values ----
@@ -205,6 +210,8 @@ static const struct Spec { const char *name; bool value; Apply apply; } SPECS[] 
 	{"--rectify-out", true, [](Options &o, const char *v) { o.rectify_out = v; return o.rectify_detail = true; }},
 	{"--rectify-radius", true, rectify_radius},
 	{"--rectify-gamma", true, rectify_gamma},
+	{"--denoise-moments", false, flag<&Options::denoise_moments>},
+	{"--variance-out", true, text<&Options::variance_out>},
 	{"--guides-out", true, text<&Options::guides_out>},
 	{"--pose", true, text<&Options::pose>},
 	{"--by-vertices", false, flag<&Options::by_vertices>},
@@ -267,7 +274,12 @@ int check_options(Options *opt)
 	if(o.until && (o.primary >= 0 || o.spp < 2 || o.check_every < 1)) return refuse("--noise needs --spp >= 2, --check-every >= 1 and no --primary");
 	if(o.adaptive && (!o.until || o.save_every > 0)) return refuse("--adaptive needs --noise T and does not combine with --save-every");
 	if(!o.adaptive && !o.spp_out.empty()) return refuse("--spp-out needs --adaptive");
-	if(o.denoise && (o.primary >= 0 || o.spp < 2)) return refuse("--denoise needs --spp >= 2 and no --primary");
+	if(!o.variance_out.empty() && !o.denoise_moments) return refuse("--variance-out needs --denoise-moments");
+	if(o.denoise_moments && o.rectify) return refuse("--denoise-moments does not combine with --rectify: the clamp would leave the second moment inconsistent with the colour");
+	if(o.denoise_moments && o.denoise_specular) return refuse("--denoise-moments does not combine with --denoise-specular");
+	if(o.denoise_moments && !(o.denoise && o.temporal)) return refuse("--denoise-moments needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out");
+	if(o.denoise_moments && (o.primary >= 0 || o.spp < 1)) return refuse("--denoise with --denoise-moments needs --spp >= 1 and no --primary");
+	if(o.denoise && !o.denoise_moments && (o.primary >= 0 || o.spp < 2)) return refuse("--denoise needs --spp >= 2 and no --primary");
 	if(o.denoise && (o.denoise_levels < 1 || o.denoise_levels > 6)) return refuse("--denoise-levels must be in 1 .. 6");
 	if(o.denoise_specular && !o.denoise) return refuse("--denoise-specular needs --denoise file.exr");
 	if(o.denoise_specular && (o.temporal || o.follow_motion || o.rectify))

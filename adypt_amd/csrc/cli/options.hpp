@@ -33,6 +33,8 @@ struct Options
 	bool rectify_detail = false; // one of --rectify-gamma, --rectify-radius, --rectify-out was given
 	adypt_rectify_params rectify_params{3, 1.0f};
 	std::string rectify_out;
+	bool denoise_moments = false; // --denoise-moments: every temporal call is a moments call, from 1 spp
+	std::string variance_out;
 	std::string pose, part_matrices;
 	bool by_vertices = false, recompute_normals = false; // --pose by the mesh binding; its normals computed on the device
 	std::vector<std::string> morph_targets;

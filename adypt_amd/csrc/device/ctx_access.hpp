@@ -60,8 +60,9 @@ struct DenoiseInputs {
 	std::vector<int32_t> block_index;  // host copy of `blocks`
 	std::vector<int32_t> block_spp;    // samples in every owned block
 };
-// ADYPT_OK, or ADYPT_E_STATE with the reason in the context's error (statistics off, a viewer's image, a block below 2 spp)
-int ctx_denoise_ready(adypt_ctx *c, const char *fn);
+// ADYPT_OK, or ADYPT_E_STATE with the reason in the context's error (statistics off, a viewer's image, a block below min_spp: 1 for a moments call,
+// whose S0 is defined from one sample, 2 for every other)
+int ctx_denoise_ready(adypt_ctx *c, const char *fn, int min_spp);
 DenoiseInputs ctx_denoise_inputs(adypt_ctx *c);
 // see tracer.hip
 int ctx_capture_guides(adypt_ctx *c, const char *fn, float4 *albedo, float4 *normal, float4 *position, float4 *hits);

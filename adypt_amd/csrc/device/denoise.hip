@@ -18,6 +18,10 @@
 //     k_rectify_window<R>  a rectified call only (the definition: rectify.hpp), before the merge and inside its stage of the timer: per pixel the mean of the
 //                    (2 R + 1)^2 window of the call's own images on the pixel's surface and the squared limit a history value may lie from it, row-major
 //                    R0 = (mu.rgb, k), R1 = (g.rgb, 0); k_temporal_merge<., true> clamps the history to them and writes the share of its length it kept
+//     k_moments_variance  a moments call only (the definition: moments.hpp), behind the merge and inside its stage of the timer: such a call's prepare
+//                    (k_denoise_prepare_moments) and merge (k_temporal_merge_moments) carry the raw second moment S where the variance stands;
+//                    this kernel makes the variance of every pixel from the merged (D, S) and n_out — a 7 x 7 window of the merged image where the
+//                    history is short — and writes (D, V) into X0, which the first level then reads.  The merged (D, S) is what a commit leaves
 //     k_atrous<LAST>  one level per launch, X0 ping-pongs; the last level multiplies the albedo back and writes the W x H x 3 result
 // Several devices: every context captures the guides of its own blocks, the host puts the devices' local images back to back in rank order, their
 // block lists likewise (every block has one owner, and k_denoise_prepare takes any block list and writes at the picture's coordinates), uploads them
@@ -100,6 +104,7 @@ struct History {
 	Buffer<float4> h0, h1, h2, ha;
 	TemporalCamera camera;
 	bool present = false;
+	bool moments = false;            // which kind of call wrote it: H0.w is S (a moments call) or V.  A call finds only a history of its own kind
 	Buffer<float4> snapshot;
 	int64_t snapshot_tris = 0;       // the triangles the snapshot holds; 0: the history has none (a context's scene never has 0: adypt_create, adypt_set_triangles)
 	StageTimer<2> snapshot_timer;    // the copy kernel of the last commit with a snapshot
@@ -112,6 +117,8 @@ struct History {
 	// how many triangles of the snapshot the gather may trust for a scene of n_tris triangles (a snapshot of another count is none: adypt_set_triangles
 	// drops it, so this only guards)
 	int64_t known_tris(int64_t n_tris) const { return present && snapshot_tris == n_tris ? snapshot_tris : 0; }
+	// whether a call of the kind given finds it
+	bool found_by(bool moments_call) const { return present && moments == moments_call; }
 	// The snapshot of a committing motion call: the records as they are now, enqueued on `stream` behind the call's gather, which reads the old one.  The
 	// history has none from here until the caller has waited for the stream and commits with *n_tris: a failure in between leaves every pixel unmoved.
 	int enqueue_snapshot(adypt_ctx *c, hipStream_t stream, int64_t *n_tris)
@@ -129,8 +136,9 @@ struct History {
 	}
 	// A finished call's merged image, guides (X2.w = n_out) and camera become the history: swapped in, nothing is copied, and what the history held is
 	// overwritten by the call's next prepare.  snapshot_of: what enqueue_snapshot gave; 0: the call made none, and the history has none from here.
-	void commit(Buffer<float4> &merged, Buffer<float4> &x1, Buffer<float4> &x2, Buffer<float4> &xa, const CtxCamera &cam, int64_t snapshot_of)
+	void commit(Buffer<float4> &merged, Buffer<float4> &x1, Buffer<float4> &x2, Buffer<float4> &xa, const CtxCamera &cam, int64_t snapshot_of, bool of_moments)
 	{
+		moments = of_moments;
 		std::swap(merged, h0); std::swap(x1, h1); std::swap(x2, h2); std::swap(xa, ha);
 		camera = temporal_camera(cam.origin, cam.inv_proj, cam.inv_view);
 		snapshot_tris = snapshot_of;
@@ -185,6 +193,15 @@ struct Denoiser {
 	int chain_bounces = 0;
 	StageTimer<2> chain_timer;
 
+	// variance from temporal moments (moments.hpp): the variance read-out, 4 B per image pixel, and the counters of the pixels that took the window estimate (512 B),
+	// allocated at the first moments call; the count and the variance kernel's time of the last one
+	Buffer<float> variance;
+	Buffer<unsigned long long> spatial_count;
+	bool variance_valid = false; // as length_valid, of a moments call and `variance`
+	int64_t pixels_spatial = 0;
+	unsigned long long spatial_readback[kMomentsCountSlots] = {}; // where the running call's counters are copied to (a member: the copy is enqueued, and outlives a call that fails behind it)
+	StageTimer<2> variance_timer;
+
 	size_t pixels() const { return (size_t)width * (size_t)height; }
 };
 
@@ -209,6 +226,8 @@ struct DenoiseCall {
 	const char *fn;
 	std::string refused;            // why the arguments are refused; empty: they are not
 	int bounces = 0;                // adypt_denoise_specular: the guides follow mirrors and glass for this many bounces; 0: the primary hit's guides
+	bool moments = false;           // of Temporal and Motion: the variance comes from temporal luminance moments (moments.hpp); never rectified
+	int min_spp() const { return moments ? 1 : 2; } // the samples every block has to hold: V0 of denoise_prepare is not defined below 2, S0 is from 1
 };
 
 // the call of the ABI structs (null: the defaults — 5 levels, 4.0, 0.1; cap 64, committing; radius 3, gamma 1); tp is looked at by Temporal and Motion
@@ -239,6 +258,15 @@ DenoiseCall make_specular_call(const char *fn, const adypt_denoise_params *p, co
 	return call;
 }
 
+// adypt_denoise_temporal_moments' call: a Temporal or Motion call whose fourth channel is S (it has no rectified form: the clamp would move the colour
+// and leave S inconsistent with it — and none with followed guides, as no temporal call has)
+DenoiseCall make_moments_call(const char *fn, const adypt_denoise_params *p, const adypt_temporal_params *tp, int follow_motion)
+{
+	DenoiseCall call = make_call(follow_motion ? Mode::Motion : Mode::Temporal, fn, p, tp);
+	call.moments = true;
+	return call;
+}
+
 // prepare (+ the gather + the temporal merge) + the levels (+ the snapshot) of a call, on `stream`; d's images are the whole picture's
 // (ensure_filter_images), `cam` the camera of the context the guides were captured by
 int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages &in, const DenoiseCall &call, const CtxCamera &cam)
@@ -258,13 +286,18 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 		CTX_TRY(c, at_least(d->r0, n)); CTX_TRY(c, at_least(d->r1, n)); CTX_TRY(c, at_least(d->kept, n));
 		d->kept_valid = false;
 	}
+	if(call.moments)
+	{
+		CTX_TRY(c, at_least(d->variance, n)); CTX_TRY(c, at_least(d->spatial_count, kMomentsCountSlots));
+		d->variance_valid = false;
+	}
 	const int width = d->width, height = d->height, n_px = in.n_blocks * kBlockPixels;
 	const int blocks_x = (width + kBlockDim - 1) / kBlockDim;
 	const int32_t *blocks = in.as<kBlocks>();
 	const float4 *normal = in.as<kNormal>(), *position = in.as<kPosition>(), *hits = in.as<kHits>();
 	const LaunchShape prepare = prepare_launch(n_px);
 	// (followed guides: X1.w is the class the chain left in the .w of the primary-hit image)
-	hipLaunchKernelGGL(call.bounces > 0 ? k_denoise_prepare_class : k_denoise_prepare, prepare.grid, prepare.block, 0, stream, in.as<kAccum>(), in.as<kMoments>(), blocks, in.as<kBlockSpp>(), n_px, blocks_x, width, height,
+	hipLaunchKernelGGL(call.moments ? k_denoise_prepare_moments : call.bounces > 0 ? k_denoise_prepare_class : k_denoise_prepare, prepare.grid, prepare.block, 0, stream, in.as<kAccum>(), in.as<kMoments>(), blocks, in.as<kBlockSpp>(), n_px, blocks_x, width, height,
 	                   in.as<kAlbedo>(), normal, position, hits, d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get());
 	CTX_TRY(c, hipGetLastError());
 	CTX_TRY(c, d->timer.mark(2, stream));
@@ -294,15 +327,38 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 			CTX_TRY(c, d->window_timer.mark(1, stream));
 		}
 		const auto merge = call.rectify ? (with_motion ? k_temporal_merge<true, true> : k_temporal_merge<false, true>) : (with_motion ? k_temporal_merge<true, false> : k_temporal_merge<false, false>);
-		hipLaunchKernelGGL(merge, merge_shape.grid, merge_shape.block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, d->x2.get(), (const float4 *)d->xa, (const float4 *)h.h0, (const float4 *)h.h1,
-		                   (const float4 *)h.h2, (const float4 *)h.ha, d->xm.get(), d->length.get(), width, height, h.present ? 1 : 0, h.camera, call.history_cap, (const float4 *)d->xp,
-		                   (const float4 *)d->xn, (const float4 *)d->r0, (const float4 *)d->r1, d->kept.get(), call.gamma);
+		if(call.moments)
+		{
+			hipLaunchKernelGGL(with_motion ? k_temporal_merge_moments<true> : k_temporal_merge_moments<false>, merge_shape.grid, merge_shape.block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1,
+			                   d->x2.get(), (const float4 *)d->xa, (const float4 *)h.h0, (const float4 *)h.h1, (const float4 *)h.h2, (const float4 *)h.ha, d->xm.get(), d->length.get(), width, height,
+			                   h.found_by(true) ? 1 : 0, h.camera, call.history_cap, (const float4 *)d->xp, (const float4 *)d->xn);
+		}
+		else
+		{
+			hipLaunchKernelGGL(merge, merge_shape.grid, merge_shape.block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, d->x2.get(), (const float4 *)d->xa, (const float4 *)h.h0, (const float4 *)h.h1,
+			                   (const float4 *)h.h2, (const float4 *)h.ha, d->xm.get(), d->length.get(), width, height, h.found_by(false) ? 1 : 0, h.camera, call.history_cap, (const float4 *)d->xp,
+			                   (const float4 *)d->xn, (const float4 *)d->r0, (const float4 *)d->r1, d->kept.get(), call.gamma);
+		}
 		CTX_TRY(c, hipGetLastError());
+		if(call.moments)
+		{
+			// (D, V) of the merged (D, S) into X0[0], which the merge has read and the first level reads; the merged image itself stays for the commit
+			RectifyOrigin origin;
+			for(int k = 0; k < 3; ++k) origin.o[k] = cam.origin[k];
+			const LaunchShape variance_shape = variance_launch(width, height);
+			CTX_TRY(c, hipMemsetAsync(d->spatial_count.get(), 0, sizeof(d->spatial_readback), stream));
+			CTX_TRY(c, d->variance_timer.mark(0, stream));
+			hipLaunchKernelGGL(k_moments_variance, variance_shape.grid, variance_shape.block, 0, stream, (const float4 *)d->xm, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, d->x0[0].get(),
+			                   d->variance.get(), d->spatial_count.get(), width, height, origin);
+			CTX_TRY(c, hipGetLastError());
+			CTX_TRY(c, d->variance_timer.mark(1, stream));
+			CTX_TRY(c, hipMemcpyAsync(d->spatial_readback, d->spatial_count.get(), sizeof(d->spatial_readback), hipMemcpyDeviceToHost, stream));
+		}
 		CTX_TRY(c, d->timer.mark(marks.merge, stream));
 	}
 	for(int l = 0; l < prm.levels; ++l)
 	{
-		const float4 *src = (l == 0 && with_history) ? d->xm : d->x0[l & 1];
+		const float4 *src = (l == 0 && with_history && !call.moments) ? d->xm : d->x0[l & 1];
 		float4 *dst = d->x0[(l & 1) ^ 1];
 		const auto level = l == prm.levels - 1 ? k_atrous<true> : k_atrous<false>;
 		hipLaunchKernelGGL(level, level_shape.grid, level_shape.block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
@@ -317,7 +373,13 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 	if(with_history) d->length_valid = true;
 	if(with_motion) d->xp_valid = true;
 	if(call.rectify) { d->kept_valid = true; d->rectify_radius = call.radius; d->rectify_gamma = call.gamma; }
-	if(call.commit) h.commit(d->xm, d->x1, d->x2, d->xa, cam, snapshot_of);
+	if(call.moments)
+	{
+		d->variance_valid = true;
+		d->pixels_spatial = 0;
+		for(const unsigned long long n_slot : d->spatial_readback) d->pixels_spatial += (int64_t)n_slot;
+	}
+	if(call.commit) h.commit(d->xm, d->x1, d->x2, d->xa, cam, snapshot_of, call.moments);
 	return ADYPT_OK;
 }
 
@@ -472,6 +534,26 @@ int get_rectify(adypt_ctx *c, const char *fn, adypt_denoise_rectify *out)
 	return ADYPT_OK;
 }
 
+// the variance the first level saw in the last moments call
+int read_variance(adypt_ctx *c, const char *fn, float *v)
+{
+	return read_image(c, fn, ": no moments call has run yet (adypt_denoise_temporal_moments)", v, 1, [](Denoiser *d) { return d->variance_valid ? d->variance.get() : nullptr; });
+}
+
+int get_moments(adypt_ctx *c, const char *fn, adypt_denoise_moments *out)
+{
+	if(!out) return ctx_fail(c, ADYPT_E_INVALID, std::string(fn) + ": out is null");
+	*out = adypt_denoise_moments{};
+	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
+	if(!d) return ADYPT_OK;
+	out->device_bytes = (int64_t)(d->variance.bytes() + d->spatial_count.bytes());
+	if(!d->variance_valid) return ADYPT_OK;
+	out->have = 1;
+	out->pixels_spatial = d->pixels_spatial;
+	(void)d->variance_timer.read(&out->variance_ms, 1, 1, false);
+	return ADYPT_OK;
+}
+
 int read_guides(adypt_ctx *c, const char *fn, int bounces, float *albedo, float *normal, float *position, uint8_t *hit, int8_t *chain); // (below, beside its entry points)
 
 // what the last chain of a context did: its counters are read here, behind whatever the context's stream still holds
@@ -509,7 +591,7 @@ int denoise_context(adypt_ctx *c, const DenoiseCall &call)
 	const char *fn = call.fn;
 	const CtxInfo i = ctx_info(c);
 	if(i.nranks != 1) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the context is a tile shard (tile_nranks > 1): the filter needs the whole image (adypt_multi_denoise)");
-	CTX_STEP(ctx_denoise_ready(c, fn));
+	CTX_STEP(ctx_denoise_ready(c, fn, call.min_spp()));
 	CTX_TRY(c, hipSetDevice(i.device));
 	Denoiser *d = denoiser_of(c);
 	CTX_STEP(ensure_filter_images(c, d, i));
@@ -546,6 +628,15 @@ int adypt_denoise_temporal_rectified(adypt_ctx *c, const adypt_denoise_params *p
 {
 	return denoise_context(c, make_call(follow_motion ? Mode::Motion : Mode::Temporal, "adypt_denoise_temporal_rectified", p, tp, true, rp));
 }
+
+int adypt_denoise_temporal_moments(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp, int follow_motion)
+{
+	return denoise_context(c, make_moments_call("adypt_denoise_temporal_moments", p, tp, follow_motion));
+}
+
+int adypt_read_denoise_variance(adypt_ctx *c, float *v) { return c && v ? read_variance(c, "adypt_read_denoise_variance", v) : ADYPT_E_INVALID; }
+
+int adypt_get_denoise_moments(adypt_ctx *c, adypt_denoise_moments *out) { return c ? get_moments(c, "adypt_get_denoise_moments", out) : ADYPT_E_INVALID; }
 
 int adypt_read_denoise_rectify(adypt_ctx *c, float *kept) { return c && kept ? read_rectify(c, "adypt_read_denoise_rectify", kept) : ADYPT_E_INVALID; }
 
@@ -652,7 +743,8 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 	const char *fn = call.fn;
 	std::vector<adypt_ctx *> ctx;
 	for(int k = 0; k < n_dev; ++k) ctx.push_back(adypt_multi_context(m, k));
-	CTX_STEP(multi_each(m, [fn](adypt_ctx *c) { return ctx_denoise_ready(c, fn); }));
+	const int min_spp = call.min_spp();
+	CTX_STEP(multi_each(m, [fn, min_spp](adypt_ctx *c) { return ctx_denoise_ready(c, fn, min_spp); }));
 	// every device captures the guides of its own blocks: all enqueued before the first is waited for
 	const int bounces = call.bounces; // (followed guides: every device follows the chains of its own blocks; the class comes along in the primary-hit image)
 	CTX_STEP(multi_each(m, [fn, bounces](adypt_ctx *c) {
@@ -726,6 +818,22 @@ int adypt_multi_denoise_temporal_motion(adypt_multi *m, const adypt_denoise_para
 int adypt_multi_denoise_temporal_rectified(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_rectify_params *rp, int follow_motion)
 {
 	return multi_denoise(m, make_call(follow_motion ? Mode::Motion : Mode::Temporal, "adypt_multi_denoise_temporal_rectified", p, tp, true, rp));
+}
+
+int adypt_multi_denoise_temporal_moments(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp, int follow_motion)
+{
+	return multi_denoise(m, make_moments_call("adypt_multi_denoise_temporal_moments", p, tp, follow_motion));
+}
+
+// the variance read-out and the count live on the first device, where the merge and the variance kernel run
+int adypt_multi_read_denoise_variance(adypt_multi *m, float *v)
+{
+	return v ? on_root(m, [=](adypt_ctx *c) { return read_variance(c, "adypt_multi_read_denoise_variance", v); }) : ADYPT_E_INVALID;
+}
+
+int adypt_multi_get_denoise_moments(adypt_multi *m, adypt_denoise_moments *out)
+{
+	return on_root(m, [=](adypt_ctx *c) { return get_moments(c, "adypt_multi_get_denoise_moments", out); });
 }
 
 // the window statistics and the kept read-out live on the first device, where the merge runs

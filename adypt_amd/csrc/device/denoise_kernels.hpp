@@ -25,7 +25,8 @@ inline LaunchShape local_pixels_launch(int n_px) { return LaunchShape{dim3((unsi
 
 // CLASS: X1.w is the class code the chain through mirrors and glass left in the .w of the primary-hit image (k_chain_start, k_chain_step) instead of the
 // hit flag: adypt_denoise_specular's instance, k_denoise_prepare_class.  The other instance is what k_denoise_prepare was before there was a chain.
-template <bool CLASS>
+// MOMENTS: X0.w = S0, the raw second moment of moments.hpp, defined from 1 spp: a moments call's instance, k_denoise_prepare_moments.
+template <bool CLASS, bool MOMENTS = false>
 __device__ __forceinline__ void denoise_prepare_pixel(const float4 *accum, const float2 *moments, const int32_t *blocks, const int32_t *block_spp, int n_px, int blocks_x, int width, int height,
                                                       const float4 *g_albedo, const float4 *g_normal, const float4 *g_position, const float4 *g_hits, float4 *x0, float4 *x1, float4 *x2,
                                                       float4 *xa)
@@ -37,7 +38,8 @@ __device__ __forceinline__ void denoise_prepare_pixel(const float4 *accum, const
 	if(x >= width || y >= height) return; // (blocks at the right and bottom edge stick out)
 	const size_t p = (size_t)y * width + x;
 	const float4 c = accum[L], a = g_albedo[L], n = g_normal[L], q = g_position[L];
-	const Dn4 d = denoise_prepare(c.x, c.y, c.z, moments[L].y, (float)block_spp[L >> 10], a.x, a.y, a.z);
+	const Dn4 d = MOMENTS ? moments_prepare(c.x, c.y, c.z, moments[L].y, (float)block_spp[L >> 10], a.x, a.y, a.z)
+	                      : denoise_prepare(c.x, c.y, c.z, moments[L].y, (float)block_spp[L >> 10], a.x, a.y, a.z);
 	x0[p] = make_float4(d.x, d.y, d.z, d.w);
 	x1[p] = make_float4(n.x, n.y, n.z, CLASS ? g_hits[L].w : (__float_as_int(g_hits[L].x) != -1 ? 1.0f : 0.0f));
 	x2[p] = make_float4(q.x, q.y, q.z, (float)block_spp[L >> 10]); // (.w: the sample count, which only the temporal merge reads)
@@ -54,6 +56,12 @@ __global__ __launch_bounds__(kPixelThreads) void k_denoise_prepare_class(const f
                                                                          float4 *x0, float4 *x1, float4 *x2, float4 *xa)
 {
 	denoise_prepare_pixel<true>(accum, moments, blocks, block_spp, n_px, blocks_x, width, height, g_albedo, g_normal, g_position, g_hits, x0, x1, x2, xa);
+}
+__global__ __launch_bounds__(kPixelThreads) void k_denoise_prepare_moments(const float4 *accum, const float2 *moments, const int32_t *blocks, const int32_t *block_spp, int n_px, int blocks_x,
+                                                                           int width, int height, const float4 *g_albedo, const float4 *g_normal, const float4 *g_position, const float4 *g_hits,
+                                                                           float4 *x0, float4 *x1, float4 *x2, float4 *xa)
+{
+	denoise_prepare_pixel<false, true>(accum, moments, blocks, block_spp, n_px, blocks_x, width, height, g_albedo, g_normal, g_position, g_hits, x0, x1, x2, xa);
 }
 inline LaunchShape prepare_launch(int n_px) { return local_pixels_launch(n_px); }
 
@@ -274,12 +282,12 @@ struct DeviceHistory {
 // (4 B): 164 B per pixel.  The history's camera comes by value.  MOTION: through k_motion_gather's XP, XN (32 B per pixel more), which the other
 // instance never looks at (they stand last, so that its kernel arguments lie where they lay before there was a motion call).  RECTIFY: the history is held
 // against k_rectify_window's R0, R1 (32 B per pixel more read) and the share of its length it kept is written (4 B); these stand last in turn, and the
-// instances without it pass temporal_merge a constant "off": their code is what it was.
-template <bool MOTION, bool RECTIFY>
-__global__ __launch_bounds__(kAtrousX * kAtrousY) void k_temporal_merge(const float4 *x0, const float4 *x1, float4 *x2, const float4 *xa, const float4 *h0, const float4 *h1,
-                                                                         const float4 *h2, const float4 *ha, float4 *merged, float *length, int width, int height, int have,
-                                                                         TemporalCamera cam, float history_cap, const float4 *xp, const float4 *xn, const float4 *r0, const float4 *r1, float *kept,
-                                                                         float gamma)
+// instances without it pass temporal_merge a constant "off": their code is what it was.  MOMENTS (k_temporal_merge_moments, below): the fourth channel of
+// X0, of the history and of the merged image is the raw second moment S (moments.hpp), blended with w; same bytes, never together with RECTIFY.
+template <bool MOTION, bool RECTIFY, bool MOMENTS>
+__device__ __forceinline__ void temporal_merge_pixel(const float4 *x0, const float4 *x1, float4 *x2, const float4 *xa, const float4 *h0, const float4 *h1, const float4 *h2, const float4 *ha,
+                                                     float4 *merged, float *length, int width, int height, int have, const TemporalCamera &cam, float history_cap, const float4 *xp,
+                                                     const float4 *xn, const float4 *r0, const float4 *r1, float *kept, float gamma)
 {
 	const int x = blockIdx.x * kAtrousX + threadIdx.x, y = blockIdx.y * kAtrousY + threadIdx.y;
 	if(x >= width || y >= height) return;
@@ -288,13 +296,29 @@ __global__ __launch_bounds__(kAtrousX * kAtrousY) void k_temporal_merge(const fl
 	const DeviceHistory hist{h0, h1, h2, ha};
 	Rectify rect;
 	if(RECTIFY) rect = Rectify{true, DeviceImages::load(r0, p), DeviceImages::load(r1, p), gamma};
-	const TemporalOut r = MOTION ? temporal_merge_motion(hist, have != 0, cam, width, height, DeviceImages::load(x0, p), DeviceImages::load(x1, p), DeviceImages::load(xa, p), c2.w, history_cap,
+	const TemporalOut r = MOTION ? temporal_merge_motion<MOMENTS>(hist, have != 0, cam, width, height, DeviceImages::load(x0, p), DeviceImages::load(x1, p), DeviceImages::load(xa, p), c2.w, history_cap,
 	                                                     DeviceImages::load(xp, p), DeviceImages::load(xn, p), rect)
-	                             : temporal_merge(hist, have != 0, cam, width, height, DeviceImages::load(x0, p), DeviceImages::load(x1, p), c2, DeviceImages::load(xa, p), c2.w, history_cap, rect);
+	                             : temporal_merge<MOMENTS>(hist, have != 0, cam, width, height, DeviceImages::load(x0, p), DeviceImages::load(x1, p), c2, DeviceImages::load(xa, p), c2.w, history_cap, rect);
 	merged[p] = make_float4(r.x0.x, r.x0.y, r.x0.z, r.x0.w);
 	x2[p] = make_float4(c2.x, c2.y, c2.z, r.n);
 	length[p] = r.n;
 	if(RECTIFY) kept[p] = r.kept;
+}
+template <bool MOTION, bool RECTIFY>
+__global__ __launch_bounds__(kAtrousX * kAtrousY) void k_temporal_merge(const float4 *x0, const float4 *x1, float4 *x2, const float4 *xa, const float4 *h0, const float4 *h1,
+                                                                         const float4 *h2, const float4 *ha, float4 *merged, float *length, int width, int height, int have,
+                                                                         TemporalCamera cam, float history_cap, const float4 *xp, const float4 *xn, const float4 *r0, const float4 *r1, float *kept,
+                                                                         float gamma)
+{
+	temporal_merge_pixel<MOTION, RECTIFY, false>(x0, x1, x2, xa, h0, h1, h2, ha, merged, length, width, height, have, cam, history_cap, xp, xn, r0, r1, kept, gamma);
+}
+// a moments call's merge: k_temporal_merge<MOTION, false>'s arguments without the rectified call's
+template <bool MOTION>
+__global__ __launch_bounds__(kAtrousX * kAtrousY) void k_temporal_merge_moments(const float4 *x0, const float4 *x1, float4 *x2, const float4 *xa, const float4 *h0, const float4 *h1,
+                                                                                 const float4 *h2, const float4 *ha, float4 *merged, float *length, int width, int height, int have,
+                                                                                 TemporalCamera cam, float history_cap, const float4 *xp, const float4 *xn)
+{
+	temporal_merge_pixel<MOTION, false, true>(x0, x1, x2, xa, h0, h1, h2, ha, merged, length, width, height, have, cam, history_cap, xp, xn, nullptr, nullptr, nullptr, 0.0f);
 }
 inline LaunchShape merge_launch(int width, int height) { return image_launch(width, height); }
 
@@ -359,6 +383,86 @@ __global__ __launch_bounds__(kAtrousX * kAtrousY) void k_rectify_window(const fl
 	r1[p] = make_float4(st.r1.x, st.r1.y, st.r1.z, st.r1.w);
 }
 inline LaunchShape window_launch(int width, int height) { return image_launch(width, height); }
+
+// ---- variance from temporal moments: the variance the first level sees (moments.hpp) ----
+// the planes of the staged tile of the MERGED images, one float per pixel each: lum(D), S, the normal, the point, the albedo, the hit flag
+enum MomentsPlane { kMPlaneY, kMPlaneS, kMPlaneNx, kMPlaneNy, kMPlaneNz, kMPlanePx, kMPlanePy, kMPlanePz, kMPlaneAr, kMPlaneAg, kMPlaneAb, kMPlaneHit, kMomentsPlanes };
+
+// One pixel per thread, the workgroup of k_atrous, behind the merge of a moments call.  Reads the merged (D, S) (16 B), the hit flag and n_out (4 B each);
+// writes (D, V) into `out` — the first level's source, another image than `merged`, which a commit swaps into the history as it is and whose halo the
+// neighbouring workgroups read from global memory — and V into the read-out (4 B): 44 B per pixel.  That is all where no pixel of the workgroup asks its
+// window (moments_wants_window: a hit whose history is shorter than kMomentsMinLength), which one workgroup-wide vote decides before anything else is
+// loaded: in steady state the workgroups away from what the camera uncovered (53 % of them on the bench orbit).  Where one does, the workgroup stages its 32 x 8 pixels with their halo of 3 in LDS as k_rectify_window
+// does — 38 x 14 = 532 pixels, four 16-byte loads each, as kMomentsPlanes planes of floats (25 536 B), lum(D) computed once per staged pixel — and the
+// asking threads visit their 49 taps through moments_tap, row by row: the sums are the definition's to the bit.  A tile pixel outside the image is
+// staged as zeros: its hit flag refuses it.  The loops unroll: every LDS address is the centre's plus a constant, the sums stay in registers, no scratch.
+// The pixels that took the window estimate are counted per workgroup (__syncthreads_count, in the workgroups that staged only: no other has any) and added
+// by one thread to one of kMomentsCountSlots counters, which the host sums: one atomic per wave on ONE address measured 0.30 ms of the kernel's 0.44 ms
+// at 1920 x 1080 where every pixel is counted (32 400 atomics the L2 serialises; profiles/moments_cost.txt has the figures after the change).
+constexpr int kMomentsCountSlots = 64;
+__global__ __launch_bounds__(kAtrousX * kAtrousY) void k_moments_variance(const float4 *__restrict__ merged, const float4 *__restrict__ x1, const float4 *__restrict__ x2,
+                                                                           const float4 *__restrict__ xa, float4 *__restrict__ out, float *__restrict__ variance,
+                                                                           unsigned long long *__restrict__ spatial_count, int width, int height, RectifyOrigin origin)
+{
+	constexpr int R = kMomentsRadius, TW = kAtrousX + 2 * R, TH = kAtrousY + 2 * R, TP = TW * TH;
+	__shared__ float tile[kMomentsPlanes][TP];
+	const int x = blockIdx.x * kAtrousX + threadIdx.x, y = blockIdx.y * kAtrousY + threadIdx.y;
+	const bool inside = x < width && y < height;
+	const size_t p = inside ? (size_t)y * width + x : 0;
+	float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+	float hit_flag = 0.0f, n_out = 0.0f;
+	if(inside) { m = merged[p]; hit_flag = x1[p].w; n_out = x2[p].w; }
+	const bool windowed = inside && moments_wants_window(hit_flag != 0.0f, n_out);
+	const bool staged = __syncthreads_or(windowed ? 1 : 0) != 0; // (uniform over the workgroup: every thread takes the same side below)
+	MomentsSums s{0.0f, 0.0f, 0.0f};
+	if(staged)
+	{
+		const int tid = threadIdx.y * kAtrousX + threadIdx.x;
+		const int gx0 = blockIdx.x * kAtrousX - R, gy0 = blockIdx.y * kAtrousY - R;
+		for(int i = tid; i < TP; i += kAtrousX * kAtrousY)
+		{
+			const int ty = i / TW, tx = i - ty * TW;
+			const int gx = gx0 + tx, gy = gy0 + ty;
+			float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a, c = a, d = a;
+			if(gx >= 0 && gy >= 0 && gx < width && gy < height)
+			{
+				const size_t q = (size_t)gy * width + gx;
+				a = merged[q]; b = x1[q]; c = x2[q]; d = xa[q];
+			}
+			tile[kMPlaneY][i] = noise_luminance(a.x, a.y, a.z); tile[kMPlaneS][i] = a.w;
+			tile[kMPlaneNx][i] = b.x; tile[kMPlaneNy][i] = b.y; tile[kMPlaneNz][i] = b.z; tile[kMPlaneHit][i] = b.w;
+			tile[kMPlanePx][i] = c.x; tile[kMPlanePy][i] = c.y; tile[kMPlanePz][i] = c.z;
+			tile[kMPlaneAr][i] = d.x; tile[kMPlaneAg][i] = d.y; tile[kMPlaneAb][i] = d.z;
+		}
+		__syncthreads();
+		if(windowed)
+		{
+			const int at = (threadIdx.y + R) * TW + threadIdx.x + R; // the centre in the tile; a tap is at + dy * TW + dx, inside the tile for |dx|, |dy| <= R
+			const RectifyCentre ctr = rectify_centre(Dn4{tile[kMPlaneNx][at], tile[kMPlaneNy][at], tile[kMPlaneNz][at], 1.0f}, Dn4{tile[kMPlanePx][at], tile[kMPlanePy][at], tile[kMPlanePz][at], 0.0f},
+			                                         Dn4{tile[kMPlaneAr][at], tile[kMPlaneAg][at], tile[kMPlaneAb][at], 0.0f}, origin.o);
+#pragma unroll
+			for(int dy = -R; dy <= R; ++dy)
+#pragma unroll
+				for(int dx = -R; dx <= R; ++dx)
+				{
+					const int q = at + dy * TW + dx;
+					moments_tap(ctr, s, tile[kMPlaneNx][q], tile[kMPlaneNy][q], tile[kMPlaneNz][q], tile[kMPlaneHit][q], tile[kMPlanePx][q], tile[kMPlanePy][q], tile[kMPlanePz][q], tile[kMPlaneAr][q],
+					            tile[kMPlaneAg][q], tile[kMPlaneAb][q], tile[kMPlaneY][q], tile[kMPlaneS][q]);
+				}
+		}
+	}
+	const MomentsVariance r = moments_finish(moments_own(noise_luminance(m.x, m.y, m.z), m.w), n_out, windowed, s);
+	if(staged) // (uniform over the workgroup)
+	{
+		const int n_spatial = __syncthreads_count(inside && r.spatial ? 1 : 0);
+		if(threadIdx.x == 0 && threadIdx.y == 0 && n_spatial > 0)
+			atomicAdd(spatial_count + ((blockIdx.y * gridDim.x + blockIdx.x) & (kMomentsCountSlots - 1)), (unsigned long long)n_spatial);
+	}
+	if(!inside) return;
+	out[p] = make_float4(m.x, m.y, m.z, r.v);
+	variance[p] = r.v;
+}
+inline LaunchShape variance_launch(int width, int height) { return image_launch(width, height); }
 
 constexpr int kSnapshotVecs = 5; // the first 80 bytes of a record: words 0..17, and the material id and the class word, which nothing here reads
 static_assert(kSnapshotVecs * 4 >= kTemporalTriWords, "the snapshot holds the words temporal_previous_point reads");

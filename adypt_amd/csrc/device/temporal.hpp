@@ -31,6 +31,7 @@ inline bool temporal_cap_valid(float cap) { return cap > 0.0f && cap <= kTempora
 }  // namespace adypt
 
 #include "rectify.hpp" // rectifying stale history against the current call's own neighbourhood: the window statistics and the clamp (uses the constants above)
+#include "moments.hpp" // a moments call (from 1 spp per pose): the fourth channel is a raw second moment S, the variance is made after the merge (uses both)
 
 namespace adypt {
 
@@ -84,7 +85,9 @@ struct TemporalOut { Dn4 x0; float n; float kept; };
 // surface stands still), temporal_merge_motion what temporal_previous_point made of the hit triangle as it was then.
 // rect.on (rectify.hpp): where the window of the pixel has at least kRectifyMinTaps taps, the history's colour is clamped to the window's mean within
 // gamma * sqrt(g) per channel and its length multiplied by f before the blend; a length that is then not positive takes no history.  hv stays.
-template <class Hist>
+// MOMENTS (moments.hpp): the fourth channel of c0 and of the history is the raw second moment S, blended like a colour — S_h = sum w S_q / sum w,
+// S = (n S0 + n_h S_h) / (n + n_h); a compile-time constant, so that the other instances are what they were.
+template <bool MOMENTS = false, class Hist>
 ADYPT_HOST_DEVICE TemporalOut temporal_merge_through(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, bool hit, float nx, float ny, float nz,
                                                      float px, float py, float pz, const Dn4 &ca, float n, float history_cap, const Rectify rect = Rectify{})
 {
@@ -120,12 +123,12 @@ ADYPT_HOST_DEVICE TemporalOut temporal_merge_through(const Hist &hist, bool have
 			const float w = (tx == 0 ? 1.0f - ux : ux) * (ty == 0 ? 1.0f - uy : uy);
 			sw = sw + w;
 			sr = sr + w * q0.x; sg = sg + w * q0.y; sb = sb + w * q0.z;
-			sv = sv + (w * w) * q0.w;
+			sv = sv + (MOMENTS ? w : w * w) * q0.w;
 			sn = sn + w * q2.w;
 		}
 	if(!(sw > kTemporalMinWeight)) return out;
 	float hr = sr / sw, hg = sg / sw, hb = sb / sw;
-	const float hv = sv / (sw * sw);
+	const float hv = MOMENTS ? sv / sw : sv / (sw * sw);
 	const float hq = sn / sw;
 	float nh = hq < history_cap ? hq : history_cap;
 	if(rect.on && rect.r0.w >= (float)kRectifyMinTaps)
@@ -136,7 +139,7 @@ ADYPT_HOST_DEVICE TemporalOut temporal_merge_through(const Hist &hist, bool have
 	}
 	const float den = n + nh;
 	out.x0.x = (n * c0.x + nh * hr) / den; out.x0.y = (n * c0.y + nh * hg) / den; out.x0.z = (n * c0.z + nh * hb) / den;
-	out.x0.w = ((n * n) * c0.w + (nh * nh) * hv) / (den * den);
+	out.x0.w = MOMENTS ? (n * c0.w + nh * hv) / den : ((n * n) * c0.w + (nh * nh) * hv) / (den * den);
 	out.n = den;
 	return out;
 }
@@ -144,11 +147,11 @@ ADYPT_HOST_DEVICE TemporalOut temporal_merge_through(const Hist &hist, bool have
 // The merge at pixel (px, py).  c0 = (D0.rgb, V0) of denoise_prepare, c1 = (N.xyz, hit), c2 = (P.xyz, .), ca = (A.rgb, .) of the current call, n the
 // sample count of the pixel's block.  `hist` answers h0(i), h1(i), h2(i), ha(i) for the row-major pixel index i of the history; have = false: there
 // is none.  A tap that does not count is skipped entirely (an accumulator keeps its word).
-template <class Hist>
+template <bool MOMENTS = false, class Hist>
 ADYPT_HOST_DEVICE TemporalOut temporal_merge(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, const Dn4 &c1, const Dn4 &c2, const Dn4 &ca,
                                              float n, float history_cap, const Rectify rect = Rectify{})
 {
-	return temporal_merge_through(hist, have, cam, width, height, c0, c1.w != 0.0f, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z, ca, n, history_cap, rect);
+	return temporal_merge_through<MOMENTS>(hist, have, cam, width, height, c0, c1.w != 0.0f, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z, ca, n, history_cap, rect);
 }
 
 // ---- following moved geometry ----
@@ -194,11 +197,11 @@ ADYPT_HOST_DEVICE TemporalPrevious temporal_previous_point(const float *prev, co
 
 // The motion form of the merge: through (P_prev, N_prev).  The call's own (D0, V0), and the X1 / X2 that become history on a commit, stay the current
 // pose's; the albedo test, the finiteness tests, the weights, the cap and the blend are temporal_merge's.
-template <class Hist>
+template <bool MOMENTS = false, class Hist>
 ADYPT_HOST_DEVICE TemporalOut temporal_merge_motion(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, const Dn4 &c1, const Dn4 &ca, float n,
                                                     float history_cap, const Dn4 &xp, const Dn4 &xn, const Rectify rect = Rectify{})
 {
-	return temporal_merge_through(hist, have && xn.w != 0.0f, cam, width, height, c0, c1.w != 0.0f, xn.x, xn.y, xn.z, xp.x, xp.y, xp.z, ca, n, history_cap, rect);
+	return temporal_merge_through<MOMENTS>(hist, have && xn.w != 0.0f, cam, width, height, c0, c1.w != 0.0f, xn.x, xn.y, xn.z, xp.x, xp.y, xp.z, ca, n, history_cap, rect);
 }
 
 }  // namespace adypt

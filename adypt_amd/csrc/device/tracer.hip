@@ -698,13 +698,14 @@ int ctx_adaptive_ready(adypt_ctx *c, const char *fn)
 int ctx_freeze_blocks(adypt_ctx *c, const int32_t *blocks, size_t n, int spp) { return freeze_blocks(c, blocks, n, spp); }
 
 // ---- what the denoiser (denoise.hip) needs of a context ----
-int ctx_denoise_ready(adypt_ctx *c, const char *fn)
+int ctx_denoise_ready(adypt_ctx *c, const char *fn, int min_spp)
 {
+	const std::string too_few = min_spp >= 2 ? ": needs at least 2 spp in every block (the variance of a pixel's mean is not defined below)" : ": needs at least 1 spp in every block";
 	TRY_CREATE(noise_ready(c, fn, 0));
 	if(c->view_type != 3) return fail(c, ADYPT_E_STATE, std::string(fn) + ": the image is not path-traced (the last frame was a primary-ray viewer's)");
 	for(size_t i = 0; i < c->ab.owned.size(); ++i)
-		if(c->ab.spp_of(i, c->spp) < 2) return fail(c, ADYPT_E_STATE, std::string(fn) + ": needs at least 2 spp in every block (the variance of a pixel's mean is not defined below)");
-	if(c->ab.owned.empty() && c->spp < 2) return fail(c, ADYPT_E_STATE, std::string(fn) + ": needs at least 2 spp in every block (the variance of a pixel's mean is not defined below)");
+		if(c->ab.spp_of(i, c->spp) < min_spp) return fail(c, ADYPT_E_STATE, std::string(fn) + too_few);
+	if(c->ab.owned.empty() && c->spp < min_spp) return fail(c, ADYPT_E_STATE, std::string(fn) + too_few);
 	return ADYPT_OK;
 }
 DenoiseInputs ctx_denoise_inputs(adypt_ctx *c)

@@ -396,7 +396,10 @@ namespace {
 
 // The kernels of the chain through mirrors and glass are compiled here with the others but have no entry: between two of their rounds stands the
 // context's own traversal, so they are held to their truth through the product (tests/test_gpu_denoise_specular.py), k_denoise_prepare_class with them.
-[[maybe_unused]] const void *const kKernelsWithoutEntry[] = {(const void *)k_chain_start, (const void *)k_chain_step, (const void *)k_denoise_prepare_class};
+// Likewise the kernels of a moments call (moments.hpp): tests/test_gpu_denoise_moments.py holds them to their truth through the product.
+[[maybe_unused]] const void *const kKernelsWithoutEntry[] = {(const void *)k_chain_start, (const void *)k_chain_step, (const void *)k_denoise_prepare_class,
+                                                             (const void *)k_denoise_prepare_moments, (const void *)k_temporal_merge_moments<false>,
+                                                             (const void *)k_temporal_merge_moments<true>, (const void *)k_moments_variance};
 
 constexpr uint32_t kUnwritten = 0x7fc0deadu; // every output is filled with this quiet NaN before the launch: a pixel no thread wrote keeps it
 constexpr int kMaxSide = 4096;

@@ -384,6 +384,33 @@ int adypt_denoise_temporal_rectified(adypt_ctx *ctx, const adypt_denoise_params 
 int adypt_read_denoise_rectify(adypt_ctx *ctx, float *kept);
 int adypt_get_denoise_rectify(adypt_ctx *ctx, adypt_denoise_rectify *out);
 
+/* ---- variance from temporal moments: a temporal call from 1 spp per pose -------------------------------------------------------------------------
+ * Every call above needs 2 spp in every block: V0 = m2 / (n (n - 1)).  A moments call carries, where the variance stands in the merged image and in
+ * the history, the per-sample raw second moment of the demodulated luminance, S0 = lum(D0)^2 + (m2 / n) / (lum(A) + 0.01)^2 (lum(D0)^2 at n = 1), and
+ * blends it over the history like a colour (the taps, tests, weights, cap and colour blend are adypt_denoise_temporal's to the bit; with follow_motion
+ * adypt_denoise_temporal_motion's).  The variance the levels see is made per pixel after the merge: own = max(S - lum(D)^2, 0); a miss pixel, and a hit
+ * pixel whose merged length n_out is at least 4, take own / n_out; a hit pixel with a shorter history takes, over the 7 x 7 window of the merged image,
+ * the taps on its surface (the rectified call's tests against the centre, and finite lum(D_q), S_q): max(mean S_q - (mean lum(D_q))^2, 0) / n_out where
+ * at least 4 taps count, own / n_out otherwise.  The definition is pinned bit for bit in csrc/device/moments.hpp and temporal.hpp; tests/moments_truth.py
+ * restates it in numpy.  A history says which kind of call wrote it: a moments call finds none in one a plain temporal (or rectified) call left, and
+ * the other way round; a committing call of either kind replaces it.  The snapshot follows adypt_denoise_temporal_motion's rule.
+ * Not covered: a rectified form (the clamp moves the colour and would leave S inconsistent with it) and followed guides (adypt_denoise_specular has no
+ * temporal form) — this call has no argument for either; one process per GPU (no variant, as for adypt_denoise).
+ * Memory: 4 B per image pixel (the variance read-out) + 512 B (the counters), allocated at the first moments call; the merged image and the history are the
+ * temporal call's own.  Several devices: on the first. */
+typedef struct adypt_denoise_moments {
+	int32_t have;                /* 1: a moments call has run (else the two below are 0) */
+	float variance_ms;           /* HIP-event time of its variance kernel alone (adypt_get_denoise_merge_ms covers the merge and it) */
+	int64_t pixels_spatial;      /* pixels that took the window estimate in it */
+	int64_t device_bytes;        /* the variance read-out and the counters as allocated */
+} adypt_denoise_moments;
+/* adypt_denoise_temporal (follow_motion 0) or adypt_denoise_temporal_motion (not 0) from at least 1 spp in every block; both pointers may be NULL (the
+ * defaults).  Refusals: theirs, with 1 spp where they say 2; a refused call changes nothing. */
+int adypt_denoise_temporal_moments(adypt_ctx *ctx, const adypt_denoise_params *params, const adypt_temporal_params *temporal, int follow_motion);
+/* W*H floats: the variance V the first level saw in the last moments call.  ADYPT_E_STATE before the first */
+int adypt_read_denoise_variance(adypt_ctx *ctx, float *v);
+int adypt_get_denoise_moments(adypt_ctx *ctx, adypt_denoise_moments *out);
+
 /* ---- mirrors and glass: guides of the first surface that is not a delta material ------------------------------------------------------------------
  * adypt_denoise guides a pixel by its primary hit.  On a perfect mirror (illum 3..5) or glass (illum 6, 7) that is the mirror's own plane, its own normal
  * and albedo 0, and the pixel carries the hit flag of the wall beside it: the levels pool across the silhouette and across everything the mirror
@@ -795,6 +822,10 @@ int adypt_multi_get_denoise_motion(adypt_multi *m, adypt_denoise_motion *out);
 int adypt_multi_denoise_temporal_rectified(adypt_multi *m, const adypt_denoise_params *params, const adypt_temporal_params *temporal, const adypt_rectify_params *rectify, int follow_motion);
 int adypt_multi_read_denoise_rectify(adypt_multi *m, float *kept);
 int adypt_multi_get_denoise_rectify(adypt_multi *m, adypt_denoise_rectify *out);
+/* adypt_denoise_temporal_moments ... for the whole image: merge and variance on the first device behind the upload; the one-device bits */
+int adypt_multi_denoise_temporal_moments(adypt_multi *m, const adypt_denoise_params *params, const adypt_temporal_params *temporal, int follow_motion);
+int adypt_multi_read_denoise_variance(adypt_multi *m, float *v);
+int adypt_multi_get_denoise_moments(adypt_multi *m, adypt_denoise_moments *out);
 /* adypt_denoise_specular ... for the whole image: every device follows the chains of its own blocks before the host collects the images; the result
  * is the one-device result bit for bit.  adypt_multi_get_denoise_specular: the counts and bytes summed over the devices, chain_ms the largest. */
 int adypt_multi_denoise_specular(adypt_multi *m, const adypt_denoise_params *params, const adypt_specular_params *specular);

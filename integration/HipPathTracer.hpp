@@ -422,6 +422,22 @@ public:
 		return false;
 	}
 
+	// DenoiseTemporal from 1 spp per pose (adypt_hip.h, adypt_denoise_temporal_moments): needs GetSPP() >= 1.  The history carries the second moment of
+	// the demodulated luminance, and the variance the filter sees is made after the merge — from the moments where the merged history is at least 4
+	// samples long, from a 7 x 7 window on the pixel's surface where it is shorter.  Such a call and DenoiseTemporal do not find each other's history.
+	// variance, where not null: W x H floats, the variance the first level saw.  No rectified form and none with followed guides.
+	bool DenoiseTemporalMoments(std::vector<float> *rgb, float historyCap = 64.0f, bool commit = true, bool followMotion = false, std::vector<float> *variance = nullptr,
+	                            const adypt_denoise_params *params = nullptr)
+	{
+		const adypt_temporal_params t = {historyCap, commit ? 1 : 0};
+		rgb->resize((size_t)m_width * m_height * 3);
+		if(variance) variance->resize((size_t)m_width * m_height);
+		if(adypt_multi_denoise_temporal_moments(m_gpus, params, &t, followMotion ? 1 : 0) == ADYPT_OK && adypt_multi_read_denoised(m_gpus, rgb->data()) == ADYPT_OK &&
+		   (!variance || adypt_multi_read_denoise_variance(m_gpus, variance->data()) == ADYPT_OK)) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
 	// The image through the denoiser with guides that follow perfect mirrors and glass (adypt_hip.h, adypt_denoise_specular): a pixel whose primary
 	// hit is a delta material is guided by the first surface its chain of up to `bounces` reflections / transmissions (1 .. 8) ends on, and pixels of
 	// different chain classes do not pool.  chain, where not null: W x H class codes (0 a primary miss, 1 a primary hit followed nowhere, 1 + L ended on a
