@@ -117,6 +117,11 @@ class DenoiseSpecular(Struct):
                 ("pixels_escaped", C.c_int64), ("pixels_truncated", C.c_int64), ("device_bytes", C.c_int64)]
 
 
+class DenoiseVirtual(Struct):
+    """adypt_denoise_virtual."""
+    _fields_ = [("have", C.c_int32), ("bounces", C.c_int32), ("pixels_followed", C.c_int64), ("pixels_with_history", C.c_int64), ("device_bytes", C.c_int64)]
+
+
 class BvhParams(C.Structure):
     _fields_ = [("max_spatial_depth", C.c_int32), ("triangle_sah", C.c_float), ("node_sah", C.c_float)]
 
@@ -267,6 +272,12 @@ _SIGS = {
     "adypt_multi_denoise_specular": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(SpecularParams)]),
     "adypt_multi_read_denoise_guides_specular": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adypt_multi_get_denoise_specular": (C.c_int, [C.c_void_p, C.POINTER(DenoiseSpecular)]),
+    "adypt_denoise_temporal_specular": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(SpecularParams)]),
+    "adypt_read_denoise_virtual": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adypt_get_denoise_virtual": (C.c_int, [C.c_void_p, C.POINTER(DenoiseVirtual)]),
+    "adypt_multi_denoise_temporal_specular": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.POINTER(SpecularParams)]),
+    "adypt_multi_read_denoise_virtual": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adypt_multi_get_denoise_virtual": (C.c_int, [C.c_void_p, C.POINTER(DenoiseVirtual)]),
     "adypt_multi_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams)]),
     "adypt_multi_read_denoised": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_read_denoise_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -751,7 +751,7 @@ class _Tracer:
     # ---- denoising (adypt_denoise, include/adypt_hip.h; the definition: csrc/device/denoise.hpp); several devices: of the whole image ----
     def Denoise(self, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 0.1, temporal: bool = False, history_cap: float = 64.0,
                 commit: bool = True, follow_motion: bool = False, rectify: bool = False, rectify_radius: int = 3, rectify_gamma: float = 1.0,
-                specular_bounces: int = 0, moments: bool = False) -> np.ndarray:
+                specular_bounces: int = 0, moments: bool = False, follow_specular: int = 0) -> np.ndarray:
         """H x W x 3 float32: the accumulated image through the variance- and primary-hit-guided a-trous filter.  Needs the noise statistics on and
         >= 2 spp in every block (moments: 1); the image, the statistics and the tracing state are left as they are.
         temporal (adypt_denoise_temporal; the definition: csrc/device/temporal.hpp): before the filter, what the last committing call left is
@@ -767,12 +767,24 @@ class _Tracer:
         sun).  rectify_radius in [1, 3], rectify_gamma a finite number >= 0.  Combines with follow_motion.
         specular_bounces (adypt_denoise_specular; the definition: csrc/device/guide_chain.hpp): 0 is the call above to the bit; K in [1, 8] guides a
         pixel whose primary hit is a perfect mirror or glass by the first surface its chain of up to K reflections / transmissions ends on, and
-        keeps pixels of different chain classes from pooling.  No temporal form: the merge reprojects the position guide through the camera.
+        keeps pixels of different chain classes from pooling.  Not together with temporal: its temporal form is follow_specular.
         moments (adypt_denoise_temporal_moments; needs temporal; the definition: csrc/device/moments.hpp): the call runs from 1 spp in every block.
         The history carries the second moment of the demodulated luminance instead of a variance, and the variance the filter sees is made after the
         merge: from the moments where the merged history is at least 4 samples long, from a 7 x 7 window on the pixel's surface where it is
         shorter.  A moments call and a plain temporal call do not find each other's history.  Combines with follow_motion; not with rectify (the
-        clamp would leave the moment inconsistent with the colour) and not with specular_bounces."""
+        clamp would leave the moment inconsistent with the colour) and not with specular_bounces.
+        follow_specular (adypt_denoise_temporal_specular; needs temporal; the definitions: guide_chain.hpp, temporal.hpp): 0 is off; K in [1, 8] is the
+        temporal call with the guides of specular_bounces=K, and a pixel whose chain ended on a surface finds its history through its virtual point —
+        the camera ray unfolded to the chain's full length, of a planar mirror the mirror image of what it shows — with every tap held against the
+        followed guides and the pixel's class.  Such a call finds only a history a call with the same K left, and the other temporal calls none in
+        its.  history_cap and commit as above; not with specular_bounces, follow_motion, rectify or moments."""
+        if follow_specular != 0:
+            if not temporal:
+                raise ValueError("Denoise: follow_specular needs temporal=True")
+            if not 1 <= follow_specular <= 8:
+                raise ValueError("Denoise: follow_specular must be 0 or in [1, 8]")
+            if specular_bounces or follow_motion or rectify or moments:
+                raise ValueError("Denoise: follow_specular does not combine with specular_bounces, follow_motion, rectify or moments")
         if moments and not temporal:
             raise ValueError("Denoise: moments=True needs temporal=True")
         if moments and rectify:
@@ -788,7 +800,10 @@ class _Tracer:
         if specular_bounces and temporal:
             raise ValueError("Denoise: specular_bounces has no temporal form (the merge reprojects the position guide through the camera)")
         prm = N.DenoiseParams(levels, sigma_l, sigma_z)
-        if specular_bounces:
+        if follow_specular:
+            tp, sp = N.TemporalParams(history_cap, 1 if commit else 0), N.SpecularParams(follow_specular)
+            self._call("denoise_temporal_specular", C.byref(prm), C.byref(tp), C.byref(sp))
+        elif specular_bounces:
             sp = N.SpecularParams(specular_bounces)
             self._call("denoise_specular", C.byref(prm), C.byref(sp))
         elif moments:
@@ -884,6 +899,22 @@ class _Tracer:
         pixels_followed, pixels_escaped, pixels_truncated, and device_bytes of what the chain keeps (several devices: sums, the slowest device's time)."""
         out = N.DenoiseSpecular()
         self._call("get_denoise_specular", C.byref(out))
+        return out.as_dict()
+
+    def ReadDenoiseVirtual(self) -> dict:
+        """Of the last Denoise(temporal=True, follow_specular=K): virtual_position (H x W x 3 float32: the virtual point of every pixel whose chain ended
+        on a surface, the position guide of every other) and distance (H x W float32: the unfolded length; 0 where the pixel is not followed or the
+        length is not a positive finite number)."""
+        p = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        dist = np.zeros((self.height, self.width), dtype=np.float32)
+        self._call("read_denoise_virtual", p.ctypes.data, dist.ctypes.data)
+        return {"virtual_position": p, "distance": dist}
+
+    def GetDenoiseVirtual(self) -> dict:
+        """have (0 / 1), bounces, pixels_followed (class >= 2) and pixels_with_history (of them, those that took history) of the last
+        Denoise(temporal=True, follow_specular=K), and device_bytes of what it keeps (several devices: summed)."""
+        out = N.DenoiseVirtual()
+        self._call("get_denoise_virtual", C.byref(out))
         return out.as_dict()
 
     def GetDenoiseTiming(self) -> dict:

@@ -361,6 +361,8 @@ static bool move_scene(Session &s)
 static int temporal_call(Session &s)
 {
 	const Options &o = s.opt;
+	const adypt_specular_params followed{o.follow_specular.value_or(0)};
+	if(o.follow_specular) return adypt_multi_denoise_temporal_specular(s.multi, &s.denoise_params, &s.temporal_params, &followed);
 	if(o.denoise_moments) return adypt_multi_denoise_temporal_moments(s.multi, &s.denoise_params, &s.temporal_params, o.follow_motion ? 1 : 0);
 	if(o.rectify) return adypt_multi_denoise_temporal_rectified(s.multi, &s.denoise_params, &s.temporal_params, &o.rectify_params, o.follow_motion ? 1 : 0);
 	return o.follow_motion ? adypt_multi_denoise_temporal_motion(s.multi, &s.denoise_params, &s.temporal_params) : adypt_multi_denoise_temporal(s.multi, &s.denoise_params, &s.temporal_params);
@@ -575,6 +577,12 @@ static bool report_temporal(Session &s)
 		if(adypt_multi_get_denoise_moments(s.multi, &info) != ADYPT_OK || adypt_multi_read_denoise_variance(s.multi, variance.data()) != ADYPT_OK) return tracer_failed(s.multi, "\n");
 		printf(", spatial variance on %lld pixels", (long long)info.pixels_spatial);
 	}
+	if(o.follow_specular)
+	{
+		adypt_denoise_virtual info;
+		if(adypt_multi_get_denoise_virtual(s.multi, &info) != ADYPT_OK) return tracer_failed(s.multi, "\n");
+		printf(", followed %lld pixels, %lld with history", (long long)info.pixels_followed, (long long)info.pixels_with_history);
+	}
 	printf("\n");
 	if(!o.rectify_out.empty() && !save_grey(s, o.rectify_out, kept, "kept history shares")) return false;
 	if(!o.variance_out.empty() && !save_grey(s, o.variance_out, variance, "variance")) return false;
@@ -614,7 +622,7 @@ static bool save_guides(Session &s)
 	if(prefix.empty()) return true;
 	std::vector<float> g[3];
 	for(auto &v : g) v.assign((size_t)s.cfg.width * s.cfg.height * 3, 0.0f);
-	const std::optional<int> &bounces = s.opt.denoise_specular; // (the followed guides, and the class codes beside them)
+	const std::optional<int> &bounces = s.opt.denoise_specular ? s.opt.denoise_specular : s.opt.follow_specular; // (the followed guides, and the class codes beside them)
 	std::vector<int8_t> chain(bounces ? (size_t)s.cfg.width * s.cfg.height : 0, 0);
 	const int r = bounces ? adypt_multi_read_denoise_guides_specular(s.multi, *bounces, g[0].data(), g[1].data(), g[2].data(), chain.data())
 	                      : adypt_multi_read_denoise_guides(s.multi, g[0].data(), g[1].data(), g[2].data(), nullptr);

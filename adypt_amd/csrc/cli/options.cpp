@@ -69,6 +69,10 @@
 //   --denoise-specular K: with --denoise only, and with none of the temporal options (else exit 2): the guides of a pixel whose primary hit is a perfect
 //              mirror or glass follow the reflection / transmission for up to K bounces, 1 .. 8, to the first surface that is neither
 //              (adypt_multi_denoise_specular).  One [PT]SPECULAR: line reports the followed, escaped and truncated pixels and the rays
+//   --follow-specular K: with a temporal --denoise call only (else exit 2): every temporal call, the --history-from poses included, is a followed one
+//              (adypt_multi_denoise_temporal_specular): the guides of --denoise-specular K, and a pixel whose chain ended on a surface finds its history
+//              through its virtual point.  Not with --denoise-specular, --follow-motion, --rectify or --denoise-moments (exit 2).  The [PT]TEMPORAL: line
+//              then ends `, followed F pixels, H with history`; --guides-out writes the followed guides and PREFIX.chain.exr
 //   --guides-out PREFIX: the feature images of the primary hit as PREFIX.albedo.exr, PREFIX.normal.exr and PREFIX.position.exr; with
 //              --denoise-specular the followed guides, and the class code of every pixel as the grey PREFIX.chain.exr
 #include "options.hpp"
@@ -83,7 +87,7 @@ const char *const USAGE =
 	"scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] "
 	"[--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--denoise-specular K] "
 	"[--history-from other.config]... [--history-cap C] [--history-out len.exr] [--follow-motion] [--rectify [--rectify-gamma G] [--rectify-radius R] "
-	"[--rectify-out kept.exr]] [--denoise-moments [--variance-out v.exr]]] [--guides-out PREFIX] [--pose moved.obj [--by-vertices [--recompute-normals]] | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] "
+	"[--rectify-out kept.exr]] [--denoise-moments [--variance-out v.exr]] [--follow-specular K]] [--guides-out PREFIX] [--pose moved.obj [--by-vertices [--recompute-normals]] | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] "
 	"[--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]";
 
 // ---- values ----
@@ -166,6 +170,13 @@ static bool denoise_specular(Options &o, const char *v)
 	o.denoise_specular = (int)bounces;
 	return true;
 }
+static bool follow_specular(Options &o, const char *v)
+{
+	double bounces;
+	if(!bounded_number(v, INTEGER, 1, 8, "--follow-specular takes a number of bounces from 1 to 8", &bounces)) return false;
+	o.follow_specular = (int)bounces;
+	return true;
+}
 static bool rebuild_above(Options &o, const char *v)
 {
 	double ratio;
@@ -212,6 +223,7 @@ static const struct Spec { const char *name; bool value; Apply apply; } SPECS[] 
 	{"--rectify-gamma", true, rectify_gamma},
 	{"--denoise-moments", false, flag<&Options::denoise_moments>},
 	{"--variance-out", true, text<&Options::variance_out>},
+	{"--follow-specular", true, follow_specular},
 	{"--guides-out", true, text<&Options::guides_out>},
 	{"--pose", true, text<&Options::pose>},
 	{"--by-vertices", false, flag<&Options::by_vertices>},
@@ -288,6 +300,9 @@ int check_options(Options *opt)
 	if(o.rectify_detail && !o.rectify) return refuse("--rectify-gamma, --rectify-radius and --rectify-out need --rectify");
 	if(o.rectify && !o.temporal) return refuse("--rectify needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out");
 	if(o.follow_motion && !o.temporal) return refuse("--follow-motion needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out");
+	if(o.follow_specular && !(o.denoise && o.temporal)) return refuse("--follow-specular needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out");
+	if(o.follow_specular && (o.denoise_specular || o.follow_motion || o.rectify || o.denoise_moments))
+		return refuse("--follow-specular does not combine with --denoise-specular, --follow-motion, --rectify or --denoise-moments");
 
 	// with --rebuild-above or --build gpu, --rebuild-method names the policy's rebuild or the first build; else naming a method asks for the rebuild
 	o.rebuild = (o.bare_rebuild || o.rebuild_method) && !above && !o.build_on_gpu;

@@ -26,6 +26,7 @@ struct Options
 	std::string noise_out, spp_out, denoise_out, guides_out;
 	int denoise_levels = 5;
 	std::optional<int> denoise_specular; // --denoise-specular K: the guides follow mirrors and glass for K bounces
+	std::optional<int> follow_specular;  // --follow-specular K: every temporal call follows them, and merges a followed pixel by its virtual point
 	std::vector<std::string> history_from;
 	std::string history_out;
 	std::optional<double> history_cap; // 64 unless given

@@ -11,6 +11,11 @@
 //     k_temporal_merge  adypt_denoise_temporal only (the definition: temporal.hpp): the history the last committing call left — its merged pre-filter
 //                    (D, V), its guides, its effective sample counts, its camera — reprojected through P and merged into (D0, V0); the levels then
 //                    read the merged image.  A commit swaps the call's images with the history's: nothing is copied
+//     k_chain_start<true>, k_chain_step<true>, k_denoise_prepare_virtual, k_temporal_merge_virtual  adypt_denoise_temporal_specular only: the chain
+//                    also unfolds the camera ray to its full length and leaves the VIRTUAL POINT of every pixel that ends on a surface (block-major,
+//                    kVirtual); prepare brings it to the picture's coordinates, XV = (Pv.xyz, len), and the merge reprojects a followed pixel through it,
+//                    holding every tap against the followed guides and the pixel's class (temporal.hpp temporal_merge_virtual).  The order of such a
+//                    call: guide capture -> chain -> prepare -> merge -> levels, on the context's stream without a host sync until the end
 //     k_motion_gather  adypt_denoise_temporal_motion only, before the merge and inside its stage of the timer: per pixel the hit triangle's words 0..17
 //                    as the last committing motion call left them (the snapshot) against the record as it is now -> where the hit point and its normal
 //                    WERE then (temporal_previous_point), row-major XP = (P_prev.xyz, moved), XN = (N_prev.xyz, valid); k_temporal_merge<true> merges
@@ -56,19 +61,22 @@ namespace {
 // The block-major images of a set of blocks on one device, in the order the several-device path uploads them: the first kPixelImages hold one element
 // per local pixel, the last two one per block.  A further image is one more name here, its element type where that is not float4, its size in the table
 // and, if it is per pixel, its place in kFetchOrder.
-enum BlockImage { kAccum, kAlbedo, kNormal, kPosition, kHits, kMoments, kBlocks, kBlockSpp, kBlockImages, kPixelImages = kBlocks };
+// kVirtual — the virtual points of adypt_denoise_temporal_specular — is allocated, fetched and uploaded by such a call only (optional_images).
+enum BlockImage { kAccum, kAlbedo, kNormal, kPosition, kHits, kMoments, kVirtual, kBlocks, kBlockSpp, kBlockImages, kPixelImages = kBlocks };
 template <BlockImage K> struct ImageElement { using type = float4; };
 template <> struct ImageElement<kMoments> { using type = float2; };
 template <> struct ImageElement<kBlocks> { using type = int32_t; };
 template <> struct ImageElement<kBlockSpp> { using type = int32_t; };
 template <BlockImage K> constexpr size_t block_bytes() { return sizeof(typename ImageElement<K>::type) * (K < kPixelImages ? kBlockPixels : 1); }
 constexpr size_t kBlockImageBytes[] = {block_bytes<kAccum>(), block_bytes<kAlbedo>(), block_bytes<kNormal>(), block_bytes<kPosition>(),
-                                       block_bytes<kHits>(), block_bytes<kMoments>(), block_bytes<kBlocks>(), block_bytes<kBlockSpp>()}; // of one block
+                                       block_bytes<kHits>(), block_bytes<kMoments>(), block_bytes<kVirtual>(), block_bytes<kBlocks>(), block_bytes<kBlockSpp>()}; // of one block
 static_assert(sizeof(kBlockImageBytes) / sizeof(size_t) == kBlockImages, "every block-major image has its size");
 // the order in which the several-device path fetches a device's per-pixel images (the uploads go in the enum's order)
-constexpr BlockImage kFetchOrder[] = {kMoments, kAccum, kAlbedo, kNormal, kPosition, kHits};
+constexpr BlockImage kFetchOrder[] = {kMoments, kAccum, kAlbedo, kNormal, kPosition, kHits, kVirtual};
 static_assert(sizeof(kFetchOrder) / sizeof(BlockImage) == kPixelImages, "every per-pixel image is fetched");
 constexpr unsigned kContextImages = 1u << kAccum | 1u << kMoments | 1u << kBlocks; // the images a context keeps itself (DenoiseInputs)
+// the images a call goes without — neither allocated nor moved between devices; unfold: the call is adypt_denoise_temporal_specular
+constexpr unsigned optional_images(bool unfold) { return unfold ? 0u : 1u << kVirtual; }
 
 // where the images of a set of n_blocks blocks lie: what the kernels are launched with
 struct LocalImages {
@@ -105,6 +113,7 @@ struct History {
 	TemporalCamera camera;
 	bool present = false;
 	bool moments = false;            // which kind of call wrote it: H0.w is S (a moments call) or V.  A call finds only a history of its own kind
+	int followed = 0;                // ... and H1.w the class of a followed call with this many bounces (a truncated chain's class depends on them), or 0: the hit flag
 	Buffer<float4> snapshot;
 	int64_t snapshot_tris = 0;       // the triangles the snapshot holds; 0: the history has none (a context's scene never has 0: adypt_create, adypt_set_triangles)
 	StageTimer<2> snapshot_timer;    // the copy kernel of the last commit with a snapshot
@@ -118,7 +127,7 @@ struct History {
 	// drops it, so this only guards)
 	int64_t known_tris(int64_t n_tris) const { return present && snapshot_tris == n_tris ? snapshot_tris : 0; }
 	// whether a call of the kind given finds it
-	bool found_by(bool moments_call) const { return present && moments == moments_call; }
+	bool found_by(bool moments_call, int followed_bounces = 0) const { return present && moments == moments_call && followed == followed_bounces; }
 	// The snapshot of a committing motion call: the records as they are now, enqueued on `stream` behind the call's gather, which reads the old one.  The
 	// history has none from here until the caller has waited for the stream and commits with *n_tris: a failure in between leaves every pixel unmoved.
 	int enqueue_snapshot(adypt_ctx *c, hipStream_t stream, int64_t *n_tris)
@@ -136,9 +145,9 @@ struct History {
 	}
 	// A finished call's merged image, guides (X2.w = n_out) and camera become the history: swapped in, nothing is copied, and what the history held is
 	// overwritten by the call's next prepare.  snapshot_of: what enqueue_snapshot gave; 0: the call made none, and the history has none from here.
-	void commit(Buffer<float4> &merged, Buffer<float4> &x1, Buffer<float4> &x2, Buffer<float4> &xa, const CtxCamera &cam, int64_t snapshot_of, bool of_moments)
+	void commit(Buffer<float4> &merged, Buffer<float4> &x1, Buffer<float4> &x2, Buffer<float4> &xa, const CtxCamera &cam, int64_t snapshot_of, bool of_moments, int of_followed)
 	{
-		moments = of_moments;
+		moments = of_moments; followed = of_followed;
 		std::swap(merged, h0); std::swap(x1, h1); std::swap(x2, h2); std::swap(xa, ha);
 		camera = temporal_camera(cam.origin, cam.inv_proj, cam.inv_view);
 		snapshot_tris = snapshot_of;
@@ -193,6 +202,15 @@ struct Denoiser {
 	int chain_bounces = 0;
 	StageTimer<2> chain_timer;
 
+	// the temporal merge by the virtual point: XV, 16 B per image pixel, and the counters (1 KiB), allocated at the first adypt_denoise_temporal_specular
+	// (the block-major virtual points, 16 B per local pixel, are own / merged's kVirtual); the bounces and the counts of the last one
+	Buffer<float4> xv;
+	Buffer<unsigned long long> virtual_count;
+	bool xv_valid = false; // as length_valid, of such a call and XV
+	int virtual_bounces = 0;
+	int64_t virtual_followed = 0, virtual_with_history = 0;
+	unsigned long long virtual_readback[2 * kVirtualCountSlots] = {}; // (a member, as spatial_readback)
+
 	// variance from temporal moments (moments.hpp): the variance read-out, 4 B per image pixel, and the counters of the pixels that took the window estimate (512 B),
 	// allocated at the first moments call; the count and the variance kernel's time of the last one
 	Buffer<float> variance;
@@ -227,6 +245,7 @@ struct DenoiseCall {
 	std::string refused;            // why the arguments are refused; empty: they are not
 	int bounces = 0;                // adypt_denoise_specular: the guides follow mirrors and glass for this many bounces; 0: the primary hit's guides
 	bool moments = false;           // of Temporal and Motion: the variance comes from temporal luminance moments (moments.hpp); never rectified
+	bool unfold = false;            // adypt_denoise_temporal_specular: a Temporal call with followed guides (bounces > 0) that merges by the virtual point
 	int min_spp() const { return moments ? 1 : 2; } // the samples every block has to hold: V0 of denoise_prepare is not defined below 2, S0 is from 1
 };
 
@@ -258,8 +277,19 @@ DenoiseCall make_specular_call(const char *fn, const adypt_denoise_params *p, co
 	return call;
 }
 
+// adypt_denoise_temporal_specular's call: a Temporal call with followed guides; adypt_denoise_temporal's refusals, then adypt_denoise_specular's
+DenoiseCall make_virtual_call(const char *fn, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_specular_params *sp)
+{
+	DenoiseCall call = make_call(Mode::Temporal, fn, p, tp);
+	if(!call.refused.empty()) return call;
+	if(!sp) call.refused = std::string(fn) + ": specular is null";
+	else if(!chain_bounces_valid(sp->bounces)) call.refused = std::string(fn) + ": bounces must be in [1, " + std::to_string(kChainMaxBounces) + "]";
+	else { call.bounces = sp->bounces; call.unfold = true; }
+	return call;
+}
+
 // adypt_denoise_temporal_moments' call: a Temporal or Motion call whose fourth channel is S (it has no rectified form: the clamp would move the colour
-// and leave S inconsistent with it — and none with followed guides, as no temporal call has)
+// and leave S inconsistent with it — and none with followed guides: make_virtual_call has no moments form)
 DenoiseCall make_moments_call(const char *fn, const adypt_denoise_params *p, const adypt_temporal_params *tp, int follow_motion)
 {
 	DenoiseCall call = make_call(follow_motion ? Mode::Motion : Mode::Temporal, fn, p, tp);
@@ -291,12 +321,21 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 		CTX_TRY(c, at_least(d->variance, n)); CTX_TRY(c, at_least(d->spatial_count, kMomentsCountSlots));
 		d->variance_valid = false;
 	}
+	if(call.unfold)
+	{
+		CTX_TRY(c, at_least(d->xv, n)); CTX_TRY(c, at_least(d->virtual_count, 2 * kVirtualCountSlots));
+		d->xv_valid = false;
+	}
 	const int width = d->width, height = d->height, n_px = in.n_blocks * kBlockPixels;
 	const int blocks_x = (width + kBlockDim - 1) / kBlockDim;
 	const int32_t *blocks = in.as<kBlocks>();
 	const float4 *normal = in.as<kNormal>(), *position = in.as<kPosition>(), *hits = in.as<kHits>();
 	const LaunchShape prepare = prepare_launch(n_px);
 	// (followed guides: X1.w is the class the chain left in the .w of the primary-hit image)
+	if(call.unfold)
+		hipLaunchKernelGGL(k_denoise_prepare_virtual, prepare.grid, prepare.block, 0, stream, in.as<kAccum>(), in.as<kMoments>(), blocks, in.as<kBlockSpp>(), n_px, blocks_x, width, height,
+		                   in.as<kAlbedo>(), normal, position, hits, d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get(), in.as<kVirtual>(), d->xv.get());
+	else
 	hipLaunchKernelGGL(call.moments ? k_denoise_prepare_moments : call.bounces > 0 ? k_denoise_prepare_class : k_denoise_prepare, prepare.grid, prepare.block, 0, stream, in.as<kAccum>(), in.as<kMoments>(), blocks, in.as<kBlockSpp>(), n_px, blocks_x, width, height,
 	                   in.as<kAlbedo>(), normal, position, hits, d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get());
 	CTX_TRY(c, hipGetLastError());
@@ -327,7 +366,15 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 			CTX_TRY(c, d->window_timer.mark(1, stream));
 		}
 		const auto merge = call.rectify ? (with_motion ? k_temporal_merge<true, true> : k_temporal_merge<false, true>) : (with_motion ? k_temporal_merge<true, false> : k_temporal_merge<false, false>);
-		if(call.moments)
+		if(call.unfold)
+		{
+			CTX_TRY(c, hipMemsetAsync(d->virtual_count.get(), 0, sizeof(d->virtual_readback), stream));
+			hipLaunchKernelGGL(k_temporal_merge_virtual, merge_shape.grid, merge_shape.block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, d->x2.get(), (const float4 *)d->xa, (const float4 *)d->xv,
+			                   (const float4 *)h.h0, (const float4 *)h.h1, (const float4 *)h.h2, (const float4 *)h.ha, d->xm.get(), d->length.get(), width, height,
+			                   h.found_by(false, call.bounces) ? 1 : 0, h.camera, call.history_cap, d->virtual_count.get());
+			CTX_TRY(c, hipMemcpyAsync(d->virtual_readback, d->virtual_count.get(), sizeof(d->virtual_readback), hipMemcpyDeviceToHost, stream));
+		}
+		else if(call.moments)
 		{
 			hipLaunchKernelGGL(with_motion ? k_temporal_merge_moments<true> : k_temporal_merge_moments<false>, merge_shape.grid, merge_shape.block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1,
 			                   d->x2.get(), (const float4 *)d->xa, (const float4 *)h.h0, (const float4 *)h.h1, (const float4 *)h.h2, (const float4 *)h.ha, d->xm.get(), d->length.get(), width, height,
@@ -379,7 +426,13 @@ int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages 
 		d->pixels_spatial = 0;
 		for(const unsigned long long n_slot : d->spatial_readback) d->pixels_spatial += (int64_t)n_slot;
 	}
-	if(call.commit) h.commit(d->xm, d->x1, d->x2, d->xa, cam, snapshot_of, call.moments);
+	if(call.unfold)
+	{
+		d->xv_valid = true; d->virtual_bounces = call.bounces;
+		d->virtual_followed = d->virtual_with_history = 0;
+		for(int k = 0; k < kVirtualCountSlots; ++k) { d->virtual_followed += (int64_t)d->virtual_readback[2 * k]; d->virtual_with_history += (int64_t)d->virtual_readback[2 * k + 1]; }
+	}
+	if(call.commit) h.commit(d->xm, d->x1, d->x2, d->xa, cam, snapshot_of, call.moments, call.unfold ? call.bounces : 0);
 	return ADYPT_OK;
 }
 
@@ -399,11 +452,11 @@ int read_stages(const Denoiser *d, float *ms, int capacity, float *merge_ms)
 
 // the context's own set, for `in` = ctx_denoise_inputs(c): the kContextImages are the context's (moments null while it keeps no noise statistics, which
 // only the guide read-out goes without), the guides and the sample counts the denoiser's
-int own_images(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, LocalImages *v)
+int own_images(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, LocalImages *v, bool unfold = false)
 {
 	*v = LocalImages{{}, in.n_blocks};
 	v->image[kAccum] = in.accum; v->image[kMoments] = in.moments; v->image[kBlocks] = in.blocks;
-	return d->own.fill(c, v, kContextImages);
+	return d->own.fill(c, v, kContextImages | optional_images(unfold));
 }
 
 // The chain through mirrors and glass over the context's own blocks (guide_chain.hpp), enqueued behind the guide capture on the context's stream
@@ -411,7 +464,8 @@ int own_images(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, LocalImages *
 // other queue.  Every round is enqueued whether it has rays or not: an empty round measures 0.05 ms (two launches that read eight counters), and
 // stopping at the first one would need a count read back — a host sync in a call that has none until its end (that form is not built).
 // The queues have been asked for (ctx_ray_queues) before the capture was enqueued.
-int enqueue_chain(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, int bounces, const CtxRayQueues &q)
+// unfold: the unfolding instances, which also leave the virtual points in the set's kVirtual (the same queues, segments and capacity check).
+int enqueue_chain(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, int bounces, const CtxRayQueues &q, bool unfold)
 {
 	const CtxInfo i = ctx_info(c);
 	const int n_px = in.n_blocks * kBlockPixels;
@@ -431,14 +485,16 @@ int enqueue_chain(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char
 	d->chain_bounces = bounces;
 	CTX_TRY(c, hipMemsetAsync(d->chain_counts.get(), 0, sizeof(ChainCounts), i.stream));
 	CTX_TRY(c, d->chain_timer.mark(0, i.stream));
-	hipLaunchKernelGGL(k_chain_start, start.grid, start.block, 0, i.stream, sc, g, in.blocks, n_px, blocks_x, i.width, i.height, origin, bounces, d->chain_state.get(), queue(0, 0), d->chain_counts.get());
+	hipLaunchKernelGGL(unfold ? k_chain_start<true> : k_chain_start<false>, start.grid, start.block, 0, i.stream, sc, g, in.blocks, n_px, blocks_x, i.width, i.height, origin, bounces, d->chain_state.get(), queue(0, 0),
+	                   d->chain_counts.get());
+	const ChainUnfold unfolded{unfold ? d->own.as<kVirtual>() : nullptr, {cam.origin[0], cam.origin[1], cam.origin[2]}};
 	CTX_TRY(c, hipGetLastError());
 	const LaunchShape step = chain_step_launch(q.segments, per_segment);
 	for(int r = 0; r < bounces; ++r)
 	{
 		CTX_STEP(ctx_trace_queue(c, r & 1, r));
-		hipLaunchKernelGGL(k_chain_step, step.grid, step.block, 0, i.stream, sc, g, queue(r & 1, r), (const float4 *)q.hit, n_px, bounces, q.tmin, d->chain_state.get(), queue((r & 1) ^ 1, r + 1),
-		                   d->chain_counts.get());
+		hipLaunchKernelGGL(unfold ? k_chain_step<true> : k_chain_step<false>, step.grid, step.block, 0, i.stream, sc, g, queue(r & 1, r), (const float4 *)q.hit, n_px, bounces, q.tmin, d->chain_state.get(),
+		                   queue((r & 1) ^ 1, r + 1), d->chain_counts.get(), unfolded);
 		CTX_TRY(c, hipGetLastError());
 	}
 	CTX_TRY(c, d->chain_timer.mark(1, i.stream));
@@ -447,13 +503,13 @@ int enqueue_chain(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char
 
 // ... and the context's guides into it, enqueued behind its frames (the sample counts are the caller's to upload); bounces > 0: followed through mirrors
 // and glass, the class of every pixel in the .w of the primary-hit image
-int capture_guides(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, LocalImages *v, int bounces = 0)
+int capture_guides(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, LocalImages *v, int bounces = 0, bool unfold = false)
 {
-	CTX_STEP(own_images(c, d, in, v));
+	CTX_STEP(own_images(c, d, in, v, unfold));
 	CtxRayQueues q{};
 	if(bounces > 0) CTX_STEP(ctx_ray_queues(c, fn, &q)); // (first: it may have to wait for frames started ahead)
 	CTX_STEP(ctx_capture_guides(c, fn, d->own.as<kAlbedo>(), d->own.as<kNormal>(), d->own.as<kPosition>(), d->own.as<kHits>()));
-	return bounces > 0 && in.n_blocks > 0 ? enqueue_chain(c, d, in, fn, bounces, q) : (int)ADYPT_OK;
+	return bounces > 0 && in.n_blocks > 0 ? enqueue_chain(c, d, in, fn, bounces, q, unfold) : (int)ADYPT_OK;
 }
 
 // `bytes` of a device array of a context on the host (the stream is drained when it returns)
@@ -554,6 +610,34 @@ int get_moments(adypt_ctx *c, const char *fn, adypt_denoise_moments *out)
 	return ADYPT_OK;
 }
 
+// XV of the last call by the virtual point: the virtual position (W x H x 3 floats) and the unfolded length (W x H floats; 0: the pixel is not followed,
+// or its length is not valid) of every pixel; either may be null
+int read_virtual(adypt_ctx *c, const char *fn, float *virtual_position, float *distance)
+{
+	const Denoiser *last = finished_denoiser(c);
+	std::vector<float4> xv(last && last->xv_valid ? last->pixels() : 0);
+	CTX_STEP(read_image(c, fn, ": no call by the virtual point has run yet (adypt_denoise_temporal_specular)", xv.data(), 1, [](Denoiser *d) { return d->xv_valid ? d->xv.get() : nullptr; }));
+	for(size_t k = 0; k < xv.size(); ++k)
+	{
+		if(virtual_position) { virtual_position[3 * k] = xv[k].x; virtual_position[3 * k + 1] = xv[k].y; virtual_position[3 * k + 2] = xv[k].z; }
+		if(distance) distance[k] = xv[k].w;
+	}
+	return ADYPT_OK;
+}
+
+int get_virtual(adypt_ctx *c, const char *fn, adypt_denoise_virtual *out)
+{
+	if(!out) return ctx_fail(c, ADYPT_E_INVALID, std::string(fn) + ": out is null");
+	*out = adypt_denoise_virtual{};
+	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
+	if(!d) return ADYPT_OK;
+	out->device_bytes = (int64_t)(d->own.image[kVirtual].bytes() + d->merged.image[kVirtual].bytes() + d->xv.bytes() + d->virtual_count.bytes());
+	if(!d->xv_valid) return ADYPT_OK;
+	out->have = 1; out->bounces = d->virtual_bounces;
+	out->pixels_followed = d->virtual_followed; out->pixels_with_history = d->virtual_with_history;
+	return ADYPT_OK;
+}
+
 int read_guides(adypt_ctx *c, const char *fn, int bounces, float *albedo, float *normal, float *position, uint8_t *hit, int8_t *chain); // (below, beside its entry points)
 
 // what the last chain of a context did: its counters are read here, behind whatever the context's stream still holds
@@ -599,7 +683,7 @@ int denoise_context(adypt_ctx *c, const DenoiseCall &call)
 	CTX_TRY(c, d->timer.mark(0, i.stream));
 	const DenoiseInputs in = ctx_denoise_inputs(c);
 	LocalImages local;
-	CTX_STEP(capture_guides(c, d, in, fn, &local, call.bounces));
+	CTX_STEP(capture_guides(c, d, in, fn, &local, call.bounces, call.unfold));
 	CTX_TRY(c, d->timer.mark(1, i.stream));
 	CTX_TRY(c, hipMemcpyAsync(d->own.as<kBlockSpp>(), in.block_spp.data(), in.block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
 	return run_filter(c, d, i.stream, local, call, ctx_camera(c));
@@ -675,6 +759,15 @@ int adypt_denoise_specular(adypt_ctx *c, const adypt_denoise_params *p, const ad
 
 int adypt_get_denoise_specular(adypt_ctx *c, adypt_denoise_specular_info *out) { return c ? get_specular(c, "adypt_get_denoise_specular", out) : ADYPT_E_INVALID; }
 
+int adypt_denoise_temporal_specular(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_specular_params *sp)
+{
+	return denoise_context(c, make_virtual_call("adypt_denoise_temporal_specular", p, tp, sp));
+}
+
+int adypt_read_denoise_virtual(adypt_ctx *c, float *virtual_position, float *distance) { return c ? read_virtual(c, "adypt_read_denoise_virtual", virtual_position, distance) : ADYPT_E_INVALID; }
+
+int adypt_get_denoise_virtual(adypt_ctx *c, adypt_denoise_virtual *out) { return c ? get_virtual(c, "adypt_get_denoise_virtual", out) : ADYPT_E_INVALID; }
+
 }  // extern "C"
 
 namespace {
@@ -746,13 +839,14 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 	const int min_spp = call.min_spp();
 	CTX_STEP(multi_each(m, [fn, min_spp](adypt_ctx *c) { return ctx_denoise_ready(c, fn, min_spp); }));
 	// every device captures the guides of its own blocks: all enqueued before the first is waited for
+	const bool unfold = call.unfold;
 	const int bounces = call.bounces; // (followed guides: every device follows the chains of its own blocks; the class comes along in the primary-hit image)
-	CTX_STEP(multi_each(m, [fn, bounces](adypt_ctx *c) {
+	CTX_STEP(multi_each(m, [fn, bounces, unfold](adypt_ctx *c) {
 		const CtxInfo i = ctx_info(c);
 		if(i.n_local_px == 0) return (int)ADYPT_OK;
 		if(hipSetDevice(i.device) != hipSuccess) return ctx_fail(c, ADYPT_E_HIP, std::string(fn) + ": hipSetDevice failed");
 		LocalImages own;
-		return capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), fn, &own, bounces);
+		return capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), fn, &own, bounces, unfold);
 	}));
 	// the local images of every device back to back in rank order, and their block lists and sample counts likewise (the counts from each context's
 	// own state in that order: multi.hip's merge is sorted by block index, which is not this order, and would launch k_noise_blocks for nothing)
@@ -760,7 +854,9 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 	size_t n_blocks = 0;
 	for(adypt_ctx *c : ctx) n_blocks += (size_t)ctx_info(c).n_local_px / kBlockPixels;
 	std::vector<uint8_t> host[kBlockImages];
-	for(int k = 0; k < kBlockImages; ++k) host[k].resize(n_blocks * kBlockImageBytes[k]);
+	const unsigned left_out = optional_images(unfold);
+	for(int k = 0; k < kBlockImages; ++k)
+		if(!(left_out >> k & 1)) host[k].resize(n_blocks * kBlockImageBytes[k]);
 	size_t at = 0; // the rank's first block in them
 	for(adypt_ctx *c : ctx)
 	{
@@ -769,9 +865,9 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 		if(hipSetDevice(i.device) != hipSuccess) return fail_ctx(c, ctx_fail(c, ADYPT_E_HIP, std::string(fn) + ": hipSetDevice failed"));
 		const DenoiseInputs in = ctx_denoise_inputs(c);
 		LocalImages own;
-		int r = own_images(c, denoiser_of(c), in, &own);
+		int r = own_images(c, denoiser_of(c), in, &own, unfold);
 		for(const BlockImage k : kFetchOrder)
-			if(r == ADYPT_OK) r = fetch(c, i, own.image[k], host[k].data() + at * kBlockImageBytes[k], (size_t)in.n_blocks * kBlockImageBytes[k]);
+			if(r == ADYPT_OK && !(left_out >> k & 1)) r = fetch(c, i, own.image[k], host[k].data() + at * kBlockImageBytes[k], (size_t)in.n_blocks * kBlockImageBytes[k]);
 		if(r != ADYPT_OK) return fail_ctx(c, r);
 		memcpy(host[kBlocks].data() + at * sizeof(int32_t), in.block_index.data(), in.block_index.size() * sizeof(int32_t));
 		memcpy(host[kBlockSpp].data() + at * sizeof(int32_t), in.block_spp.data(), in.block_spp.size() * sizeof(int32_t));
@@ -785,9 +881,10 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 		CTX_STEP(ensure_filter_images(c, d, ri));
 		d->timer.invalidate();
 		LocalImages all{{}, (int)n_blocks};
-		CTX_STEP(d->merged.fill(c, &all, 0)); // (it borrows none)
+		CTX_STEP(d->merged.fill(c, &all, left_out)); // (it borrows none)
 		CTX_TRY(c, d->timer.mark(0, ri.stream));
-		for(int k = 0; k < kBlockImages; ++k) CTX_TRY(c, hipMemcpyAsync(d->merged.image[k], host[k].data(), host[k].size(), hipMemcpyHostToDevice, ri.stream));
+		for(int k = 0; k < kBlockImages; ++k)
+			if(!(left_out >> k & 1)) CTX_TRY(c, hipMemcpyAsync(d->merged.image[k], host[k].data(), host[k].size(), hipMemcpyHostToDevice, ri.stream));
 		CTX_TRY(c, d->timer.mark(1, ri.stream));
 		return run_filter(c, d, ri.stream, all, call, ctx_camera(c)); // (adypt_multi_set_camera gives every context the same camera)
 	};
@@ -882,6 +979,33 @@ int adypt_multi_read_denoise_guides(adypt_multi *m, float *albedo, float *normal
 }
 
 int adypt_multi_denoise_specular(adypt_multi *m, const adypt_denoise_params *p, const adypt_specular_params *sp) { return multi_denoise(m, make_specular_call("adypt_multi_denoise_specular", p, sp)); }
+
+int adypt_multi_denoise_temporal_specular(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_specular_params *sp)
+{
+	return multi_denoise(m, make_virtual_call("adypt_multi_denoise_temporal_specular", p, tp, sp));
+}
+
+// XV and the counts live on the first device, where the merge runs; the bytes are summed over the devices (every device keeps its own blocks' virtual points)
+int adypt_multi_read_denoise_virtual(adypt_multi *m, float *virtual_position, float *distance)
+{
+	return on_root(m, [=](adypt_ctx *c) { return read_virtual(c, "adypt_multi_read_denoise_virtual", virtual_position, distance); });
+}
+
+int adypt_multi_get_denoise_virtual(adypt_multi *m, adypt_denoise_virtual *out)
+{
+	if(!out) return ADYPT_E_INVALID;
+	adypt_denoise_virtual sum{};
+	const int r = multi_each(m, [&sum](adypt_ctx *c) {
+		adypt_denoise_virtual one;
+		const int e = get_virtual(c, "adypt_multi_get_denoise_virtual", &one);
+		if(e != ADYPT_OK) return e;
+		sum.device_bytes += one.device_bytes;
+		if(one.have) { sum.have = 1; sum.bounces = one.bounces; sum.pixels_followed = one.pixels_followed; sum.pixels_with_history = one.pixels_with_history; }
+		return (int)ADYPT_OK;
+	});
+	if(r == ADYPT_OK) *out = sum;
+	return r;
+}
 
 int adypt_multi_read_denoise_guides_specular(adypt_multi *m, int32_t bounces, float *albedo, float *normal, float *position, int8_t *chain)
 {

@@ -63,6 +63,23 @@ __global__ __launch_bounds__(kPixelThreads) void k_denoise_prepare_moments(const
 {
 	denoise_prepare_pixel<false, true>(accum, moments, blocks, block_spp, n_px, blocks_x, width, height, g_albedo, g_normal, g_position, g_hits, x0, x1, x2, xa);
 }
+// k_denoise_prepare_class that also brings the virtual point to the picture's coordinates (adypt_denoise_temporal_specular): g_virtual is the block-major
+// image k_chain_step<true> wrote for the pixels whose chain ended on a surface, which are the pixels of class >= 2 and the only ones it is read at;
+// XV = (Pv.xyz, len) there and (P, 0) everywhere else — THE rule of who has a virtual point (guide_chain.hpp), stated here once.  16 B per pixel more
+// written, and 16 B more read at a followed pixel.
+__global__ __launch_bounds__(kPixelThreads) void k_denoise_prepare_virtual(const float4 *accum, const float2 *moments, const int32_t *blocks, const int32_t *block_spp, int n_px, int blocks_x,
+                                                                           int width, int height, const float4 *g_albedo, const float4 *g_normal, const float4 *g_position, const float4 *g_hits,
+                                                                           float4 *x0, float4 *x1, float4 *x2, float4 *xa, const float4 *g_virtual, float4 *xv)
+{
+	denoise_prepare_pixel<true>(accum, moments, blocks, block_spp, n_px, blocks_x, width, height, g_albedo, g_normal, g_position, g_hits, x0, x1, x2, xa);
+	const int L = blockIdx.x * blockDim.x + threadIdx.x;
+	if(L >= n_px) return;
+	int x, y;
+	block_pixel_xy(blocks[L >> 10], L & 1023, blocks_x, &x, &y);
+	if(x >= width || y >= height) return;
+	const float4 q = g_position[L];
+	xv[(size_t)y * width + x] = g_hits[L].w >= 2.0f ? g_virtual[L] : make_float4(q.x, q.y, q.z, 0.0f);
+}
 inline LaunchShape prepare_launch(int n_px) { return local_pixels_launch(n_px); }
 
 // ---- the chain through mirrors and glass (guide_chain.hpp) ----
@@ -115,11 +132,15 @@ __device__ __forceinline__ void chain_count(bool yes, unsigned long long *counte
 	if(yes && rank == 0u) atomicAdd(counter, (unsigned long long)__popcll(mask));
 }
 
-__device__ __forceinline__ void chain_store_state(float4 *state, int L, const ChainState &s)
+// (len: the unfolded length of the unfolding instances, which travels in the free word; the others leave it 0)
+__device__ __forceinline__ void chain_store_state(float4 *state, int L, const ChainState &s, float len = 0.0f)
 {
 	state[2 * (size_t)L] = make_float4(s.t.x, s.t.y, s.t.z, __int_as_float(s.length));
-	state[2 * (size_t)L + 1] = make_float4(s.d.x, s.d.y, s.d.z, 0.0f);
+	state[2 * (size_t)L + 1] = make_float4(s.d.x, s.d.y, s.d.z, len);
 }
+// what the unfolding instances are given beside the others' arguments: the block-major image of the virtual points, one float4 per local pixel, written
+// where a chain ends on a surface — (Pv.xyz, valid ? len : 0) — and nowhere else
+struct ChainUnfold { float4 *virt; float o[3]; }; // (o: the camera origin)
 __device__ __forceinline__ void chain_store_ray(const ChainQueue &q, uint32_t seg, uint32_t in_seg, const Ch3 &p, const Ch3 &d, float tmin, int L)
 {
 	if(in_seg >= q.seg_cap) return; // (the host sizes the launch so that a segment cannot overflow; never write outside one)
@@ -131,6 +152,9 @@ __device__ __forceinline__ void chain_store_ray(const ChainQueue &q, uint32_t se
 // One thread per local pixel of the owned block list, behind the guide capture.  Reads the primary hit (16 B) and, where it is a hit, the material
 // (48 B of its record, 16 B of the triangle's) and the normal and position guides (32 B); writes the class of a pixel that is not followed into the .w
 // of its hit (4 B), else the pixel's state (32 B) and a ray (32 B).  Workgroup b appends to segment b % segments: 256 rays at most each.
+// UNFOLD (adypt_denoise_temporal_specular's instance): the state also takes the length of the camera ray, chain_start_length — one square root more
+// per followed pixel.  The kernel itself is the template, with no body shared through a call: k_chain_start<false> is what k_chain_start was.
+template <bool UNFOLD>
 __global__ __launch_bounds__(kPixelThreads) void k_chain_start(ChainScene sc, ChainGuides g, const int32_t *__restrict__ blocks, int n_px, int blocks_x, int width, int height,
                                                                ChainOrigin origin, int bounces, float4 *__restrict__ state, ChainQueue out, ChainCounts *counts)
 {
@@ -160,7 +184,7 @@ __global__ __launch_bounds__(kPixelThreads) void k_chain_start(ChainScene sc, Ch
 	const uint32_t in_seg = chain_append(go, out.count + seg * out.seg_stride);
 	if(go)
 	{
-		chain_store_state(state, L, s);
+		chain_store_state(state, L, s, UNFOLD ? chain_start_length(p, origin.o) : 0.0f);
 		chain_store_ray(out, seg, in_seg, p, s.d, origin.tmin, L);
 	}
 	chain_count(go, &counts->followed);
@@ -172,14 +196,20 @@ inline LaunchShape chain_start_launch(int n_px) { return local_pixels_launch(n_p
 // Reads the ray's direction word and hit (32 B), the pixel's state (32 B) and at a hit 80 B of the triangle's record, 48 B of the material's and, on a
 // textured surface that ends the chain, 16 B of texture coordinates and 4 texels; either ends the pixel — albedo, normal, position (48 B) and the class
 // into the .w of its hit (4 B) — or writes the state back and appends the next ray to the same segment of the other queue (64 B).
+// UNFOLD (adypt_denoise_temporal_specular's instance): also reads the origin of the ray from the queue it consumes (16 B) and adds the ray's length to the state's
+// (chain_unfold); a pixel that ends on a surface reads the primary position guide, which it still finds in place before it overwrites it, and writes
+// its virtual point (chain_virtual_point; 16 B) — one square root and one 16-byte load more per step.  It appends to the queue as the other does.  The
+// kernel itself is the template; `unfold` stands last and k_chain_step<false> never looks at it: its code is what k_chain_step's was.
+template <bool UNFOLD>
 __global__ __launch_bounds__(kPixelThreads) void k_chain_step(ChainScene sc, ChainGuides g, ChainQueue in, const float4 *__restrict__ hit, int n_px, int bounces, float tmin,
-                                                              float4 *__restrict__ state, ChainQueue out, ChainCounts *counts)
+                                                              float4 *__restrict__ state, ChainQueue out, ChainCounts *counts, ChainUnfold unfold)
 {
 	const uint32_t seg = blockIdx.x % (uint32_t)in.segments, local = (blockIdx.x / (uint32_t)in.segments) * kPixelThreads + threadIdx.x;
 	const uint32_t n_in = min(in.count[seg * in.seg_stride], in.seg_cap);
 	bool go = false, escaped = false, truncated = false;
 	ChainState s{Ch3{1.0f, 1.0f, 1.0f}, Ch3{0.0f, 0.0f, 0.0f}, 0};
 	Ch3 p{0.0f, 0.0f, 0.0f};
+	float len = 0.0f;
 	int L = -1;
 	if(local < n_in)
 	{
@@ -208,12 +238,23 @@ __global__ __launch_bounds__(kPixelThreads) void k_chain_step(ChainScene sc, Cha
 			}
 			Ch3 n;
 			chain_hit_point(w, h.y, h.z, &p, &n);
+			if(UNFOLD)
+			{
+				const float4 ro = in.o[slot];
+				len = chain_unfold(s1.w, p, Ch3{ro.x, ro.y, ro.z});
+			}
 			const ChainMaterial m = chain_material(sc, tri, h.y, h.z, true);
 			go = chain_at_surface(s, m, n, p, bounces, &end) == kChainGoesOn;
 			truncated = !go && chain_is_delta(m.bad, m.illum);
 		}
 		if(!go)
 		{
+			if(UNFOLD && !escaped)
+			{
+				const float4 q0 = g.position[L]; // (the primary capture's: this thread is the first to overwrite it, below)
+				const ChainVirtual v = chain_virtual_point(Ch3{q0.x, q0.y, q0.z}, unfold.o, len);
+				unfold.virt[L] = make_float4(v.p.x, v.p.y, v.p.z, v.valid ? len : 0.0f);
+			}
 			g.albedo[L] = make_float4(end.albedo.x, end.albedo.y, end.albedo.z, 1.0f);
 			g.normal[L] = make_float4(end.normal.x, end.normal.y, end.normal.z, 1.0f);
 			g.position[L] = make_float4(end.position.x, end.position.y, end.position.z, 1.0f);
@@ -223,13 +264,14 @@ __global__ __launch_bounds__(kPixelThreads) void k_chain_step(ChainScene sc, Cha
 	const uint32_t in_seg = chain_append(go, out.count + seg * out.seg_stride);
 	if(go)
 	{
-		chain_store_state(state, L, s);
+		chain_store_state(state, L, s, len);
 		chain_store_ray(out, seg, in_seg, p, s.d, tmin, L);
 	}
 	chain_count(go, &counts->rays);
 	chain_count(escaped, &counts->escaped);
 	chain_count(truncated, &counts->truncated);
 }
+
 // rays_per_segment: the most rays a segment can hold in any round = 256 x the workgroups of k_chain_start that append to it
 inline LaunchShape chain_step_launch(int segments, uint32_t rays_per_segment) { return LaunchShape{dim3((unsigned)segments * ((rays_per_segment + kPixelThreads - 1) / kPixelThreads)), dim3(kPixelThreads)}; }
 
@@ -319,6 +361,34 @@ __global__ __launch_bounds__(kAtrousX * kAtrousY) void k_temporal_merge_moments(
                                                                                  TemporalCamera cam, float history_cap, const float4 *xp, const float4 *xn)
 {
 	temporal_merge_pixel<MOTION, false, true>(x0, x1, x2, xa, h0, h1, h2, ha, merged, length, width, height, have, cam, history_cap, xp, xn, nullptr, nullptr, nullptr, 0.0f);
+}
+// The merge by the virtual point (temporal.hpp temporal_merge_virtual): k_temporal_merge<false, false>'s workgroup, one pixel per thread, and its bytes with
+// XV beside the call's images (16 B more read: 180 B per pixel).  It counts the followed pixels (class >= 2) and those of them that took history
+// (n_out > n): one atomic per wave and counter as chain_count does, spread over kVirtualCountSlots pairs of counters by workgroup, which the host sums
+// (k_moments_variance tells what one address costs).  No thread leaves before the votes: every lane of a wave takes part in them.
+constexpr int kVirtualCountSlots = 64;
+__global__ __launch_bounds__(kAtrousX * kAtrousY) void k_temporal_merge_virtual(const float4 *x0, const float4 *x1, float4 *x2, const float4 *xa, const float4 *xv, const float4 *h0,
+                                                                                 const float4 *h1, const float4 *h2, const float4 *ha, float4 *merged, float *length, int width, int height,
+                                                                                 int have, TemporalCamera cam, float history_cap, unsigned long long *counts)
+{
+	const int x = blockIdx.x * kAtrousX + threadIdx.x, y = blockIdx.y * kAtrousY + threadIdx.y;
+	const bool inside = x < width && y < height;
+	bool followed = false, with_history = false;
+	if(inside)
+	{
+		const int p = y * width + x;
+		const Dn4 c1 = DeviceImages::load(x1, p), c2 = DeviceImages::load(x2, p);
+		const DeviceHistory hist{h0, h1, h2, ha};
+		const TemporalOut r = temporal_merge_virtual(hist, have != 0, cam, width, height, DeviceImages::load(x0, p), c1, c2, DeviceImages::load(xa, p), DeviceImages::load(xv, p), c2.w, history_cap);
+		merged[p] = make_float4(r.x0.x, r.x0.y, r.x0.z, r.x0.w);
+		x2[p] = make_float4(c2.x, c2.y, c2.z, r.n);
+		length[p] = r.n;
+		followed = c1.w >= 2.0f;
+		with_history = followed && r.n > c2.w;
+	}
+	unsigned long long *slot = counts + 2 * ((blockIdx.y * gridDim.x + blockIdx.x) & (kVirtualCountSlots - 1));
+	chain_count(followed, slot);
+	chain_count(with_history, slot + 1);
 }
 inline LaunchShape merge_launch(int width, int height) { return image_launch(width, height); }
 

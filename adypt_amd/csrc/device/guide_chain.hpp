@@ -151,4 +151,35 @@ ADYPT_HOST_DEVICE ChainEnd chain_escaped(const ChainState &s)
 	return ChainEnd{s.t, s.d, Ch3{0.0f, 0.0f, 0.0f}, -(s.length + 1)};
 }
 
+// ---- the virtual point (adypt_denoise_temporal_specular) ----
+// The camera ray unfolded to the chain's full length: of a planar mirror the mirror image of the surface the chain ended on, which stands still in the
+// world while the camera moves; the temporal merge reprojects a followed pixel through it (temporal.hpp temporal_merge_virtual).  Through curved mirrors
+// and refraction it is only approximate: the merge still holds every tap against the followed guides, so it then finds less history, never another surface.
+//     a chain that starts (chain_at_primary: kChainGoesOn)   len = chain_start_length(P0, O): the very `len` of chain_start_direction
+//     at every later hit                                     len <- chain_unfold(len, the hit point of chain_hit_point, the origin of the ray that found it)
+//     a chain that ends on a surface (class 1 + L, L >= 1, truncated chains too)   chain_virtual_point(P0, O, len), P0 the primary position guide
+// Who has none: class 1 pixels are their own virtual point (Pv = P, valid); classes <= 0 (a primary miss, an escaped chain) have no virtual point.
+
+ADYPT_HOST_DEVICE float chain_start_length(const Ch3 &p0, const float *origin)
+{
+	const Ch3 e{p0.x - origin[0], p0.y - origin[1], p0.z - origin[2]};
+	return sqrtf(chain_dot(e, e));
+}
+
+ADYPT_HOST_DEVICE float chain_unfold(float len, const Ch3 &hit, const Ch3 &ray_origin)
+{
+	const Ch3 e{hit.x - ray_origin.x, hit.y - ray_origin.y, hit.z - ray_origin.z};
+	return len + sqrtf(chain_dot(e, e));
+}
+
+// valid: len is a positive number up to kTemporalFiniteMax (an infinity and a NaN are refused); p is computed either way
+struct ChainVirtual { Ch3 p; bool valid; };
+
+ADYPT_HOST_DEVICE ChainVirtual chain_virtual_point(const Ch3 &p0, const float *origin, float len)
+{
+	Ch3 d0;
+	(void)chain_start_direction(p0, origin, &d0);
+	return ChainVirtual{Ch3{origin[0] + d0.x * len, origin[1] + d0.y * len, origin[2] + d0.z * len}, len > 0.0f && len <= kTemporalFiniteMax};
+}
+
 }  // namespace adypt

@@ -87,15 +87,19 @@ struct TemporalOut { Dn4 x0; float n; float kept; };
 // gamma * sqrt(g) per channel and its length multiplied by f before the blend; a length that is then not positive takes no history.  hv stays.
 // MOMENTS (moments.hpp): the fourth channel of c0 and of the history is the raw second moment S, blended like a colour — S_h = sum w S_q / sum w,
 // S = (n S0 + n_h S_h) / (n + n_h); a compile-time constant, so that the other instances are what they were.
-template <bool MOMENTS = false, class Hist>
+// VIRTUAL (temporal_merge_virtual, below): the point reprojected through the history's camera, and whose distance from it scales the plane tolerance, is
+// (vx, vy, vz) — the pixel's virtual point — while a tap's normal and plane are still held against (n, p), which are then the FOLLOWED guides; and a tap
+// counts only where its class is `cls`, the centre's.  A compile-time constant too: the other instances never look at the last four arguments.
+template <bool MOMENTS = false, bool VIRTUAL = false, class Hist>
 ADYPT_HOST_DEVICE TemporalOut temporal_merge_through(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, bool hit, float nx, float ny, float nz,
-                                                     float px, float py, float pz, const Dn4 &ca, float n, float history_cap, const Rectify rect = Rectify{})
+                                                     float px, float py, float pz, const Dn4 &ca, float n, float history_cap, const Rectify rect = Rectify{}, float cls = 0.0f,
+                                                     float vx = 0.0f, float vy = 0.0f, float vz = 0.0f)
 {
 	TemporalOut out;
 	out.x0 = c0; out.n = n; out.kept = 1.0f;
 	if(!have || !hit) return out;
 	float fx, fy, dist;
-	if(!temporal_reproject(cam, width, height, px, py, pz, &fx, &fy, &dist)) return out;
+	if(!temporal_reproject(cam, width, height, VIRTUAL ? vx : px, VIRTUAL ? vy : py, VIRTUAL ? vz : pz, &fx, &fy, &dist)) return out;
 	// floorf(fx) in [-1, width - 1]: one of the two columns at least lies inside (and a NaN is refused)
 	if(!(fx >= -1.0f && fx < (float)width && fy >= -1.0f && fy < (float)height)) return out;
 	const float bx = floorf(fx), by = floorf(fy);
@@ -110,7 +114,7 @@ ADYPT_HOST_DEVICE TemporalOut temporal_merge_through(const Hist &hist, bool have
 			if(qx < 0 || qy < 0 || qx >= width || qy >= height) continue;
 			const int q = qy * width + qx;
 			const Dn4 q1 = hist.h1(q);
-			if(!(q1.w != 0.0f)) continue;
+			if(VIRTUAL ? !(q1.w == cls) : !(q1.w != 0.0f)) continue;
 			if(!((nx * q1.x + ny * q1.y) + nz * q1.z >= kTemporalNormalMin)) continue;
 			const Dn4 q2 = hist.h2(q);
 			const float dx = q2.x - px, dy = q2.y - py, dz = q2.z - pz;
@@ -152,6 +156,27 @@ ADYPT_HOST_DEVICE TemporalOut temporal_merge(const Hist &hist, bool have, const 
                                              float n, float history_cap, const Rectify rect = Rectify{})
 {
 	return temporal_merge_through<MOMENTS>(hist, have, cam, width, height, c0, c1.w != 0.0f, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z, ca, n, history_cap, rect);
+}
+
+// ---- through mirrors and glass: the merge by the virtual point (adypt_denoise_temporal_specular) ----
+// The call's guides are the FOLLOWED ones of guide_chain.hpp: c1 = (N.xyz, class), c2 = (P.xyz, .), ca = (A.rgb, .) of the surface the pixel's chain
+// ended on, and xv = (Pv.xyz, len): the virtual point of a followed pixel (class >= 2) and the unfolded length it was made with, 0 where that length is
+// not valid (chain_virtual_point); of every other pixel xv is (P, 0) and is not looked at.  Who takes no history: a pixel with !(class >= 1) — a primary
+// miss, an escaped chain, a NaN — and a followed pixel whose virtual point is not valid.  A class 1 pixel is its own virtual point.  The point
+// reprojected is Pv and dist = |Pv - O_prev|; a tap counts where it lies inside the image, its class EQUALS the centre's, N . N_q >= 0.9,
+// |N . (P_q - P)| <= 0.02 dist, max |A_q - A| <= 0.1 — all on the followed guides — and its values are finite with n_q > 0; the weights, the least
+// weight, the cap, the blend and n_out are temporal_merge's.  For class 1 this is temporal_merge with the stricter class test: on a history whose
+// classes are all 0 or 1 the same bits.  No rectified, moments or motion form.
+template <class Hist>
+ADYPT_HOST_DEVICE TemporalOut temporal_merge_virtual(const Hist &hist, bool have, const TemporalCamera &cam, int width, int height, const Dn4 &c0, const Dn4 c1, const Dn4 c2, const Dn4 &ca,
+                                                     const Dn4 xv, float n, float history_cap)
+{
+	const float cls = c1.w;
+	const bool followed = cls >= 2.0f;
+	const bool takes = cls >= 1.0f && (!followed || (xv.w > 0.0f && xv.w <= kTemporalFiniteMax));
+	float vx = c2.x, vy = c2.y, vz = c2.z;
+	if(followed) { vx = xv.x; vy = xv.y; vz = xv.z; }
+	return temporal_merge_through<false, true>(hist, have, cam, width, height, c0, takes, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z, ca, n, history_cap, Rectify{}, cls, vx, vy, vz);
 }
 
 // ---- following moved geometry ----

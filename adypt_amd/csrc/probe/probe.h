@@ -62,6 +62,11 @@ int adypt_probe_rectify_window(int radius, const float *x0, const float *x1, con
 int adypt_probe_temporal_merge(int motion, int rectify, const float *x0, const float *x1, const float *x2, const float *xa, const float *h0, const float *h1, const float *h2, const float *ha,
                                int have, const float *origin, const float *inv_proj, const float *inv_view, float history_cap, const float *xp, const float *xn, const float *r0,
                                const float *r1, float gamma, int width, int height, float *merged, float *x2_out, float *length, float *kept);
+/* k_temporal_merge_virtual (the merge by the virtual point: temporal.hpp temporal_merge_virtual).  X1.w and H1.w hold classes, xv = (Pv.xyz, len).  Out as
+ * above, and counts: the two sums the host makes of the kernel's counters — pixels of class >= 2, and those of them that took history. */
+int adypt_probe_temporal_merge_virtual(const float *x0, const float *x1, const float *x2, const float *xa, const float *xv, const float *h0, const float *h1, const float *h2, const float *ha,
+                                       int have, const float *origin, const float *inv_proj, const float *inv_view, float history_cap, int width, int height, float *merged, float *x2_out,
+                                       float *length, uint64_t *counts);
 /* k_motion_gather.  snapshot: n_known elements of 5 float4; records: n_records >= n_known elements of tri_float4 (5..64) float4.  Both tables lie on
  * the device between 64 triangles of slack filled with 12345.0f, so that an index guard that fails shows as wrong words; a hit word outside
  * [-32, n_known + 32) is refused with -1. */

@@ -396,8 +396,10 @@ namespace {
 
 // The kernels of the chain through mirrors and glass are compiled here with the others but have no entry: between two of their rounds stands the
 // context's own traversal, so they are held to their truth through the product (tests/test_gpu_denoise_specular.py), k_denoise_prepare_class with them.
-// Likewise the kernels of a moments call (moments.hpp): tests/test_gpu_denoise_moments.py holds them to their truth through the product.
-[[maybe_unused]] const void *const kKernelsWithoutEntry[] = {(const void *)k_chain_start, (const void *)k_chain_step, (const void *)k_denoise_prepare_class,
+// Likewise the kernels of a moments call (moments.hpp): tests/test_gpu_denoise_moments.py holds them to their truth through the product; and the
+// unfolding chain with the prepare that goes with it (tests/test_gpu_denoise_virtual.py) — the merge by the virtual point has its entry below.
+[[maybe_unused]] const void *const kKernelsWithoutEntry[] = {(const void *)k_chain_start<false>, (const void *)k_chain_step<false>, (const void *)k_chain_start<true>,
+                                                             (const void *)k_chain_step<true>, (const void *)k_denoise_prepare_virtual, (const void *)k_denoise_prepare_class,
                                                              (const void *)k_denoise_prepare_moments, (const void *)k_temporal_merge_moments<false>,
                                                              (const void *)k_temporal_merge_moments<true>, (const void *)k_moments_variance};
 
@@ -501,6 +503,29 @@ int adypt_probe_temporal_merge(int motion, int rectify, const float *x0, const f
 	PROBE_TRY(launched());
 	PROBE_TRY(om.back(merged)); PROBE_TRY(d2.back(x2_out)); PROBE_TRY(ol.back(length));
 	if(rectify) PROBE_TRY(ok.back(kept));
+	return 0;
+}
+
+int adypt_probe_temporal_merge_virtual(const float *x0, const float *x1, const float *x2, const float *xa, const float *xv, const float *h0, const float *h1, const float *h2, const float *ha,
+                                       int have, const float *origin, const float *inv_proj, const float *inv_view, float history_cap, int width, int height, float *merged, float *x2_out,
+                                       float *length, uint64_t *counts)
+{
+	PROBE_REQUIRE(none_null(x0, x1, x2, xa, xv, h0, h1, h2, ha, origin, inv_proj, inv_view, merged, x2_out, length, counts) && picture_ok(width, height));
+	const size_t image = (size_t)width * height * 16;
+	Dev d0, d1, d2, da, dv, e0, e1, e2, ea, om, ol, oc;
+	PROBE_TRY(d0.in(x0, image)); PROBE_TRY(d1.in(x1, image)); PROBE_TRY(d2.in(x2, image)); PROBE_TRY(da.in(xa, image)); PROBE_TRY(dv.in(xv, image));
+	PROBE_TRY(e0.in(h0, image)); PROBE_TRY(e1.in(h1, image)); PROBE_TRY(e2.in(h2, image)); PROBE_TRY(ea.in(ha, image));
+	PROBE_TRY(om.filled(image, kUnwritten)); PROBE_TRY(ol.filled(image / 4, kUnwritten)); PROBE_TRY(oc.filled(2 * kVirtualCountSlots * sizeof(unsigned long long), 0u));
+	const TemporalCamera cam = temporal_camera(origin, inv_proj, inv_view);
+	const LaunchShape shape = merge_launch(width, height);
+	hipLaunchKernelGGL(k_temporal_merge_virtual, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), dv.as<float4>(), e0.as<float4>(), e1.as<float4>(),
+	                   e2.as<float4>(), ea.as<float4>(), om.as<float4>(), ol.as<float>(), width, height, have ? 1 : 0, cam, history_cap, oc.as<unsigned long long>());
+	PROBE_TRY(launched());
+	PROBE_TRY(om.back(merged)); PROBE_TRY(d2.back(x2_out)); PROBE_TRY(ol.back(length));
+	unsigned long long slots[2 * kVirtualCountSlots];
+	PROBE_TRY(oc.back(slots));
+	counts[0] = counts[1] = 0;
+	for(int k = 0; k < kVirtualCountSlots; ++k) { counts[0] += slots[2 * k]; counts[1] += slots[2 * k + 1]; }
 	return 0;
 }
 

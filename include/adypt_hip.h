@@ -394,8 +394,8 @@ int adypt_get_denoise_rectify(adypt_ctx *ctx, adypt_denoise_rectify *out);
  * at least 4 taps count, own / n_out otherwise.  The definition is pinned bit for bit in csrc/device/moments.hpp and temporal.hpp; tests/moments_truth.py
  * restates it in numpy.  A history says which kind of call wrote it: a moments call finds none in one a plain temporal (or rectified) call left, and
  * the other way round; a committing call of either kind replaces it.  The snapshot follows adypt_denoise_temporal_motion's rule.
- * Not covered: a rectified form (the clamp moves the colour and would leave S inconsistent with it) and followed guides (adypt_denoise_specular has no
- * temporal form) — this call has no argument for either; one process per GPU (no variant, as for adypt_denoise).
+ * Not covered: a rectified form (the clamp moves the colour and would leave S inconsistent with it) and followed guides (adypt_denoise_temporal_specular
+ * has no moments form) — this call has no argument for either; one process per GPU (no variant, as for adypt_denoise).
  * Memory: 4 B per image pixel (the variance read-out) + 512 B (the counters), allocated at the first moments call; the merged image and the history are the
  * temporal call's own.  Several devices: on the first. */
 typedef struct adypt_denoise_moments {
@@ -422,7 +422,7 @@ int adypt_get_denoise_moments(adypt_ctx *ctx, adypt_denoise_moments *out);
  * restates it in numpy.  The chain's rays run through the context's own traversal kernel on its ray queues, behind the guide capture, without a host
  * sync; towards frames started ahead the call behaves as adypt_trace_rays.  Nothing else of the context changes, as for adypt_denoise.
  * Memory: 32 B per local pixel (throughput, direction, length), allocated at the first such call.  Several devices: every device follows the chains of its
- * own blocks; the class travels in the .w of the primary-hit image.  No temporal form: the merge reprojects the position guide through the camera. */
+ * own blocks; the class travels in the .w of the primary-hit image.  Its temporal form is adypt_denoise_temporal_specular, below. */
 typedef struct adypt_specular_params {
 	int32_t bounces;             /* in [1, 8] */
 } adypt_specular_params;
@@ -442,6 +442,40 @@ int adypt_denoise_specular(adypt_ctx *ctx, const adypt_denoise_params *params, c
 /* adypt_read_denoise_guides with the chain followed for `bounces` bounces; chain (may be NULL): W*H class codes */
 int adypt_read_denoise_guides_specular(adypt_ctx *ctx, int32_t bounces, float *albedo, float *normal, float *position, int8_t *chain);
 int adypt_get_denoise_specular(adypt_ctx *ctx, adypt_denoise_specular_info *out);
+
+/* ---- mirrors and glass over time: the temporal merge by the virtual point -------------------------------------------------------------------------
+ * adypt_denoise_temporal reprojects a pixel through its position guide.  For a pixel seen in a mirror that is the mirror's surface, which under a moving
+ * camera shows another part of the reflection; and the followed position of adypt_denoise_specular is not where the camera sees the pixel.
+ * adypt_denoise_temporal_specular follows the chains as adypt_denoise_specular does and, while it does, unfolds the camera ray to the chain's full
+ * length: len = |P0 - O| + the length of every traced ray that hit.  A pixel whose chain ends on a surface (class >= 2, cut chains too) is reprojected
+ * through its VIRTUAL POINT Pv = O + d0 len (d0 the direction of the camera ray) — of a planar mirror the mirror image of the surface the chain ended on,
+ * which stands still while the camera moves.  A class 1 pixel is its own virtual point; a primary miss and an escaped chain take no history, nor does a
+ * pixel whose len is not a positive finite number.  A tap of the history counts where its class EQUALS the pixel's and the FOLLOWED normal, position and
+ * albedo pass adypt_denoise_temporal's tests, the plane tolerance being 0.02 |Pv - O_prev|; weights, cap, blend and n_out are that call's.  The levels
+ * are adypt_denoise_specular's.  The definition is pinned bit for bit in csrc/device/guide_chain.hpp and temporal.hpp; tests/virtual_truth.py restates it.
+ * History: a commit leaves the merged pre-filter (D, V), the followed guides with the class, n_out and the camera — no virtual point — and the mark
+ * "followed, K bounces".  Such a call finds only a history of its own K (a cut chain's class depends on K); adypt_denoise_temporal and its motion,
+ * rectified and moments forms find none in it, nor it in theirs.  A committing call of any kind replaces the history; this one drops the motion snapshot.
+ * Not covered: follow_motion, a rectified and a moments form (this call has no argument for them); glossy lobes (illum 2 ends the chain); glass split
+ * into a reflected and a transmitted guide; one process per GPU.  Curved mirrors and refraction get an approximate virtual point: the tests against the
+ * followed guides then find less history, never another surface.
+ * Memory: 16 B per local pixel (the block-major virtual points) + 16 B per image pixel (XV) + 1 KiB (the counters), allocated at the first such call, beside
+ * adypt_denoise_temporal's and adypt_denoise_specular's.  Several devices: every device follows the chains of its own blocks; merge and history on the first. */
+typedef struct adypt_denoise_virtual {
+	int32_t have;                /* 1: adypt_denoise_temporal_specular has run to its end (else all below but device_bytes are 0) */
+	int32_t bounces;             /* of the last such call */
+	int64_t pixels_followed;     /* pixels of class >= 2 in it: their chain ended on a surface */
+	int64_t pixels_with_history; /* ... of them, those that took history (n_out > n) */
+	int64_t device_bytes;        /* the virtual points, XV and the counters as allocated */
+} adypt_denoise_virtual;
+/* params and temporal may be NULL (the defaults), specular may not.  Refusals: adypt_denoise_temporal's, then adypt_denoise_specular's; a refused call
+ * changes nothing.  The result: adypt_read_denoised; the lengths: adypt_read_denoise_history; the merge's time: adypt_get_denoise_merge_ms; the chain
+ * stage: adypt_get_denoise_specular; adypt_denoise_history_reset drops the history as ever. */
+int adypt_denoise_temporal_specular(adypt_ctx *ctx, const adypt_denoise_params *params, const adypt_temporal_params *temporal, const adypt_specular_params *specular);
+/* of the last such call: W*H*3 floats, the virtual point of every followed pixel (the position guide of every other), and W*H floats, the unfolded
+ * length (0: not followed, or not valid); either may be NULL.  ADYPT_E_STATE before the first */
+int adypt_read_denoise_virtual(adypt_ctx *ctx, float *virtual_position, float *distance);
+int adypt_get_denoise_virtual(adypt_ctx *ctx, adypt_denoise_virtual *out);
 
 /* ---- moving geometry: new vertex positions without a new BVH and a new context ----------------------------------------------------------------
  * The tree's topology stays valid when vertices move; what goes stale are the boxes, the Woop data and the triangle records.  adypt_update_triangles
@@ -831,6 +865,11 @@ int adypt_multi_get_denoise_moments(adypt_multi *m, adypt_denoise_moments *out);
 int adypt_multi_denoise_specular(adypt_multi *m, const adypt_denoise_params *params, const adypt_specular_params *specular);
 int adypt_multi_read_denoise_guides_specular(adypt_multi *m, int32_t bounces, float *albedo, float *normal, float *position, int8_t *chain);
 int adypt_multi_get_denoise_specular(adypt_multi *m, adypt_denoise_specular_info *out);
+/* adypt_denoise_temporal_specular ... for the whole image: every device follows and unfolds the chains of its own blocks, the virtual points travel with
+ * the guides to the first device, where the merge runs and the history lives; the one-device bits.  device_bytes: summed over the devices */
+int adypt_multi_denoise_temporal_specular(adypt_multi *m, const adypt_denoise_params *params, const adypt_temporal_params *temporal, const adypt_specular_params *specular);
+int adypt_multi_read_denoise_virtual(adypt_multi *m, float *virtual_position, float *distance);
+int adypt_multi_get_denoise_virtual(adypt_multi *m, adypt_denoise_virtual *out);
 /* adypt_update_triangles on every device: the scene is replicated and every device refits its own copy; no collective.  (One process per GPU: every
  * rank calls adypt_update_triangles on its own context.) */
 int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals);

@@ -441,7 +441,7 @@ public:
 	// The image through the denoiser with guides that follow perfect mirrors and glass (adypt_hip.h, adypt_denoise_specular): a pixel whose primary
 	// hit is a delta material is guided by the first surface its chain of up to `bounces` reflections / transmissions (1 .. 8) ends on, and pixels of
 	// different chain classes do not pool.  chain, where not null: W x H class codes (0 a primary miss, 1 a primary hit followed nowhere, 1 + L ended on a
-	// surface after L bounces, -(L + 1) left the scene).  No temporal form.
+	// surface after L bounces, -(L + 1) left the scene).  Over time: DenoiseTemporalSpecular.
 	bool DenoiseSpecular(std::vector<float> *rgb, int bounces = 4, std::vector<int8_t> *chain = nullptr, const adypt_denoise_params *params = nullptr)
 	{
 		const adypt_specular_params s = {bounces};
@@ -449,6 +449,24 @@ public:
 		if(chain) chain->resize((size_t)m_width * m_height);
 		if(adypt_multi_denoise_specular(m_gpus, params, &s) == ADYPT_OK && adypt_multi_read_denoised(m_gpus, rgb->data()) == ADYPT_OK &&
 		   (!chain || adypt_multi_read_denoise_guides_specular(m_gpus, bounces, nullptr, nullptr, nullptr, chain->data()) == ADYPT_OK)) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
+	// DenoiseTemporal through mirrors and glass (adypt_hip.h, adypt_denoise_temporal_specular): the guides of DenoiseSpecular(bounces), and a pixel whose
+	// chain ended on a surface finds its history through its virtual point — the camera ray unfolded to the chain's full length, of a planar mirror the
+	// mirror image of what it shows — with every tap held against the followed guides and the pixel's class.  Such a call finds only a history a call
+	// with the same bounces left, and the other temporal calls none in its.  virtualPosition, where not null: W x H x 3 floats, the virtual point of every
+	// followed pixel (the position guide of every other).  No followMotion, rectified or moments form.
+	bool DenoiseTemporalSpecular(std::vector<float> *rgb, int bounces = 4, float historyCap = 64.0f, bool commit = true, std::vector<float> *virtualPosition = nullptr,
+	                             const adypt_denoise_params *params = nullptr)
+	{
+		const adypt_temporal_params t = {historyCap, commit ? 1 : 0};
+		const adypt_specular_params s = {bounces};
+		rgb->resize((size_t)m_width * m_height * 3);
+		if(virtualPosition) virtualPosition->resize((size_t)m_width * m_height * 3);
+		if(adypt_multi_denoise_temporal_specular(m_gpus, params, &t, &s) == ADYPT_OK && adypt_multi_read_denoised(m_gpus, rgb->data()) == ADYPT_OK &&
+		   (!virtualPosition || adypt_multi_read_denoise_virtual(m_gpus, virtualPosition->data(), nullptr) == ADYPT_OK)) return true;
 		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
 		return false;
 	}

@@ -37,7 +37,7 @@ def kernel_resources():
     out = []
     for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.sgpr_count:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", text):
         name, scratch, sgpr, vgpr = m.groups()
-        short = re.search(r"(k_chain_start|k_chain_step|k_denoise_prepare_class|k_denoise_prepare)E", name)
+        short = re.search(r"(k_chain_start|k_chain_step|k_denoise_prepare_class|k_denoise_prepare)(?:ILb0E)?E", name)  # (the chain's kernels: the instances that do not unfold)
         if short:
             out.append((short.group(1), int(vgpr), int(sgpr), int(scratch)))
     return sorted(out)
