@@ -67,6 +67,22 @@ int adypt_probe_temporal_merge(int motion, int rectify, const float *x0, const f
 int adypt_probe_temporal_merge_virtual(const float *x0, const float *x1, const float *x2, const float *xa, const float *xv, const float *h0, const float *h1, const float *h2, const float *ha,
                                        int have, const float *origin, const float *inv_proj, const float *inv_view, float history_cap, int width, int height, float *merged, float *x2_out,
                                        float *length, uint64_t *counts);
+/* k_denoise_prepare_class, _moments and _virtual: adypt_probe_denoise_prepare's arguments behind which of the three.  hits.w holds the class word for the
+ * class and virtual instances; g_virtual (block-major) and xv (an image, pre-filled like the others) are looked at by the virtual instance only and
+ * may be null for the other two. */
+enum { ADYPT_PROBE_PREPARE_CLASS = 0, ADYPT_PROBE_PREPARE_MOMENTS = 1, ADYPT_PROBE_PREPARE_VIRTUAL = 2 };
+int adypt_probe_denoise_prepare_instance(int instance, const float *accum, const float *moments, const float *albedo, const float *normal, const float *position, const float *hits,
+                                         const int32_t *blocks, const int32_t *block_spp, int n_blocks, int width, int height, float *x0, float *x1, float *x2, float *xa,
+                                         const float *g_virtual, float *xv);
+/* k_temporal_merge_moments<motion != 0>: adypt_probe_temporal_merge's arguments without the rectified call's; the fourth channel of X0, H0 and merged
+ * is the raw second moment S. */
+int adypt_probe_temporal_merge_moments(int motion, const float *x0, const float *x1, const float *x2, const float *xa, const float *h0, const float *h1, const float *h2, const float *ha,
+                                       int have, const float *origin, const float *inv_proj, const float *inv_view, float history_cap, const float *xp, const float *xn, int width,
+                                       int height, float *merged, float *x2_out, float *length);
+/* k_moments_variance on the merged images (merged = (D.rgb, S), X2.w = n_out); origin: the current camera's, 3 floats.  Out: `out` = (D.rgb, V), the
+ * variance read-out (one float per pixel), and the sum the host makes of the kernel's 64 count slots (zeroed before the launch). */
+int adypt_probe_moments_variance(const float *merged, const float *x1, const float *x2, const float *xa, int width, int height, const float *origin, float *out, float *variance,
+                                 uint64_t *spatial_count);
 /* k_motion_gather.  snapshot: n_known elements of 5 float4; records: n_records >= n_known elements of tri_float4 (5..64) float4.  Both tables lie on
  * the device between 64 triangles of slack filled with 12345.0f, so that an index guard that fails shows as wrong words; a hit word outside
  * [-32, n_known + 32) is refused with -1. */
@@ -74,6 +90,29 @@ int adypt_probe_motion_gather(const float *hits, const float *normal, const floa
                               int64_t n_known, const float *records, int64_t n_records, int tri_float4, float *xp, float *xn);
 /* k_motion_snapshot: n_tris (1..2^20) records of tri_float4 float4 -> n_tris elements of 5 float4 */
 int adypt_probe_motion_snapshot(const float *records, int tri_float4, int64_t n_tris, float *snapshot);
+/* ---- The chain through mirrors and glass: k_chain_start<unfold != 0> and k_chain_step<unfold != 0>, one launch each.
+ * The scene: n_tris (1..2^20) device triangle records of 8 float4 and n_mats (1..4096) device material records of 5 float4 (the reference's 64 bytes
+ * and (texel offset, w, h, 0) of the diffuse texture); at most one texture, tex_rgb (w x h RGB8, laid out as adypt_probe_sample_texture lays it out) or
+ * null for none: a material whose diffuse-texture word is 0 must describe it as (0, w, h).  Both tables lie on the device between 64 records of slack
+ * filled with 12345.0f.  Refused with -1: a hit word (the bits of a hit's .x) outside [-32, n_tris + 32) other than INT32_MAX, a triangle's material id
+ * outside [-32, n_mats + 32), bounces outside 1..8, segments outside 1..64, seg_cap outside 1..2^20.
+ * A queue is segments x seg_cap slots of o = (origin, tmin) and d = (direction, the local pixel as bits); its counters lie 16 words apart:
+ * count[16 s] of segment s, every other word stays 0.  counts: rays, followed, escaped, truncated (the kernel's ChainCounts, zero before the launch). */
+/* k_chain_start over the block list (1..64 blocks): the block-major guides (float4 per local pixel; hits.x the hit word, .y .z = u v) are updated in
+ * place — the kernel writes nothing but the class into hits.w of the pixels it does not follow.  Out, each pre-filled with 0x7fc0dead: state (2 float4
+ * per local pixel) and the queue's o and d; queue_count (segments x 16 words) starts at 0. */
+int adypt_probe_chain_start(int unfold, const float *triangles, int64_t n_tris, const float *materials, int n_mats, const uint8_t *tex_rgb, int tex_w, int tex_h, float *albedo,
+                            float *normal, float *position, float *hits, const int32_t *blocks, int n_blocks, int width, int height, const float *origin, float tmin, int bounces,
+                            int segments, uint32_t seg_cap, float *state, float *queue_o, float *queue_d, uint32_t *queue_count, uint64_t *counts);
+/* k_chain_step over the queue (in_o, in_d, in_count) the traversal answered with in_hit (float4 per slot: the hit word as bits, u, v, t), launched with
+ * chain_step_launch(segments, seg_cap).  n_px (1..2^22): the local pixels the guides (float4 each), the state (2 float4 each) and, with unfold, virt
+ * (float4 each) hold; all are updated in place and lie on the device between 64 elements of slack: a word of the slack that changed is answered with
+ * -10001.  Every slot's pixel word (the bits of in_d's .w) must lie in [-32, n_px + 32) or be INT32_MAX, every slot's hit word as above.  out_o and out_d
+ * are pre-filled with 0x7fc0dead, out_count starts at 0.  virt and origin (the camera's, 3 floats) are looked at with unfold only. */
+int adypt_probe_chain_step(int unfold, const float *triangles, int64_t n_tris, const float *materials, int n_mats, const uint8_t *tex_rgb, int tex_w, int tex_h, float *albedo,
+                           float *normal, float *position, float *hits, int n_px, int segments, uint32_t seg_cap, const float *in_o, const float *in_d, const float *in_hit,
+                           const uint32_t *in_count, int bounces, float tmin, float *state, float *out_o, float *out_d, uint32_t *out_count, uint64_t *counts, float *virt,
+                           const float *origin);
 
 #ifdef __cplusplus
 }

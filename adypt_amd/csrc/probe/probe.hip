@@ -65,6 +65,21 @@ inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kThreads - 1) / kT
 inline hipError_t launched() { const hipError_t e = hipGetLastError(); return e != hipSuccess ? e : hipDeviceSynchronize(); }
 template <class... P> bool none_null(P... p) { return (... && (p != nullptr)); }
 
+// RGB8 -> the device's texel rows (upload_textures_and_materials, scene_upload.hpp): w + 1 per row, the last a copy of the first
+std::vector<uint32_t> texel_rows(const uint8_t *rgb, int w, int h)
+{
+	const size_t row = (size_t)w + 1;
+	std::vector<uint32_t> texels(row * (size_t)h);
+	for(int y = 0; y < h; ++y)
+	{
+		uint32_t *o = texels.data() + row * (size_t)y;
+		const uint8_t *in = rgb + (size_t)y * (size_t)w * 3;
+		for(int x = 0; x < w; ++x) o[x] = (uint32_t)in[x * 3] | (uint32_t)in[x * 3 + 1] << 8 | (uint32_t)in[x * 3 + 2] << 16 | 0xff000000u;
+		o[w] = o[0];
+	}
+	return texels;
+}
+
 __device__ __forceinline__ F3 ld_f3(const float *a, int64_t i) { return f3(a[3 * i], a[3 * i + 1], a[3 * i + 2]); }
 __device__ __forceinline__ void st_f3(float *a, int64_t i, F3 v) { a[3 * i] = v.x; a[3 * i + 1] = v.y; a[3 * i + 2] = v.z; }
 
@@ -349,15 +364,7 @@ int adypt_probe_sample_texture(const uint8_t *rgb, int w, int h, const float *s,
 	PROBE_CHECK_N(n); PROBE_REQUIRE(none_null(rgb, s, t, out));
 	PROBE_REQUIRE(w > 0 && h > 0 && ((int64_t)w + 1) * (int64_t)h <= kMaxElements);
 	// the layout of upload_textures_and_materials (scene_upload.hpp), which is one step of adypt_create there and not a function of its own
-	const size_t row = (size_t)w + 1;
-	std::vector<uint32_t> texels(row * (size_t)h);
-	for(int y = 0; y < h; ++y)
-	{
-		uint32_t *o = texels.data() + row * (size_t)y;
-		const uint8_t *in = rgb + (size_t)y * (size_t)w * 3;
-		for(int x = 0; x < w; ++x) o[x] = (uint32_t)in[x * 3] | (uint32_t)in[x * 3 + 1] << 8 | (uint32_t)in[x * 3 + 2] << 16 | 0xff000000u;
-		o[w] = o[0];
-	}
+	const std::vector<uint32_t> texels = texel_rows(rgb, w, h);
 	Dev dtex, ds, dt, dout;
 	PROBE_TRY(dtex.in(texels.data(), texels.size() * 4)); PROBE_TRY(ds.in(s, n * 4)); PROBE_TRY(dt.in(t, n * 4)); PROBE_TRY(dout.out(n * 12));
 	p_sample_texture<<<grid_for(n), kThreads>>>(n, dtex.as<uint32_t>(), w, h, ds.as<float>(), dt.as<float>(), dout.as<float>());
@@ -394,20 +401,15 @@ int adypt_probe_noise(const float *samples, int k, int first, int n_frames, floa
 // ---- denoise_kernels.hpp: the product's kernels, launched with the product's launch shapes ------------------------------------------------
 namespace {
 
-// The kernels of the chain through mirrors and glass are compiled here with the others but have no entry: between two of their rounds stands the
-// context's own traversal, so they are held to their truth through the product (tests/test_gpu_denoise_specular.py), k_denoise_prepare_class with them.
-// Likewise the kernels of a moments call (moments.hpp): tests/test_gpu_denoise_moments.py holds them to their truth through the product; and the
-// unfolding chain with the prepare that goes with it (tests/test_gpu_denoise_virtual.py) — the merge by the virtual point has its entry below.
-[[maybe_unused]] const void *const kKernelsWithoutEntry[] = {(const void *)k_chain_start<false>, (const void *)k_chain_step<false>, (const void *)k_chain_start<true>,
-                                                             (const void *)k_chain_step<true>, (const void *)k_denoise_prepare_virtual, (const void *)k_denoise_prepare_class,
-                                                             (const void *)k_denoise_prepare_moments, (const void *)k_temporal_merge_moments<false>,
-                                                             (const void *)k_temporal_merge_moments<true>, (const void *)k_moments_variance};
-
 constexpr uint32_t kUnwritten = 0x7fc0deadu; // every output is filled with this quiet NaN before the launch: a pixel no thread wrote keeps it
 constexpr int kMaxSide = 4096;
 constexpr int64_t kSlackTris = 64;           // triangles of slack in front of and behind the gather's two tables ...
 constexpr uint32_t kSlackWord = 0x4640e400u; // ... filled with 12345.0f
 constexpr int64_t kMaxStray = 32;            // how far outside [0, n_known) a hit word may point (the slack is twice that)
+
+constexpr int64_t kSlackMats = 64;           // materials of slack round the chain's material table, and elements round what it indexes by a pixel word
+constexpr int kSlackTouched = 10001;         // what a chain entry answers (negated) when a word of the slack round an array it writes has changed
+constexpr uint32_t kProbeSegStride = 16;     // counters of the chain's queues lie this many words apart, as the context's cursors do
 
 bool picture_ok(int width, int height) { return width >= 1 && height >= 1 && width <= kMaxSide && height <= kMaxSide; }
 int blocks_across(int width) { return (width + kBlockDim - 1) / kBlockDim; }
@@ -420,6 +422,76 @@ bool block_list_ok(const int32_t *blocks, int n_blocks, int width, int height)
 		if(blocks[k] < 0 || blocks[k] >= n_grid) return false;
 	return true;
 }
+
+// a hit word or a pixel word a chain kernel may be given: what a failing guard would use as an index stays inside the slack — or is INT32_MAX, the one
+// far word the guards are held against (as an index it lies outside every allocation of the process)
+bool word_ok(int32_t word, int64_t n) { return ((int64_t)word >= -kMaxStray && (int64_t)word < n + kMaxStray) || word == INT32_MAX; }
+int32_t word_of(const float *f) { int32_t w; memcpy(&w, f, 4); return w; }
+
+// the scene of a chain entry on the device: both tables between slack, at most one texture
+struct ProbeChainScene {
+	Dev tris, mats, texels;
+	ChainScene sc;
+};
+// triangles: n_tris records of kTriFloat4 float4; materials: n_mats records of kMatFloat4 float4, the fifth (texel offset, w, h, 0) of the diffuse texture
+bool chain_scene_ok(const float *triangles, int64_t n_tris, const float *materials, int n_mats, const uint8_t *tex_rgb, int tex_w, int tex_h)
+{
+	if(!triangles || !materials || n_tris < 1 || n_tris > (1 << 20) || n_mats < 1 || n_mats > 4096) return false;
+	if(tex_rgb && !(tex_w > 0 && tex_h > 0 && ((int64_t)tex_w + 1) * (int64_t)tex_h <= kMaxElements)) return false;
+	for(int64_t t = 0; t < n_tris; ++t)
+	{
+		const int32_t matid = word_of(triangles + (size_t)t * kTriFloat4 * 4 + 18);
+		if(matid < -kMaxStray || matid >= n_mats + kMaxStray) return false;
+	}
+	for(int m = 0; m < n_mats; ++m) // a material that names the texture describes it as the upload would
+	{
+		const float *mp = materials + (size_t)m * kMatFloat4 * 4;
+		if(tex_rgb && word_of(mp) == 0 && !(word_of(mp + 16) == 0 && word_of(mp + 17) == tex_w && word_of(mp + 18) == tex_h)) return false;
+	}
+	return true;
+}
+hipError_t chain_scene_in(ProbeChainScene *s, const float *triangles, int64_t n_tris, const float *materials, int n_mats, const uint8_t *tex_rgb, int tex_w, int tex_h)
+{
+	const size_t tri = (size_t)kTriFloat4 * 16, mat = (size_t)kMatFloat4 * 16;
+	hipError_t e;
+	if((e = s->tris.filled((size_t)(n_tris + 2 * kSlackTris) * tri, kSlackWord)) != hipSuccess || (e = s->tris.put((size_t)kSlackTris * tri, triangles, (size_t)n_tris * tri)) != hipSuccess) return e;
+	if((e = s->mats.filled((size_t)(n_mats + 2 * kSlackMats) * mat, kSlackWord)) != hipSuccess || (e = s->mats.put((size_t)kSlackMats * mat, materials, (size_t)n_mats * mat)) != hipSuccess) return e;
+	if(tex_rgb)
+	{
+		const std::vector<uint32_t> texels = texel_rows(tex_rgb, tex_w, tex_h);
+		if((e = s->texels.in(texels.data(), texels.size() * 4)) != hipSuccess) return e;
+	}
+	s->sc = ChainScene{s->tris.as<float4>() + kSlackTris * kTriFloat4, s->mats.as<float4>() + kSlackMats * kMatFloat4, tex_rgb ? s->texels.as<uint32_t>() : nullptr, n_tris, n_mats, tex_rgb ? 1 : 0};
+	return hipSuccess;
+}
+
+// an array of n float4 elements a chain kernel indexes by a pixel word, between kSlackMats elements of slack on either side
+class Slacked {
+public:
+	hipError_t in(const float *host, size_t n)
+	{
+		n_ = n;
+		const hipError_t e = d_.filled((n + 2 * (size_t)kSlackMats) * 16, kSlackWord);
+		return e != hipSuccess ? e : d_.put((size_t)kSlackMats * 16, host, n * 16);
+	}
+	float4 *get() const { return d_.as<float4>() + kSlackMats; }
+	// the elements back to the host; *intact: no word of the slack has changed
+	hipError_t back(float *host, bool *intact) const
+	{
+		std::vector<uint32_t> all((n_ + 2 * (size_t)kSlackMats) * 4);
+		const hipError_t e = d_.back(all.data());
+		if(e != hipSuccess) return e;
+		for(size_t k = 0; k < (size_t)kSlackMats * 4; ++k)
+			if(all[k] != kSlackWord || all[all.size() - 1 - k] != kSlackWord) *intact = false;
+		memcpy(host, all.data() + (size_t)kSlackMats * 4, n_ * 16);
+		return hipSuccess;
+	}
+private:
+	Dev d_;
+	size_t n_ = 0;
+};
+
+bool chain_queue_ok(int segments, uint32_t seg_cap) { return segments >= 1 && segments <= 64 && seg_cap >= 1 && seg_cap <= (1u << 20) && (int64_t)segments * seg_cap <= kMaxElements; }
 
 } // namespace
 
@@ -566,6 +638,151 @@ int adypt_probe_motion_snapshot(const float *records, int tri_float4, int64_t n_
 	PROBE_TRY(launched());
 	PROBE_TRY(dsnap.back(snapshot));
 	return 0;
+}
+
+int adypt_probe_denoise_prepare_instance(int instance, const float *accum, const float *moments, const float *albedo, const float *normal, const float *position, const float *hits,
+                                         const int32_t *blocks, const int32_t *block_spp, int n_blocks, int width, int height, float *x0, float *x1, float *x2, float *xa,
+                                         const float *g_virtual, float *xv)
+{
+	PROBE_REQUIRE(instance >= ADYPT_PROBE_PREPARE_CLASS && instance <= ADYPT_PROBE_PREPARE_VIRTUAL);
+	PROBE_REQUIRE(none_null(accum, moments, albedo, normal, position, hits, block_spp, x0, x1, x2, xa));
+	PROBE_REQUIRE(instance != ADYPT_PROBE_PREPARE_VIRTUAL || none_null(g_virtual, xv));
+	PROBE_REQUIRE(picture_ok(width, height) && block_list_ok(blocks, n_blocks, width, height));
+	const int n_px = n_blocks * kBlockPixels;
+	const size_t local = (size_t)n_px * 16, image = (size_t)width * height * 16;
+	Dev dc, dm, da, dn, dp, dh, db, ds, dv, o0, o1, o2, oa, ov;
+	PROBE_TRY(dc.in(accum, local)); PROBE_TRY(dm.in(moments, local / 2)); PROBE_TRY(da.in(albedo, local)); PROBE_TRY(dn.in(normal, local)); PROBE_TRY(dp.in(position, local));
+	PROBE_TRY(dh.in(hits, local)); PROBE_TRY(db.in(blocks, (size_t)n_blocks * 4)); PROBE_TRY(ds.in(block_spp, (size_t)n_blocks * 4));
+	PROBE_TRY(o0.filled(image, kUnwritten)); PROBE_TRY(o1.filled(image, kUnwritten)); PROBE_TRY(o2.filled(image, kUnwritten)); PROBE_TRY(oa.filled(image, kUnwritten));
+	const LaunchShape shape = prepare_launch(n_px);
+	if(instance == ADYPT_PROBE_PREPARE_VIRTUAL)
+	{
+		PROBE_TRY(dv.in(g_virtual, local)); PROBE_TRY(ov.filled(image, kUnwritten));
+		hipLaunchKernelGGL(k_denoise_prepare_virtual, shape.grid, shape.block, 0, 0, dc.as<float4>(), dm.as<float2>(), db.as<int32_t>(), ds.as<int32_t>(), n_px, blocks_across(width), width, height,
+		                   da.as<float4>(), dn.as<float4>(), dp.as<float4>(), dh.as<float4>(), o0.as<float4>(), o1.as<float4>(), o2.as<float4>(), oa.as<float4>(), dv.as<float4>(), ov.as<float4>());
+	}
+	else
+		hipLaunchKernelGGL(instance == ADYPT_PROBE_PREPARE_CLASS ? k_denoise_prepare_class : k_denoise_prepare_moments, shape.grid, shape.block, 0, 0, dc.as<float4>(), dm.as<float2>(),
+		                   db.as<int32_t>(), ds.as<int32_t>(), n_px, blocks_across(width), width, height, da.as<float4>(), dn.as<float4>(), dp.as<float4>(), dh.as<float4>(), o0.as<float4>(),
+		                   o1.as<float4>(), o2.as<float4>(), oa.as<float4>());
+	PROBE_TRY(launched());
+	PROBE_TRY(o0.back(x0)); PROBE_TRY(o1.back(x1)); PROBE_TRY(o2.back(x2)); PROBE_TRY(oa.back(xa));
+	if(instance == ADYPT_PROBE_PREPARE_VIRTUAL) PROBE_TRY(ov.back(xv));
+	return 0;
+}
+
+int adypt_probe_temporal_merge_moments(int motion, const float *x0, const float *x1, const float *x2, const float *xa, const float *h0, const float *h1, const float *h2, const float *ha,
+                                       int have, const float *origin, const float *inv_proj, const float *inv_view, float history_cap, const float *xp, const float *xn, int width,
+                                       int height, float *merged, float *x2_out, float *length)
+{
+	PROBE_REQUIRE(none_null(x0, x1, x2, xa, h0, h1, h2, ha, origin, inv_proj, inv_view, merged, x2_out, length) && picture_ok(width, height));
+	PROBE_REQUIRE(!motion || none_null(xp, xn));
+	const size_t image = (size_t)width * height * 16;
+	Dev d0, d1, d2, da, e0, e1, e2, ea, dxp, dxn, om, ol;
+	PROBE_TRY(d0.in(x0, image)); PROBE_TRY(d1.in(x1, image)); PROBE_TRY(d2.in(x2, image)); PROBE_TRY(da.in(xa, image));
+	PROBE_TRY(e0.in(h0, image)); PROBE_TRY(e1.in(h1, image)); PROBE_TRY(e2.in(h2, image)); PROBE_TRY(ea.in(ha, image));
+	if(motion) { PROBE_TRY(dxp.in(xp, image)); PROBE_TRY(dxn.in(xn, image)); }
+	PROBE_TRY(om.filled(image, kUnwritten)); PROBE_TRY(ol.filled(image / 4, kUnwritten));
+	const TemporalCamera cam = temporal_camera(origin, inv_proj, inv_view);
+	const LaunchShape shape = merge_launch(width, height);
+	// (the instance without motion never looks at XP, XN: they are null here, as in a context that never followed motion)
+	hipLaunchKernelGGL(motion ? k_temporal_merge_moments<true> : k_temporal_merge_moments<false>, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(),
+	                   e0.as<float4>(), e1.as<float4>(), e2.as<float4>(), ea.as<float4>(), om.as<float4>(), ol.as<float>(), width, height, have ? 1 : 0, cam, history_cap, dxp.as<float4>(),
+	                   dxn.as<float4>());
+	PROBE_TRY(launched());
+	PROBE_TRY(om.back(merged)); PROBE_TRY(d2.back(x2_out)); PROBE_TRY(ol.back(length));
+	return 0;
+}
+
+int adypt_probe_moments_variance(const float *merged, const float *x1, const float *x2, const float *xa, int width, int height, const float *origin, float *out, float *variance,
+                                 uint64_t *spatial_count)
+{
+	PROBE_REQUIRE(none_null(merged, x1, x2, xa, origin, out, variance, spatial_count) && picture_ok(width, height));
+	const size_t image = (size_t)width * height * 16;
+	Dev dm, d1, d2, da, oo, ov, oc;
+	PROBE_TRY(dm.in(merged, image)); PROBE_TRY(d1.in(x1, image)); PROBE_TRY(d2.in(x2, image)); PROBE_TRY(da.in(xa, image));
+	PROBE_TRY(oo.filled(image, kUnwritten)); PROBE_TRY(ov.filled(image / 4, kUnwritten)); PROBE_TRY(oc.filled(kMomentsCountSlots * sizeof(unsigned long long), 0u));
+	RectifyOrigin o;
+	for(int k = 0; k < 3; ++k) o.o[k] = origin[k];
+	const LaunchShape shape = variance_launch(width, height);
+	hipLaunchKernelGGL(k_moments_variance, shape.grid, shape.block, 0, 0, dm.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), oo.as<float4>(), ov.as<float>(),
+	                   oc.as<unsigned long long>(), width, height, o);
+	PROBE_TRY(launched());
+	PROBE_TRY(oo.back(out)); PROBE_TRY(ov.back(variance));
+	unsigned long long slots[kMomentsCountSlots];
+	PROBE_TRY(oc.back(slots));
+	*spatial_count = 0;
+	for(int k = 0; k < kMomentsCountSlots; ++k) *spatial_count += slots[k];
+	return 0;
+}
+
+int adypt_probe_chain_start(int unfold, const float *triangles, int64_t n_tris, const float *materials, int n_mats, const uint8_t *tex_rgb, int tex_w, int tex_h, float *albedo,
+                            float *normal, float *position, float *hits, const int32_t *blocks, int n_blocks, int width, int height, const float *origin, float tmin, int bounces,
+                            int segments, uint32_t seg_cap, float *state, float *queue_o, float *queue_d, uint32_t *queue_count, uint64_t *counts)
+{
+	PROBE_REQUIRE(none_null(albedo, normal, position, hits, origin, state, queue_o, queue_d, queue_count, counts));
+	PROBE_REQUIRE(picture_ok(width, height) && block_list_ok(blocks, n_blocks, width, height) && n_blocks <= 64 && chain_bounces_valid(bounces) && chain_queue_ok(segments, seg_cap));
+	PROBE_REQUIRE(chain_scene_ok(triangles, n_tris, materials, n_mats, tex_rgb, tex_w, tex_h));
+	const int n_px = n_blocks * kBlockPixels;
+	for(int L = 0; L < n_px; ++L) PROBE_REQUIRE(word_ok(word_of(hits + (size_t)L * 4), n_tris));
+	const size_t local = (size_t)n_px * 16, queue = (size_t)segments * seg_cap * 16, cursors = (size_t)segments * kProbeSegStride * 4;
+	ProbeChainScene scene;
+	PROBE_TRY(chain_scene_in(&scene, triangles, n_tris, materials, n_mats, tex_rgb, tex_w, tex_h));
+	Dev da, dn, dp, dh, db, ds, qo, qd, qc, dc;
+	PROBE_TRY(da.in(albedo, local)); PROBE_TRY(dn.in(normal, local)); PROBE_TRY(dp.in(position, local)); PROBE_TRY(dh.in(hits, local)); PROBE_TRY(db.in(blocks, (size_t)n_blocks * 4));
+	PROBE_TRY(ds.filled(2 * local, kUnwritten)); PROBE_TRY(qo.filled(queue, kUnwritten)); PROBE_TRY(qd.filled(queue, kUnwritten)); PROBE_TRY(qc.filled(cursors, 0u));
+	PROBE_TRY(dc.filled(sizeof(ChainCounts), 0u));
+	const ChainGuides g{da.as<float4>(), dn.as<float4>(), dp.as<float4>(), dh.as<float4>()};
+	const ChainQueue out{qo.as<float4>(), qd.as<float4>(), qc.as<uint32_t>(), seg_cap, kProbeSegStride, segments};
+	const ChainOrigin o{{origin[0], origin[1], origin[2]}, tmin};
+	const LaunchShape shape = chain_start_launch(n_px);
+	hipLaunchKernelGGL(unfold ? k_chain_start<true> : k_chain_start<false>, shape.grid, shape.block, 0, 0, scene.sc, g, db.as<int32_t>(), n_px, blocks_across(width), width, height, o, bounces,
+	                   ds.as<float4>(), out, dc.as<ChainCounts>());
+	PROBE_TRY(launched());
+	PROBE_TRY(da.back(albedo)); PROBE_TRY(dn.back(normal)); PROBE_TRY(dp.back(position)); PROBE_TRY(dh.back(hits));
+	PROBE_TRY(ds.back(state)); PROBE_TRY(qo.back(queue_o)); PROBE_TRY(qd.back(queue_d)); PROBE_TRY(qc.back(queue_count));
+	ChainCounts c;
+	PROBE_TRY(dc.back(&c));
+	counts[0] = c.rays; counts[1] = c.followed; counts[2] = c.escaped; counts[3] = c.truncated;
+	return 0;
+}
+
+int adypt_probe_chain_step(int unfold, const float *triangles, int64_t n_tris, const float *materials, int n_mats, const uint8_t *tex_rgb, int tex_w, int tex_h, float *albedo,
+                           float *normal, float *position, float *hits, int n_px, int segments, uint32_t seg_cap, const float *in_o, const float *in_d, const float *in_hit,
+                           const uint32_t *in_count, int bounces, float tmin, float *state, float *out_o, float *out_d, uint32_t *out_count, uint64_t *counts, float *virt,
+                           const float *origin)
+{
+	PROBE_REQUIRE(none_null(albedo, normal, position, hits, in_o, in_d, in_hit, in_count, state, out_o, out_d, out_count, counts) && (!unfold || none_null(virt, origin)));
+	PROBE_REQUIRE(n_px >= 1 && n_px <= (1 << 22) && chain_bounces_valid(bounces) && chain_queue_ok(segments, seg_cap));
+	PROBE_REQUIRE(chain_scene_ok(triangles, n_tris, materials, n_mats, tex_rgb, tex_w, tex_h));
+	const size_t slots = (size_t)segments * seg_cap;
+	for(size_t k = 0; k < slots; ++k) PROBE_REQUIRE(word_ok(word_of(in_d + k * 4 + 3), n_px) && word_ok(word_of(in_hit + k * 4), n_tris));
+	const size_t queue = slots * 16, cursors = (size_t)segments * kProbeSegStride * 4;
+	ProbeChainScene scene;
+	PROBE_TRY(chain_scene_in(&scene, triangles, n_tris, materials, n_mats, tex_rgb, tex_w, tex_h));
+	Slacked da, dn, dp, dh, ds, dv;
+	Dev io, id, ih, ic, qo, qd, qc, dc;
+	PROBE_TRY(da.in(albedo, n_px)); PROBE_TRY(dn.in(normal, n_px)); PROBE_TRY(dp.in(position, n_px)); PROBE_TRY(dh.in(hits, n_px)); PROBE_TRY(ds.in(state, 2 * (size_t)n_px));
+	if(unfold) PROBE_TRY(dv.in(virt, n_px));
+	PROBE_TRY(io.in(in_o, queue)); PROBE_TRY(id.in(in_d, queue)); PROBE_TRY(ih.in(in_hit, queue)); PROBE_TRY(ic.in(in_count, cursors));
+	PROBE_TRY(qo.filled(queue, kUnwritten)); PROBE_TRY(qd.filled(queue, kUnwritten)); PROBE_TRY(qc.filled(cursors, 0u)); PROBE_TRY(dc.filled(sizeof(ChainCounts), 0u));
+	const ChainGuides g{da.get(), dn.get(), dp.get(), dh.get()};
+	const ChainQueue in{io.as<float4>(), id.as<float4>(), ic.as<uint32_t>(), seg_cap, kProbeSegStride, segments};
+	const ChainQueue out{qo.as<float4>(), qd.as<float4>(), qc.as<uint32_t>(), seg_cap, kProbeSegStride, segments};
+	ChainUnfold u{unfold ? dv.get() : nullptr, {0.0f, 0.0f, 0.0f}};
+	if(unfold) for(int k = 0; k < 3; ++k) u.o[k] = origin[k];
+	const LaunchShape shape = chain_step_launch(segments, seg_cap); // (seg_cap: the most rays a segment can hold)
+	hipLaunchKernelGGL(unfold ? k_chain_step<true> : k_chain_step<false>, shape.grid, shape.block, 0, 0, scene.sc, g, in, ih.as<float4>(), n_px, bounces, tmin, ds.get(), out,
+	                   dc.as<ChainCounts>(), u);
+	PROBE_TRY(launched());
+	bool intact = true;
+	PROBE_TRY(da.back(albedo, &intact)); PROBE_TRY(dn.back(normal, &intact)); PROBE_TRY(dp.back(position, &intact)); PROBE_TRY(dh.back(hits, &intact)); PROBE_TRY(ds.back(state, &intact));
+	if(unfold) PROBE_TRY(dv.back(virt, &intact));
+	PROBE_TRY(qo.back(out_o)); PROBE_TRY(qd.back(out_d)); PROBE_TRY(qc.back(out_count));
+	ChainCounts c;
+	PROBE_TRY(dc.back(&c));
+	counts[0] = c.rays; counts[1] = c.followed; counts[2] = c.escaped; counts[3] = c.truncated;
+	return intact ? 0 : -kSlackTouched;
 }
 
 } // extern "C"

@@ -32,8 +32,9 @@ def prepare(C, m2, n, A):
     return D0, S0, ka
 
 
-def merge(D0, S0, n, N, P, A, hit, hist, cap=64.0, through=None):
-    """temporal_merge_through<true> of every pixel: (Dm, S, n_out).  through: None, or (N_prev, P_prev, valid) of the motion form."""
+def merge(D0, S0, n, N, P, A, hit, hist, cap=64.0, through=None, square_tap_weight=False):
+    """temporal_merge_through<true> of every pixel: (Dm, S, n_out).  through: None, or (N_prev, P_prev, valid) of the motion form.
+    square_tap_weight=True: a tap's S taken with w * w instead of w (not part of the definition: what an edge input must tell from it)."""
     D0, S0, n = np.asarray(D0, np.float32), np.asarray(S0, np.float32), np.asarray(n, np.float32)
     h, w = S0.shape
     if hist is None:
@@ -68,7 +69,7 @@ def merge(D0, S0, n, N, P, A, hit, hist, cap=64.0, through=None):
                 wgt = ((F(1.0) - ux) if tx == 0 else ux) * ((F(1.0) - uy) if ty == 0 else uy)
                 sw = np.where(counts, sw + wgt, sw)
                 sd = np.where(counts[..., None], sd + wgt[..., None] * Dq, sd)
-                ss = np.where(counts, ss + wgt * Sq, ss)
+                ss = np.where(counts, ss + (wgt * wgt if square_tap_weight else wgt) * Sq, ss)
                 sn = np.where(counts, sn + wgt * nq, sn)
         take = ok & (sw > TT.MIN_WEIGHT)
         Dh, Sh, hq = sd / sw[..., None], ss / sw, sn / sw

@@ -258,6 +258,105 @@ def temporal_merge(x, hist, have, cam, cap, motion=None, rectify=None):
     return merged, x2, length, kept
 
 
+PREPARE_INSTANCES = {"class": 0, "moments": 1, "virtual": 2}  # probe.h ADYPT_PROBE_PREPARE_*
+
+
+def denoise_prepare_instance(instance, accum, moments, albedo, normal, position, hits, blocks, block_spp, w, h, virtual=None):
+    """k_denoise_prepare_class / _moments / _virtual over denoise_prepare's arrays (hits.w: the class word) and, for "virtual", the block-major image of
+    the virtual points: X0, X1, X2, XA and, for "virtual", XV, each (h, w, 4)."""
+    blocks, block_spp = _i32(blocks), _i32(block_spp)
+    nb = len(blocks)
+    assert len(block_spp) == nb and (virtual is not None) == (instance == "virtual")
+    out = [np.empty((h, w, 4), F32) for _ in range(5 if instance == "virtual" else 4)]
+    _call("denoise_prepare_instance", C.c_int(PREPARE_INSTANCES[instance]), _local(accum, nb), _local(moments, nb, 2), _local(albedo, nb), _local(normal, nb), _local(position, nb),
+          _local(hits, nb), blocks, block_spp, C.c_int(nb), C.c_int(w), C.c_int(h), *out[:4], _local(virtual, nb) if virtual is not None else None, out[4] if virtual is not None else None)
+    return out
+
+
+def temporal_merge_moments(x, hist, have, cam, cap, motion=None):
+    """k_temporal_merge_moments<motion is not None>: temporal_merge's arguments, the fourth channel of X0 and H0 holding S: (merged (h, w, 4), X2 as the
+    kernel leaves it, length (h, w))."""
+    h, w = np.shape(x[0])[:2]
+    x, hist = [_img(a, h, w) for a in x], [_img(a, h, w) for a in hist]
+    o, ip, iv = (_f(v) for v in cam)
+    assert len(o) == 3 and len(ip) == 16 and len(iv) == 16
+    xp, xn = (_img(a, h, w) for a in motion) if motion is not None else (None, None)
+    merged, x2, length = np.empty((h, w, 4), F32), np.empty((h, w, 4), F32), np.empty((h, w), F32)
+    _call("temporal_merge_moments", C.c_int(motion is not None), *x, *hist, C.c_int(1 if have else 0), o, ip, iv, C.c_float(cap), xp, xn, C.c_int(w), C.c_int(h), merged, x2, length)
+    return merged, x2, length
+
+
+def moments_variance(merged, x1, x2, xa, origin):
+    """k_moments_variance: (out (h, w, 4) = (D, V), the variance read-out (h, w), the sum of the kernel's count slots)."""
+    h, w = np.shape(merged)[:2]
+    out, variance, count = np.empty((h, w, 4), F32), np.empty((h, w), F32), np.zeros(1, np.uint64)
+    o = _f(origin)
+    assert len(o) == 3
+    _call("moments_variance", _img(merged, h, w), _img(x1, h, w), _img(x2, h, w), _img(xa, h, w), C.c_int(w), C.c_int(h), o, out, variance, count)
+    return out, variance, int(count[0])
+
+
+# ---- the chain through mirrors and glass: k_chain_start, k_chain_step ----
+SEG_STRIDE = 16  # words between the counters of two segments of a queue
+
+
+def device_materials(materials, texture=None):
+    """(n, 20) float32: MAT_DT materials in the device's layout — the 64 bytes, then (texel offset, w, h, 0) of the diffuse texture where the material names
+    the one texture there is (as upload_textures_and_materials leaves it)."""
+    m = np.ascontiguousarray(materials).view(MAT_DT).reshape(-1)
+    out = np.zeros((len(m), 20), U32)
+    out[:, :16] = m.view(U32).reshape(len(m), 16)
+    if texture is not None:
+        out[m["dtex"] == 0, 16:19] = np.array([0, texture.shape[1], texture.shape[0]], U32)
+    return out.view(F32)
+
+
+def _scene_args(scene):
+    """scene = (records (n_tris, 32), materials (n_mats, 20), texture (h, w, 3) uint8 or None)"""
+    records, materials, texture = scene
+    records, materials = np.ascontiguousarray(records).view(F32).reshape(-1, 32), np.ascontiguousarray(materials).view(F32).reshape(-1, 20)
+    tex = None if texture is None else np.ascontiguousarray(texture, dtype=np.uint8)
+    assert tex is None or (tex.ndim == 3 and tex.shape[2] == 3)
+    return [records, C.c_int64(len(records)), materials, C.c_int(len(materials)), tex, C.c_int(0 if tex is None else tex.shape[1]), C.c_int(0 if tex is None else tex.shape[0])]
+
+
+def chain_start(unfold, scene, albedo, normal, position, hits, blocks, w, h, origin, tmin, bounces, segments, seg_cap):
+    """k_chain_start<unfold>: dict(albedo, normal, position, hits: the block-major guides as the kernel leaves them; state (n_px, 2, 4); o, d (segments,
+    seg_cap, 4): the queue; count (segments,) and count_words (segments, 16): its counters; counts = dict(rays, followed, escaped, truncated))."""
+    blocks = _i32(blocks)
+    nb = len(blocks)
+    g = [_local(a, nb).copy() for a in (albedo, normal, position, hits)]
+    state, qo, qd = np.empty((nb * 1024, 2, 4), F32), np.empty((segments, seg_cap, 4), F32), np.empty((segments, seg_cap, 4), F32)
+    qc, counts = np.empty((segments, SEG_STRIDE), U32), np.zeros(4, np.uint64)
+    o = _f(origin)
+    assert len(o) == 3
+    _call("chain_start", C.c_int(1 if unfold else 0), *_scene_args(scene), *g, blocks, C.c_int(nb), C.c_int(w), C.c_int(h), o, C.c_float(tmin), C.c_int(bounces), C.c_int(segments),
+          C.c_uint32(seg_cap), state, qo, qd, qc, counts)
+    return dict(albedo=g[0], normal=g[1], position=g[2], hits=g[3], state=state, o=qo, d=qd, count=qc[:, 0].copy(), count_words=qc,
+                counts=dict(zip(("rays", "followed", "escaped", "truncated"), (int(v) for v in counts))))
+
+
+def chain_step(unfold, scene, albedo, normal, position, hits, state, queue, bounces, tmin, virt=None, origin=None):
+    """k_chain_step<unfold>.  The guides (n_px, 4), state (n_px, 2, 4) and with unfold virt (n_px, 4); queue = dict(o, d, hit (segments, seg_cap, 4), count
+    (segments,)).  -> dict(albedo, normal, position, hits, state, virt as the kernel leaves them; o, d, count, count_words: the queue it wrote; counts)."""
+    n_px = len(hits)
+    g = [np.ascontiguousarray(a, dtype=F32).reshape(n_px, 4).copy() for a in (albedo, normal, position, hits)]
+    state = np.ascontiguousarray(state, dtype=F32).reshape(n_px, 2, 4).copy()
+    qi = [np.ascontiguousarray(queue[k], dtype=F32) for k in ("o", "d", "hit")]
+    segments, seg_cap = qi[0].shape[:2]
+    assert all(a.shape == (segments, seg_cap, 4) for a in qi)
+    ic = np.zeros((segments, SEG_STRIDE), U32)
+    ic[:, 0] = queue["count"]
+    qo, qd = np.empty((segments, seg_cap, 4), F32), np.empty((segments, seg_cap, 4), F32)
+    qc, counts = np.empty((segments, SEG_STRIDE), U32), np.zeros(4, np.uint64)
+    assert (virt is not None and origin is not None) or not unfold
+    virt = np.ascontiguousarray(virt, dtype=F32).reshape(n_px, 4).copy() if unfold else None
+    _call("chain_step", C.c_int(1 if unfold else 0), *_scene_args(scene), *g, C.c_int(n_px), C.c_int(segments), C.c_uint32(seg_cap), *qi, ic, C.c_int(bounces), C.c_float(tmin), state, qo,
+          qd, qc, counts, virt, _f(origin) if unfold else None)
+    return dict(albedo=g[0], normal=g[1], position=g[2], hits=g[3], state=state, virt=virt, o=qo, d=qd, count=qc[:, 0].copy(), count_words=qc,
+                counts=dict(zip(("rays", "followed", "escaped", "truncated"), (int(v) for v in counts))))
+
+
 def motion_gather(hits, normal, position, blocks, w, h, snapshot, records):
     """k_motion_gather: snapshot (n_known, 20) float32, records (n_records >= n_known, 4 * tri_float4): XP, XN (h, w, 4)."""
     blocks = _i32(blocks)

@@ -183,6 +183,56 @@ def chain_guides(osc, P, K, primary=None, ops=None):
     return out
 
 
+# ---- one kernel's part of the chain: what k_chain_start does per pixel and k_chain_step per ray, composed from the operations above ----
+def start(osc, tri, normal, position, origin, K, ops=None, unfold=None):
+    """The start of the chain at every pixel given: tri (n,) int32 the primary hit words (a word outside [0, triangles) is no known triangle), normal and
+    position (n, 3) the captured guides.  -> dict(go (n,) bool: the pixel is followed; cls (n,) float32: the class of a pixel that is NOT followed (1 where
+    the word is not -1, else 0); d, T (n, 3): the first ray's direction and the throughput of a followed pixel; length (n,): the unfolded length so far
+    with `unfold` (virtual_truth.NumpyUnfold), 0 without)."""
+    ops = ops or NumpyOps()
+    tri = np.asarray(tri, np.int32)
+    cnt = len(tri)
+    normal, position = np.asarray(normal, np.float32).reshape(cnt, 3), np.asarray(position, np.float32).reshape(cnt, 3)
+    go, d, T, length = np.zeros(cnt, bool), np.zeros((cnt, 3), np.float32), np.ones((cnt, 3), np.float32), np.zeros(cnt, np.float32)
+    at = np.flatnonzero((tri >= 0) & (tri < len(osc.triangles)))
+    if len(at):
+        bad, illum, _, ks, ior, _ = materials_of(osc, tri[at])
+        go[at], d[at], T[at] = ops.at_primary(bad, illum, ks, ior, normal[at], position[at], origin, K)
+    if unfold is not None and go.any():
+        length[go] = unfold.start_length(position[go], origin)
+    return dict(go=go, cls=np.where(tri != -1, F(1), F(0)).astype(np.float32), d=d, T=T, length=length)
+
+
+def step(osc, tri, u, v, T, d, L, K, ray_origin=None, length=None, ops=None, unfold=None):
+    """One round of the chain for the rays given: tri (n,) int32 the closest-hit words the traversal answered, (u, v) of the hits, (T, d, L) the state
+    the rays were traced with and, with `unfold`, ray_origin (n, 3) and length (n,) so far.  -> dict(go: the chain goes on; escaped, truncated (n,) bool;
+    albedo, normal, position (n, 3) and cls (n,) int32: the guides of a chain that ended (where ~go); p: the hit point, d, T, L, length: the state and
+    the next ray's origin where go)."""
+    ops = ops or NumpyOps()
+    tri, L = np.asarray(tri, np.int32), np.asarray(L, np.int32)
+    cnt = len(tri)
+    T, d = np.asarray(T, np.float32).reshape(cnt, 3), np.asarray(d, np.float32).reshape(cnt, 3)
+    escaped = ~((tri >= 0) & (tri < len(osc.triangles)))
+    out = dict(go=np.zeros(cnt, bool), escaped=escaped, truncated=np.zeros(cnt, bool), albedo=T.copy(), normal=d.copy(), position=np.zeros((cnt, 3), np.float32),
+               cls=(-(L + 1)).astype(np.int32), p=np.zeros((cnt, 3), np.float32), d=d.copy(), T=T.copy(), L=L.copy(),
+               length=np.zeros(cnt, np.float32) if length is None else np.asarray(length, np.float32).copy())
+    at = np.flatnonzero(~escaped)
+    if len(at) == 0:
+        return out
+    L1 = L[at] + 1
+    p, n = getattr(ops, "hit_point", hit_point)(tri_words(osc, tri[at]), np.asarray(u, np.float32)[at].copy(), np.asarray(v, np.float32)[at].copy())
+    if unfold is not None:
+        out["length"][at] = unfold.unfold(out["length"][at], p, np.asarray(ray_origin, np.float32).reshape(cnt, 3)[at])
+    bad, illum, kd, ks, ior, dtex = materials_of(osc, tri[at])
+    delta = ~bad & (illum >= 3) & (illum <= 7)
+    kd = textured_kd(osc, tri[at], np.asarray(u, np.float32)[at], np.asarray(v, np.float32)[at], kd, np.where(delta, -1, dtex))
+    go, albedo, d2, T2 = ops.at_surface(T[at], d[at], L1, bad, illum, kd, ks, ior, n, K)
+    out["go"][at], out["truncated"][at] = go, ~go & delta
+    out["albedo"][at], out["normal"][at], out["position"][at], out["cls"][at] = albedo, n, p, 1 + L1
+    out["p"][at], out["d"][at], out["T"][at], out["L"][at] = p, d2, T2, L1
+    return out
+
+
 def level(Dm, V, N, P, cls, step, sigma_l, sigma_z):
     """tests/denoise_truth.py level with a class per pixel: a tap counts where its class is the centre's; `hit` is class != 0."""
     sigma_l, sigma_z = F(sigma_l), F(sigma_z)

@@ -399,3 +399,133 @@ def test_the_new_symbols_are_declared_and_bound():
     from adypt_amd import api
     for cls in (api.HipPathTracer, api.MultiPathTracer):
         assert hasattr(cls, "ReadDenoiseVariance") and hasattr(cls, "GetDenoiseMoments")
+
+
+# ---- the edge inputs the kernels are probed with on the GPU (tests/moments_edge_inputs.py), through the header ----
+RAW_DRIVER = r"""
+#include "temporal.hpp"
+#include <cstdio>
+#include <cstring>
+#include <vector>
+using namespace adypt;
+// IN:  int32 mode, w, h, flag_a, flag_b, then by mode (n = w h; an image is n float4):
+//   0  prepare   flag_a: moments_prepare, else denoise_prepare.  float32 C[n][3], m2[n], count[n], A[n][3]                      OUT: X0
+//   1  merge     flag_a: have, flag_b: motion.  float32 cap, cam[35], images X0 X1 X2 XA H0 H1 H2 HA and with motion XP XN      OUT: merged, float32 n_out[n]
+//   2  variance  float32 origin[3], images merged X1 X2 XA                                                                     OUT: float32 V[n], spatial[n] (0 / 1)
+struct Img {
+	const Dn4 *a, *b, *c, *d;
+	Dn4 x0(int i) const { return a[i]; }
+	Dn4 x1(int i) const { return b[i]; }
+	Dn4 x2(int i) const { return c[i]; }
+	Dn4 xa(int i) const { return d[i]; }
+	Dn4 h0(int i) const { return a[i]; }
+	Dn4 h1(int i) const { return b[i]; }
+	Dn4 h2(int i) const { return c[i]; }
+	Dn4 ha(int i) const { return d[i]; }
+};
+static bool rd(FILE *f, std::vector<float> &v) { return fread(v.data(), 4, v.size(), f) == v.size(); }
+static bool image(FILE *f, std::vector<Dn4> &v)
+{
+	static_assert(sizeof(Dn4) == 16, "four floats");
+	return fread(v.data(), 16, v.size(), f) == v.size();
+}
+int main(int argc, char **argv)
+{
+	if(argc != 3) return 2;
+	FILE *in = fopen(argv[1], "rb"), *out = fopen(argv[2], "wb");
+	if(!in || !out) return 3;
+	int32_t h[5];
+	if(fread(h, 4, 5, in) != 5) return 4;
+	const int width = h[1], height = h[2];
+	const size_t n = (size_t)width * height;
+	if(h[0] == 0)
+	{
+		std::vector<float> C(n * 3), m2(n), cnt(n), A(n * 3);
+		if(!rd(in, C) || !rd(in, m2) || !rd(in, cnt) || !rd(in, A)) return 4;
+		std::vector<Dn4> x0(n);
+		for(size_t i = 0; i < n; ++i)
+			x0[i] = h[3] ? moments_prepare(C[3 * i], C[3 * i + 1], C[3 * i + 2], m2[i], cnt[i], A[3 * i], A[3 * i + 1], A[3 * i + 2])
+			             : denoise_prepare(C[3 * i], C[3 * i + 1], C[3 * i + 2], m2[i], cnt[i], A[3 * i], A[3 * i + 1], A[3 * i + 2]);
+		fwrite(x0.data(), 16, n, out);
+	}
+	else if(h[0] == 1)
+	{
+		std::vector<float> s(36);
+		std::vector<Dn4> x0(n), x1(n), x2(n), xa(n), h0(n), h1(n), h2(n), ha(n), xp(n), xn(n), merged(n);
+		if(!rd(in, s) || !image(in, x0) || !image(in, x1) || !image(in, x2) || !image(in, xa) || !image(in, h0) || !image(in, h1) || !image(in, h2) || !image(in, ha)) return 4;
+		if(h[4] && (!image(in, xp) || !image(in, xn))) return 4;
+		const TemporalCamera tc = temporal_camera(&s[1], &s[4], &s[20]);
+		const Img hist{h0.data(), h1.data(), h2.data(), ha.data()};
+		std::vector<float> no(n);
+		for(size_t i = 0; i < n; ++i)
+		{
+			const TemporalOut m = h[4] ? temporal_merge_motion<true>(hist, h[3] != 0, tc, width, height, x0[i], x1[i], xa[i], x2[i].w, s[0], xp[i], xn[i])
+			                           : temporal_merge<true>(hist, h[3] != 0, tc, width, height, x0[i], x1[i], x2[i], xa[i], x2[i].w, s[0]);
+			merged[i] = m.x0; no[i] = m.n;
+		}
+		fwrite(merged.data(), 16, n, out); fwrite(no.data(), 4, n, out);
+	}
+	else
+	{
+		std::vector<float> o(3), V(n), sp(n);
+		std::vector<Dn4> x0(n), x1(n), x2(n), xa(n);
+		if(!rd(in, o) || !image(in, x0) || !image(in, x1) || !image(in, x2) || !image(in, xa)) return 4;
+		const Img img{x0.data(), x1.data(), x2.data(), xa.data()};
+		for(int y = 0; y < height; ++y)
+			for(int x = 0; x < width; ++x)
+			{
+				const MomentsVariance r = moments_variance(img, width, height, x, y, o.data());
+				V[(size_t)y * width + x] = r.v; sp[(size_t)y * width + x] = r.spatial ? 1.0f : 0.0f;
+			}
+		fwrite(V.data(), 4, n, out); fwrite(sp.data(), 4, n, out);
+	}
+	fclose(out);
+	return 0;
+}
+"""
+
+
+def test_the_probes_edge_inputs_through_the_header(tmp_path):
+    """tests/moments_edge_inputs.py — what tests/test_gpu_moments_probes.py gives the kernels — through moments_prepare, denoise_prepare,
+    temporal_merge<true>, temporal_merge_motion<true> and moments_variance compiled on the host: header and numpy agree to the bit, and every case reaches
+    what it is named after.  The GPU run then adds only kernel against truth."""
+    from tests import denoise_edge_inputs as E
+    from tests import moments_edge_inputs as M
+    src, exe = str(tmp_path / "raw.cpp"), str(tmp_path / "raw")
+    open(src, "w").write(RAW_DRIVER)
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-I", DEVICE, src, "-o", exe])
+
+    def run(head, *arrays):
+        with open(str(tmp_path / "in.bin"), "wb") as f:
+            f.write(np.array(head, np.int32).tobytes() + b"".join(np.ascontiguousarray(a, dtype=np.float32).tobytes() for a in arrays))
+        subprocess.check_call([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")])
+        return np.fromfile(str(tmp_path / "out.bin"), dtype=np.float32)
+
+    def agree(got, want, what):
+        assert M.same_bits(got, want).all(), "%s: %d words differ from the numpy restatement" % (what, int((~M.same_bits(got, want)).sum()))
+    for name, case in M.prepare_cases().items():
+        w, h = case["w"], case["h"]
+        for instance in ("class", "moments", "virtual"):
+            assert M.prepare_reach(case, instance), (name, instance)
+        for instance in ("class", "moments"):
+            got = run([0, w, h, instance == "moments", 0], case["C"], case["m2"], D.block_counts(h, w, case["spp"]), case["A"])
+            agree(got.reshape(h, w, 4), M.prepare_truth(case, instance)[0], "prepare %s %s" % (instance, name))
+    for key, case in M.merge_cases().items():
+        assert case["reach"](M.merge_truth(case)), key
+        im = E.images(case["call"])
+        h, w = im["hit"].shape
+        hist = case["hist"]
+        H, raw = E.h_images(hist if hist is not None else case.get("stale"), h, w)
+        _, XP, XN, _ = M.merge_through(case)
+        for motion in (False, True):
+            t = M.merge_truth(dict((k, v) for k, v in case.items() if motion or k != "tri"), motion=motion)
+            got = run([1, w, h, hist is not None, motion], [case["kw"].get("cap", 64.0)], *raw, *E.x_images(im), *H, *((XP, XN) if motion else ()))
+            agree(got[:4 * h * w].reshape(h, w, 4), E.rgba(t["D"], t["V"]), "merge %s, motion %s" % (key, motion))
+            agree(got[4 * h * w:].reshape(h, w), t["n_out"], "n_out of %s, motion %s" % (key, motion))
+    for name, case in M.variance_cases().items():
+        t = M.variance_truth(case)
+        assert case["reach"](t), name
+        w, h = case["w"], case["h"]
+        got = run([2, w, h, 0, 0], case["origin"], *M.variance_images(case))
+        agree(got[:h * w].reshape(h, w), t["V"], "variance " + name)
+        assert np.array_equal(got[h * w:].reshape(h, w) != 0, t["spatial"]), name

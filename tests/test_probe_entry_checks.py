@@ -34,7 +34,8 @@ def test_bad_counts_sizes_and_null_pointers_are_refused():
     assert lib.adypt_probe_noise(p, C.c_int(4096), C.c_int(0), C.c_int(2), p, p, p, C.c_int64(1 << 13)) == INVALID  # n * k beyond 2^24 samples
 
 
-KERNEL_ENTRIES = ("denoise_prepare", "atrous", "rectify_window", "temporal_merge", "motion_gather", "motion_snapshot")
+KERNEL_ENTRIES = ("denoise_prepare", "atrous", "rectify_window", "temporal_merge", "motion_gather", "motion_snapshot", "temporal_merge_virtual", "denoise_prepare_instance",
+                  "temporal_merge_moments", "moments_variance", "chain_start", "chain_step")
 
 
 def test_the_denoiser_kernel_entries_refuse_what_a_kernel_must_not_be_given():
@@ -71,3 +72,73 @@ def test_the_denoiser_kernel_entries_refuse_what_a_kernel_must_not_be_given():
     merge = lambda motion, rectify, xp, r0, kept, w=8: lib.adypt_probe_temporal_merge(i(motion), i(rectify), p, p, p, p, p, p, p, p, i(1), p, p, p, C.c_float(64.0), xp, xp, r0, r0,  # noqa: E731
                                                                                        C.c_float(1.0), i(w), i(8), p, p, p, kept)
     assert merge(1, 0, None, None, None) == INVALID and merge(0, 1, None, None, p) == INVALID and merge(0, 1, None, p, None) == INVALID and merge(0, 0, None, None, None, w=0) == INVALID
+
+
+def test_the_moments_and_prepare_instance_entries_refuse_what_a_kernel_must_not_be_given():
+    lib = P.lib()
+    buf = np.zeros(4 * 1024, np.float32)
+    p = buf.ctypes.data_as(C.c_void_p)
+    i = C.c_int
+    spp = np.array([8], np.int32).ctypes.data_as(C.c_void_p)
+    zero = np.array([0], np.int32).ctypes.data_as(C.c_void_p)
+    prepare = lambda instance, b=zero, nb=1, w=8, h=8, x0=p, gv=p, xv=p: lib.adypt_probe_denoise_prepare_instance(i(instance), p, p, p, p, p, p, b, spp, i(nb), i(w), i(h), x0, p, p, p, gv, xv)  # noqa: E731
+    assert prepare(-1) == INVALID and prepare(3) == INVALID, "an instance that is none of the three"
+    assert prepare(2, gv=None) == INVALID and prepare(2, xv=None) == INVALID and prepare(0, x0=None) == INVALID and prepare(1, b=None) == INVALID
+    for block, w, h in ((-1, 8, 8), (1, 8, 8), (2, 33, 9), (0, 0, 8), (0, 8, 4097)):
+        b = np.array([block], np.int32).ctypes.data_as(C.c_void_p)
+        for instance in (0, 1, 2):
+            assert prepare(instance, b=b, w=w, h=h) == INVALID, (instance, block, w, h)
+    assert prepare(0, nb=0) == INVALID
+    merge = lambda motion, xp, w=8, h=8, x0=p, out=p: lib.adypt_probe_temporal_merge_moments(i(motion), x0, p, p, p, p, p, p, p, i(1), p, p, p, C.c_float(64.0), xp, xp, i(w), i(h), p, p, out)  # noqa: E731
+    assert merge(1, None) == INVALID and merge(0, None, w=0) == INVALID and merge(0, None, h=4097) == INVALID and merge(0, None, x0=None) == INVALID and merge(0, p, out=None) == INVALID
+    variance = lambda w=8, h=8, origin=p, count=p: lib.adypt_probe_moments_variance(p, p, p, p, i(w), i(h), origin, p, p, count)  # noqa: E731
+    assert variance(w=0) == INVALID and variance(h=-1) == INVALID and variance(w=4097) == INVALID and variance(origin=None) == INVALID and variance(count=None) == INVALID
+
+
+def test_the_chain_entries_refuse_what_a_kernel_must_not_be_given():
+    """Null pointers, sizes out of range, and a hit word, a material id or a pixel word outside the slack: refused before anything is allocated or
+    launched — a chain kernel reads where a hit word and a material id say and writes where a pixel word says."""
+    lib = P.lib()
+    i, u32, i64, f = C.c_int, C.c_uint32, C.c_int64, C.c_float
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    buf = np.zeros(8 * 1024, np.float32)
+    p = ptr(buf)
+    zero = ptr(np.array([0], np.int32))
+    tris, mats = np.zeros((4, 32), np.float32), np.zeros((2, 20), np.float32)
+    mats.view(np.int32)[:, 0] = -1
+    tex = np.zeros((3, 4, 3), np.uint8)
+
+    def start(tris=tris, n_tris=4, mats=mats, n_mats=2, tex=None, tw=0, th=0, hits=p, blocks=zero, nb=1, w=8, h=8, origin=p, bounces=8, segments=2, cap=512, state=p, counts=p):
+        return lib.adypt_probe_chain_start(i(0), None if tris is None else ptr(tris), i64(n_tris), None if mats is None else ptr(mats), i(n_mats), None if tex is None else ptr(tex), i(tw),
+                                           i(th), p, p, p, hits, blocks, i(nb), i(w), i(h), origin, f(0.001), i(bounces), i(segments), u32(cap), state, p, p, p, counts)
+
+    def step(tris=tris, n_tris=4, mats=mats, n_mats=2, n_px=1024, segments=2, cap=8, in_d=p, in_hit=p, bounces=8, unfold=0, virt=p, origin=p, out_count=p):
+        return lib.adypt_probe_chain_step(i(unfold), ptr(tris), i64(n_tris), ptr(mats), i(n_mats), None, i(0), i(0), p, p, p, p, i(n_px), i(segments), u32(cap), p, in_d, in_hit, p,
+                                          i(bounces), f(0.001), p, p, p, out_count, p, virt, origin)
+    for call in (start, step):
+        assert call(n_tris=0) == INVALID and call(n_tris=(1 << 20) + 1) == INVALID and call(n_mats=0) == INVALID and call(n_mats=4097) == INVALID
+        assert call(bounces=0) == INVALID and call(bounces=9) == INVALID and call(segments=0) == INVALID and call(segments=65) == INVALID and call(cap=0) == INVALID and call(cap=(1 << 20) + 1) == INVALID
+        for matid in (-33, 34):  # (a triangle's material id farther than 32 from [0, n_mats))
+            bad = tris.copy()
+            bad.view(np.int32)[2, 18] = matid
+            assert call(tris=bad) == INVALID, matid
+    assert start(tris=None) == INVALID and start(mats=None) == INVALID and start(hits=None) == INVALID and start(origin=None) == INVALID and start(state=None) == INVALID and start(counts=None) == INVALID
+    assert start(blocks=None) == INVALID and start(nb=0) == INVALID and start(nb=65) == INVALID and start(w=0) == INVALID and start(h=4097) == INVALID
+    assert start(blocks=ptr(np.array([1], np.int32))) == INVALID, "a block outside the picture's grid"
+    assert start(tex=tex, tw=0, th=3) == INVALID and start(tex=tex, tw=4, th=-1) == INVALID
+    named = mats.copy()
+    named.view(np.int32)[1, 0] = 0  # names the texture, and describes it as (0, 0, 0)
+    assert start(mats=named, tex=tex, tw=4, th=3) == INVALID, "a material that names the texture and does not describe it"
+    for word in (-33, 4 + 32, 2 ** 31 - 2, -2 ** 31):
+        hits = np.zeros(4 * 1024, np.float32)
+        hits.view(np.int32)[4 * 17] = word
+        assert start(hits=ptr(hits)) == INVALID, word
+        queue = np.zeros(4 * 16, np.float32)
+        queue.view(np.int32)[4 * 5] = word
+        assert step(in_hit=ptr(queue)) == INVALID, word
+    for word in (-33, 1024 + 32, 2 ** 31 - 2, -2 ** 31):
+        queue = np.zeros(4 * 16, np.float32)
+        queue.view(np.int32)[4 * 5 + 3] = word
+        assert step(in_d=ptr(queue)) == INVALID, word
+    assert step(n_px=0) == INVALID and step(n_px=(1 << 22) + 1) == INVALID and step(in_d=None) == INVALID and step(out_count=None) == INVALID
+    assert step(unfold=1, virt=None) == INVALID and step(unfold=1, origin=None) == INVALID

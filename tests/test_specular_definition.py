@@ -119,13 +119,17 @@ class HeaderOps:
         return out, r.astype(bool)
 
 
-@pytest.fixture(scope="module")
-def header(tmp_path_factory):
-    d = tmp_path_factory.mktemp("specular_driver")
+def build_header(d):
+    """HeaderOps over the driver compiled in the directory d"""
     src, so = str(d / "driver.cpp"), str(d / "libdriver.so")
     open(src, "w").write(DRIVER)
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-I", DEVICE, src, "-o", so])
     return HeaderOps(C.CDLL(so))
+
+
+@pytest.fixture(scope="module")
+def header(tmp_path_factory):
+    return build_header(tmp_path_factory.mktemp("specular_driver"))
 
 
 def test_header_needs_no_hip_include_and_has_no_fma_exp_or_pow():
@@ -285,3 +289,37 @@ def test_the_new_symbols_are_declared_and_bound():
         assert name in N.EXPORTS and hasattr(N.lib, name), name
     assert "typedef struct adypt_specular_params" in header and N.lib.adypt_abi_version() == 4
     assert C.sizeof(N.SpecularParams) == 4 and C.sizeof(N.DenoiseSpecular) == 56
+
+
+def assert_same_arrays(got, want, keys, tag):
+    for k in keys:
+        a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
+        differing = int((bits(a) != bits(b)).sum()) if a.dtype == np.float32 else int((a != b).sum())
+        assert differing == 0, "%s: %d words of %s differ from the numpy restatement" % (tag, differing, k)
+
+
+def test_the_probes_edge_inputs_through_the_header(header):
+    """tests/chain_edge_inputs.py — what tests/test_gpu_chain_probes.py gives k_chain_start<false> and k_chain_step<false> — with chain_at_primary,
+    chain_hit_point and chain_at_surface of the compiled header in place of numpy's: the same followed pixels, states, rays, guides and counts to the bit,
+    and every case reaches what it is named after.  The GPU run then adds only kernel against truth."""
+    from tests import chain_edge_inputs as CE
+    sc = CE.scene()
+    for picture in CE.START_PICTURES:
+        for n_blocks in (1, 2, 3):
+            for pattern in CE.START_PATTERNS:
+                case = CE.start_case(picture, n_blocks, pattern)
+                want = CE.start_truth(sc, case, False)
+                assert CE.start_reach(case, want), (picture, n_blocks, pattern)
+                assert_same_arrays(CE.start_truth(sc, case, False, ops=header), want, ("go", "hits_w", "state", "o", "d"), "start %s %d %s" % (picture, n_blocks, pattern))
+    case = CE.overflow_case()
+    want = CE.start_truth(sc, case, False)
+    assert CE.start_reach(case, want) and want["go"][:64].all() and want["go"].sum() == 64
+    assert_same_arrays(CE.start_truth(sc, case, False, ops=header), want, ("go", "hits_w", "state", "o", "d"), "start overflow")
+    for name in CE.STEP_COUNTS:
+        case = CE.step_case(name)
+        want = CE.step_truth(sc, case, False)
+        assert CE.step_reach(sc, case, want, False), name
+        got = CE.step_truth(sc, case, False, ops=header)
+        assert_same_arrays(got, want, ("albedo", "normal", "position", "hits", "state", "go"), "step " + name)
+        assert_same_arrays(dict(o=got["rays"][0], d=got["rays"][1]), dict(o=want["rays"][0], d=want["rays"][1]), ("o", "d"), "step %s: the rays" % name)
+        assert (got["escaped"], got["truncated"]) == (want["escaped"], want["truncated"])

@@ -355,3 +355,29 @@ def test_the_new_symbols_are_declared_and_bound():
             assert re.search(r"\bint %s\(" % name, header), name
             assert name in N.EXPORTS and hasattr(N.lib, name), name
     assert "typedef struct adypt_denoise_virtual" in header and C.sizeof(N.DenoiseVirtual) == 32
+
+
+def test_the_chain_probes_edge_inputs_through_the_header(lib, tmp_path):
+    """tests/chain_edge_inputs.py — what tests/test_gpu_chain_probes.py gives k_chain_start<true> and k_chain_step<true> — with the compiled header's
+    chain_at_primary, chain_hit_point, chain_at_surface, chain_start_length, chain_unfold and chain_virtual_point in place of numpy's: the same states
+    with their lengths, rays, guides and virtual points to the bit, and every case reaches what it is named after."""
+    from tests import chain_edge_inputs as CE
+    ops, lengths = SD.build_header(tmp_path), HeaderUnfold(lib)
+    sc = CE.scene()
+    for picture in CE.START_PICTURES:
+        for n_blocks in (1, 2, 3):
+            for pattern in CE.START_PATTERNS:
+                case = CE.start_case(picture, n_blocks, pattern)
+                want = CE.start_truth(sc, case, True)
+                assert CE.start_reach(case, want), (picture, n_blocks, pattern)
+                if want["go"].any():
+                    assert (want["state"][want["go"], 1, 3] > 0).all(), "a followed pixel's camera ray has a length"
+                SD.assert_same_arrays(CE.start_truth(sc, case, True, ops=ops, lengths=lengths), want, ("go", "hits_w", "state", "o", "d"), "start %s %d %s" % (picture, n_blocks, pattern))
+    for name in CE.STEP_COUNTS:
+        case = CE.step_case(name)
+        want = CE.step_truth(sc, case, True)
+        assert CE.step_reach(sc, case, want, True), name
+        got = CE.step_truth(sc, case, True, ops=ops, lengths=lengths)
+        SD.assert_same_arrays(got, want, ("albedo", "normal", "position", "hits", "state", "virt", "go"), "step " + name)
+        SD.assert_same_arrays(dict(o=got["rays"][0], d=got["rays"][1]), dict(o=want["rays"][0], d=want["rays"][1]), ("o", "d"), "step %s: the rays" % name)
+        assert (got["escaped"], got["truncated"]) == (want["escaped"], want["truncated"])
