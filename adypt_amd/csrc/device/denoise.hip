@@ -35,15 +35,18 @@
 // The host side, in the order of the file:
 //     BlockImages   the block-major images of a set of blocks on one device, named once (BlockImage) and handled in loops: the context's own set
 //                   and, on the first device of several, the merged set of all devices.  LocalImages is the view of a set the kernels are launched with
-//     History       what the last committing call left, its camera and its snapshot.  Its methods are the lifetime rule and its only writers
-//     Denoiser      everything kept per context.  While timer.completed(), `last` says what the last finished run was (LastRun; StageMarks knows where
-//                   the marks of a run of a mode stand), and rgb is its result
-//     DenoiseCall   one call, made once from the ABI structs (make_call): mode, parameters with their defaults, and the refusal if there is one
-//     run_filter    prepare (+ gather + merge) + levels (+ snapshot) of a call over a set of images; denoise_context and multi_denoise are the two fronts
+//     History       what the last committing call left, its kind (HistoryKind), its camera and its snapshot.  Its methods are the lifetime rule and
+//                   its only writers
+//     the stages    one struct per stage that only some calls have — MergeStage, MotionStage, WindowStage, MomentsStage, VirtualStage, ChainStage —
+//                   each with its buffers, its read-out flag, its timer, counters and last parameters, and the same members: ensure, enqueue,
+//                   finished, fill
+//     Denoiser      everything kept per context: the picture's images, the history, the stages.  While timer.completed(), `last` says what the last
+//                   finished run was, and rgb is its result
+//     run_filter    the steps of a call (denoise_call.hpp: DenoiseCall, made once from the ABI structs by make_call) over a set of images, in order:
+//                   prepare, [gather], [window], merge, [variance], levels, [snapshot], sync, finished; denoise_context and multi_denoise are the fronts
 #include "ctx_unit.hpp"
 #include "tile_layout.hpp"
-#include "denoise.hpp"
-#include "temporal.hpp"
+#include "denoise_call.hpp"
 #include "denoise_internal.hpp"
 #include "../../../include/adypt_hip.h"
 
@@ -61,7 +64,7 @@ namespace {
 // The block-major images of a set of blocks on one device, in the order the several-device path uploads them: the first kPixelImages hold one element
 // per local pixel, the last two one per block.  A further image is one more name here, its element type where that is not float4, its size in the table
 // and, if it is per pixel, its place in kFetchOrder.
-// kVirtual — the virtual points of adypt_denoise_temporal_specular — is allocated, fetched and uploaded by such a call only (optional_images).
+// kVirtual — the virtual points of a call by the virtual point — is allocated, fetched and uploaded by such a call only (optional_images).
 enum BlockImage { kAccum, kAlbedo, kNormal, kPosition, kHits, kMoments, kVirtual, kBlocks, kBlockSpp, kBlockImages, kPixelImages = kBlocks };
 template <BlockImage K> struct ImageElement { using type = float4; };
 template <> struct ImageElement<kMoments> { using type = float2; };
@@ -75,8 +78,9 @@ static_assert(sizeof(kBlockImageBytes) / sizeof(size_t) == kBlockImages, "every 
 constexpr BlockImage kFetchOrder[] = {kMoments, kAccum, kAlbedo, kNormal, kPosition, kHits, kVirtual};
 static_assert(sizeof(kFetchOrder) / sizeof(BlockImage) == kPixelImages, "every per-pixel image is fetched");
 constexpr unsigned kContextImages = 1u << kAccum | 1u << kMoments | 1u << kBlocks; // the images a context keeps itself (DenoiseInputs)
-// the images a call goes without — neither allocated nor moved between devices; unfold: the call is adypt_denoise_temporal_specular
-constexpr unsigned optional_images(bool unfold) { return unfold ? 0u : 1u << kVirtual; }
+// the images a call goes without — neither allocated nor moved between devices, and null in its LocalImages
+constexpr unsigned kWithoutVirtual = 1u << kVirtual;
+inline unsigned optional_images(const DenoiseCall &call) { return call.virtual_point() ? 0u : kWithoutVirtual; }
 
 // where the images of a set of n_blocks blocks lie: what the kernels are launched with
 struct LocalImages {
@@ -112,8 +116,7 @@ struct History {
 	Buffer<float4> h0, h1, h2, ha;
 	TemporalCamera camera;
 	bool present = false;
-	bool moments = false;            // which kind of call wrote it: H0.w is S (a moments call) or V.  A call finds only a history of its own kind
-	int followed = 0;                // ... and H1.w the class of a followed call with this many bounces (a truncated chain's class depends on them), or 0: the hit flag
+	HistoryKind kind;                // of the call that wrote it: a call finds only a history of its own kind
 	Buffer<float4> snapshot;
 	int64_t snapshot_tris = 0;       // the triangles the snapshot holds; 0: the history has none (a context's scene never has 0: adypt_create, adypt_set_triangles)
 	StageTimer<2> snapshot_timer;    // the copy kernel of the last commit with a snapshot
@@ -126,8 +129,7 @@ struct History {
 	// how many triangles of the snapshot the gather may trust for a scene of n_tris triangles (a snapshot of another count is none: adypt_set_triangles
 	// drops it, so this only guards)
 	int64_t known_tris(int64_t n_tris) const { return present && snapshot_tris == n_tris ? snapshot_tris : 0; }
-	// whether a call of the kind given finds it
-	bool found_by(bool moments_call, int followed_bounces = 0) const { return present && moments == moments_call && followed == followed_bounces; }
+	int found_by(const DenoiseCall &call) const { return present && kind == call.kind() ? 1 : 0; } // (the `have` of the merge kernels)
 	// The snapshot of a committing motion call: the records as they are now, enqueued on `stream` behind the call's gather, which reads the old one.  The
 	// history has none from here until the caller has waited for the stream and commits with *n_tris: a failure in between leaves every pixel unmoved.
 	int enqueue_snapshot(adypt_ctx *c, hipStream_t stream, int64_t *n_tris)
@@ -145,9 +147,9 @@ struct History {
 	}
 	// A finished call's merged image, guides (X2.w = n_out) and camera become the history: swapped in, nothing is copied, and what the history held is
 	// overwritten by the call's next prepare.  snapshot_of: what enqueue_snapshot gave; 0: the call made none, and the history has none from here.
-	void commit(Buffer<float4> &merged, Buffer<float4> &x1, Buffer<float4> &x2, Buffer<float4> &xa, const CtxCamera &cam, int64_t snapshot_of, bool of_moments, int of_followed)
+	void commit(Buffer<float4> &merged, Buffer<float4> &x1, Buffer<float4> &x2, Buffer<float4> &xa, const CtxCamera &cam, int64_t snapshot_of, const HistoryKind &of_call)
 	{
-		moments = of_moments; followed = of_followed;
+		kind = of_call;
 		std::swap(merged, h0); std::swap(x1, h1); std::swap(x2, h2); std::swap(xa, ha);
 		camera = temporal_camera(cam.origin, cam.inv_proj, cam.inv_view);
 		snapshot_tris = snapshot_of;
@@ -158,18 +160,198 @@ struct History {
 	void triangles_replaced() { snapshot_tris = 0; snapshot.release(); }
 };
 
-enum class Mode { Plain, Temporal, Motion }; // adypt_denoise, adypt_denoise_temporal, adypt_denoise_temporal_motion
-
-constexpr int kTimingEvents = 4 + kDenoiseMaxLevels; // start, guides, prepare, (the temporal merge,) every level
-
-// Where the marks of the stage timer stand in a run of a mode: 0 the start, 1 behind the guides (several devices: the upload), 2 behind prepare, then —
-// Temporal and Motion only — one behind the merge (Motion: the gather and the merge), then one behind every level.  Stage k lies between marks k, k + 1.
-struct StageMarks {
-	int merge, first_level; // merge 0: the mode has no such stage
-	explicit StageMarks(Mode m) : merge(m == Mode::Plain ? 0 : 3), first_level(m == Mode::Plain ? 3 : 4) {}
+// the filter's row-major images of the whole picture as the kernels of one call are launched with them (x0: what prepare writes and level 0 leaves)
+struct Picture {
+	float4 *x0, *x1, *x2, *xa;
+	int width, height;
+	int blocks_x() const { return (width + kBlockDim - 1) / kBlockDim; }
 };
 
-struct LastRun { Mode mode = Mode::Plain; int levels = 0; };
+// ---- the stages that only some calls have ----
+// Each keeps what its calls leave for the read-outs, and the same members.  ensure(c, n): room for a picture of n pixels, and the read-out invalid
+// from here — it is called before anything that can overwrite the stage's images is enqueued.  enqueue: the stage's kernels, on the call's stream.
+// finished(call): behind the wait for the stream; a call that has the stage makes its read-out valid and leaves its parameters and counts, a call
+// of another kind changes nothing — so a read-out answers from the first call of its kind that ran to its end, and a call that failed leaves it
+// refused until the next one has.  fill: the stage's adypt_denoise_* struct, zeroed by the caller; device_bytes whether or not a call has run.
+// Nothing outside a stage writes its `valid`.
+
+// following moved geometry (adypt_denoise_temporal_motion, the rectified and the moments call with follow_motion): XP, XN, 32 B per image pixel,
+// allocated at the first such call.  (The snapshot is the history's: it lives and dies with what was committed.)
+struct MotionStage {
+	Buffer<float4> xp, xn;
+	bool valid = false;
+	int ensure(adypt_ctx *c, size_t n) { valid = false; CTX_TRY(c, at_least(xp, n)); CTX_TRY(c, at_least(xn, n)); return ADYPT_OK; }
+	// k_motion_gather: where every pixel's hit point and normal were when the history was committed
+	int enqueue(adypt_ctx *c, hipStream_t stream, const LocalImages &in, const Picture &px, const History &h)
+	{
+		const CtxScene sc = ctx_scene(c);
+		const int n_px = in.n_blocks * kBlockPixels;
+		const LaunchShape gather = gather_launch(n_px);
+		hipLaunchKernelGGL(k_motion_gather, gather.grid, gather.block, 0, stream, in.as<kHits>(), in.as<kNormal>(), in.as<kPosition>(), in.as<kBlocks>(), n_px, px.blocks_x(), px.width, px.height,
+		                   (const float4 *)h.snapshot, h.known_tris(sc.n_tris), (const float4 *)sc.triangles, sc.tri_float4, xp.get(), xn.get());
+		CTX_TRY(c, hipGetLastError());
+		return ADYPT_OK;
+	}
+	void finished(const DenoiseCall &call) { if(call.motion) valid = true; }
+	void fill(const History &h, adypt_denoise_motion *out) const
+	{
+		out->have_snapshot = h.snapshot_tris > 0 ? 1 : 0;
+		out->n_tris = h.snapshot_tris;
+		out->device_bytes = (int64_t)(h.snapshot.bytes() + xp.bytes() + xn.bytes());
+		if(out->have_snapshot) (void)h.snapshot_timer.read(&out->snapshot_ms, 1, 1, false);
+	}
+};
+
+// rectifying stale history (rectify.hpp): R0, R1 and the kept read-out, 36 B per image pixel, allocated at the first rectified call; the parameters and
+// the window kernel's time of the last one
+struct WindowStage {
+	Buffer<float4> r0, r1;
+	Buffer<float> kept;
+	bool valid = false;
+	int radius = 0; float gamma = 0.0f;
+	StageTimer<2> timer;
+	int ensure(adypt_ctx *c, size_t n) { valid = false; CTX_TRY(c, at_least(r0, n)); CTX_TRY(c, at_least(r1, n)); CTX_TRY(c, at_least(kept, n)); return ADYPT_OK; }
+	// k_rectify_window<call.radius>: the window statistics of the call's own images, which the merge then clamps the history to
+	int enqueue(adypt_ctx *c, hipStream_t stream, const Picture &px, const RectifyOrigin &origin, const DenoiseCall &call)
+	{
+		const LaunchShape shape = window_launch(px.width, px.height);
+		CTX_TRY(c, timer.mark(0, stream));
+		hipLaunchKernelGGL(window_instance(call.radius), shape.grid, shape.block, 0, stream, (const float4 *)px.x0, (const float4 *)px.x1, (const float4 *)px.x2, (const float4 *)px.xa, r0.get(), r1.get(),
+		                   px.width, px.height, origin);
+		CTX_TRY(c, hipGetLastError());
+		CTX_TRY(c, timer.mark(1, stream));
+		return ADYPT_OK;
+	}
+	void finished(const DenoiseCall &call) { if(call.rectify) { valid = true; radius = call.radius; gamma = call.gamma; } }
+	void fill(adypt_denoise_rectify *out) const
+	{
+		out->device_bytes = (int64_t)(r0.bytes() + r1.bytes() + kept.bytes());
+		if(!valid) return;
+		out->have = 1;
+		out->radius = radius; out->gamma = gamma;
+		(void)timer.read(&out->window_ms, 1, 1, false);
+	}
+};
+
+// variance from temporal moments (moments.hpp): the variance read-out, 4 B per image pixel, and the counters of the pixels that took the window
+// estimate (512 B), allocated at the first moments call; the count and the variance kernel's time of the last one
+struct MomentsStage {
+	Buffer<float> variance;
+	Buffer<unsigned long long> count;
+	bool valid = false;
+	int64_t pixels_spatial = 0;
+	unsigned long long readback[kMomentsCountSlots] = {}; // where the running call's counters are copied to (a member: the copy is enqueued, and outlives a call that fails behind it)
+	StageTimer<2> timer;
+	int ensure(adypt_ctx *c, size_t n) { valid = false; CTX_TRY(c, at_least(variance, n)); CTX_TRY(c, at_least(count, kMomentsCountSlots)); return ADYPT_OK; }
+	// k_moments_variance: (D, V) of the merged (D, S) into X0, which the merge has read and the first level reads; the merged image itself stays for the commit
+	int enqueue(adypt_ctx *c, hipStream_t stream, const Picture &px, const float4 *merged, const RectifyOrigin &origin)
+	{
+		const LaunchShape shape = variance_launch(px.width, px.height);
+		CTX_TRY(c, hipMemsetAsync(count.get(), 0, sizeof(readback), stream));
+		CTX_TRY(c, timer.mark(0, stream));
+		hipLaunchKernelGGL(k_moments_variance, shape.grid, shape.block, 0, stream, merged, (const float4 *)px.x1, (const float4 *)px.x2, (const float4 *)px.xa, px.x0, variance.get(), count.get(), px.width,
+		                   px.height, origin);
+		CTX_TRY(c, hipGetLastError());
+		CTX_TRY(c, timer.mark(1, stream));
+		CTX_TRY(c, hipMemcpyAsync(readback, count.get(), sizeof(readback), hipMemcpyDeviceToHost, stream));
+		return ADYPT_OK;
+	}
+	void finished(const DenoiseCall &call)
+	{
+		if(!call.moments) return;
+		valid = true;
+		pixels_spatial = 0;
+		for(const unsigned long long n_slot : readback) pixels_spatial += (int64_t)n_slot;
+	}
+	void fill(adypt_denoise_moments *out) const
+	{
+		out->device_bytes = (int64_t)(variance.bytes() + count.bytes());
+		if(!valid) return;
+		out->have = 1;
+		out->pixels_spatial = pixels_spatial;
+		(void)timer.read(&out->variance_ms, 1, 1, false);
+	}
+};
+
+// the temporal merge by the virtual point: XV, 16 B per image pixel, and the counters (1 KiB), allocated at the first such call (the block-major
+// virtual points, 16 B per local pixel, are the block-image sets' kVirtual); the bounces and the counts of the last one
+struct VirtualStage {
+	Buffer<float4> xv;
+	Buffer<unsigned long long> count;
+	bool valid = false;
+	int bounces = 0;
+	int64_t followed = 0, with_history = 0;
+	unsigned long long readback[2 * kVirtualCountSlots] = {}; // (a member, as MomentsStage's)
+	int ensure(adypt_ctx *c, size_t n) { valid = false; CTX_TRY(c, at_least(xv, n)); CTX_TRY(c, at_least(count, 2 * kVirtualCountSlots)); return ADYPT_OK; }
+	// k_temporal_merge_virtual: such a call's merge, into `merged` and `length`
+	int enqueue(adypt_ctx *c, hipStream_t stream, const Picture &px, const History &h, const DenoiseCall &call, float4 *merged, float *length)
+	{
+		const LaunchShape shape = merge_launch(px.width, px.height);
+		CTX_TRY(c, hipMemsetAsync(count.get(), 0, sizeof(readback), stream));
+		hipLaunchKernelGGL(k_temporal_merge_virtual, shape.grid, shape.block, 0, stream, (const float4 *)px.x0, (const float4 *)px.x1, px.x2, (const float4 *)px.xa, (const float4 *)xv, (const float4 *)h.h0,
+		                   (const float4 *)h.h1, (const float4 *)h.h2, (const float4 *)h.ha, merged, length, px.width, px.height, h.found_by(call), h.camera, call.history_cap, count.get());
+		CTX_TRY(c, hipMemcpyAsync(readback, count.get(), sizeof(readback), hipMemcpyDeviceToHost, stream));
+		return ADYPT_OK;
+	}
+	void finished(const DenoiseCall &call)
+	{
+		if(!call.virtual_point()) return;
+		valid = true; bounces = call.bounces;
+		followed = with_history = 0;
+		for(int k = 0; k < kVirtualCountSlots; ++k) { followed += (int64_t)readback[2 * k]; with_history += (int64_t)readback[2 * k + 1]; }
+	}
+	// block_major_bytes: of the virtual points the context's block-image sets hold
+	void fill(size_t block_major_bytes, adypt_denoise_virtual *out) const
+	{
+		out->device_bytes = (int64_t)(block_major_bytes + xv.bytes() + count.bytes());
+		if(!valid) return;
+		out->have = 1; out->bounces = bounces;
+		out->pixels_followed = followed; out->pixels_with_history = with_history;
+	}
+};
+
+// every call with history: the merged image of the call and the length read-out, 20 B per image pixel, allocated at the first such call
+struct MergeStage {
+	Buffer<float4> xm;
+	Buffer<float> length;
+	bool valid = false;
+	int ensure(adypt_ctx *c, size_t n) { valid = false; CTX_TRY(c, at_least(xm, n)); CTX_TRY(c, at_least(length, n)); return ADYPT_OK; }
+	// the merge of the call's form: by the virtual point, of a moments call, or k_temporal_merge<call.motion, call.rectify>.  (An instance never looks at
+	// the images of a stage its call has not: they may be null.)
+	int enqueue(adypt_ctx *c, hipStream_t stream, const Picture &px, const History &h, const DenoiseCall &call, const MotionStage &motion, const WindowStage &window, VirtualStage &virt)
+	{
+		if(call.virtual_point()) CTX_STEP(virt.enqueue(c, stream, px, h, call, xm.get(), length.get()));
+		else
+		{
+			const LaunchShape shape = merge_launch(px.width, px.height);
+			if(call.moments)
+				hipLaunchKernelGGL(merge_moments_instance(call.motion), shape.grid, shape.block, 0, stream, (const float4 *)px.x0, (const float4 *)px.x1, px.x2, (const float4 *)px.xa, (const float4 *)h.h0,
+				                   (const float4 *)h.h1, (const float4 *)h.h2, (const float4 *)h.ha, xm.get(), length.get(), px.width, px.height, h.found_by(call), h.camera, call.history_cap,
+				                   (const float4 *)motion.xp, (const float4 *)motion.xn);
+			else
+				hipLaunchKernelGGL(merge_instance(call.motion, call.rectify), shape.grid, shape.block, 0, stream, (const float4 *)px.x0, (const float4 *)px.x1, px.x2, (const float4 *)px.xa, (const float4 *)h.h0,
+				                   (const float4 *)h.h1, (const float4 *)h.h2, (const float4 *)h.ha, xm.get(), length.get(), px.width, px.height, h.found_by(call), h.camera, call.history_cap,
+				                   (const float4 *)motion.xp, (const float4 *)motion.xn, (const float4 *)window.r0, (const float4 *)window.r1, window.kept.get(), call.gamma);
+		}
+		CTX_TRY(c, hipGetLastError());
+		return ADYPT_OK;
+	}
+	void finished(const DenoiseCall &call) { if(call.history) valid = true; }
+};
+
+// following mirrors and glass (guide_chain.hpp): the chain's state, 32 B per local pixel, and its counters, allocated at the first call or guide
+// read-out with bounces; the bounces of the last one (0: none has been enqueued) and the time of its chain stage.  It has no `valid` and no finished:
+// its counters stay on the device, and fill reads them behind whatever the context's stream still holds.  enqueue: enqueue_chain below.
+struct ChainStage {
+	Buffer<float4> state;
+	Buffer<ChainCounts> counts;
+	int bounces = 0;
+	StageTimer<2> timer;
+	int ensure(adypt_ctx *c, size_t n_local_px) { CTX_TRY(c, at_least(state, n_local_px * 2)); CTX_TRY(c, at_least(counts, 1)); return ADYPT_OK; }
+	int fill(adypt_ctx *c, adypt_denoise_specular_info *out) const;
+};
+
+struct LastRun { bool history = false; int levels = 0; };
 
 // Everything the denoiser keeps per context; parked in the context (ctx_attachment), freed by adypt_destroy (the context's device is current then).
 struct Denoiser {
@@ -178,49 +360,35 @@ struct Denoiser {
 	// the filter's row-major images of the whole picture: 80 B + 12 B (the result) per image pixel
 	Buffer<float4> x0[2], x1, x2, xa;
 	Buffer<float> rgb;
-	StageTimer<kTimingEvents> timer; // completed: the last filter ran to its end, rgb is its result and `last` says what it was
+	StageTimer<kDenoiseTimingEvents> timer; // completed: the last filter ran to its end, rgb is its result and `last` says what it was
 	LastRun last;
-	// the temporal merge, allocated at the first temporal call only: the merged image of the call and the length read-out (20 B per image pixel), and the history
-	Buffer<float4> xm;
-	Buffer<float> length;
-	bool length_valid = false; // a temporal call has run to its end since `length` was allocated, and none has failed over it since: calls of other modes leave it
-	History history;
-	// following moved geometry: XP, XN, 32 B per image pixel, allocated at the first motion call
-	Buffer<float4> xp, xn;
-	bool xp_valid = false; // as length_valid, of a motion call and XP, XN
-	// rectifying stale history: R0, R1 and the kept read-out, 36 B per image pixel, allocated at the first rectified call; nothing of it outlives a call
-	// but the read-outs: the parameters and the window kernel's time of the last rectified call
-	Buffer<float4> r0, r1;
-	Buffer<float> kept;
-	bool kept_valid = false; // as length_valid, of a rectified call and `kept`
-	int rectify_radius = 0; float rectify_gamma = 0.0f;
-	StageTimer<2> window_timer;
-	// following mirrors and glass (guide_chain.hpp): the chain's state, 32 B per local pixel, and its counters, allocated at the first such call; the
-	// bounces of the last one (0: none has been enqueued) and the time of its chain stage
-	Buffer<float4> chain_state;
-	Buffer<ChainCounts> chain_counts;
-	int chain_bounces = 0;
-	StageTimer<2> chain_timer;
-
-	// the temporal merge by the virtual point: XV, 16 B per image pixel, and the counters (1 KiB), allocated at the first adypt_denoise_temporal_specular
-	// (the block-major virtual points, 16 B per local pixel, are own / merged's kVirtual); the bounces and the counts of the last one
-	Buffer<float4> xv;
-	Buffer<unsigned long long> virtual_count;
-	bool xv_valid = false; // as length_valid, of such a call and XV
-	int virtual_bounces = 0;
-	int64_t virtual_followed = 0, virtual_with_history = 0;
-	unsigned long long virtual_readback[2 * kVirtualCountSlots] = {}; // (a member, as spatial_readback)
-
-	// variance from temporal moments (moments.hpp): the variance read-out, 4 B per image pixel, and the counters of the pixels that took the window estimate (512 B),
-	// allocated at the first moments call; the count and the variance kernel's time of the last one
-	Buffer<float> variance;
-	Buffer<unsigned long long> spatial_count;
-	bool variance_valid = false; // as length_valid, of a moments call and `variance`
-	int64_t pixels_spatial = 0;
-	unsigned long long spatial_readback[kMomentsCountSlots] = {}; // where the running call's counters are copied to (a member: the copy is enqueued, and outlives a call that fails behind it)
-	StageTimer<2> variance_timer;
+	History history; // allocated at the first call with history
+	MergeStage merge;
+	MotionStage motion;
+	WindowStage window;
+	MomentsStage moments;
+	VirtualStage virt;
+	ChainStage chain;
 
 	size_t pixels() const { return (size_t)width * (size_t)height; }
+	// room for what the call's stages write (and for the history they read); their read-outs are invalid from here until the call is finished
+	int ensure_stages(adypt_ctx *c, const DenoiseCall &call)
+	{
+		const size_t n = pixels();
+		if(call.history) { CTX_STEP(merge.ensure(c, n)); CTX_STEP(history.ensure(c, n)); }
+		if(call.motion) CTX_STEP(motion.ensure(c, n));
+		if(call.rectify) CTX_STEP(window.ensure(c, n));
+		if(call.moments) CTX_STEP(moments.ensure(c, n));
+		if(call.virtual_point()) CTX_STEP(virt.ensure(c, n));
+		return ADYPT_OK;
+	}
+	// the call's stream has been waited for
+	void finished(const DenoiseCall &call)
+	{
+		last = LastRun{call.history, call.prm.levels};
+		timer.complete();
+		merge.finished(call); motion.finished(call); window.finished(call); moments.finished(call); virt.finished(call);
+	}
 };
 
 Denoiser *denoiser_of(adypt_ctx *c) { return ctx_state<Denoiser>(c, kAttachDenoise); }
@@ -235,215 +403,60 @@ int ensure_filter_images(adypt_ctx *c, Denoiser *d, const CtxInfo &i)
 	return ADYPT_OK;
 }
 
-// one call: what the three entry points of a front differ in, and what they are given
-struct DenoiseCall {
-	DenoiseParams prm;
-	Mode mode;
-	float history_cap; bool commit; // of Temporal and Motion; a Plain call commits nothing
-	bool rectify; int radius; float gamma; // of Temporal and Motion: the history is rectified (rectify.hpp)
-	const char *fn;
-	std::string refused;            // why the arguments are refused; empty: they are not
-	int bounces = 0;                // adypt_denoise_specular: the guides follow mirrors and glass for this many bounces; 0: the primary hit's guides
-	bool moments = false;           // of Temporal and Motion: the variance comes from temporal luminance moments (moments.hpp); never rectified
-	bool unfold = false;            // adypt_denoise_temporal_specular: a Temporal call with followed guides (bounces > 0) that merges by the virtual point
-	int min_spp() const { return moments ? 1 : 2; } // the samples every block has to hold: V0 of denoise_prepare is not defined below 2, S0 is from 1
-};
-
-// the call of the ABI structs (null: the defaults — 5 levels, 4.0, 0.1; cap 64, committing; radius 3, gamma 1); tp is looked at by Temporal and Motion
-// only, rp by a rectified call (`rectify`) only
-DenoiseCall make_call(Mode mode, const char *fn, const adypt_denoise_params *p, const adypt_temporal_params *tp, bool rectify = false, const adypt_rectify_params *rp = nullptr)
-{
-	const bool with_history = mode != Mode::Plain;
-	DenoiseCall call{p ? DenoiseParams{p->levels, p->sigma_l, p->sigma_z} : kDenoiseDefaults, mode, kTemporalDefaultCap, with_history, with_history && rectify, kRectifyDefaultRadius,
-	                 kRectifyDefaultGamma, fn, {}};
-	if(with_history && tp) { call.history_cap = tp->history_cap; call.commit = tp->commit != 0; }
-	if(call.rectify && rp) { call.radius = rp->radius; call.gamma = rp->gamma; }
-	if(!denoise_params_valid(call.prm))
-		call.refused = std::string(fn) + ": levels must be in [1, " + std::to_string(kDenoiseMaxLevels) + "], sigma_l and sigma_z positive numbers";
-	else if(with_history && !temporal_cap_valid(call.history_cap)) call.refused = std::string(fn) + ": history_cap must be a positive finite number";
-	else if(call.rectify && !rectify_params_valid(call.radius, call.gamma))
-		call.refused = std::string(fn) + ": the rectify radius must be in [1, " + std::to_string(kRectifyMaxRadius) + "], gamma a finite number that is not negative";
-	return call;
-}
-
-// adypt_denoise_specular's call: a Plain call with followed guides
-DenoiseCall make_specular_call(const char *fn, const adypt_denoise_params *p, const adypt_specular_params *sp)
-{
-	DenoiseCall call = make_call(Mode::Plain, fn, p, nullptr);
-	if(!call.refused.empty()) return call;
-	if(!sp) call.refused = std::string(fn) + ": specular is null";
-	else if(!chain_bounces_valid(sp->bounces)) call.refused = std::string(fn) + ": bounces must be in [1, " + std::to_string(kChainMaxBounces) + "]";
-	else call.bounces = sp->bounces;
-	return call;
-}
-
-// adypt_denoise_temporal_specular's call: a Temporal call with followed guides; adypt_denoise_temporal's refusals, then adypt_denoise_specular's
-DenoiseCall make_virtual_call(const char *fn, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_specular_params *sp)
-{
-	DenoiseCall call = make_call(Mode::Temporal, fn, p, tp);
-	if(!call.refused.empty()) return call;
-	if(!sp) call.refused = std::string(fn) + ": specular is null";
-	else if(!chain_bounces_valid(sp->bounces)) call.refused = std::string(fn) + ": bounces must be in [1, " + std::to_string(kChainMaxBounces) + "]";
-	else { call.bounces = sp->bounces; call.unfold = true; }
-	return call;
-}
-
-// adypt_denoise_temporal_moments' call: a Temporal or Motion call whose fourth channel is S (it has no rectified form: the clamp would move the colour
-// and leave S inconsistent with it — and none with followed guides: make_virtual_call has no moments form)
-DenoiseCall make_moments_call(const char *fn, const adypt_denoise_params *p, const adypt_temporal_params *tp, int follow_motion)
-{
-	DenoiseCall call = make_call(follow_motion ? Mode::Motion : Mode::Temporal, fn, p, tp);
-	call.moments = true;
-	return call;
-}
-
-// prepare (+ the gather + the temporal merge) + the levels (+ the snapshot) of a call, on `stream`; d's images are the whole picture's
-// (ensure_filter_images), `cam` the camera of the context the guides were captured by
+// The steps of a call on `stream`, none of which waits for the host until the end; d's images are the whole picture's (ensure_filter_images), `cam`
+// the camera of the context the guides were captured by.  A step in brackets is a stage only some calls have.
 int run_filter(adypt_ctx *c, Denoiser *d, hipStream_t stream, const LocalImages &in, const DenoiseCall &call, const CtxCamera &cam)
 {
-	const bool with_history = call.mode != Mode::Plain, with_motion = call.mode == Mode::Motion;
-	const DenoiseParams &prm = call.prm;
 	History &h = d->history;
-	const size_t n = d->pixels();
-	if(with_history) { CTX_TRY(c, at_least(d->xm, n)); CTX_STEP(h.ensure(c, n)); CTX_TRY(c, at_least(d->length, n)); }
-	if(with_motion)
-	{
-		CTX_TRY(c, at_least(d->xp, n)); CTX_TRY(c, at_least(d->xn, n));
-		d->xp_valid = false;
-	}
-	if(call.rectify)
-	{
-		CTX_TRY(c, at_least(d->r0, n)); CTX_TRY(c, at_least(d->r1, n)); CTX_TRY(c, at_least(d->kept, n));
-		d->kept_valid = false;
-	}
-	if(call.moments)
-	{
-		CTX_TRY(c, at_least(d->variance, n)); CTX_TRY(c, at_least(d->spatial_count, kMomentsCountSlots));
-		d->variance_valid = false;
-	}
-	if(call.unfold)
-	{
-		CTX_TRY(c, at_least(d->xv, n)); CTX_TRY(c, at_least(d->virtual_count, 2 * kVirtualCountSlots));
-		d->xv_valid = false;
-	}
-	const int width = d->width, height = d->height, n_px = in.n_blocks * kBlockPixels;
-	const int blocks_x = (width + kBlockDim - 1) / kBlockDim;
-	const int32_t *blocks = in.as<kBlocks>();
-	const float4 *normal = in.as<kNormal>(), *position = in.as<kPosition>(), *hits = in.as<kHits>();
+	CTX_STEP(d->ensure_stages(c, call));
+	const Picture px{d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get(), d->width, d->height};
+	const RectifyOrigin origin{{cam.origin[0], cam.origin[1], cam.origin[2]}};
+	const int n_px = in.n_blocks * kBlockPixels;
+	// prepare (followed guides: X1.w is the class the chain left in the .w of the primary-hit image; by the virtual point: XV beside the four)
 	const LaunchShape prepare = prepare_launch(n_px);
-	// (followed guides: X1.w is the class the chain left in the .w of the primary-hit image)
-	if(call.unfold)
-		hipLaunchKernelGGL(k_denoise_prepare_virtual, prepare.grid, prepare.block, 0, stream, in.as<kAccum>(), in.as<kMoments>(), blocks, in.as<kBlockSpp>(), n_px, blocks_x, width, height,
-		                   in.as<kAlbedo>(), normal, position, hits, d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get(), in.as<kVirtual>(), d->xv.get());
+	if(call.virtual_point())
+		hipLaunchKernelGGL(k_denoise_prepare_virtual, prepare.grid, prepare.block, 0, stream, in.as<kAccum>(), in.as<kMoments>(), in.as<kBlocks>(), in.as<kBlockSpp>(), n_px, px.blocks_x(), px.width, px.height,
+		                   in.as<kAlbedo>(), in.as<kNormal>(), in.as<kPosition>(), in.as<kHits>(), px.x0, px.x1, px.x2, px.xa, in.as<kVirtual>(), d->virt.xv.get());
 	else
-	hipLaunchKernelGGL(call.moments ? k_denoise_prepare_moments : call.bounces > 0 ? k_denoise_prepare_class : k_denoise_prepare, prepare.grid, prepare.block, 0, stream, in.as<kAccum>(), in.as<kMoments>(), blocks, in.as<kBlockSpp>(), n_px, blocks_x, width, height,
-	                   in.as<kAlbedo>(), normal, position, hits, d->x0[0].get(), d->x1.get(), d->x2.get(), d->xa.get());
+		hipLaunchKernelGGL(prepare_instance(call.moments, call.bounces > 0), prepare.grid, prepare.block, 0, stream, in.as<kAccum>(), in.as<kMoments>(), in.as<kBlocks>(), in.as<kBlockSpp>(), n_px, px.blocks_x(),
+		                   px.width, px.height, in.as<kAlbedo>(), in.as<kNormal>(), in.as<kPosition>(), in.as<kHits>(), px.x0, px.x1, px.x2, px.xa);
 	CTX_TRY(c, hipGetLastError());
 	CTX_TRY(c, d->timer.mark(2, stream));
-	const LaunchShape window_shape = window_launch(width, height), merge_shape = merge_launch(width, height), level_shape = atrous_launch(width, height);
-	const StageMarks marks(call.mode);
-	if(with_history)
+	const StageMarks marks = call.marks();
+	if(call.history)
 	{
-		d->length_valid = false;
-		if(with_motion)
-		{
-			const CtxScene sc = ctx_scene(c);
-			const LaunchShape gather = gather_launch(n_px);
-			hipLaunchKernelGGL(k_motion_gather, gather.grid, gather.block, 0, stream, hits, normal, position, blocks, n_px, blocks_x, width, height, (const float4 *)h.snapshot,
-			                   h.known_tris(sc.n_tris), (const float4 *)sc.triangles, sc.tri_float4, d->xp.get(), d->xn.get());
-			CTX_TRY(c, hipGetLastError());
-		}
-		if(call.rectify)
-		{
-			const auto window = call.radius == 1 ? k_rectify_window<1> : call.radius == 2 ? k_rectify_window<2> : k_rectify_window<3>;
-			static_assert(kRectifyMaxRadius == 3, "one instance of k_rectify_window per radius");
-			RectifyOrigin origin;
-			for(int k = 0; k < 3; ++k) origin.o[k] = cam.origin[k];
-			CTX_TRY(c, d->window_timer.mark(0, stream));
-			hipLaunchKernelGGL(window, window_shape.grid, window_shape.block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, d->r0.get(), d->r1.get(), width, height,
-			                   origin);
-			CTX_TRY(c, hipGetLastError());
-			CTX_TRY(c, d->window_timer.mark(1, stream));
-		}
-		const auto merge = call.rectify ? (with_motion ? k_temporal_merge<true, true> : k_temporal_merge<false, true>) : (with_motion ? k_temporal_merge<true, false> : k_temporal_merge<false, false>);
-		if(call.unfold)
-		{
-			CTX_TRY(c, hipMemsetAsync(d->virtual_count.get(), 0, sizeof(d->virtual_readback), stream));
-			hipLaunchKernelGGL(k_temporal_merge_virtual, merge_shape.grid, merge_shape.block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, d->x2.get(), (const float4 *)d->xa, (const float4 *)d->xv,
-			                   (const float4 *)h.h0, (const float4 *)h.h1, (const float4 *)h.h2, (const float4 *)h.ha, d->xm.get(), d->length.get(), width, height,
-			                   h.found_by(false, call.bounces) ? 1 : 0, h.camera, call.history_cap, d->virtual_count.get());
-			CTX_TRY(c, hipMemcpyAsync(d->virtual_readback, d->virtual_count.get(), sizeof(d->virtual_readback), hipMemcpyDeviceToHost, stream));
-		}
-		else if(call.moments)
-		{
-			hipLaunchKernelGGL(with_motion ? k_temporal_merge_moments<true> : k_temporal_merge_moments<false>, merge_shape.grid, merge_shape.block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1,
-			                   d->x2.get(), (const float4 *)d->xa, (const float4 *)h.h0, (const float4 *)h.h1, (const float4 *)h.h2, (const float4 *)h.ha, d->xm.get(), d->length.get(), width, height,
-			                   h.found_by(true) ? 1 : 0, h.camera, call.history_cap, (const float4 *)d->xp, (const float4 *)d->xn);
-		}
-		else
-		{
-			hipLaunchKernelGGL(merge, merge_shape.grid, merge_shape.block, 0, stream, (const float4 *)d->x0[0], (const float4 *)d->x1, d->x2.get(), (const float4 *)d->xa, (const float4 *)h.h0, (const float4 *)h.h1,
-			                   (const float4 *)h.h2, (const float4 *)h.ha, d->xm.get(), d->length.get(), width, height, h.found_by(false) ? 1 : 0, h.camera, call.history_cap, (const float4 *)d->xp,
-			                   (const float4 *)d->xn, (const float4 *)d->r0, (const float4 *)d->r1, d->kept.get(), call.gamma);
-		}
-		CTX_TRY(c, hipGetLastError());
-		if(call.moments)
-		{
-			// (D, V) of the merged (D, S) into X0[0], which the merge has read and the first level reads; the merged image itself stays for the commit
-			RectifyOrigin origin;
-			for(int k = 0; k < 3; ++k) origin.o[k] = cam.origin[k];
-			const LaunchShape variance_shape = variance_launch(width, height);
-			CTX_TRY(c, hipMemsetAsync(d->spatial_count.get(), 0, sizeof(d->spatial_readback), stream));
-			CTX_TRY(c, d->variance_timer.mark(0, stream));
-			hipLaunchKernelGGL(k_moments_variance, variance_shape.grid, variance_shape.block, 0, stream, (const float4 *)d->xm, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, d->x0[0].get(),
-			                   d->variance.get(), d->spatial_count.get(), width, height, origin);
-			CTX_TRY(c, hipGetLastError());
-			CTX_TRY(c, d->variance_timer.mark(1, stream));
-			CTX_TRY(c, hipMemcpyAsync(d->spatial_readback, d->spatial_count.get(), sizeof(d->spatial_readback), hipMemcpyDeviceToHost, stream));
-		}
+		if(call.motion) CTX_STEP(d->motion.enqueue(c, stream, in, px, h));                           // [gather]
+		if(call.rectify) CTX_STEP(d->window.enqueue(c, stream, px, origin, call));                   // [window]
+		CTX_STEP(d->merge.enqueue(c, stream, px, h, call, d->motion, d->window, d->virt));           // merge
+		if(call.moments) CTX_STEP(d->moments.enqueue(c, stream, px, d->merge.xm.get(), origin));     // [variance]
 		CTX_TRY(c, d->timer.mark(marks.merge, stream));
 	}
+	const LaunchShape level_shape = atrous_launch(px.width, px.height);
+	const DenoiseParams &prm = call.prm;
 	for(int l = 0; l < prm.levels; ++l)
 	{
-		const float4 *src = (l == 0 && with_history && !call.moments) ? d->xm : d->x0[l & 1];
+		const float4 *src = l == 0 && call.levels_read_merged() ? d->merge.xm : d->x0[l & 1];
 		float4 *dst = d->x0[(l & 1) ^ 1];
-		const auto level = l == prm.levels - 1 ? k_atrous<true> : k_atrous<false>;
-		hipLaunchKernelGGL(level, level_shape.grid, level_shape.block, 0, stream, src, (const float4 *)d->x1, (const float4 *)d->x2, (const float4 *)d->xa, dst, d->rgb.get(), width, height, 1 << l, prm.sigma_l, prm.sigma_z);
+		hipLaunchKernelGGL(atrous_instance(l == prm.levels - 1), level_shape.grid, level_shape.block, 0, stream, src, (const float4 *)px.x1, (const float4 *)px.x2, (const float4 *)px.xa, dst, d->rgb.get(), px.width, px.height, 1 << l, prm.sigma_l, prm.sigma_z);
 		CTX_TRY(c, hipGetLastError());
 		CTX_TRY(c, d->timer.mark(marks.first_level + l, stream));
 	}
 	int64_t snapshot_of = 0;
-	if(with_motion && call.commit) CTX_STEP(h.enqueue_snapshot(c, stream, &snapshot_of));
+	if(call.motion && call.commit) CTX_STEP(h.enqueue_snapshot(c, stream, &snapshot_of));            // [snapshot]
 	CTX_TRY(c, hipStreamSynchronize(stream));
-	d->last = LastRun{call.mode, prm.levels};
-	d->timer.complete();
-	if(with_history) d->length_valid = true;
-	if(with_motion) d->xp_valid = true;
-	if(call.rectify) { d->kept_valid = true; d->rectify_radius = call.radius; d->rectify_gamma = call.gamma; }
-	if(call.moments)
-	{
-		d->variance_valid = true;
-		d->pixels_spatial = 0;
-		for(const unsigned long long n_slot : d->spatial_readback) d->pixels_spatial += (int64_t)n_slot;
-	}
-	if(call.unfold)
-	{
-		d->xv_valid = true; d->virtual_bounces = call.bounces;
-		d->virtual_followed = d->virtual_with_history = 0;
-		for(int k = 0; k < kVirtualCountSlots; ++k) { d->virtual_followed += (int64_t)d->virtual_readback[2 * k]; d->virtual_with_history += (int64_t)d->virtual_readback[2 * k + 1]; }
-	}
-	if(call.commit) h.commit(d->xm, d->x1, d->x2, d->xa, cam, snapshot_of, call.moments, call.unfold ? call.bounces : 0);
+	d->finished(call);
+	if(call.commit) h.commit(d->merge.xm, d->x1, d->x2, d->xa, cam, snapshot_of, call.kind());
 	return ADYPT_OK;
 }
 
 // The stage times of the last finished run.  ms, where `capacity` holds them: guides, prepare and every level, adypt_get_denoise_timing's layout
-// whatever the mode (returns their number); merge_ms, where not null: the merge's stage, which stands between prepare's and the first level's.
+// with or without history (returns their number); merge_ms, where not null: the merge's stage, which stands between prepare's and the first level's.
 int read_stages(const Denoiser *d, float *ms, int capacity, float *merge_ms)
 {
-	const StageMarks marks(d->last.mode);
+	const StageMarks marks = stage_marks(d->last.history);
 	const int n = 2 + d->last.levels;
-	float all[kTimingEvents];
-	d->timer.read(all, kTimingEvents, marks.first_level - 1 + d->last.levels, false);
+	float all[kDenoiseTimingEvents];
+	d->timer.read(all, kDenoiseTimingEvents, marks.first_level - 1 + d->last.levels, false);
 	if(merge_ms) *merge_ms = marks.merge ? all[marks.merge - 1] : 0.0f;
 	if(capacity < n) return n;
 	for(int k = 0; k < n; ++k) ms[k] = all[k < 2 ? k : k + marks.first_level - 3];
@@ -451,12 +464,12 @@ int read_stages(const Denoiser *d, float *ms, int capacity, float *merge_ms)
 }
 
 // the context's own set, for `in` = ctx_denoise_inputs(c): the kContextImages are the context's (moments null while it keeps no noise statistics, which
-// only the guide read-out goes without), the guides and the sample counts the denoiser's
-int own_images(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, LocalImages *v, bool unfold = false)
+// only the guide read-out goes without), the guides and the sample counts the denoiser's; left_out: optional_images of the call
+int own_images(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, LocalImages *v, unsigned left_out = kWithoutVirtual)
 {
 	*v = LocalImages{{}, in.n_blocks};
 	v->image[kAccum] = in.accum; v->image[kMoments] = in.moments; v->image[kBlocks] = in.blocks;
-	return d->own.fill(c, v, kContextImages | optional_images(unfold));
+	return d->own.fill(c, v, kContextImages | left_out);
 }
 
 // The chain through mirrors and glass over the context's own blocks (guide_chain.hpp), enqueued behind the guide capture on the context's stream
@@ -464,16 +477,17 @@ int own_images(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, LocalImages *
 // other queue.  Every round is enqueued whether it has rays or not: an empty round measures 0.05 ms (two launches that read eight counters), and
 // stopping at the first one would need a count read back — a host sync in a call that has none until its end (that form is not built).
 // The queues have been asked for (ctx_ray_queues) before the capture was enqueued.
-// unfold: the unfolding instances, which also leave the virtual points in the set's kVirtual (the same queues, segments and capacity check).
-int enqueue_chain(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, int bounces, const CtxRayQueues &q, bool unfold)
+// Where the set `own` has room for virtual points (a call by the virtual point: optional_images) the unfolding instances run, which also leave them
+// there (the same queues, segments and capacity check).
+int enqueue_chain(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, int bounces, const CtxRayQueues &q, const LocalImages &own)
 {
 	const CtxInfo i = ctx_info(c);
 	const int n_px = in.n_blocks * kBlockPixels;
 	const LaunchShape start = chain_start_launch(n_px);
 	const uint32_t per_segment = ((start.grid.x + (unsigned)q.segments - 1) / (unsigned)q.segments) * kPixelThreads; // the most rays a segment is given
 	if(per_segment > q.seg_cap || bounces + 1 > q.rounds) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the context's ray queues cannot hold the chain's rays");
-	CTX_TRY(c, at_least(d->chain_state, (size_t)n_px * 2));
-	CTX_TRY(c, at_least(d->chain_counts, 1));
+	ChainStage &chain = d->chain;
+	CTX_STEP(chain.ensure(c, (size_t)n_px));
 	const CtxScene scene = ctx_scene(c);
 	const CtxMaterials mats = ctx_materials(c);
 	const CtxCamera cam = ctx_camera(c);
@@ -482,34 +496,35 @@ int enqueue_chain(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char
 	const ChainOrigin origin{{cam.origin[0], cam.origin[1], cam.origin[2]}, q.tmin};
 	auto queue = [&q](int parity, int round) { return ChainQueue{q.o[parity], q.d[parity], q.count + (size_t)round * q.round_stride, q.seg_cap, q.seg_stride, q.segments}; };
 	const int blocks_x = (i.width + kBlockDim - 1) / kBlockDim;
-	d->chain_bounces = bounces;
-	CTX_TRY(c, hipMemsetAsync(d->chain_counts.get(), 0, sizeof(ChainCounts), i.stream));
-	CTX_TRY(c, d->chain_timer.mark(0, i.stream));
-	hipLaunchKernelGGL(unfold ? k_chain_start<true> : k_chain_start<false>, start.grid, start.block, 0, i.stream, sc, g, in.blocks, n_px, blocks_x, i.width, i.height, origin, bounces, d->chain_state.get(), queue(0, 0),
-	                   d->chain_counts.get());
+	const bool unfold = own.image[kVirtual] != nullptr;
+	chain.bounces = bounces;
+	CTX_TRY(c, hipMemsetAsync(chain.counts.get(), 0, sizeof(ChainCounts), i.stream));
+	CTX_TRY(c, chain.timer.mark(0, i.stream));
+	hipLaunchKernelGGL(chain_start_instance(unfold), start.grid, start.block, 0, i.stream, sc, g, in.blocks, n_px, blocks_x, i.width, i.height, origin, bounces, chain.state.get(), queue(0, 0),
+	                   chain.counts.get());
 	const ChainUnfold unfolded{unfold ? d->own.as<kVirtual>() : nullptr, {cam.origin[0], cam.origin[1], cam.origin[2]}};
 	CTX_TRY(c, hipGetLastError());
 	const LaunchShape step = chain_step_launch(q.segments, per_segment);
 	for(int r = 0; r < bounces; ++r)
 	{
 		CTX_STEP(ctx_trace_queue(c, r & 1, r));
-		hipLaunchKernelGGL(unfold ? k_chain_step<true> : k_chain_step<false>, step.grid, step.block, 0, i.stream, sc, g, queue(r & 1, r), (const float4 *)q.hit, n_px, bounces, q.tmin, d->chain_state.get(),
-		                   queue((r & 1) ^ 1, r + 1), d->chain_counts.get(), unfolded);
+		hipLaunchKernelGGL(chain_step_instance(unfold), step.grid, step.block, 0, i.stream, sc, g, queue(r & 1, r), (const float4 *)q.hit, n_px, bounces, q.tmin, chain.state.get(),
+		                   queue((r & 1) ^ 1, r + 1), chain.counts.get(), unfolded);
 		CTX_TRY(c, hipGetLastError());
 	}
-	CTX_TRY(c, d->chain_timer.mark(1, i.stream));
+	CTX_TRY(c, chain.timer.mark(1, i.stream));
 	return ADYPT_OK;
 }
 
 // ... and the context's guides into it, enqueued behind its frames (the sample counts are the caller's to upload); bounces > 0: followed through mirrors
 // and glass, the class of every pixel in the .w of the primary-hit image
-int capture_guides(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, LocalImages *v, int bounces = 0, bool unfold = false)
+int capture_guides(adypt_ctx *c, Denoiser *d, const DenoiseInputs &in, const char *fn, LocalImages *v, int bounces = 0, unsigned left_out = kWithoutVirtual)
 {
-	CTX_STEP(own_images(c, d, in, v, unfold));
+	CTX_STEP(own_images(c, d, in, v, left_out));
 	CtxRayQueues q{};
 	if(bounces > 0) CTX_STEP(ctx_ray_queues(c, fn, &q)); // (first: it may have to wait for frames started ahead)
 	CTX_STEP(ctx_capture_guides(c, fn, d->own.as<kAlbedo>(), d->own.as<kNormal>(), d->own.as<kPosition>(), d->own.as<kHits>()));
-	return bounces > 0 && in.n_blocks > 0 ? enqueue_chain(c, d, in, fn, bounces, q, unfold) : (int)ADYPT_OK;
+	return bounces > 0 && in.n_blocks > 0 ? enqueue_chain(c, d, in, fn, bounces, q, *v) : (int)ADYPT_OK;
 }
 
 // `bytes` of a device array of a context on the host (the stream is drained when it returns)
@@ -539,135 +554,111 @@ int read_result(adypt_ctx *c, const char *fn, float *rgb)
 
 int read_history_length(adypt_ctx *c, const char *fn, float *length)
 {
-	return read_image(c, fn, ": no temporal call has run yet (adypt_denoise_temporal)", length, 1, [](Denoiser *d) { return d->length_valid ? d->length.get() : nullptr; });
+	return read_image(c, fn, ": no temporal call has run yet (adypt_denoise_temporal)", length, 1, [](Denoiser *d) { return d->merge.valid ? d->merge.length.get() : nullptr; });
 }
 
-// XP of the last motion call: the previous position (W x H x 3 floats) and the moved flag (W x H bytes) of every pixel; either may be null
-int read_motion(adypt_ctx *c, const char *fn, float *prev_position, uint8_t *moved)
+// A float4 read-out image of the last finished run (`image` as read_image's) split into the caller's arrays: xyz, W x H x 3 floats, and w through
+// `flag`, W x H elements; either may be null
+template <class W, class Pick, class Flag> int read_split(adypt_ctx *c, const char *fn, const char *none, float *xyz, W *w, Pick image, Flag flag)
 {
-	const Denoiser *last = finished_denoiser(c);
-	std::vector<float4> xp(last && last->xp_valid ? last->pixels() : 0); // (nothing where the call is about to be refused)
-	CTX_STEP(read_image(c, fn, ": no motion call has run yet (adypt_denoise_temporal_motion)", xp.data(), 1, [](Denoiser *d) { return d->xp_valid ? d->xp.get() : nullptr; }));
-	for(size_t k = 0; k < xp.size(); ++k)
+	Denoiser *d = finished_denoiser(c);
+	std::vector<float4> host(d && image(d) ? d->pixels() : 0); // (nothing where the call is about to be refused)
+	CTX_STEP(read_image(c, fn, none, host.data(), 1, image));
+	for(size_t k = 0; k < host.size(); ++k)
 	{
-		if(prev_position) { prev_position[3 * k] = xp[k].x; prev_position[3 * k + 1] = xp[k].y; prev_position[3 * k + 2] = xp[k].z; }
-		if(moved) moved[k] = xp[k].w != 0.0f ? 1 : 0;
+		if(xyz) { xyz[3 * k] = host[k].x; xyz[3 * k + 1] = host[k].y; xyz[3 * k + 2] = host[k].z; }
+		if(w) w[k] = flag(host[k].w);
 	}
 	return ADYPT_OK;
 }
 
-int get_motion(adypt_ctx *c, const char *fn, adypt_denoise_motion *out)
+// XP of the last motion call: the previous position and the moved flag (bytes) of every pixel
+int read_motion(adypt_ctx *c, const char *fn, float *prev_position, uint8_t *moved)
 {
-	if(!out) return ctx_fail(c, ADYPT_E_INVALID, std::string(fn) + ": out is null");
-	*out = adypt_denoise_motion{};
-	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
-	if(!d) return ADYPT_OK;
-	const History &h = d->history;
-	out->have_snapshot = h.snapshot_tris > 0 ? 1 : 0;
-	out->n_tris = h.snapshot_tris;
-	out->device_bytes = (int64_t)(h.snapshot.bytes() + d->xp.bytes() + d->xn.bytes());
-	if(out->have_snapshot) (void)h.snapshot_timer.read(&out->snapshot_ms, 1, 1, false);
-	return ADYPT_OK;
+	return read_split(c, fn, ": no motion call has run yet (adypt_denoise_temporal_motion)", prev_position, moved, [](Denoiser *d) { return d->motion.valid ? d->motion.xp.get() : nullptr; },
+	                  [](float w) { return (uint8_t)(w != 0.0f ? 1 : 0); });
+}
+
+// XV of the last call by the virtual point: the virtual position and the unfolded length (0: the pixel is not followed, or its length is not valid)
+int read_virtual(adypt_ctx *c, const char *fn, float *virtual_position, float *distance)
+{
+	return read_split(c, fn, ": no call by the virtual point has run yet (adypt_denoise_temporal_specular)", virtual_position, distance,
+	                  [](Denoiser *d) { return d->virt.valid ? d->virt.xv.get() : nullptr; }, [](float w) { return w; });
 }
 
 // the share of its length every pixel's history kept in the last rectified call
 int read_rectify(adypt_ctx *c, const char *fn, float *kept)
 {
-	return read_image(c, fn, ": no rectified call has run yet (adypt_denoise_temporal_rectified)", kept, 1, [](Denoiser *d) { return d->kept_valid ? d->kept.get() : nullptr; });
-}
-
-int get_rectify(adypt_ctx *c, const char *fn, adypt_denoise_rectify *out)
-{
-	if(!out) return ctx_fail(c, ADYPT_E_INVALID, std::string(fn) + ": out is null");
-	*out = adypt_denoise_rectify{};
-	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
-	if(!d) return ADYPT_OK;
-	out->device_bytes = (int64_t)(d->r0.bytes() + d->r1.bytes() + d->kept.bytes());
-	if(!d->kept_valid) return ADYPT_OK;
-	out->have = 1;
-	out->radius = d->rectify_radius; out->gamma = d->rectify_gamma;
-	(void)d->window_timer.read(&out->window_ms, 1, 1, false);
-	return ADYPT_OK;
+	return read_image(c, fn, ": no rectified call has run yet (adypt_denoise_temporal_rectified)", kept, 1, [](Denoiser *d) { return d->window.valid ? d->window.kept.get() : nullptr; });
 }
 
 // the variance the first level saw in the last moments call
 int read_variance(adypt_ctx *c, const char *fn, float *v)
 {
-	return read_image(c, fn, ": no moments call has run yet (adypt_denoise_temporal_moments)", v, 1, [](Denoiser *d) { return d->variance_valid ? d->variance.get() : nullptr; });
+	return read_image(c, fn, ": no moments call has run yet (adypt_denoise_temporal_moments)", v, 1, [](Denoiser *d) { return d->moments.valid ? d->moments.variance.get() : nullptr; });
+}
+
+// What an adypt_get_denoise_* call answers: `out` refused when null, zeroed, and — where the context has denoised at all — filled by `fill`
+// (an int: ADYPT_OK, or the step that failed)
+template <class Info, class Fill> int get_info(adypt_ctx *c, const char *fn, Info *out, Fill fill)
+{
+	if(!out) return ctx_fail(c, ADYPT_E_INVALID, std::string(fn) + ": out is null");
+	*out = Info{};
+	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
+	return d ? fill(d) : (int)ADYPT_OK;
+}
+
+int get_motion(adypt_ctx *c, const char *fn, adypt_denoise_motion *out)
+{
+	return get_info(c, fn, out, [out](const Denoiser *d) { d->motion.fill(d->history, out); return (int)ADYPT_OK; });
+}
+
+int get_rectify(adypt_ctx *c, const char *fn, adypt_denoise_rectify *out)
+{
+	return get_info(c, fn, out, [out](const Denoiser *d) { d->window.fill(out); return (int)ADYPT_OK; });
 }
 
 int get_moments(adypt_ctx *c, const char *fn, adypt_denoise_moments *out)
 {
-	if(!out) return ctx_fail(c, ADYPT_E_INVALID, std::string(fn) + ": out is null");
-	*out = adypt_denoise_moments{};
-	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
-	if(!d) return ADYPT_OK;
-	out->device_bytes = (int64_t)(d->variance.bytes() + d->spatial_count.bytes());
-	if(!d->variance_valid) return ADYPT_OK;
-	out->have = 1;
-	out->pixels_spatial = d->pixels_spatial;
-	(void)d->variance_timer.read(&out->variance_ms, 1, 1, false);
-	return ADYPT_OK;
-}
-
-// XV of the last call by the virtual point: the virtual position (W x H x 3 floats) and the unfolded length (W x H floats; 0: the pixel is not followed,
-// or its length is not valid) of every pixel; either may be null
-int read_virtual(adypt_ctx *c, const char *fn, float *virtual_position, float *distance)
-{
-	const Denoiser *last = finished_denoiser(c);
-	std::vector<float4> xv(last && last->xv_valid ? last->pixels() : 0);
-	CTX_STEP(read_image(c, fn, ": no call by the virtual point has run yet (adypt_denoise_temporal_specular)", xv.data(), 1, [](Denoiser *d) { return d->xv_valid ? d->xv.get() : nullptr; }));
-	for(size_t k = 0; k < xv.size(); ++k)
-	{
-		if(virtual_position) { virtual_position[3 * k] = xv[k].x; virtual_position[3 * k + 1] = xv[k].y; virtual_position[3 * k + 2] = xv[k].z; }
-		if(distance) distance[k] = xv[k].w;
-	}
-	return ADYPT_OK;
+	return get_info(c, fn, out, [out](const Denoiser *d) { d->moments.fill(out); return (int)ADYPT_OK; });
 }
 
 int get_virtual(adypt_ctx *c, const char *fn, adypt_denoise_virtual *out)
 {
-	if(!out) return ctx_fail(c, ADYPT_E_INVALID, std::string(fn) + ": out is null");
-	*out = adypt_denoise_virtual{};
-	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
-	if(!d) return ADYPT_OK;
-	out->device_bytes = (int64_t)(d->own.image[kVirtual].bytes() + d->merged.image[kVirtual].bytes() + d->xv.bytes() + d->virtual_count.bytes());
-	if(!d->xv_valid) return ADYPT_OK;
-	out->have = 1; out->bounces = d->virtual_bounces;
-	out->pixels_followed = d->virtual_followed; out->pixels_with_history = d->virtual_with_history;
-	return ADYPT_OK;
+	return get_info(c, fn, out, [out](const Denoiser *d) { d->virt.fill(d->own.image[kVirtual].bytes() + d->merged.image[kVirtual].bytes(), out); return (int)ADYPT_OK; });
 }
 
 int read_guides(adypt_ctx *c, const char *fn, int bounces, float *albedo, float *normal, float *position, uint8_t *hit, int8_t *chain); // (below, beside its entry points)
 
 // what the last chain of a context did: its counters are read here, behind whatever the context's stream still holds
-int get_specular(adypt_ctx *c, const char *fn, adypt_denoise_specular_info *out)
+int ChainStage::fill(adypt_ctx *c, adypt_denoise_specular_info *out) const
 {
-	if(!out) return ctx_fail(c, ADYPT_E_INVALID, std::string(fn) + ": out is null");
-	*out = adypt_denoise_specular_info{};
-	const Denoiser *d = ctx_state_if_any<Denoiser>(c, kAttachDenoise);
-	if(!d) return ADYPT_OK;
-	out->device_bytes = (int64_t)(d->chain_state.bytes() + d->chain_counts.bytes());
-	if(d->chain_bounces == 0) return ADYPT_OK;
+	out->device_bytes = (int64_t)(state.bytes() + counts.bytes());
+	if(bounces == 0) return ADYPT_OK;
 	const CtxInfo i = ctx_info(c);
 	CTX_TRY(c, hipSetDevice(i.device));
 	ChainCounts n;
-	CTX_STEP(fetch(c, i, d->chain_counts.get(), &n, sizeof(n)));
-	out->have = 1; out->bounces = d->chain_bounces;
-	(void)d->chain_timer.read(&out->chain_ms, 1, 1, false);
+	CTX_STEP(fetch(c, i, counts.get(), &n, sizeof(n)));
+	out->have = 1; out->bounces = bounces;
+	(void)timer.read(&out->chain_ms, 1, 1, false);
 	out->rays = (int64_t)n.rays; out->pixels_followed = (int64_t)n.followed; out->pixels_escaped = (int64_t)n.escaped; out->pixels_truncated = (int64_t)n.truncated;
 	return ADYPT_OK;
+}
+
+int get_specular(adypt_ctx *c, const char *fn, adypt_denoise_specular_info *out)
+{
+	return get_info(c, fn, out, [c, out](const Denoiser *d) { return d->chain.fill(c, out); });
 }
 
 int read_merge_ms(adypt_ctx *c, const char *fn, float *ms)
 {
 	Denoiser *d = finished_denoiser(c);
-	if(!d || d->last.mode == Mode::Plain) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the last filter was not a temporal call (adypt_denoise_temporal)");
+	if(!d || !d->last.history) return ctx_fail(c, ADYPT_E_STATE, std::string(fn) + ": the last filter was not a temporal call (adypt_denoise_temporal)");
 	read_stages(d, nullptr, 0, ms);
 	return ADYPT_OK;
 }
 
-// the three denoise calls of one context
+// a denoise call of one context
 int denoise_context(adypt_ctx *c, const DenoiseCall &call)
 {
 	if(!c) return ADYPT_E_INVALID;
@@ -683,7 +674,7 @@ int denoise_context(adypt_ctx *c, const DenoiseCall &call)
 	CTX_TRY(c, d->timer.mark(0, i.stream));
 	const DenoiseInputs in = ctx_denoise_inputs(c);
 	LocalImages local;
-	CTX_STEP(capture_guides(c, d, in, fn, &local, call.bounces, call.unfold));
+	CTX_STEP(capture_guides(c, d, in, fn, &local, call.bounces, optional_images(call)));
 	CTX_TRY(c, d->timer.mark(1, i.stream));
 	CTX_TRY(c, hipMemcpyAsync(d->own.as<kBlockSpp>(), in.block_spp.data(), in.block_spp.size() * sizeof(int32_t), hipMemcpyHostToDevice, i.stream));
 	return run_filter(c, d, i.stream, local, call, ctx_camera(c));
@@ -702,20 +693,20 @@ void denoise_triangles_replaced(adypt_ctx *c)
 
 extern "C" {
 
-int adypt_denoise(adypt_ctx *c, const adypt_denoise_params *p) { return denoise_context(c, make_call(Mode::Plain, "adypt_denoise", p, nullptr)); }
+int adypt_denoise(adypt_ctx *c, const adypt_denoise_params *p) { return denoise_context(c, make_call("adypt_denoise", 0, p)); }
 
-int adypt_denoise_temporal(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return denoise_context(c, make_call(Mode::Temporal, "adypt_denoise_temporal", p, tp)); }
+int adypt_denoise_temporal(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return denoise_context(c, make_call("adypt_denoise_temporal", kWithHistory, p, tp)); }
 
-int adypt_denoise_temporal_motion(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return denoise_context(c, make_call(Mode::Motion, "adypt_denoise_temporal_motion", p, tp)); }
+int adypt_denoise_temporal_motion(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return denoise_context(c, make_call("adypt_denoise_temporal_motion", kWithHistory | kWithMotion, p, tp)); }
 
 int adypt_denoise_temporal_rectified(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_rectify_params *rp, int follow_motion)
 {
-	return denoise_context(c, make_call(follow_motion ? Mode::Motion : Mode::Temporal, "adypt_denoise_temporal_rectified", p, tp, true, rp));
+	return denoise_context(c, make_call("adypt_denoise_temporal_rectified", kWithHistory | kWithRectify | motion_if(follow_motion), p, tp, rp));
 }
 
 int adypt_denoise_temporal_moments(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp, int follow_motion)
 {
-	return denoise_context(c, make_moments_call("adypt_denoise_temporal_moments", p, tp, follow_motion));
+	return denoise_context(c, make_call("adypt_denoise_temporal_moments", kWithHistory | kWithMoments | motion_if(follow_motion), p, tp));
 }
 
 int adypt_read_denoise_variance(adypt_ctx *c, float *v) { return c && v ? read_variance(c, "adypt_read_denoise_variance", v) : ADYPT_E_INVALID; }
@@ -755,13 +746,13 @@ int adypt_read_denoise_guides_specular(adypt_ctx *c, int32_t bounces, float *alb
 	return read_guides(c, "adypt_read_denoise_guides_specular", bounces, albedo, normal, position, nullptr, chain);
 }
 
-int adypt_denoise_specular(adypt_ctx *c, const adypt_denoise_params *p, const adypt_specular_params *sp) { return denoise_context(c, make_specular_call("adypt_denoise_specular", p, sp)); }
+int adypt_denoise_specular(adypt_ctx *c, const adypt_denoise_params *p, const adypt_specular_params *sp) { return denoise_context(c, make_call("adypt_denoise_specular", kWithSpecular, p, nullptr, nullptr, sp)); }
 
 int adypt_get_denoise_specular(adypt_ctx *c, adypt_denoise_specular_info *out) { return c ? get_specular(c, "adypt_get_denoise_specular", out) : ADYPT_E_INVALID; }
 
 int adypt_denoise_temporal_specular(adypt_ctx *c, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_specular_params *sp)
 {
-	return denoise_context(c, make_virtual_call("adypt_denoise_temporal_specular", p, tp, sp));
+	return denoise_context(c, make_call("adypt_denoise_temporal_specular", kWithHistory | kWithSpecular, p, tp, nullptr, sp));
 }
 
 int adypt_read_denoise_virtual(adypt_ctx *c, float *virtual_position, float *distance) { return c ? read_virtual(c, "adypt_read_denoise_virtual", virtual_position, distance) : ADYPT_E_INVALID; }
@@ -824,7 +815,7 @@ int adypt_get_denoise_timing(adypt_ctx *c, float *ms, int capacity)
 
 namespace {
 
-// the three denoise calls of a handle: the merge runs on the first device, where the filter runs, and the history lives there
+// a denoise call of a handle: the merge runs on the first device, where the filter runs, and the history lives there
 int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 {
 	const int n_dev = adypt_multi_device_count(m);
@@ -839,14 +830,14 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 	const int min_spp = call.min_spp();
 	CTX_STEP(multi_each(m, [fn, min_spp](adypt_ctx *c) { return ctx_denoise_ready(c, fn, min_spp); }));
 	// every device captures the guides of its own blocks: all enqueued before the first is waited for
-	const bool unfold = call.unfold;
+	const unsigned left_out = optional_images(call);
 	const int bounces = call.bounces; // (followed guides: every device follows the chains of its own blocks; the class comes along in the primary-hit image)
-	CTX_STEP(multi_each(m, [fn, bounces, unfold](adypt_ctx *c) {
+	CTX_STEP(multi_each(m, [fn, bounces, left_out](adypt_ctx *c) {
 		const CtxInfo i = ctx_info(c);
 		if(i.n_local_px == 0) return (int)ADYPT_OK;
 		if(hipSetDevice(i.device) != hipSuccess) return ctx_fail(c, ADYPT_E_HIP, std::string(fn) + ": hipSetDevice failed");
 		LocalImages own;
-		return capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), fn, &own, bounces, unfold);
+		return capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), fn, &own, bounces, left_out);
 	}));
 	// the local images of every device back to back in rank order, and their block lists and sample counts likewise (the counts from each context's
 	// own state in that order: multi.hip's merge is sorted by block index, which is not this order, and would launch k_noise_blocks for nothing)
@@ -854,7 +845,6 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 	size_t n_blocks = 0;
 	for(adypt_ctx *c : ctx) n_blocks += (size_t)ctx_info(c).n_local_px / kBlockPixels;
 	std::vector<uint8_t> host[kBlockImages];
-	const unsigned left_out = optional_images(unfold);
 	for(int k = 0; k < kBlockImages; ++k)
 		if(!(left_out >> k & 1)) host[k].resize(n_blocks * kBlockImageBytes[k]);
 	size_t at = 0; // the rank's first block in them
@@ -865,7 +855,7 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 		if(hipSetDevice(i.device) != hipSuccess) return fail_ctx(c, ctx_fail(c, ADYPT_E_HIP, std::string(fn) + ": hipSetDevice failed"));
 		const DenoiseInputs in = ctx_denoise_inputs(c);
 		LocalImages own;
-		int r = own_images(c, denoiser_of(c), in, &own, unfold);
+		int r = own_images(c, denoiser_of(c), in, &own, left_out);
 		for(const BlockImage k : kFetchOrder)
 			if(r == ADYPT_OK && !(left_out >> k & 1)) r = fetch(c, i, own.image[k], host[k].data() + at * kBlockImageBytes[k], (size_t)in.n_blocks * kBlockImageBytes[k]);
 		if(r != ADYPT_OK) return fail_ctx(c, r);
@@ -902,24 +892,41 @@ template <class F> int on_root(adypt_multi *m, F f)
 	return r;
 }
 
+// a per-device info struct over the devices: every device's bytes, and `add` for what the devices that have something say
+template <class Info, class Get, class Add> int sum_info(adypt_multi *m, Info *out, Get get, Add add)
+{
+	if(!out) return ADYPT_E_INVALID;
+	Info sum{};
+	const int r = multi_each(m, [&](adypt_ctx *c) {
+		Info one;
+		const int e = get(c, &one);
+		if(e != ADYPT_OK) return e;
+		sum.device_bytes += one.device_bytes;
+		if(one.have) { sum.have = 1; sum.bounces = one.bounces; add(&sum, one); }
+		return (int)ADYPT_OK;
+	});
+	if(r == ADYPT_OK) *out = sum;
+	return r;
+}
+
 }  // namespace
 
 extern "C" {
 
-int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p) { return multi_denoise(m, make_call(Mode::Plain, "adypt_multi_denoise", p, nullptr)); }
+int adypt_multi_denoise(adypt_multi *m, const adypt_denoise_params *p) { return multi_denoise(m, make_call("adypt_multi_denoise", 0, p)); }
 
-int adypt_multi_denoise_temporal(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return multi_denoise(m, make_call(Mode::Temporal, "adypt_multi_denoise_temporal", p, tp)); }
+int adypt_multi_denoise_temporal(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return multi_denoise(m, make_call("adypt_multi_denoise_temporal", kWithHistory, p, tp)); }
 
-int adypt_multi_denoise_temporal_motion(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return multi_denoise(m, make_call(Mode::Motion, "adypt_multi_denoise_temporal_motion", p, tp)); }
+int adypt_multi_denoise_temporal_motion(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp) { return multi_denoise(m, make_call("adypt_multi_denoise_temporal_motion", kWithHistory | kWithMotion, p, tp)); }
 
 int adypt_multi_denoise_temporal_rectified(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_rectify_params *rp, int follow_motion)
 {
-	return multi_denoise(m, make_call(follow_motion ? Mode::Motion : Mode::Temporal, "adypt_multi_denoise_temporal_rectified", p, tp, true, rp));
+	return multi_denoise(m, make_call("adypt_multi_denoise_temporal_rectified", kWithHistory | kWithRectify | motion_if(follow_motion), p, tp, rp));
 }
 
 int adypt_multi_denoise_temporal_moments(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp, int follow_motion)
 {
-	return multi_denoise(m, make_moments_call("adypt_multi_denoise_temporal_moments", p, tp, follow_motion));
+	return multi_denoise(m, make_call("adypt_multi_denoise_temporal_moments", kWithHistory | kWithMoments | motion_if(follow_motion), p, tp));
 }
 
 // the variance read-out and the count live on the first device, where the merge and the variance kernel run
@@ -978,11 +985,11 @@ int adypt_multi_read_denoise_guides(adypt_multi *m, float *albedo, float *normal
 	return multi_each(m, [=](adypt_ctx *c) { return adypt_read_denoise_guides(c, albedo, normal, position, hit); });
 }
 
-int adypt_multi_denoise_specular(adypt_multi *m, const adypt_denoise_params *p, const adypt_specular_params *sp) { return multi_denoise(m, make_specular_call("adypt_multi_denoise_specular", p, sp)); }
+int adypt_multi_denoise_specular(adypt_multi *m, const adypt_denoise_params *p, const adypt_specular_params *sp) { return multi_denoise(m, make_call("adypt_multi_denoise_specular", kWithSpecular, p, nullptr, nullptr, sp)); }
 
 int adypt_multi_denoise_temporal_specular(adypt_multi *m, const adypt_denoise_params *p, const adypt_temporal_params *tp, const adypt_specular_params *sp)
 {
-	return multi_denoise(m, make_virtual_call("adypt_multi_denoise_temporal_specular", p, tp, sp));
+	return multi_denoise(m, make_call("adypt_multi_denoise_temporal_specular", kWithHistory | kWithSpecular, p, tp, nullptr, sp));
 }
 
 // XV and the counts live on the first device, where the merge runs; the bytes are summed over the devices (every device keeps its own blocks' virtual points)
@@ -993,18 +1000,8 @@ int adypt_multi_read_denoise_virtual(adypt_multi *m, float *virtual_position, fl
 
 int adypt_multi_get_denoise_virtual(adypt_multi *m, adypt_denoise_virtual *out)
 {
-	if(!out) return ADYPT_E_INVALID;
-	adypt_denoise_virtual sum{};
-	const int r = multi_each(m, [&sum](adypt_ctx *c) {
-		adypt_denoise_virtual one;
-		const int e = get_virtual(c, "adypt_multi_get_denoise_virtual", &one);
-		if(e != ADYPT_OK) return e;
-		sum.device_bytes += one.device_bytes;
-		if(one.have) { sum.have = 1; sum.bounces = one.bounces; sum.pixels_followed = one.pixels_followed; sum.pixels_with_history = one.pixels_with_history; }
-		return (int)ADYPT_OK;
-	});
-	if(r == ADYPT_OK) *out = sum;
-	return r;
+	return sum_info(m, out, [](adypt_ctx *c, adypt_denoise_virtual *one) { return get_virtual(c, "adypt_multi_get_denoise_virtual", one); },
+	                [](adypt_denoise_virtual *sum, const adypt_denoise_virtual &one) { sum->pixels_followed = one.pixels_followed; sum->pixels_with_history = one.pixels_with_history; });
 }
 
 int adypt_multi_read_denoise_guides_specular(adypt_multi *m, int32_t bounces, float *albedo, float *normal, float *position, int8_t *chain)
@@ -1015,20 +1012,11 @@ int adypt_multi_read_denoise_guides_specular(adypt_multi *m, int32_t bounces, fl
 // every device followed the chains of its own blocks: the counts and the bytes are sums, the time the slowest device's
 int adypt_multi_get_denoise_specular(adypt_multi *m, adypt_denoise_specular_info *out)
 {
-	if(!out) return ADYPT_E_INVALID;
-	adypt_denoise_specular_info sum{};
-	const int r = multi_each(m, [&sum](adypt_ctx *c) {
-		adypt_denoise_specular_info one;
-		const int e = get_specular(c, "adypt_multi_get_denoise_specular", &one);
-		if(e != ADYPT_OK) return e;
-		sum.device_bytes += one.device_bytes;
-		if(!one.have) return (int)ADYPT_OK;
-		sum.have = 1; sum.bounces = one.bounces; sum.chain_ms = std::max(sum.chain_ms, one.chain_ms);
-		sum.rays += one.rays; sum.pixels_followed += one.pixels_followed; sum.pixels_escaped += one.pixels_escaped; sum.pixels_truncated += one.pixels_truncated;
-		return (int)ADYPT_OK;
-	});
-	if(r == ADYPT_OK) *out = sum;
-	return r;
+	return sum_info(m, out, [](adypt_ctx *c, adypt_denoise_specular_info *one) { return get_specular(c, "adypt_multi_get_denoise_specular", one); },
+	                [](adypt_denoise_specular_info *sum, const adypt_denoise_specular_info &one) {
+		                sum->chain_ms = std::max(sum->chain_ms, one.chain_ms);
+		                sum->rays += one.rays; sum->pixels_followed += one.pixels_followed; sum->pixels_escaped += one.pixels_escaped; sum->pixels_truncated += one.pixels_truncated;
+	                });
 }
 
 }  // extern "C"

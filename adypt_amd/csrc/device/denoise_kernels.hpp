@@ -1,7 +1,8 @@
 // The denoiser's kernels and the shape each is launched with, in a header of their own so that two libraries compile the same text: denoise.hip, which
 // is the product, and csrc/probe/probe.hip, which runs every kernel on arrays a test makes (tests/test_gpu_denoise_probes.py).  The kernels stay in the
 // anonymous namespace: each including unit has its own copies, and nothing here is visible outside it.  Who launches a kernel takes the grid and the
-// workgroup from the *_launch function beside it — denoise.hip and the probe alike — so that the probe's launch shape cannot drift from the product's.
+// workgroup from the *_launch function beside it — denoise.hip and the probe alike — so that the probe's launch shape cannot drift from the product's; the instance of a
+// templated kernel likewise, from the *_instance functions at the end.
 // What the stages are and in which order they run: the head of denoise.hip.
 #pragma once
 #include "tile_layout.hpp"
@@ -588,5 +589,24 @@ __global__ __launch_bounds__(kPixelThreads) void k_motion_gather(const float4 *_
 	xn[p] = make_float4(r.xn.x, r.xn.y, r.xn.z, r.xn.w);
 }
 inline LaunchShape gather_launch(int n_px) { return local_pixels_launch(n_px); }
+
+// ---- which instance of a kernel a launch takes ----
+// Asked here by denoise.hip and the probe alike, as the launch shapes are.  (Together, and in this order: a unit's code object holds the instances of
+// the templates in the order they are first named.)
+// the prepare of a call: `moments`, else `followed` (X1.w is the class); k_denoise_prepare_virtual has arguments of its own and no place here
+inline decltype(&k_denoise_prepare) prepare_instance(bool moments, bool followed) { return moments ? k_denoise_prepare_moments : followed ? k_denoise_prepare_class : k_denoise_prepare; }
+inline decltype(&k_rectify_window<1>) window_instance(int radius)
+{
+	static_assert(kRectifyMaxRadius == 3, "one instance of k_rectify_window per radius");
+	return radius == 1 ? k_rectify_window<1> : radius == 2 ? k_rectify_window<2> : k_rectify_window<3>;
+}
+inline decltype(&k_temporal_merge<false, false>) merge_instance(bool motion, bool rectify)
+{
+	return rectify ? (motion ? k_temporal_merge<true, true> : k_temporal_merge<false, true>) : (motion ? k_temporal_merge<true, false> : k_temporal_merge<false, false>);
+}
+inline decltype(&k_temporal_merge_moments<false>) merge_moments_instance(bool motion) { return motion ? k_temporal_merge_moments<true> : k_temporal_merge_moments<false>; }
+inline decltype(&k_atrous<false>) atrous_instance(bool last) { return last ? k_atrous<true> : k_atrous<false>; }
+inline decltype(&k_chain_start<false>) chain_start_instance(bool unfold) { return unfold ? k_chain_start<true> : k_chain_start<false>; }
+inline decltype(&k_chain_step<false>) chain_step_instance(bool unfold) { return unfold ? k_chain_step<true> : k_chain_step<false>; }
 
 }  // namespace

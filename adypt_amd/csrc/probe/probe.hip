@@ -509,7 +509,7 @@ int adypt_probe_denoise_prepare(const float *accum, const float *moments, const 
 	PROBE_TRY(dh.in(hits, local)); PROBE_TRY(db.in(blocks, (size_t)n_blocks * 4)); PROBE_TRY(ds.in(block_spp, (size_t)n_blocks * 4));
 	PROBE_TRY(o0.filled(image, kUnwritten)); PROBE_TRY(o1.filled(image, kUnwritten)); PROBE_TRY(o2.filled(image, kUnwritten)); PROBE_TRY(oa.filled(image, kUnwritten));
 	const LaunchShape shape = prepare_launch(n_px);
-	hipLaunchKernelGGL(k_denoise_prepare, shape.grid, shape.block, 0, 0, dc.as<float4>(), dm.as<float2>(), db.as<int32_t>(), ds.as<int32_t>(), n_px, blocks_across(width), width, height,
+	hipLaunchKernelGGL(prepare_instance(false, false), shape.grid, shape.block, 0, 0, dc.as<float4>(), dm.as<float2>(), db.as<int32_t>(), ds.as<int32_t>(), n_px, blocks_across(width), width, height,
 	                   da.as<float4>(), dn.as<float4>(), dp.as<float4>(), dh.as<float4>(), o0.as<float4>(), o1.as<float4>(), o2.as<float4>(), oa.as<float4>());
 	PROBE_TRY(launched());
 	PROBE_TRY(o0.back(x0)); PROBE_TRY(o1.back(x1)); PROBE_TRY(o2.back(x2)); PROBE_TRY(oa.back(xa));
@@ -525,10 +525,8 @@ int adypt_probe_atrous(const float *x0, const float *x1, const float *x2, const 
 	PROBE_TRY(dout.filled(last ? image / 4 * 3 : image, kUnwritten));
 	const LaunchShape shape = atrous_launch(width, height);
 	// (as run_filter launches a level: the image the instance does not write is never touched)
-	if(last) hipLaunchKernelGGL(k_atrous<true>, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), (float4 *)nullptr, dout.as<float>(), width, height,
-	                            step, sigma_l, sigma_z);
-	else hipLaunchKernelGGL(k_atrous<false>, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), dout.as<float4>(), (float *)nullptr, width, height,
-	                        step, sigma_l, sigma_z);
+	hipLaunchKernelGGL(atrous_instance(last != 0), shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), last ? (float4 *)nullptr : dout.as<float4>(),
+	                   last ? dout.as<float>() : (float *)nullptr, width, height, step, sigma_l, sigma_z);
 	PROBE_TRY(launched());
 	PROBE_TRY(dout.back(out));
 	return 0;
@@ -541,12 +539,10 @@ int adypt_probe_rectify_window(int radius, const float *x0, const float *x1, con
 	Dev d0, d1, d2, da, o0, o1;
 	PROBE_TRY(d0.in(x0, image)); PROBE_TRY(d1.in(x1, image)); PROBE_TRY(d2.in(x2, image)); PROBE_TRY(da.in(xa, image));
 	PROBE_TRY(o0.filled(image, kUnwritten)); PROBE_TRY(o1.filled(image, kUnwritten));
-	const auto window = radius == 1 ? k_rectify_window<1> : radius == 2 ? k_rectify_window<2> : k_rectify_window<3>;
-	static_assert(kRectifyMaxRadius == 3, "one instance of k_rectify_window per radius");
 	RectifyOrigin o;
 	for(int k = 0; k < 3; ++k) o.o[k] = origin[k];
 	const LaunchShape shape = window_launch(width, height);
-	hipLaunchKernelGGL(window, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), o0.as<float4>(), o1.as<float4>(), width, height, o);
+	hipLaunchKernelGGL(window_instance(radius), shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), o0.as<float4>(), o1.as<float4>(), width, height, o);
 	PROBE_TRY(launched());
 	PROBE_TRY(o0.back(r0)); PROBE_TRY(o1.back(r1));
 	return 0;
@@ -566,10 +562,9 @@ int adypt_probe_temporal_merge(int motion, int rectify, const float *x0, const f
 	if(rectify) { PROBE_TRY(dr0.in(r0, image)); PROBE_TRY(dr1.in(r1, image)); PROBE_TRY(ok.filled(image / 4, kUnwritten)); }
 	PROBE_TRY(om.filled(image, kUnwritten)); PROBE_TRY(ol.filled(image / 4, kUnwritten));
 	const TemporalCamera cam = temporal_camera(origin, inv_proj, inv_view);
-	const auto merge = rectify ? (motion ? k_temporal_merge<true, true> : k_temporal_merge<false, true>) : (motion ? k_temporal_merge<true, false> : k_temporal_merge<false, false>);
 	const LaunchShape shape = merge_launch(width, height);
 	// (an instance never looks at the images of a form it is not: they are null here, as they are in a context that never made such a call)
-	hipLaunchKernelGGL(merge, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), e0.as<float4>(), e1.as<float4>(), e2.as<float4>(),
+	hipLaunchKernelGGL(merge_instance(motion != 0, rectify != 0), shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(), e0.as<float4>(), e1.as<float4>(), e2.as<float4>(),
 	                   ea.as<float4>(), om.as<float4>(), ol.as<float>(), width, height, have ? 1 : 0, cam, history_cap, dxp.as<float4>(), dxn.as<float4>(), dr0.as<float4>(), dr1.as<float4>(),
 	                   ok.as<float>(), gamma);
 	PROBE_TRY(launched());
@@ -662,7 +657,7 @@ int adypt_probe_denoise_prepare_instance(int instance, const float *accum, const
 		                   da.as<float4>(), dn.as<float4>(), dp.as<float4>(), dh.as<float4>(), o0.as<float4>(), o1.as<float4>(), o2.as<float4>(), oa.as<float4>(), dv.as<float4>(), ov.as<float4>());
 	}
 	else
-		hipLaunchKernelGGL(instance == ADYPT_PROBE_PREPARE_CLASS ? k_denoise_prepare_class : k_denoise_prepare_moments, shape.grid, shape.block, 0, 0, dc.as<float4>(), dm.as<float2>(),
+		hipLaunchKernelGGL(prepare_instance(instance == ADYPT_PROBE_PREPARE_MOMENTS, instance == ADYPT_PROBE_PREPARE_CLASS), shape.grid, shape.block, 0, 0, dc.as<float4>(), dm.as<float2>(),
 		                   db.as<int32_t>(), ds.as<int32_t>(), n_px, blocks_across(width), width, height, da.as<float4>(), dn.as<float4>(), dp.as<float4>(), dh.as<float4>(), o0.as<float4>(),
 		                   o1.as<float4>(), o2.as<float4>(), oa.as<float4>());
 	PROBE_TRY(launched());
@@ -686,7 +681,7 @@ int adypt_probe_temporal_merge_moments(int motion, const float *x0, const float 
 	const TemporalCamera cam = temporal_camera(origin, inv_proj, inv_view);
 	const LaunchShape shape = merge_launch(width, height);
 	// (the instance without motion never looks at XP, XN: they are null here, as in a context that never followed motion)
-	hipLaunchKernelGGL(motion ? k_temporal_merge_moments<true> : k_temporal_merge_moments<false>, shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(),
+	hipLaunchKernelGGL(merge_moments_instance(motion != 0), shape.grid, shape.block, 0, 0, d0.as<float4>(), d1.as<float4>(), d2.as<float4>(), da.as<float4>(),
 	                   e0.as<float4>(), e1.as<float4>(), e2.as<float4>(), ea.as<float4>(), om.as<float4>(), ol.as<float>(), width, height, have ? 1 : 0, cam, history_cap, dxp.as<float4>(),
 	                   dxn.as<float4>());
 	PROBE_TRY(launched());
@@ -736,7 +731,7 @@ int adypt_probe_chain_start(int unfold, const float *triangles, int64_t n_tris, 
 	const ChainQueue out{qo.as<float4>(), qd.as<float4>(), qc.as<uint32_t>(), seg_cap, kProbeSegStride, segments};
 	const ChainOrigin o{{origin[0], origin[1], origin[2]}, tmin};
 	const LaunchShape shape = chain_start_launch(n_px);
-	hipLaunchKernelGGL(unfold ? k_chain_start<true> : k_chain_start<false>, shape.grid, shape.block, 0, 0, scene.sc, g, db.as<int32_t>(), n_px, blocks_across(width), width, height, o, bounces,
+	hipLaunchKernelGGL(chain_start_instance(unfold != 0), shape.grid, shape.block, 0, 0, scene.sc, g, db.as<int32_t>(), n_px, blocks_across(width), width, height, o, bounces,
 	                   ds.as<float4>(), out, dc.as<ChainCounts>());
 	PROBE_TRY(launched());
 	PROBE_TRY(da.back(albedo)); PROBE_TRY(dn.back(normal)); PROBE_TRY(dp.back(position)); PROBE_TRY(dh.back(hits));
@@ -772,7 +767,7 @@ int adypt_probe_chain_step(int unfold, const float *triangles, int64_t n_tris, c
 	ChainUnfold u{unfold ? dv.get() : nullptr, {0.0f, 0.0f, 0.0f}};
 	if(unfold) for(int k = 0; k < 3; ++k) u.o[k] = origin[k];
 	const LaunchShape shape = chain_step_launch(segments, seg_cap); // (seg_cap: the most rays a segment can hold)
-	hipLaunchKernelGGL(unfold ? k_chain_step<true> : k_chain_step<false>, shape.grid, shape.block, 0, 0, scene.sc, g, in, ih.as<float4>(), n_px, bounces, tmin, ds.get(), out,
+	hipLaunchKernelGGL(chain_step_instance(unfold != 0), shape.grid, shape.block, 0, 0, scene.sc, g, in, ih.as<float4>(), n_px, bounces, tmin, ds.get(), out,
 	                   dc.as<ChainCounts>(), u);
 	PROBE_TRY(launched());
 	bool intact = true;
