@@ -179,6 +179,12 @@ class MeshBinding(Struct):
     _fields_ = [("n_vertices", C.c_int64), ("n_tris", C.c_int64), ("max_valence", C.c_int32), ("device_bytes", C.c_int64)]
 
 
+class AppearanceInfo(Struct):
+    """adypt_appearance_info."""
+    _fields_ = [("n_mats", C.c_int64), ("n_texels", C.c_int64), ("device_bytes", C.c_int64), ("reclassed", C.c_int64), ("n_textures", C.c_int32),
+                ("staged_ms", C.c_float), ("packed_ms", C.c_float), ("classified_ms", C.c_float)]
+
+
 # every symbol include/*.h declares, with its signature (tests/test_abi.py checks the export list against the headers)
 _SIGS = {
     # adypt_hip.h
@@ -344,6 +350,16 @@ _SIGS = {
     "adypt_multi_read_vertex_normals": (C.c_int, [C.c_void_p, C.c_void_p]),
     "adypt_multi_unbind_mesh": (C.c_int, [C.c_void_p]),
     "adypt_multi_get_mesh_binding": (C.c_int, [C.c_void_p, C.POINTER(MeshBinding)]),
+    # materials, textures and triangle attributes changed on the GPU
+    "adypt_set_materials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
+    "adypt_update_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
+    "adypt_set_triangle_attributes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "adypt_read_material_records": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_read_texels": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_get_appearance": (C.c_int, [C.c_void_p, C.POINTER(AppearanceInfo)]),
+    "adypt_multi_set_materials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
+    "adypt_multi_update_texture": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
+    "adypt_multi_set_triangle_attributes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     # native multi-GPU (RCCL inside the library)
     "adypt_create_multi": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int]),
     "adypt_destroy_multi": (None, [C.c_void_p]),
@@ -412,6 +428,7 @@ _SIGS = {
     "adypt_bvh_cost": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(BvhParams), C.POINTER(TreeCost)]),
     "adypt_woop_matrices": (None, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "adypt_pack_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "adypt_pack_appearance": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adypt_pose_triangles": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "adypt_pose_triangles_morph": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_int32, C.c_void_p]),

@@ -412,6 +412,42 @@ ROOT_CARD_DT = np.dtype([("q", "<f4", (8, 6)), ("scale", "<f4", 3), ("origin", "
                          ("inner_only", "<u4"), ("enabled", "<u4"), ("pad", "<u4"), ("is_inner", "u1", 8), ("bit_index", "u1", 8), ("child_bits", "u1", 8)])
 
 
+def _materials_array(who: str, materials) -> np.ndarray:
+    """The material table as bytes: a whole number of 64-byte GPUMaterial records (none is allowed)."""
+    m = np.ascontiguousarray(materials).view(np.uint8).reshape(-1)
+    if len(m) % MAT_BYTES:
+        raise ValueError("%s: the materials are not a whole number of %d-byte records" % (who, MAT_BYTES))
+    return m
+
+
+def _texture_table(who: str, textures) -> tuple:
+    """(adypt_texture array or None, count, what it points into) of a sequence of uint8 [h, w, 3] images; sizes and pointers are the library's to refuse."""
+    tex = [np.ascontiguousarray(t, dtype=np.uint8) for t in textures]
+    for t in tex:
+        if t.ndim != 3 or t.shape[2] != 3:
+            raise ValueError("%s: a texture is uint8 [height, width, 3]" % who)
+    arr = (N.Texture * max(1, len(tex)))()
+    for i, t in enumerate(tex):
+        arr[i].width, arr[i].height, arr[i].rgb = t.shape[1], t.shape[0], (t.ctypes.data if t.size else None)
+    return (C.addressof(arr) if tex else None), len(tex), [arr] + tex
+
+
+def pack_appearance(materials, textures=()) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The device's material table and texture arena of a scene, made on the host (adypt_pack_appearance; the definition: csrc/device/appearance.hpp):
+    (records uint32 [n_mats, 20], texels uint32 [words], descriptors int32 [n_textures, 4] = (offset, w, h, 0)) — what ReadMaterialRecords() and
+    ReadTexels() give after Initialize or SetMaterials with the same arrays, byte for byte."""
+    m = _materials_array("pack_appearance", materials)
+    tex, n_tex, keep = _texture_table("pack_appearance", textures)
+    args = (m.ctypes.data if len(m) else None, len(m) // MAT_BYTES, tex, n_tex)
+    words = N.lib.adypt_pack_appearance(*args, None, None, None)
+    if words < 0:
+        raise N.AdyptError(int(words), "adypt_pack_appearance: a texture without pixels, or 2^31 texels and more")
+    rec, texels, desc = np.zeros((len(m) // MAT_BYTES, 20), np.uint32), np.zeros(int(words), np.uint32), np.zeros((n_tex, 4), np.int32)
+    r = N.lib.adypt_pack_appearance(*args, rec.ctypes.data, texels.ctypes.data, desc.ctypes.data)
+    assert r == words and keep
+    return rec, texels, desc
+
+
 def decode_root_card(node: np.ndarray, allow: bool = True) -> np.ndarray:
     """adypt_decode_root_card: one 80-byte node as the ROOT_CARD_DT record k_path's shading round tests new rays against."""
     n = np.ascontiguousarray(node).view(np.uint8).reshape(-1)
@@ -1111,11 +1147,65 @@ class _Tracer:
     # ---- replacing the triangles on the GPU (adypt_set_triangles, include/adypt_hip.h; the record: csrc/device/tri_record.hpp) ----
     def SetTriangles(self, triangles: np.ndarray, cfg: Optional[N.BvhParams] = None, method: str = "ploc", radius: int = 8, split_budget: float = 0.0) -> dict:
         """Replaces ALL triangles by the given ones (uint8, n x 100 bytes as Scene.GetTriangles() gives them; any n >= 1) and builds their tree on the
-        GPU as RebuildBVH(cfg, method, radius, split_budget) would; materials, textures, camera and configuration stay.  Nothing changes when the call
+        GPU as RebuildBVH(cfg, method, radius, split_budget) would; materials and textures (SetMaterials changes those), camera and configuration stay.  Nothing changes when the call
         is refused or fails.  Leaves the tracer as Reset() does (0 spp).  Several devices: on every device.  Returns RebuildBVH's dict."""
         info = N.RebuildInfo()
         self._call("set_triangles", *_set_triangles_args("SetTriangles", triangles, cfg, method, radius, split_budget), C.byref(info))
         return info.as_dict()
+
+    # ---- materials, textures and triangle attributes changed on the GPU (adypt_set_materials ..., include/adypt_hip.h; csrc/device/appearance.hpp) ----
+    def SetMaterials(self, materials, textures=None) -> dict:
+        """Replaces the material table (uint8, n x 64 bytes as Scene.GetMaterials() gives them; any n >= 0) and, unless textures is None, ALL textures
+        (a sequence of uint8 [h, w, 3], possibly empty); every triangle is classified again.  Nothing changes when the call is refused or fails.
+        Leaves the tracer as UpdateTriangles() does (0 spp); tree, bindings and the denoiser's history stay.  Several devices: on every device.
+        Returns GetAppearance()."""
+        m = _materials_array("SetMaterials", materials)
+        tex, n_tex, keep = (None, -1, None) if textures is None else _texture_table("SetMaterials", textures)
+        self._call("set_materials", m.ctypes.data if len(m) else None, len(m) // MAT_BYTES, tex, n_tex)
+        del keep
+        return self.GetAppearance()
+
+    def UpdateTexture(self, index: int, rgb) -> dict:
+        """New texels (uint8 [h, w, 3]) for texture `index`, in place: the size must be the texture's own (another size: SetMaterials).  Leaves the
+        tracer at 0 spp.  Returns GetAppearance()."""
+        t = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if t.ndim != 3 or t.shape[2] != 3:
+            raise ValueError("UpdateTexture: a texture is uint8 [height, width, 3]")
+        self._call("update_texture", int(index), t.ctypes.data if t.size else None, t.shape[1], t.shape[0])
+        return self.GetAppearance()
+
+    def SetTriangleAttributes(self, first: int, material_ids=None, texcoords=None) -> dict:
+        """Material ids (int32 [count]) and/or texture coordinates (float32 [count, 6]) for the triangles from `first` on; class words follow the ids.
+        Ids are not checked (a bad id renders as a bad material and is counted).  Leaves the tracer at 0 spp.  Returns GetAppearance(), whose
+        'reclassed' counts the triangles whose class word changed."""
+        ids = None if material_ids is None else np.ascontiguousarray(material_ids, dtype=np.int32).reshape(-1)
+        uv = None if texcoords is None else np.ascontiguousarray(texcoords, dtype=np.float32).reshape(-1, 6)
+        if ids is not None and uv is not None and len(ids) != len(uv):
+            raise ValueError("SetTriangleAttributes: %d material ids and %d sets of texture coordinates" % (len(ids), len(uv)))
+        count = len(ids) if ids is not None else len(uv) if uv is not None else 0
+        self._call("set_triangle_attributes", int(first), count, None if ids is None else ids.ctypes.data, None if uv is None else uv.ctypes.data)
+        return self.GetAppearance()
+
+    def GetAppearance(self) -> dict:
+        """adypt_appearance_info of the (first) device: counts, device bytes, and of the last setter the reclassified triangles and its stage times."""
+        c = self._contexts()[0]
+        info = N.AppearanceInfo()
+        N.check(N.lib.adypt_get_appearance(c, C.byref(info)), c)
+        return info.as_dict()
+
+    def ReadMaterialRecords(self) -> np.ndarray:
+        """The 80-byte material records of the (first) device (uint32 [n_mats, 20])."""
+        c = self._contexts()[0]
+        rec = np.zeros((self.GetAppearance()["n_mats"], 20), dtype=np.uint32)
+        N.check(N.lib.adypt_read_material_records(c, rec.ctypes.data if len(rec) else np.zeros(1, np.uint32).ctypes.data), c)
+        return rec
+
+    def ReadTexels(self) -> np.ndarray:
+        """The texture arena of the (first) device (uint32 [n_texels]): rows of w + 1 RGBA8 words (pack_appearance)."""
+        c = self._contexts()[0]
+        out = np.zeros(max(1, self.GetAppearance()["n_texels"]), dtype=np.uint32)
+        N.check(N.lib.adypt_read_texels(c, out.ctypes.data), c)
+        return out[:self.GetAppearance()["n_texels"]]
 
     def GetTriangleCount(self) -> int:
         """The triangles the (first) device holds now."""

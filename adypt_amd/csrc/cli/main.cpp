@@ -23,6 +23,7 @@ struct Session
 	const void *tris = nullptr, *mats = nullptr, *tex = nullptr;
 	int64_t n_tris = 0, n_mats = 0;
 	int32_t n_tex = 0;
+	adypt_scene *appearance = nullptr; // --materials-from: the scene whose material table and textures the context is given before the main render
 	adypt_bvh *bvh = nullptr;
 	adypt_multi *multi = nullptr;
 	std::vector<float> pose_positions, pose_normals; // --pose: what replaces the scene's vertices and normals once the context exists
@@ -210,6 +211,15 @@ static bool load_morph_targets(Session &s)
 	return true;
 }
 
+static bool load_materials(Session &s)
+{
+	const std::string &other = s.opt.materials_from;
+	if(other.empty()) return true;
+	if(adypt_scene_load(other.c_str(), &s.appearance) != ADYPT_OK) { fprintf(stderr, "[INSTANCE]Err: Unable to load materials %s: %s\n", other.c_str(), adypt_host_last_error()); return false; }
+	if(*adypt_scene_warnings(s.appearance)) printf("[SCENE]Warn: %s", adypt_scene_warnings(s.appearance));
+	return true;
+}
+
 // the cached .bvh, or a host build that is then cached; neither with --build gpu
 static bool load_bvh(Session &s)
 {
@@ -225,7 +235,7 @@ static bool load_bvh(Session &s)
 
 static bool load_inputs(Session &s)
 {
-	return load_configs(s) && load_scene(s) && load_pose(s) && load_parts(s) && load_morph_targets(s) && load_bvh(s);
+	return load_configs(s) && load_scene(s) && load_pose(s) && load_parts(s) && load_morph_targets(s) && load_materials(s) && load_bvh(s);
 }
 
 // ---- the tracer ----
@@ -387,6 +397,20 @@ static bool commit_history_poses(Session &s)
 		if(r != ADYPT_OK) return tracer_failed(s.multi);
 		printf("[PT]INFO: history pose %s: %d spp committed\n", o.history_from[k].c_str(), o.spp);
 	}
+	return true;
+}
+
+// --materials-from: after the history poses, which show the old surfaces, and before the main render
+static bool swap_materials(Session &s)
+{
+	if(!s.appearance) return true;
+	const void *mats, *tex;
+	const int64_t n_mats = adypt_scene_materials(s.appearance, &mats);
+	const int32_t n_tex = adypt_scene_textures(s.appearance, &tex);
+	adypt_appearance_info info;
+	if(adypt_multi_set_materials(s.multi, mats, n_mats, (const adypt_texture *)tex, n_tex) != ADYPT_OK || adypt_get_appearance(adypt_multi_context(s.multi, 0), &info) != ADYPT_OK)
+		return tracer_failed(s.multi);
+	printf("[PT]MATERIALS: materials %lld textures %d reclassed %lld of %lld triangles\n", (long long)info.n_mats, (int)info.n_textures, (long long)info.reclassed, (long long)s.n_tris);
 	return true;
 }
 
@@ -640,6 +664,7 @@ static void release(Session &s)
 	adypt_destroy_multi(s.multi);
 	if(s.bvh) adypt_bvh_free(s.bvh);
 	adypt_scene_free(s.scene);
+	if(s.appearance) adypt_scene_free(s.appearance);
 	adypt_config_save(s.opt.config.c_str(), &s.cfg);
 }
 
@@ -655,7 +680,7 @@ int main(int argc, char **argv)
 	if(!follow && !move_scene(s)) return 1;
 	if(!commit_history_poses(s)) return 1;
 	if(follow && !move_scene(s)) return 1;
-	if(!back_to_the_main_view(s) || !render(s)) return 1;
+	if(!swap_materials(s) || !back_to_the_main_view(s) || !render(s)) return 1;
 	if(!report_and_save_image(s) || !report_noise(s) || !save_denoised(s) || !save_guides(s)) return 1;
 	release(s);
 	return 0;

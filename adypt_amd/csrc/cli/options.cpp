@@ -32,6 +32,11 @@
 //              refitted, its SAH cost measured, and rebuilt only where that is more than R times the cost of the tree as loaded (R finite and >= 0, no
 //              default; 0 always rebuilds).  --rebuild-method, --ploc-radius and --split-budget then name the rebuild of that policy (linear unless
 //              given) instead of asking for one outright
+//   --materials-from other.obj: the other OBJ is loaded with the scene loader and the context is given ITS material table and textures
+//              (adypt_multi_set_materials): the triangles keep their material ids, which now name the other table's entries, and are classified again.
+//              With --history-from the swap comes after the history poses have been rendered and committed and before the main render: the history
+//              shows the old light, the case --rectify is for.  One [PT]MATERIALS: line reports materials, textures and the triangles whose class
+//              changed.  A file that cannot be opened, or the option given twice, is exit 2
 //   --sun-visibility: enable the occlusion query the reference has commented out (pathtracer.glsl:132)
 //   --preview: what the reference shows in its window (shaders/screen.glsl), as PNG
 //   --devices: pixel tiles sharded over several GPUs of the node (adypt_create_multi), radiance gathered on the first one
@@ -88,7 +93,7 @@ const char *const USAGE =
 	"[--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--denoise-specular K] "
 	"[--history-from other.config]... [--history-cap C] [--history-out len.exr] [--follow-motion] [--rectify [--rectify-gamma G] [--rectify-radius R] "
 	"[--rectify-out kept.exr]] [--denoise-moments [--variance-out v.exr]] [--follow-specular K]] [--guides-out PREFIX] [--pose moved.obj [--by-vertices [--recompute-normals]] | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] "
-	"[--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu]";
+	"[--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu] [--materials-from other.obj]";
 
 // ---- values ----
 // The whole of text as one number in [lo, hi]; else `<takes>, not <text>` on stderr and false.  An integer is read as one: 2.0 is not 2.
@@ -192,6 +197,14 @@ static bool build_where(Options &o, const char *v)
 	return true;
 }
 
+static bool materials_from(Options &o, const char *v)
+{
+	if(!o.materials_from.empty()) { fprintf(stderr, "--materials-from is given twice: one table replaces the scene's\n"); return false; }
+	if(!*v) { fprintf(stderr, "--materials-from takes the name of an OBJ file\n"); return false; }
+	o.materials_from = v;
+	return true;
+}
+
 static const struct Spec { const char *name; bool value; Apply apply; } SPECS[] = {
 	{"--spp", true, lenient_int<&Options::spp>},
 	{"--out", true, text<&Options::out>},
@@ -236,6 +249,7 @@ static const struct Spec { const char *name; bool value; Apply apply; } SPECS[] 
 	{"--rebuild-method", true, [](Options &o, const char *v) { o.rebuild_method = v; return true; }},
 	{"--build", true, build_where},
 	{"--ploc-radius", true, lenient_int<&Options::ploc_radius>},
+	{"--materials-from", true, materials_from},
 	{"--split-budget", true, [](Options &o, const char *v) { o.split_budget = atof(v); return true; }},
 };
 
@@ -303,6 +317,13 @@ int check_options(Options *opt)
 	if(o.follow_specular && !(o.denoise && o.temporal)) return refuse("--follow-specular needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out");
 	if(o.follow_specular && (o.denoise_specular || o.follow_motion || o.rectify || o.denoise_moments))
 		return refuse("--follow-specular does not combine with --denoise-specular, --follow-motion, --rectify or --denoise-moments");
+
+	if(!o.materials_from.empty())
+	{
+		FILE *f = fopen(o.materials_from.c_str(), "rb");
+		if(!f) { fprintf(stderr, "--materials-from %s: the file cannot be opened\n", o.materials_from.c_str()); return 2; }
+		fclose(f);
+	}
 
 	// with --rebuild-above or --build gpu, --rebuild-method names the policy's rebuild or the first build; else naming a method asks for the rebuild
 	o.rebuild = (o.bare_rebuild || o.rebuild_method) && !above && !o.build_on_gpu;

@@ -44,6 +44,7 @@ struct Options
 	std::optional<std::string> rebuild_method;
 	std::optional<double> rebuild_above, split_budget;
 	int ploc_radius = 8;
+	std::string materials_from; // --materials-from other.obj: that scene's material table and textures, given to the context before the main render
 
 	// derived by check_options
 	bool until = false, denoise = false, temporal = false, morphing = false;

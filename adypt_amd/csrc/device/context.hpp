@@ -90,7 +90,8 @@ struct adypt_ctx {
 	Event sobol_done[kSobolSlots];
 	std::vector<EventPair> events, free_events; // kernel timing (instrumentation flag 1): pairs in flight, pairs to use again
 
-	// scene (the topology is immutable after create; adypt_update_triangles, refit.hip, rewrites positions, normals, Woop data and the boxes in place)
+	// scene (the topology is immutable after create; adypt_update_triangles, refit.hip, rewrites positions, normals, Woop data and the boxes in place;
+	// adypt_set_materials, appearance.hip, replaces the material table and the texels and rewrites the triangles' material words)
 	Buffer<uint4> d_nodes;
 	Buffer<float4> d_woop, d_triangles, d_materials;
 	Buffer<int32_t> d_tri_indices, d_local_blocks;
@@ -102,6 +103,8 @@ struct adypt_ctx {
 	std::vector<int64_t> all_blocks_offset;
 	int64_t n_nodes = 0, n_refs = 0, n_tris = 0, n_mats = 0;
 	int n_tex = 0;
+	std::vector<int32_t> tex_desc;            // host copy of the textures' descriptors (appearance.hpp): (offset, w, h, 0) each
+	int64_t n_texels = 0;                     // words of d_texels in use
 	int width = 0, height = 0, blocks_x = 0, blocks_y = 0, rank = 0, nranks = 1;
 	int n_local_blocks = 0, n_local_px = 0;
 	int64_t n_image_px = 0; // pixels of the owned blocks that lie inside the image (= camera rays per frame)

@@ -36,7 +36,7 @@ struct Attachment {
 	~Attachment() { reset(); }
 	void reset(void *q = nullptr, void (*f)(void *) = nullptr) { if(p && free_fn) free_fn(p); p = q; free_fn = f; }
 };
-enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachBuild, kAttachGeometry, kAttachPose, kAttachMesh, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes, build.hip's scratch, geometry.hip's staging, pose.hip's rest pose and binding, mesh.hip's index buffer and incidence lists
+enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachBuild, kAttachGeometry, kAttachPose, kAttachMesh, kAttachAppearance, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes, build.hip's scratch, geometry.hip's staging, pose.hip's rest pose and binding, mesh.hip's index buffer and incidence lists, appearance.hip's staging
 Attachment &ctx_attachment(adypt_ctx *c, AttachKind kind);
 
 // ---- noise statistics and adaptive sampling, per context (adypt_trace_adaptive and adypt_multi_trace_adaptive are one loop over these) ----
@@ -124,6 +124,23 @@ struct NewGeometry {
 // ctx_replace_bvh that takes the triangles the tree was built of as well: records, class bytes, tree, per-reference copy and the triangle count change
 // together or not at all
 int ctx_replace_geometry(adypt_ctx *c, NewGeometry *geometry, Buffer<uint4> *nodes, Buffer<int32_t> *tri_indices, Buffer<float4> *woop, int64_t n_nodes, int64_t n_refs);
+// ---- changing what the surfaces look like (appearance.hip), per context: see tracer.hip ----
+// what appearance.hip rewrites in place or reads out: the arrays as they are now
+struct CtxAppearance {
+	float4 *materials;            // n_mats records of mat_float4 float4
+	uint32_t *texels;             // n_texels words (appearance.hpp)
+	uint8_t *tri_class;           // n_tris bytes, or null where the context keeps none
+	float4 *ref_triangles;        // n_refs records, or null where the context keeps no per-reference copy
+	const int32_t *tex_desc;      // HOST: n_textures descriptors (offset, w, h, 0)
+	int64_t n_mats, n_texels;
+	int n_textures, mat_float4;
+	size_t device_bytes;          // of the table and the arena
+	bool expand_whole;            // ADYPT_APPEARANCE_EXPAND=1 (measurement): the whole per-reference copy is made again, not k_ref_attributes' part of it
+};
+CtxAppearance ctx_appearance(adypt_ctx *c);
+// The material table, and with `texels` the texture arena and its descriptors, replaced by new ones that are complete on the context's stream: table,
+// arena, n_mats and n_tex change in one step, which cannot fail; the old arrays go back with the caller's owners.  texels null: the textures stay.
+void ctx_replace_appearance(adypt_ctx *c, Buffer<float4> *materials, int64_t n_mats, Buffer<uint32_t> *texels, std::vector<int32_t> *tex_desc, int64_t n_texels);
 // the reason adypt_last_error(NULL) gives on this thread: of a create that returned no context
 void ctx_set_create_error(const std::string &msg);
 // multi.hip: the message adypt_multi_last_error answers

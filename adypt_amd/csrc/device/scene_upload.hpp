@@ -61,6 +61,7 @@ int upload_textures_and_materials(adypt_ctx *c, const adypt_scene_desc *d)
 		}
 	}
 	TRY_CREATE(upload(c, &c->d_texels, texels.data(), texels.size()));
+	c->n_texels = (int64_t)texels.size(); c->tex_desc = desc; // (what adypt_update_texture and adypt_read_texels go by: appearance.hip)
 	// materials: the reference's 64 bytes + the descriptor of the diffuse texture (one fetch less per textured hit)
 	std::vector<uint8_t> mats((size_t)std::max<int64_t>(d->n_mats, 1) * kMatFloat4 * 16, 0);
 	for(int64_t m = 0; m < d->n_mats; ++m)

@@ -648,7 +648,7 @@ Tunables read_tunables()
 	t.frames_in_flight = (int)num("ADYPT_FRAMES_IN_FLIGHT", 1, kMaxFramesInFlight, 0);
 	t.pipeline = (int)num("ADYPT_PIPELINE", 1, kMaxPipes, kDefaultPipes);
 	t.fused_bounces = flag("ADYPT_FUSED_BOUNCES", 1); t.first_fused = flag("ADYPT_FIRST_FUSED", 1); t.single_fused = flag("ADYPT_SINGLE_FUSED", 1);
-	t.gen_deal = flag("ADYPT_GEN_DEAL", 1); t.shade_bin = flag("ADYPT_SHADE_BIN", 0); t.single_overlap = flag("ADYPT_SINGLE_OVERLAP", 1);
+	t.gen_deal = flag("ADYPT_GEN_DEAL", 1); t.shade_bin = flag("ADYPT_SHADE_BIN", 0); t.appearance_expand = flag("ADYPT_APPEARANCE_EXPAND", 0); t.single_overlap = flag("ADYPT_SINGLE_OVERLAP", 1);
 	t.refill_min = (int)num("ADYPT_REFILL_MIN", 1, 64, 0); t.refill_min_primary = (int)num("ADYPT_REFILL_MIN_PRIMARY", 1, 64, 0);
 	t.bite = (int)num("ADYPT_BITE", 1, 4096, 0); t.bite_primary = (int)num("ADYPT_BITE_PRIMARY", 1, 4096, 0);
 	t.chunk = (int)num("ADYPT_CHUNK", 16, 4096, 0); t.endgame = (int)num("ADYPT_ENDGAME", 0, 1024, -1);
@@ -813,6 +813,22 @@ int ctx_replace_bvh(adypt_ctx *c, Buffer<uint4> *nodes, Buffer<int32_t> *tri_ind
 CtxMaterials ctx_materials(adypt_ctx *c)
 {
 	return CtxMaterials{(const float4 *)c->d_materials, c->n_mats, c->n_tex, kMatFloat4, c->tun.shade_bin != 0, (const uint32_t *)c->d_texels};
+}
+// ---- what changing the appearance (appearance.hip) needs of a context ----
+CtxAppearance ctx_appearance(adypt_ctx *c)
+{
+	return CtxAppearance{c->d_materials, c->d_texels, c->tun.shade_bin ? c->d_tri_class.get() : nullptr, c->d_ref_triangles, c->tex_desc.data(), c->n_mats, c->n_texels, c->n_tex, kMatFloat4,
+	                     c->d_materials.bytes() + c->d_texels.bytes(), c->tun.appearance_expand != 0};
+}
+void ctx_replace_appearance(adypt_ctx *c, Buffer<float4> *materials, int64_t n_mats, Buffer<uint32_t> *texels, std::vector<int32_t> *tex_desc, int64_t n_texels)
+{
+	std::swap(c->d_materials, *materials);
+	c->n_mats = n_mats;
+	if(!texels) return;
+	std::swap(c->d_texels, *texels);
+	c->tex_desc.swap(*tex_desc);
+	c->n_tex = (int)(c->tex_desc.size() / 4);
+	c->n_texels = n_texels;
 }
 void ctx_set_create_error(const std::string &msg) { g_create_error = msg; }
 // ctx_replace_bvh, and with `geometry` the triangles the tree was built of as well (packed by k_pack_triangles, complete on the context's stream): the

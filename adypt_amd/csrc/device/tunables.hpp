@@ -24,6 +24,7 @@
 //   ADYPT_PATH_LDS_DEPTH          path_lds_depth         1..kLdsStackMax  auto    LDS part of k_path's stack
 //   ADYPT_PATH_VERBOSE            path_verbose           0/1            0         print k_path's launch geometry
 //   ADYPT_REF_TRIANGLES_MAX_MB    ref_triangles_max_mb   0..2^20        auto      per-reference triangle copy for k_path only below this size (0 = never)
+//   ADYPT_APPEARANCE_EXPAND       appearance_expand      0/1            0         the appearance setters make the whole per-reference copy again (measurement: tools/appearance_cost.py)
 //   ADYPT_RCCL_LIB                rccl_lib               path           ""        librccl to dlopen first (adypt_amd/_native.py: the one bundled with torch)
 //   ADYPT_GATHER_TIMEOUT          gather_timeout_s       0..86400       120       watchdog of the multi-GPU gather (0 = none): the process exits non-zero
 //
@@ -43,7 +44,7 @@ namespace adypt {
 struct Tunables {
 	int frames_in_flight = 0;       // 0 = automatic
 	int pipeline = 1;
-	int fused_bounces = 1, first_fused = 1, single_fused = 1, single_overlap = 1, gen_deal = 1, shade_bin = 0;
+	int fused_bounces = 1, first_fused = 1, single_fused = 1, single_overlap = 1, gen_deal = 1, shade_bin = 0, appearance_expand = 0;
 	int refill_min = 0, refill_min_primary = 0, bite = 0, bite_primary = 0, chunk = 0, endgame = -1, shade_min = 0, rare_min = -1, defer_max = -1; // 0 (endgame, rare_min, defer_max: -1) = the built-in default
 	int lds_stack_depth = 0, trace_blocks_per_cu = 0, path_blocks_per_cu = 0, path_lds_depth = 0, path_verbose = 0;
 	long ref_triangles_max_mb = -1; // -1 = automatic

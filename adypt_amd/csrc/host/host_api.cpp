@@ -7,6 +7,7 @@
 #include "../device/presplit.hpp"
 #include "../device/root_card.hpp"
 #include "../device/tri_record.hpp"
+#include "../device/appearance.hpp"
 #include "../../../include/adypt_hip.h"
 
 #include <algorithm>
@@ -488,6 +489,45 @@ int adypt_pack_triangles(const void *triangles, int64_t n_tris, const void *mate
 	}
 	});
 	return ADYPT_OK;
+}
+
+int64_t adypt_pack_appearance(const void *materials, int64_t n_mats, const void *textures, int32_t n_textures, void *records_out, uint32_t *texels_out, int32_t *desc_out)
+{
+	if(n_mats < 0 || n_textures < 0 || (n_mats > 0 && !materials) || (n_textures > 0 && !textures)) return ADYPT_E_INVALID;
+	// (../device/appearance.hpp: the text adypt_set_materials and k_pack_texels compile too)
+	const adypt_texture *tex = (const adypt_texture *)textures;
+	std::vector<int32_t> wh((size_t)n_textures * 2), desc((size_t)n_textures * kTexDescWords);
+	for(int32_t t = 0; t < n_textures; ++t)
+	{
+		if(!tex[t].rgb) return ADYPT_E_INVALID;
+		wh[2 * t] = tex[t].width; wh[2 * t + 1] = tex[t].height;
+	}
+	int64_t arena = 0;
+	if(appearance_describe(wh.data(), n_textures, desc.data(), &arena)) return ADYPT_E_INVALID;
+	if(desc_out && n_textures) memcpy(desc_out, desc.data(), desc.size() * sizeof(int32_t));
+	if(texels_out)
+		for(int32_t t = 0; t < n_textures; ++t)
+		{
+			uint32_t *out = texels_out + desc[t * kTexDescWords];
+			const uint32_t w = (uint32_t)tex[t].width, n = w * (uint32_t)tex[t].height;
+			for(uint32_t p = 0; p < n; ++p)
+			{
+				const uint8_t *in = tex[t].rgb + (size_t)p * 3;
+				bool wraps;
+				const uint32_t at = texel_place(p, w, &wraps), word = texel_word(in[0], in[1], in[2]);
+				out[at] = word;
+				if(wraps) out[at + w] = word;
+			}
+		}
+	if(records_out)
+		for(int64_t m = 0; m < n_mats; ++m)
+		{
+			uint32_t src[kMatSourceWords], rec[kMatRecordWords];
+			memcpy(src, (const uint8_t *)materials + (size_t)m * kMatSourceBytes, sizeof(src));
+			for(int k = 0; k < kMatRecordWords; ++k) rec[k] = material_record_word(src, k, n_textures, desc.data());
+			memcpy((uint8_t *)records_out + (size_t)m * kMatRecordBytes, rec, sizeof(rec));
+		}
+	return arena;
 }
 
 void adypt_camera_matrices(float fov, float yaw, float pitch, int width, int height, float inv_proj[16], float inv_view[16])

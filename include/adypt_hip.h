@@ -482,7 +482,7 @@ int adypt_get_denoise_virtual(adypt_ctx *ctx, adypt_denoise_virtual *out);
  * replaces the positions (count x 9 floats: p0 p1 p2 of every triangle) and, unless normals is NULL, the normals (count x 9 floats) of triangles
  * [first, first + count), and then ALWAYS recomputes the Woop data of every reference and refits every node, bottom up, on the GPU: the exact rule is
  * csrc/device/refit.hpp, which the host's adypt_bvh_refit compiles too — adypt_read_bvh afterwards equals adypt_bvh_refit + adypt_woop_matrices of the
- * moved triangles byte for byte (the 12 Woop floats of a degenerate triangle are NaN on both sides; a NaN's sign and payload are the processor's).  Material ids and texture coordinates stay.  The context is drained first (frames enqueued earlier finish with the old
+ * moved triangles byte for byte (the 12 Woop floats of a degenerate triangle are NaN on both sides; a NaN's sign and payload are the processor's).  Material ids and texture coordinates stay (adypt_set_triangle_attributes changes those).  The context is drained first (frames enqueued earlier finish with the old
  * pose) and is left as adypt_reset leaves it: 0 spp, frozen blocks thawed, frames parked ahead dropped, the primary-hit cache invalid.  A refitted tree
  * renders the moved scene correctly but is slower to traverse than a rebuilt one, the more the further the pose is from the one the tree was built
  * for, and more so for trees built with spatial splits (Moving geometry): rebuild for poses that are far away — adypt_update_triangles_auto
@@ -562,7 +562,7 @@ int adypt_read_tri_indices(adypt_ctx *ctx, int32_t *out);
  * adypt_rebuild_bvh (method 0; radius is not looked at, split_budget must be 0), adypt_rebuild_bvh_ploc or adypt_rebuild_bvh_ploc_split (method 1) would:
  * afterwards adypt_read_bvh and adypt_read_tri_indices equal the host's adypt_bvh_build_linear / _ploc / _ploc_split of those triangles and
  * adypt_woop_matrices of them byte for byte, and adypt_read_triangle_records equals adypt_pack_triangles (adypt_host.h; the definition is
- * csrc/device/tri_record.hpp, compiled by both).  Materials, textures, image, camera, parameters and every switch of the context stay; material ids are
+ * csrc/device/tri_record.hpp, compiled by both).  Materials and textures (which adypt_set_materials replaces), image, camera, parameters and every switch of the context stay; material ids are
  * not checked, as adypt_create does not check them (a bad id renders as a bad material and is counted).
  * In this order: the arguments are checked; the context is drained; the caller's array is copied to a staging buffer on the device; k_pack_triangles
  * writes the records (and the class bytes of ADYPT_SHADE_BIN=1) into new arrays; the tree is built from those; only then does the context take records,
@@ -735,6 +735,45 @@ int adypt_read_vertex_normals(adypt_ctx *ctx, float *normals /* n_vertices x 3: 
 int adypt_get_mesh_timing(adypt_ctx *ctx, float *ms, int capacity);
 int adypt_unbind_mesh(adypt_ctx *ctx);
 int adypt_get_mesh_binding(adypt_ctx *ctx, adypt_mesh_binding *out);
+
+/* ---- appearance: materials, textures and the triangles' material words, changed on the device -------------------------------------------------
+ * What a surface looks like can change as geometry and camera can, without a new context: a lamp switched on, a colour that fades, a texture that
+ * scrolls, triangles given another material.  The definition of the bytes is csrc/device/appearance.hpp, which the host's adypt_pack_appearance
+ * (adypt_host.h) compiles too: adypt_read_material_records and adypt_read_texels afterwards equal what it gives, and what adypt_create makes of the
+ * same arrays, byte for byte.
+ * adypt_set_materials replaces the material table (n_mats x 64-byte GPUMaterial, any n_mats >= 0) and, with n_textures >= 0, ALL textures;
+ * textures NULL with n_textures -1 keeps the textures.  In this order: the arguments are checked; the context is drained; the caller's RGB8 bytes are
+ * copied to a staging buffer as they are and k_pack_texels writes the padded rows into a NEW arena; the new table is uploaded into a NEW buffer; every
+ * triangle's class word (and class byte, ADYPT_SHADE_BIN=1) is written again from the new table (k_tri_attributes), the per-reference copy following;
+ * only then does the context take table, arena and both counts, in one step.
+ * adypt_update_texture writes new texels into texture `index` in place: width and height must be the texture's own.  Nothing else changes.
+ * adypt_set_triangle_attributes gives the triangles [first, first + count) material ids (int32 each) and/or texture coordinates (6 floats each, as in
+ * the 100-byte Triangle); either array may be NULL, not both.  Ids are not checked, as adypt_create does not check them (a bad id renders as a bad
+ * material and is counted).  Class word and class byte of the range follow the ids.
+ * All three: ADYPT_E_INVALID — a null array, n_mats < 0, a texture without pixels or without rgb, 2^31 texels and more, an index or a range outside
+ * what the context holds, another size in adypt_update_texture — is found before anything is touched, and ADYPT_E_OOM before anything of the context is
+ * written: a refused or failed call changes nothing.  The context is drained first and is left as adypt_update_triangles leaves it: 0 spp, frozen
+ * blocks thawed, frames parked ahead dropped, the primary-hit cache started again.  The tree, the Woop data, pose, morph and mesh bindings, the
+ * reference cost of adypt_update_triangles_auto and the denoiser's history and snapshot stay: the history's albedo test drops a repainted surface, and
+ * adypt_denoise_temporal_rectified is for the light that changed on a surface that stands still.
+ * Memory: at the peak of adypt_set_materials the old and the new table and arena exist side by side; the staging buffers (3 B per texel of a call, 28 B
+ * per triangle of a range) are kept at their largest. */
+typedef struct adypt_appearance_info {
+	int64_t n_mats;
+	int64_t n_texels;            /* words of the arena */
+	int64_t device_bytes;        /* table, arena and the staging buffers */
+	int64_t reclassed;           /* triangles whose class word the last setter changed */
+	int32_t n_textures;
+	float staged_ms, packed_ms, classified_ms; /* HIP-event times of the last setter: the staging copies, k_pack_texels, k_tri_attributes and the per-reference copy */
+} adypt_appearance_info;
+int adypt_set_materials(adypt_ctx *ctx, const void *materials /* n_mats x 64 bytes */, int64_t n_mats, const adypt_texture *textures, int32_t n_textures /* -1 with NULL: kept */);
+int adypt_update_texture(adypt_ctx *ctx, int32_t index, const uint8_t *rgb /* width x height x 3 */, int32_t width, int32_t height);
+int adypt_set_triangle_attributes(adypt_ctx *ctx, int64_t first, int64_t count, const int32_t *material_ids /* count, or NULL */, const float *texcoords /* count x 6, or NULL */);
+/* the device's material records as they are now: n_mats x 80 bytes */
+int adypt_read_material_records(adypt_ctx *ctx, void *out);
+/* the texture arena as it is now: adypt_appearance_info::n_texels words */
+int adypt_read_texels(adypt_ctx *ctx, uint32_t *out);
+int adypt_get_appearance(adypt_ctx *ctx, adypt_appearance_info *out);
 
 /* Trace an arbitrary batch of rays through the same traversal kernel: rays = n x 8 floats
  * (ox, oy, oz, tmin, dx, dy, dz, unused).  with_stats selects the instrumented kernel variant. */
@@ -912,6 +951,11 @@ int adypt_multi_pose_vertices(adypt_multi *m, const float *positions, const floa
 int adypt_multi_read_vertex_normals(adypt_multi *m, float *normals);
 int adypt_multi_unbind_mesh(adypt_multi *m);
 int adypt_multi_get_mesh_binding(adypt_multi *m, adypt_mesh_binding *out);
+/* adypt_set_materials / adypt_update_texture / adypt_set_triangle_attributes on every device, in device order: the scene is replicated; no collective.
+ * Bad arguments are refused by the first device, so no device has changed.  The read-outs are per context: adypt_multi_context(m, k). */
+int adypt_multi_set_materials(adypt_multi *m, const void *materials, int64_t n_mats, const adypt_texture *textures, int32_t n_textures);
+int adypt_multi_update_texture(adypt_multi *m, int32_t index, const uint8_t *rgb, int32_t width, int32_t height);
+int adypt_multi_set_triangle_attributes(adypt_multi *m, int64_t first, int64_t count, const int32_t *material_ids, const float *texcoords);
 /* creates the RCCL communicators now (otherwise: at the first gather, and only when n_dev > 1); lets a caller — and the
  * one-GPU test — find out at start-up whether RCCL is usable */
 int adypt_multi_comm_init(adypt_multi *m);

@@ -160,6 +160,15 @@ void adypt_woop_matrices(const void *tris, const int32_t *tri_indices, int64_t n
  * outside [0, n_mats)).  Either may be NULL.  materials: n_mats 64-byte GPUMaterial.  The definition is csrc/device/tri_record.hpp, which the device
  * (adypt_set_triangles of adypt_hip.h) compiles too: both give the same bytes.  ADYPT_E_INVALID for a null array that is needed or a negative count. */
 int adypt_pack_triangles(const void *triangles, int64_t n_tris, const void *materials, int64_t n_mats, int32_t n_textures, void *records_out, uint8_t *classes_out);
+/* The device's material table and texture arena of a scene: records_out = n_mats x 80 bytes — a material's 64 bytes, then (texel offset, w, h, 0) of its
+ * diffuse texture where 0 <= dtex < n_textures, else 16 zero bytes; texels_out = the arena's words — texture after texture, back to back, each h rows of
+ * w + 1 words r | g << 8 | b << 16 | 0xff000000, a row's last word a copy of its first; desc_out = n_textures x (offset, w, h, 0).  Any output may be
+ * NULL.  textures: n_textures adypt_texture (adypt_hip.h).  Returns the arena's length in words (below 2^31), so a first call with NULL outputs gives
+ * the size of texels_out.  The definition is csrc/device/appearance.hpp, which the device (adypt_set_materials, adypt_update_texture of adypt_hip.h)
+ * compiles too: both give the same bytes.  ADYPT_E_INVALID — nothing is written — for a null array that is needed, a negative count, a texture
+ * without pixels or 2^31 texels and more. */
+int64_t adypt_pack_appearance(const void *materials, int64_t n_mats, const void *textures /* adypt_texture[] */, int32_t n_textures, void *records_out, uint32_t *texels_out,
+                              int32_t *desc_out);
 /* `n_tris` 100-byte Triangles posed by row-major 3x4 matrices (n_matrices x 12 floats, n_matrices in [1, 65536]): positions through the matrix, normals
  * through its cofactor matrix and normalised again, texture coordinates and material id as they are; triangles_out = n_tris x 100 bytes, which may be
  * triangles_in.  Either parts (one index per triangle) or joints and weights (n_tris x 12 each: vertex v's four slots at 4 v; a slot of weight 0 is

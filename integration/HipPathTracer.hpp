@@ -33,8 +33,7 @@ public:
 	enum ViewerTypes { kDiffuse = 0, kSpecular, kEmissive, kPTRadiance, kNormal, kPosition };
 	ViewerTypes m_viewer_type = kDiffuse;
 
-private:
-	// the 64-byte record uuMaterials holds (shaders/pathtracer.glsl:10-19)
+	// the 64-byte record uuMaterials holds (shaders/pathtracer.glsl:10-19): what SetMaterials takes
 	struct GPUMaterial
 	{
 		int32_t m_dtex; float m_dr, m_dg, m_db;
@@ -44,12 +43,22 @@ private:
 	};
 	static_assert(sizeof(GPUMaterial) == 64, "material record layout");
 
+private:
+
 	adypt_multi *m_gpus = nullptr; // one tile shard per device; a single device is the n_dev = 1 case of the same calls
 	const InstanceConfig::PT *m_config = nullptr;
 	int m_width = 0, m_height = 0;
 	std::vector<GPUMaterial> m_materials;
 	std::vector<adypt_texture> m_textures;
 	std::vector<unsigned char *> m_texture_pixels; // stbi_load results, freed in the destructor
+
+	// the end of SetMaterials, UpdateTexture and SetTriangleAttributes
+	bool appearance_done(int code, adypt_appearance_info *info)
+	{
+		if(code == ADYPT_OK && (!info || adypt_get_appearance(adypt_multi_context(m_gpus, 0), info) == ADYPT_OK)) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
 
 	// diffuse textures are shared by name; 8-bit RGB, first row = top (Scene.cpp flips v at load)
 	int load_texture(std::map<std::string, int> &by_name, const std::string &filename)
@@ -389,6 +398,34 @@ public:
 		return false;
 	}
 	bool UnbindMesh() { return adypt_multi_unbind_mesh(m_gpus) == ADYPT_OK; }
+
+	// What the surfaces look like, changed on the GPU without a new context (adypt_hip.h, adypt_set_materials / adypt_update_texture /
+	// adypt_set_triangle_attributes): a lamp switched on, a colour that fades, a texture that scrolls, triangles given another material.  SetMaterials
+	// replaces the material table (any number of entries) and, with a texture list, ALL textures (width x height x 3 bytes each, which only have to
+	// live until the call returns); without one the textures stay.  UpdateTexture writes new texels into one texture in place: its own size.
+	// SetTriangleAttributes gives the triangles from `first` on material ids and / or texture coordinates (6 floats per triangle); an empty vector
+	// leaves that attribute alone.  Tree, bindings and the denoiser's history stay; nothing changes when a call fails.  The sample counter restarts as
+	// after UpdateTriangles.  *info (may be nullptr): the first device's counts, the triangles whose class changed, and the stage times.
+	bool SetMaterials(const std::vector<GPUMaterial> &materials, adypt_appearance_info *info = nullptr)
+	{
+		static_assert(sizeof(GPUMaterial) == 64, "GPUMaterial is the 64-byte record adypt_set_materials takes");
+		return appearance_done(adypt_multi_set_materials(m_gpus, materials.data(), (int64_t)materials.size(), nullptr, -1), info);
+	}
+	bool SetMaterials(const std::vector<GPUMaterial> &materials, const std::vector<adypt_texture> &textures, adypt_appearance_info *info = nullptr)
+	{
+		return appearance_done(adypt_multi_set_materials(m_gpus, materials.data(), (int64_t)materials.size(), textures.data(), (int32_t)textures.size()), info);
+	}
+	bool UpdateTexture(int32_t index, const uint8_t *rgb, int32_t width, int32_t height, adypt_appearance_info *info = nullptr)
+	{
+		return appearance_done(adypt_multi_update_texture(m_gpus, index, rgb, width, height), info);
+	}
+	bool SetTriangleAttributes(int64_t first, const std::vector<int32_t> &material_ids, const std::vector<float> &texcoords = std::vector<float>(), adypt_appearance_info *info = nullptr)
+	{
+		const bool shaped = texcoords.size() % 6 == 0 && (material_ids.empty() || texcoords.empty() || texcoords.size() == 6 * material_ids.size());
+		if(!shaped) { printf("[PT]ERR: SetTriangleAttributes: six texture coordinates per triangle, as many triangles as material ids\n"); return false; }
+		const int64_t count = (int64_t)(material_ids.empty() ? texcoords.size() / 6 : material_ids.size());
+		return appearance_done(adypt_multi_set_triangle_attributes(m_gpus, first, count, material_ids.empty() ? nullptr : material_ids.data(), texcoords.empty() ? nullptr : texcoords.data()), info);
+	}
 
 	// The image through the denoiser with its history across poses (adypt_hip.h, adypt_denoise_temporal): W x H x 3 floats into *rgb.  Needs
 	// SetNoiseStats(true) and GetSPP() >= 2.  commit: this call's state becomes the history (once per pose: after tracing, before the camera or the

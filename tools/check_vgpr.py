@@ -32,7 +32,7 @@ def kernels(src):
 
 def main():
     bad = []
-    for src in ("device/tracer.hip", "device/multi.hip", "device/denoise.hip", "device/refit.hip", "device/build.hip", "device/geometry.hip", "device/pose.hip", "device/mesh.hip"):
+    for src in ("device/tracer.hip", "device/multi.hip", "device/denoise.hip", "device/refit.hip", "device/build.hip", "device/geometry.hip", "device/pose.hip", "device/mesh.hip", "device/appearance.hip"):
         for name, n, uses, private in sorted(kernels(src)):
             flag = "  scratch: %d B per lane" % private if private else ""
             if uses:
