@@ -76,6 +76,19 @@ class Adaptive(C.Structure):
         return d
 
 
+class HistoryPlanParams(C.Structure):
+    """adypt_history_plan_params."""
+    _fields_ = [("target", C.c_int32), ("min_spp", C.c_int32), ("max_spp", C.c_int32), ("step", C.c_int32), ("tolerance_permille", C.c_int32),
+                ("history_cap", C.c_float), ("follow_motion", C.c_int32), ("moments", C.c_int32)]
+
+
+class HistoryPlan(Struct):
+    """adypt_history_plan: what adypt_plan_by_history and adypt_trace_by_history report."""
+    _fields_ = [("blocks", C.c_int32), ("want_min", C.c_int32), ("want_max", C.c_int32), ("spp", C.c_int32), ("pixels", C.c_int64),
+                ("pixels_with_history", C.c_int64), ("pixel_samples", C.c_int64), ("mean_reach", C.c_double), ("capture_ms", C.c_float),
+                ("reach_ms", C.c_float), ("device_bytes", C.c_int64)]
+
+
 class DenoiseParams(C.Structure):
     """adypt_denoise_params."""
     _fields_ = [("levels", C.c_int32), ("sigma_l", C.c_float), ("sigma_z", C.c_float)]
@@ -236,6 +249,16 @@ _SIGS = {
     "adypt_trace_until": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Noise)]),
     "adypt_trace_adaptive": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Adaptive)]),
     "adypt_read_block_spp": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "adypt_plan_by_history": (C.c_int, [C.c_void_p, C.POINTER(HistoryPlanParams), C.POINTER(HistoryPlan)]),
+    "adypt_trace_by_history": (C.c_int, [C.c_void_p, C.POINTER(HistoryPlanParams), C.POINTER(HistoryPlan)]),
+    "adypt_read_history_reach": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_read_sample_plan": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "adypt_read_history_bins": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "adypt_multi_plan_by_history": (C.c_int, [C.c_void_p, C.POINTER(HistoryPlanParams), C.POINTER(HistoryPlan)]),
+    "adypt_multi_trace_by_history": (C.c_int, [C.c_void_p, C.POINTER(HistoryPlanParams), C.POINTER(HistoryPlan)]),
+    "adypt_multi_read_history_reach": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "adypt_multi_read_sample_plan": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "adypt_multi_read_history_bins": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "adypt_multi_trace_adaptive": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Adaptive)]),
     "adypt_multi_set_noise_stats": (C.c_int, [C.c_void_p, C.c_int]),
     "adypt_multi_get_noise": (C.c_int, [C.c_void_p, C.POINTER(Noise)]),

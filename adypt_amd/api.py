@@ -784,6 +784,56 @@ class _Tracer:
             out[by * 32:(by + 1) * 32, bx * 32:(bx + 1) * 32] = n
         return out
 
+    # ---- history-aware sampling (adypt_plan_by_history, include/adypt_hip.h; the definition: csrc/device/history_reach.hpp) ----
+    def _by_history(self, name, target, min_spp, max_spp, step, tolerance_permille, history_cap, follow_motion, moments) -> dict:
+        prm = N.HistoryPlanParams(target, min_spp, max_spp, step, tolerance_permille, history_cap, 1 if follow_motion else 0, 1 if moments else 0)
+        out = N.HistoryPlan()
+        self._call(name, C.byref(prm), C.byref(out))
+        return out.as_dict()
+
+    def PlanByHistory(self, target: int, min_spp: int = 2, max_spp: int = 64, step: int = 4, tolerance_permille: int = 31,
+                      history_cap: float = 64.0, follow_motion: bool = False, moments: bool = False) -> dict:
+        """Before the first sample of a pose (GetSPP() == 0, nothing frozen, the camera set, the noise statistics on): captures the primary-hit guides,
+        works out how many samples of history Denoise(temporal=True[, follow_motion][, moments]) WILL find at every pixel (ReadHistoryReach) and gives
+        every 32x32 block the smallest sample count of min_spp, min_spp + step, ..., max_spp that leaves at most tolerance_permille / 1000 of its hit
+        pixels below `target` samples of history and own samples together (ReadSamplePlan).  Traces nothing, freezes nothing, and leaves the history
+        and every later Denoise() as they were.  Not covered: rectify (the plan may overestimate the history there) and follow_specular.
+        blocks, want_min, want_max, spp, pixels, pixels_with_history, pixel_samples, mean_reach, capture_ms, reach_ms, device_bytes."""
+        return self._by_history("plan_by_history", target, min_spp, max_spp, step, tolerance_permille, history_cap, follow_motion, moments)
+
+    def TraceByHistory(self, target: int, min_spp: int = 2, max_spp: int = 64, step: int = 4, tolerance_permille: int = 31,
+                       history_cap: float = 64.0, follow_motion: bool = False, moments: bool = False) -> dict:
+        """PlanByHistory, then the tracing it asks for: the distinct sample counts in ascending order, the blocks of each frozen at it (a frozen block
+        holds the bits of the uniform image at its count), the blocks of the largest left active.  ReadBlockSPP() is ReadSamplePlan() afterwards."""
+        self.m_viewer_type = ViewerTypes.kPTRadiance
+        return self._by_history("trace_by_history", target, min_spp, max_spp, step, tolerance_permille, history_cap, follow_motion, moments)
+
+    def ReadHistoryReach(self) -> np.ndarray:
+        """H x W float32: the samples of history every pixel will find, of the last plan (0: a miss, or no history)."""
+        r = np.zeros((self.height, self.width), dtype=np.float32)
+        self._call("read_history_reach", r.ctypes.data)
+        return r
+
+    def _read_plan(self, name: str, per_block: int, dtype) -> Tuple[np.ndarray, np.ndarray]:
+        n = self._fn(name)(self._h, None, None, 0)
+        if n < 0:
+            self._check(int(n))
+        idx, v = np.zeros(n, dtype=np.int32), np.zeros((n, per_block) if per_block > 1 else n, dtype=dtype)
+        if n:
+            r = self._fn(name)(self._h, idx.ctypes.data, v.ctypes.data, n)
+            if r < 0:
+                self._check(int(r))
+        return idx, v
+
+    def ReadSamplePlan(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(block index int32, planned sample count int32) of every 32x32 block of the last plan, ascending block index."""
+        return self._read_plan("read_sample_plan", 1, np.int32)
+
+    def ReadHistoryBins(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(block index int32, bins uint32 (blocks, 65)) of the last plan: bins[i, k] = the hit pixels of block i inside the image whose reach has
+        floor k (k == 64: a reach of 64 or more)."""
+        return self._read_plan("read_history_bins", 65, np.uint32)
+
     # ---- denoising (adypt_denoise, include/adypt_hip.h; the definition: csrc/device/denoise.hpp); several devices: of the whole image ----
     def Denoise(self, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 0.1, temporal: bool = False, history_cap: float = 64.0,
                 commit: bool = True, follow_motion: bool = False, rectify: bool = False, rectify_radius: int = 3, rectify_gamma: float = 1.0,

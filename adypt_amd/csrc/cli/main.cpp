@@ -42,6 +42,7 @@ struct Session
 	std::vector<uint8_t> rgba8;
 	adypt_noise noise;
 	adypt_adaptive adapt;
+	adypt_history_plan plan;
 	double render_ms = 0.0; // wall time of the render without its progressive saves
 };
 
@@ -466,7 +467,14 @@ static bool render(Session &s)
 	int r = ADYPT_OK;
 	memset(&s.noise, 0, sizeof(s.noise));
 	memset(&s.adapt, 0, sizeof(s.adapt));
-	if(o.adaptive)
+	memset(&s.plan, 0, sizeof(s.plan));
+	if(o.history_samples)
+	{
+		// by the history: --spp is the cap, every block stops where history and own samples together reach the target
+		const adypt_history_plan_params by_history{*o.history_samples, 2, o.spp, o.history_step, o.history_tolerance, s.temporal_params.history_cap, o.follow_motion ? 1 : 0, o.denoise_moments ? 1 : 0};
+		r = adypt_multi_trace_by_history(multi, &by_history, &s.plan);
+	}
+	else if(o.adaptive)
 	{
 		r = adypt_multi_trace_adaptive(multi, o.noise_target, o.min_spp, o.spp, o.check_every, &s.adapt);
 		s.noise = s.adapt.noise;
@@ -539,6 +547,34 @@ static bool pixel_spp(const Session &s, std::vector<float> *count_of)
 		for(size_t b = 0; b < index.size(); ++b)
 			for(int y = (index[b] / blocks_x) * 32; y < std::min(h, (index[b] / blocks_x + 1) * 32); ++y)
 				for(int x = (index[b] % blocks_x) * 32; x < std::min(w, (index[b] % blocks_x + 1) * 32); ++x) (*count_of)[(size_t)y * w + x] = (float)count[b];
+	}
+	return true;
+}
+
+// --history-samples: its line and its images
+static bool report_plan(Session &s)
+{
+	const Options &o = s.opt;
+	if(!o.history_samples) return true;
+	const adypt_history_plan &plan = s.plan;
+	printf("[PT]PLAN: blocks %d want %d..%d pixel_samples %lld (uniform %lld) with_history %lld of %lld mean_reach %.3f\n", plan.blocks, plan.want_min, plan.want_max, (long long)plan.pixel_samples,
+	       (long long)*o.history_samples * plan.pixels, (long long)plan.pixels_with_history, (long long)plan.pixels, plan.mean_reach);
+	if(!o.reach_out.empty())
+	{
+		std::vector<float> reach((size_t)s.cfg.width * s.cfg.height, 0.0f);
+		if(adypt_multi_read_history_reach(s.multi, reach.data()) != ADYPT_OK) return tracer_failed(s.multi);
+		if(!save_grey(s, o.reach_out, reach, "history reach")) return false;
+	}
+	if(!o.plan_out.empty())
+	{
+		const int w = s.cfg.width, h = s.cfg.height, blocks_x = (w + 31) / 32;
+		std::vector<int32_t> index((size_t)plan.blocks), want(index.size());
+		if(adypt_multi_read_sample_plan(s.multi, index.data(), want.data(), plan.blocks) != plan.blocks) return tracer_failed(s.multi);
+		std::vector<float> want_of((size_t)w * h, 0.0f);
+		for(size_t b = 0; b < index.size(); ++b)
+			for(int y = (index[b] / blocks_x) * 32; y < std::min(h, (index[b] / blocks_x + 1) * 32); ++y)
+				for(int x = (index[b] % blocks_x) * 32; x < std::min(w, (index[b] % blocks_x + 1) * 32); ++x) want_of[(size_t)y * w + x] = (float)want[b];
+		if(!save_grey(s, o.plan_out, want_of, "planned sample counts")) return false;
 	}
 	return true;
 }
@@ -681,7 +717,7 @@ int main(int argc, char **argv)
 	if(!commit_history_poses(s)) return 1;
 	if(follow && !move_scene(s)) return 1;
 	if(!swap_materials(s) || !back_to_the_main_view(s) || !render(s)) return 1;
-	if(!report_and_save_image(s) || !report_noise(s) || !save_denoised(s) || !save_guides(s)) return 1;
+	if(!report_and_save_image(s) || !report_noise(s) || !report_plan(s) || !save_denoised(s) || !save_guides(s)) return 1;
 	release(s);
 	return 0;
 }

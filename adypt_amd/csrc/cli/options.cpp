@@ -78,6 +78,15 @@
 //              (adypt_multi_denoise_temporal_specular): the guides of --denoise-specular K, and a pixel whose chain ended on a surface finds its history
 //              through its virtual point.  Not with --denoise-specular, --follow-motion, --rectify or --denoise-moments (exit 2).  The [PT]TEMPORAL: line
 //              then ends `, followed F pixels, H with history`; --guides-out writes the followed guides and PREFIX.chain.exr
+//   --history-samples T: with a temporal --denoise call only (else exit 2): the main render, after the --history-from poses, is traced by the history
+//              (adypt_multi_trace_by_history): before its first sample every pixel is asked how many samples of history the temporal call WILL find for it,
+//              and every 32x32 block is traced to the smallest of 2, 2 + S, 2 + 2 S, ... (--history-step S, default 4; the last cut to --spp, which is
+//              the cap) that brings all but P permille of its hit pixels (--history-tolerance P, 0 .. 999, default 31) to T samples, history and own
+//              together.  T in 1 .. 1048576.  It follows --follow-motion and --denoise-moments, and takes --history-cap.  Not with --noise, --adaptive,
+//              --save-every, --rectify or --follow-specular, and --spp must be at least 2 (exit 2).  The --history-from poses are rendered at --spp as
+//              without it.  One line: [PT]PLAN: blocks B want W0..W1 pixel_samples N (uniform T*pixels) with_history H of P mean_reach L.
+//              --reach-out reach.exr: the samples of history every pixel will find; --plan-out want.exr: every pixel's block's sample count; both grey
+//              EXRs.  --history-step, --history-tolerance, --reach-out and --plan-out need --history-samples
 //   --guides-out PREFIX: the feature images of the primary hit as PREFIX.albedo.exr, PREFIX.normal.exr and PREFIX.position.exr; with
 //              --denoise-specular the followed guides, and the class code of every pixel as the grey PREFIX.chain.exr
 #include "options.hpp"
@@ -92,7 +101,8 @@ const char *const USAGE =
 	"scene.config [--spp N] [--out file.exr] [--fp16] [--primary TYPE] [--preview file.png] [--sun-visibility] [--seed S] [--device D | --devices D0,D1,...] "
 	"[--save-every K] [--noise T [--min-spp N] [--check-every K] [--noise-out file.exr] [--adaptive [--spp-out file.exr]]] [--denoise file.exr [--denoise-levels L] [--denoise-specular K] "
 	"[--history-from other.config]... [--history-cap C] [--history-out len.exr] [--follow-motion] [--rectify [--rectify-gamma G] [--rectify-radius R] "
-	"[--rectify-out kept.exr]] [--denoise-moments [--variance-out v.exr]] [--follow-specular K]] [--guides-out PREFIX] [--pose moved.obj [--by-vertices [--recompute-normals]] | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] "
+	"[--rectify-out kept.exr]] [--denoise-moments [--variance-out v.exr]] [--follow-specular K] "
+	"[--history-samples T [--history-step S] [--history-tolerance P] [--reach-out reach.exr] [--plan-out want.exr]]] [--guides-out PREFIX] [--pose moved.obj [--by-vertices [--recompute-normals]] | --part-matrices FILE] [--morph-target FILE.obj]... [--morph-weights w0,w1,...] [--rebuild] "
 	"[--rebuild-method linear|ploc [--ploc-radius R] [--split-budget B]] [--rebuild-above R] [--build gpu] [--materials-from other.obj]";
 
 // ---- values ----
@@ -182,6 +192,27 @@ static bool follow_specular(Options &o, const char *v)
 	o.follow_specular = (int)bounces;
 	return true;
 }
+static bool history_samples(Options &o, const char *v)
+{
+	double target;
+	if(!bounded_number(v, INTEGER, 1, 1 << 20, "--history-samples takes a number of samples from 1 to 1048576", &target)) return false;
+	o.history_samples = (int)target;
+	return true;
+}
+static bool history_step(Options &o, const char *v)
+{
+	double step;
+	if(!bounded_number(v, INTEGER, 1, 1 << 20, "--history-step takes a number of samples from 1 to 1048576", &step)) return false;
+	o.history_step = (int)step;
+	return o.history_plan_detail = true;
+}
+static bool history_tolerance(Options &o, const char *v)
+{
+	double permille;
+	if(!bounded_number(v, INTEGER, 0, 999, "--history-tolerance takes a number of permille from 0 to 999", &permille)) return false;
+	o.history_tolerance = (int)permille;
+	return o.history_plan_detail = true;
+}
 static bool rebuild_above(Options &o, const char *v)
 {
 	double ratio;
@@ -237,6 +268,11 @@ static const struct Spec { const char *name; bool value; Apply apply; } SPECS[] 
 	{"--denoise-moments", false, flag<&Options::denoise_moments>},
 	{"--variance-out", true, text<&Options::variance_out>},
 	{"--follow-specular", true, follow_specular},
+	{"--history-samples", true, history_samples},
+	{"--history-step", true, history_step},
+	{"--history-tolerance", true, history_tolerance},
+	{"--reach-out", true, [](Options &o, const char *v) { o.reach_out = v; return o.history_plan_detail = true; }},
+	{"--plan-out", true, [](Options &o, const char *v) { o.plan_out = v; return o.history_plan_detail = true; }},
 	{"--guides-out", true, text<&Options::guides_out>},
 	{"--pose", true, text<&Options::pose>},
 	{"--by-vertices", false, flag<&Options::by_vertices>},
@@ -317,6 +353,11 @@ int check_options(Options *opt)
 	if(o.follow_specular && !(o.denoise && o.temporal)) return refuse("--follow-specular needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out");
 	if(o.follow_specular && (o.denoise_specular || o.follow_motion || o.rectify || o.denoise_moments))
 		return refuse("--follow-specular does not combine with --denoise-specular, --follow-motion, --rectify or --denoise-moments");
+	if(o.history_plan_detail && !o.history_samples) return refuse("--history-step, --history-tolerance, --reach-out and --plan-out need --history-samples T");
+	if(o.history_samples && !(o.denoise && o.temporal)) return refuse("--history-samples needs a temporal --denoise call: --denoise file.exr with --history-from, --history-cap or --history-out");
+	if(o.history_samples && (o.until || o.adaptive || o.save_every > 0)) return refuse("--history-samples plans the samples itself: not together with --noise, --adaptive or --save-every");
+	if(o.history_samples && (o.rectify || o.follow_specular)) return refuse("--history-samples does not combine with --rectify or --follow-specular: the plan does not cover them");
+	if(o.history_samples && o.spp < 2) return refuse("--history-samples needs --spp >= 2: no block stops below 2 samples");
 
 	if(!o.materials_from.empty())
 	{

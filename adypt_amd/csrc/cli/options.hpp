@@ -36,6 +36,10 @@ struct Options
 	std::string rectify_out;
 	bool denoise_moments = false; // --denoise-moments: every temporal call is a moments call, from 1 spp
 	std::string variance_out;
+	std::optional<int> history_samples; // --history-samples T: the main render is traced by the history (adypt_multi_trace_by_history), --spp the cap
+	int history_step = 4, history_tolerance = 31;
+	bool history_plan_detail = false;   // one of --history-step, --history-tolerance, --reach-out, --plan-out was given
+	std::string reach_out, plan_out;
 	std::string pose, part_matrices;
 	bool by_vertices = false, recompute_normals = false; // --pose by the mesh binding; its normals computed on the device
 	std::vector<std::string> morph_targets;

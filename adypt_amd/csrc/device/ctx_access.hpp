@@ -36,7 +36,7 @@ struct Attachment {
 	~Attachment() { reset(); }
 	void reset(void *q = nullptr, void (*f)(void *) = nullptr) { if(p && free_fn) free_fn(p); p = q; free_fn = f; }
 };
-enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachBuild, kAttachGeometry, kAttachPose, kAttachMesh, kAttachAppearance, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes, build.hip's scratch, geometry.hip's staging, pose.hip's rest pose and binding, mesh.hip's index buffer and incidence lists, appearance.hip's staging
+enum AttachKind { kAttachComm = 0, kAttachDenoise, kAttachRefit, kAttachBuild, kAttachGeometry, kAttachPose, kAttachMesh, kAttachAppearance, kAttachHistoryPlan, kAttachKinds }; // multi.hip's communicator, denoise.hip's images, refit.hip's plan and boxes, build.hip's scratch, geometry.hip's staging, pose.hip's rest pose and binding, mesh.hip's index buffer and incidence lists, appearance.hip's staging, history_plan.hip's reach image, bins and last plan
 Attachment &ctx_attachment(adypt_ctx *c, AttachKind kind);
 
 // ---- noise statistics and adaptive sampling, per context (adypt_trace_adaptive and adypt_multi_trace_adaptive are one loop over these) ----
@@ -44,6 +44,11 @@ Attachment &ctx_attachment(adypt_ctx *c, AttachKind kind);
 int noise_ready(adypt_ctx *c, const char *fn, int min_spp);
 // noise_ready(c, fn, 0), and no look-ahead: parked frames belong to a block set that a check may change
 int ctx_adaptive_ready(adypt_ctx *c, const char *fn);
+// ctx_adaptive_ready, and what a plan made before the first sample of a pose needs beside it (history_plan.hip): a camera, the ray queues, a frame
+// counter at 0 and no frozen block; ADYPT_E_STATE with `fn` named otherwise.  Nothing changes.
+int ctx_plan_ready(adypt_ctx *c, const char *fn);
+// the frame counter (adypt_get_spp)
+int ctx_spp(adypt_ctx *c);
 // THE reader of a context's block results (k_noise_blocks behind the frames; adypt_get_noise and adypt_read_block_noise are written on it): APPENDS
 // the owned blocks, ascending, each at its own sample count; nothing for a shard that owns no block.  The caller has asked noise_ready(c, fn, 2).
 int ctx_read_blocks(adypt_ctx *c, std::vector<BlockState> *blocks);

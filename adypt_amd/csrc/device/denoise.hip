@@ -815,23 +815,15 @@ int adypt_get_denoise_timing(adypt_ctx *c, float *ms, int capacity)
 
 namespace {
 
-// a denoise call of a handle: the merge runs on the first device, where the filter runs, and the history lives there
-int multi_denoise(adypt_multi *m, const DenoiseCall &call)
+// The first half of a call over several devices, which multi_denoise and the plan by history (denoise_plan_inputs_multi) share: every device
+// captures the guides of its own blocks — all enqueued before the first is waited for; bounces > 0: every device follows the chains of its own
+// blocks, the class comes along in the primary-hit image — and the host collects the local images of every device back to back in rank order, their
+// block lists and sample counts likewise (the counts from each context's own state in that order: multi.hip's merge is sorted by block index, which
+// is not this order, and would launch k_noise_blocks for nothing).  left_out: the images that neither travel nor are allocated.
+struct HostImages { std::vector<uint8_t> image[kBlockImages]; size_t n_blocks = 0; };
+int collect_guides(adypt_multi *m, const std::vector<adypt_ctx *> &ctx, const char *fn, int bounces, unsigned left_out, HostImages *out)
 {
-	const int n_dev = adypt_multi_device_count(m);
-	if(n_dev < 1) return ADYPT_E_INVALID;
-	adypt_ctx *root = adypt_multi_context(m, 0);
-	if(n_dev == 1) return multi_each(m, [&call](adypt_ctx *c) { return denoise_context(c, call); });
 	auto fail_ctx = [m](adypt_ctx *c, int r) { multi_set_error(m, adypt_last_error(c)); return r; };
-	if(!call.refused.empty()) { multi_set_error(m, call.refused); return ADYPT_E_INVALID; }
-	const char *fn = call.fn;
-	std::vector<adypt_ctx *> ctx;
-	for(int k = 0; k < n_dev; ++k) ctx.push_back(adypt_multi_context(m, k));
-	const int min_spp = call.min_spp();
-	CTX_STEP(multi_each(m, [fn, min_spp](adypt_ctx *c) { return ctx_denoise_ready(c, fn, min_spp); }));
-	// every device captures the guides of its own blocks: all enqueued before the first is waited for
-	const unsigned left_out = optional_images(call);
-	const int bounces = call.bounces; // (followed guides: every device follows the chains of its own blocks; the class comes along in the primary-hit image)
 	CTX_STEP(multi_each(m, [fn, bounces, left_out](adypt_ctx *c) {
 		const CtxInfo i = ctx_info(c);
 		if(i.n_local_px == 0) return (int)ADYPT_OK;
@@ -839,12 +831,9 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 		LocalImages own;
 		return capture_guides(c, denoiser_of(c), ctx_denoise_inputs(c), fn, &own, bounces, left_out);
 	}));
-	// the local images of every device back to back in rank order, and their block lists and sample counts likewise (the counts from each context's
-	// own state in that order: multi.hip's merge is sorted by block index, which is not this order, and would launch k_noise_blocks for nothing)
-	const CtxInfo ri = ctx_info(root);
 	size_t n_blocks = 0;
 	for(adypt_ctx *c : ctx) n_blocks += (size_t)ctx_info(c).n_local_px / kBlockPixels;
-	std::vector<uint8_t> host[kBlockImages];
+	std::vector<uint8_t> *host = out->image;
 	for(int k = 0; k < kBlockImages; ++k)
 		if(!(left_out >> k & 1)) host[k].resize(n_blocks * kBlockImageBytes[k]);
 	size_t at = 0; // the rank's first block in them
@@ -860,9 +849,39 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 			if(r == ADYPT_OK && !(left_out >> k & 1)) r = fetch(c, i, own.image[k], host[k].data() + at * kBlockImageBytes[k], (size_t)in.n_blocks * kBlockImageBytes[k]);
 		if(r != ADYPT_OK) return fail_ctx(c, r);
 		memcpy(host[kBlocks].data() + at * sizeof(int32_t), in.block_index.data(), in.block_index.size() * sizeof(int32_t));
-		memcpy(host[kBlockSpp].data() + at * sizeof(int32_t), in.block_spp.data(), in.block_spp.size() * sizeof(int32_t));
+		if(!(left_out >> kBlockSpp & 1)) memcpy(host[kBlockSpp].data() + at * sizeof(int32_t), in.block_spp.data(), in.block_spp.size() * sizeof(int32_t));
 		at += (size_t)in.n_blocks;
 	}
+	out->n_blocks = n_blocks;
+	return ADYPT_OK;
+}
+// ... uploaded to the set `merged` of the first device, whose device is current: enqueued on `stream`, `host` has to outlive the wait for it
+int upload_guides(adypt_ctx *c, Denoiser *d, hipStream_t stream, const HostImages &host, unsigned left_out)
+{
+	for(int k = 0; k < kBlockImages; ++k)
+		if(!(left_out >> k & 1)) CTX_TRY(c, hipMemcpyAsync(d->merged.image[k], host.image[k].data(), host.image[k].size(), hipMemcpyHostToDevice, stream));
+	return ADYPT_OK;
+}
+
+// a denoise call of a handle: the merge runs on the first device, where the filter runs, and the history lives there
+int multi_denoise(adypt_multi *m, const DenoiseCall &call)
+{
+	const int n_dev = adypt_multi_device_count(m);
+	if(n_dev < 1) return ADYPT_E_INVALID;
+	adypt_ctx *root = adypt_multi_context(m, 0);
+	if(n_dev == 1) return multi_each(m, [&call](adypt_ctx *c) { return denoise_context(c, call); });
+	auto fail_ctx = [m](adypt_ctx *c, int r) { multi_set_error(m, adypt_last_error(c)); return r; };
+	if(!call.refused.empty()) { multi_set_error(m, call.refused); return ADYPT_E_INVALID; }
+	const char *fn = call.fn;
+	std::vector<adypt_ctx *> ctx;
+	for(int k = 0; k < n_dev; ++k) ctx.push_back(adypt_multi_context(m, k));
+	const int min_spp = call.min_spp();
+	CTX_STEP(multi_each(m, [fn, min_spp](adypt_ctx *c) { return ctx_denoise_ready(c, fn, min_spp); }));
+	const unsigned left_out = optional_images(call);
+	HostImages host;
+	CTX_STEP(collect_guides(m, ctx, fn, call.bounces, left_out, &host));
+	const CtxInfo ri = ctx_info(root);
+	const size_t n_blocks = host.n_blocks;
 	// ... uploaded to the first device, where the same prepare / a-trous launches run
 	adypt_ctx *c = root;
 	auto steps = [&]() -> int {
@@ -873,8 +892,7 @@ int multi_denoise(adypt_multi *m, const DenoiseCall &call)
 		LocalImages all{{}, (int)n_blocks};
 		CTX_STEP(d->merged.fill(c, &all, left_out)); // (it borrows none)
 		CTX_TRY(c, d->timer.mark(0, ri.stream));
-		for(int k = 0; k < kBlockImages; ++k)
-			if(!(left_out >> k & 1)) CTX_TRY(c, hipMemcpyAsync(d->merged.image[k], host[k].data(), host[k].size(), hipMemcpyHostToDevice, ri.stream));
+		CTX_STEP(upload_guides(c, d, ri.stream, host, left_out));
 		CTX_TRY(c, d->timer.mark(1, ri.stream));
 		return run_filter(c, d, ri.stream, all, call, ctx_camera(c)); // (adypt_multi_set_camera gives every context the same camera)
 	};
@@ -1020,3 +1038,65 @@ int adypt_multi_get_denoise_specular(adypt_multi *m, adypt_denoise_specular_info
 }
 
 }  // extern "C"
+
+// ---- what history_plan.hip needs (denoise_internal.hpp) ----
+namespace {
+
+// the images a plan goes without: it is made at 0 spp, of the guides alone
+constexpr unsigned kPlanLeftOut = kWithoutVirtual | 1u << kAccum | 1u << kMoments | 1u << kBlockSpp;
+
+// the guides of the set `v` and the history a call of the kind {moments, 0} finds in d
+void plan_inputs_of(adypt_ctx *c, const Denoiser *d, const LocalImages &v, bool moments, PlanInputs *out)
+{
+	const History &h = d->history;
+	out->albedo = v.as<kAlbedo>(); out->normal = v.as<kNormal>(); out->position = v.as<kPosition>(); out->hits = v.as<kHits>();
+	out->blocks = v.as<kBlocks>(); out->n_blocks = v.n_blocks;
+	out->have = h.present && h.kind == HistoryKind{moments, 0} ? 1 : 0;
+	out->h0 = h.h0; out->h1 = h.h1; out->h2 = h.h2; out->ha = h.ha;
+	out->camera = h.camera;
+	out->snapshot = h.snapshot;
+	out->known_tris = h.known_tris(ctx_scene(c).n_tris);
+}
+
+}  // namespace
+
+namespace adypt {
+
+int denoise_plan_inputs(adypt_ctx *c, const char *fn, bool moments, PlanInputs *out)
+{
+	Denoiser *d = denoiser_of(c);
+	const DenoiseInputs in = ctx_denoise_inputs(c);
+	LocalImages local;
+	CTX_STEP(capture_guides(c, d, in, fn, &local));
+	plan_inputs_of(c, d, local, moments, out);
+	out->block_index = in.block_index;
+	return ADYPT_OK;
+}
+
+int denoise_plan_inputs_multi(adypt_multi *m, const char *fn, bool moments, PlanInputs *out)
+{
+	const int n_dev = adypt_multi_device_count(m);
+	std::vector<adypt_ctx *> ctx;
+	for(int k = 0; k < n_dev; ++k) ctx.push_back(adypt_multi_context(m, k));
+	HostImages host;
+	CTX_STEP(collect_guides(m, ctx, fn, 0, kPlanLeftOut, &host));
+	adypt_ctx *c = ctx[0];
+	const CtxInfo ri = ctx_info(c);
+	auto steps = [&]() -> int {
+		CTX_TRY(c, hipSetDevice(ri.device));
+		Denoiser *d = denoiser_of(c);
+		LocalImages all{{}, (int)host.n_blocks};
+		CTX_STEP(d->merged.fill(c, &all, kPlanLeftOut));
+		CTX_STEP(upload_guides(c, d, ri.stream, host, kPlanLeftOut));
+		CTX_TRY(c, hipStreamSynchronize(ri.stream)); // (the host's copies end with this call)
+		plan_inputs_of(c, d, all, moments, out);
+		out->block_index.resize(host.n_blocks);
+		memcpy(out->block_index.data(), host.image[kBlocks].data(), host.n_blocks * sizeof(int32_t));
+		return ADYPT_OK;
+	};
+	const int r = steps();
+	if(r != ADYPT_OK) multi_set_error(m, adypt_last_error(c));
+	return r;
+}
+
+}  // namespace adypt

@@ -696,6 +696,16 @@ int ctx_adaptive_ready(adypt_ctx *c, const char *fn)
 	return ADYPT_OK;
 }
 int ctx_freeze_blocks(adypt_ctx *c, const int32_t *blocks, size_t n, int spp) { return freeze_blocks(c, blocks, n, spp); }
+int ctx_plan_ready(adypt_ctx *c, const char *fn)
+{
+	TRY_CREATE(ctx_adaptive_ready(c, fn));
+	if(!c->have_camera) return fail(c, ADYPT_E_STATE, std::string(fn) + ": call adypt_set_camera first");
+	if(!c->queues_ok) return fail(c, ADYPT_E_STATE, std::string(fn) + ": the context lost its ray queues (failed adypt_set_frames_in_flight)");
+	if(c->ab.any_frozen()) return fail(c, ADYPT_E_STATE, std::string(fn) + ": blocks are frozen (adypt_reset first)");
+	if(c->spp != 0) return fail(c, ADYPT_E_STATE, std::string(fn) + ": the plan is made before the first sample of a pose (adypt_reset first: adypt_get_spp is " + std::to_string(c->spp) + ")");
+	return ADYPT_OK;
+}
+int ctx_spp(adypt_ctx *c) { return c->spp; }
 
 // ---- what the denoiser (denoise.hip) needs of a context ----
 int ctx_denoise_ready(adypt_ctx *c, const char *fn, int min_spp)

@@ -265,6 +265,51 @@ int adypt_trace_adaptive(adypt_ctx *ctx, double target, int min_spp, int max_spp
  * of owned blocks and writes the arrays only when capacity holds them all, like adypt_read_block_noise; works with the statistics off. */
 int64_t adypt_read_block_spp(adypt_ctx *ctx, int32_t *block_index, int32_t *spp, int64_t capacity);
 
+/* ---- history-aware sampling: every block is traced only as far as its history falls short ------------------------------------------
+ * Before the first sample of a pose: the primary-hit guides are captured at 0 spp, every pixel is asked how many samples of history the temporal
+ * merge (adypt_denoise_temporal, below) WILL find for it — the merge's acceptance rule is a function of the guides, the history and its camera
+ * alone — and every 32x32 block gets a sample count of its own: the smallest of min_spp, min_spp + step, ... (the last cut to max_spp) that
+ * leaves at most tolerance_permille / 1000 of the block's hit pixels with floor(reach) + count < target; max_spp where none does, min_spp for a
+ * block without a hit pixel.  The definition is pinned in csrc/device/history_reach.hpp (tests/history_reach_truth.py restates it in numpy): the
+ * reach of a pixel is, bit for bit, what adypt_denoise_temporal[_motion / _moments] adds to the block's sample count in adypt_read_denoise_history.
+ * follow_motion: the motion form (through where the hit point was at the last committing motion call).  moments: the history looked for is a
+ * moments call's; a history of another kind — a followed one included — counts as none, as does no denoiser or no history yet: every block of a
+ * first pose gets the first candidate >= target.  Not covered: adypt_denoise_temporal_rectified shortens the length by a share that depends on the
+ * samples not yet traced (the plan may overestimate the history there), and adypt_denoise_temporal_specular has a rule of its own.
+ * adypt_plan_by_history traces nothing and freezes nothing; adypt_trace_by_history is the plan followed by the tracing: the distinct counts in
+ * ascending order, for each `count - spp` frames (adypt_trace_spp) and then the blocks of that count frozen at it (see adaptive sampling above: a
+ * frozen block holds the uniform image's bits at its count); the blocks of the largest count stay active.  Neither touches the history, its kind, its
+ * camera or its snapshot, nor any bit of a later adypt_denoise*; no read-out of an earlier denoise call is invalidated.
+ * ADYPT_E_STATE, nothing changed: the statistics are off, look-ahead is on, the context is a tile shard (adypt_multi_plan_by_history), no camera is
+ * set, adypt_get_spp is not 0, blocks are frozen.  ADYPT_E_INVALID, nothing changed: not 1 <= target <= 1 << 20, 2 <= min_spp <= max_spp, step >= 1,
+ * 0 <= tolerance_permille <= 999 and history_cap a positive finite number.  params NULL: target 16, 2, 64, 4, 31, 64.0, 0, 0.
+ * Memory: 4 B per local pixel + 260 B per owned block (the 65 bins), allocated at the first plan. */
+typedef struct adypt_history_plan_params {
+	int32_t target, min_spp, max_spp, step, tolerance_permille;
+	float history_cap;
+	int32_t follow_motion, moments;
+} adypt_history_plan_params;
+typedef struct adypt_history_plan {
+	int32_t blocks, want_min, want_max; /* blocks of the image and the least and the largest planned count */
+	int32_t spp;                        /* the frame counter when the call returned: 0 after a plan, want_max after adypt_trace_by_history */
+	int64_t pixels;                     /* pixels inside the image */
+	int64_t pixels_with_history;        /* hit pixels that will find at least one whole sample of history */
+	int64_t pixel_samples;              /* sum over blocks of (pixels inside the image) x (the block's planned count) */
+	double mean_reach;                  /* sum of floor(min(reach, 64)) over the hit pixels / pixels */
+	float capture_ms, reach_ms;         /* the guide capture (several devices: and the upload) and the reach kernel */
+	int64_t device_bytes;               /* of the reach image and the bins */
+} adypt_history_plan;
+int adypt_plan_by_history(adypt_ctx *ctx, const adypt_history_plan_params *params, adypt_history_plan *info);
+int adypt_trace_by_history(adypt_ctx *ctx, const adypt_history_plan_params *params, adypt_history_plan *info);
+/* the reach of every pixel of the last plan, W x H floats (0: a miss, or no history); ADYPT_E_STATE before the first plan */
+int adypt_read_history_reach(adypt_ctx *ctx, float *reach);
+/* the last plan, ascending block index: returns the number of blocks and writes the arrays only when capacity holds them all (NULL arrays or
+ * capacity 0: the size alone), like adypt_read_block_spp; ADYPT_E_STATE before the first plan */
+int64_t adypt_read_sample_plan(adypt_ctx *ctx, int32_t *block_index, int32_t *want, int64_t capacity);
+/* the 65 bins of every block of the last plan, ascending block index, capacity counted in blocks: bins[65 * i + k] = the hit pixels of block i inside
+ * the image with floor(reach) == k (k == 64: reach >= 64) */
+int64_t adypt_read_history_bins(adypt_ctx *ctx, int32_t *block_index, uint32_t *bins, int64_t capacity);
+
 /* ---- denoising: a usable image at 16-32 spp from the statistics the library already keeps --------------------------------------
  * An edge-avoiding a-trous wavelet filter (the spatial half of SVGF) over the albedo-demodulated radiance, guided by the primary hit's normal,
  * position and hit flag; the luminance edge-stopping is scaled by the variance of the pixel's mean, m2 / (n (n - 1)) from the noise moments with n
@@ -909,6 +954,14 @@ int adypt_multi_get_denoise_specular(adypt_multi *m, adypt_denoise_specular_info
 int adypt_multi_denoise_temporal_specular(adypt_multi *m, const adypt_denoise_params *params, const adypt_temporal_params *temporal, const adypt_specular_params *specular);
 int adypt_multi_read_denoise_virtual(adypt_multi *m, float *virtual_position, float *distance);
 int adypt_multi_get_denoise_virtual(adypt_multi *m, adypt_denoise_virtual *out);
+/* adypt_plan_by_history ... for the whole image: every device captures the guides of its own blocks, they travel to the first device as for
+ * adypt_multi_denoise, the reach kernel runs there over all blocks (the history lives there), the plan is made on the host, and every device freezes
+ * its own blocks; the same plan and the same image as one device.  The read-outs answer from the first device.  (One process per GPU is not covered.) */
+int adypt_multi_plan_by_history(adypt_multi *m, const adypt_history_plan_params *params, adypt_history_plan *info);
+int adypt_multi_trace_by_history(adypt_multi *m, const adypt_history_plan_params *params, adypt_history_plan *info);
+int adypt_multi_read_history_reach(adypt_multi *m, float *reach);
+int64_t adypt_multi_read_sample_plan(adypt_multi *m, int32_t *block_index, int32_t *want, int64_t capacity);
+int64_t adypt_multi_read_history_bins(adypt_multi *m, int32_t *block_index, uint32_t *bins, int64_t capacity);
 /* adypt_update_triangles on every device: the scene is replicated and every device refits its own copy; no collective.  (One process per GPU: every
  * rank calls adypt_update_triangles on its own context.) */
 int adypt_multi_update_triangles(adypt_multi *m, int64_t first, int64_t count, const float *positions, const float *normals);

@@ -105,6 +105,20 @@ private:
 		return adypt_multi_set_params(m_gpus, &p) == ADYPT_OK;
 	}
 
+	// PlanByHistory and TraceByHistory
+	bool by_history(bool trace, int target, adypt_history_plan *out, std::vector<float> *reach, int minSpp, int maxSpp, int step, int tolerancePermille, float historyCap, bool followMotion,
+	                bool moments)
+	{
+		const adypt_history_plan_params p = {target, minSpp, maxSpp, step, tolerancePermille, historyCap, followMotion ? 1 : 0, moments ? 1 : 0};
+		if(trace && adypt_multi_get_spp(m_gpus) == 0) update_config_args(); // (a plan alone leaves everything to the call that traces)
+		if(trace) m_viewer_type = kPTRadiance;
+		if(reach) reach->resize((size_t)m_width * m_height);
+		if((trace ? adypt_multi_trace_by_history(m_gpus, &p, out) : adypt_multi_plan_by_history(m_gpus, &p, out)) == ADYPT_OK &&
+		   (!reach || adypt_multi_read_history_reach(m_gpus, reach->data()) == ADYPT_OK)) return true;
+		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
+		return false;
+	}
+
 public:
 	HipPathTracer() = default;
 	HipPathTracer(const HipPathTracer &) = delete;
@@ -211,6 +225,23 @@ public:
 		if(adypt_multi_trace_adaptive(m_gpus, target, min_spp, max_spp, check_every, out) == ADYPT_OK) return true;
 		printf("[PT]ERR: %s\n", adypt_multi_last_error(m_gpus));
 		return false;
+	}
+
+	// History-aware sampling (adypt_hip.h, adypt_plan_by_history): before the first sample of a pose — a camera set, the counter at 0, the noise statistics
+	// on — every 32x32 block gets the smallest sample count of minSpp, minSpp + step, ..., maxSpp that brings all but tolerancePermille / 1000 of its hit
+	// pixels to `target` samples, the history DenoiseTemporal (followMotion: DenoiseTemporalMotion; moments: DenoiseTemporalMoments) will find for them and
+	// their own together.  PlanByHistory only plans: nothing is traced or frozen, and no later call sees a difference.  TraceByHistory also traces: every
+	// block holds the pixels of the uniform image at its own count afterwards.  reach (may be null): W x H floats, the samples of history every pixel
+	// will find.  Not covered: DenoiseTemporalRectified (the plan may overestimate its history) and DenoiseTemporalSpecular.
+	bool PlanByHistory(int target, adypt_history_plan *out = nullptr, std::vector<float> *reach = nullptr, int minSpp = 2, int maxSpp = 64, int step = 4, int tolerancePermille = 31,
+	                   float historyCap = 64.0f, bool followMotion = false, bool moments = false)
+	{
+		return by_history(false, target, out, reach, minSpp, maxSpp, step, tolerancePermille, historyCap, followMotion, moments);
+	}
+	bool TraceByHistory(int target, adypt_history_plan *out = nullptr, std::vector<float> *reach = nullptr, int minSpp = 2, int maxSpp = 64, int step = 4, int tolerancePermille = 31,
+	                    float historyCap = 64.0f, bool followMotion = false, bool moments = false)
+	{
+		return by_history(true, target, out, reach, minSpp, maxSpp, step, tolerancePermille, historyCap, followMotion, moments);
 	}
 
 	// Moving geometry (adypt_hip.h, adypt_update_triangles): new positions (count x 9 floats, p0 p1 p2 per triangle) and, unless null, normals (count x 9)
